@@ -3,9 +3,10 @@
 en_UK/apope_low VITS graph, hot path only (``onnx_model.run`` + ``audio_float_to_int16``, the reference's
 own timed region, mimic3_tts/voice.py:229-232).
 
-    python bench.py --gpus N --steps K --warmup W    # N > 1 without a launcher: re-executes itself under torch.distributed.run
+    python bench.py --gpus N --steps K --warmup W    # N > 1 without a launcher: runs itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (what the driver launches for N > 1)
     python bench.py --gpus N --single-process        # one process, N devices (the unchanged mimic3-server's shape)
+    python bench.py ... --dump-outputs DIR           # also write what the last timed step returned as DIR/*.npy (dump_outputs)
 
 A "step" is one pass of the hot path over the job's batch of synthetic phoneme ids.  Workload: BASELINE.json's
 batch of 256 independent utterances of 128 phoneme ids, durations forced to 6 frames/id -> 768 latent frames =
@@ -194,6 +195,57 @@ def make_batch(B, Tx, base):
     return ids, np.full(B, Tx, np.int64)
 
 
+DUMP_SAMPLE_BYTES = 32 << 20  # waveform bytes of a whole --dump-outputs (all ranks together): the dump stays well under 64 MB
+
+
+def merge_calls(outs):
+    """The results of the calls that make up one step (--single-process: one batch per device) as one result: rows
+    concatenated in call order, waveforms zero-padded to the widest call (the engine writes zeros past a row's length),
+    scalars (l_max, ty_max) their maximum."""
+    if len(outs) == 1:
+        return outs[0]
+    merged = {}
+    for name in outs[0]:
+        vs = [np.asarray(o[name]) for o in outs]
+        if vs[0].ndim == 0:
+            merged[name] = max(vs)
+        elif vs[0].ndim == 2:
+            width = max(v.shape[1] for v in vs)
+            merged[name] = np.concatenate([np.pad(v, ((0, 0), (0, width - v.shape[1]))) for v in vs])
+        else:
+            merged[name] = np.concatenate(vs)
+    return merged
+
+
+def dump_outputs(out, directory, prefix="", budget=DUMP_SAMPLE_BYTES):
+    """``--dump-outputs``: what one step returned to its caller, as ``<prefix><name>.npy`` in float32 (int16 / float32 values,
+    exact) or float64 (everything else).  A waveform whose float32 copy exceeds `budget` bytes (the int16 PCM of the batch of
+    256 is 201 MB; with several ranks each gets DUMP_SAMPLE_BYTES / ranks) is written as the columns of a fixed seeded sample
+    (``<name>_columns.npy`` names them), with every row's sum and sum of squares over all its samples beside it
+    (``<name>_row_sum.npy``, ``<name>_row_sumsq.npy``: float64, exact for int16), so that no sample goes unchecked."""
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, a):
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype in (np.int16, np.float32) else np.float64)
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+    for name, v in out.items():
+        v = np.asarray(v)
+        if v.ndim == 2 and v.size * 4 > budget:
+            k = max(1, budget // (4 * v.shape[0]))
+            cols = np.sort(np.random.default_rng(0).choice(v.shape[1], size=k, replace=False))
+            save(name + "_columns", cols)
+            sums = np.zeros((v.shape[0], 2))
+            for b, row in enumerate(v):
+                r = row.astype(np.float64)
+                sums[b] = r.sum(), np.dot(r, r)
+            save(name + "_row_sum", sums[:, 0])
+            save(name + "_row_sumsq", sums[:, 1])
+            v = v[:, cols]
+        save(name, v)
+
+
 class Workload:
     """One voice on one or more devices: ``streams`` engine handles per device, steps dealt to them in turn."""
 
@@ -223,19 +275,22 @@ class Workload:
                      utterance_base=self.rank * self.B + i * self.world * self.B, want_float=False, want_pcm16=True,
                      device_only=device_only)
 
-    def run_steps(self, n, device_only=False):
+    def run_steps(self, n, device_only=False, keep=1):
         """n steps; with S > 1 handles, S host threads each drive one engine handle (own HIP stream and workspace)
         and take step numbers from a shared counter, so the small-kernel front half of one batch overlaps the
         matrix-core back half of another.  Every step is a complete, independent run() whose int16 result is in
-        host memory when it returns (unless device_only)."""
+        host memory when it returns (unless device_only).  Returns the results of the last `keep` steps (numbers
+        n - keep .. n - 1) in step order, whichever handle ran them."""
         engines = self.engines
+        first = max(0, n - keep)
+        kept = {}
         if len(engines) == 1:
-            last = None
             for i in range(n):
-                last = self.step(i, device_only=device_only)
-            return last
+                out = self.step(i, device_only=device_only)
+                if i >= first:
+                    kept[i] = out
+            return [kept[i] for i in sorted(kept)]
         counter = itertools.count()
-        outs = [None] * len(engines)
         errs = []
 
         def work(k):
@@ -244,7 +299,9 @@ class Workload:
                     i = next(counter)
                     if i >= n:
                         return
-                    outs[k] = self.step(i, engines[k], device_only)
+                    out = self.step(i, engines[k], device_only)
+                    if i >= first:
+                        kept[i] = out
             except Exception as ex:  # noqa: BLE001 - re-raised below
                 errs.append(ex)
 
@@ -253,7 +310,7 @@ class Workload:
         [t.join() for t in ts]
         if errs:
             raise errs[0]
-        return next((o for o in outs if o is not None), None)
+        return [kept[i] for i in sorted(kept)]
 
     def size_workspaces(self):
         for e in self.engines:  # every handle sizes its workspace on first use: never inside the timed region
@@ -331,6 +388,15 @@ def roofline_of(rep, table, tot_ms, nsteps, workload_key, voice, math="f32", tra
     }
 
 
+def write_table(directory, name, table):
+    """``--kernel-tables DIR``: a per-kernel table as DIR/<name>.json.  Without the option nothing is written: the benchmark
+    never writes into the source tree, which may be read-only."""
+    if directory:
+        os.makedirs(directory, exist_ok=True)
+        with open(os.path.join(directory, name + ".json"), "w") as f:
+            json.dump(table, f, indent=1)
+
+
 def print_table(title, table):
     print(title, file=sys.stderr)
     for row in table:
@@ -338,12 +404,22 @@ def print_table(title, table):
               f"{100 * row['share']:5.1f}%  {row['tflops']:7.2f} TFLOP/s  {row['gbs_algorithmic']:8.1f} GB/s", file=sys.stderr)
 
 
+def visible_device_count():
+    """HIP devices visible, counted by a short-lived child process: the caller never initialises the runtime itself."""
+    import subprocess
+
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300)
+    lines = r.stdout.split()
+    return int(lines[-1]) if r.returncode == 0 and lines and lines[-1].isdigit() else 0
+
+
 def plan_launch(gpus, single_process, env, visible_devices):
     """How `bench.py --gpus N` starts (no torch, no device: tests/test_session_and_sharding.py drives it with stubbed counts).
 
     ("run",)                  this process is one rank of a WORLD_SIZE == N job (or N == 1): go on
     ("single",)               --single-process: one process, one host thread per device (the mimic3-server shape)
-    ("reexec", make_cmd)      WORLD_SIZE unset and N > 1: `python bench.py --gpus N` re-executes itself as
+    ("reexec", make_cmd)      WORLD_SIZE unset and N > 1: `python bench.py --gpus N` starts itself as a child process
                               `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`
                               (one rank per GPU over RCCL, exactly what the driver launches for N > 1)
     ("error", message)        N devices requested, fewer visible / WORLD_SIZE disagrees with --gpus
@@ -412,6 +488,11 @@ def main():
     ap.add_argument("--no-preheat", action="store_true",
                     help="skip the untimed pre-heat steps in front of the warm-up (rounds 1-3 and the driver's BENCH_r01-r03 were "
                          "measured without them; the JSON says which protocol ran: device.preheat)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all): the outputs of two builds can then be compared")
+    ap.add_argument("--kernel-tables", metavar="DIR", default=None,
+                    help="write the per-kernel HIP-event tables as DIR/bench_kernels*.json (they are printed to stderr either way)")
     args = ap.parse_args()
 
     import torch
@@ -419,15 +500,21 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    # a plain `python bench.py --gpus N` (N > 1, no launcher) only starts the ranks: it counts the devices in a child process
+    # that has exited before they start, so that it never holds a device open itself
+    launcher_only = args.gpus > 1 and not args.single_process and "WORLD_SIZE" not in os.environ
     plan = plan_launch(args.gpus, args.single_process, os.environ,
+                       visible_device_count() if launcher_only else
                        torch.cuda.device_count() if torch.cuda.is_available() else 0)
     if plan[0] == "error":
         raise SystemExit(plan[1])
-    if plan[0] == "reexec":  # plain `python bench.py --gpus N`: become the N-rank job the contract describes
+    if plan[0] == "reexec":  # plain `python bench.py --gpus N`: start the N-rank job the contract describes and wait for it
+        import subprocess
+
         cmd = plan[1](sys.executable, os.path.abspath(__file__), sys.argv[1:])
         print("bench.py: WORLD_SIZE unset, --gpus %d -> %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(cmd[0], cmd)
+        raise SystemExit(subprocess.call(cmd))  # a child process, never exec
     single = plan[0] == "single"
     torch.cuda.set_device(local_rank)
     dist = None
@@ -470,11 +557,12 @@ def main():
         else:
             torch.cuda.synchronize()
 
-    def timed(w, steps, warmup, device_only=False):
+    def timed(w, steps, warmup, device_only=False, keep=1):
+        """-> (seconds, the results of the last `keep` steps in step order)"""
         w.run_steps(warmup, device_only)
         barrier()
         t0 = time.perf_counter()
-        out = w.run_steps(steps, device_only)
+        out = w.run_steps(steps, device_only, keep)
         barrier()
         el = time.perf_counter() - t0
         per_rank[:] = [el]
@@ -541,9 +629,15 @@ def main():
     preheat["sclk_mhz_first_last"] = [hist[0][1], hist[-1][1]] if hist else None
     barrier()
     mon.start()  # (sampling starts with the warm-up steps; it reads two sysfs files every 10 ms)
-    elapsed, out = timed(wl, calls, args.warmup * (n_gpus if single else 1))
+    # (single-process: the last job step is the last n_gpus calls, one batch per device)
+    elapsed, last_step = timed(wl, calls, args.warmup * (n_gpus if single else 1), keep=n_gpus if single else 1)
+    out = last_step[-1]
     headline_per_rank_ms = [e / args.steps * 1e3 for e in per_rank]
     dev_window = mon.stop()
+    if args.dump_outputs:  # every rank writes its own shard of the last step, within its share of the budget
+        dump_outputs(merge_calls(last_step), args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                     budget=DUMP_SAMPLE_BYTES // world)
+    del last_step
     samples_per_call = int(out["lengths"].sum())
     samples_per_step = samples_per_call * n_gpus
     value = samples_per_step * args.steps / elapsed
@@ -649,9 +743,7 @@ def main():
         dev_ms = eng.last_run_ms()
         if not args.no_roofline:
             rep1, rows1, tot1 = kernel_table(eng, lambda i: b1(), 3)
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_kernels_b1.json"), "w") as f:
-                json.dump(rows1, f, indent=1)
+            write_table(args.kernel_tables, "bench_kernels_b1", rows1)
             print("batch-1 golden shape, per-kernel (HIP events): total %.3f ms over %d launches" %
                   (tot1 / 3, sum(r["launches_per_step"] for r in rows1)), file=sys.stderr)
             for r in rows1[:10]:
@@ -694,9 +786,7 @@ def main():
             result["roofline"]["sclk_mhz_during_table"] = table_window["sclk_mhz"]["median"]
             result["roofline"]["power_w_during_table"] = table_window["power_w"]["mean"]
         result["device"]["kernel_table_window"] = table_window
-        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-        with open(os.path.join(ROOT, "gpurun_out", "bench_kernels.json"), "w") as f:
-            json.dump(table, f, indent=1)
+        write_table(args.kernel_tables, "bench_kernels", table)
         print_table("per-kernel (HIP events):", table)
 
     if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
@@ -713,7 +803,7 @@ def main():
                       multispeaker_sid=True, math=args.math)
         vw.size_workspaces()
         vsteps = max(60, args.steps // 3)  # >= 60 steps after 10 warm-up: a 20-step leg measures clock ramp and first-touch costs
-        el_v, out_v = timed(vw, vsteps, 10)
+        el_v, [out_v] = timed(vw, vsteps, 10)
         sps = int(out_v["lengths"].sum())
         extra = {
             "workload": f"en_US/vctk_low (109 speakers, gin 512), 32 utterances x 128 phoneme ids, sid = b mod 109, forced "
@@ -724,8 +814,7 @@ def main():
         if not args.no_roofline:
             repv, tablev, totv = kernel_table(vw.engines[0], lambda i: vw.step(i, device_only=True), 3)
             extra["roofline"] = roofline_of(repv, tablev, totv, 3, [32, 128, fpi], "vctk_low", math)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_kernels_vctk.json"), "w") as f:
-                json.dump(tablev, f, indent=1)
+            write_table(args.kernel_tables, "bench_kernels_vctk", tablev)
             print_table("vctk_low b32, per-kernel (HIP events):", tablev[:12])
         result["extra"] = {"vctk_low_b32": extra}
         vw.close()
@@ -736,7 +825,7 @@ def main():
                       multispeaker_sid=cfg.is_multispeaker, math=args.math)
         ow.size_workspaces()
         osteps = max(60, args.steps) if ob == 32 else max(8, args.steps // 16)
-        el_g, out_g = timed(ow, osteps, 10 if ob == 32 else 2)
+        el_g, [out_g] = timed(ow, osteps, 10 if ob == 32 else 2)
         spb = int(out_g["lengths"].sum())
         oleg = {"workload": f"en_UK/apope_low, {ob} utterances x {Tx} phoneme ids on ONE GPU, forced {fpi} frames/id; host-to-host",
                 "value": spb * osteps / el_g, "unit": "samples/s", "steps": osteps, "ms_per_step": el_g / osteps * 1e3,
@@ -782,15 +871,14 @@ def main():
                           math="f32")
             fw.size_workspaces()
             fsteps = max(60, args.steps // 4)
-            el_f, out_f = timed(fw, fsteps, 10)
+            el_f, [out_f] = timed(fw, fsteps, 10)
             f32_leg = {"math": "f32", "value": int(out_f["lengths"].sum()) * fsteps / el_f, "unit": "samples/s", "steps": fsteps,
                        "ms_per_step": el_f / fsteps * 1e3,
                        "note": "same workload, every dense conv on v_mfma_f32_32x32x2_f32 (MI355VITS_MATH=f32)"}
             if not args.no_roofline:
                 repf, tablef, totf = kernel_table(fw.engines[0], lambda i: fw.step(i, device_only=True), 3)
                 f32_leg["roofline"] = roofline_of(repf, tablef, totf, 3, [B, Tx, fpi], args.voice, "f32")
-                with open(os.path.join(ROOT, "gpurun_out", "bench_kernels_f32.json"), "w") as f:
-                    json.dump(tablef, f, indent=1)
+                write_table(args.kernel_tables, "bench_kernels_f32", tablef)
             result["extra"]["f32_mfma"] = f32_leg
             fw.close()
             # ---- BASELINE.json configs[4], first slice: bf16 weights (reduced precision: its own tolerance, rel RMS <= 2e-2,
@@ -798,7 +886,7 @@ def main():
             bw = Workload(cfg, weights, devices, args.streams, B, Tx, fpi, rank, world, multispeaker_sid=cfg.is_multispeaker,
                           math="bf16w")
             bw.size_workspaces()
-            el_b, out_b = timed(bw, fsteps, 10)
+            el_b, [out_b] = timed(bw, fsteps, 10)
             bw_leg = {"math": "bf16w", "dtype": "bf16-weights (bf16 x exact-f32 activations, f32 accumulate)",
                       "value": int(out_b["lengths"].sum()) * fsteps / el_b, "unit": "samples/s", "steps": fsteps,
                       "ms_per_step": el_b / fsteps * 1e3,
@@ -817,7 +905,7 @@ def main():
             hw = Workload(cfg, weights, devices, args.streams, B, Tx, fpi, rank, world, multispeaker_sid=cfg.is_multispeaker,
                           math="f16x2")
             hw.size_workspaces()
-            el_h, out_h = timed(hw, fsteps, 10)
+            el_h, [out_h] = timed(hw, fsteps, 10)
             h2_leg = {"math": "f16x2", "dtype": "f32 in / out / accumulate; dense-conv operands as 2 x fp16 (22 bits), 3 MFMA products",
                       "value": int(out_h["lengths"].sum()) * fsteps / el_h, "unit": "samples/s", "steps": fsteps,
                       "ms_per_step": el_h / fsteps * 1e3,
