@@ -1370,13 +1370,15 @@ __device__ __forceinline__ void epi_std_tile_buf(const ConvArgs& a, int b, int c
 // k_enc_b3 for LARGE grids (round 6; batch 256: 32,768 phoneme columns, and the flow's pointwise convs at frame resolution).  The
 // 64 x 64 form above streams every weight fragment through the L1 for ONE 32-column tile (and twice: its two column-tile waves load
 // the same rows): 8 waves x 3 KiB per 192 MFMA cycles = 128 B per clock against the L1's 64 — the matrix pipe cannot pass 0.5
-// (measured 0.31 - 0.35 busy).  Here a workgroup owns 32 NCT columns (128) x NW 32-row tiles: the slice of those columns is staged
-// once (150 KiB at 192 channels), wave w streams row tile w's fragments — nobody else's — and every fragment feeds NCT column tiles
-// (24 MFMAs = 768 cycles per 3 KiB: 32 B per clock and CU with eight waves); a.rb_loop row blocks of NW tiles one after the other.
+// (measured 0.31 - 0.35 busy).  Here a workgroup of NW = 8 waves owns 32 NCT columns (128) x 8 32-row tiles: the slice of those columns
+// is staged once (150 KiB at 192 channels), wave w streams row tile w's fragments — nobody else's — and every fragment feeds NCT column
+// tiles (24 MFMAs = 768 cycles per 3 KiB: 32 B per clock and CU with eight waves); a.rb_loop row blocks of 8 tiles (SIX: 6) one after
+// the other.
 // b3_chunk walks k-groups and taps in the same order for every accumulator: an output element has the bits of the 64 x 64 form.
-template <bool W1, int NG, int NCT, int NW, bool SIX = false>
-__global__ __launch_bounds__(64 * NW) void k_enc_b3w(ConvArgs a) {
-    static_assert(!SIX || (NW == 8 && NCT == 4), "six row tiles x four column tiles dealt to eight waves");
+template <bool W1, int NG, int NCT, bool SIX = false>
+__global__ __launch_bounds__(512) void k_enc_b3w(ConvArgs a) {
+    constexpr int NW = 8;
+    static_assert(!SIX || NCT == 4, "six row tiles x four column tiles dealt to eight waves");
     DYN_SMEM(float, smem);
     uint4* planes = reinterpret_cast<uint4*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wid = WAVE_UNIFORM(tid >> 6);
@@ -1602,24 +1604,20 @@ void launch_enc_conv_b3(const ConvArgs& a_in, hipStream_t s) {
             const int LDw = 32 * NCT + (a.K - 1) * a.dil;
             const size_t shw = (size_t)3 * ng * 2 * LDw * 16;
             dim3 gridw((a.T + 32 * NCT - 1) / (32 * NCT), 1, a.B * a.ksplit);
-            auto gow = [&](auto kfn, int threads) {
+            auto gow = [&](auto kfn) {
 #ifndef MI355_EMU
                 set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
 #endif
-                LAUNCH_KERNEL(kfn, gridw, dim3(threads), shw, s, a);
+                LAUNCH_KERNEL(kfn, gridw, dim3(512), shw, s, a);
             };
             const bool w1 = a.math == MATH_BF16W;
-            // row blocks of six tiles: dealt to eight waves (SIX) unless the lab switch asks for the round-6a form (one row tile per wave, six waves)
-            bool six8 = nw == 6;
-            if (const char* f = lab_getenv("MI355VITS_ENC_SIX8")) six8 = six8 && atoi(f) != 0;
+            // row blocks of six tiles (nw == 6): dealt to the eight waves (SIX)
             if (ng == ENC_NG) {
-                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, 8>, 512); else gow(k_enc_b3w<false, ENC_NG, NCT, 8>, 512); }
-                else if (six8) { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, 8, true>, 512); else gow(k_enc_b3w<false, ENC_NG, NCT, 8, true>, 512); }
-                else { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, 6>, 384); else gow(k_enc_b3w<false, ENC_NG, NCT, 6>, 384); }
+                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT>); else gow(k_enc_b3w<false, ENC_NG, NCT>); }
+                else { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, true>); else gow(k_enc_b3w<false, ENC_NG, NCT, true>); }
             } else {
-                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, 8>, 512); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, 8>, 512); }
-                else if (six8) { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, 8, true>, 512); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, 8, true>, 512); }
-                else { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, 6>, 384); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, 6>, 384); }
+                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT>); }
+                else { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, true>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, true>); }
             }
             return;
         }

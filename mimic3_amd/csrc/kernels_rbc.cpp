@@ -23,7 +23,7 @@
 //     stores (lanes past the tensor switched off by the buffer range check: no branch between a load's issue and its use,
 //     kernels_mrfs.cpp).
 // The sum order of an output element — k-group, tap, six products small terms first — does not depend on the item width, so the
-// 32-column form used for small grids (one utterance) gives the same bits as the 128-column form.
+// 32-column form used for small grids (one utterance) gives the same bits as the 128-column form (k_rb_conv_pw, further down).
 // Weights: pack_conv_weights_p16 fragments (the k_mrf_p order: [row tile][tap][k-group][plane][lane]).
 #include <algorithm>
 #include <vector>
@@ -36,7 +36,6 @@ namespace m355 {
 namespace {
 constexpr size_t RBC_LDS_LIMIT = 160 * 1024;
 constexpr int RBC_C = 128, RBC_G = RBC_C / 32, RBC_REC = RBC_C / 8;
-constexpr int RBC_PW_DEFAULT = 1;  // wide items on the producer-wave form (k_rb_conv_pw)
 constexpr int RBC_WR = 4;  // weight-fragment ring: the running step and three ahead (the step count is a multiple of 4)
 }  // namespace
 
@@ -61,8 +60,9 @@ struct RbcGeo {
     static constexpr size_t LDS = 3 * (size_t)PS16;
 };
 
-template <int K, int DIL, int NCT>
+template <int K, int DIL>
 __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
+    constexpr int NCT = 2;  // 32-column items (small grids); 128-column items run on k_rb_conv_pw
     using GE = RbcGeo<K, DIL, NCT>;
     constexpr int G = RBC_G, N = GE::N, PAD = GE::PAD, LD = GE::LD, LDP = GE::LDP, S = G * K, SH = S / 2;
     constexpr int ROUNDS = GE::ROUNDS, HALF = GE::HALF, NP = NCT / 2, WR = RBC_WR;
@@ -360,21 +360,9 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
 // of the half after that in one burst — a CU's vector-memory path returns in issue order across waves, so the matrix waves' weight
 // loads wait behind whatever the producers have in flight: one burst per phase costs that once, a trickle would cost it every step.
 // Element by element the arithmetic is k_rb_conv's (k-group, tap, six products small terms first, the same epilogue): bit-identical.
-// PRIO: the SIMD's arbiter serves the OLDER of two ready waves, so of a SIMD's two matrix waves (w and w + 4) the older one takes ~70 %
-// of the matrix pipe while both have work, finishes its phase early and idles at the barrier, and the younger one runs the rest of
-// its phase ALONE — at ~73 % of the pipe's rate (one wave's two accumulator chains and one-pair-ahead LDS reads do not fill it).
-// With PRIO the younger wave runs the first ~3/4 of a phase's steps at s_setprio 1 (it leads), then drops to 0 (the older one
-// leads): both reach the barrier together, and the pipe has two ready waves for the whole phase.
-// (s_setprio takes an immediate and only waves 4 .. 7 want it: the test and the branch live inside ONE asm statement — as a C++ `if`
-// they split the unrolled phase into basic blocks, and hipcc's wait-count pass answers that with vmcnt(0) drains and 92 bytes of spills)
-#ifdef MI355_EMU
-#define RBC_SETPRIO_YOUNG(mt, p) ((void)0)
-#else
-#define RBC_SETPRIO_YOUNG(mt, p) asm volatile("s_cmp_lt_u32 %0, 4\n\ts_cbranch_scc1 1f\n\ts_setprio " #p "\n1:" ::"s"(mt) : "scc")
-#endif
 // CLK (lab build, MI355VITS_RBC_CLOCKS=1): shader-clock stamps of waves 0, 4 (the two matrix waves of one SIMD) and 8 (its producer)
 // at the phase boundaries of every item, written by lane 0 to a.part ([workgroup][wave slot][item][8 stamps], low 32 bits)
-template <int K, int DIL, int WD, int PRIO, bool CLK = false>  // PRIO: 0 off, 1 = 3/4 of a phase, 2 = every other step, 3 = every other tile pair
+template <int K, int DIL, int WD, bool CLK = false>
 __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
     constexpr int NCT = 8;
     using GE = RbcGeo<K, DIL, NCT>;
@@ -586,15 +574,9 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
             uint4 Bf[2][2][3];
             b_read(h * SH, 0, Bf[0][0]);
             b_read(h * SH, 1, Bf[0][1]);
-            if (PRIO == 1) RBC_SETPRIO_YOUNG(mt, 1);
             MI355_UNROLL
             for (int sl = 0; sl < SH; ++sl) {
                 const int s = h * SH + sl;
-                if (PRIO == 1 && sl == (3 * SH + 2) / 4) RBC_SETPRIO_YOUNG(mt, 0);
-                if (PRIO == 2) {
-                    if (sl & 1) RBC_SETPRIO_YOUNG(mt, 0);
-                    else RBC_SETPRIO_YOUNG(mt, 1);
-                }
                 w_load((s + WD) % S, Wr[(s + WD) % WR]);
                 if (h == 1 && sl >= SH - 2) {  // the residual tiles, four per step in the phase's last two steps
                     MI355_UNROLL
@@ -604,10 +586,6 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
                 MI355_UNROLL
                 for (int jp = 0; jp < NP; ++jp) {
                     const int cur = jp & 1;
-                    if (PRIO == 3) {
-                        if (jp & 1) RBC_SETPRIO_YOUNG(mt, 0);
-                        else RBC_SETPRIO_YOUNG(mt, 1);
-                    }
                     if (jp + 1 < NP) {
                         b_read(s, 2 * jp + 2, Bf[cur ^ 1][0]);
                         b_read(s, 2 * jp + 3, Bf[cur ^ 1][1]);
@@ -639,7 +617,6 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
                     SCHED_FENCE();
                 }
             }
-            if (PRIO >= 2) RBC_SETPRIO_YOUNG(mt, 0);
             stamp(cslot, 1 + 2 * h);
             __syncthreads();
             stamp(cslot, 2 + 2 * h);
@@ -990,7 +967,7 @@ struct Ups64Geo {
     static constexpr size_t LDS = 2 * (size_t)BUF;
 };
 
-template <int NCT, bool ST16>
+template <int NCT>
 __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
     using GE = Ups64Geo<NCT>;
     constexpr int G = GE::G, K = GE::K, S = GE::S, NPOS = GE::NPOS, LD = GE::LD, LDP = GE::LDP, ROUNDS = GE::ROUNDS, FULL = GE::FULL, NP = NCT / 2;
@@ -1204,7 +1181,7 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
                 const int i = im.t0 + il;
                 const bool on = il < NPOS && i < a.T;
                 const int ch = m0 >> 2, n0 = 4 * i - 2;
-                if (ST16 && !edge) {
+                if (!edge) {
                     const unsigned o = on ? 4u * (unsigned)(ch * a.y_ld + n0) : BUF_OOB;
                     buf_store_f4(ybuf, o, 0u, c[0] + bia[0], c[1] + bia[1], c[2] + bia[2], c[3] + bia[3]);
                 } else {
@@ -1250,24 +1227,14 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
     // (the form follows the items that HAVE work: a ragged batch is as large as the sum of its rows)
     bool wide = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, 128) >= cus;
     if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
-    auto go = [&](auto kfn, size_t lds, int ncols) {
+    // wide items: the producer-wave form (twelve waves, k_rb_conv_pw); narrow items: k_rb_conv (eight waves)
+    auto go = [&](auto kfn, size_t lds, int ncols, int threads) {
         a.nvalid = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, ncols);
         const long nitems = a.nvalid;
         if (nitems <= 0) return;
         dim3 grid((unsigned)(nitems < cus ? nitems : cus));  // persistent: one workgroup per CU
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, grid, dim3(512), lds, s, a);
-    };
-    // wide items: the producer-wave form (twelve waves), MI355VITS_RBC_PW=0 (lab / tests): staging inside the matrix waves' streams
-    int pw = RBC_PW_DEFAULT;
-    if (const char* f = lab_getenv("MI355VITS_RBC_PW")) pw = atoi(f);
-    auto go_pw = [&](auto kfn, size_t lds) {
-        a.nvalid = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, 128);
-        const long nitems = a.nvalid;
-        if (nitems <= 0) return;
-        dim3 grid((unsigned)(nitems < cus ? nitems : cus));
-        set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, grid, dim3(768), lds, s, a);
+        LAUNCH_KERNEL(kfn, grid, dim3(threads), lds, s, a);
     };
 #if defined(MI355_LAB) && !defined(MI355_EMU)
     if (wide && lab_getenv("MI355VITS_RBC_CLOCKS") && ((a.K == 7 && a.dil == 3) || (a.K == 3 && a.dil == 1))) {
@@ -1283,13 +1250,12 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
             HIP_CHECK(hipMemsetAsync(dbg, 0, nb, s));
             ConvArgs c = a;
             c.part = dbg;
-            const int prio = pw == 2 ? 1 : 0;
             auto launch_c = [&](auto kfn, size_t lds) {
                 set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
                 LAUNCH_KERNEL(kfn, dim3(grid), dim3(768), lds, s, c);
             };
-            if (a.K == 7) { if (prio) launch_c(k_rb_conv_pw<7, 3, 3, 1, true>, RbcGeo<7, 3, 8>::LDS); else launch_c(k_rb_conv_pw<7, 3, 3, 0, true>, RbcGeo<7, 3, 8>::LDS); }
-            else { if (prio) launch_c(k_rb_conv_pw<3, 1, 3, 1, true>, RbcGeo<3, 1, 8>::LDS); else launch_c(k_rb_conv_pw<3, 1, 3, 0, true>, RbcGeo<3, 1, 8>::LDS); }
+            if (a.K == 7) launch_c(k_rb_conv_pw<7, 3, 3, true>, RbcGeo<7, 3, 8>::LDS);
+            else launch_c(k_rb_conv_pw<3, 1, 3, true>, RbcGeo<3, 1, 8>::LDS);
             HIP_CHECK(hipStreamSynchronize(s));
             std::vector<unsigned> h((size_t)grid * 3 * 8 * 8);
             HIP_CHECK(hipMemcpy(h.data(), dbg, nb, hipMemcpyDeviceToHost));
@@ -1297,7 +1263,7 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
             const int wg = grid > 7 ? 7 : 0;
             const char* names[3] = {"matrix wave 0", "matrix wave 4", "producer wave 8"};
             for (int slot = 0; slot < 3; ++slot) {
-                fprintf(stderr, "rb_conv_pw<%d,%d> prio=%d clocks wg %d %s:", a.K, a.dil, (int)prio, wg, names[slot]);
+                fprintf(stderr, "rb_conv_pw<%d,%d> clocks wg %d %s:", a.K, a.dil, wg, names[slot]);
                 for (int it = 0; it < 6; ++it) {
                     const unsigned* t = &h[(((size_t)wg * 3 + slot) * 8 + it) * 8];
                     if (slot < 2) fprintf(stderr, " | item %d: phase0 %u barrier %u phase1 %u barrier %u epilogue %u", it, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4]);
@@ -1311,21 +1277,11 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
         }
     }
 #endif
-#if defined(MI355_LAB) && !defined(MI355_EMU)
-#define RBC_LAB_PRIO(KK, DD)                                                                     \
-    if (wide && pw == 3) { go_pw(k_rb_conv_pw<KK, DD, 3, 2>, RbcGeo<KK, DD, 8>::LDS); return; }  \
-    if (wide && pw == 4) { go_pw(k_rb_conv_pw<KK, DD, 3, 3>, RbcGeo<KK, DD, 8>::LDS); return; }
-#else
-#define RBC_LAB_PRIO(KK, DD)
-#endif
-#define RBC_CASE(KK, DD)                                                             \
-    if (a.K == KK && a.dil == DD) {                                                  \
-        RBC_LAB_PRIO(KK, DD)                                                         \
-        if (wide && pw == 2) go_pw(k_rb_conv_pw<KK, DD, 3, 1>, RbcGeo<KK, DD, 8>::LDS);   \
-        else if (wide && pw) go_pw(k_rb_conv_pw<KK, DD, 3, 0>, RbcGeo<KK, DD, 8>::LDS);   \
-        else if (wide) go(k_rb_conv<KK, DD, 8>, RbcGeo<KK, DD, 8>::LDS, 128);        \
-        else go(k_rb_conv<KK, DD, 2>, RbcGeo<KK, DD, 2>::LDS, 32);                   \
-        return;                                                                      \
+#define RBC_CASE(KK, DD)                                                              \
+    if (a.K == KK && a.dil == DD) {                                                   \
+        if (wide) go(k_rb_conv_pw<KK, DD, 3>, RbcGeo<KK, DD, 8>::LDS, 128, 768);      \
+        else go(k_rb_conv<KK, DD>, RbcGeo<KK, DD, 2>::LDS, 32, 512);                  \
+        return;                                                                       \
     }
     RBC_CASE(3, 1)
     RBC_CASE(3, 2)
@@ -1416,11 +1372,8 @@ void launch_ups_pl(ConvArgs a, hipStream_t s) {
         const long n127 = (long)a.B * ((a.T + 126) / 127);
         bool wide = n127 >= cus;
         if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;
-        const bool st8 = lab_getenv("MI355VITS_UPS64_ST8") != nullptr;  // lab / tests: two 8-byte stores per tile (round 4)
-        if (wide && st8) go(k_ups64<8, false>, Ups64Geo<8>::LDS, 127);
-        else if (wide) go(k_ups64<8, true>, Ups64Geo<8>::LDS, 127);
-        else if (st8) go(k_ups64<2, false>, Ups64Geo<2>::LDS, 31);
-        else go(k_ups64<2, true>, Ups64Geo<2>::LDS, 31);
+        if (wide) go(k_ups64<8>, Ups64Geo<8>::LDS, 127);
+        else go(k_ups64<2>, Ups64Geo<2>::LDS, 31);
     }
 }
 

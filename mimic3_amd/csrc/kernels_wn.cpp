@@ -437,7 +437,6 @@ __global__ __launch_bounds__(64 * NW) MIN_WAVES_PER_SIMD(3) void k_wn_layer_h192
 // LDS: max(3 planes x 192 ch x 104 col x 2 B = 117 KiB, raw 384 x 96 x 4 B = 144 KiB).
 // ------------------------------------------------------------------------------------------------
 constexpr int WNB_H = 192, WNB_NG = WNB_H / 16;
-constexpr int WNB_DEFAULT_WAVES = 4;
 constexpr int WNB_RING = 4;  // weight-fragment buffers of the four-wave form
 constexpr int WNB_EPI = 1;   // epilogue form of the four-wave, 96-column kernel (template parameter EP; 1 since round 5: profiles/r05_wn_epilogue_ab.txt)
 // phase clocks of one workgroup (lab build, MI355VITS_WN_ABLATE bit 64): shader-clock deltas printed by workgroup (3, 5), wave 0
@@ -457,7 +456,7 @@ constexpr int WNB_EPI = 1;   // epilogue form of the four-wave, 96-column kernel
 #define WN_TS_DECL() ((void)0)
 #define WN_TS(i) ((void)0)
 #define WN_TS_END() ((void)0)
-#endif  // waves of the 96-column form: see launch_wn_layer_b3
+#endif
 
 // NT column tiles per workgroup: 3 (96 columns) when the grid fills the chip, 1 (32 columns) for small grids (one
 // utterance: a third of the dependent MFMA chain per wave, three times the workgroups).  The arithmetic of an output
@@ -467,23 +466,14 @@ constexpr int WNB_EPI = 1;   // epilogue form of the four-wave, 96-column kernel
 // H2 (MATH_F16X2): operands as two fp16 planes (activations x 2^4 while they are split, weights x 2^13 when packed), three
 // products per multiply-add; the accumulators run scaled by 2^17 (bias and conditioning enter scaled) and are unscaled,
 // exactly, where they leave the matrix cores — the gate and the residual / skip updates see the same values as before.
-// MW row tiles (of the 12) per wave: 3 = four waves, one per SIMD with the whole register file each; 1 = twelve waves, three per
-// SIMD with 170 registers each — the same fragments fetched once per workgroup, the same products in the same order per
-// accumulator (bit-identical), but three instruction streams per SIMD to cover each other's L2 / LDS waits in the matrix loops
-// (the four-wave form loses 40 % on a box whose fabric answers slower).
-// RA: weight-fragment ring of the four-wave form (b3.h b3_chunk_ra): 2 = one group ahead (rounds 2 - 4), 4 = three groups ahead
+// Four waves, one per SIMD with the whole register file each; MW = 3 row tiles (of the 12) per wave.
+// RA: weight-fragment ring (b3.h b3_chunk_ra): 2 = one group ahead (nt 1, bf16 weights, f16x2), 4 = three groups ahead
 // EP: the epilogue's old-value loads (h residual: L2 hits, skip accumulator: HBM) — 0 = one tile ahead of the stores (rounds 2 - 4), 1 = three
-// tiles ahead (48 loads in flight per lane: the nine tiles of a wave were nine dependent round trips), 2 = three ahead AND the first three
-// tiles' loads issued in front of the barrier behind the gate phase (they land under the res/skip conv's first steps; lab form)
-// TW ("two workgroups per CU"): 64-column tiles whose LDS fits twice into a CU (h planes 68 columns = 76.5 KiB, u planes
-// 72 KiB) with <= 256 registers per wave, so that one workgroup's
-// HBM phases (staging, the h / skip read-modify-write) run under the other's matrix loops — at the price of streaming the layer's
-// fragments once per 64 instead of once per 96 columns.  The same products in the same order per output element: bit-identical.
-template <bool W1, int NT, bool H2, int MW, int RA, int EP, bool TW>
+// tiles ahead (48 loads in flight per lane: the nine tiles of a wave were nine dependent round trips)
+template <bool W1, int NT, bool H2, int RA, int EP>
 __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
-    constexpr int NWV = 12 / MW, NTH = 64 * NWV;
+    constexpr int MW = 3, NWV = 4, NTH = 256;
     static_assert(!(W1 && H2), "one reduced-operand variant at a time");
-    static_assert(!TW || (NT == 2 && MW == 3 && !H2), "the two-per-CU form: four waves, 64 columns");
     constexpr int H = WNB_H, T_B = 32 * NT, NG = WNB_NG;
     constexpr int NP = H2 ? 2 : 3, GW = H2 ? 128 : 192;  // planes per operand; uint4 per weight-fragment group
     constexpr float ACC = H2 ? F16X2_ACC_SCALE : 1.0f, UNACC = H2 ? 1.0f / F16X2_ACC_SCALE : 1.0f;
@@ -498,7 +488,7 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
     if (t0 >= len) return;  // ragged batches (round 6): a tile past its row's length is never computed (kernels_mrfp.cpp next_item)
     const int pad = (a.K - 1) / 2 * a.dil;
     const int tlo = t0 - pad;
-    const int ts = TW ? tlo : (tlo >= 0 ? (tlo & ~3) : -(((-tlo) + 3) & ~3));  // (TW: no alignment slack — 68 staged columns, 76.5 KiB)
+    const int ts = tlo >= 0 ? (tlo & ~3) : -(((-tlo) + 3) & ~3);
     const int toff = tlo - ts;
     const int LD = a.ldx;          // staged columns of the h tile
     WN_TS_DECL();
@@ -506,7 +496,7 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
     const int PS = NG * 2 * LD;    // uint4 per plane
     const bool two = a.Crs == 2 * H;
 
-    if (!(LAB_ABLATE(a) & 2)) stage_planes<NG, (TW ? 8 : (MW == 3 ? NG : 4)), H2>(a.h_in + (long)b * a.h_bs, a.h_ld, LD, ts, len, 1.0f, planes, PS, tid, NTH);  // column sets x row batches: one round trip
+    if (!(LAB_ABLATE(a) & 2)) stage_planes<NG, NG, H2>(a.h_in + (long)b * a.h_bs, a.h_ld, LD, ts, len, 1.0f, planes, PS, tid, NTH);  // column sets x row batches: one round trip
     __syncthreads();
     WN_TS(1);
 
@@ -531,9 +521,7 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
             wp[i] = reinterpret_cast<const uint4*>(a.w_in) + (long)q * a.K * NG * GW + lane;
         }
         if (!(LAB_ABLATE(a) & 1)) {
-            // (twelve waves: 170 registers each — the form with the B fragments single-buffered, same products in the same order)
             if constexpr (H2) h2_chunk<MW, NT, NG, NT>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
-            else if constexpr (MW == 1 || TW) b3_chunk_lean<MW, NT, NG, W1>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);  // (TW: 256 registers)
             else if constexpr (RA > 2 && NT >= 4) b3_chunk_lean_ra<MW, NT, NG, W1, RA>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);  // (four column tiles: B single-buffered)
             else if constexpr (RA > 2) b3_chunk_ra<MW, NT, NG, NT, W1, RA>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
             else b3_chunk<MW, NT, NG, NT, W1>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
@@ -624,11 +612,6 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
         MI355_UNROLL
         for (int r = 0; r < 16; ++r) o[r] = buf_load_f32(rs, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * row4);
     };
-    if constexpr (EP == 2) {
-        MI355_UNROLL
-        for (int k = 0; k < EPA; ++k) load_tile_b(k / NT, k % NT, old[k]);
-        SCHED_FENCE();
-    }
     constexpr int PSU = NG * 2 * T_B;
     __syncthreads();
     WN_TS(4);
@@ -649,13 +632,12 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
             wp[i] = reinterpret_cast<const uint4*>(a.w_rs) + (long)q * NG * GW + lane;
         }
         if (!(LAB_ABLATE(a) & 1)) {
-            if (two || MW == 1) {  // (twelve waves, six tiles: waves 6 .. 11 recompute the last tile, discarded below)
+            if (two) {
                 if constexpr (H2) h2_chunk<MW, NT, NG, NT>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-                else if constexpr (MW == 1 || TW) b3_chunk_lean<MW, NT, NG, W1>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
                 else if constexpr (RA > 2 && NT >= 4) b3_chunk_lean_ra<MW, NT, NG, W1, RA>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
                 else if constexpr (RA > 2) b3_chunk_ra<MW, NT, NG, NT, W1, RA>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
                 else b3_chunk<MW, NT, NG, NT, W1>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-            } else if constexpr (MW == 3) {  // 6 tiles: waves 0, 1 two tiles, waves 2, 3 one (second index clamped)
+            } else {  // 6 tiles: waves 0, 1 two tiles, waves 2, 3 one (second index clamped)
                 f32x16 a2[2][NT];
                 const uint4* w2[2] = {wp[0], wp[1]};
                 MI355_UNROLL
@@ -711,10 +693,8 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
             MI355_UNROLL
             for (int r = 0; r < 16; ++r) buf_store_f32(rs, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * row4, live ? o[r] + acc[i][j][r] : 0.0f);
         };
-        if constexpr (EP == 1) {
-            MI355_UNROLL
-            for (int k = 0; k < EPA && k < MW * NT; ++k) load_tile_b(k / NT, k % NT, old[k]);
-        }
+        MI355_UNROLL
+        for (int k = 0; k < EPA && k < MW * NT; ++k) load_tile_b(k / NT, k % NT, old[k]);
         MI355_UNROLL
         for (int k = 0; k < MW * NT; ++k) {
             if (k + EPA < MW * NT) load_tile_b((k + EPA) / NT, (k + EPA) % NT, old[(k + EPA) % EPR]);
@@ -726,14 +706,9 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
     WN_TS_END();
 }
 
-template <bool W1, int NT, bool H2 = false, int MW = 3, int RA = 2, int EP = 0>
-__global__ __launch_bounds__(64 * (12 / MW)) void k_wn_layer_b3(WnArgs a) {
-    wn_layer_b3_body<W1, NT, H2, MW, RA, EP, false>(a);
-}
-// the two-per-CU form: <= 256 registers per wave (two waves per SIMD), 76.5 KiB of LDS
-template <bool W1>
-__global__ __launch_bounds__(256, 2) void k_wn_layer_b3_tw(WnArgs a) {
-    wn_layer_b3_body<W1, 2, false, 3, 2, 1, true>(a);
+template <bool W1, int NT, bool H2 = false, int RA = 2, int EP = 0>
+__global__ __launch_bounds__(256) void k_wn_layer_b3(WnArgs a) {
+    wn_layer_b3_body<W1, NT, H2, RA, EP>(a);
 }
 
 bool wn_layer_b3_supported(int H, int K, int dil) {
@@ -759,70 +734,38 @@ void launch_wn_layer_b3(WnArgs a, hipStream_t s) {
         if ((double)((nwg4 + cus - 1) / cus) * 1.28 < (double)((nwg3 + cus - 1) / cus)) nt = 4;
     }
     if (nt == 4 && (a.math == MATH_F16X2 || ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL || (a.K - 1) * a.dil > 8))) nt = 3;  // (buffer-addressed epilogue; 160 KiB of LDS)
-    // the two-workgroups-per-CU form (64-column tiles, k_wn_layer_b3_tw): large grids of the default / bf16-weights math
-    // Measured on the MI355X (profiles/r05_wn_two_per_cu_ab.txt): 8.5 % SLOWER than the 96-column form at batch 256 (14.3 vs 13.2 ms per 16
-    // layers x 256 rows), 31 % slower at batch 32 (384 workgroups on 512 slots) — what the overlap of the HBM phases gains, the 1.5 x
-    // weight stream through the L1 and the leaner loop (2 x 3 instead of 3 x 3 tiles per fragment pair) lose again.  Lab build and CPU
-    // model only, as the A/B of that statement (MI355VITS_WN_TW=1).
-    bool tw = false;
-#if defined(MI355_LAB) || defined(MI355_EMU)
-    if (const char* f = lab_getenv("MI355VITS_WN_TW")) tw = atoi(f) != 0 && nt == 3 && a.math != MATH_F16X2;
-#endif
-    if ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL) tw = false;  // (its epilogue: a 32-row tile within the buffer range)
-    if (tw && (size_t)3 * WNB_NG * 2 * (64 + (a.K - 1) * a.dil) * 16 > 80 * 1024) tw = false;  // two of them must fit a CU's 160 KiB
-    if (tw) nt = 2;
     const int tb = 32 * nt;
-    a.ldx = tw ? tb + (a.K - 1) * a.dil : ((tb + (a.K - 1) * a.dil + 3 + 3) & ~3);
+    a.ldx = (tb + (a.K - 1) * a.dil + 3 + 3) & ~3;
     const size_t shmem = (size_t)3 * WNB_NG * 2 * a.ldx * 16;  // the h planes; u's planes (column pitch tb <= ldx) take their place
     dim3 grid((a.T + tb - 1) / tb, a.B);
-    // four waves (one per SIMD, the whole register file each) is the product's form.  The twelve-wave form (three per SIMD; MW = 1)
-    // is bit-identical and measured EQUAL on the MI355X (16 layers 1.77 vs 1.76 ms, profiles/r04_wn_experiments.txt): the matrix
-    // loops do not wait on latencies that more waves could cover, what the layer loses it loses in its serial phases — so it is
-    // compiled into the lab build and the CPU model only (MI355VITS_WN_WAVES=12), as the A/B of that statement
-    const char* nw_s = lab_getenv("MI355VITS_WN_WAVES");
-    const int nw = nw_s ? atoi(nw_s) : WNB_DEFAULT_WAVES;
-    auto go = [&](auto kfn, int threads) {
+    // four waves (one per SIMD, the whole register file each).  A twelve-wave form (three per SIMD) was bit-identical and measured
+    // EQUAL (16 layers 1.77 vs 1.76 ms, profiles/r04_wn_experiments.txt); a two-workgroups-per-CU form (64-column tiles) 8.5 % slower
+    // at batch 256 (profiles/r05_wn_two_per_cu_ab.txt)
+    auto go = [&](auto kfn) {
 #ifndef MI355_EMU
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
 #endif
-        LAUNCH_KERNEL(kfn, grid, dim3(threads), shmem, s, a);
+        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, a);
     };
-#if defined(MI355_LAB) || defined(MI355_EMU)
-    if (tw) {
-        if (a.math == MATH_BF16W) go(k_wn_layer_b3_tw<true>, 256);
-        else go(k_wn_layer_b3_tw<false>, 256);
-    } else
-#endif
     if (nt == 4 && a.math != MATH_F16X2) {
         // weight fragments three groups ahead as in the 96-column form, the B fragments single-buffered (b3_chunk_lean_ra: with both
-        // double-buffered the loop spills 148 B at four column tiles); MI355VITS_WN_RING=2: one group ahead, B double-buffered
-        int ring = WNB_RING;
-        if (const char* f = lab_getenv("MI355VITS_WN_RING")) ring = atoi(f);
-        if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 4, false, 3, 4, 1>, 256);
-        else if (ring > 2) go(k_wn_layer_b3<false, 4, false, 3, 4, 1>, 256);
-        else go(k_wn_layer_b3<false, 4, false, 3, 2, 1>, 256);
+        // double-buffered the loop spills 148 B at four column tiles)
+        if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 4, false, WNB_RING, 1>);
+        else go(k_wn_layer_b3<false, 4, false, WNB_RING, 1>);
     } else if (nt == 1) {
-        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 1, true>, 256);
-        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 1>, 256);
-        else go(k_wn_layer_b3<false, 1>, 256);
-#if defined(MI355_LAB) || defined(MI355_EMU)
-    } else if (nw == 12 && a.math != MATH_F16X2) {
-        if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 3, false, 1>, 768);
-        else go(k_wn_layer_b3<false, 3, false, 1>, 768);
-#endif
+        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 1, true>);
+        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 1>);
+        else go(k_wn_layer_b3<false, 1>);
     } else {
-        // default math, large grids: the weight fragments three groups ahead (WNB_RING; MI355VITS_WN_RING=2: one group ahead)
-        int ring = WNB_RING;
-        if (const char* f = lab_getenv("MI355VITS_WN_RING")) ring = atoi(f);
+        // default math, large grids: the weight fragments three groups ahead (WNB_RING), the epilogue's loads three tiles ahead (WNB_EPI;
+        // MI355VITS_WN_EPI=0: one tile ahead, the form past the buffer range)
         int epi = WNB_EPI;
         if (const char* f = lab_getenv("MI355VITS_WN_EPI")) epi = atoi(f);
         if ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL) epi = 0;  // a 32-row tile must fit the buffer range
-        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 3, true>, 256);
-        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 3>, 256);
-        else if (ring > 2 && epi == 2) go(k_wn_layer_b3<false, 3, false, 3, 4, 2>, 256);
-        else if (ring > 2 && epi == 1) go(k_wn_layer_b3<false, 3, false, 3, 4, 1>, 256);
-        else if (ring > 2) go(k_wn_layer_b3<false, 3, false, 3, 4>, 256);
-        else go(k_wn_layer_b3<false, 3>, 256);
+        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 3, true>);
+        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 3>);
+        else if (epi == 1) go(k_wn_layer_b3<false, 3, false, WNB_RING, 1>);
+        else go(k_wn_layer_b3<false, 3, false, WNB_RING>);
     }
 }
 

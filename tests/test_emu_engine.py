@@ -458,10 +458,10 @@ def test_encoder_convs_on_the_slice_kernel(emu_lib):
 
 
 def test_encoder_wide_forms_are_bitwise_the_64_column_form(emu_lib):
-    """k_enc_b3w (128 columns x all of a conv's 32-row tiles per workgroup) against the 64 x 64 form, and its two ways of running a block
-    of SIX row tiles (FFN conv_2, q / k / v, the couplings' pre conv: 192 output rows): one row tile per wave on six waves
-    (MI355VITS_ENC_SIX8=0) or the 24 (row tile, column tile) units dealt three to a wave on eight waves (the default since round 6).
-    Same products in the same order per output element: every text-side tap, z and the waveform bit for bit, ragged rows included."""
+    """k_enc_b3w (128 columns x all of a conv's 32-row tiles per workgroup) against the 64 x 64 form, blocks of SIX row tiles (FFN
+    conv_2, q / k / v, the couplings' pre conv: 192 output rows) included: their 24 (row tile, column tile) units dealt three to a wave
+    on eight waves.  Same products in the same order per output element: every text-side tap, z and the waveform bit for bit, ragged
+    rows included."""
     import os
 
     cfg = VitsConfig.tiny_h192()
@@ -471,8 +471,7 @@ def test_encoder_wide_forms_are_bitwise_the_64_column_form(emu_lib):
     ids = np.random.default_rng(9).integers(1, cfg.num_symbols, (3, 150))
     lengths = np.array([150, 33, 129])
     res = {}
-    for tag, env in (("narrow", {"MI355VITS_ENC_WIDE": "0"}), ("six", {"MI355VITS_ENC_WIDE": "1", "MI355VITS_ENC_SIX8": "0"}),
-                     ("eight", {"MI355VITS_ENC_WIDE": "1"})):
+    for tag, env in (("narrow", {"MI355VITS_ENC_WIDE": "0"}), ("eight", {"MI355VITS_ENC_WIDE": "1"})):
         os.environ.update(env)
         try:
             eng = Engine(blob, library=emu_lib)
@@ -483,9 +482,8 @@ def test_encoder_wide_forms_are_bitwise_the_64_column_form(emu_lib):
         finally:
             for k in env:
                 del os.environ[k]
-    for tag in ("six", "eight"):
-        for k, (a, b) in enumerate(zip(res["narrow"], res[tag])):
-            assert np.array_equal(a, b), (tag, k)
+    for k, (a, b) in enumerate(zip(res["narrow"], res["eight"])):
+        assert np.array_equal(a, b), k
 
 
 @pytest.mark.parametrize("n_speakers", [1, 3])
@@ -523,59 +521,17 @@ def test_bf16x3_fused_wavenet_layer_kernel(emu_lib, n_speakers):
         finally:
             del os.environ["MI355VITS_WN_B3_NT"]
     assert np.array_equal(by_nt["1"], by_nt["3"]) and np.array_equal(by_nt["4"], by_nt["3"])
-    # ... and the twelve-wave form of the 96-column tile (one row tile per wave, three waves per SIMD) against the four-wave one
-    by_nw = {}
-    for nw in ("4", "12"):
-        os.environ["MI355VITS_WN_B3_NT"] = "3"
-        os.environ["MI355VITS_WN_WAVES"] = nw
-        try:
-            for mode in ("bf16x3", "bf16w"):
-                eng = Engine(blob, library=emu_lib)
-                eng.set_math(mode)
-                by_nw[nw, mode] = eng.run(ids, np.array([30, 17]), (0.667, 1.0, 0.8), sid, forced_durations=forced, seed=3)["audio"]
-                eng.close()
-        finally:
-            del os.environ["MI355VITS_WN_B3_NT"], os.environ["MI355VITS_WN_WAVES"]
-    assert np.array_equal(by_nw["4", "bf16x3"], by_nt["3"])
-    for mode in ("bf16x3", "bf16w"):
-        assert np.array_equal(by_nw["4", mode], by_nw["12", mode]), mode
-    # ... and the four-wave form's weight-fragment ring: three groups ahead (the default, round 5) against one group ahead
+    # ... and the epilogue's old-value loads three tiles ahead as buffer instructions (EP = 1): the same additions on the same values
     os.environ["MI355VITS_WN_B3_NT"] = "3"
-    os.environ["MI355VITS_WN_RING"] = "2"
+    os.environ["MI355VITS_WN_EPI"] = "1"
     try:
         eng = Engine(blob, library=emu_lib)
         eng.set_math("bf16x3")
-        ring2 = eng.run(ids, np.array([30, 17]), (0.667, 1.0, 0.8), sid, forced_durations=forced, seed=3)["audio"]
+        got = eng.run(ids, np.array([30, 17]), (0.667, 1.0, 0.8), sid, forced_durations=forced, seed=3)["audio"]
         eng.close()
     finally:
-        del os.environ["MI355VITS_WN_B3_NT"], os.environ["MI355VITS_WN_RING"]
-    assert np.array_equal(ring2, by_nt["3"])
-    # ... and the epilogue's old-value loads three tiles ahead as buffer instructions (EP = 1), the first three issued in front of the
-    # gate phase (EP = 2): the same additions on the same values
-    for epi in ("1", "2"):
-        os.environ["MI355VITS_WN_B3_NT"] = "3"
-        os.environ["MI355VITS_WN_EPI"] = epi
-        try:
-            eng = Engine(blob, library=emu_lib)
-            eng.set_math("bf16x3")
-            got = eng.run(ids, np.array([30, 17]), (0.667, 1.0, 0.8), sid, forced_durations=forced, seed=3)["audio"]
-            eng.close()
-        finally:
-            del os.environ["MI355VITS_WN_B3_NT"], os.environ["MI355VITS_WN_EPI"]
-        assert np.array_equal(got, by_nt["3"]), epi
-    # ... and the two-workgroups-per-CU form (k_wn_layer_b3_tw: 64-column tiles, 68 staged columns, the raw result gated one 32-column
-    # tile at a time, B fragments single-buffered) in the default and the bf16-weights mode
-    for mode in ("bf16x3", "bf16w"):
-        os.environ["MI355VITS_WN_B3_NT"] = "3"
-        os.environ["MI355VITS_WN_TW"] = "1"
-        try:
-            eng = Engine(blob, library=emu_lib)
-            eng.set_math(mode)
-            got = eng.run(ids, np.array([30, 17]), (0.667, 1.0, 0.8), sid, forced_durations=forced, seed=3)["audio"]
-            eng.close()
-        finally:
-            del os.environ["MI355VITS_WN_B3_NT"], os.environ["MI355VITS_WN_TW"]
-        assert np.array_equal(got, by_nw["4", mode]), mode
+        del os.environ["MI355VITS_WN_B3_NT"], os.environ["MI355VITS_WN_EPI"]
+    assert np.array_equal(got, by_nt["3"])
 
 
 def test_f16x2_mode_fused_mrf_stages(emu_lib):
@@ -819,14 +775,13 @@ def test_resblock_conv_128_channels_resident_input(emu_lib, monkeypatch):
     ids = np.random.default_rng(8).integers(1, cfg.num_symbols, (3, Tx))
     lengths = np.array([Tx, Tx - 9, Tx - 1])
     outs, taps = {}, {}
-    # "wide" = 128-column items on the producer-wave form (k_rb_conv_pw: twelve waves, waves 8 .. 11 only stage; the default), "wide_pw0"
-    # = the same items with the staging inside the matrix waves' streams (k_rb_conv), "wide_pw2" = weight fragments two steps ahead
-    for tag, env in (("wide", {"MI355VITS_RBC_WIDE": "1"}), ("wide_pw0", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_PW": "0"}),
-                     ("wide_pw2", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_PW": "2"}), ("narrow", {"MI355VITS_RBC_WIDE": "0"}),
+    # "wide" = 128-column items on the producer-wave form (k_rb_conv_pw: twelve waves, waves 8 .. 11 only stage), "narrow" = 32-column
+    # items on k_rb_conv (the staging inside the matrix waves' streams)
+    for tag, env in (("wide", {"MI355VITS_RBC_WIDE": "1"}), ("narrow", {"MI355VITS_RBC_WIDE": "0"}),
                      ("wide_o0", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_ITEM_ORDER": "0"}),  # items w, w + W, ... instead of XCD-major
                      ("narrow_o0", {"MI355VITS_RBC_WIDE": "0", "MI355VITS_RBC_ITEM_ORDER": "0"}),
                      ("old", {"MI355VITS_NO_RBC": "1"})):
-        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_RBC_PW", "MI355VITS_RBC_ITEM_ORDER"):
+        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_RBC_ITEM_ORDER"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -839,7 +794,7 @@ def test_resblock_conv_128_channels_resident_input(emu_lib, monkeypatch):
         assert "dec.rb.s0" in labels, labels
         taps[tag] = eng.tap("dec.mrf.0")
         eng.close()
-    for tag in ("wide_pw0", "wide_pw2", "narrow", "wide_o0", "narrow_o0"):
+    for tag in ("narrow", "wide_o0", "narrow_o0"):
         assert np.array_equal(taps["wide"], taps[tag]), tag
         assert np.array_equal(outs["wide"]["audio"], outs[tag]["audio"]), tag
     for bi in range(3):
@@ -866,11 +821,9 @@ def test_polyphase_upsamplers_resident_input(emu_lib, monkeypatch):
     ids = np.random.default_rng(9).integers(1, cfg.num_symbols, (2, Tx))
     lengths = np.array([Tx, Tx - 5])
     outs, taps = {}, {}
-    # "..._st8": k_ups64 with the round-4 epilogue (two 8-byte stores per tile instead of one 16-byte store in a row's interior items)
     for tag, env in (("wide", {"MI355VITS_RBC_WIDE": "1"}), ("narrow", {"MI355VITS_RBC_WIDE": "0"}), ("old", {"MI355VITS_NO_RBC": "1"}),
-                     ("wide_st8", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_UPS64_ST8": "1"}), ("narrow_st8", {"MI355VITS_RBC_WIDE": "0", "MI355VITS_UPS64_ST8": "1"}),
                      ("wide_o0", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_ITEM_ORDER": "0"}), ("narrow_o0", {"MI355VITS_RBC_WIDE": "0", "MI355VITS_RBC_ITEM_ORDER": "0"})):
-        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_UPS64_ST8", "MI355VITS_RBC_ITEM_ORDER"):
+        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_RBC_ITEM_ORDER"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -881,7 +834,7 @@ def test_polyphase_upsamplers_resident_input(emu_lib, monkeypatch):
         taps[tag] = {k: eng.tap(k) for k in ("dec.ups.0", "dec.ups.1", "dec.ups.2")}
         eng.close()
     for k in taps["wide"]:
-        for tag in ("narrow", "wide_st8", "narrow_st8", "wide_o0", "narrow_o0"):
+        for tag in ("narrow", "wide_o0", "narrow_o0"):
             assert np.array_equal(taps["wide"][k], taps[tag][k]), (k, tag)
         assert not np.array_equal(taps["wide"][k], taps["old"][k]), k  # (another kernel did run: another order of summation)
     assert np.array_equal(outs["wide"]["audio"], outs["narrow"]["audio"])

@@ -177,13 +177,12 @@ def test_resblock_conv_128_channels_on_the_device(lab_lib, monkeypatch):
     forced = np.full((B, Tx), 6, np.int32)
     res = {}
     # "wide" = 128-column items on the producer-wave form (k_rb_conv_pw, the default), run TWICE ("wide_again": a race between the producer
-    # waves' LDS stores and the matrix waves' reads would show as a difference between two runs — the CPU model cannot see one); "wide_pw0" =
-    # the staging inside the matrix waves' streams (k_rb_conv), "wide_pw2" = weight fragments two steps ahead instead of three
+    # waves' LDS stores and the matrix waves' reads would show as a difference between two runs — the CPU model cannot see one); "narrow" =
+    # 32-column items on k_rb_conv (the staging inside the matrix waves' streams)
     for tag, env in (("default", {}), ("wide", {"MI355VITS_RBC_WIDE": "1"}), ("wide_again", {"MI355VITS_RBC_WIDE": "1"}),
-                     ("wide_pw0", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_PW": "0"}), ("wide_pw2", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_PW": "2"}),
                      ("narrow", {"MI355VITS_RBC_WIDE": "0"}), ("old", {"MI355VITS_NO_RBC": "1"}),
                      ("wide_o0", {"MI355VITS_RBC_WIDE": "1", "MI355VITS_RBC_ITEM_ORDER": "0"})):  # items w, w + W, ... instead of XCD-major
-        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_RBC_PW", "MI355VITS_RBC_ITEM_ORDER"):
+        for k in ("MI355VITS_RBC_WIDE", "MI355VITS_NO_RBC", "MI355VITS_RBC_ITEM_ORDER"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -194,7 +193,7 @@ def test_resblock_conv_128_channels_on_the_device(lab_lib, monkeypatch):
         assert ("dec.mrf_fused.s0" in labels) == (tag == "old"), (tag, labels)
         res[tag] = eng.tap("dec.mrf.0"), out["audio"].copy(), out["lengths"].copy(), eng.tap("dec.ups.1"), eng.tap("dec.ups.2"), eng.tap("dec.ups.0")
         eng.close()
-    for tag in ("default", "narrow", "wide_again", "wide_pw0", "wide_pw2", "wide_o0"):
+    for tag in ("default", "narrow", "wide_again", "wide_o0"):
         for k in (0, 1, 3, 4, 5):
             assert np.array_equal(res[tag][k], res["wide"][k]), (tag, k)
     for bi in range(B):
@@ -206,11 +205,11 @@ def test_resblock_conv_128_channels_on_the_device(lab_lib, monkeypatch):
 
 
 def test_round5_memory_bound_kernels_on_the_device(lab_lib, monkeypatch):
-    """Round 5's two memory-side rewrites against the kernels they replace, on the MI355X at the full-size shapes, BIT FOR BIT:
+    """Round 5's memory-side rewrite of conv_post against the kernel it replaces, on the MI355X at the full-size shapes, BIT FOR BIT:
     k_conv_post_tanh_dpp (one 16-byte load per lane, channel and tile, the taps' neighbours through DPP wave shifts — `wave_shr:1`
-    exists on the device only: the CPU model uses its shuffle) vs the round-1 kernel (MI355VITS_CONV_POST_V1=1), and k_ups64's
-    one 16-byte store per tile vs two 8-byte stores (MI355VITS_UPS64_ST8=1).  Waveform, lengths, int16 and the 64 -> 32 upsampler's
-    tap; ragged rows (ending inside a tile / an item), a one-phoneme row; each variant also against itself on a second engine."""
+    exists on the device only: the CPU model uses its shuffle) vs the round-1 kernel (MI355VITS_CONV_POST_V1=1).  Waveform, lengths,
+    int16 and the 64 -> 32 upsampler's tap; ragged rows (ending inside a tile / an item), a one-phoneme row; the default also against
+    itself on a second engine."""
     cfg = VitsConfig.apope_low()
     w = W.synthetic_weights(cfg, seed=1234)
     blob = W.pack(cfg, w)
@@ -219,25 +218,24 @@ def test_round5_memory_bound_kernels_on_the_device(lab_lib, monkeypatch):
     lengths = np.array([Tx, Tx, 97, Tx, 64, Tx, 1, 127])
     forced = np.full((B, Tx), 6, np.int32)
     res = {}
-    for tag, env in (("new", {}), ("new_again", {}), ("post_v1", {"MI355VITS_CONV_POST_V1": "1"}), ("st8", {"MI355VITS_UPS64_ST8": "1"}),
-                     ("both_old", {"MI355VITS_CONV_POST_V1": "1", "MI355VITS_UPS64_ST8": "1"})):
-        for k in ("MI355VITS_CONV_POST_V1", "MI355VITS_UPS64_ST8"):
-            monkeypatch.delenv(k, raising=False)
+    for tag, env in (("new", {}), ("new_again", {}), ("post_v1", {"MI355VITS_CONV_POST_V1": "1"})):
+        monkeypatch.delenv("MI355VITS_CONV_POST_V1", raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         eng = Engine(blob, library=lab_lib, device=0)
         out = eng.run(ids, lengths, [0.667, 1.0, 0.8], forced_durations=forced, seed=3, debug_taps=True, want_pcm16=True)
         res[tag] = out["audio"].copy(), out["lengths"].copy(), out["pcm"].copy(), eng.tap("dec.ups.2")
         eng.close()
-    for tag in ("new_again", "post_v1", "st8", "both_old"):
+    for tag in ("new_again", "post_v1"):
         for k in range(4):
             assert np.array_equal(res[tag][k], res["new"][k]), (tag, k)
 
 
-def test_wavenet_layer_weight_ring_depths_agree_bitwise_on_the_device(lab_lib, monkeypatch):
-    """k_wn_layer_b3 with its weight fragments three groups ahead (a ring of four buffers: the default since round 5, for the boxes
-    whose L2 loses the layer's fragments to the activation stream) against one group ahead (MI355VITS_WN_RING=2) at the bench
-    shape's tile form: z and the waveform BIT FOR BIT (the same products in the same order per accumulator)."""
+def test_wavenet_layer_epilogue_and_tile_forms_agree_bitwise_on_the_device(lab_lib, monkeypatch):
+    """k_wn_layer_b3 at the bench shape's 96-column tiles (weight fragments three groups ahead) against itself on a second engine,
+    against both epilogue forms (old values one tile ahead, MI355VITS_WN_EPI=0 — the form past the buffer range — and three tiles
+    ahead) and against the 128-column tiles large grids run since round 6: z and the waveform BIT FOR BIT (the same products in the
+    same order per accumulator)."""
     cfg = VitsConfig.apope_low()
     w = W.synthetic_weights(cfg, seed=1234)
     blob = W.pack(cfg, w)
@@ -247,24 +245,16 @@ def test_wavenet_layer_weight_ring_depths_agree_bitwise_on_the_device(lab_lib, m
     forced = np.full((B, Tx), 6, np.int32)
     res = {}
     monkeypatch.setenv("MI355VITS_WN_B3_NT", "3")
-    for tag, ring in (("ring4", None), ("ring2", "2"), ("ring4_again", None), ("epi0", "e0"), ("epi1", "e1"), ("epi2", "e2"), ("tw", "tw"), ("nt4", "nt4"), ("nt4r2", "nt4r2")):
-        monkeypatch.setenv("MI355VITS_WN_B3_NT", "4" if (ring or "").startswith("nt4") else "3")  # (nt4: the 128-column tiles large grids run since round 6)
-        monkeypatch.delenv("MI355VITS_WN_RING", raising=False)
+    for tag, form in (("ring4", None), ("ring4_again", None), ("epi0", "e0"), ("epi1", "e1"), ("nt4", "nt4")):
+        monkeypatch.setenv("MI355VITS_WN_B3_NT", "4" if form == "nt4" else "3")  # (nt4: the 128-column tiles large grids run since round 6)
         monkeypatch.delenv("MI355VITS_WN_EPI", raising=False)
-        monkeypatch.delenv("MI355VITS_WN_TW", raising=False)
-        if ring == "tw":  # the two-workgroups-per-CU form (64-column tiles)
-            monkeypatch.setenv("MI355VITS_WN_TW", "1")
-        elif ring is not None and ring.startswith("e"):  # the epilogue forms (old values one / three tiles ahead / + issued before the gate)
-            monkeypatch.setenv("MI355VITS_WN_EPI", ring[1:])
-        elif ring == "nt4r2":  # 128-column tiles with the fragments one group ahead (B double-buffered) instead of three (B single-buffered)
-            monkeypatch.setenv("MI355VITS_WN_RING", "2")
-        elif ring is not None and ring != "nt4":
-            monkeypatch.setenv("MI355VITS_WN_RING", ring)
+        if form is not None and form.startswith("e"):  # the epilogue forms (old values one / three tiles ahead)
+            monkeypatch.setenv("MI355VITS_WN_EPI", form[1:])
         eng = Engine(blob, library=lab_lib, device=0)
         out = eng.run(ids, lengths, [0.667, 1.0, 0.8], forced_durations=forced, seed=3, debug_taps=True)
         res[tag] = eng.tap("z"), out["audio"].copy(), out["lengths"].copy()
         eng.close()
-    for tag in ("ring2", "ring4_again", "epi0", "epi1", "epi2", "tw", "nt4", "nt4r2"):
+    for tag in ("ring4_again", "epi0", "epi1", "nt4"):
         for k in range(3):
             assert np.array_equal(res[tag][k], res["ring4"][k]), (tag, k)
 
@@ -306,20 +296,15 @@ def test_encoder_128_column_form_is_bitwise_the_64_column_form(lab_lib, monkeypa
     ids = np.random.default_rng(6).integers(1, cfg.num_symbols, (6, Tx))
     lengths = [Tx, 65, 1, 129, 128, 77]
     res = {}
-    for tag, env, six8 in (("narrow", "0", None), ("wide", "1", None), ("wide6", "1", "0")):  # (wide6: six-row-tile blocks on six waves, the round-6a form)
+    for tag, env in (("narrow", "0"), ("wide", "1")):
         monkeypatch.setenv("MI355VITS_ENC_WIDE", env)
-        if six8 is None:
-            monkeypatch.delenv("MI355VITS_ENC_SIX8", raising=False)
-        else:
-            monkeypatch.setenv("MI355VITS_ENC_SIX8", six8)
         eng = Engine(blob, library=lab_lib, device=0)
         eng.profile_enable(True)
         out = eng.run(ids, lengths, [0.667, 1.0, 0.8], debug_taps=True, seed=14)
         res[tag] = [eng.tap(k) for k in ("x", "stats", "dp.h", "w_ceil", "z_p", "z")] + [out["lengths"].copy(), out["audio"].copy()]
         eng.close()
-    for tag in ("wide", "wide6"):
-        for k, (a, b) in enumerate(zip(res["narrow"], res[tag])):
-            assert np.array_equal(a, b), (tag, k)
+    for k, (a, b) in enumerate(zip(res["narrow"], res["wide"])):
+        assert np.array_equal(a, b), k
 
 
 def test_attention_high_occupancy_form_is_bitwise_the_prefetched_form(lab_lib, monkeypatch):

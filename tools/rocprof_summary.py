@@ -69,7 +69,7 @@ def _labels(B, Tx, fpi):
         "dec.mrf_fused.s0": ("k_mrf_fused<4, 2, 3, 3, 2, 160, 128, 1>", 2 * 4 * B * 128 * Ty * 8),
         "dec.mrf_fused.s1": ("k_mrf_fused<2, 4, 6, 3, 2, 320, 288, 1>", 2 * 4 * B * 64 * Ty * 64),
         "dec.mrf_fused.s2": ("k_mrf_fused<1, 8, 16, 3, 2, 640, 608, 1>", 2 * 4 * B * 32 * Ty * 256),
-        "flow.wn_layer_b3": ("k_wn_layer_b3<false, 3>", 4 * 4 * B * 192 * Ty + 6 * (384 * 192 * 5 + 384 * 192)),  # h r+w, skip r+w, bf16x3 weights
+        "flow.wn_layer_b3": ("k_wn_layer_b3<false, 3, false, 4, 1>", 4 * 4 * B * 192 * Ty + 6 * (384 * 192 * 5 + 384 * 192)),  # h r+w, skip r+w, bf16x3 weights
         # MATH_F16X2 (bench --math f16x2)
         "f16x2:dec.mrf_fused.s1": ("k_mrf_fused<2, 4, 6, 3, 2, 320, 288, 3>", 2 * 4 * B * 64 * Ty * 64),
         "f16x2:dec.mrf_fused.s2": ("k_mrf_fused<1, 8, 16, 3, 2, 640, 608, 3>", 2 * 4 * B * 32 * Ty * 256),
