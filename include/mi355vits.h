@@ -106,6 +106,16 @@ typedef struct mi355vits_run_args {
                                 * settings.volume / 100 (mimic3_tts/tts.py:542-543).  0 or 1 = leave as is. */
 } mi355vits_run_args;
 
+/* Per-row synthesis settings of one batched call (mi355vits_run_rows).  Each pointer may be NULL: then every row takes the
+ * run_args value (row b keyed run_args.utterance_base + b).  The reference passes these per sentence: mimic3_http's
+ * noiseScale / lengthScale / noiseW (mimic3_http/app.py:172-182), SSML <prosody rate> dividing length_scale
+ * (mimic3_tts/voice.py:168-170) and <prosody volume> setting settings.volume (mimic3_tts/tts.py:542-543). */
+typedef struct mi355vits_row_args {
+    const float* scales;        /* [B,3] noise_scale, length_scale, noise_w per row; NULL = args->scales for every row */
+    const double* pcm_volume;   /* [B] with WANT_PCM16, audioop.mul factor per row (0 or 1 = as is); NULL = args->pcm_volume */
+    const uint64_t* utterance;  /* [B] Philox utterance index per row; NULL = args->utterance_base + b */
+} mi355vits_row_args;
+
 typedef struct mi355vits_result {
     int32_t batch;
     int64_t l_max;     /* samples per row = hop * max_b frames_b */
@@ -172,6 +182,17 @@ int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out);
  * them with mi355vits_free_result.  With MI355VITS_DEVICE_ONLY the audio stays in the engine's
  * workspace until the next run; mi355vits_fetch copies it out afterwards. */
 int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_result* out);
+/* mi355vits_run with per-row settings: one call for a batch whose rows differ in scales, PCM volume or noise key
+ * (mi355vits_run(h, a, o) is mi355vits_run_rows(h, a, NULL, o)).  args->scales may be NULL when rows->scales is given.
+ * Every row is validated as mi355vits_run validates its scales; a bad row fails the call with MI355VITS_ERR_INVALID and a
+ * message that names it ("row 3: length_scale must be > 0").
+ * Contract: for any row b the result (lengths, audio, pcm, peaks) is bitwise what mi355vits_run gives for that row alone with
+ * scales = rows->scales[b], pcm_volume = rows->pcm_volume[b] and utterance_base = rows->utterance[b] — in every math mode, as
+ * long as the padded phoneme length tx_max stays in the row's own encoder length class (<= 128 / 256 / 512 / beyond): the
+ * text encoder picks its kernels by tx_max.  Rows with equal settings and keys therefore give equal audio whichever batch,
+ * position or call they ride in. */
+int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                       mi355vits_result* out);
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out);
 void mi355vits_free_result(mi355vits_result* r);
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been

@@ -31,7 +31,7 @@ HOOKS_LIBRARY = os.path.join(_HERE, "csrc", "libmi355vits_hooks.so")
 EXPORTED_SYMBOLS = (
     "mi355vits_version", "mi355vits_device_count", "mi355vits_create", "mi355vits_create_from_buffer", "mi355vits_clone", "mi355vits_destroy",
     "mi355vits_device_result", "mi355vits_set_math", "mi355vits_get_math",
-    "mi355vits_get_config", "mi355vits_run", "mi355vits_fetch", "mi355vits_free_result",
+    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
 )
@@ -63,6 +63,14 @@ class RunArgs(ctypes.Structure):
         ("forced_durations", ctypes.POINTER(ctypes.c_int32)),
         ("flags", ctypes.c_uint32),
         ("pcm_volume", ctypes.c_double),
+    ]
+
+
+class RowArgs(ctypes.Structure):
+    _fields_ = [
+        ("scales", ctypes.POINTER(ctypes.c_float)),
+        ("pcm_volume", ctypes.POINTER(ctypes.c_double)),
+        ("utterance", ctypes.POINTER(ctypes.c_uint64)),
     ]
 
 
@@ -124,6 +132,7 @@ class NativeLibrary:
         L.mi355vits_destroy.restype = None
         L.mi355vits_get_config.argtypes = [H, ctypes.POINTER(CVitsConfig)]
         L.mi355vits_run.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(Result)]
+        L.mi355vits_run_rows.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(Result)]
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
@@ -340,7 +349,10 @@ class Engine:
     # ---- one synthesis call ---------------------------------------------------------------------
     def run(self, ids, lengths, scales, sid=None, *, seed: int = 0, utterance_base: int = 0, noise_w=None,
             noise_z=None, forced_durations=None, want_float: bool = True, want_pcm16: bool = False,
-            device_only: bool = False, debug_taps: bool = False, pcm_volume: float = 1.0) -> Dict[str, np.ndarray]:
+            device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> Dict[str, np.ndarray]:
+        """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
+        ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
+        its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class)."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         if ids.ndim != 2:
             raise ValueError("'input' must have shape [batch, phonemes]")
@@ -348,15 +360,35 @@ class Engine:
         lengths = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
         if lengths.shape[0] != B:
             raise ValueError("'input_lengths' must have shape [batch]")
-        scales = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
-        if scales.shape[0] != 3:
+        scales = np.ascontiguousarray(scales, dtype=np.float32)
+        rows = RowArgs()
+        per_row = False
+        if scales.ndim == 2:
+            if scales.shape != (B, 3):
+                raise ValueError("per-row 'scales' must have shape [batch, 3]")
+            rows.scales, per_row = _fptr(scales), True
+        elif scales.reshape(-1).shape[0] != 3:
             raise ValueError("'scales' must hold [noise_scale, length_scale, noise_w]")
         a = RunArgs()
         keep = [ids, lengths, scales]
         a.batch, a.tx_max = B, Tx
         a.ids = ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         a.lengths = lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        a.scales = _fptr(scales)
+        if not per_row:
+            a.scales = _fptr(scales)
+        if np.ndim(pcm_volume) > 0:
+            vol = np.ascontiguousarray(pcm_volume, dtype=np.float64).reshape(-1)
+            if vol.shape[0] != B:
+                raise ValueError("per-row 'pcm_volume' must have shape [batch]")
+            keep.append(vol)
+            rows.pcm_volume, per_row = vol.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), True
+            pcm_volume = 1.0
+        if utterance_keys is not None:
+            keys = np.array([int(k) & 0xFFFFFFFFFFFFFFFF for k in np.asarray(utterance_keys).reshape(-1).tolist()], np.uint64)
+            if keys.shape[0] != B:
+                raise ValueError("'utterance_keys' must have shape [batch]")
+            keep.append(keys)
+            rows.utterance, per_row = keys.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), True
         if sid is not None:
             sid = np.ascontiguousarray(sid, dtype=np.int64).reshape(-1)
             if sid.shape[0] != B:
@@ -388,7 +420,10 @@ class Engine:
                   (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         a.pcm_volume = float(pcm_volume)
         r = Result()
-        self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
+        if per_row:
+            self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
+        else:
+            self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
         del keep
         return self._take(r)
 

@@ -106,12 +106,17 @@ int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
 }
 
 int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_result* out) {
+    return mi355vits_run_rows(h, args, nullptr, out);
+}
+
+int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                       mi355vits_result* out) {
     if (out) memset(out, 0, sizeof(*out));  // before anything can fail: free_result below must never see garbage
     if (!h) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);
     int rc = guarded(h, [&] {
         if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run(*args, out);
+        h->eng->run(*args, rows, out);
     });
     if (rc != MI355VITS_OK && out) mi355vits_free_result(out);  // never hand back partial audio
     return rc;

@@ -1022,7 +1022,7 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
 
     {
         ProfScope ps(prof_, "sdp.noise");
-        launch_sdp_noise(d_z2_, d_noise_w_, B, Tx, args.scales[2], args.seed, args.utterance_base, stream_);
+        launch_sdp_noise(d_z2_, d_noise_w_, B, Tx, d_scales_, args.seed, d_utt_, stream_);
     }
     int ch0 = 0;  // physical channel that is logical channel 0
     for (int j = c.dp_n_flows - 1; j >= 1; --j) {
@@ -1069,7 +1069,7 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
     {
         ProfScope ps(prof_, "durations");
         // logical channel 0 uses EA parameters [0]
-        launch_durations(d_z2_, ch0, model_->ea_m[0], model_->ea_logs[0], d_len_, d_forced_, B, Tx, args.scales[1], d_logw_, d_wceil_,
+        launch_durations(d_z2_, ch0, model_->ea_m[0], model_->ea_logs[0], d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_,
                          d_cum_, d_ylen_, stream_);
     }
     tap("logw", d_logw_, {B, 1, Tx});
@@ -1086,8 +1086,8 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
     const long zbs = (long)I * Ty, hbs = (long)H * Ty;
     {
         ProfScope ps(prof_, "expand_prior", 0, 4.0 * B * I * Ty * 3);
-        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, args.noise_z_frames, B, I, Tx, Ty, args.scales[0],
-                            args.seed, args.utterance_base, d_z_, stream_);
+        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, args.noise_z_frames, B, I, Tx, Ty, d_scales_,
+                            args.seed, d_utt_, d_z_, stream_);
     }
     tap("z_p", d_z_, {B, I, Ty}, d_ylen_, 1);
 
@@ -1455,12 +1455,14 @@ struct ResultOwner {
 };
 }  // namespace
 
-void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
+void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
     const mi355vits_config& c = cfg_;
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    if (!args.ids || !args.lengths || !args.scales) throw EngineError(MI355VITS_ERR_INVALID, "input, input_lengths and scales are required");
+    const float* row_scales = rows ? rows->scales : nullptr;
+    if (!args.ids || !args.lengths || (!args.scales && !row_scales))
+        throw EngineError(MI355VITS_ERR_INVALID, "input, input_lengths and scales are required");
     const bool multi = c.n_speakers > 1;
     if (multi && !args.sid) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
     const int B = args.batch, Tx = args.tx_max;
@@ -1472,10 +1474,26 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
             throw EngineError(MI355VITS_ERR_INVALID, "phoneme sequence too long: at most " + std::to_string(tx_cap) +
                                                      " ids per utterance (split the text into sentences, as Mimic 3 does)");
     }
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(args.scales[i])) throw EngineError(MI355VITS_ERR_INVALID, "scales must be finite");
-    if (args.scales[0] < 0 || args.scales[2] < 0) throw EngineError(MI355VITS_ERR_INVALID, "noise scales must be >= 0");
-    if (!(args.scales[1] > 0)) throw EngineError(MI355VITS_ERR_INVALID, "length_scale must be > 0");
+    // per-row settings: rows->* where given, else args' value broadcast to every row (row b keyed utterance_base + b)
+    std::vector<float> sc3((size_t)B * 3);
+    std::vector<double> vol(B);
+    std::vector<unsigned long long> utt(B);
+    bool any_noise_z = false;  // some row samples the prior noise (the only case that reads injected noise_z)
+    for (int b = 0; b < B; ++b) {
+        const float* sc = row_scales ? row_scales + (size_t)b * 3 : args.scales;
+        auto bad = [&](const char* what) {  // a per-row message names the row
+            return EngineError(MI355VITS_ERR_INVALID, (row_scales ? "row " + std::to_string(b) + ": " : std::string()) + what);
+        };
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(sc[i])) throw bad("scales must be finite");
+        if (sc[0] < 0 || sc[2] < 0) throw bad("noise scales must be >= 0");
+        if (!(sc[1] > 0)) throw bad("length_scale must be > 0");
+        for (int i = 0; i < 3; ++i) sc3[(size_t)b * 3 + i] = sc[i];
+        any_noise_z = any_noise_z || sc[0] != 0.0f;
+        const double v = (rows && rows->pcm_volume) ? rows->pcm_volume[b] : args.pcm_volume;
+        vol[b] = (v > 0.0) ? v : 1.0;
+        utt[b] = (rows && rows->utterance) ? rows->utterance[b] : args.utterance_base + (unsigned long long)b;
+    }
     std::vector<int> len32(B);
     for (int b = 0; b < B; ++b) {
         if (args.lengths[b] < 0 || args.lengths[b] > Tx) throw EngineError(MI355VITS_ERR_INVALID, "input_lengths out of range");
@@ -1503,6 +1521,7 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
     // ---------------- phase A workspace
     const size_t fBT = (size_t)B * Tx;
     size_t need_a = pad(fBT * 8) + pad((size_t)B * 8) + 6 * pad((size_t)B * 4) + 3 * pad(fBT * 4);
+    need_a += pad((size_t)B * 3 * 4) + 2 * pad((size_t)B * 8);  // per-row scales, volumes, keys
     need_a += 3 * pad(fBT * H * 4) + pad(fBT * 3 * H * 4) + pad(fBT * F * 4) + pad(fBT * 2 * I * 4);  // x,x2,att,qkv,ffn,stats
     need_a += 4 * pad(fBT * H * 4) + pad(fBT * nth * 4) + 2 * pad(fBT * 2 * 4) + pad(fBT * 4);          // h,d0,d1,d2,theta,z2,noise_w,logw
     if (F % 192 == 0 && F / 192 > 1 && H <= 256) need_a += pad(fBT * H * (F / 192) * 4);  // slice sums of the FFN's second conv
@@ -1515,6 +1534,9 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
     d_ids_ = arena_a_.alloc<long long>(fBT);
     d_sid_ = arena_a_.alloc<long long>(B);
     d_len_ = arena_a_.alloc<int>(B);
+    d_scales_ = arena_a_.alloc<float>((size_t)B * 3);
+    d_vol_ = arena_a_.alloc<double>(B);
+    d_utt_ = arena_a_.alloc<unsigned long long>(B);
     d_forced_ = nullptr;
     if (args.forced_durations) d_forced_ = arena_a_.alloc<int>(fBT);
     d_noise_w_ = nullptr;
@@ -1558,6 +1580,9 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
         put(d_ids_, args.ids, fBT * 8);
         put(d_len_, len32.data(), (size_t)B * 4);
         if (multi) put(d_sid_, args.sid, (size_t)B * 8);
+        put(d_scales_, sc3.data(), (size_t)B * 3 * 4);
+        put(d_vol_, vol.data(), (size_t)B * 8);
+        put(d_utt_, utt.data(), (size_t)B * 8);
         if (args.forced_durations) put(d_forced_, args.forced_durations, fBT * 4);
         if (args.noise_w) put(d_noise_w_, args.noise_w, fBT * 2 * 4);
         // h_in_ is a member: it outlives the copy whatever HIP does with pageable sources
@@ -1589,7 +1614,7 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
         if (h_ylen_[b] < 1 || h_ylen_[b] > DURATION_FRAME_CAP) throw EngineError(MI355VITS_ERR_INVALID, "predicted duration out of range (bad weights or length_scale?)");
         Ty = std::max(Ty, h_ylen_[b]);
     }
-    if (args.noise_z && args.scales[0] != 0.0f && args.noise_z_frames < Ty)
+    if (args.noise_z && any_noise_z && args.noise_z_frames < Ty)
         throw EngineError(MI355VITS_ERR_INVALID, "noise_z has fewer frames than the utterance needs");
     if (taps_on_) {
         // w_ceil as floats for the tap interface
@@ -1622,7 +1647,7 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
     }
     const size_t fBTy = (size_t)B * Ty;
     size_t need_b = pad(fBTy * I * 4) + 4 * pad(fBTy * H * 4);
-    if (args.noise_z && args.scales[0] != 0.0f) need_b += pad((size_t)B * I * args.noise_z_frames * 4);
+    if (args.noise_z && any_noise_z) need_b += pad((size_t)B * I * args.noise_z_frames * 4);
     need_b += 4 * pad((size_t)B * max_stage * 4) + pad((size_t)B * L_ * 4) + pad((size_t)B * L_ * 2);
     need_b += pad((size_t)(c.n_upsamples + 2) * B * 4);
     arena_b_.reserve(need_b + 4096, stream_);
@@ -1633,7 +1658,7 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
     d_fskip_ = arena_b_.alloc<float>(fBTy * H);
     d_fu_ = arena_b_.alloc<float>(fBTy * H);
     d_noise_z_ = nullptr;
-    if (args.noise_z && args.scales[0] != 0.0f) {
+    if (args.noise_z && any_noise_z) {
         d_noise_z_ = arena_b_.alloc<float>((size_t)B * I * args.noise_z_frames);
         HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * I * args.noise_z_frames * 4, hipMemcpyHostToDevice, stream_));
     }
@@ -1662,8 +1687,7 @@ void Engine::run(const mi355vits_run_args& args, mi355vits_result* out) {
     have_pcm_ = false;
     if (args.flags & MI355VITS_WANT_PCM16) {
         ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)L_);
-        pcm_volume_ = (args.pcm_volume > 0.0) ? args.pcm_volume : 1.0;
-        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, pcm_volume_);
+        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, d_vol_);
         have_pcm_ = true;
     }
     HIP_CHECK(hipEventRecord(ev_end_, stream_));
@@ -1695,7 +1719,7 @@ void Engine::copy_out(uint32_t want, mi355vits_result* out) {
     }
     if (!dev_only && (want & MI355VITS_WANT_PCM16)) {
         if (!have_pcm_) {
-            launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, 1.0);
+            launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, nullptr);
             have_pcm_ = true;
         }
         own->pcm = PinnedPool::get().take(sizeof(int16_t) * (size_t)B * L_ + 16, &own->pcm_cap);
@@ -1710,7 +1734,7 @@ void Engine::device_buffers(const int16_t** pcm, const float** audio, long* row_
     if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "device_buffers: no completed run on this handle");
     HIP_CHECK(hipSetDevice(device_));
     if (pcm && !have_pcm_) {
-        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B_, (int)L_, d_pcm_, L_, stream_, 1.0);
+        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B_, (int)L_, d_pcm_, L_, stream_, nullptr);
         have_pcm_ = true;
     }
     HIP_CHECK(hipStreamSynchronize(stream_));  // the caller reads them from another stream (RCCL)

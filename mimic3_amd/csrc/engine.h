@@ -129,7 +129,8 @@ class Engine {
     const std::shared_ptr<Model>& model() const { return model_; }
     // device pointers of the last run's results (valid until the next run on this handle); for device-side gathers
     void device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths);
-    void run(const mi355vits_run_args& args, mi355vits_result* out);
+    // rows: per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
+    void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out);
     void fetch(uint32_t want, mi355vits_result* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
@@ -208,9 +209,12 @@ class Engine {
     int B_ = 0, Tx_ = 0, Ty_ = 0;
     long L_ = 0;
     bool have_result_ = false, have_pcm_ = false;
-    double pcm_volume_ = 1.0;
     // phase-A buffers (sized by B, Tx)
     long long *d_ids_ = nullptr, *d_sid_ = nullptr;
+    // per-row settings, uploaded with the inputs: [B,3] noise_scale, length_scale, noise_w; [B] PCM volume; [B] Philox keys
+    float* d_scales_ = nullptr;
+    double* d_vol_ = nullptr;
+    unsigned long long* d_utt_ = nullptr;
     int *d_len_ = nullptr, *d_wceil_ = nullptr, *d_cum_ = nullptr, *d_ylen_ = nullptr, *d_alen_ = nullptr,
         *d_forced_ = nullptr;
     float *d_x_ = nullptr, *d_x2_ = nullptr, *d_qkv_ = nullptr, *d_att_ = nullptr, *d_ffn_ = nullptr, *d_part_ = nullptr,

@@ -201,10 +201,10 @@ void launch_wn_layer_b3(WnArgs a, hipStream_t s);
 void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, int Cin, int K, int B, int L,
                            const int* valid_len, float* audio, long audio_bs, unsigned* peak_bits, hipStream_t s);
 // audio_float_to_int16 per utterance (utils.py:237-244) from the peaks found above.
-// volume != 1: followed by audioop.mul(pcm, 2, volume) (tts.py:542-543): sample * volume in double, clipped to
-// [-32768, 32767], rounded toward minus infinity.
+// volumes [B] (device; NULL = 1 for every row): a row's volume != 1 is followed by audioop.mul(pcm, 2, volume) (tts.py:542-543):
+// sample * volume in double, clipped to [-32768, 32767], rounded toward minus infinity.
 void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, const int* valid_len, int B, int L,
-                  int16_t* pcm, long pcm_bs, hipStream_t s, double volume = 1.0);
+                  int16_t* pcm, long pcm_bs, hipStream_t s, const double* volumes = nullptr);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,
@@ -287,20 +287,21 @@ void launch_convflow_pre(const float* z, int ch, const float* w, const float* bi
 // z[b,1-ch] <- RQS^-1(z[b,1-ch]; theta[b,:,t]) inside the tail bound; then z *= mask     (A.7)
 void launch_spline_inverse(float* z, int ch_x0, const float* theta, const int* len, int B, int T, int nbins,
                            float tail, float inv_sqrt_fc, hipStream_t s);
-// z init: z[b,c,t] = noise * noise_w (Philox or injected)
-void launch_sdp_noise(float* z, const float* injected, int B, int T, float noise_w, unsigned long long seed,
-                      unsigned long long utt_base, hipStream_t s);
+// per-row synthesis settings, device arrays: scales [B,3] = noise_scale, length_scale, noise_w; utt [B] = Philox utterance index
+// z init: z[b,c,t] = noise * noise_w[b] (Philox under key utt[b], or injected)
+void launch_sdp_noise(float* z, const float* injected, int B, int T, const float* scales, unsigned long long seed,
+                      const unsigned long long* utt, hipStream_t s);
 // most latent frames one utterance may have (4.2 M frames = 13.5 h of audio); larger / non-finite predictions are an error
 constexpr int DURATION_FRAME_CAP = 1 << 22;
-// EA^-1 on channel `ch` -> logw; durations: w = ceil(exp(logw)*mask*ls) (or forced); cum = inclusive scan;
+// EA^-1 on channel `ch` -> logw; durations: w = ceil(exp(logw)*mask*ls[b]) (or forced); cum = inclusive scan;
 // ylen = max(1, sum)
 void launch_durations(const float* z, int ch, float ea_m, float ea_logs, const int* len, const int* forced, int B,
-                      int T, float length_scale, float* logw, int* w_ceil, int* cum, int* ylen, hipStream_t s);
+                      int T, const float* scales, float* logw, int* w_ceil, int* cum, int* ylen, hipStream_t s);
 
 // ---------------------------------------------------------------- length regulator + prior sampling (K6, K7)
 void launch_expand_prior(const float* stats /*[B,2I,Tx]: m_p | logs_p*/, const int* cum, const int* ylen,
                          const float* injected, int injected_frames, int B, int I, int Tx, int Ty,
-                         float noise_scale, unsigned long long seed, unsigned long long utt_base, float* z,
+                         const float* scales, unsigned long long seed, const unsigned long long* utt, float* z,
                          hipStream_t s);
 
 // ---------------------------------------------------------------- speaker conditioning (A.11)

@@ -2302,10 +2302,11 @@ void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, 
 }
 
 // audio_float_to_int16 (mimic3_tts/utils.py:237-244) per utterance: scale = 32767 / max(0.01, peak),
-// clip to +-32767, truncate toward zero.  Rows are zero beyond their valid length.
+// clip to +-32767, truncate toward zero.  Rows are zero beyond their valid length.  volume: [B] or NULL (1 for every row).
 __global__ __launch_bounds__(256) void k_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits,
-                                               const int* valid_len, int L, int16_t* pcm, long pcm_bs, double volume) {
+                                               const int* valid_len, int L, int16_t* pcm, long pcm_bs, const double* volumes) {
     const int b = blockIdx.y;
+    const double volume = volumes ? volumes[b] : 1.0;
     const float peak = fmaxf(0.01f, __uint_as_float(peak_bits[b]));
     const float scale = 32767.0f / peak;
     const int vl = valid_len ? valid_len[b] : L;
@@ -2328,11 +2329,11 @@ __global__ __launch_bounds__(256) void k_pcm16(const float* audio, long audio_bs
 }
 
 void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, const int* valid_len, int B, int L,
-                  int16_t* pcm, long pcm_bs, hipStream_t s, double volume) {
+                  int16_t* pcm, long pcm_bs, hipStream_t s, const double* volumes) {
     if (L <= 0 || B <= 0) return;
     int gx = (L + 255) / 256;
     if (gx > 2048) gx = 2048;
-    LAUNCH_KERNEL(k_pcm16, dim3(gx, B), dim3(256), 0, s, audio, audio_bs, peak_bits, valid_len, L, pcm, pcm_bs, volume);
+    LAUNCH_KERNEL(k_pcm16, dim3(gx, B), dim3(256), 0, s, audio, audio_bs, peak_bits, valid_len, L, pcm, pcm_bs, volumes);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1311,29 +1311,31 @@ void launch_dds_stack(const DdsStackArgs& a, int C, hipStream_t s) {
     LAUNCH_KERNEL(kfn, grid, dim3(64 * 6), sh, s, av);
 }
 
-__global__ __launch_bounds__(64) void k_sdp_noise(float* z, const float* injected, int T, float noise_w,
-                                                  unsigned long long seed, unsigned long long utt_base) {
+__global__ __launch_bounds__(64) void k_sdp_noise(float* z, const float* injected, int T, const float* scales,
+                                                  unsigned long long seed, const unsigned long long* utt) {
     const int b = blockIdx.y;
     const int t = blockIdx.x * 64 + threadIdx.x;
     if (t >= T) return;
+    const float noise_w = scales[(long)b * 3 + 2];
     for (int c = 0; c < 2; ++c) {
         const long o = ((long)b * 2 + c) * T + t;
         float n = 0.0f;
-        if (noise_w != 0.0f) n = injected ? injected[o] : philox_normal(seed, utt_base + b, 0u, (unsigned)c, (unsigned)t);
+        if (noise_w != 0.0f) n = injected ? injected[o] : philox_normal(seed, utt[b], 0u, (unsigned)c, (unsigned)t);
         z[o] = n * noise_w;
     }
 }
-void launch_sdp_noise(float* z, const float* injected, int B, int T, float noise_w, unsigned long long seed,
-                      unsigned long long utt_base, hipStream_t s) {
-    LAUNCH_KERNEL(k_sdp_noise, dim3((T + 63) / 64, B), dim3(64), 0, s, z, injected, T, noise_w, seed, utt_base);
+void launch_sdp_noise(float* z, const float* injected, int B, int T, const float* scales, unsigned long long seed,
+                      const unsigned long long* utt, hipStream_t s) {
+    LAUNCH_KERNEL(k_sdp_noise, dim3((T + 63) / 64, B), dim3(64), 0, s, z, injected, T, scales, seed, utt);
 }
 
 // EA^-1 (HF:703) on the logical channel 0, then K6: w = ceil(exp(logw) * mask * length_scale), inclusive scan.
 __global__ __launch_bounds__(256) void k_durations(const float* z, int ch, float ea_m, float ea_logs, const int* len,
-                                                   const int* forced, int T, float length_scale, float* logw,
+                                                   const int* forced, int T, const float* scales, float* logw,
                                                    int* w_ceil, int* cum, int* ylen) {
     const int b = blockIdx.x;
     const int L = len[b];
+    const float length_scale = scales[(long)b * 3 + 1];
     const float es = expf(-ea_logs);
     for (int t = threadIdx.x; t < T; t += 256) {
         const float m = t < L ? 1.0f : 0.0f;
@@ -1361,8 +1363,8 @@ __global__ __launch_bounds__(256) void k_durations(const float* z, int ch, float
     }
 }
 void launch_durations(const float* z, int ch, float ea_m, float ea_logs, const int* len, const int* forced, int B,
-                      int T, float length_scale, float* logw, int* w_ceil, int* cum, int* ylen, hipStream_t s) {
-    LAUNCH_KERNEL(k_durations, dim3(B), dim3(256), 0, s, z, ch, ea_m, ea_logs, len, forced, T, length_scale, logw,
+                      int T, const float* scales, float* logw, int* w_ceil, int* cum, int* ylen, hipStream_t s) {
+    LAUNCH_KERNEL(k_durations, dim3(B), dim3(256), 0, s, z, ch, ea_m, ea_logs, len, forced, T, scales, logw,
                   w_ceil, cum, ylen);
 }
 
@@ -1372,8 +1374,8 @@ void launch_durations(const float* z, int ch, float ea_m, float ea_logs, const i
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_expand_prior(const float* stats, const int* cum, const int* ylen,
                                                       const float* injected, int injected_frames, int I, int Tx,
-                                                      int Ty, float noise_scale, unsigned long long seed,
-                                                      unsigned long long utt_base, float* z) {
+                                                      int Ty, const float* scales, unsigned long long seed,
+                                                      const unsigned long long* utt, float* z) {
     const int b = blockIdx.y;
     const int t = blockIdx.x * 64 + (threadIdx.x & 63);
     const int cg = threadIdx.x >> 6;
@@ -1386,6 +1388,7 @@ __global__ __launch_bounds__(256) void k_expand_prior(const float* stats, const 
     }
     const int j = lo;
     const bool valid = t < ylen[b] && j < Tx;
+    const float noise_scale = scales[(long)b * 3];
     for (int c = cg; c < I; c += 4) {
         float v = 0.0f;
         if (valid) {
@@ -1394,7 +1397,7 @@ __global__ __launch_bounds__(256) void k_expand_prior(const float* stats, const 
             if (noise_scale != 0.0f) {
                 const float ls = stats[((long)b * 2 * I + I + c) * Tx + j];
                 const float n = injected ? injected[((long)b * I + c) * injected_frames + t]
-                                         : philox_normal(seed, utt_base + b, 1u, (unsigned)c, (unsigned)t);
+                                         : philox_normal(seed, utt[b], 1u, (unsigned)c, (unsigned)t);
                 v = m + n * expf(ls) * noise_scale;
             }
         }
@@ -1402,10 +1405,10 @@ __global__ __launch_bounds__(256) void k_expand_prior(const float* stats, const 
     }
 }
 void launch_expand_prior(const float* stats, const int* cum, const int* ylen, const float* injected,
-                         int injected_frames, int B, int I, int Tx, int Ty, float noise_scale, unsigned long long seed,
-                         unsigned long long utt_base, float* z, hipStream_t s) {
+                         int injected_frames, int B, int I, int Tx, int Ty, const float* scales, unsigned long long seed,
+                         const unsigned long long* utt, float* z, hipStream_t s) {
     LAUNCH_KERNEL(k_expand_prior, dim3((Ty + 63) / 64, B), dim3(256), 0, s, stats, cum, ylen, injected, injected_frames,
-                  I, Tx, Ty, noise_scale, seed, utt_base, z);
+                  I, Tx, Ty, scales, seed, utt, z);
 }
 
 // ------------------------------------------------------------------------------------------------

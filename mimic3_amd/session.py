@@ -268,6 +268,10 @@ class _LanePool:
             return len(self._free)
 
 
+# run keywords that may differ between the rows of one engine call (mi355vits_run_rows)
+_ROW_SETTINGS = ("pcm_volume", "utterance_keys")
+
+
 class _MicroBatcher:
     """Coalesces concurrent B = 1 requests into batched engine calls (one dispatcher thread per session).
 
@@ -361,14 +365,16 @@ class _MicroBatcher:
                             self._inflight_cv.wait(timeout=0.0002)
             while len(items) < self._max and not stop and take(0):  # whatever arrived meanwhile rides along
                 pass
-            # only requests with identical scales / output kind can share a call (the ABI takes one `scales`); and only
-            # requests of the same phoneme-length class: the text encoder picks its attention / FFN kernels by the padded
-            # length (<= 128, 256, 512, beyond), so within a class a row gets the kernels — and the bits — it would get alone
+            # scales, PCM volume and noise key are per row (mi355vits_run_rows), so requests with any settings share a call; only
+            # the output kind and sid presence must agree, and the phoneme-length class: the text encoder picks its attention /
+            # FFN kernels by the padded length (<= 128, 256, 512, beyond), so within a class a row gets the kernels — and the
+            # bits — it would get alone
             groups: Dict[Any, list] = {}
             for it in items:
                 n = int(it[1][0])
                 bucket = 0 if n <= 128 else (1 if n <= 256 else (2 if n <= 512 else 3))
-                key = (tuple(np.asarray(it[2], np.float32).tolist()), it[3] is None, tuple(sorted(it[4].items())), bucket)
+                kind = tuple(sorted((k, v) for k, v in it[4].items() if k not in _ROW_SETTINGS))
+                key = (it[3] is None, kind, bucket)
                 groups.setdefault(key, []).append(it)
             for group in groups.values():
                 with self._inflight_cv:
@@ -404,11 +410,27 @@ class _MicroBatcher:
                 ids[b, :n] = g[0][0, :n]
                 lens[b] = n
             sid = None if group[0][3] is None else np.array([int(g[3][0]) for g in group], np.int64)
-            kw = dict(group[0][4])
+            kw = {k: v for k, v in group[0][4].items() if k not in _ROW_SETTINGS}
+            scales = group[0][2]
+            if B > 1:
+                # per-row arrays only where the rows differ: a uniform batch takes the plain call, as before
+                rows = np.stack([np.asarray(g[2], np.float32).reshape(3) for g in group])
+                if (rows != rows[0]).any():
+                    scales = rows
+                vols = [float(np.asarray(g[4].get("pcm_volume", 1.0), np.float64).reshape(-1)[0]) for g in group]
+                if any(v != vols[0] for v in vols):
+                    kw["pcm_volume"] = np.asarray(vols, np.float64)
+                elif "pcm_volume" in group[0][4]:
+                    kw["pcm_volume"] = vols[0]
+                keys = [g[4]["utterance_keys"][0] if g[4].get("utterance_keys") is not None else None for g in group]
+                if any(k is not None for k in keys):
+                    kw["utterance_keys"] = keys  # rows without a key of their own get base + b (_engine_run)
+            else:
+                kw = dict(group[0][4])
             session = self._session_ref()
             if session is None:
                 raise RuntimeError("session closed")
-            out = session._engine_run(ids, lens, group[0][2], sid, **kw)
+            out = session._engine_run(ids, lens, scales, sid, **kw)
             del session  # (the batch stays "in flight" through the slicing below: handing the next batch out earlier was measured —
             # 19.1k -> 16.9k x real time at 64 clients, the batches shrink from 15.5 to 12.2: profiles/r06_serve_policies.txt)
             with self._count_lock:
@@ -536,20 +558,31 @@ class InferenceSession:
         return [audio[:, None, :]]
 
     # ---- engine extensions --------------------------------------------------------------------
-    def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume: Optional[float] = None, direct: bool = False
+    def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None
                   ) -> Tuple[List[np.ndarray], np.ndarray]:
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
         ``volume`` (percent, like ``Mimic3Settings.volume``): additionally applies
         ``audioop.mul(audio_bytes, 2, volume / 100)`` (``tts.py:542-543``) in the same kernel — same bytes as the host
-        call, one pass fewer over the audio.  ``direct``: a single-utterance call goes straight to a lane instead
-        of through the micro-batcher's queue (a planned request's first sentence: two thread hand-overs fewer; same bits)."""
-        kw = {}
-        if volume is not None and float(volume) != 100.0:
+        call, one pass fewer over the audio.  A sequence gives each row its own volume.  ``direct``: a
+        single-utterance call goes straight to a lane instead of through the micro-batcher's queue (a planned request's first
+        sentence: two thread hand-overs fewer; same bits).  ``utterance_keys`` ([B] ints): the Philox utterance index of each
+        row instead of the session's running count (``reserve_utterances``) — a row's noise, hence its audio at nonzero
+        noise scales, then depends on its own inputs only, not on the batch or the moment it rides in."""
+        kw: Dict[str, Any] = {}
+        if volume is not None and np.ndim(volume) > 0:
+            vols = [float(v) for v in np.asarray(volume, np.float64).reshape(-1)]
+            if not all(v > 0.0 for v in vols):
+                raise InvalidArgument("volume must be > 0 (percent)")
+            if any(v != 100.0 for v in vols):
+                kw["pcm_volume"] = np.asarray([v / 100.0 for v in vols], np.float64)
+        elif volume is not None and float(volume) != 100.0:
             if not float(volume) > 0.0:
                 raise InvalidArgument("volume must be > 0 (percent)")
             kw["pcm_volume"] = float(volume) / 100.0
+        if utterance_keys is not None:
+            kw["utterance_keys"] = [int(k) for k in np.asarray(utterance_keys).reshape(-1).tolist()]
         out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
         return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
 
@@ -580,15 +613,26 @@ class InferenceSession:
         self.last_lengths = out["lengths"]
         return out
 
-    def _engine_run(self, ids, lengths, scales, sid, **kw) -> Dict[str, np.ndarray]:
-        if self._closed:
-            raise RuntimeError("session is closed")
+    def reserve_utterances(self, n: int) -> int:
+        """Reserve ``n`` consecutive Philox utterance indices of this session; returns the first.  Calls without
+        ``utterance_keys`` draw theirs from the same count, so reserved keys are never reused by them."""
         with self._lock:
             base = self._utterances
-            self._utterances += ids.shape[0]
+            self._utterances += int(n)
+        return base
+
+    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, **kw) -> Dict[str, np.ndarray]:
+        if self._closed:
+            raise RuntimeError("session is closed")
+        keys = None if utterance_keys is None else list(utterance_keys)
+        base = 0
+        if keys is None or any(k is None for k in keys):
+            base = self.reserve_utterances(ids.shape[0])
+            if keys is not None:
+                keys = [base + b if k is None else int(k) for b, k in enumerate(keys)]
         eng = self._free_lanes.acquire()  # blocks while every lane is busy; first come first served
         try:
-            return eng.run(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, **kw)
+            return eng.run(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
         except _native.NativeError as e:
             if e.code == -1:
                 raise InvalidArgument(str(e)) from None

@@ -45,7 +45,10 @@ def shard_feed(feed: Dict[str, np.ndarray], world_size: int, rank: int, balance:
     else:
         lo, hi = shard_bounds(B, world_size, rank)
         rows = np.arange(lo, hi, dtype=np.int64)
-    out = {"input": ids[rows], "input_lengths": np.asarray(feed["input_lengths"])[rows], "scales": feed["scales"]}
+    scales = feed["scales"]
+    if np.ndim(scales) == 2:  # per-row scales [B, 3] (engine extension): this rank's rows
+        scales = np.asarray(scales)[rows]
+    out = {"input": ids[rows], "input_lengths": np.asarray(feed["input_lengths"])[rows], "scales": scales}
     if "sid" in feed:
         out["sid"] = np.asarray(feed["sid"])[rows]
     return out, rows

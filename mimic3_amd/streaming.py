@@ -93,16 +93,25 @@ def _batch_feed(rows: Sequence[Sequence[int]], scales, sid: Optional[int]) -> Di
     return feed
 
 
+def _keys(base: Optional[int], idx: Sequence[int]) -> dict:
+    """``run_pcm16`` keywords that key sentence i's noise ``base + i`` (none without a base: a session-like object without keys)."""
+    return {} if base is None else {"utterance_keys": [base + i for i in idx]}
+
+
 def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1.0, 0.8), sid: Optional[int] = None,
                    volume: Optional[float] = None, head: int = 0, max_batch: int = 48, workers: int = 4,
-                   stats: Optional[dict] = None, first_alone: bool = True) -> Iterator[np.ndarray]:
+                   stats: Optional[dict] = None, first_alone: bool = True, utterance_base: Optional[int] = None
+                   ) -> Iterator[np.ndarray]:
     """``stream_sentences`` for a request whose sentence list is known up front ("look-ahead batching of all
     Mimic3Phonemes pending in one end_utterance"): the batches of ``plan_batches`` are issued as BATCHED engine calls on the
     session's lanes (no arrival window, no per-sentence thread), the chunks are yielded in sentence order as their batches
-    finish.  A batched row is bitwise its single call (same phoneme-length class), so the stream's bytes do not depend on the
-    plan.  ``first_alone``: sentence 0 has the device to itself — the other batches are issued when its audio is in the caller's
-    hands (issued together, a 40-row batch's kernels fill the chip and the single sentence takes 6 ms instead of 2:
-    profiles/r06_serve_bench.log).  ``stats`` (optional dict) receives ``batches``, ``padding_efficiency`` = valid / computed
+    finish.  Sentence i's noise is keyed ``utterance_base + i`` wherever it runs (without ``utterance_base`` the stream reserves
+    ``len(sentences)`` keys of the session up front), and a batched row is bitwise its single call (same phoneme-length class), so
+    the stream's bytes depend neither on the plan nor on thread timing: for a given ``utterance_base`` they are the chunks of
+    ``stream_sentences`` on a lazy iterable and of one ``run_pcm16(..., utterance_keys=[utterance_base + i])`` per sentence, and
+    at deterministic scales (both noise scales 0) always.  ``first_alone``: sentence 0 has the device to itself — the other
+    batches are issued when its audio is in the caller's hands (issued together, a 40-row batch's kernels fill the chip and the
+    single sentence takes 6 ms instead of 2: profiles/r06_serve_bench.log).  ``stats`` (optional dict) receives ``batches``, ``padding_efficiency`` = valid / computed
     output samples (a batch computes every row up to its longest) and ``text_padding_efficiency`` (the same for phoneme positions).
 
     A failing sentence: its batch is retried row by row, the error surfaces at that sentence's turn, later ones are not
@@ -110,6 +119,9 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
     sentences = list(sentences)  # (shallow: the rows are read when their batch's feed is built)
     if not sentences:
         return
+    if utterance_base is None and hasattr(session, "reserve_utterances"):
+        utterance_base = session.reserve_utterances(len(sentences))
+    base = utterance_base
     pool = ThreadPoolExecutor(max_workers=max(1, workers), thread_name_prefix="mi355vits-plan")
     done: Dict[int, object] = {}
     valid = computed = tvalid = tcomputed = 0
@@ -120,7 +132,7 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
 
     def run_batch(idx):
         try:
-            rows, lengths = session.run_pcm16(_batch_feed([sentences[i] for i in idx], scales, sid), volume=volume)
+            rows, lengths = session.run_pcm16(_batch_feed([sentences[i] for i in idx], scales, sid), volume=volume, **_keys(base, idx))
             return list(rows), np.asarray(lengths)  # (views of the call's own pinned result buffer, which they keep alive)
         except Exception:
             if len(idx) == 1:
@@ -128,7 +140,7 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
             out = []  # a bad row must not take its batch-mates with it: one call per row, each with its own outcome
             for i in idx:
                 try:
-                    out.append(session.run_pcm16(_feed(sentences[i], scales, sid), volume=volume)[0][0])
+                    out.append(session.run_pcm16(_feed(sentences[i], scales, sid), volume=volume, **_keys(base, [i]))[0][0])
                 except Exception as e:  # noqa: BLE001 - delivered at the sentence's turn
                     out.append(e)
             return out, None
@@ -143,9 +155,9 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
         f0: Future = Future()
         try:
             try:
-                r0 = session.run_pcm16(_feed(sentences[0], scales, sid), volume=volume, direct=True)
+                r0 = session.run_pcm16(_feed(sentences[0], scales, sid), volume=volume, direct=True, **_keys(base, [0]))
             except TypeError:  # a session-like object without the `direct` extension
-                r0 = session.run_pcm16(_feed(sentences[0], scales, sid), volume=volume)
+                r0 = session.run_pcm16(_feed(sentences[0], scales, sid), volume=volume, **_keys(base, [0]))
             f0.set_result((list(r0[0]), None))
         except Exception as e:  # noqa: BLE001 - raised at the sentence's turn below
             f0.set_exception(e)
@@ -187,13 +199,17 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
 
 def stream_sentences(session, sentences: Iterable[Sequence[int]], scales=(0.667, 1.0, 0.8), sid: Optional[int] = None,
                      volume: Optional[float] = None, look_ahead: int = 8, plan: Optional[bool] = None,
-                     stats: Optional[dict] = None) -> Iterator[np.ndarray]:
+                     stats: Optional[dict] = None, utterance_base: Optional[int] = None) -> Iterator[np.ndarray]:
     """Yield the int16 audio of each sentence (a sequence of phoneme ids, the boundary the reference crosses at
     ``voice.py:180``) in order, keeping up to ``look_ahead`` sentences in flight on ``session``.
 
     ``plan``: a request that arrives as a list / tuple is planned (``stream_planned``: sentence 0 alone, then length-sorted
     batches cut from the whole list); a lazy iterable is consumed ``look_ahead`` sentences
-    ahead of the consumer, one call per sentence, and batching is left to the session's micro-batcher.  Same chunks either way.
+    ahead of the consumer, one call per sentence, and batching is left to the session's micro-batcher.
+
+    Sentence i's noise is keyed ``utterance_base + i`` in either mode.  Without ``utterance_base`` a planned stream reserves
+    ``len(sentences)`` keys of the session up front, a lazy one reserves one key per sentence as it submits it (sentence order).
+    So the chunks are identical across modes for a given ``utterance_base``, and at deterministic scales always.
 
     An exception of a sentence surfaces when its turn comes (like the reference, which raises at the failing sentence);
     sentences after it are cancelled or drained, never yielded."""
@@ -203,8 +219,11 @@ def stream_sentences(session, sentences: Iterable[Sequence[int]], scales=(0.667,
         plan = isinstance(sentences, (list, tuple))
     if plan:
         lanes = len(getattr(session, "_engines", [None]))
-        yield from stream_planned(session, list(sentences), scales=scales, sid=sid, volume=volume, workers=max(2, lanes + 1), stats=stats)
+        yield from stream_planned(session, list(sentences), scales=scales, sid=sid, volume=volume, workers=max(2, lanes + 1), stats=stats,
+                                  utterance_base=utterance_base)
         return
+    reserve = getattr(session, "reserve_utterances", None)
+    count = [0]
     it = iter(sentences)
     pool = ThreadPoolExecutor(max_workers=look_ahead, thread_name_prefix="mi355vits-stream")
     pending = []
@@ -214,7 +233,11 @@ def stream_sentences(session, sentences: Iterable[Sequence[int]], scales=(0.667,
             ids = next(it)
         except StopIteration:
             return False
-        pending.append(pool.submit(lambda f=_feed(ids, scales, sid): session.run_pcm16(f, volume=volume)[0][0]))
+        i = count[0]
+        count[0] += 1
+        base = utterance_base + i if utterance_base is not None else (reserve(1) if reserve is not None else None)
+        kw = _keys(base, [0])
+        pending.append(pool.submit(lambda f=_feed(ids, scales, sid), kw=kw: session.run_pcm16(f, volume=volume, **kw)[0][0]))
         return True
 
     try:

@@ -11,7 +11,12 @@ other workers (mimic3_tts/voice.py:277-292, mimic3_http/synthesis.py:88-136) —
 and, with STREAM=1, a long-form request (BASELINE.json configs[4]: ~10k characters = 120 sentences) delivered as a chunked
 stream (mimic3_amd.streaming): time to first audio and total time vs synthesising everything before answering.
 
-Prints one JSON line per mode: sentences/s, audio seconds per second, latency percentiles.  Run on the GPU box.
+MIXED=K gives client k the synthesis settings k mod K out of eight (length_scale 1.0, 0.8, 1.2, 1.5 x noise_scale 0.667, 0.5;
+noise_w 0.8; MIXED=1, the default, is every client on 0.667 / 1.0 / 0.8): per-request settings as mimic3_http receives them, which
+the micro-batcher merges into one call (mi355vits_run_rows).
+
+Prints one JSON line per mode: sentences/s, audio seconds per second, latency percentiles, engine calls (`batches`) and the
+requests they carried.  Run on the GPU box.
 MI355VITS_DEVICES=all spreads every session over all visible GPUs (in-process device round-robin).
 """
 import json
@@ -33,6 +38,10 @@ from mimic3_amd.session import InferenceSession, SessionOptions  # noqa: E402
 def main():
     clients = int(os.environ.get("CLIENTS", "64"))
     seconds = float(os.environ.get("SECONDS", "4"))
+    mixed = max(1, int(os.environ.get("MIXED", "1")))
+    settings = [np.array([ns, ls, 0.8], np.float32) for ls in (1.0, 0.8, 1.2, 1.5) for ns in (0.667, 0.5)]
+    if mixed > len(settings):
+        raise SystemExit(f"MIXED must be <= {len(settings)}")
     cfg = VitsConfig.apope_low()
     blob = W.pack(cfg, W.synthetic_weights(cfg, seed=1234, frames_per_id=6.0))
     rng = np.random.default_rng(0)
@@ -66,7 +75,10 @@ def main():
             mine, n = [], 0
             while time.perf_counter() < stop:
                 t0 = time.perf_counter()
-                rows, lengths = sess.run_pcm16(feeds[i % len(feeds)])
+                f = feeds[i % len(feeds)]
+                if mixed > 1:
+                    f = dict(f, scales=settings[k % mixed])
+                rows, lengths = sess.run_pcm16(f)
                 mine.append(time.perf_counter() - t0)
                 n += int(lengths[0])
                 i += clients
@@ -80,11 +92,12 @@ def main():
         [t.join() for t in ts]
         wall = time.perf_counter() - t0
         lat_ms = np.sort(np.array(lat)) * 1e3
-        out = {"mode": name, "clients": clients, "lanes": lanes, "micro_batch_window_ms": window, "sentences_per_s": len(lat) / wall,
+        out = {"mode": name, "clients": clients, "mixed": mixed, "lanes": lanes, "micro_batch_window_ms": window, "sentences_per_s": len(lat) / wall,
                "audio_s_per_s": samples[0] / 22050 / wall, "latency_ms_p50": float(lat_ms[len(lat_ms) // 2]),
                "latency_ms_p95": float(lat_ms[int(0.95 * len(lat_ms))]), "latency_ms_max": float(lat_ms[-1])}
         if sess._batcher is not None:
             out["mean_batch"] = sess._batcher.requests / max(1, sess._batcher.batches)
+            out["batches"], out["requests"] = sess._batcher.batches, sess._batcher.requests
         print(json.dumps(out), flush=True)
         sess.close()
     if os.environ.get("STREAM"):
