@@ -7,6 +7,7 @@ own timed region, mimic3_tts/voice.py:229-232).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (what the driver launches for N > 1)
     python bench.py --gpus N --single-process        # one process, N devices (the unchanged mimic3-server's shape)
     python bench.py ... --dump-outputs DIR           # also write what the last timed step returned as DIR/*.npy (dump_outputs)
+    python bench.py ... --full                       # also every leg beyond the headline (below); the --no-* switches drop single legs
 
 A "step" is one pass of the hot path over the job's batch of synthetic phoneme ids.  Workload: BASELINE.json's
 batch of 256 independent utterances of 128 phoneme ids, durations forced to 6 frames/id -> 768 latent frames =
@@ -17,12 +18,17 @@ one GPU at ``--gpus 1`` (the configuration the metric names; ``value`` IS the ba
 
 Timed region = what the reference times around ``run`` + int16: phoneme ids start in host memory (1 KiB per
 utterance), the int16 result ENDS in host memory (pinned buffers recycled by the library, D2H inside the
-region): ``value`` is host-to-host.  ``device_only`` in the JSON is the same loop with the int16 result left
-in HBM (compute-side number).  Batch-1 latency / RTF on the reference's golden-utterance shape (180 ids ->
-991 frames) is measured in the same run ("latency_b1"), and BASELINE.json configs[2] (en_US/vctk_low,
-32 x 128 ids, sid = b mod 109) as "vctk_low_b32" with its own roofline.
+region): ``value`` is host-to-host.
 
-The JSON line also carries
+A plain run does only what the headline needs: set-up, an untimed pre-heat, the warm-up, the timed steps, --dump-outputs, and
+the JSON line with the headline figures (value, ms_per_step, rtf, b256_ms at batch 256, ...), their "config" and
+  "device"       — (after an untimed pre-heat of the same steps until the shader clock is steady: "device.preheat")
+                   shader / memory / fabric clocks, socket power and cap, partition modes of the HIP device from sysfs, sampled
+                   every 10 ms over the timed loop (with --full also over the per-kernel table); a one-line summary of it sits
+                   in "config".
+--full measures everything else in the same process after the headline, and the line also carries
+  "device_only"  — the headline loop with the int16 result left in HBM (compute-side number)
+  "latency_b1"   — batch-1 latency / RTF on the reference's golden-utterance shape (180 ids -> 991 frames)
   "roofline"     — dominant kernel group, algorithmic FLOPs / launch time measured with HIP events on the
                    engine's stream (mi355vits_profile_*), against the matrix-core peak of its path, plus HBM numbers;
                    "traffic" = HBM bytes per launch MEASURED IN THIS RUN by two counters-only rocprofv3 passes of a
@@ -30,18 +36,16 @@ The JSON line also carries
   "host_ms_per_step" — one handle driven sequentially: call wall time vs device time
   "cpu_baseline" — the PyTorch-CPU oracle (onnxruntime is not installed here) timed on this host's cores on
                    a bounded sample of the same workload (rank 0, N = 1 only), with the engine checked against it
-  first level    — the metric's other configurations as NUMBERS: latency_b1_ms / b1_x_realtime / b1_launches (configs[1]), b256_ms,
+  first level    — the metric's other configurations as NUMBERS: latency_b1_ms / b1_x_realtime / b1_launches (configs[1]),
                    b32_ms / b32_samples_per_s (the 32-row shard of the eight-GPU run on this one device), longform_first_audio_ms /
                    longform_total_ms / longform_padding_efficiency (configs[4]), serve64_* / ragged_b1_calls_x_realtime (the reference's real
                    call shape: one ragged sentence per call), probe_* (the box probe: L2-hit stream GB/s, L2-hit latency, HBM copy GB/s)
-  "extra"        — vctk_low b32 (configs[2]), the 32-row shard on ONE GPU with its kernel table, long-form streaming (configs[4]:
-                   120 sentences through mimic3_amd.streaming on one session, default math and bf16 weights), the f32-MFMA /
-                   bf16-weights / f16x2 math modes; they run after the headline's handles are closed (open idle handles alias
-                   HIP streams onto shared hardware queues: tools/floor_diag2.py).
-  "device"       — (after an untimed pre-heat of the same steps until the shader clock is steady: "device.preheat")
-                   shader / memory / fabric clocks, socket power and cap, partition modes of the HIP device from sysfs, sampled
-                   every 10 ms over the timed loop and over the per-kernel table; one-line summaries of it, of the batch-1
-                   latency, the batch-256 leg and the streaming leg sit in "config" (the driver's record keeps that object).
+  "extra"        — vctk_low b32 (configs[2]: 32 x 128 ids, sid = b mod 109, with its own roofline), the 32-row shard on ONE GPU
+                   with its kernel table, long-form streaming (configs[4]: 120 sentences through mimic3_amd.streaming on one
+                   session, default math and bf16 weights), the f32-MFMA / bf16-weights / f16x2 math modes; they run after the
+                   headline's handles are closed (open idle handles alias HIP streams onto shared hardware queues:
+                   tools/floor_diag2.py).  One-line summaries of the batch-1 latency, the other batch's leg, the serving shape
+                   and the streaming leg sit in "config".
 """
 from __future__ import annotations
 
@@ -478,13 +482,18 @@ def main():
                     help="engine handles (HIP streams) kept in flight per GPU; steps are dealt to them in turn")
     ap.add_argument("--single-process", action="store_true",
                     help="drive all --gpus devices from this one process (threads), no torch.distributed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-b1", action="store_true", help="skip the batch-1 latency leg (profiling runs: keeps per-kernel "
-                    "averages pure batch-32)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the device-only and vctk_low legs")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 counter passes that measure roofline.traffic")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="wall budget of the CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: box probe, host-side split, device-only loop, batch-1 "
+                         "latency, per-kernel tables and roofline, CPU baseline, extra configurations and math modes (without it "
+                         "a run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel tables and the roofline")
+    ap.add_argument("--no-b1", action="store_true", help="with --full: skip the batch-1 latency leg (profiling runs: keeps "
+                    "per-kernel averages pure batch-32)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the device-only and extra-configuration legs")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 counter passes that measure "
+                    "roofline.traffic")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="wall budget of the CPU-baseline sample (--full)")
     ap.add_argument("--no-preheat", action="store_true",
                     help="skip the untimed pre-heat steps in front of the warm-up (rounds 1-3 and the driver's BENCH_r01-r03 were "
                          "measured without them; the JSON says which protocol ran: device.preheat)")
@@ -492,7 +501,8 @@ def main():
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
                          "(float32 / float64, at most 64 MB in all): the outputs of two builds can then be compared")
     ap.add_argument("--kernel-tables", metavar="DIR", default=None,
-                    help="write the per-kernel HIP-event tables as DIR/bench_kernels*.json (they are printed to stderr either way)")
+                    help="with --full: write the per-kernel HIP-event tables as DIR/bench_kernels*.json (they are printed to "
+                         "stderr either way)")
     args = ap.parse_args()
 
     import torch
@@ -593,7 +603,7 @@ def main():
     t_ph = time.perf_counter()
     hist = []
     box_probe = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:  # ~10 ms: what this lease's chip gives the kernels' access patterns (include/mi355vits_lab.h mi355vits_probe_device;
             # the hooks live in libmi355vits_hooks.so = the product's objects + csrc/lab_api.cpp, never in the timed path)
             from mimic3_amd._native import Engine as _Engine, hooks_library
@@ -693,6 +703,7 @@ def main():
 
     if rank == 0:
         print(f"headline: {value:.4g} samples/s, {ms_per_step:.3f} ms/step over {elapsed:.2f} s (host-to-host)", file=sys.stderr)
+    if rank == 0 and args.full:
         # where a step's wall time goes on ONE handle driven sequentially: the call as the caller sees it (Python marshalling +
         # H2D of the ids + launches + the sync on the frame counts + D2H of the int16 into a pooled pinned buffer) against the
         # device time between the call's first and last HIP event; with `streams` handles in flight the headline hides most
@@ -709,7 +720,7 @@ def main():
                                       "note": "median of 10 sequential calls on one handle; host_side = call wall - device time "
                                               "between the call's first and last event"}
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # same loop, int16 result left in HBM: the compute-side number (round 1's headline definition)
         n_dev = max(10, calls // 4)
         el_d, _ = timed(wl, n_dev, 3, device_only=True)
@@ -720,7 +731,7 @@ def main():
                 "steps": steps_d, "note": "int16 result left in HBM (no D2H inside the timed region)",
             }
 
-    if rank == 0 and not args.no_b1:
+    if rank == 0 and args.full and not args.no_b1:
         # ---- configs[1]: batch 1, golden-utterance shape (991 frames = 253,696 samples = 11.505 s)
         Txg = 180
         ids1 = np.random.default_rng(99).integers(1, 50, (1, Txg)).astype(np.int64)
@@ -767,7 +778,7 @@ def main():
             med * 1e3, (n1 / SAMPLE_RATE) / med, result["latency_b1"].get("launches", "?"),
             ("%.3f" % result["latency_b1"]["kernel_ms"]) if "kernel_ms" in result["latency_b1"] else "?"))[:127]
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         nsteps = 3
         for i in range(3):  # the batch-1 leg above leaves the chip mostly idle: back to the loaded clocks before the table
             wl.step(i, device_only=True)
@@ -789,14 +800,14 @@ def main():
         write_table(args.kernel_tables, "bench_kernels", table)
         print_table("per-kernel (HIP events):", table)
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, weights, wl, args.cpu_seconds)
 
     # the extra legs open their own handles: the headline's go first.  HIP maps a process's streams onto a few hardware
     # queues; with the headline's idle handles still open two ACTIVE handles of a leg can land on one queue and serialise —
     # measured (tools/floor_diag2.py): 7.87 ms per step alone, 9.45 ms with two idle handles open, 7.88 ms after closing them
     wl.close()
-    if rank == 0 and n_gpus == 1 and not args.no_extra and args.voice == "apope_low":
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_extra and args.voice == "apope_low":
         # ---- BASELINE.json configs[2]: en_US/vctk_low multi-speaker, batch 32 x 128 phonemes, one MI355X
         vcfg = VitsConfig.vctk_low()
         vw = Workload(vcfg, W.synthetic_weights(vcfg, seed=1234), devices, args.streams, 32, 128, fpi, 0, 1,
@@ -1145,7 +1156,7 @@ def measure_traffic_in_run(label, argv_tail, timeout_s=240):
         d = tempfile.mkdtemp(prefix="mi355vits_pmc_", dir="/tmp")
         try:
             cmd = [prof, "--pmc", counter, "-d", d, "--", sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1",
-                   "--streams", "1", "--no-cpu-baseline", "--no-extra", "--no-b1", "--no-roofline", "--no-traffic"] + argv_tail
+                   "--streams", "1"] + argv_tail
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
                 env.pop(k, None)

@@ -632,6 +632,19 @@ def test_bench_cli_fails_only_for_missing_devices():
     assert "torch.distributed.run" not in tail and "--single-process" not in tail
 
 
+def test_bench_cli_takes_full():
+    """`--full` (every leg beyond the headline: roofline, CPU baseline, other configurations) is an option of the same command:
+    on a box without enough devices it, too, ends with the device-count message, not a usage error."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--full"],
+                       capture_output=True, text=True, timeout=300, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert r.returncode != 0
+    tail = (r.stderr or r.stdout).strip().splitlines()[-1]
+    assert "devices requested" in tail or "no HIP device visible" in tail, tail
+
+
 def test_planned_batches_of_a_known_request(emu_lib):
     """SURVEY N2 (tts.py:470-515: end_utterance holds every pending sentence): stream_sentences on a LIST plans its batches —
     sentence 0 alone, a head batch, the rest length-sorted inside its phoneme-length class — and yields exactly the chunks of

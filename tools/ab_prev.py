@@ -75,7 +75,7 @@ def main():
             for tag, lib in (("prev", a.prev), ("new", keep)):
                 shutil.copy2(lib, PRODUCT)
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(a.batch), "--steps", str(a.steps), "--warmup", "5",
-                       "--no-extra", "--no-cpu-baseline", "--no-traffic", "--no-b1"]
+                       "--full", "--no-extra", "--no-cpu-baseline", "--no-traffic", "--no-b1"]
                 pr = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
                 try:
                     d = json.loads(pr.stdout.strip().splitlines()[-1])
