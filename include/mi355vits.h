@@ -60,6 +60,11 @@ typedef struct mi355vits_config {
     int32_t flow_wn_layers;
     int32_t flow_wn_kernel;
     int32_t flow_wn_dilation_rate;
+    /* Duration predictor.  The stochastic one (use_sdp = true): dp_n_flows >= 2 ConvFlows, dp_dds_layers DDS layers,
+     * dp_num_bins spline bins.  dp_n_flows == 0 marks the deterministic one (use_sdp = false: conv_1 / norm_1 / conv_2 /
+     * norm_2 / proj); then dp_dds_layers and dp_num_bins are 0, its kernel size is dp_kernel_size and its filter width F
+     * is the length of the container's dp.conv_1.bias.  A library older than this rule rejects such a container as an
+     * invalid voice config. */
     int32_t dp_kernel_size;
     int32_t dp_dds_layers;
     int32_t dp_n_flows;

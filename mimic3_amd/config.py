@@ -51,6 +51,7 @@ class VitsConfig:
     dp_n_flows: int = 4             # ConvFlows; inference uses n-1 (A.7)
     dp_num_bins: int = 10
     dp_tail_bound: float = 5.0
+    dp_filter_channels: int = 256   # deterministic predictor (use_sdp=False): filter width of conv_1 / conv_2
     # --- AudioConfig (mimic3_tts/config.py:30-60) ---
     sample_rate: int = 22050
     hop_length: int = 256
@@ -97,8 +98,8 @@ class VitsConfig:
                 raise ValueError("upsample kernel - rate must be even")
         if self.is_multispeaker and self.gin_channels <= 0:
             raise ValueError("multi-speaker voice needs gin_channels > 0")
-        if not self.use_sdp:
-            raise ValueError("only the stochastic duration predictor is supported (use_sdp=True)")
+        if not self.use_sdp and self.dp_filter_channels < 1:
+            raise ValueError("the deterministic duration predictor needs dp_filter_channels > 0")
 
     # the two voices named by BASELINE.json, pinned in SURVEY.md §8a-0
     @staticmethod
@@ -245,9 +246,10 @@ class VitsConfig:
         c.flow_wn_kernel = self.flow_wn_kernel
         c.flow_wn_dilation_rate = self.flow_wn_dilation_rate
         c.dp_kernel_size = self.dp_kernel_size
-        c.dp_dds_layers = self.dp_dds_layers
-        c.dp_n_flows = self.dp_n_flows
-        c.dp_num_bins = self.dp_num_bins
+        # dp_n_flows == 0 marks the deterministic predictor (include/mi355vits.h); its F travels in the tensor table
+        c.dp_dds_layers = self.dp_dds_layers if self.use_sdp else 0
+        c.dp_n_flows = self.dp_n_flows if self.use_sdp else 0
+        c.dp_num_bins = self.dp_num_bins if self.use_sdp else 0
         c.dp_tail_bound = self.dp_tail_bound
         c.sample_rate = self.sample_rate
         c.hop_length = self.hop_length
@@ -257,7 +259,11 @@ class VitsConfig:
     def from_c(c: "CVitsConfig") -> "VitsConfig":
         nk = c.n_resblock_kernels
         nu = c.n_upsamples
-        return VitsConfig(
+        sdp = c.dp_n_flows != 0
+        # deterministic predictor: the SDP-only fields keep their defaults (the C struct holds 0 there); F is set by the
+        # caller from the tensor table (weights.unpack)
+        dp = dict(dp_dds_layers=c.dp_dds_layers, dp_n_flows=c.dp_n_flows, dp_num_bins=c.dp_num_bins) if sdp else {}
+        return VitsConfig(use_sdp=sdp, **dp,
             num_symbols=c.num_symbols, n_speakers=c.n_speakers, inter_channels=c.inter_channels,
             hidden_channels=c.hidden_channels, filter_channels=c.filter_channels, n_heads=c.n_heads,
             n_layers=c.n_layers, kernel_size=c.kernel_size, resblock=str(c.resblock),
@@ -271,7 +277,6 @@ class VitsConfig:
             gin_channels=c.gin_channels, window_size=c.window_size, flow_n_flows=c.flow_n_flows,
             flow_wn_layers=c.flow_wn_layers, flow_wn_kernel=c.flow_wn_kernel,
             flow_wn_dilation_rate=c.flow_wn_dilation_rate, dp_kernel_size=c.dp_kernel_size,
-            dp_dds_layers=c.dp_dds_layers, dp_n_flows=c.dp_n_flows, dp_num_bins=c.dp_num_bins,
             dp_tail_bound=c.dp_tail_bound, sample_rate=c.sample_rate, hop_length=c.hop_length,
         )
 

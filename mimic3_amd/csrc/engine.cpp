@@ -334,8 +334,10 @@ static void validate_config(const mi355vits_config& c) {
         if (c.resblock_n_dilations[j] < 1 || c.resblock_n_dilations[j] > MI355VITS_MAX_STAGES) bad("resblock dilations");
     }
     if (c.n_speakers > 1 && c.gin_channels < 1) bad("multi-speaker voice needs gin_channels");
-    if (c.dp_num_bins < 2 || c.dp_num_bins > 16) bad("dp_num_bins");
-    if (c.dp_n_flows < 2 || c.flow_n_flows < 1 || c.flow_wn_layers < 1) bad("flow depth");
+    // dp_n_flows == 0 marks the deterministic duration predictor (include/mi355vits.h); it has no DDS layers and no spline
+    const bool det_dp = c.dp_n_flows == 0;
+    if (det_dp ? (c.dp_num_bins != 0 || c.dp_dds_layers != 0) : (c.dp_num_bins < 2 || c.dp_num_bins > 16)) bad("dp_num_bins");
+    if ((!det_dp && c.dp_n_flows < 2) || c.flow_n_flows < 1 || c.flow_wn_layers < 1) bad("flow depth");
     if (c.flow_wn_kernel % 2 == 0 || c.dp_kernel_size % 2 == 0) bad("flow / dp kernels must be odd");
     if (c.window_size < 0 || c.n_layers < 1 || c.kernel_size < 1) bad("encoder");
     // plausibility caps: a corrupted header must not turn into absurd loops or allocations
@@ -345,7 +347,7 @@ static void validate_config(const mi355vits_config& c) {
         bad("channel / symbol counts out of range");
     if (c.n_layers > 64 || c.kernel_size > 63 || c.window_size > 15 || c.flow_n_flows > 32 || c.flow_wn_layers > 32 ||
         c.flow_wn_kernel < 1 || c.flow_wn_kernel > 63 || c.flow_wn_dilation_rate < 1 || c.flow_wn_dilation_rate > 8 ||
-        c.dp_n_flows > 16 || c.dp_dds_layers < 1 || c.dp_dds_layers > 8 || c.dp_kernel_size < 1 || c.dp_kernel_size > 63 ||
+        c.dp_n_flows > 16 || (!det_dp && c.dp_dds_layers < 1) || c.dp_dds_layers > 8 || c.dp_kernel_size < 1 || c.dp_kernel_size > 63 ||
         !(c.dp_tail_bound > 0.0f) || c.hop_length > (1 << 16))
         bad("depth / kernel sizes out of range");
     for (int i = 0; i < c.n_upsamples; ++i)
@@ -491,6 +493,26 @@ void Engine::construct(const WeightsFile& wf, int device) {
     }
     add_conv(wf, "enc.proj", "enc_p.proj", 2 * I, H, 1, true);
 
+    // ---- deterministic duration predictor (dp_n_flows == 0): F from the container's tensor table
+    if (c.dp_n_flows == 0) {
+        const auto it = wf.tensors.find("dp.conv_1.bias");
+        if (it == wf.tensors.end() || it->second.dims.size() != 1)
+            throw EngineError(MI355VITS_ERR_FORMAT, "missing tensor dp.conv_1.bias (deterministic duration predictor)");
+        const int DF = it->second.dims[0], K = c.dp_kernel_size;
+        if (!dp_det_supported(H, DF, K))
+            throw EngineError(MI355VITS_ERR_FORMAT, S("deterministic duration predictor: hidden %d / filter %d / kernel %d not supported "
+                                                           "(multiples of 32 up to 256, odd kernel up to 7)", H, DF, K));
+        model_->dp_filter = DF;
+        add_conv(wf, "dp.conv_1", "dp.conv_1", DF, H, K, true);
+        add_conv(wf, "dp.conv_2", "dp.conv_2", DF, DF, K, true);
+        for (const char* n : {"dp.norm_1.gamma", "dp.norm_1.beta", "dp.norm_2.gamma", "dp.norm_2.beta"}) add_vec(wf, n, {DF});
+        add_vec(wf, "dp.proj.weight", {1, DF, 1});
+        add_vec(wf, "dp.proj.bias", {1});
+        if (gin) {
+            add_vec(wf, "dp.cond.weight", {H, gin, 1});
+            add_vec(wf, "dp.cond.bias", {H});
+        }
+    } else {
     // ---- stochastic duration predictor (inference half)
     add_conv(wf, "dp.pre", "dp.pre", H, H, 1, true);
     add_conv(wf, "dp.proj", "dp.proj", H, H, 1, true);
@@ -511,6 +533,7 @@ void Engine::construct(const WeightsFile& wf, int device) {
         add_vec(wf, p + ".pre.bias", {H});
         add_dds(p + ".convs", H);
         add_conv(wf, p + ".proj", p + ".proj", 3 * c.dp_num_bins - 1, H, 1, true);
+    }
     }
 
     // ---- residual coupling flow.  The channel flips between couplings are folded into the weights:
@@ -949,7 +972,47 @@ void Engine::dds(const std::string& key, float* X, float* Y1, float* Y2, int B, 
     }
 }
 
+// deterministic predictor (dp_n_flows == 0): k_dp_det writes logw into channel 0 of z2, and k_durations reads it back through an
+// identity ElementwiseAffine ((z - 0) * expf(-0) * m: exact).  noise_w is not used, as in upstream VITS.
+void Engine::duration_predictor_det(int B, int Tx) {
+    const mi355vits_config& c = cfg_;
+    const int H = c.hidden_channels, DF = model_->dp_filter, K = c.dp_kernel_size;
+    DpDetArgs a;
+    a.x = d_x_;
+    a.cond = d_cond_dp_;
+    a.cond_bs = H;
+    const bool f32 = tmath() == MATH_F32;  // every other mode: the exact three-term split (durations must not move)
+    auto wt = [&](const ConvW& w) { return P(f32 ? w.packed : w.packed_b3s); };
+    const ConvW& c1 = cw("dp.conv_1");
+    const ConvW& c2 = cw("dp.conv_2");
+    if ((f32 ? c1.packed : c1.packed_b3s) == NO_OFF || (f32 ? c2.packed : c2.packed_b3s) == NO_OFF)
+        throw EngineError(MI355VITS_ERR_INTERNAL, "dp.det: conv without packed weights");
+    a.w1 = wt(c1); a.b1 = P(c1.bias); a.g1 = vec("dp.norm_1.gamma"); a.be1 = vec("dp.norm_1.beta");
+    a.w2 = wt(c2); a.b2 = P(c2.bias); a.g2 = vec("dp.norm_2.gamma"); a.be2 = vec("dp.norm_2.beta");
+    a.pw = vec("dp.proj.weight");
+    a.pb = vec("dp.proj.bias");
+    a.len = d_len_;
+    a.out = d_z2_;
+    a.out_bs = 2L * Tx;
+    a.B = B; a.T = Tx; a.H = H; a.F = DF; a.K = K;
+    a.math = f32 ? (int)MATH_F32 : (int)MATH_BF16X3;
+    {
+        const double flops = 2.0 * B * (double)Tx * ((double)K * H * DF + (double)K * DF * DF + DF);
+        ProfScope ps(prof_, "dp.det", flops, 4.0 * B * (double)Tx * (H + 1));
+        launch_dp_det(a, stream_);
+    }
+    {
+        ProfScope ps(prof_, "durations");
+        launch_durations(d_z2_, 0, 0.0f, 0.0f, d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_, d_cum_, d_ylen_, stream_);
+    }
+    tap("logw", d_logw_, {B, 1, Tx});
+}
+
 void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
+    if (model_->dp_filter) {
+        duration_predictor_det(B, Tx);
+        return;
+    }
     const mi355vits_config& c = cfg_;
     const int H = c.hidden_channels;
     const long bs = (long)H * Tx;
@@ -1513,7 +1576,7 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     taps_.clear();
 
     const int H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels;
-    const int nth = 3 * c.dp_num_bins - 1;
+    const int nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
     const int C0 = c.upsample_initial_channel;
     const int gin = multi ? c.gin_channels : 0;
     auto pad = [](size_t bytes) { return DeviceArena::padded(bytes); };

@@ -112,6 +112,7 @@ struct Model {
     std::unordered_map<std::string, ConvW> convs;
     std::unordered_map<std::string, size_t> vecs;
     float ea_m[2] = {0, 0}, ea_logs[2] = {0, 0};
+    int dp_filter = 0;  // deterministic duration predictor (dp_n_flows == 0): its filter width F; 0 for the stochastic one
     bool flow_reversed_out = false;
     size_t bytes = 0;
     ~Model();
@@ -165,6 +166,7 @@ class Engine {
     void tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len = nullptr, int factor = 1);
     void text_encoder(int B, int Tx);
     void duration_predictor(int B, int Tx, const mi355vits_run_args& args);
+    void duration_predictor_det(int B, int Tx);
     void dds(const std::string& key, float* X, float* Y1, float* Y2, int B, int T);
     void flow_and_decoder(int B, int Ty, const mi355vits_run_args& args);
     void copy_out(uint32_t want, mi355vits_result* out);

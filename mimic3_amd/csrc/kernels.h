@@ -281,6 +281,27 @@ struct DdsStackArgs {
 };
 bool dds_stack_supported(int C, int K, int n_layers, int proj_cout);
 void launch_dds_stack(const DdsStackArgs& a, int C, hipStream_t s);
+// ---------------------------------------------------------------- deterministic duration predictor (use_sdp = false)
+// logw = proj(LN_2(relu(conv_2(LN_1(relu(conv_1((x + cond) * m))) * m))) * m) * m in one launch (kernels_dp.cpp, k_dp_det).
+// w1 / w2: layout-1 bf16 planes (pack_conv_weights_bf16x3_mode) in the split-bf16 modes, packed f32 A fragments in MATH_F32.
+struct DpDetArgs {
+    const float* x = nullptr;     // text-encoder output [B, H, T]
+    const float* cond = nullptr;  // + cond[b * cond_bs + c] before the mask (multi-speaker) or null
+    long cond_bs = 0;
+    const float* w1 = nullptr; const float* b1 = nullptr; const float* g1 = nullptr; const float* be1 = nullptr;  // conv_1, norm_1
+    const float* w2 = nullptr; const float* b2 = nullptr; const float* g2 = nullptr; const float* be2 = nullptr;  // conv_2, norm_2
+    const float* pw = nullptr;    // proj weight [F]
+    const float* pb = nullptr;    // proj bias [1]
+    const int* len = nullptr;
+    float* out = nullptr;         // logw at out[b * out_bs + t]; zero at t >= len[b]
+    long out_bs = 0;
+    int B = 1, T = 0, H = 0, F = 0, K = 3;
+    int math = MATH_BF16X3;       // MATH_F32: v_mfma_f32_32x32x2_f32; any other mode: exact split-bf16 products
+};
+bool dp_det_supported(int H, int F, int K);  // H, F multiples of 32 up to 256; K odd up to 7
+size_t dp_det_lds_bytes(int H, int F, int K, int math);
+void launch_dp_det(const DpDetArgs& a, hipStream_t s);
+
 // h[b,c,t] = w[c] * z[b,ch,t] + bias[c] + g[b,c,t]      (ConvFlow.pre on one channel + conditioning)
 void launch_convflow_pre(const float* z, int ch, const float* w, const float* bias, const float* g, int B, int C,
                          int T, float* h, hipStream_t s);

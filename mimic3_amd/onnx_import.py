@@ -300,16 +300,21 @@ def conv_execution_order(cfg: VitsConfig) -> List[str]:
             r += [f"{prefix}.convs_sep.{i}", f"{prefix}.convs_1x1.{i}"]
         return r
 
-    out.append("dp.pre")
-    if gin:
-        out.append("dp.cond")
-    out += dds("dp.convs")
-    out.append("dp.proj")
-    for j in range(cfg.dp_n_flows - 1, 0, -1):  # reversed list with the first ConvFlow dropped
-        idx = 1 + 2 * j
-        out.append(f"dp.flows.{idx}.pre")
-        out += dds(f"dp.flows.{idx}.convs")
-        out.append(f"dp.flows.{idx}.proj")
+    if cfg.use_sdp:
+        out.append("dp.pre")
+        if gin:
+            out.append("dp.cond")
+        out += dds("dp.convs")
+        out.append("dp.proj")
+        for j in range(cfg.dp_n_flows - 1, 0, -1):  # reversed list with the first ConvFlow dropped
+            idx = 1 + 2 * j
+            out.append(f"dp.flows.{idx}.pre")
+            out += dds(f"dp.flows.{idx}.convs")
+            out.append(f"dp.flows.{idx}.proj")
+    else:  # deterministic predictor: x + cond(g), then conv_1 -> norm_1 -> conv_2 -> norm_2 -> proj
+        if gin:
+            out.append("dp.cond")
+        out += ["dp.conv_1", "dp.conv_2", "dp.proj"]
     for j in range(cfg.flow_n_flows - 1, -1, -1):
         f = f"flow.flows.{2 * j}"
         out.append(f"{f}.pre")
@@ -355,6 +360,8 @@ def pointwise_execution_order(cfg: VitsConfig) -> List[str]:
             r += ln(f"{prefix}.norms_1.{i}") + ln(f"{prefix}.norms_2.{i}")
         return r
 
+    if not cfg.use_sdp:
+        return out + ln("dp.norm_1") + ln("dp.norm_2")
     out += dds("dp.convs")
     for j in range(cfg.dp_n_flows - 1, 0, -1):
         out += dds(f"dp.flows.{1 + 2 * j}.convs")
@@ -440,12 +447,21 @@ def infer_config(model: OnnxModel, base: Optional[VitsConfig] = None) -> VitsCon
         cfg.n_speakers, cfg.gin_channels = (int(x) for x in t["emb_g.weight"].shape)
     else:
         cfg.n_speakers = 1
-    cfg.dp_dds_layers = count("dp.convs.convs_sep.{}.bias")
-    if "dp.convs.convs_sep.0.weight" in t:
-        cfg.dp_kernel_size = int(t["dp.convs.convs_sep.0.weight"].shape[2])
-    n_cf = count("dp.flows.{}.pre.bias", start=3, step=2)
-    cfg.dp_n_flows = n_cf + 1
-    cfg.dp_num_bins = (int(need("dp.flows.3.proj.bias").shape[0]) + 1) // 3
+    # deterministic duration predictor (upstream DurationPredictor, use_sdp=False): conv_1 ... proj and no flows
+    # (neither named: what config.json says, else the stochastic one)
+    if "dp.flows.3.pre.bias" in t:
+        cfg.use_sdp = True
+    elif "dp.conv_1.bias" in t:
+        cfg.use_sdp = False
+    if cfg.use_sdp:
+        cfg.dp_dds_layers = count("dp.convs.convs_sep.{}.bias")
+        if "dp.convs.convs_sep.0.weight" in t:
+            cfg.dp_kernel_size = int(t["dp.convs.convs_sep.0.weight"].shape[2])
+        n_cf = count("dp.flows.{}.pre.bias", start=3, step=2)
+        cfg.dp_n_flows = n_cf + 1
+        cfg.dp_num_bins = (int(need("dp.flows.3.proj.bias").shape[0]) + 1) // 3
+    elif "dp.conv_1.bias" in t:
+        cfg.dp_filter_channels = int(t["dp.conv_1.bias"].shape[0])
     cfg.flow_n_flows = count("flow.flows.{}.pre.bias", step=2)
     cfg.flow_wn_layers = count("flow.flows.0.enc.in_layers.{}.bias")
     cfg.upsample_initial_channel = int(need("dec.conv_pre.bias").shape[0])
@@ -464,6 +480,12 @@ def infer_config(model: OnnxModel, base: Optional[VitsConfig] = None) -> VitsCon
         a = table.get(nd.inputs[1])
         return None if a is None else tuple(int(x) for x in a.shape)
 
+    if not cfg.use_sdp:  # the kernel size of conv_1: its weight by name, or the Conv node that adds its bias
+        nd = by_bias.get("dp.conv_1.bias")
+        if "dp.conv_1.weight" in t and t["dp.conv_1.weight"] is not None:
+            cfg.dp_kernel_size = int(t["dp.conv_1.weight"].shape[2])
+        elif nd is not None and wshape(nd):
+            cfg.dp_kernel_size = wshape(nd)[2]
     nd = by_bias.get("flow.flows.0.enc.in_layers.0.bias")
     if nd is not None and wshape(nd):
         cfg.flow_wn_kernel = wshape(nd)[2]
@@ -693,6 +715,12 @@ def describe(onnx_path: str) -> str:
              f"producer  {m.producer} (opset {m.opset})", f"inputs    {m.inputs}", f"outputs   {m.outputs}",
              f"nodes     {len(m.nodes)} ({sum(1 for n in m.nodes if n.op in ('Conv', 'ConvTranspose'))} conv)",
              f"initialisers {len(m.initializers)} ({len(anon)} anonymous), {n_bytes} bytes"]
+    try:
+        cfg = infer_config(m)
+        lines.append("duration  " + ("stochastic (use_sdp=true)" if cfg.use_sdp else
+                                     f"deterministic (use_sdp=false, filter {cfg.dp_filter_channels}, kernel {cfg.dp_kernel_size})"))
+    except (OnnxImportError, ValueError) as e:
+        lines.append(f"duration  unknown ({e})")
     return "\n".join(lines)
 
 
@@ -712,7 +740,10 @@ def main(argv=None) -> int:
     except OnnxImportError as e:
         print(f"error: {e}", file=sys.stderr)
         return 1
+    with open(out, "rb") as f:
+        cfg = W.unpack(f.read())[0]
     print(out)
+    print("duration predictor:", "stochastic" if cfg.use_sdp else f"deterministic (filter {cfg.dp_filter_channels})", file=sys.stderr)
     return 0
 
 

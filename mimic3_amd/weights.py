@@ -84,20 +84,31 @@ def tensor_specs(cfg: VitsConfig) -> "OrderedDict[str, Tuple[int, ...]]":
             ln(f"{prefix}.norms_1.{i}", c)
             ln(f"{prefix}.norms_2.{i}", c)
 
-    conv("dp.pre", H, H, 1)
-    conv("dp.proj", H, H, 1)
-    dds("dp.convs", H)
-    if gin:
-        conv("dp.cond", H, gin, 1)
-    s["dp.flows.0.m"] = (2, 1)
-    s["dp.flows.0.logs"] = (2, 1)
-    # upstream list: [EA, CF, Flip, CF, Flip, ...] -> ConvFlows at odd indices.
-    # Reverse mode drops the first ConvFlow (index 1) — it is never read, so not stored.
-    for j in range(1, cfg.dp_n_flows):
-        idx = 1 + 2 * j
-        conv(f"dp.flows.{idx}.pre", H, 1, 1)
-        dds(f"dp.flows.{idx}.convs", H)
-        conv(f"dp.flows.{idx}.proj", 3 * cfg.dp_num_bins - 1, H, 1)
+    if cfg.use_sdp:
+        conv("dp.pre", H, H, 1)
+        conv("dp.proj", H, H, 1)
+        dds("dp.convs", H)
+        if gin:
+            conv("dp.cond", H, gin, 1)
+        s["dp.flows.0.m"] = (2, 1)
+        s["dp.flows.0.logs"] = (2, 1)
+        # upstream list: [EA, CF, Flip, CF, Flip, ...] -> ConvFlows at odd indices.
+        # Reverse mode drops the first ConvFlow (index 1) — it is never read, so not stored.
+        for j in range(1, cfg.dp_n_flows):
+            idx = 1 + 2 * j
+            conv(f"dp.flows.{idx}.pre", H, 1, 1)
+            dds(f"dp.flows.{idx}.convs", H)
+            conv(f"dp.flows.{idx}.proj", 3 * cfg.dp_num_bins - 1, H, 1)
+    else:
+        # --- deterministic duration predictor (upstream models.DurationPredictor)
+        DF, K = cfg.dp_filter_channels, cfg.dp_kernel_size
+        conv("dp.conv_1", DF, H, K)
+        ln("dp.norm_1", DF)
+        conv("dp.conv_2", DF, DF, K)
+        ln("dp.norm_2", DF)
+        conv("dp.proj", 1, DF, 1)
+        if gin:
+            conv("dp.cond", H, gin, 1)
 
     # --- residual coupling flow (K8); upstream list [RCL, Flip, ...] -> RCLs at even indices
     for j in range(cfg.flow_n_flows):
@@ -150,7 +161,11 @@ def synthetic_weights(cfg: VitsConfig, seed: int = 1234, frames_per_id: float = 
     rng = np.random.default_rng(seed)
     w: Dict[str, np.ndarray] = {}
     for name, shape in tensor_specs(cfg).items():
-        if name.endswith(".gamma"):
+        if name == "dp.proj.bias" and not cfg.use_sdp:
+            t = np.full(shape, math.log(frames_per_id))  # exp(logw) lands near frames_per_id
+        elif name == "dp.proj.weight" and not cfg.use_sdp:
+            t = rng.standard_normal(shape) * (0.3 / math.sqrt(shape[1]))  # LN_2's output is O(1) per channel: logw varies by ~0.3
+        elif name.endswith(".gamma"):
             t = 1.0 + 0.1 * rng.standard_normal(shape)
         elif name.endswith(".beta"):
             t = 0.1 * rng.standard_normal(shape)
@@ -284,6 +299,8 @@ def unpack(blob: bytes) -> Tuple[VitsConfig, Dict[str, np.ndarray]]:
         (off,) = struct.unpack_from("<Q", blob, pos)
         pos += 8
         entries.append((name, dims, off))
+        if name == "dp.conv_1.bias" and not cfg.use_sdp and len(dims) == 1:
+            cfg.dp_filter_channels = int(dims[0])  # the deterministic predictor's F is not in the C struct
     (dbytes,) = struct.unpack_from("<Q", blob, pos)
     pos += 8
     pos += (-pos) % 64
