@@ -193,8 +193,8 @@ int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_
  * message that names it ("row 3: length_scale must be > 0").
  * Contract: for any row b the result (lengths, audio, pcm, peaks) is bitwise what mi355vits_run gives for that row alone with
  * scales = rows->scales[b], pcm_volume = rows->pcm_volume[b] and utterance_base = rows->utterance[b] — in every math mode, as
- * long as the padded phoneme length tx_max stays in the row's own encoder length class (<= 128 / 256 / 512 / beyond): the
- * text encoder picks its kernels by tx_max.  Rows with equal settings and keys therefore give equal audio whichever batch,
+ * long as the padded phoneme length tx_max stays in the row's own encoder length class (<= 128 / 256 / 512 / cap / beyond, where
+ * cap = 4096 - head_dim - (2 window + 1), 3,991 for the released voices): the text encoder picks its kernels by tx_max.  Rows with equal settings and keys therefore give equal audio whichever batch,
  * position or call they ride in. */
 int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                        mi355vits_result* out);

@@ -42,6 +42,11 @@ typedef struct mi355vits_conv_test {
 int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t);
 int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Cout, int Tin, int K, int stride,
                                     const float* x, const float* w, const float* bias, float in_slope, float* y);
+/* Kernel unit-test hook: relative-position attention on host buffers.  qkv [B, 3H, T], emb_rel_k / emb_rel_v
+ * [2W+1, H/n_heads], len [B] (0 <= len <= T), out [B, H, T].  impl: 0 = VALU kernel (T <= rel_attention_valu_cap), 1 = the
+ * f32-MFMA kernel (T <= 512), 2 = the streamed kernel (any T).  Query rows at or past len[b]: what the kernel writes. */
+int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int n_heads, int W, const float* qkv,
+                                 const float* emb_rel_k, const float* emb_rel_v, const int32_t* len, float* out);
 /* Kernel micro-benchmark hook (tools/convbench.py): times `reps` launches of one MFMA Conv1d on random device data.
  * epi: 0 = standard epilogue (bias + residual), 1 = WaveNet gate (Cout = 2*H), 2 = res/skip.  (The tile-shape overrides
  * MI355VITS_CONV_CFG / MI355VITS_CONV_CHUNK exist in the lab build of the library only, csrc/hipx.h lab_getenv.) */

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
+    "mi355vits_test_rel_attention",
 )
 
 
@@ -167,6 +168,8 @@ class NativeLibrary:
             L.mi355vits_bench_conv1d.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_probe_device.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
             L.mi355vits_probe_weights.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+            L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
+                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
 
     def _need_hooks(self):
         if not self.has_hooks:
@@ -225,6 +228,24 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return y
+
+    def test_rel_attention(self, qkv, emb_rel_k, emb_rel_v, lengths, n_heads, impl=2, device=0) -> np.ndarray:
+        """Relative-position attention through one kernel: impl 0 = VALU, 1 = f32-MFMA (T <= 512), 2 = streamed.
+        qkv [B, 3H, T], emb_rel_* [2W+1, H/n_heads], lengths [B] -> [B, H, T]."""
+        self._need_hooks()
+        qkv = np.ascontiguousarray(qkv, np.float32)
+        ek = np.ascontiguousarray(emb_rel_k, np.float32)
+        ev = np.ascontiguousarray(emb_rel_v, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32)
+        B, H3, T = qkv.shape
+        H = H3 // 3
+        W = (ek.shape[0] - 1) // 2
+        out = np.zeros((B, H, T), np.float32)
+        rc = self.lib.mi355vits_test_rel_attention(device, impl, B, T, H, n_heads, W, _fptr(qkv), _fptr(ek), _fptr(ev),
+                                                   ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(out))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out
 
     def bench_conv1d(self, B, Cin, Cout, T, K, dilation=1, epi=0, reps=20, device=0) -> float:
         self._need_hooks()

@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import json
 from dataclasses import dataclass, field, asdict
-from typing import Tuple
+from typing import Optional, Tuple
 
 MAX_STAGES = 8  # upsample stages / resblock kernels / dilations per resblock
 
@@ -76,6 +76,12 @@ class VitsConfig:
         for r in self.upsample_rates:
             f *= r
         return f
+
+    @property
+    def attention_cap(self) -> int:
+        """Longest padded phoneme length the VALU attention kernel serves (one score row per wave in 64 KiB of LDS); longer
+        batches run the streamed attention kernel.  Mirrors rel_attention_valu_cap in csrc/kernels_misc.cpp."""
+        return 64 * 1024 // 16 - self.hidden_channels // self.n_heads - (2 * self.window_size + 1)
 
     def validate(self) -> None:
         if self.resblock not in ("1", "2"):
@@ -316,3 +322,12 @@ class CVitsConfig(ctypes.Structure):
         ("sample_rate", ctypes.c_int32),
         ("hop_length", ctypes.c_int32),
     ]
+
+
+def tx_class(n: int, cap: Optional[int] = None) -> int:
+    """The encoder length class of a padded phoneme length: within a class a batched row gets the kernels — and the bits — it
+    gets alone (the text encoder picks its attention / FFN kernels by tx_max): <= 128, <= 256, <= 512, <= cap, beyond cap.
+    ``cap`` is the voice's ``VitsConfig.attention_cap``; without it the last two classes are one (lengths above the cap are then
+    not told apart)."""
+    c = 0 if n <= 128 else (1 if n <= 256 else (2 if n <= 512 else 3))
+    return 4 if c == 3 and cap is not None and n > cap else c

@@ -842,7 +842,13 @@ void Engine::text_encoder(int B, int Tx) {
         q.y = d_qkv_; q.y_bs = 3 * xbs; q.y_ld = Tx;
         q.B = B; q.T = Tx;
         conv("enc.qkv", cw(S("enc.%d.qkv", i)), q);
-        {
+        if (Tx > rel_attention_valu_cap(H, c.n_heads, c.window_size)) {
+            // beyond the VALU kernel's LDS row buffer: keys streamed (lengths up to the cap keep their kernels and bits)
+            const double fl = 4.0 * B * (double)Tx * Tx * H;
+            ProfScope ps(prof_, "enc.attention.stream", fl, 4.0 * B * 4 * H * Tx);
+            launch_rel_attention_stream(d_qkv_, vec(a + ".emb_rel_k"), vec(a + ".emb_rel_v"), d_len_, B, Tx, H, c.n_heads,
+                                        c.window_size, d_att_, stream_);
+        } else {
             const double fl = 4.0 * B * (double)Tx * Tx * H;
             ProfScope ps(prof_, "enc.attention", fl, 4.0 * B * 4 * H * Tx);
             if (!force_generic_ && rel_attention_mfma_supported(Tx, H, c.n_heads, c.window_size))
@@ -1530,13 +1536,11 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     if (multi && !args.sid) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
     const int B = args.batch, Tx = args.tx_max;
     if ((long)B * Tx > (1L << 26)) throw EngineError(MI355VITS_ERR_INVALID, "batch * tx_max too large");
-    {
-        // beyond 512 ids the attention falls back to a kernel that keeps one score row per wave in LDS (64 KiB)
-        const int d = c.hidden_channels / c.n_heads, tx_cap = (64 * 1024) / 16 - d - (2 * c.window_size + 1);
-        if (Tx > 512 && Tx > tx_cap)
-            throw EngineError(MI355VITS_ERR_INVALID, "phoneme sequence too long: at most " + std::to_string(tx_cap) +
-                                                     " ids per utterance (split the text into sentences, as Mimic 3 does)");
-    }
+    if (Tx > rel_attention_valu_cap(c.hidden_channels, c.n_heads, c.window_size) &&
+        !rel_attention_stream_supported(c.hidden_channels, c.n_heads, c.window_size))
+        throw EngineError(MI355VITS_ERR_INVALID, "tx_max above " + std::to_string(rel_attention_valu_cap(c.hidden_channels, c.n_heads, c.window_size)) +
+                                                 " ids needs the streamed attention kernel, which supports an even head width <= 128 and a "
+                                                 "relative window <= 15 only");
     // per-row settings: rows->* where given, else args' value broadcast to every row (row b keyed utterance_base + b)
     std::vector<float> sc3((size_t)B * 3);
     std::vector<double> vol(B);

@@ -233,6 +233,12 @@ void launch_rel_attention(const float* qkv, const float* emb_rel_k, const float*
 bool rel_attention_mfma_supported(int T, int H, int n_heads, int window);
 void launch_rel_attention_mfma(const float* qkv, const float* emb_rel_k, const float* emb_rel_v, const int* len,
                                int B, int T, int H, int n_heads, int window, float* out, hipStream_t s);
+// same contract for any T: keys streamed through an online softmax (k_rel_attention_stream; even head width <= 128, window <= 15)
+bool rel_attention_stream_supported(int H, int n_heads, int window);
+void launch_rel_attention_stream(const float* qkv, const float* emb_rel_k, const float* emb_rel_v, const int* len,
+                                 int B, int T, int H, int n_heads, int window, float* out, hipStream_t s);
+// longest T the VALU kernel k_rel_attention serves: one score row per wave in 64 KiB of LDS
+int rel_attention_valu_cap(int H, int n_heads, int window);
 
 // ---------------------------------------------------------------- stochastic duration predictor pieces
 // y = gelu(LN(dwconv_k,d(x * mask)))   (first half of a DDS layer, A.6)

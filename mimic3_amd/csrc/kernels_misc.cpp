@@ -545,11 +545,14 @@ __global__ __launch_bounds__(256) void k_rel_attention(const float* qkv, const f
         __syncthreads();
     }
 }
+int rel_attention_valu_cap(int H, int n_heads, int window) {
+    return (64 * 1024) / (4 * (int)sizeof(float)) - H / n_heads - (2 * window + 1);
+}
 void launch_rel_attention(const float* qkv, const float* emb_rel_k, const float* emb_rel_v, const int* len, int B,
                           int T, int H, int n_heads, int window, float* out, hipStream_t s) {
     const int d = H / n_heads;
     const size_t shmem = sizeof(float) * 4 * (size_t)(d + T + 2 * window + 1);
-    if (shmem > 64 * 1024) throw std::runtime_error("rel_attention: phoneme sequence too long for the LDS row buffer");
+    if (T > rel_attention_valu_cap(H, n_heads, window)) throw std::runtime_error("rel_attention: T beyond the LDS row buffer of the VALU kernel");
     LAUNCH_KERNEL(k_rel_attention, dim3((T + ATT_ROWS - 1) / ATT_ROWS, n_heads, B), dim3(256), shmem, s, qkv, emb_rel_k,
                   emb_rel_v, len, T, H, n_heads, window, out);
 }

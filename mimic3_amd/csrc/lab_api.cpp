@@ -191,6 +191,38 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
     });
 }
 
+int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int n_heads, int W, const float* qkv,
+                                 const float* emb_rel_k, const float* emb_rel_v, const int32_t* len, float* out) {
+    return guarded(nullptr, [&] {
+        if (!qkv || !emb_rel_k || !emb_rel_v || !len || !out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || n_heads < 1 || H % n_heads || W < 0) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        for (int b = 0; b < B; ++b)
+            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        const int d = H / n_heads, nrel = 2 * W + 1;
+        if (impl == 0 && T > rel_attention_valu_cap(H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "T beyond the VALU kernel's LDS row buffer");
+        if (impl == 1 && !rel_attention_mfma_supported(T, H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
+        if (impl == 2 && !rel_attention_stream_supported(H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the streamed kernel");
+        if (impl < 0 || impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nq = (size_t)B * 3 * H * T, no = (size_t)B * H * T, ne = (size_t)nrel * d;
+        DevBuf dq(nq * 4), dk(ne * 4), dv(ne * 4), dl((size_t)B * 4), dout(no * 4);
+        HIP_CHECK(hipMemcpy(dq.p, qkv, nq * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dk.p, emb_rel_k, ne * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dv.p, emb_rel_v, ne * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dout.p, out, no * 4, hipMemcpyHostToDevice));
+        if (impl == 0)
+            launch_rel_attention(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
+        else if (impl == 1)
+            launch_rel_attention_mfma(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
+        else
+            launch_rel_attention_stream(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.p, no * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_bench_conv1d(int device, int B, int Cin, int Cout, int T, int K, int dilation, int epi, int reps,
                            float* ms_per_launch) {
     return guarded(nullptr, [&] {

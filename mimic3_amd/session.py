@@ -24,7 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _native
-from .config import VitsConfig
+from .config import VitsConfig, tx_class
 
 
 class GraphOptimizationLevel:
@@ -286,6 +286,7 @@ class _MicroBatcher:
         self._session_ref = weakref.ref(session)
         self._window = window_s
         self._max = max(1, int(max_batch))
+        self._cap = session.config.attention_cap  # the voice's last length-class boundary (config.tx_class)
         self._q: "queue.Queue" = queue.Queue()
         self.batches = 0
         self.requests = 0
@@ -367,12 +368,11 @@ class _MicroBatcher:
                 pass
             # scales, PCM volume and noise key are per row (mi355vits_run_rows), so requests with any settings share a call; only
             # the output kind and sid presence must agree, and the phoneme-length class: the text encoder picks its attention /
-            # FFN kernels by the padded length (<= 128, 256, 512, beyond), so within a class a row gets the kernels — and the
-            # bits — it would get alone
+            # FFN kernels by the padded length (<= 128, 256, 512, the voice's attention cap, beyond: config.tx_class), so within
+            # a class a row gets the kernels — and the bits — it would get alone
             groups: Dict[Any, list] = {}
             for it in items:
-                n = int(it[1][0])
-                bucket = 0 if n <= 128 else (1 if n <= 256 else (2 if n <= 512 else 3))
+                bucket = tx_class(int(it[1][0]), self._cap)
                 kind = tuple(sorted((k, v) for k, v in it[4].items() if k not in _ROW_SETTINGS))
                 key = (it[3] is None, kind, bucket)
                 groups.setdefault(key, []).append(it)

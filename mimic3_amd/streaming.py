@@ -24,6 +24,7 @@ from typing import Dict, Iterable, Iterator, Optional, Sequence
 
 import numpy as np
 
+from .config import tx_class
 from .postprocess import silence
 
 STREAM_SIZE = 0xFFFFFFFF  # RIFF / data chunk size of a WAV whose length is not known when the header is sent
@@ -43,20 +44,20 @@ def _feed(ids: Sequence[int], scales, sid: Optional[int]) -> Dict[str, np.ndarra
     return feed
 
 
-def _tx_class(n: int) -> int:
-    """The phoneme-length classes within which a batched row gets the kernels — and the bits — it gets alone (the text encoder
-    picks its attention / FFN kernels by the padded length; session._MicroBatcher groups arrivals the same way)."""
-    return 0 if n <= 128 else (1 if n <= 256 else (2 if n <= 512 else 3))
+# the phoneme-length classes within which a batched row gets the kernels — and the bits — it gets alone (session._MicroBatcher
+# groups arrivals with the same helper)
+_tx_class = tx_class
 
 
-def plan_batches(lengths: Sequence[int], head: int = 0, max_batch: int = 48) -> list:
+def plan_batches(lengths: Sequence[int], head: int = 0, max_batch: int = 48, cap: Optional[int] = None) -> list:
     """Batches for a request whose sentences are all known (``end_utterance`` holds every pending ``Mimic3Phonemes`` when it
     starts, ``mimic3_tts/tts.py:470-515``): sentence 0 ALONE (its audio is what the listener waits for), then — optionally — the
     next ``head`` sentences as one batch (for playback that must continue before the rest is done; at 16,000 x real time the rest
     of a 10k-character request is done 15 ms later, so the default is 0), then everything else sorted by length inside its
     phoneme-length class and cut into batches of at most ``max_batch`` — rows of one batch have similar lengths, so little of a
     batched call is padding (the decoder computes every row up to the batch's longest).  Returns lists of sentence indices, in
-    the order the batches should be issued (by the earliest sentence they hold)."""
+    the order the batches should be issued (by the earliest sentence they hold).  ``cap``: the voice's ``attention_cap``, which
+    separates the lengths above it into a class of their own (``config.tx_class``)."""
     n = len(lengths)
     if n == 0:
         return []
@@ -65,12 +66,12 @@ def plan_batches(lengths: Sequence[int], head: int = 0, max_batch: int = 48) -> 
         first = list(range(1, min(n, 1 + max(0, head))))
         by_class: dict = {}
         for i in first:
-            by_class.setdefault(_tx_class(int(lengths[i])), []).append(i)
+            by_class.setdefault(_tx_class(int(lengths[i]), cap), []).append(i)
         batches.extend(by_class.values())
     rest = list(range(1 + max(0, head), n))
     by_class = {}
     for i in rest:
-        by_class.setdefault(_tx_class(int(lengths[i])), []).append(i)
+        by_class.setdefault(_tx_class(int(lengths[i]), cap), []).append(i)
     tail = []
     for idx in by_class.values():
         idx.sort(key=lambda i: (int(lengths[i]), i))
@@ -126,9 +127,12 @@ def stream_planned(session, sentences: Sequence[Sequence[int]], scales=(0.667, 1
     done: Dict[int, object] = {}
     valid = computed = tvalid = tcomputed = 0
 
+    cfg = getattr(session, "config", None)
+    cap = getattr(cfg, "attention_cap", None)
+
     def prepare():
         lens = [len(s) for s in sentences]
-        return plan_batches(lens, head=head, max_batch=max_batch), lens
+        return plan_batches(lens, head=head, max_batch=max_batch, cap=cap), lens
 
     def run_batch(idx):
         try:
