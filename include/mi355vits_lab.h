@@ -40,8 +40,14 @@ typedef struct mi355vits_conv_test {
     int32_t accumulate;
 } mi355vits_conv_test;
 int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t);
+/* in_len [B] (0 <= in_len[b] <= Tin) or NULL = every row at full length; impl 3 only.  Output positions at or past in_len[b] x stride
+ * are left undefined. */
 int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Cout, int Tin, int K, int stride,
-                                    const float* x, const float* w, const float* bias, float in_slope, float* y);
+                                    const float* x, const float* w, const float* bias, float in_slope, const int32_t* in_len, float* y);
+/* Test hook: fills the whole capacity of the handle's two workspace arenas with a 32-bit pattern (on the engine stream, then
+ * synchronises).  A later run on the same handle that does not outgrow the workspace finds the pattern in every column it does
+ * not write: the columns past a row's end must reach no valid sample (consumers mask by select, never by multiply). */
+int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern);
 /* Kernel unit-test hook: relative-position attention on host buffers.  qkv [B, 3H, T], emb_rel_k / emb_rel_v
  * [2W+1, H/n_heads], len [B] (0 <= len <= T), out [B, H, T].  impl: 0 = VALU kernel (T <= rel_attention_valu_cap), 1 = the
  * f32-MFMA kernel (T <= 512), 2 = the streamed kernel (any T).  Query rows at or past len[b]: what the kernel writes. */

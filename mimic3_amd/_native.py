@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
-    "mi355vits_test_rel_attention",
+    "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace",
 )
 
 
@@ -163,7 +163,8 @@ class NativeLibrary:
             L.mi355vits_test_conv_transpose1d.argtypes = [
                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                 ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
-                ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(ctypes.c_float)]
+                ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
+            L.mi355vits_test_fill_workspace.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
             L.mi355vits_test_mfma_layout.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_bench_conv1d.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_probe_device.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -215,19 +216,30 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return y
 
-    def test_conv_transpose1d(self, x, w, bias, stride, in_slope=1.0, device=0, impl=0) -> np.ndarray:
+    def test_conv_transpose1d(self, x, w, bias, stride, in_slope=1.0, device=0, impl=0, in_len=None) -> np.ndarray:
+        """in_len [B]: per-row input lengths (impl 3 only; None = every row at full length); output positions at or past
+        in_len[b] x stride are left undefined."""
         self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         B, Cin, Tin = x.shape
         _, Cout, K = w.shape
         b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        ln = None if in_len is None else np.ascontiguousarray(in_len, np.int32)
         y = np.zeros((B, Cout, Tin * stride), np.float32)
         rc = self.lib.mi355vits_test_conv_transpose1d(device, impl, B, Cin, Cout, Tin, K, stride, _fptr(x), _fptr(w),
-                                                      _fptr(b), in_slope, _fptr(y))
+                                                      _fptr(b), in_slope,
+                                                      None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(y))
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return y
+
+    def emu_set_cu_count(self, n: int) -> None:
+        """The compute units the CPU model reports to the grid sizing of every launch after this call (default 8; n < 1 restores it).
+        CPU model only: the device libraries report what the device has."""
+        if not hasattr(self.lib, "mi355vits_emu_set_cu_count"):
+            raise RuntimeError(f"{self.path} is not the CPU model of the kernels")
+        self.lib.mi355vits_emu_set_cu_count(ctypes.c_int(int(n)))
 
     def test_rel_attention(self, qkv, emb_rel_k, emb_rel_v, lengths, n_heads, impl=2, device=0) -> np.ndarray:
         """Relative-position attention through one kernel: impl 0 = VALU, 1 = f32-MFMA (T <= 512), 2 = streamed.
@@ -520,6 +532,12 @@ class Engine:
         self._check(self.native.lib.mi355vits_probe_weights(self._h, out))
         return {"arena_stream8_GBps": [round(out[0]), round(out[1]), round(out[2])], "arena_stream1_GBps": [round(out[3]), round(out[4]), round(out[5])],
                 "windows": int(out[6]), "arena_addr_low36": hex(int(out[7]))}
+
+    def fill_workspace(self, pattern: int) -> None:
+        """Fill both workspace arenas of this handle with a 32-bit pattern (include/mi355vits_lab.h mi355vits_test_fill_workspace; the
+        handle must come from a library that carries the hooks).  A later run that does not outgrow the workspace keeps it."""
+        self.native._need_hooks()
+        self._check(self.native.lib.mi355vits_test_fill_workspace(self._h, ctypes.c_uint32(pattern & 0xFFFFFFFF)))
 
     def profile_enable(self, on: bool = True) -> None:
         self._check(self.native.lib.mi355vits_profile_enable(self._h, int(on)))

@@ -129,8 +129,18 @@ void DeviceArena::reserve(size_t bytes, hipStream_t s) {
     base_ = static_cast<unsigned char*>(p);
     cap_ = want;
     // zero-filled once per (re)allocation: the decoder / flow kernels never compute items past a row's length in a ragged batch
-    // (kernels_mrfp.cpp next_item), so those columns keep what the arena held before — which must be finite, not fresh-memory NaNs
+    // (kernels_mrfp.cpp), so those columns keep whatever an earlier run left there — consumers mask by select, never by multiply
+    // (a NaN or Inf there must reach no valid sample); tests/test_grid_geometry_and_poison.py is the guard
     HIP_CHECK(hipMemsetAsync(base_, 0, want, s));
+}
+void DeviceArena::fill(uint32_t pattern, hipStream_t s) {
+    if (!base_) return;
+#ifdef MI355_EMU
+    (void)s;  // the CPU model's device memory is host memory
+    std::fill_n(reinterpret_cast<uint32_t*>(base_), cap_ / 4, pattern);
+#else
+    HIP_CHECK(hipMemsetD32Async(base_, (int)pattern, cap_ / 4, s));
+#endif
 }
 void* DeviceArena::alloc_bytes(size_t bytes) {
     const size_t need = padded(bytes);
@@ -629,6 +639,13 @@ void Engine::construct(const WeightsFile& wf, int device) {
     model_->bytes = host_stage_.size() * sizeof(float);
     HIP_CHECK(hipMemcpy(model_->dev_weights, host_stage_.data(), host_stage_.size() * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float>().swap(host_stage_);
+}
+
+void Engine::fill_workspace(uint32_t pattern) {
+    HIP_CHECK(hipSetDevice(device_));
+    arena_a_.fill(pattern, stream_);
+    arena_b_.fill(pattern, stream_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 void Engine::probe_weights(double out[8]) {

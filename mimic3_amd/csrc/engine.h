@@ -39,6 +39,7 @@ class DeviceArena {
     ~DeviceArena();
     void reserve(size_t bytes, hipStream_t s);  // may reallocate (synchronises the stream first)
     void reset() { off_ = 0; }
+    void fill(uint32_t pattern, hipStream_t s);  // every byte of the capacity (tests: mi355vits_test_fill_workspace)
     template <typename T> T* alloc(size_t n) { return reinterpret_cast<T*>(alloc_bytes(n * sizeof(T))); }
     size_t capacity() const { return cap_; }
     size_t used() const { return off_; }
@@ -127,6 +128,8 @@ class Engine {
     // diagnostics (mi355vits_probe_weights): how fast every CU together streams 2.6 MB windows of THIS replica's weight arena out of
     // the L2 — eight loads in flight per lane (bandwidth) and one (latency per fragment); min / median / max over the windows
     void probe_weights(double out[8]);
+    // test hook (mi355vits_test_fill_workspace): both workspace arenas filled with a 32-bit pattern, synchronised
+    void fill_workspace(uint32_t pattern);
     const std::shared_ptr<Model>& model() const { return model_; }
     // device pointers of the last run's results (valid until the next run on this handle); for device-side gathers
     void device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths);

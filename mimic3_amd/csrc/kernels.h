@@ -168,7 +168,7 @@ void launch_rb_conv(ConvArgs a, hipStream_t s);
 void pack_conv_weights_p16n(const float* w, int Cout, int Cin, int K, uint32_t* out);
 bool ups_pl_supported(const ConvArgs& a);
 void launch_ups_pl(ConvArgs a, hipStream_t s);
-int current_device_cu_count();  // compute units of the current device (persistent grids), looked up once per device
+int current_device_cu_count();  // compute units of the current device (persistent grids): cached per device (CPU model: reread)
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set once per (kernel, current device)
 void set_max_dynamic_lds(const void* fn, int bytes);
 

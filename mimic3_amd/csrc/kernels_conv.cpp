@@ -1701,20 +1701,6 @@ void launch_cfg(const ConvArgs& a, int n_tiles, hipStream_t s) {
 // (the polyphase upsamplers) take 64-channel chunks when C_in allows — with so few taps a 32-channel chunk is only 72 - 144
 // MFMAs per wave between two stage / barrier cycles.  The chunk size is a function of the layer alone (never of the batch),
 // so the summation order of an output does not depend on what it is batched with.
-// compute units of the current device (persistent grids), looked up once per device
-static int device_cu_count() {
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int n = cached[dev].load(std::memory_order_relaxed);
-    if (n <= 0) {
-        hipDeviceProp_t p;
-        n = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-}
-
 template <int MT, int NT, int WM, int WN, int EPI>
 void launch_b3(const ConvArgs& a, int n_tiles, hipStream_t s) {
     constexpr int T_B = 32 * NT * WN;
@@ -1745,7 +1731,7 @@ void launch_b3(const ConvArgs& a, int n_tiles, hipStream_t s) {
         if (wide && a.shuf_s && (a.shuf_s & 3) == 0 && !no_pc && 2 * shmem <= 160 * 1024) {
             // persistent producer / consumer form: two staging buffers, one workgroup per CU
             const long total = (long)grid.x * grid.y * grid.z;
-            const int cus = device_cu_count();
+            const int cus = current_device_cu_count();
             shmem *= 2;
             grid = dim3((unsigned)(total < cus ? total : cus), 1, 1);
             auto gop = [&](auto kfn) {

@@ -159,8 +159,9 @@ __global__ __launch_bounds__(512) void k_mrf_p(MrfArgs a) {
     // that XCD's L2; the eighths hold equal numbers of VALID items whatever the rows' lengths).  A cursor (row, first valid index
     // of that row, its count) turns an index into (row, column block); the indices of a workgroup only grow.
     const int nitems = a.nvalid;
-    const int nblk = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int per_xcd = (nitems + 7) >> 3, nslot = (nblk + 7 - xcd) >> 3;  // blocks on this XCD (nblk need not be a multiple of 8)
+    // (grids of fewer than eight workgroups: as many groups as workgroups, so that every group's items have a workgroup)
+    const int nblk = gridDim.x, ngrp = nblk < 8 ? nblk : 8, xcd = blockIdx.x % ngrp, slot = blockIdx.x / ngrp;
+    const int per_xcd = (nitems + ngrp - 1) / ngrp, nslot = (nblk + ngrp - 1 - xcd) / ngrp;  // blocks on this XCD (nblk need not be a multiple of 8)
     const int item_end = (xcd + 1) * per_xcd < nitems ? (xcd + 1) * per_xcd : nitems;
     auto row_len = [&](int bb) MI355_INLINE_LAMBDA {
         int ln = a.len ? a.len[bb] : a.T;
@@ -649,10 +650,16 @@ void set_max_dynamic_lds(const void* fn, int bytes) {
 #endif
 }
 
+// the one lookup of the compute-unit count behind every persistent grid and every form chosen by grid size
 int current_device_cu_count() {
-    static std::atomic<int> cached[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+#ifdef MI355_EMU
+    // the CPU model's count is a test parameter (mi355vits_emu_set_cu_count): read at every launch, never cached
+    hipDeviceProp_t p;
+    return (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
+#else
+    static std::atomic<int> cached[64];  // looked up once per device
     int n = cached[dev].load(std::memory_order_relaxed);
     if (n <= 0) {
         hipDeviceProp_t p;
@@ -660,6 +667,7 @@ int current_device_cu_count() {
         cached[dev].store(n, std::memory_order_relaxed);
     }
     return n;
+#endif
 }
 
 void launch_mrf_p(MrfArgs a, hipStream_t s) {

@@ -44,12 +44,16 @@ constexpr int RBC_WR = 4;  // weight-fragment ring: the running step and three a
 // fall into — would so land on eight different XCDs and be fetched from HBM by each of them.  XCD-major: logical item it = 8 q + x
 // becomes the q-th item of XCD x's contiguous eighth of the items (a bijection for every item count), so that the 32 CUs of an XCD work
 // on neighbouring items at the same time and the shared bytes come out of that XCD's L2 (k_mrf_p has walked its items like this since round 3).
+// The cursor only moves forward, so a workgroup's remapped items must grow: they do when W % 8 == 0 or W == the item count (rbc_order).
 __device__ __forceinline__ int rbc_item(int it, int n, int order) {
     if (!order) return it;
     const int x = it & 7, q = it >> 3, f = n >> 3, rm = n & 7;
     return x * f + (x < rm ? x : rm) + q;
 }
 constexpr int RBC_ITEM_ORDER = 1;
+// the item order a launch of `grid` persistent workgroups over `nitems` items may use: XCD-major only where every workgroup's
+// sequence w, w + W, ... stays increasing after rbc_item (otherwise the forward-only cursor would skip whole rows' items)
+inline int rbc_order(int order, long nitems, int grid) { return grid % 8 == 0 || grid == nitems ? order : 0; }
 
 template <int K, int DIL, int NCT>
 struct RbcGeo {
@@ -1233,6 +1237,7 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
         const long nitems = a.nvalid;
         if (nitems <= 0) return;
         dim3 grid((unsigned)(nitems < cus ? nitems : cus));  // persistent: one workgroup per CU
+        a.item_order = rbc_order(a.item_order, nitems, (int)grid.x);
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
         LAUNCH_KERNEL(kfn, grid, dim3(threads), lds, s, a);
     };
@@ -1355,6 +1360,7 @@ void launch_ups_pl(ConvArgs a, hipStream_t s) {
         const long nitems = a.nvalid;
         if (nitems <= 0) return;
         dim3 grid((unsigned)(nitems < cus ? nitems : cus));
+        a.item_order = rbc_order(a.item_order, nitems, (int)grid.x);
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
         LAUNCH_KERNEL(kfn, grid, dim3(512), lds, s, a);
     };

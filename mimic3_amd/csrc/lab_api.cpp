@@ -107,23 +107,32 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
     });
 }
 
+int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->fill_workspace(pattern); });
+}
+
 int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Cout, int Tin, int K, int stride,
-                                    const float* x, const float* w, const float* bias, float in_slope, float* y) {
+                                    const float* x, const float* w, const float* bias, float in_slope, const int32_t* in_len, float* y) {
     return guarded(nullptr, [&] {
         if (!x || !w || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (in_len && impl != 3) throw EngineError(MI355VITS_ERR_INVALID, "per-row lengths: impl 3 only");
+        for (int b = 0; in_len && b < B; ++b)
+            if (in_len[b] < 0 || in_len[b] > Tin) throw EngineError(MI355VITS_ERR_INVALID, "in_len out of range");
         HIP_CHECK(hipSetDevice(device));
         const size_t nx = (size_t)B * Cin * Tin, ny = (size_t)B * Cout * Tin * stride, nw = (size_t)Cin * Cout * K;
         DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(Cout * 4);
         HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
         if (impl == 3) {
             // the resident-input polyphase kernels (k_ups_pl: 256 -> 128, 128 -> 64; k_ups64: 64 -> 32), MATH_BF16X3; a valid length per
-            // row is part of their contract (the engine always has one): every row at full length here
+            // row is part of their contract (the engine always has one): in_len, or every row at full length
             const int taps = convt_taps(K, stride);
             std::vector<float> wv((size_t)stride * Cout * Cin * taps), bv((size_t)stride * Cout);
             convt_to_polyphase(w, bias, Cin, Cout, K, stride, wv.data(), bv.data());
             std::vector<uint32_t> pp(p16_packed_words(stride * Cout, Cin, taps));
             pack_conv_weights_p16n(wv.data(), stride * Cout, Cin, taps, pp.data());
-            std::vector<int> lens((size_t)B, Tin);
+            std::vector<int> lens = in_len ? std::vector<int>(in_len, in_len + B) : std::vector<int>((size_t)B, Tin);
             DevBuf dpp(pp.size() * 4), dbias(bv.size() * 4), dlen((size_t)B * 4);
             HIP_CHECK(hipMemcpy(dpp.p, pp.data(), pp.size() * 4, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dbias.p, bv.data(), bv.size() * 4, hipMemcpyHostToDevice));

@@ -93,12 +93,15 @@ static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t
     *ms = std::chrono::duration<float, std::milli>(b->t - a->t).count();
     return hipSuccess;
 }
+// the compute units the model reports: 8 unless a test sets another count (mi355vits_emu_set_cu_count, hip_emu_impl.cpp) to vary
+// the grids of the persistent kernels; the library rereads it at every launch (current_device_cu_count)
+inline std::atomic<int> hipemu_cu_count{8};
 struct hipDeviceProp_t { char name[256]; int multiProcessorCount; size_t totalGlobalMem; char gcnArchName[256]; };
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     memset(p, 0, sizeof(*p));
     strcpy(p->name, "hipemu (CPU)");
     strcpy(p->gcnArchName, "emu");
-    p->multiProcessorCount = 8;
+    p->multiProcessorCount = hipemu_cu_count.load(std::memory_order_relaxed);
     p->totalGlobalMem = size_t(8) << 30;
     return hipSuccess;
 }
