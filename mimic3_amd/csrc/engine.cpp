@@ -216,7 +216,7 @@ size_t Engine::stage(const float* p, size_t n) {
 }
 
 const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<float>& w, const std::vector<float>* bias,
-                                   int Cout, int Cin, int K, int epi) {
+                                   int Cout, int Cin, int K, int epi, ConvRole role) {
     if (w.size() != (size_t)Cout * Cin * K) throw EngineError(MI355VITS_ERR_INTERNAL, "add_conv_data size: " + key);
     ConvW c;
     c.Cout = Cout; c.Cin = Cin; c.K = K; c.epi = epi;
@@ -226,13 +226,14 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
         std::vector<float> pk(mfma_packed_floats(Cout, Cin, K), 0.0f);
         pack_conv_weights_mfma_mode(w.data(), Cout, Cin, K, epi == EPI_GATE ? EPI_GATE : EPI_STD, pk.data());
         c.packed = stage(pk.data(), pk.size());
-        if (key.rfind("dec.rb.", 0) == 0 && epi == EPI_STD && Cin % 8 == 0 && Cout % 32 == 0) {
+        const bool rb = role == ROLE_RESBLOCK && epi == EPI_STD;
+        if (rb && Cin % 8 == 0 && Cout % 32 == 0) {
             // fused MRF stage: a lane's A fragments of four consecutive channel pairs side by side
             std::vector<float> p4(pk.size());
             regroup_packed_x4(pk.data(), pk.size(), p4.data());
             c.packed4 = stage(p4.data(), p4.size());
         }
-        if (key.rfind("dec.rb.", 0) == 0 && epi == EPI_STD && Cin % 16 == 0 && Cout % 32 == 0) {
+        if (rb && Cin % 16 == 0 && Cout % 32 == 0) {
             // the same weights as three bf16 planes for the split-operand path (MATH_BF16X3)
             std::vector<uint32_t> b3(bf16x3_packed_words(Cout, Cin, K));
             pack_conv_weights_bf16x3(w.data(), Cout, Cin, K, b3.data());
@@ -243,13 +244,13 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
             if (pack_conv_weights_f16x2(w.data(), Cout, Cin, K, h2.data()))
                 c.packed_h2 = stage(reinterpret_cast<const float*>(h2.data()), h2.size());
         }
-        if (key.rfind("dec.rb.", 0) == 0 && epi == EPI_STD && Cin == Cout && Cin % 32 == 0 && (K == 3 || K == 5 || K == 7)) {
+        if (rb && Cin == Cout && Cin % 32 == 0 && (K == 3 || K == 5 || K == 7)) {
             // ... and in the fragment order of k_mrf_p (16-row tiles, 32-channel k-groups)
             std::vector<uint32_t> pp(p16_packed_words(Cout, Cin, K));
             pack_conv_weights_p16(w.data(), Cout, Cin, K, pp.data());
             c.packed_p = stage(reinterpret_cast<const float*>(pp.data()), pp.size());
         }
-        if (key.rfind("dec.ups.", 0) == 0 && epi == EPI_STD && (Cin == 64 || Cin == 128 || Cin == 256) && Cout % 128 == 0 && K == 2) {
+        if (role == ROLE_UPSAMPLER && epi == EPI_STD && (Cin == 64 || Cin == 128 || Cin == 256) && Cout % 128 == 0 && K == 2) {
             // polyphase upsamplers 128 -> 64 / 64 -> 32: fragments of 16-row tiles in natural row order (k_ups_pl)
             std::vector<uint32_t> pp(p16_packed_words(Cout, Cin, K));
             pack_conv_weights_p16n(w.data(), Cout, Cin, K, pp.data());
@@ -288,15 +289,14 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
 }
 
 const ConvW& Engine::add_conv(const WeightsFile& wf, const std::string& key, const std::string& tensor, int Cout, int Cin,
-                              int K, bool bias, int epi) {
+                              int K, bool bias, int epi, ConvRole role) {
     const HostTensor& w = wf.get(tensor + ".weight", {Cout, Cin, K});
-    std::vector<float> wv(w.data, w.data + w.count);
+    std::vector<float> wv(w.data, w.data + w.count), bv;
     if (bias) {
         const HostTensor& b = wf.get(tensor + ".bias", {Cout});
-        std::vector<float> bv(b.data, b.data + b.count);
-        return add_conv_data(key, wv, &bv, Cout, Cin, K, epi);
+        bv.assign(b.data, b.data + b.count);
     }
-    return add_conv_data(key, wv, nullptr, Cout, Cin, K, epi);
+    return add_conv_data(key, wv, bias ? &bv : nullptr, Cout, Cin, K, epi, role);
 }
 
 void Engine::add_vec(const WeightsFile& wf, const std::string& name, std::initializer_list<int> dims) {
@@ -392,22 +392,32 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         open_device(device_);
         model_ = lane0.model_;
         math_ = lane0.math_;
-        b3_min_work_ = lane0.b3_min_work_;
-        wn_b3_ = lane0.wn_b3_;
-        no_mrf_p_ = lane0.no_mrf_p_;
-        no_rbc_ = lane0.no_rbc_;
-        no_fused_dds_ = lane0.no_fused_dds_;
-        no_dds_stack_ = lane0.no_dds_stack_;
-        no_dds_stack_b3_ = lane0.no_dds_stack_b3_;
-        no_enc_gemm_ = lane0.no_enc_gemm_;
-        no_enc_o_ln_ = lane0.no_enc_o_ln_;
-        no_flow_gemm_ = lane0.no_flow_gemm_;
-        enc_b3_ = lane0.enc_b3_;
-        no_f16x2_convs_ = lane0.no_f16x2_convs_;
+        sw_ = lane0.sw_;
     } catch (...) {
         release();
         throw;
     }
+}
+
+LabSwitches LabSwitches::from_env() {
+    auto one = [](const char* name) { const char* v = lab_getenv(name); return v && v[0] == '1'; };
+    auto set = [](const char* name) { return lab_getenv(name) != nullptr; };
+    LabSwitches s;
+    s.force_generic = one("MI355VITS_FORCE_GENERIC");
+    s.no_fused_wn = one("MI355VITS_NO_FUSED_WN");
+    s.no_fused_mrf = one("MI355VITS_NO_FUSED_MRF");
+    if (const char* bw = lab_getenv("MI355VITS_B3_MIN_WORK")) s.b3_min_work = atoi(bw);
+    s.wn_b3 = set("MI355VITS_WN_B3");
+    s.no_mrf_p = set("MI355VITS_NO_MRF_P");
+    s.no_rbc = set("MI355VITS_NO_RBC");
+    s.no_fused_dds = set("MI355VITS_NO_FUSED_DDS");
+    s.no_dds_stack = set("MI355VITS_NO_DDS_STACK");
+    s.no_dds_stack_b3 = set("MI355VITS_NO_DDS_STACK_B3");
+    s.no_enc_gemm = set("MI355VITS_NO_ENC_GEMM");
+    s.no_enc_o_ln = set("MI355VITS_NO_ENC_O_LN");
+    s.no_flow_gemm = set("MI355VITS_NO_FLOW_GEMM");
+    s.no_f16x2_convs = set("MI355VITS_F16X2_NO_CONVS");
+    return s;
 }
 
 void Engine::open_device(int device) {
@@ -420,25 +430,7 @@ void Engine::open_device(int device) {
     HIP_CHECK(hipEventCreate(&ev_start_));
     HIP_CHECK(hipEventCreate(&ev_end_));
     prof_.stream = stream_;
-    const char* fg = lab_getenv("MI355VITS_FORCE_GENERIC");
-    force_generic_ = fg && fg[0] == '1';
-    const char* nw = lab_getenv("MI355VITS_NO_FUSED_WN");
-    no_fused_wn_ = nw && nw[0] == '1';
-    const char* nf = lab_getenv("MI355VITS_NO_FUSED_MRF");
-    no_fused_mrf_ = nf && nf[0] == '1';
-    const char* bw = lab_getenv("MI355VITS_B3_MIN_WORK");
-    b3_min_work_ = bw ? atoi(bw) : 256;
-    wn_b3_ = lab_getenv("MI355VITS_WN_B3") != nullptr;
-    no_mrf_p_ = lab_getenv("MI355VITS_NO_MRF_P") != nullptr;
-    no_rbc_ = lab_getenv("MI355VITS_NO_RBC") != nullptr;
-    no_fused_dds_ = lab_getenv("MI355VITS_NO_FUSED_DDS") != nullptr;
-    no_dds_stack_ = lab_getenv("MI355VITS_NO_DDS_STACK") != nullptr;
-    no_dds_stack_b3_ = lab_getenv("MI355VITS_NO_DDS_STACK_B3") != nullptr;
-    no_enc_gemm_ = lab_getenv("MI355VITS_NO_ENC_GEMM") != nullptr;
-    no_enc_o_ln_ = lab_getenv("MI355VITS_NO_ENC_O_LN") != nullptr;
-    no_flow_gemm_ = lab_getenv("MI355VITS_NO_FLOW_GEMM") != nullptr;
-    enc_b3_ = lab_getenv("MI355VITS_NO_ENC_B3") == nullptr;
-    no_f16x2_convs_ = lab_getenv("MI355VITS_F16X2_NO_CONVS") != nullptr;
+    sw_ = LabSwitches::from_env();
     math_ = MATH_BF16X3;  // default (see include/mi355vits.h: f32-grade results; MI355VITS_MATH=f32 for v_mfma_f32_*)
     const char* mm = getenv("MI355VITS_MATH");
     if (mm && mm[0]) {
@@ -608,7 +600,7 @@ void Engine::construct(const WeightsFile& wf, int device) {
             const HostTensor& b = wf.get(S("dec.ups.%d.bias", i), {ch / 2});
             std::vector<float> wv((size_t)ur * (ch / 2) * ch * taps), bv((size_t)ur * (ch / 2));
             convt_to_polyphase(w.data, b.data, ch, ch / 2, uk, ur, wv.data(), bv.data());
-            add_conv_data(S("dec.ups.%d.poly", i), wv, &bv, ur * (ch / 2), ch, taps);
+            add_conv_data(S("dec.ups.%d.poly", i), wv, &bv, ur * (ch / 2), ch, taps, EPI_STD, ROLE_UPSAMPLER);
         }
         ch /= 2;
         for (int j = 0; j < c.n_resblock_kernels; ++j) {
@@ -616,10 +608,10 @@ void Engine::construct(const WeightsFile& wf, int device) {
             const int rk = c.resblock_kernel_sizes[j];
             for (int m = 0; m < c.resblock_n_dilations[j]; ++m) {
                 if (c.resblock == 2) {
-                    add_conv(wf, S("dec.rb.%d.c.%d", n, m), S("dec.resblocks.%d.convs.%d", n, m), ch, ch, rk, true);
+                    add_conv(wf, S("dec.rb.%d.c.%d", n, m), S("dec.resblocks.%d.convs.%d", n, m), ch, ch, rk, true, EPI_STD, ROLE_RESBLOCK);
                 } else {
-                    add_conv(wf, S("dec.rb.%d.c1.%d", n, m), S("dec.resblocks.%d.convs1.%d", n, m), ch, ch, rk, true);
-                    add_conv(wf, S("dec.rb.%d.c2.%d", n, m), S("dec.resblocks.%d.convs2.%d", n, m), ch, ch, rk, true);
+                    add_conv(wf, S("dec.rb.%d.c1.%d", n, m), S("dec.resblocks.%d.convs1.%d", n, m), ch, ch, rk, true, EPI_STD, ROLE_RESBLOCK);
+                    add_conv(wf, S("dec.rb.%d.c2.%d", n, m), S("dec.resblocks.%d.convs2.%d", n, m), ch, ch, rk, true, EPI_STD, ROLE_RESBLOCK);
                 }
             }
         }
@@ -715,29 +707,44 @@ Engine::~Engine() { release(); }
 // =================================================================================================
 // launch helpers
 // =================================================================================================
-bool Engine::enc_gemm(const ConvW& w, const ConvArgs& a) const {
-    // phoneme-sized convs, and the pointwise convs around the coupling layers' WaveNet stacks (frames: K = 1 only)
-    return !force_generic_ && !no_enc_gemm_ && (!phase_b_ || (w.K == 1 && !no_flow_gemm_)) && math_on_bf16(pmath()) && w.packed_b3s != NO_OFF &&
-           a.epi == EPI_STD && w.epi == EPI_STD && !a.shuf_s && a.Tin < 0 && !a.accumulate && enc_conv_b3_supported(w.Cin, w.Cout, w.K, a.dil) &&
-           a.ksplit == enc_conv_b3_slices(w.Cin) && (a.ksplit == 1 || a.part);  // a split conv only where the caller adds up the slices
-}
-
-// a filled-in conv of the decoder that k_rb_conv takes (MATH_BF16X3 only: the other modes keep their kernels)
-bool Engine::rbc_ok(const ConvW& w, const ConvArgs& a) const {
-    return phase_b_ && !force_generic_ && !no_rbc_ && math_ == MATH_BF16X3 && w.packed_p != NO_OFF && rb_conv_supported(a);
-}
-
-void Engine::conv(const char* label, const ConvW& w, ConvArgs a) {
+void Engine::fill_conv(const ConvW& w, ConvArgs& a) const {
     // frames-sized tensors: the kernel is a function of the layer, not of the batch's padding.  Phoneme-sized ones (the text
     // encoder) stay on the f32 kernels except the wide FFN conv (192 -> 768, k3: K Cin >= 512 and >= 4 row blocks), whose
     // grid fills most of the chip even at one column tile per row — again a rule of the layer alone
-    const bool wide_enc = !phase_b_ && enc_b3_ && w.K * w.Cin >= 512 && w.Cout >= 512 && a.epi == EPI_STD;
+    const bool wide_enc = !phase_b_ && w.K * w.Cin >= 512 && w.Cout >= 512 && a.epi == EPI_STD;
     a.fixed_rule = (phase_b_ || wide_enc) ? 1 : 0;
     a.Cin = w.Cin;
     a.Cout = w.Cout;
     a.K = w.K;
     a.bias = P(w.bias);
     if (a.pad < 0) a.pad = (w.K * a.dil - a.dil) / 2;
+}
+
+// The one place that decides which kernel a dense conv runs on; `a` is filled in (fill_conv).
+ConvKernel Engine::pick_conv(const ConvW& w, const ConvArgs& a) const {
+    // every input channel resident in LDS (kernels_rbc.cpp), MATH_BF16X3 only: the other modes keep their kernels
+    const bool resident = phase_b_ && !sw_.force_generic && !sw_.no_rbc && math_ == MATH_BF16X3 && w.packed_p != NO_OFF;
+    if (resident && a.shuf_s && ups_pl_supported(a)) return UPS_PL;  // polyphase upsamplers 128 -> 64, 64 -> 32 (k_ups_pl)
+    if (resident && rb_conv_supported(a)) return RB_CONV;            // 128-channel resblock convs, one launch per conv (k_rb_conv)
+    // phoneme-sized convs, and the pointwise convs around the coupling layers' WaveNet stacks (frames: K = 1 only): one 192-channel
+    // slice per workgroup, staged once (k_enc_b3); a split conv only where the caller adds up the slices
+    if (!sw_.force_generic && !sw_.no_enc_gemm && (!phase_b_ || (w.K == 1 && !sw_.no_flow_gemm)) && math_on_bf16(pmath()) &&
+        w.packed_b3s != NO_OFF && a.epi == EPI_STD && w.epi == EPI_STD && !a.shuf_s && a.Tin < 0 && !a.accumulate &&
+        enc_conv_b3_supported(w.Cin, w.Cout, w.K, a.dil) && a.ksplit == enc_conv_b3_slices(w.Cin) && (a.ksplit == 1 || a.part))
+        return ENC_B3;
+    if (sw_.force_generic || w.packed == NO_OFF) return GENERIC;
+    // split-bf16 staged kernel where it pays: convs with little work per staged chunk (1x1 convs, the last
+    // upsampler: K * Cin < 256) spend more on splitting the chunk than the faster matrix-core loop saves
+    // (measured: flow.pre / post, res_skip, upsample 64 -> 32); MI355VITS_B3_MIN_WORK overrides the threshold (tests).
+    // math_on_bf16(a.math): the caller's opt-in (MI355VITS_WN_B3)
+    if (math_on_bf16(pmath()) && w.packed_b3s != NO_OFF &&
+        (math_on_bf16(a.math) || ((w.K * w.Cin >= sw_.b3_min_work || (a.shuf_s && w.Cin % 64 == 0)) && a.epi == EPI_STD)))
+        return (math_ == MATH_F16X2 && w.packed_h2s != NO_OFF && a.epi == EPI_STD && !sw_.no_f16x2_convs) ? STAGED_F16X2 : STAGED_B3;
+    return MFMA_F32;
+}
+
+void Engine::conv(const char* label, const ConvW& w, ConvArgs a) {
+    fill_conv(w, a);
     if ((a.epi == EPI_GATE) != (w.epi == EPI_GATE)) throw EngineError(MI355VITS_ERR_INTERNAL, "conv epilogue / packing mismatch");
     const double flops = 2.0 * a.B * (double)a.T * w.Cout * w.Cin * w.K;
     double ch_io = (double)w.Cin + (a.epi == EPI_GATE ? a.H : w.Cout);
@@ -746,49 +753,26 @@ void Engine::conv(const char* label, const ConvW& w, ConvArgs a) {
     if (a.epi == EPI_RESSKIP) ch_io += w.Cout;  // h and skip are read-modify-write
     const double bytes = 4.0 * a.B * (double)a.T * ch_io + 4.0 * (double)w.Cout * w.Cin * w.K;
     ProfScope ps(prof_, label, flops, bytes);
-    if (a.shuf_s && phase_b_ && !force_generic_ && !no_rbc_ && math_ == MATH_BF16X3 && w.packed_p != NO_OFF && ups_pl_supported(a)) {
-        a.w = P(w.packed_p);  // polyphase upsamplers 128 -> 64, 64 -> 32: every input channel resident (k_ups_pl)
-        a.math = MATH_BF16X3;
-        if (d_slen_ && a.in_len >= d_slen_ && a.in_len < d_slen_ + h_slen_.size()) a.in_len_host = h_slen_.data() + (a.in_len - d_slen_);
-        launch_ups_pl(a, stream_);
-        return;
-    }
-    if (rbc_ok(w, a)) {  // 128-channel resblock convs: every input channel resident, one launch per conv (k_rb_conv)
-        a.w = P(w.packed_p);
-        a.math = MATH_BF16X3;
+    const ConvKernel kernel = pick_conv(w, a);
+    switch (kernel) {  // the weights in the kernel's format, its math
+    case UPS_PL:
+    case RB_CONV:
+        a.w = P(w.packed_p); a.math = MATH_BF16X3;
         // the host's copy of the row lengths (the per-stage lengths are made on the host and uploaded as one table): the launcher
         // counts the (row, column block) items that have work from it
         if (d_slen_ && a.in_len >= d_slen_ && a.in_len < d_slen_ + h_slen_.size()) a.in_len_host = h_slen_.data() + (a.in_len - d_slen_);
-        launch_rb_conv(a, stream_);
-        return;
+        break;
+    case ENC_B3: a.wb3 = P(w.packed_b3s); a.math = pmath(); break;
+    case STAGED_B3: a.w = P(w.packed); a.wb3 = P(w.packed_b3s); a.math = pmath(); break;
+    case STAGED_F16X2: a.w = P(w.packed); a.wb3 = P(w.packed_h2s); a.math = MATH_F16X2; break;  // two fp16 terms per operand
+    case MFMA_F32: a.w = P(w.packed); a.math = MATH_F32; break;
+    case GENERIC: a.w = P(w.raw); break;
     }
-    if (enc_gemm(w, a)) {  // phoneme-sized dense convs: one 192-channel slice per workgroup, staged once (k_enc_b3)
-        a.wb3 = P(w.packed_b3s);
-        a.math = pmath();
-        launch_enc_conv_b3(a, stream_);
-        return;
-    }
-    if (!force_generic_ && w.packed != NO_OFF) {
-        a.w = P(w.packed);
-        // split-bf16 staged kernel where it pays: convs with little work per staged chunk (1x1 convs, the last
-        // upsampler: K * Cin < 256) spend more on splitting the chunk than the faster matrix-core loop saves
-        // (measured: flow.pre / post, res_skip, upsample 64 -> 32); MI355VITS_B3_MIN_WORK overrides the threshold (tests)
-        if (math_on_bf16(pmath()) && w.packed_b3s != NO_OFF &&
-            (math_on_bf16(a.math) || ((w.K * w.Cin >= b3_min_work_ || (a.shuf_s && w.Cin % 64 == 0)) && a.epi == EPI_STD))) {
-            a.wb3 = P(w.packed_b3s);
-            a.math = pmath();
-            if (math_ == MATH_F16X2 && w.packed_h2s != NO_OFF && a.epi == EPI_STD && !no_f16x2_convs_) {  // two fp16 terms per operand
-                a.wb3 = P(w.packed_h2s);
-                a.math = MATH_F16X2;
-            }
-        } else {
-            a.math = MATH_F32;
-        }
-        launch_conv1d_mfma(a, stream_);
-    } else {
-        a.w = P(w.raw);
-        launch_conv1d_generic(a, stream_);
-    }
+    if (kernel == UPS_PL) launch_ups_pl(a, stream_);
+    else if (kernel == RB_CONV) launch_rb_conv(a, stream_);
+    else if (kernel == ENC_B3) launch_enc_conv_b3(a, stream_);
+    else if (kernel == GENERIC) launch_conv1d_generic(a, stream_);
+    else launch_conv1d_mfma(a, stream_);
 }
 
 void Engine::tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len, int factor) {
@@ -868,7 +852,7 @@ void Engine::text_encoder(int B, int Tx) {
         } else {
             const double fl = 4.0 * B * (double)Tx * Tx * H;
             ProfScope ps(prof_, "enc.attention", fl, 4.0 * B * 4 * H * Tx);
-            if (!force_generic_ && rel_attention_mfma_supported(Tx, H, c.n_heads, c.window_size))
+            if (!sw_.force_generic && rel_attention_mfma_supported(Tx, H, c.n_heads, c.window_size))
                 launch_rel_attention_mfma(d_qkv_, vec(a + ".emb_rel_k"), vec(a + ".emb_rel_v"), d_len_, B, Tx, H, c.n_heads,
                                           c.window_size, d_att_, stream_);
             else
@@ -881,10 +865,10 @@ void Engine::text_encoder(int B, int Tx) {
         o.res = d_x_; o.res_bs = xbs; o.res_ld = Tx;
         o.B = B; o.T = Tx;
         const ConvW& wo = cw(S("enc.%d.o", i));
-        if (enc_gemm(wo, o) && !no_enc_o_ln_ && enc_o_ln_supported(wo.Cin, wo.Cout, wo.K)) {
+        fill_conv(wo, o);
+        if (pick_conv(wo, o) == ENC_B3 && !sw_.no_enc_o_ln && enc_o_ln_supported(wo.Cin, wo.Cout, wo.K)) {
             // o-proj + residual + LayerNorm in one launch, in place on x (k_enc_o_ln)
             o.y = d_x_;
-            o.Cin = wo.Cin; o.Cout = wo.Cout; o.K = wo.K; o.bias = P(wo.bias);
             o.wb3 = P(wo.packed_b3s);
             o.math = tmath();
             ProfScope ps(prof_, "enc.o_ln", 2.0 * B * (double)Tx * H * H, 4.0 * B * 3 * H * Tx);
@@ -916,7 +900,8 @@ void Engine::text_encoder(int B, int Tx) {
         if (d_part_ && w2.Cout == H && enc_conv_b3_slices(w2.Cin) > 1 && enc_conv_b3_slices(w2.Cin) * 192 == F) {
             f2.ksplit = enc_conv_b3_slices(w2.Cin);
             f2.part = d_part_;
-            split2 = enc_gemm(w2, f2);
+            fill_conv(w2, f2);
+            split2 = pick_conv(w2, f2) == ENC_B3;
             if (!split2) { f2.ksplit = 1; f2.part = nullptr; }
         }
         conv("enc.ffn2", w2, f2);
@@ -953,7 +938,7 @@ void Engine::dds(const std::string& key, float* X, float* Y1, float* Y2, int B, 
     const int C = c.hidden_channels;
     const long bs = (long)C * T;
     int dil = 1;
-    if (!force_generic_ && !no_fused_dds_ && c.dp_dds_layers >= 2 && dds_layer_fused_supported(C) &&
+    if (!sw_.force_generic && !sw_.no_fused_dds && c.dp_dds_layers >= 2 && dds_layer_fused_supported(C) &&
         cw(key + S(".convs_1x1.%d", 0)).packed != NO_OFF) {
         // one launch per layer; x ping-pongs through the scratch buffers and the last layer lands in X again
         const float* src = X;
@@ -1041,12 +1026,12 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
     const long bs = (long)H * Tx;
     const int nth = 3 * c.dp_num_bins - 1;
     // the whole stack in one launch each (k_dds_stack): pre + DDS layers + proj, and for a ConvFlow the spline too
-    const bool stack = !force_generic_ && !no_fused_dds_ && !no_dds_stack_ &&
+    const bool stack = !sw_.force_generic && !sw_.no_fused_dds && !sw_.no_dds_stack &&
                        dds_stack_supported(H, c.dp_kernel_size, c.dp_dds_layers, H) && nth <= H && c.dp_num_bins <= 16 &&
                        cw("dp.pre").packed != NO_OFF && cw("dp.proj").packed != NO_OFF && cw("dp.pre").packed_b3s != NO_OFF &&
                        cw("dp.proj").packed_b3s != NO_OFF;
     // the stack's 1x1 convs: bf16 planes in the split-bf16 math modes (k_dds_stack_b3), f32 A fragments in MATH_F32
-    const bool stack_b3 = math_on_bf16(tmath()) && !no_dds_stack_b3_;
+    const bool stack_b3 = math_on_bf16(tmath()) && !sw_.no_dds_stack_b3;
     auto stack_w = [&](const ConvW& w) -> const float* {
         const size_t off = stack_b3 ? w.packed_b3s : w.packed;
         return off == NO_OFF ? nullptr : P(off);
@@ -1164,118 +1149,270 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
 // =================================================================================================
 // K6/K7 expand + K8 flow^-1 + K9-K12 decoder
 // =================================================================================================
+// stage i's profile label out of {stage 0, 1, 2, later}: tests and bench.py key their kernel tables by these strings
+static const char* stage_label(int i, const char* const (&t)[4]) { return t[std::min(i, 3)]; }
+
+// one residual coupling layer, inverted: x1 = (x1 - post(WN(pre(x0)))) * mask
+void Engine::coupling_layer(int j, int B, int Ty) {
+    const mi355vits_config& c = cfg_;
+    const int H = c.hidden_channels, I = c.inter_channels, half = I / 2;
+    const long zbs = (long)I * Ty, hbs = (long)H * Ty;
+    const bool rev = ((c.flow_n_flows - 1 - j) % 2) == 0;
+    float* x0 = d_z_ + (rev ? (long)half * Ty : 0);
+    float* x1 = d_z_ + (rev ? 0 : (long)half * Ty);
+    ConvArgs pre;
+    pre.x = x0; pre.x_bs = zbs; pre.x_ld = Ty;
+    pre.y = d_fh_; pre.y_bs = hbs; pre.y_ld = Ty;
+    pre.out_len = d_ylen_;
+    pre.B = B; pre.T = Ty;
+    conv("flow.pre", cw(S("flow.%d.pre", j)), pre);
+    float* hcur = d_fh_;
+    float* hnext = d_fh2_;
+    for (int l = 0; l < c.flow_wn_layers; ++l) {
+        int dil = 1;
+        for (int q = 0; q < l; ++q) dil *= c.flow_wn_dilation_rate;
+        const ConvW& win = cw(S("flow.%d.in.%d", j, l));
+        const ConvW& wrs = cw(S("flow.%d.rs.%d", j, l));
+        const float* cond_l = d_cond_flow_.empty() ? nullptr : d_cond_flow_[j] + (long)l * 2 * H;
+        // in-layer + res/skip through the staged split-bf16 kernel (two launches, `u` through HBM: 38 MB per layer, nothing next
+        // to the matrix-core time saved) instead of a fused layer: measured 2.09 + 1.70 ms vs 3.65 ms per step for the fused f32
+        // layer — no gain (small grids, scalar res/skip epilogue); opt-in for A/B and for the tests
+        const bool wn_b3 = sw_.wn_b3 && math_on_bf16(kmath()) && win.packed_b3s != NO_OFF && wrs.packed_b3s != NO_OFF &&
+                           conv1d_b3_supported(win.Cin, win.Cout, win.K, dil, Ty) && !sw_.force_generic;
+        const bool fused = !sw_.force_generic && !sw_.no_fused_wn && !wn_b3;
+        // fused layer on the bf16 matrix cores (k_wn_layer_b3), else on the f32 ones (k_wn_layer).  Chosen by the layer shape
+        // alone (never by the grid size), so a row's bits do not depend on what it is batched with.
+        const bool b3 = fused && math_on_bf16(kmath()) && win.packed_b3w != NO_OFF && wrs.packed_b3s != NO_OFF &&
+                        wn_layer_b3_supported(H, win.K, dil);
+        if (b3 || (fused && wn_layer_fused_supported(H, win.K, dil))) {
+            const bool h2 = b3 && math_ == MATH_F16X2 && win.packed_h2s != NO_OFF && wrs.packed_h2s != NO_OFF;  // two fp16 terms per operand
+            WnArgs w;
+            w.h_in = hcur; w.h_out = hnext; w.h_bs = hbs; w.h_ld = Ty;
+            w.skip = d_fskip_; w.s_bs = hbs; w.s_ld = Ty;
+            w.w_in = P(h2 ? win.packed_h2s : (b3 ? win.packed_b3w : win.packed)); w.b_in = P(win.bias);
+            w.w_rs = P(h2 ? wrs.packed_h2s : (b3 ? wrs.packed_b3s : wrs.packed)); w.b_rs = P(wrs.bias);
+            w.cond = cond_l; w.cond_bs = 2L * H * c.flow_wn_layers;
+            w.len = d_ylen_;
+            w.B = B; w.H = H; w.T = Ty; w.K = win.K; w.dil = dil; w.Crs = wrs.Cout; w.skip_init = (l == 0);
+            if (b3) w.math = h2 ? (int)MATH_F16X2 : kmath();
+            const double fl = 2.0 * B * (double)Ty * H * ((double)win.Cout * win.K + wrs.Cout);
+            ProfScope ps(prof_, b3 ? "flow.wn_layer_b3" : "flow.wn_layer", fl, 4.0 * B * (double)Ty * H * 4);
+            if (b3) launch_wn_layer_b3(w, stream_);
+            else launch_wn_layer(w, stream_);
+            if (wrs.Cout == 2 * H) std::swap(hcur, hnext);  // the last layer leaves h untouched
+            continue;
+        }
+        ConvArgs in;
+        in.x = hcur; in.x_bs = hbs; in.x_ld = Ty;
+        in.y = d_fu_; in.y_bs = hbs; in.y_ld = Ty;
+        in.epi = EPI_GATE; in.H = H; in.dil = dil;
+        if (cond_l) {
+            in.cond = cond_l;
+            in.cond_bs = 2L * H * c.flow_wn_layers;
+        }
+        in.B = B; in.T = Ty;
+        if (wn_b3) in.math = kmath();
+        conv("flow.in_gate", win, in);
+        ConvArgs rs;
+        rs.x = d_fu_; rs.x_bs = hbs; rs.x_ld = Ty;
+        rs.y = hcur; rs.y_bs = hbs; rs.y_ld = Ty;
+        rs.y2 = d_fskip_; rs.y2_bs = hbs; rs.y2_ld = Ty;
+        rs.epi = EPI_RESSKIP; rs.H = H; rs.skip_init = (l == 0);
+        rs.out_len = d_ylen_;
+        rs.B = B; rs.T = Ty;
+        if (wn_b3) rs.math = kmath();
+        conv("flow.res_skip", wrs, rs);
+    }
+    ConvArgs post;
+    post.x = d_fskip_; post.x_bs = hbs; post.x_ld = Ty;
+    post.y = x1; post.y_bs = zbs; post.y_ld = Ty;
+    post.res = x1; post.res_bs = zbs; post.res_ld = Ty; post.res_sub = 1;
+    post.in_len = d_ylen_; post.out_len = d_ylen_;
+    post.B = B; post.T = Ty;
+    conv("flow.post_couple", cw(S("flow.%d.post", j)), post);
+}
+
+// conv m of ResBlock2 j in stage i, conv by conv: x = x + conv_{k,d}(lrelu(x)), from bufA through bufB / bufT, the block's last
+// conv scaled and accumulated onto the stage output bufC
+ConvArgs Engine::rb2_conv_args(int i, int j, int m, int B, int ch, long T) const {
+    const mi355vits_config& c = cfg_;
+    float* const pp[2] = {d_bufB_, d_bufT_};
+    const bool last = (m == c.resblock_n_dilations[j] - 1);
+    const float* src = m == 0 ? d_bufA_ : pp[(m - 1) & 1];
+    ConvArgs a;
+    a.x = src; a.x_bs = (long)ch * T; a.x_ld = (int)T;
+    a.y = last ? d_bufC_ : pp[m & 1]; a.y_bs = (long)ch * T; a.y_ld = (int)T;
+    a.res = src; a.res_bs = (long)ch * T; a.res_ld = (int)T;
+    a.in_slope = 0.1f; a.dil = c.resblock_dilations[j * MI355VITS_MAX_STAGES + m];
+    a.in_len = d_slen_ + (long)(i + 1) * B;  // rows end at their own length (batched == unbatched)
+    if (last) { a.out_scale = 1.0f / c.n_resblock_kernels; a.accumulate = (j > 0); }
+    a.B = B; a.T = (int)T;
+    return a;
+}
+
+// ResBlock2 stages: the leading resblocks of stage i (input bufA [B,ch,T], output bufC) in one launch where a fused kernel takes
+// them.  Returns how many it took; decoder_stage runs the rest conv by conv.
+int Engine::mrf_stage(int i, int B, int ch, long T) {
+    const mi355vits_config& c = cfg_;
+    const int nk = c.n_resblock_kernels;
+    if (sw_.force_generic || sw_.no_fused_mrf || c.resblock != 2 || nk > MRF_MAX_RB) return 0;
+    MrfArgs m;
+    for (int j = 0; j < nk; ++j) {
+        if (c.resblock_n_dilations[j] != 2) return 0;
+        m.k[j] = c.resblock_kernel_sizes[j];
+        m.d1[j] = c.resblock_dilations[j * MI355VITS_MAX_STAGES + 0];
+        m.d2[j] = c.resblock_dilations[j * MI355VITS_MAX_STAGES + 1];
+    }
+    m.x = d_bufA_; m.x_bs = (long)ch * T; m.x_ld = (int)T;
+    m.y = d_bufC_; m.y_bs = (long)ch * T; m.y_ld = (int)T;
+    m.len = d_slen_ + (long)(i + 1) * B; m.B = B; m.C = ch; m.T = (int)T;
+    m.len_host = h_slen_.data() + (size_t)(i + 1) * B;
+    auto rb = [&](int j, int q) -> const ConvW& { return cw(S("dec.rb.%d.c.%d", i * nk + j, q)); };
+    // resblocks 0 .. n - 1 with their weights in format fmt, and their flops; false if a conv has no such copy
+    double flops = 0;
+    auto take = [&](int n, size_t ConvW::*fmt) {
+        flops = 0;
+        for (int j = 0; j < n; ++j) {
+            for (int q = 0; q < 2; ++q) {
+                const ConvW& w = rb(j, q);
+                if (w.*fmt == NO_OFF) return false;
+                m.w[j][q] = P(w.*fmt);
+                m.bias[j][q] = P(w.bias);
+            }
+            flops += 2.0 * 2.0 * B * (double)T * ch * ch * m.k[j];
+        }
+        m.nrb = n;
+        return true;
+    };
+    const double bytes = 8.0 * B * (double)T * ch;
+    // MATH_BF16X3: the whole stage on planes split once, weights in registers (k_mrf_p)
+    if (math_ == MATH_BF16X3 && !sw_.no_mrf_p && mrf_p_supported(ch, nk, m.k, m.d1, m.d2) && take(nk, &ConvW::packed_p)) {
+        m.math = MATH_BF16X3;
+        // large grids: the row sweep (k_mrf_s: fragments register-resident per segment, no halo recompute); small ones:
+        // (row, column block) items (k_mrf_p).  The two agree bit for bit, so the choice may follow the grid.
+        // 64 channels: one pass per resblock (k_mrf_s).  32 channels: k_mrf_p (its single-pass sweep, k_mrf_s1, measured equal in
+        // round 4 — 2.33 vs 2.34 ms, 2.37 vs 2.36 with 48-column steps — and was deleted in round 5: DESIGN.md §6)
+        const bool sw_ok = ch != 32 && mrf_s_supported(ch, nk, m.k, m.d1, m.d2);
+        int seg = !sw_ok ? 0 : mrf_s_segment(ch, B, (int)T, current_device_cu_count(), m.len_host);
+        if (const char* f = lab_getenv("MI355VITS_MRF_SWEEP_SEG")) seg = sw_ok ? atoi(f) : 0;  // lab / tests (read per call)
+        if (seg > 0) {
+            m.seg = seg;
+            ProfScope ps(prof_, stage_label(i, {"dec.mrf_s", "dec.mrf_s.s1", "dec.mrf_s.s2", "dec.mrf_s"}), flops, bytes);
+            launch_mrf_s(m, stream_);
+        } else {
+            ProfScope ps(prof_, stage_label(i, {"dec.mrf_p", "dec.mrf_p.s1", "dec.mrf_p.s2", "dec.mrf_p"}), flops, bytes);
+            launch_mrf_p(m, stream_);
+        }
+        return nk;
+    }
+    // 128 channels in MATH_BF16X3: conv by conv on k_rb_conv (every input channel resident in LDS, kernels_rbc.cpp)
+    bool rbc_stage = true;
+    for (int j = 0; j < nk && rbc_stage; ++j)
+        for (int q = 0; q < 2 && rbc_stage; ++q) {
+            const ConvW& w = rb(j, q);
+            ConvArgs a = rb2_conv_args(i, j, q, B, ch, T);  // what decoder_stage launches if nothing is fused
+            fill_conv(w, a);
+            rbc_stage = pick_conv(w, a) == RB_CONV;
+        }
+    if (rbc_stage) return 0;
+    // the longest prefix of resblocks whose tiles fit LDS together (128 channels: only the narrow ones)
+    int p = nk;
+    while (p > 0 && !(mrf_fused_supported(ch, p, m.k, m.d1, m.d2) && rb(0, 0).packed4 != NO_OFF)) --p;
+    if (p == 0) return 0;
+    if (math_ == MATH_F16X2 && take(p, &ConvW::packed_h2)) m.math = MATH_F16X2;
+    else if (math_on_bf16(kmath()) && take(p, &ConvW::packed_b3)) m.math = kmath();
+    else if (take(p, &ConvW::packed4)) m.math = MATH_F32;
+    else return 0;
+    if (p < nk) m.out_scale = 1.0f / nk;
+    ProfScope ps(prof_, stage_label(i, {"dec.mrf_fused.s0", "dec.mrf_fused.s1", "dec.mrf_fused.s2", "dec.mrf_fused"}), flops, bytes);
+    launch_mrf_fused(m, stream_);
+    return p;
+}
+
+void Engine::decoder_stage(int i, int B, int ch, long T) {
+    const mi355vits_config& c = cfg_;
+    const int r = c.upsample_rates[i], k = c.upsample_kernel_sizes[i], nk = c.n_resblock_kernels;
+    const ConvW& up = cw(S("dec.ups.%d.poly", i));
+    if (!sw_.force_generic && up.packed != NO_OFF) {
+        ConvArgs u;
+        u.x = d_bufC_; u.x_bs = (long)ch * T; u.x_ld = (int)T;
+        u.y = d_bufA_; u.y_bs = (long)(ch / 2) * T * r; u.y_ld = (int)(T * r);
+        u.in_slope = 0.1f; u.in_len = d_slen_ + (long)i * B;
+        u.pad = up.K - 1; u.Tin = (int)T;
+        u.shuf_s = r; u.shuf_p = (k - r) / 2; u.shuf_cout = ch / 2; u.shuf_T = (int)(T * r);
+        u.B = B; u.T = (int)T + up.K - 1;
+        conv(stage_label(i, {"dec.upsample.s0", "dec.upsample.s1", "dec.upsample.s2+", "dec.upsample.s2+"}), up, u);
+    } else {
+        ConvTArgs u;
+        u.x = d_bufC_; u.x_bs = (long)ch * T; u.x_ld = (int)T;
+        u.y = d_bufA_; u.y_bs = (long)(ch / 2) * T * r; u.y_ld = (int)(T * r);
+        u.w = vec(S("dec.ups.%d.weight", i)); u.bias = vec(S("dec.ups.%d.bias", i));
+        u.B = B; u.Cin = ch; u.Cout = ch / 2; u.Tin = (int)T; u.K = k; u.stride = r; u.pad = (k - r) / 2;
+        u.in_slope = 0.1f;
+        u.in_len = d_slen_ + (long)i * B;
+        const int taps = (k + r - 1) / r;
+        ProfScope ps(prof_, "dec.upsample", 2.0 * B * (double)T * r * ch * (ch / 2) * taps,
+                     4.0 * B * ((double)ch * T + (double)(ch / 2) * T * r));
+        launch_conv_transpose1d(u, stream_);
+    }
+    ch /= 2;
+    T *= r;
+    const long sbs = (long)ch * T;
+    const int* slen = d_slen_ + (long)(i + 1) * B;  // rows end at their own length (batched == unbatched)
+    tap(S("dec.ups.%d", i).c_str(), d_bufA_, {B, ch, T}, d_ylen_, (int)(T / Ty_));
+    // resblocks 0 .. n_fused-1 of this stage run in the fused kernel, the rest conv by conv
+    for (int j = mrf_stage(i, B, ch, T); j < nk; ++j) {
+        const int n = i * nk + j;
+        const int nd = c.resblock_n_dilations[j];
+        const float* src = d_bufA_;
+        for (int m = 0; m < nd; ++m) {
+            if (c.resblock == 2) {
+                conv(stage_label(i, {"dec.rb.s0", "dec.rb.s1", "dec.rb.s2+", "dec.rb.s2+"}), cw(S("dec.rb.%d.c.%d", n, m)),
+                     rb2_conv_args(i, j, m, B, ch, T));
+                continue;
+            }
+            // xt = c2(lrelu(c1(lrelu(x)))); x = xt + x
+            // the pair's output may overwrite its own residual source in place (c2 reads `mid`, and each
+            // thread reads res[co,t] before writing y[co,t]); only the stage input bufA must survive.
+            const bool last = (m == nd - 1);
+            float* mid = d_bufT_;
+            float* dst = last ? d_bufC_ : d_bufB_;
+            ConvArgs a1;
+            a1.x = src; a1.x_bs = sbs; a1.x_ld = (int)T;
+            a1.y = mid; a1.y_bs = sbs; a1.y_ld = (int)T;
+            a1.in_slope = 0.1f; a1.dil = c.resblock_dilations[j * MI355VITS_MAX_STAGES + m]; a1.in_len = slen;
+            a1.B = B; a1.T = (int)T;
+            conv("dec.rb1.c1", cw(S("dec.rb.%d.c1.%d", n, m)), a1);
+            ConvArgs a2;
+            a2.x = mid; a2.x_bs = sbs; a2.x_ld = (int)T;
+            a2.y = dst; a2.y_bs = sbs; a2.y_ld = (int)T;
+            a2.res = src; a2.res_bs = sbs; a2.res_ld = (int)T;
+            a2.in_slope = 0.1f; a2.dil = 1; a2.in_len = slen;
+            if (last) { a2.out_scale = 1.0f / nk; a2.accumulate = (j > 0); }
+            a2.B = B; a2.T = (int)T;
+            conv("dec.rb1.c2", cw(S("dec.rb.%d.c2.%d", n, m)), a2);
+            src = dst;
+        }
+    }
+    tap(S("dec.mrf.%d", i).c_str(), d_bufC_, {B, ch, T}, d_ylen_, (int)(T / Ty_));
+}
+
+// expand, flows, conv_pre, stages, conv_post
 void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
     struct PhaseB { bool& f; explicit PhaseB(bool& r) : f(r) { f = true; } ~PhaseB() { f = false; } } phase_guard(phase_b_);
     const mi355vits_config& c = cfg_;
-    const int H = c.hidden_channels, I = c.inter_channels, half = I / 2;
-    const int Tx = Tx_;
-    const long zbs = (long)I * Ty, hbs = (long)H * Ty;
+    const int I = c.inter_channels, C0 = c.upsample_initial_channel;
     {
         ProfScope ps(prof_, "expand_prior", 0, 4.0 * B * I * Ty * 3);
-        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, args.noise_z_frames, B, I, Tx, Ty, d_scales_,
+        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, args.noise_z_frames, B, I, Tx_, Ty, d_scales_,
                             args.seed, d_utt_, d_z_, stream_);
     }
     tap("z_p", d_z_, {B, I, Ty}, d_ylen_, 1);
-
-    for (int j = c.flow_n_flows - 1; j >= 0; --j) {
-        const int e = c.flow_n_flows - 1 - j;
-        const bool rev = (e % 2) == 0;
-        float* x0 = d_z_ + (rev ? (long)half * Ty : 0);
-        float* x1 = d_z_ + (rev ? 0 : (long)half * Ty);
-        ConvArgs pre;
-        pre.x = x0; pre.x_bs = zbs; pre.x_ld = Ty;
-        pre.y = d_fh_; pre.y_bs = hbs; pre.y_ld = Ty;
-        pre.out_len = d_ylen_;
-        pre.B = B; pre.T = Ty;
-        conv("flow.pre", cw(S("flow.%d.pre", j)), pre);
-        float* hcur = d_fh_;
-        float* hnext = d_fh2_;
-        for (int l = 0; l < c.flow_wn_layers; ++l) {
-            int dil = 1;
-            for (int q = 0; q < l; ++q) dil *= c.flow_wn_dilation_rate;
-            const ConvW& win = cw(S("flow.%d.in.%d", j, l));
-            const ConvW& wrs = cw(S("flow.%d.rs.%d", j, l));
-            const float* cond_l = d_cond_flow_.empty() ? nullptr : d_cond_flow_[j] + (long)l * 2 * H;
-            // split-bf16 math: the in-layer and the res/skip convs go through the staged bf16 kernel (two launches, `u`
-            // through HBM: 38 MB per layer, nothing next to the matrix-core time saved); the fused kernel is f32-MFMA
-            // in-layer + res/skip through the staged split-bf16 kernel instead of the fused f32 layer: measured 2.09 + 1.70 ms
-            // vs 3.65 ms per step — no gain (small grids, scalar res/skip epilogue); opt-in for A/B and for the tests
-            const bool wn_b3 = wn_b3_ && math_on_bf16(kmath()) && win.packed_b3s != NO_OFF && wrs.packed_b3s != NO_OFF &&
-                               conv1d_b3_supported(win.Cin, win.Cout, win.K, dil, Ty) && !force_generic_;
-            if (!force_generic_ && !no_fused_wn_ && !wn_b3 && math_on_bf16(kmath()) && win.packed_b3w != NO_OFF &&
-                wrs.packed_b3s != NO_OFF && wn_layer_b3_supported(H, win.K, dil)) {
-                // fused layer on the bf16 matrix cores.  Chosen by the layer shape alone (never by the grid size), so a
-                // row's bits do not depend on what it is batched with.
-                WnArgs w;
-                w.h_in = hcur; w.h_out = hnext; w.h_bs = hbs; w.h_ld = Ty;
-                w.skip = d_fskip_; w.s_bs = hbs; w.s_ld = Ty;
-                w.w_in = P(win.packed_b3w); w.b_in = P(win.bias);
-                w.w_rs = P(wrs.packed_b3s); w.b_rs = P(wrs.bias);
-                w.cond = cond_l; w.cond_bs = 2L * H * c.flow_wn_layers;
-                w.len = d_ylen_;
-                w.B = B; w.H = H; w.T = Ty; w.K = win.K; w.dil = dil; w.Crs = wrs.Cout; w.skip_init = (l == 0);
-                w.math = kmath();
-                if (math_ == MATH_F16X2 && win.packed_h2s != NO_OFF && wrs.packed_h2s != NO_OFF) {  // two fp16 terms per operand
-                    w.w_in = P(win.packed_h2s);
-                    w.w_rs = P(wrs.packed_h2s);
-                    w.math = MATH_F16X2;
-                }
-                const double fl = 2.0 * B * (double)Ty * H * ((double)win.Cout * win.K + wrs.Cout);
-                ProfScope ps(prof_, "flow.wn_layer_b3", fl, 4.0 * B * (double)Ty * H * 4);
-                launch_wn_layer_b3(w, stream_);
-                if (wrs.Cout == 2 * H) std::swap(hcur, hnext);
-                continue;
-            }
-            if (!force_generic_ && !no_fused_wn_ && !wn_b3 && wn_layer_fused_supported(H, win.K, dil)) {
-                WnArgs w;
-                w.h_in = hcur; w.h_out = hnext; w.h_bs = hbs; w.h_ld = Ty;
-                w.skip = d_fskip_; w.s_bs = hbs; w.s_ld = Ty;
-                w.w_in = P(win.packed); w.b_in = P(win.bias);
-                w.w_rs = P(wrs.packed); w.b_rs = P(wrs.bias);
-                w.cond = cond_l; w.cond_bs = 2L * H * c.flow_wn_layers;
-                w.len = d_ylen_;
-                w.B = B; w.H = H; w.T = Ty; w.K = win.K; w.dil = dil; w.Crs = wrs.Cout; w.skip_init = (l == 0);
-                const double fl = 2.0 * B * (double)Ty * H * ((double)win.Cout * win.K + wrs.Cout);
-                ProfScope ps(prof_, "flow.wn_layer", fl, 4.0 * B * (double)Ty * H * 4);
-                launch_wn_layer(w, stream_);
-                if (wrs.Cout == 2 * H) std::swap(hcur, hnext);  // the last layer leaves h untouched
-                continue;
-            }
-            ConvArgs in;
-            in.x = hcur; in.x_bs = hbs; in.x_ld = Ty;
-            in.y = d_fu_; in.y_bs = hbs; in.y_ld = Ty;
-            in.epi = EPI_GATE; in.H = H; in.dil = dil;
-            if (cond_l) {
-                in.cond = cond_l;
-                in.cond_bs = 2L * H * c.flow_wn_layers;
-            }
-            in.B = B; in.T = Ty;
-            if (wn_b3) in.math = kmath();
-            conv("flow.in_gate", win, in);
-            ConvArgs rs;
-            rs.x = d_fu_; rs.x_bs = hbs; rs.x_ld = Ty;
-            rs.y = hcur; rs.y_bs = hbs; rs.y_ld = Ty;
-            rs.y2 = d_fskip_; rs.y2_bs = hbs; rs.y2_ld = Ty;
-            rs.epi = EPI_RESSKIP; rs.H = H; rs.skip_init = (l == 0);
-            rs.out_len = d_ylen_;
-            rs.B = B; rs.T = Ty;
-            if (wn_b3) rs.math = kmath();
-            conv("flow.res_skip", wrs, rs);
-        }
-        ConvArgs post;
-        post.x = d_fskip_; post.x_bs = hbs; post.x_ld = Ty;
-        post.y = x1; post.y_bs = zbs; post.y_ld = Ty;
-        post.res = x1; post.res_bs = zbs; post.res_ld = Ty; post.res_sub = 1;
-        post.in_len = d_ylen_; post.out_len = d_ylen_;
-        post.B = B; post.T = Ty;
-        conv("flow.post_couple", cw(S("flow.%d.post", j)), post);
-    }
+    for (int j = c.flow_n_flows - 1; j >= 0; --j) coupling_layer(j, B, Ty);
     tap("z", d_z_, {B, I, Ty}, d_ylen_, 1);
 
-    // ---- decoder
-    const int C0 = c.upsample_initial_channel;
     ConvArgs cp;
-    cp.x = d_z_; cp.x_bs = zbs; cp.x_ld = Ty;
+    cp.x = d_z_; cp.x_bs = (long)I * Ty; cp.x_ld = Ty;
     cp.y = d_bufC_; cp.y_bs = (long)C0 * Ty; cp.y_ld = Ty;
     cp.in_len = d_ylen_;
     cp.cond = d_cond_dec_; cp.cond_bs = C0;
@@ -1285,177 +1422,11 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
 
     int ch = C0;
     long T = Ty;
-    const int nk = c.n_resblock_kernels;
     HIP_CHECK(hipMemsetAsync(d_peaks_, 0, sizeof(unsigned) * B, stream_));
     for (int i = 0; i < c.n_upsamples; ++i) {
-        const int r = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
-        const ConvW& up = cw(S("dec.ups.%d.poly", i));
-        if (!force_generic_ && up.packed != NO_OFF) {
-            ConvArgs u;
-            u.x = d_bufC_; u.x_bs = (long)ch * T; u.x_ld = (int)T;
-            u.y = d_bufA_; u.y_bs = (long)(ch / 2) * T * r; u.y_ld = (int)(T * r);
-            u.in_slope = 0.1f; u.in_len = d_slen_ + (long)i * B;
-            u.pad = up.K - 1; u.Tin = (int)T;
-            u.shuf_s = r; u.shuf_p = (k - r) / 2; u.shuf_cout = ch / 2; u.shuf_T = (int)(T * r);
-            u.B = B; u.T = (int)T + up.K - 1;
-            conv(i == 0 ? "dec.upsample.s0" : (i == 1 ? "dec.upsample.s1" : "dec.upsample.s2+"), up, u);
-        } else {
-            ConvTArgs u;
-            u.x = d_bufC_; u.x_bs = (long)ch * T; u.x_ld = (int)T;
-            u.y = d_bufA_; u.y_bs = (long)(ch / 2) * T * r; u.y_ld = (int)(T * r);
-            u.w = vec(S("dec.ups.%d.weight", i)); u.bias = vec(S("dec.ups.%d.bias", i));
-            u.B = B; u.Cin = ch; u.Cout = ch / 2; u.Tin = (int)T; u.K = k; u.stride = r; u.pad = (k - r) / 2;
-            u.in_slope = 0.1f;
-            u.in_len = d_slen_ + (long)i * B;
-            const int taps = (k + r - 1) / r;
-            ProfScope ps(prof_, "dec.upsample", 2.0 * B * (double)T * r * ch * (ch / 2) * taps,
-                         4.0 * B * ((double)ch * T + (double)(ch / 2) * T * r));
-            launch_conv_transpose1d(u, stream_);
-        }
+        decoder_stage(i, B, ch, T);
         ch /= 2;
-        T *= r;
-        const long sbs = (long)ch * T;
-        const int* slen = d_slen_ + (long)(i + 1) * B;  // rows end at their own length (batched == unbatched)
-        tap(S("dec.ups.%d", i).c_str(), d_bufA_, {B, ch, T}, d_ylen_, (int)(T / Ty));
-        int n_fused = 0;  // resblocks 0 .. n_fused-1 of this stage run in the fused kernel, the rest conv by conv
-        if (!force_generic_ && !no_fused_mrf_ && c.resblock == 2 && nk <= MRF_MAX_RB) {
-            MrfArgs m;
-            bool two = true;
-            for (int j = 0; j < nk; ++j) two = two && c.resblock_n_dilations[j] == 2;
-            if (two) {
-                for (int j = 0; j < nk; ++j) {
-                    m.k[j] = c.resblock_kernel_sizes[j];
-                    m.d1[j] = c.resblock_dilations[j * MI355VITS_MAX_STAGES + 0];
-                    m.d2[j] = c.resblock_dilations[j * MI355VITS_MAX_STAGES + 1];
-                }
-                // MATH_BF16X3: the whole stage on planes split once, weights in registers (k_mrf_p)
-                bool all_p = math_ == MATH_BF16X3 && !no_mrf_p_ && mrf_p_supported(ch, nk, m.k, m.d1, m.d2);
-                for (int j = 0; j < nk && all_p; ++j)
-                    for (int q = 0; q < 2; ++q) all_p = all_p && cw(S("dec.rb.%d.c.%d", i * nk + j, q)).packed_p != NO_OFF;
-                if (all_p) {
-                    double flops = 0;
-                    for (int j = 0; j < nk; ++j) {
-                        for (int q = 0; q < 2; ++q) {
-                            const ConvW& w = cw(S("dec.rb.%d.c.%d", i * nk + j, q));
-                            m.w[j][q] = P(w.packed_p);
-                            m.bias[j][q] = P(w.bias);
-                        }
-                        flops += 2.0 * 2.0 * B * (double)T * ch * ch * m.k[j];
-                    }
-                    m.nrb = nk;
-                    m.math = MATH_BF16X3;
-                    m.x = d_bufA_; m.x_bs = sbs; m.x_ld = (int)T;
-                    m.y = d_bufC_; m.y_bs = sbs; m.y_ld = (int)T;
-                    m.len = slen; m.B = B; m.C = ch; m.T = (int)T;
-                    m.len_host = h_slen_.data() + (size_t)(i + 1) * B;
-                    // large grids: the row sweep (k_mrf_s: fragments register-resident per segment, no halo recompute); small ones:
-                    // (row, column block) items (k_mrf_p).  The two agree bit for bit, so the choice may follow the grid.
-                    // 64 channels: one pass per resblock (k_mrf_s).  32 channels: k_mrf_p (its single-pass sweep, k_mrf_s1, measured equal in
-                    // round 4 — 2.33 vs 2.34 ms, 2.37 vs 2.36 with 48-column steps — and was deleted in round 5: DESIGN.md §6)
-                    bool sw_ok = ch != 32 && mrf_s_supported(ch, nk, m.k, m.d1, m.d2);
-                    int seg = !sw_ok ? 0 : mrf_s_segment(ch, B, (int)T, current_device_cu_count(), m.len_host);
-                    if (const char* f = lab_getenv("MI355VITS_MRF_SWEEP_SEG")) seg = sw_ok ? atoi(f) : 0;  // lab / tests
-                    if (seg > 0) {
-                        m.seg = seg;
-                        ProfScope ps(prof_, i == 1 ? "dec.mrf_s.s1" : (i == 2 ? "dec.mrf_s.s2" : "dec.mrf_s"), flops, 8.0 * B * (double)T * ch);
-                        launch_mrf_s(m, stream_);
-                    } else {
-                        ProfScope ps(prof_, i == 1 ? "dec.mrf_p.s1" : (i == 2 ? "dec.mrf_p.s2" : "dec.mrf_p"), flops, 8.0 * B * (double)T * ch);
-                        launch_mrf_p(m, stream_);
-                    }
-                    n_fused = nk;
-                }
-                // 128 channels in MATH_BF16X3: conv by conv on k_rb_conv (every input channel resident in LDS, kernels_rbc.cpp)
-                bool rbc_stage = !n_fused && math_ == MATH_BF16X3 && !no_rbc_;
-                for (int j = 0; j < nk && rbc_stage; ++j)
-                    for (int q = 0; q < 2; ++q) {
-                        const ConvW& w = cw(S("dec.rb.%d.c.%d", i * nk + j, q));
-                        ConvArgs probe;
-                        probe.Cin = w.Cin; probe.Cout = w.Cout; probe.K = w.K; probe.dil = q == 0 ? m.d1[j] : m.d2[j];
-                        probe.pad = (w.K - 1) / 2 * probe.dil; probe.res = d_bufA_; probe.in_len = slen; probe.T = (int)T;
-                        probe.x_ld = probe.res_ld = probe.y_ld = (int)T;  // (the stage's tensors are dense rows: what the launches below pass)
-                        rbc_stage = rbc_stage && rbc_ok(w, probe);
-                    }
-                // the longest prefix of resblocks whose tiles fit LDS together (128 channels: only the narrow ones)
-                int p = (n_fused || rbc_stage) ? 0 : nk;
-                while (p > 0 && !(mrf_fused_supported(ch, p, m.k, m.d1, m.d2) && cw(S("dec.rb.%d.c.%d", i * nk, 0)).packed4 != NO_OFF)) --p;
-                if (p > 0) {
-                    double flops = 0;
-                    bool b3 = math_on_bf16(kmath());
-                    bool h2 = math_ == MATH_F16X2;
-                    for (int j = 0; j < p; ++j)
-                        for (int q = 0; q < 2; ++q) {
-                            b3 = b3 && cw(S("dec.rb.%d.c.%d", i * nk + j, q)).packed_b3 != NO_OFF;
-                            h2 = h2 && cw(S("dec.rb.%d.c.%d", i * nk + j, q)).packed_h2 != NO_OFF;
-                        }
-                    m.math = h2 ? (int)MATH_F16X2 : (b3 ? kmath() : (int)MATH_F32);
-                    for (int j = 0; j < p; ++j) {
-                        for (int q = 0; q < 2; ++q) {
-                            const ConvW& w = cw(S("dec.rb.%d.c.%d", i * nk + j, q));
-                            m.w[j][q] = P(h2 ? w.packed_h2 : (b3 ? w.packed_b3 : w.packed4));
-                            m.bias[j][q] = P(w.bias);
-                        }
-                        flops += 2.0 * 2.0 * B * (double)T * ch * ch * m.k[j];
-                    }
-                    m.nrb = p;
-                    if (p < nk) m.out_scale = 1.0f / nk;
-                    m.x = d_bufA_; m.x_bs = sbs; m.x_ld = (int)T;
-                    m.y = d_bufC_; m.y_bs = sbs; m.y_ld = (int)T;
-                    m.len = slen; m.B = B; m.C = ch; m.T = (int)T;
-                    m.len_host = h_slen_.data() + (size_t)(i + 1) * B;
-                    const double bytes = 8.0 * B * (double)T * ch;
-                    ProfScope ps(prof_, i == 1 ? "dec.mrf_fused.s1" : (i == 2 ? "dec.mrf_fused.s2" : (i == 0 ? "dec.mrf_fused.s0" : "dec.mrf_fused")), flops,
-                                 bytes);
-                    launch_mrf_fused(m, stream_);
-                    n_fused = p;
-                }
-            }
-        }
-        for (int j = n_fused; j < nk; ++j) {
-            const int n = i * nk + j;
-            const int nd = c.resblock_n_dilations[j];
-            const float* src = d_bufA_;
-            float* pp[2] = {d_bufB_, d_bufT_};
-            for (int m = 0; m < nd; ++m) {
-                const int dil = c.resblock_dilations[j * MI355VITS_MAX_STAGES + m];
-                const bool last = (m == nd - 1);
-                if (c.resblock == 2) {
-                    // x = x + conv_{k,d}(lrelu(x))
-                    float* dst = last ? d_bufC_ : pp[m & 1];
-                    ConvArgs a;
-                    a.x = src; a.x_bs = sbs; a.x_ld = (int)T;
-                    a.y = dst; a.y_bs = sbs; a.y_ld = (int)T;
-                    a.res = src; a.res_bs = sbs; a.res_ld = (int)T;
-                    a.in_slope = 0.1f; a.dil = dil; a.in_len = slen;
-                    if (last) { a.out_scale = 1.0f / nk; a.accumulate = (j > 0); }
-                    a.B = B; a.T = (int)T;
-                    conv(i == 0 ? "dec.rb.s0" : (i == 1 ? "dec.rb.s1" : "dec.rb.s2+"), cw(S("dec.rb.%d.c.%d", n, m)), a);
-                    src = dst;
-                } else {
-                    // xt = c2(lrelu(c1(lrelu(x)))); x = xt + x
-                    // the pair's output may overwrite its own residual source in place (c2 reads `mid`, and each
-                    // thread reads res[co,t] before writing y[co,t]); only the stage input bufA must survive.
-                    float* mid = d_bufT_;
-                    float* dst = last ? d_bufC_ : d_bufB_;
-                    ConvArgs a1;
-                    a1.x = src; a1.x_bs = sbs; a1.x_ld = (int)T;
-                    a1.y = mid; a1.y_bs = sbs; a1.y_ld = (int)T;
-                    a1.in_slope = 0.1f; a1.dil = dil; a1.in_len = slen;
-                    a1.B = B; a1.T = (int)T;
-                    conv("dec.rb1.c1", cw(S("dec.rb.%d.c1.%d", n, m)), a1);
-                    ConvArgs a2;
-                    a2.x = mid; a2.x_bs = sbs; a2.x_ld = (int)T;
-                    a2.y = dst; a2.y_bs = sbs; a2.y_ld = (int)T;
-                    a2.res = src; a2.res_bs = sbs; a2.res_ld = (int)T;
-                    a2.in_slope = 0.1f; a2.dil = 1; a2.in_len = slen;
-                    if (last) { a2.out_scale = 1.0f / nk; a2.accumulate = (j > 0); }
-                    a2.B = B; a2.T = (int)T;
-                    conv("dec.rb1.c2", cw(S("dec.rb.%d.c2.%d", n, m)), a2);
-                    src = dst;
-                }
-            }
-        }
-        tap(S("dec.mrf.%d", i).c_str(), d_bufC_, {B, ch, T}, d_ylen_, (int)(T / Ty));
+        T *= c.upsample_rates[i];
     }
     {
         ProfScope ps(prof_, "dec.conv_post_tanh", 2.0 * B * (double)T * ch * 7, 4.0 * B * (double)T * (ch + 1));
@@ -1541,6 +1512,74 @@ struct ResultOwner {
 };
 }  // namespace
 
+// The sequence of alloc calls below IS the workspace layout: run() plays it against an ArenaCount for the size to reserve, then
+// against the arena for the pointers.
+template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w) {
+    const mi355vits_config& c = cfg_;
+    const size_t H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels, fBT = B * Tx;
+    const size_t nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
+    // the call's host inputs sit side by side so that ONE host-to-device copy brings them all (each copy from pageable memory
+    // is a staging pass + a copy kernel: ~35 us apiece in the stream of a single utterance): d_ids_ .. up to d_ylen_
+    d_ids_ = ar.template alloc<long long>(fBT);
+    d_sid_ = ar.template alloc<long long>(B);
+    d_len_ = ar.template alloc<int>(B);
+    d_scales_ = ar.template alloc<float>(B * 3);
+    d_vol_ = ar.template alloc<double>(B);
+    d_utt_ = ar.template alloc<unsigned long long>(B);
+    d_forced_ = forced ? ar.template alloc<int>(fBT) : nullptr;
+    d_noise_w_ = noise_w ? ar.template alloc<float>(fBT * 2) : nullptr;
+    d_ylen_ = ar.template alloc<int>(B);
+    d_peaks_ = ar.template alloc<unsigned>(B);
+    d_wceil_ = ar.template alloc<int>(fBT);
+    d_cum_ = ar.template alloc<int>(fBT);
+    d_x_ = ar.template alloc<float>(fBT * H);
+    d_x2_ = ar.template alloc<float>(fBT * H);
+    d_att_ = ar.template alloc<float>(fBT * H);
+    d_qkv_ = ar.template alloc<float>(fBT * 3 * H);
+    d_ffn_ = ar.template alloc<float>(fBT * F);
+    // slice sums of the FFN's second conv
+    d_part_ = (F % 192 == 0 && F / 192 > 1 && H <= 256) ? ar.template alloc<float>(fBT * H * (F / 192)) : nullptr;
+    d_stats_ = ar.template alloc<float>(fBT * 2 * I);
+    d_h_ = ar.template alloc<float>(fBT * H);
+    d_d0_ = ar.template alloc<float>(fBT * H);
+    d_d1_ = ar.template alloc<float>(fBT * H);
+    d_d2_ = ar.template alloc<float>(fBT * H);
+    d_theta_ = ar.template alloc<float>(fBT * nth);
+    d_z2_ = ar.template alloc<float>(fBT * 2);
+    d_logw_ = ar.template alloc<float>(fBT);
+    const bool cond = c.n_speakers > 1 && c.gin_channels;
+    d_cond_dp_ = cond ? ar.template alloc<float>(B * H) : nullptr;
+    d_cond_dec_ = cond ? ar.template alloc<float>(B * c.upsample_initial_channel) : nullptr;
+    d_cond_flow_.clear();
+    for (int j = 0; cond && j < c.flow_n_flows; ++j) d_cond_flow_.push_back(ar.template alloc<float>(B * 2 * H * c.flow_wn_layers));
+}
+
+template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames) {
+    const mi355vits_config& c = cfg_;
+    const size_t H = c.hidden_channels, I = c.inter_channels, fBTy = B * Ty;
+    size_t ch = c.upsample_initial_channel, T = Ty, max_stage = ch * T;  // the widest decoder tensor of a row
+    for (int i = 0; i < c.n_upsamples; ++i) {
+        ch /= 2;
+        T *= c.upsample_rates[i];
+        max_stage = std::max(max_stage, ch * T);
+    }
+    d_z_ = ar.template alloc<float>(fBTy * I);
+    d_fh_ = ar.template alloc<float>(fBTy * H);
+    d_fh2_ = ar.template alloc<float>(fBTy * H);
+    d_fskip_ = ar.template alloc<float>(fBTy * H);
+    d_fu_ = ar.template alloc<float>(fBTy * H);
+    d_noise_z_ = noise_z_frames ? ar.template alloc<float>(B * I * noise_z_frames) : nullptr;
+    d_bufA_ = ar.template alloc<float>(B * max_stage);
+    d_bufB_ = ar.template alloc<float>(B * max_stage);
+    d_bufT_ = ar.template alloc<float>(B * max_stage);
+    d_bufC_ = ar.template alloc<float>(B * max_stage);
+    d_audio_ = ar.template alloc<float>(B * L_);
+    d_pcm_ = ar.template alloc<int16_t>(B * L_);
+    // per-stage valid lengths and (last row) the audio lengths
+    d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B);
+    d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
+}
+
 void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
     const mi355vits_config& c = cfg_;
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
@@ -1596,62 +1635,18 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();
 
-    const int H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels;
-    const int nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
-    const int C0 = c.upsample_initial_channel;
+    const int H = c.hidden_channels, C0 = c.upsample_initial_channel;
     const int gin = multi ? c.gin_channels : 0;
-    auto pad = [](size_t bytes) { return DeviceArena::padded(bytes); };
 
-    // ---------------- phase A workspace
+    // ---------------- phase A workspace.  Sized with the optional inputs present: a handle that served a call without them does not
+    // reallocate when the next call brings them
     const size_t fBT = (size_t)B * Tx;
-    size_t need_a = pad(fBT * 8) + pad((size_t)B * 8) + 6 * pad((size_t)B * 4) + 3 * pad(fBT * 4);
-    need_a += pad((size_t)B * 3 * 4) + 2 * pad((size_t)B * 8);  // per-row scales, volumes, keys
-    need_a += 3 * pad(fBT * H * 4) + pad(fBT * 3 * H * 4) + pad(fBT * F * 4) + pad(fBT * 2 * I * 4);  // x,x2,att,qkv,ffn,stats
-    need_a += 4 * pad(fBT * H * 4) + pad(fBT * nth * 4) + 2 * pad(fBT * 2 * 4) + pad(fBT * 4);          // h,d0,d1,d2,theta,z2,noise_w,logw
-    if (F % 192 == 0 && F / 192 > 1 && H <= 256) need_a += pad(fBT * H * (F / 192) * 4);  // slice sums of the FFN's second conv
-    if (gin) need_a += pad((size_t)B * H * 4) + pad((size_t)B * C0 * 4) + (size_t)c.flow_n_flows * pad((size_t)B * 2 * H * c.flow_wn_layers * 4);
-    arena_a_.reserve(need_a + 4096, stream_);
+    ArenaCount size_a;
+    layout_a(size_a, B, Tx, true, true);
+    arena_a_.reserve(size_a.bytes + 4096, stream_);
     arena_a_.reset();
-    // the call's host inputs sit side by side so that ONE host-to-device copy brings them all (each copy from pageable memory
-    // is a staging pass + a copy kernel: ~35 us apiece in the stream of a single utterance)
-    const size_t in_off = arena_a_.used();
-    d_ids_ = arena_a_.alloc<long long>(fBT);
-    d_sid_ = arena_a_.alloc<long long>(B);
-    d_len_ = arena_a_.alloc<int>(B);
-    d_scales_ = arena_a_.alloc<float>((size_t)B * 3);
-    d_vol_ = arena_a_.alloc<double>(B);
-    d_utt_ = arena_a_.alloc<unsigned long long>(B);
-    d_forced_ = nullptr;
-    if (args.forced_durations) d_forced_ = arena_a_.alloc<int>(fBT);
-    d_noise_w_ = nullptr;
-    if (args.noise_w) d_noise_w_ = arena_a_.alloc<float>(fBT * 2);
-    const size_t in_bytes = arena_a_.used() - in_off;
-    d_ylen_ = arena_a_.alloc<int>(B);
-    d_peaks_ = arena_a_.alloc<unsigned>(B);
-    d_wceil_ = arena_a_.alloc<int>(fBT);
-    d_cum_ = arena_a_.alloc<int>(fBT);
-    d_x_ = arena_a_.alloc<float>(fBT * H);
-    d_x2_ = arena_a_.alloc<float>(fBT * H);
-    d_att_ = arena_a_.alloc<float>(fBT * H);
-    d_qkv_ = arena_a_.alloc<float>(fBT * 3 * H);
-    d_ffn_ = arena_a_.alloc<float>(fBT * F);
-    d_part_ = (F % 192 == 0 && F / 192 > 1 && H <= 256) ? arena_a_.alloc<float>(fBT * H * (F / 192)) : nullptr;
-    d_stats_ = arena_a_.alloc<float>(fBT * 2 * I);
-    d_h_ = arena_a_.alloc<float>(fBT * H);
-    d_d0_ = arena_a_.alloc<float>(fBT * H);
-    d_d1_ = arena_a_.alloc<float>(fBT * H);
-    d_d2_ = arena_a_.alloc<float>(fBT * H);
-    d_theta_ = arena_a_.alloc<float>(fBT * nth);
-    d_z2_ = arena_a_.alloc<float>(fBT * 2);
-    d_logw_ = arena_a_.alloc<float>(fBT);
-    d_cond_dp_ = nullptr;
-    d_cond_dec_ = nullptr;
-    d_cond_flow_.clear();
-    if (gin) {
-        d_cond_dp_ = arena_a_.alloc<float>((size_t)B * H);
-        d_cond_dec_ = arena_a_.alloc<float>((size_t)B * C0);
-        for (int j = 0; j < c.flow_n_flows; ++j) d_cond_flow_.push_back(arena_a_.alloc<float>((size_t)B * 2 * H * c.flow_wn_layers));
-    }
+    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr);
+    const size_t in_bytes = reinterpret_cast<unsigned char*>(d_ylen_) - reinterpret_cast<unsigned char*>(d_ids_);
 
     HIP_CHECK(hipEventRecord(ev_start_, stream_));
     timed_ = false;
@@ -1720,38 +1715,13 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     L_ = (long)Ty * hop;
 
     // ---------------- phase B workspace
-    size_t max_stage = (size_t)C0 * Ty;
-    {
-        size_t ch = C0, T = Ty;
-        for (int i = 0; i < c.n_upsamples; ++i) {
-            ch /= 2;
-            T *= c.upsample_rates[i];
-            max_stage = std::max(max_stage, ch * T);
-        }
-    }
-    const size_t fBTy = (size_t)B * Ty;
-    size_t need_b = pad(fBTy * I * 4) + 4 * pad(fBTy * H * 4);
-    if (args.noise_z && any_noise_z) need_b += pad((size_t)B * I * args.noise_z_frames * 4);
-    need_b += 4 * pad((size_t)B * max_stage * 4) + pad((size_t)B * L_ * 4) + pad((size_t)B * L_ * 2);
-    need_b += pad((size_t)(c.n_upsamples + 2) * B * 4);
-    arena_b_.reserve(need_b + 4096, stream_);
+    const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
+    ArenaCount size_b;
+    layout_b(size_b, B, Ty, nz_frames);
+    arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
-    d_z_ = arena_b_.alloc<float>(fBTy * I);
-    d_fh_ = arena_b_.alloc<float>(fBTy * H);
-    d_fh2_ = arena_b_.alloc<float>(fBTy * H);
-    d_fskip_ = arena_b_.alloc<float>(fBTy * H);
-    d_fu_ = arena_b_.alloc<float>(fBTy * H);
-    d_noise_z_ = nullptr;
-    if (args.noise_z && any_noise_z) {
-        d_noise_z_ = arena_b_.alloc<float>((size_t)B * I * args.noise_z_frames);
-        HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * I * args.noise_z_frames * 4, hipMemcpyHostToDevice, stream_));
-    }
-    d_bufA_ = arena_b_.alloc<float>((size_t)B * max_stage);
-    d_bufB_ = arena_b_.alloc<float>((size_t)B * max_stage);
-    d_bufT_ = arena_b_.alloc<float>((size_t)B * max_stage);
-    d_bufC_ = arena_b_.alloc<float>((size_t)B * max_stage);
-    d_audio_ = arena_b_.alloc<float>((size_t)B * L_);
-    d_pcm_ = arena_b_.alloc<int16_t>((size_t)B * L_);
+    layout_b(arena_b_, B, Ty, nz_frames);
+    if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     h_slen_.assign((size_t)(c.n_upsamples + 2) * B, 0);
     {
@@ -1762,8 +1732,6 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
         }
         for (int b = 0; b < B; ++b) h_slen_[(size_t)(c.n_upsamples + 1) * B + b] = (int)(h_ylen_[b] * hop);
     }
-    d_slen_ = arena_b_.alloc<int>(h_slen_.size());
-    d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
     HIP_CHECK(hipMemcpyAsync(d_slen_, h_slen_.data(), h_slen_.size() * 4, hipMemcpyHostToDevice, stream_));
 
     flow_and_decoder(B, Ty, args);

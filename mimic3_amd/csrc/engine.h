@@ -50,6 +50,10 @@ class DeviceArena {
     unsigned char* base_ = nullptr;
     size_t cap_ = 0, off_ = 0;
 };
+struct ArenaCount {  // stand-in that only adds up what a sequence of allocs takes
+    size_t bytes = 0;
+    template <typename T> T* alloc(size_t n) { bytes += DeviceArena::padded(n * sizeof(T)); return nullptr; }
+};
 
 // ---------------------------------------------------------------- HIP-event profiler on the engine stream
 struct Profiler {
@@ -103,6 +107,30 @@ struct ConvW {
     int Cout = 0, Cin = 0, K = 1;
     int epi = EPI_STD;  // tile map the packed copy was built for
 };
+// what a conv is in the graph, declared by whoever adds it: decides which of the copies above are packed (Engine::add_conv_data)
+enum ConvRole { ROLE_PLAIN, ROLE_RESBLOCK, ROLE_UPSAMPLER };
+// the kernel one dense conv runs on, in the order Engine::pick_conv tries them
+enum ConvKernel { UPS_PL, RB_CONV, ENC_B3, STAGED_B3, STAGED_F16X2, MFMA_F32, GENERIC };
+
+// ---------------------------------------------------------------- lab switches (MI355VITS_* through lab_getenv: tests, A/B runs)
+// Read once when a handle is created; a cloned lane takes lane 0's.  The product build's lab_getenv returns null: all defaults.
+struct LabSwitches {
+    bool force_generic = false;    // FORCE_GENERIC=1: every layer on its generic kernel
+    bool no_fused_wn = false;      // NO_FUSED_WN=1: in-layer + res/skip as two launches (A/B + fallback)
+    bool no_fused_mrf = false;     // NO_FUSED_MRF=1: conv-by-conv resblocks (A/B + fallback)
+    int b3_min_work = 256;         // B3_MIN_WORK: MATH_BF16X3: smallest K * Cin routed to the staged split-bf16 conv kernel
+    bool wn_b3 = false;            // WN_B3: MATH_BF16X3: WaveNet layers as two staged split-bf16 convs instead of the fused f32 layer
+    bool no_mrf_p = false;         // NO_MRF_P: keep the on-the-fly split MRF kernel (A/B against k_mrf_p)
+    bool no_rbc = false;           // NO_RBC: the 128-channel stage on k_mrf_fused + the staged conv (A/B against k_rb_conv)
+    bool no_fused_dds = false;     // NO_FUSED_DDS: DDS layers as three launches (A/B + fallback)
+    bool no_dds_stack = false;     // NO_DDS_STACK: one launch per DDS layer / pre / proj / spline (A/B + fallback)
+    bool no_dds_stack_b3 = false;  // NO_DDS_STACK_B3: the f32-MFMA form of the stack in every math mode (A/B)
+    bool no_enc_gemm = false;      // NO_ENC_GEMM: phoneme-sized convs on the general conv kernels (A/B + fallback)
+    bool no_enc_o_ln = false;      // NO_ENC_O_LN: o-proj and its LayerNorm as two launches (A/B + fallback)
+    bool no_flow_gemm = false;     // NO_FLOW_GEMM: flow.pre / flow.post on the general conv kernels (A/B + fallback)
+    bool no_f16x2_convs = false;   // F16X2_NO_CONVS: in MATH_F16X2 keep the staged convs / upsamplers on bf16x3
+    static LabSwitches from_env();
+};
 
 // ---------------------------------------------------------------- one weight replica on one device
 // Uploaded once per (voice, device); every engine handle ("lane") created on that device through mi355vits_clone shares
@@ -153,9 +181,9 @@ class Engine {
     // weight staging
     size_t stage(const float* p, size_t n);
     const ConvW& add_conv(const WeightsFile& wf, const std::string& key, const std::string& tensor, int Cout, int Cin,
-                          int K, bool bias, int epi = EPI_STD);
+                          int K, bool bias, int epi = EPI_STD, ConvRole role = ROLE_PLAIN);
     const ConvW& add_conv_data(const std::string& key, const std::vector<float>& w, const std::vector<float>* bias,
-                               int Cout, int Cin, int K, int epi = EPI_STD);
+                               int Cout, int Cin, int K, int epi = EPI_STD, ConvRole role = ROLE_PLAIN);
     void add_vec(const WeightsFile& wf, const std::string& name, std::initializer_list<int> dims);
     const float* vec(const std::string& name) const;
     const float* P(size_t off) const { return off == NO_OFF ? nullptr : model_->dev_weights + off; }
@@ -163,8 +191,8 @@ class Engine {
 
     // launch helpers
     void conv(const char* label, const ConvW& w, ConvArgs a);
-    bool rbc_ok(const ConvW& w, const ConvArgs& a) const;    // this conv runs on k_rb_conv (128-channel resblock conv, MATH_BF16X3)
-    bool enc_gemm(const ConvW& w, const ConvArgs& a) const;  // this conv runs on k_enc_b3 (phoneme-sized, split-bf16)
+    void fill_conv(const ConvW& w, ConvArgs& a) const;             // the shape fields of `a` from w (Cin, Cout, K, bias, default pad, fixed_rule)
+    ConvKernel pick_conv(const ConvW& w, const ConvArgs& a) const;  // the kernel conv() runs the filled-in `a` on (callers may ask ahead)
     // row_len / factor: frame-resolution taps of a ragged batch are zeroed past len[b] * factor (those columns are not computed)
     void tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len = nullptr, int factor = 1);
     void text_encoder(int B, int Tx);
@@ -172,6 +200,13 @@ class Engine {
     void duration_predictor_det(int B, int Tx);
     void dds(const std::string& key, float* X, float* Y1, float* Y2, int B, int T);
     void flow_and_decoder(int B, int Ty, const mi355vits_run_args& args);
+    void coupling_layer(int j, int B, int Ty);
+    void decoder_stage(int i, int B, int ch, long T);  // upsampler i on bufC [B,ch,T] -> bufA, its resblocks -> bufC
+    int mrf_stage(int i, int B, int ch, long T);       // the stage's leading resblocks in one launch; how many it took
+    ConvArgs rb2_conv_args(int i, int j, int m, int B, int ch, long T) const;
+    // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
+    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
+    template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames);
     void copy_out(uint32_t want, mi355vits_result* out);
 
     mi355vits_config cfg_{};
@@ -179,15 +214,9 @@ class Engine {
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_start_ = nullptr, ev_end_ = nullptr;
     bool timed_ = false;
-    bool phase_b_ = false;       // inside flow_and_decoder (see Engine::conv)
-    bool force_generic_ = false;
-    int b3_min_work_ = 256;      // MATH_BF16X3: smallest K * Cin routed to the staged split-bf16 conv kernel
-    bool no_flow_gemm_ = false;  // MI355VITS_NO_FLOW_GEMM=1: flow.pre / flow.post on the general conv kernels (A/B + fallback)
-    bool no_enc_o_ln_ = false;   // MI355VITS_NO_ENC_O_LN=1: o-proj and its LayerNorm as two launches (A/B + fallback)
-    bool no_enc_gemm_ = false;   // MI355VITS_NO_ENC_GEMM=1: phoneme-sized convs on the general conv kernels (A/B + fallback)
-    bool no_dds_stack_b3_ = false;  // MI355VITS_NO_DDS_STACK_B3=1: the f32-MFMA form of the stack in every math mode (A/B)
-    bool no_dds_stack_ = false;  // MI355VITS_NO_DDS_STACK=1: one launch per DDS layer / pre / proj / spline (A/B + fallback)
-    bool no_fused_dds_ = false;  // MI355VITS_NO_FUSED_DDS=1: DDS layers as three launches (A/B + fallback)
+    bool phase_b_ = false;       // inside flow_and_decoder (see Engine::fill_conv, pick_conv)
+    LabSwitches sw_;
+    int math_ = MATH_BF16X3;     // which matrix-core path the dense convs take (include/mi355vits.h: MI355VITS_MATH_*)
     // the math mode of the kernels that have no fp16 form of their own: in F16X2 they run as BF16X3 (the kernels that do —
     // fused MRF stages, fused WaveNet layers, staged convs, upsamplers — are switched where they are launched)
     int kmath() const { return math_ == MATH_F16X2 ? (int)MATH_BF16X3 : math_; }
@@ -195,20 +224,12 @@ class Engine {
     // discontinuous, so in MATH_BF16W it runs the exact three-term split and utterance lengths equal the default mode's
     int tmath() const { return kmath() == MATH_BF16W ? (int)MATH_BF16X3 : kmath(); }
     int pmath() const { return phase_b_ ? kmath() : tmath(); }  // math of the launch helpers shared by both phases
-    bool no_f16x2_convs_ = false;  // MI355VITS_F16X2_NO_CONVS=1: in MATH_F16X2 keep the staged convs / upsamplers on bf16x3
-    bool enc_b3_ = true;           // the encoder's wide FFN conv on the split-bf16 staged kernel (MI355VITS_NO_ENC_B3=1: f32 kernel)
-    bool no_rbc_ = false;        // MI355VITS_NO_RBC=1: the 128-channel stage on k_mrf_fused + the staged conv (A/B against k_rb_conv)
-    bool no_mrf_p_ = false;      // MI355VITS_NO_MRF_P=1: keep the on-the-fly split MRF kernel (A/B against k_mrf_p)
-    bool wn_b3_ = false;         // MATH_BF16X3: WaveNet layers as two staged split-bf16 convs instead of the fused f32 layer
-    int math_ = MATH_BF16X3;     // which matrix-core path the dense convs take (include/mi355vits.h: MI355VITS_MATH_*)
-    bool no_fused_wn_ = false;   // MI355VITS_NO_FUSED_WN=1: in-layer + res/skip as two launches (A/B + fallback)
-    bool no_fused_mrf_ = false;  // MI355VITS_NO_FUSED_MRF=1: conv-by-conv resblocks (A/B + fallback)
     Profiler prof_;
 
     std::vector<float> host_stage_;
     std::shared_ptr<Model> model_;
 
-    DeviceArena arena_a_, arena_b_, arena_taps_;
+    DeviceArena arena_a_, arena_b_;
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
