@@ -200,6 +200,57 @@ int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const
                        mi355vits_result* out);
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out);
 void mi355vits_free_result(mi355vits_result* r);
+
+/* ---- Packed results: a batch's finished audio as ONE contiguous PCM / WAV stream.
+ * What the reference does to the int16 audio of a request's sentences on the host — silence between them
+ * (Mimic3TextToSpeechSystem.add_break, mimic3_tts/tts.py:452-465: int(ms / 1000 * sample_rate) zero samples) and WAV framing
+ * (opentts_abc/__init__.py:117-127) — done by one kernel (k_pcm16_pack) and brought to the host by one copy of exactly
+ * n_bytes: only the valid samples of each row, rows in the order the caller names, no padding to the longest row. */
+typedef struct mi355vits_pack_args {
+    int32_t n;                   /* entries of the stream, 1 <= n <= batch */
+    const int32_t* order;        /* [n] batch row of entry i; NULL = 0 .. n-1.  A row appears at most once. */
+    const int64_t* lead_samples; /* [n] zero samples in front of entry i (add_break); NULL = none */
+    int64_t tail_samples;        /* zero samples after the last entry */
+    int32_t wav_header;          /* != 0: 44-byte RIFF/WAVE header (PCM, mono, 16 bit, the voice's sample rate) in front */
+} mi355vits_pack_args;
+
+typedef struct mi355vits_packed_result {
+    int32_t n;
+    int64_t total_samples;   /* silences included, header excluded */
+    uint8_t* bytes;          /* header (if asked) + 2 * total_samples bytes, little-endian int16; pinned, callee-owned */
+    size_t n_bytes;
+    int16_t* pcm;            /* = bytes + (wav_header ? 44 : 0) */
+    int64_t* offsets;        /* [n] first audio sample of entry i in pcm (after its lead silence) */
+    int64_t* lengths;        /* [n] valid samples of entry i */
+    float* peaks;            /* [n] max |audio| over entry i's valid samples */
+    void* owner_;            /* private */
+} mi355vits_packed_result;
+
+/* One synthesis call whose result is the packed stream (pack == NULL: every row, in order, no silence, no header).
+ * Contract:
+ *  - Entry i's samples pcm[offsets[i] .. offsets[i] + lengths[i]) are BITWISE row order[i]'s valid samples of
+ *    mi355vits_run_rows(... MI355VITS_WANT_PCM16 ...) for the same arguments, per-row volumes included, in every math mode:
+ *    the same audio_float_to_int16 + audioop.mul arithmetic as the padded int16 result, operation for operation.  lengths /
+ *    peaks are that call's values for those rows.  Every other sample of the stream is zero, and is written by the kernel.
+ *  - With wav_header, bytes[0, n_bytes) is the file the stdlib `wave` module writes around the same chunks (44-byte header,
+ *    PCM, mono, 16 bit, the voice's sample rate), byte for byte.
+ *  - MI355VITS_WANT_* and MI355VITS_DEVICE_ONLY in args->flags are ignored: the call produces the packed stream and nothing
+ *    else (neither the padded int16 pass nor a padded copy to the host runs); MI355VITS_DEBUG_TAPS works as before.
+ *    Afterwards mi355vits_fetch / mi355vits_device_result serve the padded forms from the float audio, as after a
+ *    MI355VITS_DEVICE_ONLY run.
+ *  - Errors are found before any result is sized or any packing is launched and return MI355VITS_ERR_INVALID with a message
+ *    that names the entry or the limit ("pack entry 3: row 9 out of range", "pack entry 2: row 2 appears twice",
+ *    "pack entry 1: negative silence"): n outside 1 .. batch, a bad order, negative counts, total_samples > 2^31 - 1, and with
+ *    a header a data size that does not fit RIFF's 32-bit fields.  Never partial audio.
+ *  - No extra host round trip: the call synchronises its stream twice, like mi355vits_run (frame counts, result); the offsets
+ *    are made on the host from the frame counts and uploaded with the per-stage length table. */
+int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                         const mi355vits_pack_args* pack /* may be NULL */, mi355vits_packed_result* out);
+/* Pack the LAST completed run of the handle again (whatever flags it had, packed or not), with that run's per-row volumes and
+ * another order / silences / header; no synthesis work is repeated. */
+int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out);
+void mi355vits_free_packed(mi355vits_packed_result* r);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

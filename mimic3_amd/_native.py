@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
+    "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
@@ -88,6 +89,33 @@ class Result(ctypes.Structure):
     ]
 
 
+class PackArgs(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_int32),
+        ("order", ctypes.POINTER(ctypes.c_int32)),
+        ("lead_samples", ctypes.POINTER(ctypes.c_int64)),
+        ("tail_samples", ctypes.c_int64),
+        ("wav_header", ctypes.c_int32),
+    ]
+
+
+class PackedResult(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_int32),
+        ("total_samples", ctypes.c_int64),
+        ("bytes", ctypes.POINTER(ctypes.c_uint8)),
+        ("n_bytes", ctypes.c_size_t),
+        ("pcm", ctypes.POINTER(ctypes.c_int16)),
+        ("offsets", ctypes.POINTER(ctypes.c_int64)),
+        ("lengths", ctypes.POINTER(ctypes.c_int64)),
+        ("peaks", ctypes.POINTER(ctypes.c_float)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+WAV_HEADER_BYTES = 44
+
+
 class ConvTest(ctypes.Structure):
     _fields_ = [
         ("impl", ctypes.c_int32), ("B", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
@@ -137,6 +165,11 @@ class NativeLibrary:
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
+        L.mi355vits_run_packed.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(PackArgs),
+                                           ctypes.POINTER(PackedResult)]
+        L.mi355vits_fetch_packed.argtypes = [H, ctypes.POINTER(PackArgs), ctypes.POINTER(PackedResult)]
+        L.mi355vits_free_packed.argtypes = [ctypes.POINTER(PackedResult)]
+        L.mi355vits_free_packed.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -336,6 +369,40 @@ class _ResultHolder:
             pass
 
 
+class _PackedHolder:
+    """The same for one ``mi355vits_packed_result``: the pinned block lives as long as any view of it."""
+
+    def __init__(self, native: "NativeLibrary", r: PackedResult):
+        self._native = native
+        self._r = PackedResult()
+        ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(PackedResult))
+
+    def view(self) -> np.ndarray:
+        """Every byte of the block (header, if any, + data) as one uint8 array that owns the holder."""
+        n = int(self._r.n_bytes)
+        buf = (ctypes.c_uint8 * n).from_address(ctypes.addressof(self._r.bytes.contents))
+        buf._holder = self
+        return np.frombuffer(buf, dtype=np.uint8, count=n)
+
+    def __del__(self):
+        try:
+            self._native.lib.mi355vits_free_packed(ctypes.byref(self._r))
+        except Exception:
+            pass
+
+
+class PackedAudio:
+    """A batch's audio as one contiguous stream (``mi355vits_run_packed``).  Everything is a view of ONE pinned block that goes
+    back to the library when the last view is gone: ``pcm`` int16 [total_samples] (silences included), ``rows[i]`` =
+    ``pcm[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
+    when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry."""
+
+    def __init__(self, pcm, offsets, lengths, peaks, wav):
+        self.pcm, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
+        self.total_samples = int(pcm.shape[0])
+        self.rows = [pcm[int(o): int(o) + int(n)] for o, n in zip(offsets, lengths)]
+
+
 class Engine:
     """A voice loaded on one GPU (wraps ``mi355vits_handle``)."""
 
@@ -363,6 +430,7 @@ class Engine:
         self._check(L.mi355vits_get_config(self._h, ctypes.byref(c)))
         self.config = VitsConfig.from_c(c)
         self.device = device
+        self._last_batch = 0  # rows of the last completed run (fetch_packed's default pack with a tail or a header)
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -386,6 +454,22 @@ class Engine:
         """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
         ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
         its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class)."""
+        a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
+                                            pcm_volume, utterance_keys)
+        a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
+                  (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
+        r = Result()
+        if per_row:
+            self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
+        else:
+            self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
+        del keep
+        self._last_batch = int(a.batch)
+        return self._take(r)
+
+    def _args(self, ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations, pcm_volume, utterance_keys):
+        """The feed as ``mi355vits_run_args`` + ``mi355vits_row_args`` (flags not set): (args, rows, any per-row setting, the
+        arrays the two structs point into — keep them alive across the call)."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         if ids.ndim != 2:
             raise ValueError("'input' must have shape [batch, phonemes]")
@@ -449,16 +533,78 @@ class Engine:
                 raise ValueError("forced_durations must have shape [batch, phonemes]")
             keep.append(forced_durations)
             a.forced_durations = forced_durations.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
-                  (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         a.pcm_volume = float(pcm_volume)
-        r = Result()
-        if per_row:
-            self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
-        else:
-            self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
-        del keep
-        return self._take(r)
+        return a, rows, per_row, keep
+
+    # ---- the packed stream ----------------------------------------------------------------------
+    @staticmethod
+    def _pack_args(order, lead_samples, tail_samples, wav):
+        """``mi355vits_pack_args`` (or None: the library's default pack) + the arrays it points into."""
+        if order is None and lead_samples is None and not tail_samples and not wav:
+            return None, []
+        p, keep = PackArgs(), []
+        for name, arr, dtype, ctype in (("order", order, np.int32, ctypes.c_int32), ("lead_samples", lead_samples, np.int64, ctypes.c_int64)):
+            if arr is not None:
+                src = np.asarray(arr).reshape(-1)
+                if src.size and not np.issubdtype(src.dtype, np.integer):
+                    raise ValueError(f"'{name}' must hold integers")
+                v = np.ascontiguousarray(src, dtype=dtype)
+                keep.append(v)
+                setattr(p, name, v.ctypes.data_as(ctypes.POINTER(ctype)))
+        sizes = {int(v.shape[0]) for v in keep}
+        if len(sizes) > 1:
+            raise ValueError("'order' and 'lead_samples' must have the same length")
+        p.n = sizes.pop() if sizes else -1  # -1: every row of the batch, filled in by the caller
+        p.tail_samples = int(tail_samples)
+        p.wav_header = int(bool(wav))
+        return p, keep
+
+    def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
+                   seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
+                   debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> PackedAudio:
+        """One synthesis call whose result is ONE contiguous int16 stream (``mi355vits_run_packed``): entry i = the valid samples
+        of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
+        the last entry, with ``wav`` a 44-byte RIFF header in front.  Each entry is bitwise that row of
+        ``run(..., want_pcm16=True)`` for the same arguments; one kernel, one device-to-host copy of exactly that many bytes."""
+        a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
+                                            pcm_volume, utterance_keys)
+        a.flags = DEBUG_TAPS if debug_taps else 0
+        p, pkeep = self._pack_args(order, lead_samples, tail_samples, wav)
+        if p is not None and p.n < 0:
+            p.n = a.batch
+        r = PackedResult()
+        self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                         None if p is None else ctypes.byref(p), ctypes.byref(r)))
+        del keep, pkeep
+        self._last_batch = int(a.batch)
+        return self._take_packed(r, bool(wav))
+
+    def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
+        """Pack the last completed run of this handle again (``mi355vits_fetch_packed``): that run's rows and per-row volumes,
+        another order / silences / header; nothing is synthesised again."""
+        p, pkeep = self._pack_args(order, lead_samples, tail_samples, wav)
+        if p is not None and p.n < 0:
+            p.n = self._last_batch  # every row of the last run (0 before the first: the library names the error)
+        r = PackedResult()
+        self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
+        del pkeep
+        return self._take_packed(r, bool(wav))
+
+    def _take_packed(self, r: PackedResult, wav: bool) -> PackedAudio:
+        n = int(r.n)
+        try:
+            offsets = np.ctypeslib.as_array(r.offsets, shape=(n,)).copy()
+            lens = np.ctypeslib.as_array(r.lengths, shape=(n,)).copy()
+            peaks = np.ctypeslib.as_array(r.peaks, shape=(n,)).copy()
+            hdr = WAV_HEADER_BYTES if wav else 0
+            if int(r.n_bytes) != hdr + 2 * int(r.total_samples):
+                raise RuntimeError("mi355vits_packed_result: n_bytes does not match total_samples")
+        except BaseException:
+            self.native.lib.mi355vits_free_packed(ctypes.byref(r))
+            raise
+        block = _PackedHolder(self.native, r).view()
+        pcm = block[hdr:].view("<i2")
+        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None)
 
     MATH_MODES = {"f32": 0, "bf16x3": 1, "bf16w": 2, "f16x2": 3}
 

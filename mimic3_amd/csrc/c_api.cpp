@@ -133,6 +133,30 @@ int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* o
 
 void mi355vits_free_result(mi355vits_result* r) { free_result_impl(r); }
 
+int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                         const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    int rc = guarded(h, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        h->eng->run_packed(*args, rows, pack, out);
+    });
+    if (rc != MI355VITS_OK && out) mi355vits_free_packed(out);  // never hand back partial audio
+    return rc;
+}
+
+int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    int rc = guarded(h, [&] { h->eng->fetch_packed(pack, out); });
+    if (rc != MI355VITS_OK && out) mi355vits_free_packed(out);
+    return rc;
+}
+
+void mi355vits_free_packed(mi355vits_packed_result* r) { free_packed_impl(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

@@ -637,6 +637,7 @@ void Engine::fill_workspace(uint32_t pattern) {
     HIP_CHECK(hipSetDevice(device_));
     arena_a_.fill(pattern, stream_);
     arena_b_.fill(pattern, stream_);
+    arena_p_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1580,10 +1581,34 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
 }
 
+// what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
+struct Engine::PackPlan {
+    int n = 0;
+    bool wav = false;
+    std::vector<int> order;
+    std::vector<int64_t> lead;
+    int64_t tail = 0;
+    // made by place_pack from the frame counts
+    std::vector<int64_t> offsets, lengths;
+    int64_t total = 0, audio = 0;
+};
+
+// Packed calls only: the segment table and the stream, behind everything layout_b placed — no other pointer moves, so a call
+// that packs nothing runs on the layout it always had.
+template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples) {
+    d_pack_seg_ = ar.template alloc<int>(3 * n);
+    d_pack_ = ar.template alloc<int16_t>(pcm_pack_capacity((long)samples));
+}
+
 void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
-    const mi355vits_config& c = cfg_;
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
+    synthesize(args, rows, nullptr);
+    copy_out(args.flags, out);
+}
+
+void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan) {
+    const mi355vits_config& c = cfg_;
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     const float* row_scales = rows ? rows->scales : nullptr;
     if (!args.ids || !args.lengths || (!args.scales && !row_scales))
@@ -1713,17 +1738,25 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     Ty_ = Ty;
     const long hop = c.hop_length;
     L_ = (long)Ty * hop;
+    if (plan) place_pack(*plan);  // offsets from the frame counts just read; the size limits, before phase B is sized
 
     // ---------------- phase B workspace
     const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
     ArenaCount size_b;
     layout_b(size_b, B, Ty, nz_frames);
+    if (plan) layout_pack(size_b, plan->n, plan->total);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
     layout_b(arena_b_, B, Ty, nz_frames);
+    layout_b_end_ = arena_b_.used();
+    d_pack_seg_ = nullptr;
+    d_pack_ = nullptr;
+    if (plan) layout_pack(arena_b_, plan->n, plan->total);
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
-    h_slen_.assign((size_t)(c.n_upsamples + 2) * B, 0);
+    // (a packed call's segment table sits right behind d_slen_ in the arena: the same copy brings it)
+    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + 3 * (size_t)plan->n : (size_t)(c.n_upsamples + 2) * B, 0);
+    if (plan) fill_pack_seg(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
     {
         long f = 1;
         for (int i = 0; i <= c.n_upsamples; ++i) {
@@ -1737,7 +1770,9 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     flow_and_decoder(B, Ty, args);
 
     have_pcm_ = false;
-    if (args.flags & MI355VITS_WANT_PCM16) {
+    if (plan) {
+        launch_pack(*plan);  // the packed stream and nothing else: MI355VITS_WANT_* / DEVICE_ONLY are not looked at
+    } else if (args.flags & MI355VITS_WANT_PCM16) {
         ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)L_);
         launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, d_vol_);
         have_pcm_ = true;
@@ -1745,7 +1780,6 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     HIP_CHECK(hipEventRecord(ev_end_, stream_));
     timed_ = true;
     have_result_ = true;
-    copy_out(args.flags, out);
 }
 
 void Engine::copy_out(uint32_t want, mi355vits_result* out) {
@@ -1780,6 +1814,183 @@ void Engine::copy_out(uint32_t want, mi355vits_result* out) {
     }
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (int b = 0; b < B; ++b) memcpy(&out->peaks[b], &pk[b], 4);
+}
+
+// ---------------------------------------------------------------- packed results (mi355vits_run_packed / mi355vits_fetch_packed)
+namespace {
+constexpr int64_t PACK_MAX_SAMPLES = 0x7fffffffLL;                       // total_samples <= 2^31 - 1
+constexpr int64_t RIFF_MAX_SAMPLES = (0xffffffffLL - 36) / 2;            // 36 + 2 * total_samples must fit RIFF's 32-bit size
+constexpr size_t WAV_HEADER_BYTES = 44;
+EngineError pack_error(int entry, const std::string& what) {
+    return EngineError(MI355VITS_ERR_INVALID, (entry >= 0 ? "pack entry " + std::to_string(entry) + ": " : std::string("pack: ")) + what);
+}
+void check_pack_size(int entry, int64_t samples, bool wav) {
+    if (samples > PACK_MAX_SAMPLES) throw pack_error(entry, "total_samples exceeds 2^31 - 1");
+    if (wav && samples > RIFF_MAX_SAMPLES) throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (36 + 2 * total_samples > 2^32 - 1)");
+}
+struct PackedOwner {
+    void* bytes = nullptr;
+    size_t cap = 0;
+    void* offsets = nullptr;
+    void* lengths = nullptr;
+    void* peaks = nullptr;
+};
+}  // namespace
+
+// Everything that can be wrong with the pack arguments alone, before anything is sized or launched.
+void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const {
+    plan.n = pack ? pack->n : B;
+    if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
+    plan.wav = pack && pack->wav_header != 0;
+    plan.tail = pack ? pack->tail_samples : 0;
+    plan.order.resize(plan.n);
+    plan.lead.assign(plan.n, 0);
+    std::vector<int> at(B, -1);
+    int64_t silence = 0;
+    for (int i = 0; i < plan.n; ++i) {
+        const int row = (pack && pack->order) ? pack->order[i] : i;
+        if (row < 0 || row >= B) throw pack_error(i, "row " + std::to_string(row) + " out of range (batch = " + std::to_string(B) + ")");
+        if (at[row] >= 0) throw pack_error(i, "row " + std::to_string(row) + " appears twice (also entry " + std::to_string(at[row]) + ")");
+        at[row] = i;
+        plan.order[i] = row;
+        const int64_t lead = (pack && pack->lead_samples) ? pack->lead_samples[i] : 0;
+        if (lead < 0) throw pack_error(i, "negative silence (" + std::to_string(lead) + " samples)");
+        check_pack_size(i, lead, plan.wav);
+        plan.lead[i] = lead;
+        silence += lead;
+        check_pack_size(i, silence, plan.wav);  // the silences alone: no row is synthesised for a stream that cannot exist
+    }
+    if (plan.tail < 0) throw pack_error(-1, "negative tail silence (" + std::to_string(plan.tail) + " samples)");
+    check_pack_size(-1, plan.tail, plan.wav);
+    check_pack_size(-1, silence + plan.tail, plan.wav);
+}
+
+// Where every entry goes, from the frame counts the host already holds; the size limits with the audio counted in.
+void Engine::place_pack(PackPlan& plan) const {
+    plan.offsets.resize(plan.n);
+    plan.lengths.resize(plan.n);
+    int64_t pos = 0;
+    plan.audio = 0;
+    for (int i = 0; i < plan.n; ++i) {
+        pos += plan.lead[i];
+        plan.offsets[i] = pos;
+        plan.lengths[i] = (int64_t)h_ylen_[plan.order[i]] * cfg_.hop_length;
+        pos += plan.lengths[i];
+        plan.audio += plan.lengths[i];
+        check_pack_size(i, pos, plan.wav);
+    }
+    plan.total = pos + plan.tail;
+    check_pack_size(-1, plan.total, plan.wav);
+}
+
+void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
+    for (int i = 0; i < plan.n; ++i) {
+        seg[i] = (int)plan.offsets[i];
+        seg[plan.n + i] = plan.order[i];
+        seg[2 * plan.n + i] = (int)plan.lengths[i];
+    }
+}
+
+void Engine::launch_pack(const PackPlan& plan) {
+    ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
+    launch_pcm16_pack(d_audio_, L_, d_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
+}
+
+void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
+    const int n = plan.n;
+    auto* own = new PackedOwner();
+    out->owner_ = own;
+    out->n = n;
+    out->total_samples = plan.total;
+    own->offsets = malloc(sizeof(int64_t) * n);
+    own->lengths = malloc(sizeof(int64_t) * n);
+    own->peaks = malloc(sizeof(float) * n);
+    out->offsets = static_cast<int64_t*>(own->offsets);
+    out->lengths = static_cast<int64_t*>(own->lengths);
+    out->peaks = static_cast<float*>(own->peaks);
+    if (!out->offsets || !out->lengths || !out->peaks) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
+    const size_t hdr = plan.wav ? WAV_HEADER_BYTES : 0, data = 2 * (size_t)plan.total;
+    own->bytes = PinnedPool::get().take(hdr + data + 16, &own->cap);
+    out->bytes = static_cast<uint8_t*>(own->bytes);
+    out->n_bytes = hdr + data;
+    out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);
+    std::vector<unsigned> pk(B_);
+    HIP_CHECK(hipMemcpyAsync(pk.data(), d_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
+    if (plan.wav) {
+        // RIFF/WAVE, PCM, mono, 16 bit: the 44 bytes the stdlib `wave` module writes (little-endian fields)
+        uint8_t* h = out->bytes;
+        auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
+        auto u16 = [&](size_t at, uint32_t v) { h[at] = (uint8_t)v; h[at + 1] = (uint8_t)(v >> 8); };
+        const uint32_t rate = (uint32_t)cfg_.sample_rate;
+        memcpy(h, "RIFF", 4);
+        u32(4, (uint32_t)(36 + data));
+        memcpy(h + 8, "WAVEfmt ", 8);
+        u32(16, 16);
+        u16(20, 1);
+        u16(22, 1);
+        u32(24, rate);
+        u32(28, rate * 2);
+        u16(32, 2);
+        u16(34, 16);
+        memcpy(h + 36, "data", 4);
+        u32(40, (uint32_t)data);
+    }
+    for (int i = 0; i < n; ++i) {
+        out->offsets[i] = plan.offsets[i];
+        out->lengths[i] = plan.lengths[i];
+    }
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int i = 0; i < n; ++i) memcpy(&out->peaks[i], &pk[plan.order[i]], 4);
+}
+
+void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
+                        mi355vits_packed_result* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
+    PackPlan plan;
+    plan_pack(pack, args.batch, plan);
+    synthesize(args, rows, &plan);
+    copy_out_packed(plan, out);
+}
+
+void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_packed: no completed run on this handle");
+    PackPlan plan;
+    plan_pack(pack, B_, plan);
+    place_pack(plan);
+    HIP_CHECK(hipSetDevice(device_));
+    // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
+    // else in an arena of its own
+    ArenaCount need;
+    layout_pack(need, plan.n, plan.total);
+    if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
+        arena_b_.rewind(layout_b_end_);
+        layout_pack(arena_b_, plan.n, plan.total);
+    } else {
+        arena_p_.reserve(need.bytes + 4096, stream_);
+        arena_p_.reset();
+        layout_pack(arena_p_, plan.n, plan.total);
+    }
+    h_pack_seg_.assign(3 * (size_t)plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
+    fill_pack_seg(plan, h_pack_seg_.data());
+    HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
+    launch_pack(plan);
+    copy_out_packed(plan, out);
+}
+
+void free_packed_impl(mi355vits_packed_result* r) {
+    if (!r || !r->owner_) return;
+    auto* own = static_cast<PackedOwner*>(r->owner_);
+    PinnedPool::get().give(own->bytes, own->cap);
+    free(own->offsets);
+    free(own->lengths);
+    free(own->peaks);
+    delete own;
+    memset(r, 0, sizeof(*r));
 }
 
 void Engine::device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths) {

@@ -39,6 +39,7 @@ class DeviceArena {
     ~DeviceArena();
     void reserve(size_t bytes, hipStream_t s);  // may reallocate (synchronises the stream first)
     void reset() { off_ = 0; }
+    void rewind(size_t off) { off_ = off; }     // back to an earlier used(): what was allocated after it is given up
     void fill(uint32_t pattern, hipStream_t s);  // every byte of the capacity (tests: mi355vits_test_fill_workspace)
     template <typename T> T* alloc(size_t n) { return reinterpret_cast<T*>(alloc_bytes(n * sizeof(T))); }
     size_t capacity() const { return cap_; }
@@ -164,6 +165,10 @@ class Engine {
     // rows: per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
     void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out);
     void fetch(uint32_t want, mi355vits_result* out);
+    // the packed stream (mi355vits_run_packed / mi355vits_fetch_packed): pack == NULL = every row, in order, no silence, no header
+    void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
+                    mi355vits_packed_result* out);
+    void fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -207,7 +212,17 @@ class Engine {
     // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames);
+    template <typename A> void layout_pack(A& ar, size_t n, size_t samples);  // continues layout_b in packed calls, and only there
     void copy_out(uint32_t want, mi355vits_result* out);
+    // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
+    // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
+    struct PackPlan;
+    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan);
+    void plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const;  // validates; nothing sized or launched yet
+    void place_pack(PackPlan& plan) const;                                           // offsets / total from h_ylen_; the size limits
+    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [3][n]: first sample, row, length
+    void launch_pack(const PackPlan& plan);
+    void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
 
     mi355vits_config cfg_{};
     int device_ = 0;
@@ -230,6 +245,7 @@ class Engine {
     std::shared_ptr<Model> model_;
 
     DeviceArena arena_a_, arena_b_;
+    DeviceArena arena_p_;  // mi355vits_fetch_packed only: the packed stream of a run whose frame-side arena has no room left for it
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -257,11 +273,18 @@ class Engine {
     int16_t* d_pcm_ = nullptr;
     unsigned* d_peaks_ = nullptr;
     int* d_slen_ = nullptr;  // [n_upsamples + 1][B] valid frames per decoder stage
+    // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table [3][n] right behind
+    // d_slen_ (one upload brings both) and the stream itself
+    int* d_pack_seg_ = nullptr;
+    int16_t* d_pack_ = nullptr;
+    size_t layout_b_end_ = 0;  // arena_b_.used() behind d_slen_: where fetch_packed puts its buffers when there is room
     std::vector<int> h_ylen_;
     std::vector<unsigned char> h_in_;  // the call's host inputs, laid out like their device block (one upload)
-    std::vector<int> h_slen_;         // per-stage valid lengths + audio lengths (one upload)
+    std::vector<int> h_slen_;         // per-stage valid lengths + audio lengths (one upload; packed calls: + the segment table)
+    std::vector<int> h_pack_seg_;     // fetch_packed's segment table (its own upload)
 };
 
 void free_result_impl(mi355vits_result* r);
+void free_packed_impl(mi355vits_packed_result* r);
 
 }  // namespace m355

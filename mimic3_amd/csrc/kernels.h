@@ -205,6 +205,14 @@ void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, 
 // sample * volume in double, clipped to [-32768, 32767], rounded toward minus infinity.
 void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, const int* valid_len, int B, int L,
                   int16_t* pcm, long pcm_bs, hipStream_t s, const double* volumes = nullptr);
+// The same conversion into ONE contiguous stream (mi355vits_run_packed): entry i = row seg[n + i]'s first seg[2n + i] samples at
+// out[seg[i] ..), entries in ascending order of seg[i]; every other sample of out[0, total) is written as zero (break silences,
+// tail).  seg = [3][n] int32 on the device (first sample, row, length).  out is 16-byte aligned and holds pcm_pack_capacity(total)
+// samples (whole 16-byte stores).  Sample for sample k_pcm16's arithmetic.
+constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes x one 16-byte store
+inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
+void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
+                       int16_t* out, long total, hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

@@ -6,6 +6,9 @@
   for callers that already hold PCM;
 * breaks — ``add_break``: ``int(ms / 1000 * sample_rate)`` zero samples (``tts.py:452-465``);
 * WAV framing — ``wave.open`` around the concatenated bytes (``opentts_abc/__init__.py:117-127``).
+
+``silence`` / ``wav_bytes`` / ``utterances_to_wav`` do the last two in numpy for callers that hold PCM rows; ``request_wav`` has
+the engine do them: one ``InferenceSession.run_packed`` call returns the finished file (``mi355vits_run_packed``).
 """
 from __future__ import annotations
 
@@ -48,3 +51,28 @@ def utterances_to_wav(pcm_rows: Sequence[np.ndarray], sample_rate: int = 22050, 
             parts.append(silence(break_ms, sample_rate))
         parts.append(row)
     return wav_bytes(parts, sample_rate)
+
+
+def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Optional[float] = None, **settings) -> bytes:
+    """A request's sentences (one phoneme-id list each) -> the WAV the reference hands out (``mimic3_http/app.py:157-227``), in ONE
+    engine call: the id lists are padded into a batch, ``InferenceSession.run_packed(..., wav=True)`` synthesises them, puts
+    ``break_ms`` of silence between consecutive sentences and frames the stream on the GPU side — the one-call form of
+    ``utterances_to_wav`` over per-sentence ``run_pcm16`` calls, with no host pass over the audio.
+
+    ``settings``: ``scales`` ([3] or [B, 3]; default the reference's 0.667 / 1.0 / 0.8), ``sid`` (multi-speaker voices), and
+    ``volume`` / ``utterance_keys`` / ``tail_ms`` as ``run_packed`` takes them."""
+    rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]
+    if not rows or any(r.size == 0 for r in rows):
+        raise ValueError("request_wav needs at least one sentence, each with at least one phoneme id")
+    B, Tx = len(rows), max(r.size for r in rows)
+    ids = np.zeros((B, Tx), np.int64)
+    for b, r in enumerate(rows):
+        ids[b, : r.size] = r
+    feed = {"input": ids, "input_lengths": np.array([r.size for r in rows], np.int64),
+            "scales": np.asarray(settings.pop("scales", (0.667, 1.0, 0.8)), np.float32)}
+    sid = settings.pop("sid", None)
+    if sid is not None:
+        feed["sid"] = np.broadcast_to(np.asarray(sid, np.int64).reshape(-1), (B,)).copy()
+    lead_ms = [break_ms if (i and break_ms) else 0.0 for i in range(B)]
+    out = session.run_packed(feed, lead_ms=lead_ms, wav=True, **settings)
+    return bytes(out.wav)

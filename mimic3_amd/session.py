@@ -570,6 +570,35 @@ class InferenceSession:
         sentence: two thread hand-overs fewer; same bits).  ``utterance_keys`` ([B] ints): the Philox utterance index of each
         row instead of the session's running count (``reserve_utterances``) — a row's noise, hence its audio at nonzero
         noise scales, then depends on its own inputs only, not on the batch or the moment it rides in."""
+        kw = self._pcm_kw(volume, utterance_keys)
+        out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
+        return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
+
+    def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
+                   volume=None, utterance_keys=None) -> "_native.PackedAudio":
+        """The batch's finished audio as ONE contiguous int16 stream (``mi355vits_run_packed``): only the valid
+        samples of each row, rows in the order ``order`` names (default: all, in order), ``lead_ms[i]`` / ``lead_samples[i]`` of
+        silence in front of entry i (``add_break``, ``tts.py:452-465``: ``int(ms / 1000 * sample_rate)`` zero samples at the
+        voice's sample rate), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
+        copy of exactly those bytes.  Same feed, ``volume`` and ``utterance_keys`` as ``run_pcm16``, and every entry is bitwise
+        that call's row.  Returns ``_native.PackedAudio`` (``pcm``, ``rows`` — views of ``pcm`` —, ``offsets``, ``lengths``,
+        ``peaks``, ``wav``).  Always goes straight to a lane, never through the micro-batcher."""
+        kw = self._pcm_kw(volume, utterance_keys)
+        rate = self.config.sample_rate
+        if lead_ms is not None:
+            if lead_samples is not None:
+                raise InvalidArgument("give lead_ms or lead_samples, not both")
+            lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
+        ids, lengths, sid = self._feed(input_feed)
+        keys = kw.pop("utterance_keys", None)
+        out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
+                               lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
+        self.last_lengths = out.lengths
+        return out
+
+    @staticmethod
+    def _pcm_kw(volume, utterance_keys) -> Dict[str, Any]:
+        """``volume`` (percent, scalar or per row) and ``utterance_keys`` as the engine's keywords."""
         kw: Dict[str, Any] = {}
         if volume is not None and np.ndim(volume) > 0:
             vols = [float(v) for v in np.asarray(volume, np.float64).reshape(-1)]
@@ -583,10 +612,20 @@ class InferenceSession:
             kw["pcm_volume"] = float(volume) / 100.0
         if utterance_keys is not None:
             kw["utterance_keys"] = [int(k) for k in np.asarray(utterance_keys).reshape(-1).tolist()]
-        out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
-        return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
+        return kw
 
     def _run(self, input_feed, _direct: bool = False, **kw) -> Dict[str, np.ndarray]:
+        ids, lengths, sid = self._feed(input_feed)
+        if self._batcher is not None and not _direct and ids.shape[0] == 1 and lengths.shape[0] == 1 and 0 <= int(lengths[0]) <= ids.shape[1]:
+            sid1 = None if sid is None else np.asarray(sid).reshape(-1)
+            out = self._batcher.submit(np.asarray(ids, np.int64), lengths.astype(np.int64), input_feed["scales"], sid1, kw).result()
+        else:
+            out = self._engine_run(ids, lengths, input_feed["scales"], sid, **kw)
+        self.last_lengths = out["lengths"]
+        return out
+
+    def _feed(self, input_feed):
+        """The feed dict checked as onnxruntime checks it: (ids [B, Tx], lengths [B], sid or None)."""
         if not isinstance(input_feed, dict):
             raise InvalidArgument("input_feed must be a dict of numpy arrays")
         required = ["input", "input_lengths", "scales"] + (["sid"] if self.config.is_multispeaker else [])
@@ -605,13 +644,7 @@ class InferenceSession:
             raise InvalidArgument("'input' must be an int64 tensor")
         sid = input_feed.get("sid") if self.config.is_multispeaker else None
         lengths = np.asarray(input_feed["input_lengths"]).reshape(-1)
-        if self._batcher is not None and not _direct and ids.shape[0] == 1 and lengths.shape[0] == 1 and 0 <= int(lengths[0]) <= ids.shape[1]:
-            sid1 = None if sid is None else np.asarray(sid).reshape(-1)
-            out = self._batcher.submit(np.asarray(ids, np.int64), lengths.astype(np.int64), input_feed["scales"], sid1, kw).result()
-        else:
-            out = self._engine_run(ids, lengths, input_feed["scales"], sid, **kw)
-        self.last_lengths = out["lengths"]
-        return out
+        return ids, lengths, sid
 
     def reserve_utterances(self, n: int) -> int:
         """Reserve ``n`` consecutive Philox utterance indices of this session; returns the first.  Calls without
@@ -621,7 +654,7 @@ class InferenceSession:
             self._utterances += int(n)
         return base
 
-    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, **kw) -> Dict[str, np.ndarray]:
+    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, **kw):
         if self._closed:
             raise RuntimeError("session is closed")
         keys = None if utterance_keys is None else list(utterance_keys)
@@ -632,7 +665,8 @@ class InferenceSession:
                 keys = [base + b if k is None else int(k) for b, k in enumerate(keys)]
         eng = self._free_lanes.acquire()  # blocks while every lane is busy; first come first served
         try:
-            return eng.run(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
+            call = eng.run_packed if _packed else eng.run
+            return call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
         except _native.NativeError as e:
             if e.code == -1:
                 raise InvalidArgument(str(e)) from None
