@@ -183,6 +183,26 @@ int mi355vits_set_math(mi355vits_handle h, int mode);
 int mi355vits_get_math(mi355vits_handle h);
 int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out);
 
+/* ---- Output sample rate.  0 (the default) or the voice's own rate = native: nothing below applies and nothing is launched
+ * or laid out for it.  With another rate set, every result of a run is the synthesized waveform band-limited and resampled to
+ * that rate as f32 on the GPU (k_resample), and everything behind the waveform works on the resampled rows:
+ *   y[k] = sum_j h[k M - j L + half] x[j],  x zero outside the row's samples,  lengths[b] = ceil(n_b L / M),
+ *   L / M = hz / config.sample_rate reduced, h = L x the Kaiser (beta 5) windowed sinc with cut-off 1 / max(L, M) of Nyquist,
+ *   half = 10 max(L, M) taps each side, unit DC gain — the filter and the output of scipy.signal.resample_poly(x, L, M);
+ *   f32 products and sums in one fixed order per sample, so a row of a batch is bitwise the row alone.
+ *  - mi355vits_run / _run_rows: audio, pcm, lengths, peaks (max |y| over the resampled row: what audio_float_to_int16
+ *    normalises by) and l_max (= max lengths, the row stride) are at the output rate; ty_max stays in frames.
+ *  - mi355vits_run_packed / _fetch_packed: lead_samples, tail_samples, offsets, total_samples count output-rate samples, the RIFF
+ *    header carries the output rate, and the size limits are checked on the resampled sizes before anything is sized or launched.
+ *  - The setting is read when a run starts; mi355vits_fetch / _fetch_packed / _device_result serve the last run at the rate it
+ *    ran at.  MI355VITS_DEBUG_TAPS and mi355vits_get_config().sample_rate stay native.  mi355vits_clone inherits the setting.
+ *  - Supported: hz >= 1 with both terms of the reduced ratio <= 640 (from 22,050 Hz: 8000, 11025, 16000, 24000, 32000, 44100,
+ *    48000, 88200, 96000 ...).  Anything else returns MI355VITS_ERR_INVALID with a message naming the rate and the reduced ratio
+ *    and leaves the setting as it was.  A row whose resampled length does not fit int32 fails its run the same way.
+ *  - No additional stream synchronisation or host round trip per call: the resampled lengths follow from the frame counts. */
+int mi355vits_set_output_rate(mi355vits_handle h, int32_t hz);
+int32_t mi355vits_get_output_rate(mi355vits_handle h); /* the effective rate: the voice's own when unset */
+
 /* One synthesis call.  `out` is filled with callee-allocated (pinned) host buffers; release
  * them with mi355vits_free_result.  With MI355VITS_DEVICE_ONLY the audio stays in the engine's
  * workspace until the next run; mi355vits_fetch copies it out afterwards. */

@@ -53,6 +53,13 @@ int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern);
  * f32-MFMA kernel (T <= 512), 2 = the streamed kernel (any T).  Query rows at or past len[b]: what the kernel writes. */
 int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int n_heads, int W, const float* qkv,
                                  const float* emb_rel_k, const float* emb_rel_v, const int32_t* len, float* out);
+/* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
+ * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
+ * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros
+ * past a row's output length); y_lengths [B], peaks [B] = max |y| over the valid samples.  MI355VITS_ERR_INVALID for a rate pair
+ * the engine would refuse. */
+int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* x, const int32_t* lengths, int32_t in_hz,
+                            int32_t out_hz, int64_t y_stride, float* y, int32_t* y_lengths, float* peaks);
 /* Kernel micro-benchmark hook (tools/convbench.py): times `reps` launches of one MFMA Conv1d on random device data.
  * epi: 0 = standard epilogue (bias + residual), 1 = WaveNet gate (Cout = 2*H), 2 = res/skip.  (The tile-shape overrides
  * MI355VITS_CONV_CFG / MI355VITS_CONV_CHUNK exist in the lab build of the library only, csrc/hipx.h lab_getenv.) */

@@ -35,11 +35,12 @@ EXPORTED_SYMBOLS = (
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
+    "mi355vits_set_output_rate", "mi355vits_get_output_rate",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
-    "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace",
+    "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
 )
 
 
@@ -157,6 +158,9 @@ class NativeLibrary:
                                               ctypes.POINTER(ctypes.c_void_p)]
         L.mi355vits_set_math.argtypes = [H, ctypes.c_int]
         L.mi355vits_get_math.argtypes = [H]
+        L.mi355vits_set_output_rate.argtypes = [H, ctypes.c_int32]
+        L.mi355vits_get_output_rate.argtypes = [H]
+        L.mi355vits_get_output_rate.restype = ctypes.c_int32
         L.mi355vits_destroy.argtypes = [H]
         L.mi355vits_destroy.restype = None
         L.mi355vits_get_config.argtypes = [H, ctypes.POINTER(CVitsConfig)]
@@ -202,6 +206,10 @@ class NativeLibrary:
             L.mi355vits_bench_conv1d.argtypes = [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_probe_device.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
             L.mi355vits_probe_weights.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+            L.mi355vits_test_resample.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_float),
+                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
 
@@ -291,6 +299,27 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return out
+
+    def test_resample(self, x, lengths, in_hz: int, out_hz: int, device=0):
+        """The product's resampler launch (k_resample) on caller-given f32 rows: x [B, row_stride], lengths [B] valid samples
+        of each row (what lies past them is never looked at) -> (y [B, max n_out] with zeros past a row's output length,
+        y_lengths [B], peaks [B])."""
+        self._need_hooks()
+        x = np.ascontiguousarray(x, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        B, stride = x.shape
+        g = int(np.gcd(int(in_hz), int(out_hz))) if in_hz > 0 and out_hz > 0 else 1
+        up, down = int(out_hz) // g, int(in_hz) // g
+        ys = max(1, int(max(-(-int(n) * up // down) for n in ln))) if up > 0 else 1
+        y = np.empty((B, ys), np.float32)
+        yl = np.zeros(B, np.int32)
+        pk = np.zeros(B, np.float32)
+        rc = self.lib.mi355vits_test_resample(device, B, stride, _fptr(x), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              int(in_hz), int(out_hz), ys, _fptr(y), yl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              _fptr(pk))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return y, yl, pk
 
     def bench_conv1d(self, B, Cin, Cout, T, K, dilation=1, epi=0, reps=20, device=0) -> float:
         self._need_hooks()
@@ -397,8 +426,9 @@ class PackedAudio:
     ``pcm[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
     when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry."""
 
-    def __init__(self, pcm, offsets, lengths, peaks, wav):
+    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None):
         self.pcm, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
+        self.sample_rate = sample_rate  # of every sample of the stream: the rate the run ran at
         self.total_samples = int(pcm.shape[0])
         self.rows = [pcm[int(o): int(o) + int(n)] for o, n in zip(offsets, lengths)]
 
@@ -431,6 +461,7 @@ class Engine:
         self.config = VitsConfig.from_c(c)
         self.device = device
         self._last_batch = 0  # rows of the last completed run (fetch_packed's default pack with a tail or a header)
+        self._last_rate = int(self.config.sample_rate)  # the rate it ran at (results of a run keep it)
 
     def _check(self, rc: int) -> None:
         if rc != 0:
@@ -465,6 +496,7 @@ class Engine:
             self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
         del keep
         self._last_batch = int(a.batch)
+        self._last_rate = self.output_rate  # read when the run started; only this thread sets it meanwhile
         return self._take(r)
 
     def _args(self, ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations, pcm_volume, utterance_keys):
@@ -577,6 +609,7 @@ class Engine:
                                                          None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del keep, pkeep
         self._last_batch = int(a.batch)
+        self._last_rate = self.output_rate
         return self._take_packed(r, bool(wav))
 
     def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
@@ -604,7 +637,24 @@ class Engine:
             raise
         block = _PackedHolder(self.native, r).view()
         pcm = block[hdr:].view("<i2")
-        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None)
+        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate)
+
+    def set_output_rate(self, hz) -> None:
+        """The sample rate of every result of the runs that start after this (``mi355vits_set_output_rate``): ``None`` / 0 or
+        the voice's own rate = native; else the waveform is resampled on the GPU (``scipy.signal.resample_poly``'s filter and
+        output) before the int16 conversion, packing and silences.  A rate whose reduced ratio to the voice's has a term above
+        640 raises and leaves the setting as it was."""
+        self._check(self.native.lib.mi355vits_set_output_rate(self._h, int(hz or 0)))
+
+    @property
+    def output_rate(self) -> int:
+        """The effective rate of the next run's results: the voice's own when none is set."""
+        return int(self.native.lib.mi355vits_get_output_rate(self._h))
+
+    @property
+    def last_rate(self) -> int:
+        """The rate the last completed run of this handle ran at: what ``fetch`` / ``fetch_packed`` / ``device_result`` serve."""
+        return self._last_rate
 
     MATH_MODES = {"f32": 0, "bf16x3": 1, "bf16w": 2, "f16x2": 3}
 

@@ -97,6 +97,17 @@ int mi355vits_get_math(mi355vits_handle h) {
     return h->eng->math();
 }
 
+int mi355vits_set_output_rate(mi355vits_handle h, int32_t hz) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_output_rate(hz); });
+}
+int32_t mi355vits_get_output_rate(mi355vits_handle h) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return h->eng->output_rate();
+}
+
 int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
     if (!h) return MI355VITS_ERR_INVALID;
     return guarded(h, [&] {

@@ -393,6 +393,7 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         model_ = lane0.model_;
         math_ = lane0.math_;
         sw_ = lane0.sw_;
+        if (lane0.out_hz_) set_output_rate(lane0.out_hz_);
     } catch (...) {
         release();
         throw;
@@ -445,6 +446,41 @@ void Engine::open_device(int device) {
 void Engine::set_math(int mode) {
     if (mode != MATH_F32 && mode != MATH_BF16X3 && mode != MATH_BF16W && mode != MATH_F16X2) throw EngineError(MI355VITS_ERR_INVALID, "unknown math mode");
     math_ = mode;
+}
+
+// The rate of every result of the runs that start after this.  Nothing of the handle changes unless the whole setting succeeds.
+void Engine::set_output_rate(int hz) {
+    if (hz == 0 || hz == cfg_.sample_rate) {  // native: no kernel, no buffer (the table of an earlier setting stays where it is, unused)
+        out_hz_ = 0;
+        return;
+    }
+    if (d_rs_coef_ && hz == rs_.out_hz) {  // the table of this rate is still on the device (set, then native, then set again)
+        out_hz_ = hz;
+        return;
+    }
+    ResampleFilter f;
+    if (!resample_design(cfg_.sample_rate, hz, f)) {
+        std::string ratio;
+        if (hz >= 1) {
+            int a = hz, b = cfg_.sample_rate;
+            while (b) { const int t = a % b; a = b; b = t; }
+            ratio = " = " + std::to_string(hz / a) + " / " + std::to_string(cfg_.sample_rate / a) + " of the voice's " + std::to_string(cfg_.sample_rate) + " Hz";
+        }
+        throw EngineError(MI355VITS_ERR_INVALID, "output rate " + std::to_string(hz) + " Hz" + ratio + " not supported: the rate must be >= 1 and both terms of the reduced ratio <= " +
+                                                     std::to_string(RESAMPLE_MAX_RATIO));
+    }
+    HIP_CHECK(hipSetDevice(device_));
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, f.table.size() * 4));
+    if (hipMemcpy(p, f.table.data(), f.table.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(p);
+        throw EngineError(MI355VITS_ERR_DEVICE, "output rate: the filter upload failed");
+    }
+    HIP_CHECK(hipStreamSynchronize(stream_));  // no run of this handle still reads the table about to be freed
+    if (d_rs_coef_) (void)hipFree(d_rs_coef_);
+    d_rs_coef_ = static_cast<float*>(p);
+    rs_ = std::move(f);
+    out_hz_ = hz;
 }
 
 void Engine::construct(const WeightsFile& wf, int device) {
@@ -695,6 +731,8 @@ void Engine::release() noexcept {
     if (stream_) (void)hipStreamSynchronize(stream_);
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();
+    if (d_rs_coef_) (void)hipFree(d_rs_coef_);
+    d_rs_coef_ = nullptr;
     model_.reset();  // the replica is freed with its last lane
     if (ev_start_) (void)hipEventDestroy(ev_start_);
     if (ev_end_) (void)hipEventDestroy(ev_end_);
@@ -1555,7 +1593,7 @@ template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool for
     for (int j = 0; cond && j < c.flow_n_flows; ++j) d_cond_flow_.push_back(ar.template alloc<float>(B * 2 * H * c.flow_wn_layers));
 }
 
-template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames) {
+template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr) {
     const mi355vits_config& c = cfg_;
     const size_t H = c.hidden_channels, I = c.inter_channels, fBTy = B * Ty;
     size_t ch = c.upsample_initial_channel, T = Ty, max_stage = ch * T;  // the widest decoder tensor of a row
@@ -1575,10 +1613,13 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_bufT_ = ar.template alloc<float>(B * max_stage);
     d_bufC_ = ar.template alloc<float>(B * max_stage);
     d_audio_ = ar.template alloc<float>(B * L_);
-    d_pcm_ = ar.template alloc<int16_t>(B * L_);
-    // per-stage valid lengths and (last row) the audio lengths
-    d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B);
+    d_pcm_ = ar.template alloc<int16_t>(B * (Lr ? Lr : (size_t)L_));  // of the rows the caller receives
+    d_raudio_ = Lr ? ar.template alloc<float>(B * Lr) : nullptr;
+    d_rpeaks_ = Lr ? ar.template alloc<unsigned>(B) : nullptr;
+    // per-stage valid lengths and (last row) the audio lengths; a resampled run's table behind them
+    d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B + (Lr ? resample_tab_ints((int)B) : 0));
     d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
+    d_rtab_ = Lr ? d_alen_ + B : nullptr;
 }
 
 // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
@@ -1738,24 +1779,40 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     Ty_ = Ty;
     const long hop = c.hop_length;
     L_ = (long)Ty * hop;
+    // the rows the caller receives: the waveform itself, or with an output rate set what the resampler makes of it — lengths from
+    // the frame counts, so its table rides in the upload below
+    const bool rs = out_hz_ != 0;
+    run_hz_ = rs ? out_hz_ : c.sample_rate;
+    h_olen_.resize(B);
+    Lo_ = rs ? 0 : L_;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = (int64_t)h_ylen_[b] * hop;
+        h_olen_[b] = rs ? (int64_t)resample_out_len(n, rs_.L, rs_.M) : n;
+        if (h_olen_[b] > 0x7fffffffLL)
+            throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": " + std::to_string(h_olen_[b]) + " samples at " + std::to_string(run_hz_) + " Hz do not fit 32 bits");
+        if (rs) Lo_ = std::max<long>(Lo_, (long)h_olen_[b]);
+    }
     if (plan) place_pack(*plan);  // offsets from the frame counts just read; the size limits, before phase B is sized
 
     // ---------------- phase B workspace
     const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
     ArenaCount size_b;
-    layout_b(size_b, B, Ty, nz_frames);
+    layout_b(size_b, B, Ty, nz_frames, rs ? Lo_ : 0);
     if (plan) layout_pack(size_b, plan->n, plan->total);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
-    layout_b(arena_b_, B, Ty, nz_frames);
+    layout_b(arena_b_, B, Ty, nz_frames, rs ? Lo_ : 0);
     layout_b_end_ = arena_b_.used();
+    o_audio_ = rs ? d_raudio_ : d_audio_;
+    o_peaks_ = rs ? d_rpeaks_ : d_peaks_;
+    o_alen_ = rs ? d_rtab_ : d_alen_;
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
     if (plan) layout_pack(arena_b_, plan->n, plan->total);
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     // (a packed call's segment table sits right behind d_slen_ in the arena: the same copy brings it)
-    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + 3 * (size_t)plan->n : (size_t)(c.n_upsamples + 2) * B, 0);
+    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + 3 * (size_t)plan->n : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
     if (plan) fill_pack_seg(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
     {
         long f = 1;
@@ -1765,16 +1822,28 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         }
         for (int b = 0; b < B; ++b) h_slen_[(size_t)(c.n_upsamples + 1) * B + b] = (int)(h_ylen_[b] * hop);
     }
+    long rs_items = 0;
+    if (rs) rs_items = resample_fill_tab(rs_, h_slen_.data() + (d_alen_ - d_slen_), B, h_slen_.data() + (d_rtab_ - d_slen_));
     HIP_CHECK(hipMemcpyAsync(d_slen_, h_slen_.data(), h_slen_.size() * 4, hipMemcpyHostToDevice, stream_));
 
     flow_and_decoder(B, Ty, args);
+    if (rs) {
+        double n_in = 0, n_out = 0;
+        for (int b = 0; b < B; ++b) {
+            n_in += (double)h_ylen_[b] * hop;
+            n_out += (double)h_olen_[b];
+        }
+        ProfScope ps(prof_, "resample", 2.0 * rs_.tpp * n_out, 4.0 * n_in + 4.0 * n_out);
+        HIP_CHECK(hipMemsetAsync(d_rpeaks_, 0, sizeof(unsigned) * B, stream_));
+        launch_resample(rs_, d_rs_coef_, d_audio_, L_, d_alen_, B, d_rtab_, rs_items, d_raudio_, Lo_, (int)Lo_, d_rpeaks_, stream_);
+    }
 
     have_pcm_ = false;
     if (plan) {
         launch_pack(*plan);  // the packed stream and nothing else: MI355VITS_WANT_* / DEVICE_ONLY are not looked at
     } else if (args.flags & MI355VITS_WANT_PCM16) {
-        ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)L_);
-        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, d_vol_);
+        ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)Lo_);
+        launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B, (int)Lo_, d_pcm_, Lo_, stream_, d_vol_);
         have_pcm_ = true;
     }
     HIP_CHECK(hipEventRecord(ev_end_, stream_));
@@ -1787,30 +1856,30 @@ void Engine::copy_out(uint32_t want, mi355vits_result* out) {
     auto* own = new ResultOwner();
     out->owner_ = own;
     out->batch = B;
-    out->l_max = L_;
+    out->l_max = Lo_;
     out->ty_max = Ty_;
     own->lengths = malloc(sizeof(int64_t) * B);
     own->peaks = malloc(sizeof(float) * B);
     out->lengths = static_cast<int64_t*>(own->lengths);
     out->peaks = static_cast<float*>(own->peaks);
     if (!out->lengths || !out->peaks) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
-    for (int b = 0; b < B; ++b) out->lengths[b] = (int64_t)h_ylen_[b] * cfg_.hop_length;
+    for (int b = 0; b < B; ++b) out->lengths[b] = h_olen_[b];
     std::vector<unsigned> pk(B);
-    HIP_CHECK(hipMemcpyAsync(pk.data(), d_peaks_, sizeof(unsigned) * B, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B, hipMemcpyDeviceToHost, stream_));
     const bool dev_only = (want & MI355VITS_DEVICE_ONLY) != 0;
     if (!dev_only && (want & MI355VITS_WANT_FLOAT)) {
-        own->audio = PinnedPool::get().take(sizeof(float) * (size_t)B * L_ + 16, &own->audio_cap);
+        own->audio = PinnedPool::get().take(sizeof(float) * (size_t)B * Lo_ + 16, &own->audio_cap);
         out->audio = static_cast<float*>(own->audio);
-        HIP_CHECK(hipMemcpyAsync(out->audio, d_audio_, sizeof(float) * (size_t)B * L_, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(out->audio, o_audio_, sizeof(float) * (size_t)B * Lo_, hipMemcpyDeviceToHost, stream_));
     }
     if (!dev_only && (want & MI355VITS_WANT_PCM16)) {
         if (!have_pcm_) {
-            launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B, (int)L_, d_pcm_, L_, stream_, nullptr);
+            launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B, (int)Lo_, d_pcm_, Lo_, stream_, nullptr);
             have_pcm_ = true;
         }
-        own->pcm = PinnedPool::get().take(sizeof(int16_t) * (size_t)B * L_ + 16, &own->pcm_cap);
+        own->pcm = PinnedPool::get().take(sizeof(int16_t) * (size_t)B * Lo_ + 16, &own->pcm_cap);
         out->pcm = static_cast<int16_t*>(own->pcm);
-        HIP_CHECK(hipMemcpyAsync(out->pcm, d_pcm_, sizeof(int16_t) * (size_t)B * L_, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(out->pcm, d_pcm_, sizeof(int16_t) * (size_t)B * Lo_, hipMemcpyDeviceToHost, stream_));
     }
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (int b = 0; b < B; ++b) memcpy(&out->peaks[b], &pk[b], 4);
@@ -1874,7 +1943,7 @@ void Engine::place_pack(PackPlan& plan) const {
     for (int i = 0; i < plan.n; ++i) {
         pos += plan.lead[i];
         plan.offsets[i] = pos;
-        plan.lengths[i] = (int64_t)h_ylen_[plan.order[i]] * cfg_.hop_length;
+        plan.lengths[i] = h_olen_[plan.order[i]];  // at the run's rate
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
         check_pack_size(i, pos, plan.wav);
@@ -1893,7 +1962,7 @@ void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
 
 void Engine::launch_pack(const PackPlan& plan) {
     ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
-    launch_pcm16_pack(d_audio_, L_, d_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
+    launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
 }
 
 void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
@@ -1915,14 +1984,14 @@ void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out)
     out->n_bytes = hdr + data;
     out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);
     std::vector<unsigned> pk(B_);
-    HIP_CHECK(hipMemcpyAsync(pk.data(), d_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
     if (plan.wav) {
         // RIFF/WAVE, PCM, mono, 16 bit: the 44 bytes the stdlib `wave` module writes (little-endian fields)
         uint8_t* h = out->bytes;
         auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
         auto u16 = [&](size_t at, uint32_t v) { h[at] = (uint8_t)v; h[at + 1] = (uint8_t)(v >> 8); };
-        const uint32_t rate = (uint32_t)cfg_.sample_rate;
+        const uint32_t rate = (uint32_t)run_hz_;  // the rate the run ran at
         memcpy(h, "RIFF", 4);
         u32(4, (uint32_t)(36 + data));
         memcpy(h + 8, "WAVEfmt ", 8);
@@ -1997,15 +2066,15 @@ void Engine::device_buffers(const int16_t** pcm, const float** audio, long* row_
     if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "device_buffers: no completed run on this handle");
     HIP_CHECK(hipSetDevice(device_));
     if (pcm && !have_pcm_) {
-        launch_pcm16(d_audio_, L_, d_peaks_, d_alen_, B_, (int)L_, d_pcm_, L_, stream_, nullptr);
+        launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B_, (int)Lo_, d_pcm_, Lo_, stream_, nullptr);
         have_pcm_ = true;
     }
     HIP_CHECK(hipStreamSynchronize(stream_));  // the caller reads them from another stream (RCCL)
     if (pcm) *pcm = d_pcm_;
-    if (audio) *audio = d_audio_;
-    if (row_stride) *row_stride = L_;
+    if (audio) *audio = o_audio_;
+    if (row_stride) *row_stride = Lo_;
     if (batch) *batch = B_;
-    if (dev_lengths) *dev_lengths = d_alen_;
+    if (dev_lengths) *dev_lengths = o_alen_;
 }
 
 void Engine::fetch(uint32_t want, mi355vits_result* out) {

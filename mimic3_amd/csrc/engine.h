@@ -172,6 +172,9 @@ class Engine {
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
+    // the rate of every result (mi355vits_set_output_rate): 0 or the voice's own = native.  Read when a run starts.
+    void set_output_rate(int hz);
+    int output_rate() const { return out_hz_ ? out_hz_ : cfg_.sample_rate; }
     Profiler& profiler() { return prof_; }
     float last_run_ms();
     long get_tap(const std::string& name, float* out, size_t cap, int64_t dims[4], long row0 = 0, long nrows = -1);
@@ -211,7 +214,8 @@ class Engine {
     ConvArgs rb2_conv_args(int i, int j, int m, int B, int ch, long T) const;
     // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
-    template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames);
+    // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
+    template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
     template <typename A> void layout_pack(A& ar, size_t n, size_t samples);  // continues layout_b in packed calls, and only there
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
@@ -272,6 +276,21 @@ class Engine {
     float* d_audio_ = nullptr;
     int16_t* d_pcm_ = nullptr;
     unsigned* d_peaks_ = nullptr;
+    // output rate (mi355vits_set_output_rate).  The filter of the handle's setting, its table on the device; a run at another
+    // rate than the voice's resamples d_audio_ into d_raudio_ (k_resample) and everything behind the waveform works on the o_*
+    // view: the resampled rows, or in a native run d_audio_ / d_peaks_ / d_alen_ / L_ themselves.
+    int out_hz_ = 0;               // the setting: 0 = native
+    ResampleFilter rs_;
+    float* d_rs_coef_ = nullptr;   // rs_.table (an allocation of its own: it outlives the runs)
+    int run_hz_ = 0;               // the rate the last run ran at
+    float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
+    unsigned* d_rpeaks_ = nullptr;
+    int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)
+    const float* o_audio_ = nullptr;
+    const unsigned* o_peaks_ = nullptr;
+    const int* o_alen_ = nullptr;
+    long Lo_ = 0;                  // row stride and l_max of the results
+    std::vector<int64_t> h_olen_;  // [B] valid samples of a row at the run's rate
     int* d_slen_ = nullptr;  // [n_upsamples + 1][B] valid frames per decoder stage
     // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table [3][n] right behind
     // d_slen_ (one upload brings both) and the stream itself

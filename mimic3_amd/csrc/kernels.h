@@ -4,6 +4,8 @@
 #pragma once
 #include "hipx.h"
 
+#include <vector>
+
 namespace m355 {
 
 struct Profiler;  // engine.h
@@ -213,6 +215,32 @@ constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes
 inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
                        int16_t* out, long total, hipStream_t s);
+
+// ---------------------------------------------------------------- output at a requested sample rate (kernels_resample.cpp)
+// y[k] = sum_j h[k M - j L + half] x[j], x zero outside [0, n): what scipy.signal.resample_poly(x, L, M) returns with its default
+// filter (Kaiser beta 5, half = 10 max(L, M) taps each side, cut-off 1 / max(L, M), gain L); n_out = ceil(n L / M).
+constexpr int RESAMPLE_MAX_RATIO = 640;  // max(L, M) of a supported rate pair: at most 12,801 taps
+struct ResampleFilter {
+    int in_hz = 0, out_hz = 0;
+    int L = 1, M = 1, half = 0;
+    int tpp = 0;    // taps of one phase: ceil((2 half + 1) / L)
+    int tp = 0;     // a phase's row in the table: tpp rounded up to a multiple of 4 with tp / 4 odd (zero taps behind)
+    int tile = 0;   // outputs per work item (what fits the LDS beside the table; 1024 for every common rate)
+    std::vector<float> table;  // [L][tp], phase-major; row p holds h[p + (tpp - 1 - i) L] at i: the order the taps are summed in
+};
+// designs the filter in double; false when out_hz < 1 or max(L, M) > RESAMPLE_MAX_RATIO (f untouched)
+bool resample_design(int in_hz, int out_hz, ResampleFilter& f);
+inline long long resample_out_len(long long n, int L, int M) { return (n * L + M - 1) / M; }
+// the kernel's per-call table: [B] output lengths, then [B + 1] first work item of every row (a row has max(1, ceil(n_out / tile))
+// items); n_in = the rows' input lengths on the host.  Returns the number of work items.
+inline size_t resample_tab_ints(int B) { return 2 * (size_t)B + 1; }
+long resample_fill_tab(const ResampleFilter& f, const int* n_in, int B, int* tab);
+// x [B] rows of x_bs floats, x_len [B] (device); coef = f.table on the device; tab = the table above on the device.  Writes every
+// sample of y's rows [0, y_ld): zeros at and past a row's output length.  peak_bits [B] must be zero: max |y| over the valid samples
+// is added with an atomic max on the float's bits.  Every output sample is one fixed chain of tp fused multiply-adds, whatever the
+// tile, the grid or the batch.
+void launch_resample(const ResampleFilter& f, const float* coef, const float* x, long x_bs, const int* x_len, int B, const int* tab,
+                     long items, float* y, long y_bs, int y_ld, unsigned* peak_bits, hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

@@ -107,6 +107,37 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
     });
 }
 
+int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* x, const int32_t* lengths, int32_t in_hz,
+                            int32_t out_hz, int64_t y_stride, float* y, int32_t* y_lengths, float* peaks) {
+    return guarded(nullptr, [&] {
+        if (!x || !lengths || !y || !y_lengths || !peaks || B < 1 || row_stride < 1 || y_stride < 1 || y_stride > 0x7fffffffLL)
+            throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        ResampleFilter f;
+        if (!resample_design(in_hz, out_hz, f)) throw EngineError(MI355VITS_ERR_INVALID, "rate pair not supported");
+        std::vector<int> tab(resample_tab_ints(B));
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 0 || lengths[b] > row_stride || resample_out_len(lengths[b], f.L, f.M) > y_stride)
+                throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+        const long items = resample_fill_tab(f, lengths, B, tab.data());
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nx = (size_t)B * row_stride, ny = (size_t)B * y_stride;
+        DevBuf dx(nx * 4), dy(ny * 4), dl(B * 4), dt(tab.size() * 4), dc(f.table.size() * 4), dp(B * 4);
+        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, lengths, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dt.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, f.table.data(), f.table.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dy.p, 0xff, ny * 4));  // NaNs: the kernel writes every sample of y
+        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
+        launch_resample(f, dc.as<float>(), dx.as<float>(), (long)row_stride, dl.as<int>(), B, dt.as<int>(), items, dy.as<float>(),
+                        (long)y_stride, (int)y_stride, dp.as<unsigned>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b) y_lengths[b] = tab[b];
+    });
+}
+
 int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern) {
     if (!h) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);

@@ -60,7 +60,8 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     ``utterances_to_wav`` over per-sentence ``run_pcm16`` calls, with no host pass over the audio.
 
     ``settings``: ``scales`` ([3] or [B, 3]; default the reference's 0.667 / 1.0 / 0.8), ``sid`` (multi-speaker voices), and
-    ``volume`` / ``utterance_keys`` / ``tail_ms`` as ``run_packed`` takes them."""
+    ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` as ``run_packed`` takes them (with ``sample_rate`` the file is
+    at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it)."""
     rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]
     if not rows or any(r.size == 0 for r in rows):
         raise ValueError("request_wav needs at least one sentence, each with at least one phoneme id")

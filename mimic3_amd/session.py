@@ -488,6 +488,9 @@ class InferenceSession:
         self._providers = ["MI355XExecutionProvider"]
         device = _device_from_providers(providers, provider_options, self._sess_options)
         library = kwargs.pop("_library", None)  # tests only: an explicit NativeLibrary
+        # the rate of every result (Engine.set_output_rate): None = the voice's own; a call's ``sample_rate=`` goes before it
+        rate = kwargs.pop("output_sample_rate", None)
+        self.output_sample_rate: Optional[int] = int(rate) if rate else None
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -510,6 +513,12 @@ class InferenceSession:
             if getattr(self._sess_options, "math", None):
                 for e in self._engines:
                     e.set_math(self._sess_options.math)
+            if self.output_sample_rate:
+                try:
+                    for e in self._engines:  # a rate the engine refuses fails here, not in the first call
+                        e.set_output_rate(self.output_sample_rate)
+                except _native.NativeError as e:
+                    raise InvalidArgument(str(e)) from None
         except BaseException:
             for e in reversed(self._engines):  # clones before the handles whose weights they share
                 e.close()
@@ -558,8 +567,8 @@ class InferenceSession:
         return [audio[:, None, :]]
 
     # ---- engine extensions --------------------------------------------------------------------
-    def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None
-                  ) -> Tuple[List[np.ndarray], np.ndarray]:
+    def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
+                  sample_rate: Optional[int] = None) -> Tuple[List[np.ndarray], np.ndarray]:
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -569,22 +578,28 @@ class InferenceSession:
         single-utterance call goes straight to a lane instead of through the micro-batcher's queue (a planned request's first
         sentence: two thread hand-overs fewer; same bits).  ``utterance_keys`` ([B] ints): the Philox utterance index of each
         row instead of the session's running count (``reserve_utterances``) — a row's noise, hence its audio at nonzero
-        noise scales, then depends on its own inputs only, not on the batch or the moment it rides in."""
+        noise scales, then depends on its own inputs only, not on the batch or the moment it rides in.  ``sample_rate``: the
+        rate of this call's audio instead of the session's ``output_sample_rate`` (resampled as f32 on the GPU before the int16
+        conversion; not a per-row setting: micro-batched requests of different rates never share an engine call)."""
         kw = self._pcm_kw(volume, utterance_keys)
+        if sample_rate is not None:
+            kw["sample_rate"] = int(sample_rate)
         out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
         return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
-                   volume=None, utterance_keys=None) -> "_native.PackedAudio":
+                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous int16 stream (``mi355vits_run_packed``): only the valid
         samples of each row, rows in the order ``order`` names (default: all, in order), ``lead_ms[i]`` / ``lead_samples[i]`` of
         silence in front of entry i (``add_break``, ``tts.py:452-465``: ``int(ms / 1000 * sample_rate)`` zero samples at the
-        voice's sample rate), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
+        rate of the stream: ``sample_rate``, else the session's ``output_sample_rate``, else the voice's), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
         copy of exactly those bytes.  Same feed, ``volume`` and ``utterance_keys`` as ``run_pcm16``, and every entry is bitwise
         that call's row.  Returns ``_native.PackedAudio`` (``pcm``, ``rows`` — views of ``pcm`` —, ``offsets``, ``lengths``,
-        ``peaks``, ``wav``).  Always goes straight to a lane, never through the micro-batcher."""
+        ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher."""
         kw = self._pcm_kw(volume, utterance_keys)
-        rate = self.config.sample_rate
+        if sample_rate is not None:
+            kw["sample_rate"] = int(sample_rate)
+        rate = int(sample_rate or self.output_sample_rate or self.config.sample_rate)
         if lead_ms is not None:
             if lead_samples is not None:
                 raise InvalidArgument("give lead_ms or lead_samples, not both")
@@ -654,7 +669,7 @@ class InferenceSession:
             self._utterances += int(n)
         return base
 
-    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, **kw):
+    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, **kw):
         if self._closed:
             raise RuntimeError("session is closed")
         keys = None if utterance_keys is None else list(utterance_keys)
@@ -665,6 +680,8 @@ class InferenceSession:
                 keys = [base + b if k is None else int(k) for b, k in enumerate(keys)]
         eng = self._free_lanes.acquire()  # blocks while every lane is busy; first come first served
         try:
+            # the call owns the lane: its rate is set here and read by the engine when the run starts
+            eng.set_output_rate(sample_rate if sample_rate is not None else self.output_sample_rate)
             call = eng.run_packed if _packed else eng.run
             return call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
         except _native.NativeError as e:
