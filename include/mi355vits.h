@@ -271,6 +271,47 @@ int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, con
 int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out);
 void mi355vits_free_packed(mi355vits_packed_result* r);
 
+/* ---- Sample encoding of the packed stream.  MI355VITS_ENC_S16LE (the default) = the stream described above and nothing below
+ * applies: k_pcm16_pack runs as ever, the 44-byte header is the PCM one, every byte is what it was before this setting existed.
+ * With another encoding the kernel that touches every output sample writes the format the caller ships (k_pack_enc), so neither a
+ * second pass over the audio on the host (audioop.lin2ulaw) nor bytes nobody wants cross the bus:
+ *   MI355VITS_ENC_ULAW / _ALAW  G.711, 1 byte per sample (telephony at 8000 Hz: see mi355vits_set_output_rate).  Entry i's byte k
+ *                     is the G.711 code of int16 sample k of the S16LE stream for the same arguments — the value after
+ *                     audio_float_to_int16 and the row's audioop.mul volume — and equals CPython's audioop.lin2ulaw(x, 2) /
+ *                     audioop.lin2alaw(x, 2) for all 65,536 inputs.  Every other byte of the stream is the code of sample 0:
+ *                     0xFF (mu-law) / 0xD5 (A-law) — silence is NOT zero bytes — and is written by the kernel.
+ *   MI355VITS_ENC_F32LE  the float waveform itself, 4 bytes per sample.  Entry i's samples are BITWISE the valid samples of that
+ *                     row's MI355VITS_WANT_FLOAT audio at the run's output rate: no normalisation, and pcm_volume does not apply
+ *                     (as with MI355VITS_WANT_FLOAT).  Every other sample is 0.0f.
+ *  - Scope: packed streams only (mi355vits_run_packed, mi355vits_fetch_packed).  mi355vits_run / _run_rows / _fetch /
+ *    _device_result and the padded pcm / audio results are unchanged by it.
+ *  - The setting is read when a pack is made: at the start of mi355vits_run_packed and at each mi355vits_fetch_packed.  After one
+ *    synthesis, fetch_packed can therefore serve the same run in several encodings, no synthesis work repeated.
+ *    mi355vits_clone inherits the setting.  An unknown value returns MI355VITS_ERR_INVALID with a message naming the value and
+ *    leaves the setting as it was.
+ *  - Result fields: offsets, lengths, total_samples (and lead_samples / tail_samples) stay in SAMPLES; peaks are as before.
+ *    n_bytes = header + bytes_per_sample * total_samples (+ pad).  pcm points at the first data byte whatever the encoding: cast
+ *    it to uint8_t* (G.711) or float* (F32LE; 4-byte aligned with or without a header).
+ *  - wav_header != 0 with a non-S16LE encoding: the 58-byte non-PCM form, little-endian —
+ *      "RIFF" u32 50 + data + pad  "WAVE"
+ *      "fmt " u32 18  u16 tag (7 mu-law, 6 A-law, 3 IEEE float)  u16 1  u32 rate  u32 rate * bytes_per_sample
+ *             u16 bytes_per_sample  u16 8 * bytes_per_sample  u16 0
+ *      "fact" u32 4  u32 total_samples
+ *      "data" u32 data
+ *    for F32LE byte for byte what scipy.io.wavfile.write(f, rate, float32_mono) writes.  pad = one zero byte behind the data
+ *    when data is odd (G.711 only): the RIFF size field and n_bytes count it, the data size field does not.
+ *  - Size limits, checked before anything is sized or launched, with messages that name the entry or the limit:
+ *    total_samples <= 2^31 - 1 as before; with a header the RIFF limit follows from the encoding (F32LE: 50 + 4 * total_samples
+ *    <= 2^32 - 1).
+ *  - No additional stream synchronisation or host round trip; the copy from the device is exactly bytes_per_sample *
+ *    total_samples bytes. */
+#define MI355VITS_ENC_S16LE 0   /* default: the int16 stream, bit for bit */
+#define MI355VITS_ENC_ULAW  1   /* G.711 mu-law, 1 byte per sample */
+#define MI355VITS_ENC_ALAW  2   /* G.711 A-law,  1 byte per sample */
+#define MI355VITS_ENC_F32LE 3   /* the float waveform itself, 4 bytes per sample */
+int mi355vits_set_output_encoding(mi355vits_handle h, int enc);
+int mi355vits_get_output_encoding(mi355vits_handle h);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

@@ -60,6 +60,9 @@ int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int 
  * the engine would refuse. */
 int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* x, const int32_t* lengths, int32_t in_hz,
                             int32_t out_hz, int64_t y_stride, float* y, int32_t* y_lengths, float* peaks);
+/* Kernel unit-test hook: the G.711 encoders of the encoded packed streams (mi355vits_set_output_encoding) over an array on the
+ * current device.  law = MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW; out[i] = the code of in[i].  65,536 inputs cover the function. */
+int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);
 /* Kernel micro-benchmark hook (tools/convbench.py): times `reps` launches of one MFMA Conv1d on random device data.
  * epi: 0 = standard epilogue (bias + residual), 1 = WaveNet gate (Cout = 2*H), 2 = res/skip.  (The tile-shape overrides
  * MI355VITS_CONV_CFG / MI355VITS_CONV_CHUNK exist in the lab build of the library only, csrc/hipx.h lab_getenv.) */

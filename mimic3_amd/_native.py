@@ -36,11 +36,13 @@ EXPORTED_SYMBOLS = (
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
     "mi355vits_set_output_rate", "mi355vits_get_output_rate",
+    "mi355vits_set_output_encoding", "mi355vits_get_output_encoding",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
+    "mi355vits_lab_g711_encode",
 )
 
 
@@ -115,6 +117,20 @@ class PackedResult(ctypes.Structure):
 
 
 WAV_HEADER_BYTES = 44
+WAV_HEADER_BYTES_NON_PCM = 58  # fmt 18 + fact: the header of a packed stream in any encoding but s16le
+# mi355vits_set_output_encoding: name -> (MI355VITS_ENC_*, numpy dtype of a sample)
+ENCODINGS = {"s16le": (0, "<i2"), "ulaw": (1, "u1"), "alaw": (2, "u1"), "f32le": (3, "<f4")}
+_ENCODING_NAMES = {v[0]: k for k, v in ENCODINGS.items()}
+
+
+def encoding_id(encoding) -> int:
+    """``"s16le"`` / ``"ulaw"`` / ``"alaw"`` / ``"f32le"`` (or the MI355VITS_ENC_* value itself) -> MI355VITS_ENC_*; an unknown
+    name raises ``ValueError``, an unknown number is left to the library to refuse."""
+    if isinstance(encoding, str):
+        if encoding.lower() not in ENCODINGS:
+            raise ValueError(f"unknown output encoding {encoding!r} (one of {', '.join(ENCODINGS)})")
+        return ENCODINGS[encoding.lower()][0]
+    return int(encoding)
 
 
 class ConvTest(ctypes.Structure):
@@ -161,6 +177,8 @@ class NativeLibrary:
         L.mi355vits_set_output_rate.argtypes = [H, ctypes.c_int32]
         L.mi355vits_get_output_rate.argtypes = [H]
         L.mi355vits_get_output_rate.restype = ctypes.c_int32
+        L.mi355vits_set_output_encoding.argtypes = [H, ctypes.c_int]
+        L.mi355vits_get_output_encoding.argtypes = [H]
         L.mi355vits_destroy.argtypes = [H]
         L.mi355vits_destroy.restype = None
         L.mi355vits_get_config.argtypes = [H, ctypes.POINTER(CVitsConfig)]
@@ -210,6 +228,7 @@ class NativeLibrary:
                                                   ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
                                                   ctypes.POINTER(ctypes.c_float)]
+            L.mi355vits_lab_g711_encode.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_long, ctypes.POINTER(ctypes.c_uint8)]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
 
@@ -228,6 +247,17 @@ class NativeLibrary:
         return (self.lib.mi355vits_last_error(None) or b"").decode("utf-8", "replace")
 
     # ---- kernel unit-test hooks -------------------------------------------------------------
+    def lab_g711_encode(self, law, samples) -> np.ndarray:
+        """The device's G.711 encoders (the ones of the encoded packed streams) over int16 ``samples``; law "ulaw" / "alaw"."""
+        self._need_hooks()
+        x = np.ascontiguousarray(samples, np.int16).reshape(-1)
+        out = np.empty(x.shape[0], np.uint8)
+        rc = self.lib.mi355vits_lab_g711_encode(encoding_id(law), x.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), x.shape[0],
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out
+
     def test_conv1d(self, x, w, bias=None, res=None, dilation=1, impl=1, in_len=None, out_len=None, in_slope=1.0,
                     relu=False, out_scale=1.0, res_sub=False, accumulate_into=None, device=0) -> np.ndarray:
         self._need_hooks()
@@ -422,15 +452,24 @@ class _PackedHolder:
 
 class PackedAudio:
     """A batch's audio as one contiguous stream (``mi355vits_run_packed``).  Everything is a view of ONE pinned block that goes
-    back to the library when the last view is gone: ``pcm`` int16 [total_samples] (silences included), ``rows[i]`` =
-    ``pcm[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
-    when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry."""
+    back to the library when the last view is gone: ``data`` [total_samples] (silences included) in the stream's ``encoding`` —
+    int16 ("s16le"), uint8 G.711 codes ("ulaw" / "alaw") or float32 ("f32le") —, ``rows[i]`` =
+    ``data[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
+    when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry, in samples.  ``pcm`` is ``data`` of an
+    int16 stream, and raises for any other encoding."""
 
-    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None):
-        self.pcm, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
+    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le"):
+        self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
+        self.encoding = encoding
         self.sample_rate = sample_rate  # of every sample of the stream: the rate the run ran at
         self.total_samples = int(pcm.shape[0])
         self.rows = [pcm[int(o): int(o) + int(n)] for o, n in zip(offsets, lengths)]
+
+    @property
+    def pcm(self):
+        if self.encoding != "s16le":
+            raise ValueError(f"this packed stream is {self.encoding}, not int16 PCM: read .data")
+        return self.data
 
 
 class Engine:
@@ -594,7 +633,8 @@ class Engine:
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
                    debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> PackedAudio:
-        """One synthesis call whose result is ONE contiguous int16 stream (``mi355vits_run_packed``): entry i = the valid samples
+        """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
+        ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
         the last entry, with ``wav`` a 44-byte RIFF header in front.  Each entry is bitwise that row of
         ``run(..., want_pcm16=True)`` for the same arguments; one kernel, one device-to-host copy of exactly that many bytes."""
@@ -604,13 +644,14 @@ class Engine:
         p, pkeep = self._pack_args(order, lead_samples, tail_samples, wav)
         if p is not None and p.n < 0:
             p.n = a.batch
+        enc = self.output_encoding  # read by the library when the call starts; only this thread sets it meanwhile
         r = PackedResult()
         self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                          None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del keep, pkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate
-        return self._take_packed(r, bool(wav))
+        return self._take_packed(r, bool(wav), enc)
 
     def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
         """Pack the last completed run of this handle again (``mi355vits_fetch_packed``): that run's rows and per-row volumes,
@@ -618,26 +659,40 @@ class Engine:
         p, pkeep = self._pack_args(order, lead_samples, tail_samples, wav)
         if p is not None and p.n < 0:
             p.n = self._last_batch  # every row of the last run (0 before the first: the library names the error)
+        enc = self.output_encoding
         r = PackedResult()
         self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del pkeep
-        return self._take_packed(r, bool(wav))
+        return self._take_packed(r, bool(wav), enc)
 
-    def _take_packed(self, r: PackedResult, wav: bool) -> PackedAudio:
+    def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le") -> PackedAudio:
         n = int(r.n)
         try:
             offsets = np.ctypeslib.as_array(r.offsets, shape=(n,)).copy()
             lens = np.ctypeslib.as_array(r.lengths, shape=(n,)).copy()
             peaks = np.ctypeslib.as_array(r.peaks, shape=(n,)).copy()
-            hdr = WAV_HEADER_BYTES if wav else 0
-            if int(r.n_bytes) != hdr + 2 * int(r.total_samples):
+            dtype = np.dtype(ENCODINGS[enc][1])
+            hdr = (WAV_HEADER_BYTES if enc == "s16le" else WAV_HEADER_BYTES_NON_PCM) if wav else 0
+            data = dtype.itemsize * int(r.total_samples)
+            if int(r.n_bytes) != hdr + data + (data & 1 if wav else 0):  # a WAV's odd data size is followed by one pad byte
                 raise RuntimeError("mi355vits_packed_result: n_bytes does not match total_samples")
         except BaseException:
             self.native.lib.mi355vits_free_packed(ctypes.byref(r))
             raise
         block = _PackedHolder(self.native, r).view()
-        pcm = block[hdr:].view("<i2")
-        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate)
+        pcm = block[hdr: hdr + data].view(dtype)
+        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc)
+
+    def set_output_encoding(self, encoding) -> None:
+        """The sample encoding of the packed streams made after this (``mi355vits_set_output_encoding``): ``"s16le"`` (the
+        default), ``"ulaw"`` / ``"alaw"`` (G.711, one byte per sample: the codes of ``audioop.lin2ulaw`` / ``lin2alaw`` of the
+        int16 stream) or ``"f32le"`` (the float waveform itself; ``pcm_volume`` does not apply).  Read by ``run_packed`` and by
+        each ``fetch_packed``; ``run`` / ``fetch`` are unchanged by it."""
+        self._check(self.native.lib.mi355vits_set_output_encoding(self._h, encoding_id(encoding)))
+
+    @property
+    def output_encoding(self) -> str:
+        return _ENCODING_NAMES[int(self.native.lib.mi355vits_get_output_encoding(self._h))]
 
     def set_output_rate(self, hz) -> None:
         """The sample rate of every result of the runs that start after this (``mi355vits_set_output_rate``): ``None`` / 0 or

@@ -108,6 +108,17 @@ int32_t mi355vits_get_output_rate(mi355vits_handle h) {
     return h->eng->output_rate();
 }
 
+int mi355vits_set_output_encoding(mi355vits_handle h, int enc) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_output_encoding(enc); });
+}
+int mi355vits_get_output_encoding(mi355vits_handle h) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return h->eng->output_encoding();
+}
+
 int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
     if (!h) return MI355VITS_ERR_INVALID;
     return guarded(h, [&] {

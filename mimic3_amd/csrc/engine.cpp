@@ -394,6 +394,7 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         math_ = lane0.math_;
         sw_ = lane0.sw_;
         if (lane0.out_hz_) set_output_rate(lane0.out_hz_);
+        enc_ = lane0.enc_;
     } catch (...) {
         release();
         throw;
@@ -481,6 +482,15 @@ void Engine::set_output_rate(int hz) {
     d_rs_coef_ = static_cast<float*>(p);
     rs_ = std::move(f);
     out_hz_ = hz;
+}
+
+static_assert(MI355VITS_ENC_S16LE == PACK_ENC_S16 && MI355VITS_ENC_ULAW == PACK_ENC_ULAW && MI355VITS_ENC_ALAW == PACK_ENC_ALAW &&
+                  MI355VITS_ENC_F32LE == PACK_ENC_F32, "the ABI's encoding values are the kernels' own");
+// The sample encoding of the packed streams made after this (read by run_packed / fetch_packed when they plan their pack).
+void Engine::set_output_encoding(int enc) {
+    if (enc != MI355VITS_ENC_S16LE && enc != MI355VITS_ENC_ULAW && enc != MI355VITS_ENC_ALAW && enc != MI355VITS_ENC_F32LE)
+        throw EngineError(MI355VITS_ERR_INVALID, "output encoding " + std::to_string(enc) + " unknown (0 = s16le, 1 = ulaw, 2 = alaw, 3 = f32le)");
+    enc_ = enc;
 }
 
 void Engine::construct(const WeightsFile& wf, int device) {
@@ -1632,13 +1642,17 @@ struct Engine::PackPlan {
     // made by place_pack from the frame counts
     std::vector<int64_t> offsets, lengths;
     int64_t total = 0, audio = 0;
+    // the handle's output encoding when the pack was planned (MI355VITS_ENC_* = PackEncoding)
+    int enc = PACK_ENC_S16;
+    int bps() const { return pack_bytes_per_sample(enc); }
+    size_t header_bytes() const { return !wav ? 0 : enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
 };
 
 // Packed calls only: the segment table and the stream, behind everything layout_b placed — no other pointer moves, so a call
 // that packs nothing runs on the layout it always had.
-template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples) {
+template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples, int enc) {
     d_pack_seg_ = ar.template alloc<int>(3 * n);
-    d_pack_ = ar.template alloc<int16_t>(pcm_pack_capacity((long)samples));
+    d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(enc, (long)samples));  // in bytes, the last store's overrun included
 }
 
 void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
@@ -1798,7 +1812,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
     ArenaCount size_b;
     layout_b(size_b, B, Ty, nz_frames, rs ? Lo_ : 0);
-    if (plan) layout_pack(size_b, plan->n, plan->total);
+    if (plan) layout_pack(size_b, plan->n, plan->total, plan->enc);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
     layout_b(arena_b_, B, Ty, nz_frames, rs ? Lo_ : 0);
@@ -1808,7 +1822,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     o_alen_ = rs ? d_rtab_ : d_alen_;
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
-    if (plan) layout_pack(arena_b_, plan->n, plan->total);
+    if (plan) layout_pack(arena_b_, plan->n, plan->total, plan->enc);
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     // (a packed call's segment table sits right behind d_slen_ in the arena: the same copy brings it)
@@ -1889,13 +1903,20 @@ void Engine::copy_out(uint32_t want, mi355vits_result* out) {
 namespace {
 constexpr int64_t PACK_MAX_SAMPLES = 0x7fffffffLL;                       // total_samples <= 2^31 - 1
 constexpr int64_t RIFF_MAX_SAMPLES = (0xffffffffLL - 36) / 2;            // 36 + 2 * total_samples must fit RIFF's 32-bit size
-constexpr size_t WAV_HEADER_BYTES = 44;
 EngineError pack_error(int entry, const std::string& what) {
     return EngineError(MI355VITS_ERR_INVALID, (entry >= 0 ? "pack entry " + std::to_string(entry) + ": " : std::string("pack: ")) + what);
 }
-void check_pack_size(int entry, int64_t samples, bool wav) {
+void check_pack_size(int entry, int64_t samples, bool wav, int enc) {
     if (samples > PACK_MAX_SAMPLES) throw pack_error(entry, "total_samples exceeds 2^31 - 1");
-    if (wav && samples > RIFF_MAX_SAMPLES) throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (36 + 2 * total_samples > 2^32 - 1)");
+    if (!wav) return;
+    if (enc == PACK_ENC_S16) {
+        if (samples > RIFF_MAX_SAMPLES) throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (36 + 2 * total_samples > 2^32 - 1)");
+        return;
+    }
+    // the 58-byte non-PCM form: RIFF size = 50 + data (+ one pad byte behind an odd data size: G.711 only)
+    const int64_t bps = pack_bytes_per_sample(enc), data = bps * samples;
+    if (50 + data + (data & 1) > 0xffffffffLL)
+        throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (50 + " + std::to_string(bps) + " * total_samples > 2^32 - 1)");
 }
 struct PackedOwner {
     void* bytes = nullptr;
@@ -1911,6 +1932,7 @@ void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) c
     plan.n = pack ? pack->n : B;
     if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
     plan.wav = pack && pack->wav_header != 0;
+    plan.enc = enc_;  // the setting is read here: when a pack is made
     plan.tail = pack ? pack->tail_samples : 0;
     plan.order.resize(plan.n);
     plan.lead.assign(plan.n, 0);
@@ -1924,14 +1946,14 @@ void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) c
         plan.order[i] = row;
         const int64_t lead = (pack && pack->lead_samples) ? pack->lead_samples[i] : 0;
         if (lead < 0) throw pack_error(i, "negative silence (" + std::to_string(lead) + " samples)");
-        check_pack_size(i, lead, plan.wav);
+        check_pack_size(i, lead, plan.wav, plan.enc);
         plan.lead[i] = lead;
         silence += lead;
-        check_pack_size(i, silence, plan.wav);  // the silences alone: no row is synthesised for a stream that cannot exist
+        check_pack_size(i, silence, plan.wav, plan.enc);  // the silences alone: no row is synthesised for a stream that cannot exist
     }
     if (plan.tail < 0) throw pack_error(-1, "negative tail silence (" + std::to_string(plan.tail) + " samples)");
-    check_pack_size(-1, plan.tail, plan.wav);
-    check_pack_size(-1, silence + plan.tail, plan.wav);
+    check_pack_size(-1, plan.tail, plan.wav, plan.enc);
+    check_pack_size(-1, silence + plan.tail, plan.wav, plan.enc);
 }
 
 // Where every entry goes, from the frame counts the host already holds; the size limits with the audio counted in.
@@ -1946,10 +1968,10 @@ void Engine::place_pack(PackPlan& plan) const {
         plan.lengths[i] = h_olen_[plan.order[i]];  // at the run's rate
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
-        check_pack_size(i, pos, plan.wav);
+        check_pack_size(i, pos, plan.wav, plan.enc);
     }
     plan.total = pos + plan.tail;
-    check_pack_size(-1, plan.total, plan.wav);
+    check_pack_size(-1, plan.total, plan.wav, plan.enc);
 }
 
 void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
@@ -1961,8 +1983,14 @@ void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
 }
 
 void Engine::launch_pack(const PackPlan& plan) {
-    ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
-    launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
+    if (plan.enc == PACK_ENC_S16) {
+        ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
+        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_);
+        return;
+    }
+    const char* label = plan.enc == PACK_ENC_ULAW ? "pack.ulaw" : plan.enc == PACK_ENC_ALAW ? "pack.alaw" : "pack.f32";
+    ProfScope ps(prof_, label, 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
+    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
 }
 
 void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
@@ -1978,15 +2006,41 @@ void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out)
     out->lengths = static_cast<int64_t*>(own->lengths);
     out->peaks = static_cast<float*>(own->peaks);
     if (!out->offsets || !out->lengths || !out->peaks) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
-    const size_t hdr = plan.wav ? WAV_HEADER_BYTES : 0, data = 2 * (size_t)plan.total;
-    own->bytes = PinnedPool::get().take(hdr + data + 16, &own->cap);
-    out->bytes = static_cast<uint8_t*>(own->bytes);
-    out->n_bytes = hdr + data;
-    out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);
+    const size_t hdr = plan.header_bytes(), data = (size_t)plan.bps() * (size_t)plan.total;
+    const size_t pad = (plan.wav && (data & 1)) ? 1 : 0;  // RIFF chunks are word-aligned: one zero byte behind an odd data size (G.711 only)
+    const size_t lead = hdr == 58 ? 6 : 0;  // the 58-byte header starts 6 bytes into the block: the data behind it keeps the block's alignment
+    own->bytes = PinnedPool::get().take(lead + hdr + data + pad + 16, &own->cap);
+    out->bytes = static_cast<uint8_t*>(own->bytes) + lead;
+    out->n_bytes = hdr + data + pad;
+    out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);  // the first data byte, whatever the encoding
     std::vector<unsigned> pk(B_);
     HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
-    if (plan.wav) {
+    if (plan.wav && plan.enc != PACK_ENC_S16) {
+        // RIFF/WAVE, the non-PCM form (an 18-byte fmt chunk with cbSize 0, then a fact chunk with the sample count): 58 bytes, what
+        // scipy.io.wavfile.write puts in front of float32 data; format tag 7 = mu-law, 6 = A-law, 3 = IEEE float
+        uint8_t* h = out->bytes;
+        auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
+        auto u16 = [&](size_t at, uint32_t v) { h[at] = (uint8_t)v; h[at + 1] = (uint8_t)(v >> 8); };
+        const uint32_t rate = (uint32_t)run_hz_, bps = (uint32_t)plan.bps();
+        memcpy(h, "RIFF", 4);
+        u32(4, (uint32_t)(50 + data + pad));
+        memcpy(h + 8, "WAVEfmt ", 8);
+        u32(16, 18);
+        u16(20, plan.enc == PACK_ENC_ULAW ? 7 : plan.enc == PACK_ENC_ALAW ? 6 : 3);
+        u16(22, 1);
+        u32(24, rate);
+        u32(28, rate * bps);
+        u16(32, bps);
+        u16(34, 8 * bps);
+        u16(36, 0);
+        memcpy(h + 38, "fact", 4);
+        u32(42, 4);
+        u32(46, (uint32_t)plan.total);
+        memcpy(h + 50, "data", 4);
+        u32(54, (uint32_t)data);
+        if (pad) h[hdr + data] = 0;
+    } else if (plan.wav) {
         // RIFF/WAVE, PCM, mono, 16 bit: the 44 bytes the stdlib `wave` module writes (little-endian fields)
         uint8_t* h = out->bytes;
         auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
@@ -2035,14 +2089,14 @@ void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_resu
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
     ArenaCount need;
-    layout_pack(need, plan.n, plan.total);
+    layout_pack(need, plan.n, plan.total, plan.enc);
     if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
         arena_b_.rewind(layout_b_end_);
-        layout_pack(arena_b_, plan.n, plan.total);
+        layout_pack(arena_b_, plan.n, plan.total, plan.enc);
     } else {
         arena_p_.reserve(need.bytes + 4096, stream_);
         arena_p_.reset();
-        layout_pack(arena_p_, plan.n, plan.total);
+        layout_pack(arena_p_, plan.n, plan.total, plan.enc);
     }
     h_pack_seg_.assign(3 * (size_t)plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
     fill_pack_seg(plan, h_pack_seg_.data());

@@ -175,6 +175,9 @@ class Engine {
     // the rate of every result (mi355vits_set_output_rate): 0 or the voice's own = native.  Read when a run starts.
     void set_output_rate(int hz);
     int output_rate() const { return out_hz_ ? out_hz_ : cfg_.sample_rate; }
+    // the sample encoding of the packed streams (mi355vits_set_output_encoding).  Read when a pack is made.
+    void set_output_encoding(int enc);
+    int output_encoding() const { return enc_; }
     Profiler& profiler() { return prof_; }
     float last_run_ms();
     long get_tap(const std::string& name, float* out, size_t cap, int64_t dims[4], long row0 = 0, long nrows = -1);
@@ -216,7 +219,7 @@ class Engine {
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
-    template <typename A> void layout_pack(A& ar, size_t n, size_t samples);  // continues layout_b in packed calls, and only there
+    template <typename A> void layout_pack(A& ar, size_t n, size_t samples, int enc);  // continues layout_b in packed calls, and only there
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
     // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
@@ -283,6 +286,7 @@ class Engine {
     ResampleFilter rs_;
     float* d_rs_coef_ = nullptr;   // rs_.table (an allocation of its own: it outlives the runs)
     int run_hz_ = 0;               // the rate the last run ran at
+    int enc_ = 0;                  // MI355VITS_ENC_* of the packed streams (mi355vits_set_output_encoding): 0 = int16
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
     int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)
@@ -295,7 +299,7 @@ class Engine {
     // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table [3][n] right behind
     // d_slen_ (one upload brings both) and the stream itself
     int* d_pack_seg_ = nullptr;
-    int16_t* d_pack_ = nullptr;
+    uint8_t* d_pack_ = nullptr;  // pack_capacity_bytes(encoding, total) bytes
     size_t layout_b_end_ = 0;  // arena_b_.used() behind d_slen_: where fetch_packed puts its buffers when there is room
     std::vector<int> h_ylen_;
     std::vector<unsigned char> h_in_;  // the call's host inputs, laid out like their device block (one upload)

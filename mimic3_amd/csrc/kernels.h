@@ -215,6 +215,20 @@ constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes
 inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
                        int16_t* out, long total, hipStream_t s);
+// The packed stream in another sample encoding (mi355vits_set_output_encoding; kernels_pack.cpp): the same table, the same
+// destination-major walk, one 16-byte store per lane.  PACK_ENC_ULAW / _ALAW: byte k = the G.711 code of the int16 sample
+// k_pcm16_pack stores there, every other byte the code of sample 0 (0xFF / 0xD5); a lane owns 16 samples.  PACK_ENC_F32: the
+// rows' float samples themselves (no normalisation, no volume: peak_bits / volumes are not read), 0.0f elsewhere; a lane owns 4.
+// out is 16-byte aligned and holds pack_capacity_bytes(enc, total) bytes; byte offsets are 64-bit.
+enum PackEncoding { PACK_ENC_S16 = 0, PACK_ENC_ULAW = 1, PACK_ENC_ALAW = 2, PACK_ENC_F32 = 3 };
+inline int pack_bytes_per_sample(int enc) { return enc == PACK_ENC_S16 ? 2 : enc == PACK_ENC_F32 ? 4 : 1; }
+inline size_t pack_capacity_bytes(int enc, long total) {
+    return enc == PACK_ENC_S16 ? 2 * pcm_pack_capacity(total) : ((size_t)total * pack_bytes_per_sample(enc) + 15) & ~size_t(15);
+}
+void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
+                         int n, uint8_t* out, long total, hipStream_t s);
+// G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
+void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 
 // ---------------------------------------------------------------- output at a requested sample rate (kernels_resample.cpp)
 // y[k] = sum_j h[k M - j L + half] x[j], x zero outside [0, n): what scipy.signal.resample_poly(x, L, M) returns with its default

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "pcm_quant.h"
 #include <atomic>
 #include <type_traits>
 #include "b3.h"
@@ -2329,19 +2330,7 @@ void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, 
 // samples of it and writes them with ONE 16-byte store, whatever the (odd) offsets of the rows inside the stream; a persistent
 // grid deals the chunks out in consecutive runs.  Every sample of [0, capacity) has exactly one writer: no atomics, and the silences are zeros
 // because this kernel stores them (the workspace is never assumed clean).
-// One valid sample, operation for operation what k_pcm16 does to it (audio_float_to_int16, then audioop.mul):
-__device__ __forceinline__ int pcm16_quant(float a, float scale, double volume) {
-    float v = a * scale;
-    v = fminf(fmaxf(v, -32767.0f), 32767.0f);
-    int q = (int)v;
-    if (volume != 1.0) {
-        double d = (double)q * volume;
-        if (d > 32767.0) d = 32767.0;
-        else if (d < -32768.0 + 1.0) d = -32768.0;
-        q = (int)floor(d);
-    }
-    return q;
-}
+// One valid sample, operation for operation what k_pcm16 does to it (audio_float_to_int16, then audioop.mul): pcm16_quant, pcm_quant.h
 __device__ __forceinline__ unsigned pcm16_pair(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
 
 __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,

@@ -138,6 +138,19 @@ int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* 
     });
 }
 
+int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out) {
+    return guarded(nullptr, [&] {
+        if (!in || !out || n < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        if (law != MI355VITS_ENC_ULAW && law != MI355VITS_ENC_ALAW) throw EngineError(MI355VITS_ERR_INVALID, "law must be MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW");
+        DevBuf di((size_t)n * 2), dout((size_t)n);
+        HIP_CHECK(hipMemcpy(di.p, in, (size_t)n * 2, hipMemcpyHostToDevice));
+        launch_g711_encode(law, di.as<int16_t>(), n, dout.as<uint8_t>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern) {
     if (!h) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);

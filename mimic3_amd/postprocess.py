@@ -35,8 +35,46 @@ def silence(ms: Union[int, float], sample_rate: int = 22050) -> np.ndarray:
     return np.zeros(int((ms / 1000.0) * sample_rate), dtype=np.int16)
 
 
-def wav_bytes(chunks: Iterable[np.ndarray], sample_rate: int = 22050) -> bytes:
-    """One RIFF/WAVE file (PCM 16-bit mono) around the concatenated chunks — what ``text_to_wav`` returns."""
+def lin2ulaw(pcm: np.ndarray) -> np.ndarray:
+    """``audioop.lin2ulaw(pcm.tobytes(), 2)`` as a uint8 array (G.711 mu-law; CPython ``Modules/audioop.c``,
+    ``st_14linear2ulaw``), for callers that already hold int16 PCM — the arithmetic of the engine's "ulaw" packed stream."""
+    v = np.asarray(pcm, dtype=np.int16).astype(np.int32) >> 2
+    mask = np.where(v < 0, 0x7F, 0xFF)
+    m = np.minimum(np.abs(v), 8159) + 33  # 33 .. 8192
+    seg = np.searchsorted(np.array([0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF]), m, side="left")  # first end >= m; 8: none
+    code = np.where(seg >= 8, 0x7F, (seg << 4) | ((m >> (seg + 1)) & 15))
+    return (code ^ mask).astype(np.uint8)
+
+
+def lin2alaw(pcm: np.ndarray) -> np.ndarray:
+    """``audioop.lin2alaw(pcm.tobytes(), 2)`` as a uint8 array (G.711 A-law; ``st_linear2alaw``)."""
+    v = np.asarray(pcm, dtype=np.int16).astype(np.int32) >> 3
+    mask = np.where(v >= 0, 0xD5, 0x55)
+    m = np.where(v >= 0, v, -v - 1)  # 0 .. 4095
+    seg = np.searchsorted(np.array([0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF]), m, side="left")
+    code = (seg << 4) | ((m >> np.where(seg < 2, 1, seg)) & 15)
+    return (code ^ mask).astype(np.uint8)
+
+
+# encoding -> (numpy dtype of a sample, WAVE format tag)
+_WAV_FORMATS = {"s16le": ("<i2", 1), "ulaw": ("u1", 7), "alaw": ("u1", 6), "f32le": ("<f4", 3)}
+
+
+def wav_bytes(chunks: Iterable[np.ndarray], sample_rate: int = 22050, encoding: str = "s16le") -> bytes:
+    """One RIFF/WAVE file (mono) around the concatenated chunks — with the default ``encoding`` PCM 16-bit: what ``text_to_wav``
+    returns.  ``"ulaw"`` / ``"alaw"`` (chunks hold G.711 codes, uint8) and ``"f32le"`` (float32 samples) take the 58-byte
+    non-PCM header (18-byte ``fmt``, ``fact`` with the sample count) and a pad byte behind an odd data size: the file
+    ``run_packed(..., wav=True, encoding=...)`` returns, and for float32 the one ``scipy.io.wavfile.write`` writes."""
+    if encoding not in _WAV_FORMATS:
+        raise ValueError(f"unknown output encoding {encoding!r} (one of {', '.join(_WAV_FORMATS)})")
+    dtype, tag = _WAV_FORMATS[encoding]
+    if encoding != "s16le":
+        data = b"".join(np.ascontiguousarray(c, dtype=dtype).tobytes() for c in chunks)
+        bps = np.dtype(dtype).itemsize
+        pad = b"\0" * (len(data) & 1)
+        hdr = b"RIFF" + struct.pack("<I", 50 + len(data) + len(pad)) + b"WAVE" + b"fmt " + struct.pack(
+            "<IHHIIHHH", 18, tag, 1, sample_rate, sample_rate * bps, bps, 8 * bps, 0) + b"fact" + struct.pack("<II", 4, len(data) // bps)
+        return hdr + b"data" + struct.pack("<I", len(data)) + data + pad
     data = b"".join(np.ascontiguousarray(c, dtype="<i2").tobytes() for c in chunks)
     hdr = b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate,
                                                                                          sample_rate * 2, 2, 16)
@@ -60,8 +98,9 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     ``utterances_to_wav`` over per-sentence ``run_pcm16`` calls, with no host pass over the audio.
 
     ``settings``: ``scales`` ([3] or [B, 3]; default the reference's 0.667 / 1.0 / 0.8), ``sid`` (multi-speaker voices), and
-    ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` as ``run_packed`` takes them (with ``sample_rate`` the file is
-    at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it)."""
+    ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` / ``encoding`` as ``run_packed`` takes them (with
+    ``sample_rate`` the file is at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it; with
+    ``encoding="ulaw"`` and ``sample_rate=8000`` it is the G.711 file a telephony stack plays)."""
     rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]
     if not rows or any(r.size == 0 for r in rows):
         raise ValueError("request_wav needs at least one sentence, each with at least one phoneme id")

@@ -477,6 +477,13 @@ class _MicroBatcher:
             self._thread.join(timeout=5.0)
 
 
+def _encoding_name(encoding) -> str:
+    """A packed stream's sample encoding as its lower-case name; ``ValueError`` for anything else."""
+    if not isinstance(encoding, str) or encoding.lower() not in _native.ENCODINGS:
+        raise ValueError(f"unknown output encoding {encoding!r} (one of {', '.join(_native.ENCODINGS)})")
+    return encoding.lower()
+
+
 class InferenceSession:
     """Drop-in for the object stored in ``Mimic3Voice.onnx_model``."""
 
@@ -491,6 +498,8 @@ class InferenceSession:
         # the rate of every result (Engine.set_output_rate): None = the voice's own; a call's ``sample_rate=`` goes before it
         rate = kwargs.pop("output_sample_rate", None)
         self.output_sample_rate: Optional[int] = int(rate) if rate else None
+        # the sample encoding of the packed streams (Engine.set_output_encoding); a call's ``encoding=`` goes before it
+        self.output_encoding: str = _encoding_name(kwargs.pop("output_encoding", None) or "s16le")
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -588,8 +597,10 @@ class InferenceSession:
         return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
-                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None) -> "_native.PackedAudio":
-        """The batch's finished audio as ONE contiguous int16 stream (``mi355vits_run_packed``): only the valid
+                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None) -> "_native.PackedAudio":
+        """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
+        ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
+        the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
         samples of each row, rows in the order ``order`` names (default: all, in order), ``lead_ms[i]`` / ``lead_samples[i]`` of
         silence in front of entry i (``add_break``, ``tts.py:452-465``: ``int(ms / 1000 * sample_rate)`` zero samples at the
         rate of the stream: ``sample_rate``, else the session's ``output_sample_rate``, else the voice's), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
@@ -599,6 +610,7 @@ class InferenceSession:
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
+        kw["encoding"] = _encoding_name(encoding) if encoding is not None else self.output_encoding
         rate = int(sample_rate or self.output_sample_rate or self.config.sample_rate)
         if lead_ms is not None:
             if lead_samples is not None:
@@ -669,7 +681,7 @@ class InferenceSession:
             self._utterances += int(n)
         return base
 
-    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, **kw):
+    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None, **kw):
         if self._closed:
             raise RuntimeError("session is closed")
         keys = None if utterance_keys is None else list(utterance_keys)
@@ -682,6 +694,8 @@ class InferenceSession:
         try:
             # the call owns the lane: its rate is set here and read by the engine when the run starts
             eng.set_output_rate(sample_rate if sample_rate is not None else self.output_sample_rate)
+            if _packed:  # the encoding concerns packed streams only; read by the engine when the pack is planned
+                eng.set_output_encoding(encoding or self.output_encoding)
             call = eng.run_packed if _packed else eng.run
             return call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
         except _native.NativeError as e:

@@ -2,6 +2,11 @@
 
     python tools/ab_prev.py bits  PREV.so NEW.so          # the same ragged batch through both: waveforms, lengths, PCM compared bitwise
     python tools/ab_prev.py bench PREV.so NEW.so [--batch 256 --steps 20 --rounds 2]
+    python tools/ab_prev.py digest [--root TREE]          # sha256 of a tree's own results: `bits` across an ABI change
+
+`bits` opens both files with THIS tree's binding, so PREV must export every entry point the binding knows.  When the ABI has grown
+since PREV, run `digest` once in each tree (or with --root on a checkout that holds its built library) and compare the lines: the
+ragged batch of `bits`, and the headline shape (256 rows x 128 ids x 6 forced frames) as padded int16 and as the default packed stream.
 
 `bench` swaps the file bench.py opens (mimic3_amd/csrc/libmi355vits.so) — the product reads no library switch — and always puts NEW
 back at the end.  Output: one line per run with ms/step and the kernel table rows named in --rows.
@@ -44,16 +49,55 @@ def run_bits(lib_path, math=None):
     return out
 
 
+def run_digest(root):
+    """One line per result of the tree at `root`, through that tree's own package and product library."""
+    import hashlib
+
+    sys.path.insert(0, root)
+    import numpy as np
+
+    from mimic3_amd import weights as W
+    from mimic3_amd._native import Engine
+    from mimic3_amd.config import VitsConfig
+
+    def sha(*arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        return h.hexdigest()[:32]
+
+    for voice, (audio, lengths, pcm) in run_bits(os.path.join(root, "mimic3_amd", "csrc", "libmi355vits.so")).items():
+        print(f"digest ragged {voice}: audio {sha(audio)} lengths {sha(lengths)} pcm {sha(pcm)}")
+    cfg = VitsConfig.apope_low()
+    eng = Engine(W.pack(cfg, W.synthetic_weights(cfg, seed=7, frames_per_id=3.0)), device=0)
+    B, Tx = 256, 128
+    ids = np.random.default_rng(1).integers(1, cfg.num_symbols, (B, Tx))
+    lens, forced = np.full(B, Tx, np.int64), np.full((B, Tx), 6, np.int32)
+    r = eng.run(ids, lens, [0.667, 1.0, 0.8], forced_durations=forced, seed=1, want_float=True, want_pcm16=True)
+    print(f"digest headline padded: audio {sha(r['audio'])} lengths {sha(r['lengths'])} pcm {sha(r['pcm'])} peaks {sha(r['peaks'])}")
+    del r
+    pk = eng.run_packed(ids, lens, [0.667, 1.0, 0.8], forced_durations=forced, seed=1, lead_samples=[7] * B, tail_samples=11, wav=True,
+                        pcm_volume=np.linspace(0.5, 3.0, B))
+    print(f"digest headline packed wav: bytes {sha(np.frombuffer(bytes(pk.wav), np.uint8))} offsets {sha(pk.offsets)} peaks {sha(pk.peaks)}")
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["bits", "bench"])
-    ap.add_argument("prev")
-    ap.add_argument("new")
+    ap.add_argument("mode", choices=["bits", "bench", "digest"])
+    ap.add_argument("prev", nargs="?")
+    ap.add_argument("new", nargs="?")
+    ap.add_argument("--root", default=ROOT)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--rows", default="flow.wn_layer_b3,dec.mrf_p.s2,dec.mrf_s.s1,dec.rb.s0,enc.ffn1,enc.ffn2,dec.conv_pre")
     a = ap.parse_args()
+    if a.mode == "digest":
+        run_digest(os.path.abspath(a.root))
+        return
+    if not a.prev or not a.new:
+        ap.error("bits / bench need PREV.so and NEW.so")
     if a.mode == "bits":
         import numpy as np
 
