@@ -312,6 +312,53 @@ void mi355vits_free_packed(mi355vits_packed_result* r);
 int mi355vits_set_output_encoding(mi355vits_handle h, int enc);
 int mi355vits_get_output_encoding(mi355vits_handle h);
 
+/* ---- Phoneme timing and levels: WHERE in a run's audio each phoneme sits, and how loud it is there.  What speech marks for
+ * captions, visemes and lip-sync, a position for the reference's SSML <mark> (MarkResult carries a name and no time:
+ * opentts_abc/__init__.py:131-139, mimic3_tts/tts.py:467-468), cutting a stream at word boundaries and duration editing
+ * (forced_durations is the matching INPUT) need.  The reference cannot give it: onnx_model.run returns the waveform only.
+ * mi355vits_fetch_alignment serves the LAST COMPLETED RUN of the handle whatever its flags were (padded, MI355VITS_DEVICE_ONLY or
+ * packed), at the rate it ran at, as mi355vits_fetch does.  One kernel (k_align) makes every array on the GPU.
+ *   frames[b,t]   latent frames of phoneme t: the run's ceil(exp(logw) * length_scale), or its forced_durations value.
+ *   start[b,t] = ceil(hop * c[t-1] * L / M),  samples[b,t] = ceil(hop * c[t] * L / M) - start[b,t],  c[t] = frames[b,0] + .. +
+ *                 frames[b,t], c[-1] = 0, hop = config.hop_length, L / M = the run's reduced rate ratio (1 / 1 in a native run),
+ *                 in exact 64-bit integers: start is the first sample of the row, at the run's rate, whose time is not before the
+ *                 phoneme's native start (k_resample has zero delay: output sample k sits at native time k M / L).
+ *  - start[b,0] = 0; the spans are disjoint, ordered and tile the row: start[b,t+1] = start[b,t] + samples[b,t], and their sum is
+ *    lengths[b] of the run exactly (ceil(n L / M) is the resampler's length rule).  A phoneme of zero frames has samples = 0 and
+ *    the next phoneme's start.
+ *  - Positions t >= input_lengths[b]: frames = samples = 0, start = the end of the covered part, peak = rms = 0.
+ *  - The one exception: a row whose durations sum to 0 still yields one frame of audio (the frame count is max(1, sum)), so it has
+ *    all-zero spans and lengths[b] = ceil(hop L / M) > 0.
+ *  - MI355VITS_ALIGN_LEVELS in `want`: peak / rms over the span of the run's float waveform at its output rate — the
+ *    MI355VITS_WANT_FLOAT samples: before the int16 normalisation, pcm_volume does not apply.  peak = max |y|,
+ *    rms = (float) sqrt(sum((double) y * y) / samples), both 0 for an empty span; double accumulation in one fixed order per
+ *    phoneme, so a row of a batch is bitwise the row alone, and for every row with at least one frame max_t peak[b,t] is bitwise
+ *    peaks[b] of the run.  Without the flag peak and rms are NULL and no kernel reads the audio.
+ *  - sample_rate = the rate that run ran at: start / samples count these samples.  In a packed stream phoneme t of entry i is
+ *    pcm[offsets[i] + start[order[i],t] ..) in any encoding (offsets are in samples).
+ *  - One stream synchronisation and one device-to-host copy per call; the arrays are one pinned block, released by
+ *    mi355vits_free_alignment.  The call works in an arena of its own: what mi355vits_fetch / _fetch_packed / _device_result
+ *    serve afterwards is what they served before.  Serialised per handle like every other call.
+ *  - Errors: before any completed run MI355VITS_ERR_INVALID with "fetch_alignment: no completed run on this handle" (a failed run
+ *    leaves the previous run served, or none, exactly as for mi355vits_fetch); a NULL out or unknown bits in want:
+ *    MI355VITS_ERR_INVALID.
+ *  - With profiling enabled the launch is reported as "align": bytes = 12 * B * tx_max, with levels 4 * sum(lengths) + 20 * B * tx_max. */
+#define MI355VITS_ALIGN_LEVELS 1u   /* also peak and rms per phoneme (one pass over the valid samples) */
+
+typedef struct mi355vits_alignment {
+    int32_t batch, tx_max;   /* of the run served */
+    int32_t sample_rate;     /* the rate that run ran at: start / samples count these samples */
+    int32_t* frames;         /* [B, tx_max] latent frames of phoneme t: the run's w_ceil */
+    int32_t* start;          /* [B, tx_max] first sample of phoneme t within its row */
+    int32_t* samples;        /* [B, tx_max] samples of phoneme t */
+    float* peak;             /* [B, tx_max] or NULL: max |y| over the span */
+    float* rms;              /* [B, tx_max] or NULL: sqrt(mean y^2) over the span */
+    void* owner_;            /* private */
+} mi355vits_alignment;
+
+int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out);
+void mi355vits_free_alignment(mi355vits_alignment* r);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

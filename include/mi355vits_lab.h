@@ -60,6 +60,15 @@ int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int 
  * the engine would refuse. */
 int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* x, const int32_t* lengths, int32_t in_hz,
                             int32_t out_hz, int64_t y_stride, float* y, int32_t* y_lengths, float* peaks);
+/* Kernel unit-test hook: the product's alignment launch (k_align, mi355vits_fetch_alignment) alone on host buffers.  frames [B, T]
+ * (read at t < len[b] only; 0 <= frames, a row's sum within the duration cap), len [B] (0 <= len[b] <= T) phonemes of a row,
+ * audio [B] rows of row_stride floats with alen [B] (0 <= alen[b] <= row_stride) valid samples each: what lies past them is never
+ * looked at (a span's levels stop at alen[b]).  hop samples per frame, L / M the rate ratio (1 <= L, M <= 640).  Writes
+ * out_frames / out_start / out_samples [B, T] and, when both are given, out_peak / out_rms [B, T]; with both NULL the timing-only
+ * form of the kernel runs and the audio is not read. */
+int mi355vits_test_alignment(int device, int B, int T, const int32_t* frames, const int32_t* len, int64_t row_stride, const float* audio,
+                             const int32_t* alen, int32_t hop, int32_t L, int32_t M, int32_t* out_frames, int32_t* out_start,
+                             int32_t* out_samples, float* out_peak, float* out_rms);
 /* Kernel unit-test hook: the G.711 encoders of the encoded packed streams (mi355vits_set_output_encoding) over an array on the
  * current device.  law = MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW; out[i] = the code of in[i].  65,536 inputs cover the function. */
 int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);

@@ -37,12 +37,13 @@ EXPORTED_SYMBOLS = (
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
     "mi355vits_set_output_rate", "mi355vits_get_output_rate",
     "mi355vits_set_output_encoding", "mi355vits_get_output_encoding",
+    "mi355vits_fetch_alignment", "mi355vits_free_alignment",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
-    "mi355vits_lab_g711_encode",
+    "mi355vits_lab_g711_encode", "mi355vits_test_alignment",
 )
 
 
@@ -114,6 +115,34 @@ class PackedResult(ctypes.Structure):
         ("peaks", ctypes.POINTER(ctypes.c_float)),
         ("owner_", ctypes.c_void_p),
     ]
+
+
+class AlignmentResult(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("tx_max", ctypes.c_int32),
+        ("sample_rate", ctypes.c_int32),
+        ("frames", ctypes.POINTER(ctypes.c_int32)),
+        ("start", ctypes.POINTER(ctypes.c_int32)),
+        ("samples", ctypes.POINTER(ctypes.c_int32)),
+        ("peak", ctypes.POINTER(ctypes.c_float)),
+        ("rms", ctypes.POINTER(ctypes.c_float)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+ALIGN_LEVELS = 1
+
+
+class Alignment:
+    """Where in a run's audio each phoneme sits (``mi355vits_fetch_alignment``): ``frames`` / ``start`` / ``samples`` [B, Tx]
+    integer arrays — phoneme t of row b is samples ``start[b, t] : start[b, t] + samples[b, t]`` of that row at ``sample_rate``,
+    the rate the run ran at; the spans tile the row — and with levels ``peak`` / ``rms`` [B, Tx] float32 over each span of the
+    float waveform (else ``None``).  All arrays are copies owned by Python."""
+
+    def __init__(self, frames, start, samples, peak=None, rms=None, sample_rate=None):
+        self.frames, self.start, self.samples, self.peak, self.rms = frames, start, samples, peak, rms
+        self.sample_rate = sample_rate
 
 
 WAV_HEADER_BYTES = 44
@@ -192,6 +221,9 @@ class NativeLibrary:
         L.mi355vits_fetch_packed.argtypes = [H, ctypes.POINTER(PackArgs), ctypes.POINTER(PackedResult)]
         L.mi355vits_free_packed.argtypes = [ctypes.POINTER(PackedResult)]
         L.mi355vits_free_packed.restype = None
+        L.mi355vits_fetch_alignment.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(AlignmentResult)]
+        L.mi355vits_free_alignment.argtypes = [ctypes.POINTER(AlignmentResult)]
+        L.mi355vits_free_alignment.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -229,6 +261,9 @@ class NativeLibrary:
                                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
                                                   ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_lab_g711_encode.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_long, ctypes.POINTER(ctypes.c_uint8)]
+            i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+            L.mi355vits_test_alignment.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int64, f32p, i32p,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
 
@@ -351,6 +386,28 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return y, yl, pk
 
+    def test_alignment(self, frames, lengths, audio, alen, hop: int, L: int = 1, M: int = 1, levels: bool = True, device=0) -> Alignment:
+        """The product's alignment launch (k_align) alone on caller-given arrays: frames [B, T] int32 (read below lengths[b]
+        only), lengths [B] phonemes of a row, audio [B, row_stride] f32 with alen [B] valid samples each (what lies past them is
+        never looked at), hop samples per frame, L / M the rate ratio -> ``Alignment`` (``sample_rate`` None)."""
+        self._need_hooks()
+        fr = np.ascontiguousarray(frames, np.int32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        au = np.ascontiguousarray(audio, np.float32)
+        al = np.ascontiguousarray(alen, np.int32).reshape(-1)
+        B, T = fr.shape
+        if au.ndim != 2 or au.shape[0] != B or ln.shape[0] != B or al.shape[0] != B:
+            raise ValueError("frames [B, T], lengths [B], audio [B, row_stride], alen [B]")
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        o = [np.zeros((B, T), np.int32) for _ in range(3)]
+        lv = [np.zeros((B, T), np.float32) for _ in range(2)] if levels else [None, None]
+        rc = self.lib.mi355vits_test_alignment(device, B, T, fr.ctypes.data_as(i32p), ln.ctypes.data_as(i32p), au.shape[1], _fptr(au),
+                                               al.ctypes.data_as(i32p), int(hop), int(L), int(M), o[0].ctypes.data_as(i32p),
+                                               o[1].ctypes.data_as(i32p), o[2].ctypes.data_as(i32p), _fptr(lv[0]), _fptr(lv[1]))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return Alignment(o[0], o[1], o[2], lv[0], lv[1], None)
+
     def bench_conv1d(self, B, Cin, Cout, T, K, dilation=1, epi=0, reps=20, device=0) -> float:
         self._need_hooks()
         ms = ctypes.c_float(-1.0)
@@ -459,6 +516,7 @@ class PackedAudio:
     int16 stream, and raises for any other encoding."""
 
     def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le"):
+        self.alignment: Optional[Alignment] = None  # set by InferenceSession.run_packed(alignment=...): spans in stream samples
         self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
         self.encoding = encoding
         self.sample_rate = sample_rate  # of every sample of the stream: the rate the run ran at
@@ -745,6 +803,18 @@ class Engine:
         flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0)
         self._check(self.native.lib.mi355vits_fetch(self._h, flags, ctypes.byref(r)))
         return self._take(r)
+
+    def fetch_alignment(self, levels: bool = False) -> Alignment:
+        """Phoneme timing of the last completed run of this handle (``mi355vits_fetch_alignment``), whatever its flags were, at
+        the rate it ran at; ``levels``: also peak and rms of each phoneme's span of the float waveform."""
+        r = AlignmentResult()
+        self._check(self.native.lib.mi355vits_fetch_alignment(self._h, ALIGN_LEVELS if levels else 0, ctypes.byref(r)))
+        try:
+            shape = (int(r.batch), int(r.tx_max))
+            take = lambda p: np.ctypeslib.as_array(p, shape=shape).copy() if p else None  # noqa: E731
+            return Alignment(take(r.frames), take(r.start), take(r.samples), take(r.peak), take(r.rms), int(r.sample_rate))
+        finally:
+            self.native.lib.mi355vits_free_alignment(ctypes.byref(r))
 
     def _take(self, r: Result) -> Dict[str, np.ndarray]:
         """Result struct -> numpy.  The waveform arrays are *views of the callee's pinned buffers* that own them: the

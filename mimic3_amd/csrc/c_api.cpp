@@ -179,6 +179,17 @@ int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, 
 
 void mi355vits_free_packed(mi355vits_packed_result* r) { free_packed_impl(r); }
 
+int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    int rc = guarded(h, [&] { h->eng->fetch_alignment(want, out); });
+    if (rc != MI355VITS_OK && out) mi355vits_free_alignment(out);
+    return rc;
+}
+
+void mi355vits_free_alignment(mi355vits_alignment* r) { free_alignment_impl(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

@@ -684,6 +684,7 @@ void Engine::fill_workspace(uint32_t pattern) {
     arena_a_.fill(pattern, stream_);
     arena_b_.fill(pattern, stream_);
     arena_p_.fill(pattern, stream_);
+    arena_al_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1797,6 +1798,8 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     // the frame counts, so its table rides in the upload below
     const bool rs = out_hz_ != 0;
     run_hz_ = rs ? out_hz_ : c.sample_rate;
+    run_L_ = rs ? rs_.L : 1;
+    run_M_ = rs ? rs_.M : 1;
     h_olen_.resize(B);
     Lo_ = rs ? 0 : L_;
     for (int b = 0; b < B; ++b) {
@@ -2112,6 +2115,60 @@ void free_packed_impl(mi355vits_packed_result* r) {
     free(own->offsets);
     free(own->lengths);
     free(own->peaks);
+    delete own;
+    memset(r, 0, sizeof(*r));
+}
+
+// ---------------------------------------------------------------- phoneme timing and levels (mi355vits_fetch_alignment)
+namespace {
+struct AlignOwner {
+    void* block = nullptr;
+    size_t cap = 0;
+};
+}  // namespace
+
+void Engine::fetch_alignment(uint32_t want, mi355vits_alignment* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (want & ~MI355VITS_ALIGN_LEVELS) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: unknown bits in want (" + std::to_string(want) + ")");
+    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: no completed run on this handle");
+    HIP_CHECK(hipSetDevice(device_));
+    const bool levels = (want & MI355VITS_ALIGN_LEVELS) != 0;
+    const size_t n = (size_t)B_ * Tx_, arrays = levels ? 5 : 3;
+    // one device block, array after array, in an arena of its own: the last run's buffers (phase A: durations, phase B: audio)
+    // and whatever a fetch laid out behind them stay where they are
+    arena_al_.reserve(5 * n * 4 + 4096, stream_);
+    arena_al_.reset();
+    int* d = arena_al_.alloc<int>(5 * n);
+    float* d_peak = levels ? reinterpret_cast<float*>(d + 3 * n) : nullptr;
+    float* d_rms = levels ? reinterpret_cast<float*>(d + 4 * n) : nullptr;
+    {
+        double audio = 0;
+        for (int b = 0; b < B_; ++b) audio += (double)h_olen_[b];
+        ProfScope ps(prof_, "align", 0, levels ? 4.0 * audio + 20.0 * (double)n : 12.0 * (double)n);
+        launch_align(d_wceil_, d_cum_, d_len_, B_, Tx_, o_audio_, Lo_, o_alen_, cfg_.hop_length, run_L_, run_M_, d, d + n, d + 2 * n,
+                     d_peak, d_rms, stream_);
+    }
+    auto* own = new AlignOwner();
+    out->owner_ = own;
+    own->block = PinnedPool::get().take(arrays * n * 4 + 16, &own->cap);
+    HIP_CHECK(hipMemcpyAsync(own->block, d, arrays * n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    int32_t* h = static_cast<int32_t*>(own->block);
+    out->batch = B_;
+    out->tx_max = Tx_;
+    out->sample_rate = run_hz_;
+    out->frames = h;
+    out->start = h + n;
+    out->samples = h + 2 * n;
+    out->peak = levels ? reinterpret_cast<float*>(h + 3 * n) : nullptr;
+    out->rms = levels ? reinterpret_cast<float*>(h + 4 * n) : nullptr;
+}
+
+void free_alignment_impl(mi355vits_alignment* r) {
+    if (!r || !r->owner_) return;
+    auto* own = static_cast<AlignOwner*>(r->owner_);
+    PinnedPool::get().give(own->block, own->cap);
     delete own;
     memset(r, 0, sizeof(*r));
 }

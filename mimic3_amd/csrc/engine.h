@@ -169,6 +169,8 @@ class Engine {
     void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
                     mi355vits_packed_result* out);
     void fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out);
+    // phoneme timing (and, with MI355VITS_ALIGN_LEVELS, levels) of the last completed run (mi355vits_fetch_alignment)
+    void fetch_alignment(uint32_t want, mi355vits_alignment* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -253,6 +255,7 @@ class Engine {
 
     DeviceArena arena_a_, arena_b_;
     DeviceArena arena_p_;  // mi355vits_fetch_packed only: the packed stream of a run whose frame-side arena has no room left for it
+    DeviceArena arena_al_;  // mi355vits_fetch_alignment only: its five arrays, outside everything a run or a fetch lays out
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -286,6 +289,7 @@ class Engine {
     ResampleFilter rs_;
     float* d_rs_coef_ = nullptr;   // rs_.table (an allocation of its own: it outlives the runs)
     int run_hz_ = 0;               // the rate the last run ran at
+    int run_L_ = 1, run_M_ = 1;    // its reduced ratio to the voice's rate (1 / 1 native): the handle's setting may have moved on
     int enc_ = 0;                  // MI355VITS_ENC_* of the packed streams (mi355vits_set_output_encoding): 0 = int16
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
@@ -309,5 +313,6 @@ class Engine {
 
 void free_result_impl(mi355vits_result* r);
 void free_packed_impl(mi355vits_packed_result* r);
+void free_alignment_impl(mi355vits_alignment* r);
 
 }  // namespace m355

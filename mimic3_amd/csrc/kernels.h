@@ -256,6 +256,15 @@ long resample_fill_tab(const ResampleFilter& f, const int* n_in, int B, int* tab
 void launch_resample(const ResampleFilter& f, const float* coef, const float* x, long x_bs, const int* x_len, int B, const int* tab,
                      long items, float* y, long y_bs, int y_ld, unsigned* peak_bits, hipStream_t s);
 
+// ---------------------------------------------------------------- phoneme timing and levels of a run (kernels_align.cpp)
+// w_ceil / cum [B, T] (k_durations' frames and their inclusive scan; read at t < len[b] only), len [B] phonemes of a row, audio [B]
+// rows of audio_bs floats with alen [B] valid samples (alen[b] <= audio_bs), hop samples per frame, L / M the reduced rate ratio.
+// Writes [B, T] each: frames, start = ceil(hop c[t-1] L / M), samples = ceil(hop c[t] L / M) - start, and with peak and rms both
+// given max |y| and (float) sqrt(sum((double) y y) / samples) over the span (0 for an empty one); peak == rms == nullptr: the
+// audio is not read.  At t >= len[b]: 0 frames, 0 samples, start = the end of the covered part, levels 0.
+void launch_align(const int* w_ceil, const int* cum, const int* len, int B, int T, const float* audio, long audio_bs, const int* alen,
+                  int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s);
+
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,
                   float scale, float* y, hipStream_t s);

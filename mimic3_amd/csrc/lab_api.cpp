@@ -138,6 +138,55 @@ int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* 
     });
 }
 
+int mi355vits_test_alignment(int device, int B, int T, const int32_t* frames, const int32_t* len, int64_t row_stride, const float* audio,
+                             const int32_t* alen, int32_t hop, int32_t L, int32_t M, int32_t* out_frames, int32_t* out_start,
+                             int32_t* out_samples, float* out_peak, float* out_rms) {
+    return guarded(nullptr, [&] {
+        if (!frames || !len || !audio || !alen || !out_frames || !out_start || !out_samples || B < 1 || T < 1 || row_stride < 1)
+            throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        if ((out_peak == nullptr) != (out_rms == nullptr)) throw EngineError(MI355VITS_ERR_INVALID, "peak and rms: both or neither");
+        if (hop < 1 || L < 1 || M < 1 || L > RESAMPLE_MAX_RATIO || M > RESAMPLE_MAX_RATIO) throw EngineError(MI355VITS_ERR_INVALID, "hop, L, M out of range");
+        const size_t n = (size_t)B * T;
+        // cum = the inclusive scan of the frames a row's phonemes have (k_durations' d_cum_); behind a row's count it is left as
+        // a pattern: the kernel must not look there
+        std::vector<int> cum(n, 0x7f7f7f7f);
+        for (int b = 0; b < B; ++b) {
+            if (len[b] < 0 || len[b] > T || alen[b] < 0 || alen[b] > row_stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            long long acc = 0;
+            for (int t = 0; t < len[b]; ++t) {
+                const int f = frames[(size_t)b * T + t];
+                if (f < 0 || f > DURATION_FRAME_CAP) throw EngineError(MI355VITS_ERR_INVALID, "frames out of range");
+                acc += f;
+                if (acc > DURATION_FRAME_CAP) throw EngineError(MI355VITS_ERR_INVALID, "a row's frames exceed the duration cap");
+                cum[(size_t)b * T + t] = (int)acc;
+            }
+            if (resample_out_len(acc * hop, L, M) > 0x7fffffffLL) throw EngineError(MI355VITS_ERR_INVALID, "row does not fit 32 bits");
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t na = (size_t)B * row_stride;
+        DevBuf df(n * 4), dc(n * 4), dl(B * 4), da(na * 4), dal(B * 4), dout(5 * n * 4);
+        HIP_CHECK(hipMemcpy(df.p, frames, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, cum.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dal.p, alen, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xff, 5 * n * 4));  // the kernel writes every element it is asked for
+        int* d = dout.as<int>();
+        launch_align(df.as<int>(), dc.as<int>(), dl.as<int>(), B, T, da.as<float>(), (long)row_stride, dal.as<int>(), hop, L, M, d, d + n,
+                     d + 2 * n, out_peak ? reinterpret_cast<float*>(d + 3 * n) : nullptr, out_peak ? reinterpret_cast<float*>(d + 4 * n) : nullptr,
+                     nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out_frames, d, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_start, d + n, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_samples, d + 2 * n, n * 4, hipMemcpyDeviceToHost));
+        if (out_peak) {
+            HIP_CHECK(hipMemcpy(out_peak, d + 3 * n, n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(out_rms, d + 4 * n, n * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
 int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out) {
     return guarded(nullptr, [&] {
         if (!in || !out || n < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");

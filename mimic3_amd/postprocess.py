@@ -116,3 +116,37 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     lead_ms = [break_ms if (i and break_ms) else 0.0 for i in range(B)]
     out = session.run_packed(feed, lead_ms=lead_ms, wav=True, **settings)
     return bytes(out.wav)
+
+
+def marks(alignment, row: int, spans: Sequence) -> list:
+    """Id ranges of one row -> speech marks (word / phoneme times for captions, visemes, a position for an SSML ``<mark>``).
+
+    ``alignment``: an ``_native.Alignment`` (``InferenceSession.run_pcm16(..., alignment=True)``, ``run_packed(...,
+    alignment=True)`` — then the samples are stream samples —, ``Engine.fetch_alignment``); ``spans``: ``(label, first_id_index,
+    end_id_index)`` each, the half-open range of phoneme-id positions of that row the label covers (words and the interleaving
+    of their ids are the caller's: above the id boundary).  Returns one dict per span: ``label``, ``start_sample``,
+    ``end_sample`` (half-open), ``start_s``, ``end_s`` (samples / ``alignment.sample_rate``) and, when the alignment carries
+    levels, ``peak`` = the largest per-phoneme peak and ``rms`` = ``sqrt(sum(rms_t^2 * n_t) / sum(n_t))`` over the span's phonemes
+    (0 for a span without samples)."""
+    start = np.asarray(alignment.start)[row].astype(np.int64)
+    count = np.asarray(alignment.samples)[row].astype(np.int64)
+    tx = int(start.shape[0])
+    rate = float(alignment.sample_rate)
+    out = []
+    for label, first, end in spans:
+        first, end = int(first), int(end)
+        if not 0 <= first <= end <= tx:
+            raise ValueError(f"span {label!r}: id range [{first}, {end}) outside 0 .. {tx}")
+        if first < tx:
+            s = int(start[first])
+        else:  # an empty span behind the last position: the end of the row
+            s = int(start[tx - 1] + count[tx - 1])
+        e = int(start[end - 1] + count[end - 1]) if end > first else s
+        m = {"label": label, "start_sample": s, "end_sample": e, "start_s": s / rate, "end_s": e / rate}
+        if alignment.peak is not None and alignment.rms is not None:
+            n = count[first:end].astype(np.float64)
+            r = np.asarray(alignment.rms)[row, first:end].astype(np.float64)
+            m["peak"] = float(np.max(np.asarray(alignment.peak)[row, first:end], initial=0.0))
+            m["rms"] = float(np.sqrt(np.sum(r * r * n) / np.sum(n))) if np.sum(n) > 0 else 0.0
+        out.append(m)
+    return out

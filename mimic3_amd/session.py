@@ -484,6 +484,15 @@ def _encoding_name(encoding) -> str:
     return encoding.lower()
 
 
+def _alignment_levels(alignment) -> bool:
+    """``alignment=True`` -> timing only, ``"levels"`` -> peak and rms too; anything else raises ``ValueError``."""
+    if alignment is True:
+        return False
+    if isinstance(alignment, str) and alignment.lower() == "levels":
+        return True
+    raise ValueError(f"alignment must be False, True or 'levels', not {alignment!r}")
+
+
 class InferenceSession:
     """Drop-in for the object stored in ``Mimic3Voice.onnx_model``."""
 
@@ -577,7 +586,7 @@ class InferenceSession:
 
     # ---- engine extensions --------------------------------------------------------------------
     def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
-                  sample_rate: Optional[int] = None) -> Tuple[List[np.ndarray], np.ndarray]:
+                  sample_rate: Optional[int] = None, alignment=False):
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -589,15 +598,26 @@ class InferenceSession:
         row instead of the session's running count (``reserve_utterances``) — a row's noise, hence its audio at nonzero
         noise scales, then depends on its own inputs only, not on the batch or the moment it rides in.  ``sample_rate``: the
         rate of this call's audio instead of the session's ``output_sample_rate`` (resampled as f32 on the GPU before the int16
-        conversion; not a per-row setting: micro-batched requests of different rates never share an engine call)."""
+        conversion; not a per-row setting: micro-batched requests of different rates never share an engine call).
+        ``alignment`` (``True``, or ``"levels"`` for peak and rms too): also where each phoneme sits in its row
+        (``mi355vits_fetch_alignment``) — the call then goes straight to a lane, never through the micro-batcher, fetches the
+        alignment on that lane before releasing it, and returns (rows, lengths, ``_native.Alignment``)."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
+        if alignment:
+            ids, lengths, sid = self._feed(input_feed)
+            keys = kw.pop("utterance_keys", None)
+            out, al = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _alignment=_alignment_levels(alignment),
+                                       want_float=False, want_pcm16=True, **kw)
+            self.last_lengths = out["lengths"]
+            return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"], al
         out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
         return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
-                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None) -> "_native.PackedAudio":
+                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+                   alignment=False) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -606,7 +626,10 @@ class InferenceSession:
         rate of the stream: ``sample_rate``, else the session's ``output_sample_rate``, else the voice's), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
         copy of exactly those bytes.  Same feed, ``volume`` and ``utterance_keys`` as ``run_pcm16``, and every entry is bitwise
         that call's row.  Returns ``_native.PackedAudio`` (``pcm``, ``rows`` — views of ``pcm`` —, ``offsets``, ``lengths``,
-        ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher."""
+        ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher.
+        ``alignment`` (``True`` / ``"levels"``): sets ``PackedAudio.alignment`` (default ``None``) in STREAM coordinates — row i
+        belongs to entry i and ``offsets[i]`` is added to ``start``, so ``data[start[i, t] : start[i, t] + samples[i, t]]`` is
+        phoneme t of entry i in any encoding."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -618,8 +641,16 @@ class InferenceSession:
             lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
         ids, lengths, sid = self._feed(input_feed)
         keys = kw.pop("utterance_keys", None)
+        if alignment:
+            kw["_alignment"] = _alignment_levels(alignment)
         out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
                                lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
+        if alignment:
+            out, al = out
+            rows = np.arange(len(out.offsets)) if order is None else np.asarray(order, np.int64).reshape(-1)
+            pick = lambda a: None if a is None else a[rows]  # noqa: E731
+            out.alignment = _native.Alignment(al.frames[rows], al.start[rows].astype(np.int64) + np.asarray(out.offsets, np.int64)[:, None],
+                                              al.samples[rows], pick(al.peak), pick(al.rms), al.sample_rate)
         self.last_lengths = out.lengths
         return out
 
@@ -681,7 +712,10 @@ class InferenceSession:
             self._utterances += int(n)
         return base
 
-    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None, **kw):
+    def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
+                    _alignment=None, **kw):
+        """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
+        — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
             raise RuntimeError("session is closed")
         keys = None if utterance_keys is None else list(utterance_keys)
@@ -697,7 +731,8 @@ class InferenceSession:
             if _packed:  # the encoding concerns packed streams only; read by the engine when the pack is planned
                 eng.set_output_encoding(encoding or self.output_encoding)
             call = eng.run_packed if _packed else eng.run
-            return call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
+            out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
+            return out if _alignment is None else (out, eng.fetch_alignment(levels=_alignment))
         except _native.NativeError as e:
             if e.code == -1:
                 raise InvalidArgument(str(e)) from None
