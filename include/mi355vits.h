@@ -359,6 +359,57 @@ typedef struct mi355vits_alignment {
 int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out);
 void mi355vits_free_alignment(mi355vits_alignment* r);
 
+/* ---- Exact pauses: trim each entry's quiet edges in the packed streams.  A VITS voice puts a stretch of near-silence of its own at
+ * the start and the end of every sentence; the reference adds its break (int(ms / 1000 * sample_rate) zero samples,
+ * mimic3_tts/tts.py:452-465) on top of it, so a 250 ms break is heard as 250 ms plus two unknown tails.  With edge trimming on, an
+ * entry of a packed stream is its row cut to the loud part, and lead_samples is the pause.  The rule is exact — integers from f32
+ * comparisons, no tolerance: for a row with n valid samples y[0..n) at the run's rate (the MI355VITS_WANT_FLOAT samples) and peak p
+ * (bitwise peaks[b] of the run),
+ *     thr = p * ratio                 one IEEE f32 multiply, rounded to nearest
+ *     sample k is loud  iff  fabsf(y[k]) >= thr           (exactly at thr: loud; a NaN: not loud)
+ *     first = max(0, s_first - keep_samples),  end = min(n, s_last + 1 + keep_samples)       s_first / s_last: first / last loud sample
+ * ratio <= 1 makes the sample that holds the peak loud: a row is never emptied (end - first >= 1 for n >= 1); an all-zero row has
+ * thr = 0, every sample loud and nothing cut.  One kernel (k_edges) reads the valid samples once; keep and the clamps are the host's.
+ *  - mi355vits_set_edge_trim: ratio = 0 (the default): off — nothing below applies, nothing is launched or laid out, every byte is
+ *    what it was.  ratio NaN, < 0 or > 1, or keep_samples < 0: MI355VITS_ERR_INVALID, the message names the value, the setting stays.
+ *    keep_samples counts samples at the run's output rate, like lead_samples.  mi355vits_clone inherits the setting.  It is read when
+ *    a pack is made and at each mi355vits_fetch_edges (as mi355vits_set_output_encoding is): one synthesis can be packed trimmed and
+ *    untrimmed, at several thresholds, with no synthesis work repeated.
+ *  - Scope: the packed streams and mi355vits_fetch_edges only.  mi355vits_run / _run_rows / _fetch / _device_result, the padded
+ *    audio / pcm, lengths, peaks, l_max, and mi355vits_fetch_alignment (row coordinates) stay bit for bit what they are whatever the
+ *    setting; a caller of the padded forms slices with first / end.
+ *  - mi355vits_run_packed / _fetch_packed with trimming on: entry i of row r is samples [first[r], end[r]) of that row, bitwise those
+ *    samples of the untrimmed stream for the same arguments in every encoding and math mode (the int16 and G.711 scales are still the
+ *    row's peak and volume; F32LE is bits in, bits out).  lengths[i] = end[r] - first[r]; offsets and total_samples follow from the
+ *    trimmed lengths; peaks[i] is the row's peak as before; every other sample is the silence code, written by the kernel; the RIFF
+ *    sizes and the fact count are the trimmed stream's.  The size checks that need only n, order and the silences run before
+ *    synthesis as before; the limits that count audio are checked on the TRIMMED sizes before the pack is sized or launched: the
+ *    result is never partial audio, and a run_packed that fails there leaves no result served, as a failed run does.
+ *  - Synchronisation: the offsets now depend on the audio.  A trimmed mi355vits_run_packed synchronises the stream three times
+ *    instead of twice (frame counts, edges, result), a trimmed mi355vits_fetch_packed twice instead of once, and each copies 8 * B
+ *    bytes more to the host.  The edges of the last run under the last ratio are kept on the host: a repeated fetch at the same
+ *    ratio does not launch again.  With ratio = 0 the counts are what they were.
+ *  - mi355vits_fetch_edges serves the LAST COMPLETED RUN whatever its flags were, at the rate it ran at, under the current setting.
+ *    It works in an arena of its own: what mi355vits_fetch / _fetch_packed / _fetch_alignment / _device_result serve afterwards is
+ *    what they served before.  Before any completed run: MI355VITS_ERR_INVALID with "fetch_edges: no completed run on this handle";
+ *    a NULL out: MI355VITS_ERR_INVALID.  With the setting off: first = 0, end = lengths, nothing launched.
+ *  - With profiling enabled the launch is reported as "edges": bytes = 4 * sum(lengths) + 8 * B. */
+int mi355vits_set_edge_trim(mi355vits_handle h, float ratio, int32_t keep_samples);
+int mi355vits_get_edge_trim(mi355vits_handle h, float* ratio, int32_t* keep_samples);
+
+typedef struct mi355vits_edges {
+    int32_t batch;
+    int32_t sample_rate;   /* the rate the run served ran at: first / end count these samples */
+    float ratio;           /* the setting the arrays were made with (0: off — first = 0, end = lengths) */
+    int32_t keep_samples;
+    int32_t* first;        /* [B] first kept sample of row b */
+    int32_t* end;          /* [B] one past the last kept sample */
+    void* owner_;          /* private */
+} mi355vits_edges;
+
+int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out);
+void mi355vits_free_edges(mi355vits_edges* r);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

@@ -69,6 +69,12 @@ int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* 
 int mi355vits_test_alignment(int device, int B, int T, const int32_t* frames, const int32_t* len, int64_t row_stride, const float* audio,
                              const int32_t* alen, int32_t hop, int32_t L, int32_t M, int32_t* out_frames, int32_t* out_start,
                              int32_t* out_samples, float* out_peak, float* out_rms);
+/* Kernel unit-test hook: the edge kernel (k_edges, mi355vits_set_edge_trim) alone over host arrays on the current device.  audio [B]
+ * rows of `stride` floats, lens [B] (0 <= lens[b] <= stride) valid samples, peaks [B], 0 < ratio <= 1.  Writes s_first[b] = the first
+ * sample with fabsf(y) >= peaks[b] * ratio (lens[b] when there is none) and s_last[b] = the last (-1).  What lies behind a row is
+ * never looked at. */
+int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, const float* peaks, int B, float ratio, int32_t* s_first,
+                        int32_t* s_last);
 /* Kernel unit-test hook: the G.711 encoders of the encoded packed streams (mi355vits_set_output_encoding) over an array on the
  * current device.  law = MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW; out[i] = the code of in[i].  65,536 inputs cover the function. */
 int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);

@@ -38,12 +38,13 @@ EXPORTED_SYMBOLS = (
     "mi355vits_set_output_rate", "mi355vits_get_output_rate",
     "mi355vits_set_output_encoding", "mi355vits_get_output_encoding",
     "mi355vits_fetch_alignment", "mi355vits_free_alignment",
+    "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
-    "mi355vits_lab_g711_encode", "mi355vits_test_alignment",
+    "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
 )
 
 
@@ -132,6 +133,27 @@ class AlignmentResult(ctypes.Structure):
 
 
 ALIGN_LEVELS = 1
+
+
+class EdgesResult(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("sample_rate", ctypes.c_int32),
+        ("ratio", ctypes.c_float),
+        ("keep_samples", ctypes.c_int32),
+        ("first", ctypes.POINTER(ctypes.c_int32)),
+        ("end", ctypes.POINTER(ctypes.c_int32)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class Edges:
+    """The kept part of every row of a run under an edge-trim setting (``mi355vits_fetch_edges``): row b keeps samples
+    ``first[b] : end[b]`` at ``sample_rate``, the rate the run ran at; ``ratio`` / ``keep_samples`` the setting the arrays were made
+    with (ratio 0: off — ``first`` = 0, ``end`` = the lengths).  The arrays are copies owned by Python."""
+
+    def __init__(self, first, end, ratio, keep_samples, sample_rate):
+        self.first, self.end, self.ratio, self.keep_samples, self.sample_rate = first, end, ratio, keep_samples, sample_rate
 
 
 class Alignment:
@@ -224,6 +246,11 @@ class NativeLibrary:
         L.mi355vits_fetch_alignment.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.argtypes = [ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.restype = None
+        L.mi355vits_set_edge_trim.argtypes = [H, ctypes.c_float, ctypes.c_int32]
+        L.mi355vits_get_edge_trim.argtypes = [H, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
+        L.mi355vits_fetch_edges.argtypes = [H, ctypes.POINTER(EdgesResult)]
+        L.mi355vits_free_edges.argtypes = [ctypes.POINTER(EdgesResult)]
+        L.mi355vits_free_edges.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -262,6 +289,7 @@ class NativeLibrary:
                                                   ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_lab_g711_encode.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_long, ctypes.POINTER(ctypes.c_uint8)]
             i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+            L.mi355vits_lab_edges.argtypes = [f32p, ctypes.c_long, i32p, f32p, ctypes.c_int, ctypes.c_float, i32p, i32p]
             L.mi355vits_test_alignment.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int64, f32p, i32p,
                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
@@ -292,6 +320,25 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return out
+
+    def lab_edges(self, audio, lengths, peaks, ratio):
+        """The edge kernel (k_edges) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is never
+        looked at), peaks [B] f32, 0 < ratio <= 1 -> (s_first, s_last) int32 [B]: the first / last sample with
+        ``abs(y) >= peaks[b] * ratio`` in f32 (lengths[b] / -1 when there is none)."""
+        self._need_hooks()
+        au = np.ascontiguousarray(audio, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        pk = np.ascontiguousarray(peaks, np.float32).reshape(-1)
+        if au.ndim != 2 or ln.shape[0] != au.shape[0] or pk.shape[0] != au.shape[0]:
+            raise ValueError("audio [B, stride], lengths [B], peaks [B]")
+        B = au.shape[0]
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        first, last = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        rc = self.lib.mi355vits_lab_edges(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), _fptr(pk), B, float(ratio),
+                                          first.ctypes.data_as(i32p), last.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return first, last
 
     def test_conv1d(self, x, w, bias=None, res=None, dilation=1, impl=1, in_len=None, out_len=None, in_slope=1.0,
                     relu=False, out_scale=1.0, res_sub=False, accumulate_into=None, device=0) -> np.ndarray:
@@ -513,9 +560,11 @@ class PackedAudio:
     int16 ("s16le"), uint8 G.711 codes ("ulaw" / "alaw") or float32 ("f32le") —, ``rows[i]`` =
     ``data[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
     when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry, in samples.  ``pcm`` is ``data`` of an
-    int16 stream, and raises for any other encoding."""
+    int16 stream, and raises for any other encoding.  With edge trimming on (``Engine.set_edge_trim``) entry i is samples
+    ``first[i] : end[i]`` of its row (``lengths[i] = end[i] - first[i]``); both are ``None`` when trimming is off."""
 
-    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le"):
+    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le", first=None, end=None):
+        self.first, self.end = first, end
         self.alignment: Optional[Alignment] = None  # set by InferenceSession.run_packed(alignment=...): spans in stream samples
         self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
         self.encoding = encoding
@@ -703,13 +752,14 @@ class Engine:
         if p is not None and p.n < 0:
             p.n = a.batch
         enc = self.output_encoding  # read by the library when the call starts; only this thread sets it meanwhile
+        trimmed = self.edge_trim[0] != 0.0  # likewise
         r = PackedResult()
         self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                          None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del keep, pkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate
-        return self._take_packed(r, bool(wav), enc)
+        return self._take_packed(r, bool(wav), enc, order if trimmed else None, trimmed)
 
     def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
         """Pack the last completed run of this handle again (``mi355vits_fetch_packed``): that run's rows and per-row volumes,
@@ -718,12 +768,13 @@ class Engine:
         if p is not None and p.n < 0:
             p.n = self._last_batch  # every row of the last run (0 before the first: the library names the error)
         enc = self.output_encoding
+        trimmed = self.edge_trim[0] != 0.0
         r = PackedResult()
         self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del pkeep
-        return self._take_packed(r, bool(wav), enc)
+        return self._take_packed(r, bool(wav), enc, order if trimmed else None, trimmed)
 
-    def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le") -> PackedAudio:
+    def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le", order=None, trimmed: bool = False) -> PackedAudio:
         n = int(r.n)
         try:
             offsets = np.ctypeslib.as_array(r.offsets, shape=(n,)).copy()
@@ -739,7 +790,40 @@ class Engine:
             raise
         block = _PackedHolder(self.native, r).view()
         pcm = block[hdr: hdr + data].view(dtype)
-        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc)
+        first = end = None
+        if trimmed:
+            # the edges the pack was placed with: the library holds them on the host for this ratio, nothing is launched
+            e = self.fetch_edges()
+            rows = np.arange(n) if order is None else np.asarray(order, np.int64).reshape(-1)
+            first, end = e.first[rows], e.end[rows]
+        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc, first, end)
+
+    def set_edge_trim(self, ratio, keep_samples: int = 0) -> None:
+        """Trim each entry's quiet edges in the packed streams made after this (``mi355vits_set_edge_trim``): a sample is loud iff
+        ``abs(y) >= peak * ratio`` (one f32 multiply), an entry is its row from ``keep_samples`` before the first loud sample to
+        ``keep_samples`` behind the last.  ``ratio`` 0 (the default) = off; NaN, < 0, > 1 or a negative keep raise and leave the
+        setting as it was.  Read by ``run_packed``, each ``fetch_packed`` and each ``fetch_edges``; the padded results, ``fetch``
+        and ``fetch_alignment`` are unchanged by it."""
+        self._check(self.native.lib.mi355vits_set_edge_trim(self._h, float(ratio or 0.0), int(keep_samples)))
+
+    @property
+    def edge_trim(self):
+        """``(ratio, keep_samples)`` of ``set_edge_trim``; ratio 0.0 = off."""
+        ratio, keep = ctypes.c_float(), ctypes.c_int32()
+        self._check(self.native.lib.mi355vits_get_edge_trim(self._h, ctypes.byref(ratio), ctypes.byref(keep)))
+        return float(ratio.value), int(keep.value)
+
+    def fetch_edges(self) -> Edges:
+        """``first`` / ``end`` of every row of the last completed run under the current ``set_edge_trim`` setting
+        (``mi355vits_fetch_edges``), whatever the run's flags were, at the rate it ran at."""
+        r = EdgesResult()
+        self._check(self.native.lib.mi355vits_fetch_edges(self._h, ctypes.byref(r)))
+        try:
+            B = int(r.batch)
+            take = lambda p: np.ctypeslib.as_array(p, shape=(B,)).copy()  # noqa: E731
+            return Edges(take(r.first), take(r.end), float(r.ratio), int(r.keep_samples), int(r.sample_rate))
+        finally:
+            self.native.lib.mi355vits_free_edges(ctypes.byref(r))
 
     def set_output_encoding(self, encoding) -> None:
         """The sample encoding of the packed streams made after this (``mi355vits_set_output_encoding``): ``"s16le"`` (the

@@ -190,6 +190,31 @@ int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_align
 
 void mi355vits_free_alignment(mi355vits_alignment* r) { free_alignment_impl(r); }
 
+int mi355vits_set_edge_trim(mi355vits_handle h, float ratio, int32_t keep_samples) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_edge_trim(ratio, keep_samples); });
+}
+
+int mi355vits_get_edge_trim(mi355vits_handle h, float* ratio, int32_t* keep_samples) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    if (ratio) *ratio = h->eng->edge_trim_ratio();
+    if (keep_samples) *keep_samples = h->eng->edge_trim_keep();
+    return MI355VITS_OK;
+}
+
+int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    int rc = guarded(h, [&] { h->eng->fetch_edges(out); });
+    if (rc != MI355VITS_OK && out) mi355vits_free_edges(out);
+    return rc;
+}
+
+void mi355vits_free_edges(mi355vits_edges* r) { free_edges_impl(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

@@ -395,6 +395,8 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         sw_ = lane0.sw_;
         if (lane0.out_hz_) set_output_rate(lane0.out_hz_);
         enc_ = lane0.enc_;
+        trim_ratio_ = lane0.trim_ratio_;
+        trim_keep_ = lane0.trim_keep_;
     } catch (...) {
         release();
         throw;
@@ -685,6 +687,7 @@ void Engine::fill_workspace(uint32_t pattern) {
     arena_b_.fill(pattern, stream_);
     arena_p_.fill(pattern, stream_);
     arena_al_.fill(pattern, stream_);
+    arena_ed_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1645,14 +1648,20 @@ struct Engine::PackPlan {
     int64_t total = 0, audio = 0;
     // the handle's output encoding when the pack was planned (MI355VITS_ENC_* = PackEncoding)
     int enc = PACK_ENC_S16;
+    // the handle's edge trimming when the pack was planned (ratio 0 = off); with it on, place_pack fills skip: the first sample
+    // of its row each entry starts at
+    float ratio = 0.0f;
+    int keep = 0;
+    std::vector<int> skip;
+    bool trimmed() const { return ratio != 0.0f; }
     int bps() const { return pack_bytes_per_sample(enc); }
     size_t header_bytes() const { return !wav ? 0 : enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
 };
 
 // Packed calls only: the segment table and the stream, behind everything layout_b placed — no other pointer moves, so a call
 // that packs nothing runs on the layout it always had.
-template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples, int enc) {
-    d_pack_seg_ = ar.template alloc<int>(3 * n);
+template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples, int enc, int seg_rows) {
+    d_pack_seg_ = ar.template alloc<int>((size_t)seg_rows * n);
     d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(enc, (long)samples));  // in bytes, the last store's overrun included
 }
 
@@ -1712,6 +1721,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
 
     HIP_CHECK(hipSetDevice(device_));
     have_result_ = false;
+    have_edges_ = false;
     taps_on_ = (args.flags & MI355VITS_DEBUG_TAPS) != 0;
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();
@@ -1936,6 +1946,8 @@ void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) c
     if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
     plan.wav = pack && pack->wav_header != 0;
     plan.enc = enc_;  // the setting is read here: when a pack is made
+    plan.ratio = trim_ratio_;  // likewise
+    plan.keep = trim_keep_;
     plan.tail = pack ? pack->tail_samples : 0;
     plan.order.resize(plan.n);
     plan.lead.assign(plan.n, 0);
@@ -1959,16 +1971,26 @@ void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) c
     check_pack_size(-1, silence + plan.tail, plan.wav, plan.enc);
 }
 
-// Where every entry goes, from the frame counts the host already holds; the size limits with the audio counted in.
+// Where every entry goes, from the frame counts the host already holds — with trimming on from the edges as well (h_edges_ at the
+// plan's ratio: find_edges first); the size limits with the audio counted in.
 void Engine::place_pack(PackPlan& plan) const {
     plan.offsets.resize(plan.n);
     plan.lengths.resize(plan.n);
+    plan.skip.assign(plan.trimmed() ? plan.n : 0, 0);
     int64_t pos = 0;
     plan.audio = 0;
     for (int i = 0; i < plan.n; ++i) {
         pos += plan.lead[i];
         plan.offsets[i] = pos;
         plan.lengths[i] = h_olen_[plan.order[i]];  // at the run's rate
+        if (plan.trimmed()) {
+            const int row = plan.order[i];
+            const int64_t n = h_olen_[row];
+            const int64_t first = std::max<int64_t>(0, (int64_t)h_edges_[row] - plan.keep);
+            const int64_t end = std::min<int64_t>(n, (int64_t)h_edges_[B_ + row] + 1 + plan.keep);
+            plan.skip[i] = (int)std::min(first, n);
+            plan.lengths[i] = std::max<int64_t>(0, end - plan.skip[i]);  // (a row without a loud sample — a NaN peak — keeps nothing)
+        }
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
         check_pack_size(i, pos, plan.wav, plan.enc);
@@ -1982,18 +2004,19 @@ void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
         seg[i] = (int)plan.offsets[i];
         seg[plan.n + i] = plan.order[i];
         seg[2 * plan.n + i] = (int)plan.lengths[i];
+        if (plan.trimmed()) seg[3 * plan.n + i] = plan.skip[i];
     }
 }
 
 void Engine::launch_pack(const PackPlan& plan) {
     if (plan.enc == PACK_ENC_S16) {
         ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
-        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_);
+        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_, plan.trimmed());
         return;
     }
     const char* label = plan.enc == PACK_ENC_ULAW ? "pack.ulaw" : plan.enc == PACK_ENC_ALAW ? "pack.alaw" : "pack.f32";
     ProfScope ps(prof_, label, 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
-    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_);
+    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_, plan.trimmed());
 }
 
 void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
@@ -2077,8 +2100,24 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     PackPlan plan;
     plan_pack(pack, args.batch, plan);
-    synthesize(args, rows, &plan);
-    copy_out_packed(plan, out);
+    if (!plan.trimmed()) {
+        synthesize(args, rows, &plan);
+        copy_out_packed(plan, out);
+        return;
+    }
+    // Trimming on: the offsets depend on the audio.  Synthesise without an early pack table (and without the padded int16 pass: a
+    // packed call looks at no MI355VITS_WANT_* flag), find the edges (k_edges, 8 B bytes, one synchronisation), then what
+    // fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
+    mi355vits_run_args a = args;
+    a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
+    synthesize(a, rows, nullptr);
+    try {
+        pack_last_run(plan, out);
+        HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its edges and its pack
+    } catch (...) {
+        have_result_ = false;
+        throw;
+    }
 }
 
 void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
@@ -2087,21 +2126,27 @@ void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_resu
     if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_packed: no completed run on this handle");
     PackPlan plan;
     plan_pack(pack, B_, plan);
-    place_pack(plan);
+    pack_last_run(plan, out);
+}
+
+void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipSetDevice(device_));
+    if (plan.trimmed()) find_edges(plan.ratio);
+    place_pack(plan);
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
+    const int seg_rows = plan.trimmed() ? 4 : 3;
     ArenaCount need;
-    layout_pack(need, plan.n, plan.total, plan.enc);
+    layout_pack(need, plan.n, plan.total, plan.enc, seg_rows);
     if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
         arena_b_.rewind(layout_b_end_);
-        layout_pack(arena_b_, plan.n, plan.total, plan.enc);
+        layout_pack(arena_b_, plan.n, plan.total, plan.enc, seg_rows);
     } else {
         arena_p_.reserve(need.bytes + 4096, stream_);
         arena_p_.reset();
-        layout_pack(arena_p_, plan.n, plan.total, plan.enc);
+        layout_pack(arena_p_, plan.n, plan.total, plan.enc, seg_rows);
     }
-    h_pack_seg_.assign(3 * (size_t)plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
+    h_pack_seg_.assign((size_t)seg_rows * plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
     fill_pack_seg(plan, h_pack_seg_.data());
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
     launch_pack(plan);
@@ -2169,6 +2214,80 @@ void free_alignment_impl(mi355vits_alignment* r) {
     if (!r || !r->owner_) return;
     auto* own = static_cast<AlignOwner*>(r->owner_);
     PinnedPool::get().give(own->block, own->cap);
+    delete own;
+    memset(r, 0, sizeof(*r));
+}
+
+// ---------------------------------------------------------------- the quiet edges of a run's rows (mi355vits_set_edge_trim / _fetch_edges)
+void Engine::set_edge_trim(float ratio, int keep_samples) {
+    if (!(ratio >= 0.0f && ratio <= 1.0f))  // NaN fails both
+        throw EngineError(MI355VITS_ERR_INVALID, "set_edge_trim: ratio " + std::to_string(ratio) + " is outside [0, 1]");
+    if (keep_samples < 0) throw EngineError(MI355VITS_ERR_INVALID, "set_edge_trim: keep_samples " + std::to_string(keep_samples) + " is negative");
+    trim_ratio_ = ratio;
+    trim_keep_ = keep_samples;
+}
+
+// The raw first / last loud sample of every row of the last run at `ratio` into h_edges_: one launch in an arena of its own, one
+// 8 B byte copy, one synchronisation — or nothing when the host still holds them for this ratio.
+void Engine::find_edges(float ratio) {
+    if (have_edges_ && h_edges_ratio_ == ratio) return;
+    const int B = B_;
+    arena_ed_.reserve(2 * (size_t)B * 4 + 4096, stream_);
+    arena_ed_.reset();
+    int* d = arena_ed_.alloc<int>(2 * (size_t)B);
+    {
+        double audio = 0;
+        for (int b = 0; b < B; ++b) audio += (double)h_olen_[b];
+        ProfScope ps(prof_, "edges", 0, 4.0 * audio + 8.0 * (double)B);
+        launch_edges(o_audio_, Lo_, o_alen_, o_peaks_, B, Lo_, ratio, d, d + B, stream_);
+    }
+    h_edges_.resize(2 * (size_t)B);
+    HIP_CHECK(hipMemcpyAsync(h_edges_.data(), d, 2 * (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    h_edges_ratio_ = ratio;
+    have_edges_ = true;
+}
+
+namespace {
+struct EdgesOwner {
+    void* block = nullptr;
+};
+}  // namespace
+
+void Engine::fetch_edges(mi355vits_edges* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_edges: result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_edges: no completed run on this handle");
+    HIP_CHECK(hipSetDevice(device_));
+    const float ratio = trim_ratio_;
+    const int keep = trim_keep_;
+    if (ratio != 0.0f) find_edges(ratio);
+    auto* own = new EdgesOwner();
+    out->owner_ = own;
+    own->block = malloc(sizeof(int32_t) * 2 * (size_t)B_);
+    if (!own->block) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
+    out->batch = B_;
+    out->sample_rate = run_hz_;
+    out->ratio = ratio;
+    out->keep_samples = keep;
+    out->first = static_cast<int32_t*>(own->block);
+    out->end = out->first + B_;
+    for (int b = 0; b < B_; ++b) {
+        const int64_t n = h_olen_[b];
+        int64_t first = 0, end = n;
+        if (ratio != 0.0f) {
+            first = std::min<int64_t>(n, std::max<int64_t>(0, (int64_t)h_edges_[b] - keep));
+            end = std::max<int64_t>(first, std::min<int64_t>(n, (int64_t)h_edges_[B_ + b] + 1 + keep));
+        }
+        out->first[b] = (int32_t)first;
+        out->end[b] = (int32_t)end;
+    }
+}
+
+void free_edges_impl(mi355vits_edges* r) {
+    if (!r || !r->owner_) return;
+    auto* own = static_cast<EdgesOwner*>(r->owner_);
+    free(own->block);
     delete own;
     memset(r, 0, sizeof(*r));
 }

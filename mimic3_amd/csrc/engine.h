@@ -171,6 +171,12 @@ class Engine {
     void fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out);
     // phoneme timing (and, with MI355VITS_ALIGN_LEVELS, levels) of the last completed run (mi355vits_fetch_alignment)
     void fetch_alignment(uint32_t want, mi355vits_alignment* out);
+    // edge trimming of the packed streams (mi355vits_set_edge_trim): ratio 0 = off.  Read when a pack is made and at fetch_edges.
+    void set_edge_trim(float ratio, int keep_samples);
+    float edge_trim_ratio() const { return trim_ratio_; }
+    int edge_trim_keep() const { return trim_keep_; }
+    // first / end of every row of the last completed run under the current setting (mi355vits_fetch_edges)
+    void fetch_edges(mi355vits_edges* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -221,7 +227,8 @@ class Engine {
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
-    template <typename A> void layout_pack(A& ar, size_t n, size_t samples, int enc);  // continues layout_b in packed calls, and only there
+    // continues layout_b in packed calls, and only there; seg_rows: 3, or 4 in a trimmed pack
+    template <typename A> void layout_pack(A& ar, size_t n, size_t samples, int enc, int seg_rows = 3);
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
     // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
@@ -229,8 +236,10 @@ class Engine {
     void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan);
     void plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const;  // validates; nothing sized or launched yet
     void place_pack(PackPlan& plan) const;                                           // offsets / total from h_ylen_; the size limits
-    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [3][n]: first sample, row, length
+    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [3][n]: first sample, row, length (trimmed: [4][n], + first source sample)
     void launch_pack(const PackPlan& plan);
+    void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
+    void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
     void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
 
     mi355vits_config cfg_{};
@@ -256,6 +265,7 @@ class Engine {
     DeviceArena arena_a_, arena_b_;
     DeviceArena arena_p_;  // mi355vits_fetch_packed only: the packed stream of a run whose frame-side arena has no room left for it
     DeviceArena arena_al_;  // mi355vits_fetch_alignment only: its five arrays, outside everything a run or a fetch lays out
+    DeviceArena arena_ed_;  // k_edges' two words per row, likewise
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -291,6 +301,13 @@ class Engine {
     int run_hz_ = 0;               // the rate the last run ran at
     int run_L_ = 1, run_M_ = 1;    // its reduced ratio to the voice's rate (1 / 1 native): the handle's setting may have moved on
     int enc_ = 0;                  // MI355VITS_ENC_* of the packed streams (mi355vits_set_output_encoding): 0 = int16
+    // edge trimming (mi355vits_set_edge_trim): the setting, and the last run's raw first / last loud sample per row at h_edges_ratio_
+    // (kept on the host so a repeated fetch_packed / fetch_edges does not launch again; dropped when a run starts)
+    float trim_ratio_ = 0.0f;
+    int trim_keep_ = 0;
+    std::vector<int> h_edges_;     // [2][B]: s_first (n when none), s_last (-1)
+    float h_edges_ratio_ = 0.0f;
+    bool have_edges_ = false;
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
     int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)
@@ -314,5 +331,6 @@ class Engine {
 void free_result_impl(mi355vits_result* r);
 void free_packed_impl(mi355vits_packed_result* r);
 void free_alignment_impl(mi355vits_alignment* r);
+void free_edges_impl(mi355vits_edges* r);
 
 }  // namespace m355

@@ -213,8 +213,10 @@ void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, 
 // samples (whole 16-byte stores).  Sample for sample k_pcm16's arithmetic.
 constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes x one 16-byte store
 inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
+// trimmed = true (packs with edge trimming on only): seg = [4][n], the fourth row the first SOURCE sample of the entry — entry i is
+// row seg[n + i]'s samples [seg[3n + i], seg[3n + i] + seg[2n + i]).  false: the three-row table and the instantiation it always had.
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s);
+                       int16_t* out, long total, hipStream_t s, bool trimmed = false);
 // The packed stream in another sample encoding (mi355vits_set_output_encoding; kernels_pack.cpp): the same table, the same
 // destination-major walk, one 16-byte store per lane.  PACK_ENC_ULAW / _ALAW: byte k = the G.711 code of the int16 sample
 // k_pcm16_pack stores there, every other byte the code of sample 0 (0xFF / 0xD5); a lane owns 16 samples.  PACK_ENC_F32: the
@@ -226,7 +228,7 @@ inline size_t pack_capacity_bytes(int enc, long total) {
     return enc == PACK_ENC_S16 ? 2 * pcm_pack_capacity(total) : ((size_t)total * pack_bytes_per_sample(enc) + 15) & ~size_t(15);
 }
 void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
-                         int n, uint8_t* out, long total, hipStream_t s);
+                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed = false);
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 
@@ -264,6 +266,13 @@ void launch_resample(const ResampleFilter& f, const float* coef, const float* x,
 // audio is not read.  At t >= len[b]: 0 frames, 0 samples, start = the end of the covered part, levels 0.
 void launch_align(const int* w_ceil, const int* cum, const int* len, int B, int T, const float* audio, long audio_bs, const int* alen,
                   int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s);
+
+// ---------------------------------------------------------------- the quiet edges of a run's rows (kernels_edges.cpp)
+// audio [B] rows of audio_bs floats with alen [B] valid samples (device), peak_bits [B] the rows' peaks, l_max >= every alen[b].
+// thr = peak * ratio (one f32 multiply); a sample is loud iff fabsf(y) >= thr.  Writes first[b] = the first loud sample of row b (or
+// max(alen[b], 0) when there is none) and last[b] = the last (or -1); both words are initialised here, on s, whatever they held.
+void launch_edges(const float* audio, long audio_bs, const int* alen, const unsigned* peak_bits, int B, long l_max, float ratio,
+                  int* first, int* last, hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

@@ -2333,12 +2333,15 @@ void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, 
 // One valid sample, operation for operation what k_pcm16 does to it (audio_float_to_int16, then audioop.mul): pcm16_quant, pcm_quant.h
 __device__ __forceinline__ unsigned pcm16_pair(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
 
+// TRIM (packs with edge trimming on): the table has a fourth row, the first source sample of each entry
+template <bool TRIM>
 __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
                                                     const double* __restrict__ volumes, const int* __restrict__ seg, int n,
                                                     int16_t* __restrict__ out, long total) {
     const int* s_off = seg;          // first sample of entry i's audio in the stream, ascending
     const int* s_row = seg + n;      // its batch row
     const int* s_len = seg + 2 * n;  // its valid samples
+    const int* s_skip = seg + 3 * n;  // TRIM only: the row's sample the entry starts at
     const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
     // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
     const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
@@ -2371,7 +2374,7 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
         unsigned w0, w1, w2, w3;
         if (le >= 0 && s0 + 8 <= off + len) {
             // all eight samples inside one row's audio: 32 contiguous source bytes, in the widest loads their alignment allows
-            const float* src = audio + (long)row * audio_bs + (s0 - off);
+            const float* src = audio + (long)row * audio_bs + (TRIM ? s_skip[lc] : 0) + (s0 - off);
             const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
             const double volume = volumes ? volumes[row] : 1.0;
             float v0, v1, v2, v3, v4, v5, v6, v7;
@@ -2403,7 +2406,7 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
                 const long o = s_off[cc];
                 const int r = s_row[cc];
                 const bool valid = ce >= 0 && sp < o + s_len[cc];
-                const float a = audio[valid ? (long)r * audio_bs + (sp - o) : 0L];
+                const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
                 const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
                 const double volume = volumes ? volumes[r] : 1.0;
                 q[k] = valid ? pcm16_quant(a, scale, volume) : 0;
@@ -2420,11 +2423,15 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
 }
 
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s) {
+                       int16_t* out, long total, hipStream_t s, bool trimmed) {
     if (total <= 0 || n <= 0) return;
     const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
     const long gx = std::min<long>(nchunks, 8L * current_device_cu_count());  // 8 workgroups of 4 waves per CU: every SIMD full
-    LAUNCH_KERNEL(k_pcm16_pack, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    if (trimmed) {
+        LAUNCH_KERNEL(k_pcm16_pack<true>, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    } else {
+        LAUNCH_KERNEL(k_pcm16_pack<false>, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

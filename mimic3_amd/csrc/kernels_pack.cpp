@@ -25,7 +25,7 @@ __device__ __forceinline__ unsigned pack_quad(unsigned c0, unsigned c1, unsigned
     return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
 }
 
-template <int ENC>
+template <int ENC, bool TRIM>
 __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
                                                   const double* __restrict__ volumes, const int* __restrict__ seg, int n,
                                                   uint8_t* __restrict__ out, long total) {
@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
     const int* s_off = seg;          // first sample of entry i's audio in the stream, ascending
     const int* s_row = seg + n;      // its batch row
     const int* s_len = seg + 2 * n;  // its valid samples
+    const int* s_skip = seg + 3 * n;  // TRIM only (a [4][n] table): the row's sample the entry starts at
     const long nchunks = (total + CHUNK - 1) / CHUNK;
     // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
     const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
         unsigned w[4];
         if (le >= 0 && s0 + S <= off + len) {
             // the lane's samples all inside one row's audio: 4 S contiguous source bytes, in the widest loads their alignment allows
-            const float* src = audio + (long)row * audio_bs + (s0 - off);
+            const float* src = audio + (long)row * audio_bs + (TRIM ? s_skip[lc] : 0) + (s0 - off);
             float v[S];
             const uintptr_t al = reinterpret_cast<uintptr_t>(src);
             if ((al & 15) == 0) {
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
                 const long o = s_off[cc];
                 const int r = s_row[cc];
                 const bool valid = ce >= 0 && sp < o + s_len[cc];
-                const float a = audio[valid ? (long)r * audio_bs + (sp - o) : 0L];
+                const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
                 if constexpr (F32) {
                     c[k] = valid ? __float_as_uint(a) : SILENCE;
                 } else {
@@ -135,21 +136,25 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
 
 template <int ENC>
 static void launch_pack_enc(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                            uint8_t* out, long total, hipStream_t s) {
+                            uint8_t* out, long total, hipStream_t s, bool trimmed) {
     const long chunk = 256L * (ENC == PACK_ENC_F32 ? 4 : 16);
     const long nchunks = (total + chunk - 1) / chunk;
     const long gx = std::min<long>(nchunks, 8L * current_device_cu_count());  // 8 workgroups of 4 waves per CU: every SIMD full
-    LAUNCH_KERNEL(k_pack_enc<ENC>, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    if (trimmed) {
+        LAUNCH_KERNEL((k_pack_enc<ENC, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    } else {
+        LAUNCH_KERNEL((k_pack_enc<ENC, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    }
 }
 
 void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
-                         int n, uint8_t* out, long total, hipStream_t s) {
+                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed) {
     if (total <= 0 || n <= 0) return;
     switch (enc) {
-        case PACK_ENC_ULAW: launch_pack_enc<PACK_ENC_ULAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s); break;
-        case PACK_ENC_ALAW: launch_pack_enc<PACK_ENC_ALAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s); break;
-        case PACK_ENC_F32: launch_pack_enc<PACK_ENC_F32>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s); break;
-        default: launch_pcm16_pack(audio, audio_bs, peak_bits, volumes, seg, n, reinterpret_cast<int16_t*>(out), total, s);
+        case PACK_ENC_ULAW: launch_pack_enc<PACK_ENC_ULAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
+        case PACK_ENC_ALAW: launch_pack_enc<PACK_ENC_ALAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
+        case PACK_ENC_F32: launch_pack_enc<PACK_ENC_F32>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
+        default: launch_pcm16_pack(audio, audio_bs, peak_bits, volumes, seg, n, reinterpret_cast<int16_t*>(out), total, s, trimmed);
     }
 }
 

@@ -200,6 +200,31 @@ int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out) 
     });
 }
 
+int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, const float* peaks, int B, float ratio, int32_t* s_first,
+                        int32_t* s_last) {
+    return guarded(nullptr, [&] {
+        if (!audio || !lens || !peaks || !s_first || !s_last || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        if (!(ratio > 0.0f && ratio <= 1.0f)) throw EngineError(MI355VITS_ERR_INVALID, "ratio must be in (0, 1]");
+        long l_max = 0;
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            l_max = std::max<long>(l_max, lens[b]);
+        }
+        const size_t na = (size_t)B * stride;
+        DevBuf da(na * 4), dl((size_t)B * 4), dp((size_t)B * 4), dout((size_t)B * 8);
+        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dp.p, peaks, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0x5a, (size_t)B * 8));  // the launch initialises its words itself
+        int* d = dout.as<int>();
+        launch_edges(da.as<float>(), stride, dl.as<int>(), dp.as<unsigned>(), B, l_max, ratio, d, d + B, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(s_first, d, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(s_last, d + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern) {
     if (!h) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);

@@ -484,6 +484,17 @@ def _encoding_name(encoding) -> str:
     return encoding.lower()
 
 
+def _trim_ratio(db) -> float:
+    """An edge-trim threshold in dB below a row's peak as the engine's ratio: ``float(np.float32(10 ** (db / 20)))``; ``None`` =
+    off (0.0).  ``db`` must be finite and <= 0, else ``ValueError``."""
+    if db is None:
+        return 0.0
+    db = float(db)
+    if not np.isfinite(db) or db > 0.0:
+        raise ValueError(f"edge trim threshold must be finite and <= 0 dB, not {db!r}")
+    return float(np.float32(10.0 ** (db / 20.0)))
+
+
 def _alignment_levels(alignment) -> bool:
     """``alignment=True`` -> timing only, ``"levels"`` -> peak and rms too; anything else raises ``ValueError``."""
     if alignment is True:
@@ -509,6 +520,13 @@ class InferenceSession:
         self.output_sample_rate: Optional[int] = int(rate) if rate else None
         # the sample encoding of the packed streams (Engine.set_output_encoding); a call's ``encoding=`` goes before it
         self.output_encoding: str = _encoding_name(kwargs.pop("output_encoding", None) or "s16le")
+        # edge trimming of the packed streams (Engine.set_edge_trim): dB below each row's peak, None = off, and the milliseconds
+        # kept around the loud part; a call's ``trim_db=`` / ``trim_keep_ms=`` go before them
+        self.edge_trim_db: Optional[float] = kwargs.pop("edge_trim_db", None)
+        _trim_ratio(self.edge_trim_db)
+        self.edge_trim_keep_ms: float = float(kwargs.pop("edge_trim_keep_ms", 0) or 0)
+        if self.edge_trim_keep_ms < 0:
+            raise ValueError("edge_trim_keep_ms must be >= 0")
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -617,7 +635,7 @@ class InferenceSession:
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-                   alignment=False) -> "_native.PackedAudio":
+                   alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -629,7 +647,14 @@ class InferenceSession:
         ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher.
         ``alignment`` (``True`` / ``"levels"``): sets ``PackedAudio.alignment`` (default ``None``) in STREAM coordinates — row i
         belongs to entry i and ``offsets[i]`` is added to ``start``, so ``data[start[i, t] : start[i, t] + samples[i, t]]`` is
-        phoneme t of entry i in any encoding."""
+        phoneme t of entry i in any encoding.
+        ``trim_db`` (else the session's ``edge_trim_db``; ``None`` = off): each entry is its row cut to the part from the first to
+        the last sample at or above ``peak * float32(10 ** (trim_db / 20))`` (``Engine.set_edge_trim``; finite and <= 0, else
+        ``ValueError``) with ``int(trim_keep_ms / 1000 * rate)`` samples (else the session's ``edge_trim_keep_ms``) kept on each
+        side, so ``lead_ms`` is the pause that is heard; ``PackedAudio.first`` / ``.end`` say what was kept.  The alignment of a
+        trimmed stream follows the cut: a span is clipped to the entry (a phoneme wholly cut has ``samples`` = 0), the spans
+        still tile the entry and sum to ``lengths[i]``; ``frames`` stay the run's own, and ``peak`` / ``rms`` stay those of the
+        UNTRIMMED span."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -643,14 +668,25 @@ class InferenceSession:
         keys = kw.pop("utterance_keys", None)
         if alignment:
             kw["_alignment"] = _alignment_levels(alignment)
+        ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
+        keep_ms = float(trim_keep_ms if trim_keep_ms is not None else self.edge_trim_keep_ms)
+        if keep_ms < 0:
+            raise ValueError("trim_keep_ms must be >= 0")
+        kw["_trim"] = (ratio, int((keep_ms / 1000.0) * rate))
         out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
                                lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
         if alignment:
             out, al = out
             rows = np.arange(len(out.offsets)) if order is None else np.asarray(order, np.int64).reshape(-1)
             pick = lambda a: None if a is None else a[rows]  # noqa: E731
-            out.alignment = _native.Alignment(al.frames[rows], al.start[rows].astype(np.int64) + np.asarray(out.offsets, np.int64)[:, None],
-                                              al.samples[rows], pick(al.peak), pick(al.rms), al.sample_rate)
+            start, samples = al.start[rows].astype(np.int64), al.samples[rows].astype(np.int64)
+            if out.first is not None:  # a trimmed stream: the spans follow the cut, clipped to the entry
+                first = np.asarray(out.first, np.int64)[:, None]
+                n = np.asarray(out.lengths, np.int64)[:, None]
+                s0, s1 = np.clip(start - first, 0, n), np.clip(start + samples - first, 0, n)
+                start, samples = s0, s1 - s0
+            out.alignment = _native.Alignment(al.frames[rows], start + np.asarray(out.offsets, np.int64)[:, None],
+                                              samples.astype(al.samples.dtype), pick(al.peak), pick(al.rms), al.sample_rate)
         self.last_lengths = out.lengths
         return out
 
@@ -713,7 +749,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, **kw):
+                    _alignment=None, _trim=None, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -730,6 +766,7 @@ class InferenceSession:
             eng.set_output_rate(sample_rate if sample_rate is not None else self.output_sample_rate)
             if _packed:  # the encoding concerns packed streams only; read by the engine when the pack is planned
                 eng.set_output_encoding(encoding or self.output_encoding)
+                eng.set_edge_trim(*(_trim or (0.0, 0)))  # likewise; set on every call: back to off for a call that does not ask
             call = eng.run_packed if _packed else eng.run
             out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
             return out if _alignment is None else (out, eng.fetch_alignment(levels=_alignment))
