@@ -410,6 +410,62 @@ typedef struct mi355vits_edges {
 int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out);
 void mi355vits_free_edges(mi355vits_edges* r);
 
+/* ---- Equal loudness across a request: ITU-R BS.1770-4 / EBU R128 integrated loudness of every row, and a target gain in the packed
+ * streams.  The int16 conversion scales every sentence so that its largest sample is 32767 (audio_float_to_int16): a two-word
+ * interjection and a forty-word sentence get the same peak and very different loudness, and one plosive sets the level of its whole
+ * sentence.  With a loudness target each entry of a packed stream is scaled to the target instead, from the float waveform, before any
+ * quantisation.  Each row is measured alone, mono: its n valid samples x[0..n) at the run's rate fs (the MI355VITS_WANT_FLOAT samples;
+ * pcm_volume does not apply), all arithmetic IEEE double:
+ *     K-weighting: two biquads in cascade, zero state at sample 0, coefficients by the bilinear derivation for any fs —
+ *       shelf:     f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *                  Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0,
+ *                  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *       high pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 likewise; b = [1, -2, 1], a as above
+ *       (at 48 kHz the table of BS.1770)
+ *     S = (fs + 5) / 10 (integer): the 100 ms step;  E_j = sum of y[k]^2 over step j of the filtered row
+ *     z_i = (E_i + E_{i+1} + E_{i+2} + E_{i+3}) / (4 S) for i = 0 .. nb - 1, nb = (n - 4 S) / S + 1: whole 400 ms blocks only;
+ *       a row with 0 < n < 4 S is one block over all of it, z_0 = sum y^2 / n, nb = 1; n = 0: nb = 0
+ *     l_i = -0.691 + 10 log10(z_i);  absolute gate l_i > -70;  relative gate l_i > -0.691 + 10 log10(mean z over the absolutely gated) - 10
+ *     lufs = -0.691 + 10 log10(mean z over the blocks passing both), -inf when no block passes the absolute gate
+ *     gain: g = 10^((target - lufs) / 20) (1.0 when lufs = -inf), cap = 10^(ceiling / 20) / peak (none when the peak is 0),
+ *       gain = min(g, cap), limited = cap < g.  No limiter and no compressor: the ceiling only bounds the gain.
+ *  - mi355vits_set_loudness_target: target_lufs = 0 (the default): off — nothing below is launched or laid out by a pack, every byte is
+ *    what it was.  On: -70 <= target_lufs < 0 with a finite ceiling_dbfs <= 0; anything else, NaN included: MI355VITS_ERR_INVALID, the
+ *    message names the value, the setting stays.  mi355vits_clone inherits it.  Read when a pack is made and at each
+ *    mi355vits_fetch_loudness (as the encoding and the edge trimming are): one synthesis can be packed at several targets and
+ *    un-normalised with no synthesis work repeated.
+ *  - Scope: the samples of the packed streams only.  mi355vits_run / _run_rows / _fetch / _device_result, the padded audio / pcm,
+ *    lengths, peaks, mi355vits_fetch_alignment and mi355vits_fetch_edges never move.  In a packed stream the row's factor becomes
+ *    scale = (float)(32767.0 * gain) in place of 32767.0f / fmaxf(0.01f, peak); the clamp, the truncation, pcm_volume and G.711 behind
+ *    it are unchanged; MI355VITS_ENC_F32LE writes x[k] * (float)gain.  peaks[i] stays the row's float peak.  The whole row is measured
+ *    whatever the edge trimming: a trimmed entry is bitwise [first, end) of the untrimmed entry at the same target.
+ *  - Synchronisation: the scales depend on the audio.  mi355vits_run_packed with a target synchronises three times instead of twice
+ *    (frame counts, measurement, result) — also with edge trimming on: both measurements go before the same synchronisation —,
+ *    mi355vits_fetch_packed twice.  The measurement of the last run is kept on the host: a repeated fetch at any target launches
+ *    nothing; a run drops it.
+ *  - mi355vits_fetch_loudness serves the LAST COMPLETED RUN whatever its flags were, at the rate it ran at; with the target off it
+ *    still measures (gain = 0.0, limited = 0).  It works in an arena of its own: what the other fetches serve afterwards is what they
+ *    served before.  Before any completed run: MI355VITS_ERR_INVALID with "fetch_loudness: no completed run on this handle"; a NULL
+ *    out: MI355VITS_ERR_INVALID.  The measure is offered from 4000 Hz up: a run at a lower output rate is MI355VITS_ERR_INVALID here
+ *    and in a pack with a target.
+ *  - With profiling enabled the two launches are reported as "loudness": bytes = 4 * sum(lengths) + 8 * sum(steps) + 16 * B. */
+int mi355vits_set_loudness_target(mi355vits_handle h, float target_lufs, float ceiling_dbfs);
+int mi355vits_get_loudness_target(mi355vits_handle h, float* target_lufs, float* ceiling_dbfs);
+
+typedef struct mi355vits_loudness {
+    int32_t batch, sample_rate;          /* of the run served */
+    float target_lufs, ceiling_dbfs;     /* the setting the arrays were made with; target 0 = off */
+    double* lufs;       /* [B] integrated loudness; -inf when no block passes the absolute gate */
+    double* gain;       /* [B] linear gain applied in packed streams; 0.0 when off */
+    int32_t* blocks;    /* [B] */
+    int32_t* gated;     /* [B] */
+    int32_t* limited;   /* [B] 1 where the ceiling bounded the gain */
+    void* owner_;
+} mi355vits_loudness;
+
+int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out);
+void mi355vits_free_loudness(mi355vits_loudness* r);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

@@ -75,6 +75,14 @@ int mi355vits_test_alignment(int device, int B, int T, const int32_t* frames, co
  * never looked at. */
 int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, const float* peaks, int B, float ratio, int32_t* s_first,
                         int32_t* s_last);
+/* Kernel unit-test hook: the loudness kernels (k_loud, k_loud_gate; mi355vits_set_loudness_target) alone over host arrays on the
+ * current device.  audio [B] rows of `stride` floats, lens [B] (0 <= lens[b] <= stride) valid samples at `rate` Hz (>= 4000).  Writes
+ * lufs / blocks / gated [B] as mi355vits_fetch_loudness defines them.  What lies behind a row is never looked at. */
+int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens, int B, int32_t rate, double* lufs, int32_t* blocks,
+                           int32_t* gated);
+/* How k_loud cuts a row at `rate`: *step = S, the 100 ms step; *warmup = W(rate), the samples an item that starts inside a row runs
+ * before it counts; *steps_per_item = K (a work item is K * S samples of one row).  Host arithmetic only: no kernel runs. */
+int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, int32_t* steps_per_item);
 /* Kernel unit-test hook: the G.711 encoders of the encoded packed streams (mi355vits_set_output_encoding) over an array on the
  * current device.  law = MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW; out[i] = the code of in[i].  65,536 inputs cover the function. */
 int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);

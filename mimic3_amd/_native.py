@@ -39,12 +39,14 @@ EXPORTED_SYMBOLS = (
     "mi355vits_set_output_encoding", "mi355vits_get_output_encoding",
     "mi355vits_fetch_alignment", "mi355vits_free_alignment",
     "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
+    "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
+    "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan",
 )
 
 
@@ -145,6 +147,33 @@ class EdgesResult(ctypes.Structure):
         ("end", ctypes.POINTER(ctypes.c_int32)),
         ("owner_", ctypes.c_void_p),
     ]
+
+
+class LoudnessResult(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("sample_rate", ctypes.c_int32),
+        ("target_lufs", ctypes.c_float),
+        ("ceiling_dbfs", ctypes.c_float),
+        ("lufs", ctypes.POINTER(ctypes.c_double)),
+        ("gain", ctypes.POINTER(ctypes.c_double)),
+        ("blocks", ctypes.POINTER(ctypes.c_int32)),
+        ("gated", ctypes.POINTER(ctypes.c_int32)),
+        ("limited", ctypes.POINTER(ctypes.c_int32)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class Loudness:
+    """ITU-R BS.1770-4 integrated loudness of every row of a run (``mi355vits_fetch_loudness``): ``lufs`` [B] float64 (``-inf``
+    where no block passes the absolute gate), ``blocks`` / ``gated`` [B] the 400 ms blocks of the row and those passing both
+    gates, and under the setting ``target_lufs`` / ``ceiling_dbfs`` (target 0.0: off) the linear ``gain`` [B] a packed stream
+    applies (0.0 when off) and ``limited`` [B] bool where the ceiling bounded it.  ``sample_rate`` is the rate the run ran at.
+    The arrays are copies owned by Python."""
+
+    def __init__(self, lufs, gain, blocks, gated, limited, target_lufs, ceiling_dbfs, sample_rate):
+        self.lufs, self.gain, self.blocks, self.gated, self.limited = lufs, gain, blocks, gated, limited
+        self.target_lufs, self.ceiling_dbfs, self.sample_rate = target_lufs, ceiling_dbfs, sample_rate
 
 
 class Edges:
@@ -251,6 +280,11 @@ class NativeLibrary:
         L.mi355vits_fetch_edges.argtypes = [H, ctypes.POINTER(EdgesResult)]
         L.mi355vits_free_edges.argtypes = [ctypes.POINTER(EdgesResult)]
         L.mi355vits_free_edges.restype = None
+        L.mi355vits_set_loudness_target.argtypes = [H, ctypes.c_float, ctypes.c_float]
+        L.mi355vits_get_loudness_target.argtypes = [H, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        L.mi355vits_fetch_loudness.argtypes = [H, ctypes.POINTER(LoudnessResult)]
+        L.mi355vits_free_loudness.argtypes = [ctypes.POINTER(LoudnessResult)]
+        L.mi355vits_free_loudness.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -290,6 +324,8 @@ class NativeLibrary:
             L.mi355vits_lab_g711_encode.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_long, ctypes.POINTER(ctypes.c_uint8)]
             i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
             L.mi355vits_lab_edges.argtypes = [f32p, ctypes.c_long, i32p, f32p, ctypes.c_int, ctypes.c_float, i32p, i32p]
+            L.mi355vits_lab_loudness.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), i32p, i32p]
+            L.mi355vits_lab_loudness_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p]
             L.mi355vits_test_alignment.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int64, f32p, i32p,
                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
@@ -339,6 +375,35 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return first, last
+
+    def lab_loudness(self, audio, lengths, rate):
+        """The loudness kernels (k_loud, k_loud_gate) alone: audio [B, stride] f32 with lengths [B] valid samples each at ``rate`` Hz
+        (what lies behind them is never looked at) -> (lufs float64 [B], blocks int32 [B], gated int32 [B]) as
+        ``mi355vits_fetch_loudness`` defines them."""
+        self._need_hooks()
+        au = np.ascontiguousarray(audio, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        if au.ndim != 2 or ln.shape[0] != au.shape[0]:
+            raise ValueError("audio [B, stride], lengths [B]")
+        B = au.shape[0]
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        lufs, blocks, gated = np.zeros(B, np.float64), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        rc = self.lib.mi355vits_lab_loudness(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, int(rate),
+                                             lufs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), blocks.ctypes.data_as(i32p),
+                                             gated.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return lufs, blocks, gated
+
+    def lab_loudness_plan(self, rate):
+        """How k_loud cuts a row at ``rate`` Hz: ``(S, W, K)`` — the 100 ms step, the warm-up samples of a work item that starts
+        inside a row, and the steps of a work item (an item is ``K * S`` samples of one row).  Host arithmetic only."""
+        self._need_hooks()
+        s, w, k = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        rc = self.lib.mi355vits_lab_loudness_plan(int(rate), ctypes.byref(s), ctypes.byref(w), ctypes.byref(k))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return int(s.value), int(w.value), int(k.value)
 
     def test_conv1d(self, x, w, bias=None, res=None, dilation=1, impl=1, in_len=None, out_len=None, in_slope=1.0,
                     relu=False, out_scale=1.0, res_sub=False, accumulate_into=None, device=0) -> np.ndarray:
@@ -561,10 +626,14 @@ class PackedAudio:
     ``data[offsets[i] : offsets[i] + lengths[i]]`` (no copies), ``wav`` the whole file (header + data) as a memoryview, or None
     when no header was asked for; ``offsets`` / ``lengths`` / ``peaks`` [n] per entry, in samples.  ``pcm`` is ``data`` of an
     int16 stream, and raises for any other encoding.  With edge trimming on (``Engine.set_edge_trim``) entry i is samples
-    ``first[i] : end[i]`` of its row (``lengths[i] = end[i] - first[i]``); both are ``None`` when trimming is off."""
+    ``first[i] : end[i]`` of its row (``lengths[i] = end[i] - first[i]``); both are ``None`` when trimming is off.  With a loudness
+    target (``Engine.set_loudness_target``) ``lufs[i]`` is the entry's row's integrated loudness, ``gain[i]`` the linear gain its
+    samples carry and ``limited[i]`` whether the ceiling bounded it; all three are ``None`` when the target is off."""
 
-    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le", first=None, end=None):
+    def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le", first=None, end=None, lufs=None,
+                 gain=None, limited=None):
         self.first, self.end = first, end
+        self.lufs, self.gain, self.limited = lufs, gain, limited
         self.alignment: Optional[Alignment] = None  # set by InferenceSession.run_packed(alignment=...): spans in stream samples
         self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
         self.encoding = encoding
@@ -753,13 +822,14 @@ class Engine:
             p.n = a.batch
         enc = self.output_encoding  # read by the library when the call starts; only this thread sets it meanwhile
         trimmed = self.edge_trim[0] != 0.0  # likewise
+        normalised = self.loudness_target[0] != 0.0
         r = PackedResult()
         self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                          None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del keep, pkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate
-        return self._take_packed(r, bool(wav), enc, order if trimmed else None, trimmed)
+        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised)
 
     def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
         """Pack the last completed run of this handle again (``mi355vits_fetch_packed``): that run's rows and per-row volumes,
@@ -769,12 +839,14 @@ class Engine:
             p.n = self._last_batch  # every row of the last run (0 before the first: the library names the error)
         enc = self.output_encoding
         trimmed = self.edge_trim[0] != 0.0
+        normalised = self.loudness_target[0] != 0.0
         r = PackedResult()
         self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del pkeep
-        return self._take_packed(r, bool(wav), enc, order if trimmed else None, trimmed)
+        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised)
 
-    def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le", order=None, trimmed: bool = False) -> PackedAudio:
+    def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le", order=None, trimmed: bool = False,
+                     normalised: bool = False) -> PackedAudio:
         n = int(r.n)
         try:
             offsets = np.ctypeslib.as_array(r.offsets, shape=(n,)).copy()
@@ -796,7 +868,42 @@ class Engine:
             e = self.fetch_edges()
             rows = np.arange(n) if order is None else np.asarray(order, np.int64).reshape(-1)
             first, end = e.first[rows], e.end[rows]
-        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc, first, end)
+        lufs = gain = limited = None
+        if normalised:
+            # the measurement the pack was scaled with: the library holds it on the host, nothing is launched
+            ld = self.fetch_loudness()
+            rows = np.arange(n) if order is None else np.asarray(order, np.int64).reshape(-1)
+            lufs, gain, limited = ld.lufs[rows], ld.gain[rows], ld.limited[rows]
+        return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc, first, end, lufs,
+                           gain, limited)
+
+    def set_loudness_target(self, lufs, ceiling_db: float = -1.0) -> None:
+        """Scale each entry of the packed streams made after this to ``lufs`` LUFS of ITU-R BS.1770-4 integrated loudness
+        (``mi355vits_set_loudness_target``): ``gain = min(10 ** ((lufs - measured) / 20), 10 ** (ceiling_db / 20) / peak)`` takes
+        the place of the peak normalisation of the int16 conversion (``"f32le"``: one multiply).  ``None`` / 0 (the default) =
+        off; on: -70 <= lufs < 0 with a finite ``ceiling_db`` <= 0 — anything else raises and leaves the setting as it was.  Read by
+        ``run_packed``, each ``fetch_packed`` and each ``fetch_loudness``; everything else is unchanged by it."""
+        self._check(self.native.lib.mi355vits_set_loudness_target(self._h, float(lufs or 0.0), float(ceiling_db)))
+
+    @property
+    def loudness_target(self):
+        """``(target_lufs, ceiling_db)`` of ``set_loudness_target``; target 0.0 = off."""
+        t, c = ctypes.c_float(), ctypes.c_float()
+        self._check(self.native.lib.mi355vits_get_loudness_target(self._h, ctypes.byref(t), ctypes.byref(c)))
+        return float(t.value), float(c.value)
+
+    def fetch_loudness(self) -> Loudness:
+        """The integrated loudness of every row of the last completed run, and the gains of the current ``set_loudness_target``
+        setting (``mi355vits_fetch_loudness``), whatever the run's flags were, at the rate it ran at."""
+        r = LoudnessResult()
+        self._check(self.native.lib.mi355vits_fetch_loudness(self._h, ctypes.byref(r)))
+        try:
+            B = int(r.batch)
+            take = lambda p: np.ctypeslib.as_array(p, shape=(B,)).copy()  # noqa: E731
+            return Loudness(take(r.lufs), take(r.gain), take(r.blocks), take(r.gated), take(r.limited).astype(bool),
+                            float(r.target_lufs), float(r.ceiling_dbfs), int(r.sample_rate))
+        finally:
+            self.native.lib.mi355vits_free_loudness(ctypes.byref(r))
 
     def set_edge_trim(self, ratio, keep_samples: int = 0) -> None:
         """Trim each entry's quiet edges in the packed streams made after this (``mi355vits_set_edge_trim``): a sample is loud iff

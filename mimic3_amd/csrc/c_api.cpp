@@ -215,6 +215,31 @@ int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out) {
 
 void mi355vits_free_edges(mi355vits_edges* r) { free_edges_impl(r); }
 
+int mi355vits_set_loudness_target(mi355vits_handle h, float target_lufs, float ceiling_dbfs) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_loudness_target(target_lufs, ceiling_dbfs); });
+}
+
+int mi355vits_get_loudness_target(mi355vits_handle h, float* target_lufs, float* ceiling_dbfs) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    if (target_lufs) *target_lufs = h->eng->loudness_target();
+    if (ceiling_dbfs) *ceiling_dbfs = h->eng->loudness_ceiling();
+    return MI355VITS_OK;
+}
+
+int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    int rc = guarded(h, [&] { h->eng->fetch_loudness(out); });
+    if (rc != MI355VITS_OK && out) mi355vits_free_loudness(out);
+    return rc;
+}
+
+void mi355vits_free_loudness(mi355vits_loudness* r) { free_loudness_impl(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

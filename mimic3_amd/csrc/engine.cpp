@@ -397,6 +397,8 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         enc_ = lane0.enc_;
         trim_ratio_ = lane0.trim_ratio_;
         trim_keep_ = lane0.trim_keep_;
+        loud_target_ = lane0.loud_target_;
+        loud_ceiling_ = lane0.loud_ceiling_;
     } catch (...) {
         release();
         throw;
@@ -688,6 +690,7 @@ void Engine::fill_workspace(uint32_t pattern) {
     arena_p_.fill(pattern, stream_);
     arena_al_.fill(pattern, stream_);
     arena_ed_.fill(pattern, stream_);
+    arena_ld_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1654,6 +1657,11 @@ struct Engine::PackPlan {
     int keep = 0;
     std::vector<int> skip;
     bool trimmed() const { return ratio != 0.0f; }
+    // the handle's loudness target when the pack was planned (0 = off); with it on, place_pack fills gain: each entry's linear gain
+    float target = 0.0f, ceiling = 0.0f;
+    std::vector<double> gain;
+    bool normalised() const { return target != 0.0f; }
+    int seg_rows() const { return 3 + (trimmed() ? 1 : 0) + (normalised() ? 1 : 0); }
     int bps() const { return pack_bytes_per_sample(enc); }
     size_t header_bytes() const { return !wav ? 0 : enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
 };
@@ -1722,6 +1730,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     HIP_CHECK(hipSetDevice(device_));
     have_result_ = false;
     have_edges_ = false;
+    have_loud_ = false;
     taps_on_ = (args.flags & MI355VITS_DEBUG_TAPS) != 0;
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();
@@ -1948,6 +1957,8 @@ void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) c
     plan.enc = enc_;  // the setting is read here: when a pack is made
     plan.ratio = trim_ratio_;  // likewise
     plan.keep = trim_keep_;
+    plan.target = loud_target_;
+    plan.ceiling = loud_ceiling_;
     plan.tail = pack ? pack->tail_samples : 0;
     plan.order.resize(plan.n);
     plan.lead.assign(plan.n, 0);
@@ -1977,6 +1988,7 @@ void Engine::place_pack(PackPlan& plan) const {
     plan.offsets.resize(plan.n);
     plan.lengths.resize(plan.n);
     plan.skip.assign(plan.trimmed() ? plan.n : 0, 0);
+    plan.gain.assign(plan.normalised() ? plan.n : 0, 0.0);
     int64_t pos = 0;
     plan.audio = 0;
     for (int i = 0; i < plan.n; ++i) {
@@ -1990,6 +2002,11 @@ void Engine::place_pack(PackPlan& plan) const {
             const int64_t end = std::min<int64_t>(n, (int64_t)h_edges_[B_ + row] + 1 + plan.keep);
             plan.skip[i] = (int)std::min(first, n);
             plan.lengths[i] = std::max<int64_t>(0, end - plan.skip[i]);  // (a row without a loud sample — a NaN peak — keeps nothing)
+        }
+        if (plan.normalised()) {
+            const int row = plan.order[i];
+            bool limited;
+            loudness_gain(h_loud_[row], h_loud_peaks_[row], plan.target, plan.ceiling, &plan.gain[i], &limited);
         }
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
@@ -2005,18 +2022,23 @@ void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
         seg[plan.n + i] = plan.order[i];
         seg[2 * plan.n + i] = (int)plan.lengths[i];
         if (plan.trimmed()) seg[3 * plan.n + i] = plan.skip[i];
+        if (plan.normalised()) {
+            // the entry's f32 scale: 32767 * gain in double, rounded once (F32LE: the gain itself)
+            const float scale = plan.enc == PACK_ENC_F32 ? (float)plan.gain[i] : (float)(32767.0 * plan.gain[i]);
+            memcpy(&seg[(plan.trimmed() ? 4 : 3) * plan.n + i], &scale, 4);
+        }
     }
 }
 
 void Engine::launch_pack(const PackPlan& plan) {
     if (plan.enc == PACK_ENC_S16) {
         ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
-        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_, plan.trimmed());
+        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_, plan.trimmed(), plan.normalised());
         return;
     }
     const char* label = plan.enc == PACK_ENC_ULAW ? "pack.ulaw" : plan.enc == PACK_ENC_ALAW ? "pack.alaw" : "pack.f32";
     ProfScope ps(prof_, label, 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
-    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_, plan.trimmed());
+    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_, plan.trimmed(), plan.normalised());
 }
 
 void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
@@ -2100,14 +2122,14 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     PackPlan plan;
     plan_pack(pack, args.batch, plan);
-    if (!plan.trimmed()) {
+    if (!plan.trimmed() && !plan.normalised()) {
         synthesize(args, rows, &plan);
         copy_out_packed(plan, out);
         return;
     }
-    // Trimming on: the offsets depend on the audio.  Synthesise without an early pack table (and without the padded int16 pass: a
-    // packed call looks at no MI355VITS_WANT_* flag), find the edges (k_edges, 8 B bytes, one synchronisation), then what
-    // fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
+    // Trimming or a loudness target on: the offsets / the scales depend on the audio.  Synthesise without an early pack table (and
+    // without the padded int16 pass: a packed call looks at no MI355VITS_WANT_* flag), measure (k_edges and / or k_loud, their
+    // copies, ONE synchronisation), then what fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
     mi355vits_run_args a = args;
     a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
     synthesize(a, rows, nullptr);
@@ -2131,11 +2153,11 @@ void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_resu
 
 void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipSetDevice(device_));
-    if (plan.trimmed()) find_edges(plan.ratio);
+    measure_last_run(plan.ratio, plan.normalised());
     place_pack(plan);
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
-    const int seg_rows = plan.trimmed() ? 4 : 3;
+    const int seg_rows = plan.seg_rows();
     ArenaCount need;
     layout_pack(need, plan.n, plan.total, plan.enc, seg_rows);
     if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
@@ -2230,7 +2252,14 @@ void Engine::set_edge_trim(float ratio, int keep_samples) {
 // The raw first / last loud sample of every row of the last run at `ratio` into h_edges_: one launch in an arena of its own, one
 // 8 B byte copy, one synchronisation — or nothing when the host still holds them for this ratio.
 void Engine::find_edges(float ratio) {
-    if (have_edges_ && h_edges_ratio_ == ratio) return;
+    if (!enqueue_edges(ratio)) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    have_edges_ = true;
+}
+
+bool Engine::enqueue_edges(float ratio) {
+    if (have_edges_ && h_edges_ratio_ == ratio) return false;
+    have_edges_ = false;
     const int B = B_;
     arena_ed_.reserve(2 * (size_t)B * 4 + 4096, stream_);
     arena_ed_.reset();
@@ -2243,9 +2272,122 @@ void Engine::find_edges(float ratio) {
     }
     h_edges_.resize(2 * (size_t)B);
     HIP_CHECK(hipMemcpyAsync(h_edges_.data(), d, 2 * (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
     h_edges_ratio_ = ratio;
-    have_edges_ = true;
+    return true;  // have_edges_ once the caller has synchronised
+}
+
+// What a pack needs from the audio before it can be placed: the edges at `ratio` (0: none) and / or the loudness, each launched
+// only when the host does not hold it, behind ONE synchronisation.
+void Engine::measure_last_run(float ratio, bool loud) {
+    const bool e = ratio != 0.0f && enqueue_edges(ratio);
+    const bool l = loud && enqueue_loudness();
+    if (!e && !l) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (e) have_edges_ = true;
+    if (l) have_loud_ = true;
+}
+
+// ---------------------------------------------------------------- BS.1770 loudness of a run's rows (mi355vits_set_loudness_target / _fetch_loudness)
+void Engine::set_loudness_target(float target_lufs, float ceiling_dbfs) {
+    if (!(target_lufs == 0.0f || (target_lufs >= -70.0f && target_lufs < 0.0f)))  // NaN fails all
+        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_target: target " + std::to_string(target_lufs) + " LUFS is neither 0 (off) nor in [-70, 0)");
+    if (target_lufs != 0.0f && !(std::isfinite(ceiling_dbfs) && ceiling_dbfs <= 0.0f))
+        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_target: ceiling " + std::to_string(ceiling_dbfs) + " dBFS is not a finite value <= 0");
+    loud_target_ = target_lufs;
+    if (target_lufs != 0.0f) loud_ceiling_ = ceiling_dbfs;
+}
+
+// The gain rule, in double: g = 10^((T - lufs) / 20) (1 for a row without a gated block), bounded by 10^(c / 20) / peak.
+void Engine::loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited) {
+    const double g = std::isinf(lufs) ? 1.0 : std::pow(10.0, ((double)target - lufs) / 20.0);
+    const double p = (double)peak;
+    *gain = g;
+    *limited = false;
+    if (p != 0.0) {
+        const double cap = std::pow(10.0, (double)ceiling / 20.0) / p;
+        if (cap < g) {
+            *gain = cap;
+            *limited = true;
+        }
+    }
+}
+
+// k_loud / k_loud_gate over the last run's rows in an arena of their own, and the copy of 16 B bytes + the peaks; nothing when the
+// host still holds them.
+bool Engine::enqueue_loudness() {
+    if (have_loud_) return false;
+    const int B = B_;
+    LoudnessPlan lp;
+    if (!loudness_plan(run_hz_, lp))
+        throw EngineError(MI355VITS_ERR_INVALID, "loudness: K-weighting is not offered below " + std::to_string(LOUD_MIN_HZ) + " Hz (the run's rate is " + std::to_string(run_hz_) + " Hz)");
+    long l_max = 0;
+    double audio = 0, steps = 0;
+    for (int b = 0; b < B; ++b) {
+        l_max = std::max<long>(l_max, h_olen_[b]);
+        audio += (double)h_olen_[b];
+        steps += (double)loudness_steps(h_olen_[b], lp.S);
+    }
+    const size_t ldE = (size_t)std::max<long>(1, loudness_steps(l_max, lp.S));
+    arena_ld_.reserve(16 * (size_t)B + 8 * (size_t)B * ldE + 4096, stream_);
+    arena_ld_.reset();
+    double* d = arena_ld_.alloc<double>(2 * (size_t)B);
+    double* dE = arena_ld_.alloc<double>((size_t)B * ldE);
+    int* d_blocks = reinterpret_cast<int*>(d + B);
+    {
+        ProfScope ps(prof_, "loudness", 0, 4.0 * audio + 8.0 * steps + 16.0 * (double)B);
+        launch_loudness(run_hz_, o_audio_, Lo_, o_alen_, B, l_max, dE, (long)ldE, d, d_blocks, d_blocks + B, stream_);
+    }
+    h_loud_.resize(2 * (size_t)B);
+    h_loud_peaks_.resize((size_t)B);
+    HIP_CHECK(hipMemcpyAsync(h_loud_.data(), d, 16 * (size_t)B, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(h_loud_peaks_.data(), o_peaks_, 4 * (size_t)B, hipMemcpyDeviceToHost, stream_));
+    return true;  // have_loud_ once the caller has synchronised
+}
+
+namespace {
+struct LoudnessOwner {
+    void* block = nullptr;
+    size_t cap = 0;
+};
+}  // namespace
+
+void Engine::fetch_loudness(mi355vits_loudness* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_loudness: result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_loudness: no completed run on this handle");
+    HIP_CHECK(hipSetDevice(device_));
+    const float target = loud_target_, ceiling = loud_ceiling_;
+    measure_last_run(0.0f, true);
+    const size_t B = (size_t)B_;
+    auto* own = new LoudnessOwner();
+    out->owner_ = own;
+    own->block = PinnedPool::get().take(28 * B + 16, &own->cap);  // lufs, gain: doubles; blocks, gated, limited: int32
+    out->batch = B_;
+    out->sample_rate = run_hz_;
+    out->target_lufs = target;
+    out->ceiling_dbfs = ceiling;
+    out->lufs = static_cast<double*>(own->block);
+    out->gain = out->lufs + B;
+    out->blocks = reinterpret_cast<int32_t*>(out->gain + B);
+    out->gated = out->blocks + B;
+    out->limited = out->gated + B;
+    memcpy(out->lufs, h_loud_.data(), 8 * B);
+    memcpy(out->blocks, h_loud_.data() + B, 8 * B);  // blocks, then gated
+    for (size_t b = 0; b < B; ++b) {
+        double g = 0.0;
+        bool lim = false;
+        if (target != 0.0f) loudness_gain(out->lufs[b], h_loud_peaks_[b], target, ceiling, &g, &lim);
+        out->gain[b] = g;
+        out->limited[b] = lim ? 1 : 0;
+    }
+}
+
+void free_loudness_impl(mi355vits_loudness* r) {
+    if (!r || !r->owner_) return;
+    auto* own = static_cast<LoudnessOwner*>(r->owner_);
+    PinnedPool::get().give(own->block, own->cap);
+    delete own;
+    memset(r, 0, sizeof(*r));
 }
 
 namespace {

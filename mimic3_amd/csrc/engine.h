@@ -177,6 +177,13 @@ class Engine {
     int edge_trim_keep() const { return trim_keep_; }
     // first / end of every row of the last completed run under the current setting (mi355vits_fetch_edges)
     void fetch_edges(mi355vits_edges* out);
+    // loudness target of the packed streams (mi355vits_set_loudness_target): target 0 = off.  Read when a pack is made and at
+    // fetch_loudness.
+    void set_loudness_target(float target_lufs, float ceiling_dbfs);
+    float loudness_target() const { return loud_target_; }
+    float loudness_ceiling() const { return loud_ceiling_; }
+    // BS.1770 integrated loudness of every row of the last completed run, and the gains of the current setting (mi355vits_fetch_loudness)
+    void fetch_loudness(mi355vits_loudness* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -227,7 +234,7 @@ class Engine {
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
-    // continues layout_b in packed calls, and only there; seg_rows: 3, or 4 in a trimmed pack
+    // continues layout_b in packed calls, and only there; seg_rows: 3, + 1 in a trimmed pack, + 1 in a normalised one
     template <typename A> void layout_pack(A& ar, size_t n, size_t samples, int enc, int seg_rows = 3);
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
@@ -241,6 +248,10 @@ class Engine {
     void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
     void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
+    bool enqueue_edges(float ratio);  // k_edges and its copy on the stream unless the host holds the edges of `ratio`; true: a synchronisation is owed
+    bool enqueue_loudness();          // k_loud / k_loud_gate and their copy likewise (throws below LOUD_MIN_HZ)
+    void measure_last_run(float ratio, bool loud);  // what a pack needs from the audio: both launches, then ONE synchronisation (or none)
+    static void loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited);
 
     mi355vits_config cfg_{};
     int device_ = 0;
@@ -266,6 +277,7 @@ class Engine {
     DeviceArena arena_p_;  // mi355vits_fetch_packed only: the packed stream of a run whose frame-side arena has no room left for it
     DeviceArena arena_al_;  // mi355vits_fetch_alignment only: its five arrays, outside everything a run or a fetch lays out
     DeviceArena arena_ed_;  // k_edges' two words per row, likewise
+    DeviceArena arena_ld_;  // k_loud's step energies and k_loud_gate's 16 bytes per row, likewise
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -308,6 +320,12 @@ class Engine {
     std::vector<int> h_edges_;     // [2][B]: s_first (n when none), s_last (-1)
     float h_edges_ratio_ = 0.0f;
     bool have_edges_ = false;
+    // loudness (mi355vits_set_loudness_target): the setting, and the last run's raw measurement (lufs [B] doubles, blocks [B],
+    // gated [B]) with its peaks, kept on the host so that a fetch at any target launches nothing; dropped when a run starts
+    float loud_target_ = 0.0f, loud_ceiling_ = -1.0f;
+    std::vector<double> h_loud_;  // 2 B doubles: lufs, then blocks / gated as int32 pairs
+    std::vector<float> h_loud_peaks_;
+    bool have_loud_ = false;
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
     int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)
@@ -332,5 +350,6 @@ void free_result_impl(mi355vits_result* r);
 void free_packed_impl(mi355vits_packed_result* r);
 void free_alignment_impl(mi355vits_alignment* r);
 void free_edges_impl(mi355vits_edges* r);
+void free_loudness_impl(mi355vits_loudness* r);
 
 }  // namespace m355

@@ -215,8 +215,10 @@ constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes
 inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
 // trimmed = true (packs with edge trimming on only): seg = [4][n], the fourth row the first SOURCE sample of the entry — entry i is
 // row seg[n + i]'s samples [seg[3n + i], seg[3n + i] + seg[2n + i]).  false: the three-row table and the instantiation it always had.
+// normalised = true (packs with a loudness target only): one more row behind those, the bits of the entry's f32 scale — 32767 * gain,
+// which replaces 32767 / max(0.01, peak) (PACK_ENC_F32: the gain itself, one f32 multiply per sample).
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s, bool trimmed = false);
+                       int16_t* out, long total, hipStream_t s, bool trimmed = false, bool normalised = false);
 // The packed stream in another sample encoding (mi355vits_set_output_encoding; kernels_pack.cpp): the same table, the same
 // destination-major walk, one 16-byte store per lane.  PACK_ENC_ULAW / _ALAW: byte k = the G.711 code of the int16 sample
 // k_pcm16_pack stores there, every other byte the code of sample 0 (0xFF / 0xD5); a lane owns 16 samples.  PACK_ENC_F32: the
@@ -228,7 +230,7 @@ inline size_t pack_capacity_bytes(int enc, long total) {
     return enc == PACK_ENC_S16 ? 2 * pcm_pack_capacity(total) : ((size_t)total * pack_bytes_per_sample(enc) + 15) & ~size_t(15);
 }
 void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
-                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed = false);
+                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed = false, bool normalised = false);
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 
@@ -273,6 +275,23 @@ void launch_align(const int* w_ceil, const int* cum, const int* len, int B, int 
 // max(alen[b], 0) when there is none) and last[b] = the last (or -1); both words are initialised here, on s, whatever they held.
 void launch_edges(const float* audio, long audio_bs, const int* alen, const unsigned* peak_bits, int B, long l_max, float ratio,
                   int* first, int* last, hipStream_t s);
+
+// ---------------------------------------------------------------- BS.1770 integrated loudness of a run's rows (kernels_loudness.cpp)
+constexpr int LOUD_MIN_HZ = 4000;  // K-weighting's shelf sits at 1,682 Hz: below this rate the measure is not offered
+constexpr int LOUD_MAX_K = 16;
+// What the host derives from the rate: S = (fs + 5) / 10 the 100 ms step, W the warm-up of an item that starts inside a row (the
+// smallest W with sum_{k >= W} |h[k]| <= 2^-40 sum |h|), K steps per work item (K S >= 4 W), c the cascade's coefficients.
+struct LoudnessPlan {
+    int fs = 0, S = 0, W = 0, K = 0;
+    double c[7] = {};
+};
+bool loudness_plan(int fs, LoudnessPlan& out);  // false below LOUD_MIN_HZ; computed once per rate and process
+inline long loudness_steps(long n, int S) { return n > 0 ? (n + S - 1) / S : 0; }  // the steps of a row, its partial last one included
+// audio [B] rows of audio_bs floats with alen [B] valid samples (device), l_max >= every alen[b], fs >= LOUD_MIN_HZ.  k_loud writes
+// E[b * ldE + j] = the K-weighted energy of step j for j < loudness_steps(alen[b]) (ldE >= loudness_steps(l_max)), k_loud_gate
+// lufs / blocks / gated [B]; every word read is written on s before.  What lies behind a row is never looked at.
+void launch_loudness(int fs, const float* audio, long audio_bs, const int* alen, int B, long l_max, double* E, long ldE, double* lufs,
+                     int* blocks, int* gated, hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

@@ -2334,7 +2334,9 @@ void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, 
 __device__ __forceinline__ unsigned pcm16_pair(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
 
 // TRIM (packs with edge trimming on): the table has a fourth row, the first source sample of each entry
-template <bool TRIM>
+// NORM (packs with a loudness target): one more row behind the others, the bits of the entry's f32 scale, 32767 * gain, which takes
+// the place of 32767 / max(0.01, peak)
+template <bool TRIM, bool NORM>
 __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
                                                     const double* __restrict__ volumes, const int* __restrict__ seg, int n,
                                                     int16_t* __restrict__ out, long total) {
@@ -2342,6 +2344,7 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
     const int* s_row = seg + n;      // its batch row
     const int* s_len = seg + 2 * n;  // its valid samples
     const int* s_skip = seg + 3 * n;  // TRIM only: the row's sample the entry starts at
+    const int* s_scale = seg + (TRIM ? 4 : 3) * n;  // NORM only
     const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
     // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
     const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
@@ -2375,7 +2378,7 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
         if (le >= 0 && s0 + 8 <= off + len) {
             // all eight samples inside one row's audio: 32 contiguous source bytes, in the widest loads their alignment allows
             const float* src = audio + (long)row * audio_bs + (TRIM ? s_skip[lc] : 0) + (s0 - off);
-            const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
+            const float scale = NORM ? __int_as_float(s_scale[lc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
             const double volume = volumes ? volumes[row] : 1.0;
             float v0, v1, v2, v3, v4, v5, v6, v7;
             const uintptr_t al = reinterpret_cast<uintptr_t>(src);
@@ -2407,7 +2410,7 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
                 const int r = s_row[cc];
                 const bool valid = ce >= 0 && sp < o + s_len[cc];
                 const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
-                const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
+                const float scale = NORM ? __int_as_float(s_scale[cc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
                 const double volume = volumes ? volumes[r] : 1.0;
                 q[k] = valid ? pcm16_quant(a, scale, volume) : 0;
             }
@@ -2423,14 +2426,20 @@ __global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ au
 }
 
 void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s, bool trimmed) {
+                       int16_t* out, long total, hipStream_t s, bool trimmed, bool normalised) {
     if (total <= 0 || n <= 0) return;
     const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
     const long gx = std::min<long>(nchunks, 8L * current_device_cu_count());  // 8 workgroups of 4 waves per CU: every SIMD full
-    if (trimmed) {
-        LAUNCH_KERNEL(k_pcm16_pack<true>, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    if (normalised) {
+        if (trimmed) {
+            LAUNCH_KERNEL((k_pcm16_pack<true, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        } else {
+            LAUNCH_KERNEL((k_pcm16_pack<false, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        }
+    } else if (trimmed) {
+        LAUNCH_KERNEL((k_pcm16_pack<true, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
     } else {
-        LAUNCH_KERNEL(k_pcm16_pack<false>, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        LAUNCH_KERNEL((k_pcm16_pack<false, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
     }
 }
 

@@ -25,7 +25,9 @@ __device__ __forceinline__ unsigned pack_quad(unsigned c0, unsigned c1, unsigned
     return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
 }
 
-template <int ENC, bool TRIM>
+// NORM (packs with a loudness target only): one more table row behind the others, the entry's f32 scale — 32767 * gain in place of
+// 32767 / max(0.01, peak) for the int16-based encodings, the gain itself for F32 (one f32 multiply)
+template <int ENC, bool TRIM, bool NORM>
 __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
                                                   const double* __restrict__ volumes, const int* __restrict__ seg, int n,
                                                   uint8_t* __restrict__ out, long total) {
@@ -38,6 +40,7 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
     const int* s_row = seg + n;      // its batch row
     const int* s_len = seg + 2 * n;  // its valid samples
     const int* s_skip = seg + 3 * n;  // TRIM only (a [4][n] table): the row's sample the entry starts at
+    const int* s_scale = seg + (TRIM ? 4 : 3) * n;  // NORM only: the bits of the entry's f32 scale
     const long nchunks = (total + CHUNK - 1) / CHUNK;
     // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
     const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
@@ -91,9 +94,9 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
             }
             if constexpr (F32) {
                 MI355_UNROLL
-                for (int k = 0; k < 4; ++k) w[k] = __float_as_uint(v[k]);
+                for (int k = 0; k < 4; ++k) w[k] = __float_as_uint(NORM ? v[k] * __int_as_float(s_scale[lc]) : v[k]);
             } else {
-                const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
+                const float scale = NORM ? __int_as_float(s_scale[lc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
                 const double volume = volumes ? volumes[row] : 1.0;
                 MI355_UNROLL
                 for (int k = 0; k < 4; ++k)
@@ -115,9 +118,9 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
                 const bool valid = ce >= 0 && sp < o + s_len[cc];
                 const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
                 if constexpr (F32) {
-                    c[k] = valid ? __float_as_uint(a) : SILENCE;
+                    c[k] = valid ? __float_as_uint(NORM ? a * __int_as_float(s_scale[cc]) : a) : SILENCE;
                 } else {
-                    const float scale = 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
+                    const float scale = NORM ? __int_as_float(s_scale[cc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
                     const double volume = volumes ? volumes[r] : 1.0;
                     c[k] = valid ? pack_code<ENC>(pcm16_quant(a, scale, volume)) : SILENCE;
                 }
@@ -136,25 +139,31 @@ __global__ __launch_bounds__(256) void k_pack_enc(const float* __restrict__ audi
 
 template <int ENC>
 static void launch_pack_enc(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                            uint8_t* out, long total, hipStream_t s, bool trimmed) {
+                            uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised) {
     const long chunk = 256L * (ENC == PACK_ENC_F32 ? 4 : 16);
     const long nchunks = (total + chunk - 1) / chunk;
     const long gx = std::min<long>(nchunks, 8L * current_device_cu_count());  // 8 workgroups of 4 waves per CU: every SIMD full
-    if (trimmed) {
-        LAUNCH_KERNEL((k_pack_enc<ENC, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+    if (normalised) {
+        if (trimmed) {
+            LAUNCH_KERNEL((k_pack_enc<ENC, true, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        } else {
+            LAUNCH_KERNEL((k_pack_enc<ENC, false, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        }
+    } else if (trimmed) {
+        LAUNCH_KERNEL((k_pack_enc<ENC, true, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
     } else {
-        LAUNCH_KERNEL((k_pack_enc<ENC, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
+        LAUNCH_KERNEL((k_pack_enc<ENC, false, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
     }
 }
 
 void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
-                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed) {
+                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised) {
     if (total <= 0 || n <= 0) return;
     switch (enc) {
-        case PACK_ENC_ULAW: launch_pack_enc<PACK_ENC_ULAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
-        case PACK_ENC_ALAW: launch_pack_enc<PACK_ENC_ALAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
-        case PACK_ENC_F32: launch_pack_enc<PACK_ENC_F32>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed); break;
-        default: launch_pcm16_pack(audio, audio_bs, peak_bits, volumes, seg, n, reinterpret_cast<int16_t*>(out), total, s, trimmed);
+        case PACK_ENC_ULAW: launch_pack_enc<PACK_ENC_ULAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed, normalised); break;
+        case PACK_ENC_ALAW: launch_pack_enc<PACK_ENC_ALAW>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed, normalised); break;
+        case PACK_ENC_F32: launch_pack_enc<PACK_ENC_F32>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, s, trimmed, normalised); break;
+        default: launch_pcm16_pack(audio, audio_bs, peak_bits, volumes, seg, n, reinterpret_cast<int16_t*>(out), total, s, trimmed, normalised);
     }
 }
 

@@ -225,6 +225,45 @@ int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, co
     });
 }
 
+int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens, int B, int32_t rate, double* lufs, int32_t* blocks,
+                           int32_t* gated) {
+    return guarded(nullptr, [&] {
+        if (!audio || !lens || !lufs || !blocks || !gated || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        LoudnessPlan lp;
+        if (!loudness_plan(rate, lp)) throw EngineError(MI355VITS_ERR_INVALID, "rate " + std::to_string(rate) + " Hz is below " + std::to_string(LOUD_MIN_HZ) + " Hz");
+        long l_max = 0;
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            l_max = std::max<long>(l_max, lens[b]);
+        }
+        const size_t na = (size_t)B * stride;
+        const long ldE = std::max<long>(1, loudness_steps(l_max, lp.S));
+        DevBuf da(na * 4), dl((size_t)B * 4), dE((size_t)B * ldE * 8), dout((size_t)B * 16);
+        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dE.p, 0xff, (size_t)B * ldE * 8));  // NaN: the launch writes every energy it reads
+        HIP_CHECK(hipMemset(dout.p, 0x5a, (size_t)B * 16));
+        double* d_lufs = dout.as<double>();
+        int* d_blocks = reinterpret_cast<int*>(d_lufs + B);
+        launch_loudness(rate, da.as<float>(), stride, dl.as<int>(), B, l_max, dE.as<double>(), ldE, d_lufs, d_blocks, d_blocks + B, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(lufs, d_lufs, (size_t)B * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(blocks, d_blocks, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(gated, d_blocks + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, int32_t* steps_per_item) {
+    return guarded(nullptr, [&] {
+        LoudnessPlan lp;
+        if (!loudness_plan(rate, lp)) throw EngineError(MI355VITS_ERR_INVALID, "rate " + std::to_string(rate) + " Hz is below " + std::to_string(LOUD_MIN_HZ) + " Hz");
+        if (step) *step = lp.S;
+        if (warmup) *warmup = lp.W;
+        if (steps_per_item) *steps_per_item = lp.K;
+    });
+}
+
 int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern) {
     if (!h) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);

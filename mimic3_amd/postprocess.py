@@ -98,8 +98,9 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     ``utterances_to_wav`` over per-sentence ``run_pcm16`` calls, with no host pass over the audio.
 
     ``settings``: ``scales`` ([3] or [B, 3]; default the reference's 0.667 / 1.0 / 0.8), ``sid`` (multi-speaker voices), and
-    ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` / ``encoding`` / ``trim_db`` / ``trim_keep_ms`` as
-    ``run_packed`` takes them (with ``trim_db`` each sentence is cut to its loud part, so ``break_ms`` is the pause heard; with
+    ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` / ``encoding`` / ``trim_db`` / ``trim_keep_ms`` /
+    ``loudness`` / ``ceiling_db`` as ``run_packed`` takes them (with ``loudness=-23`` every sentence is scaled to that BS.1770
+    integrated loudness instead of to its own peak; with ``trim_db`` each sentence is cut to its loud part, so ``break_ms`` is the pause heard; with
     ``sample_rate`` the file is at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it; with
     ``encoding="ulaw"`` and ``sample_rate=8000`` it is the G.711 file a telephony stack plays)."""
     rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]

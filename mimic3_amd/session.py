@@ -495,6 +495,20 @@ def _trim_ratio(db) -> float:
     return float(np.float32(10.0 ** (db / 20.0)))
 
 
+def _loudness_setting(lufs, ceiling_db):
+    """A loudness target as the engine's ``(target_lufs, ceiling_dbfs)``; ``None`` = off ``(0.0, ceiling)``.  On: -70 <= lufs < 0 and
+    a finite ceiling <= 0 dBFS, else ``ValueError``."""
+    ceiling = -1.0 if ceiling_db is None else float(ceiling_db)
+    if lufs is None:
+        return 0.0, ceiling
+    lufs = float(lufs)
+    if not (-70.0 <= lufs < 0.0):
+        raise ValueError(f"loudness target must be in [-70, 0) LUFS, not {lufs!r}")
+    if not np.isfinite(ceiling) or ceiling > 0.0:
+        raise ValueError(f"loudness ceiling must be finite and <= 0 dBFS, not {ceiling!r}")
+    return lufs, ceiling
+
+
 def _alignment_levels(alignment) -> bool:
     """``alignment=True`` -> timing only, ``"levels"`` -> peak and rms too; anything else raises ``ValueError``."""
     if alignment is True:
@@ -527,6 +541,11 @@ class InferenceSession:
         self.edge_trim_keep_ms: float = float(kwargs.pop("edge_trim_keep_ms", 0) or 0)
         if self.edge_trim_keep_ms < 0:
             raise ValueError("edge_trim_keep_ms must be >= 0")
+        # loudness target of the packed streams (Engine.set_loudness_target): LUFS, None = off, and the ceiling in dBFS that bounds
+        # the gain; a call's ``loudness=`` / ``ceiling_db=`` go before them
+        self.loudness_lufs: Optional[float] = kwargs.pop("loudness_lufs", None)
+        self.loudness_ceiling_db: float = float(kwargs.pop("loudness_ceiling_db", -1.0))
+        _loudness_setting(self.loudness_lufs, self.loudness_ceiling_db)
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -635,7 +654,8 @@ class InferenceSession:
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-                   alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None) -> "_native.PackedAudio":
+                   alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
+                   loudness: Optional[float] = None, ceiling_db: Optional[float] = None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -654,7 +674,11 @@ class InferenceSession:
         side, so ``lead_ms`` is the pause that is heard; ``PackedAudio.first`` / ``.end`` say what was kept.  The alignment of a
         trimmed stream follows the cut: a span is clipped to the entry (a phoneme wholly cut has ``samples`` = 0), the spans
         still tile the entry and sum to ``lengths[i]``; ``frames`` stay the run's own, and ``peak`` / ``rms`` stay those of the
-        UNTRIMMED span."""
+        UNTRIMMED span.
+        ``loudness`` (else the session's ``loudness_lufs``; ``None`` = off): each entry is scaled to that ITU-R BS.1770-4 integrated
+        loudness in LUFS instead of to its own peak, with the gain bounded so that no sample passes ``ceiling_db`` dBFS (else the
+        session's ``loudness_ceiling_db``, default -1) — ``Engine.set_loudness_target``; -70 <= loudness < 0 and a finite ceiling
+        <= 0, else ``ValueError``.  ``PackedAudio.lufs`` / ``.gain`` / ``.limited`` say what was measured and applied."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -673,6 +697,8 @@ class InferenceSession:
         if keep_ms < 0:
             raise ValueError("trim_keep_ms must be >= 0")
         kw["_trim"] = (ratio, int((keep_ms / 1000.0) * rate))
+        kw["_loudness"] = _loudness_setting(loudness if loudness is not None else self.loudness_lufs,
+                                            ceiling_db if ceiling_db is not None else self.loudness_ceiling_db)
         out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
                                lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
         if alignment:
@@ -749,7 +775,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, _trim=None, **kw):
+                    _alignment=None, _trim=None, _loudness=None, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -767,6 +793,7 @@ class InferenceSession:
             if _packed:  # the encoding concerns packed streams only; read by the engine when the pack is planned
                 eng.set_output_encoding(encoding or self.output_encoding)
                 eng.set_edge_trim(*(_trim or (0.0, 0)))  # likewise; set on every call: back to off for a call that does not ask
+                eng.set_loudness_target(*(_loudness or (0.0, -1.0)))  # likewise
             call = eng.run_packed if _packed else eng.run
             out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
             return out if _alignment is None else (out, eng.fetch_alignment(levels=_alignment))
