@@ -224,7 +224,7 @@ void mi355vits_free_result(mi355vits_result* r);
 /* ---- Packed results: a batch's finished audio as ONE contiguous PCM / WAV stream.
  * What the reference does to the int16 audio of a request's sentences on the host — silence between them
  * (Mimic3TextToSpeechSystem.add_break, mimic3_tts/tts.py:452-465: int(ms / 1000 * sample_rate) zero samples) and WAV framing
- * (opentts_abc/__init__.py:117-127) — done by one kernel (k_pcm16_pack) and brought to the host by one copy of exactly
+ * (opentts_abc/__init__.py:117-127) — done by one kernel (k_pack, csrc/kernels_pack.cpp) and brought to the host by one copy of exactly
  * n_bytes: only the valid samples of each row, rows in the order the caller names, no padding to the longest row. */
 typedef struct mi355vits_pack_args {
     int32_t n;                   /* entries of the stream, 1 <= n <= batch */
@@ -272,8 +272,8 @@ int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, 
 void mi355vits_free_packed(mi355vits_packed_result* r);
 
 /* ---- Sample encoding of the packed stream.  MI355VITS_ENC_S16LE (the default) = the stream described above and nothing below
- * applies: k_pcm16_pack runs as ever, the 44-byte header is the PCM one, every byte is what it was before this setting existed.
- * With another encoding the kernel that touches every output sample writes the format the caller ships (k_pack_enc), so neither a
+ * applies: the 44-byte header is the PCM one, every byte is what it was before this setting existed.
+ * With another encoding the same kernel (k_pack: one template over the encodings) writes the format the caller ships, so neither a
  * second pass over the audio on the host (audioop.lin2ulaw) nor bytes nobody wants cross the bus:
  *   MI355VITS_ENC_ULAW / _ALAW  G.711, 1 byte per sample (telephony at 8000 Hz: see mi355vits_set_output_rate).  Entry i's byte k
  *                     is the G.711 code of int16 sample k of the S16LE stream for the same arguments — the value after

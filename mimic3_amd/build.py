@@ -18,11 +18,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
-SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "engine.cpp", "c_api.cpp"]
+SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "engine.cpp", "engine_results.cpp", "c_api.cpp"]
 # csrc/lab_api.cpp = the hooks of include/mi355vits_lab.h (kernel unit tests, conv micro-benchmark, box probes): NOT in the product
 # library; linked with the product's own objects into libmi355vits_hooks.so, and compiled into the lab build and the CPU model
 HOOK_SOURCES = ["lab_api.cpp"]
 PER_FILE_FLAGS = {}
+MAX_COMPILE_JOBS = 16  # compilers at once, however many processors the machine reports
 LAB_FILE_FLAGS = {}  # per-file flags of the lab build's side of a running A/B (none at the moment)
 # throw-away instrumented twins of the lab build (MI355_LAB_VARIANT=<name> python -m mimic3_amd.build lab -> libmi355vits_lab_<name>.so)
 VARIANT_FILE_FLAGS = {"clk": {"kernels_mrfp.cpp": ["-DMRFP_CLOCKS"]}}  # shader-clock stamps inside k_mrf_p<32> (MI355VITS_MRFP_CLOCKS=1)
@@ -88,7 +89,7 @@ def build_hip(force: bool = False, verbose_resources: bool = False, lab: bool = 
             jobs.append(base + PER_FILE_FLAGS.get(s, []) + lab_flags + ["-c", src, "-o", obj])
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, MAX_COMPILE_JOBS)) as ex:
             list(ex.map(_run, jobs))
     objs = [os.path.join(objdir, s.replace(".cpp", ".o")) for s in srcs]
     # the product library: everything but the hooks; the same objects + the hooks = libmi355vits_hooks.so (test infrastructure)
@@ -113,7 +114,7 @@ def build_emu(force: bool = False) -> str:
     jobs = [base + ["-c", s, "-o", o] for s, o in zip(srcs, objs) if force or _stale(o, [s] + hdrs)]
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, MAX_COMPILE_JOBS)) as ex:
             list(ex.map(_run, jobs))
     if jobs or _stale(EMU_LIB, objs):
         _run([cxx, "-shared", "-fPIC"] + objs + ["-o", EMU_LIB + ".tmp", "-lpthread"])

@@ -9,6 +9,24 @@ int create_common(WeightsFile& wf, int device, mi355vits_handle* out) {
     *out = h.release();
     return MI355VITS_OK;
 }
+
+// mi355vits_free_*: what the struct's owner holds goes back, the struct is zeroed (idempotent; a struct without an owner is left alone)
+template <typename R> void free_struct(R* r) {
+    if (!r || !r->owner_) return;
+    release_result_owner(r->owner_);
+    memset(r, 0, sizeof(*r));
+}
+
+// A call that fills a result struct: the struct zeroed before anything can fail (its free must never see garbage), the handle
+// locked, exceptions fenced, and after a failure whatever was filled freed again — never partial audio.
+template <typename R, typename F> int result_call(mi355vits_handle h, R* out, F&& fn) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    const int rc = guarded(h, fn);
+    if (rc != MI355VITS_OK && out) free_struct(out);
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -133,62 +151,37 @@ int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_
 
 int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                        mi355vits_result* out) {
-    if (out) memset(out, 0, sizeof(*out));  // before anything can fail: free_result below must never see garbage
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] {
+    return result_call(h, out, [&] {
         if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
         h->eng->run(*args, rows, out);
     });
-    if (rc != MI355VITS_OK && out) mi355vits_free_result(out);  // never hand back partial audio
-    return rc;
 }
 
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] { h->eng->fetch(want_flags, out); });
-    if (rc != MI355VITS_OK && out) mi355vits_free_result(out);
-    return rc;
+    return result_call(h, out, [&] { h->eng->fetch(want_flags, out); });
 }
 
-void mi355vits_free_result(mi355vits_result* r) { free_result_impl(r); }
+void mi355vits_free_result(mi355vits_result* r) { free_struct(r); }
 
 int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                          const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] {
+    return result_call(h, out, [&] {
         if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
         h->eng->run_packed(*args, rows, pack, out);
     });
-    if (rc != MI355VITS_OK && out) mi355vits_free_packed(out);  // never hand back partial audio
-    return rc;
 }
 
 int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] { h->eng->fetch_packed(pack, out); });
-    if (rc != MI355VITS_OK && out) mi355vits_free_packed(out);
-    return rc;
+    return result_call(h, out, [&] { h->eng->fetch_packed(pack, out); });
 }
 
-void mi355vits_free_packed(mi355vits_packed_result* r) { free_packed_impl(r); }
+void mi355vits_free_packed(mi355vits_packed_result* r) { free_struct(r); }
 
 int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] { h->eng->fetch_alignment(want, out); });
-    if (rc != MI355VITS_OK && out) mi355vits_free_alignment(out);
-    return rc;
+    return result_call(h, out, [&] { h->eng->fetch_alignment(want, out); });
 }
 
-void mi355vits_free_alignment(mi355vits_alignment* r) { free_alignment_impl(r); }
+void mi355vits_free_alignment(mi355vits_alignment* r) { free_struct(r); }
 
 int mi355vits_set_edge_trim(mi355vits_handle h, float ratio, int32_t keep_samples) {
     if (!h) return MI355VITS_ERR_INVALID;
@@ -205,15 +198,10 @@ int mi355vits_get_edge_trim(mi355vits_handle h, float* ratio, int32_t* keep_samp
 }
 
 int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] { h->eng->fetch_edges(out); });
-    if (rc != MI355VITS_OK && out) mi355vits_free_edges(out);
-    return rc;
+    return result_call(h, out, [&] { h->eng->fetch_edges(out); });
 }
 
-void mi355vits_free_edges(mi355vits_edges* r) { free_edges_impl(r); }
+void mi355vits_free_edges(mi355vits_edges* r) { free_struct(r); }
 
 int mi355vits_set_loudness_target(mi355vits_handle h, float target_lufs, float ceiling_dbfs) {
     if (!h) return MI355VITS_ERR_INVALID;
@@ -230,15 +218,10 @@ int mi355vits_get_loudness_target(mi355vits_handle h, float* target_lufs, float*
 }
 
 int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out) {
-    if (out) memset(out, 0, sizeof(*out));
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    int rc = guarded(h, [&] { h->eng->fetch_loudness(out); });
-    if (rc != MI355VITS_OK && out) mi355vits_free_loudness(out);
-    return rc;
+    return result_call(h, out, [&] { h->eng->fetch_loudness(out); });
 }
 
-void mi355vits_free_loudness(mi355vits_loudness* r) { free_loudness_impl(r); }
+void mi355vits_free_loudness(mi355vits_loudness* r) { free_struct(r); }
 
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 

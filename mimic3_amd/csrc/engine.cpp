@@ -1,7 +1,8 @@
 // engine.cpp — weight upload (with the load-time repacks the kernels want) and the launch sequence of one
 // synthesis call: text encoder -> stochastic duration predictor -> length regulator -> flow^-1 -> HiFi-GAN
 // -> tanh / peak / int16.  Everything runs on one HIP stream; the only host round trip inside a call is
-// the 4*B-byte read of the frame counts that size the second half of the graph.
+// the 4*B-byte read of the frame counts that size the second half of the graph.  What is done with the finished
+// waveform — copy-outs, packed streams, alignment, edges, loudness — is engine_results.cpp.
 #include "engine.h"
 
 #include <algorithm>
@@ -394,11 +395,7 @@ Engine::Engine(const Engine& lane0) : cfg_(lane0.cfg_), device_(lane0.device_) {
         math_ = lane0.math_;
         sw_ = lane0.sw_;
         if (lane0.out_hz_) set_output_rate(lane0.out_hz_);
-        enc_ = lane0.enc_;
-        trim_ratio_ = lane0.trim_ratio_;
-        trim_keep_ = lane0.trim_keep_;
-        loud_target_ = lane0.loud_target_;
-        loud_ceiling_ = lane0.loud_ceiling_;
+        pack_ = lane0.pack_;
     } catch (...) {
         release();
         throw;
@@ -486,15 +483,6 @@ void Engine::set_output_rate(int hz) {
     d_rs_coef_ = static_cast<float*>(p);
     rs_ = std::move(f);
     out_hz_ = hz;
-}
-
-static_assert(MI355VITS_ENC_S16LE == PACK_ENC_S16 && MI355VITS_ENC_ULAW == PACK_ENC_ULAW && MI355VITS_ENC_ALAW == PACK_ENC_ALAW &&
-                  MI355VITS_ENC_F32LE == PACK_ENC_F32, "the ABI's encoding values are the kernels' own");
-// The sample encoding of the packed streams made after this (read by run_packed / fetch_packed when they plan their pack).
-void Engine::set_output_encoding(int enc) {
-    if (enc != MI355VITS_ENC_S16LE && enc != MI355VITS_ENC_ULAW && enc != MI355VITS_ENC_ALAW && enc != MI355VITS_ENC_F32LE)
-        throw EngineError(MI355VITS_ERR_INVALID, "output encoding " + std::to_string(enc) + " unknown (0 = s16le, 1 = ulaw, 2 = alaw, 3 = f32le)");
-    enc_ = enc;
 }
 
 void Engine::construct(const WeightsFile& wf, int device) {
@@ -1494,80 +1482,6 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
 // =================================================================================================
 // one synthesis call
 // =================================================================================================
-namespace {
-// Pinned host buffers for results, recycled process-wide: hipHostMalloc costs milliseconds for a 12 MB block (page
-// pinning + IOMMU mapping), more than the D2H itself, so a buffer released by mi355vits_free_result goes back on a
-// free list and the next call of any handle takes the smallest one that fits.  Buffers are handed out exclusively
-// (a result stays valid until its free_result, whatever runs meanwhile); at most POOL_KEEP_BYTES stay cached.
-class PinnedPool {
-  public:
-    static PinnedPool& get() {
-        static PinnedPool* p = new PinnedPool();  // never destroyed: no hipHostFree after the runtime has shut down
-        return *p;
-    }
-    void* take(size_t bytes, size_t* cap) {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            auto it = free_.lower_bound(bytes);
-            // a block more than twice as large as needed is left for a caller that needs it
-            if (it != free_.end() && it->first <= 2 * bytes + (1 << 16)) {
-                void* p = it->second;
-                *cap = it->first;
-                cached_ -= it->first;
-                free_.erase(it);
-                return p;
-            }
-        }
-        const size_t want = ((bytes + (1 << 16) - 1) >> 16) << 16;  // 64 KiB granules: nearby sizes share blocks
-        void* p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-            trim(0);
-            if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess)
-                throw EngineError(MI355VITS_ERR_NOMEM, "out of pinned host memory (result buffer)");
-        }
-        *cap = want;
-        return p;
-    }
-    void give(void* p, size_t cap) {
-        if (!p) return;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            free_.emplace(cap, p);
-            cached_ += cap;
-        }
-        trim(POOL_KEEP_BYTES);
-    }
-
-  private:
-    static constexpr size_t POOL_KEEP_BYTES = size_t(1) << 30;
-    void trim(size_t keep) {
-        std::vector<void*> drop;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            while (cached_ > keep && !free_.empty()) {
-                auto it = std::prev(free_.end());
-                cached_ -= it->first;
-                drop.push_back(it->second);
-                free_.erase(it);
-            }
-        }
-        for (void* p : drop) (void)hipHostFree(p);
-    }
-    std::mutex mu_;
-    std::multimap<size_t, void*> free_;
-    size_t cached_ = 0;
-};
-
-struct ResultOwner {
-    void* audio = nullptr;
-    size_t audio_cap = 0;
-    void* pcm = nullptr;
-    size_t pcm_cap = 0;
-    void* lengths = nullptr;
-    void* peaks = nullptr;
-};
-}  // namespace
-
 // The sequence of alloc calls below IS the workspace layout: run() plays it against an ArenaCount for the size to reserve, then
 // against the arena for the pointers.
 template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w) {
@@ -1637,40 +1551,6 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B + (Lr ? resample_tab_ints((int)B) : 0));
     d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
     d_rtab_ = Lr ? d_alen_ + B : nullptr;
-}
-
-// what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
-struct Engine::PackPlan {
-    int n = 0;
-    bool wav = false;
-    std::vector<int> order;
-    std::vector<int64_t> lead;
-    int64_t tail = 0;
-    // made by place_pack from the frame counts
-    std::vector<int64_t> offsets, lengths;
-    int64_t total = 0, audio = 0;
-    // the handle's output encoding when the pack was planned (MI355VITS_ENC_* = PackEncoding)
-    int enc = PACK_ENC_S16;
-    // the handle's edge trimming when the pack was planned (ratio 0 = off); with it on, place_pack fills skip: the first sample
-    // of its row each entry starts at
-    float ratio = 0.0f;
-    int keep = 0;
-    std::vector<int> skip;
-    bool trimmed() const { return ratio != 0.0f; }
-    // the handle's loudness target when the pack was planned (0 = off); with it on, place_pack fills gain: each entry's linear gain
-    float target = 0.0f, ceiling = 0.0f;
-    std::vector<double> gain;
-    bool normalised() const { return target != 0.0f; }
-    int seg_rows() const { return 3 + (trimmed() ? 1 : 0) + (normalised() ? 1 : 0); }
-    int bps() const { return pack_bytes_per_sample(enc); }
-    size_t header_bytes() const { return !wav ? 0 : enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
-};
-
-// Packed calls only: the segment table and the stream, behind everything layout_b placed — no other pointer moves, so a call
-// that packs nothing runs on the layout it always had.
-template <typename A> void Engine::layout_pack(A& ar, size_t n, size_t samples, int enc, int seg_rows) {
-    d_pack_seg_ = ar.template alloc<int>((size_t)seg_rows * n);
-    d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(enc, (long)samples));  // in bytes, the last store's overrun included
 }
 
 void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
@@ -1834,7 +1714,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
     ArenaCount size_b;
     layout_b(size_b, B, Ty, nz_frames, rs ? Lo_ : 0);
-    if (plan) layout_pack(size_b, plan->n, plan->total, plan->enc);
+    if (plan) layout_pack(size_b, *plan);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
     layout_b(arena_b_, B, Ty, nz_frames, rs ? Lo_ : 0);
@@ -1844,11 +1724,11 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     o_alen_ = rs ? d_rtab_ : d_alen_;
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
-    if (plan) layout_pack(arena_b_, plan->n, plan->total, plan->enc);
+    if (plan) layout_pack(arena_b_, *plan);
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     // (a packed call's segment table sits right behind d_slen_ in the arena: the same copy brings it)
-    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + 3 * (size_t)plan->n : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
+    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + (size_t)plan->seg_rows() * plan->n : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
     if (plan) fill_pack_seg(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
     {
         long f = 1;
@@ -1885,587 +1765,6 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     HIP_CHECK(hipEventRecord(ev_end_, stream_));
     timed_ = true;
     have_result_ = true;
-}
-
-void Engine::copy_out(uint32_t want, mi355vits_result* out) {
-    const int B = B_;
-    auto* own = new ResultOwner();
-    out->owner_ = own;
-    out->batch = B;
-    out->l_max = Lo_;
-    out->ty_max = Ty_;
-    own->lengths = malloc(sizeof(int64_t) * B);
-    own->peaks = malloc(sizeof(float) * B);
-    out->lengths = static_cast<int64_t*>(own->lengths);
-    out->peaks = static_cast<float*>(own->peaks);
-    if (!out->lengths || !out->peaks) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
-    for (int b = 0; b < B; ++b) out->lengths[b] = h_olen_[b];
-    std::vector<unsigned> pk(B);
-    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B, hipMemcpyDeviceToHost, stream_));
-    const bool dev_only = (want & MI355VITS_DEVICE_ONLY) != 0;
-    if (!dev_only && (want & MI355VITS_WANT_FLOAT)) {
-        own->audio = PinnedPool::get().take(sizeof(float) * (size_t)B * Lo_ + 16, &own->audio_cap);
-        out->audio = static_cast<float*>(own->audio);
-        HIP_CHECK(hipMemcpyAsync(out->audio, o_audio_, sizeof(float) * (size_t)B * Lo_, hipMemcpyDeviceToHost, stream_));
-    }
-    if (!dev_only && (want & MI355VITS_WANT_PCM16)) {
-        if (!have_pcm_) {
-            launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B, (int)Lo_, d_pcm_, Lo_, stream_, nullptr);
-            have_pcm_ = true;
-        }
-        own->pcm = PinnedPool::get().take(sizeof(int16_t) * (size_t)B * Lo_ + 16, &own->pcm_cap);
-        out->pcm = static_cast<int16_t*>(own->pcm);
-        HIP_CHECK(hipMemcpyAsync(out->pcm, d_pcm_, sizeof(int16_t) * (size_t)B * Lo_, hipMemcpyDeviceToHost, stream_));
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int b = 0; b < B; ++b) memcpy(&out->peaks[b], &pk[b], 4);
-}
-
-// ---------------------------------------------------------------- packed results (mi355vits_run_packed / mi355vits_fetch_packed)
-namespace {
-constexpr int64_t PACK_MAX_SAMPLES = 0x7fffffffLL;                       // total_samples <= 2^31 - 1
-constexpr int64_t RIFF_MAX_SAMPLES = (0xffffffffLL - 36) / 2;            // 36 + 2 * total_samples must fit RIFF's 32-bit size
-EngineError pack_error(int entry, const std::string& what) {
-    return EngineError(MI355VITS_ERR_INVALID, (entry >= 0 ? "pack entry " + std::to_string(entry) + ": " : std::string("pack: ")) + what);
-}
-void check_pack_size(int entry, int64_t samples, bool wav, int enc) {
-    if (samples > PACK_MAX_SAMPLES) throw pack_error(entry, "total_samples exceeds 2^31 - 1");
-    if (!wav) return;
-    if (enc == PACK_ENC_S16) {
-        if (samples > RIFF_MAX_SAMPLES) throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (36 + 2 * total_samples > 2^32 - 1)");
-        return;
-    }
-    // the 58-byte non-PCM form: RIFF size = 50 + data (+ one pad byte behind an odd data size: G.711 only)
-    const int64_t bps = pack_bytes_per_sample(enc), data = bps * samples;
-    if (50 + data + (data & 1) > 0xffffffffLL)
-        throw pack_error(entry, "WAV data size does not fit RIFF's 32-bit fields (50 + " + std::to_string(bps) + " * total_samples > 2^32 - 1)");
-}
-struct PackedOwner {
-    void* bytes = nullptr;
-    size_t cap = 0;
-    void* offsets = nullptr;
-    void* lengths = nullptr;
-    void* peaks = nullptr;
-};
-}  // namespace
-
-// Everything that can be wrong with the pack arguments alone, before anything is sized or launched.
-void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const {
-    plan.n = pack ? pack->n : B;
-    if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
-    plan.wav = pack && pack->wav_header != 0;
-    plan.enc = enc_;  // the setting is read here: when a pack is made
-    plan.ratio = trim_ratio_;  // likewise
-    plan.keep = trim_keep_;
-    plan.target = loud_target_;
-    plan.ceiling = loud_ceiling_;
-    plan.tail = pack ? pack->tail_samples : 0;
-    plan.order.resize(plan.n);
-    plan.lead.assign(plan.n, 0);
-    std::vector<int> at(B, -1);
-    int64_t silence = 0;
-    for (int i = 0; i < plan.n; ++i) {
-        const int row = (pack && pack->order) ? pack->order[i] : i;
-        if (row < 0 || row >= B) throw pack_error(i, "row " + std::to_string(row) + " out of range (batch = " + std::to_string(B) + ")");
-        if (at[row] >= 0) throw pack_error(i, "row " + std::to_string(row) + " appears twice (also entry " + std::to_string(at[row]) + ")");
-        at[row] = i;
-        plan.order[i] = row;
-        const int64_t lead = (pack && pack->lead_samples) ? pack->lead_samples[i] : 0;
-        if (lead < 0) throw pack_error(i, "negative silence (" + std::to_string(lead) + " samples)");
-        check_pack_size(i, lead, plan.wav, plan.enc);
-        plan.lead[i] = lead;
-        silence += lead;
-        check_pack_size(i, silence, plan.wav, plan.enc);  // the silences alone: no row is synthesised for a stream that cannot exist
-    }
-    if (plan.tail < 0) throw pack_error(-1, "negative tail silence (" + std::to_string(plan.tail) + " samples)");
-    check_pack_size(-1, plan.tail, plan.wav, plan.enc);
-    check_pack_size(-1, silence + plan.tail, plan.wav, plan.enc);
-}
-
-// Where every entry goes, from the frame counts the host already holds — with trimming on from the edges as well (h_edges_ at the
-// plan's ratio: find_edges first); the size limits with the audio counted in.
-void Engine::place_pack(PackPlan& plan) const {
-    plan.offsets.resize(plan.n);
-    plan.lengths.resize(plan.n);
-    plan.skip.assign(plan.trimmed() ? plan.n : 0, 0);
-    plan.gain.assign(plan.normalised() ? plan.n : 0, 0.0);
-    int64_t pos = 0;
-    plan.audio = 0;
-    for (int i = 0; i < plan.n; ++i) {
-        pos += plan.lead[i];
-        plan.offsets[i] = pos;
-        plan.lengths[i] = h_olen_[plan.order[i]];  // at the run's rate
-        if (plan.trimmed()) {
-            const int row = plan.order[i];
-            const int64_t n = h_olen_[row];
-            const int64_t first = std::max<int64_t>(0, (int64_t)h_edges_[row] - plan.keep);
-            const int64_t end = std::min<int64_t>(n, (int64_t)h_edges_[B_ + row] + 1 + plan.keep);
-            plan.skip[i] = (int)std::min(first, n);
-            plan.lengths[i] = std::max<int64_t>(0, end - plan.skip[i]);  // (a row without a loud sample — a NaN peak — keeps nothing)
-        }
-        if (plan.normalised()) {
-            const int row = plan.order[i];
-            bool limited;
-            loudness_gain(h_loud_[row], h_loud_peaks_[row], plan.target, plan.ceiling, &plan.gain[i], &limited);
-        }
-        pos += plan.lengths[i];
-        plan.audio += plan.lengths[i];
-        check_pack_size(i, pos, plan.wav, plan.enc);
-    }
-    plan.total = pos + plan.tail;
-    check_pack_size(-1, plan.total, plan.wav, plan.enc);
-}
-
-void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
-    for (int i = 0; i < plan.n; ++i) {
-        seg[i] = (int)plan.offsets[i];
-        seg[plan.n + i] = plan.order[i];
-        seg[2 * plan.n + i] = (int)plan.lengths[i];
-        if (plan.trimmed()) seg[3 * plan.n + i] = plan.skip[i];
-        if (plan.normalised()) {
-            // the entry's f32 scale: 32767 * gain in double, rounded once (F32LE: the gain itself)
-            const float scale = plan.enc == PACK_ENC_F32 ? (float)plan.gain[i] : (float)(32767.0 * plan.gain[i]);
-            memcpy(&seg[(plan.trimmed() ? 4 : 3) * plan.n + i], &scale, 4);
-        }
-    }
-}
-
-void Engine::launch_pack(const PackPlan& plan) {
-    if (plan.enc == PACK_ENC_S16) {
-        ProfScope ps(prof_, "pcm16.pack", 0, 4.0 * (double)plan.audio + 2.0 * (double)plan.total);
-        launch_pcm16_pack(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, reinterpret_cast<int16_t*>(d_pack_), (long)plan.total, stream_, plan.trimmed(), plan.normalised());
-        return;
-    }
-    const char* label = plan.enc == PACK_ENC_ULAW ? "pack.ulaw" : plan.enc == PACK_ENC_ALAW ? "pack.alaw" : "pack.f32";
-    ProfScope ps(prof_, label, 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
-    launch_pack_encoded(plan.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_, plan.trimmed(), plan.normalised());
-}
-
-void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
-    const int n = plan.n;
-    auto* own = new PackedOwner();
-    out->owner_ = own;
-    out->n = n;
-    out->total_samples = plan.total;
-    own->offsets = malloc(sizeof(int64_t) * n);
-    own->lengths = malloc(sizeof(int64_t) * n);
-    own->peaks = malloc(sizeof(float) * n);
-    out->offsets = static_cast<int64_t*>(own->offsets);
-    out->lengths = static_cast<int64_t*>(own->lengths);
-    out->peaks = static_cast<float*>(own->peaks);
-    if (!out->offsets || !out->lengths || !out->peaks) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
-    const size_t hdr = plan.header_bytes(), data = (size_t)plan.bps() * (size_t)plan.total;
-    const size_t pad = (plan.wav && (data & 1)) ? 1 : 0;  // RIFF chunks are word-aligned: one zero byte behind an odd data size (G.711 only)
-    const size_t lead = hdr == 58 ? 6 : 0;  // the 58-byte header starts 6 bytes into the block: the data behind it keeps the block's alignment
-    own->bytes = PinnedPool::get().take(lead + hdr + data + pad + 16, &own->cap);
-    out->bytes = static_cast<uint8_t*>(own->bytes) + lead;
-    out->n_bytes = hdr + data + pad;
-    out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);  // the first data byte, whatever the encoding
-    std::vector<unsigned> pk(B_);
-    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
-    if (plan.wav && plan.enc != PACK_ENC_S16) {
-        // RIFF/WAVE, the non-PCM form (an 18-byte fmt chunk with cbSize 0, then a fact chunk with the sample count): 58 bytes, what
-        // scipy.io.wavfile.write puts in front of float32 data; format tag 7 = mu-law, 6 = A-law, 3 = IEEE float
-        uint8_t* h = out->bytes;
-        auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
-        auto u16 = [&](size_t at, uint32_t v) { h[at] = (uint8_t)v; h[at + 1] = (uint8_t)(v >> 8); };
-        const uint32_t rate = (uint32_t)run_hz_, bps = (uint32_t)plan.bps();
-        memcpy(h, "RIFF", 4);
-        u32(4, (uint32_t)(50 + data + pad));
-        memcpy(h + 8, "WAVEfmt ", 8);
-        u32(16, 18);
-        u16(20, plan.enc == PACK_ENC_ULAW ? 7 : plan.enc == PACK_ENC_ALAW ? 6 : 3);
-        u16(22, 1);
-        u32(24, rate);
-        u32(28, rate * bps);
-        u16(32, bps);
-        u16(34, 8 * bps);
-        u16(36, 0);
-        memcpy(h + 38, "fact", 4);
-        u32(42, 4);
-        u32(46, (uint32_t)plan.total);
-        memcpy(h + 50, "data", 4);
-        u32(54, (uint32_t)data);
-        if (pad) h[hdr + data] = 0;
-    } else if (plan.wav) {
-        // RIFF/WAVE, PCM, mono, 16 bit: the 44 bytes the stdlib `wave` module writes (little-endian fields)
-        uint8_t* h = out->bytes;
-        auto u32 = [&](size_t at, uint32_t v) { for (int k = 0; k < 4; ++k) h[at + k] = (uint8_t)(v >> (8 * k)); };
-        auto u16 = [&](size_t at, uint32_t v) { h[at] = (uint8_t)v; h[at + 1] = (uint8_t)(v >> 8); };
-        const uint32_t rate = (uint32_t)run_hz_;  // the rate the run ran at
-        memcpy(h, "RIFF", 4);
-        u32(4, (uint32_t)(36 + data));
-        memcpy(h + 8, "WAVEfmt ", 8);
-        u32(16, 16);
-        u16(20, 1);
-        u16(22, 1);
-        u32(24, rate);
-        u32(28, rate * 2);
-        u16(32, 2);
-        u16(34, 16);
-        memcpy(h + 36, "data", 4);
-        u32(40, (uint32_t)data);
-    }
-    for (int i = 0; i < n; ++i) {
-        out->offsets[i] = plan.offsets[i];
-        out->lengths[i] = plan.lengths[i];
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int i = 0; i < n; ++i) memcpy(&out->peaks[i], &pk[plan.order[i]], 4);
-}
-
-void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
-                        mi355vits_packed_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    PackPlan plan;
-    plan_pack(pack, args.batch, plan);
-    if (!plan.trimmed() && !plan.normalised()) {
-        synthesize(args, rows, &plan);
-        copy_out_packed(plan, out);
-        return;
-    }
-    // Trimming or a loudness target on: the offsets / the scales depend on the audio.  Synthesise without an early pack table (and
-    // without the padded int16 pass: a packed call looks at no MI355VITS_WANT_* flag), measure (k_edges and / or k_loud, their
-    // copies, ONE synchronisation), then what fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
-    mi355vits_run_args a = args;
-    a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
-    synthesize(a, rows, nullptr);
-    try {
-        pack_last_run(plan, out);
-        HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its edges and its pack
-    } catch (...) {
-        have_result_ = false;
-        throw;
-    }
-}
-
-void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_packed: no completed run on this handle");
-    PackPlan plan;
-    plan_pack(pack, B_, plan);
-    pack_last_run(plan, out);
-}
-
-void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
-    HIP_CHECK(hipSetDevice(device_));
-    measure_last_run(plan.ratio, plan.normalised());
-    place_pack(plan);
-    // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
-    // else in an arena of its own
-    const int seg_rows = plan.seg_rows();
-    ArenaCount need;
-    layout_pack(need, plan.n, plan.total, plan.enc, seg_rows);
-    if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
-        arena_b_.rewind(layout_b_end_);
-        layout_pack(arena_b_, plan.n, plan.total, plan.enc, seg_rows);
-    } else {
-        arena_p_.reserve(need.bytes + 4096, stream_);
-        arena_p_.reset();
-        layout_pack(arena_p_, plan.n, plan.total, plan.enc, seg_rows);
-    }
-    h_pack_seg_.assign((size_t)seg_rows * plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
-    fill_pack_seg(plan, h_pack_seg_.data());
-    HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
-    launch_pack(plan);
-    copy_out_packed(plan, out);
-}
-
-void free_packed_impl(mi355vits_packed_result* r) {
-    if (!r || !r->owner_) return;
-    auto* own = static_cast<PackedOwner*>(r->owner_);
-    PinnedPool::get().give(own->bytes, own->cap);
-    free(own->offsets);
-    free(own->lengths);
-    free(own->peaks);
-    delete own;
-    memset(r, 0, sizeof(*r));
-}
-
-// ---------------------------------------------------------------- phoneme timing and levels (mi355vits_fetch_alignment)
-namespace {
-struct AlignOwner {
-    void* block = nullptr;
-    size_t cap = 0;
-};
-}  // namespace
-
-void Engine::fetch_alignment(uint32_t want, mi355vits_alignment* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (want & ~MI355VITS_ALIGN_LEVELS) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: unknown bits in want (" + std::to_string(want) + ")");
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_alignment: no completed run on this handle");
-    HIP_CHECK(hipSetDevice(device_));
-    const bool levels = (want & MI355VITS_ALIGN_LEVELS) != 0;
-    const size_t n = (size_t)B_ * Tx_, arrays = levels ? 5 : 3;
-    // one device block, array after array, in an arena of its own: the last run's buffers (phase A: durations, phase B: audio)
-    // and whatever a fetch laid out behind them stay where they are
-    arena_al_.reserve(5 * n * 4 + 4096, stream_);
-    arena_al_.reset();
-    int* d = arena_al_.alloc<int>(5 * n);
-    float* d_peak = levels ? reinterpret_cast<float*>(d + 3 * n) : nullptr;
-    float* d_rms = levels ? reinterpret_cast<float*>(d + 4 * n) : nullptr;
-    {
-        double audio = 0;
-        for (int b = 0; b < B_; ++b) audio += (double)h_olen_[b];
-        ProfScope ps(prof_, "align", 0, levels ? 4.0 * audio + 20.0 * (double)n : 12.0 * (double)n);
-        launch_align(d_wceil_, d_cum_, d_len_, B_, Tx_, o_audio_, Lo_, o_alen_, cfg_.hop_length, run_L_, run_M_, d, d + n, d + 2 * n,
-                     d_peak, d_rms, stream_);
-    }
-    auto* own = new AlignOwner();
-    out->owner_ = own;
-    own->block = PinnedPool::get().take(arrays * n * 4 + 16, &own->cap);
-    HIP_CHECK(hipMemcpyAsync(own->block, d, arrays * n * 4, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    int32_t* h = static_cast<int32_t*>(own->block);
-    out->batch = B_;
-    out->tx_max = Tx_;
-    out->sample_rate = run_hz_;
-    out->frames = h;
-    out->start = h + n;
-    out->samples = h + 2 * n;
-    out->peak = levels ? reinterpret_cast<float*>(h + 3 * n) : nullptr;
-    out->rms = levels ? reinterpret_cast<float*>(h + 4 * n) : nullptr;
-}
-
-void free_alignment_impl(mi355vits_alignment* r) {
-    if (!r || !r->owner_) return;
-    auto* own = static_cast<AlignOwner*>(r->owner_);
-    PinnedPool::get().give(own->block, own->cap);
-    delete own;
-    memset(r, 0, sizeof(*r));
-}
-
-// ---------------------------------------------------------------- the quiet edges of a run's rows (mi355vits_set_edge_trim / _fetch_edges)
-void Engine::set_edge_trim(float ratio, int keep_samples) {
-    if (!(ratio >= 0.0f && ratio <= 1.0f))  // NaN fails both
-        throw EngineError(MI355VITS_ERR_INVALID, "set_edge_trim: ratio " + std::to_string(ratio) + " is outside [0, 1]");
-    if (keep_samples < 0) throw EngineError(MI355VITS_ERR_INVALID, "set_edge_trim: keep_samples " + std::to_string(keep_samples) + " is negative");
-    trim_ratio_ = ratio;
-    trim_keep_ = keep_samples;
-}
-
-// The raw first / last loud sample of every row of the last run at `ratio` into h_edges_: one launch in an arena of its own, one
-// 8 B byte copy, one synchronisation — or nothing when the host still holds them for this ratio.
-void Engine::find_edges(float ratio) {
-    if (!enqueue_edges(ratio)) return;
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    have_edges_ = true;
-}
-
-bool Engine::enqueue_edges(float ratio) {
-    if (have_edges_ && h_edges_ratio_ == ratio) return false;
-    have_edges_ = false;
-    const int B = B_;
-    arena_ed_.reserve(2 * (size_t)B * 4 + 4096, stream_);
-    arena_ed_.reset();
-    int* d = arena_ed_.alloc<int>(2 * (size_t)B);
-    {
-        double audio = 0;
-        for (int b = 0; b < B; ++b) audio += (double)h_olen_[b];
-        ProfScope ps(prof_, "edges", 0, 4.0 * audio + 8.0 * (double)B);
-        launch_edges(o_audio_, Lo_, o_alen_, o_peaks_, B, Lo_, ratio, d, d + B, stream_);
-    }
-    h_edges_.resize(2 * (size_t)B);
-    HIP_CHECK(hipMemcpyAsync(h_edges_.data(), d, 2 * (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
-    h_edges_ratio_ = ratio;
-    return true;  // have_edges_ once the caller has synchronised
-}
-
-// What a pack needs from the audio before it can be placed: the edges at `ratio` (0: none) and / or the loudness, each launched
-// only when the host does not hold it, behind ONE synchronisation.
-void Engine::measure_last_run(float ratio, bool loud) {
-    const bool e = ratio != 0.0f && enqueue_edges(ratio);
-    const bool l = loud && enqueue_loudness();
-    if (!e && !l) return;
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    if (e) have_edges_ = true;
-    if (l) have_loud_ = true;
-}
-
-// ---------------------------------------------------------------- BS.1770 loudness of a run's rows (mi355vits_set_loudness_target / _fetch_loudness)
-void Engine::set_loudness_target(float target_lufs, float ceiling_dbfs) {
-    if (!(target_lufs == 0.0f || (target_lufs >= -70.0f && target_lufs < 0.0f)))  // NaN fails all
-        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_target: target " + std::to_string(target_lufs) + " LUFS is neither 0 (off) nor in [-70, 0)");
-    if (target_lufs != 0.0f && !(std::isfinite(ceiling_dbfs) && ceiling_dbfs <= 0.0f))
-        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_target: ceiling " + std::to_string(ceiling_dbfs) + " dBFS is not a finite value <= 0");
-    loud_target_ = target_lufs;
-    if (target_lufs != 0.0f) loud_ceiling_ = ceiling_dbfs;
-}
-
-// The gain rule, in double: g = 10^((T - lufs) / 20) (1 for a row without a gated block), bounded by 10^(c / 20) / peak.
-void Engine::loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited) {
-    const double g = std::isinf(lufs) ? 1.0 : std::pow(10.0, ((double)target - lufs) / 20.0);
-    const double p = (double)peak;
-    *gain = g;
-    *limited = false;
-    if (p != 0.0) {
-        const double cap = std::pow(10.0, (double)ceiling / 20.0) / p;
-        if (cap < g) {
-            *gain = cap;
-            *limited = true;
-        }
-    }
-}
-
-// k_loud / k_loud_gate over the last run's rows in an arena of their own, and the copy of 16 B bytes + the peaks; nothing when the
-// host still holds them.
-bool Engine::enqueue_loudness() {
-    if (have_loud_) return false;
-    const int B = B_;
-    LoudnessPlan lp;
-    if (!loudness_plan(run_hz_, lp))
-        throw EngineError(MI355VITS_ERR_INVALID, "loudness: K-weighting is not offered below " + std::to_string(LOUD_MIN_HZ) + " Hz (the run's rate is " + std::to_string(run_hz_) + " Hz)");
-    long l_max = 0;
-    double audio = 0, steps = 0;
-    for (int b = 0; b < B; ++b) {
-        l_max = std::max<long>(l_max, h_olen_[b]);
-        audio += (double)h_olen_[b];
-        steps += (double)loudness_steps(h_olen_[b], lp.S);
-    }
-    const size_t ldE = (size_t)std::max<long>(1, loudness_steps(l_max, lp.S));
-    arena_ld_.reserve(16 * (size_t)B + 8 * (size_t)B * ldE + 4096, stream_);
-    arena_ld_.reset();
-    double* d = arena_ld_.alloc<double>(2 * (size_t)B);
-    double* dE = arena_ld_.alloc<double>((size_t)B * ldE);
-    int* d_blocks = reinterpret_cast<int*>(d + B);
-    {
-        ProfScope ps(prof_, "loudness", 0, 4.0 * audio + 8.0 * steps + 16.0 * (double)B);
-        launch_loudness(run_hz_, o_audio_, Lo_, o_alen_, B, l_max, dE, (long)ldE, d, d_blocks, d_blocks + B, stream_);
-    }
-    h_loud_.resize(2 * (size_t)B);
-    h_loud_peaks_.resize((size_t)B);
-    HIP_CHECK(hipMemcpyAsync(h_loud_.data(), d, 16 * (size_t)B, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(h_loud_peaks_.data(), o_peaks_, 4 * (size_t)B, hipMemcpyDeviceToHost, stream_));
-    return true;  // have_loud_ once the caller has synchronised
-}
-
-namespace {
-struct LoudnessOwner {
-    void* block = nullptr;
-    size_t cap = 0;
-};
-}  // namespace
-
-void Engine::fetch_loudness(mi355vits_loudness* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_loudness: result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_loudness: no completed run on this handle");
-    HIP_CHECK(hipSetDevice(device_));
-    const float target = loud_target_, ceiling = loud_ceiling_;
-    measure_last_run(0.0f, true);
-    const size_t B = (size_t)B_;
-    auto* own = new LoudnessOwner();
-    out->owner_ = own;
-    own->block = PinnedPool::get().take(28 * B + 16, &own->cap);  // lufs, gain: doubles; blocks, gated, limited: int32
-    out->batch = B_;
-    out->sample_rate = run_hz_;
-    out->target_lufs = target;
-    out->ceiling_dbfs = ceiling;
-    out->lufs = static_cast<double*>(own->block);
-    out->gain = out->lufs + B;
-    out->blocks = reinterpret_cast<int32_t*>(out->gain + B);
-    out->gated = out->blocks + B;
-    out->limited = out->gated + B;
-    memcpy(out->lufs, h_loud_.data(), 8 * B);
-    memcpy(out->blocks, h_loud_.data() + B, 8 * B);  // blocks, then gated
-    for (size_t b = 0; b < B; ++b) {
-        double g = 0.0;
-        bool lim = false;
-        if (target != 0.0f) loudness_gain(out->lufs[b], h_loud_peaks_[b], target, ceiling, &g, &lim);
-        out->gain[b] = g;
-        out->limited[b] = lim ? 1 : 0;
-    }
-}
-
-void free_loudness_impl(mi355vits_loudness* r) {
-    if (!r || !r->owner_) return;
-    auto* own = static_cast<LoudnessOwner*>(r->owner_);
-    PinnedPool::get().give(own->block, own->cap);
-    delete own;
-    memset(r, 0, sizeof(*r));
-}
-
-namespace {
-struct EdgesOwner {
-    void* block = nullptr;
-};
-}  // namespace
-
-void Engine::fetch_edges(mi355vits_edges* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "fetch_edges: result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch_edges: no completed run on this handle");
-    HIP_CHECK(hipSetDevice(device_));
-    const float ratio = trim_ratio_;
-    const int keep = trim_keep_;
-    if (ratio != 0.0f) find_edges(ratio);
-    auto* own = new EdgesOwner();
-    out->owner_ = own;
-    own->block = malloc(sizeof(int32_t) * 2 * (size_t)B_);
-    if (!own->block) throw EngineError(MI355VITS_ERR_NOMEM, "out of host memory");
-    out->batch = B_;
-    out->sample_rate = run_hz_;
-    out->ratio = ratio;
-    out->keep_samples = keep;
-    out->first = static_cast<int32_t*>(own->block);
-    out->end = out->first + B_;
-    for (int b = 0; b < B_; ++b) {
-        const int64_t n = h_olen_[b];
-        int64_t first = 0, end = n;
-        if (ratio != 0.0f) {
-            first = std::min<int64_t>(n, std::max<int64_t>(0, (int64_t)h_edges_[b] - keep));
-            end = std::max<int64_t>(first, std::min<int64_t>(n, (int64_t)h_edges_[B_ + b] + 1 + keep));
-        }
-        out->first[b] = (int32_t)first;
-        out->end[b] = (int32_t)end;
-    }
-}
-
-void free_edges_impl(mi355vits_edges* r) {
-    if (!r || !r->owner_) return;
-    auto* own = static_cast<EdgesOwner*>(r->owner_);
-    free(own->block);
-    delete own;
-    memset(r, 0, sizeof(*r));
-}
-
-void Engine::device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths) {
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "device_buffers: no completed run on this handle");
-    HIP_CHECK(hipSetDevice(device_));
-    if (pcm && !have_pcm_) {
-        launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B_, (int)Lo_, d_pcm_, Lo_, stream_, nullptr);
-        have_pcm_ = true;
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));  // the caller reads them from another stream (RCCL)
-    if (pcm) *pcm = d_pcm_;
-    if (audio) *audio = o_audio_;
-    if (row_stride) *row_stride = Lo_;
-    if (batch) *batch = B_;
-    if (dev_lengths) *dev_lengths = o_alen_;
-}
-
-void Engine::fetch(uint32_t want, mi355vits_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (!have_result_) throw EngineError(MI355VITS_ERR_INVALID, "fetch: no completed run on this handle");
-    HIP_CHECK(hipSetDevice(device_));
-    copy_out(want & ~MI355VITS_DEVICE_ONLY, out);
-}
-
-void free_result_impl(mi355vits_result* r) {
-    if (!r || !r->owner_) return;
-    auto* own = static_cast<ResultOwner*>(r->owner_);
-    PinnedPool::get().give(own->audio, own->audio_cap);
-    PinnedPool::get().give(own->pcm, own->pcm_cap);
-    free(own->lengths);
-    free(own->peaks);
-    delete own;
-    memset(r, 0, sizeof(*r));
 }
 
 }  // namespace m355

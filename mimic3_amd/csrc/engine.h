@@ -148,6 +148,17 @@ struct Model {
     ~Model();
 };
 
+// ---------------------------------------------------------------- the handle's settings of the packed streams
+// Written by the setters (which validate), copied whole into a pack's plan when it is made and into a cloned lane.
+struct PackSettings {
+    int enc = PACK_ENC_S16;      // mi355vits_set_output_encoding: MI355VITS_ENC_* = PackEncoding
+    float trim_ratio = 0.0f;     // mi355vits_set_edge_trim: 0 = off
+    int trim_keep = 0;
+    float loud_target = 0.0f, loud_ceiling = -1.0f;  // mi355vits_set_loudness_target: target 0 = off
+    bool trimmed() const { return trim_ratio != 0.0f; }
+    bool normalised() const { return loud_target != 0.0f; }
+};
+
 // ---------------------------------------------------------------- the engine
 class Engine {
   public:
@@ -173,15 +184,15 @@ class Engine {
     void fetch_alignment(uint32_t want, mi355vits_alignment* out);
     // edge trimming of the packed streams (mi355vits_set_edge_trim): ratio 0 = off.  Read when a pack is made and at fetch_edges.
     void set_edge_trim(float ratio, int keep_samples);
-    float edge_trim_ratio() const { return trim_ratio_; }
-    int edge_trim_keep() const { return trim_keep_; }
+    float edge_trim_ratio() const { return pack_.trim_ratio; }
+    int edge_trim_keep() const { return pack_.trim_keep; }
     // first / end of every row of the last completed run under the current setting (mi355vits_fetch_edges)
     void fetch_edges(mi355vits_edges* out);
     // loudness target of the packed streams (mi355vits_set_loudness_target): target 0 = off.  Read when a pack is made and at
     // fetch_loudness.
     void set_loudness_target(float target_lufs, float ceiling_dbfs);
-    float loudness_target() const { return loud_target_; }
-    float loudness_ceiling() const { return loud_ceiling_; }
+    float loudness_target() const { return pack_.loud_target; }
+    float loudness_ceiling() const { return pack_.loud_ceiling; }
     // BS.1770 integrated loudness of every row of the last completed run, and the gains of the current setting (mi355vits_fetch_loudness)
     void fetch_loudness(mi355vits_loudness* out);
     const mi355vits_config& config() const { return cfg_; }
@@ -192,7 +203,7 @@ class Engine {
     int output_rate() const { return out_hz_ ? out_hz_ : cfg_.sample_rate; }
     // the sample encoding of the packed streams (mi355vits_set_output_encoding).  Read when a pack is made.
     void set_output_encoding(int enc);
-    int output_encoding() const { return enc_; }
+    int output_encoding() const { return pack_.enc; }
     Profiler& profiler() { return prof_; }
     float last_run_ms();
     long get_tap(const std::string& name, float* out, size_t cap, int64_t dims[4], long row0 = 0, long nrows = -1);
@@ -234,16 +245,39 @@ class Engine {
     template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
-    // continues layout_b in packed calls, and only there; seg_rows: 3, + 1 in a trimmed pack, + 1 in a normalised one
-    template <typename A> void layout_pack(A& ar, size_t n, size_t samples, int enc, int seg_rows = 3);
+    // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
+    struct PackPlan {
+        int n = 0;
+        bool wav = false;
+        std::vector<int> order;
+        std::vector<int64_t> lead;
+        int64_t tail = 0;
+        PackSettings set;  // the handle's settings when the pack was planned
+        // made by place_pack from the frame counts (trimmed: and the edges; normalised: and the loudness)
+        std::vector<int64_t> offsets, lengths;
+        int64_t total = 0, audio = 0;
+        std::vector<int> skip;     // trimmed only: the first sample of its row each entry starts at
+        std::vector<double> gain;  // normalised only: each entry's linear gain
+        int seg_rows() const { return pack_seg_rows(set.trimmed(), set.normalised()); }
+        int bps() const { return pack_bytes_per_sample(set.enc); }
+        size_t header_bytes() const { return !wav ? 0 : set.enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
+    };
+    // Packed calls only: the plan's segment table and stream, behind everything layout_b placed — no other pointer moves, so a
+    // call that packs nothing runs on the layout it always had.
+    template <typename A> void layout_pack(A& ar, const PackPlan& plan) {
+        d_pack_seg_ = ar.template alloc<int>((size_t)plan.seg_rows() * plan.n);
+        d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(plan.set.enc, (long)plan.total));  // in bytes, the last store's overrun included
+    }
+    // ---- everything behind the waveform: engine_results.cpp
+    // what every fetch starts with: a result struct to fill, zeroed; a completed run to serve; its device current
+    template <typename R> void begin_fetch(R* out, const char* call, bool call_in_null_text = true);
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
     // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
-    struct PackPlan;
     void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan);
     void plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const;  // validates; nothing sized or launched yet
     void place_pack(PackPlan& plan) const;                                           // offsets / total from h_ylen_; the size limits
-    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [3][n]: first sample, row, length (trimmed: [4][n], + first source sample)
+    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [plan.seg_rows()][n] (kernels.h: PACK_SEG_*)
     void launch_pack(const PackPlan& plan);
     void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
@@ -312,17 +346,14 @@ class Engine {
     float* d_rs_coef_ = nullptr;   // rs_.table (an allocation of its own: it outlives the runs)
     int run_hz_ = 0;               // the rate the last run ran at
     int run_L_ = 1, run_M_ = 1;    // its reduced ratio to the voice's rate (1 / 1 native): the handle's setting may have moved on
-    int enc_ = 0;                  // MI355VITS_ENC_* of the packed streams (mi355vits_set_output_encoding): 0 = int16
-    // edge trimming (mi355vits_set_edge_trim): the setting, and the last run's raw first / last loud sample per row at h_edges_ratio_
-    // (kept on the host so a repeated fetch_packed / fetch_edges does not launch again; dropped when a run starts)
-    float trim_ratio_ = 0.0f;
-    int trim_keep_ = 0;
+    PackSettings pack_;            // encoding, edge trimming and loudness target of the packed streams
+    // edge trimming: the last run's raw first / last loud sample per row at h_edges_ratio_ (kept on the host so a repeated
+    // fetch_packed / fetch_edges does not launch again; dropped when a run starts)
     std::vector<int> h_edges_;     // [2][B]: s_first (n when none), s_last (-1)
     float h_edges_ratio_ = 0.0f;
     bool have_edges_ = false;
-    // loudness (mi355vits_set_loudness_target): the setting, and the last run's raw measurement (lufs [B] doubles, blocks [B],
-    // gated [B]) with its peaks, kept on the host so that a fetch at any target launches nothing; dropped when a run starts
-    float loud_target_ = 0.0f, loud_ceiling_ = -1.0f;
+    // loudness: the last run's raw measurement (lufs [B] doubles, blocks [B], gated [B]) with its peaks, kept on the host so that
+    // a fetch at any target launches nothing; dropped when a run starts
     std::vector<double> h_loud_;  // 2 B doubles: lufs, then blocks / gated as int32 pairs
     std::vector<float> h_loud_peaks_;
     bool have_loud_ = false;
@@ -335,7 +366,7 @@ class Engine {
     long Lo_ = 0;                  // row stride and l_max of the results
     std::vector<int64_t> h_olen_;  // [B] valid samples of a row at the run's rate
     int* d_slen_ = nullptr;  // [n_upsamples + 1][B] valid frames per decoder stage
-    // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table [3][n] right behind
+    // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table right behind
     // d_slen_ (one upload brings both) and the stream itself
     int* d_pack_seg_ = nullptr;
     uint8_t* d_pack_ = nullptr;  // pack_capacity_bytes(encoding, total) bytes
@@ -346,10 +377,7 @@ class Engine {
     std::vector<int> h_pack_seg_;     // fetch_packed's segment table (its own upload)
 };
 
-void free_result_impl(mi355vits_result* r);
-void free_packed_impl(mi355vits_packed_result* r);
-void free_alignment_impl(mi355vits_alignment* r);
-void free_edges_impl(mi355vits_edges* r);
-void free_loudness_impl(mi355vits_loudness* r);
+// what the owner_ of any of the five result structs points to goes back: pinned blocks to the pool, heap blocks freed (engine_results.cpp)
+void release_result_owner(void* owner);
 
 }  // namespace m355

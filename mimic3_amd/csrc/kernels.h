@@ -207,30 +207,30 @@ void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, 
 // sample * volume in double, clipped to [-32768, 32767], rounded toward minus infinity.
 void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, const int* valid_len, int B, int L,
                   int16_t* pcm, long pcm_bs, hipStream_t s, const double* volumes = nullptr);
-// The same conversion into ONE contiguous stream (mi355vits_run_packed): entry i = row seg[n + i]'s first seg[2n + i] samples at
-// out[seg[i] ..), entries in ascending order of seg[i]; every other sample of out[0, total) is written as zero (break silences,
-// tail).  seg = [3][n] int32 on the device (first sample, row, length).  out is 16-byte aligned and holds pcm_pack_capacity(total)
-// samples (whole 16-byte stores).  Sample for sample k_pcm16's arithmetic.
-constexpr int PCM_PACK_CHUNK = 2048;  // output samples per work item: 256 lanes x one 16-byte store
-inline size_t pcm_pack_capacity(long total) { return ((size_t)total + 7) & ~size_t(7); }
-// trimmed = true (packs with edge trimming on only): seg = [4][n], the fourth row the first SOURCE sample of the entry — entry i is
-// row seg[n + i]'s samples [seg[3n + i], seg[3n + i] + seg[2n + i]).  false: the three-row table and the instantiation it always had.
-// normalised = true (packs with a loudness target only): one more row behind those, the bits of the entry's f32 scale — 32767 * gain,
-// which replaces 32767 / max(0.01, peak) (PACK_ENC_F32: the gain itself, one f32 multiply per sample).
-void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s, bool trimmed = false, bool normalised = false);
-// The packed stream in another sample encoding (mi355vits_set_output_encoding; kernels_pack.cpp): the same table, the same
-// destination-major walk, one 16-byte store per lane.  PACK_ENC_ULAW / _ALAW: byte k = the G.711 code of the int16 sample
-// k_pcm16_pack stores there, every other byte the code of sample 0 (0xFF / 0xD5); a lane owns 16 samples.  PACK_ENC_F32: the
-// rows' float samples themselves (no normalisation, no volume: peak_bits / volumes are not read), 0.0f elsewhere; a lane owns 4.
-// out is 16-byte aligned and holds pack_capacity_bytes(enc, total) bytes; byte offsets are 64-bit.
+// The same conversion into ONE contiguous stream (mi355vits_run_packed / _fetch_packed; k_pack in kernels_pack.cpp), in the sample
+// encoding the caller ships (mi355vits_set_output_encoding).  Entry i = row seg[row][i]'s first seg[length][i] samples at
+// out[seg[offset][i] ..), entries in ascending order of their offsets; every other sample of out[0, total) is written as the
+// encoding's silence (break silences, tail).  One kernel for all encodings — a destination-major walk, one 16-byte store per lane:
+//   PACK_ENC_S16            sample for sample k_pcm16's arithmetic, silence 0; a lane owns 8 samples
+//   PACK_ENC_ULAW / _ALAW   byte k = the G.711 code of that int16 sample, silence the code of sample 0 (0xFF / 0xD5); a lane owns 16
+//   PACK_ENC_F32            the rows' float samples themselves (no normalisation, no volume: peak_bits / volumes are not read),
+//                           silence 0.0f; a lane owns 4
+// out is 16-byte aligned and holds pack_capacity_bytes(enc, total) bytes (whole 16-byte stores); byte offsets are 64-bit.
 enum PackEncoding { PACK_ENC_S16 = 0, PACK_ENC_ULAW = 1, PACK_ENC_ALAW = 2, PACK_ENC_F32 = 3 };
-inline int pack_bytes_per_sample(int enc) { return enc == PACK_ENC_S16 ? 2 : enc == PACK_ENC_F32 ? 4 : 1; }
-inline size_t pack_capacity_bytes(int enc, long total) {
-    return enc == PACK_ENC_S16 ? 2 * pcm_pack_capacity(total) : ((size_t)total * pack_bytes_per_sample(enc) + 15) & ~size_t(15);
-}
-void launch_pack_encoded(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg,
-                         int n, uint8_t* out, long total, hipStream_t s, bool trimmed = false, bool normalised = false);
+constexpr int pack_bytes_per_sample(int enc) { return enc == PACK_ENC_S16 ? 2 : enc == PACK_ENC_F32 ? 4 : 1; }
+inline size_t pack_capacity_bytes(int enc, long total) { return ((size_t)total * pack_bytes_per_sample(enc) + 15) & ~size_t(15); }
+// The segment table seg = [pack_seg_rows(trimmed, normalised)][n] int32 on the device — its shape is defined here and nowhere else:
+//   PACK_SEG_OFFSET, _ROW, _LENGTH   always: the entry's first sample in the stream, its batch row, its valid samples
+//   PACK_SEG_SKIP                    trimmed (packs with edge trimming on) only: the first SOURCE sample of the entry — entry i is
+//                                    its row's samples [skip, skip + length)
+//   pack_seg_scale_row(trimmed)      normalised (packs with a loudness target) only, behind the others: the bits of the entry's f32
+//                                    scale — 32767 * gain, which replaces 32767 / max(0.01, peak) (PACK_ENC_F32: the gain itself,
+//                                    one f32 multiply per sample)
+enum { PACK_SEG_OFFSET = 0, PACK_SEG_ROW = 1, PACK_SEG_LENGTH = 2, PACK_SEG_SKIP = 3 };
+constexpr int pack_seg_scale_row(bool trimmed) { return trimmed ? 4 : 3; }
+constexpr int pack_seg_rows(bool trimmed, bool normalised) { return pack_seg_scale_row(trimmed) + (normalised ? 1 : 0); }
+void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
+                 uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised);
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 

@@ -18,7 +18,6 @@
 #include <cstring>
 
 #include "kernels.h"
-#include "pcm_quant.h"
 #include <atomic>
 #include <type_traits>
 #include "b3.h"
@@ -2321,126 +2320,6 @@ void launch_pcm16(const float* audio, long audio_bs, const unsigned* peak_bits, 
     int gx = (L + 255) / 256;
     if (gx > 2048) gx = 2048;
     LAUNCH_KERNEL(k_pcm16, dim3(gx, B), dim3(256), 0, s, audio, audio_bs, peak_bits, valid_len, L, pcm, pcm_bs, volumes);
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_pcm16_pack: a batch's int16 audio as one contiguous stream (mi355vits_run_packed / _fetch_packed)
-// ------------------------------------------------------------------------------------------------
-// Destination-major: a work item is one 16-byte-aligned chunk of PCM_PACK_CHUNK output samples, a lane owns 8 consecutive
-// samples of it and writes them with ONE 16-byte store, whatever the (odd) offsets of the rows inside the stream; a persistent
-// grid deals the chunks out in consecutive runs.  Every sample of [0, capacity) has exactly one writer: no atomics, and the silences are zeros
-// because this kernel stores them (the workspace is never assumed clean).
-// One valid sample, operation for operation what k_pcm16 does to it (audio_float_to_int16, then audioop.mul): pcm16_quant, pcm_quant.h
-__device__ __forceinline__ unsigned pcm16_pair(int lo, int hi) { return ((unsigned)lo & 0xffffu) | ((unsigned)hi << 16); }
-
-// TRIM (packs with edge trimming on): the table has a fourth row, the first source sample of each entry
-// NORM (packs with a loudness target): one more row behind the others, the bits of the entry's f32 scale, 32767 * gain, which takes
-// the place of 32767 / max(0.01, peak)
-template <bool TRIM, bool NORM>
-__global__ __launch_bounds__(256) void k_pcm16_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
-                                                    const double* __restrict__ volumes, const int* __restrict__ seg, int n,
-                                                    int16_t* __restrict__ out, long total) {
-    const int* s_off = seg;          // first sample of entry i's audio in the stream, ascending
-    const int* s_row = seg + n;      // its batch row
-    const int* s_len = seg + 2 * n;  // its valid samples
-    const int* s_skip = seg + 3 * n;  // TRIM only: the row's sample the entry starts at
-    const int* s_scale = seg + (TRIM ? 4 : 3) * n;  // NORM only
-    const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
-    // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
-    const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
-    long chunk = blockIdx.x * per + (blockIdx.x < rem ? (long)blockIdx.x : rem);
-    const long chunk_end = chunk + per + (blockIdx.x < rem ? 1 : 0);
-    if (chunk >= chunk_end) return;
-    // the entry the first chunk starts in: the last one whose audio begins at or before the chunk's first sample (-1: the
-    // stream's leading silence).  Uniform per workgroup; afterwards the cursor only moves forward.
-    int e;
-    {
-        const long c0 = chunk * PCM_PACK_CHUNK;
-        int lo = 0, hi = n;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_off[mid] <= c0) lo = mid + 1;
-            else hi = mid;
-        }
-        e = lo - 1;
-    }
-    for (; chunk < chunk_end; ++chunk) {
-        const long c0 = chunk * PCM_PACK_CHUNK;
-        while (e + 1 < n && s_off[e + 1] <= c0) ++e;
-        const long s0 = c0 + 8 * (long)threadIdx.x;
-        if (s0 >= total) continue;  // (the last store of the stream may run up to 7 samples into the buffer's padding)
-        int le = e;
-        while (le + 1 < n && s_off[le + 1] <= s0) ++le;
-        const int lc = le < 0 ? 0 : le;
-        const long off = s_off[lc];
-        const int row = s_row[lc], len = s_len[lc];
-        unsigned w0, w1, w2, w3;
-        if (le >= 0 && s0 + 8 <= off + len) {
-            // all eight samples inside one row's audio: 32 contiguous source bytes, in the widest loads their alignment allows
-            const float* src = audio + (long)row * audio_bs + (TRIM ? s_skip[lc] : 0) + (s0 - off);
-            const float scale = NORM ? __int_as_float(s_scale[lc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
-            const double volume = volumes ? volumes[row] : 1.0;
-            float v0, v1, v2, v3, v4, v5, v6, v7;
-            const uintptr_t al = reinterpret_cast<uintptr_t>(src);
-            if ((al & 15) == 0) {
-                const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-                v0 = a.x; v1 = a.y; v2 = a.z; v3 = a.w; v4 = b.x; v5 = b.y; v6 = b.z; v7 = b.w;
-            } else if ((al & 7) == 0) {
-                const float2 a = *reinterpret_cast<const float2*>(src), b = *reinterpret_cast<const float2*>(src + 2),
-                             c = *reinterpret_cast<const float2*>(src + 4), d = *reinterpret_cast<const float2*>(src + 6);
-                v0 = a.x; v1 = a.y; v2 = b.x; v3 = b.y; v4 = c.x; v5 = c.y; v6 = d.x; v7 = d.y;
-            } else {
-                v0 = src[0]; v1 = src[1]; v2 = src[2]; v3 = src[3]; v4 = src[4]; v5 = src[5]; v6 = src[6]; v7 = src[7];
-            }
-            w0 = pcm16_pair(pcm16_quant(v0, scale, volume), pcm16_quant(v1, scale, volume));
-            w1 = pcm16_pair(pcm16_quant(v2, scale, volume), pcm16_quant(v3, scale, volume));
-            w2 = pcm16_pair(pcm16_quant(v4, scale, volume), pcm16_quant(v5, scale, volume));
-            w3 = pcm16_pair(pcm16_quant(v6, scale, volume), pcm16_quant(v7, scale, volume));
-        } else {
-            // a boundary inside the eight samples (row end, silence, next row's start, head or tail of the stream): sample by
-            // sample with a cursor of its own; loads go through a clamped index, the value is selected afterwards
-            int ce = le;
-            int q[8];
-            MI355_UNROLL
-            for (int k = 0; k < 8; ++k) {
-                const long sp = s0 + k;
-                while (ce + 1 < n && s_off[ce + 1] <= sp) ++ce;
-                const int cc = ce < 0 ? 0 : ce;
-                const long o = s_off[cc];
-                const int r = s_row[cc];
-                const bool valid = ce >= 0 && sp < o + s_len[cc];
-                const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
-                const float scale = NORM ? __int_as_float(s_scale[cc]) : 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[r]));
-                const double volume = volumes ? volumes[r] : 1.0;
-                q[k] = valid ? pcm16_quant(a, scale, volume) : 0;
-            }
-            w0 = pcm16_pair(q[0], q[1]);
-            w1 = pcm16_pair(q[2], q[3]);
-            w2 = pcm16_pair(q[4], q[5]);
-            w3 = pcm16_pair(q[6], q[7]);
-        }
-        uint4 w;
-        w.x = w0; w.y = w1; w.z = w2; w.w = w3;
-        *reinterpret_cast<uint4*>(out + s0) = w;
-    }
-}
-
-void launch_pcm16_pack(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                       int16_t* out, long total, hipStream_t s, bool trimmed, bool normalised) {
-    if (total <= 0 || n <= 0) return;
-    const long nchunks = (total + PCM_PACK_CHUNK - 1) / PCM_PACK_CHUNK;
-    const long gx = std::min<long>(nchunks, 8L * current_device_cu_count());  // 8 workgroups of 4 waves per CU: every SIMD full
-    if (normalised) {
-        if (trimmed) {
-            LAUNCH_KERNEL((k_pcm16_pack<true, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
-        } else {
-            LAUNCH_KERNEL((k_pcm16_pack<false, true>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
-        }
-    } else if (trimmed) {
-        LAUNCH_KERNEL((k_pcm16_pack<true, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
-    } else {
-        LAUNCH_KERNEL((k_pcm16_pack<false, false>), dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------

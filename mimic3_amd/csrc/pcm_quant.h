@@ -1,5 +1,5 @@
-// pcm_quant.h — the one float -> int16 sample conversion every PCM kernel shares (k_pcm16_pack in kernels_conv.cpp, the encoded
-// packed streams in kernels_pack.cpp), and the G.711 companders that work on its result.
+// pcm_quant.h — the one float -> int16 sample conversion of the packed streams (k_pack in kernels_pack.cpp), operation for operation
+// k_pcm16's, and the G.711 companders that work on its result (k_pack, k_g711_encode).
 #pragma once
 #include "hipx.h"
 

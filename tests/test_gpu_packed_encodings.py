@@ -1,4 +1,4 @@
-"""Device twin of tests/test_packed_encodings.py (pytest -m gpu): mi355vits_set_output_encoding and k_pack_enc on the MI355X at
+"""Device twin of tests/test_packed_encodings.py (pytest -m gpu): mi355vits_set_output_encoding and k_pack on the MI355X at
 sizes a user runs.  The yardsticks are the device's own int16 packed stream and padded float rows (both older than the setting),
 the committed audioop tables (tests/golden/g711_tables.npz) and the header builder of tests/g711_ref.py — neither audioop nor
 scipy nor the reference is needed."""
@@ -15,6 +15,8 @@ import g711_ref as G  # noqa: E402
 from mimic3_amd import weights as W  # noqa: E402
 from mimic3_amd._native import Engine  # noqa: E402
 from mimic3_amd.config import VitsConfig  # noqa: E402
+from tests.test_gpu_resample import _ragged as _ragged_case  # noqa: E402
+from tests.test_packed_encodings import check_every_kernel_form  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SEED = 0xC0FFEE
@@ -205,4 +207,13 @@ def test_encoded_streams_on_a_nan_filled_workspace(gpu_hooks, tables):
     for enc in ENCODINGS:
         eng.set_output_encoding(enc)
         assert bytes(eng.fetch_packed(**spec).wav) == want[enc], enc
+    eng.close()
+
+
+def test_every_kernel_form(gpu_lib, tables):
+    """All sixteen forms of the packing kernel (encoding x trimmed x normalised) on the device: six ragged rows of up to 40 ids of
+    the released single-speaker voice's shape, one synthesis, sixteen packs (tests/test_packed_encodings.py)."""
+    cfg = VitsConfig.apope_low()
+    eng = Engine(W.pack(cfg, W.synthetic_weights(cfg, seed=151, frames_per_id=3.0)), device=0, library=gpu_lib)
+    assert len(check_every_kernel_form(eng, _ragged_case(cfg, 17, B=6, hi=40), tables)) == 16
     eng.close()

@@ -1,4 +1,4 @@
-"""Device twin of tests/test_packed_results.py (pytest -m gpu): mi355vits_run_packed / mi355vits_fetch_packed and k_pcm16_pack on
+"""Device twin of tests/test_packed_results.py (pytest -m gpu): mi355vits_run_packed / mi355vits_fetch_packed and k_pack<S16> on
 the MI355X at sizes a user runs — ragged batches of the released voices' shapes (synthetic weights), the benchmark's headline
 shape, one utterance of the streamed-attention class, and a NaN-filled workspace.  The yardstick is the padded call
 (Engine.run(..., want_pcm16=True)) on the same engine + host numpy / postprocess.wav_bytes."""

@@ -1,4 +1,4 @@
-"""The sample encoding of the packed stream (mi355vits_set_output_encoding; k_pack_enc in csrc/kernels_pack.cpp): G.711
+"""The sample encoding of the packed stream (mi355vits_set_output_encoding; k_pack in csrc/kernels_pack.cpp): G.711
 mu-law / A-law bytes or the float samples themselves instead of int16, written by the kernel that packs.  On the CPU model of
 the kernels (tests/emu); test_gpu_packed_encodings.py runs the same contract on the MI355X.
 
@@ -27,7 +27,7 @@ SEED = 0xC0FFEE
 SCALES = np.array([[0.667, 1.0, 0.8], [0.0, 1.6, 0.0], [0.5, 0.7, 0.3], [0.9, 1.2, 1.1], [0.333, 0.85, 0.0]], np.float32)
 KEYS = [7, 1_000_003, 42, (1 << 40) + 5, 3]
 VOLUMES = [50.0, 100.0, 150.0, 300.0, 7.5]  # percent; 300 % clips
-G711_CHUNK = 4096  # output samples of one work item of k_pack_enc in the G.711 forms (256 lanes x 16); the float form: 1024
+G711_CHUNK = 4096  # output samples of one work item of k_pack in the G.711 forms (256 lanes x 16); the float form: 1024
 DEFAULT_CUS = 8
 LAWS = ("ulaw", "alaw")
 ALL_INT16 = np.arange(-32768, 32768, dtype=np.int32).astype(np.int16)
@@ -367,7 +367,7 @@ def test_encoded_streams_on_a_poisoned_workspace(emu_lib, tables):
 
 
 def test_encoded_streams_do_not_depend_on_the_cu_count(emu_lib, cu_count, tables):
-    """k_pack_enc's persistent grid is sized by the compute units: 1, 7 and 256 of them give the default count's bytes — fewer
+    """k_pack's persistent grid is sized by the compute units: 1, 7 and 256 of them give the default count's bytes — fewer
     workgroups than work items, more than work items, and far more."""
     cfg = VitsConfig.tiny()
     blob = W.pack(cfg, W.synthetic_weights(cfg, seed=33))
@@ -399,6 +399,131 @@ def test_encoded_streams_do_not_depend_on_the_cu_count(emu_lib, cu_count, tables
                 assert got[law][58: 58 + s16.size] == G.encode(tables[law], s16).tobytes()
         assert got == want, cus
         eng.close()
+
+
+# ---------------------------------------------------------------------------------------------- every form of the kernel
+KERNEL_FORM_LEADS = [1, 7, 13, 0, 5, 3, 9, 11]  # with a hop that is a multiple of 8, every entry but the fourth starts at an odd offset
+KERNEL_FORM_TAIL = 3
+KERNEL_FORM_TRIM, KERNEL_FORM_TARGET = (0.9, 3), (-23.0, -1.0)
+KERNEL_FORM_ENCODINGS = ("s16le", "ulaw", "alaw", "f32le")
+SILENCE_BITS = {"s16le": 0, "ulaw": G.SILENCE["ulaw"], "alaw": G.SILENCE["alaw"], "f32le": 0}
+
+
+def _kernel_form_streams(eng, a):
+    """ONE synthesis of the batch `a` on `eng`, then a fetch_packed in each of the sixteen forms — a permuted order, odd leading
+    silences, a tail, no header: (the pack arguments, the run's lengths per entry, {(encoding, trimmed, normalised): PackedAudio})."""
+    n = len(a["lens"])
+    assert n <= len(KERNEL_FORM_LEADS)
+    order = [int(b) for b in np.random.default_rng(n).permutation(n)]
+    assert order != sorted(order)
+    spec = dict(order=order, lead_samples=KERNEL_FORM_LEADS[:n], tail_samples=KERNEL_FORM_TAIL)
+    eng.set_edge_trim(0.0)
+    eng.set_loudness_target(None)
+    full = eng.run(a["ids"], a["lens"], a["scales"], a.get("sid"), want_float=False, **a["kw"])
+    lengths = [int(full["lengths"][b]) for b in order]
+    got = {}
+    for enc in KERNEL_FORM_ENCODINGS:
+        eng.set_output_encoding(enc)
+        for trim in (False, True):
+            eng.set_edge_trim(*(KERNEL_FORM_TRIM if trim else (0.0,)))
+            for norm in (False, True):
+                eng.set_loudness_target(*(KERNEL_FORM_TARGET if norm else (None,)))
+                got[enc, trim, norm] = pk = eng.fetch_packed(**spec)
+                assert pk.encoding == enc and pk.wav is None
+    eng.set_edge_trim(0.0)
+    eng.set_loudness_target(None)
+    eng.set_output_encoding("s16le")
+    return spec, lengths, got
+
+
+def check_every_kernel_form(eng, a, tables):
+    """The packing kernel is one template over (encoding, trimmed, normalised): sixteen forms.  One synthesis of the batch `a` on
+    `eng` and a fetch_packed in each form (_kernel_form_streams), and bit for bit:
+      * early against late route: the plain stream of each encoding is what run_packed returns on a fresh lane;
+      * trimmed against untrimmed: entry i is [first[i], end[i]) of the untrimmed entry of the same encoding and target, and
+        offsets / lengths are the running sums of the leads and end - first;
+      * the G.711 entries of every trim / target setting are the table codes of the int16 entries of the same setting;
+      * every sample outside the entries holds the encoding's silence code.
+    Returns {(encoding, trimmed, normalised): the stream's bytes}."""
+    encodings = KERNEL_FORM_ENCODINGS
+    spec, lengths, got = _kernel_form_streams(eng, a)
+    n, lead = len(lengths), spec["lead_samples"]
+    # silence: every sample that belongs to no entry
+    for (enc, trim, norm), pk in got.items():
+        gap = _gap_mask(pk)
+        bits = pk.data.view(np.uint32) if enc == "f32le" else pk.data
+        assert gap.sum() == sum(lead) + KERNEL_FORM_TAIL and (bits[gap] == SILENCE_BITS[enc]).all(), (enc, trim, norm)
+    # early against late route
+    fresh = Engine(eng)  # another lane: no completed run, the same weights
+    fresh.set_edge_trim(0.0)
+    fresh.set_loudness_target(None)
+    for enc in encodings:
+        early = _packed_in(fresh, enc, a["ids"], a["lens"], a["scales"], a.get("sid"), **spec, **a["kw"])
+        late = got[enc, False, False]
+        assert early.data.tobytes() == late.data.tobytes(), enc
+        _same_layout(early, late)
+        assert [int(x) for x in late.lengths] == lengths
+    fresh.close()
+    # trimmed against untrimmed
+    shorter = 0
+    for enc in encodings:
+        for norm in (False, True):
+            whole, cut = got[enc, False, norm], got[enc, True, norm]
+            first, end = cut.first.astype(np.int64), cut.end.astype(np.int64)
+            pos, offsets = 0, []
+            for i in range(n):
+                assert cut.rows[i].tobytes() == whole.rows[i][int(first[i]): int(end[i])].tobytes(), (enc, norm, i)
+                offsets.append(pos + lead[i])
+                pos = offsets[-1] + int(end[i] - first[i])
+            assert [int(x) for x in cut.offsets] == offsets and [int(x) for x in cut.lengths] == [int(x) for x in end - first]
+            assert cut.total_samples == pos + KERNEL_FORM_TAIL
+            shorter += cut.total_samples < whole.total_samples
+    assert shorter == 8  # (the batch's side) trimming at 0.9 of the peak takes something away
+    # G.711 codes of the int16 entries of the same setting
+    for trim in (False, True):
+        for norm in (False, True):
+            s16 = got["s16le", trim, norm]
+            for law in LAWS:
+                pk = got[law, trim, norm]
+                _same_layout(pk, s16)
+                assert np.array_equal(pk.data, G.encode(tables[law], s16.pcm)), (law, trim, norm)
+    assert got["s16le", False, True].data.tobytes() != got["s16le", False, False].data.tobytes()  # the target does something
+    return {k: v.data.tobytes() for k, v in got.items()}
+
+
+def _kernel_form_batch(cfg):
+    """Forced durations on the tiny voice (hop 8): a row of one phoneme x one frame — 8 samples: exactly one int16 lane store,
+    half a G.711 one, two float ones —, a row of 4,224 samples — more than one 4,096-sample G.711 work item, so the chunk cursor
+    and the aligned fast path both run —, and three rows in between."""
+    phonemes, frames = [24, 1, 5, 11, 17], [22, 1, 3, 7, 2]
+    B, Tx = len(phonemes), max(phonemes)
+    rng = np.random.default_rng(29)
+    ids = np.zeros((B, Tx), np.int64)
+    forced = np.zeros((B, Tx), np.int32)
+    for b in range(B):
+        ids[b, : phonemes[b]] = rng.integers(1, cfg.num_symbols, phonemes[b])
+        forced[b, : phonemes[b]] = frames[b]
+    assert phonemes[0] * frames[0] * cfg.hop_length >= 4200 > G711_CHUNK and phonemes[1] * frames[1] * cfg.hop_length == 8
+    return dict(ids=ids, lens=np.array(phonemes, np.int64), sid=None, scales=SCALES,
+                kw=dict(seed=SEED, utterance_keys=KEYS, pcm_volume=np.array(VOLUMES) / 100.0, forced_durations=forced))
+
+
+def test_every_kernel_form(emu_lib, cu_count, tables):
+    """check_every_kernel_form at the smallest shapes the walk can go wrong at; the sixteen streams again with 1 and 13 emulated
+    compute units: the bytes do not move."""
+    cfg = VitsConfig.tiny()
+    blob = W.pack(cfg, W.synthetic_weights(cfg, seed=29))
+    a = _kernel_form_batch(cfg)
+    eng = Engine(blob, library=emu_lib)
+    want = check_every_kernel_form(eng, a, tables)
+    eng.close()
+    assert len(want) == 16
+    for cus in (1, 13):
+        cu_count(cus)
+        eng = Engine(blob, library=emu_lib)
+        got = {k: v.data.tobytes() for k, v in _kernel_form_streams(eng, a)[2].items()}
+        eng.close()
+        assert got == want, cus
 
 
 # ---------------------------------------------------------------------------------------------- the Python layer

@@ -1,4 +1,4 @@
-"""Packed results (mi355vits_run_packed / mi355vits_fetch_packed, k_pcm16_pack): a batch's int16 audio as ONE contiguous
+"""Packed results (mi355vits_run_packed / mi355vits_fetch_packed, k_pack<S16>): a batch's int16 audio as ONE contiguous
 stream — only the valid samples of each row, rows in the order the caller names, break silences between them, optionally
 behind a RIFF header.  On the CPU model of the kernels (tests/emu); test_gpu_packed_results.py runs the same contract on the
 MI355X.
@@ -24,7 +24,7 @@ SEED = 0xC0FFEE
 SCALES = np.array([[0.667, 1.0, 0.8], [0.0, 1.6, 0.0], [0.5, 0.7, 0.3], [0.9, 1.2, 1.1], [0.333, 0.85, 0.0]], np.float32)
 KEYS = [7, 1_000_003, 42, (1 << 40) + 5, 3]
 VOLUMES = [50.0, 100.0, 150.0, 300.0, 7.5]  # percent; 300 % clips
-CHUNK = 2048  # output samples of one work item of k_pcm16_pack (csrc/kernels.h: PCM_PACK_CHUNK)
+CHUNK = 2048  # output samples of one work item of k_pack in its int16 form (csrc/kernels_pack.cpp: 256 lanes x 8)
 DEFAULT_CUS = 8  # what the CPU model reports unless a test sets another count
 
 
@@ -237,7 +237,7 @@ def test_packed_stream_on_a_poisoned_workspace(emu_lib):
 
 
 def test_packed_stream_does_not_depend_on_the_cu_count(emu_lib, cu_count):
-    """k_pcm16_pack's persistent grid is sized by the compute units: 1, 3, 8, 13 and 256 of them give the same bytes.  The tiny
+    """k_pack's persistent grid is sized by the compute units: 1, 3, 8, 13 and 256 of them give the same bytes.  The tiny
     voice's hop is 8, so forced durations of 30 .. 80 frames per id make the stream at least 40 of the kernel's work items — a
     count that is no multiple of 3, 8 or 13 — from rows of unequal length."""
     cfg = VitsConfig.tiny()

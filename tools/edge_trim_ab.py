@@ -4,8 +4,9 @@
 
 On the headline shape (256 rows x 128 ids x 6 forced frames, apope_low shapes, synthetic weights) and on 48 ragged rows (20 .. 128
 ids, natural durations):
-1. the `edges` kernel from mi355vits_profile_report beside `align` with levels and `pcm16.pack` of the same run, and `pcm16.pack`
-   trimmed (at -40 dB with 10 ms kept, and at ratio 0.9, which cuts these noise-like voices deeply) against untrimmed from one synthesis;
+1. the `edges` kernel from mi355vits_profile_report beside `align` with levels and `pcm16.pack` (k_pack<S16>, csrc/kernels_pack.cpp)
+   of the same run, and `pcm16.pack` trimmed (k_pack<S16, TRIM>; at -40 dB with 10 ms kept, and at ratio 0.9, which cuts these
+   noise-like voices deeply) against untrimmed from one synthesis;
 2. host to host: run_packed(wav=True) with trimming off against trimming on at -40 dB with 10 ms kept, and against both the same rule
    on the host — run_packed, the float audio fetched, numpy finds each row's edges, slices and re-joins, postprocess.wav_bytes frames —
    with the two files compared for equality; and fetch_alignment (timing only) on such a run, the project's own measured price of

@@ -4,8 +4,8 @@ DESIGN.md's packed-results section).
   python tools/encodings_ab.py [--reps 7] [--out FILE]
 
 1. Headline shape (256 rows x 128 ids x 6 forced frames, apope_low shapes, synthetic weights): one synthesis per round, then
-   mi355vits_fetch_packed in each encoding — k_pcm16_pack (profile label `pcm16.pack`, 6 B per sample) against k_pack_enc
-   (`pack.ulaw` / `pack.alaw`, 5 B per sample; `pack.f32`, 8 B per sample) from mi355vits_profile_report, with the bytes each
+   mi355vits_fetch_packed in each encoding — the forms of the one kernel k_pack (csrc/kernels_pack.cpp): int16 (profile label `pcm16.pack`,
+   6 B per sample) against G.711 / f32 (`pack.ulaw` / `pack.alaw`, 5 B per sample; `pack.f32`, 8 B per sample) from mi355vits_profile_report, with the bytes each
    copies from the device beside them.
 2. 48 ragged rows (20 .. 128 ids, natural durations) at 8000 Hz to one mu-law WAV with 250 ms breaks, host-to-host:
    run_packed(encoding="ulaw", wav=True) against run_packed(wav=True) + mu-law on the host (audioop.lin2ulaw where the interpreter

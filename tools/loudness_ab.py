@@ -6,7 +6,8 @@ DESIGN.md §4.11 and §6).
 On the headline shape (256 rows x 128 ids x 6 forced frames, apope_low shapes, synthetic weights) and on 48 ragged rows (20 .. 128
 ids, natural durations):
 1. the `loudness` launches (k_loud + k_loud_gate) from mi355vits_profile_report beside `edges`, `align` with levels and `pcm16.pack`
-   of the same run, and `pcm16.pack` with the scale row against without from one synthesis; `loudness` also as bytes / s and as a
+   (k_pack<S16>, csrc/kernels_pack.cpp) of the same run, and `pcm16.pack` with the scale row (k_pack<S16, .., NORM>) against
+   without from one synthesis; `loudness` also as bytes / s and as a
    share of mi355vits_last_run_ms;
 2. host to host, 250 ms breaks, ids in -> file bytes out: run_packed(wav=True) with the target off (bit for bit what it was before
    the setting existed) against loudness = -23 LUFS, and against the host route — run_packed, the float audio fetched, the

@@ -3,7 +3,7 @@
   python tools/packed_ab.py [--reps 7] [--out FILE]
 
 1. Headline shape (256 rows x 128 ids x 6 forced frames, apope_low shapes, synthetic weights): k_pcm16 (profile label
-   `pcm16`) against k_pcm16_pack (`pcm16.pack`) from mi355vits_profile_report — both move 6 B per sample there —, and the
+   `pcm16`) against k_pack<S16> (csrc/kernels_pack.cpp; `pcm16.pack`) from mi355vits_profile_report — both move 6 B per sample there —, and the
    calls' device times (mi355vits_last_run_ms) and host-to-host times.
 2. A ragged batch (48 rows of 20 .. 128 ids, natural durations): host-to-host time to one WAV with 250 ms breaks —
    run_packed(wav=True) against the padded int16 call + postprocess.utterances_to_wav — with the bytes each side copies from the
