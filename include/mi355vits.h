@@ -466,6 +466,78 @@ typedef struct mi355vits_loudness {
 int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out);
 void mi355vits_free_loudness(mi355vits_loudness* r);
 
+/* ---- Packed streams per request: SEVERAL independent streams out of one run.  A server that batches the sentences of many clients
+ * into one synthesis call (one or a few rows per client) wants one finished stream per CLIENT — its own order, silences, header,
+ * encoding, trim and loudness target — not one stream per call.  One kernel (k_pack_streams, csrc/kernels_pack.cpp) writes all of them
+ * into ONE block, and one device-to-host copy of exactly n_bytes brings them back.
+ * Block layout: stream s occupies bytes[stream_offset[s], + stream_bytes[s]) = its RIFF header if asked for (44 bytes for S16LE, 58
+ * otherwise), its data, and the RIFF pad byte behind an odd data size.  Its first data byte sits at data_offset[s], a multiple of 16
+ * (the block itself is page aligned: F32LE / S16LE data can be read in place); streams follow each other in the order given, and every
+ * byte of [0, n_bytes) outside the streams is zero.
+ *  - Stream s: bytes[stream_offset[s], + stream_bytes[s]) is BITWISE what mi355vits_fetch_packed returns for streams[s].pack on the same
+ *    run with the handle set to that stream's encoding, trim and loudness target (mi355vits_set_output_encoding / _set_edge_trim /
+ *    _set_loudness_target) — in every math mode, at the run's output rate, header and pad byte included.  Its entries' offsets (in
+ *    samples within the stream's data) / lengths / peaks and its total_samples are that call's; first[] is the first source sample of
+ *    each entry (0 untrimmed), gain[] / lufs[] / limited[] what mi355vits_fetch_loudness reports for the entry's row at that stream's
+ *    target (all 0 for a stream without one).  Entries are flattened stream after stream: stream s owns [entry_base[s], entry_base[s + 1]).
+ *  - The handle's own encoding, trim and loudness settings are NOT read by the two calls and not changed by them.
+ *  - A row appears at most once within a stream, as in mi355vits_run_packed; it may appear in several streams (the same sentence as
+ *    int16 and as mu-law, say).
+ *  - As for mi355vits_run_packed, MI355VITS_WANT_* / MI355VITS_DEVICE_ONLY are ignored and no padded int16 pass runs; mi355vits_fetch /
+ *    _fetch_packed / _fetch_alignment / _fetch_edges / _fetch_loudness / _device_result serve afterwards what they serve after a
+ *    MI355VITS_DEVICE_ONLY run, and a mi355vits_fetch_streams does not change what they served before it.
+ *  - Synchronisation: mi355vits_run_streams synchronises twice when no stream trims or normalises (the table rides with the per-stage
+ *    length table), three times otherwise; mi355vits_fetch_streams once, or twice.  Loudness is measured once per run, edges once per
+ *    distinct non-zero ratio among the streams, all measurements in front of the same synchronisation.  The host keeps what it
+ *    measured: a repeated fetch at known ratios launches nothing before the pack.
+ *  - One k_pack_streams launch and one device-to-host copy of exactly n_bytes.  With profiling enabled the launch is reported as
+ *    "pack.streams": bytes = 4 * sum(lengths) + n_bytes.
+ *  - Errors are found before anything is sized or launched, return MI355VITS_ERR_INVALID, and the message names the stream:
+ *    "stream 2: pack entry 1: row 9 out of range", "stream 0: unknown encoding 7", "stream 3: trim ratio 1.5 is outside [0, 1]",
+ *    "stream 1: loudness target 3 LUFS is neither 0 (off) nor in [-70, 0)".  The validation rules and the per-stream size limits are
+ *    those of the single-stream calls and their setters; in addition the block is limited: "streams: block of N bytes exceeds
+ *    2^31 - 1".  n_streams < 1 or a NULL array: MI355VITS_ERR_INVALID.  Never partial audio; a mi355vits_run_streams that fails on the
+ *    trimmed sizes leaves no result served, as mi355vits_run_packed does; mi355vits_fetch_streams before any completed run:
+ *    "fetch_streams: no completed run on this handle".
+ *  - Out of scope: alignment in stream coordinates (add offsets to mi355vits_fetch_alignment's spans, or use mi355vits_run_packed), and
+ *    several output rates in one call (the rate is a property of the run). */
+typedef struct mi355vits_stream_args {
+    mi355vits_pack_args pack;   /* entries (batch rows), lead / tail silences, wav_header: as for mi355vits_run_packed */
+    int32_t encoding;           /* MI355VITS_ENC_* of THIS stream */
+    float trim_ratio;           /* 0 = off; as mi355vits_set_edge_trim */
+    int32_t trim_keep_samples;
+    float target_lufs;          /* 0 = off; as mi355vits_set_loudness_target */
+    float ceiling_dbfs;
+} mi355vits_stream_args;
+
+typedef struct mi355vits_streams_result {
+    int32_t n_streams;
+    int32_t n_entries;         /* of all streams together */
+    uint8_t* bytes;            /* the block; pinned, callee-owned */
+    size_t n_bytes;
+    int64_t* stream_offset;    /* [S] first byte of stream s: its header if it has one */
+    int64_t* stream_bytes;     /* [S] header + data + pad */
+    int64_t* data_offset;      /* [S] first data byte of stream s; a multiple of 16 */
+    int64_t* total_samples;    /* [S] silences included */
+    int32_t* encoding;         /* [S] */
+    int32_t* entry_base;       /* [S + 1] stream s owns entries [entry_base[s], entry_base[s + 1]) of the arrays below */
+    int32_t* rows;             /* [E] batch row of the entry */
+    int64_t* offsets;          /* [E] first audio sample of the entry within its stream's data, in samples */
+    int64_t* lengths;          /* [E] */
+    float* peaks;              /* [E] */
+    int32_t* first;            /* [E] first source sample of the entry (0 untrimmed) */
+    double* lufs;              /* [E] of the entry's row; 0 in a stream without a loudness target */
+    double* gain;              /* [E] linear gain the entry carries; 0 likewise */
+    int32_t* limited;          /* [E] */
+    void* owner_;              /* private */
+} mi355vits_streams_result;
+
+int mi355vits_run_streams(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                          const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out);
+/* The LAST completed run of the handle as streams again (whatever flags it had); no synthesis work is repeated. */
+int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out);
+void mi355vits_free_streams(mi355vits_streams_result* r);
+
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid
  * sample counts [batch] (int32, device).  For the optional device-side result gather over RCCL (north star; SURVEY.md

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "mi355vits_fetch_alignment", "mi355vits_free_alignment",
     "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
     "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
+    "mi355vits_run_streams", "mi355vits_fetch_streams", "mi355vits_free_streams",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
@@ -116,6 +117,41 @@ class PackedResult(ctypes.Structure):
         ("offsets", ctypes.POINTER(ctypes.c_int64)),
         ("lengths", ctypes.POINTER(ctypes.c_int64)),
         ("peaks", ctypes.POINTER(ctypes.c_float)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class StreamArgs(ctypes.Structure):
+    _fields_ = [
+        ("pack", PackArgs),
+        ("encoding", ctypes.c_int32),
+        ("trim_ratio", ctypes.c_float),
+        ("trim_keep_samples", ctypes.c_int32),
+        ("target_lufs", ctypes.c_float),
+        ("ceiling_dbfs", ctypes.c_float),
+    ]
+
+
+class StreamsResult(ctypes.Structure):
+    _fields_ = [
+        ("n_streams", ctypes.c_int32),
+        ("n_entries", ctypes.c_int32),
+        ("bytes", ctypes.POINTER(ctypes.c_uint8)),
+        ("n_bytes", ctypes.c_size_t),
+        ("stream_offset", ctypes.POINTER(ctypes.c_int64)),
+        ("stream_bytes", ctypes.POINTER(ctypes.c_int64)),
+        ("data_offset", ctypes.POINTER(ctypes.c_int64)),
+        ("total_samples", ctypes.POINTER(ctypes.c_int64)),
+        ("encoding", ctypes.POINTER(ctypes.c_int32)),
+        ("entry_base", ctypes.POINTER(ctypes.c_int32)),
+        ("rows", ctypes.POINTER(ctypes.c_int32)),
+        ("offsets", ctypes.POINTER(ctypes.c_int64)),
+        ("lengths", ctypes.POINTER(ctypes.c_int64)),
+        ("peaks", ctypes.POINTER(ctypes.c_float)),
+        ("first", ctypes.POINTER(ctypes.c_int32)),
+        ("lufs", ctypes.POINTER(ctypes.c_double)),
+        ("gain", ctypes.POINTER(ctypes.c_double)),
+        ("limited", ctypes.POINTER(ctypes.c_int32)),
         ("owner_", ctypes.c_void_p),
     ]
 
@@ -272,6 +308,11 @@ class NativeLibrary:
         L.mi355vits_fetch_packed.argtypes = [H, ctypes.POINTER(PackArgs), ctypes.POINTER(PackedResult)]
         L.mi355vits_free_packed.argtypes = [ctypes.POINTER(PackedResult)]
         L.mi355vits_free_packed.restype = None
+        L.mi355vits_run_streams.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(StreamArgs), ctypes.c_int32,
+                                            ctypes.POINTER(StreamsResult)]
+        L.mi355vits_fetch_streams.argtypes = [H, ctypes.POINTER(StreamArgs), ctypes.c_int32, ctypes.POINTER(StreamsResult)]
+        L.mi355vits_free_streams.argtypes = [ctypes.POINTER(StreamsResult)]
+        L.mi355vits_free_streams.restype = None
         L.mi355vits_fetch_alignment.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.argtypes = [ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.restype = None
@@ -619,6 +660,28 @@ class _PackedHolder:
             pass
 
 
+class _StreamsHolder:
+    """The same for one ``mi355vits_streams_result``: ONE pinned block shared by the views of all its streams."""
+
+    def __init__(self, native: "NativeLibrary", r: StreamsResult):
+        self._native = native
+        self._r = StreamsResult()
+        ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(StreamsResult))
+
+    def view(self) -> np.ndarray:
+        """Every byte of the block as one uint8 array that owns the holder."""
+        n = int(self._r.n_bytes)
+        buf = (ctypes.c_uint8 * n).from_address(ctypes.addressof(self._r.bytes.contents))
+        buf._holder = self
+        return np.frombuffer(buf, dtype=np.uint8, count=n)
+
+    def __del__(self):
+        try:
+            self._native.lib.mi355vits_free_streams(ctypes.byref(self._r))
+        except Exception:
+            pass
+
+
 class PackedAudio:
     """A batch's audio as one contiguous stream (``mi355vits_run_packed``).  Everything is a view of ONE pinned block that goes
     back to the library when the last view is gone: ``data`` [total_samples] (silences included) in the stream's ``encoding`` —
@@ -635,6 +698,9 @@ class PackedAudio:
         self.first, self.end = first, end
         self.lufs, self.gain, self.limited = lufs, gain, limited
         self.alignment: Optional[Alignment] = None  # set by InferenceSession.run_packed(alignment=...): spans in stream samples
+        # a stream of Engine.run_streams / fetch_streams: the uint8 block all streams of that call share, and this stream's place in
+        # it — block[stream_offset : stream_offset + stream_bytes] = header (if any) + data + pad; data_offset % 16 == 0.  Else None.
+        self.block = self.stream_offset = self.stream_bytes = self.data_offset = None
         self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
         self.encoding = encoding
         self.sample_rate = sample_rate  # of every sample of the stream: the rate the run ran at
@@ -844,6 +910,93 @@ class Engine:
         self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del pkeep
         return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised)
+
+    # ---- several streams out of one run ---------------------------------------------------------
+    @staticmethod
+    def _stream_args(streams, batch: int):
+        """A list of stream dicts — ``order`` (default: every row), ``lead_samples``, ``tail_samples``, ``wav``, ``encoding``
+        (default "s16le"), ``trim=(ratio, keep_samples)``, ``loudness=(lufs, ceiling_db)`` — as an array of
+        ``mi355vits_stream_args``, their count, what the array points into, and (trimmed, normalised) per stream."""
+        known = {"order", "lead_samples", "tail_samples", "wav", "encoding", "trim", "loudness"}
+        streams = list(streams)
+        arr, keep, flags = (StreamArgs * max(1, len(streams)))(), [], []
+        for i, st in enumerate(streams):
+            if set(st) - known:
+                raise ValueError(f"stream {i}: unknown key(s) {sorted(set(st) - known)}")
+            p, pkeep = Engine._pack_args(st.get("order"), st.get("lead_samples"), st.get("tail_samples", 0) or 0, st.get("wav", False))
+            if p is None:
+                p = PackArgs()
+                p.n = -1
+            if p.n < 0:
+                p.n = int(batch)
+            keep.append(pkeep)
+            a = arr[i]
+            a.pack = p
+            a.encoding = encoding_id(st.get("encoding") or "s16le")
+            ratio, tkeep = st.get("trim") or (0.0, 0)
+            a.trim_ratio, a.trim_keep_samples = float(ratio or 0.0), int(tkeep)
+            lufs, ceiling = st.get("loudness") or (0.0, -1.0)
+            a.target_lufs, a.ceiling_dbfs = float(lufs or 0.0), float(-1.0 if ceiling is None else ceiling)
+            flags.append((a.trim_ratio != 0.0, a.target_lufs != 0.0))
+        return arr, len(streams), keep, flags
+
+    def run_streams(self, ids, lengths, scales, sid=None, *, streams, seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None,
+                    forced_durations=None, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> List["PackedAudio"]:
+        """One synthesis call whose result is SEVERAL streams (``mi355vits_run_streams``), one per dict of ``streams``: ``order``
+        (the batch rows of the stream; default: all), ``lead_samples``, ``tail_samples``, ``wav``, ``encoding``, ``trim=(ratio,
+        keep_samples)``, ``loudness=(lufs, ceiling_db)``.  Stream s is bitwise ``fetch_packed`` of the same pack with the handle set to
+        that stream's encoding, trim and target; the handle's own settings are neither read nor changed.  One kernel writes all
+        streams into one pinned block, one device-to-host copy brings it; the ``PackedAudio`` returned per stream are views of it."""
+        a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
+                                            pcm_volume, utterance_keys)
+        a.flags = DEBUG_TAPS if debug_taps else 0
+        arr, n, skeep, flags = self._stream_args(streams, int(a.batch))
+        r = StreamsResult()
+        self._check(self.native.lib.mi355vits_run_streams(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None, arr, n,
+                                                          ctypes.byref(r)))
+        del keep, skeep
+        self._last_batch = int(a.batch)
+        self._last_rate = self.output_rate
+        return self._take_streams(r, flags)
+
+    def fetch_streams(self, streams) -> List["PackedAudio"]:
+        """The last completed run of this handle as streams again (``mi355vits_fetch_streams``); nothing is synthesised again."""
+        arr, n, skeep, flags = self._stream_args(streams, self._last_batch)
+        r = StreamsResult()
+        self._check(self.native.lib.mi355vits_fetch_streams(self._h, arr, n, ctypes.byref(r)))
+        del skeep
+        return self._take_streams(r, flags)
+
+    def _take_streams(self, r: StreamsResult, flags) -> List["PackedAudio"]:
+        """``flags[s]`` = (trimmed, normalised) of stream s: which of ``first`` / ``end`` and ``lufs`` / ``gain`` / ``limited`` it fills."""
+        S, E = int(r.n_streams), int(r.n_entries)
+        try:
+            per_stream = lambda p: np.ctypeslib.as_array(p, shape=(S,)).copy()  # noqa: E731
+            per_entry = lambda p: np.ctypeslib.as_array(p, shape=(E,)).copy()  # noqa: E731
+            begin, nbytes, data_at, totals, encs = (per_stream(p) for p in (r.stream_offset, r.stream_bytes, r.data_offset, r.total_samples, r.encoding))
+            base = np.ctypeslib.as_array(r.entry_base, shape=(S + 1,)).copy()
+            offsets, lens, peaks, first = (per_entry(p) for p in (r.offsets, r.lengths, r.peaks, r.first))
+            lufs, gain, limited = per_entry(r.lufs), per_entry(r.gain), per_entry(r.limited).astype(bool)
+        except BaseException:
+            self.native.lib.mi355vits_free_streams(ctypes.byref(r))
+            raise
+        block = _StreamsHolder(self.native, r).view()  # the views below keep the block alive: no per-stream copy
+        out = []
+        for s in range(S):
+            enc = _ENCODING_NAMES[int(encs[s])]
+            dtype = np.dtype(ENCODINGS[enc][1])
+            e0, e1 = int(base[s]), int(base[s + 1])
+            d0 = int(data_at[s])
+            pcm = block[d0: d0 + dtype.itemsize * int(totals[s])].view(dtype)
+            wav = memoryview(block[int(begin[s]): int(begin[s]) + int(nbytes[s])]) if d0 != int(begin[s]) else None
+            trimmed, normalised = flags[s]
+            out.append(PackedAudio(pcm, offsets[e0:e1], lens[e0:e1], peaks[e0:e1], wav, self._last_rate, enc,
+                                   first[e0:e1] if trimmed else None, first[e0:e1] + lens[e0:e1].astype(first.dtype) if trimmed else None,
+                                   lufs[e0:e1] if normalised else None, gain[e0:e1] if normalised else None,
+                                   limited[e0:e1] if normalised else None))
+            # where the stream sits in the block all streams of the call share
+            out[-1].block, out[-1].stream_offset, out[-1].stream_bytes, out[-1].data_offset = block, int(begin[s]), int(nbytes[s]), d0
+        return out
 
     def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le", order=None, trimmed: bool = False,
                      normalised: bool = False) -> PackedAudio:

@@ -177,6 +177,20 @@ int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, 
 
 void mi355vits_free_packed(mi355vits_packed_result* r) { free_struct(r); }
 
+int mi355vits_run_streams(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                          const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
+    return result_call(h, out, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        h->eng->run_streams(*args, rows, streams, n_streams, out);
+    });
+}
+
+int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
+    return result_call(h, out, [&] { h->eng->fetch_streams(streams, n_streams, out); });
+}
+
+void mi355vits_free_streams(mi355vits_streams_result* r) { free_struct(r); }
+
 int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out) {
     return result_call(h, out, [&] { h->eng->fetch_alignment(want, out); });
 }

@@ -180,6 +180,11 @@ class Engine {
     void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
                     mi355vits_packed_result* out);
     void fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out);
+    // several streams out of one run (mi355vits_run_streams / mi355vits_fetch_streams): each with its own pack, encoding, trim and
+    // loudness target; the handle's own settings are neither read nor changed
+    void run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
+                     mi355vits_streams_result* out);
+    void fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out);
     // phoneme timing (and, with MI355VITS_ALIGN_LEVELS, levels) of the last completed run (mi355vits_fetch_alignment)
     void fetch_alignment(uint32_t want, mi355vits_alignment* out);
     // edge trimming of the packed streams (mi355vits_set_edge_trim): ratio 0 = off.  Read when a pack is made and at fetch_edges.
@@ -262,6 +267,22 @@ class Engine {
         int bps() const { return pack_bytes_per_sample(set.enc); }
         size_t header_bytes() const { return !wav ? 0 : set.enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
     };
+    // what a streams call puts where: one PackPlan per stream (with that stream's settings), then the streams' places in the block
+    struct StreamsPlan {
+        std::vector<PackPlan> streams;
+        std::vector<int64_t> begin, data;  // block byte offset of each stream's first byte (its header) / first data byte (16-byte aligned)
+        int64_t n_bytes = 0, audio = 0;    // the block; the audio samples in it
+        int entries = 0;
+        bool measured() const {            // some stream trims or normalises: the places depend on the audio
+            for (const PackPlan& p : streams)
+                if (p.set.trimmed() || p.set.normalised()) return true;
+            return false;
+        }
+    };
+    template <typename A> void layout_streams(A& ar, const StreamsPlan& sp) {
+        d_pack_seg_ = ar.template alloc<int>(pack_streams_table_words(sp.entries, (int)sp.streams.size()));
+        d_pack_ = ar.template alloc<uint8_t>(pack_streams_capacity((long)sp.n_bytes));
+    }
     // Packed calls only: the plan's segment table and stream, behind everything layout_b placed — no other pointer moves, so a
     // call that packs nothing runs on the layout it always had.
     template <typename A> void layout_pack(A& ar, const PackPlan& plan) {
@@ -274,17 +295,28 @@ class Engine {
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
     // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
-    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan);
-    void plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const;  // validates; nothing sized or launched yet
+    // (or with a streams plan the block of streams, likewise)
+    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan, StreamsPlan* streams = nullptr);
+    void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
     void place_pack(PackPlan& plan) const;                                           // offsets / total from h_ylen_; the size limits
     void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [plan.seg_rows()][n] (kernels.h: PACK_SEG_*)
     void launch_pack(const PackPlan& plan);
     void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
+    void plan_streams(const mi355vits_stream_args* streams, int n_streams, int B, StreamsPlan& sp) const;  // validates every stream, naming it
+    void place_streams(StreamsPlan& sp) const;                          // place_pack per stream, then the block's layout and its limit
+    void fill_streams_table(const StreamsPlan& sp, int* tab) const;     // kernels.h: PACK_ENT_* / PACK_STREAM_*
+    void launch_streams(const StreamsPlan& sp);
+    void streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out);  // fetch_streams behind its checks; the second half of a measured run_streams
+    void copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out);
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
     void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
-    bool enqueue_edges(float ratio);  // k_edges and its copy on the stream unless the host holds the edges of `ratio`; true: a synchronisation is owed
+    // k_edges and its copy on the stream for each of the distinct non-zero `ratios` the host does not hold; true: a synchronisation is
+    // owed.  keep: what the host holds at other ratios stays (a streams call); else the ratio measured replaces it, as ever
+    bool enqueue_edges(const std::vector<float>& ratios, bool keep);
+    const std::vector<int>& edges_at(float ratio) const;  // [2][B] of the last run at a ratio the host holds
     bool enqueue_loudness();          // k_loud / k_loud_gate and their copy likewise (throws below LOUD_MIN_HZ)
-    void measure_last_run(float ratio, bool loud);  // what a pack needs from the audio: both launches, then ONE synchronisation (or none)
+    // what a pack needs from the audio: every launch, then ONE synchronisation (or none)
+    void measure_last_run(const std::vector<float>& ratios, bool loud, bool keep);
     static void loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited);
 
     mi355vits_config cfg_{};
@@ -347,11 +379,16 @@ class Engine {
     int run_hz_ = 0;               // the rate the last run ran at
     int run_L_ = 1, run_M_ = 1;    // its reduced ratio to the voice's rate (1 / 1 native): the handle's setting may have moved on
     PackSettings pack_;            // encoding, edge trimming and loudness target of the packed streams
-    // edge trimming: the last run's raw first / last loud sample per row at h_edges_ratio_ (kept on the host so a repeated
-    // fetch_packed / fetch_edges does not launch again; dropped when a run starts)
-    std::vector<int> h_edges_;     // [2][B]: s_first (n when none), s_last (-1)
-    float h_edges_ratio_ = 0.0f;
-    bool have_edges_ = false;
+    // edge trimming: the last run's raw first / last loud sample per row at each ratio measured so far (kept on the host so a
+    // repeated fetch_packed / fetch_streams / fetch_edges does not launch again; dropped when a run starts).  A single-stream call
+    // at a ratio not held replaces them by that one; a streams call adds its distinct ratios.
+    struct EdgeSet {
+        float ratio;
+        std::vector<int> edges;  // [2][B]: s_first (n when none), s_last (-1)
+        bool ready;              // the copy has been synchronised
+    };
+    std::vector<EdgeSet> h_edges_;
+    bool have_edges_ = false;      // false: a run has started since, h_edges_ is of an earlier run
     // loudness: the last run's raw measurement (lufs [B] doubles, blocks [B], gated [B]) with its peaks, kept on the host so that
     // a fetch at any target launches nothing; dropped when a run starts
     std::vector<double> h_loud_;  // 2 B doubles: lufs, then blocks / gated as int32 pairs

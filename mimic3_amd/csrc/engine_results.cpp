@@ -204,7 +204,8 @@ void trimmed_span(int64_t n, int64_t first_loud, int64_t last_loud, int64_t keep
 // module writes (PCM, format tag 1).  Any other encoding: the non-PCM form — an 18-byte fmt chunk with cbSize 0, then a fact chunk with
 // the sample count —, 58 bytes, what scipy.io.wavfile.write puts in front of float32 data; format tag 7 = mu-law, 6 = A-law,
 // 3 = IEEE float.  RIFF chunks are word-aligned: behind an odd data size (G.711 only) goes one zero byte, written here as well.
-void write_wav_header(uint8_t* h, int enc, uint32_t rate, int64_t total, size_t data) {
+// (with_pad = false: the header's own bytes only — a streams block, whose pad bytes the kernel writes)
+void write_wav_header(uint8_t* h, int enc, uint32_t rate, int64_t total, size_t data, bool with_pad = true) {
     const bool pcm = enc == PACK_ENC_S16;
     const uint32_t bps = (uint32_t)pack_bytes_per_sample(enc), pad = (uint32_t)(data & 1);
     size_t at = 0;
@@ -230,16 +231,16 @@ void write_wav_header(uint8_t* h, int enc, uint32_t rate, int64_t total, size_t 
     }
     tag("data");
     u32((uint32_t)data);
-    if (pad) h[at + data] = 0;
+    if (pad && with_pad) h[at + data] = 0;
 }
 }  // namespace
 
 // Everything that can be wrong with the pack arguments alone, before anything is sized or launched.
-void Engine::plan_pack(const mi355vits_pack_args* pack, int B, PackPlan& plan) const {
+void Engine::plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const {
     plan.n = pack ? pack->n : B;
     if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
     plan.wav = pack && pack->wav_header != 0;
-    plan.set = pack_;  // the settings are read here: when a pack is made
+    plan.set = set;  // the handle's settings are read by the caller: when a pack is made (a streams call brings each stream's own)
     plan.tail = pack ? pack->tail_samples : 0;
     plan.order.resize(plan.n);
     plan.lead.assign(plan.n, 0);
@@ -280,7 +281,8 @@ void Engine::place_pack(PackPlan& plan) const {
         plan.lengths[i] = h_olen_[row];  // at the run's rate
         if (set.trimmed()) {
             int64_t first, end;
-            trimmed_span(h_olen_[row], h_edges_[row], h_edges_[B_ + row], set.trim_keep, &first, &end);
+            const std::vector<int>& ed = edges_at(set.trim_ratio);
+            trimmed_span(h_olen_[row], ed[row], ed[B_ + row], set.trim_keep, &first, &end);
             plan.skip[i] = (int)first;
             plan.lengths[i] = end - first;
         }
@@ -351,7 +353,7 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
     memset(out, 0, sizeof(*out));
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     PackPlan plan;
-    plan_pack(pack, args.batch, plan);
+    plan_pack(pack, args.batch, pack_, plan);
     if (!plan.set.trimmed() && !plan.set.normalised()) {
         synthesize(args, rows, &plan);
         copy_out_packed(plan, out);
@@ -375,13 +377,13 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
 void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
     begin_fetch(out, "fetch_packed", false);
     PackPlan plan;
-    plan_pack(pack, B_, plan);
+    plan_pack(pack, B_, pack_, plan);
     pack_last_run(plan, out);
 }
 
 void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipSetDevice(device_));
-    measure_last_run(plan.set.trim_ratio, plan.set.normalised());
+    measure_last_run({plan.set.trim_ratio}, plan.set.normalised(), false);
     place_pack(plan);
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
@@ -400,6 +402,228 @@ void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
     launch_pack(plan);
     copy_out_packed(plan, out);
+}
+
+// ---------------------------------------------------------------- several streams of one run (mi355vits_run_streams / mi355vits_fetch_streams)
+namespace {
+std::string fmt_g(double v) {
+    char b[64];
+    snprintf(b, sizeof b, "%g", v);
+    return b;
+}
+constexpr int64_t STREAMS_MAX_BYTES = 0x7fffffffLL;  // the block's offsets fit the table's words
+}  // namespace
+
+// Everything that can be wrong with the arguments alone: each stream's settings by the rules of the setters, its pack by plan_pack's.
+void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, int B, StreamsPlan& sp) const {
+    if (!streams || n_streams < 1)
+        throw EngineError(MI355VITS_ERR_INVALID, "streams: a non-null array of n_streams >= 1 streams is required (n_streams = " + std::to_string(n_streams) + ")");
+    sp.streams.assign((size_t)n_streams, PackPlan());
+    sp.entries = 0;
+    for (int s = 0; s < n_streams; ++s) {
+        const mi355vits_stream_args& a = streams[s];
+        const std::string name = "stream " + std::to_string(s) + ": ";
+        auto bad = [&](const std::string& what) { return EngineError(MI355VITS_ERR_INVALID, name + what); };
+        if (a.encoding != MI355VITS_ENC_S16LE && a.encoding != MI355VITS_ENC_ULAW && a.encoding != MI355VITS_ENC_ALAW && a.encoding != MI355VITS_ENC_F32LE)
+            throw bad("unknown encoding " + std::to_string(a.encoding) + " (0 = s16le, 1 = ulaw, 2 = alaw, 3 = f32le)");
+        if (!(a.trim_ratio >= 0.0f && a.trim_ratio <= 1.0f)) throw bad("trim ratio " + fmt_g(a.trim_ratio) + " is outside [0, 1]");  // NaN fails both
+        if (a.trim_keep_samples < 0) throw bad("trim keep_samples " + std::to_string(a.trim_keep_samples) + " is negative");
+        if (!(a.target_lufs == 0.0f || (a.target_lufs >= -70.0f && a.target_lufs < 0.0f)))
+            throw bad("loudness target " + fmt_g(a.target_lufs) + " LUFS is neither 0 (off) nor in [-70, 0)");
+        if (a.target_lufs != 0.0f && !(std::isfinite(a.ceiling_dbfs) && a.ceiling_dbfs <= 0.0f))
+            throw bad("loudness ceiling " + fmt_g(a.ceiling_dbfs) + " dBFS is not a finite value <= 0");
+        PackSettings set;
+        set.enc = a.encoding;
+        set.trim_ratio = a.trim_ratio;
+        set.trim_keep = a.trim_keep_samples;
+        set.loud_target = a.target_lufs;
+        if (a.target_lufs != 0.0f) set.loud_ceiling = a.ceiling_dbfs;
+        try {
+            plan_pack(&a.pack, B, set, sp.streams[s]);
+        } catch (const EngineError& e) {
+            throw EngineError(e.code, name + e.what());
+        }
+        sp.entries += sp.streams[s].n;
+    }
+}
+
+// Every stream placed as its own pack, then the streams in the block: each one's first data byte at the next multiple of 16 that
+// leaves room for its header, the header right in front of it, the RIFF pad byte behind an odd data size.
+void Engine::place_streams(StreamsPlan& sp) const {
+    const size_t S = sp.streams.size();
+    sp.begin.resize(S);
+    sp.data.resize(S);
+    sp.audio = 0;
+    int64_t pos = 0;
+    for (size_t s = 0; s < S; ++s) {
+        PackPlan& p = sp.streams[s];
+        try {
+            place_pack(p);
+        } catch (const EngineError& e) {
+            throw EngineError(e.code, "stream " + std::to_string(s) + ": " + e.what());
+        }
+        const int64_t hdr = (int64_t)p.header_bytes(), bytes = (int64_t)p.bps() * p.total;
+        sp.data[s] = (pos + hdr + 15) & ~int64_t(15);
+        sp.begin[s] = sp.data[s] - hdr;
+        pos = sp.data[s] + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
+        sp.audio += p.audio;
+        if (pos > STREAMS_MAX_BYTES) {
+            // (what the remaining streams add only makes it larger: the size named is the block up to this stream)
+            throw EngineError(MI355VITS_ERR_INVALID, "streams: block of " + std::to_string(pos) + " bytes exceeds 2^31 - 1");
+        }
+    }
+    sp.n_bytes = pos;
+}
+
+void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
+    const size_t n = (size_t)sp.entries;
+    int* st = tab + PACK_ENT_ROWS * n;
+    size_t e = 0;
+    for (size_t s = 0; s < sp.streams.size(); ++s) {
+        const PackPlan& p = sp.streams[s];
+        const PackSettings& set = p.set;
+        const int64_t bytes = (int64_t)p.bps() * p.total;
+        for (int i = 0; i < p.n; ++i, ++e) {
+            tab[PACK_ENT_OFFSET * n + e] = (int)(sp.data[s] + (int64_t)p.bps() * p.offsets[i]);
+            tab[PACK_ENT_ROW * n + e] = p.order[i];
+            tab[PACK_ENT_LENGTH * n + e] = (int)p.lengths[i];
+            tab[PACK_ENT_SKIP * n + e] = set.trimmed() ? p.skip[i] : 0;
+            tab[PACK_ENT_ENC * n + e] = set.enc | (set.normalised() ? (int)PACK_ENT_SCALED : 0);
+            float scale = 0.0f;  // fill_pack_seg's: 32767 * gain in double, rounded once (F32LE: the gain itself)
+            if (set.normalised()) scale = set.enc == PACK_ENC_F32 ? (float)p.gain[i] : (float)(32767.0 * p.gain[i]);
+            memcpy(&tab[PACK_ENT_SCALE * n + e], &scale, 4);
+        }
+        int* r = st + PACK_STREAM_WORDS * s;
+        r[PACK_STREAM_BEGIN] = (int)sp.begin[s];
+        r[PACK_STREAM_DATA] = (int)sp.data[s];
+        r[PACK_STREAM_END] = (int)(sp.data[s] + bytes);
+        r[PACK_STREAM_ENC] = set.enc;
+        uint8_t h[4 * (PACK_STREAM_WORDS - PACK_STREAM_HEADER)] = {0};
+        if (p.wav) write_wav_header(h, set.enc, (uint32_t)run_hz_, p.total, (size_t)bytes, false);  // the rate the run ran at
+        for (int k = 0; k < PACK_STREAM_WORDS - PACK_STREAM_HEADER; ++k)
+            r[PACK_STREAM_HEADER + k] = (int)((uint32_t)h[4 * k] | ((uint32_t)h[4 * k + 1] << 8) | ((uint32_t)h[4 * k + 2] << 16) | ((uint32_t)h[4 * k + 3] << 24));
+    }
+}
+
+void Engine::launch_streams(const StreamsPlan& sp) {
+    ProfScope ps(prof_, "pack.streams", 0, 4.0 * (double)sp.audio + (double)sp.n_bytes);
+    launch_pack_streams(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, sp.entries, (int)sp.streams.size(), d_pack_, (long)sp.n_bytes, stream_);
+}
+
+void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out) {
+    const size_t S = sp.streams.size(), E = (size_t)sp.entries;
+    Owner* own = new_owner(out);
+    out->n_streams = (int32_t)S;
+    out->n_entries = (int32_t)E;
+    out->stream_offset = own->alloc<int64_t>(S);
+    out->stream_bytes = own->alloc<int64_t>(S);
+    out->data_offset = own->alloc<int64_t>(S);
+    out->total_samples = own->alloc<int64_t>(S);
+    out->encoding = own->alloc<int32_t>(S);
+    out->entry_base = own->alloc<int32_t>(S + 1);
+    out->rows = own->alloc<int32_t>(E);
+    out->offsets = own->alloc<int64_t>(E);
+    out->lengths = own->alloc<int64_t>(E);
+    out->peaks = own->alloc<float>(E);
+    out->first = own->alloc<int32_t>(E);
+    out->lufs = own->alloc<double>(E);
+    out->gain = own->alloc<double>(E);
+    out->limited = own->alloc<int32_t>(E);
+    out->bytes = static_cast<uint8_t*>(own->take_pinned((size_t)sp.n_bytes + 16));
+    out->n_bytes = (size_t)sp.n_bytes;
+    std::vector<unsigned> pk(B_);
+    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, (size_t)sp.n_bytes, hipMemcpyDeviceToHost, stream_));  // exactly the block: finished files
+    size_t e = 0;
+    for (size_t s = 0; s < S; ++s) {
+        const PackPlan& p = sp.streams[s];
+        const int64_t bytes = (int64_t)p.bps() * p.total;
+        out->stream_offset[s] = sp.begin[s];
+        out->data_offset[s] = sp.data[s];
+        out->stream_bytes[s] = (sp.data[s] - sp.begin[s]) + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
+        out->total_samples[s] = p.total;
+        out->encoding[s] = p.set.enc;
+        out->entry_base[s] = (int32_t)e;
+        for (int i = 0; i < p.n; ++i, ++e) {
+            const int row = p.order[i];
+            out->rows[e] = row;
+            out->offsets[e] = p.offsets[i];
+            out->lengths[e] = p.lengths[i];
+            out->first[e] = p.set.trimmed() ? p.skip[i] : 0;
+            out->lufs[e] = out->gain[e] = 0.0;
+            out->limited[e] = 0;
+            if (p.set.normalised()) {
+                bool lim = false;
+                out->lufs[e] = h_loud_[row];
+                loudness_gain(h_loud_[row], h_loud_peaks_[row], p.set.loud_target, p.set.loud_ceiling, &out->gain[e], &lim);
+                out->limited[e] = lim ? 1 : 0;
+            }
+        }
+    }
+    out->entry_base[S] = (int32_t)e;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (size_t i = 0; i < E; ++i) memcpy(&out->peaks[i], &pk[out->rows[i]], 4);
+}
+
+void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
+                         mi355vits_streams_result* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
+    StreamsPlan sp;
+    plan_streams(streams, n_streams, args.batch, sp);
+    if (!sp.measured()) {
+        synthesize(args, rows, nullptr, &sp);
+        copy_out_streams(sp, out);
+        return;
+    }
+    // Some stream trims or normalises: as a trimmed run_packed — synthesise without an early table and without the padded int16
+    // pass, measure (ONE synchronisation), then what fetch_streams does.  A limit exceeded by the trimmed sizes leaves no result served.
+    mi355vits_run_args a = args;
+    a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
+    synthesize(a, rows, nullptr);
+    try {
+        streams_last_run(sp, out);
+        HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its measurements and its pack
+    } catch (...) {
+        have_result_ = false;
+        throw;
+    }
+}
+
+void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out) {
+    begin_fetch(out, "fetch_streams");
+    StreamsPlan sp;
+    plan_streams(streams, n_streams, B_, sp);
+    streams_last_run(sp, out);
+}
+
+void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
+    HIP_CHECK(hipSetDevice(device_));
+    std::vector<float> ratios;
+    bool loud = false;
+    for (const PackPlan& p : sp.streams) {
+        ratios.push_back(p.set.trim_ratio);
+        loud = loud || p.set.normalised();
+    }
+    measure_last_run(ratios, loud, true);
+    place_streams(sp);
+    // where pack_last_run puts its buffers: behind the last run's frame-side layout where the arena has room, else in arena_p_
+    ArenaCount need;
+    layout_streams(need, sp);
+    if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
+        arena_b_.rewind(layout_b_end_);
+        layout_streams(arena_b_, sp);
+    } else {
+        arena_p_.reserve(need.bytes + 4096, stream_);
+        arena_p_.reset();
+        layout_streams(arena_p_, sp);
+    }
+    h_pack_seg_.assign(pack_streams_table_words(sp.entries, (int)sp.streams.size()), 0);
+    fill_streams_table(sp, h_pack_seg_.data());
+    HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
+    launch_streams(sp);
+    copy_out_streams(sp, out);
 }
 
 // ---------------------------------------------------------------- phoneme timing and levels (mi355vits_fetch_alignment)
@@ -447,39 +671,54 @@ void Engine::set_edge_trim(float ratio, int keep_samples) {
 
 // The raw first / last loud sample of every row of the last run at `ratio` into h_edges_: one launch in an arena of its own, one
 // 8 B byte copy, one synchronisation — or nothing when the host still holds them for this ratio.
-void Engine::find_edges(float ratio) {
-    if (!enqueue_edges(ratio)) return;
-    HIP_CHECK(hipStreamSynchronize(stream_));
+void Engine::find_edges(float ratio) { measure_last_run({ratio}, false, false); }
+
+const std::vector<int>& Engine::edges_at(float ratio) const {
+    if (have_edges_)
+        for (const EdgeSet& e : h_edges_)
+            if (e.ready && e.ratio == ratio) return e.edges;
+    throw EngineError(MI355VITS_ERR_INTERNAL, "edges of ratio " + std::to_string(ratio) + " were not measured");
+}
+
+bool Engine::enqueue_edges(const std::vector<float>& ratios, bool keep) {
+    if (!have_edges_) h_edges_.clear();  // of an earlier run
     have_edges_ = true;
-}
-
-bool Engine::enqueue_edges(float ratio) {
-    if (have_edges_ && h_edges_ratio_ == ratio) return false;
-    have_edges_ = false;
-    const int B = B_;
-    arena_ed_.reserve(2 * (size_t)B * 4 + 4096, stream_);
-    arena_ed_.reset();
-    int* d = arena_ed_.alloc<int>(2 * (size_t)B);
-    {
-        double audio = 0;
-        for (int b = 0; b < B; ++b) audio += (double)h_olen_[b];
-        ProfScope ps(prof_, "edges", 0, 4.0 * audio + 8.0 * (double)B);
-        launch_edges(o_audio_, Lo_, o_alen_, o_peaks_, B, Lo_, ratio, d, d + B, stream_);
+    h_edges_.erase(std::remove_if(h_edges_.begin(), h_edges_.end(), [](const EdgeSet& e) { return !e.ready; }), h_edges_.end());  // a copy that failed
+    std::vector<float> todo;  // the distinct non-zero ratios the host does not hold
+    for (float r : ratios) {
+        bool held = r == 0.0f || std::find(todo.begin(), todo.end(), r) != todo.end();
+        for (const EdgeSet& e : h_edges_) held = held || e.ratio == r;
+        if (!held) todo.push_back(r);
     }
-    h_edges_.resize(2 * (size_t)B);
-    HIP_CHECK(hipMemcpyAsync(h_edges_.data(), d, 2 * (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
-    h_edges_ratio_ = ratio;
-    return true;  // have_edges_ once the caller has synchronised
+    if (todo.empty()) return false;
+    if (!keep) h_edges_.clear();
+    const int B = B_;
+    arena_ed_.reserve(todo.size() * DeviceArena::padded(2 * (size_t)B * 4) + 4096, stream_);
+    arena_ed_.reset();
+    double audio = 0;
+    for (int b = 0; b < B; ++b) audio += (double)h_olen_[b];
+    h_edges_.reserve(h_edges_.size() + todo.size());
+    for (float ratio : todo) {
+        int* d = arena_ed_.alloc<int>(2 * (size_t)B);
+        {
+            ProfScope ps(prof_, "edges", 0, 4.0 * audio + 8.0 * (double)B);
+            launch_edges(o_audio_, Lo_, o_alen_, o_peaks_, B, Lo_, ratio, d, d + B, stream_);
+        }
+        h_edges_.push_back(EdgeSet{ratio, std::vector<int>(2 * (size_t)B), false});
+        HIP_CHECK(hipMemcpyAsync(h_edges_.back().edges.data(), d, 2 * (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    }
+    return true;  // ready once the caller has synchronised
 }
 
-// What a pack needs from the audio before it can be placed: the edges at `ratio` (0: none) and / or the loudness, each launched
-// only when the host does not hold it, behind ONE synchronisation.
-void Engine::measure_last_run(float ratio, bool loud) {
-    const bool e = ratio != 0.0f && enqueue_edges(ratio);
+// What a pack needs from the audio before it can be placed: the edges at each of `ratios` (0: none) and / or the loudness, each
+// launched only when the host does not hold it, behind ONE synchronisation.
+void Engine::measure_last_run(const std::vector<float>& ratios, bool loud, bool keep) {
+    const bool e = enqueue_edges(ratios, keep);
     const bool l = loud && enqueue_loudness();
     if (!e && !l) return;
     HIP_CHECK(hipStreamSynchronize(stream_));
-    if (e) have_edges_ = true;
+    if (e)
+        for (EdgeSet& s : h_edges_) s.ready = true;
     if (l) have_loud_ = true;
 }
 
@@ -543,7 +782,7 @@ bool Engine::enqueue_loudness() {
 void Engine::fetch_loudness(mi355vits_loudness* out) {
     begin_fetch(out, "fetch_loudness");
     const float target = pack_.loud_target, ceiling = pack_.loud_ceiling;
-    measure_last_run(0.0f, true);
+    measure_last_run({}, true, false);
     const size_t B = (size_t)B_;
     out->batch = B_;
     out->sample_rate = run_hz_;
@@ -576,10 +815,11 @@ void Engine::fetch_edges(mi355vits_edges* out) {
     out->keep_samples = keep;
     out->first = new_owner(out)->alloc<int32_t>(2 * (size_t)B_);
     out->end = out->first + B_;
+    const std::vector<int>* ed = ratio != 0.0f ? &edges_at(ratio) : nullptr;
     for (int b = 0; b < B_; ++b) {
         const int64_t n = h_olen_[b];
         int64_t first = 0, end = n;
-        if (ratio != 0.0f) trimmed_span(n, h_edges_[b], h_edges_[B_ + b], keep, &first, &end);
+        if (ed) trimmed_span(n, (*ed)[b], (*ed)[B_ + b], keep, &first, &end);
         out->first[b] = (int32_t)first;
         out->end[b] = (int32_t)end;
     }

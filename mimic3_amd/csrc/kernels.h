@@ -231,6 +231,35 @@ constexpr int pack_seg_scale_row(bool trimmed) { return trimmed ? 4 : 3; }
 constexpr int pack_seg_rows(bool trimmed, bool normalised) { return pack_seg_scale_row(trimmed) + (normalised ? 1 : 0); }
 void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
                  uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised);
+// SEVERAL streams in one block (mi355vits_run_streams / _fetch_streams; k_pack_streams in kernels_pack.cpp): each stream with its own
+// order, silences, header, encoding, trim and scale, addressed in BYTES of the block.  The host lays the block out so that every
+// stream's first data byte sits at a 16-byte-aligned block offset (a lane's 16-byte store then owns whole samples inside any data
+// region) and its RIFF header, if any, ends right in front of it; the kernel writes every byte of [0, n_bytes) and the last store's
+// overrun — audio, each stream's own silence code, the header bytes (made on the host, copied from the table), pad bytes and the
+// gaps between streams (zero).  Two int32 tables, uploaded as one block tab = [entry table][stream table]; their shape is defined
+// here and nowhere else:
+//   entry table [PACK_ENT_ROWS][n_entries], the entries of all streams in ascending order of their block offsets:
+//     PACK_ENT_OFFSET   block byte offset of the entry's first sample
+//     PACK_ENT_ROW      its batch row
+//     PACK_ENT_LENGTH   its valid samples
+//     PACK_ENT_SKIP     its first source sample (0 untrimmed)
+//     PACK_ENT_ENC      its stream's PackEncoding; + PACK_ENT_SCALED when a host-made scale applies (a stream with a loudness target)
+//     PACK_ENT_SCALE    then the bits of that f32 scale (as pack_seg_scale_row's)
+//   stream table [n_streams][PACK_STREAM_WORDS], streams in ascending order:
+//     PACK_STREAM_BEGIN block byte offset of the stream's first byte (its header, if it has one)
+//     PACK_STREAM_DATA  of its first data byte (16-byte aligned)
+//     PACK_STREAM_END   one past its last data byte (the RIFF pad byte and the gap behind it are zero)
+//     PACK_STREAM_ENC   its PackEncoding (the silence code)
+//     PACK_STREAM_HEADER .. + 15: the header's bytes as little-endian words (44 or 58 of the 64 are used)
+// The block is limited to 2^31 - 1 bytes: the offsets fit a word.  out holds pack_streams_capacity(n_bytes) bytes.
+enum { PACK_ENT_OFFSET = 0, PACK_ENT_ROW = 1, PACK_ENT_LENGTH = 2, PACK_ENT_SKIP = 3, PACK_ENT_ENC = 4, PACK_ENT_SCALE = 5, PACK_ENT_ROWS = 6 };
+enum { PACK_ENT_SCALED = 4 };  // flag in the PACK_ENT_ENC word, above the encoding's two bits
+enum { PACK_STREAM_BEGIN = 0, PACK_STREAM_DATA = 1, PACK_STREAM_END = 2, PACK_STREAM_ENC = 3, PACK_STREAM_HEADER = 4, PACK_STREAM_WORDS = 20 };
+constexpr long PACK_STREAMS_ITEM_BYTES = 256L * 16;  // a work item: 256 lanes x one 16-byte store
+inline size_t pack_streams_capacity(long n_bytes) { return ((size_t)n_bytes + 15) & ~size_t(15); }
+inline size_t pack_streams_table_words(int n_entries, int n_streams) { return (size_t)PACK_ENT_ROWS * n_entries + (size_t)PACK_STREAM_WORDS * n_streams; }
+void launch_pack_streams(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* tab, int n_entries,
+                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s);
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 

@@ -159,6 +159,182 @@ void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* pea
     LAUNCH_KERNEL(forms[enc][trimmed][normalised], dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total);
 }
 
+// ---- k_pack_streams: SEVERAL streams in one block (mi355vits_run_streams / _fetch_streams), each with its own encoding, header, trim
+// and scale.  k_pack's structure addressed in BYTES of the block (kernels.h: PACK_ENT_* / PACK_STREAM_*):
+//   * a work item is 256 lanes x one 16-byte store at a 16-byte-aligned block offset; every stream's data starts at such an offset, so
+//     inside a data region a lane owns whole samples (16 G.711 codes, 8 int16, 4 floats);
+//   * the persistent grid, the binary search and the forward-only cursors are k_pack's — one cursor over the entries, one over the
+//     streams;
+//   * a lane whose 16 bytes lie inside one entry's audio takes the wide-load path of that entry's encoding, a lane wholly inside one
+//     stream's silence stores its code, and everything else — an entry end, a silence, the next entry, a pad byte, a gap, a header, the
+//     end of the block — walks its 16 byte positions with cursors of its own;
+//   * every byte of [0, n_bytes) and of the last store's overrun has exactly one writer; the header bytes are the table's.
+// The sample arithmetic is pack_scale / pack_sample / pcm16_quant / g711_* above, chosen per entry at run time.
+constexpr int pack_bps_shift(int enc) { return enc == PACK_ENC_S16 ? 1 : enc == PACK_ENC_F32 ? 2 : 0; }  // log2(pack_bytes_per_sample): no 64-bit division
+__device__ __forceinline__ float streams_scale(int encw, int scale_bits, const unsigned* peak_bits, int row) {
+    if (encw & PACK_ENT_SCALED) return __int_as_float(scale_bits);  // pack_scale<.., true>
+    if ((encw & 3) == PACK_ENC_F32) return 1.0f;                     // a float stream without a target reads no peak
+    return 32767.0f / fmaxf(0.01f, __uint_as_float(peak_bits[row]));
+}
+// one sample's code in the low bytes_per_sample bytes
+__device__ __forceinline__ unsigned streams_code(int encw, float a, float scale, double volume) {
+    switch (encw & 3) {
+    case PACK_ENC_S16: return pack_sample<PACK_ENC_S16, false>(a, scale, volume) & 0xffffu;
+    case PACK_ENC_ULAW: return pack_sample<PACK_ENC_ULAW, false>(a, scale, volume);
+    case PACK_ENC_ALAW: return pack_sample<PACK_ENC_ALAW, false>(a, scale, volume);
+    default: return (encw & PACK_ENT_SCALED) ? pack_sample<PACK_ENC_F32, true>(a, scale, volume) : pack_sample<PACK_ENC_F32, false>(a, scale, volume);
+    }
+}
+// a lane's 16 bytes inside one entry's audio: 4 S contiguous source bytes, in the widest loads their alignment allows (as k_pack)
+template <int ENC> __device__ __forceinline__ uint4 streams_lane(const float* src, bool scaled, float scale, double volume) {
+    constexpr int S = pack_lane_samples(ENC);
+    float v[S];
+    const uintptr_t al = reinterpret_cast<uintptr_t>(src);
+    if ((al & 15) == 0) {
+        MI355_UNROLL
+        for (int k = 0; k < S / 4; ++k) {
+            const float4 a = reinterpret_cast<const float4*>(src)[k];
+            v[4 * k] = a.x; v[4 * k + 1] = a.y; v[4 * k + 2] = a.z; v[4 * k + 3] = a.w;
+        }
+    } else if ((al & 7) == 0) {
+        MI355_UNROLL
+        for (int k = 0; k < S / 2; ++k) {
+            const float2 a = reinterpret_cast<const float2*>(src)[k];
+            v[2 * k] = a.x; v[2 * k + 1] = a.y;
+        }
+    } else {
+        MI355_UNROLL
+        for (int k = 0; k < S; ++k) v[k] = src[k];
+    }
+    unsigned c[S];
+    MI355_UNROLL
+    for (int k = 0; k < S; ++k)
+        c[k] = (ENC == PACK_ENC_F32 && scaled) ? pack_sample<ENC, true>(v[k], scale, volume) : pack_sample<ENC, false>(v[k], scale, volume);
+    return pack_words<ENC>(c);
+}
+
+__global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                                      const double* __restrict__ volumes, const int* __restrict__ tab, int n, int ns,
+                                                      uint8_t* __restrict__ out, long total) {
+    constexpr long ITEM = PACK_STREAMS_ITEM_BYTES;
+    constexpr int W = PACK_STREAM_WORDS;
+    const int* e_off = tab + PACK_ENT_OFFSET * n;   // block byte offset of entry i's first sample, ascending over all streams
+    const int* e_row = tab + PACK_ENT_ROW * n;
+    const int* e_len = tab + PACK_ENT_LENGTH * n;   // in samples
+    const int* e_skip = tab + PACK_ENT_SKIP * n;
+    const int* e_enc = tab + PACK_ENT_ENC * n;      // the encoding, + PACK_ENT_SCALED
+    const int* e_scale = tab + PACK_ENT_SCALE * n;
+    const int* st = tab + PACK_ENT_ROWS * n;        // [ns][W]: the streams
+    const long nitems = (total + ITEM - 1) / ITEM;
+    const long per = nitems / gridDim.x, rem = nitems % gridDim.x;
+    long item = blockIdx.x * per + (blockIdx.x < rem ? (long)blockIdx.x : rem);
+    const long item_end = item + per + (blockIdx.x < rem ? 1 : 0);
+    if (item >= item_end) return;
+    // the entry and the stream the first work item starts in: the last ones that begin at or before its first byte (-1: none yet).
+    // Uniform per workgroup; afterwards both cursors only move forward.
+    int e, s;
+    {
+        const long c0 = item * ITEM;
+        int lo = 0, hi = n;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (e_off[mid] <= c0) lo = mid + 1;
+            else hi = mid;
+        }
+        e = lo - 1;
+        lo = 0, hi = ns;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (st[mid * W + PACK_STREAM_BEGIN] <= c0) lo = mid + 1;
+            else hi = mid;
+        }
+        s = lo - 1;
+    }
+    for (; item < item_end; ++item) {
+        const long c0 = item * ITEM;
+        while (e + 1 < n && e_off[e + 1] <= c0) ++e;
+        while (s + 1 < ns && st[(s + 1) * W + PACK_STREAM_BEGIN] <= c0) ++s;
+        const long p0 = c0 + 16L * threadIdx.x;
+        if (p0 >= total) continue;  // (the block's last store may run up to 15 bytes into the buffer's padding)
+        int le = e, ls = s;
+        while (le + 1 < n && e_off[le + 1] <= p0) ++le;
+        while (ls + 1 < ns && st[(ls + 1) * W + PACK_STREAM_BEGIN] <= p0) ++ls;
+        const int lc = le < 0 ? 0 : le;
+        const long off = e_off[lc];
+        const int encw = e_enc[lc], enc = encw & 3;
+        const int sh = pack_bps_shift(enc);
+        const long aend = off + ((long)e_len[lc] << sh);  // one past the entry's audio
+        uint4 w;
+        if (le >= 0 && p0 + 16 <= aend) {
+            // data regions start 16-byte aligned and samples are aligned inside them: p0 - off is a whole number of samples
+            const int row = e_row[lc];
+            const float* src = audio + (long)row * audio_bs + e_skip[lc] + ((p0 - off) >> sh);
+            const float scale = streams_scale(encw, e_scale[lc], peak_bits, row);
+            const double volume = (enc != PACK_ENC_F32 && volumes) ? volumes[row] : 1.0;
+            const bool scaled = (encw & PACK_ENT_SCALED) != 0;
+            switch (enc) {
+            case PACK_ENC_S16: w = streams_lane<PACK_ENC_S16>(src, scaled, scale, volume); break;
+            case PACK_ENC_ULAW: w = streams_lane<PACK_ENC_ULAW>(src, scaled, scale, volume); break;
+            case PACK_ENC_ALAW: w = streams_lane<PACK_ENC_ALAW>(src, scaled, scale, volume); break;
+            default: w = streams_lane<PACK_ENC_F32>(src, scaled, scale, volume); break;
+            }
+        } else {
+            const int sc = ls < 0 ? 0 : ls;
+            const long d0 = st[sc * W + PACK_STREAM_DATA], d1 = st[sc * W + PACK_STREAM_END];
+            const long quiet0 = (le >= 0 && aend > d0) ? aend : d0;                 // behind the entry's audio, inside the stream's data
+            const long next = le + 1 < n ? (long)e_off[le + 1] : 0x7fffffffffffL;  // the next entry's audio
+            if (ls >= 0 && p0 >= quiet0 && p0 + 16 <= (d1 < next ? d1 : next)) {
+                // 16 bytes of one stream's silence: its code in every byte (0 / 0xFF / 0xD5 / the bytes of 0.0f)
+                const unsigned q = pack_silence(st[sc * W + PACK_STREAM_ENC]) * 0x01010101u;
+                w.x = q; w.y = q; w.z = q; w.w = q;
+            } else {
+                // a boundary inside the lane's bytes: byte by byte with cursors of its own; loads go through clamped indices, the value
+                // is selected afterwards.  A sample's bytes never straddle two lanes, so its code is made at its first byte (and only
+                // there) and kept.
+                int ce = le, cs = ls;
+                unsigned code = 0, ww[4] = {0u, 0u, 0u, 0u};
+                MI355_UNROLL
+                for (int k = 0; k < 16; ++k) {
+                    const long p = p0 + k;
+                    while (ce + 1 < n && e_off[ce + 1] <= p) ++ce;
+                    while (cs + 1 < ns && st[(cs + 1) * W + PACK_STREAM_BEGIN] <= p) ++cs;
+                    const int cc = ce < 0 ? 0 : ce;
+                    const int ew = e_enc[cc], bs = pack_bps_shift(ew & 3);
+                    const long rel = p - e_off[cc];
+                    const bool in_audio = ce >= 0 && rel < ((long)e_len[cc] << bs);
+                    const int sub = (int)(rel & ((1 << bs) - 1));  // the byte of its sample
+                    const bool first = in_audio && sub == 0;
+                    const int r = e_row[cc];
+                    const float a = audio[first ? (long)r * audio_bs + e_skip[cc] + (rel >> bs) : 0L];
+                    if (first) {  // header, gap, silence and a sample's later bytes pay no sample arithmetic
+                        const float scale = streams_scale(ew, e_scale[cc], peak_bits, r);
+                        const double volume = ((ew & 3) != PACK_ENC_F32 && volumes) ? volumes[r] : 1.0;
+                        code = streams_code(ew, a, scale, volume);
+                    }
+                    // outside every entry's audio: a header byte, the stream's silence code, or zero (pad byte, gap, in front of stream 0)
+                    const int* sr = st + (cs < 0 ? 0 : cs) * W;
+                    const long hb = sr[PACK_STREAM_BEGIN], db = sr[PACK_STREAM_DATA], de = sr[PACK_STREAM_END];
+                    const int hrel = (cs >= 0 && p < db) ? (int)(p - hb) : 0;
+                    const unsigned hbyte = ((unsigned)sr[PACK_STREAM_HEADER + (hrel >> 2)] >> (8 * (hrel & 3))) & 0xffu;
+                    const unsigned quiet = cs < 0 ? 0u : p < db ? hbyte : p < de ? pack_silence(sr[PACK_STREAM_ENC]) : 0u;
+                    const unsigned byte = in_audio ? (code >> (8 * sub)) & 0xffu : quiet;
+                    ww[k >> 2] |= byte << (8 * (k & 3));
+                }
+                w.x = ww[0]; w.y = ww[1]; w.z = ww[2]; w.w = ww[3];
+            }
+        }
+        *reinterpret_cast<uint4*>(out + p0) = w;
+    }
+}
+
+void launch_pack_streams(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* tab, int n_entries,
+                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s) {
+    if (n_bytes <= 0 || n_entries <= 0 || n_streams <= 0) return;
+    const long nitems = (n_bytes + PACK_STREAMS_ITEM_BYTES - 1) / PACK_STREAMS_ITEM_BYTES;
+    const long gx = std::min<long>(nitems, 8L * current_device_cu_count());  // as k_pack: 8 workgroups of 4 waves per CU
+    LAUNCH_KERNEL(k_pack_streams, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, tab, n_entries, n_streams, out, n_bytes);
+}
+
 // the encoders alone over an array (mi355vits_lab_g711_encode): exhaustive tests on the CPU model and on the device
 __global__ __launch_bounds__(256) void k_g711_encode(int law, const int16_t* __restrict__ in, long n, uint8_t* __restrict__ out) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {

@@ -91,7 +91,8 @@ def utterances_to_wav(pcm_rows: Sequence[np.ndarray], sample_rate: int = 22050, 
     return wav_bytes(parts, sample_rate)
 
 
-def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Optional[float] = None, **settings) -> bytes:
+def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Optional[float] = None, shared: bool = False,
+                **settings) -> bytes:
     """A request's sentences (one phoneme-id list each) -> the WAV the reference hands out (``mimic3_http/app.py:157-227``), in ONE
     engine call: the id lists are padded into a batch, ``InferenceSession.run_packed(..., wav=True)`` synthesises them, puts
     ``break_ms`` of silence between consecutive sentences and frames the stream on the GPU side — the one-call form of
@@ -102,7 +103,11 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     ``loudness`` / ``ceiling_db`` as ``run_packed`` takes them (with ``loudness=-23`` every sentence is scaled to that BS.1770
     integrated loudness instead of to its own peak; with ``trim_db`` each sentence is cut to its loud part, so ``break_ms`` is the pause heard; with
     ``sample_rate`` the file is at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it; with
-    ``encoding="ulaw"`` and ``sample_rate=8000`` it is the G.711 file a telephony stack plays)."""
+    ``encoding="ulaw"`` and ``sample_rate=8000`` it is the G.711 file a telephony stack plays).
+
+    ``shared=True``: through ``InferenceSession.run_stream`` instead — on a session with a micro-batcher the request's sentences
+    share ONE engine call with the requests of other clients that arrive meanwhile, each request still getting its own finished
+    file (``mi355vits_run_streams``); the same bytes."""
     rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]
     if not rows or any(r.size == 0 for r in rows):
         raise ValueError("request_wav needs at least one sentence, each with at least one phoneme id")
@@ -116,7 +121,7 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     if sid is not None:
         feed["sid"] = np.broadcast_to(np.asarray(sid, np.int64).reshape(-1), (B,)).copy()
     lead_ms = [break_ms if (i and break_ms) else 0.0 for i in range(B)]
-    out = session.run_packed(feed, lead_ms=lead_ms, wav=True, **settings)
+    out = (session.run_stream if shared else session.run_packed)(feed, lead_ms=lead_ms, wav=True, **settings)
     return bytes(out.wav)
 
 

@@ -370,13 +370,30 @@ class _MicroBatcher:
             # the output kind and sid presence must agree, and the phoneme-length class: the text encoder picks its attention /
             # FFN kernels by the padded length (<= 128, 256, 512, the voice's attention cap, beyond: config.tx_class), so within
             # a class a row gets the kernels — and the bits — it would get alone
+            # A stream request (run_stream) brings one or more rows and what ITS stream of the call looks like ("_stream": order,
+            # silences, header, encoding, trim, loudness — per stream, so nothing to group by); its class is that of its padded width,
+            # which is what its own call would run at.
             groups: Dict[Any, list] = {}
             for it in items:
-                bucket = tx_class(int(it[1][0]), self._cap)
-                kind = tuple(sorted((k, v) for k, v in it[4].items() if k not in _ROW_SETTINGS))
+                stream = "_stream" in it[4]
+                bucket = tx_class(int(it[0].shape[1]) if stream else int(it[1][0]), self._cap)
+                kind = tuple(sorted((k, v) for k, v in it[4].items() if k not in _ROW_SETTINGS and k != "_stream"))
                 key = (it[3] is None, kind, bucket)
                 groups.setdefault(key, []).append(it)
+            batches = []
             for group in groups.values():
+                if "_stream" not in group[0][4]:
+                    batches.append(group)
+                    continue
+                part, rows = [], 0  # stream requests: no engine call above micro_batch_max rows
+                for it in group:
+                    if part and rows + it[0].shape[0] > self._max:
+                        batches.append(part)
+                        part, rows = [], 0
+                    part.append(it)
+                    rows += it[0].shape[0]
+                batches.append(part)
+            for group in batches:
                 with self._inflight_cv:
                     self._inflight += 1
                 if self._pool is not None:
@@ -399,7 +416,64 @@ class _MicroBatcher:
         finally:
             lane_done()
 
+    def _run_stream_group(self, group):
+        """Stream requests as ONE ``run_streams`` call: every request's rows side by side, one stream of the block per request, and
+        each caller's result a view of that shared block (no slice is copied)."""
+        try:
+            tx = max(int(g[0].shape[1]) for g in group)
+            B = sum(int(g[0].shape[0]) for g in group)
+            ids = np.zeros((B, tx), np.int64)
+            lens = np.zeros(B, np.int64)
+            scales = np.zeros((B, 3), np.float32)
+            vols, keys, sids, streams = [], [], [], []
+            r0 = 0
+            for g in group:
+                R = int(g[0].shape[0])
+                # (run_stream has checked order and lead_samples against the request's OWN rows: adding r0 must never reach a neighbour's)
+                _check_stream_rows(g[4]["_stream"].get("order"), g[4]["_stream"].get("lead_samples"), R)
+                ids[r0:r0 + R, : g[0].shape[1]] = g[0]
+                lens[r0:r0 + R] = g[1]
+                scales[r0:r0 + R] = np.asarray(g[2], np.float32).reshape(-1, 3)  # [3] or [R, 3]
+                vols += [float(v) for v in np.broadcast_to(np.asarray(g[4].get("pcm_volume", 1.0), np.float64).reshape(-1), (R,))]
+                k = g[4].get("utterance_keys")
+                keys += [None] * R if k is None else list(k)
+                if g[3] is not None:
+                    sids += [int(v) for v in np.asarray(g[3]).reshape(-1)]
+                st = dict(g[4]["_stream"])
+                n = R if st.get("lead_samples") is None else len(np.asarray(st["lead_samples"]).reshape(-1))  # without an order: entries 0 .. n - 1
+                st["order"] = (np.arange(n) if st.get("order") is None else np.asarray(st["order"]).reshape(-1)) + r0
+                streams.append(st)
+                r0 += R
+            kw = {k: v for k, v in group[0][4].items() if k not in _ROW_SETTINGS and k not in ("_stream", "_kind")}
+            if any(v != 1.0 for v in vols):
+                kw["pcm_volume"] = np.asarray(vols, np.float64)
+            if any(k is not None for k in keys):
+                kw["utterance_keys"] = keys  # rows without a key of their own get base + b (_engine_run)
+            session = self._session_ref()
+            if session is None:
+                raise RuntimeError("session closed")
+            out = session._engine_run(ids, lens, scales if (scales != scales[0]).any() else scales[0].copy(),
+                                      np.asarray(sids, np.int64) if group[0][3] is not None else None, _streams=streams, **kw)
+            del session
+            with self._count_lock:
+                self.batches += 1
+                self.requests += len(group)
+            for g, pa in zip(group, out):
+                g[5].set_result(pa)
+        except BaseException as e:
+            if len(group) > 1:
+                # a bad request must not poison its batch-mates: fall back to one call per request
+                for g in group:
+                    if not g[5].done():
+                        self._run_stream_group([g])
+                return
+            for g in group:
+                if not g[5].done():
+                    g[5].set_exception(e)
+
     def _run_group(self, group, lane_done=None):
+        if "_stream" in group[0][4]:
+            return self._run_stream_group(group)
         try:
             tx = max(int(g[0].shape[1]) for g in group)
             B = len(group)
@@ -475,6 +549,36 @@ class _MicroBatcher:
         if not on_dispatcher and self._thread.is_alive():
             self._q.put(None)  # the drain above may have swallowed the sentinel of a dispatcher that was still busy
             self._thread.join(timeout=5.0)
+
+
+def _check_stream_rows(order, lead_samples, rows: int) -> None:
+    """A stream request's ``order`` / ``lead_samples`` against ITS OWN ``rows`` rows, by the rules the library applies to a call of
+    those rows alone — in a shared call the library sees the whole batch, where an index past the request's rows is another
+    client's sentence.  Raises ``InvalidArgument`` naming the entry."""
+    n = rows
+    if order is not None:
+        o = np.asarray(order).reshape(-1)
+        if o.size and not np.issubdtype(o.dtype, np.integer):
+            raise InvalidArgument("'order' must hold integers")
+        n = int(o.size)
+        if n < 1 or n > rows:
+            raise InvalidArgument(f"pack: n = {n} out of range (1 .. batch = {rows})")
+        seen: Dict[int, int] = {}
+        for i, r in enumerate(int(v) for v in o):
+            if r < 0 or r >= rows:
+                raise InvalidArgument(f"pack entry {i}: row {r} out of range (batch = {rows})")
+            if r in seen:
+                raise InvalidArgument(f"pack entry {i}: row {r} appears twice (also entry {seen[r]})")
+            seen[r] = i
+    if lead_samples is not None:
+        lead = np.asarray(lead_samples).reshape(-1)
+        if lead.size and not np.issubdtype(lead.dtype, np.integer):
+            raise InvalidArgument("'lead_samples' must hold integers")
+        if order is None:  # entries 0 .. n - 1, n the number of silences given (as run_packed)
+            if lead.size < 1 or lead.size > rows:
+                raise InvalidArgument(f"pack: n = {int(lead.size)} out of range (1 .. batch = {rows})")
+        elif int(lead.size) != n:
+            raise InvalidArgument("'order' and 'lead_samples' must have the same length")
 
 
 def _encoding_name(encoding) -> str:
@@ -664,7 +768,7 @@ class InferenceSession:
         rate of the stream: ``sample_rate``, else the session's ``output_sample_rate``, else the voice's), ``tail_ms`` after the last, with ``wav`` behind a RIFF header — one kernel, one device-to-host
         copy of exactly those bytes.  Same feed, ``volume`` and ``utterance_keys`` as ``run_pcm16``, and every entry is bitwise
         that call's row.  Returns ``_native.PackedAudio`` (``pcm``, ``rows`` — views of ``pcm`` —, ``offsets``, ``lengths``,
-        ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher.
+        ``peaks``, ``wav``, ``sample_rate``).  Always goes straight to a lane, never through the micro-batcher (``run_stream`` does).
         ``alignment`` (``True`` / ``"levels"``): sets ``PackedAudio.alignment`` (default ``None``) in STREAM coordinates — row i
         belongs to entry i and ``offsets[i]`` is added to ``start``, so ``data[start[i, t] : start[i, t] + samples[i, t]]`` is
         phoneme t of entry i in any encoding.
@@ -713,6 +817,55 @@ class InferenceSession:
                 start, samples = s0, s1 - s0
             out.alignment = _native.Alignment(al.frames[rows], start + np.asarray(out.offsets, np.int64)[:, None],
                                               samples.astype(al.samples.dtype), pick(al.peak), pick(al.rms), al.sample_rate)
+        self.last_lengths = out.lengths
+        return out
+
+    def run_stream(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
+                   volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+                   trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None, loudness: Optional[float] = None,
+                   ceiling_db: Optional[float] = None) -> "_native.PackedAudio":
+        """``run_packed`` (same keywords, except ``alignment``; same ``PackedAudio``; the same bytes when ``utterance_keys`` are
+        given or the noise scales are zero — a row without a key of its own takes its Philox index from its place in the shared
+        call, as in any micro-batched call, so its noise is not that of the request run alone) THROUGH the micro-batcher: the
+        feed's rows — one or a few sentences of one client — share an engine call with the requests of other callers that arrive
+        meanwhile, and come back as that caller's own finished stream (``mi355vits_run_streams``: one stream per request, each
+        with its own order, silences, header, encoding, trim and loudness target; one kernel, one device-to-host copy for the whole
+        batch).  Requests group by ``sid`` presence, phoneme-length class and output rate only.  The result is a view of the
+        batch's shared pinned block: nothing is copied per request.  A feed of more than ``micro_batch_max`` rows, or a session
+        without a micro-batcher, takes ``run_packed`` directly."""
+        ids, lengths, sid = self._feed(input_feed)
+        B = int(ids.shape[0])
+        if self._batcher is None or B > self._batcher._max or lengths.shape[0] != B:
+            return self.run_packed(input_feed, order=order, lead_ms=lead_ms, lead_samples=lead_samples, tail_ms=tail_ms, wav=wav,
+                                   volume=volume, utterance_keys=utterance_keys, sample_rate=sample_rate, encoding=encoding,
+                                   trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db)
+        kw = self._pcm_kw(volume, utterance_keys)
+        for name in ("pcm_volume", "utterance_keys"):
+            if name in kw and np.ndim(kw[name]) > 0 and len(kw[name]) != B:
+                raise InvalidArgument(f"per-row '{name}' must have shape [batch]")
+        if sample_rate is not None:
+            kw["sample_rate"] = int(sample_rate)
+        rate = int(sample_rate or self.output_sample_rate or self.config.sample_rate)
+        if lead_ms is not None:
+            if lead_samples is not None:
+                raise InvalidArgument("give lead_ms or lead_samples, not both")
+            lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
+        ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
+        keep_ms = float(trim_keep_ms if trim_keep_ms is not None else self.edge_trim_keep_ms)
+        if keep_ms < 0:
+            raise ValueError("trim_keep_ms must be >= 0")
+        _check_stream_rows(order, lead_samples, B)  # against this request's own rows, before it shares a call with others
+        scales = np.asarray(input_feed["scales"], np.float32)
+        if scales.size not in (3, 3 * B):
+            raise InvalidArgument("'scales' must hold [noise_scale, length_scale, noise_w] (or one such row per sentence)")
+        kw["_kind"] = "stream"
+        kw["_stream"] = dict(order=order, lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=bool(wav),
+                             encoding=_encoding_name(encoding) if encoding is not None else self.output_encoding,
+                             trim=(ratio, int((keep_ms / 1000.0) * rate)),
+                             loudness=_loudness_setting(loudness if loudness is not None else self.loudness_lufs,
+                                                        ceiling_db if ceiling_db is not None else self.loudness_ceiling_db))
+        sid1 = None if sid is None else np.asarray(sid).reshape(-1)
+        out = self._batcher.submit(np.asarray(ids, np.int64), lengths.astype(np.int64), scales, sid1, kw).result()
         self.last_lengths = out.lengths
         return out
 
@@ -775,7 +928,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, _trim=None, _loudness=None, **kw):
+                    _alignment=None, _trim=None, _loudness=None, _streams=None, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -794,7 +947,9 @@ class InferenceSession:
                 eng.set_output_encoding(encoding or self.output_encoding)
                 eng.set_edge_trim(*(_trim or (0.0, 0)))  # likewise; set on every call: back to off for a call that does not ask
                 eng.set_loudness_target(*(_loudness or (0.0, -1.0)))  # likewise
-            call = eng.run_packed if _packed else eng.run
+            if _streams is not None:  # every stream brings its own encoding, trim and target: the lane's settings are not read
+                kw["streams"] = _streams
+            call = eng.run_streams if _streams is not None else eng.run_packed if _packed else eng.run
             out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
             return out if _alignment is None else (out, eng.fetch_alignment(levels=_alignment))
         except _native.NativeError as e:
