@@ -428,7 +428,9 @@ void mi355vits_free_edges(mi355vits_edges* r);
  *     l_i = -0.691 + 10 log10(z_i);  absolute gate l_i > -70;  relative gate l_i > -0.691 + 10 log10(mean z over the absolutely gated) - 10
  *     lufs = -0.691 + 10 log10(mean z over the blocks passing both), -inf when no block passes the absolute gate
  *     gain: g = 10^((target - lufs) / 20) (1.0 when lufs = -inf), cap = 10^(ceiling / 20) / peak (none when the peak is 0),
- *       gain = min(g, cap), limited = cap < g.  No limiter and no compressor: the ceiling only bounds the gain.
+ *       gain = min(g, cap), limited = cap < g.  By default the ceiling only bounds the gain: a row it holds back ends below target and
+ *       says so (limited).  mi355vits_set_loudness_limiter (below) turns on a look-ahead peak limiter that brings such a row to
+ *       its target instead; there is no compressor.
  *  - mi355vits_set_loudness_target: target_lufs = 0 (the default): off — nothing below is launched or laid out by a pack, every byte is
  *    what it was.  On: -70 <= target_lufs < 0 with a finite ceiling_dbfs <= 0; anything else, NaN included: MI355VITS_ERR_INVALID, the
  *    message names the value, the setting stays.  mi355vits_clone inherits it.  Read when a pack is made and at each
@@ -466,6 +468,71 @@ typedef struct mi355vits_loudness {
 int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out);
 void mi355vits_free_loudness(mi355vits_loudness* r);
 
+/* ---- Reach the loudness target: a look-ahead peak limiter on the float waveform of the packed streams, before any quantisation.
+ * Without it one plosive sets the level of its whole sentence again whenever the ceiling binds (gain = cap < g) — which is what
+ * happens at the targets speech products use (-16 LUFS, -14 LUFS with a -1 or -2 dB ceiling): speech commonly has a crest factor
+ * above what such a target leaves under the ceiling.  (General knowledge about speech, not a measurement of this project: the
+ * synthetic voices of its test suite are far flatter.)  With the limiter on, a row the ceiling would hold back keeps its full gain g and
+ * only the samples within L samples of a peak are turned down, by a curve that is defined exactly — integers wherever an order could
+ * matter, so the same bits at any grid, CU count, batch or row address.  Per row of a pack with a loudness target:
+ *     x[0..n) the row's valid float samples at the run's rate;  g = 10^((target - lufs) / 20) in double, 1.0 for lufs = -inf;
+ *     c = 10^(ceiling / 20);  p the row's peak;  L >= 1 the window in samples;  ONE = 2^30
+ *     the row is OVER iff the gain rule above marks it limited (cap = c / p < g).  A row that is not over is untouched by everything
+ *     below: its bytes are those of the limiter off.  For a row that is over:
+ *       a[t]  = g * fabs((double) x[t])                              one double multiply
+ *       rq[t] = a[t] > c ? (int32) floor((c / a[t]) * 2^30) : ONE    IEEE double divide; NaN -> ONE; rq[t] = ONE for t < 0 or t >= n
+ *       mq[i] = min over i <= t <= i + L of rq[t]                    for i = -L .. n - 1
+ *       sq[k] = sum over k - L <= i <= k of mq[i]                    int64: exact in any order
+ *       s[k]  = (double) sq[k] / ((double)(L + 1) * 2^30)
+ *       scale[k] = (float)(U * (g * s[k]))                           double, in this order; U = 32767.0 (S16LE, G.711) or 1.0 (F32LE)
+ *     scale[k] replaces the entry's single scale: S16LE and G.711 samples are pcm16_quant(x[k], scale[k], volume) and the G.711
+ *     encoders as before, F32LE samples x[k] * scale[k].  pcm_volume still acts behind the scale and still clamps.
+ *   Consequences:
+ *   1. The ceiling holds.  Every window behind sq[k] contains k, so s[k] <= rq[k] / 2^30 <= c / a[k]: in reals g |x[k]| s[k] <= c.
+ *      After the two f32 roundings an F32LE sample satisfies |y| <= c (1 + 2^-22), an int16 sample at volume 1 |q| <= floor(32767 c) + 1.
+ *   2. Samples away from peaks keep their bits.  Where sq[k] = (L + 1) 2^30, s[k] = 1.0 exactly and scale[k] is bitwise (float)(U g):
+ *      what an uncapped gain g writes.
+ *   3. Placement cannot change the result: nothing depends on the grid, the batch, the CU count or the row's address.  A row of a
+ *      batch is bitwise the row alone; a trimmed entry is bitwise [first, end) of the untrimmed one — the curve is made on the whole
+ *      row, as the loudness is measured on it.
+ *   The window is symmetric: the gain falls over L samples before a peak and recovers over L behind it.  A longer L means less
+ *   distortion and more ducking; that trade is the caller's.  No separate release time, no true-peak (oversampled) detection.
+ *  - mi355vits_set_loudness_limiter: window_samples = 0 (the default): off — nothing is launched, laid out or changed, every byte and
+ *    every synchronisation is what it was.  On: 1 <= window_samples <= 4096, counted at the run's output rate (as keep_samples is);
+ *    anything else: MI355VITS_ERR_INVALID, the message names the value, the setting stays.  Read when a pack is made (as the target
+ *    is), at mi355vits_fetch_loudness and at mi355vits_fetch_limiter; mi355vits_clone inherits it.  Without a loudness target it does nothing.
+ *  - With it on, mi355vits_run_packed / _fetch_packed limit the over rows of a pack with a target instead of capping their gain;
+ *    mi355vits_fetch_loudness and the packed results then report gain = g (uncapped) and limited = 1 for those rows.
+ *  - mi355vits_run_streams / _fetch_streams (below) cannot carry a per-stream window — mi355vits_stream_args is frozen —: the handle's
+ *    window applies to every stream that has a target.
+ *  - mi355vits_fetch_limiter serves the LAST COMPLETED RUN under the handle's current target, ceiling and window, in an arena of its
+ *    own (what the other fetches serve afterwards is what they served before): engaged[b] = the row is over, reduced_samples[b] = the
+ *    count of k with sq[k] < (L + 1) 2^30, min_scale[b] = min over k of s[k] (1.0 for a row that is not over).  With the limiter or
+ *    the target off: zeros / 1.0, and nothing is launched.  Before any completed run: MI355VITS_ERR_INVALID with "fetch_limiter: no
+ *    completed run on this handle"; a NULL out: MI355VITS_ERR_INVALID.
+ *  - Synchronisation: none added.  The curve needs g, which the host has after the measurement's synchronisation; k_limit
+ *    (csrc/kernels_limit.cpp) runs between that synchronisation and the pack, on the same stream: mi355vits_run_packed with a target
+ *    stays at three synchronisations, mi355vits_fetch_packed at two — once the limiter's workspace has reached its size: the first
+ *    pack (and the first mi355vits_fetch_limiter) whose jobs outgrow it reallocates it, which waits for the stream, as the packed
+ *    stream's own buffer does when it grows.  The curve is made per pack and not kept.  A pack on no row of
+ *    which the limiter engages launches no k_limit and is packed by the kernels of the limiter off.
+ *  - With profiling enabled the launch is reported as "limit": bytes = 8 * sum(lengths of the jobs) + 16 * jobs; a job is one over
+ *    row under one (target, ceiling, U) — in a streams call a row shared by streams of the same setting is one job. */
+int mi355vits_set_loudness_limiter(mi355vits_handle h, int32_t window_samples);
+int32_t mi355vits_get_loudness_limiter(mi355vits_handle h);
+
+typedef struct mi355vits_limiter {
+    int32_t batch, sample_rate;   /* of the run served */
+    int32_t window_samples;       /* the setting the arrays were made with; 0 = off */
+    int32_t* engaged;             /* [B] 1 where the row is over: the limiter acts on it */
+    int32_t* reduced_samples;     /* [B] samples whose scale lies below the row's full gain */
+    double* min_scale;            /* [B] min s[k]; 1.0 for a row that is not over */
+    void* owner_;
+} mi355vits_limiter;
+
+int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out);
+void mi355vits_free_limiter(mi355vits_limiter* r);
+
 /* ---- Packed streams per request: SEVERAL independent streams out of one run.  A server that batches the sentences of many clients
  * into one synthesis call (one or a few rows per client) wants one finished stream per CLIENT — its own order, silences, header,
  * encoding, trim and loudness target — not one stream per call.  One kernel (k_pack_streams, csrc/kernels_pack.cpp) writes all of them
@@ -480,7 +547,9 @@ void mi355vits_free_loudness(mi355vits_loudness* r);
  *    samples within the stream's data) / lengths / peaks and its total_samples are that call's; first[] is the first source sample of
  *    each entry (0 untrimmed), gain[] / lufs[] / limited[] what mi355vits_fetch_loudness reports for the entry's row at that stream's
  *    target (all 0 for a stream without one).  Entries are flattened stream after stream: stream s owns [entry_base[s], entry_base[s + 1]).
- *  - The handle's own encoding, trim and loudness settings are NOT read by the two calls and not changed by them.
+ *  - The handle's own encoding, trim and loudness settings are NOT read by the two calls and not changed by them.  The handle's limiter
+ *    window (mi355vits_set_loudness_limiter) is the one handle setting the two calls DO read: it applies to every stream that has a
+ *    target, and stream s is bitwise mi355vits_fetch_packed under that stream's settings plus the handle's limiter window.
  *  - A row appears at most once within a stream, as in mi355vits_run_packed; it may appear in several streams (the same sentence as
  *    int16 and as mu-law, say).
  *  - As for mi355vits_run_packed, MI355VITS_WANT_* / MI355VITS_DEVICE_ONLY are ignored and no padded int16 pass runs; mi355vits_fetch /

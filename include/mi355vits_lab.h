@@ -80,6 +80,13 @@ int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, co
  * lufs / blocks / gated [B] as mi355vits_fetch_loudness defines them.  What lies behind a row is never looked at. */
 int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens, int B, int32_t rate, double* lufs, int32_t* blocks,
                            int32_t* gated);
+/* Kernel unit-test hook: the limiter kernel (k_limit; mi355vits_set_loudness_limiter) alone over host arrays on the current device:
+ * audio [B] rows of `stride` floats with lens [B] valid samples each, g [B] the rows' gains, c the linear ceiling, U the encoding's
+ * unit (32767.0 or 1.0), 1 <= L <= 4096 the window -> scale_out [B][stride] (scale[k] of include/mi355vits.h's rule at a row's valid
+ * samples, 0 behind them), sq_min [B] = min sq[k] and reduced [B] = the count of sq[k] < (L + 1) 2^30 ((L + 1) 2^30 and 0 for an
+ * empty row).  Every row is a job, over the ceiling or not.  What lies behind a row is never looked at. */
+int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
+                        float* scale_out, int64_t* sq_min, int32_t* reduced);
 /* How k_loud cuts a row at `rate`: *step = S, the 100 ms step; *warmup = W(rate), the samples an item that starts inside a row runs
  * before it counts; *steps_per_item = K (a work item is K * S samples of one row).  Host arithmetic only: no kernel runs. */
 int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, int32_t* steps_per_item);

@@ -41,13 +41,14 @@ EXPORTED_SYMBOLS = (
     "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
     "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
     "mi355vits_run_streams", "mi355vits_fetch_streams", "mi355vits_free_streams",
+    "mi355vits_set_loudness_limiter", "mi355vits_get_loudness_limiter", "mi355vits_fetch_limiter", "mi355vits_free_limiter",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
     "mi355vits_test_conv1d", "mi355vits_test_conv_transpose1d", "mi355vits_test_mfma_layout", "mi355vits_bench_conv1d", "mi355vits_probe_device", "mi355vits_probe_weights",
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
-    "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan",
+    "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
 )
 
 
@@ -200,6 +201,44 @@ class LoudnessResult(ctypes.Structure):
     ]
 
 
+class LimiterResult(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("sample_rate", ctypes.c_int32),
+        ("window_samples", ctypes.c_int32),
+        ("engaged", ctypes.POINTER(ctypes.c_int32)),
+        ("reduced_samples", ctypes.POINTER(ctypes.c_int32)),
+        ("min_scale", ctypes.POINTER(ctypes.c_double)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class Limiter:
+    """What the look-ahead peak limiter does to every row of a run under the handle's target, ceiling and window
+    (``mi355vits_fetch_limiter``): ``engaged`` [B] bool where the ceiling would hold the row's gain back (the limiter acts on it),
+    ``reduced_samples`` [B] the samples whose scale lies below the row's full gain, ``min_scale`` [B] float64 the smallest factor
+    the curve applies on top of the gain (1.0 for a row it leaves alone).  ``window_samples`` 0: off — all zeros / 1.0.  The arrays
+    are copies owned by Python."""
+
+    def __init__(self, engaged, reduced_samples, min_scale, window_samples, sample_rate):
+        self.engaged, self.reduced_samples, self.min_scale = engaged, reduced_samples, min_scale
+        self.window_samples, self.sample_rate = window_samples, sample_rate
+
+
+LIMITER_MAX_WINDOW = 4096  # samples: mi355vits_set_loudness_limiter
+
+
+def limiter_window(ms, rate) -> int:
+    """A limiter window in milliseconds as samples at ``rate`` Hz (``round(ms * rate / 1000)``); ``None`` = off = 0.  A window
+    outside 1 .. 4096 samples raises ``ValueError`` naming it."""
+    if ms is None:
+        return 0
+    n = float(ms) * float(rate) / 1000.0
+    if not (n == n and abs(n) < 1e12) or not 1 <= int(round(n)) <= LIMITER_MAX_WINDOW:
+        raise ValueError(f"limiter window of {ms!r} ms is {n:g} samples at {rate} Hz: outside 1 .. {LIMITER_MAX_WINDOW}")
+    return int(round(n))
+
+
 class Loudness:
     """ITU-R BS.1770-4 integrated loudness of every row of a run (``mi355vits_fetch_loudness``): ``lufs`` [B] float64 (``-inf``
     where no block passes the absolute gate), ``blocks`` / ``gated`` [B] the 400 ms blocks of the row and those passing both
@@ -326,6 +365,12 @@ class NativeLibrary:
         L.mi355vits_fetch_loudness.argtypes = [H, ctypes.POINTER(LoudnessResult)]
         L.mi355vits_free_loudness.argtypes = [ctypes.POINTER(LoudnessResult)]
         L.mi355vits_free_loudness.restype = None
+        L.mi355vits_set_loudness_limiter.argtypes = [H, ctypes.c_int32]
+        L.mi355vits_get_loudness_limiter.argtypes = [H]
+        L.mi355vits_get_loudness_limiter.restype = ctypes.c_int32
+        L.mi355vits_fetch_limiter.argtypes = [H, ctypes.POINTER(LimiterResult)]
+        L.mi355vits_free_limiter.argtypes = [ctypes.POINTER(LimiterResult)]
+        L.mi355vits_free_limiter.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -367,6 +412,8 @@ class NativeLibrary:
             L.mi355vits_lab_edges.argtypes = [f32p, ctypes.c_long, i32p, f32p, ctypes.c_int, ctypes.c_float, i32p, i32p]
             L.mi355vits_lab_loudness.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), i32p, i32p]
             L.mi355vits_lab_loudness_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p]
+            L.mi355vits_lab_limit.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_int32, f32p, ctypes.POINTER(ctypes.c_int64), i32p]
             L.mi355vits_test_alignment.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int64, f32p, i32p,
                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
@@ -435,6 +482,28 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return lufs, blocks, gated
+
+    def lab_limit(self, audio, lengths, g, c, U, window):
+        """The limiter kernel (k_limit) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is
+        never looked at), g [B] float64 the rows' gains, c the linear ceiling, U the encoding's unit (32767.0 or 1.0), ``window`` = L
+        in samples -> (scale float32 [B, stride] — the rule's ``scale[k]`` at a row's valid samples, 0 behind them —, sq_min int64 [B],
+        reduced int32 [B]) as ``include/mi355vits.h`` defines them.  Every row is a job, over the ceiling or not."""
+        self._need_hooks()
+        au = np.ascontiguousarray(audio, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        gg = np.ascontiguousarray(g, np.float64).reshape(-1)
+        if au.ndim != 2 or ln.shape[0] != au.shape[0] or gg.shape[0] != au.shape[0]:
+            raise ValueError("audio [B, stride], lengths [B], g [B]")
+        B = au.shape[0]
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        scale = np.zeros(au.shape, np.float32)
+        sq_min, reduced = np.zeros(B, np.int64), np.zeros(B, np.int32)
+        rc = self.lib.mi355vits_lab_limit(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                          float(c), float(U), int(window), _fptr(scale), sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                          reduced.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return scale, sq_min, reduced
 
     def lab_loudness_plan(self, rate):
         """How k_loud cuts a row at ``rate`` Hz: ``(S, W, K)`` — the 100 ms step, the warm-up samples of a work item that starts
@@ -1057,6 +1126,35 @@ class Engine:
                             float(r.target_lufs), float(r.ceiling_dbfs), int(r.sample_rate))
         finally:
             self.native.lib.mi355vits_free_loudness(ctypes.byref(r))
+
+    def set_loudness_limiter(self, window_samples) -> None:
+        """Turn the look-ahead peak limiter of the packed streams on (``mi355vits_set_loudness_limiter``): with a loudness target
+        set, a row the ceiling would hold back keeps its full gain and only the samples within ``window_samples`` (1 .. 4096, at the
+        run's rate) of a peak are turned down — the row reaches its target.  ``None`` / 0 (the default) = off; anything else raises
+        and leaves the setting as it was.  Read by ``run_packed``, each ``fetch_packed``, ``run_streams`` / ``fetch_streams`` (for
+        every stream with a target), ``fetch_loudness`` and ``fetch_limiter``; without a target it does nothing."""
+        self._check(self.native.lib.mi355vits_set_loudness_limiter(self._h, int(window_samples or 0)))
+
+    @property
+    def loudness_limiter(self) -> int:
+        """The window of ``set_loudness_limiter`` in samples; 0 = off."""
+        return int(self.native.lib.mi355vits_get_loudness_limiter(self._h))
+
+    def fetch_limiter(self) -> Limiter:
+        """Which rows of the last completed run the limiter engages on under the current target, ceiling and window, and how far
+        (``mi355vits_fetch_limiter``)."""
+        r = LimiterResult()
+        self._check(self.native.lib.mi355vits_fetch_limiter(self._h, ctypes.byref(r)))
+        try:
+            B = int(r.batch)
+            take = lambda p: np.ctypeslib.as_array(p, shape=(B,)).copy()  # noqa: E731
+            return Limiter(take(r.engaged).astype(bool), take(r.reduced_samples), take(r.min_scale), int(r.window_samples), int(r.sample_rate))
+        finally:
+            self.native.lib.mi355vits_free_limiter(ctypes.byref(r))
+
+    def lab_limit(self, audio, lengths, g, c, U, window):
+        """``NativeLibrary.lab_limit`` of this engine's library (the hooks library, the lab build or the CPU model)."""
+        return self.native.lab_limit(audio, lengths, g, c, U, window)
 
     def set_edge_trim(self, ratio, keep_samples: int = 0) -> None:
         """Trim each entry's quiet edges in the packed streams made after this (``mi355vits_set_edge_trim``): a sample is loud iff

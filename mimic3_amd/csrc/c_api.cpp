@@ -237,6 +237,24 @@ int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out) {
 
 void mi355vits_free_loudness(mi355vits_loudness* r) { free_struct(r); }
 
+int mi355vits_set_loudness_limiter(mi355vits_handle h, int32_t window_samples) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_loudness_limiter(window_samples); });
+}
+
+int32_t mi355vits_get_loudness_limiter(mi355vits_handle h) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return h->eng->loudness_limiter();
+}
+
+int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out) {
+    return result_call(h, out, [&] { h->eng->fetch_limiter(out); });
+}
+
+void mi355vits_free_limiter(mi355vits_limiter* r) { free_struct(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

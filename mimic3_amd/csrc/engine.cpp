@@ -679,6 +679,8 @@ void Engine::fill_workspace(uint32_t pattern) {
     arena_al_.fill(pattern, stream_);
     arena_ed_.fill(pattern, stream_);
     arena_ld_.fill(pattern, stream_);
+    arena_lm_.fill(pattern, stream_);
+    arena_lf_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -155,8 +155,10 @@ struct PackSettings {
     float trim_ratio = 0.0f;     // mi355vits_set_edge_trim: 0 = off
     int trim_keep = 0;
     float loud_target = 0.0f, loud_ceiling = -1.0f;  // mi355vits_set_loudness_target: target 0 = off
+    int limit_window = 0;        // mi355vits_set_loudness_limiter: samples at the run's rate, 0 = off; acts on packs with a target only
     bool trimmed() const { return trim_ratio != 0.0f; }
     bool normalised() const { return loud_target != 0.0f; }
+    bool limiting() const { return normalised() && limit_window > 0; }
 };
 
 // ---------------------------------------------------------------- the engine
@@ -200,6 +202,12 @@ class Engine {
     float loudness_ceiling() const { return pack_.loud_ceiling; }
     // BS.1770 integrated loudness of every row of the last completed run, and the gains of the current setting (mi355vits_fetch_loudness)
     void fetch_loudness(mi355vits_loudness* out);
+    // look-ahead peak limiter of the packed streams with a target (mi355vits_set_loudness_limiter): window 0 = off.  Read when a pack
+    // is made (a streams call reads it too: its one handle setting), at fetch_loudness and at fetch_limiter.
+    void set_loudness_limiter(int window_samples);
+    int loudness_limiter() const { return pack_.limit_window; }
+    // which rows of the last completed run the limiter engages on under the current target, ceiling and window, and how far
+    void fetch_limiter(mi355vits_limiter* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -263,7 +271,11 @@ class Engine {
         int64_t total = 0, audio = 0;
         std::vector<int> skip;     // trimmed only: the first sample of its row each entry starts at
         std::vector<double> gain;  // normalised only: each entry's linear gain
-        int seg_rows() const { return pack_seg_rows(set.trimmed(), set.normalised()); }
+        // limiting only, and only when the limiter engages on some entry (else empty): per entry -1, or first its job and, once
+        // the jobs are placed, its offset into the curves
+        std::vector<int> curve;
+        bool curved() const { return !curve.empty(); }
+        int seg_rows() const { return pack_seg_rows(set.trimmed(), set.normalised(), curved()); }
         int bps() const { return pack_bytes_per_sample(set.enc); }
         size_t header_bytes() const { return !wav ? 0 : set.enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
     };
@@ -273,6 +285,7 @@ class Engine {
         std::vector<int64_t> begin, data;  // block byte offset of each stream's first byte (its header) / first data byte (16-byte aligned)
         int64_t n_bytes = 0, audio = 0;    // the block; the audio samples in it
         int entries = 0;
+        bool curved = false;               // the limiter engages on some entry: the table has its curve row
         bool measured() const {            // some stream trims or normalises: the places depend on the audio
             for (const PackPlan& p : streams)
                 if (p.set.trimmed() || p.set.normalised()) return true;
@@ -280,7 +293,7 @@ class Engine {
         }
     };
     template <typename A> void layout_streams(A& ar, const StreamsPlan& sp) {
-        d_pack_seg_ = ar.template alloc<int>(pack_streams_table_words(sp.entries, (int)sp.streams.size()));
+        d_pack_seg_ = ar.template alloc<int>(pack_streams_table_words(sp.entries, (int)sp.streams.size(), sp.curved));
         d_pack_ = ar.template alloc<uint8_t>(pack_streams_capacity((long)sp.n_bytes));
     }
     // Packed calls only: the plan's segment table and stream, behind everything layout_b placed — no other pointer moves, so a
@@ -317,7 +330,15 @@ class Engine {
     bool enqueue_loudness();          // k_loud / k_loud_gate and their copy likewise (throws below LOUD_MIN_HZ)
     // what a pack needs from the audio: every launch, then ONE synchronisation (or none)
     void measure_last_run(const std::vector<float>& ratios, bool loud, bool keep);
-    static void loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited);
+    // window > 0 (the limiter on): a limited row keeps its uncapped gain — k_limit holds its peaks under the ceiling instead
+    static void loudness_gain(double lufs, float peak, float target, float ceiling, int window, double* gain, bool* limited);
+    // The limiter's jobs of a pack / a block / a fetch_limiter.  limit_job: the job of (row, set's target, ceiling and encoding
+    // class) among `jobs`, appended when new.  run_limit_jobs: the jobs placed (their offsets checked before anything is sized),
+    // uploaded and k_limit launched in `arena`; with_curve: d_curve_ = the curves, else statistics only.  Returns the device statistics.
+    int limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g) const;
+    LimitStat* run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve);
+    void limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const;  // plan.curve = each over entry's job (after place_pack)
+    static void curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs);  // plan.curve: jobs -> their placed offsets
 
     mi355vits_config cfg_{};
     int device_ = 0;
@@ -344,6 +365,8 @@ class Engine {
     DeviceArena arena_al_;  // mi355vits_fetch_alignment only: its five arrays, outside everything a run or a fetch lays out
     DeviceArena arena_ed_;  // k_edges' two words per row, likewise
     DeviceArena arena_ld_;  // k_loud's step energies and k_loud_gate's 16 bytes per row, likewise
+    DeviceArena arena_lm_;  // k_limit's jobs, statistics and curves of the pack being made: no fetch serves from it
+    DeviceArena arena_lf_;  // mi355vits_fetch_limiter only: k_limit's jobs and statistics
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -412,6 +435,8 @@ class Engine {
     std::vector<unsigned char> h_in_;  // the call's host inputs, laid out like their device block (one upload)
     std::vector<int> h_slen_;         // per-stage valid lengths + audio lengths (one upload; packed calls: + the segment table)
     std::vector<int> h_pack_seg_;     // fetch_packed's segment table (its own upload)
+    std::vector<LimitJob> h_limit_jobs_;  // k_limit's job table (its own upload)
+    float* d_curve_ = nullptr;        // the curves of the pack being made (arena_lm_), nullptr when the limiter engages on no entry
 };
 
 // what the owner_ of any of the five result structs points to goes back: pinned blocks to the pool, heap blocks freed (engine_results.cpp)

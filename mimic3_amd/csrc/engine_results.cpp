@@ -288,7 +288,7 @@ void Engine::place_pack(PackPlan& plan) const {
         }
         if (set.normalised()) {
             bool limited;
-            loudness_gain(h_loud_[row], h_loud_peaks_[row], set.loud_target, set.loud_ceiling, &plan.gain[i], &limited);
+            loudness_gain(h_loud_[row], h_loud_peaks_[row], set.loud_target, set.loud_ceiling, set.limit_window, &plan.gain[i], &limited);
         }
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
@@ -311,6 +311,7 @@ void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
             const float scale = set.enc == PACK_ENC_F32 ? (float)plan.gain[i] : (float)(32767.0 * plan.gain[i]);
             memcpy(&seg[pack_seg_scale_row(set.trimmed()) * n + i], &scale, 4);
         }
+        if (plan.curved()) seg[pack_seg_curve_row(set.trimmed()) * n + i] = plan.curve[i];
     }
 }
 
@@ -318,7 +319,7 @@ void Engine::launch_pack(const PackPlan& plan) {
     static const char* const labels[] = {"pcm16.pack", "pack.ulaw", "pack.alaw", "pack.f32"};  // by PackEncoding
     ProfScope ps(prof_, labels[plan.set.enc], 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
     m355::launch_pack(plan.set.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_,
-                      plan.set.trimmed(), plan.set.normalised());
+                      plan.set.trimmed(), plan.set.normalised(), plan.curved() ? d_curve_ : nullptr);
 }
 
 void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
@@ -385,6 +386,15 @@ void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipSetDevice(device_));
     measure_last_run({plan.set.trim_ratio}, plan.set.normalised(), false);
     place_pack(plan);
+    if (plan.set.limiting()) {
+        // the limiter: one job per entry the ceiling would hold back; the curves are made before the pack, on the same stream
+        std::vector<LimitJob> jobs;
+        limit_pack(plan, jobs);
+        if (!jobs.empty()) {
+            run_limit_jobs(jobs, plan.set.limit_window, arena_lm_, true);
+            curve_offsets(plan, jobs);
+        }
+    }
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
     ArenaCount need;
@@ -438,6 +448,7 @@ void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, i
         set.trim_keep = a.trim_keep_samples;
         set.loud_target = a.target_lufs;
         if (a.target_lufs != 0.0f) set.loud_ceiling = a.ceiling_dbfs;
+        set.limit_window = pack_.limit_window;  // the one handle setting a streams call reads: mi355vits_stream_args is frozen
         try {
             plan_pack(&a.pack, B, set, sp.streams[s]);
         } catch (const EngineError& e) {
@@ -477,7 +488,7 @@ void Engine::place_streams(StreamsPlan& sp) const {
 
 void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
     const size_t n = (size_t)sp.entries;
-    int* st = tab + PACK_ENT_ROWS * n;
+    int* st = tab + pack_ent_rows(sp.curved) * n;
     size_t e = 0;
     for (size_t s = 0; s < sp.streams.size(); ++s) {
         const PackPlan& p = sp.streams[s];
@@ -488,7 +499,9 @@ void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
             tab[PACK_ENT_ROW * n + e] = p.order[i];
             tab[PACK_ENT_LENGTH * n + e] = (int)p.lengths[i];
             tab[PACK_ENT_SKIP * n + e] = set.trimmed() ? p.skip[i] : 0;
-            tab[PACK_ENT_ENC * n + e] = set.enc | (set.normalised() ? (int)PACK_ENT_SCALED : 0);
+            const bool curved = p.curved() && p.curve[i] >= 0;
+            tab[PACK_ENT_ENC * n + e] = set.enc | (set.normalised() ? (int)PACK_ENT_SCALED : 0) | (curved ? (int)PACK_ENT_CURVED : 0);
+            if (sp.curved) tab[PACK_ENT_CURVE * n + e] = curved ? p.curve[i] : 0;
             float scale = 0.0f;  // fill_pack_seg's: 32767 * gain in double, rounded once (F32LE: the gain itself)
             if (set.normalised()) scale = set.enc == PACK_ENC_F32 ? (float)p.gain[i] : (float)(32767.0 * p.gain[i]);
             memcpy(&tab[PACK_ENT_SCALE * n + e], &scale, 4);
@@ -507,7 +520,8 @@ void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
 
 void Engine::launch_streams(const StreamsPlan& sp) {
     ProfScope ps(prof_, "pack.streams", 0, 4.0 * (double)sp.audio + (double)sp.n_bytes);
-    launch_pack_streams(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, sp.entries, (int)sp.streams.size(), d_pack_, (long)sp.n_bytes, stream_);
+    launch_pack_streams(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, sp.entries, (int)sp.streams.size(), d_pack_, (long)sp.n_bytes, stream_,
+                        sp.curved ? d_curve_ : nullptr);
 }
 
 void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out) {
@@ -555,7 +569,7 @@ void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* o
             if (p.set.normalised()) {
                 bool lim = false;
                 out->lufs[e] = h_loud_[row];
-                loudness_gain(h_loud_[row], h_loud_peaks_[row], p.set.loud_target, p.set.loud_ceiling, &out->gain[e], &lim);
+                loudness_gain(h_loud_[row], h_loud_peaks_[row], p.set.loud_target, p.set.loud_ceiling, p.set.limit_window, &out->gain[e], &lim);
                 out->limited[e] = lim ? 1 : 0;
             }
         }
@@ -608,6 +622,17 @@ void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
     }
     measure_last_run(ratios, loud, true);
     place_streams(sp);
+    {
+        // the limiter: one job per distinct (row, target, ceiling, encoding class) among the entries the ceiling would hold back
+        std::vector<LimitJob> jobs;
+        for (PackPlan& p : sp.streams)
+            if (p.set.limiting()) limit_pack(p, jobs);
+        sp.curved = !jobs.empty();
+        if (sp.curved) {
+            run_limit_jobs(jobs, pack_.limit_window, arena_lm_, true);
+            for (PackPlan& p : sp.streams) curve_offsets(p, jobs);
+        }
+    }
     // where pack_last_run puts its buffers: behind the last run's frame-side layout where the arena has room, else in arena_p_
     ArenaCount need;
     layout_streams(need, sp);
@@ -619,7 +644,7 @@ void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
         arena_p_.reset();
         layout_streams(arena_p_, sp);
     }
-    h_pack_seg_.assign(pack_streams_table_words(sp.entries, (int)sp.streams.size()), 0);
+    h_pack_seg_.assign(pack_streams_table_words(sp.entries, (int)sp.streams.size(), sp.curved), 0);
     fill_streams_table(sp, h_pack_seg_.data());
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
     launch_streams(sp);
@@ -733,7 +758,7 @@ void Engine::set_loudness_target(float target_lufs, float ceiling_dbfs) {
 }
 
 // The gain rule, in double: g = 10^((T - lufs) / 20) (1 for a row without a gated block), bounded by 10^(c / 20) / peak.
-void Engine::loudness_gain(double lufs, float peak, float target, float ceiling, double* gain, bool* limited) {
+void Engine::loudness_gain(double lufs, float peak, float target, float ceiling, int window, double* gain, bool* limited) {
     const double g = std::isinf(lufs) ? 1.0 : std::pow(10.0, ((double)target - lufs) / 20.0);
     const double p = (double)peak;
     *gain = g;
@@ -741,7 +766,7 @@ void Engine::loudness_gain(double lufs, float peak, float target, float ceiling,
     if (p != 0.0) {
         const double cap = std::pow(10.0, (double)ceiling / 20.0) / p;
         if (cap < g) {
-            *gain = cap;
+            if (window <= 0) *gain = cap;  // (the limiter on: the row keeps g and k_limit holds its peaks under the ceiling)
             *limited = true;
         }
     }
@@ -782,6 +807,7 @@ bool Engine::enqueue_loudness() {
 void Engine::fetch_loudness(mi355vits_loudness* out) {
     begin_fetch(out, "fetch_loudness");
     const float target = pack_.loud_target, ceiling = pack_.loud_ceiling;
+    const int window = pack_.limit_window;
     measure_last_run({}, true, false);
     const size_t B = (size_t)B_;
     out->batch = B_;
@@ -798,9 +824,116 @@ void Engine::fetch_loudness(mi355vits_loudness* out) {
     for (size_t b = 0; b < B; ++b) {
         double g = 0.0;
         bool lim = false;
-        if (target != 0.0f) loudness_gain(out->lufs[b], h_loud_peaks_[b], target, ceiling, &g, &lim);
+        if (target != 0.0f) loudness_gain(out->lufs[b], h_loud_peaks_[b], target, ceiling, window, &g, &lim);
         out->gain[b] = g;
         out->limited[b] = lim ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------- the look-ahead peak limiter (mi355vits_set_loudness_limiter / _fetch_limiter)
+void Engine::set_loudness_limiter(int window_samples) {
+    if (window_samples != 0 && (window_samples < 1 || window_samples > LIMIT_MAX_WINDOW))
+        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_limiter: window of " + std::to_string(window_samples) +
+                                                     " samples is neither 0 (off) nor in [1, " + std::to_string(LIMIT_MAX_WINDOW) + "]");
+    pack_.limit_window = window_samples;
+}
+
+int Engine::limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g) const {
+    const double c = std::pow(10.0, (double)set.loud_ceiling / 20.0);
+    const double U = set.enc == PACK_ENC_F32 ? 1.0 : 32767.0;
+    // (a linear scan: quadratic in the over entries of a streams call, which a micro-batch keeps to tens; a single pack never repeats a row)
+    for (size_t j = 0; j < jobs.size(); ++j)
+        if (jobs[j].row == row && jobs[j].g == g && jobs[j].c == c && jobs[j].U == U) return (int)j;  // (g is a function of the row and the target)
+    LimitJob job;
+    job.g = g;
+    job.c = c;
+    job.U = U;
+    job.row = row;
+    job.n = (int)h_olen_[row];  // the curve is made on the whole row, as the loudness is measured on it
+    job.off = job.tile0 = 0;
+    jobs.push_back(job);
+    return (int)jobs.size() - 1;
+}
+
+void Engine::limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const {
+    const PackSettings& set = plan.set;
+    std::vector<int> curve(plan.n, -1);
+    bool any = false;
+    for (int i = 0; i < plan.n; ++i) {
+        const int row = plan.order[i];
+        double g;
+        bool over;
+        loudness_gain(h_loud_[row], h_loud_peaks_[row], set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
+        if (!over || h_olen_[row] < 1) continue;
+        curve[i] = limit_job(jobs, row, set, g);
+        any = true;
+    }
+    if (any) plan.curve.swap(curve);
+}
+
+void Engine::curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs) {
+    for (int& c : plan.curve)
+        if (c >= 0) c = jobs[(size_t)c].off;
+}
+
+LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve) {
+    long floats = 0;
+    const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
+    if (tiles < 0)
+        throw EngineError(MI355VITS_ERR_INVALID, "limiter: the curves of the rows over the ceiling together exceed 2^31 - 1 samples");
+    const size_t nj = jobs.size();
+    // (reserve waits for the stream when the arena has to grow: "no synchronisation added" holds from the second pack of a size on, as for arena_p_)
+    arena.reserve(DeviceArena::padded(sizeof(LimitJob) * nj) + DeviceArena::padded(sizeof(LimitStat) * nj) +
+                      (with_curve ? DeviceArena::padded(4 * (size_t)floats) : 0) + 4096, stream_);
+    arena.reset();
+    LimitJob* d_jobs = arena.alloc<LimitJob>(nj);
+    LimitStat* d_stats = arena.alloc<LimitStat>(nj);
+    float* curve = with_curve ? arena.alloc<float>((size_t)floats) : nullptr;
+    if (with_curve) d_curve_ = curve;
+    h_limit_jobs_ = jobs;  // a member: it outlives the copy
+    HIP_CHECK(hipMemcpyAsync(d_jobs, h_limit_jobs_.data(), sizeof(LimitJob) * nj, hipMemcpyHostToDevice, stream_));
+    {
+        ProfScope ps(prof_, "limit", 0, 8.0 * (double)floats + 16.0 * (double)nj);
+        launch_limit(d_jobs, (int)nj, tiles, window, o_audio_, Lo_, d_stats, curve, stream_);
+    }
+    return d_stats;
+}
+
+void Engine::fetch_limiter(mi355vits_limiter* out) {
+    begin_fetch(out, "fetch_limiter");
+    const PackSettings set = pack_;
+    const size_t B = (size_t)B_;
+    Owner* own = new_owner(out);
+    out->batch = B_;
+    out->sample_rate = run_hz_;
+    out->window_samples = set.limit_window;
+    out->engaged = own->alloc<int32_t>(B);
+    out->reduced_samples = own->alloc<int32_t>(B);
+    out->min_scale = own->alloc<double>(B);
+    for (size_t b = 0; b < B; ++b) {
+        out->engaged[b] = out->reduced_samples[b] = 0;
+        out->min_scale[b] = 1.0;
+    }
+    if (!set.limiting()) return;  // nothing is measured or launched
+    measure_last_run({}, true, false);
+    std::vector<LimitJob> jobs;
+    for (int b = 0; b < B_; ++b) {
+        double g;
+        bool over;
+        loudness_gain(h_loud_[b], h_loud_peaks_[b], set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
+        if (over && h_olen_[b] >= 1) (void)limit_job(jobs, b, set, g);
+    }
+    if (jobs.empty()) return;
+    const LimitStat* d_stats = run_limit_jobs(jobs, set.limit_window, arena_lf_, false);
+    std::vector<LimitStat> st(jobs.size());
+    HIP_CHECK(hipMemcpyAsync(st.data(), d_stats, sizeof(LimitStat) * st.size(), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    const double den = (double)(set.limit_window + 1) * 1073741824.0;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        const int b = jobs[j].row;
+        out->engaged[b] = 1;
+        out->reduced_samples[b] = st[j].reduced;
+        out->min_scale[b] = (double)st[j].sq_min / den;
     }
 }
 

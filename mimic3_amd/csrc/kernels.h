@@ -228,9 +228,15 @@ inline size_t pack_capacity_bytes(int enc, long total) { return ((size_t)total *
 //                                    one f32 multiply per sample)
 enum { PACK_SEG_OFFSET = 0, PACK_SEG_ROW = 1, PACK_SEG_LENGTH = 2, PACK_SEG_SKIP = 3 };
 constexpr int pack_seg_scale_row(bool trimmed) { return trimmed ? 4 : 3; }
+//   pack_seg_curve_row(trimmed)      curved (normalised packs on some entry of which the limiter engaged: launch_pack with a curve)
+//                                    only, behind the scale: the entry's offset into the curves — sample k of its ROW is scaled by
+//                                    curve[offset + k] in place of the entry's scale — or -1 for an entry that keeps its scale
 constexpr int pack_seg_rows(bool trimmed, bool normalised) { return pack_seg_scale_row(trimmed) + (normalised ? 1 : 0); }
+constexpr int pack_seg_curve_row(bool trimmed) { return pack_seg_scale_row(trimmed) + 1; }
+constexpr int pack_seg_rows(bool trimmed, bool normalised, bool curved) { return pack_seg_rows(trimmed, normalised) + (curved ? 1 : 0); }
+// curve != nullptr (normalised only): k_limit's scales, the table has its curve row
 void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                 uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised);
+                 uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised, const float* curve = nullptr);
 // SEVERAL streams in one block (mi355vits_run_streams / _fetch_streams; k_pack_streams in kernels_pack.cpp): each stream with its own
 // order, silences, header, encoding, trim and scale, addressed in BYTES of the block.  The host lays the block out so that every
 // stream's first data byte sits at a 16-byte-aligned block offset (a lane's 16-byte store then owns whole samples inside any data
@@ -245,6 +251,9 @@ void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* pea
 //     PACK_ENT_SKIP     its first source sample (0 untrimmed)
 //     PACK_ENT_ENC      its stream's PackEncoding; + PACK_ENT_SCALED when a host-made scale applies (a stream with a loudness target)
 //     PACK_ENT_SCALE    then the bits of that f32 scale (as pack_seg_scale_row's)
+//     PACK_ENT_CURVE    curved blocks (launch_pack_streams with a curve) only, a seventh row: the offset into the curves of an entry
+//                       flagged PACK_ENT_CURVED in its PACK_ENT_ENC word (as pack_seg_curve_row's); the table of any other block
+//                       has six rows, as ever
 //   stream table [n_streams][PACK_STREAM_WORDS], streams in ascending order:
 //     PACK_STREAM_BEGIN block byte offset of the stream's first byte (its header, if it has one)
 //     PACK_STREAM_DATA  of its first data byte (16-byte aligned)
@@ -253,13 +262,17 @@ void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* pea
 //     PACK_STREAM_HEADER .. + 15: the header's bytes as little-endian words (44 or 58 of the 64 are used)
 // The block is limited to 2^31 - 1 bytes: the offsets fit a word.  out holds pack_streams_capacity(n_bytes) bytes.
 enum { PACK_ENT_OFFSET = 0, PACK_ENT_ROW = 1, PACK_ENT_LENGTH = 2, PACK_ENT_SKIP = 3, PACK_ENT_ENC = 4, PACK_ENT_SCALE = 5, PACK_ENT_ROWS = 6 };
-enum { PACK_ENT_SCALED = 4 };  // flag in the PACK_ENT_ENC word, above the encoding's two bits
+enum { PACK_ENT_SCALED = 4, PACK_ENT_CURVED = 8 };  // flags in the PACK_ENT_ENC word, above the encoding's two bits
+enum { PACK_ENT_CURVE = 6 };
+constexpr int pack_ent_rows(bool curved) { return curved ? PACK_ENT_ROWS + 1 : PACK_ENT_ROWS; }
 enum { PACK_STREAM_BEGIN = 0, PACK_STREAM_DATA = 1, PACK_STREAM_END = 2, PACK_STREAM_ENC = 3, PACK_STREAM_HEADER = 4, PACK_STREAM_WORDS = 20 };
 constexpr long PACK_STREAMS_ITEM_BYTES = 256L * 16;  // a work item: 256 lanes x one 16-byte store
 inline size_t pack_streams_capacity(long n_bytes) { return ((size_t)n_bytes + 15) & ~size_t(15); }
-inline size_t pack_streams_table_words(int n_entries, int n_streams) { return (size_t)PACK_ENT_ROWS * n_entries + (size_t)PACK_STREAM_WORDS * n_streams; }
+inline size_t pack_streams_table_words(int n_entries, int n_streams, bool curved = false) {
+    return (size_t)pack_ent_rows(curved) * n_entries + (size_t)PACK_STREAM_WORDS * n_streams;
+}
 void launch_pack_streams(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* tab, int n_entries,
-                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s);
+                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s, const float* curve = nullptr);
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 
@@ -321,6 +334,28 @@ inline long loudness_steps(long n, int S) { return n > 0 ? (n + S - 1) / S : 0; 
 // lufs / blocks / gated [B]; every word read is written on s before.  What lies behind a row is never looked at.
 void launch_loudness(int fs, const float* audio, long audio_bs, const int* alen, int B, long l_max, double* E, long ldE, double* lufs,
                      int* blocks, int* gated, hipStream_t s);
+
+// ---------------------------------------------------------------- look-ahead peak limiter of the packed streams (kernels_limit.cpp)
+constexpr int LIMIT_MAX_WINDOW = 4096;  // the largest window L in samples: tile + 2 L staged samples fit 48 KB of LDS
+constexpr int LIMIT_TILE = 4096;        // samples of a work item
+constexpr long LIMIT_MAX_CURVE = 0x7fffffffL;  // the curves of a launch together: their offsets fit an int
+// One row under one (g, c, U): scale[k] of its n >= 1 samples goes to curve[off + k]; tile0 = its first work item.  off and tile0
+// are limit_place_jobs': jobs one behind the other, in the order given.
+struct LimitJob {
+    double g, c, U;
+    int row, n, off, tile0;
+};
+struct LimitStat {
+    unsigned long long sq_min;  // min sq[k] over the job's samples ((L + 1) 2^30 when nothing was reduced)
+    int reduced, pad;           // samples with sq[k] < (L + 1) 2^30
+};
+// fills off / tile0 of every job; returns the work items of the launch and *curve_floats = the floats of all curves, or -1 when a
+// job is empty or the curves together exceed LIMIT_MAX_CURVE floats
+long limit_place_jobs(LimitJob* jobs, int n_jobs, long* curve_floats);
+// jobs / stats [n_jobs] and curve on the device; audio rows of audio_bs floats (a job reads its row's [0, n) and nothing behind
+// it); 1 <= L <= LIMIT_MAX_WINDOW.  stats are initialised here, on s, whatever they held; curve == nullptr: statistics only.
+void launch_limit(const LimitJob* jobs, int n_jobs, long tiles, int L, const float* audio, long audio_bs, LimitStat* stats, float* curve,
+                  hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

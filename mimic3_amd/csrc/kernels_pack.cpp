@@ -54,11 +54,13 @@ template <int ENC> __device__ __forceinline__ uint4 pack_words(const unsigned (&
     return st;
 }
 
-// TRIM / NORM: the table's optional rows (kernels.h: pack_seg_*)
-template <int ENC, bool TRIM, bool NORM>
-__global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
-                                              const double* __restrict__ volumes, const int* __restrict__ seg, int n,
-                                              uint8_t* __restrict__ out, long total) {
+// TRIM / NORM / CURVE: the table's optional rows (kernels.h: pack_seg_*).  CURVE (behind NORM: a pack whose limiter engaged): an
+// entry with a curve offset >= 0 takes sample k's scale from curve[offset + k] (k counted in its ROW, so a trimmed entry reads the
+// curve where the untrimmed one does) in place of the entry's one scale; -1: the entry's scale, as without CURVE.
+template <int ENC, bool TRIM, bool NORM, bool CURVE>
+__device__ __forceinline__ void pack_body(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                          const double* __restrict__ volumes, const int* __restrict__ seg, int n,
+                                          uint8_t* __restrict__ out, long total, const float* __restrict__ curve) {
     constexpr int S = pack_lane_samples(ENC);       // samples of a lane's 16-byte store
     constexpr int BPS = pack_bytes_per_sample(ENC);
     constexpr long CHUNK = 256L * S;                // output samples per work item
@@ -69,6 +71,7 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, l
     const int* s_len = seg + PACK_SEG_LENGTH * n;   // its valid samples
     const int* s_skip = seg + PACK_SEG_SKIP * n;    // TRIM only: the row's sample the entry starts at
     const int* s_scale = seg + pack_seg_scale_row(TRIM) * n;  // NORM only: the bits of the entry's f32 scale
+    const int* s_curve = seg + pack_seg_curve_row(TRIM) * n;  // CURVE only: the entry's curve offset, or -1
     const long nchunks = (total + CHUNK - 1) / CHUNK;
     // consecutive chunks per workgroup (the first `rem` workgroups take one more): the cursor below then crosses each entry once
     const long per = nchunks / gridDim.x, rem = nchunks % gridDim.x;
@@ -104,6 +107,11 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, l
             const float* src = audio + (long)row * audio_bs + (TRIM ? s_skip[lc] : 0) + (s0 - off);
             const float scale = pack_scale<ENC, NORM>(s_scale, peak_bits, lc, row);
             const double volume = (VOL && volumes) ? volumes[row] : 1.0;
+            const float* cv = nullptr;  // CURVE: the scales of the lane's samples
+            if constexpr (CURVE) {
+                const int co = s_curve[lc];
+                if (co >= 0) cv = curve + co + (TRIM ? s_skip[lc] : 0) + (s0 - off);
+            }
             float v[S];
             const uintptr_t al = reinterpret_cast<uintptr_t>(src);
             if ((al & 15) == 0) {
@@ -123,7 +131,10 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, l
                 for (int k = 0; k < S; ++k) v[k] = src[k];
             }
             MI355_UNROLL
-            for (int k = 0; k < S; ++k) c[k] = pack_sample<ENC, NORM>(v[k], scale, volume);
+            for (int k = 0; k < S; ++k) {
+                if constexpr (CURVE) c[k] = pack_sample<ENC, NORM>(v[k], cv ? cv[k] : scale, volume);
+                else c[k] = pack_sample<ENC, NORM>(v[k], scale, volume);
+            }
         } else {
             // a boundary inside the lane's samples (row end, silence, next row's start, head or tail of the stream): sample by
             // sample with a cursor of its own; loads go through a clamped index, the value is selected afterwards
@@ -137,7 +148,13 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, l
                 const int r = s_row[cc];
                 const bool valid = ce >= 0 && sp < o + s_len[cc];
                 const float a = audio[valid ? (long)r * audio_bs + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
-                const float scale = pack_scale<ENC, NORM>(s_scale, peak_bits, cc, r);
+                float scale = pack_scale<ENC, NORM>(s_scale, peak_bits, cc, r);
+                if constexpr (CURVE) {
+                    const int co = s_curve[cc];
+                    const bool curved = valid && co >= 0;
+                    const float cs = curve[curved ? (long)co + (TRIM ? s_skip[cc] : 0) + (sp - o) : 0L];
+                    scale = curved ? cs : scale;
+                }
                 const double volume = (VOL && volumes) ? volumes[r] : 1.0;
                 c[k] = valid ? pack_sample<ENC, NORM>(a, scale, volume) : SILENCE;
             }
@@ -146,9 +163,34 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, l
     }
 }
 
+template <int ENC, bool TRIM, bool NORM>
+__global__ __launch_bounds__(256) void k_pack(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                              const double* __restrict__ volumes, const int* __restrict__ seg, int n,
+                                              uint8_t* __restrict__ out, long total) {
+    pack_body<ENC, TRIM, NORM, false>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, nullptr);
+}
+// a pack whose limiter engaged on some entry: k_pack<ENC, TRIM, true> with the table's curve row and the curves
+template <int ENC, bool TRIM>
+__global__ __launch_bounds__(256) void k_pack_curve(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                                    const double* __restrict__ volumes, const int* __restrict__ seg, int n,
+                                                    uint8_t* __restrict__ out, long total, const float* __restrict__ curve) {
+    pack_body<ENC, TRIM, true, true>(audio, audio_bs, peak_bits, volumes, seg, n, out, total, curve);
+}
+
 void launch_pack(int enc, const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* seg, int n,
-                 uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised) {
+                 uint8_t* out, long total, hipStream_t s, bool trimmed, bool normalised, const float* curve) {
     if (total <= 0 || n <= 0) return;
+    if (curve) {
+        using CurveKernel = void (*)(const float*, long, const unsigned*, const double*, const int*, int, uint8_t*, long, const float*);
+#define PACK_CURVE_FORMS(ENC) {k_pack_curve<ENC, false>, k_pack_curve<ENC, true>}
+        static const CurveKernel curve_forms[4][2] = {PACK_CURVE_FORMS(PACK_ENC_S16), PACK_CURVE_FORMS(PACK_ENC_ULAW), PACK_CURVE_FORMS(PACK_ENC_ALAW), PACK_CURVE_FORMS(PACK_ENC_F32)};
+#undef PACK_CURVE_FORMS
+        const long cchunk = 256L * pack_lane_samples(enc);
+        const long cn = (total + cchunk - 1) / cchunk;
+        const long cgx = std::min<long>(cn, 8L * current_device_cu_count());
+        LAUNCH_KERNEL(curve_forms[enc][trimmed], dim3((unsigned)cgx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, seg, n, out, total, curve);
+        return;
+    }
     using Kernel = void (*)(const float*, long, const unsigned*, const double*, const int*, int, uint8_t*, long);
 #define PACK_FORMS(ENC) {{k_pack<ENC, false, false>, k_pack<ENC, false, true>}, {k_pack<ENC, true, false>, k_pack<ENC, true, true>}}
     static const Kernel forms[4][2][2] = {PACK_FORMS(PACK_ENC_S16), PACK_FORMS(PACK_ENC_ULAW), PACK_FORMS(PACK_ENC_ALAW), PACK_FORMS(PACK_ENC_F32)};
@@ -186,7 +228,8 @@ __device__ __forceinline__ unsigned streams_code(int encw, float a, float scale,
     }
 }
 // a lane's 16 bytes inside one entry's audio: 4 S contiguous source bytes, in the widest loads their alignment allows (as k_pack)
-template <int ENC> __device__ __forceinline__ uint4 streams_lane(const float* src, bool scaled, float scale, double volume) {
+// (CURVE with cv != nullptr: sample k's scale is cv[k] in place of the entry's)
+template <int ENC, bool CURVE> __device__ __forceinline__ uint4 streams_lane(const float* src, bool scaled, float scale, double volume, const float* cv) {
     constexpr int S = pack_lane_samples(ENC);
     float v[S];
     const uintptr_t al = reinterpret_cast<uintptr_t>(src);
@@ -208,14 +251,20 @@ template <int ENC> __device__ __forceinline__ uint4 streams_lane(const float* sr
     }
     unsigned c[S];
     MI355_UNROLL
-    for (int k = 0; k < S; ++k)
-        c[k] = (ENC == PACK_ENC_F32 && scaled) ? pack_sample<ENC, true>(v[k], scale, volume) : pack_sample<ENC, false>(v[k], scale, volume);
+    for (int k = 0; k < S; ++k) {
+        float sk = scale;
+        if constexpr (CURVE) sk = cv ? cv[k] : scale;
+        c[k] = (ENC == PACK_ENC_F32 && scaled) ? pack_sample<ENC, true>(v[k], sk, volume) : pack_sample<ENC, false>(v[k], sk, volume);
+    }
     return pack_words<ENC>(c);
 }
 
-__global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
-                                                      const double* __restrict__ volumes, const int* __restrict__ tab, int n, int ns,
-                                                      uint8_t* __restrict__ out, long total) {
+// CURVE: the entry table has the PACK_ENT_CURVE row; an entry flagged PACK_ENT_CURVED takes sample k's scale from curve[offset + k]
+// (k counted in its row) — a block some of whose entries the limiter engaged on
+template <bool CURVE>
+__device__ __forceinline__ void streams_body(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                             const double* __restrict__ volumes, const int* __restrict__ tab, int n, int ns,
+                                             uint8_t* __restrict__ out, long total, const float* __restrict__ curve) {
     constexpr long ITEM = PACK_STREAMS_ITEM_BYTES;
     constexpr int W = PACK_STREAM_WORDS;
     const int* e_off = tab + PACK_ENT_OFFSET * n;   // block byte offset of entry i's first sample, ascending over all streams
@@ -224,7 +273,8 @@ __global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ 
     const int* e_skip = tab + PACK_ENT_SKIP * n;
     const int* e_enc = tab + PACK_ENT_ENC * n;      // the encoding, + PACK_ENT_SCALED
     const int* e_scale = tab + PACK_ENT_SCALE * n;
-    const int* st = tab + PACK_ENT_ROWS * n;        // [ns][W]: the streams
+    const int* e_curve = tab + PACK_ENT_CURVE * n;  // CURVE only
+    const int* st = tab + pack_ent_rows(CURVE) * n;  // [ns][W]: the streams
     const long nitems = (total + ITEM - 1) / ITEM;
     const long per = nitems / gridDim.x, rem = nitems % gridDim.x;
     long item = blockIdx.x * per + (blockIdx.x < rem ? (long)blockIdx.x : rem);
@@ -272,11 +322,15 @@ __global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ 
             const float scale = streams_scale(encw, e_scale[lc], peak_bits, row);
             const double volume = (enc != PACK_ENC_F32 && volumes) ? volumes[row] : 1.0;
             const bool scaled = (encw & PACK_ENT_SCALED) != 0;
+            const float* cv = nullptr;
+            if constexpr (CURVE) {
+                if (encw & PACK_ENT_CURVED) cv = curve + e_curve[lc] + e_skip[lc] + ((p0 - off) >> sh);
+            }
             switch (enc) {
-            case PACK_ENC_S16: w = streams_lane<PACK_ENC_S16>(src, scaled, scale, volume); break;
-            case PACK_ENC_ULAW: w = streams_lane<PACK_ENC_ULAW>(src, scaled, scale, volume); break;
-            case PACK_ENC_ALAW: w = streams_lane<PACK_ENC_ALAW>(src, scaled, scale, volume); break;
-            default: w = streams_lane<PACK_ENC_F32>(src, scaled, scale, volume); break;
+            case PACK_ENC_S16: w = streams_lane<PACK_ENC_S16, CURVE>(src, scaled, scale, volume, cv); break;
+            case PACK_ENC_ULAW: w = streams_lane<PACK_ENC_ULAW, CURVE>(src, scaled, scale, volume, cv); break;
+            case PACK_ENC_ALAW: w = streams_lane<PACK_ENC_ALAW, CURVE>(src, scaled, scale, volume, cv); break;
+            default: w = streams_lane<PACK_ENC_F32, CURVE>(src, scaled, scale, volume, cv); break;
             }
         } else {
             const int sc = ls < 0 ? 0 : ls;
@@ -307,7 +361,10 @@ __global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ 
                     const int r = e_row[cc];
                     const float a = audio[first ? (long)r * audio_bs + e_skip[cc] + (rel >> bs) : 0L];
                     if (first) {  // header, gap, silence and a sample's later bytes pay no sample arithmetic
-                        const float scale = streams_scale(ew, e_scale[cc], peak_bits, r);
+                        float scale = streams_scale(ew, e_scale[cc], peak_bits, r);
+                        if constexpr (CURVE) {
+                            if (ew & PACK_ENT_CURVED) scale = curve[(long)e_curve[cc] + e_skip[cc] + (rel >> bs)];
+                        }
                         const double volume = ((ew & 3) != PACK_ENC_F32 && volumes) ? volumes[r] : 1.0;
                         code = streams_code(ew, a, scale, volume);
                     }
@@ -327,11 +384,26 @@ __global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ 
     }
 }
 
+__global__ __launch_bounds__(256) void k_pack_streams(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                                      const double* __restrict__ volumes, const int* __restrict__ tab, int n, int ns,
+                                                      uint8_t* __restrict__ out, long total) {
+    streams_body<false>(audio, audio_bs, peak_bits, volumes, tab, n, ns, out, total, nullptr);
+}
+__global__ __launch_bounds__(256) void k_pack_streams_curve(const float* __restrict__ audio, long audio_bs, const unsigned* __restrict__ peak_bits,
+                                                            const double* __restrict__ volumes, const int* __restrict__ tab, int n, int ns,
+                                                            uint8_t* __restrict__ out, long total, const float* __restrict__ curve) {
+    streams_body<true>(audio, audio_bs, peak_bits, volumes, tab, n, ns, out, total, curve);
+}
+
 void launch_pack_streams(const float* audio, long audio_bs, const unsigned* peak_bits, const double* volumes, const int* tab, int n_entries,
-                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s) {
+                         int n_streams, uint8_t* out, long n_bytes, hipStream_t s, const float* curve) {
     if (n_bytes <= 0 || n_entries <= 0 || n_streams <= 0) return;
     const long nitems = (n_bytes + PACK_STREAMS_ITEM_BYTES - 1) / PACK_STREAMS_ITEM_BYTES;
     const long gx = std::min<long>(nitems, 8L * current_device_cu_count());  // as k_pack: 8 workgroups of 4 waves per CU
+    if (curve) {
+        LAUNCH_KERNEL(k_pack_streams_curve, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, tab, n_entries, n_streams, out, n_bytes, curve);
+        return;
+    }
     LAUNCH_KERNEL(k_pack_streams, dim3((unsigned)gx), dim3(256), 0, s, audio, audio_bs, peak_bits, volumes, tab, n_entries, n_streams, out, n_bytes);
 }
 

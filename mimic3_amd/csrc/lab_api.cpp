@@ -254,6 +254,51 @@ int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens,
     });
 }
 
+int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
+                        float* scale_out, int64_t* sq_min, int32_t* reduced) {
+    return guarded(nullptr, [&] {
+        if (!audio || !lens || !g || !scale_out || !sq_min || !reduced || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        if (L < 1 || L > LIMIT_MAX_WINDOW) throw EngineError(MI355VITS_ERR_INVALID, "window " + std::to_string(L) + " is outside [1, " + std::to_string(LIMIT_MAX_WINDOW) + "]");
+        if (!(c > 0.0 && std::isfinite(c)) || !(U > 0.0 && std::isfinite(U))) throw EngineError(MI355VITS_ERR_INVALID, "c and U must be finite and > 0");
+        // one job per non-empty row; its curve goes where the row's samples are: scale_out has the audio's shape
+        std::vector<LimitJob> jobs;
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            if (!(g[b] > 0.0 && std::isfinite(g[b]))) throw EngineError(MI355VITS_ERR_INVALID, "g must be finite and > 0");
+            sq_min[b] = (int64_t)(L + 1) << 30;
+            reduced[b] = 0;
+            if (lens[b] < 1) continue;
+            LimitJob j;
+            j.g = g[b]; j.c = c; j.U = U; j.row = b; j.n = lens[b]; j.off = j.tile0 = 0;
+            jobs.push_back(j);
+        }
+        const size_t na = (size_t)B * stride;
+        for (size_t i = 0; i < na; ++i) scale_out[i] = 0.0f;
+        if (jobs.empty()) return;
+        long floats = 0;
+        const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
+        if (tiles < 0) throw EngineError(MI355VITS_ERR_INVALID, "the curves together exceed 2^31 - 1 samples");
+        DevBuf da(na * 4), dj(jobs.size() * sizeof(LimitJob)), ds(jobs.size() * sizeof(LimitStat)), dc((size_t)floats * 4);
+        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dj.p, jobs.data(), jobs.size() * sizeof(LimitJob), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(ds.p, 0x5a, jobs.size() * sizeof(LimitStat)));  // the launch initialises its words itself
+        HIP_CHECK(hipMemset(dc.p, 0xff, (size_t)floats * 4));              // NaN: the launch writes every curve element
+        launch_limit(dj.as<LimitJob>(), (int)jobs.size(), tiles, L, da.as<float>(), stride, ds.as<LimitStat>(), dc.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        std::vector<LimitStat> st(jobs.size());
+        std::vector<float> cv((size_t)floats);
+        HIP_CHECK(hipMemcpy(st.data(), ds.p, st.size() * sizeof(LimitStat), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cv.data(), dc.p, cv.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            const int b = jobs[j].row;
+            memcpy(scale_out + (size_t)b * stride, cv.data() + jobs[j].off, (size_t)jobs[j].n * 4);
+            sq_min[b] = (int64_t)st[j].sq_min;
+            reduced[b] = st[j].reduced;
+        }
+    });
+}
+
 int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, int32_t* steps_per_item) {
     return guarded(nullptr, [&] {
         LoudnessPlan lp;

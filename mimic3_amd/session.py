@@ -650,6 +650,13 @@ class InferenceSession:
         self.loudness_lufs: Optional[float] = kwargs.pop("loudness_lufs", None)
         self.loudness_ceiling_db: float = float(kwargs.pop("loudness_ceiling_db", -1.0))
         _loudness_setting(self.loudness_lufs, self.loudness_ceiling_db)
+        # look-ahead peak limiter of the packed streams with a target (Engine.set_loudness_limiter): its window in milliseconds,
+        # None = off; a call's ``limiter_ms=`` goes before it.  Milliseconds become samples at the run's rate when a call is made.
+        self.loudness_limiter_ms: Optional[float] = kwargs.pop("loudness_limiter_ms", None)
+        if self.loudness_limiter_ms is not None:
+            ms = float(self.loudness_limiter_ms)
+            if not (np.isfinite(ms) and ms > 0.0):
+                raise ValueError(f"loudness_limiter_ms must be finite and > 0 (or None = off), not {self.loudness_limiter_ms!r}")
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -759,7 +766,8 @@ class InferenceSession:
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
-                   loudness: Optional[float] = None, ceiling_db: Optional[float] = None) -> "_native.PackedAudio":
+                   loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
+                   limiter_ms: Optional[float] = None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -782,7 +790,11 @@ class InferenceSession:
         ``loudness`` (else the session's ``loudness_lufs``; ``None`` = off): each entry is scaled to that ITU-R BS.1770-4 integrated
         loudness in LUFS instead of to its own peak, with the gain bounded so that no sample passes ``ceiling_db`` dBFS (else the
         session's ``loudness_ceiling_db``, default -1) — ``Engine.set_loudness_target``; -70 <= loudness < 0 and a finite ceiling
-        <= 0, else ``ValueError``.  ``PackedAudio.lufs`` / ``.gain`` / ``.limited`` say what was measured and applied."""
+        <= 0, else ``ValueError``.  ``PackedAudio.lufs`` / ``.gain`` / ``.limited`` say what was measured and applied.
+        ``limiter_ms`` (else the session's ``loudness_limiter_ms``; ``None`` = off): with a loudness target, an entry the ceiling
+        would hold back is brought to its target by a look-ahead peak limiter with a window of ``round(limiter_ms * rate / 1000)``
+        samples instead (``Engine.set_loudness_limiter``; 1 .. 4096 samples, else ``ValueError`` naming the value); ``.gain`` is then
+        the uncapped gain and ``.limited`` marks the entries the limiter acted on."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -803,6 +815,7 @@ class InferenceSession:
         kw["_trim"] = (ratio, int((keep_ms / 1000.0) * rate))
         kw["_loudness"] = _loudness_setting(loudness if loudness is not None else self.loudness_lufs,
                                             ceiling_db if ceiling_db is not None else self.loudness_ceiling_db)
+        kw["_limiter"] = _native.limiter_window(limiter_ms if limiter_ms is not None else self.loudness_limiter_ms, rate)
         out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
                                lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
         if alignment:
@@ -823,14 +836,15 @@ class InferenceSession:
     def run_stream(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None, loudness: Optional[float] = None,
-                   ceiling_db: Optional[float] = None) -> "_native.PackedAudio":
+                   ceiling_db: Optional[float] = None, limiter_ms: Optional[float] = None) -> "_native.PackedAudio":
         """``run_packed`` (same keywords, except ``alignment``; same ``PackedAudio``; the same bytes when ``utterance_keys`` are
         given or the noise scales are zero — a row without a key of its own takes its Philox index from its place in the shared
         call, as in any micro-batched call, so its noise is not that of the request run alone) THROUGH the micro-batcher: the
         feed's rows — one or a few sentences of one client — share an engine call with the requests of other callers that arrive
         meanwhile, and come back as that caller's own finished stream (``mi355vits_run_streams``: one stream per request, each
         with its own order, silences, header, encoding, trim and loudness target; one kernel, one device-to-host copy for the whole
-        batch).  Requests group by ``sid`` presence, phoneme-length class and output rate only.  The result is a view of the
+        batch).  Requests group by ``sid`` presence, phoneme-length class, output rate and limiter window only (the window is the
+        one setting ``mi355vits_run_streams`` reads from the handle, so requests with different ``limiter_ms`` never share a call).  The result is a view of the
         batch's shared pinned block: nothing is copied per request.  A feed of more than ``micro_batch_max`` rows, or a session
         without a micro-batcher, takes ``run_packed`` directly."""
         ids, lengths, sid = self._feed(input_feed)
@@ -838,7 +852,8 @@ class InferenceSession:
         if self._batcher is None or B > self._batcher._max or lengths.shape[0] != B:
             return self.run_packed(input_feed, order=order, lead_ms=lead_ms, lead_samples=lead_samples, tail_ms=tail_ms, wav=wav,
                                    volume=volume, utterance_keys=utterance_keys, sample_rate=sample_rate, encoding=encoding,
-                                   trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db)
+                                   trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db,
+                                   limiter_ms=limiter_ms)
         kw = self._pcm_kw(volume, utterance_keys)
         for name in ("pcm_volume", "utterance_keys"):
             if name in kw and np.ndim(kw[name]) > 0 and len(kw[name]) != B:
@@ -859,6 +874,8 @@ class InferenceSession:
         if scales.size not in (3, 3 * B):
             raise InvalidArgument("'scales' must hold [noise_scale, length_scale, noise_w] (or one such row per sentence)")
         kw["_kind"] = "stream"
+        # a top-level keyword, not part of the stream's own settings: the micro-batcher groups by it
+        kw["_limiter"] = _native.limiter_window(limiter_ms if limiter_ms is not None else self.loudness_limiter_ms, rate)
         kw["_stream"] = dict(order=order, lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=bool(wav),
                              encoding=_encoding_name(encoding) if encoding is not None else self.output_encoding,
                              trim=(ratio, int((keep_ms / 1000.0) * rate)),
@@ -928,7 +945,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, _trim=None, _loudness=None, _streams=None, **kw):
+                    _alignment=None, _trim=None, _loudness=None, _streams=None, _limiter=0, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -947,7 +964,9 @@ class InferenceSession:
                 eng.set_output_encoding(encoding or self.output_encoding)
                 eng.set_edge_trim(*(_trim or (0.0, 0)))  # likewise; set on every call: back to off for a call that does not ask
                 eng.set_loudness_target(*(_loudness or (0.0, -1.0)))  # likewise
-            if _streams is not None:  # every stream brings its own encoding, trim and target: the lane's settings are not read
+            if _packed or _streams is not None:  # the limiter window: set on every packed call, back to off for one that does not ask
+                eng.set_loudness_limiter(_limiter or 0)
+            if _streams is not None:  # every stream brings its own encoding, trim and target: of the lane's settings only the limiter window is read
                 kw["streams"] = _streams
             call = eng.run_streams if _streams is not None else eng.run_packed if _packed else eng.run
             out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
