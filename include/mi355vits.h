@@ -496,7 +496,8 @@ void mi355vits_free_loudness(mi355vits_loudness* r);
  *      batch is bitwise the row alone; a trimmed entry is bitwise [first, end) of the untrimmed one — the curve is made on the whole
  *      row, as the loudness is measured on it.
  *   The window is symmetric: the gain falls over L samples before a peak and recovers over L behind it.  A longer L means less
- *   distortion and more ducking; that trade is the caller's.  No separate release time, no true-peak (oversampled) detection.
+ *   distortion and more ducking; that trade is the caller's.  No separate release time.  What the ceiling bounds is the SAMPLE peak unless
+ *   mi355vits_set_loudness_ceiling_mode (the section after this one) says otherwise.
  *  - mi355vits_set_loudness_limiter: window_samples = 0 (the default): off — nothing is launched, laid out or changed, every byte and
  *    every synchronisation is what it was.  On: 1 <= window_samples <= 4096, counted at the run's output rate (as keep_samples is);
  *    anything else: MI355VITS_ERR_INVALID, the message names the value, the setting stays.  Read when a pack is made (as the target
@@ -532,6 +533,64 @@ typedef struct mi355vits_limiter {
 
 int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out);
 void mi355vits_free_limiter(mi355vits_limiter* r);
+
+/* ---- A true-peak ceiling: the 4x oversampled peak of every row, on the GPU.  The ceiling above bounds SAMPLES; R128 and the delivery
+ * specifications built on it state theirs in dBTP, for the reconstructed waveform, whose peaks lie between the samples (how far above
+ * them depends on the material: DESIGN.md 4.14 has what was measured at the native rate and at 8 kHz).  In true-peak mode the gain
+ * rule and the limiter look at an oversampled peak instead.  Per row of a completed run: x[0..n) its valid float samples at the run's
+ * rate (the MI355VITS_WANT_FLOAT samples; pcm_volume does not apply).  All arithmetic is IEEE double, every product is rounded once
+ * and every sum is rounded once: there is NO fused multiply-add.
+ *     h[0..80]  = the 81 taps of scipy.signal.resample_poly(., 4, 1)'s default filter (Kaiser window beta 5, half = 40, cut-off 1/4,
+ *                 gain 4): fixed constants of the library, literal in csrc/kernels_truepeak.cpp
+ *     u[j]      = sum over i = 0 .. 20, ascending, starting from 0.0, of  h[p + 4 i] * (double) x[q - i]
+ *                 where j + 40 = 4 q + p, 0 <= p < 4, h[m] = 0 for m > 80, x = 0 outside [0, n);   j = 0 .. 4 n - 1
+ *     v[j]      = fabs((double) x[j / 4]) when j % 4 == 0   (phase 0 is the samples themselves: its centre tap is 1.0006, not 1)
+ *                 fabs(u[j])              otherwise
+ *     tp        = max over j of v[j], taken with "v > m" from m = 0.0: a NaN is never taken;  n = 0: tp = 0
+ *     e[t]      = max over j in [4 t - 3, 4 t + 3] within [0, 4 n) of v[j], same comparison          the envelope of sample t
+ *   max_t e[t] = tp;  e[t] >= |x[t]|;  e[t] depends on x[t - 11 .. t + 10] only;  tp >= (double) peak.  The factor is 4 relative to
+ *   the run's rate, whatever that rate is: after mi355vits_set_output_rate the row is band-limited to its own Nyquist, so the
+ *   proportions are those of BS.1770's 48 kHz case.  No claim is made to reproduce the coefficient table of BS.1770 Annex 2:
+ *   implementations differ there, and the rule above is the contract.
+ *  - mi355vits_set_loudness_ceiling_mode: MI355VITS_CEILING_SAMPLE (the default): every byte, launch and synchronisation is what it
+ *    was.  MI355VITS_CEILING_TRUE_PEAK: wherever the loudness rule and the limiter rule above use the row's peak or
+ *    fabs((double) x[t]) they use tp or e[t] —
+ *      gain rule: cap = c / tp (none when tp = 0), gain = min(g, cap), limited = cap < g;  a row is OVER iff c / tp < g;
+ *      limiter:   a[t] = g * e[t]; everything behind it (rq, mq, sq, s, scale) is unchanged.
+ *    Any other value: MI355VITS_ERR_INVALID, the message names it, the setting stays.  Read where the loudness target is read: when a
+ *    pack is made, at mi355vits_fetch_loudness and mi355vits_fetch_limiter, and by mi355vits_run_streams / _fetch_streams from the
+ *    handle, as they read the limiter window (mi355vits_stream_args is frozen: the mode applies to every stream that has a target).
+ *    mi355vits_clone inherits it.  Without a loudness target it does nothing to a pack.
+ *   Consequences:
+ *   1. Without the limiter, g tp <= c holds in reals for a capped row: the oversampled peak of the scaled row is under the ceiling.
+ *   2. With the limiter, g e[k] s[k] <= c holds: every SAMPLE obeys the ceiling as before, and both neighbours of an inter-sample
+ *      peak are turned down.
+ *   3. The true peak of the limited output is not bounded by a theorem, because the gain curve modulates the signal.  It is
+ *      measured (tests/test_true_peak.py) and not promised.
+ *   4. Nothing depends on the grid, the batch, the CU count or the row's address.  A row of a batch is bitwise the row alone.
+ *  - Synchronisation: none added.  The measurement (k_true_peak, csrc/kernels_truepeak.cpp) is launched next to the loudness
+ *    measurement, in front of the same synchronisation; tp of the last run is kept on the host with the loudness (a repeated fetch
+ *    launches nothing, a run drops it).  The envelope of the over rows is written between that synchronisation and the pack, into
+ *    the limiter's workspace, right before k_limit; a pack on no row of which the limiter engages launches neither.
+ *  - mi355vits_fetch_true_peak serves the LAST COMPLETED RUN whatever its flags were, at the rate it ran at, and measures whatever
+ *    the mode.  It works in an arena of its own: what the other fetches serve afterwards is what they served before.  Before any
+ *    completed run: MI355VITS_ERR_INVALID with "fetch_true_peak: no completed run on this handle"; a NULL out: MI355VITS_ERR_INVALID.
+ *  - With profiling enabled the measurement is reported as "truepeak": bytes = 4 * sum(lengths) + 8 * B; the envelope pass as
+ *    "truepeak.env": bytes = 12 * sum(lengths of the jobs). */
+#define MI355VITS_CEILING_SAMPLE 0
+#define MI355VITS_CEILING_TRUE_PEAK 1
+int mi355vits_set_loudness_ceiling_mode(mi355vits_handle h, int mode);
+int mi355vits_get_loudness_ceiling_mode(mi355vits_handle h);
+
+typedef struct mi355vits_true_peak {
+    int32_t batch, sample_rate;   /* of the run served */
+    double* true_peak;            /* [B] tp, linear */
+    float* peak;                  /* [B] the row's sample peak: bitwise peaks[b] of the run */
+    void* owner_;
+} mi355vits_true_peak;
+
+int mi355vits_fetch_true_peak(mi355vits_handle h, mi355vits_true_peak* out);
+void mi355vits_free_true_peak(mi355vits_true_peak* r);
 
 /* ---- Packed streams per request: SEVERAL independent streams out of one run.  A server that batches the sentences of many clients
  * into one synthesis call (one or a few rows per client) wants one finished stream per CLIENT — its own order, silences, header,

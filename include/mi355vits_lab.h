@@ -87,6 +87,19 @@ int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens,
  * empty row).  Every row is a job, over the ceiling or not.  What lies behind a row is never looked at. */
 int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
                         float* scale_out, int64_t* sq_min, int32_t* reduced);
+/* The same with an envelope (the true-peak ceiling mode, k_limit<true>): env [B][stride] doubles, env[b][t] in place of
+ * fabs((double) audio[b][t]) at a row's valid samples (finite, >= 0; what lies behind them is never looked at).  env = NULL: the
+ * call above. */
+int mi355vits_lab_limit_env(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
+                            const double* env, float* scale_out, int64_t* sq_min, int32_t* reduced);
+/* Kernel unit-test hook: the true-peak kernels (k_true_peak, k_true_peak_env; mi355vits_set_loudness_ceiling_mode) alone over host
+ * arrays on the current device.  audio [B] rows of `stride` floats with lens [B] (0 <= lens[b] <= stride) valid samples -> tp [B] and
+ * env_out [B][stride] (e[t] at a row's valid samples, 0 behind them; NULL: the measurement only) as include/mi355vits.h defines them.
+ * On the device the rows start `offset_floats` (0 .. 3) floats behind a 16-byte boundary plus whatever their stride adds.  What lies
+ * behind a row is never looked at. */
+int mi355vits_lab_true_peak(const float* audio, long stride, const int32_t* lens, int B, int32_t offset_floats, double* tp, double* env_out);
+/* The library's tap table h[0..80] (taps: room for 81 doubles, or NULL) and the samples of a k_true_peak work item.  No kernel runs. */
+int mi355vits_lab_true_peak_plan(double* taps, int32_t* tile);
 /* How k_loud cuts a row at `rate`: *step = S, the 100 ms step; *warmup = W(rate), the samples an item that starts inside a row runs
  * before it counts; *steps_per_item = K (a work item is K * S samples of one row).  Host arithmetic only: no kernel runs. */
 int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, int32_t* steps_per_item);

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
     "mi355vits_run_streams", "mi355vits_fetch_streams", "mi355vits_free_streams",
     "mi355vits_set_loudness_limiter", "mi355vits_get_loudness_limiter", "mi355vits_fetch_limiter", "mi355vits_free_limiter",
+    "mi355vits_set_loudness_ceiling_mode", "mi355vits_get_loudness_ceiling_mode", "mi355vits_fetch_true_peak", "mi355vits_free_true_peak",
 )
 # every symbol include/mi355vits_lab.h declares: exported by libmi355vits_hooks.so, the lab build and the CPU model — NOT by the product
 LAB_SYMBOLS = (
@@ -49,6 +50,7 @@ LAB_SYMBOLS = (
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
+    "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan",
 )
 
 
@@ -228,6 +230,39 @@ class Limiter:
 LIMITER_MAX_WINDOW = 4096  # samples: mi355vits_set_loudness_limiter
 
 
+class TruePeakResult(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int32),
+        ("sample_rate", ctypes.c_int32),
+        ("true_peak", ctypes.POINTER(ctypes.c_double)),
+        ("peak", ctypes.POINTER(ctypes.c_float)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class TruePeak:
+    """The 4x oversampled peak of every row of a run (``mi355vits_fetch_true_peak``): ``true_peak`` [B] float64, linear, ``peak`` [B]
+    float32 the rows' sample peaks (bitwise the run's ``peaks``), ``dbtp`` [B] float64 = 20 log10(true_peak) (``-inf`` for 0).
+    ``sample_rate`` is the rate the run ran at.  The arrays are copies owned by Python."""
+
+    def __init__(self, true_peak, peak, sample_rate):
+        self.true_peak, self.peak, self.sample_rate = true_peak, peak, sample_rate
+        with np.errstate(divide="ignore"):
+            self.dbtp = 20.0 * np.log10(true_peak)
+
+
+CEILING_MODES = {"sample": 0, "true_peak": 1}  # mi355vits_set_loudness_ceiling_mode: MI355VITS_CEILING_*
+
+
+def ceiling_mode_id(mode) -> int:
+    """``"sample"`` / ``"true_peak"`` (or ``False`` / ``True``) as the ABI's value; anything else raises ``ValueError`` naming it."""
+    if isinstance(mode, (bool, np.bool_)):
+        return int(mode)
+    if mode not in CEILING_MODES:
+        raise ValueError(f"ceiling mode {mode!r} is neither 'sample' nor 'true_peak'")
+    return CEILING_MODES[mode]
+
+
 def limiter_window(ms, rate) -> int:
     """A limiter window in milliseconds as samples at ``rate`` Hz (``round(ms * rate / 1000)``); ``None`` = off = 0.  A window
     outside 1 .. 4096 samples raises ``ValueError`` naming it."""
@@ -371,6 +406,11 @@ class NativeLibrary:
         L.mi355vits_fetch_limiter.argtypes = [H, ctypes.POINTER(LimiterResult)]
         L.mi355vits_free_limiter.argtypes = [ctypes.POINTER(LimiterResult)]
         L.mi355vits_free_limiter.restype = None
+        L.mi355vits_set_loudness_ceiling_mode.argtypes = [H, ctypes.c_int]
+        L.mi355vits_get_loudness_ceiling_mode.argtypes = [H]
+        L.mi355vits_fetch_true_peak.argtypes = [H, ctypes.POINTER(TruePeakResult)]
+        L.mi355vits_free_true_peak.argtypes = [ctypes.POINTER(TruePeakResult)]
+        L.mi355vits_free_true_peak.restype = None
         L.mi355vits_last_error.argtypes = [H]
         L.mi355vits_last_error.restype = ctypes.c_char_p
         L.mi355vits_profile_enable.argtypes = [H, ctypes.c_int]
@@ -414,6 +454,11 @@ class NativeLibrary:
             L.mi355vits_lab_loudness_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p]
             L.mi355vits_lab_limit.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
                                               ctypes.c_double, ctypes.c_int32, f32p, ctypes.POINTER(ctypes.c_int64), i32p]
+            f64p = ctypes.POINTER(ctypes.c_double)
+            L.mi355vits_lab_limit_env.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, f64p, ctypes.c_double, ctypes.c_double,
+                                                  ctypes.c_int32, f64p, f32p, ctypes.POINTER(ctypes.c_int64), i32p]
+            L.mi355vits_lab_true_peak.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.c_int32, f64p, f64p]
+            L.mi355vits_lab_true_peak_plan.argtypes = [f64p, i32p]
             L.mi355vits_test_alignment.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int64, f32p, i32p,
                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
@@ -483,11 +528,40 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return lufs, blocks, gated
 
-    def lab_limit(self, audio, lengths, g, c, U, window):
+    def lab_true_peak(self, audio, lengths, offset=0, envelope=True):
+        """The true-peak kernels (k_true_peak, k_true_peak_env) alone: audio [B, stride] f32 with lengths [B] valid samples each (what
+        lies behind them is never looked at), on the device ``offset`` (0 .. 3) floats behind a 16-byte boundary -> (tp float64 [B],
+        e float64 [B, stride] — the rule's ``e[t]`` at a row's valid samples, 0 behind them; ``None`` with ``envelope=False``)."""
+        self._need_hooks()
+        au = np.ascontiguousarray(audio, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        if au.ndim != 2 or ln.shape[0] != au.shape[0]:
+            raise ValueError("audio [B, stride], lengths [B]")
+        B = au.shape[0]
+        f64p = ctypes.POINTER(ctypes.c_double)
+        tp = np.zeros(B, np.float64)
+        env = np.zeros(au.shape, np.float64) if envelope else None
+        rc = self.lib.mi355vits_lab_true_peak(_fptr(au), au.shape[1], ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), B, int(offset),
+                                              tp.ctypes.data_as(f64p), env.ctypes.data_as(f64p) if envelope else None)
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return tp, env
+
+    def lab_true_peak_plan(self):
+        """``(taps float64 [81], tile)``: the library's tap table ``h`` and the samples of a k_true_peak work item.  No kernel runs."""
+        self._need_hooks()
+        taps, tile = np.zeros(81, np.float64), ctypes.c_int32()
+        rc = self.lib.mi355vits_lab_true_peak_plan(taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(tile))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return taps, int(tile.value)
+
+    def lab_limit(self, audio, lengths, g, c, U, window, envelope=None):
         """The limiter kernel (k_limit) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is
         never looked at), g [B] float64 the rows' gains, c the linear ceiling, U the encoding's unit (32767.0 or 1.0), ``window`` = L
         in samples -> (scale float32 [B, stride] — the rule's ``scale[k]`` at a row's valid samples, 0 behind them —, sq_min int64 [B],
-        reduced int32 [B]) as ``include/mi355vits.h`` defines them.  Every row is a job, over the ceiling or not."""
+        reduced int32 [B]) as ``include/mi355vits.h`` defines them.  Every row is a job, over the ceiling or not.  ``envelope``
+        [B, stride] float64: the true-peak form — ``envelope[b, t]`` in place of ``abs(audio[b, t])``."""
         self._need_hooks()
         au = np.ascontiguousarray(audio, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
@@ -498,9 +572,18 @@ class NativeLibrary:
         i32p = ctypes.POINTER(ctypes.c_int32)
         scale = np.zeros(au.shape, np.float32)
         sq_min, reduced = np.zeros(B, np.int64), np.zeros(B, np.int32)
-        rc = self.lib.mi355vits_lab_limit(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                          float(c), float(U), int(window), _fptr(scale), sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                          reduced.ctypes.data_as(i32p))
+        f64p = ctypes.POINTER(ctypes.c_double)
+        if envelope is not None:
+            ev = np.ascontiguousarray(envelope, np.float64)
+            if ev.shape != au.shape:
+                raise ValueError("envelope has the audio's shape")
+            rc = self.lib.mi355vits_lab_limit_env(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(f64p), float(c), float(U),
+                                                  int(window), ev.ctypes.data_as(f64p), _fptr(scale),
+                                                  sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), reduced.ctypes.data_as(i32p))
+        else:
+            rc = self.lib.mi355vits_lab_limit(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(f64p),
+                                              float(c), float(U), int(window), _fptr(scale), sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                              reduced.ctypes.data_as(i32p))
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return scale, sq_min, reduced
@@ -1152,9 +1235,31 @@ class Engine:
         finally:
             self.native.lib.mi355vits_free_limiter(ctypes.byref(r))
 
-    def lab_limit(self, audio, lengths, g, c, U, window):
+    def lab_limit(self, audio, lengths, g, c, U, window, envelope=None):
         """``NativeLibrary.lab_limit`` of this engine's library (the hooks library, the lab build or the CPU model)."""
-        return self.native.lab_limit(audio, lengths, g, c, U, window)
+        return self.native.lab_limit(audio, lengths, g, c, U, window, envelope)
+
+    def set_loudness_ceiling_mode(self, mode) -> None:
+        """What the ceiling of the loudness target bounds (``mi355vits_set_loudness_ceiling_mode``): ``"sample"`` (the default) the
+        row's sample peak, ``"true_peak"`` its 4x oversampled peak — in the gain rule and in what the limiter looks at.  Read where
+        the limiter window is read; without a target it does nothing to a pack."""
+        self._check(self.native.lib.mi355vits_set_loudness_ceiling_mode(self._h, ceiling_mode_id(mode)))
+
+    @property
+    def loudness_ceiling_mode(self) -> str:
+        """``"sample"`` or ``"true_peak"``."""
+        return "true_peak" if int(self.native.lib.mi355vits_get_loudness_ceiling_mode(self._h)) == 1 else "sample"
+
+    def fetch_true_peak(self) -> TruePeak:
+        """The 4x oversampled peak of every row of the last completed run, whatever the mode (``mi355vits_fetch_true_peak``)."""
+        r = TruePeakResult()
+        self._check(self.native.lib.mi355vits_fetch_true_peak(self._h, ctypes.byref(r)))
+        try:
+            B = int(r.batch)
+            return TruePeak(np.ctypeslib.as_array(r.true_peak, shape=(B,)).copy(), np.ctypeslib.as_array(r.peak, shape=(B,)).copy(),
+                            int(r.sample_rate))
+        finally:
+            self.native.lib.mi355vits_free_true_peak(ctypes.byref(r))
 
     def set_edge_trim(self, ratio, keep_samples: int = 0) -> None:
         """Trim each entry's quiet edges in the packed streams made after this (``mi355vits_set_edge_trim``): a sample is loud iff

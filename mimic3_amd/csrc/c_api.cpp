@@ -255,6 +255,24 @@ int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out) {
 
 void mi355vits_free_limiter(mi355vits_limiter* r) { free_struct(r); }
 
+int mi355vits_set_loudness_ceiling_mode(mi355vits_handle h, int mode) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_loudness_ceiling_mode(mode); });
+}
+
+int mi355vits_get_loudness_ceiling_mode(mi355vits_handle h) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return h->eng->loudness_ceiling_mode();
+}
+
+int mi355vits_fetch_true_peak(mi355vits_handle h, mi355vits_true_peak* out) {
+    return result_call(h, out, [&] { h->eng->fetch_true_peak(out); });
+}
+
+void mi355vits_free_true_peak(mi355vits_true_peak* r) { free_struct(r); }
+
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {

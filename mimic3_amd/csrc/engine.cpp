@@ -681,6 +681,7 @@ void Engine::fill_workspace(uint32_t pattern) {
     arena_ld_.fill(pattern, stream_);
     arena_lm_.fill(pattern, stream_);
     arena_lf_.fill(pattern, stream_);
+    arena_tp_.fill(pattern, stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
@@ -1613,6 +1614,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     have_result_ = false;
     have_edges_ = false;
     have_loud_ = false;
+    have_tp_ = false;
     taps_on_ = (args.flags & MI355VITS_DEBUG_TAPS) != 0;
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();

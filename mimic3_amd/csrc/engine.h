@@ -156,9 +156,11 @@ struct PackSettings {
     int trim_keep = 0;
     float loud_target = 0.0f, loud_ceiling = -1.0f;  // mi355vits_set_loudness_target: target 0 = off
     int limit_window = 0;        // mi355vits_set_loudness_limiter: samples at the run's rate, 0 = off; acts on packs with a target only
+    int ceil_mode = 0;           // mi355vits_set_loudness_ceiling_mode: MI355VITS_CEILING_*; acts on packs with a target only
     bool trimmed() const { return trim_ratio != 0.0f; }
     bool normalised() const { return loud_target != 0.0f; }
     bool limiting() const { return normalised() && limit_window > 0; }
+    bool true_peak() const { return normalised() && ceil_mode == MI355VITS_CEILING_TRUE_PEAK; }
 };
 
 // ---------------------------------------------------------------- the engine
@@ -208,6 +210,12 @@ class Engine {
     int loudness_limiter() const { return pack_.limit_window; }
     // which rows of the last completed run the limiter engages on under the current target, ceiling and window, and how far
     void fetch_limiter(mi355vits_limiter* out);
+    // what the ceiling of the loudness target bounds (mi355vits_set_loudness_ceiling_mode): the row's sample peak or its 4x
+    // oversampled peak.  Read where the limiter window is read.
+    void set_loudness_ceiling_mode(int mode);
+    int loudness_ceiling_mode() const { return pack_.ceil_mode; }
+    // the 4x oversampled peak of every row of the last completed run, whatever the mode (mi355vits_fetch_true_peak)
+    void fetch_true_peak(mi355vits_true_peak* out);
     const mi355vits_config& config() const { return cfg_; }
     void set_math(int mode);
     int math() const { return math_; }
@@ -328,15 +336,19 @@ class Engine {
     bool enqueue_edges(const std::vector<float>& ratios, bool keep);
     const std::vector<int>& edges_at(float ratio) const;  // [2][B] of the last run at a ratio the host holds
     bool enqueue_loudness();          // k_loud / k_loud_gate and their copy likewise (throws below LOUD_MIN_HZ)
+    bool enqueue_true_peak();         // k_true_peak and its copy likewise
     // what a pack needs from the audio: every launch, then ONE synchronisation (or none)
-    void measure_last_run(const std::vector<float>& ratios, bool loud, bool keep);
+    void measure_last_run(const std::vector<float>& ratios, bool loud, bool keep, bool true_peak = false);
+    // the peak the ceiling bounds, in double: the row's sample peak, or in true-peak mode its oversampled peak (measured before)
+    double ceiling_peak(int row, const PackSettings& set) const { return set.true_peak() ? h_tp_[(size_t)row] : (double)h_loud_peaks_[(size_t)row]; }
     // window > 0 (the limiter on): a limited row keeps its uncapped gain — k_limit holds its peaks under the ceiling instead
-    static void loudness_gain(double lufs, float peak, float target, float ceiling, int window, double* gain, bool* limited);
+    static void loudness_gain(double lufs, double peak, float target, float ceiling, int window, double* gain, bool* limited);
     // The limiter's jobs of a pack / a block / a fetch_limiter.  limit_job: the job of (row, set's target, ceiling and encoding
     // class) among `jobs`, appended when new.  run_limit_jobs: the jobs placed (their offsets checked before anything is sized),
     // uploaded and k_limit launched in `arena`; with_curve: d_curve_ = the curves, else statistics only.  Returns the device statistics.
     int limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g) const;
-    LimitStat* run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve);
+    // true_peak: k_true_peak_env writes the jobs' envelopes into the same arena first and k_limit reads them instead of the samples
+    LimitStat* run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve, bool true_peak);
     void limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const;  // plan.curve = each over entry's job (after place_pack)
     static void curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs);  // plan.curve: jobs -> their placed offsets
 
@@ -367,6 +379,7 @@ class Engine {
     DeviceArena arena_ld_;  // k_loud's step energies and k_loud_gate's 16 bytes per row, likewise
     DeviceArena arena_lm_;  // k_limit's jobs, statistics and curves of the pack being made: no fetch serves from it
     DeviceArena arena_lf_;  // mi355vits_fetch_limiter only: k_limit's jobs and statistics
+    DeviceArena arena_tp_;  // k_true_peak's 8 bytes per row, outside everything a run or another fetch lays out
     std::vector<Tap> taps_;
     bool taps_on_ = false;
     int B_ = 0, Tx_ = 0, Ty_ = 0;
@@ -417,6 +430,10 @@ class Engine {
     std::vector<double> h_loud_;  // 2 B doubles: lufs, then blocks / gated as int32 pairs
     std::vector<float> h_loud_peaks_;
     bool have_loud_ = false;
+    // true peak: the last run's tp [B] with the peaks [B] of the run, kept on the host likewise; dropped when a run starts
+    std::vector<double> h_tp_;
+    std::vector<float> h_tp_peaks_;
+    bool have_tp_ = false;
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
     int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)

@@ -288,7 +288,7 @@ void Engine::place_pack(PackPlan& plan) const {
         }
         if (set.normalised()) {
             bool limited;
-            loudness_gain(h_loud_[row], h_loud_peaks_[row], set.loud_target, set.loud_ceiling, set.limit_window, &plan.gain[i], &limited);
+            loudness_gain(h_loud_[row], ceiling_peak(row, set), set.loud_target, set.loud_ceiling, set.limit_window, &plan.gain[i], &limited);
         }
         pos += plan.lengths[i];
         plan.audio += plan.lengths[i];
@@ -384,14 +384,14 @@ void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_resu
 
 void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     HIP_CHECK(hipSetDevice(device_));
-    measure_last_run({plan.set.trim_ratio}, plan.set.normalised(), false);
+    measure_last_run({plan.set.trim_ratio}, plan.set.normalised(), false, plan.set.true_peak());
     place_pack(plan);
     if (plan.set.limiting()) {
         // the limiter: one job per entry the ceiling would hold back; the curves are made before the pack, on the same stream
         std::vector<LimitJob> jobs;
         limit_pack(plan, jobs);
         if (!jobs.empty()) {
-            run_limit_jobs(jobs, plan.set.limit_window, arena_lm_, true);
+            run_limit_jobs(jobs, plan.set.limit_window, arena_lm_, true, plan.set.true_peak());
             curve_offsets(plan, jobs);
         }
     }
@@ -448,7 +448,8 @@ void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, i
         set.trim_keep = a.trim_keep_samples;
         set.loud_target = a.target_lufs;
         if (a.target_lufs != 0.0f) set.loud_ceiling = a.ceiling_dbfs;
-        set.limit_window = pack_.limit_window;  // the one handle setting a streams call reads: mi355vits_stream_args is frozen
+        set.limit_window = pack_.limit_window;  // the handle settings a streams call reads: mi355vits_stream_args is frozen
+        set.ceil_mode = pack_.ceil_mode;
         try {
             plan_pack(&a.pack, B, set, sp.streams[s]);
         } catch (const EngineError& e) {
@@ -569,7 +570,7 @@ void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* o
             if (p.set.normalised()) {
                 bool lim = false;
                 out->lufs[e] = h_loud_[row];
-                loudness_gain(h_loud_[row], h_loud_peaks_[row], p.set.loud_target, p.set.loud_ceiling, p.set.limit_window, &out->gain[e], &lim);
+                loudness_gain(h_loud_[row], ceiling_peak(row, p.set), p.set.loud_target, p.set.loud_ceiling, p.set.limit_window, &out->gain[e], &lim);
                 out->limited[e] = lim ? 1 : 0;
             }
         }
@@ -615,12 +616,13 @@ void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, 
 void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
     HIP_CHECK(hipSetDevice(device_));
     std::vector<float> ratios;
-    bool loud = false;
+    bool loud = false, tp = false;
     for (const PackPlan& p : sp.streams) {
         ratios.push_back(p.set.trim_ratio);
         loud = loud || p.set.normalised();
+        tp = tp || p.set.true_peak();
     }
-    measure_last_run(ratios, loud, true);
+    measure_last_run(ratios, loud, true, tp);
     place_streams(sp);
     {
         // the limiter: one job per distinct (row, target, ceiling, encoding class) among the entries the ceiling would hold back
@@ -629,7 +631,7 @@ void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
             if (p.set.limiting()) limit_pack(p, jobs);
         sp.curved = !jobs.empty();
         if (sp.curved) {
-            run_limit_jobs(jobs, pack_.limit_window, arena_lm_, true);
+            run_limit_jobs(jobs, pack_.limit_window, arena_lm_, true, pack_.ceil_mode == MI355VITS_CEILING_TRUE_PEAK);
             for (PackPlan& p : sp.streams) curve_offsets(p, jobs);
         }
     }
@@ -737,14 +739,16 @@ bool Engine::enqueue_edges(const std::vector<float>& ratios, bool keep) {
 
 // What a pack needs from the audio before it can be placed: the edges at each of `ratios` (0: none) and / or the loudness, each
 // launched only when the host does not hold it, behind ONE synchronisation.
-void Engine::measure_last_run(const std::vector<float>& ratios, bool loud, bool keep) {
+void Engine::measure_last_run(const std::vector<float>& ratios, bool loud, bool keep, bool true_peak) {
     const bool e = enqueue_edges(ratios, keep);
     const bool l = loud && enqueue_loudness();
-    if (!e && !l) return;
+    const bool t = true_peak && enqueue_true_peak();
+    if (!e && !l && !t) return;
     HIP_CHECK(hipStreamSynchronize(stream_));
     if (e)
         for (EdgeSet& s : h_edges_) s.ready = true;
     if (l) have_loud_ = true;
+    if (t) have_tp_ = true;
 }
 
 // ---------------------------------------------------------------- BS.1770 loudness of a run's rows (mi355vits_set_loudness_target / _fetch_loudness)
@@ -758,9 +762,9 @@ void Engine::set_loudness_target(float target_lufs, float ceiling_dbfs) {
 }
 
 // The gain rule, in double: g = 10^((T - lufs) / 20) (1 for a row without a gated block), bounded by 10^(c / 20) / peak.
-void Engine::loudness_gain(double lufs, float peak, float target, float ceiling, int window, double* gain, bool* limited) {
+void Engine::loudness_gain(double lufs, double peak, float target, float ceiling, int window, double* gain, bool* limited) {
     const double g = std::isinf(lufs) ? 1.0 : std::pow(10.0, ((double)target - lufs) / 20.0);
-    const double p = (double)peak;
+    const double p = peak;  // (the sample peak converted exactly, or the oversampled peak: never NaN)
     *gain = g;
     *limited = false;
     if (p != 0.0) {
@@ -808,7 +812,8 @@ void Engine::fetch_loudness(mi355vits_loudness* out) {
     begin_fetch(out, "fetch_loudness");
     const float target = pack_.loud_target, ceiling = pack_.loud_ceiling;
     const int window = pack_.limit_window;
-    measure_last_run({}, true, false);
+    const PackSettings set = pack_;
+    measure_last_run({}, true, false, set.true_peak());
     const size_t B = (size_t)B_;
     out->batch = B_;
     out->sample_rate = run_hz_;
@@ -824,7 +829,7 @@ void Engine::fetch_loudness(mi355vits_loudness* out) {
     for (size_t b = 0; b < B; ++b) {
         double g = 0.0;
         bool lim = false;
-        if (target != 0.0f) loudness_gain(out->lufs[b], h_loud_peaks_[b], target, ceiling, window, &g, &lim);
+        if (target != 0.0f) loudness_gain(out->lufs[b], ceiling_peak((int)b, set), target, ceiling, window, &g, &lim);
         out->gain[b] = g;
         out->limited[b] = lim ? 1 : 0;
     }
@@ -863,7 +868,7 @@ void Engine::limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const {
         const int row = plan.order[i];
         double g;
         bool over;
-        loudness_gain(h_loud_[row], h_loud_peaks_[row], set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
+        loudness_gain(h_loud_[row], ceiling_peak(row, set), set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
         if (!over || h_olen_[row] < 1) continue;
         curve[i] = limit_job(jobs, row, set, g);
         any = true;
@@ -876,7 +881,7 @@ void Engine::curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs) {
         if (c >= 0) c = jobs[(size_t)c].off;
 }
 
-LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve) {
+LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve, bool true_peak) {
     long floats = 0;
     const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
     if (tiles < 0)
@@ -884,17 +889,23 @@ LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, Devic
     const size_t nj = jobs.size();
     // (reserve waits for the stream when the arena has to grow: "no synchronisation added" holds from the second pack of a size on, as for arena_p_)
     arena.reserve(DeviceArena::padded(sizeof(LimitJob) * nj) + DeviceArena::padded(sizeof(LimitStat) * nj) +
-                      (with_curve ? DeviceArena::padded(4 * (size_t)floats) : 0) + 4096, stream_);
+                      (with_curve ? DeviceArena::padded(4 * (size_t)floats) : 0) + (true_peak ? DeviceArena::padded(8 * (size_t)floats) : 0) + 4096,
+                  stream_);
     arena.reset();
     LimitJob* d_jobs = arena.alloc<LimitJob>(nj);
     LimitStat* d_stats = arena.alloc<LimitStat>(nj);
     float* curve = with_curve ? arena.alloc<float>((size_t)floats) : nullptr;
+    double* env = true_peak ? arena.alloc<double>((size_t)floats) : nullptr;  // e[t] of every job, one behind the other as the curves are
     if (with_curve) d_curve_ = curve;
     h_limit_jobs_ = jobs;  // a member: it outlives the copy
     HIP_CHECK(hipMemcpyAsync(d_jobs, h_limit_jobs_.data(), sizeof(LimitJob) * nj, hipMemcpyHostToDevice, stream_));
+    if (true_peak) {
+        ProfScope ps(prof_, "truepeak.env", 0, 12.0 * (double)floats);
+        launch_true_peak_env(d_jobs, (int)nj, tiles, o_audio_, Lo_, env, stream_);
+    }
     {
         ProfScope ps(prof_, "limit", 0, 8.0 * (double)floats + 16.0 * (double)nj);
-        launch_limit(d_jobs, (int)nj, tiles, window, o_audio_, Lo_, d_stats, curve, stream_);
+        launch_limit(d_jobs, (int)nj, tiles, window, o_audio_, Lo_, d_stats, curve, stream_, env);
     }
     return d_stats;
 }
@@ -915,16 +926,16 @@ void Engine::fetch_limiter(mi355vits_limiter* out) {
         out->min_scale[b] = 1.0;
     }
     if (!set.limiting()) return;  // nothing is measured or launched
-    measure_last_run({}, true, false);
+    measure_last_run({}, true, false, set.true_peak());
     std::vector<LimitJob> jobs;
     for (int b = 0; b < B_; ++b) {
         double g;
         bool over;
-        loudness_gain(h_loud_[b], h_loud_peaks_[b], set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
+        loudness_gain(h_loud_[b], ceiling_peak(b, set), set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
         if (over && h_olen_[b] >= 1) (void)limit_job(jobs, b, set, g);
     }
     if (jobs.empty()) return;
-    const LimitStat* d_stats = run_limit_jobs(jobs, set.limit_window, arena_lf_, false);
+    const LimitStat* d_stats = run_limit_jobs(jobs, set.limit_window, arena_lf_, false, set.true_peak());
     std::vector<LimitStat> st(jobs.size());
     HIP_CHECK(hipMemcpyAsync(st.data(), d_stats, sizeof(LimitStat) * st.size(), hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -935,6 +946,50 @@ void Engine::fetch_limiter(mi355vits_limiter* out) {
         out->reduced_samples[b] = st[j].reduced;
         out->min_scale[b] = (double)st[j].sq_min / den;
     }
+}
+
+// ---------------------------------------------------------------- the 4x oversampled peak (mi355vits_set_loudness_ceiling_mode / _fetch_true_peak)
+void Engine::set_loudness_ceiling_mode(int mode) {
+    if (mode != MI355VITS_CEILING_SAMPLE && mode != MI355VITS_CEILING_TRUE_PEAK)
+        throw EngineError(MI355VITS_ERR_INVALID, "set_loudness_ceiling_mode: mode " + std::to_string(mode) + " unknown (0 = sample peak, 1 = true peak)");
+    pack_.ceil_mode = mode;
+}
+
+// k_true_peak over the last run's rows in an arena of its own, and the copy of 8 B bytes + the peaks; nothing when the host still
+// holds them.
+bool Engine::enqueue_true_peak() {
+    if (have_tp_) return false;
+    const int B = B_;
+    long l_max = 0;
+    double audio = 0;
+    for (int b = 0; b < B; ++b) {
+        l_max = std::max<long>(l_max, h_olen_[b]);
+        audio += (double)h_olen_[b];
+    }
+    arena_tp_.reserve(8 * (size_t)B + 4096, stream_);
+    arena_tp_.reset();
+    double* d = arena_tp_.alloc<double>((size_t)B);
+    {
+        ProfScope ps(prof_, "truepeak", 0, 4.0 * audio + 8.0 * (double)B);
+        launch_true_peak(o_audio_, Lo_, o_alen_, B, l_max, d, stream_);
+    }
+    h_tp_.resize((size_t)B);
+    h_tp_peaks_.resize((size_t)B);
+    HIP_CHECK(hipMemcpyAsync(h_tp_.data(), d, 8 * (size_t)B, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(h_tp_peaks_.data(), o_peaks_, 4 * (size_t)B, hipMemcpyDeviceToHost, stream_));
+    return true;  // have_tp_ once the caller has synchronised
+}
+
+void Engine::fetch_true_peak(mi355vits_true_peak* out) {
+    begin_fetch(out, "fetch_true_peak");
+    measure_last_run({}, false, false, true);
+    const size_t B = (size_t)B_;
+    out->batch = B_;
+    out->sample_rate = run_hz_;
+    out->true_peak = static_cast<double*>(new_owner(out)->take_pinned(12 * B + 16));  // true_peak: doubles; peak: floats
+    out->peak = reinterpret_cast<float*>(out->true_peak + B);
+    memcpy(out->true_peak, h_tp_.data(), 8 * B);
+    memcpy(out->peak, h_tp_peaks_.data(), 4 * B);
 }
 
 void Engine::fetch_edges(mi355vits_edges* out) {

@@ -354,8 +354,19 @@ struct LimitStat {
 long limit_place_jobs(LimitJob* jobs, int n_jobs, long* curve_floats);
 // jobs / stats [n_jobs] and curve on the device; audio rows of audio_bs floats (a job reads its row's [0, n) and nothing behind
 // it); 1 <= L <= LIMIT_MAX_WINDOW.  stats are initialised here, on s, whatever they held; curve == nullptr: statistics only.
+// env != nullptr (true-peak ceiling mode): rq is made from env[job.off + t] — launch_true_peak_env's e[t] — instead of fabs((double) x[t]).
 void launch_limit(const LimitJob* jobs, int n_jobs, long tiles, int L, const float* audio, long audio_bs, LimitStat* stats, float* curve,
-                  hipStream_t s);
+                  hipStream_t s, const double* env = nullptr);
+
+// ---------------------------------------------------------------- 4x oversampled peak and its envelope (kernels_truepeak.cpp)
+constexpr int TRUE_PEAK_TAPS = 81;          // scipy.signal.resample_poly(., 4, 1)'s default filter: literal doubles in the source
+constexpr int TRUE_PEAK_TILE = LIMIT_TILE;  // samples of a work item: the envelope form runs on the limiter's job table
+const double* true_peak_taps();             // [TRUE_PEAK_TAPS]
+// audio [B] rows of audio_bs floats with alen [B] valid samples (device), l_max >= every alen[b] -> tp [B] doubles (device): the rule
+// of include/mi355vits.h.  tp is initialised here, on s, whatever it held.  What lies behind a row is never looked at.
+void launch_true_peak(const float* audio, long audio_bs, const int* alen, int B, long l_max, double* tp, hipStream_t s);
+// e[t] of every job's row to env[job.off + t] (jobs / tiles: limit_place_jobs'); every element has exactly one writer
+void launch_true_peak_env(const LimitJob* jobs, int n_jobs, long tiles, const float* audio, long audio_bs, double* env, hipStream_t s);
 
 // ---------------------------------------------------------------- encoder pieces
 void launch_embed(const long long* ids, const int* len, const float* emb, int B, int T, int H, int num_symbols,

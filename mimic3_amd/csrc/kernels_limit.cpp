@@ -18,6 +18,8 @@
 //   * Every curve element has exactly one writer (a plain store).  The two statistics of a job — min sq and the count of
 //     sq < (L + 1) 2^30 — are reduced over the workgroup and go through ONE integer atomicMin and ONE atomicAdd per item, on words
 //     k_limit_init set on the same stream before: the workspace is never assumed clean.
+//   * k_limit<true> (the true-peak ceiling mode, kernels_truepeak.cpp): a[t] = g * e[t] with e[t] read from the envelope array
+//     k_true_peak_env wrote for the same job table; everything behind rq is the same code.
 #include "kernels.h"
 
 #include <algorithm>
@@ -47,15 +49,20 @@ __global__ __launch_bounds__(256) void k_limit_init(LimitStat* __restrict__ stat
     stats[j].pad = 0;
 }
 
-__device__ __forceinline__ int limit_rq(float x, bool in, double g, double c) {
-    const double a = g * fabs((double)x);
+__device__ __forceinline__ int limit_rq_abs(double ax, bool in, double g, double c) {
+    const double a = g * ax;
     const bool over = in && a > c;  // NaN compares false
     const int q = (int)floor((c / (over ? a : c)) * 1073741824.0);  // (the quotient of a sample that is not over is 1: no division by 0)
     return over ? q : LIMIT_ONE;
 }
+__device__ __forceinline__ int limit_rq(float x, bool in, double g, double c) { return limit_rq_abs(fabs((double)x), in, g, c); }
 
+// ENV: the true-peak ceiling mode — a sample's rq is made from env[job.off + t] (k_true_peak_env's e[t], never NaN) and the audio is
+// not read.  ENV = false is the sample-peak kernel as it always was.
+template <bool ENV>
 __global__ __launch_bounds__(256) void k_limit(const LimitJob* __restrict__ jobs, int n_jobs, int L, const float* __restrict__ audio,
-                                               long audio_bs, LimitStat* __restrict__ stats, float* __restrict__ curve) {
+                                               long audio_bs, LimitStat* __restrict__ stats, float* __restrict__ curve,
+                                               const double* __restrict__ env) {
     __shared__ int buf[LIMIT_BUF];
     __shared__ long long sc[2][256];
     __shared__ long long tp[257];
@@ -83,26 +90,35 @@ __global__ __launch_bounds__(256) void k_limit(const LimitJob* __restrict__ jobs
     const int sh = (int)((mis + t0) & 3);
     const long w0 = t0 - sh;
     const int nq = (N + sh + 3) >> 2;
-    for (int q = tid; q < nq; q += 256) {
-        const long k = w0 + 4L * q;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        bool in[4] = {false, false, false, false};
-        if (k >= 0 && k + 4 <= n) {
-            const float4 a = *reinterpret_cast<const float4*>(y + k);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-            in[0] = in[1] = in[2] = in[3] = true;
-        } else if (k + 4 > 0 && k < n) {
+    if constexpr (ENV) {  // (doubles in the limiter's own workspace, one per sample of the job: no quads, no alignment question)
+        const double* e = env + (long)jobs[job].off;
+        for (int j = tid; j < N; j += 256) {
+            const long k = t0 + j;
+            const bool in = k >= 0 && k < n;
+            buf[j] = limit_rq_abs(e[in ? k : 0L], in, g, c);
+        }
+    } else {
+        for (int q = tid; q < nq; q += 256) {
+            const long k = w0 + 4L * q;
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            bool in[4] = {false, false, false, false};
+            if (k >= 0 && k + 4 <= n) {
+                const float4 a = *reinterpret_cast<const float4*>(y + k);
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+                in[0] = in[1] = in[2] = in[3] = true;
+            } else if (k + 4 > 0 && k < n) {
+                MI355_UNROLL
+                for (int cc = 0; cc < 4; ++cc) {
+                    const long kc = k + cc;
+                    in[cc] = kc >= 0 && kc < n;
+                    v[cc] = y[in[cc] ? kc : 0L];
+                }
+            }
             MI355_UNROLL
             for (int cc = 0; cc < 4; ++cc) {
-                const long kc = k + cc;
-                in[cc] = kc >= 0 && kc < n;
-                v[cc] = y[in[cc] ? kc : 0L];
+                const int j = 4 * q + cc - sh;
+                if (j >= 0 && j < N) buf[j] = limit_rq(v[cc], in[cc], g, c);
             }
-        }
-        MI355_UNROLL
-        for (int cc = 0; cc < 4; ++cc) {
-            const int j = 4 * q + cc - sh;
-            if (j >= 0 && j < N) buf[j] = limit_rq(v[cc], in[cc], g, c);
         }
     }
     __syncthreads();
@@ -217,11 +233,15 @@ long limit_place_jobs(LimitJob* jobs, int n_jobs, long* curve_floats) {
 }
 
 void launch_limit(const LimitJob* jobs, int n_jobs, long tiles, int L, const float* audio, long audio_bs, LimitStat* stats, float* curve,
-                  hipStream_t s) {
+                  hipStream_t s, const double* env) {
     if (n_jobs <= 0 || L < 1 || L > LIMIT_MAX_WINDOW) return;
     LAUNCH_KERNEL(k_limit_init, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s, stats, n_jobs, L);
     if (tiles <= 0) return;
-    LAUNCH_KERNEL(k_limit, dim3((unsigned)tiles), dim3(256), 0, s, jobs, n_jobs, L, audio, audio_bs, stats, curve);
+    if (env) {
+        LAUNCH_KERNEL(k_limit<true>, dim3((unsigned)tiles), dim3(256), 0, s, jobs, n_jobs, L, audio, audio_bs, stats, curve, env);
+    } else {
+        LAUNCH_KERNEL(k_limit<false>, dim3((unsigned)tiles), dim3(256), 0, s, jobs, n_jobs, L, audio, audio_bs, stats, curve, env);
+    }
 }
 
 }  // namespace m355

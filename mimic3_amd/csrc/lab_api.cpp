@@ -256,6 +256,11 @@ int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens,
 
 int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
                         float* scale_out, int64_t* sq_min, int32_t* reduced) {
+    return mi355vits_lab_limit_env(audio, stride, lens, B, g, c, U, L, nullptr, scale_out, sq_min, reduced);
+}
+
+int mi355vits_lab_limit_env(const float* audio, long stride, const int32_t* lens, int B, const double* g, double c, double U, int32_t L,
+                            const double* env, float* scale_out, int64_t* sq_min, int32_t* reduced) {
     return guarded(nullptr, [&] {
         if (!audio || !lens || !g || !scale_out || !sq_min || !reduced || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
         if (L < 1 || L > LIMIT_MAX_WINDOW) throw EngineError(MI355VITS_ERR_INVALID, "window " + std::to_string(L) + " is outside [1, " + std::to_string(LIMIT_MAX_WINDOW) + "]");
@@ -283,7 +288,12 @@ int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, in
         HIP_CHECK(hipMemcpy(dj.p, jobs.data(), jobs.size() * sizeof(LimitJob), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(ds.p, 0x5a, jobs.size() * sizeof(LimitStat)));  // the launch initialises its words itself
         HIP_CHECK(hipMemset(dc.p, 0xff, (size_t)floats * 4));              // NaN: the launch writes every curve element
-        launch_limit(dj.as<LimitJob>(), (int)jobs.size(), tiles, L, da.as<float>(), stride, ds.as<LimitStat>(), dc.as<float>(), nullptr);
+        DevBuf de(env ? (size_t)floats * 8 : 8);
+        if (env)  // the jobs' envelopes one behind the other, as k_true_peak_env leaves them
+            for (const LimitJob& j : jobs)
+                HIP_CHECK(hipMemcpy(de.as<double>() + j.off, env + (size_t)j.row * stride, (size_t)j.n * 8, hipMemcpyHostToDevice));
+        launch_limit(dj.as<LimitJob>(), (int)jobs.size(), tiles, L, da.as<float>(), stride, ds.as<LimitStat>(), dc.as<float>(), nullptr,
+                     env ? de.as<double>() : nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipGetLastError());
         std::vector<LimitStat> st(jobs.size());
@@ -296,6 +306,55 @@ int mi355vits_lab_limit(const float* audio, long stride, const int32_t* lens, in
             sq_min[b] = (int64_t)st[j].sq_min;
             reduced[b] = st[j].reduced;
         }
+    });
+}
+
+int mi355vits_lab_true_peak(const float* audio, long stride, const int32_t* lens, int B, int32_t offset_floats, double* tp, double* env_out) {
+    return guarded(nullptr, [&] {
+        if (!audio || !lens || !tp || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
+        if (offset_floats < 0 || offset_floats > 3) throw EngineError(MI355VITS_ERR_INVALID, "offset_floats must be 0 .. 3");
+        long l_max = 0;
+        std::vector<LimitJob> jobs;  // the envelope form: one job per non-empty row
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            l_max = std::max<long>(l_max, lens[b]);
+            if (lens[b] < 1) continue;
+            LimitJob j;
+            j.g = j.c = j.U = 1.0; j.row = b; j.n = lens[b]; j.off = j.tile0 = 0;
+            jobs.push_back(j);
+        }
+        const size_t na = (size_t)B * stride;
+        DevBuf da((na + 4) * 4), dl((size_t)B * 4), dt((size_t)B * 8);
+        HIP_CHECK(hipMemset(da.p, 0xff, (na + 4) * 4));  // NaN in front of the first row and behind the last
+        float* d_audio = da.as<float>() + offset_floats;
+        HIP_CHECK(hipMemcpy(d_audio, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dt.p, 0x5a, (size_t)B * 8));  // the launch initialises its words itself
+        launch_true_peak(d_audio, stride, dl.as<int>(), B, l_max, dt.as<double>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(tp, dt.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+        if (!env_out) return;
+        for (size_t i = 0; i < na; ++i) env_out[i] = 0.0;
+        if (jobs.empty()) return;
+        long floats = 0;
+        const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
+        if (tiles < 0) throw EngineError(MI355VITS_ERR_INVALID, "the envelopes together exceed 2^31 - 1 samples");
+        DevBuf dj(jobs.size() * sizeof(LimitJob)), de((size_t)floats * 8);
+        HIP_CHECK(hipMemcpy(dj.p, jobs.data(), jobs.size() * sizeof(LimitJob), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(de.p, 0xff, (size_t)floats * 8));  // NaN: the launch writes every element
+        launch_true_peak_env(dj.as<LimitJob>(), (int)jobs.size(), tiles, d_audio, stride, de.as<double>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        for (const LimitJob& j : jobs)
+            HIP_CHECK(hipMemcpy(env_out + (size_t)j.row * stride, de.as<double>() + j.off, (size_t)j.n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_true_peak_plan(double* taps, int32_t* tile) {
+    return guarded(nullptr, [&] {
+        if (taps) memcpy(taps, true_peak_taps(), sizeof(double) * TRUE_PEAK_TAPS);
+        if (tile) *tile = TRUE_PEAK_TILE;
     });
 }
 

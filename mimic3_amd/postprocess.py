@@ -100,9 +100,10 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
 
     ``settings``: ``scales`` ([3] or [B, 3]; default the reference's 0.667 / 1.0 / 0.8), ``sid`` (multi-speaker voices), and
     ``volume`` / ``utterance_keys`` / ``tail_ms`` / ``sample_rate`` / ``encoding`` / ``trim_db`` / ``trim_keep_ms`` /
-    ``loudness`` / ``ceiling_db`` / ``limiter_ms`` as ``run_packed`` takes them (with ``loudness=-23`` every sentence is scaled to that BS.1770
+    ``loudness`` / ``ceiling_db`` / ``limiter_ms`` / ``true_peak`` as ``run_packed`` takes them (with ``loudness=-23`` every sentence is scaled to that BS.1770
     integrated loudness instead of to its own peak, and with ``limiter_ms=5`` a sentence whose peak the ceiling would hold back
-    reaches the target through a look-ahead peak limiter; with ``trim_db`` each sentence is cut to its loud part, so ``break_ms`` is the pause heard; with
+    reaches the target through a look-ahead peak limiter, and with ``true_peak=True`` the ceiling is in dBTP: it bounds the 4x
+    oversampled peak; with ``trim_db`` each sentence is cut to its loud part, so ``break_ms`` is the pause heard; with
     ``sample_rate`` the file is at that rate and ``break_ms`` counts ``int(ms / 1000 * sample_rate)`` samples of it; with
     ``encoding="ulaw"`` and ``sample_rate=8000`` it is the G.711 file a telephony stack plays).
 

@@ -657,6 +657,9 @@ class InferenceSession:
             ms = float(self.loudness_limiter_ms)
             if not (np.isfinite(ms) and ms > 0.0):
                 raise ValueError(f"loudness_limiter_ms must be finite and > 0 (or None = off), not {self.loudness_limiter_ms!r}")
+        # what the ceiling bounds (Engine.set_loudness_ceiling_mode): False = the sample peak, True = the 4x oversampled peak; a
+        # call's ``true_peak=`` goes before it
+        self.loudness_true_peak: bool = bool(kwargs.pop("loudness_true_peak", False))
         if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
             weights = _model_bytes(bytes(path_or_bytes))
             self._model_path = None
@@ -767,7 +770,7 @@ class InferenceSession:
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
-                   limiter_ms: Optional[float] = None) -> "_native.PackedAudio":
+                   limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -794,7 +797,10 @@ class InferenceSession:
         ``limiter_ms`` (else the session's ``loudness_limiter_ms``; ``None`` = off): with a loudness target, an entry the ceiling
         would hold back is brought to its target by a look-ahead peak limiter with a window of ``round(limiter_ms * rate / 1000)``
         samples instead (``Engine.set_loudness_limiter``; 1 .. 4096 samples, else ``ValueError`` naming the value); ``.gain`` is then
-        the uncapped gain and ``.limited`` marks the entries the limiter acted on."""
+        the uncapped gain and ``.limited`` marks the entries the limiter acted on.
+        ``true_peak`` (else the session's ``loudness_true_peak``): with a loudness target, ``ceiling_db`` bounds the entry's 4x
+        oversampled peak (dBTP) instead of its largest sample, in the gain and in what the limiter looks at
+        (``Engine.set_loudness_ceiling_mode``)."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -816,6 +822,7 @@ class InferenceSession:
         kw["_loudness"] = _loudness_setting(loudness if loudness is not None else self.loudness_lufs,
                                             ceiling_db if ceiling_db is not None else self.loudness_ceiling_db)
         kw["_limiter"] = _native.limiter_window(limiter_ms if limiter_ms is not None else self.loudness_limiter_ms, rate)
+        kw["_ceiling"] = bool(self.loudness_true_peak if true_peak is None else true_peak)
         out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _packed=True, order=order,
                                lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=wav, **kw)
         if alignment:
@@ -836,15 +843,17 @@ class InferenceSession:
     def run_stream(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None, loudness: Optional[float] = None,
-                   ceiling_db: Optional[float] = None, limiter_ms: Optional[float] = None) -> "_native.PackedAudio":
+                   ceiling_db: Optional[float] = None, limiter_ms: Optional[float] = None,
+                   true_peak: Optional[bool] = None) -> "_native.PackedAudio":
         """``run_packed`` (same keywords, except ``alignment``; same ``PackedAudio``; the same bytes when ``utterance_keys`` are
         given or the noise scales are zero — a row without a key of its own takes its Philox index from its place in the shared
         call, as in any micro-batched call, so its noise is not that of the request run alone) THROUGH the micro-batcher: the
         feed's rows — one or a few sentences of one client — share an engine call with the requests of other callers that arrive
         meanwhile, and come back as that caller's own finished stream (``mi355vits_run_streams``: one stream per request, each
         with its own order, silences, header, encoding, trim and loudness target; one kernel, one device-to-host copy for the whole
-        batch).  Requests group by ``sid`` presence, phoneme-length class, output rate and limiter window only (the window is the
-        one setting ``mi355vits_run_streams`` reads from the handle, so requests with different ``limiter_ms`` never share a call).  The result is a view of the
+        batch).  Requests group by ``sid`` presence, phoneme-length class, output rate, limiter window and ceiling mode only (the window
+        and the mode are the settings ``mi355vits_run_streams`` reads from the handle, so requests with different ``limiter_ms`` or
+        ``true_peak`` never share a call).  The result is a view of the
         batch's shared pinned block: nothing is copied per request.  A feed of more than ``micro_batch_max`` rows, or a session
         without a micro-batcher, takes ``run_packed`` directly."""
         ids, lengths, sid = self._feed(input_feed)
@@ -853,7 +862,7 @@ class InferenceSession:
             return self.run_packed(input_feed, order=order, lead_ms=lead_ms, lead_samples=lead_samples, tail_ms=tail_ms, wav=wav,
                                    volume=volume, utterance_keys=utterance_keys, sample_rate=sample_rate, encoding=encoding,
                                    trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db,
-                                   limiter_ms=limiter_ms)
+                                   limiter_ms=limiter_ms, true_peak=true_peak)
         kw = self._pcm_kw(volume, utterance_keys)
         for name in ("pcm_volume", "utterance_keys"):
             if name in kw and np.ndim(kw[name]) > 0 and len(kw[name]) != B:
@@ -876,6 +885,7 @@ class InferenceSession:
         kw["_kind"] = "stream"
         # a top-level keyword, not part of the stream's own settings: the micro-batcher groups by it
         kw["_limiter"] = _native.limiter_window(limiter_ms if limiter_ms is not None else self.loudness_limiter_ms, rate)
+        kw["_ceiling"] = bool(self.loudness_true_peak if true_peak is None else true_peak)  # likewise
         kw["_stream"] = dict(order=order, lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=bool(wav),
                              encoding=_encoding_name(encoding) if encoding is not None else self.output_encoding,
                              trim=(ratio, int((keep_ms / 1000.0) * rate)),
@@ -945,7 +955,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, _trim=None, _loudness=None, _streams=None, _limiter=0, **kw):
+                    _alignment=None, _trim=None, _loudness=None, _streams=None, _limiter=0, _ceiling=False, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -966,7 +976,8 @@ class InferenceSession:
                 eng.set_loudness_target(*(_loudness or (0.0, -1.0)))  # likewise
             if _packed or _streams is not None:  # the limiter window: set on every packed call, back to off for one that does not ask
                 eng.set_loudness_limiter(_limiter or 0)
-            if _streams is not None:  # every stream brings its own encoding, trim and target: of the lane's settings only the limiter window is read
+                eng.set_loudness_ceiling_mode(bool(_ceiling))  # the ceiling mode likewise: back to the sample peak for a call that does not ask
+            if _streams is not None:  # every stream brings its own encoding, trim and target: of the lane's settings only the limiter window and the ceiling mode are read
                 kw["streams"] = _streams
             call = eng.run_streams if _streams is not None else eng.run_packed if _packed else eng.run
             out = call(ids, lengths, scales, sid, seed=self._seed, utterance_base=base, utterance_keys=keys, **kw)
