@@ -592,6 +592,46 @@ typedef struct mi355vits_true_peak {
 int mi355vits_fetch_true_peak(mi355vits_handle h, mi355vits_true_peak* out);
 void mi355vits_free_true_peak(mi355vits_true_peak* r);
 
+/* ---- The packed stream as FLAC: lossless frames encoded on the GPU.  MI355VITS_COMPRESS_NONE (the default) = nothing below
+ * applies: every byte, launch and synchronisation is what it was before this setting existed.
+ * FLAC is a compression layer over the S16LE stream, not a fifth sample encoding: the int16 stream k_pack writes on the device —
+ * with every setting applied: order, silences, volume, output rate, edge trim, loudness target, limiter, ceiling mode — is turned
+ * into FLAC frames by a second kernel (k_flac_frames, one workgroup per frame of 4096 samples), and only the compressed bytes cross
+ * the bus.
+ *  - With MI355VITS_COMPRESS_FLAC, bytes[0, n_bytes) of the mi355vits_packed_result is a complete FLAC file: "fLaC", one STREAMINFO
+ *    block (42 bytes together: block size 4096, the smallest and largest frame in bytes, the run's rate, 1 channel, 16 bits,
+ *    total_samples; the MD5 field is all zero — NOT computed: it needs a serial pass over the whole stream), then the frames back to
+ *    back.  pcm points at the first frame, bytes + 42.  n, total_samples, offsets, lengths and peaks are exactly those of the same
+ *    call uncompressed, in SAMPLES.
+ *  - Contract: decoding the file yields, sample for sample and bit for bit, the int16 stream mi355vits_fetch_packed returns for the
+ *    same pack arguments and handle settings with compression off — in every math mode, at any output rate, with trim, loudness,
+ *    limiter and true-peak mode on or off.  The bytes are a pure function of (int16 stream, rate): nothing depends on the grid, the
+ *    CU count, the batch or an address.
+ *  - The subset of RFC 9639 written (DESIGN.md §4.15 has every field): fixed block size 4096 (the last frame may be short), one
+ *    subframe per frame — constant when all samples are equal, else the fixed predictor of order 0 .. 4 with the fewest bits (Rice
+ *    partition order 4 in a full block, 0 in a short one; every Rice parameter 0 .. 14 chosen by exact count, never the escape
+ *    code), or verbatim when no order saves a bit — CRC-8 over the frame header and CRC-16 over the frame.
+ *    The bytes are pinned by a reference encoder and an independently written decoder in the test suite; they have not met a
+ *    third-party decoder.
+ *  - The setting is read when a pack is made: at the start of mi355vits_run_packed and at each mi355vits_fetch_packed, as the
+ *    encoding is.  One synthesis can therefore be fetched raw and as FLAC, no synthesis work repeated.  mi355vits_clone inherits it.
+ *    An unknown value returns MI355VITS_ERR_INVALID with a message naming the value and leaves the setting as it was.
+ *  - Errors, all MI355VITS_ERR_INVALID, found before anything is sized or launched: an output encoding other than S16LE
+ *    ("pack: FLAC compresses the s16le stream; output encoding is ulaw"), wav_header != 0 ("a FLAC stream carries its own
+ *    header"), a run rate above 1,048,575 Hz (STREAMINFO's 20 bits).  total_samples <= 2^31 - 1 as before.
+ *  - Size: a frame is at most 16 + 2 * (its samples) bytes, so n_bytes <= 42 + 16 * frames + 2 * total_samples; a full frame of
+ *    equal samples is 11 bytes.
+ *  - Cost: the compressed size depends on the audio, so a FLAC pack costs exactly ONE stream synchronisation more than the same
+ *    call uncompressed and copies 4 * (frames + 1) bytes more to the host (the frame sizes and their total); the copy of the result
+ *    is exactly n_bytes - 42 bytes.  The profiler reports the launches as pack.flac with 2 * total_samples + (n_bytes - 42) bytes,
+ *    behind the pcm16.pack line of the S16LE pack in front of them.
+ *  - Scope: mi355vits_run_packed and mi355vits_fetch_packed.  mi355vits_run_streams / _fetch_streams never read the setting
+ *    (mi355vits_stream_args is frozen) and stay byte for byte what they are. */
+#define MI355VITS_COMPRESS_NONE 0   /* default: every byte, launch and synchronisation is what it was */
+#define MI355VITS_COMPRESS_FLAC 1
+int mi355vits_set_output_compression(mi355vits_handle h, int mode);
+int mi355vits_get_output_compression(mi355vits_handle h);
+
 /* ---- Packed streams per request: SEVERAL independent streams out of one run.  A server that batches the sentences of many clients
  * into one synthesis call (one or a few rows per client) wants one finished stream per CLIENT — its own order, silences, header,
  * encoding, trim and loudness target — not one stream per call.  One kernel (k_pack_streams, csrc/kernels_pack.cpp) writes all of them

@@ -106,6 +106,14 @@ int mi355vits_lab_loudness_plan(int32_t rate, int32_t* step, int32_t* warmup, in
 /* Kernel unit-test hook: the G.711 encoders of the encoded packed streams (mi355vits_set_output_encoding) over an array on the
  * current device.  law = MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW; out[i] = the code of in[i].  65,536 inputs cover the function. */
 int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);
+/* Kernel unit-test hook: the FLAC kernels (k_flac_frames, k_flac_scan, k_flac_gather; mi355vits_set_output_compression) alone over an
+ * arbitrary int16 stream on the current device: pcm [n] (n >= 0) at `rate` Hz (1 .. 1,048,575) -> out[0, *n_bytes) = the complete
+ * file (42 header bytes, then the frames), frame_sizes [ceil(n / 4096)] (or NULL) = the bytes of every frame.  The frames carry the
+ * numbers first_frame, first_frame + 1, ... (all below 2^21; STREAMINFO is that of a stream that starts here), so a test reaches the
+ * multi-byte frame numbers with two frames.  On the device the samples start as many bytes behind a 16-byte boundary as pcm does on
+ * the host (pcm & 15).  cap < the file's size: MI355VITS_ERR_INVALID, with *n_bytes = the size needed. */
+int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_frame, uint8_t* out, size_t cap, size_t* n_bytes,
+                       int32_t* frame_sizes);
 /* Kernel micro-benchmark hook (tools/convbench.py): times `reps` launches of one MFMA Conv1d on random device data.
  * epi: 0 = standard epilogue (bias + residual), 1 = WaveNet gate (Cout = 2*H), 2 = res/skip.  (The tile-shape overrides
  * MI355VITS_CONV_CFG / MI355VITS_CONV_CHUNK exist in the lab build of the library only, csrc/hipx.h lab_getenv.) */

@@ -7,6 +7,7 @@ binding at its CPU model of the kernels, ``tests/emu/libmi355vits_emu.so``.)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -37,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
     "mi355vits_set_output_rate", "mi355vits_get_output_rate",
     "mi355vits_set_output_encoding", "mi355vits_get_output_encoding",
+    "mi355vits_set_output_compression", "mi355vits_get_output_compression",
     "mi355vits_fetch_alignment", "mi355vits_free_alignment",
     "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
     "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
@@ -50,7 +52,7 @@ LAB_SYMBOLS = (
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
-    "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan",
+    "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac",
 )
 
 
@@ -313,6 +315,23 @@ ENCODINGS = {"s16le": (0, "<i2"), "ulaw": (1, "u1"), "alaw": (2, "u1"), "f32le":
 _ENCODING_NAMES = {v[0]: k for k, v in ENCODINGS.items()}
 
 
+# mi355vits_set_output_compression: name -> MI355VITS_COMPRESS_*
+COMPRESSIONS = {None: 0, "none": 0, "flac": 1}
+FLAC_HEADER_BYTES = 42  # "fLaC" + the STREAMINFO block: the first frame starts here
+_HANDLE = object()  # compression=: "whatever the handle's setting is"
+
+
+def compression_id(compression) -> int:
+    """``"flac"`` / ``None`` (or ``"none"``, or the MI355VITS_COMPRESS_* value itself) -> MI355VITS_COMPRESS_*; an unknown name raises
+    ``ValueError``, an unknown number is left to the library to refuse."""
+    if compression is None or isinstance(compression, str):
+        key = compression.lower() if isinstance(compression, str) else None
+        if key not in COMPRESSIONS:
+            raise ValueError(f"unknown output compression {compression!r} ('flac' or None)")
+        return COMPRESSIONS[key]
+    return int(compression)
+
+
 def encoding_id(encoding) -> int:
     """``"s16le"`` / ``"ulaw"`` / ``"alaw"`` / ``"f32le"`` (or the MI355VITS_ENC_* value itself) -> MI355VITS_ENC_*; an unknown
     name raises ``ValueError``, an unknown number is left to the library to refuse."""
@@ -369,6 +388,8 @@ class NativeLibrary:
         L.mi355vits_get_output_rate.restype = ctypes.c_int32
         L.mi355vits_set_output_encoding.argtypes = [H, ctypes.c_int]
         L.mi355vits_get_output_encoding.argtypes = [H]
+        L.mi355vits_set_output_compression.argtypes = [H, ctypes.c_int]
+        L.mi355vits_get_output_compression.argtypes = [H]
         L.mi355vits_destroy.argtypes = [H]
         L.mi355vits_destroy.restype = None
         L.mi355vits_get_config.argtypes = [H, ctypes.POINTER(CVitsConfig)]
@@ -449,6 +470,8 @@ class NativeLibrary:
                                                   ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_lab_g711_encode.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int16), ctypes.c_long, ctypes.POINTER(ctypes.c_uint8)]
             i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+            L.mi355vits_lab_flac.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8),
+                                             ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), i32p]
             L.mi355vits_lab_edges.argtypes = [f32p, ctypes.c_long, i32p, f32p, ctypes.c_int, ctypes.c_float, i32p, i32p]
             L.mi355vits_lab_loudness.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), i32p, i32p]
             L.mi355vits_lab_loudness_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p]
@@ -489,6 +512,25 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return out
+
+    def lab_flac(self, samples, rate: int, first_frame: int = 0):
+        """The FLAC kernels alone over int16 ``samples`` (a contiguous 1-d int16 array is read where it is: its address modulo 16 is
+        the samples' on the device) -> (the complete file as bytes, frame sizes int32 [ceil(n / 4096)])."""
+        self._need_hooks()
+        x = np.asarray(samples)
+        if x.dtype != np.int16 or x.ndim != 1 or not x.flags.c_contiguous:
+            x = np.ascontiguousarray(samples, np.int16).reshape(-1)
+        n = int(x.shape[0])
+        frames = (n + 4095) // 4096
+        out = np.empty(42 + 16 * frames + 2 * n, np.uint8)
+        sizes = np.zeros(max(frames, 1), np.int32)
+        got = ctypes.c_size_t(0)
+        rc = self.lib.mi355vits_lab_flac(ctypes.c_void_p(x.ctypes.data), n, int(rate), int(first_frame),
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.shape[0], ctypes.byref(got),
+                                         sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out[: int(got.value)].tobytes(), sizes[:frames].copy()
 
     def lab_edges(self, audio, lengths, peaks, ratio):
         """The edge kernel (k_edges) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is never
@@ -843,10 +885,14 @@ class PackedAudio:
     int16 stream, and raises for any other encoding.  With edge trimming on (``Engine.set_edge_trim``) entry i is samples
     ``first[i] : end[i]`` of its row (``lengths[i] = end[i] - first[i]``); both are ``None`` when trimming is off.  With a loudness
     target (``Engine.set_loudness_target``) ``lufs[i]`` is the entry's row's integrated loudness, ``gain[i]`` the linear gain its
-    samples carry and ``limited[i]`` whether the ceiling bounded it; all three are ``None`` when the target is off."""
+    samples carry and ``limited[i]`` whether the ceiling bounded it; all three are ``None`` when the target is off.
+    A compressed stream (``compression == "flac"``): ``flac`` is the complete FLAC file as a memoryview of the block, ``data``,
+    ``rows`` and ``wav`` are ``None`` (no decoder is part of the product), and ``offsets`` / ``lengths`` / ``peaks`` /
+    ``total_samples`` are those of the same call uncompressed, in samples."""
 
     def __init__(self, pcm, offsets, lengths, peaks, wav, sample_rate=None, encoding="s16le", first=None, end=None, lufs=None,
-                 gain=None, limited=None):
+                 gain=None, limited=None, compression=None, flac=None, total_samples=None):
+        self.compression, self.flac = compression, flac
         self.first, self.end = first, end
         self.lufs, self.gain, self.limited = lufs, gain, limited
         self.alignment: Optional[Alignment] = None  # set by InferenceSession.run_packed(alignment=...): spans in stream samples
@@ -856,11 +902,13 @@ class PackedAudio:
         self.data, self.offsets, self.lengths, self.peaks, self.wav = pcm, offsets, lengths, peaks, wav
         self.encoding = encoding
         self.sample_rate = sample_rate  # of every sample of the stream: the rate the run ran at
-        self.total_samples = int(pcm.shape[0])
-        self.rows = [pcm[int(o): int(o) + int(n)] for o, n in zip(offsets, lengths)]
+        self.total_samples = int(pcm.shape[0]) if pcm is not None else int(total_samples)
+        self.rows = None if pcm is None else [pcm[int(o): int(o) + int(n)] for o, n in zip(offsets, lengths)]
 
     @property
     def pcm(self):
+        if self.compression:
+            raise ValueError(f"this packed stream is compressed ({self.compression}): read .flac")
         if self.encoding != "s16le":
             raise ValueError(f"this packed stream is {self.encoding}, not int16 PCM: read .data")
         return self.data
@@ -1026,12 +1074,15 @@ class Engine:
 
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
-                   debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> PackedAudio:
+                   debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE) -> PackedAudio:
         """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
         ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
         the last entry, with ``wav`` a 44-byte RIFF header in front.  Each entry is bitwise that row of
-        ``run(..., want_pcm16=True)`` for the same arguments; one kernel, one device-to-host copy of exactly that many bytes."""
+        ``run(..., want_pcm16=True)`` for the same arguments; one kernel, one device-to-host copy of exactly that many bytes.
+        ``compression="flac"`` / ``None``: this call's stream compressed or not, whatever ``set_output_compression`` says (the
+        setting is put back afterwards); with FLAC the result's ``.flac`` is the file and ``wav=True`` raises ``ValueError``."""
+        comp = self._call_compression(compression, wav)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = DEBUG_TAPS if debug_taps else 0
@@ -1042,16 +1093,19 @@ class Engine:
         trimmed = self.edge_trim[0] != 0.0  # likewise
         normalised = self.loudness_target[0] != 0.0
         r = PackedResult()
-        self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
-                                                         None if p is None else ctypes.byref(p), ctypes.byref(r)))
+        with self._compression_for_call(compression):
+            self._check(self.native.lib.mi355vits_run_packed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                             None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del keep, pkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate
-        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised)
+        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised, comp)
 
-    def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False) -> PackedAudio:
+    def fetch_packed(self, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False, compression=_HANDLE) -> PackedAudio:
         """Pack the last completed run of this handle again (``mi355vits_fetch_packed``): that run's rows and per-row volumes,
-        another order / silences / header; nothing is synthesised again."""
+        another order / silences / header; nothing is synthesised again.  ``compression`` as for ``run_packed``: one synthesis can be
+        fetched raw and as FLAC."""
+        comp = self._call_compression(compression, wav)
         p, pkeep = self._pack_args(order, lead_samples, tail_samples, wav)
         if p is not None and p.n < 0:
             p.n = self._last_batch  # every row of the last run (0 before the first: the library names the error)
@@ -1059,9 +1113,34 @@ class Engine:
         trimmed = self.edge_trim[0] != 0.0
         normalised = self.loudness_target[0] != 0.0
         r = PackedResult()
-        self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
+        with self._compression_for_call(compression):
+            self._check(self.native.lib.mi355vits_fetch_packed(self._h, None if p is None else ctypes.byref(p), ctypes.byref(r)))
         del pkeep
-        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised)
+        return self._take_packed(r, bool(wav), enc, order if (trimmed or normalised) else None, trimmed, normalised, comp)
+
+    def _call_compression(self, compression, wav):
+        """The compression a packed call will run with (its ``compression=`` or the handle's setting), as a name or None."""
+        if compression is _HANDLE:
+            comp = self.output_compression
+        else:
+            comp = {0: None, 1: "flac"}.get(compression_id(compression), compression)  # (an unknown number: the library refuses it)
+        if comp == "flac" and wav:
+            raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
+        return comp
+
+    @contextlib.contextmanager
+    def _compression_for_call(self, compression):
+        """The handle's compression set to ``compression`` inside the ``with`` and put back behind it (nothing for ``_HANDLE``).
+        Not safe on a handle that several threads share: as with every setter, one thread owns a handle while it calls."""
+        if compression is _HANDLE:
+            yield
+            return
+        before = int(self.native.lib.mi355vits_get_output_compression(self._h))
+        self._check(self.native.lib.mi355vits_set_output_compression(self._h, compression_id(compression)))
+        try:
+            yield
+        finally:
+            self.native.lib.mi355vits_set_output_compression(self._h, before)
 
     # ---- several streams out of one run ---------------------------------------------------------
     @staticmethod
@@ -1151,7 +1230,7 @@ class Engine:
         return out
 
     def _take_packed(self, r: PackedResult, wav: bool, enc: str = "s16le", order=None, trimmed: bool = False,
-                     normalised: bool = False) -> PackedAudio:
+                     normalised: bool = False, compression=None) -> PackedAudio:
         n = int(r.n)
         try:
             offsets = np.ctypeslib.as_array(r.offsets, shape=(n,)).copy()
@@ -1160,13 +1239,17 @@ class Engine:
             dtype = np.dtype(ENCODINGS[enc][1])
             hdr = (WAV_HEADER_BYTES if enc == "s16le" else WAV_HEADER_BYTES_NON_PCM) if wav else 0
             data = dtype.itemsize * int(r.total_samples)
-            if int(r.n_bytes) != hdr + data + (data & 1 if wav else 0):  # a WAV's odd data size is followed by one pad byte
+            total = int(r.total_samples)
+            if compression:
+                if int(r.n_bytes) < FLAC_HEADER_BYTES:
+                    raise RuntimeError("mi355vits_packed_result: a FLAC stream shorter than its header")
+            elif int(r.n_bytes) != hdr + data + (data & 1 if wav else 0):  # a WAV's odd data size is followed by one pad byte
                 raise RuntimeError("mi355vits_packed_result: n_bytes does not match total_samples")
         except BaseException:
             self.native.lib.mi355vits_free_packed(ctypes.byref(r))
             raise
         block = _PackedHolder(self.native, r).view()
-        pcm = block[hdr: hdr + data].view(dtype)
+        pcm = None if compression else block[hdr: hdr + data].view(dtype)
         first = end = None
         if trimmed:
             # the edges the pack was placed with: the library holds them on the host for this ratio, nothing is launched
@@ -1180,7 +1263,7 @@ class Engine:
             rows = np.arange(n) if order is None else np.asarray(order, np.int64).reshape(-1)
             lufs, gain, limited = ld.lufs[rows], ld.gain[rows], ld.limited[rows]
         return PackedAudio(pcm, offsets, lens, peaks, memoryview(block) if wav else None, self._last_rate, enc, first, end, lufs,
-                           gain, limited)
+                           gain, limited, compression or None, memoryview(block) if compression else None, total)
 
     def set_loudness_target(self, lufs, ceiling_db: float = -1.0) -> None:
         """Scale each entry of the packed streams made after this to ``lufs`` LUFS of ITU-R BS.1770-4 integrated loudness
@@ -1298,6 +1381,16 @@ class Engine:
     @property
     def output_encoding(self) -> str:
         return _ENCODING_NAMES[int(self.native.lib.mi355vits_get_output_encoding(self._h))]
+
+    def set_output_compression(self, compression) -> None:
+        """The compression of the packed stream made after this (``mi355vits_set_output_compression``): ``"flac"`` — the S16LE
+        stream as a complete FLAC file, its frames encoded on the GPU, lossless — or ``None`` (the default).  Read by ``run_packed``
+        and by each ``fetch_packed``; ``run_streams`` / ``fetch_streams`` and everything else are unchanged by it."""
+        self._check(self.native.lib.mi355vits_set_output_compression(self._h, compression_id(compression)))
+
+    @property
+    def output_compression(self) -> Optional[str]:
+        return "flac" if int(self.native.lib.mi355vits_get_output_compression(self._h)) == 1 else None
 
     def set_output_rate(self, hz) -> None:
         """The sample rate of every result of the runs that start after this (``mi355vits_set_output_rate``): ``None`` / 0 or

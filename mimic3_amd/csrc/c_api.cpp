@@ -137,6 +137,17 @@ int mi355vits_get_output_encoding(mi355vits_handle h) {
     return h->eng->output_encoding();
 }
 
+int mi355vits_set_output_compression(mi355vits_handle h, int mode) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->set_output_compression(mode); });
+}
+int mi355vits_get_output_compression(mi355vits_handle h) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return h->eng->output_compression();
+}
+
 int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
     if (!h) return MI355VITS_ERR_INVALID;
     return guarded(h, [&] {

@@ -157,10 +157,12 @@ struct PackSettings {
     float loud_target = 0.0f, loud_ceiling = -1.0f;  // mi355vits_set_loudness_target: target 0 = off
     int limit_window = 0;        // mi355vits_set_loudness_limiter: samples at the run's rate, 0 = off; acts on packs with a target only
     int ceil_mode = 0;           // mi355vits_set_loudness_ceiling_mode: MI355VITS_CEILING_*; acts on packs with a target only
+    int compress = 0;            // mi355vits_set_output_compression: MI355VITS_COMPRESS_*; single packs only (a streams call never reads it)
     bool trimmed() const { return trim_ratio != 0.0f; }
     bool normalised() const { return loud_target != 0.0f; }
     bool limiting() const { return normalised() && limit_window > 0; }
     bool true_peak() const { return normalised() && ceil_mode == MI355VITS_CEILING_TRUE_PEAK; }
+    bool flac() const { return compress == MI355VITS_COMPRESS_FLAC; }
 };
 
 // ---------------------------------------------------------------- the engine
@@ -225,6 +227,9 @@ class Engine {
     // the sample encoding of the packed streams (mi355vits_set_output_encoding).  Read when a pack is made.
     void set_output_encoding(int enc);
     int output_encoding() const { return pack_.enc; }
+    // the compression of the packed stream (mi355vits_set_output_compression): FLAC frames of the S16LE stream.  Read when a pack is made.
+    void set_output_compression(int mode);
+    int output_compression() const { return pack_.compress; }
     Profiler& profiler() { return prof_; }
     float last_run_ms();
     long get_tap(const std::string& name, float* out, size_t cap, int64_t dims[4], long row0 = 0, long nrows = -1);
@@ -310,6 +315,16 @@ class Engine {
         d_pack_seg_ = ar.template alloc<int>((size_t)plan.seg_rows() * plan.n);
         d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(plan.set.enc, (long)plan.total));  // in bytes, the last store's overrun included
     }
+    // FLAC packs only, behind layout_pack in the same arena: the one job (the S16LE stream k_pack wrote), a slot and a size word per
+    // frame (+ the total), the frames' offsets, and the frames back to back — what the host copies
+    template <typename A> void layout_flac(A& ar, const PackPlan& plan) {
+        const size_t frames = (size_t)flac_frames((long)plan.total);
+        d_flac_jobs_ = ar.template alloc<FlacJob>(1);
+        d_flac_slots_ = ar.template alloc<uint8_t>(frames * FLAC_SLOT_BYTES);
+        d_flac_sizes_ = ar.template alloc<int>(frames + 1);
+        d_flac_offsets_ = ar.template alloc<long long>(frames);
+        d_flac_out_ = ar.template alloc<uint8_t>(flac_out_capacity((long)frames, (long)plan.total));
+    }
     // ---- everything behind the waveform: engine_results.cpp
     // what every fetch starts with: a result struct to fill, zeroed; a completed run to serve; its device current
     template <typename R> void begin_fetch(R* out, const char* call, bool call_in_null_text = true);
@@ -331,6 +346,8 @@ class Engine {
     void copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out);
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
     void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
+    void launch_flac(const PackPlan& plan);  // the stream at d_pack_ -> frames, sizes, d_flac_out_
+    void copy_out_flac(const PackPlan& plan, mi355vits_packed_result* out);  // sizes, ONE synchronisation more, then exactly the frames
     // k_edges and its copy on the stream for each of the distinct non-zero `ratios` the host does not hold; true: a synchronisation is
     // owed.  keep: what the host holds at other ratios stays (a streams call); else the ratio measured replaces it, as ever
     bool enqueue_edges(const std::vector<float>& ratios, bool keep);
@@ -454,6 +471,14 @@ class Engine {
     std::vector<int> h_pack_seg_;     // fetch_packed's segment table (its own upload)
     std::vector<LimitJob> h_limit_jobs_;  // k_limit's job table (its own upload)
     float* d_curve_ = nullptr;        // the curves of the pack being made (arena_lm_), nullptr when the limiter engages on no entry
+    // FLAC packs only (layout_flac)
+    FlacJob* d_flac_jobs_ = nullptr;
+    uint8_t *d_flac_slots_ = nullptr, *d_flac_out_ = nullptr;
+    int* d_flac_sizes_ = nullptr;
+    long long* d_flac_offsets_ = nullptr;
+    FlacJob h_flac_job_{};            // its own upload: a member outlives the copy
+    std::vector<int> h_flac_sizes_;   // the frame sizes and their total, as copied
+    int flac_prof_rec_ = -1;          // the profiler's record of the pack.flac launches under way: its bytes are known after the sizes
 };
 
 // what the owner_ of any of the five result structs points to goes back: pinned blocks to the pool, heap blocks freed (engine_results.cpp)

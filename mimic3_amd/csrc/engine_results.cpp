@@ -174,11 +174,24 @@ void Engine::set_output_encoding(int enc) {
     pack_.enc = enc;
 }
 
+// The compression of the packed stream made after this (read by run_packed / fetch_packed when they plan their pack; never by a
+// streams call).
+void Engine::set_output_compression(int mode) {
+    if (mode != MI355VITS_COMPRESS_NONE && mode != MI355VITS_COMPRESS_FLAC)
+        throw EngineError(MI355VITS_ERR_INVALID, "output compression " + std::to_string(mode) + " unknown (0 = none, 1 = flac)");
+    pack_.compress = mode;
+}
+
 namespace {
 constexpr int64_t PACK_MAX_SAMPLES = 0x7fffffffLL;                       // total_samples <= 2^31 - 1
 constexpr int64_t RIFF_MAX_SAMPLES = (0xffffffffLL - 36) / 2;            // 36 + 2 * total_samples must fit RIFF's 32-bit size
 EngineError pack_error(int entry, const std::string& what) {
     return EngineError(MI355VITS_ERR_INVALID, (entry >= 0 ? "pack entry " + std::to_string(entry) + ": " : std::string("pack: ")) + what);
+}
+// FLAC's STREAMINFO holds the rate in 20 bits
+void check_flac_rate(int hz) {
+    if (hz > FLAC_MAX_RATE)
+        throw pack_error(-1, "a FLAC stream holds rates up to " + std::to_string(FLAC_MAX_RATE) + " Hz; the run's rate is " + std::to_string(hz) + " Hz");
 }
 void check_pack_size(int entry, int64_t samples, bool wav, int enc) {
     if (samples > PACK_MAX_SAMPLES) throw pack_error(entry, "total_samples exceeds 2^31 - 1");
@@ -237,6 +250,12 @@ void write_wav_header(uint8_t* h, int enc, uint32_t rate, int64_t total, size_t 
 
 // Everything that can be wrong with the pack arguments alone, before anything is sized or launched.
 void Engine::plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const {
+    if (set.flac()) {
+        // FLAC is a layer over the S16LE stream, and a file of its own
+        static const char* const enc_names[] = {"s16le", "ulaw", "alaw", "f32le"};  // by PackEncoding
+        if (set.enc != PACK_ENC_S16) throw pack_error(-1, std::string("FLAC compresses the s16le stream; output encoding is ") + enc_names[set.enc]);
+        if (pack && pack->wav_header != 0) throw pack_error(-1, "a FLAC stream carries its own header (wav_header must be 0)");
+    }
     plan.n = pack ? pack->n : B;
     if (plan.n < 1 || plan.n > B) throw pack_error(-1, "n = " + std::to_string(plan.n) + " out of range (1 .. batch = " + std::to_string(B) + ")");
     plan.wav = pack && pack->wav_header != 0;
@@ -355,11 +374,13 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     PackPlan plan;
     plan_pack(pack, args.batch, pack_, plan);
-    if (!plan.set.trimmed() && !plan.set.normalised()) {
+    if (plan.set.flac()) check_flac_rate(output_rate());  // the rate this run will run at
+    if (!plan.set.trimmed() && !plan.set.normalised() && !plan.set.flac()) {
         synthesize(args, rows, &plan);
         copy_out_packed(plan, out);
         return;
     }
+    // (FLAC: the frames are made from the finished stream, behind it in the arena: the fetch's path, with nothing to measure)
     // Trimming or a loudness target on: the offsets / the scales depend on the audio.  Synthesise without an early pack table (and
     // without the padded int16 pass: a packed call looks at no MI355VITS_WANT_* flag), measure (k_edges and / or k_loud, their
     // copies, ONE synchronisation), then what fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
@@ -379,6 +400,7 @@ void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_resu
     begin_fetch(out, "fetch_packed", false);
     PackPlan plan;
     plan_pack(pack, B_, pack_, plan);
+    if (plan.set.flac()) check_flac_rate(run_hz_);
     pack_last_run(plan, out);
 }
 
@@ -397,21 +419,83 @@ void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
     }
     // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
     // else in an arena of its own
+    const bool flac = plan.set.flac();
     ArenaCount need;
     layout_pack(need, plan);
+    if (flac) layout_flac(need, plan);
     if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
         arena_b_.rewind(layout_b_end_);
         layout_pack(arena_b_, plan);
+        if (flac) layout_flac(arena_b_, plan);
     } else {
         arena_p_.reserve(need.bytes + 4096, stream_);
         arena_p_.reset();
         layout_pack(arena_p_, plan);
+        if (flac) layout_flac(arena_p_, plan);
     }
     h_pack_seg_.assign((size_t)plan.seg_rows() * plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
     fill_pack_seg(plan, h_pack_seg_.data());
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
     launch_pack(plan);
+    if (flac) {
+        launch_flac(plan);
+        copy_out_flac(plan, out);
+        return;
+    }
     copy_out_packed(plan, out);
+}
+
+// The S16LE stream k_pack just wrote as FLAC frames: one job, a workgroup per frame, the sizes scanned, the frames gathered.
+void Engine::launch_flac(const PackPlan& plan) {
+    const long frames = flac_frames((long)plan.total);
+    flac_prof_rec_ = -1;
+    if (frames == 0) return;
+    h_flac_job_ = FlacJob{reinterpret_cast<const int16_t*>(d_pack_), (long)plan.total, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(d_flac_jobs_, &h_flac_job_, sizeof(FlacJob), hipMemcpyHostToDevice, stream_));
+    ProfScope ps(prof_, "pack.flac", 0, 2.0 * (double)plan.total);  // + the frames' bytes once the host knows them (copy_out_flac)
+    flac_prof_rec_ = ps.rec;
+    launch_flac_frames(d_flac_jobs_, 1, frames, run_hz_, d_flac_slots_, d_flac_sizes_, stream_);
+    launch_flac_gather(d_flac_slots_, d_flac_sizes_, d_flac_offsets_, frames, d_flac_out_, stream_);
+}
+
+// The compressed size depends on the audio: the frame sizes and their total come first (4 * (frames + 1) bytes, ONE synchronisation
+// more than an uncompressed pack), then exactly the frames land behind the 42 header bytes the host writes.
+void Engine::copy_out_flac(const PackPlan& plan, mi355vits_packed_result* out) {
+    const int n = plan.n;
+    const long frames = flac_frames((long)plan.total);
+    Owner* own = new_owner(out);
+    out->n = n;
+    out->total_samples = plan.total;
+    out->offsets = own->alloc<int64_t>(n);
+    out->lengths = own->alloc<int64_t>(n);
+    out->peaks = own->alloc<float>(n);
+    std::vector<unsigned> pk(B_);
+    h_flac_sizes_.assign((size_t)frames + 1, 0);
+    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
+    if (frames > 0) HIP_CHECK(hipMemcpyAsync(h_flac_sizes_.data(), d_flac_sizes_, 4 * ((size_t)frames + 1), hipMemcpyDeviceToHost, stream_));
+    for (int i = 0; i < n; ++i) {
+        out->offsets[i] = plan.offsets[i];
+        out->lengths[i] = plan.lengths[i];
+    }
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int i = 0; i < n; ++i) memcpy(&out->peaks[i], &pk[plan.order[i]], 4);
+    size_t data = 0;
+    for (long f = 0; f < frames; ++f) {
+        const int sz = h_flac_sizes_[(size_t)f];
+        if (sz < 11 || sz > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sz) + " bytes");
+        data += (size_t)sz;
+    }
+    if ((unsigned)h_flac_sizes_[(size_t)frames] != (unsigned)data) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's total differs from the sum of the frame sizes");
+    if (flac_prof_rec_ >= 0 && (size_t)flac_prof_rec_ < prof_.recs.size()) prof_.recs[(size_t)flac_prof_rec_].bytes += (double)data;
+    const size_t lead = 6;  // the 42-byte header starts 6 bytes into the block: the frames behind it keep the block's alignment
+    out->bytes = static_cast<uint8_t*>(own->take_pinned(lead + FLAC_HEADER_BYTES + data + 16)) + lead;
+    out->n_bytes = FLAC_HEADER_BYTES + data;
+    out->pcm = reinterpret_cast<int16_t*>(out->bytes + FLAC_HEADER_BYTES);  // the first frame
+    flac_stream_header(out->bytes, run_hz_, plan.total, h_flac_sizes_.data(), frames);
+    if (data) {
+        HIP_CHECK(hipMemcpyAsync(out->bytes + FLAC_HEADER_BYTES, d_flac_out_, data, hipMemcpyDeviceToHost, stream_));  // exactly the frames
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    }
 }
 
 // ---------------------------------------------------------------- several streams of one run (mi355vits_run_streams / mi355vits_fetch_streams)

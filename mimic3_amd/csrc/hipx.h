@@ -24,6 +24,7 @@ typedef hipemu_f32x4 f32x4;
 #define WAVE_UNIFORM(x) (x)
 #define FAST_EXPF(x) expf(x)
 static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }  // the device builtin: leading zeros, 32 for 0
+static inline unsigned atomicOr(unsigned* p, unsigned v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }  // ds_or_b32 on LDS words
 #define FAST_RCPF(x) (1.0f / (x))
 #define SCHED_FENCE() ((void)0)
 #define MIN_WAVES_PER_SIMD(n)

@@ -276,6 +276,31 @@ void launch_pack_streams(const float* audio, long audio_bs, const unsigned* peak
 // G.711 of n int16 samples on the device with the stream kernels' own encoders (law: PACK_ENC_ULAW / PACK_ENC_ALAW): the lab hook
 void launch_g711_encode(int law, const int16_t* in, long n, uint8_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------- the S16LE stream as FLAC frames (kernels_flac.cpp)
+// A job is one int16 stream: frame f of it holds samples [4096 f, min(4096 (f + 1), n)) and carries the number first_frame + f; its
+// frames take the slots slot0 .. of the slot and size tables, the jobs in ascending slot0.  k_flac_frames writes frame w to
+// slots + w * FLAC_SLOT_BYTES (16-byte aligned) and its byte count to sizes[w]; launch_flac_gather scans the sizes (offsets[w] = the
+// bytes in front of frame w, sizes[n_frames] = the low 32 bits of the total) and puts the frames back to back at out.  A frame is
+// at most 16 + 2 * block bytes, so out holds flac_out_capacity bytes.  Integer arithmetic only; the bytes depend on nothing but
+// (samples, rate, first_frame).
+constexpr int FLAC_BLOCK = 4096;
+constexpr int FLAC_SLOT_BYTES = 8208;
+constexpr int FLAC_HEADER_BYTES = 42;      // "fLaC" + the STREAMINFO block
+constexpr int FLAC_MAX_RATE = 0xfffff;     // STREAMINFO's 20 bits
+constexpr long FLAC_MAX_FRAME_NUMBER = 0x1fffff;  // four bytes of the header's extended UTF-8
+struct FlacJob {
+    const int16_t* src;
+    long n;
+    int first_frame;
+    int slot0;
+};
+inline long flac_frames(long n) { return (n + FLAC_BLOCK - 1) / FLAC_BLOCK; }
+inline size_t flac_out_capacity(long n_frames, long total) { return (16 * (size_t)n_frames + 2 * (size_t)total + 15) & ~size_t(15); }
+void launch_flac_frames(const FlacJob* jobs, int n_jobs, long n_frames, int rate, uint8_t* slots, int* sizes, hipStream_t s);
+void launch_flac_gather(const uint8_t* slots, int* sizes, long long* offsets, long n_frames, uint8_t* out, hipStream_t s);
+// the 42 bytes in front of the frames, from the frame sizes the host holds (min / max frame size); the MD5 field stays zero
+void flac_stream_header(uint8_t* h, int rate, int64_t total, const int* sizes, long n_frames);
+
 // ---------------------------------------------------------------- output at a requested sample rate (kernels_resample.cpp)
 // y[k] = sum_j h[k M - j L + half] x[j], x zero outside [0, n): what scipy.signal.resample_poly(x, L, M) returns with its default
 // filter (Kaiser beta 5, half = 10 max(L, M) taps each side, cut-off 1 / max(L, M), gain L); n_out = ceil(n L / M).

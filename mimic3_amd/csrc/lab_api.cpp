@@ -200,6 +200,42 @@ int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out) 
     });
 }
 
+int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_frame, uint8_t* out, size_t cap, size_t* n_bytes,
+                       int32_t* frame_sizes) {
+    return guarded(nullptr, [&] {
+        if (n_bytes) *n_bytes = 0;
+        if ((!pcm && n > 0) || !out || !n_bytes || n < 0 || n > 0x7fffffffL) throw EngineError(MI355VITS_ERR_INVALID, "null argument or n out of range");
+        if (rate < 1 || rate > FLAC_MAX_RATE) throw EngineError(MI355VITS_ERR_INVALID, "rate must be in [1, 1048575]");
+        const long frames = flac_frames(n);
+        if (first_frame < 0 || (long)first_frame + frames > FLAC_MAX_FRAME_NUMBER + 1) throw EngineError(MI355VITS_ERR_INVALID, "frame numbers must stay below 2^21");
+        const size_t lead = n > 0 ? (reinterpret_cast<uintptr_t>(pcm) & 15) : 0;  // the host pointer's place behind a 16-byte boundary, kept
+        DevBuf din(lead + (size_t)n * 2 + 16), djob(sizeof(FlacJob)), dslots((size_t)frames * FLAC_SLOT_BYTES), dsizes(((size_t)frames + 1) * 4),
+            doff((size_t)frames * 8), dout(flac_out_capacity(frames, n));
+        int16_t* src = reinterpret_cast<int16_t*>(din.as<uint8_t>() + lead);
+        if (n > 0) HIP_CHECK(hipMemcpy(src, pcm, (size_t)n * 2, hipMemcpyHostToDevice));
+        const FlacJob job = {src, n, first_frame, 0};
+        HIP_CHECK(hipMemcpy(djob.p, &job, sizeof(job), hipMemcpyHostToDevice));
+        launch_flac_frames(djob.as<FlacJob>(), 1, frames, rate, dslots.as<uint8_t>(), dsizes.as<int>(), nullptr);
+        launch_flac_gather(dslots.as<uint8_t>(), dsizes.as<int>(), doff.as<long long>(), frames, dout.as<uint8_t>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        std::vector<int> sizes((size_t)frames + 1, 0);
+        if (frames > 0) HIP_CHECK(hipMemcpy(sizes.data(), dsizes.p, sizes.size() * 4, hipMemcpyDeviceToHost));
+        size_t data = 0;
+        for (long f = 0; f < frames; ++f) {
+            if (sizes[f] < 11 || sizes[f] > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sizes[f]) + " bytes");
+            data += (size_t)sizes[f];
+        }
+        if ((unsigned)sizes[frames] != (unsigned)data) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's total differs from the sum of the frame sizes");
+        *n_bytes = FLAC_HEADER_BYTES + data;
+        if (cap < *n_bytes) throw EngineError(MI355VITS_ERR_INVALID, "flac: the file has " + std::to_string(*n_bytes) + " bytes, out holds " + std::to_string(cap));
+        flac_stream_header(out, rate, n, sizes.data(), frames);
+        if (data) HIP_CHECK(hipMemcpy(out + FLAC_HEADER_BYTES, dout.p, data, hipMemcpyDeviceToHost));
+        if (frame_sizes)
+            for (long f = 0; f < frames; ++f) frame_sizes[f] = sizes[f];
+    });
+}
+
 int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, const float* peaks, int B, float ratio, int32_t* s_first,
                         int32_t* s_last) {
     return guarded(nullptr, [&] {

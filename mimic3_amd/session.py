@@ -588,6 +588,18 @@ def _encoding_name(encoding) -> str:
     return encoding.lower()
 
 
+_SESSION = object()  # compression=: "whatever the session's output_compression is"
+
+
+def _compression_name(compression) -> Optional[str]:
+    """A packed stream's compression as ``"flac"`` or ``None`` (also for ``"none"``); ``ValueError`` for anything else."""
+    if compression is None:
+        return None
+    if not isinstance(compression, str) or compression.lower() not in ("flac", "none"):
+        raise ValueError(f"unknown output compression {compression!r} ('flac' or None)")
+    return "flac" if compression.lower() == "flac" else None
+
+
 def _trim_ratio(db) -> float:
     """An edge-trim threshold in dB below a row's peak as the engine's ratio: ``float(np.float32(10 ** (db / 20)))``; ``None`` =
     off (0.0).  ``db`` must be finite and <= 0, else ``ValueError``."""
@@ -638,6 +650,8 @@ class InferenceSession:
         self.output_sample_rate: Optional[int] = int(rate) if rate else None
         # the sample encoding of the packed streams (Engine.set_output_encoding); a call's ``encoding=`` goes before it
         self.output_encoding: str = _encoding_name(kwargs.pop("output_encoding", None) or "s16le")
+        # the compression of the packed stream (Engine.set_output_compression): "flac" or None; a call's ``compression=`` goes before it
+        self.output_compression: Optional[str] = _compression_name(kwargs.pop("output_compression", None))
         # edge trimming of the packed streams (Engine.set_edge_trim): dB below each row's peak, None = off, and the milliseconds
         # kept around the loud part; a call's ``trim_db=`` / ``trim_keep_ms=`` go before them
         self.edge_trim_db: Optional[float] = kwargs.pop("edge_trim_db", None)
@@ -770,7 +784,7 @@ class InferenceSession:
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
-                   limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None) -> "_native.PackedAudio":
+                   limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -800,8 +814,17 @@ class InferenceSession:
         the uncapped gain and ``.limited`` marks the entries the limiter acted on.
         ``true_peak`` (else the session's ``loudness_true_peak``): with a loudness target, ``ceiling_db`` bounds the entry's 4x
         oversampled peak (dBTP) instead of its largest sample, in the gain and in what the limiter looks at
-        (``Engine.set_loudness_ceiling_mode``)."""
+        (``Engine.set_loudness_ceiling_mode``).
+        ``compression`` (``"flac"`` / ``None``; else the session's ``output_compression``): the int16 stream — with everything above
+        applied — as a complete FLAC file, its frames encoded on the GPU, lossless (``Engine.set_output_compression``):
+        ``PackedAudio.flac`` is the file, ``.data`` / ``.rows`` / ``.wav`` are ``None``, ``.offsets`` / ``.lengths`` / ``.peaks`` /
+        ``.total_samples`` are those of the uncompressed call.  ``wav=True`` with it raises ``ValueError``; any encoding but
+        "s16le" is refused by the library."""
+        comp = self.output_compression if compression is _SESSION else _compression_name(compression)
+        if comp and wav:
+            raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
         kw = self._pcm_kw(volume, utterance_keys)
+        kw["_compression"] = comp
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
         kw["encoding"] = _encoding_name(encoding) if encoding is not None else self.output_encoding
@@ -844,8 +867,9 @@ class InferenceSession:
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None, loudness: Optional[float] = None,
                    ceiling_db: Optional[float] = None, limiter_ms: Optional[float] = None,
-                   true_peak: Optional[bool] = None) -> "_native.PackedAudio":
-        """``run_packed`` (same keywords, except ``alignment``; same ``PackedAudio``; the same bytes when ``utterance_keys`` are
+                   true_peak: Optional[bool] = None, compression=None) -> "_native.PackedAudio":
+        """``run_packed`` (same keywords, except ``alignment`` and ``compression``: a stream is never compressed, whatever the
+        session's ``output_compression``, and ``compression="flac"`` raises ``ValueError`` — FLAC is not offered in streams yet; same ``PackedAudio``; the same bytes when ``utterance_keys`` are
         given or the noise scales are zero — a row without a key of its own takes its Philox index from its place in the shared
         call, as in any micro-batched call, so its noise is not that of the request run alone) THROUGH the micro-batcher: the
         feed's rows — one or a few sentences of one client — share an engine call with the requests of other callers that arrive
@@ -856,13 +880,15 @@ class InferenceSession:
         ``true_peak`` never share a call).  The result is a view of the
         batch's shared pinned block: nothing is copied per request.  A feed of more than ``micro_batch_max`` rows, or a session
         without a micro-batcher, takes ``run_packed`` directly."""
+        if _compression_name(compression):
+            raise ValueError("run_stream: FLAC is not offered in streams yet (use run_packed(..., compression='flac'))")
         ids, lengths, sid = self._feed(input_feed)
         B = int(ids.shape[0])
         if self._batcher is None or B > self._batcher._max or lengths.shape[0] != B:
             return self.run_packed(input_feed, order=order, lead_ms=lead_ms, lead_samples=lead_samples, tail_ms=tail_ms, wav=wav,
                                    volume=volume, utterance_keys=utterance_keys, sample_rate=sample_rate, encoding=encoding,
                                    trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db,
-                                   limiter_ms=limiter_ms, true_peak=true_peak)
+                                   limiter_ms=limiter_ms, true_peak=true_peak, compression=None)
         kw = self._pcm_kw(volume, utterance_keys)
         for name in ("pcm_volume", "utterance_keys"):
             if name in kw and np.ndim(kw[name]) > 0 and len(kw[name]) != B:
@@ -955,7 +981,7 @@ class InferenceSession:
         return base
 
     def _engine_run(self, ids, lengths, scales, sid, utterance_keys=None, _packed: bool = False, sample_rate=None, encoding=None,
-                    _alignment=None, _trim=None, _loudness=None, _streams=None, _limiter=0, _ceiling=False, **kw):
+                    _alignment=None, _trim=None, _loudness=None, _streams=None, _limiter=0, _ceiling=False, _compression=None, **kw):
         """``_alignment`` (None, or whether levels are wanted): fetch the run's alignment on the same lane before it is released
         — a fetch after the release would race with other threads' runs — and return (result, alignment)."""
         if self._closed:
@@ -974,6 +1000,7 @@ class InferenceSession:
                 eng.set_output_encoding(encoding or self.output_encoding)
                 eng.set_edge_trim(*(_trim or (0.0, 0)))  # likewise; set on every call: back to off for a call that does not ask
                 eng.set_loudness_target(*(_loudness or (0.0, -1.0)))  # likewise
+                eng.set_output_compression(_compression)  # likewise
             if _packed or _streams is not None:  # the limiter window: set on every packed call, back to off for one that does not ask
                 eng.set_loudness_limiter(_limiter or 0)
                 eng.set_loudness_ceiling_mode(bool(_ceiling))  # the ceiling mode likewise: back to the sample peak for a call that does not ask
