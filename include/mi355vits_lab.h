@@ -50,7 +50,11 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
 int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern);
 /* Kernel unit-test hook: relative-position attention on host buffers.  qkv [B, 3H, T], emb_rel_k / emb_rel_v
  * [2W+1, H/n_heads], len [B] (0 <= len <= T), out [B, H, T].  impl: 0 = VALU kernel (T <= rel_attention_valu_cap), 1 = the
- * f32-MFMA kernel (T <= 512), 2 = the streamed kernel (any T).  Query rows at or past len[b]: what the kernel writes. */
+ * f32-MFMA kernel (T <= 512, even head width, W <= 15), 2 = the streamed kernel (any T; even head width <= 128, W <= 15).  A shape
+ * the chosen kernel does not serve is MI355VITS_ERR_INVALID before any launch.  Every element of out is written.  Query rows at or
+ * past len[b]: impl 0 and 1 write what the reference's -1e4 fill gives there — every logit equal, so the plain mean of v over all T
+ * columns of the batch, padding included (plus the band's E_v rows over T): finite for finite input, dependent on T and on what lies
+ * past len[b], never read by a valid frame; impl 2 writes exact zeros.  Columns below len[b] depend on neither T nor the padding. */
 int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int n_heads, int W, const float* qkv,
                                  const float* emb_rel_k, const float* emb_rel_v, const int32_t* len, float* out);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of

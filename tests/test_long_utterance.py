@@ -10,52 +10,8 @@ from mimic3_amd import weights as W
 from mimic3_amd.config import VitsConfig, tx_class
 from mimic3_amd.session import InferenceSession, SessionOptions
 
+from tests.attention_ref import attention_case, rel_attention_fp64
 from tests.util import check_parity
-
-
-def rel_attention_fp64(qkv, ek, ev, lengths, n_heads):
-    """SURVEY A.4 restated in float64: s = (q / sqrt d) . k + the band term via E_k, keys past the row's length masked,
-    softmax, o = P V + the band term via E_v.  Query rows at or past the length are left at zero."""
-    qkv = np.asarray(qkv, np.float64)
-    ek = np.asarray(ek, np.float64)
-    ev = np.asarray(ev, np.float64)
-    B, H3, T = qkv.shape
-    H = H3 // 3
-    d = H // n_heads
-    Wn = (ek.shape[0] - 1) // 2
-    out = np.zeros((B, H, T))
-    for b in range(B):
-        L = int(lengths[b])
-        if L == 0:
-            continue
-        idx = np.arange(L)
-        rel = idx[None, :] - idx[:, None]
-        inwin = np.abs(rel) <= Wn
-        relc = np.clip(rel + Wn, 0, 2 * Wn)
-        for h in range(n_heads):
-            c0 = h * d
-            q = qkv[b, c0:c0 + d, :L].T / np.sqrt(d)
-            k = qkv[b, H + c0:H + c0 + d, :L].T
-            v = qkv[b, 2 * H + c0:2 * H + c0 + d, :L].T
-            rl = q @ ek.T
-            s = q @ k.T + np.where(inwin, np.take_along_axis(rl, relc, axis=1), 0.0)
-            p = np.exp(s - s.max(axis=1, keepdims=True))
-            p /= p.sum(axis=1, keepdims=True)
-            pw = np.where(inwin, p, 0.0)
-            relw = np.zeros((L, 2 * Wn + 1))
-            for r in range(2 * Wn + 1):
-                np.add.at(relw[:, r], idx, np.where(relc == r, pw, 0.0).sum(axis=1))
-            out[b, c0:c0 + d, :L] = (p @ v + relw @ ev).T
-    return out
-
-
-def attention_case(T, d, lengths, n_heads=2, Wn=4, seed=0):
-    rng = np.random.default_rng(seed + T + 7 * d)
-    H = d * n_heads
-    qkv = rng.standard_normal((len(lengths), 3 * H, T)).astype(np.float32)
-    ek = (0.5 * rng.standard_normal((2 * Wn + 1, d))).astype(np.float32)
-    ev = (0.5 * rng.standard_normal((2 * Wn + 1, d))).astype(np.float32)
-    return qkv, ek, ev, np.asarray(lengths, np.int32)
 
 
 def check_stream_vs_fp64(lib, T, d, lengths, n_heads=2):
