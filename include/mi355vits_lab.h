@@ -57,6 +57,86 @@ int mi355vits_test_fill_workspace(mi355vits_handle h, uint32_t pattern);
  * past len[b], never read by a valid frame; impl 2 writes exact zeros.  Columns below len[b] depend on neither T nor the padding. */
 int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int n_heads, int W, const float* qkv,
                                  const float* emb_rel_k, const float* emb_rel_v, const int32_t* len, float* out);
+/* Kernel unit-test hook: ONE WaveNet layer of the coupling flow (csrc/kernels_wn.cpp) on host buffers:
+ *   u = tanh(in(h)[:H] + cond[:H]) * sigmoid(in(h)[H:] + cond[H:]),  rs = res_skip(u),
+ *   Crs = 2H: h' = (h + rs[:H]) * mask, skip (+)= rs[H:];   Crs = H (a stack's last layer): skip (+)= rs, h' is not written.
+ * in = a "same" conv with K taps (odd) at `dilation`, res_skip a 1x1 conv; skip_init != 0: skip = instead of skip +=.  The hook packs
+ * the weights with the library's own pack functions, as the engine does for the chosen path.
+ * impl: 0 = the two launches the engine falls back to (gate conv, then res/skip conv in place: the f32-MFMA conv kernel, the
+ *           generic one for odd H, decided per conv as the engine does), math MI355VITS_MATH_F32;
+ *       1 = launch_wn_layer (k_wn_layer<1> at H = 32; k_wn_layer<6>, k_wn_layer_h192<4 | 12> at H = 192, chosen by the grid),
+ *           math MI355VITS_MATH_F32;
+ *       2 = launch_wn_layer_b3 (k_wn_layer_b3: H = 192, (K - 1) * dilation <= 24; 32-, 96- or 128-column tiles chosen by the grid,
+ *           the 128-column form only for (K - 1) * dilation <= 8), math MI355VITS_MATH_BF16X3.
+ * A shape or math mode the chosen path does not serve is MI355VITS_ERR_INVALID before any launch.  Which form of an impl runs is
+ * the launcher's business (its grid rule; in the lab build and the CPU model also MI355VITS_WN_B3_NT, MI355VITS_WN_EPI,
+ * MI355VITS_WN_SIX_WAVES, read at every launch); all forms of one impl give the same bits.
+ * At and past len[b] (0 <= len[b] <= T), per row:
+ *   h_in    impl 1 and 2 never use it there: every staged column is masked at len[b] (impl 2 does load h_in there for the residual of
+ *           the last tile it computes, and discards it by select: any finite or non-finite bits may lie there).  impl 0 READS it, as the
+ *           engine's two-launch path does (its h is zero there because every layer masks h'): the caller keeps it zero.
+ *   h_out   (Crs = 2H) impl 0 and 1 write zeros at every column len[b] <= t < T.  impl 2 never computes a tile that starts at or
+ *           past len[b]: zeros from len[b] to the end of the tile that holds column len[b] - 1 (tile = mi355vits_lab_wn_plan's
+ *           width), every later column keeps what h_out held; a row with len[b] = 0 is not touched at all.  Crs = H: no path writes
+ *           h_out; for impl 1 and 2 the hook still reads the device's buffer back, so a stray write shows (impl 0 works in place on
+ *           its copy of h_in and returns the caller's h_out as it came).
+ *   skip    is NOT masked (its consumer masks): impl 0 and 1 apply the update at every column t < T, with u computed from a zero input
+ *           there; impl 2 does so inside the last computed tile, and every later column keeps what skip held.
+ * Columns below len[b] depend on nothing at or past len[b] and on no other row. */
+typedef struct mi355vits_wn_test {
+    int32_t impl, B, H, T, K, dilation, Crs, skip_init, math;
+    const float* h_in;   /* [B,H,T] */
+    const float* w_in;   /* [2H,H,K]: tanh rows, then sigmoid rows */
+    const float* b_in;   /* [2H] */
+    const float* w_rs;   /* [Crs,H,1] */
+    const float* b_rs;   /* [Crs] */
+    const float* cond;   /* [B,2H] or NULL */
+    const int32_t* len;  /* [B] */
+    float* h_out;        /* [B,H,T]: its prior contents go to the device first */
+    float* skip;         /* [B,H,T], in / out */
+} mi355vits_wn_test;
+int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t);
+/* What the launchers would pick for a [B, 192, T] layer with (K, dilation) on the current device: *b3_tile = the columns of a
+ * k_wn_layer_b3 workgroup (32, 96 or 128), *f32_geometry = launch_wn_layer's wave geometry (0: 4 waves x 3 tiles, 1: 6 x 2, 2: 12 x 1).
+ * The launchers' own functions (with the lab switches where they are read).  No kernel runs. */
+int mi355vits_lab_wn_plan(int B, int T, int K, int dilation, int32_t* b3_tile, int32_t* f32_geometry);
+/* Kernel unit-test hook: ONE multi-receptive-field stage of the decoder (csrc/kernels_mrf.cpp, kernels_mrfp.cpp,
+ * kernels_mrfs.cpp) on host buffers:  y = s * sum_j RB_j(x), s = out_scale when out_scale > 0, else 1 / nrb;
+ *   RB_j: x1 = x + conv_{k_j, d1_j}(lrelu_0.1(x)) + b;  x2 = x1 + conv_{k_j, d2_j}(lrelu_0.1(x1)) + b   ("same" convs),
+ * every row evaluated alone on its own [:, :len[b]] with zero padding (x1 counts as zero at and past len[b] too).  The hook packs
+ * w[j][q] [C, C, k_j] with the library's own pack functions, as the engine does for the chosen kernel, and passes len_host.
+ * impl: 0 = launch_mrf_fused (k_mrf_fused: C in {32, 64, 128}, nrb 1 .. 4, what fits LDS), math MI355VITS_MATH_F32 or _BF16X3;
+ *       1 = launch_mrf_p (k_mrf_p<32 | 64>: C in {32, 64}, taps (3, 5, 7); on the device dilations (1,2), (2,6), (3,12) only),
+ *           math MI355VITS_MATH_BF16X3, out_scale as above;
+ *       2 = launch_mrf_s (k_mrf_s<64>: as impl 1 with C = 64) with segments of `seg` columns: any positive multiple of the step
+ *           (mi355vits_lab_mrf_plan's width) is served — a segment is an independent work item with its own pipeline fill, so
+ *           segments shorter than mrf_s_segment would ever return are right, only slow; anything else is refused.
+ * A shape, math mode or seg the chosen kernel does not serve is MI355VITS_ERR_INVALID before any launch.  impl 1 and 2 give the same bits.
+ * At and past len[b] (0 <= len[b] <= T), per row:
+ *   x       no kernel uses it there: every load is clamped to column len[b] - 1 and masked by select.
+ *   y       impl 0 writes every column t < T (past len[b]: what the rule gives for a zero input, finite).  impl 1 never computes a
+ *           work item that starts at or past len[b]: it writes up to the end of the item that holds column len[b] - 1 (finite values),
+ *           every later column keeps what y held.  impl 2 likewise with the step inside a segment: within the segment that holds
+ *           column len[b] - 1 it writes up to the end of that column's step (and never past the segment), later columns keep
+ *           what y held.  A row with len[b] = 0 is not touched by impl 1 and 2.
+ * Columns below len[b] depend on nothing at or past len[b] and on no other row. */
+typedef struct mi355vits_mrf_test {
+    int32_t impl, B, C, T, nrb, math, seg;
+    int32_t k[4], d1[4], d2[4];
+    const float* x;           /* [B,C,T] */
+    const float* w[4][2];     /* [C,C,k[j]] */
+    const float* bias[4][2];  /* [C] */
+    const int32_t* len;       /* [B] */
+    float out_scale;
+    float* y;                 /* [B,C,T]: its prior contents go to the device first */
+} mi355vits_mrf_test;
+int mi355vits_test_mrf_stage(int device, const mi355vits_mrf_test* t);
+/* How kernel `impl` (as above) cuts a row of a C-channel stage: *width = the columns of a work item (T_B of k_mrf_fused / k_mrf_p, the
+ * step of k_mrf_s), *halo = max_j (k_j - 1) / 2 * (d1_j + d2_j), the columns an output looks to either side, *x_ring / *x1_ring = the
+ * sweep's LDS ring lengths in columns (0 for impl 0 and 1).  MI355VITS_ERR_INVALID where the kernel does not serve the stage.
+ * Host arithmetic only: no kernel runs. */
+int mi355vits_lab_mrf_plan(int impl, int C, int nrb, const int32_t* k, const int32_t* d1, const int32_t* d2, int32_t* width,
+                           int32_t* halo, int32_t* x_ring, int32_t* x1_ring);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
  * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
  * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros

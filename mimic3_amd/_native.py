@@ -53,6 +53,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac",
+    "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
 )
 
 
@@ -60,6 +61,25 @@ class NativeError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"mi355vits error {code}: {message}")
         self.code = code
+
+
+class WnTest(ctypes.Structure):
+    """struct mi355vits_wn_test of include/mi355vits_lab.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("impl", "B", "H", "T", "K", "dilation", "Crs", "skip_init", "math")] + [
+        (n, ctypes.POINTER(ctypes.c_float)) for n in ("h_in", "w_in", "b_in", "w_rs", "b_rs", "cond")] + [
+        ("len", ctypes.POINTER(ctypes.c_int32)), ("h_out", ctypes.POINTER(ctypes.c_float)), ("skip", ctypes.POINTER(ctypes.c_float))]
+
+
+class MrfTest(ctypes.Structure):
+    """struct mi355vits_mrf_test of include/mi355vits_lab.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("impl", "B", "C", "T", "nrb", "math", "seg")] + [
+        (n, ctypes.c_int32 * 4) for n in ("k", "d1", "d2")] + [
+        ("x", ctypes.POINTER(ctypes.c_float)), ("w", (ctypes.POINTER(ctypes.c_float) * 2) * 4),
+        ("bias", (ctypes.POINTER(ctypes.c_float) * 2) * 4), ("len", ctypes.POINTER(ctypes.c_int32)),
+        ("out_scale", ctypes.c_float), ("y", ctypes.POINTER(ctypes.c_float))]
+
+
+MATH_F32, MATH_BF16X3 = 0, 1  # csrc/kernels.h MathMode, MI355VITS_MATH_*
 
 
 class RunArgs(ctypes.Structure):
@@ -486,6 +506,10 @@ class NativeLibrary:
                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i32p, i32p, i32p, f32p, f32p]
             L.mi355vits_test_rel_attention.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_float)] * 3 + [
                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
+            L.mi355vits_test_wn_layer.argtypes = [ctypes.c_int, ctypes.POINTER(WnTest)]
+            L.mi355vits_lab_wn_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p]
+            L.mi355vits_test_mrf_stage.argtypes = [ctypes.c_int, ctypes.POINTER(MrfTest)]
+            L.mi355vits_lab_mrf_plan.argtypes = [ctypes.c_int] * 3 + [i32p] * 7
 
     def _need_hooks(self):
         if not self.has_hooks:
@@ -711,6 +735,83 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return out
+
+    def test_wn_layer(self, h, skip, w_in, b_in, w_rs, b_rs, lengths, dilation=1, cond=None, skip_init=False, impl=1, math=None,
+                      h_out_prior=None, device=0):
+        """One WaveNet layer of the coupling flow through one path (include/mi355vits_lab.h: mi355vits_test_wn_layer): impl 0 = the
+        two-launch path, 1 = launch_wn_layer (MATH_F32), 2 = launch_wn_layer_b3 (MATH_BF16X3).  h, skip [B, H, T], w_in [2H, H, K],
+        w_rs [Crs, H, 1], cond [B, 2H] or None, lengths [B]; h_out_prior = what the output buffer of h' holds before the launch
+        (zeros).  Returns (h', skip'); with Crs = H, h' is h_out_prior unchanged."""
+        self._need_hooks()
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        h, w_in, b_in, w_rs, b_rs = f(h), f(w_in), f(b_in), f(w_rs), f(b_rs)
+        skip = f(skip).copy()
+        B, H, T = h.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        h_out = np.zeros_like(h) if h_out_prior is None else f(h_out_prior).copy()
+        assert skip.shape == h.shape == h_out.shape and w_in.shape[:2] == (2 * H, H) and w_rs.shape[1:] == (H, 1) and ln.shape == (B,)
+        assert b_in.shape == (2 * H,) and b_rs.shape == (w_rs.shape[0],)
+        c = None if cond is None else f(cond)
+        assert c is None or c.shape == (B, 2 * H)
+        t = WnTest()
+        t.impl, t.B, t.H, t.T, t.K, t.dilation, t.Crs, t.skip_init = impl, B, H, T, w_in.shape[2], int(dilation), w_rs.shape[0], int(bool(skip_init))
+        t.math = (MATH_BF16X3 if impl == 2 else MATH_F32) if math is None else int(math)
+        t.h_in, t.w_in, t.b_in, t.w_rs, t.b_rs, t.cond = _fptr(h), _fptr(w_in), _fptr(b_in), _fptr(w_rs), _fptr(b_rs), _fptr(c)
+        t.len, t.h_out, t.skip = ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(h_out), _fptr(skip)
+        rc = self.lib.mi355vits_test_wn_layer(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return h_out, skip
+
+    def lab_wn_plan(self, B, T, K=5, dilation=1):
+        """What the WaveNet launchers pick for a [B, 192, T] layer on the current device: (the columns of a k_wn_layer_b3 tile — 32, 96
+        or 128 —, launch_wn_layer's geometry 0 / 1 / 2).  No kernel runs."""
+        self._need_hooks()
+        tile, geom = ctypes.c_int32(), ctypes.c_int32()
+        rc = self.lib.mi355vits_lab_wn_plan(int(B), int(T), int(K), int(dilation), ctypes.byref(tile), ctypes.byref(geom))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return int(tile.value), int(geom.value)
+
+    def test_mrf_stage(self, x, ks, d1, d2, weights, biases, lengths, impl=0, math=None, out_scale=0.0, seg=0, y_prior=None, device=0):
+        """One multi-receptive-field stage through one kernel (include/mi355vits_lab.h: mi355vits_test_mrf_stage): impl 0 = k_mrf_fused
+        (MATH_F32 unless math says MATH_BF16X3), 1 = k_mrf_p, 2 = k_mrf_s with segments of ``seg`` columns.  x [B, C, T];
+        weights[j][q] [C, C, ks[j]], biases[j][q] [C]; lengths [B]; y_prior = what the output buffer holds before the launch (zeros)."""
+        self._need_hooks()
+        x = np.ascontiguousarray(x, np.float32)
+        B, C, T = x.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        y = np.zeros_like(x) if y_prior is None else np.ascontiguousarray(y_prior, np.float32).copy()
+        nrb = len(ks)
+        assert y.shape == x.shape and ln.shape == (B,) and 1 <= nrb <= 4 and len(d1) == len(d2) == len(weights) == len(biases) == nrb
+        t = MrfTest()
+        t.impl, t.B, t.C, t.T, t.nrb, t.seg = impl, B, C, T, nrb, int(seg)
+        t.math = (MATH_F32 if impl == 0 else MATH_BF16X3) if math is None else int(math)
+        keep = []
+        for j in range(nrb):
+            t.k[j], t.d1[j], t.d2[j] = int(ks[j]), int(d1[j]), int(d2[j])
+            for q in range(2):
+                w = np.ascontiguousarray(weights[j][q], np.float32)
+                bq = np.ascontiguousarray(biases[j][q], np.float32)
+                assert w.shape == (C, C, ks[j]) and bq.shape == (C,)
+                keep += [w, bq]
+                t.w[j][q], t.bias[j][q] = _fptr(w), _fptr(bq)
+        t.x, t.len, t.out_scale, t.y = _fptr(x), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), float(out_scale), _fptr(y)
+        rc = self.lib.mi355vits_test_mrf_stage(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return y
+
+    def lab_mrf_plan(self, impl, C, ks, d1, d2):
+        """How MRF kernel ``impl`` (0 fused, 1 k_mrf_p, 2 k_mrf_s) cuts a row: (work-item width, halo, x ring, x1 ring) in columns; the
+        rings are the sweep's (0 otherwise).  NativeError where the kernel does not serve the stage.  Host arithmetic only."""
+        self._need_hooks()
+        arr = lambda v: (ctypes.c_int32 * len(v))(*[int(e) for e in v])
+        out = [ctypes.c_int32() for _ in range(4)]
+        rc = self.lib.mi355vits_lab_mrf_plan(int(impl), int(C), len(ks), arr(ks), arr(d1), arr(d2), *[ctypes.byref(o) for o in out])
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return tuple(int(o.value) for o in out)
 
     def test_resample(self, x, lengths, in_hz: int, out_hz: int, device=0):
         """The product's resampler launch (k_resample) on caller-given f32 rows: x [B, row_stride], lengths [B] valid samples

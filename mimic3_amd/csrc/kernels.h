@@ -145,6 +145,22 @@ struct MrfArgs {
 };
 bool mrf_fused_supported(int C, int nrb, const int* k, const int* d1, const int* d2);
 void launch_mrf_fused(MrfArgs a, hipStream_t s);
+// How the three stage kernels cut a row (host arithmetic; the unit-test hooks' plan call): width = the columns of a work item
+// (T_B of k_mrf_fused / k_mrf_p, the step TS of k_mrf_s), halo = max_j (r1_j + r2_j), the columns a stage's output looks to either
+// side; x_ring / x1_ring = the sweep's LDS ring lengths in columns (0 for the other two).  false (nothing written) where the
+// kernel's _supported is false.
+inline int mrf_stage_halo(int nrb, const int* k, const int* d1, const int* d2) {  // max_j (r1_j + r2_j): the one definition
+    int R = 0;
+    for (int j = 0; j < nrb; ++j) {
+        const int r = (k[j] - 1) / 2 * d1[j] + (k[j] - 1) / 2 * d2[j];
+        R = R > r ? R : r;
+    }
+    return R;
+}
+struct MrfPlan { int width = 0, halo = 0, x_ring = 0, x1_ring = 0; };
+bool mrf_fused_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out);
+bool mrf_p_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out);
+bool mrf_s_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out);
 // MATH_BF16X3 with every element split once (kernels_mrfp.cpp): bf16 planes in LDS, the running conv's weight fragments in
 // registers, v_mfma_f32_16x16x32_bf16 tiles.  w[][] = pack_conv_weights_p16 fragments.  C = 32; taps in {3, 5, 7}.
 size_t p16_packed_words(int Cout, int Cin, int K);
@@ -196,6 +212,11 @@ void launch_wn_layer(WnArgs a, hipStream_t s);
 // fragments (plain row order: tanh rows, then sigmoid rows); 96 time columns x all rows per workgroup.
 bool wn_layer_b3_supported(int H, int K, int dil);
 void launch_wn_layer_b3(WnArgs a, hipStream_t s);
+// The 32-column tiles per workgroup (1, 3 or 4) launch_wn_layer_b3 takes for this layer on the current device, and the geometry
+// (0: 4 waves x 3 tiles, 1: 6 x 2, 2: 12 x 1) launch_wn_layer takes at H = 192: the launchers' own rules (lab build and CPU model:
+// with the switches they read), for the launchers and for the unit-test hooks' plan call.
+int wn_layer_b3_column_tiles(const WnArgs& a);
+int wn_layer_geometry(const WnArgs& a);
 
 // ---------------------------------------------------------------- decoder tail
 // y = tanh(conv_post(lrelu_0.01(x * mask))) (Cout = 1, no bias) + per-utterance max|y| over valid samples;

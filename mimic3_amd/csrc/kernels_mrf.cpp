@@ -385,6 +385,14 @@ bool mrf_fused_supported(int C, int nrb, const int* k, const int* d1, const int*
     return ((size_t)C * (ldx + ld1) + (size_t)nrb * 2 * C) * sizeof(float) <= LDS_LIMIT;
 }
 
+bool mrf_fused_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out) {
+    Geo g;
+    if (!out || !mrf_fused_supported(C, nrb, k, d1, d2) || !geometry(C, &g)) return false;
+    const int R = mrf_stage_halo(nrb, k, d1, d2);
+    *out = MrfPlan{g.T_B, R, 0, 0};
+    return true;
+}
+
 void launch_mrf_fused(MrfArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     Geo g;

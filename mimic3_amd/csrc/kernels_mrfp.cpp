@@ -634,6 +634,15 @@ bool mrf_p_supported(int C, int nrb, const int* k, const int* d1, const int* d2)
     return geometry_p(C, &g) && shape_p(C, nrb, k, d1, d2, g, &R, &ldx, &ld1, &lds);
 }
 
+bool mrf_p_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out) {
+    GeoP g;
+    int R, ldx, ld1;
+    size_t lds;
+    if (!out || !mrf_p_supported(C, nrb, k, d1, d2) || !geometry_p(C, &g) || !shape_p(C, nrb, k, d1, d2, g, &R, &ldx, &ld1, &lds)) return false;
+    *out = MrfPlan{g.T_B, R, 0, 0};  // the halo the kernel stages with (shape_p's)
+    return true;
+}
+
 // the > 64 KiB dynamic-LDS opt-in is a per-device function attribute: once per (kernel, device)
 void set_max_dynamic_lds(const void* fn, int bytes) {
 #ifndef MI355_EMU

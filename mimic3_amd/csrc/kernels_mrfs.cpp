@@ -450,6 +450,14 @@ bool mrf_s_supported(int C, int nrb, const int* k, const int* d1, const int* d2)
     return geometry_s(C, nrb, k, d1, d2, &g);
 }
 
+bool mrf_s_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfPlan* out) {
+    GeoS g;
+    if (!out || !mrf_s_supported(C, nrb, k, d1, d2) || !geometry_s(C, nrb, k, d1, d2, &g)) return false;
+    const int R = mrf_stage_halo(nrb, k, d1, d2);
+    *out = MrfPlan{g.TS, R, g.XR, g.X1R};
+    return true;
+}
+
 // Segment length for a grid: the sweep pays (r1 + r2) columns + three to five iterations of pipeline fill per (segment,
 // resblock), so segments should be long; the chip wants at least one item per CU and an even number of them per CU.
 // Returns 0 when the stage is too small for the sweep to pay (the caller runs k_mrf_p: same bits).

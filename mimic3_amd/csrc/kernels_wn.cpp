@@ -715,12 +715,7 @@ bool wn_layer_b3_supported(int H, int K, int dil) {
     return H == WNB_H && (K % 2) == 1 && K >= 1 && dil >= 1 && (K - 1) * dil <= 24;
 }
 
-void launch_wn_layer_b3(WnArgs a, hipStream_t s) {
-    if (a.T <= 0 || a.B <= 0) return;
-    if (!wn_layer_b3_supported(a.H, a.K, a.dil)) throw std::runtime_error("wn_layer_b3: unsupported shape");
-    static const int ablate = lab_getenv("MI355VITS_WN_ABLATE") ? atoi(lab_getenv("MI355VITS_WN_ABLATE")) : 0;
-    a.ablate = ablate;
-    a.vec = (a.h_ld % 4 == 0) && (a.h_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.h_in) % 16 == 0);
+int wn_layer_b3_column_tiles(const WnArgs& a) {
     // 96-column tiles when they fill the chip, 32-column tiles for small grids (same bits, see k_wn_layer_b3)
     const char* nt_s = lab_getenv("MI355VITS_WN_B3_NT");  // read per launch: tests flip it inside one process
     const long nwg3 = (long)((a.T + 95) / 96) * a.B;
@@ -734,6 +729,16 @@ void launch_wn_layer_b3(WnArgs a, hipStream_t s) {
         if ((double)((nwg4 + cus - 1) / cus) * 1.28 < (double)((nwg3 + cus - 1) / cus)) nt = 4;
     }
     if (nt == 4 && (a.math == MATH_F16X2 || ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL || (a.K - 1) * a.dil > 8))) nt = 3;  // (buffer-addressed epilogue; 160 KiB of LDS)
+    return nt;
+}
+
+void launch_wn_layer_b3(WnArgs a, hipStream_t s) {
+    if (a.T <= 0 || a.B <= 0) return;
+    if (!wn_layer_b3_supported(a.H, a.K, a.dil)) throw std::runtime_error("wn_layer_b3: unsupported shape");
+    static const int ablate = lab_getenv("MI355VITS_WN_ABLATE") ? atoi(lab_getenv("MI355VITS_WN_ABLATE")) : 0;
+    a.ablate = ablate;
+    a.vec = (a.h_ld % 4 == 0) && (a.h_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.h_in) % 16 == 0);
+    const int nt = wn_layer_b3_column_tiles(a);
     const int tb = 32 * nt;
     a.ldx = (tb + (a.K - 1) * a.dil + 3 + 3) & ~3;
     const size_t shmem = (size_t)3 * WNB_NG * 2 * a.ldx * 16;  // the h planes; u's planes (column pitch tb <= ldx) take their place
@@ -773,6 +778,13 @@ bool wn_layer_fused_supported(int H, int K, int dil) {
     return (H == 32 || H == 192) && (K % 2) == 1 && K >= 1 && dil >= 1 && (size_t)H * (32 + (K - 1) * dil + 8) * 4 <= 48 * 1024;
 }
 
+int wn_layer_geometry(const WnArgs& a) {
+    const char* six_s = lab_getenv("MI355VITS_WN_SIX_WAVES");  // read per launch: tests flip it inside one process
+    const int six_env = six_s ? atoi(six_s) : -1;
+    const long nwg = (long)((a.T + 31) / 32) * a.B;
+    return six_env >= 0 ? six_env : (nwg < 128 ? 2 : (nwg < 512 ? 1 : 0));  // 0: 4x3, 1: 6x2, 2: 12x1
+}
+
 void launch_wn_layer(WnArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     if (!wn_layer_fused_supported(a.H, a.K, a.dil)) throw std::runtime_error("wn_layer: unsupported shape");
@@ -785,10 +797,7 @@ void launch_wn_layer(WnArgs a, hipStream_t s) {
     // Three geometries with identical arithmetic (same bits): 4 waves x 3 tiles keeps the SIMDs evenly loaded when the
     // grid fills the chip; 6 x 2 and 12 x 1 have ever shorter dependent MFMA chains per wave, which is what matters when
     // only a few dozen workgroups exist (one utterance: 31 workgroups per layer).
-    const char* six_s = lab_getenv("MI355VITS_WN_SIX_WAVES");  // read per launch: tests flip it inside one process
-    const int six_env = six_s ? atoi(six_s) : -1;
-    const long nwg = (long)grid.x * grid.y;
-    const int geom = six_env >= 0 ? six_env : (nwg < 128 ? 2 : (nwg < 512 ? 1 : 0));  // 0: 4x3, 1: 6x2, 2: 12x1
+    const int geom = wn_layer_geometry(a);
     const size_t sh4 = (size_t)a.H * (a.ldx > 64 ? a.ldx : 64) * sizeof(float);  // h tile, then [2H][32] raw result
     if (a.H == 192 && geom == 0) {
         LAUNCH_KERNEL(k_wn_layer_h192<4>, grid, dim3(256), sh4, s, a);

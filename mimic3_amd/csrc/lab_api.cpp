@@ -529,6 +529,221 @@ int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int 
     });
 }
 
+// one WaveNet layer through a chosen path (include/mi355vits_lab.h says what each reads and writes at and past len[b])
+int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->h_in || !t->w_in || !t->b_in || !t->w_rs || !t->b_rs || !t->len || !t->h_out || !t->skip) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, H = t->H, T = t->T, K = t->K, dil = t->dilation, Crs = t->Crs;
+        if (B < 1 || H < 1 || T < 1 || K < 1 || (K % 2) == 0 || dil < 1 || (Crs != H && Crs != 2 * H)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if ((long)B * H * T >= 0x7fffffffL / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+        for (int b = 0; b < B; ++b)
+            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        if (t->impl < 0 || t->impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
+        if (t->impl == 2 ? t->math != MATH_BF16X3 : t->math != MATH_F32) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 for impl 0 and 1, MATH_BF16X3 for impl 2");
+        if (t->impl == 1 && !wn_layer_fused_supported(H, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused f32 layer");
+        if (t->impl == 2 && !wn_layer_b3_supported(H, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused split-bf16 layer");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)B * H * T;
+        const std::vector<float> w_in(t->w_in, t->w_in + (size_t)2 * H * H * K), w_rs(t->w_rs, t->w_rs + (size_t)Crs * H);
+        DevBuf dh(n * 4), dho(n * 4), dsk(n * 4), du(n * 4), dbi((size_t)2 * H * 4), dbr((size_t)Crs * 4), dc((size_t)B * 2 * H * 4), dl((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dh.p, t->h_in, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dho.p, t->h_out, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dsk.p, t->skip, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dbi.p, t->b_in, (size_t)2 * H * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dbr.p, t->b_rs, (size_t)Crs * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (t->cond) HIP_CHECK(hipMemcpy(dc.p, t->cond, (size_t)B * 2 * H * 4, hipMemcpyHostToDevice));
+        const long hbs = (long)H * T;
+        auto upload = [](const void* p, size_t bytes) {
+            std::unique_ptr<DevBuf> d(new DevBuf(bytes));
+            HIP_CHECK(hipMemcpy(d->p, p, bytes, hipMemcpyHostToDevice));
+            return d;
+        };
+        std::unique_ptr<DevBuf> dwi, dwr;
+        const float* h_result = dho.as<float>();
+        if (t->impl == 0) {
+            // Engine::coupling_layer's two launches: the gate conv h -> u (no input mask: the engine's h is zero past a row), then the
+            // res/skip conv u -> (h in place, skip); weights as Engine::add_conv_data stages them for Engine::pick_conv's MFMA_F32 / GENERIC
+            // (each conv on its own, as add_conv_data decides per conv: packed fragments where the MFMA kernel takes it, raw weights else)
+            const bool mfma_in = conv1d_mfma_supported(H, 2 * H, K, 1), mfma_rs = conv1d_mfma_supported(H, Crs, 1, 1);
+            if (mfma_in) {
+                std::vector<float> pi(mfma_packed_floats(2 * H, H, K), 0.0f);
+                pack_conv_weights_mfma_mode(w_in.data(), 2 * H, H, K, EPI_GATE, pi.data());
+                dwi = upload(pi.data(), pi.size() * 4);
+            } else {
+                dwi = upload(w_in.data(), w_in.size() * 4);
+            }
+            if (mfma_rs) {
+                std::vector<float> pr(mfma_packed_floats(Crs, H, 1), 0.0f);
+                pack_conv_weights_mfma_mode(w_rs.data(), Crs, H, 1, EPI_STD, pr.data());
+                dwr = upload(pr.data(), pr.size() * 4);
+            } else {
+                dwr = upload(w_rs.data(), w_rs.size() * 4);
+            }
+            ConvArgs in;
+            in.x = dh.as<float>(); in.x_bs = hbs; in.x_ld = T;
+            in.y = du.as<float>(); in.y_bs = hbs; in.y_ld = T;
+            in.epi = EPI_GATE; in.H = H; in.dil = dil;
+            if (t->cond) { in.cond = dc.as<float>(); in.cond_bs = 2L * H; }
+            in.B = B; in.T = T;
+            in.fixed_rule = 1; in.Cin = H; in.Cout = 2 * H; in.K = K; in.bias = dbi.as<float>(); in.pad = (K * dil - dil) / 2;
+            in.w = dwi->as<float>(); in.math = MATH_F32;
+            ConvArgs rs;
+            rs.x = du.as<float>(); rs.x_bs = hbs; rs.x_ld = T;
+            rs.y = dh.as<float>(); rs.y_bs = hbs; rs.y_ld = T;
+            rs.y2 = dsk.as<float>(); rs.y2_bs = hbs; rs.y2_ld = T;
+            rs.epi = EPI_RESSKIP; rs.H = H; rs.skip_init = t->skip_init != 0;
+            rs.out_len = dl.as<int>();
+            rs.B = B; rs.T = T;
+            rs.fixed_rule = 1; rs.Cin = H; rs.Cout = Crs; rs.K = 1; rs.bias = dbr.as<float>(); rs.pad = 0;
+            rs.w = dwr->as<float>(); rs.math = MATH_F32;
+            if (mfma_in) launch_conv1d_mfma(in, nullptr);
+            else launch_conv1d_generic(in, nullptr);
+            if (mfma_rs) launch_conv1d_mfma(rs, nullptr);
+            else launch_conv1d_generic(rs, nullptr);
+            h_result = dh.as<float>();  // in place
+        } else {
+            if (t->impl == 1) {
+                std::vector<float> pi(mfma_packed_floats(2 * H, H, K), 0.0f), pr(mfma_packed_floats(Crs, H, 1), 0.0f);
+                pack_conv_weights_mfma_mode(w_in.data(), 2 * H, H, K, EPI_GATE, pi.data());
+                pack_conv_weights_mfma_mode(w_rs.data(), Crs, H, 1, EPI_STD, pr.data());
+                dwi = upload(pi.data(), pi.size() * 4);
+                dwr = upload(pr.data(), pr.size() * 4);
+            } else {
+                // Engine::add_conv_data's packed_b3w: 32-row tile q of the gate conv = the tanh rows of channels 16 q .. 16 q + 15, then their
+                // sigmoid rows, as layout-1 planes; the res/skip conv in plain row order (packed_b3s)
+                const size_t row = (size_t)H * K;
+                std::vector<float> wg(w_in.size());
+                for (int q = 0; q < 2 * H / 32; ++q)
+                    for (int r = 0; r < 32; ++r) {
+                        const int src = (r < 16 ? 0 : H) + 16 * q + (r & 15);
+                        memcpy(wg.data() + ((size_t)32 * q + r) * row, w_in.data() + (size_t)src * row, row * sizeof(float));
+                    }
+                std::vector<uint32_t> bi(bf16x3_packed_words_mode(2 * H, H, K, EPI_STD)), br(bf16x3_packed_words_mode(Crs, H, 1, EPI_STD));
+                pack_conv_weights_bf16x3_mode(wg.data(), 2 * H, H, K, EPI_STD, 1, bi.data());
+                pack_conv_weights_bf16x3_mode(w_rs.data(), Crs, H, 1, EPI_STD, 1, br.data());
+                dwi = upload(bi.data(), bi.size() * 4);
+                dwr = upload(br.data(), br.size() * 4);
+            }
+            WnArgs w;
+            w.h_in = dh.as<float>(); w.h_out = dho.as<float>(); w.h_bs = hbs; w.h_ld = T;
+            w.skip = dsk.as<float>(); w.s_bs = hbs; w.s_ld = T;
+            w.w_in = dwi->as<float>(); w.b_in = dbi.as<float>();
+            w.w_rs = dwr->as<float>(); w.b_rs = dbr.as<float>();
+            if (t->cond) { w.cond = dc.as<float>(); w.cond_bs = 2L * H; }
+            w.len = dl.as<int>();
+            w.B = B; w.H = H; w.T = T; w.K = K; w.dil = dil; w.Crs = Crs; w.skip_init = t->skip_init != 0;
+            if (t->impl == 2) { w.math = MATH_BF16X3; launch_wn_layer_b3(w, nullptr); }
+            else launch_wn_layer(w, nullptr);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        // impl 1 and 2: whatever the device's h_out holds now (Crs = H: the launch must have left it as it was); impl 0 works in place
+        // on its copy of h, which a last layer leaves untouched: nothing to report then
+        if (t->impl != 0 || Crs == 2 * H) HIP_CHECK(hipMemcpy(t->h_out, h_result, n * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(t->skip, dsk.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_wn_plan(int B, int T, int K, int dilation, int32_t* b3_tile, int32_t* f32_geometry) {
+    return guarded(nullptr, [&] {
+        if (B < 1 || T < 1 || K < 1 || (K % 2) == 0 || dilation < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        WnArgs w;
+        w.B = B; w.H = 192; w.T = T; w.K = K; w.dil = dilation; w.h_ld = w.s_ld = T; w.math = MATH_BF16X3;
+        if (b3_tile) {
+            if (!wn_layer_b3_supported(w.H, K, dilation)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused split-bf16 layer");
+            *b3_tile = 32 * wn_layer_b3_column_tiles(w);
+        }
+        if (f32_geometry) *f32_geometry = wn_layer_geometry(w);
+    });
+}
+
+// one multi-receptive-field stage through a chosen kernel (include/mi355vits_lab.h says what each reads and writes at and past len[b])
+static bool mrf_test_plan(int impl, int C, int nrb, const int32_t* k, const int32_t* d1, const int32_t* d2, MrfPlan* p) {
+    if (nrb < 1 || nrb > MRF_MAX_RB || !k || !d1 || !d2) return false;
+    int kk[MRF_MAX_RB], a1[MRF_MAX_RB], a2[MRF_MAX_RB];
+    for (int j = 0; j < nrb; ++j) { kk[j] = k[j]; a1[j] = d1[j]; a2[j] = d2[j]; }
+    return impl == 0 ? mrf_fused_plan(C, nrb, kk, a1, a2, p) : impl == 1 ? mrf_p_plan(C, nrb, kk, a1, a2, p) : impl == 2 ? mrf_s_plan(C, nrb, kk, a1, a2, p) : false;
+}
+
+int mi355vits_test_mrf_stage(int device, const mi355vits_mrf_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->x || !t->len || !t->y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, C = t->C, T = t->T, nrb = t->nrb;
+        if (B < 1 || C < 1 || T < 1 || nrb < 1 || nrb > MRF_MAX_RB || !(t->out_scale >= 0.0f)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if ((long)C * T * 4 >= 0x7fffffffL || (long)B * C * T >= 0x7fffffffL / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+        for (int j = 0; j < nrb; ++j)
+            for (int q = 0; q < 2; ++q)
+                if (!t->w[j][q] || !t->bias[j][q]) throw EngineError(MI355VITS_ERR_INVALID, "null weight or bias");
+        for (int b = 0; b < B; ++b)
+            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        if (t->impl < 0 || t->impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
+        if (t->impl == 0 ? (t->math != MATH_F32 && t->math != MATH_BF16X3) : t->math != MATH_BF16X3)
+            throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 or MATH_BF16X3 for impl 0, MATH_BF16X3 for impl 1 and 2");
+        MrfPlan plan;
+        if (!mrf_test_plan(t->impl, C, nrb, t->k, t->d1, t->d2, &plan)) throw EngineError(MI355VITS_ERR_INVALID, "stage not supported by the chosen kernel");
+        if (t->impl == 2 && (t->seg < plan.width || t->seg % plan.width != 0)) throw EngineError(MI355VITS_ERR_INVALID, "seg must be a positive multiple of the sweep's step");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)B * C * T;
+        DevBuf dx(n * 4), dy(n * 4), dl((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dx.p, t->x, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, t->y, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
+        std::vector<int> len_host(t->len, t->len + B);
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        auto upload = [&](const void* p, size_t bytes) {
+            keep.emplace_back(new DevBuf(bytes));
+            HIP_CHECK(hipMemcpy(keep.back()->p, p, bytes, hipMemcpyHostToDevice));
+            return keep.back()->as<float>();
+        };
+        MrfArgs m;
+        m.x = dx.as<float>(); m.x_bs = (long)C * T; m.x_ld = T;
+        m.y = dy.as<float>(); m.y_bs = (long)C * T; m.y_ld = T;
+        m.len = dl.as<int>(); m.len_host = len_host.data(); m.B = B; m.C = C; m.T = T;
+        m.nrb = nrb; m.math = t->math; m.out_scale = t->out_scale;
+        for (int j = 0; j < nrb; ++j) {
+            const int k = t->k[j];
+            m.k[j] = k; m.d1[j] = t->d1[j]; m.d2[j] = t->d2[j];
+            for (int q = 0; q < 2; ++q) {
+                const float* w = t->w[j][q];
+                if (t->impl != 0) {  // Engine::add_conv_data's packed_p
+                    std::vector<uint32_t> pp(p16_packed_words(C, C, k));
+                    pack_conv_weights_p16(w, C, C, k, pp.data());
+                    m.w[j][q] = upload(pp.data(), pp.size() * 4);
+                } else if (t->math == MATH_BF16X3) {  // packed_b3
+                    std::vector<uint32_t> b3(bf16x3_packed_words(C, C, k));
+                    pack_conv_weights_bf16x3(w, C, C, k, b3.data());
+                    m.w[j][q] = upload(b3.data(), b3.size() * 4);
+                } else {  // packed4
+                    std::vector<float> pk(mfma_packed_floats(C, C, k), 0.0f), p4(pk.size());
+                    pack_conv_weights_mfma_mode(w, C, C, k, EPI_STD, pk.data());
+                    regroup_packed_x4(pk.data(), pk.size(), p4.data());
+                    m.w[j][q] = upload(p4.data(), p4.size() * 4);
+                }
+                m.bias[j][q] = upload(t->bias[j][q], (size_t)C * 4);
+            }
+        }
+        if (t->impl == 0) launch_mrf_fused(m, nullptr);
+        else if (t->impl == 1) launch_mrf_p(m, nullptr);
+        else { m.seg = t->seg; launch_mrf_s(m, nullptr); }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(t->y, dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_mrf_plan(int impl, int C, int nrb, const int32_t* k, const int32_t* d1, const int32_t* d2, int32_t* width,
+                           int32_t* halo, int32_t* x_ring, int32_t* x1_ring) {
+    return guarded(nullptr, [&] {
+        MrfPlan p;
+        if (!mrf_test_plan(impl, C, nrb, k, d1, d2, &p)) throw EngineError(MI355VITS_ERR_INVALID, "stage not supported by the chosen kernel");
+        if (width) *width = p.width;
+        if (halo) *halo = p.halo;
+        if (x_ring) *x_ring = p.x_ring;
+        if (x1_ring) *x1_ring = p.x1_ring;
+    });
+}
+
 int mi355vits_bench_conv1d(int device, int B, int Cin, int Cout, int T, int K, int dilation, int epi, int reps,
                            float* ms_per_launch) {
     return guarded(nullptr, [&] {
