@@ -24,8 +24,8 @@ struct ConvArgs {
     const float* res = nullptr; long res_bs = 0; int res_ld = 0;  // residual [B,Cout,T] or null
     float* y2 = nullptr; long y2_bs = 0; int y2_ld = 0;           // RESSKIP: skip accumulator [B,H,T]
     const int* in_len = nullptr;   // [B] valid length of the input (x * mask) or null
-    const int* in_len_host = nullptr;  // kernels_rbc.cpp: the host's copy of in_len (launcher: counts the items with work; null: read back)
-    int nvalid = 0;                // kernels_rbc.cpp: (row, column block) items with work, filled by the launcher (mrf_valid_items)
+    const int* in_len_host = nullptr;  // kernels_rbc.cpp: the host's copy of in_len (launcher: counts the items with work; null: read back; items.h)
+    int nvalid = 0;                // kernels_rbc.cpp: (row, column block) items with work, filled by the launcher (items.h)
     int rb_loop = 0;               // k_enc_b3: 64-row output blocks a workgroup walks over one staged slice (launcher: 3 on large grids)
     const int* out_len = nullptr;  // [B] valid length of the output (y * mask) or null
     int B = 1, Cin = 0, Cout = 0, T = 0, K = 1, dil = 1;
@@ -53,7 +53,7 @@ struct ConvArgs {
     // part[((s * B + b) * Cout + co) * T + t] (no epilogue; launch_layernorm adds them up); ksplit = 1: y with the epilogue
     int ksplit = 1;
     float* part = nullptr;
-    int item_order = 0;  // kernels_rbc.cpp (set by its launchers): 1 = the persistent workgroups walk their items XCD-major (rbc_item)
+    int item_order = 0;  // kernels_rbc.cpp (set by its launchers): 1 = the persistent workgroups walk their items XCD-major where the grid allows it (items.h)
 };
 
 // Short-sequence dense conv of the text encoder (q/k/v, o, FFN: T = phonemes) in MATH_BF16X3 / BF16W: 64 x 64 output tiles, a
@@ -166,10 +166,6 @@ bool mrf_s_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfP
 size_t p16_packed_words(int Cout, int Cin, int K);
 void pack_conv_weights_p16(const float* w, int Cout, int Cin, int K, uint32_t* out);
 bool mrf_p_supported(int C, int nrb, const int* k, const int* d1, const int* d2);
-// sum over the rows of ceil(min(len, T) / block): the (row, column block) items of a ragged batch that have work.  len_host = the
-// host's copy of the device array len (nullptr: copied back, a synchronising call — unit-test hooks only); len == nullptr: every row T
-// extra: positions a row has beyond its length (polyphase upsamplers: len input positions -> len + 1 output positions)
-int mrf_valid_items(const int* len_host, const int* len_dev, int B, int T, int block, int extra = 0);
 void launch_mrf_p(MrfArgs a, hipStream_t s);
 // The same stage, same bits, as a row sweep (kernels_mrfs.cpp): work item = (row, segment), one pass per resblock with the
 // waves specialised by conv, every conv's fragments in registers for the whole segment, no halo recompute; y accumulates the
@@ -186,6 +182,11 @@ void launch_rb_conv(ConvArgs a, hipStream_t s);
 void pack_conv_weights_p16n(const float* w, int Cout, int Cin, int K, uint32_t* out);
 bool ups_pl_supported(const ConvArgs& a);
 void launch_ups_pl(ConvArgs a, hipStream_t s);
+// ---- launch_util.cpp: what the launchers share (the items themselves, their order and the persistent grid: items.h)
+// sum over the rows of ceil(min(len, T) / block): the (row, column block) items of a ragged batch that have work.  len_host = the
+// host's copy of the device array len (nullptr: copied back, a synchronising call — unit-test hooks only); len == nullptr: every row T
+// extra: positions a row has beyond its length (polyphase upsamplers: len input positions -> len + 1 output positions)
+int valid_items(const int* len_host, const int* len_dev, int B, int T, int block, int extra = 0);
 int current_device_cu_count();  // compute units of the current device (persistent grids): cached per device (CPU model: reread)
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute: set once per (kernel, current device)
 void set_max_dynamic_lds(const void* fn, int bytes);

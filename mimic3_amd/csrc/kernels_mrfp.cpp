@@ -22,12 +22,10 @@
 //     record: row 4 q + i of tile mt = channel 32 (mt >> 1) + 8 q + 4 (mt & 1) + i (the weights are packed to match,
 //     pack_conv_weights_p16).
 // HBM traffic = read x (+halo) + write y, as before.
-#include <atomic>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
+#include "items.h"
 #include "kernels.h"
 
 namespace m355 {
@@ -129,6 +127,15 @@ struct MrfPShape {
 };
 using MrfPDyn = MrfPShape<0, 0, 0, 0, 0, 0, 0, 0>;
 
+// how k_mrf_p's cursor (items.h) reads a row's length: a plain load; no table = every row is full
+struct MrfPRowLen {
+    const MrfArgs* a;
+    __device__ __forceinline__ int operator()(int bb) const {
+        int ln = a->len ? a->len[bb] : a->T;
+        return ln > a->T ? a->T : ln;
+    }
+};
+
 template <int C, int NWM, int NWC, int NT2, int NHMAX, int K0, int K1, int K2, typename SH>
 __global__ __launch_bounds__(512) void k_mrf_p(MrfArgs a) {
     static_assert(NWM * NWC == 8 && NWM * 16 == C, "eight waves: C / 16 row tiles x column groups");
@@ -150,44 +157,18 @@ __global__ __launch_bounds__(512) void k_mrf_p(MrfArgs a) {
     float* BS = reinterpret_cast<float*>(X1p + 3 * PS1);  // [nrb][2][C] biases
     const int tid = threadIdx.x, lane = tid & 63, wid = WAVE_UNIFORM(tid >> 6);
     const int mt = wid % NWM;
-    // work items = the column blocks that HAVE work: row b contributes nv_b = ceil(len_b / T_B) of them (ragged batches, round 6: a
-    // block that starts at or past its row's length is never computed — its output columns are past the row's end, every consumer
-    // masks its input at the row's length, the workspace is zero-filled when it is allocated — so a batch costs the sum of its rows'
-    // lengths in this stage, not rows x the longest).  Valid items are numbered row by row (a.nvalid of them: counted by the
-    // launcher from the host's copy of the lengths); this workgroup takes first, first + stride, ... of its XCD's contiguous eighth
-    // (blocks of one XCD — block b runs on XCD b % 8 — walk neighbouring items: the halo columns two items share are re-read from
-    // that XCD's L2; the eighths hold equal numbers of VALID items whatever the rows' lengths).  A cursor (row, first valid index
-    // of that row, its count) turns an index into (row, column block); the indices of a workgroup only grow.
+    // work items = the (row, block of T_B columns) pairs that HAVE work, a.nvalid of them, numbered row by row; this workgroup takes
+    // first, first + stride, ... of its XCD's contiguous eighth, a forward-only cursor turns an index into (row, block): items.h
     const int nitems = a.nvalid;
     // (grids of fewer than eight workgroups: as many groups as workgroups, so that every group's items have a workgroup)
     const int nblk = gridDim.x, ngrp = nblk < 8 ? nblk : 8, xcd = blockIdx.x % ngrp, slot = blockIdx.x / ngrp;
     const int per_xcd = (nitems + ngrp - 1) / ngrp, nslot = (nblk + ngrp - 1 - xcd) / ngrp;  // blocks on this XCD (nblk need not be a multiple of 8)
     const int item_end = (xcd + 1) * per_xcd < nitems ? (xcd + 1) * per_xcd : nitems;
-    auto row_len = [&](int bb) MI355_INLINE_LAMBDA {
-        int ln = a.len ? a.len[bb] : a.T;
-        return ln > a.T ? a.T : ln;
-    };
-    struct Cursor { int r, base, nv; };
-    auto locate = [&](int v, Cursor& c) MI355_INLINE_LAMBDA {  // v < a.nvalid: the loop ends inside the batch
-        while (v >= c.base + c.nv && c.r + 1 < a.B) {  // (the row bound: a count that disagreed with the table must not walk off it)
-            c.base += c.nv;
-            ++c.r;
-            const int ln = row_len(c.r);
-            c.nv = ln > 0 ? (ln + T_B - 1) / T_B : 0;
-        }
-        c.r = WAVE_UNIFORM(c.r);
-        c.base = WAVE_UNIFORM(c.base);
-        c.nv = WAVE_UNIFORM(c.nv);
-    };
+    const MrfPRowLen row_len{&a};
+    using Cursor = ItemCursor<T_B, 0, MrfPRowLen>;
     int item = xcd * per_xcd + slot;
-    Cursor cur;
-    cur.r = 0;
-    cur.base = 0;
-    {
-        const int ln = row_len(0);
-        cur.nv = ln > 0 ? (ln + T_B - 1) / T_B : 0;
-    }
-    if (item < item_end) locate(item, cur);
+    Cursor cur(row_len, a.B, nitems, 0);
+    if (item < item_end) cur.advance(item);
 
     uint4 W[MRFP_KMAX][3];
     // fragments of (resblock j, conv c, k-group g) for this wave's row tile (wave-uniform; the lane is a 32-bit index on top)
@@ -347,7 +328,7 @@ __global__ __launch_bounds__(512) void k_mrf_p(MrfArgs a) {
         item_next = item + nslot;
         const bool more = item_next < item_end;  // wave-uniform
         Cursor cn = cur;
-        if (more) locate(item_next, cn);
+        if (more) cn.advance(item_next);
 
         stamp(0);
         if constexpr (!PIPE) stage_item(b, t0, len);
@@ -603,24 +584,6 @@ inline bool shape_p(int C, int nrb, const int* k, const int* d1, const int* d2, 
 }
 }  // namespace
 
-int mrf_valid_items(const int* len_host, const int* len_dev, int B, int T, int block, int extra) {
-    if (B <= 0 || T <= 0 || block <= 0) return 0;
-    const int full = (T + block - 1) / block;
-    if (!len_dev) return B * full;
-    std::vector<int> tmp;
-    if (!len_host) {
-        tmp.resize((size_t)B);
-        HIP_CHECK(hipMemcpy(tmp.data(), len_dev, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
-        len_host = tmp.data();
-    }
-    long n = 0;
-    for (int b = 0; b < B; ++b) {
-        const int ln = len_host[b] <= 0 ? 0 : (len_host[b] + extra > T ? T : len_host[b] + extra);
-        if (ln > 0) n += (ln + block - 1) / block;
-    }
-    return (int)n;
-}
-
 bool mrf_p_supported(int C, int nrb, const int* k, const int* d1, const int* d2) {
     GeoP g;
     int R, ldx, ld1;
@@ -643,53 +606,16 @@ bool mrf_p_plan(int C, int nrb, const int* k, const int* d1, const int* d2, MrfP
     return true;
 }
 
-// the > 64 KiB dynamic-LDS opt-in is a per-device function attribute: once per (kernel, device)
-void set_max_dynamic_lds(const void* fn, int bytes) {
-#ifndef MI355_EMU
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.count({fn, dev})) return;
-    HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.insert({fn, dev});
-#else
-    (void)fn; (void)bytes;
-#endif
-}
-
-// the one lookup of the compute-unit count behind every persistent grid and every form chosen by grid size
-int current_device_cu_count() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-#ifdef MI355_EMU
-    // the CPU model's count is a test parameter (mi355vits_emu_set_cu_count): read at every launch, never cached
-    hipDeviceProp_t p;
-    return (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-#else
-    static std::atomic<int> cached[64];  // looked up once per device
-    int n = cached[dev].load(std::memory_order_relaxed);
-    if (n <= 0) {
-        hipDeviceProp_t p;
-        n = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-#endif
-}
-
 void launch_mrf_p(MrfArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     GeoP g;
     size_t shmem = 0;
     if (!geometry_p(a.C, &g) || a.nrb < 1 || a.nrb > MRF_MAX_RB || !shape_p(a.C, a.nrb, a.k, a.d1, a.d2, g, &a.R, &a.ldx, &a.ld1, &shmem))
         throw std::runtime_error("mrf_p: unsupported stage shape");
-    a.nvalid = mrf_valid_items(a.len_host, a.len, a.B, a.T, g.T_B);
-    const long nitems = a.nvalid;
-    if (nitems <= 0) return;
-    const int cus = current_device_cu_count();
-    dim3 grid((unsigned)(nitems < cus ? nitems : cus));  // persistent: one workgroup per CU (160 KiB of LDS each)
+    const ItemLaunch il = item_launch(a.len_host, a.len, a.B, a.T, g.T_B, 0, current_device_cu_count(), 0);  // (the kernel walks contiguous eighths: no remap)
+    a.nvalid = il.nvalid;
+    if (il.nvalid <= 0) return;
+    dim3 grid((unsigned)il.grid);  // persistent: one workgroup per CU (160 KiB of LDS each)
 #ifdef MI355_LAB
     {
         const char* ab = lab_getenv("MI355VITS_MRF_ABLATE");

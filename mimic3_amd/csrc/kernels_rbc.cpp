@@ -29,6 +29,7 @@
 #include <vector>
 #include <type_traits>
 
+#include "items.h"
 #include "kernels.h"
 
 namespace m355 {
@@ -39,21 +40,50 @@ constexpr int RBC_C = 128, RBC_G = RBC_C / 32, RBC_REC = RBC_C / 8;
 constexpr int RBC_WR = 4;  // weight-fragment ring: the running step and three ahead (the step count is a multiple of 4)
 }  // namespace
 
-// Item order of the persistent workgroups.  Workgroup w runs on XCD w % 8 and walks the items w, w + W, w + 2 W, ... (W = the grid);
-// consecutive items of a row — which share their halo columns, or (k_ups64: 127-position items) the 128-byte lines their rows' ends
-// fall into — would so land on eight different XCDs and be fetched from HBM by each of them.  XCD-major: logical item it = 8 q + x
-// becomes the q-th item of XCD x's contiguous eighth of the items (a bijection for every item count), so that the 32 CUs of an XCD work
-// on neighbouring items at the same time and the shared bytes come out of that XCD's L2 (k_mrf_p has walked its items like this since round 3).
-// The cursor only moves forward, so a workgroup's remapped items must grow: they do when W % 8 == 0 or W == the item count (rbc_order).
-__device__ __forceinline__ int rbc_item(int it, int n, int order) {
-    if (!order) return it;
-    const int x = it & 7, q = it >> 3, f = n >> 3, rm = n & 7;
-    return x * f + (x < rm ? x : rm) + q;
+// The work items of all four kernels — the (row, block of N positions) pairs that HAVE work, a.nvalid of them, walked XCD-major with
+// a forward-only cursor — are items.h's (ItemCursor; the launchers: item_launch).
+constexpr int RBC_ITEM_ORDER = 1;  // XCD-major wherever the grid allows it (item_order_rule)
+
+// Staging, shared by the kernels: thread t takes the (record, column) pairs t + THREADS round of the COUNT pairs of a buffer with LD
+// columns per record (past the end: the last pair again — same bytes to the same slot, no branch).  Everything derived from t is
+// recomputed per round (hoisted, the offsets of all rounds occupy registers).
+struct StageSlot { int rec, col; };
+template <int THREADS, int COUNT, int LD>
+__device__ __forceinline__ StageSlot stage_slot(int t, int round) {
+    OPAQUE_V(t);
+    int idx = t + THREADS * round;
+    if (THREADS * (round + 1) > COUNT) idx = idx < COUNT ? idx : COUNT - 1;
+    StageSlot o;
+    o.rec = idx / LD;
+    o.col = idx - o.rec * LD;
+    return o;
 }
-constexpr int RBC_ITEM_ORDER = 1;
-// the item order a launch of `grid` persistent workgroups over `nitems` items may use: XCD-major only where every workgroup's
-// sequence w, w + W, ... stays increasing after rbc_item (otherwise the forward-only cursor would skip whole rows' items)
-inline int rbc_order(int order, long nitems, int grid) { return grid % 8 == 0 || grid == nitems ? order : 0; }
+// A record's eight channels at one column -> leaky-relu (zero outside the row) -> truncation split -> the three 16-byte plane records.
+// stage_pair = one channel pair (piece 0 .. 3 = one 32-bit word of each plane): inside the matrix stream a kernel deals the pieces
+// out between its MFMAs (its own stage_piece, which the prologues call four times in a row); stage_record = all four at once (the
+// producer waves).
+__device__ __forceinline__ void stage_pair(int piece, const float (&sv)[8], bool in, float slope, uint4 (&ph)[3]) {
+    const float v0 = in ? lrelu_f(sv[2 * piece], slope) : 0.0f, v1 = in ? lrelu_f(sv[2 * piece + 1], slope) : 0.0f;
+    unsigned h, m, l;
+    split3_sc(v0, v1, h, m, l);
+    if (piece == 0) { ph[0].x = h; ph[1].x = m; ph[2].x = l; }
+    if (piece == 1) { ph[0].y = h; ph[1].y = m; ph[2].y = l; }
+    if (piece == 2) { ph[0].z = h; ph[1].z = m; ph[2].z = l; }
+    if (piece == 3) { ph[0].w = h; ph[1].w = m; ph[2].w = l; }
+}
+struct Planes3 { uint4 p[3]; };
+__device__ __forceinline__ Planes3 stage_record(const float (&sv)[8], bool in, float slope) {
+    Planes3 o;
+    MI355_UNROLL
+    for (int pc = 0; pc < 4; ++pc) stage_pair(pc, sv, in, slope, o.p);
+    return o;
+}
+template <unsigned PS16>  // the three records to the same slot of the three planes (PS16 bytes apart)
+__device__ __forceinline__ void store_planes(char* px, const uint4 (&ph)[3]) {
+    MI355_UNROLL
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(px + (unsigned)p * PS16) = ph[p];
+}
+struct StagePos { unsigned addr; bool in; };  // where a staged record goes (byte offset in LDS), and whether its column is inside the row
 
 template <int K, int DIL, int NCT>
 struct RbcGeo {
@@ -91,58 +121,13 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
     float bia[4];
     MI355_UNROLL
     for (int r = 0; r < 4; ++r) bia[r] = a.bias ? a.bias[co0 + r] : 0.0f;
-    // work items = the (row, column block) pairs that HAVE work, a.nvalid of them, numbered row by row (ragged batches, round 6:
-    // kernels_mrfp.cpp has the argument): row b holds ceil(len_b / N); a cursor turns a valid index into (row, block) — the
-    // indices a workgroup decodes only grow
     const int nitems = a.nvalid;
     const unsigned xrow = 4u * (unsigned)a.x_ld, yrow = 4u * (unsigned)a.y_ld, rrow = 4u * (unsigned)a.res_ld;
 
-    struct Item { int b, t0, len, last; };
-    // a row's length through the scalar cache (s_load_dword: the constant address space tells hipcc that the table is read-only;
-    // as a plain global load it costs the item loop a vmcnt(0) — every prefetch drained — and one exposed round trip per item)
-    auto row_len = [&](int b) MI355_INLINE_LAMBDA {
-#ifdef MI355_EMU
-        return a.in_len[b];
-#else
-        typedef const int __attribute__((address_space(4))) * cptr_t;
-        return ((cptr_t)(a.in_len))[b];
-#endif
-    };
-    struct Cursor { int r, base, nv; };
-    auto row_nv = [&](int b) MI355_INLINE_LAMBDA {
-        int len = row_len(b);
-        if (len > a.T) len = a.T;
-        return len > 0 ? (len + N - 1) / N : 0;
-    };
-    auto decode = [&](int it, Cursor& c) MI355_INLINE_LAMBDA {
-        Item o;
-        it = rbc_item(it, nitems, a.item_order);
-        while (it >= c.base + c.nv && c.r + 1 < a.B) {  // (it < a.nvalid: ends inside the batch; the row bound guards a stale count)
-            c.base += c.nv;
-            ++c.r;
-            c.nv = row_nv(c.r);
-        }
-        c.r = WAVE_UNIFORM(c.r);
-        c.base = WAVE_UNIFORM(c.base);
-        c.nv = WAVE_UNIFORM(c.nv);
-        o.b = c.r;
-        o.t0 = WAVE_UNIFORM((it - c.base) * N);
-        int len = row_len(o.b);
-        if (len > a.T) len = a.T;
-        o.len = len;
-        o.last = o.len > 0 ? o.len - 1 : 0;
-        return o;
-    };
-
-    // ---- staging of one half-buffer (records 8 half .. 8 half + 7) of an item, round by round: a thread takes (record, column)
-    // pairs tid + 512 round (past the end: the last pair again — same bytes to the same slot, no branch): eight 4-byte loads = the
+    // ---- staging of one half-buffer (records 8 half .. 8 half + 7) of an item, round by round (stage_slot): eight 4-byte loads = the
     // record's eight channels at that column (256 contiguous bytes per wave and row), clamped into the row and masked afterwards
-    auto stage_load = [&](const Item& im, const BufRsrc& xb, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
-        int t2 = tid;
-        OPAQUE_V(t2);  // everything derived from it is recomputed per round (hoisted, the offsets of all rounds occupy registers)
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+    auto stage_load = [&](const RowItem& im, const BufRsrc& xb, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
+        const auto [rec, col] = stage_slot<512, HALF, LD>(tid, round);
         const int t = im.t0 - PAD + col;
         const int tc = t < 0 ? 0 : (t > im.last ? im.last : t);
         const unsigned o = 4u * (unsigned)(8 * (8 * half + rec) * a.x_ld + tc);
@@ -150,13 +135,8 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
         for (int e = 0; e < 8; ++e) sv[e] = buf_load_f32(xb, o, (unsigned)e * xrow);
     };
     // one quarter of a round's leaky-relu + split (pieces 0 .. 3 = channel pairs), the three 16-byte stores behind the last piece
-    struct StagePos { unsigned addr; bool in; };
-    auto stage_pos = [&](const Item& im, int half, int round) MI355_INLINE_LAMBDA {  // where a round's record goes, and whether it is inside the row
-        int t2 = tid;
-        OPAQUE_V(t2);
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+    auto stage_pos = [&](const RowItem& im, int half, int round) MI355_INLINE_LAMBDA {  // where a round's record goes, and whether it is inside the row
+        const auto [rec, col] = stage_slot<512, HALF, LD>(tid, round);
         const int t = im.t0 - PAD + col;
         StagePos sp;
         sp.in = t >= 0 && t < im.len;
@@ -164,18 +144,8 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
         return sp;
     };
     auto stage_piece = [&](int piece, const float (&sv)[8], uint4 (&ph)[3], const StagePos& sp) MI355_INLINE_LAMBDA {
-        const float v0 = sp.in ? lrelu_f(sv[2 * piece], a.in_slope) : 0.0f, v1 = sp.in ? lrelu_f(sv[2 * piece + 1], a.in_slope) : 0.0f;
-        unsigned h, m, l;
-        split3_sc(v0, v1, h, m, l);
-        if (piece == 0) { ph[0].x = h; ph[1].x = m; ph[2].x = l; }
-        if (piece == 1) { ph[0].y = h; ph[1].y = m; ph[2].y = l; }
-        if (piece == 2) { ph[0].z = h; ph[1].z = m; ph[2].z = l; }
-        if (piece == 3) {
-            ph[0].w = h; ph[1].w = m; ph[2].w = l;
-            char* px = L0 + sp.addr;
-            MI355_UNROLL
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(px + (unsigned)p * PS16) = ph[p];
-        }
+        stage_pair(piece, sv, sp.in, a.in_slope, ph);
+        if (piece == 3) store_planes<PS16>(L0 + sp.addr, ph);
     };
     auto w_load = [&](int s, uint4 (&w)[3]) MI355_INLINE_LAMBDA {  // fragments of step s = (k-group s / K, tap s % K)
         const int g = s / K, k = s % K;
@@ -191,13 +161,10 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
 
     const int it_first = (int)blockIdx.x;
     if (it_first >= nitems) return;
-    Cursor cur;
-    cur.r = 0;
-    cur.base = 0;
-    cur.nv = row_nv(0);
+    ItemCursor<N> cur(RowLenSc{a.in_len, a.T}, a.B, nitems, a.item_order);
     // ---- prologue: half 0 of the first item, the first steps' weight fragments
     {
-        const Item im = decode(it_first, cur);
+        const RowItem im = cur.decode(it_first);
         const BufRsrc xb = buf_rsrc(a.x + (long)im.b * a.x_bs);
         float sv[ROUNDS][8];
         MI355_UNROLL
@@ -219,9 +186,9 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
     MI355_NOUNROLL
     for (int it = it_first, itv = it_first; it < nitems; it = itv) {
         itv = it + (int)gridDim.x;
-        const Item im = decode(it, cur);
+        const RowItem im = cur.decode(it);
         const int itn = itv < nitems ? itv : it;  // (no next item: this one's half 0 again, unread)
-        const Item imn = decode(itn, cur);
+        const RowItem imn = cur.decode(itn);
         const BufRsrc xb = buf_rsrc(a.x + (long)im.b * a.x_bs), xbn = buf_rsrc(a.x + (long)imn.b * a.x_bs);
         const BufRsrc ybuf = buf_rsrc(a.y + (long)im.b * a.y_bs);
         const BufRsrc rbuf = buf_rsrc(a.res + (long)im.b * a.res_bs);
@@ -246,7 +213,7 @@ __global__ __launch_bounds__(512) void k_rb_conv(ConvArgs a) {
         MI355_UNROLL
         for (int h = 0; h < 2; ++h) {
             // this phase computes on half h and refills half 1 - h: the item's own second half, or the next item's first
-            const Item& ims = h == 0 ? im : imn;
+            const RowItem& ims = h == 0 ? im : imn;
             const BufRsrc& xbs = h == 0 ? xb : xbn;
             const int hs = 1 - h;
             float sv[ROUNDS][8];
@@ -378,52 +345,12 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
     DYN_SMEM(float, smem);
     char* L0 = reinterpret_cast<char*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wv = WAVE_UNIFORM(tid >> 6);
-    // work items = the (row, column block) pairs that HAVE work, a.nvalid of them, numbered row by row (ragged batches, round 6:
-    // kernels_mrfp.cpp has the argument): row b holds ceil(len_b / N); a cursor turns a valid index into (row, block) — the
-    // indices a workgroup decodes only grow
     const int nitems = a.nvalid;
     const unsigned xrow = 4u * (unsigned)a.x_ld, yrow = 4u * (unsigned)a.y_ld, rrow = 4u * (unsigned)a.res_ld;
 
-    struct Item { int b, t0, len, last; };
-    auto row_len = [&](int b) MI355_INLINE_LAMBDA {
-#ifdef MI355_EMU
-        return a.in_len[b];
-#else
-        typedef const int __attribute__((address_space(4))) * cptr_t;
-        return ((cptr_t)(a.in_len))[b];
-#endif
-    };
-    struct Cursor { int r, base, nv; };
-    auto row_nv = [&](int b) MI355_INLINE_LAMBDA {
-        int len = row_len(b);
-        if (len > a.T) len = a.T;
-        return len > 0 ? (len + N - 1) / N : 0;
-    };
-    auto decode = [&](int it, Cursor& c) MI355_INLINE_LAMBDA {
-        Item o;
-        it = rbc_item(it, nitems, a.item_order);
-        while (it >= c.base + c.nv && c.r + 1 < a.B) {  // (it < a.nvalid: ends inside the batch; the row bound guards a stale count)
-            c.base += c.nv;
-            ++c.r;
-            c.nv = row_nv(c.r);
-        }
-        c.r = WAVE_UNIFORM(c.r);
-        c.base = WAVE_UNIFORM(c.base);
-        c.nv = WAVE_UNIFORM(c.nv);
-        o.b = c.r;
-        o.t0 = WAVE_UNIFORM((it - c.base) * N);
-        int len = row_len(o.b);
-        if (len > a.T) len = a.T;
-        o.len = len;
-        o.last = o.len > 0 ? o.len - 1 : 0;
-        return o;
-    };
     const int it_first = (int)blockIdx.x;
     if (it_first >= nitems) return;
-    Cursor cur;
-    cur.r = 0;
-    cur.base = 0;
-    cur.nv = row_nv(0);
+    ItemCursor<N> cur(RowLenSc{a.in_len, a.T}, a.B, nitems, a.item_order);
     [[maybe_unused]] int clk_item = 0;
     auto stamp = [&](int slot, int k) MI355_INLINE_LAMBDA {
 #ifndef MI355_EMU
@@ -440,44 +367,24 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
         // ================================================================ producer waves: (record, column) pairs pt + 256 round
         const int cslot = wv == 8 ? 2 : -1;
         const int pt = tid - 512;
-        auto p_load = [&](const Item& im, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
+        auto p_load = [&](const RowItem& im, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
             const BufRsrc xb = buf_rsrc(a.x + (long)im.b * a.x_bs);
-            int t2 = pt;
-            OPAQUE_V(t2);
-            int idx = t2 + 256 * round;
-            if (256 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;  // past the end: the last pair again (same bytes, same slot)
-            const int rec = idx / LD, col = idx - rec * LD;
+            const auto [rec, col] = stage_slot<256, HALF, LD>(pt, round);
             const int t = im.t0 - PAD + col;
             const int tc = t < 0 ? 0 : (t > im.last ? im.last : t);
             const unsigned o = 4u * (unsigned)(8 * (8 * half + rec) * a.x_ld + tc);
             MI355_UNROLL
             for (int e = 0; e < 8; ++e) sv[e] = buf_load_f32(xb, o, (unsigned)e * xrow);
         };
-        auto p_store = [&](const Item& im, int half, int round, const float (&sv)[8]) MI355_INLINE_LAMBDA {
-            int t2 = pt;
-            OPAQUE_V(t2);
-            int idx = t2 + 256 * round;
-            if (256 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;
-            const int rec = idx / LD, col = idx - rec * LD;
+        auto p_store = [&](const RowItem& im, int half, int round, const float (&sv)[8]) MI355_INLINE_LAMBDA {
+            const auto [rec, col] = stage_slot<256, HALF, LD>(pt, round);
             const int t = im.t0 - PAD + col;
             const bool in = t >= 0 && t < im.len;
-            uint4 ph[3];
-            unsigned h, m, l;
-            split3_sc(in ? lrelu_f(sv[0], a.in_slope) : 0.0f, in ? lrelu_f(sv[1], a.in_slope) : 0.0f, h, m, l);
-            ph[0].x = h; ph[1].x = m; ph[2].x = l;
-            split3_sc(in ? lrelu_f(sv[2], a.in_slope) : 0.0f, in ? lrelu_f(sv[3], a.in_slope) : 0.0f, h, m, l);
-            ph[0].y = h; ph[1].y = m; ph[2].y = l;
-            split3_sc(in ? lrelu_f(sv[4], a.in_slope) : 0.0f, in ? lrelu_f(sv[5], a.in_slope) : 0.0f, h, m, l);
-            ph[0].z = h; ph[1].z = m; ph[2].z = l;
-            split3_sc(in ? lrelu_f(sv[6], a.in_slope) : 0.0f, in ? lrelu_f(sv[7], a.in_slope) : 0.0f, h, m, l);
-            ph[0].w = h; ph[1].w = m; ph[2].w = l;
-            char* px = L0 + (unsigned)(8 * half + rec) * REC16 + 16u * (unsigned)col;
-            MI355_UNROLL
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(px + (unsigned)p * PS16) = ph[p];
+            store_planes<PS16>(L0 + (unsigned)(8 * half + rec) * REC16 + 16u * (unsigned)col, stage_record(sv, in, a.in_slope).p);
         };
         float sv[RP][8];
         {
-            const Item im = decode(it_first, cur);
+            const RowItem im = cur.decode(it_first);
             MI355_UNROLL
             for (int r = 0; r < RP; ++r) p_load(im, 0, r, sv[r]);
             SCHED_FENCE();
@@ -491,9 +398,9 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
         MI355_NOUNROLL
         for (int it = it_first, itv = it_first; it < nitems; it = itv) {
             itv = it + (int)gridDim.x;
-            const Item im = decode(it, cur);
+            const RowItem im = cur.decode(it);
             const int itn = itv < nitems ? itv : it;  // (no next item: this one again, unread)
-            const Item imn = decode(itn, cur);
+            const RowItem imn = cur.decode(itn);
             // phase 0 (the matrix waves read half 0): this item's half 1 from the registers, then the loads of the next item's half 0
             stamp(cslot, 0);
             MI355_UNROLL
@@ -556,7 +463,7 @@ __global__ __launch_bounds__(768) void k_rb_conv_pw(ConvArgs a) {
     MI355_NOUNROLL
     for (int it = it_first, itv = it_first; it < nitems; it = itv) {
         itv = it + (int)gridDim.x;
-        const Item im = decode(it, cur);
+        const RowItem im = cur.decode(it);
         const BufRsrc ybuf = buf_rsrc(a.y + (long)im.b * a.y_bs);
         const BufRsrc rbuf = buf_rsrc(a.res + (long)im.b * a.res_bs);
         f32x4 acc[NCT];
@@ -715,64 +622,20 @@ __global__ __launch_bounds__(512) void k_ups_pl(ConvArgs a) {
         lq[p] = (unsigned)p * PS16 + (unsigned)(q * LDP + n) * 16u;
         OPAQUE_V(lq[p]);
     }
-    // work items = the (row, block of N output positions) pairs that have work: row b holds ceil((len_b + 1) / N) of them (a.T = Tin + 1
-    // positions for a full row); a.nvalid of them, numbered row by row, decoded with a forward-only cursor (ragged batches: k_rb_conv)
+    // items of N output positions; a row of len input positions has len + 1 of them (a.T = Tin + 1 for a full row)
     const int nitems = a.nvalid;
     const unsigned xrow = 4u * (unsigned)a.x_ld;
 
-    struct Item { int b, t0, len, last; };
-    auto row_len = [&](int b) MI355_INLINE_LAMBDA {
-#ifdef MI355_EMU
-        return a.in_len[b];
-#else
-        typedef const int __attribute__((address_space(4))) * cptr_t;
-        return ((cptr_t)(a.in_len))[b];
-#endif
-    };
-    struct Cursor { int r, base, nv; };
-    auto row_nv = [&](int b) MI355_INLINE_LAMBDA {
-        int len = row_len(b);
-        if (len > a.Tin) len = a.Tin;
-        return len > 0 ? (len + 1 + N - 1) / N : 0;
-    };
-    auto decode = [&](int it, Cursor& c) MI355_INLINE_LAMBDA {
-        Item o;
-        it = rbc_item(it, nitems, a.item_order);
-        while (it >= c.base + c.nv && c.r + 1 < a.B) {
-            c.base += c.nv;
-            ++c.r;
-            c.nv = row_nv(c.r);
-        }
-        c.r = WAVE_UNIFORM(c.r);
-        c.base = WAVE_UNIFORM(c.base);
-        c.nv = WAVE_UNIFORM(c.nv);
-        o.b = c.r;
-        o.t0 = WAVE_UNIFORM((it - c.base) * N);
-        int len = row_len(o.b);
-        if (len > a.Tin) len = a.Tin;
-        o.len = len;
-        o.last = o.len > 0 ? o.len - 1 : 0;
-        return o;
-    };
-    auto stage_load = [&](const Item& im, const BufRsrc& xb, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
-        int t2 = tid;
-        OPAQUE_V(t2);
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+    auto stage_load = [&](const RowItem& im, const BufRsrc& xb, int half, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
+        const auto [rec, col] = stage_slot<512, HALF, LD>(tid, round);
         const int t = im.t0 - 1 + col;
         const int tc = t < 0 ? 0 : (t > im.last ? im.last : t);
         const unsigned o = 4u * (unsigned)(8 * ((REC / 2) * half + rec) * a.x_ld + tc);
         MI355_UNROLL
         for (int e = 0; e < 8; ++e) sv[e] = buf_load_f32(xb, o, (unsigned)e * xrow);
     };
-    struct StagePos { unsigned addr; bool in; };
-    auto stage_pos = [&](const Item& im, int half, int round) MI355_INLINE_LAMBDA {
-        int t2 = tid;
-        OPAQUE_V(t2);
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > HALF) idx = idx < HALF ? idx : HALF - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+    auto stage_pos = [&](const RowItem& im, int half, int round) MI355_INLINE_LAMBDA {
+        const auto [rec, col] = stage_slot<512, HALF, LD>(tid, round);
         const int t = im.t0 - 1 + col;
         StagePos sp;
         sp.in = t >= 0 && t < im.len;
@@ -780,18 +643,8 @@ __global__ __launch_bounds__(512) void k_ups_pl(ConvArgs a) {
         return sp;
     };
     auto stage_piece = [&](int piece, const float (&sv)[8], uint4 (&ph)[3], const StagePos& sp) MI355_INLINE_LAMBDA {
-        const float v0 = sp.in ? lrelu_f(sv[2 * piece], a.in_slope) : 0.0f, v1 = sp.in ? lrelu_f(sv[2 * piece + 1], a.in_slope) : 0.0f;
-        unsigned h, m, l;
-        split3_sc(v0, v1, h, m, l);
-        if (piece == 0) { ph[0].x = h; ph[1].x = m; ph[2].x = l; }
-        if (piece == 1) { ph[0].y = h; ph[1].y = m; ph[2].y = l; }
-        if (piece == 2) { ph[0].z = h; ph[1].z = m; ph[2].z = l; }
-        if (piece == 3) {
-            ph[0].w = h; ph[1].w = m; ph[2].w = l;
-            char* px = L0 + sp.addr;
-            MI355_UNROLL
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(px + (unsigned)p * PS16) = ph[p];
-        }
+        stage_pair(piece, sv, sp.in, a.in_slope, ph);
+        if (piece == 3) store_planes<PS16>(L0 + sp.addr, ph);
     };
     // step u of an item = (row block u / S, k-group (u % S) / K, tap u % K)
     auto w_load = [&](int u, uint4 (&w)[3]) MI355_INLINE_LAMBDA {
@@ -807,14 +660,11 @@ __global__ __launch_bounds__(512) void k_ups_pl(ConvArgs a) {
     };
 
     if ((int)blockIdx.x >= nitems) return;
-    Cursor cur;
-    cur.r = 0;
-    cur.base = 0;
-    cur.nv = row_nv(0);
+    ItemCursor<N, 1> cur(RowLenSc{a.in_len, a.Tin}, a.B, nitems, a.item_order);
     float sv[ROUNDS][8];  // the half being staged: loaded one phase ahead of its stores
     {
         // prologue: half 0 of the first item (loaded and stored), the loads of its half 1, the first steps' weight fragments
-        const Item im = decode(blockIdx.x, cur);
+        const RowItem im = cur.decode(blockIdx.x);
         const BufRsrc xb = buf_rsrc(a.x + (long)im.b * a.x_bs);
         MI355_UNROLL
         for (int r = 0; r < ROUNDS; ++r) stage_load(im, xb, 0, r, sv[r]);
@@ -836,9 +686,9 @@ __global__ __launch_bounds__(512) void k_ups_pl(ConvArgs a) {
 
     MI355_NOUNROLL
     for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const Item im = decode(it, cur);
+        const RowItem im = cur.decode(it);
         const int itn = it + (int)gridDim.x < nitems ? it + (int)gridDim.x : it;
-        const Item imn = decode(itn, cur);
+        const RowItem imn = cur.decode(itn);
         const BufRsrc xbn = buf_rsrc(a.x + (long)imn.b * a.x_bs);
         const BufRsrc ybuf = buf_rsrc(a.y + (long)im.b * a.y_bs);
         f32x4 acc[NCT];
@@ -983,64 +833,21 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, mt = WAVE_UNIFORM(tid >> 6);
     const int q = lane >> 4, n = lane & 15;
     const BufRsrc wbuf = buf_rsrc(a.w);
-    const int nitems = a.nvalid;  // (row, block of NPOS positions) pairs with work, numbered row by row (k_ups_pl has the argument)
+    const int nitems = a.nvalid;  // items of NPOS output positions (a row of len input positions has len + 1)
     const unsigned xrow = 4u * (unsigned)a.x_ld;
     if ((int)blockIdx.x >= nitems) return;
 
-    struct Item { int b, t0, len, last; };
-    auto row_len = [&](int b) MI355_INLINE_LAMBDA {
-#ifdef MI355_EMU
-        return a.in_len[b];
-#else
-        typedef const int __attribute__((address_space(4))) * cptr_t;
-        return ((cptr_t)(a.in_len))[b];
-#endif
-    };
-    struct Cursor { int r, base, nv; };
-    auto row_nv = [&](int b) MI355_INLINE_LAMBDA {
-        int len = row_len(b);
-        if (len > a.Tin) len = a.Tin;
-        return len > 0 ? (len + 1 + NPOS - 1) / NPOS : 0;
-    };
-    auto decode = [&](int it, Cursor& c) MI355_INLINE_LAMBDA {
-        Item o;
-        it = rbc_item(it, nitems, a.item_order);
-        while (it >= c.base + c.nv && c.r + 1 < a.B) {
-            c.base += c.nv;
-            ++c.r;
-            c.nv = row_nv(c.r);
-        }
-        c.r = WAVE_UNIFORM(c.r);
-        c.base = WAVE_UNIFORM(c.base);
-        c.nv = WAVE_UNIFORM(c.nv);
-        o.b = c.r;
-        o.t0 = WAVE_UNIFORM((it - c.base) * NPOS);
-        int len = row_len(o.b);
-        if (len > a.Tin) len = a.Tin;
-        o.len = len;
-        o.last = o.len > 0 ? o.len - 1 : 0;
-        return o;
-    };
-    auto stage_load = [&](const Item& im, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
+    auto stage_load = [&](const RowItem& im, int round, float (&sv)[8]) MI355_INLINE_LAMBDA {
         const BufRsrc xb = buf_rsrc(a.x + (long)im.b * a.x_bs);
-        int t2 = tid;
-        OPAQUE_V(t2);
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > FULL) idx = idx < FULL ? idx : FULL - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+        const auto [rec, col] = stage_slot<512, FULL, LD>(tid, round);
         const int t = im.t0 - 1 + col;
         const int tc = t < 0 ? 0 : (t > im.last ? im.last : t);
         const unsigned o = 4u * (unsigned)(8 * rec * a.x_ld + tc);
         MI355_UNROLL
         for (int e = 0; e < 8; ++e) sv[e] = buf_load_f32(xb, o, (unsigned)e * xrow);
     };
-    struct StagePos { unsigned addr; bool in; };
-    auto stage_pos = [&](const Item& im, unsigned buf, int round) MI355_INLINE_LAMBDA {
-        int t2 = tid;
-        OPAQUE_V(t2);
-        int idx = t2 + 512 * round;
-        if (512 * (round + 1) > FULL) idx = idx < FULL ? idx : FULL - 1;
-        const int rec = idx / LD, col = idx - rec * LD;
+    auto stage_pos = [&](const RowItem& im, unsigned buf, int round) MI355_INLINE_LAMBDA {
+        const auto [rec, col] = stage_slot<512, FULL, LD>(tid, round);
         const int t = im.t0 - 1 + col;
         StagePos sp;
         sp.in = t >= 0 && t < im.len;
@@ -1048,18 +855,8 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
         return sp;
     };
     auto stage_piece = [&](int piece, const float (&sv)[8], uint4 (&ph)[3], const StagePos& sp) MI355_INLINE_LAMBDA {
-        const float v0 = sp.in ? lrelu_f(sv[2 * piece], a.in_slope) : 0.0f, v1 = sp.in ? lrelu_f(sv[2 * piece + 1], a.in_slope) : 0.0f;
-        unsigned h, m, l;
-        split3_sc(v0, v1, h, m, l);
-        if (piece == 0) { ph[0].x = h; ph[1].x = m; ph[2].x = l; }
-        if (piece == 1) { ph[0].y = h; ph[1].y = m; ph[2].y = l; }
-        if (piece == 2) { ph[0].z = h; ph[1].z = m; ph[2].z = l; }
-        if (piece == 3) {
-            ph[0].w = h; ph[1].w = m; ph[2].w = l;
-            char* px = L0 + sp.addr;
-            MI355_UNROLL
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(px + (unsigned)p * PS16) = ph[p];
-        }
+        stage_pair(piece, sv, sp.in, a.in_slope, ph);
+        if (piece == 3) store_planes<PS16>(L0 + sp.addr, ph);
     };
 
     // the four steps' fragments of this wave's row tile: resident (step u = k-group u / K, tap u % K)
@@ -1075,13 +872,10 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
 
     // prologue: the first item's planes into buffer 0, the second item's loads in flight
     float sv[ROUNDS][8];
-    Cursor csr;
-    csr.r = 0;
-    csr.base = 0;
-    csr.nv = row_nv(0);
+    ItemCursor<NPOS, 1> csr(RowLenSc{a.in_len, a.Tin}, a.B, nitems, a.item_order);
     // the item being computed, the one staged into the other buffer and the one whose loads are in flight: decoded ONCE each, in the
     // order the workgroup meets them (the cursor only moves forward); past the last item: the previous one again, unread
-    Item im = decode(blockIdx.x, csr), im1 = im;
+    RowItem im = csr.decode(blockIdx.x), im1 = im;
     {
         MI355_UNROLL
         for (int r = 0; r < ROUNDS; ++r) stage_load(im, r, sv[r]);
@@ -1093,7 +887,7 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
             MI355_UNROLL
             for (int pc = 0; pc < 4; ++pc) stage_piece(pc, sv[r], ph, sp);
         }
-        if ((int)(blockIdx.x + gridDim.x) < nitems) im1 = decode((int)(blockIdx.x + gridDim.x), csr);
+        if ((int)(blockIdx.x + gridDim.x) < nitems) im1 = csr.decode((int)(blockIdx.x + gridDim.x));
         MI355_UNROLL
         for (int r = 0; r < ROUNDS; ++r) stage_load(im1, r, sv[r]);
     }
@@ -1102,8 +896,8 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
     unsigned cur = 0;  // byte offset of the buffer this item computes from
     MI355_NOUNROLL
     for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-        Item im2 = im1;
-        if (it + 2 * (int)gridDim.x < nitems) im2 = decode(it + 2 * (int)gridDim.x, csr);
+        RowItem im2 = im1;
+        if (it + 2 * (int)gridDim.x < nitems) im2 = csr.decode(it + 2 * (int)gridDim.x);
         const BufRsrc ybuf = buf_rsrc(a.y + (long)im.b * a.y_bs);
         const unsigned other = cur == 0u ? BUF : 0u;  // the buffer item i + 1 is staged into
         const bool edge = im.t0 == 0 || 4 * (im.t0 + NPOS) + 1 >= a.shuf_T;  // position 0 or the row's last position belongs to this item
@@ -1205,6 +999,18 @@ __global__ __launch_bounds__(512) void k_ups64(ConvArgs a) {
 
 // ------------------------------------------------------------------------------------------------ host side
 namespace {
+// the item order the launchers ask for (item_launch grants it where the grid allows)
+inline int rbc_requested_order() {
+    if (const char* f = lab_getenv("MI355VITS_RBC_ITEM_ORDER")) return atoi(f);  // lab / tests: 0 = items w, w + W, ... as in round 4
+    return RBC_ITEM_ORDER;
+}
+// the items of a launch (N positions each, `extra` positions per row beyond its length) into the arguments; the persistent grid, 0 = no work
+inline int rbc_items(ConvArgs& a, int N, int extra, int cus) {
+    const ItemLaunch il = item_launch(a.in_len_host, a.in_len, a.B, a.T, N, extra, cus, rbc_requested_order());
+    a.nvalid = il.nvalid;
+    a.item_order = il.item_order;
+    return il.nvalid > 0 ? il.grid : 0;
+}
 inline bool rbc_shape(int K, int dil) {  // the "_low" voices' stage-0 convs (instantiated tap / dilation pairs)
     return (K == 3 && (dil == 1 || dil == 2)) || (K == 5 && (dil == 2 || dil == 6)) || (K == 7 && (dil == 3 || dil == 12));
 }
@@ -1226,29 +1032,22 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     if (!rb_conv_supported(a)) throw std::runtime_error("rb_conv: unsupported shape");
     const int cus = current_device_cu_count();
-    a.item_order = RBC_ITEM_ORDER;
-    if (const char* f = lab_getenv("MI355VITS_RBC_ITEM_ORDER")) a.item_order = atoi(f);  // lab / tests: 0 = items w, w + W, ... as in round 4
     // (the form follows the items that HAVE work: a ragged batch is as large as the sum of its rows)
-    bool wide = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, 128) >= cus;
+    bool wide = valid_items(a.in_len_host, a.in_len, a.B, a.T, 128) >= cus;
     if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
     // wide items: the producer-wave form (twelve waves, k_rb_conv_pw); narrow items: k_rb_conv (eight waves)
     auto go = [&](auto kfn, size_t lds, int ncols, int threads) {
-        a.nvalid = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, ncols);
-        const long nitems = a.nvalid;
-        if (nitems <= 0) return;
-        dim3 grid((unsigned)(nitems < cus ? nitems : cus));  // persistent: one workgroup per CU
-        a.item_order = rbc_order(a.item_order, nitems, (int)grid.x);
+        const int grid = rbc_items(a, ncols, 0, cus);  // persistent: one workgroup per CU
+        if (grid <= 0) return;
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, grid, dim3(threads), lds, s, a);
+        LAUNCH_KERNEL(kfn, dim3(grid), dim3(threads), lds, s, a);
     };
 #if defined(MI355_LAB) && !defined(MI355_EMU)
     if (wide && lab_getenv("MI355VITS_RBC_CLOCKS") && ((a.K == 7 && a.dil == 3) || (a.K == 3 && a.dil == 1))) {
         static int shots = 0;
         if (shots < 4) {  // (two launches of each shape: the first warms the caches)
             ++shots;
-            a.nvalid = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, 128);
-            const long nitems = a.nvalid;
-            const int grid = (int)(nitems < cus ? nitems : cus);
+            const int grid = rbc_items(a, 128, 0, cus);
             float* dbg = nullptr;
             const size_t nb = (size_t)grid * 3 * 8 * 8 * 4;
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dbg), nb));
@@ -1353,16 +1152,11 @@ void launch_ups_pl(ConvArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     if (!ups_pl_supported(a)) throw std::runtime_error("ups_pl: unsupported shape");
     const int cus = current_device_cu_count();
-    a.item_order = RBC_ITEM_ORDER;
-    if (const char* f = lab_getenv("MI355VITS_RBC_ITEM_ORDER")) a.item_order = atoi(f);  // lab / tests: 0 = items w, w + W, ... as in round 4
     auto go = [&](auto kfn, size_t lds, int ncols) {
-        a.nvalid = mrf_valid_items(a.in_len_host, a.in_len, a.B, a.T, ncols, 1);  // a row of len input positions has len + 1 output positions
-        const long nitems = a.nvalid;
-        if (nitems <= 0) return;
-        dim3 grid((unsigned)(nitems < cus ? nitems : cus));
-        a.item_order = rbc_order(a.item_order, nitems, (int)grid.x);
+        const int grid = rbc_items(a, ncols, 1, cus);  // a row of len input positions has len + 1 output positions
+        if (grid <= 0) return;
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, grid, dim3(512), lds, s, a);
+        LAUNCH_KERNEL(kfn, dim3(grid), dim3(512), lds, s, a);
     };
     if (a.Cin == 256) {  // 256 -> 128: eight row blocks over 64-column items (32 records of planes: 123 KiB)
         bool wide = (long)a.B * ((a.T + 63) / 64) >= cus;
