@@ -505,7 +505,7 @@ void mi355vits_free_loudness(mi355vits_loudness* r);
  *  - With it on, mi355vits_run_packed / _fetch_packed limit the over rows of a pack with a target instead of capping their gain;
  *    mi355vits_fetch_loudness and the packed results then report gain = g (uncapped) and limited = 1 for those rows.
  *  - mi355vits_run_streams / _fetch_streams (below) cannot carry a per-stream window — mi355vits_stream_args is frozen —: the handle's
- *    window applies to every stream that has a target.
+ *    window applies to every stream that has a target.  (A window per stream: mi355vits_run_streams2 / _fetch_streams2.)
  *  - mi355vits_fetch_limiter serves the LAST COMPLETED RUN under the handle's current target, ceiling and window, in an arena of its
  *    own (what the other fetches serve afterwards is what they served before): engaged[b] = the row is over, reduced_samples[b] = the
  *    count of k with sq[k] < (L + 1) 2^30, min_scale[b] = min over k of s[k] (1.0 for a row that is not over).  With the limiter or
@@ -626,7 +626,8 @@ void mi355vits_free_true_peak(mi355vits_true_peak* r);
  *    is exactly n_bytes - 42 bytes.  The profiler reports the launches as pack.flac with 2 * total_samples + (n_bytes - 42) bytes,
  *    behind the pcm16.pack line of the S16LE pack in front of them.
  *  - Scope: mi355vits_run_packed and mi355vits_fetch_packed.  mi355vits_run_streams / _fetch_streams never read the setting
- *    (mi355vits_stream_args is frozen) and stay byte for byte what they are. */
+ *    (mi355vits_stream_args is frozen) and stay byte for byte what they are.  FLAC per stream of a block: mi355vits_run_streams2 /
+ *    _fetch_streams2, which take the compression from the stream. */
 #define MI355VITS_COMPRESS_NONE 0   /* default: every byte, launch and synchronisation is what it was */
 #define MI355VITS_COMPRESS_FLAC 1
 int mi355vits_set_output_compression(mi355vits_handle h, int mode);
@@ -668,7 +669,9 @@ int mi355vits_get_output_compression(mi355vits_handle h);
  *    trimmed sizes leaves no result served, as mi355vits_run_packed does; mi355vits_fetch_streams before any completed run:
  *    "fetch_streams: no completed run on this handle".
  *  - Out of scope: alignment in stream coordinates (add offsets to mi355vits_fetch_alignment's spans, or use mi355vits_run_packed), and
- *    several output rates in one call (the rate is a property of the run). */
+ *    several output rates in one call (the rate is a property of the run).
+ *  - A limiter window, a ceiling mode or FLAC per stream: mi355vits_run_streams2 / _fetch_streams2 below.  These two calls and their
+ *    structs stay byte for byte what they are. */
 typedef struct mi355vits_stream_args {
     mi355vits_pack_args pack;   /* entries (batch rows), lead / tail silences, wav_header: as for mi355vits_run_packed */
     int32_t encoding;           /* MI355VITS_ENC_* of THIS stream */
@@ -705,6 +708,75 @@ int mi355vits_run_streams(mi355vits_handle h, const mi355vits_run_args* args, co
 /* The LAST completed run of the handle as streams again (whatever flags it had); no synthesis work is repeated. */
 int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out);
 void mi355vits_free_streams(mi355vits_streams_result* r);
+
+/* ---- Streams v2: compression, limiter window and ceiling mode PER STREAM.  The v1 calls above stay byte for byte what they are: they
+ * read the limiter window and the ceiling mode from the handle and never compress.  The v2 calls read NONE of the handle's pack
+ * settings — encoding, trim, target, limiter window, ceiling mode and compression all come from the stream — and change none of them,
+ * so requests that differ in any of the six share one synthesis call and one block.
+ *  - Stream s: bytes[stream_offset[s], + stream_bytes[s]) is BITWISE what mi355vits_fetch_packed returns for streams[s].base.pack on
+ *    the same run with the handle set to that stream's six settings, in every math mode and at the run's output rate: RIFF header and
+ *    pad byte, or the 42 FLAC header bytes, included.  offsets / lengths / peaks / first / lufs / gain / limited / total_samples are
+ *    that call's values, in samples (also for a compressed stream); gain and limited follow the stream's own window and mode (a row the
+ *    limiter takes over reports the uncapped gain, as mi355vits_fetch_loudness does).
+ *  - A compressed stream (MI355VITS_COMPRESS_FLAC) is a complete FLAC file: encoding[s] = MI355VITS_ENC_S16LE, stream_offset[s] a
+ *    multiple of 16, data_offset[s] = stream_offset[s] + 42 (its first frame), stream_bytes[s] = 42 + its frames, frames[s] their count.
+ *  - Block layout: bytes[0, uncompressed_bytes) is byte for byte the block a v1 call over the uncompressed streams alone, in the order
+ *    given, returns (uncompressed_bytes = 0 when there are none).  The compressed streams follow from the next multiple of 16, in the
+ *    order given, each at the next multiple of 16.  Every byte of [0, n_bytes) outside the streams is zero and written by a kernel.
+ *  - With no compressed stream a v2 call IS the v1 call: the same launches, synchronisations and copies, the same block — the limiter
+ *    launches once per distinct (window, mode) among the streams the limiter engages on, so also that is v1's when they agree.
+ *    Windows and modes add no synchronisation; k_true_peak runs iff some stream with a target is in true-peak mode.
+ *  - With at least one compressed stream: exactly ONE stream synchronisation more than the same call with those streams uncompressed
+ *    (the sizes depend on the audio); before it at most 4 * (frames + 4 * n_streams + 1) bytes go to the host; the block then arrives
+ *    in at most two copies of exactly their bytes (the uncompressed part, the compressed part).  k_pack_streams writes the
+ *    uncompressed part and, behind it in the device buffer, every compressed stream's samples as a headerless S16LE stream;
+ *    k_flac_frames runs once over one job per compressed stream; k_flac_place puts every frame and file in its place and makes the
+ *    headers; k_flac_gather_streams writes the compressed region with 16-byte stores.  Profiler: "pack.streams" bytes =
+ *    4 * sum(lengths) + the bytes k_pack_streams writes; "pack.flac" bytes = 2 * sum(total_samples of the compressed streams) +
+ *    sum(stream_bytes - 42).
+ *  - Errors: MI355VITS_ERR_INVALID, naming the stream, found before anything is sized or launched, never partial audio — every v1 rule
+ *    and message for `base`, and "stream 2: unknown compression 7", "stream 1: FLAC compresses the s16le stream; encoding is ulaw",
+ *    "stream 0: a FLAC stream carries its own header", "stream 3: limiter window 5000 is outside 0 .. 4096", "stream 3: unknown
+ *    ceiling mode 9", "stream 0: reserved fields must be 0"; a run's rate above 1,048,575 Hz with any FLAC stream.  The block limit of
+ *    2^31 - 1 bytes counts a compressed stream at its bound, 42 + 16 * frames + 2 * total_samples.
+ *  - After a v2 call every other fetch, v1 mi355vits_fetch_streams included, serves what it serves after a v1 call. */
+typedef struct mi355vits_stream_args2 {
+    mi355vits_stream_args base;      /* every field exactly as in mi355vits_run_streams */
+    int32_t compression;             /* MI355VITS_COMPRESS_* of THIS stream */
+    int32_t limiter_window_samples;  /* 0 = off; rules of mi355vits_set_loudness_limiter */
+    int32_t ceiling_mode;            /* MI355VITS_CEILING_* ; rules of mi355vits_set_loudness_ceiling_mode */
+    int32_t reserved[5];             /* must be 0 */
+} mi355vits_stream_args2;
+
+typedef struct mi355vits_streams_result2 {
+    int32_t n_streams;
+    int32_t n_entries;         /* every field down to `limited`: as in mi355vits_streams_result */
+    uint8_t* bytes;
+    size_t n_bytes;
+    int64_t* stream_offset;
+    int64_t* stream_bytes;
+    int64_t* data_offset;
+    int64_t* total_samples;
+    int32_t* encoding;
+    int32_t* entry_base;
+    int32_t* rows;
+    int64_t* offsets;
+    int64_t* lengths;
+    float* peaks;
+    int32_t* first;
+    double* lufs;
+    double* gain;
+    int32_t* limited;
+    int32_t* compression;      /* [S] MI355VITS_COMPRESS_* of stream s */
+    int32_t* frames;           /* [S] the FLAC frames of stream s; 0 when uncompressed */
+    int64_t uncompressed_bytes; /* the v1 block of the uncompressed streams in front; 0 when there are none */
+    void* owner_;              /* private */
+} mi355vits_streams_result2;
+
+int mi355vits_run_streams2(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                           const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out);
+int mi355vits_fetch_streams2(mi355vits_handle h, const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out);
+void mi355vits_free_streams2(mi355vits_streams_result2* r);
 
 /* Device pointers of the last run's results on this handle (valid until its next run; the engine's stream has been
  * synchronised when this returns): int16 [batch, row_stride] and/or float [batch, row_stride] in HBM, plus the valid

@@ -198,6 +198,13 @@ int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out);
  * the host (pcm & 15).  cap < the file's size: MI355VITS_ERR_INVALID, with *n_bytes = the size needed. */
 int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_frame, uint8_t* out, size_t cap, size_t* n_bytes,
                        int32_t* frame_sizes);
+/* Kernel unit-test hook: SEVERAL files in one block by the three kernels of the streams calls alone (k_flac_frames once over a job per
+ * array, k_flac_place, k_flac_gather_streams; mi355vits_run_streams2): pcm[j] [n[j]] (n[j] >= 0; n_jobs >= 1) at `rate` Hz ->
+ * out[0, *n_bytes) = the block, file j at out[offsets[j], + sizes[j]) with offsets[j] a multiple of 16 (offsets[0] = 0) and every
+ * byte between the files zero.  Every job's frames are numbered from 0.  On the device array j starts as many bytes behind a 16-byte
+ * boundary as pcm[j] does on the host, as in mi355vits_lab_flac.  cap < the block's size: MI355VITS_ERR_INVALID, *n_bytes = the size. */
+int mi355vits_lab_flac_jobs(const int16_t* const* pcm, const long* n, int32_t n_jobs, int32_t rate, uint8_t* out, size_t cap,
+                            size_t* n_bytes, int64_t* offsets, int64_t* sizes);
 /* Kernel micro-benchmark hook (tools/convbench.py): times `reps` launches of one MFMA Conv1d on random device data.
  * epi: 0 = standard epilogue (bias + residual), 1 = WaveNet gate (Cout = 2*H), 2 = res/skip.  (The tile-shape overrides
  * MI355VITS_CONV_CFG / MI355VITS_CONV_CHUNK exist in the lab build of the library only, csrc/hipx.h lab_getenv.) */

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "mi355vits_set_edge_trim", "mi355vits_get_edge_trim", "mi355vits_fetch_edges", "mi355vits_free_edges",
     "mi355vits_set_loudness_target", "mi355vits_get_loudness_target", "mi355vits_fetch_loudness", "mi355vits_free_loudness",
     "mi355vits_run_streams", "mi355vits_fetch_streams", "mi355vits_free_streams",
+    "mi355vits_run_streams2", "mi355vits_fetch_streams2", "mi355vits_free_streams2",
     "mi355vits_set_loudness_limiter", "mi355vits_get_loudness_limiter", "mi355vits_fetch_limiter", "mi355vits_free_limiter",
     "mi355vits_set_loudness_ceiling_mode", "mi355vits_get_loudness_ceiling_mode", "mi355vits_fetch_true_peak", "mi355vits_free_true_peak",
 )
@@ -52,7 +53,7 @@ LAB_SYMBOLS = (
     "mi355vits_test_rel_attention", "mi355vits_test_fill_workspace", "mi355vits_test_resample",
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
-    "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac",
+    "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
 )
 
@@ -177,6 +178,25 @@ class StreamsResult(ctypes.Structure):
         ("lufs", ctypes.POINTER(ctypes.c_double)),
         ("gain", ctypes.POINTER(ctypes.c_double)),
         ("limited", ctypes.POINTER(ctypes.c_int32)),
+        ("owner_", ctypes.c_void_p),
+    ]
+
+
+class StreamArgs2(ctypes.Structure):
+    _fields_ = [
+        ("base", StreamArgs),
+        ("compression", ctypes.c_int32),
+        ("limiter_window_samples", ctypes.c_int32),
+        ("ceiling_mode", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 5),
+    ]
+
+
+class StreamsResult2(ctypes.Structure):
+    _fields_ = StreamsResult._fields_[:-1] + [
+        ("compression", ctypes.POINTER(ctypes.c_int32)),
+        ("frames", ctypes.POINTER(ctypes.c_int32)),
+        ("uncompressed_bytes", ctypes.c_int64),
         ("owner_", ctypes.c_void_p),
     ]
 
@@ -428,6 +448,11 @@ class NativeLibrary:
         L.mi355vits_fetch_streams.argtypes = [H, ctypes.POINTER(StreamArgs), ctypes.c_int32, ctypes.POINTER(StreamsResult)]
         L.mi355vits_free_streams.argtypes = [ctypes.POINTER(StreamsResult)]
         L.mi355vits_free_streams.restype = None
+        L.mi355vits_run_streams2.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(StreamArgs2), ctypes.c_int32,
+                                             ctypes.POINTER(StreamsResult2)]
+        L.mi355vits_fetch_streams2.argtypes = [H, ctypes.POINTER(StreamArgs2), ctypes.c_int32, ctypes.POINTER(StreamsResult2)]
+        L.mi355vits_free_streams2.argtypes = [ctypes.POINTER(StreamsResult2)]
+        L.mi355vits_free_streams2.restype = None
         L.mi355vits_fetch_alignment.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.argtypes = [ctypes.POINTER(AlignmentResult)]
         L.mi355vits_free_alignment.restype = None
@@ -492,6 +517,9 @@ class NativeLibrary:
             i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
             L.mi355vits_lab_flac.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8),
                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), i32p]
+            L.mi355vits_lab_flac_jobs.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long), ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
             L.mi355vits_lab_edges.argtypes = [f32p, ctypes.c_long, i32p, f32p, ctypes.c_int, ctypes.c_float, i32p, i32p]
             L.mi355vits_lab_loudness.argtypes = [f32p, ctypes.c_long, i32p, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), i32p, i32p]
             L.mi355vits_lab_loudness_plan.argtypes = [ctypes.c_int32, i32p, i32p, i32p]
@@ -555,6 +583,31 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return out[: int(got.value)].tobytes(), sizes[:frames].copy()
+
+    def lab_flac_jobs(self, arrays, rate: int):
+        """SEVERAL int16 arrays as FLAC files in ONE block by the kernels of the streams calls alone (``mi355vits_lab_flac_jobs``):
+        -> (the block uint8, offsets int64 [J] — multiples of 16 —, sizes int64 [J]); file j = block[offsets[j] : offsets[j] + sizes[j]].
+        A contiguous 1-d int16 array is read where it is, as ``lab_flac`` reads it."""
+        self._need_hooks()
+        xs = []
+        for a in arrays:
+            x = np.asarray(a)
+            if x.dtype != np.int16 or x.ndim != 1 or not x.flags.c_contiguous:
+                x = np.ascontiguousarray(a, np.int16).reshape(-1)
+            xs.append(x)
+        J = len(xs)
+        ptrs = (ctypes.c_void_p * max(J, 1))(*[x.ctypes.data for x in xs])
+        ns = (ctypes.c_long * max(J, 1))(*[int(x.shape[0]) for x in xs])
+        cap = sum(((42 + 16 * ((int(x.shape[0]) + 4095) // 4096) + 2 * int(x.shape[0]) + 15) & ~15) for x in xs) + 16
+        out = np.empty(cap, np.uint8)
+        offsets, sizes = np.zeros(max(J, 1), np.int64), np.zeros(max(J, 1), np.int64)
+        got = ctypes.c_size_t(0)
+        rc = self.lib.mi355vits_lab_flac_jobs(ptrs, ns, J, int(rate), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, ctypes.byref(got),
+                                              offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                              sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out[: int(got.value)].copy(), offsets[:J].copy(), sizes[:J].copy()
 
     def lab_edges(self, audio, lengths, peaks, ratio):
         """The edge kernel (k_edges) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is never
@@ -958,10 +1011,11 @@ class _PackedHolder:
 class _StreamsHolder:
     """The same for one ``mi355vits_streams_result``: ONE pinned block shared by the views of all its streams."""
 
-    def __init__(self, native: "NativeLibrary", r: StreamsResult):
+    def __init__(self, native: "NativeLibrary", r):
         self._native = native
-        self._r = StreamsResult()
-        ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(StreamsResult))
+        self._r = type(r)()  # StreamsResult, or StreamsResult2 (mi355vits_free_streams2)
+        ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(type(r)))
+        self._free = native.lib.mi355vits_free_streams2 if isinstance(r, StreamsResult2) else native.lib.mi355vits_free_streams
 
     def view(self) -> np.ndarray:
         """Every byte of the block as one uint8 array that owns the holder."""
@@ -972,7 +1026,7 @@ class _StreamsHolder:
 
     def __del__(self):
         try:
-            self._native.lib.mi355vits_free_streams(ctypes.byref(self._r))
+            self._free(ctypes.byref(self._r))
         except Exception:
             pass
 
@@ -1248,9 +1302,12 @@ class Engine:
     def _stream_args(streams, batch: int):
         """A list of stream dicts — ``order`` (default: every row), ``lead_samples``, ``tail_samples``, ``wav``, ``encoding``
         (default "s16le"), ``trim=(ratio, keep_samples)``, ``loudness=(lufs, ceiling_db)`` — as an array of
-        ``mi355vits_stream_args``, their count, what the array points into, and (trimmed, normalised) per stream."""
-        known = {"order", "lead_samples", "tail_samples", "wav", "encoding", "trim", "loudness"}
+        ``mi355vits_stream_args``, their count, what the array points into, and (trimmed, normalised) per stream.  With any of
+        ``compression`` / ``limiter`` / ``true_peak`` in any dict: an array of ``mi355vits_stream_args2``."""
+        known = {"order", "lead_samples", "tail_samples", "wav", "encoding", "trim", "loudness"} | Engine._STREAM_KEYS2
         streams = list(streams)
+        v2 = any(not Engine._STREAM_KEYS2.isdisjoint(st) for st in streams)  # any of the v2 keys: mi355vits_stream_args2, the v2 entry
+        arr2 = (StreamArgs2 * max(1, len(streams)))() if v2 else None
         arr, keep, flags = (StreamArgs * max(1, len(streams)))(), [], []
         for i, st in enumerate(streams):
             if set(st) - known:
@@ -1262,7 +1319,7 @@ class Engine:
             if p.n < 0:
                 p.n = int(batch)
             keep.append(pkeep)
-            a = arr[i]
+            a = arr2[i].base if v2 else arr[i]
             a.pack = p
             a.encoding = encoding_id(st.get("encoding") or "s16le")
             ratio, tkeep = st.get("trim") or (0.0, 0)
@@ -1270,7 +1327,13 @@ class Engine:
             lufs, ceiling = st.get("loudness") or (0.0, -1.0)
             a.target_lufs, a.ceiling_dbfs = float(lufs or 0.0), float(-1.0 if ceiling is None else ceiling)
             flags.append((a.trim_ratio != 0.0, a.target_lufs != 0.0))
-        return arr, len(streams), keep, flags
+            if v2:
+                arr2[i].compression = compression_id(st.get("compression"))
+                arr2[i].limiter_window_samples = int(st.get("limiter") or 0)
+                arr2[i].ceiling_mode = 1 if st.get("true_peak") else 0
+        return (arr2 if v2 else arr), len(streams), keep, flags
+
+    _STREAM_KEYS2 = frozenset({"compression", "limiter", "true_peak"})
 
     def run_streams(self, ids, lengths, scales, sid=None, *, streams, seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None,
                     forced_durations=None, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> List["PackedAudio"]:
@@ -1278,14 +1341,21 @@ class Engine:
         (the batch rows of the stream; default: all), ``lead_samples``, ``tail_samples``, ``wav``, ``encoding``, ``trim=(ratio,
         keep_samples)``, ``loudness=(lufs, ceiling_db)``.  Stream s is bitwise ``fetch_packed`` of the same pack with the handle set to
         that stream's encoding, trim and target; the handle's own settings are neither read nor changed.  One kernel writes all
-        streams into one pinned block, one device-to-host copy brings it; the ``PackedAudio`` returned per stream are views of it."""
+        streams into one pinned block, one device-to-host copy brings it; the ``PackedAudio`` returned per stream are views of it.
+        If ANY dict has one of the keys ``compression`` (``"flac"`` / ``None``), ``limiter`` (the limiter window in samples, 0 = off)
+        or ``true_peak`` (bool), the call is ``mi355vits_run_streams2``: those three come from each stream as well (absent = off) and
+        the handle's limiter window and ceiling mode are not read either.  A compressed stream's ``PackedAudio`` has
+        ``compression == "flac"``, ``flac`` = a view of its file in the shared block and ``data`` / ``rows`` / ``wav`` = ``None``;
+        every stream of such a call (and of no other) also carries ``frames`` and ``uncompressed_bytes`` (the v1 block of the uncompressed streams,
+        which come first in the block)."""
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = DEBUG_TAPS if debug_taps else 0
         arr, n, skeep, flags = self._stream_args(streams, int(a.batch))
-        r = StreamsResult()
-        self._check(self.native.lib.mi355vits_run_streams(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None, arr, n,
-                                                          ctypes.byref(r)))
+        v2 = isinstance(arr[0], StreamArgs2)
+        r = StreamsResult2() if v2 else StreamsResult()
+        call = self.native.lib.mi355vits_run_streams2 if v2 else self.native.lib.mi355vits_run_streams
+        self._check(call(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None, arr, n, ctypes.byref(r)))
         del keep, skeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate
@@ -1294,12 +1364,13 @@ class Engine:
     def fetch_streams(self, streams) -> List["PackedAudio"]:
         """The last completed run of this handle as streams again (``mi355vits_fetch_streams``); nothing is synthesised again."""
         arr, n, skeep, flags = self._stream_args(streams, self._last_batch)
-        r = StreamsResult()
-        self._check(self.native.lib.mi355vits_fetch_streams(self._h, arr, n, ctypes.byref(r)))
+        v2 = isinstance(arr[0], StreamArgs2)
+        r = StreamsResult2() if v2 else StreamsResult()
+        self._check((self.native.lib.mi355vits_fetch_streams2 if v2 else self.native.lib.mi355vits_fetch_streams)(self._h, arr, n, ctypes.byref(r)))
         del skeep
         return self._take_streams(r, flags)
 
-    def _take_streams(self, r: StreamsResult, flags) -> List["PackedAudio"]:
+    def _take_streams(self, r, flags) -> List["PackedAudio"]:
         """``flags[s]`` = (trimmed, normalised) of stream s: which of ``first`` / ``end`` and ``lufs`` / ``gain`` / ``limited`` it fills."""
         S, E = int(r.n_streams), int(r.n_entries)
         try:
@@ -1309,8 +1380,12 @@ class Engine:
             base = np.ctypeslib.as_array(r.entry_base, shape=(S + 1,)).copy()
             offsets, lens, peaks, first = (per_entry(p) for p in (r.offsets, r.lengths, r.peaks, r.first))
             lufs, gain, limited = per_entry(r.lufs), per_entry(r.gain), per_entry(r.limited).astype(bool)
+            v2 = isinstance(r, StreamsResult2)
+            comps = per_stream(r.compression) if v2 else np.zeros(S, np.int32)
+            nframes = per_stream(r.frames) if v2 else np.zeros(S, np.int32)
+            plain_bytes = int(r.uncompressed_bytes) if v2 else int(r.n_bytes)
         except BaseException:
-            self.native.lib.mi355vits_free_streams(ctypes.byref(r))
+            (self.native.lib.mi355vits_free_streams2 if isinstance(r, StreamsResult2) else self.native.lib.mi355vits_free_streams)(ctypes.byref(r))
             raise
         block = _StreamsHolder(self.native, r).view()  # the views below keep the block alive: no per-stream copy
         out = []
@@ -1319,13 +1394,18 @@ class Engine:
             dtype = np.dtype(ENCODINGS[enc][1])
             e0, e1 = int(base[s]), int(base[s + 1])
             d0 = int(data_at[s])
-            pcm = block[d0: d0 + dtype.itemsize * int(totals[s])].view(dtype)
-            wav = memoryview(block[int(begin[s]): int(begin[s]) + int(nbytes[s])]) if d0 != int(begin[s]) else None
+            flac = int(comps[s]) == 1
+            whole = memoryview(block[int(begin[s]): int(begin[s]) + int(nbytes[s])]) if (flac or d0 != int(begin[s])) else None
+            pcm = None if flac else block[d0: d0 + dtype.itemsize * int(totals[s])].view(dtype)
+            wav = None if flac else whole
             trimmed, normalised = flags[s]
             out.append(PackedAudio(pcm, offsets[e0:e1], lens[e0:e1], peaks[e0:e1], wav, self._last_rate, enc,
                                    first[e0:e1] if trimmed else None, first[e0:e1] + lens[e0:e1].astype(first.dtype) if trimmed else None,
                                    lufs[e0:e1] if normalised else None, gain[e0:e1] if normalised else None,
-                                   limited[e0:e1] if normalised else None))
+                                   limited[e0:e1] if normalised else None, "flac" if flac else None, whole if flac else None,
+                                   int(totals[s])))
+            if v2:
+                out[-1].frames, out[-1].uncompressed_bytes = int(nframes[s]), plain_bytes
             # where the stream sits in the block all streams of the call share
             out[-1].block, out[-1].stream_offset, out[-1].stream_bytes, out[-1].data_offset = block, int(begin[s]), int(nbytes[s]), d0
         return out

@@ -202,6 +202,20 @@ int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* str
 
 void mi355vits_free_streams(mi355vits_streams_result* r) { free_struct(r); }
 
+int mi355vits_run_streams2(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                           const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {
+    return result_call(h, out, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        h->eng->run_streams2(*args, rows, streams, n_streams, out);
+    });
+}
+
+int mi355vits_fetch_streams2(mi355vits_handle h, const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {
+    return result_call(h, out, [&] { h->eng->fetch_streams2(streams, n_streams, out); });
+}
+
+void mi355vits_free_streams2(mi355vits_streams_result2* r) { free_struct(r); }
+
 int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out) {
     return result_call(h, out, [&] { h->eng->fetch_alignment(want, out); });
 }

@@ -157,7 +157,7 @@ struct PackSettings {
     float loud_target = 0.0f, loud_ceiling = -1.0f;  // mi355vits_set_loudness_target: target 0 = off
     int limit_window = 0;        // mi355vits_set_loudness_limiter: samples at the run's rate, 0 = off; acts on packs with a target only
     int ceil_mode = 0;           // mi355vits_set_loudness_ceiling_mode: MI355VITS_CEILING_*; acts on packs with a target only
-    int compress = 0;            // mi355vits_set_output_compression: MI355VITS_COMPRESS_*; single packs only (a streams call never reads it)
+    int compress = 0;            // mi355vits_set_output_compression: MI355VITS_COMPRESS_*; single packs (a v1 streams call never reads it; a v2 stream brings its own)
     bool trimmed() const { return trim_ratio != 0.0f; }
     bool normalised() const { return loud_target != 0.0f; }
     bool limiting() const { return normalised() && limit_window > 0; }
@@ -191,6 +191,11 @@ class Engine {
     void run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
                      mi355vits_streams_result* out);
     void fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out);
+    // the same with compression, limiter window and ceiling mode per stream (mi355vits_run_streams2 / mi355vits_fetch_streams2): NONE
+    // of the handle's pack settings is read
+    void run_streams2(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args2* streams, int n_streams,
+                      mi355vits_streams_result2* out);
+    void fetch_streams2(const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out);
     // phoneme timing (and, with MI355VITS_ALIGN_LEVELS, levels) of the last completed run (mi355vits_fetch_alignment)
     void fetch_alignment(uint32_t want, mi355vits_alignment* out);
     // edge trimming of the packed streams (mi355vits_set_edge_trim): ratio 0 = off.  Read when a pack is made and at fetch_edges.
@@ -296,9 +301,25 @@ class Engine {
     struct StreamsPlan {
         std::vector<PackPlan> streams;
         std::vector<int64_t> begin, data;  // block byte offset of each stream's first byte (its header) / first data byte (16-byte aligned)
-        int64_t n_bytes = 0, audio = 0;    // the block; the audio samples in it
+        int64_t n_bytes = 0, audio = 0;    // what k_pack_streams writes (without a compressed stream: the block); the audio samples in it
         int entries = 0;
         bool curved = false;               // the limiter engages on some entry: the table has its curve row
+        // v2 with compressed streams.  k_pack_streams' buffer holds the uncompressed streams exactly as v1 lays them
+        // out — [0, plain_bytes) —, then from the next multiple of 16 every compressed stream's samples as a headerless S16LE stream
+        // (src[s], 16-byte aligned): the streams in `dev` order.  begin / data of a compressed stream are known once its sizes are.
+        std::vector<int> dev;              // the streams in the order of their places in k_pack_streams' buffer
+        std::vector<int64_t> src;          // compressed streams: where their samples sit in that buffer (else -1)
+        std::vector<long> frames;          // compressed streams: their FLAC frames (else 0)
+        int64_t plain_bytes = 0;           // R: the v1 block of the uncompressed streams
+        int64_t flac_base = 0, flac_bound = 0;  // (R + 15) & ~15; the bound of the bytes behind it
+        long n_frames = 0;                 // of all compressed streams
+        int n_flac = 0;
+        bool compressed() const { return n_flac > 0; }  // (after place_streams)
+        bool compressed_planned() const {                // some stream asks for FLAC (from plan_streams on)
+            for (const PackPlan& p : streams)
+                if (p.set.flac()) return true;
+            return false;
+        }
         bool measured() const {            // some stream trims or normalises: the places depend on the audio
             for (const PackPlan& p : streams)
                 if (p.set.trimmed() || p.set.normalised()) return true;
@@ -308,6 +329,18 @@ class Engine {
     template <typename A> void layout_streams(A& ar, const StreamsPlan& sp) {
         d_pack_seg_ = ar.template alloc<int>(pack_streams_table_words(sp.entries, (int)sp.streams.size(), sp.curved));
         d_pack_ = ar.template alloc<uint8_t>(pack_streams_capacity((long)sp.n_bytes));
+        if (!sp.compressed()) return;
+        // behind it: a job per compressed stream, a slot per frame, the words the host reads (sizes, FLAC_INFO_* per job, the block's
+        // end), the scan and the frames' places, the headers, and the compressed region of the block
+        d_flac_jobs_ = ar.template alloc<FlacJob>((size_t)sp.n_flac);
+        d_flac_slots_ = ar.template alloc<uint8_t>((size_t)sp.n_frames * FLAC_SLOT_BYTES + 16);
+        d_flac_sizes_ = ar.template alloc<int>(flac_info_words(sp.n_frames, sp.n_flac));
+        d_flac_pre_ = ar.template alloc<unsigned>((size_t)sp.n_frames + 1);
+        d_flac_ftab_ = ar.template alloc<int2>((size_t)sp.n_frames + 1);
+        d_flac_hdr_ = ar.template alloc<unsigned>((size_t)FLAC_HDR_WORDS * sp.n_flac);
+        d_flac_items_ = ar.template alloc<int>(flac_gather_items((long)sp.flac_bound));
+        d_flac_jtab_ = ar.template alloc<int>((size_t)FLAC_JTAB_ROWS * sp.n_flac);
+        d_flac_out_ = ar.template alloc<uint8_t>((size_t)sp.flac_bound + 16);
     }
     // Packed calls only: the plan's segment table and stream, behind everything layout_b placed — no other pointer moves, so a
     // call that packs nothing runs on the layout it always had.
@@ -338,12 +371,17 @@ class Engine {
     void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [plan.seg_rows()][n] (kernels.h: PACK_SEG_*)
     void launch_pack(const PackPlan& plan);
     void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
-    void plan_streams(const mi355vits_stream_args* streams, int n_streams, int B, StreamsPlan& sp) const;  // validates every stream, naming it
+    // validates every stream, naming it (v1's streams arrive as v2 ones carrying the handle's window and mode, uncompressed)
+    void plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, StreamsPlan& sp) const;
+    std::vector<mi355vits_stream_args2> streams_v1(const mi355vits_stream_args* streams, int n_streams) const;
     void place_streams(StreamsPlan& sp) const;                          // place_pack per stream, then the block's layout and its limit
     void fill_streams_table(const StreamsPlan& sp, int* tab) const;     // kernels.h: PACK_ENT_* / PACK_STREAM_*
     void launch_streams(const StreamsPlan& sp);
-    void streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out);  // fetch_streams behind its checks; the second half of a measured run_streams
-    void copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out);
+    // fetch_streams behind its checks; the second half of a measured run_streams (R: mi355vits_streams_result or mi355vits_streams_result2)
+    template <typename R> void streams_last_run(StreamsPlan& sp, R* out);
+    template <typename R> void copy_out_streams(StreamsPlan& sp, R* out);
+    template <typename R> void run_streams_plan(const mi355vits_run_args& args, const mi355vits_row_args* rows, StreamsPlan& sp, R* out);
+    void launch_flac_streams(const StreamsPlan& sp);  // the compressed streams' samples in d_pack_ -> frames, places, d_flac_out_
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
     void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
     void launch_flac(const PackPlan& plan);  // the stream at d_pack_ -> frames, sizes, d_flac_out_
@@ -363,10 +401,18 @@ class Engine {
     // The limiter's jobs of a pack / a block / a fetch_limiter.  limit_job: the job of (row, set's target, ceiling and encoding
     // class) among `jobs`, appended when new.  run_limit_jobs: the jobs placed (their offsets checked before anything is sized),
     // uploaded and k_limit launched in `arena`; with_curve: d_curve_ = the curves, else statistics only.  Returns the device statistics.
-    int limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g) const;
+    // keys (a streams call): the (window, true-peak mode) of every job, part of its identity
+    using LimitKeys = std::vector<std::pair<int, int>>;
+    int limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g, LimitKeys* keys = nullptr) const;
+    // the jobs of a streams call: one k_limit launch per distinct key over one layout of curves (one key: run_limit_jobs itself)
+    void run_limit_groups(std::vector<LimitJob>& jobs, const LimitKeys& keys);
+    // what both end in: the placed jobs in one layout in `arena`, one upload, the launches of every group
+    struct LimitGroup { size_t first, n; long tiles, floats; int window; bool tp; };
+    LimitStat* launch_limit_groups(const std::vector<LimitJob>& placed, const std::vector<LimitGroup>& groups, long floats, DeviceArena& arena,
+                                   bool with_curve);
     // true_peak: k_true_peak_env writes the jobs' envelopes into the same arena first and k_limit reads them instead of the samples
     LimitStat* run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve, bool true_peak);
-    void limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const;  // plan.curve = each over entry's job (after place_pack)
+    void limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs, LimitKeys* keys = nullptr) const;  // plan.curve = each over entry's job (after place_pack)
     static void curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs);  // plan.curve: jobs -> their placed offsets
 
     mi355vits_config cfg_{};
@@ -477,6 +523,10 @@ class Engine {
     int* d_flac_sizes_ = nullptr;
     long long* d_flac_offsets_ = nullptr;
     FlacJob h_flac_job_{};            // its own upload: a member outlives the copy
+    std::vector<FlacJob> h_flac_jobs_;  // a streams call's jobs, likewise
+    unsigned *d_flac_pre_ = nullptr, *d_flac_hdr_ = nullptr;  // streams calls only (layout_streams)
+    int2* d_flac_ftab_ = nullptr;
+    int *d_flac_items_ = nullptr, *d_flac_jtab_ = nullptr;
     std::vector<int> h_flac_sizes_;   // the frame sizes and their total, as copied
     int flac_prof_rec_ = -1;          // the profiler's record of the pack.flac launches under way: its bytes are known after the sizes
 };

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace m355 {
 
@@ -509,13 +510,26 @@ constexpr int64_t STREAMS_MAX_BYTES = 0x7fffffffLL;  // the block's offsets fit 
 }  // namespace
 
 // Everything that can be wrong with the arguments alone: each stream's settings by the rules of the setters, its pack by plan_pack's.
-void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, int B, StreamsPlan& sp) const {
+std::vector<mi355vits_stream_args2> Engine::streams_v1(const mi355vits_stream_args* streams, int n_streams) const {
+    std::vector<mi355vits_stream_args2> v((streams && n_streams > 0) ? (size_t)n_streams : 0);
+    for (size_t s = 0; s < v.size(); ++s) {
+        memset(&v[s], 0, sizeof(v[s]));
+        v[s].base = streams[s];
+        v[s].compression = MI355VITS_COMPRESS_NONE;
+        v[s].limiter_window_samples = pack_.limit_window;  // the handle settings a v1 streams call reads: mi355vits_stream_args is frozen
+        v[s].ceiling_mode = pack_.ceil_mode;
+    }
+    return v;
+}
+
+void Engine::plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, StreamsPlan& sp) const {
     if (!streams || n_streams < 1)
         throw EngineError(MI355VITS_ERR_INVALID, "streams: a non-null array of n_streams >= 1 streams is required (n_streams = " + std::to_string(n_streams) + ")");
     sp.streams.assign((size_t)n_streams, PackPlan());
     sp.entries = 0;
     for (int s = 0; s < n_streams; ++s) {
-        const mi355vits_stream_args& a = streams[s];
+        const mi355vits_stream_args2& a2 = streams[s];
+        const mi355vits_stream_args& a = a2.base;
         const std::string name = "stream " + std::to_string(s) + ": ";
         auto bad = [&](const std::string& what) { return EngineError(MI355VITS_ERR_INVALID, name + what); };
         if (a.encoding != MI355VITS_ENC_S16LE && a.encoding != MI355VITS_ENC_ULAW && a.encoding != MI355VITS_ENC_ALAW && a.encoding != MI355VITS_ENC_F32LE)
@@ -526,14 +540,28 @@ void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, i
             throw bad("loudness target " + fmt_g(a.target_lufs) + " LUFS is neither 0 (off) nor in [-70, 0)");
         if (a.target_lufs != 0.0f && !(std::isfinite(a.ceiling_dbfs) && a.ceiling_dbfs <= 0.0f))
             throw bad("loudness ceiling " + fmt_g(a.ceiling_dbfs) + " dBFS is not a finite value <= 0");
+        if (a2.compression != MI355VITS_COMPRESS_NONE && a2.compression != MI355VITS_COMPRESS_FLAC)
+            throw bad("unknown compression " + std::to_string(a2.compression) + " (0 = none, 1 = flac)");
+        if (a2.limiter_window_samples < 0 || a2.limiter_window_samples > LIMIT_MAX_WINDOW)
+            throw bad("limiter window " + std::to_string(a2.limiter_window_samples) + " is outside 0 .. " + std::to_string(LIMIT_MAX_WINDOW));
+        if (a2.ceiling_mode != MI355VITS_CEILING_SAMPLE && a2.ceiling_mode != MI355VITS_CEILING_TRUE_PEAK)
+            throw bad("unknown ceiling mode " + std::to_string(a2.ceiling_mode) + " (0 = sample peak, 1 = true peak)");
+        for (int r : a2.reserved)
+            if (r != 0) throw bad("reserved fields must be 0");
+        if (a2.compression == MI355VITS_COMPRESS_FLAC) {
+            static const char* const enc_names[] = {"s16le", "ulaw", "alaw", "f32le"};  // by PackEncoding
+            if (a.encoding != MI355VITS_ENC_S16LE) throw bad(std::string("FLAC compresses the s16le stream; encoding is ") + enc_names[a.encoding]);
+            if (a.pack.wav_header != 0) throw bad("a FLAC stream carries its own header (wav_header must be 0)");
+        }
         PackSettings set;
         set.enc = a.encoding;
         set.trim_ratio = a.trim_ratio;
         set.trim_keep = a.trim_keep_samples;
         set.loud_target = a.target_lufs;
         if (a.target_lufs != 0.0f) set.loud_ceiling = a.ceiling_dbfs;
-        set.limit_window = pack_.limit_window;  // the handle settings a streams call reads: mi355vits_stream_args is frozen
-        set.ceil_mode = pack_.ceil_mode;
+        set.limit_window = a2.limiter_window_samples;
+        set.ceil_mode = a2.ceiling_mode;
+        set.compress = a2.compression;
         try {
             plan_pack(&a.pack, B, set, sp.streams[s]);
         } catch (const EngineError& e) {
@@ -547,9 +575,15 @@ void Engine::plan_streams(const mi355vits_stream_args* streams, int n_streams, i
 // leaves room for its header, the header right in front of it, the RIFF pad byte behind an odd data size.
 void Engine::place_streams(StreamsPlan& sp) const {
     const size_t S = sp.streams.size();
-    sp.begin.resize(S);
-    sp.data.resize(S);
+    sp.begin.assign(S, 0);
+    sp.data.assign(S, 0);
+    sp.src.assign(S, -1);
+    sp.frames.assign(S, 0);
+    sp.dev.clear();
     sp.audio = 0;
+    sp.n_flac = 0;
+    sp.n_frames = 0;
+    std::vector<int> flac;
     int64_t pos = 0;
     for (size_t s = 0; s < S; ++s) {
         PackPlan& p = sp.streams[s];
@@ -558,29 +592,57 @@ void Engine::place_streams(StreamsPlan& sp) const {
         } catch (const EngineError& e) {
             throw EngineError(e.code, "stream " + std::to_string(s) + ": " + e.what());
         }
+        sp.audio += p.audio;
+        if (p.set.flac()) {
+            flac.push_back((int)s);  // behind the uncompressed streams, below
+            continue;
+        }
         const int64_t hdr = (int64_t)p.header_bytes(), bytes = (int64_t)p.bps() * p.total;
         sp.data[s] = (pos + hdr + 15) & ~int64_t(15);
         sp.begin[s] = sp.data[s] - hdr;
         pos = sp.data[s] + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
-        sp.audio += p.audio;
+        sp.dev.push_back((int)s);
         if (pos > STREAMS_MAX_BYTES) {
             // (what the remaining streams add only makes it larger: the size named is the block up to this stream)
             throw EngineError(MI355VITS_ERR_INVALID, "streams: block of " + std::to_string(pos) + " bytes exceeds 2^31 - 1");
         }
     }
-    sp.n_bytes = pos;
+    sp.plain_bytes = sp.n_bytes = pos;
+    sp.flac_base = sp.flac_bound = 0;
+    if (flac.empty()) return;
+    // the compressed streams: their samples behind the uncompressed block, each at a multiple of 16; the block counted with every
+    // file at its bound
+    sp.flac_base = (pos + 15) & ~int64_t(15);
+    int64_t at = sp.flac_base, bound = sp.flac_base;
+    for (int s : flac) {
+        const PackPlan& p = sp.streams[(size_t)s];
+        sp.src[(size_t)s] = at;
+        sp.frames[(size_t)s] = flac_frames((long)p.total);
+        sp.n_frames += sp.frames[(size_t)s];
+        sp.dev.push_back(s);
+        sp.n_bytes = at + 2 * p.total;
+        at = (sp.n_bytes + 15) & ~int64_t(15);
+        bound += flac_file_bound((long)p.total);
+        if (bound > STREAMS_MAX_BYTES || at > STREAMS_MAX_BYTES)
+            throw EngineError(MI355VITS_ERR_INVALID, "streams: block of " + std::to_string(std::max(bound, at)) + " bytes exceeds 2^31 - 1 (a FLAC stream counted at its bound)");
+    }
+    sp.n_flac = (int)flac.size();
+    sp.flac_bound = bound - sp.flac_base;
 }
 
 void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
     const size_t n = (size_t)sp.entries;
     int* st = tab + pack_ent_rows(sp.curved) * n;
     size_t e = 0;
-    for (size_t s = 0; s < sp.streams.size(); ++s) {
+    for (size_t d = 0; d < sp.dev.size(); ++d) {
+        const size_t s = (size_t)sp.dev[d];  // in the order of their places (without a compressed stream: the order given)
         const PackPlan& p = sp.streams[s];
         const PackSettings& set = p.set;
         const int64_t bytes = (int64_t)p.bps() * p.total;
+        // (a compressed stream: its samples as a headerless S16LE stream, k_flac_frames' source)
+        const int64_t data = set.flac() ? sp.src[s] : sp.data[s], begin = set.flac() ? sp.src[s] : sp.begin[s];
         for (int i = 0; i < p.n; ++i, ++e) {
-            tab[PACK_ENT_OFFSET * n + e] = (int)(sp.data[s] + (int64_t)p.bps() * p.offsets[i]);
+            tab[PACK_ENT_OFFSET * n + e] = (int)(data + (int64_t)p.bps() * p.offsets[i]);
             tab[PACK_ENT_ROW * n + e] = p.order[i];
             tab[PACK_ENT_LENGTH * n + e] = (int)p.lengths[i];
             tab[PACK_ENT_SKIP * n + e] = set.trimmed() ? p.skip[i] : 0;
@@ -591,10 +653,10 @@ void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
             if (set.normalised()) scale = set.enc == PACK_ENC_F32 ? (float)p.gain[i] : (float)(32767.0 * p.gain[i]);
             memcpy(&tab[PACK_ENT_SCALE * n + e], &scale, 4);
         }
-        int* r = st + PACK_STREAM_WORDS * s;
-        r[PACK_STREAM_BEGIN] = (int)sp.begin[s];
-        r[PACK_STREAM_DATA] = (int)sp.data[s];
-        r[PACK_STREAM_END] = (int)(sp.data[s] + bytes);
+        int* r = st + PACK_STREAM_WORDS * d;
+        r[PACK_STREAM_BEGIN] = (int)begin;
+        r[PACK_STREAM_DATA] = (int)data;
+        r[PACK_STREAM_END] = (int)(data + bytes);
         r[PACK_STREAM_ENC] = set.enc;
         uint8_t h[4 * (PACK_STREAM_WORDS - PACK_STREAM_HEADER)] = {0};
         if (p.wav) write_wav_header(h, set.enc, (uint32_t)run_hz_, p.total, (size_t)bytes, false);  // the rate the run ran at
@@ -609,7 +671,31 @@ void Engine::launch_streams(const StreamsPlan& sp) {
                         sp.curved ? d_curve_ : nullptr);
 }
 
-void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* out) {
+// The compressed streams of a block: a job per stream over its samples in k_pack_streams' buffer, k_flac_frames once over all of them,
+// the places and headers (k_flac_place), the compressed region (k_flac_gather_streams).  One profiler record.
+void Engine::launch_flac_streams(const StreamsPlan& sp) {
+    h_flac_jobs_.clear();
+    double samples = 0;
+    long slot0 = 0;
+    for (int s : sp.dev) {
+        const PackPlan& p = sp.streams[(size_t)s];
+        if (!p.set.flac()) continue;
+        h_flac_jobs_.push_back(FlacJob{reinterpret_cast<const int16_t*>(d_pack_ + sp.src[(size_t)s]), (long)p.total, 0, (int)slot0});
+        slot0 += sp.frames[(size_t)s];
+        samples += (double)p.total;
+    }
+    HIP_CHECK(hipMemcpyAsync(d_flac_jobs_, h_flac_jobs_.data(), sizeof(FlacJob) * h_flac_jobs_.size(), hipMemcpyHostToDevice, stream_));
+    ProfScope ps(prof_, "pack.flac", 0, 2.0 * samples);  // + the frames' bytes once the host knows them (copy_out_streams)
+    flac_prof_rec_ = ps.rec;
+    launch_flac_frames(d_flac_jobs_, sp.n_flac, sp.n_frames, run_hz_, d_flac_slots_, d_flac_sizes_, stream_);
+    launch_flac_place(d_flac_jobs_, sp.n_flac, sp.n_frames, run_hz_, (long)sp.flac_base, d_flac_sizes_, d_flac_pre_, d_flac_ftab_, d_flac_hdr_,
+                      d_flac_items_, d_flac_jtab_, stream_);
+    launch_flac_gather_streams(sp.n_flac, sp.n_frames, d_flac_slots_, d_flac_sizes_, d_flac_ftab_, d_flac_hdr_, d_flac_items_, (long)sp.flac_base,
+                               (long)sp.flac_bound, d_flac_out_, stream_);
+}
+
+template <typename R> void Engine::copy_out_streams(StreamsPlan& sp, R* out) {
+    constexpr bool V2 = std::is_same<R, mi355vits_streams_result2>::value;
     const size_t S = sp.streams.size(), E = (size_t)sp.entries;
     Owner* own = new_owner(out);
     out->n_streams = (int32_t)S;
@@ -628,20 +714,69 @@ void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* o
     out->lufs = own->alloc<double>(E);
     out->gain = own->alloc<double>(E);
     out->limited = own->alloc<int32_t>(E);
-    out->bytes = static_cast<uint8_t*>(own->take_pinned((size_t)sp.n_bytes + 16));
-    out->n_bytes = (size_t)sp.n_bytes;
+    if constexpr (V2) {
+        out->compression = own->alloc<int32_t>(S);
+        out->frames = own->alloc<int32_t>(S);
+        out->uncompressed_bytes = sp.plain_bytes;
+    }
     std::vector<unsigned> pk(B_);
+    size_t block_bytes = (size_t)sp.n_bytes;
+    std::vector<int64_t> fbytes(S, 0);  // compressed streams: header + frames
+    if (sp.compressed()) {
+        // The sizes depend on the audio: the frame sizes, four words per compressed stream and the block's end come first — ONE
+        // synchronisation more than the same block uncompressed —, then exactly the block's bytes.
+        const size_t words = flac_info_words(sp.n_frames, sp.n_flac);
+        h_flac_sizes_.assign(words, 0);
+        HIP_CHECK(hipMemcpyAsync(h_flac_sizes_.data(), d_flac_sizes_, 4 * words, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        const int* info = h_flac_sizes_.data() + sp.n_frames;
+        int64_t at = sp.flac_base;
+        size_t f = 0, frame_bytes = 0;
+        int j = 0;
+        for (int s : sp.dev) {
+            if (!sp.streams[(size_t)s].set.flac()) continue;
+            int64_t bytes = FLAC_HEADER_BYTES;
+            for (long k = 0; k < sp.frames[(size_t)s]; ++k, ++f) {
+                const int sz = h_flac_sizes_[f];
+                if (sz < 11 || sz > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sz) + " bytes");
+                bytes += sz;
+            }
+            if (info[FLAC_INFO_WORDS * j + FLAC_INFO_BASE] != (int)at || info[FLAC_INFO_WORDS * j + FLAC_INFO_BYTES] != (int)bytes)
+                throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's place of stream " + std::to_string(s) + " differs from the sum of its frame sizes");
+            sp.begin[(size_t)s] = at;
+            sp.data[(size_t)s] = at + FLAC_HEADER_BYTES;
+            fbytes[(size_t)s] = bytes;
+            frame_bytes += (size_t)(bytes - FLAC_HEADER_BYTES);
+            block_bytes = (size_t)(at + bytes);
+            at = (at + bytes + 15) & ~int64_t(15);
+            ++j;
+        }
+        if ((int64_t)info[FLAC_INFO_WORDS * sp.n_flac] != (int64_t)block_bytes) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's block end differs from the host's");
+        if (flac_prof_rec_ >= 0 && (size_t)flac_prof_rec_ < prof_.recs.size()) prof_.recs[(size_t)flac_prof_rec_].bytes += (double)frame_bytes;
+    }
+    out->bytes = static_cast<uint8_t*>(own->take_pinned(block_bytes + 16));
+    out->n_bytes = block_bytes;
     HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, (size_t)sp.n_bytes, hipMemcpyDeviceToHost, stream_));  // exactly the block: finished files
+    if (!sp.compressed()) {
+        HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, block_bytes, hipMemcpyDeviceToHost, stream_));  // exactly the block: finished files
+    } else {
+        // the uncompressed part up to where the compressed one starts (the gap's zeros are k_pack_streams'), then the compressed part
+        if (sp.flac_base > 0) HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, (size_t)sp.flac_base, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(out->bytes + sp.flac_base, d_flac_out_, block_bytes - (size_t)sp.flac_base, hipMemcpyDeviceToHost, stream_));
+    }
     size_t e = 0;
     for (size_t s = 0; s < S; ++s) {
         const PackPlan& p = sp.streams[s];
         const int64_t bytes = (int64_t)p.bps() * p.total;
         out->stream_offset[s] = sp.begin[s];
         out->data_offset[s] = sp.data[s];
-        out->stream_bytes[s] = (sp.data[s] - sp.begin[s]) + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
+        out->stream_bytes[s] = p.set.flac() ? fbytes[s] : (sp.data[s] - sp.begin[s]) + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
         out->total_samples[s] = p.total;
         out->encoding[s] = p.set.enc;
+        if constexpr (V2) {
+            out->compression[s] = p.set.compress;
+            out->frames[s] = (int32_t)sp.frames[s];
+        }
         out->entry_base[s] = (int32_t)e;
         for (int i = 0; i < p.n; ++i, ++e) {
             const int row = p.order[i];
@@ -664,20 +799,14 @@ void Engine::copy_out_streams(const StreamsPlan& sp, mi355vits_streams_result* o
     for (size_t i = 0; i < E; ++i) memcpy(&out->peaks[i], &pk[out->rows[i]], 4);
 }
 
-void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
-                         mi355vits_streams_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    StreamsPlan sp;
-    plan_streams(streams, n_streams, args.batch, sp);
-    if (!sp.measured()) {
+template <typename R> void Engine::run_streams_plan(const mi355vits_run_args& args, const mi355vits_row_args* rows, StreamsPlan& sp, R* out) {
+    if (!sp.measured() && !sp.compressed_planned()) {
         synthesize(args, rows, nullptr, &sp);
         copy_out_streams(sp, out);
         return;
     }
-    // Some stream trims or normalises: as a trimmed run_packed — synthesise without an early table and without the padded int16
-    // pass, measure (ONE synchronisation), then what fetch_streams does.  A limit exceeded by the trimmed sizes leaves no result served.
+    // Some stream trims, normalises or compresses: as a trimmed run_packed — synthesise without an early table and without the padded
+    // int16 pass, measure (ONE synchronisation, or none), then what fetch_streams does.  A limit exceeded by the trimmed sizes leaves no result served.
     mi355vits_run_args a = args;
     a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
     synthesize(a, rows, nullptr);
@@ -690,14 +819,45 @@ void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_arg
     }
 }
 
+void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
+                         mi355vits_streams_result* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
+    StreamsPlan sp;
+    const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
+    plan_streams(v.empty() ? nullptr : v.data(), n_streams, args.batch, sp);
+    run_streams_plan(args, rows, sp, out);
+}
+
 void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out) {
     begin_fetch(out, "fetch_streams");
     StreamsPlan sp;
-    plan_streams(streams, n_streams, B_, sp);
+    const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
+    plan_streams(v.empty() ? nullptr : v.data(), n_streams, B_, sp);
     streams_last_run(sp, out);
 }
 
-void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
+void Engine::run_streams2(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args2* streams, int n_streams,
+                          mi355vits_streams_result2* out) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
+    StreamsPlan sp;
+    plan_streams(streams, n_streams, args.batch, sp);
+    if (sp.compressed_planned()) check_flac_rate(output_rate());  // the rate this run will run at
+    run_streams_plan(args, rows, sp, out);
+}
+
+void Engine::fetch_streams2(const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out) {
+    begin_fetch(out, "fetch_streams2");
+    StreamsPlan sp;
+    plan_streams(streams, n_streams, B_, sp);
+    if (sp.compressed_planned()) check_flac_rate(run_hz_);
+    streams_last_run(sp, out);
+}
+
+template <typename R> void Engine::streams_last_run(StreamsPlan& sp, R* out) {
     HIP_CHECK(hipSetDevice(device_));
     std::vector<float> ratios;
     bool loud = false, tp = false;
@@ -709,13 +869,14 @@ void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
     measure_last_run(ratios, loud, true, tp);
     place_streams(sp);
     {
-        // the limiter: one job per distinct (row, target, ceiling, encoding class) among the entries the ceiling would hold back
+        // the limiter: one job per distinct (row, target, ceiling, encoding class, window, mode) among the entries the ceiling would hold back
         std::vector<LimitJob> jobs;
+        LimitKeys keys;
         for (PackPlan& p : sp.streams)
-            if (p.set.limiting()) limit_pack(p, jobs);
+            if (p.set.limiting()) limit_pack(p, jobs, &keys);
         sp.curved = !jobs.empty();
         if (sp.curved) {
-            run_limit_jobs(jobs, pack_.limit_window, arena_lm_, true, pack_.ceil_mode == MI355VITS_CEILING_TRUE_PEAK);
+            run_limit_groups(jobs, keys);
             for (PackPlan& p : sp.streams) curve_offsets(p, jobs);
         }
     }
@@ -734,6 +895,8 @@ void Engine::streams_last_run(StreamsPlan& sp, mi355vits_streams_result* out) {
     fill_streams_table(sp, h_pack_seg_.data());
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
     launch_streams(sp);
+    flac_prof_rec_ = -1;
+    if (sp.compressed()) launch_flac_streams(sp);
     copy_out_streams(sp, out);
 }
 
@@ -927,12 +1090,13 @@ void Engine::set_loudness_limiter(int window_samples) {
     pack_.limit_window = window_samples;
 }
 
-int Engine::limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g) const {
+int Engine::limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& set, double g, LimitKeys* keys) const {
+    const std::pair<int, int> key(set.limit_window, set.true_peak() ? 1 : 0);
     const double c = std::pow(10.0, (double)set.loud_ceiling / 20.0);
     const double U = set.enc == PACK_ENC_F32 ? 1.0 : 32767.0;
     // (a linear scan: quadratic in the over entries of a streams call, which a micro-batch keeps to tens; a single pack never repeats a row)
     for (size_t j = 0; j < jobs.size(); ++j)
-        if (jobs[j].row == row && jobs[j].g == g && jobs[j].c == c && jobs[j].U == U) return (int)j;  // (g is a function of the row and the target)
+        if (jobs[j].row == row && jobs[j].g == g && jobs[j].c == c && jobs[j].U == U && (!keys || (*keys)[j] == key)) return (int)j;  // (g is a function of the row and the target)
     LimitJob job;
     job.g = g;
     job.c = c;
@@ -941,10 +1105,11 @@ int Engine::limit_job(std::vector<LimitJob>& jobs, int row, const PackSettings& 
     job.n = (int)h_olen_[row];  // the curve is made on the whole row, as the loudness is measured on it
     job.off = job.tile0 = 0;
     jobs.push_back(job);
+    if (keys) keys->push_back(key);
     return (int)jobs.size() - 1;
 }
 
-void Engine::limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const {
+void Engine::limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs, LimitKeys* keys) const {
     const PackSettings& set = plan.set;
     std::vector<int> curve(plan.n, -1);
     bool any = false;
@@ -954,7 +1119,7 @@ void Engine::limit_pack(PackPlan& plan, std::vector<LimitJob>& jobs) const {
         bool over;
         loudness_gain(h_loud_[row], ceiling_peak(row, set), set.loud_target, set.loud_ceiling, set.limit_window, &g, &over);
         if (!over || h_olen_[row] < 1) continue;
-        curve[i] = limit_job(jobs, row, set, g);
+        curve[i] = limit_job(jobs, row, set, g, keys);
         any = true;
     }
     if (any) plan.curve.swap(curve);
@@ -965,33 +1130,75 @@ void Engine::curve_offsets(PackPlan& plan, const std::vector<LimitJob>& jobs) {
         if (c >= 0) c = jobs[(size_t)c].off;
 }
 
-LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve, bool true_peak) {
-    long floats = 0;
-    const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
-    if (tiles < 0)
-        throw EngineError(MI355VITS_ERR_INVALID, "limiter: the curves of the rows over the ceiling together exceed 2^31 - 1 samples");
-    const size_t nj = jobs.size();
+// Placed jobs (off / tile0 set; a group's tile0 counts from 0: it is a launch of its own) in ONE layout of jobs, statistics, curves
+// and envelopes in `arena`, one upload, and per group k_true_peak_env (true-peak groups) and k_limit over its part of the table.
+LimitStat* Engine::launch_limit_groups(const std::vector<LimitJob>& placed, const std::vector<LimitGroup>& groups, long floats, DeviceArena& arena,
+                                       bool with_curve) {
+    const size_t nj = placed.size();
+    bool any_tp = false;
+    for (const LimitGroup& g : groups) any_tp = any_tp || g.tp;
     // (reserve waits for the stream when the arena has to grow: "no synchronisation added" holds from the second pack of a size on, as for arena_p_)
     arena.reserve(DeviceArena::padded(sizeof(LimitJob) * nj) + DeviceArena::padded(sizeof(LimitStat) * nj) +
-                      (with_curve ? DeviceArena::padded(4 * (size_t)floats) : 0) + (true_peak ? DeviceArena::padded(8 * (size_t)floats) : 0) + 4096,
+                      (with_curve ? DeviceArena::padded(4 * (size_t)floats) : 0) + (any_tp ? DeviceArena::padded(8 * (size_t)floats) : 0) + 4096,
                   stream_);
     arena.reset();
     LimitJob* d_jobs = arena.alloc<LimitJob>(nj);
     LimitStat* d_stats = arena.alloc<LimitStat>(nj);
     float* curve = with_curve ? arena.alloc<float>((size_t)floats) : nullptr;
-    double* env = true_peak ? arena.alloc<double>((size_t)floats) : nullptr;  // e[t] of every job, one behind the other as the curves are
+    double* env = any_tp ? arena.alloc<double>((size_t)floats) : nullptr;  // e[t] of every job, one behind the other as the curves are
     if (with_curve) d_curve_ = curve;
-    h_limit_jobs_ = jobs;  // a member: it outlives the copy
+    h_limit_jobs_ = placed;  // a member: it outlives the copy
     HIP_CHECK(hipMemcpyAsync(d_jobs, h_limit_jobs_.data(), sizeof(LimitJob) * nj, hipMemcpyHostToDevice, stream_));
-    if (true_peak) {
-        ProfScope ps(prof_, "truepeak.env", 0, 12.0 * (double)floats);
-        launch_true_peak_env(d_jobs, (int)nj, tiles, o_audio_, Lo_, env, stream_);
-    }
-    {
-        ProfScope ps(prof_, "limit", 0, 8.0 * (double)floats + 16.0 * (double)nj);
-        launch_limit(d_jobs, (int)nj, tiles, window, o_audio_, Lo_, d_stats, curve, stream_, env);
+    for (const LimitGroup& g : groups) {
+        if (g.tp) {
+            ProfScope ps(prof_, "truepeak.env", 0, 12.0 * (double)g.floats);
+            launch_true_peak_env(d_jobs + g.first, (int)g.n, g.tiles, o_audio_, Lo_, env, stream_);
+        }
+        ProfScope ps(prof_, "limit", 0, 8.0 * (double)g.floats + 16.0 * (double)g.n);
+        launch_limit(d_jobs + g.first, (int)g.n, g.tiles, g.window, o_audio_, Lo_, d_stats + g.first, curve, stream_, g.tp ? env : nullptr);
     }
     return d_stats;
+}
+
+LimitStat* Engine::run_limit_jobs(std::vector<LimitJob>& jobs, int window, DeviceArena& arena, bool with_curve, bool true_peak) {
+    long floats = 0;
+    const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
+    if (tiles < 0)
+        throw EngineError(MI355VITS_ERR_INVALID, "limiter: the curves of the rows over the ceiling together exceed 2^31 - 1 samples");
+    return launch_limit_groups(jobs, {LimitGroup{0, jobs.size(), tiles, floats, window, true_peak}}, floats, arena, with_curve);
+}
+
+// The jobs of a streams call, whose streams bring their own window and mode.  One key among them (every v1 call): run_limit_jobs as
+// ever.  Several: the jobs sorted by key (stable) and placed group by group in one layout — the curves of all groups coexist until the
+// pack has run.  A curve depends on (row, g, c, U, window, mode) alone, so each is what a single pack under that setting makes.
+void Engine::run_limit_groups(std::vector<LimitJob>& jobs, const LimitKeys& keys) {
+    bool one = true;
+    for (const auto& k : keys) one = one && k == keys[0];
+    if (one) {
+        run_limit_jobs(jobs, keys[0].first, arena_lm_, true, keys[0].second != 0);
+        return;
+    }
+    const size_t nj = jobs.size();
+    std::vector<size_t> perm(nj);
+    for (size_t j = 0; j < nj; ++j) perm[j] = j;
+    std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return keys[a] < keys[b]; });
+    std::vector<LimitGroup> groups;
+    std::vector<LimitJob> sorted(nj);
+    for (size_t k = 0; k < nj; ++k) {
+        sorted[k] = jobs[perm[k]];
+        if (k == 0 || keys[perm[k]] != keys[perm[k - 1]]) groups.push_back(LimitGroup{k, 0, 0, 0, keys[perm[k]].first, keys[perm[k]].second != 0});
+        ++groups.back().n;
+    }
+    long floats = 0;
+    for (LimitGroup& g : groups) {
+        g.tiles = limit_place_jobs(sorted.data() + g.first, (int)g.n, &g.floats);
+        if (g.tiles < 0 || floats + g.floats > LIMIT_MAX_CURVE)
+            throw EngineError(MI355VITS_ERR_INVALID, "limiter: the curves of the rows over the ceiling together exceed 2^31 - 1 samples");
+        for (size_t k = 0; k < g.n; ++k) sorted[g.first + k].off += (int)floats;  // the group's curves behind those of the groups in front
+        floats += g.floats;
+    }
+    for (size_t k = 0; k < nj; ++k) jobs[perm[k]].off = sorted[k].off;  // curve_offsets reads the callers' order
+    launch_limit_groups(sorted, groups, floats, arena_lm_, true);
 }
 
 void Engine::fetch_limiter(mi355vits_limiter* out) {

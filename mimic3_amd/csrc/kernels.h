@@ -322,6 +322,33 @@ void launch_flac_frames(const FlacJob* jobs, int n_jobs, long n_frames, int rate
 void launch_flac_gather(const uint8_t* slots, int* sizes, long long* offsets, long n_frames, uint8_t* out, hipStream_t s);
 // the 42 bytes in front of the frames, from the frame sizes the host holds (min / max frame size); the MD5 field stays zero
 void flac_stream_header(uint8_t* h, int rate, int64_t total, const int* sizes, long n_frames);
+// SEVERAL FLAC files in one block (mi355vits_run_streams2 / _fetch_streams2): one job per compressed stream, every job
+// with first_frame = 0 and slot0 = the frames of the jobs in front of it, k_flac_frames launched once over all of them.  File j sits
+// at a 16-byte-aligned block offset base[j] (base[0] = base0, base[j + 1] = base[j] + (42 + its frames' bytes rounded up to 16)): its
+// 42 header bytes, then its frames back to back.
+//   launch_flac_place    one workgroup: the scan of the frame sizes (pre [n_frames + 1]: the bytes of the frames in front, over all
+//                        jobs), per job FLAC_INFO_* at sizes[n_frames + 4 j ..], the block's end at sizes[n_frames + 4 n_jobs], per
+//                        frame its block offset and job (ftab [n_frames + 1]: .x, .y), per job the 42 header bytes
+//                        flac_stream_header makes as 12 little-endian words (hdr), per work item of the gather the last frame that
+//                        starts at or before its first byte (item_first [flac_gather_items(bound_bytes)]).  sizes holds
+//                        flac_info_words words: what the host copies in one piece.  jtab [FLAC_JTAB_ROWS n_jobs]: the job table of a
+//                        launch with more jobs than the LDS holds.
+//   launch_flac_gather_streams   destination-major: every 16-byte unit of [base0, end) has one writer lane, which assembles its 16
+//                        bytes from the frame(s), header bytes and zero gaps that cover it; persistent over bound_bytes (the host's
+//                        bound of end - base0), reading the end from the device.  out[p - base0] = block byte p; out holds
+//                        bound_bytes rounded up to 16.
+enum { FLAC_INFO_BASE = 0, FLAC_INFO_BYTES = 1, FLAC_INFO_MIN = 2, FLAC_INFO_MAX = 3, FLAC_INFO_WORDS = 4 };
+constexpr int FLAC_HDR_WORDS = 12;
+constexpr int FLAC_JTAB_ROWS = 5;
+constexpr long FLAC_GATHER_ITEM_BYTES = 256L * 16;  // a work item of the gather: 256 lanes x one 16-byte store
+inline size_t flac_info_words(long n_frames, int n_jobs) { return (size_t)n_frames + (size_t)FLAC_INFO_WORDS * n_jobs + 1; }
+inline size_t flac_gather_items(long bound_bytes) { return (size_t)((bound_bytes + FLAC_GATHER_ITEM_BYTES - 1) / FLAC_GATHER_ITEM_BYTES) + 2; }
+// a file's bound: its header, and every frame at its largest, rounded up to the next file's place
+inline long flac_file_bound(long total) { return (FLAC_HEADER_BYTES + 16 * flac_frames(total) + 2 * total + 15) & ~15L; }
+void launch_flac_place(const FlacJob* jobs, int n_jobs, long n_frames, int rate, long base0, int* sizes, unsigned* pre, int2* ftab,
+                       unsigned* hdr, int* item_first, int* jtab, hipStream_t s);
+void launch_flac_gather_streams(int n_jobs, long n_frames, const uint8_t* slots, const int* sizes, const int2* ftab, const unsigned* hdr,
+                                const int* item_first, long base0, long bound_bytes, uint8_t* out, hipStream_t s);
 
 // ---------------------------------------------------------------- output at a requested sample rate (kernels_resample.cpp)
 // y[k] = sum_j h[k M - j L + half] x[j], x zero outside [0, n): what scipy.signal.resample_poly(x, L, M) returns with its default

@@ -8,7 +8,9 @@
 //                   goes to its slot of FLAC_SLOT_BYTES with its size in the size table.
 //   k_flac_scan     one workgroup: the exclusive scan of the sizes and their total.
 //   k_flac_gather   the frames back to back in the output, one writer per byte.
-// Integer arithmetic only; the only atomics are LDS ORs.  The bytes are a function of (samples, rate, first frame number) alone.
+//   k_flac_place / k_flac_gather_streams   several files in one block (the streams calls): the places of every
+//                   frame and file and the 42 header bytes made on the device, then one 16-byte store per lane.
+// Integer arithmetic only; the only atomics are LDS ORs and k_flac_place's integer maxima.  The bytes are a function of (samples, rate, first frame number) alone.
 #include "kernels.h"
 
 #include <algorithm>
@@ -404,6 +406,295 @@ void launch_flac_gather(const uint8_t* slots, int* sizes, long long* offsets, lo
     LAUNCH_KERNEL(k_flac_scan, dim3(1), dim3(256), 0, s, sizes, n_frames, offsets);
     const long gx = std::min<long>(n_frames, 8L * current_device_cu_count());
     LAUNCH_KERNEL(k_flac_gather, dim3((unsigned)gx), dim3(256), 0, s, slots, (const int*)sizes, (const long long*)offsets, n_frames, out);
+}
+
+// ---- several files in one block (kernels.h: launch_flac_place / launch_flac_gather_streams)
+namespace {
+constexpr int PLACE_THREADS = 1024;   // 16 waves: a trip takes 4,096 frames, four per lane in 16-byte loads
+constexpr int PLACE_LDS_JOBS = 1024;  // up to this many jobs the job table lives in the LDS (20 KB), beyond it in global memory
+enum { JT_SLOT0 = 0, JT_BASE = 1, JT_PRE0 = 2, JT_NEGMIN = 3, JT_MAX = 4, JT_ROWS = 5 };  // the job table's rows, [row][job]
+
+// the workgroup's exclusive prefix of v (and the sum over all lanes): a shuffle scan per wave, the waves' sums through the LDS.
+// Unsigned adds: exact in any order.  ws holds PLACE_THREADS / 64 words; two barriers, the second frees ws for the next call.
+__device__ __forceinline__ unsigned place_scan(unsigned v, unsigned* ws, unsigned* all) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned inc = v;
+    MI355_UNROLL
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned o = __shfl_up(inc, (unsigned)d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) ws[wave] = inc;
+    __syncthreads();
+    unsigned before = 0u, sum = 0u;
+    MI355_UNROLL
+    for (int w = 0; w < PLACE_THREADS / 64; ++w) {
+        const unsigned x = ws[w];
+        before += w < wave ? x : 0u;
+        sum += x;
+    }
+    __syncthreads();
+    *all = sum;
+    return before + inc - v;
+}
+}  // namespace
+
+// One workgroup, four phases behind the scan, each a pass of coalesced accesses with the per-job values in the LDS:
+//   scan    pre[f] = the bytes of the frames in front of frame f over all jobs (16-byte loads and stores, a shuffle scan);
+//   jobs    per job its bytes (two reads of pre) and its place (a second scan, over the places rounded up to 16);
+//   frames  per frame its block offset and its job (ftab), its size into the job's smallest / largest — integer maxima in the LDS,
+//           one per run of frames a lane holds of one job: the same in any order;
+//   finish  per job FLAC_INFO_* and the 42 header bytes; per work item of the gather the last frame at or before its first byte.
+__global__ __launch_bounds__(1024) void k_flac_place(const FlacJob* __restrict__ jobs, int n_jobs, long n_frames, int rate, long base0,
+                                                     int* __restrict__ sizes, unsigned* __restrict__ pre, int2* __restrict__ ftab,
+                                                     unsigned* __restrict__ hdr, int* __restrict__ item_first, int* __restrict__ jtab) {
+    __shared__ unsigned ws[PLACE_THREADS / 64];
+    __shared__ int ls[JT_ROWS * PLACE_LDS_JOBS];
+    const int t = threadIdx.x;
+    int* __restrict__ info = sizes + n_frames;
+    const bool staged = n_jobs <= PLACE_LDS_JOBS;
+    int* const tab = staged ? ls : jtab;
+    const int ld = staged ? PLACE_LDS_JOBS : n_jobs;
+    // ---- scan: four sizes per lane and trip
+    unsigned carry = 0u;
+    for (long f0 = 0; f0 < n_frames; f0 += 4L * PLACE_THREADS) {
+        const long f = f0 + 4L * t;
+        unsigned v[4] = {0u, 0u, 0u, 0u};
+        if (f + 4 <= n_frames) {
+            const uint4 a = *reinterpret_cast<const uint4*>(sizes + f);  // (sizes is 16-byte aligned, f a multiple of 4)
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        } else {
+            MI355_UNROLL
+            for (int k = 0; k < 4; ++k) v[k] = f + k < n_frames ? (unsigned)sizes[f + k] : 0u;
+        }
+        unsigned all;
+        const unsigned b0 = carry + place_scan(v[0] + v[1] + v[2] + v[3], ws, &all);
+        uint4 o;
+        o.x = b0; o.y = b0 + v[0]; o.z = o.y + v[1]; o.w = o.z + v[2];
+        if (f + 4 <= n_frames) {
+            *reinterpret_cast<uint4*>(pre + f) = o;
+        } else {
+            if (f < n_frames) pre[f] = o.x;
+            if (f + 1 < n_frames) pre[f + 1] = o.y;
+            if (f + 2 < n_frames) pre[f + 2] = o.z;
+        }
+        carry += all;
+    }
+    if (t == 0) pre[n_frames] = carry;
+    __syncthreads();
+    // ---- jobs: bytes, and place = base0 + the places (rounded up to 16) of the jobs in front
+    unsigned at = (unsigned)base0;
+    for (int j0 = 0; j0 < n_jobs; j0 += PLACE_THREADS) {
+        const int j = j0 + t;
+        unsigned bytes = 0u, room = 0u, p0 = 0u;
+        int s0 = 0;
+        if (j < n_jobs) {
+            s0 = jobs[j].slot0;
+            const long s1 = j + 1 < n_jobs ? (long)jobs[j + 1].slot0 : n_frames;
+            p0 = pre[s0];
+            bytes = (unsigned)FLAC_HEADER_BYTES + (pre[s1] - p0);
+            room = (bytes + 15u) & ~15u;
+        }
+        unsigned all;
+        const unsigned base = at + place_scan(room, ws, &all);
+        if (j < n_jobs) {
+            tab[JT_SLOT0 * ld + j] = s0;
+            tab[JT_BASE * ld + j] = (int)base;
+            tab[JT_PRE0 * ld + j] = (int)p0;
+            tab[JT_NEGMIN * ld + j] = -0x7fffffff;  // minus the smallest frame, under the integer maximum below
+            tab[JT_MAX * ld + j] = 0;
+            info[FLAC_INFO_WORDS * j + FLAC_INFO_BASE] = (int)base;
+            info[FLAC_INFO_WORDS * j + FLAC_INFO_BYTES] = (int)bytes;
+            if (j == n_jobs - 1) info[FLAC_INFO_WORDS * n_jobs] = (int)(base + bytes);  // the block's end
+        }
+        at += all;
+    }
+    __syncthreads();
+    // ---- frames: four per lane and trip
+    for (long f0 = 0; f0 < n_frames; f0 += 4L * PLACE_THREADS) {
+        const long f = f0 + 4L * t;
+        if (f >= n_frames) continue;
+        unsigned pv[4] = {0u, 0u, 0u, 0u}, sv[4] = {0u, 0u, 0u, 0u};
+        if (f + 4 <= n_frames) {
+            const uint4 a = *reinterpret_cast<const uint4*>(pre + f), b = *reinterpret_cast<const uint4*>(sizes + f);
+            pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w;
+            sv[0] = b.x; sv[1] = b.y; sv[2] = b.z; sv[3] = b.w;
+        } else {
+            MI355_UNROLL
+            for (int k = 0; k < 4; ++k) {
+                pv[k] = f + k < n_frames ? pre[f + k] : 0u;
+                sv[k] = f + k < n_frames ? (unsigned)sizes[f + k] : 0u;
+            }
+        }
+        int j;
+        {
+            int lo = 0, hi = n_jobs;  // the last job whose first slot is at or before f: the jobs without a frame in front of it are passed
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((long)tab[JT_SLOT0 * ld + mid] <= f) lo = mid + 1;
+                else hi = mid;
+            }
+            j = lo - 1;
+        }
+        int run = j, neg = -0x7fffffff, mx = 0;
+        MI355_UNROLL
+        for (int k = 0; k < 4; ++k) {
+            if (f + k < n_frames) {
+                while (j + 1 < n_jobs && (long)tab[JT_SLOT0 * ld + j + 1] <= f + k) ++j;
+                if (j != run) {
+                    atomicMax(&tab[JT_NEGMIN * ld + run], neg);
+                    atomicMax(&tab[JT_MAX * ld + run], mx);
+                    run = j; neg = -0x7fffffff; mx = 0;
+                }
+                const int sz = (int)sv[k];
+                neg = -sz > neg ? -sz : neg;
+                mx = sz > mx ? sz : mx;
+                int2 e;
+                e.x = tab[JT_BASE * ld + j] + FLAC_HEADER_BYTES + (int)(pv[k] - (unsigned)tab[JT_PRE0 * ld + j]);
+                e.y = j;
+                ftab[f + k] = e;
+            }
+        }
+        atomicMax(&tab[JT_NEGMIN * ld + run], neg);
+        atomicMax(&tab[JT_MAX * ld + run], mx);
+    }
+    __syncthreads();
+    // ---- finish, per job: FLAC_INFO_MIN / _MAX and the 42 bytes of flac_stream_header as little-endian words
+    for (int j = t; j < n_jobs; j += PLACE_THREADS) {
+        const long s0 = tab[JT_SLOT0 * ld + j], s1 = j + 1 < n_jobs ? (long)tab[JT_SLOT0 * ld + j + 1] : n_frames;
+        const unsigned fmin = s1 > s0 ? (unsigned)(-tab[JT_NEGMIN * ld + j]) : 0u;
+        const unsigned fmax = (unsigned)tab[JT_MAX * ld + j];
+        info[FLAC_INFO_WORDS * j + FLAC_INFO_MIN] = (int)fmin;
+        info[FLAC_INFO_WORDS * j + FLAC_INFO_MAX] = (int)fmax;
+        const unsigned long long v = ((unsigned long long)(unsigned)rate << 44) | (15ULL << 36) | ((unsigned long long)jobs[j].n & 0xfffffffffULL);
+        auto byte = [&](int sh) { return (unsigned)(v >> sh) & 0xffu; };
+        unsigned* __restrict__ h = hdr + (size_t)FLAC_HDR_WORDS * j;
+        h[0] = 0x43614c66u;  // "fLaC"
+        h[1] = 0x80u | (34u << 24);
+        h[2] = (unsigned)(FLAC_BLOCK >> 8) | ((unsigned)(FLAC_BLOCK & 0xff) << 8) | ((unsigned)(FLAC_BLOCK >> 8) << 16) | ((unsigned)(FLAC_BLOCK & 0xff) << 24);
+        h[3] = ((fmin >> 16) & 0xffu) | (((fmin >> 8) & 0xffu) << 8) | ((fmin & 0xffu) << 16) | (((fmax >> 16) & 0xffu) << 24);
+        h[4] = ((fmax >> 8) & 0xffu) | ((fmax & 0xffu) << 8) | (byte(56) << 16) | (byte(48) << 24);
+        h[5] = byte(40) | (byte(32) << 8) | (byte(24) << 16) | (byte(16) << 24);
+        h[6] = byte(8) | (byte(0) << 8);
+        MI355_UNROLL
+        for (int k = 7; k < FLAC_HDR_WORDS; ++k) h[k] = 0u;
+    }
+    // ---- finish, per work item of the gather: item_first[i] = the last frame that starts at or before byte base0 + i ITEM (-1: none),
+    // for i = 0 .. the items of the block inclusive.  Frame f owns the item starts in [its offset, the next frame's offset): one writer each.
+    const long end = (long)tab[JT_BASE * ld + n_jobs - 1] + (long)(unsigned)info[FLAC_INFO_WORDS * (n_jobs - 1) + FLAC_INFO_BYTES];
+    const long last_item = (end - base0 + FLAC_GATHER_ITEM_BYTES - 1) / FLAC_GATHER_ITEM_BYTES;
+    const long first_off = n_frames > 0 ? (long)ftab[0].x : 0x7fffffffffffL;
+    for (long i = t; i <= last_item && base0 + i * FLAC_GATHER_ITEM_BYTES < first_off; i += PLACE_THREADS) item_first[i] = -1;
+    for (long f = t; f < n_frames; f += PLACE_THREADS) {
+        const long o = ftab[f].x, lim = f + 1 < n_frames ? (long)ftab[f + 1].x : 0x7fffffffffffL;
+        for (long i = (o - base0 + FLAC_GATHER_ITEM_BYTES - 1) / FLAC_GATHER_ITEM_BYTES; i <= last_item && base0 + i * FLAC_GATHER_ITEM_BYTES < lim; ++i)
+            item_first[i] = (int)f;
+    }
+}
+
+// Destination-major: a work item is 256 lanes x one 16-byte store.  item_first bounds the lane's search for its frame to the frames
+// that start inside the item; a lane whose 16 bytes lie in one frame shifts them out of the aligned words that hold them; a lane on a
+// boundary — a frame's end, up to two frame starts, one file start, a header, a gap, the block's end — loads what can cover its
+// bytes at once and picks byte by byte.
+__global__ __launch_bounds__(256) void k_flac_gather_streams(int n_jobs, long n_frames, const uint8_t* __restrict__ slots,
+                                                             const int* __restrict__ sizes, const int2* __restrict__ ftab,
+                                                             const unsigned* __restrict__ hdr, const int* __restrict__ item_first,
+                                                             long base0, long bound_bytes, uint8_t* __restrict__ out) {
+    const int* __restrict__ info = sizes + n_frames;
+    const long dev_end = info[FLAC_INFO_WORDS * n_jobs];
+    const long end = dev_end < base0 + bound_bytes ? dev_end : base0 + bound_bytes;  // (never past what out holds, whatever the sizes say)
+    const long nitems = (end - base0 + FLAC_GATHER_ITEM_BYTES - 1) / FLAC_GATHER_ITEM_BYTES;
+    for (long item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const long p0 = base0 + item * FLAC_GATHER_ITEM_BYTES + 16L * threadIdx.x;
+        const int flo = item_first[item], fhi = item_first[item + 1];  // uniform
+        if (p0 >= end) continue;  // (the block's last store may run up to 15 bytes into the buffer's padding)
+        // the last frame that starts at or before the lane's first byte (-1: none)
+        long f;
+        {
+            long lo = flo < 0 ? 0 : flo, hi = (long)fhi + 1;
+            while (lo < hi) {
+                const long mid = (lo + hi) >> 1;
+                if ((long)ftab[mid].x <= p0) lo = mid + 1;
+                else hi = mid;
+            }
+            f = lo - 1;
+        }
+        const long fc = f < 0 ? 0 : f;
+        int2 fe;
+        fe.x = 0; fe.y = 0;
+        int fsz = 0;
+        if (n_frames > 0) {
+            fe = ftab[fc];
+            fsz = sizes[fc];
+        }
+        const long q = p0 - (long)fe.x;
+        uint4 w;
+        if (f >= 0 && q + 16 <= fsz) {
+            // 16 bytes of one frame, from any byte of its 16-byte-aligned slot: the aligned words that hold them, shifted.  The fifth
+            // word starts inside the frame, so it lies in the slot (whose last word k_flac_frames wrote whole).
+            const unsigned* __restrict__ sw = reinterpret_cast<const unsigned*>(slots + (size_t)f * FLAC_SLOT_BYTES) + (q >> 2);
+            const int sh = 8 * (int)(q & 3);
+            const unsigned a0 = sw[0], a1 = sw[1], a2 = sw[2], a3 = sw[3], a4 = sh ? sw[4] : 0u;
+            auto join = [&](unsigned l, unsigned h) { return (unsigned)((((unsigned long long)h << 32) | l) >> sh); };
+            w.x = join(a0, a1); w.y = join(a1, a2); w.z = join(a2, a3); w.w = join(a3, a4);
+        } else {
+            // The file the lane's first byte lies in: the frame's, or one further on (a header, or files without a frame).  Inside
+            // the 16 bytes at most one more file starts (a file holds 42 bytes at least) and at most frames f + 1 and f + 2 (a frame
+            // holds 11): their places are loaded at once, then every byte picks its source.
+            int j = f >= 0 ? fe.y : 0;
+            if (j + 1 < n_jobs && (long)info[FLAC_INFO_WORDS * (j + 1) + FLAC_INFO_BASE] <= p0) {
+                int lo = j + 2, hi = n_jobs;  // past the frame's file: the last file that starts at or before p0, by bisection
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if ((long)info[FLAC_INFO_WORDS * mid + FLAC_INFO_BASE] <= p0) lo = mid + 1;
+                    else hi = mid;
+                }
+                j = lo - 1;
+            }
+            const long b0 = info[FLAC_INFO_WORDS * j + FLAC_INFO_BASE];
+            const long b1 = j + 1 < n_jobs ? (long)info[FLAC_INFO_WORDS * (j + 1) + FLAC_INFO_BASE] : 0x7fffffffffffL;
+            long go[3], gz[3], gi[3];
+            MI355_UNROLL
+            for (int c = 0; c < 3; ++c) {
+                const long g = f + c;
+                const bool ok = g >= 0 && g < n_frames;
+                gi[c] = ok ? g : 0;
+                go[c] = ok ? (long)ftab[gi[c]].x : 0x7fffffffffffL;
+                gz[c] = ok ? (long)sizes[gi[c]] : 0;
+            }
+            unsigned ww[4] = {0u, 0u, 0u, 0u};
+            MI355_UNROLL
+            for (int k = 0; k < 16; ++k) {
+                const long p = p0 + k;
+                const int c = go[2] <= p ? 2 : go[1] <= p ? 1 : 0;
+                const long r = p - go[c];  // (negative where no frame starts at or before p)
+                const bool in_frame = r >= 0 && r < gz[c];
+                const int jj = b1 <= p ? j + 1 : j;
+                const long hrel = p - (b1 <= p ? b1 : b0);
+                const bool in_hdr = p < end && hrel < FLAC_HEADER_BYTES;
+                unsigned byte = 0u;
+                if (in_hdr) byte = (hdr[(size_t)FLAC_HDR_WORDS * jj + (hrel >> 2)] >> (8 * (int)(hrel & 3))) & 0xffu;
+                else if (p < end && in_frame) byte = slots[(size_t)gi[c] * FLAC_SLOT_BYTES + r];
+                ww[k >> 2] |= byte << (8 * (k & 3));
+            }
+            w.x = ww[0]; w.y = ww[1]; w.z = ww[2]; w.w = ww[3];
+        }
+        *reinterpret_cast<uint4*>(out + (p0 - base0)) = w;
+    }
+}
+
+void launch_flac_place(const FlacJob* jobs, int n_jobs, long n_frames, int rate, long base0, int* sizes, unsigned* pre, int2* ftab,
+                       unsigned* hdr, int* item_first, int* jtab, hipStream_t s) {
+    if (n_jobs <= 0) return;
+    LAUNCH_KERNEL(k_flac_place, dim3(1), dim3(PLACE_THREADS), 0, s, jobs, n_jobs, n_frames, rate, base0, sizes, pre, ftab, hdr, item_first, jtab);
+}
+
+void launch_flac_gather_streams(int n_jobs, long n_frames, const uint8_t* slots, const int* sizes, const int2* ftab, const unsigned* hdr,
+                                const int* item_first, long base0, long bound_bytes, uint8_t* out, hipStream_t s) {
+    if (n_jobs <= 0 || bound_bytes <= 0) return;
+    const long nitems = (bound_bytes + FLAC_GATHER_ITEM_BYTES - 1) / FLAC_GATHER_ITEM_BYTES;
+    const long gx = std::min<long>(nitems, 8L * current_device_cu_count());  // as k_pack_streams: 8 workgroups of 4 waves per CU
+    LAUNCH_KERNEL(k_flac_gather_streams, dim3((unsigned)gx), dim3(256), 0, s, n_jobs, n_frames, slots, sizes, ftab, hdr, item_first, base0, bound_bytes, out);
 }
 
 // "fLaC", the one metadata block (STREAMINFO, flagged last) — 42 bytes; the MD5 stays zero: not computed

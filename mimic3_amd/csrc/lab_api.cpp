@@ -236,6 +236,62 @@ int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_f
     });
 }
 
+int mi355vits_lab_flac_jobs(const int16_t* const* pcm, const long* n, int32_t n_jobs, int32_t rate, uint8_t* out, size_t cap,
+                            size_t* n_bytes, int64_t* offsets, int64_t* sizes_out) {
+    return guarded(nullptr, [&] {
+        if (n_bytes) *n_bytes = 0;
+        if (!pcm || !n || !out || !n_bytes || !offsets || !sizes_out || n_jobs < 1) throw EngineError(MI355VITS_ERR_INVALID, "null argument or no job");
+        if (rate < 1 || rate > FLAC_MAX_RATE) throw EngineError(MI355VITS_ERR_INVALID, "rate must be in [1, 1048575]");
+        long frames = 0, bound = 0;
+        size_t src_bytes = 0;
+        std::vector<size_t> at((size_t)n_jobs);
+        for (int j = 0; j < n_jobs; ++j) {
+            if (n[j] < 0 || n[j] > 0x7fffffffL || (!pcm[j] && n[j] > 0)) throw EngineError(MI355VITS_ERR_INVALID, "job " + std::to_string(j) + ": null array or n out of range");
+            if (flac_frames(n[j]) > FLAC_MAX_FRAME_NUMBER + 1) throw EngineError(MI355VITS_ERR_INVALID, "frame numbers must stay below 2^21");
+            at[(size_t)j] = src_bytes + (n[j] > 0 ? (reinterpret_cast<uintptr_t>(pcm[j]) & 15) : 0);  // the host pointer's place behind a 16-byte boundary, kept
+            src_bytes = (at[(size_t)j] + (size_t)n[j] * 2 + 15) & ~size_t(15);
+            frames += flac_frames(n[j]);
+            bound += flac_file_bound(n[j]);
+            if (bound > 0x7fffffffL) throw EngineError(MI355VITS_ERR_INVALID, "the block's bound exceeds 2^31 - 1 bytes");
+        }
+        DevBuf din(src_bytes + 16), djobs(sizeof(FlacJob) * (size_t)n_jobs), dslots((size_t)frames * FLAC_SLOT_BYTES + 16),
+            dsizes(flac_info_words(frames, n_jobs) * 4), dpre(((size_t)frames + 1) * 4), dftab(((size_t)frames + 1) * 8),
+            dhdr((size_t)FLAC_HDR_WORDS * n_jobs * 4), ditems(flac_gather_items(bound) * 4), djtab((size_t)FLAC_JTAB_ROWS * n_jobs * 4),
+            dout((size_t)bound + 16);
+        std::vector<FlacJob> jobs((size_t)n_jobs);
+        long slot0 = 0;
+        for (int j = 0; j < n_jobs; ++j) {
+            int16_t* src = reinterpret_cast<int16_t*>(din.as<uint8_t>() + at[(size_t)j]);
+            if (n[j] > 0) HIP_CHECK(hipMemcpy(src, pcm[j], (size_t)n[j] * 2, hipMemcpyHostToDevice));
+            jobs[(size_t)j] = FlacJob{src, n[j], 0, (int)slot0};
+            slot0 += flac_frames(n[j]);
+        }
+        HIP_CHECK(hipMemcpy(djobs.p, jobs.data(), sizeof(FlacJob) * jobs.size(), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xa5, (size_t)bound + 16));  // the gather writes every byte of the block
+        launch_flac_frames(djobs.as<FlacJob>(), n_jobs, frames, rate, dslots.as<uint8_t>(), dsizes.as<int>(), nullptr);
+        launch_flac_place(djobs.as<FlacJob>(), n_jobs, frames, rate, 0, dsizes.as<int>(), dpre.as<unsigned>(), dftab.as<int2>(), dhdr.as<unsigned>(),
+                          ditems.as<int>(), djtab.as<int>(), nullptr);
+        launch_flac_gather_streams(n_jobs, frames, dslots.as<uint8_t>(), dsizes.as<int>(), dftab.as<int2>(), dhdr.as<unsigned>(), ditems.as<int>(), 0,
+                                   bound, dout.as<uint8_t>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        std::vector<int> info(flac_info_words(frames, n_jobs));
+        HIP_CHECK(hipMemcpy(info.data(), dsizes.p, info.size() * 4, hipMemcpyDeviceToHost));
+        const int* in = info.data() + frames;
+        for (int j = 0; j < n_jobs; ++j) {
+            offsets[j] = in[FLAC_INFO_WORDS * j + FLAC_INFO_BASE];
+            sizes_out[j] = in[FLAC_INFO_WORDS * j + FLAC_INFO_BYTES];
+            if (offsets[j] < 0 || (offsets[j] & 15) || sizes_out[j] < FLAC_HEADER_BYTES || offsets[j] + sizes_out[j] > bound)
+                throw EngineError(MI355VITS_ERR_INTERNAL, "flac: job " + std::to_string(j) + " placed outside the bound");
+        }
+        const long end = in[FLAC_INFO_WORDS * n_jobs];
+        if (end != offsets[n_jobs - 1] + sizes_out[n_jobs - 1]) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the block's end differs from the last file's");
+        *n_bytes = (size_t)end;
+        if (cap < *n_bytes) throw EngineError(MI355VITS_ERR_INVALID, "flac: the block has " + std::to_string(*n_bytes) + " bytes, out holds " + std::to_string(cap));
+        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)end, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, const float* peaks, int B, float ratio, int32_t* s_first,
                         int32_t* s_last) {
     return guarded(nullptr, [&] {

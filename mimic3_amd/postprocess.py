@@ -127,6 +127,32 @@ def request_wav(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Op
     return bytes(out.wav)
 
 
+def request_flac(session, ids_per_sentence: Sequence[Sequence[int]], break_ms: Optional[float] = None, shared: bool = False,
+                 **settings) -> bytes:
+    """``request_wav`` with the file as FLAC: the request's sentences in ONE engine call, ``break_ms`` between them, the int16
+    stream compressed on the GPU (lossless; ``InferenceSession.run_packed(..., compression="flac")``) — only the compressed bytes
+    cross to the host.  ``settings`` as for ``request_wav`` (any ``encoding`` but "s16le" is refused by the library).
+
+    ``shared=True``: through ``InferenceSession.run_request`` — on a session with a micro-batcher the request shares ONE engine call
+    with the requests of other clients that arrive meanwhile, whatever their ``limiter_ms``, ``true_peak`` or compression
+    (``mi355vits_run_streams2``), and still gets its own finished file; the same bytes."""
+    rows = [np.asarray(r, np.int64).reshape(-1) for r in ids_per_sentence]
+    if not rows or any(r.size == 0 for r in rows):
+        raise ValueError("request_flac needs at least one sentence, each with at least one phoneme id")
+    B, Tx = len(rows), max(r.size for r in rows)
+    ids = np.zeros((B, Tx), np.int64)
+    for b, r in enumerate(rows):
+        ids[b, : r.size] = r
+    feed = {"input": ids, "input_lengths": np.array([r.size for r in rows], np.int64),
+            "scales": np.asarray(settings.pop("scales", (0.667, 1.0, 0.8)), np.float32)}
+    sid = settings.pop("sid", None)
+    if sid is not None:
+        feed["sid"] = np.broadcast_to(np.asarray(sid, np.int64).reshape(-1), (B,)).copy()
+    lead_ms = [break_ms if (i and break_ms) else 0.0 for i in range(B)]
+    out = (session.run_request if shared else session.run_packed)(feed, lead_ms=lead_ms, compression="flac", **settings)
+    return bytes(out.flac)
+
+
 def marks(alignment, row: int, spans: Sequence) -> list:
     """Id ranges of one row -> speech marks (word / phoneme times for captions, visemes, a position for an SSML ``<mark>``).
 

@@ -922,6 +922,61 @@ class InferenceSession:
         self.last_lengths = out.lengths
         return out
 
+    def run_request(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
+                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+                    trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None, loudness: Optional[float] = None,
+                    ceiling_db: Optional[float] = None, limiter_ms: Optional[float] = None,
+                    true_peak: Optional[bool] = None, compression=_SESSION) -> "_native.PackedAudio":
+        """``run_stream`` with everything per request (``mi355vits_run_streams2``): the same keywords plus ``compression`` (``"flac"`` /
+        ``None``; else the session's ``output_compression``, as ``run_packed``), THROUGH the micro-batcher.  The limiter window, the
+        ceiling mode and the compression travel with the request's stream of the shared call, so requests group by ``sid`` presence,
+        phoneme-length class and output rate ONLY: clients that differ in ``limiter_ms``, ``true_peak`` or ``compression`` share one
+        engine call, and each still gets bitwise what ``run_packed`` gives it (with ``utterance_keys`` given or zero noise scales, as
+        for ``run_stream``).  A FLAC request's ``PackedAudio.flac`` is a view of its file in the batch's shared block.  A feed of more
+        than ``micro_batch_max`` rows, or a session without a micro-batcher, takes ``run_packed`` directly."""
+        comp = self.output_compression if compression is _SESSION else _compression_name(compression)
+        if comp and wav:
+            raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
+        ids, lengths, sid = self._feed(input_feed)
+        B = int(ids.shape[0])
+        if self._batcher is None or B > self._batcher._max or lengths.shape[0] != B:
+            return self.run_packed(input_feed, order=order, lead_ms=lead_ms, lead_samples=lead_samples, tail_ms=tail_ms, wav=wav,
+                                   volume=volume, utterance_keys=utterance_keys, sample_rate=sample_rate, encoding=encoding,
+                                   trim_db=trim_db, trim_keep_ms=trim_keep_ms, loudness=loudness, ceiling_db=ceiling_db,
+                                   limiter_ms=limiter_ms, true_peak=true_peak, compression=comp)
+        kw = self._pcm_kw(volume, utterance_keys)
+        for name in ("pcm_volume", "utterance_keys"):
+            if name in kw and np.ndim(kw[name]) > 0 and len(kw[name]) != B:
+                raise InvalidArgument(f"per-row '{name}' must have shape [batch]")
+        if sample_rate is not None:
+            kw["sample_rate"] = int(sample_rate)
+        rate = int(sample_rate or self.output_sample_rate or self.config.sample_rate)
+        if lead_ms is not None:
+            if lead_samples is not None:
+                raise InvalidArgument("give lead_ms or lead_samples, not both")
+            lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
+        ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
+        keep_ms = float(trim_keep_ms if trim_keep_ms is not None else self.edge_trim_keep_ms)
+        if keep_ms < 0:
+            raise ValueError("trim_keep_ms must be >= 0")
+        _check_stream_rows(order, lead_samples, B)  # against this request's own rows, before it shares a call with others
+        scales = np.asarray(input_feed["scales"], np.float32)
+        if scales.size not in (3, 3 * B):
+            raise InvalidArgument("'scales' must hold [noise_scale, length_scale, noise_w] (or one such row per sentence)")
+        kw["_kind"] = "request"  # never in one call with run_stream's requests: those read the window and the mode from the lane
+        # window, mode and compression are part of the stream's own settings (mi355vits_stream_args2): nothing to group by
+        kw["_stream"] = dict(order=order, lead_samples=lead_samples, tail_samples=int((float(tail_ms) / 1000.0) * rate), wav=bool(wav),
+                             encoding=_encoding_name(encoding) if encoding is not None else self.output_encoding,
+                             trim=(ratio, int((keep_ms / 1000.0) * rate)),
+                             loudness=_loudness_setting(loudness if loudness is not None else self.loudness_lufs,
+                                                        ceiling_db if ceiling_db is not None else self.loudness_ceiling_db),
+                             limiter=_native.limiter_window(limiter_ms if limiter_ms is not None else self.loudness_limiter_ms, rate),
+                             true_peak=bool(self.loudness_true_peak if true_peak is None else true_peak), compression=comp)
+        sid1 = None if sid is None else np.asarray(sid).reshape(-1)
+        out = self._batcher.submit(np.asarray(ids, np.int64), lengths.astype(np.int64), scales, sid1, kw).result()
+        self.last_lengths = out.lengths
+        return out
+
     @staticmethod
     def _pcm_kw(volume, utterance_keys) -> Dict[str, Any]:
         """``volume`` (percent, scalar or per row) and ``utterance_keys`` as the engine's keywords."""
