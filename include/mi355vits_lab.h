@@ -137,6 +137,85 @@ int mi355vits_test_mrf_stage(int device, const mi355vits_mrf_test* t);
  * Host arithmetic only: no kernel runs. */
 int mi355vits_lab_mrf_plan(int impl, int C, int nrb, const int32_t* k, const int32_t* d1, const int32_t* d2, int32_t* width,
                            int32_t* halo, int32_t* x_ring, int32_t* x1_ring);
+/* Kernel unit-test hook: ONE DDS stack of the stochastic duration predictor (csrc/kernels_misc.cpp) with what
+ * surrounds it, on host buffers:
+ *   pre     pre_mode 0: x = conv1x1(src) + pre_b (+ cond[b])      (StochasticDurationPredictor.pre + cond; pre_w [C, C, 1])
+ *           pre_mode 1: x = pre_w[c] * z[b, zch, t] + pre_b[c] + src[b, c, t]   (ConvFlow.pre on one channel + g; pre_w [C])
+ *   layers  x += gelu(LN2(conv1x1(gelu(LN1(dwconv_{K, K^i}(x * mask))))))   i = 0 .. n_layers - 1, LayerNorm over channels, eps 1e-5,
+ *           erf GELU; dw_w[i] [C, 1, K], w1x1[i] [C, C, 1]
+ *   proj    out = (conv1x1(x * mask) + proj_b) * mask     (proj_w [proj_cout, C, 1], or NULL: no proj, x_out only)
+ *   spline  (spline != 0; needs proj, z and proj_cout = 3 nb - 1, nb <= 16)  z[b, 1 - zch] <- RQS^-1(z[b, 1 - zch]; theta = out)
+ *           inside [-tail, tail], then z *= mask, as mi355vits_test_spline_inverse.
+ * The hook packs the 1x1 weights with the library's own pack functions, as the engine does for the chosen path.
+ * impl: 0 = one launch per piece (launch_convflow_pre or the pre conv; per layer launch_dds_dwconv_ln_gelu, the 1x1 conv, launch_layernorm
+ *           with add_to / gelu; the proj conv with in_len / out_len; launch_spline_inverse).  The convs run the f32-MFMA kernel, the
+ *           generic one where it does not take the shape (odd C), decided per conv as the engine does.  Any C >= 1, any odd K.
+ *       1 = the same pieces with launch_dds_layer per layer (k_dds_layer): C in {32, 64, 128, 192, 256}.
+ *       2 = launch_dds_stack in MATH_F32 (k_dds_stack<6>): C = 192, K = 3, n_layers <= 3 (the taps' reach <= 16 columns).
+ *       3 = launch_dds_stack in MATH_BF16X3 (k_dds_stack_b3<false>) or MATH_BF16W (k_dds_stack_b3<true>: the 1x1 / pre / proj weights
+ *           count with their leading bf16 term only).  The engine never launches the MATH_BF16W form — its tmath() maps BF16W to
+ *           BF16X3, durations must not move with the math mode — so this hook is the only way to reach k_dds_stack_b3<true>.
+ *     math: MATH_F32 for impl 0, 1, 2; MATH_BF16X3 or MATH_BF16W for impl 3.  impl 1 and 2 give the same bits below len[b], on the CPU
+ *           model and on the device (both form a LayerNorm's variance through dds_sq_sum).
+ * A shape or math mode the chosen path does not serve is MI355VITS_ERR_INVALID before any launch.
+ * At and past len[b] (0 <= len[b] <= T), per row; the prior contents of out, x_out and z go to the device first:
+ *   src, z  are READ there by every impl (clamped, unconditional loads), and every use is masked by select at len[b]: any finite or
+ *           non-finite bits may lie there.  Nothing below len[b] depends on them, on T or on another row.
+ *   x_out   is written at every column t < T.  Past len[b] it holds the same column arithmetic with every tap at or past len[b]
+ *           counted as zero — finite for finite src / z, a function of src and z THERE, never masked (the proj masks its input).
+ *   out     is written at every column t < T: exact zeros at len[b] <= t < T.
+ *   z       spline != 0: z[b, 1 - zch] is rewritten below len[b]; BOTH channels are exact zeros at len[b] <= t < T; z[b, zch] keeps
+ *           its contents below len[b].  spline == 0: no path writes z (the hook still reads the device's buffer back). */
+typedef struct mi355vits_dds_stack_test {
+    int32_t impl, math, B, C, T, K, n_layers, pre_mode, zch, proj_cout, spline, nb;
+    float tail, inv_sqrt_fc;
+    const float* src;         /* [B,C,T] */
+    const float* pre_w;       /* pre_mode 0: [C,C,1]; pre_mode 1: [C] */
+    const float* pre_b;       /* [C] */
+    const float* cond;        /* [B,C] or NULL; pre_mode 0 only */
+    const float* dw_w[4];     /* [C,1,K] */
+    const float* dw_b[4];     /* [C] */
+    const float* g1[4];       /* LN1 gamma, beta [C] */
+    const float* b1[4];
+    const float* w1x1[4];     /* [C,C,1] */
+    const float* bias1x1[4];  /* [C] */
+    const float* g2[4];       /* LN2 gamma, beta [C] */
+    const float* b2[4];
+    const float* proj_w;      /* [proj_cout,C,1] or NULL */
+    const float* proj_b;      /* [proj_cout] */
+    const int32_t* len;       /* [B] */
+    float* z;                 /* [B,2,T] in / out; NULL allowed with pre_mode 0 and no spline */
+    float* out;               /* [B,proj_cout,T]; NULL allowed without proj */
+    float* x_out;             /* [B,C,T] */
+} mi355vits_dds_stack_test;
+int mi355vits_test_dds_stack(int device, const mi355vits_dds_stack_test* t);
+/* Kernel unit-test hook: launch_spline_inverse (k_spline_inverse) alone: the rational-quadratic spline inverse with linear tails (HF
+ * modeling_vits.py: min width / height / derivative 1e-3, end derivatives from the constant) of x1 = z[b, 1 - ch_x0, t] with the
+ * parameters theta[b, :, t] ([B, 3 nb - 1, T]: nb widths and nb heights, both scaled by inv_sqrt_fc, nb - 1 interior derivatives),
+ * 2 <= nb <= 16 (anything else: MI355VITS_ERR_INVALID).  |x1| > tail, NaN: passed through.  z [B, 2, T] in / out.
+ * At and past len[b] (0 <= len[b] <= T): theta and z are read (any bits may lie there), both channels of z are written as exact
+ * zeros at len[b] <= t < T.  Below len[b], z[b, ch_x0] keeps its contents. */
+int mi355vits_test_spline_inverse(int device, int B, int T, int nb, int ch_x0, float tail, float inv_sqrt_fc, const float* theta,
+                                  const int32_t* len, float* z);
+/* Kernel unit-test hook: launch_durations (k_durations) alone.  z [B, 2, T], ch the channel read, ea_m / ea_logs the
+ * ElementwiseAffine's parameters, len [B], forced [B, T] or NULL, scales [B, 3] = noise_scale, length_scale, noise_w (length_scale
+ * is the one read) -> logw [B, T] = (z - ea_m) * exp(-ea_logs) * mask, w_ceil [B, T] = ceil(exp(logw) * mask * length_scale) (forced:
+ * forced[b, t] below len[b]); a w that is not below the frame cap 2^22 (+inf and NaN included), a forced count that is negative or above
+ * the cap: cap + 1.  cum [B, T] = the inclusive scan of w_ceil, saturating at 2 cap; ylen [B] = max(1, cum[b, T - 1]).
+ * At and past len[b] (0 <= len[b] <= T): every output is written at every t < T: logw and w_ceil are zero there, cum stays at its
+ * value.  z IS READ there and masked by a multiply: the caller keeps it finite (the engine's z is zero there: the spline writes it);
+ * forced is not read there. */
+int mi355vits_test_durations(int device, int B, int T, int ch, float ea_m, float ea_logs, const float* z, const int32_t* len,
+                             const int32_t* forced, const float* scales, float* logw, int32_t* w_ceil, int32_t* cum, int32_t* ylen);
+/* Kernel unit-test hook: launch_expand_prior (k_expand_prior; the length regulator + the prior's sample) with injected noise.
+ * stats [B, 2 I, Tx] = m_p | logs_p, cum [B, Tx] (non-decreasing, >= 0), ylen [B] (0 <= ylen[b] <= Ty), scales [B, 3] (noise_scale is
+ * the one read), injected [B, I, injected_frames] with injected_frames >= Ty, or NULL where every row's noise_scale is 0 (anything
+ * else would run the Philox generator, which has no reference here: MI355VITS_ERR_INVALID).
+ * z [B, I, Ty]: frame t of row b takes phoneme j = #{j : cum[b, j] <= t}: z = m_p[j] + injected * exp(logs_p[j]) * noise_scale (m_p[j]
+ * alone, bit for bit, at noise_scale = 0).  Every element of z is written: exact zeros at t >= ylen[b] and where j = Tx; injected is
+ * not read there, nor in a row whose noise_scale is 0. */
+int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
+                                const float* injected, int injected_frames, const float* scales, float* z);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
  * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
  * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros

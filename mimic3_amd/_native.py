@@ -55,6 +55,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
+    "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
 )
 
 
@@ -80,7 +81,17 @@ class MrfTest(ctypes.Structure):
         ("out_scale", ctypes.c_float), ("y", ctypes.POINTER(ctypes.c_float))]
 
 
-MATH_F32, MATH_BF16X3 = 0, 1  # csrc/kernels.h MathMode, MI355VITS_MATH_*
+class DdsStackTest(ctypes.Structure):
+    """struct mi355vits_dds_stack_test of include/mi355vits_lab.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("impl", "math", "B", "C", "T", "K", "n_layers", "pre_mode", "zch", "proj_cout", "spline", "nb")] + [
+        ("tail", ctypes.c_float), ("inv_sqrt_fc", ctypes.c_float)] + [
+        (n, ctypes.POINTER(ctypes.c_float)) for n in ("src", "pre_w", "pre_b", "cond")] + [
+        (n, ctypes.POINTER(ctypes.c_float) * 4) for n in ("dw_w", "dw_b", "g1", "b1", "w1x1", "bias1x1", "g2", "b2")] + [
+        ("proj_w", ctypes.POINTER(ctypes.c_float)), ("proj_b", ctypes.POINTER(ctypes.c_float)), ("len", ctypes.POINTER(ctypes.c_int32)),
+        ("z", ctypes.POINTER(ctypes.c_float)), ("out", ctypes.POINTER(ctypes.c_float)), ("x_out", ctypes.POINTER(ctypes.c_float))]
+
+
+MATH_F32, MATH_BF16X3, MATH_BF16W = 0, 1, 2  # csrc/kernels.h MathMode, MI355VITS_MATH_*
 
 
 class RunArgs(ctypes.Structure):
@@ -538,6 +549,10 @@ class NativeLibrary:
             L.mi355vits_lab_wn_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p]
             L.mi355vits_test_mrf_stage.argtypes = [ctypes.c_int, ctypes.POINTER(MrfTest)]
             L.mi355vits_lab_mrf_plan.argtypes = [ctypes.c_int] * 3 + [i32p] * 7
+            L.mi355vits_test_dds_stack.argtypes = [ctypes.c_int, ctypes.POINTER(DdsStackTest)]
+            L.mi355vits_test_spline_inverse.argtypes = [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, f32p, i32p, f32p]
+            L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
+            L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
 
     def _need_hooks(self):
         if not self.has_hooks:
@@ -865,6 +880,109 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return tuple(int(o.value) for o in out)
+
+    def test_dds_stack(self, src, pre_w, pre_b, layers, lengths, impl=2, math=None, cond=None, z=None, zch=0, proj_w=None, proj_b=None,
+                       spline=False, nb=0, tail=0.0, inv_sqrt_fc=0.0, out_prior=None, x_out_prior=None, device=0):
+        """One DDS stack of the stochastic duration predictor through one path (include/mi355vits_lab.h: mi355vits_test_dds_stack):
+        impl 0 = one launch per piece, 1 = launch_dds_layer per layer, 2 = k_dds_stack<6> (MATH_F32), 3 = k_dds_stack_b3 (MATH_BF16X3,
+        or MATH_BF16W through ``math``).  src [B, C, T]; pre_w [C, C, 1] (conv pre, with cond [B, C] or None) or [C] (affine pre on
+        z[:, zch]); layers = a list of dicts dw_w [C, 1, K], dw_b, g1, b1, w1x1 [C, C, 1], bias1x1, g2, b2; proj_w [Cp, C, 1] or None;
+        z [B, 2, T] or None.  out_prior / x_out_prior = what the output buffers hold before the launch (zeros).
+        Returns (x_out, out or None, z or None)."""
+        self._need_hooks()
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        src, pre_w, pre_b = f(src), f(pre_w), f(pre_b)
+        B, C, T = src.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        affine = pre_w.ndim == 1
+        assert pre_w.shape == ((C,) if affine else (C, C, 1)) and pre_b.shape == (C,) and ln.shape == (B,) and 1 <= len(layers) <= 4
+        t = DdsStackTest()
+        keep = []
+        K = np.asarray(layers[0]["dw_w"]).shape[2]
+        for i, lay in enumerate(layers):
+            for name, shape in (("dw_w", (C, 1, K)), ("dw_b", (C,)), ("g1", (C,)), ("b1", (C,)), ("w1x1", (C, C, 1)), ("bias1x1", (C,)),
+                                ("g2", (C,)), ("b2", (C,))):
+                a = f(lay[name])
+                assert a.shape == shape, (name, a.shape, shape)
+                keep.append(a)
+                getattr(t, name)[i] = _fptr(a)
+        c = None if cond is None else f(cond)
+        assert c is None or c.shape == (B, C)
+        zz = None if z is None else f(z).copy()
+        assert zz is None or zz.shape == (B, 2, T)
+        pw = None if proj_w is None else f(proj_w)
+        pb = None if proj_b is None else f(proj_b)
+        Cp = 0 if pw is None else pw.shape[0]
+        assert pw is None or (pw.shape == (Cp, C, 1) and pb is not None and pb.shape == (Cp,))
+        out = None if pw is None else (np.zeros((B, Cp, T), np.float32) if out_prior is None else f(out_prior).copy())
+        x_out = np.zeros_like(src) if x_out_prior is None else f(x_out_prior).copy()
+        assert x_out.shape == src.shape and (out is None or out.shape == (B, Cp, T))
+        t.impl, t.B, t.C, t.T, t.K, t.n_layers, t.pre_mode, t.zch = int(impl), B, C, T, K, len(layers), int(affine), int(zch)
+        t.math = (MATH_BF16X3 if impl == 3 else MATH_F32) if math is None else int(math)
+        t.proj_cout, t.spline, t.nb, t.tail, t.inv_sqrt_fc = Cp, int(bool(spline)), int(nb), float(tail), float(inv_sqrt_fc)
+        t.src, t.pre_w, t.pre_b, t.cond, t.proj_w, t.proj_b = _fptr(src), _fptr(pre_w), _fptr(pre_b), _fptr(c), _fptr(pw), _fptr(pb)
+        t.len, t.z, t.out, t.x_out = ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(zz), _fptr(out), _fptr(x_out)
+        rc = self.lib.mi355vits_test_dds_stack(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return x_out, out, zz
+
+    def test_spline_inverse(self, theta, z, lengths, nb, ch_x0=0, tail=5.0, inv_sqrt_fc=1.0, device=0) -> np.ndarray:
+        """launch_spline_inverse alone: theta [B, 3 nb - 1, T], z [B, 2, T], lengths [B] -> the new z (mi355vits_test_spline_inverse)."""
+        self._need_hooks()
+        theta = np.ascontiguousarray(theta, np.float32)
+        z = np.ascontiguousarray(z, np.float32).copy()
+        ln = np.ascontiguousarray(lengths, np.int32)
+        B, _, T = z.shape
+        assert z.shape == (B, 2, T) and theta.shape[0] == B and theta.shape[2] == T and ln.shape == (B,)
+        assert nb < 1 or theta.shape[1] >= 3 * min(nb, 16) - 1
+        rc = self.lib.mi355vits_test_spline_inverse(device, B, T, int(nb), int(ch_x0), float(tail), float(inv_sqrt_fc), _fptr(theta),
+                                                    ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(z))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return z
+
+    def test_durations(self, z, lengths, ea_m=0.0, ea_logs=0.0, ch=0, length_scale=1.0, forced=None, device=0):
+        """launch_durations alone: z [B, 2, T], lengths [B], length_scale a number or [B], forced [B, T] int32 or None ->
+        (logw [B, T], w_ceil [B, T], cum [B, T], ylen [B]) (mi355vits_test_durations).  The outputs start as -77 / -7.5e29."""
+        self._need_hooks()
+        z = np.ascontiguousarray(z, np.float32)
+        B, _, T = z.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        sc = np.zeros((B, 3), np.float32)
+        sc[:, 1] = np.asarray(length_scale, np.float32)
+        fo = None if forced is None else np.ascontiguousarray(forced, np.int32)
+        assert z.shape == (B, 2, T) and ln.shape == (B,) and (fo is None or fo.shape == (B, T))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        logw = np.full((B, T), -7.5e29, np.float32)
+        w_ceil, cum, ylen = np.full((B, T), -77, np.int32), np.full((B, T), -77, np.int32), np.full(B, -77, np.int32)
+        rc = self.lib.mi355vits_test_durations(device, B, T, int(ch), float(ea_m), float(ea_logs), _fptr(z), ln.ctypes.data_as(i32p),
+                                               None if fo is None else fo.ctypes.data_as(i32p), _fptr(sc), _fptr(logw),
+                                               w_ceil.ctypes.data_as(i32p), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return logw, w_ceil, cum, ylen
+
+    def test_expand_prior(self, stats, cum, ylen, Ty, noise_scale=0.0, injected=None, z_prior=None, device=0) -> np.ndarray:
+        """launch_expand_prior alone with injected noise: stats [B, 2 I, Tx], cum [B, Tx], ylen [B], noise_scale a number or [B],
+        injected [B, I, frames >= Ty] or None -> z [B, I, Ty] (mi355vits_test_expand_prior)."""
+        self._need_hooks()
+        stats = np.ascontiguousarray(stats, np.float32)
+        B, I2, Tx = stats.shape
+        I = I2 // 2
+        cum, ylen = np.ascontiguousarray(cum, np.int32), np.ascontiguousarray(ylen, np.int32)
+        sc = np.zeros((B, 3), np.float32)
+        sc[:, 0] = np.asarray(noise_scale, np.float32)
+        inj = None if injected is None else np.ascontiguousarray(injected, np.float32)
+        assert cum.shape == (B, Tx) and ylen.shape == (B,) and (inj is None or inj.shape[:2] == (B, I))
+        z = np.full((B, I, int(Ty)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
+        assert z.shape == (B, I, int(Ty))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        rc = self.lib.mi355vits_test_expand_prior(device, B, I, Tx, int(Ty), _fptr(stats), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p),
+                                                  _fptr(inj), 0 if inj is None else inj.shape[2], _fptr(sc), _fptr(z))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return z
 
     def test_resample(self, x, lengths, in_hz: int, out_hz: int, device=0):
         """The product's resampler launch (k_resample) on caller-given f32 rows: x [B, row_stride], lengths [B] valid samples

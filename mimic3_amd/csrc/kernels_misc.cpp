@@ -334,6 +334,27 @@ struct DdsLayerArgs {
     int B, C, T, K, dil;
 };
 
+// sum_i (v[i] - mean)^2 over a thread's channels, for k_dds_layer and k_dds_stack, which promise each other's bits.  On the device the
+// chain is spelled out: the square of element 1, then fused multiply-adds of elements 0, 2, 3, ...  That is what hipcc's contraction
+// makes of `q += d * d` in k_dds_layer (whose results therefore do not move); left to the compiler, k_dds_stack's second LayerNorm
+// got four fused and twelve unfused terms, and the two forms' rstd differed by an ulp in some columns.  The CPU model keeps the plain
+// sum: its compiler fuses nothing.
+template <int N>
+__device__ __forceinline__ float dds_sq_sum(const float (&v)[N], float mean) {
+#ifdef MI355_EMU
+    float q = 0.0f;
+    for (int i = 0; i < N; ++i) { const float d = v[i] - mean; q += d * d; }
+    return q;
+#else
+    const float d1 = v[1] - mean, d0 = v[0] - mean;
+    float q = d1 * d1;
+    q = fmaf(d0, d0, q);
+    MI355_UNROLL
+    for (int i = 2; i < N; ++i) { const float d = v[i] - mean; q = fmaf(d, d, q); }
+    return q;
+#endif
+}
+
 template <int NW>  // C = 32 NW
 __global__ __launch_bounds__(64 * NW) void k_dds_layer(DdsLayerArgs a) {
     constexpr int C = 32 * NW, NCG = 2 * NW, NTH = 64 * NW, NPT = 16;  // 16 channels per thread: c = cg + NCG i
@@ -384,9 +405,7 @@ __global__ __launch_bounds__(64 * NW) void k_dds_layer(DdsLayerArgs a) {
         MI355_UNROLL
         for (int i = 0; i < NPT; ++i) sum += v[i];
         const float mean = col_sum(sum) / (float)C;
-        float sq = 0.0f;
-        MI355_UNROLL
-        for (int i = 0; i < NPT; ++i) { const float d = v[i] - mean; sq += d * d; }
+        const float sq = dds_sq_sum(v, mean);
         const float rstd = 1.0f / sqrtf(col_sum(sq) / (float)C + 1e-5f);
         MI355_UNROLL
         for (int i = 0; i < NPT; ++i) {
@@ -435,9 +454,7 @@ __global__ __launch_bounds__(64 * NW) void k_dds_layer(DdsLayerArgs a) {
         MI355_UNROLL
         for (int i = 0; i < NPT; ++i) sum += z[i];
         const float mean = col_sum(sum) / (float)C;
-        float sq = 0.0f;
-        MI355_UNROLL
-        for (int i = 0; i < NPT; ++i) { const float d = z[i] - mean; sq += d * d; }
+        const float sq = dds_sq_sum(z, mean);
         const float rstd = 1.0f / sqrtf(col_sum(sq) / (float)C + 1e-5f);
         if (live) {
             float* yo = a.y + (long)b * C * a.T + t;
@@ -630,14 +647,22 @@ __device__ __forceinline__ float spline_inverse_at(const float* th, long stride,
     const float delta = in_h / in_w;
     const float d0 = dv[bin], d1 = dv[bin + 1];
     const float t1 = d0 + d1 - 2.0f * delta;
-    const float u = x1 - in_ch;
+    // The root is taken from the NEARER knot.  The reference's quadratic measures u from the lower knot; just under the upper one its
+    // qb^2 and 4 qa qc cancel (the discriminant there is (in_h d1)^2, small next to a flat knot) and float32 loses up to 1e-3 of z —
+    // and which bin an x1 within an ulp of a knot falls into is decided by the last bit of an expf.  The bin mirrored (x -> -x, y -> -y)
+    // is the same spline with d0 and d1 exchanged and u measured down from the upper knot, its root 1 - root: in the upper half that
+    // form has the small qc and no cancellation.  The lower half is the reference's expression as it always was.
+    const float u_lo = x1 - in_ch, u_hi = chh[bin + 1] - x1;
+    const bool upper = u_hi < u_lo;
+    const float u = upper ? u_hi : u_lo, dn = upper ? d1 : d0;
     const float t3 = u * t1;
-    const float qa = in_h * (delta - d0) + t3;
-    const float qb = in_h * d0 - t3;
+    const float qa = in_h * (delta - dn) + t3;
+    const float qb = in_h * dn - t3;
     const float qc = -delta * u;
-    const float disc = qb * qb - 4.0f * qa * qc;
+    // the discriminant is >= 0 inside the bin; rounding may leave it a few ulps below: that must not become a NaN duration
+    const float disc = fmaxf(qb * qb - 4.0f * qa * qc, 0.0f);
     const float root = (2.0f * qc) / (-qb - sqrtf(disc));
-    return root * in_w + in_cw;
+    return upper ? cw[bin + 1] - root * in_w : root * in_w + in_cw;
 }
 
 // One thread per (b,t)
@@ -863,10 +888,7 @@ __global__ __launch_bounds__(64 * NW) void k_dds_stack(DdsStackArgs a) {
             for (int h = 0; h < 2; ++h) {
                 if (h >= nh) continue;
                 mean[h] = st[h] / (float)C;
-                float q = 0.0f;
-                MI355_UNROLL
-                for (int i = 0; i < NPT; ++i) { const float d = v[h][i] - mean[h]; q += d * d; }
-                sq[h] = q;
+                sq[h] = dds_sq_sum(v[h], mean[h]);
             }
             col_sum(sq, nh, cb);
             MI355_UNROLL
@@ -936,10 +958,7 @@ __global__ __launch_bounds__(64 * NW) void k_dds_stack(DdsStackArgs a) {
             for (int h = 0; h < 2; ++h) {
                 if (h >= nh) continue;
                 mean[h] = st[h] / (float)C;
-                float q = 0.0f;
-                MI355_UNROLL
-                for (int i = 0; i < NPT; ++i) { const float d = z[h][i] - mean[h]; q += d * d; }
-                sq[h] = q;
+                sq[h] = dds_sq_sum(z[h], mean[h]);
             }
             col_sum(sq, nh, cb);
             MI355_UNROLL

@@ -701,6 +701,228 @@ int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t) {
     });
 }
 
+// one DDS stack of the stochastic duration predictor through a chosen path (include/mi355vits_lab.h says what each reads and writes
+// at and past len[b])
+int mi355vits_test_dds_stack(int device, const mi355vits_dds_stack_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->src || !t->pre_w || !t->pre_b || !t->len || !t->x_out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, C = t->C, T = t->T, K = t->K, NL = t->n_layers, PC = t->proj_w ? t->proj_cout : 0;
+        if (B < 1 || C < 1 || T < 1 || K < 1 || (K % 2) == 0 || NL < 1 || NL > DDS_STACK_MAX_LAYERS) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if ((long)B * C * T >= 0x7fffffffL / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+        if (t->pre_mode != DDS_PRE_CONV && t->pre_mode != DDS_PRE_AFFINE) throw EngineError(MI355VITS_ERR_INVALID, "pre_mode must be 0 or 1");
+        if (t->zch != 0 && t->zch != 1) throw EngineError(MI355VITS_ERR_INVALID, "zch must be 0 or 1");
+        for (int i = 0; i < NL; ++i)
+            if (!t->dw_w[i] || !t->dw_b[i] || !t->g1[i] || !t->b1[i] || !t->w1x1[i] || !t->bias1x1[i] || !t->g2[i] || !t->b2[i])
+                throw EngineError(MI355VITS_ERR_INVALID, "null layer argument");
+        if (t->proj_w && (!t->proj_b || !t->out || PC < 1)) throw EngineError(MI355VITS_ERR_INVALID, "proj needs proj_b, out and proj_cout >= 1");
+        if (t->pre_mode == DDS_PRE_AFFINE && !t->z) throw EngineError(MI355VITS_ERR_INVALID, "the affine pre needs z");
+        if (t->pre_mode == DDS_PRE_AFFINE && t->cond) throw EngineError(MI355VITS_ERR_INVALID, "cond goes with the conv pre only");
+        if (t->spline && (!t->proj_w || !t->z)) throw EngineError(MI355VITS_ERR_INVALID, "the spline needs proj and z");
+        if (t->spline && (t->nb < 2 || t->nb > 16)) throw EngineError(MI355VITS_ERR_INVALID, "spline: 2 <= nb <= 16");
+        if (t->spline && PC != 3 * t->nb - 1) throw EngineError(MI355VITS_ERR_INVALID, "spline: proj_cout must be 3 nb - 1");
+        for (int b = 0; b < B; ++b)
+            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        if (t->impl < 0 || t->impl > 3) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1, 2 or 3");
+        if (t->impl == 3 ? !math_on_bf16(t->math) : t->math != MATH_F32)
+            throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 for impl 0, 1 and 2, MATH_BF16X3 or MATH_BF16W for impl 3");
+        if (t->impl == 1 && !dds_layer_fused_supported(C)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused DDS layer");
+        if (t->impl >= 2 && !dds_stack_supported(C, K, NL, PC)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the DDS stack kernels");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)B * C * T, nz = (size_t)B * 2 * T, no = (size_t)B * PC * T;
+        auto upload = [](const void* p, size_t bytes) {
+            std::unique_ptr<DevBuf> d(new DevBuf(bytes));
+            if (bytes) HIP_CHECK(hipMemcpy(d->p, p, bytes, hipMemcpyHostToDevice));
+            return d;
+        };
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        auto vecf = [&](const float* p, size_t count) -> const float* {
+            keep.push_back(upload(p, count * 4));
+            return keep.back()->as<float>();
+        };
+        // a dense 1x1 conv's weights [Cout, C, 1] in the format of the chosen path, as Engine::add_conv_data stages them
+        const bool b3 = t->impl == 3;
+        auto conv_mfma = [&](int Cout) { return conv1d_mfma_supported(C, Cout, 1, 1); };
+        auto dense = [&](const float* w, int Cout) -> const float* {
+            if (b3) {
+                std::vector<uint32_t> p(bf16x3_packed_words_mode(Cout, C, 1, EPI_STD), 0u);
+                pack_conv_weights_bf16x3_mode(w, Cout, C, 1, EPI_STD, 1, p.data());
+                keep.push_back(upload(p.data(), p.size() * 4));
+            } else if (t->impl != 0 || conv_mfma(Cout)) {
+                std::vector<float> p(mfma_packed_floats(Cout, C, 1), 0.0f);
+                pack_conv_weights_mfma_mode(w, Cout, C, 1, EPI_STD, p.data());
+                keep.push_back(upload(p.data(), p.size() * 4));
+            } else {
+                keep.push_back(upload(w, (size_t)Cout * C * 4));
+            }
+            return keep.back()->as<float>();
+        };
+        DevBuf dsrc(n * 4), dxo(n * 4), dz(nz * 4), dout(no * 4), dl((size_t)B * 4), dcond((size_t)B * C * 4);
+        HIP_CHECK(hipMemcpy(dsrc.p, t->src, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dxo.p, t->x_out, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (t->z) HIP_CHECK(hipMemcpy(dz.p, t->z, nz * 4, hipMemcpyHostToDevice));
+        if (PC) HIP_CHECK(hipMemcpy(dout.p, t->out, no * 4, hipMemcpyHostToDevice));
+        if (t->cond) HIP_CHECK(hipMemcpy(dcond.p, t->cond, (size_t)B * C * 4, hipMemcpyHostToDevice));
+        const float* pre_w = t->pre_mode == DDS_PRE_AFFINE ? vecf(t->pre_w, C) : dense(t->pre_w, C);
+        const float* pre_b = vecf(t->pre_b, C);
+        const float *dw_w[DDS_STACK_MAX_LAYERS], *dw_b[DDS_STACK_MAX_LAYERS], *g1[DDS_STACK_MAX_LAYERS], *b1[DDS_STACK_MAX_LAYERS];
+        const float *w1[DDS_STACK_MAX_LAYERS], *bb[DDS_STACK_MAX_LAYERS], *g2[DDS_STACK_MAX_LAYERS], *b2[DDS_STACK_MAX_LAYERS];
+        for (int i = 0; i < NL; ++i) {
+            dw_w[i] = vecf(t->dw_w[i], (size_t)C * K); dw_b[i] = vecf(t->dw_b[i], C);
+            g1[i] = vecf(t->g1[i], C); b1[i] = vecf(t->b1[i], C);
+            w1[i] = dense(t->w1x1[i], C); bb[i] = vecf(t->bias1x1[i], C);
+            g2[i] = vecf(t->g2[i], C); b2[i] = vecf(t->b2[i], C);
+        }
+        const float* proj_w = PC ? dense(t->proj_w, PC) : nullptr;
+        const float* proj_b = PC ? vecf(t->proj_b, PC) : nullptr;
+        if (t->impl >= 2) {
+            DdsStackArgs a;
+            a.src = dsrc.as<float>(); a.pre_mode = t->pre_mode; a.pre_w = pre_w; a.pre_b = pre_b;
+            if (t->cond) { a.cond = dcond.as<float>(); a.cond_bs = C; }
+            a.z = t->z ? dz.as<float>() : nullptr; a.zch = t->zch;
+            a.n_layers = NL; a.K = K;
+            for (int i = 0; i < NL; ++i) {
+                a.dw_w[i] = dw_w[i]; a.dw_b[i] = dw_b[i]; a.g1[i] = g1[i]; a.b1[i] = b1[i];
+                a.w1x1[i] = w1[i]; a.bias1x1[i] = bb[i]; a.g2[i] = g2[i]; a.b2[i] = b2[i];
+            }
+            a.x_out = dxo.as<float>();
+            a.proj_w = proj_w; a.proj_b = proj_b; a.proj_cout = PC;
+            a.out = PC ? dout.as<float>() : nullptr;
+            a.spline = t->spline ? 1 : 0; a.nb = t->nb; a.tail = t->tail; a.inv_sqrt_fc = t->inv_sqrt_fc;
+            a.len = dl.as<int>(); a.B = B; a.T = T; a.math = t->math;
+            launch_dds_stack(a, C, nullptr);
+        } else {
+            // Engine::duration_predictor's launches without the stack kernels: x lives in d0 (d1 / d2: Engine::dds's scratch)
+            DevBuf d0(n * 4), d1(n * 4), d2(n * 4);
+            const long bs = (long)C * T;
+            auto conv1x1 = [&](const float* x, float* y, const float* w, const float* bias, int Cout, bool masked) {
+                ConvArgs a;
+                a.x = x; a.x_bs = bs; a.x_ld = T;
+                a.y = y; a.y_bs = (long)Cout * T; a.y_ld = T;
+                a.B = B; a.T = T; a.Cin = C; a.Cout = Cout; a.K = 1; a.bias = bias; a.pad = 0; a.w = w; a.math = MATH_F32;
+                if (masked) { a.in_len = dl.as<int>(); a.out_len = dl.as<int>(); }
+                return a;
+            };
+            auto run_conv = [&](const ConvArgs& a) {
+                if (conv_mfma(a.Cout)) launch_conv1d_mfma(a, nullptr);
+                else launch_conv1d_generic(a, nullptr);
+            };
+            float* X = d0.as<float>();
+            if (t->pre_mode == DDS_PRE_AFFINE) {
+                launch_convflow_pre(dz.as<float>(), t->zch, pre_w, pre_b, dsrc.as<float>(), B, C, T, X, nullptr);
+            } else {
+                ConvArgs a = conv1x1(dsrc.as<float>(), X, pre_w, pre_b, C, false);
+                if (t->cond) { a.cond = dcond.as<float>(); a.cond_bs = C; }
+                run_conv(a);
+            }
+            int dil = 1;
+            for (int i = 0; i < NL; ++i) {
+                if (t->impl == 1) {  // x ping-pongs (k_dds_layer reads its neighbours' OLD columns)
+                    float* dst = X == d0.as<float>() ? d1.as<float>() : d0.as<float>();
+                    launch_dds_layer(X, dst, dw_w[i], dw_b[i], g1[i], b1[i], w1[i], bb[i], g2[i], b2[i], dl.as<int>(), B, C, T, K, dil, nullptr);
+                    X = dst;
+                } else {
+                    launch_dds_dwconv_ln_gelu(X, dw_w[i], dw_b[i], g1[i], b1[i], dl.as<int>(), B, C, T, K, dil, d1.as<float>(), nullptr);
+                    run_conv(conv1x1(d1.as<float>(), d2.as<float>(), w1[i], bb[i], C, false));
+                    LNArgs ln;
+                    ln.x = d2.as<float>(); ln.y = X; ln.add_to = X; ln.gelu = 1;
+                    ln.B = B; ln.C = C; ln.T = T; ln.gamma = g2[i]; ln.beta = b2[i];
+                    launch_layernorm(ln, nullptr);
+                }
+                dil *= K;
+            }
+            HIP_CHECK(hipMemcpyAsync(dxo.p, X, n * 4, hipMemcpyDeviceToDevice, nullptr));
+            if (PC) run_conv(conv1x1(X, dout.as<float>(), proj_w, proj_b, PC, true));
+            if (t->spline)
+                launch_spline_inverse(dz.as<float>(), t->zch, dout.as<float>(), dl.as<int>(), B, T, t->nb, t->tail, t->inv_sqrt_fc, nullptr);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(t->x_out, dxo.p, n * 4, hipMemcpyDeviceToHost));
+        if (PC) HIP_CHECK(hipMemcpy(t->out, dout.p, no * 4, hipMemcpyDeviceToHost));
+        if (t->z) HIP_CHECK(hipMemcpy(t->z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_spline_inverse(int device, int B, int T, int nb, int ch_x0, float tail, float inv_sqrt_fc, const float* theta,
+                                  const int32_t* len, float* z) {
+    return guarded(nullptr, [&] {
+        if (!theta || !len || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || nb < 2 || nb > 16 || (ch_x0 != 0 && ch_x0 != 1)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape (2 <= nb <= 16)");
+        for (int b = 0; b < B; ++b)
+            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nt = (size_t)B * (3 * nb - 1) * T, nz = (size_t)B * 2 * T;
+        DevBuf dt(nt * 4), dz(nz * 4), dl((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dt.p, theta, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        launch_spline_inverse(dz.as<float>(), ch_x0, dt.as<float>(), dl.as<int>(), B, T, nb, tail, inv_sqrt_fc, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_durations(int device, int B, int T, int ch, float ea_m, float ea_logs, const float* z, const int32_t* len,
+                             const int32_t* forced, const float* scales, float* logw, int32_t* w_ceil, int32_t* cum, int32_t* ylen) {
+    return guarded(nullptr, [&] {
+        if (!z || !len || !scales || !logw || !w_ceil || !cum || !ylen) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || (ch != 0 && ch != 1)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        for (int b = 0; b < B; ++b)
+            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nz = (size_t)B * 2 * T, nt = (size_t)B * T;
+        DevBuf dz(nz * 4), dl((size_t)B * 4), df(nt * 4), ds((size_t)B * 3 * 4), dlw(nt * 4), dw(nt * 4), dc(nt * 4), dy((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
+        if (forced) HIP_CHECK(hipMemcpy(df.p, forced, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dlw.p, logw, nt * 4, hipMemcpyHostToDevice));  // the prior contents: a missing write shows
+        HIP_CHECK(hipMemcpy(dw.p, w_ceil, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, cum, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
+        launch_durations(dz.as<float>(), ch, ea_m, ea_logs, dl.as<int>(), forced ? df.as<int>() : nullptr, B, T, ds.as<float>(),
+                         dlw.as<float>(), dw.as<int>(), dc.as<int>(), dy.as<int>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(logw, dlw.p, nt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(w_ceil, dw.p, nt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cum, dc.p, nt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ylen, dy.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
+                                const float* injected, int injected_frames, const float* scales, float* z) {
+    return guarded(nullptr, [&] {
+        if (!stats || !cum || !ylen || !scales || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || I < 1 || Tx < 1 || Ty < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if (injected && injected_frames < Ty) throw EngineError(MI355VITS_ERR_INVALID, "injected_frames must cover Ty");
+        for (int b = 0; b < B; ++b) {
+            if (ylen[b] < 0 || ylen[b] > Ty) throw EngineError(MI355VITS_ERR_INVALID, "ylen out of range");
+            if (!injected && scales[3 * b] != 0.0f) throw EngineError(MI355VITS_ERR_INVALID, "noise_scale != 0 needs injected noise (no Philox path here)");
+            for (int j = 0; j < Tx; ++j)
+                if (cum[(size_t)b * Tx + j] < (j ? cum[(size_t)b * Tx + j - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t ns = (size_t)B * 2 * I * Tx, nc = (size_t)B * Tx, ni = injected ? (size_t)B * I * injected_frames : 0, nz = (size_t)B * I * Ty;
+        DevBuf dst(ns * 4), dc(nc * 4), dy((size_t)B * 4), di(ni * 4), ds((size_t)B * 3 * 4), dz(nz * 4), du((size_t)B * 8);
+        HIP_CHECK(hipMemcpy(dst.p, stats, ns * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, cum, nc * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (ni) HIP_CHECK(hipMemcpy(di.p, injected, ni * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(du.p, 0, (size_t)B * 8));
+        launch_expand_prior(dst.as<float>(), dc.as<int>(), dy.as<int>(), injected ? di.as<float>() : nullptr, injected_frames, B, I, Tx, Ty,
+                            ds.as<float>(), 0ull, du.as<unsigned long long>(), dz.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_lab_wn_plan(int B, int T, int K, int dilation, int32_t* b3_tile, int32_t* f32_geometry) {
     return guarded(nullptr, [&] {
         if (B < 1 || T < 1 || K < 1 || (K % 2) == 0 || dilation < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
