@@ -1104,39 +1104,17 @@ class _ResultHolder:
             pass
 
 
-class _PackedHolder:
-    """The same for one ``mi355vits_packed_result``: the pinned block lives as long as any view of it."""
+class _BlockHolder:
+    """The same for one ``mi355vits_packed_result`` or one streams result: ONE pinned block (shared by the views of all its
+    streams) that lives as long as any view of it and then goes back through ``free``, the struct's own free function."""
 
-    def __init__(self, native: "NativeLibrary", r: PackedResult):
-        self._native = native
-        self._r = PackedResult()
-        ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(PackedResult))
-
-    def view(self) -> np.ndarray:
-        """Every byte of the block (header, if any, + data) as one uint8 array that owns the holder."""
-        n = int(self._r.n_bytes)
-        buf = (ctypes.c_uint8 * n).from_address(ctypes.addressof(self._r.bytes.contents))
-        buf._holder = self
-        return np.frombuffer(buf, dtype=np.uint8, count=n)
-
-    def __del__(self):
-        try:
-            self._native.lib.mi355vits_free_packed(ctypes.byref(self._r))
-        except Exception:
-            pass
-
-
-class _StreamsHolder:
-    """The same for one ``mi355vits_streams_result``: ONE pinned block shared by the views of all its streams."""
-
-    def __init__(self, native: "NativeLibrary", r):
-        self._native = native
-        self._r = type(r)()  # StreamsResult, or StreamsResult2 (mi355vits_free_streams2)
+    def __init__(self, free, r):
+        self._free = free
+        self._r = type(r)()
         ctypes.memmove(ctypes.byref(self._r), ctypes.byref(r), ctypes.sizeof(type(r)))
-        self._free = native.lib.mi355vits_free_streams2 if isinstance(r, StreamsResult2) else native.lib.mi355vits_free_streams
 
     def view(self) -> np.ndarray:
-        """Every byte of the block as one uint8 array that owns the holder."""
+        """Every byte of the block (headers, if any, + data) as one uint8 array that owns the holder."""
         n = int(self._r.n_bytes)
         buf = (ctypes.c_uint8 * n).from_address(ctypes.addressof(self._r.bytes.contents))
         buf._holder = self
@@ -1491,6 +1469,7 @@ class Engine:
     def _take_streams(self, r, flags) -> List["PackedAudio"]:
         """``flags[s]`` = (trimmed, normalised) of stream s: which of ``first`` / ``end`` and ``lufs`` / ``gain`` / ``limited`` it fills."""
         S, E = int(r.n_streams), int(r.n_entries)
+        free = self.native.lib.mi355vits_free_streams2 if isinstance(r, StreamsResult2) else self.native.lib.mi355vits_free_streams
         try:
             per_stream = lambda p: np.ctypeslib.as_array(p, shape=(S,)).copy()  # noqa: E731
             per_entry = lambda p: np.ctypeslib.as_array(p, shape=(E,)).copy()  # noqa: E731
@@ -1503,9 +1482,9 @@ class Engine:
             nframes = per_stream(r.frames) if v2 else np.zeros(S, np.int32)
             plain_bytes = int(r.uncompressed_bytes) if v2 else int(r.n_bytes)
         except BaseException:
-            (self.native.lib.mi355vits_free_streams2 if isinstance(r, StreamsResult2) else self.native.lib.mi355vits_free_streams)(ctypes.byref(r))
+            free(ctypes.byref(r))
             raise
-        block = _StreamsHolder(self.native, r).view()  # the views below keep the block alive: no per-stream copy
+        block = _BlockHolder(free, r).view()  # the views below keep the block alive: no per-stream copy
         out = []
         for s in range(S):
             enc = _ENCODING_NAMES[int(encs[s])]
@@ -1547,7 +1526,7 @@ class Engine:
         except BaseException:
             self.native.lib.mi355vits_free_packed(ctypes.byref(r))
             raise
-        block = _PackedHolder(self.native, r).view()
+        block = _BlockHolder(self.native.lib.mi355vits_free_packed, r).view()
         pcm = None if compression else block[hdr: hdr + data].view(dtype)
         first = end = None
         if trimmed:

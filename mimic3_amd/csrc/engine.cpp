@@ -1563,7 +1563,7 @@ void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows,
     copy_out(args.flags, out);
 }
 
-void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan, StreamsPlan* streams) {
+void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan) {
     const mi355vits_config& c = cfg_;
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     const float* row_scales = rows ? rows->scales : nullptr;
@@ -1712,15 +1712,13 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
             throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": " + std::to_string(h_olen_[b]) + " samples at " + std::to_string(run_hz_) + " Hz do not fit 32 bits");
         if (rs) Lo_ = std::max<long>(Lo_, (long)h_olen_[b]);
     }
-    if (plan) place_pack(*plan);  // offsets from the frame counts just read; the size limits, before phase B is sized
-    if (streams) place_streams(*streams);  // likewise (no stream trims or normalises: run_streams)
+    if (plan) place(*plan);  // places from the frame counts just read (no early plan trims, normalises or compresses); the size limits, before phase B is sized
 
     // ---------------- phase B workspace
     const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
     ArenaCount size_b;
     layout_b(size_b, B, Ty, nz_frames, rs ? Lo_ : 0);
-    if (plan) layout_pack(size_b, *plan);
-    if (streams) layout_streams(size_b, *streams);
+    if (plan) layout(size_b, *plan);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
     layout_b(arena_b_, B, Ty, nz_frames, rs ? Lo_ : 0);
@@ -1730,15 +1728,12 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     o_alen_ = rs ? d_rtab_ : d_alen_;
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
-    if (plan) layout_pack(arena_b_, *plan);
-    if (streams) layout_streams(arena_b_, *streams);
+    if (plan) layout(arena_b_, *plan);
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
-    // (a packed call's segment table sits right behind d_slen_ in the arena: the same copy brings it)
-    const size_t table_words = plan ? (size_t)plan->seg_rows() * plan->n : streams ? pack_streams_table_words(streams->entries, (int)streams->streams.size()) : 0;
-    h_slen_.assign((plan || streams) ? (size_t)(d_pack_seg_ - d_slen_) + table_words : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
-    if (plan) fill_pack_seg(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
-    if (streams) fill_streams_table(*streams, h_slen_.data() + (d_pack_seg_ - d_slen_));
+    // (a plan's table sits right behind d_slen_ in the arena: the same copy brings it; no early block has a curve row)
+    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + plan->table_words() : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
+    if (plan) fill_table(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
     {
         long f = 1;
         for (int i = 0; i <= c.n_upsamples; ++i) {
@@ -1765,9 +1760,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
 
     have_pcm_ = false;
     if (plan) {
-        launch_pack(*plan);  // the packed stream and nothing else: MI355VITS_WANT_* / DEVICE_ONLY are not looked at
-    } else if (streams) {
-        launch_streams(*streams);  // the block of streams and nothing else, likewise
+        launch(*plan);  // the packed stream or block and nothing else (the pack kernel alone: no early plan is compressed): MI355VITS_WANT_* / DEVICE_ONLY are not looked at
     } else if (args.flags & MI355VITS_WANT_PCM16) {
         ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)Lo_);
         launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B, (int)Lo_, d_pcm_, Lo_, stream_, d_vol_);

@@ -297,25 +297,29 @@ class Engine {
         int bps() const { return pack_bytes_per_sample(set.enc); }
         size_t header_bytes() const { return !wav ? 0 : set.enc == PACK_ENC_S16 ? 44 : 58; }  // PCM form / non-PCM form (fmt 18 + fact)
     };
-    // what a streams call puts where: one PackPlan per stream (with that stream's settings), then the streams' places in the block
-    struct StreamsPlan {
+    // What a packed-form call puts where: one PackPlan per stream (with that stream's settings), then the streams' places in the block.
+    // single: a packed call (run_packed / fetch_packed) — exactly one stream, k_pack's segment table, no block and no header on the
+    // device, its FLAC frames by k_flac_gather.  Else the block form of a streams call: k_pack_streams, k_flac_place,
+    // k_flac_gather_streams.  The two device forms differ for a measured reason; everything around them is one.
+    struct OutputPlan {
+        bool single = false;
         std::vector<PackPlan> streams;
         std::vector<int64_t> begin, data;  // block byte offset of each stream's first byte (its header) / first data byte (16-byte aligned)
         int64_t n_bytes = 0, audio = 0;    // what k_pack_streams writes (without a compressed stream: the block); the audio samples in it
         int entries = 0;
-        bool curved = false;               // the limiter engages on some entry: the table has its curve row
-        // v2 with compressed streams.  k_pack_streams' buffer holds the uncompressed streams exactly as v1 lays them
+        bool curved = false;               // the limiter engages on some entry: the block's table has its curve row
+        // Compressed streams.  k_pack_streams' buffer holds the uncompressed streams exactly as v1 lays them
         // out — [0, plain_bytes) —, then from the next multiple of 16 every compressed stream's samples as a headerless S16LE stream
         // (src[s], 16-byte aligned): the streams in `dev` order.  begin / data of a compressed stream are known once its sizes are.
-        std::vector<int> dev;              // the streams in the order of their places in k_pack_streams' buffer
+        // (single: its one stream is k_pack's, src 0)
+        std::vector<int> dev;              // the streams in the order of their places in the pack kernel's buffer
         std::vector<int64_t> src;          // compressed streams: where their samples sit in that buffer (else -1)
         std::vector<long> frames;          // compressed streams: their FLAC frames (else 0)
         int64_t plain_bytes = 0;           // R: the v1 block of the uncompressed streams
         int64_t flac_base = 0, flac_bound = 0;  // (R + 15) & ~15; the bound of the bytes behind it
         long n_frames = 0;                 // of all compressed streams
         int n_flac = 0;
-        bool compressed() const { return n_flac > 0; }  // (after place_streams)
-        bool compressed_planned() const {                // some stream asks for FLAC (from plan_streams on)
+        bool compressed() const {          // some stream asks for FLAC
             for (const PackPlan& p : streams)
                 if (p.set.flac()) return true;
             return false;
@@ -325,67 +329,73 @@ class Engine {
                 if (p.set.trimmed() || p.set.normalised()) return true;
             return false;
         }
+        // the words of the kernel's table: the segment table [seg_rows][n], or the entry rows and a record per stream
+        size_t table_words() const {
+            return single ? (size_t)streams[0].seg_rows() * streams[0].n : pack_streams_table_words(entries, (int)streams.size(), curved);
+        }
     };
-    template <typename A> void layout_streams(A& ar, const StreamsPlan& sp) {
-        d_pack_seg_ = ar.template alloc<int>(pack_streams_table_words(sp.entries, (int)sp.streams.size(), sp.curved));
-        d_pack_ = ar.template alloc<uint8_t>(pack_streams_capacity((long)sp.n_bytes));
-        if (!sp.compressed()) return;
-        // behind it: a job per compressed stream, a slot per frame, the words the host reads (sizes, FLAC_INFO_* per job, the block's
-        // end), the scan and the frames' places, the headers, and the compressed region of the block
-        d_flac_jobs_ = ar.template alloc<FlacJob>((size_t)sp.n_flac);
-        d_flac_slots_ = ar.template alloc<uint8_t>((size_t)sp.n_frames * FLAC_SLOT_BYTES + 16);
-        d_flac_sizes_ = ar.template alloc<int>(flac_info_words(sp.n_frames, sp.n_flac));
-        d_flac_pre_ = ar.template alloc<unsigned>((size_t)sp.n_frames + 1);
-        d_flac_ftab_ = ar.template alloc<int2>((size_t)sp.n_frames + 1);
-        d_flac_hdr_ = ar.template alloc<unsigned>((size_t)FLAC_HDR_WORDS * sp.n_flac);
-        d_flac_items_ = ar.template alloc<int>(flac_gather_items((long)sp.flac_bound));
-        d_flac_jtab_ = ar.template alloc<int>((size_t)FLAC_JTAB_ROWS * sp.n_flac);
-        d_flac_out_ = ar.template alloc<uint8_t>((size_t)sp.flac_bound + 16);
-    }
-    // Packed calls only: the plan's segment table and stream, behind everything layout_b placed — no other pointer moves, so a
-    // call that packs nothing runs on the layout it always had.
-    template <typename A> void layout_pack(A& ar, const PackPlan& plan) {
-        d_pack_seg_ = ar.template alloc<int>((size_t)plan.seg_rows() * plan.n);
-        d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(plan.set.enc, (long)plan.total));  // in bytes, the last store's overrun included
-    }
-    // FLAC packs only, behind layout_pack in the same arena: the one job (the S16LE stream k_pack wrote), a slot and a size word per
-    // frame (+ the total), the frames' offsets, and the frames back to back — what the host copies
-    template <typename A> void layout_flac(A& ar, const PackPlan& plan) {
-        const size_t frames = (size_t)flac_frames((long)plan.total);
-        d_flac_jobs_ = ar.template alloc<FlacJob>(1);
-        d_flac_slots_ = ar.template alloc<uint8_t>(frames * FLAC_SLOT_BYTES);
-        d_flac_sizes_ = ar.template alloc<int>(frames + 1);
-        d_flac_offsets_ = ar.template alloc<long long>(frames);
-        d_flac_out_ = ar.template alloc<uint8_t>(flac_out_capacity((long)frames, (long)plan.total));
+    // Packed-form calls only: the plan's table and its stream or block, behind everything layout_b placed — no other pointer moves,
+    // so a call that packs nothing runs on the layout it always had.  Behind them, with a compressed stream, what the FLAC launches of
+    // the form need.  Run against ArenaCount for the size, then against the arena.
+    template <typename A> void layout(A& ar, const OutputPlan& op) {
+        d_pack_seg_ = ar.template alloc<int>(op.table_words());
+        if (op.single) {
+            const PackPlan& plan = op.streams[0];
+            d_pack_ = ar.template alloc<uint8_t>(pack_capacity_bytes(plan.set.enc, (long)plan.total));  // in bytes, the last store's overrun included
+            if (!op.compressed()) return;
+            // the one job (the S16LE stream k_pack wrote), a slot and a size word per frame (+ the total), the frames' offsets, and
+            // the frames back to back — what the host copies
+            const size_t frames = (size_t)op.n_frames;
+            d_flac_jobs_ = ar.template alloc<FlacJob>(1);
+            d_flac_slots_ = ar.template alloc<uint8_t>(frames * FLAC_SLOT_BYTES);
+            d_flac_sizes_ = ar.template alloc<int>(frames + 1);
+            d_flac_offsets_ = ar.template alloc<long long>(frames);
+            d_flac_out_ = ar.template alloc<uint8_t>(flac_out_capacity((long)frames, (long)plan.total));
+            return;
+        }
+        d_pack_ = ar.template alloc<uint8_t>(pack_streams_capacity((long)op.n_bytes));
+        if (!op.compressed()) return;
+        // a job per compressed stream, a slot per frame, the words the host reads (sizes, FLAC_INFO_* per job, the block's end), the
+        // scan and the frames' places, the headers, and the compressed region of the block
+        d_flac_jobs_ = ar.template alloc<FlacJob>((size_t)op.n_flac);
+        d_flac_slots_ = ar.template alloc<uint8_t>((size_t)op.n_frames * FLAC_SLOT_BYTES + 16);
+        d_flac_sizes_ = ar.template alloc<int>(flac_info_words(op.n_frames, op.n_flac));
+        d_flac_pre_ = ar.template alloc<unsigned>((size_t)op.n_frames + 1);
+        d_flac_ftab_ = ar.template alloc<int2>((size_t)op.n_frames + 1);
+        d_flac_hdr_ = ar.template alloc<unsigned>((size_t)FLAC_HDR_WORDS * op.n_flac);
+        d_flac_items_ = ar.template alloc<int>(flac_gather_items((long)op.flac_bound));
+        d_flac_jtab_ = ar.template alloc<int>((size_t)FLAC_JTAB_ROWS * op.n_flac);
+        d_flac_out_ = ar.template alloc<uint8_t>((size_t)op.flac_bound + 16);
     }
     // ---- everything behind the waveform: engine_results.cpp
     // what every fetch starts with: a result struct to fill, zeroed; a completed run to serve; its device current
     template <typename R> void begin_fetch(R* out, const char* call, bool call_in_null_text = true);
     void copy_out(uint32_t want, mi355vits_result* out);
-    // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with a pack plan
-    // the packed stream instead (its offsets made from the frame counts, its table uploaded with the per-stage lengths)
-    // (or with a streams plan the block of streams, likewise)
-    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, PackPlan* plan, StreamsPlan* streams = nullptr);
+    // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with an output plan
+    // the packed stream or block instead (its places made from the frame counts, its table uploaded with the per-stage lengths)
+    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan);
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
-    void place_pack(PackPlan& plan) const;                                           // offsets / total from h_ylen_; the size limits
-    void fill_pack_seg(const PackPlan& plan, int* seg) const;                       // the kernel's table [plan.seg_rows()][n] (kernels.h: PACK_SEG_*)
-    void launch_pack(const PackPlan& plan);
-    void pack_last_run(PackPlan& plan, mi355vits_packed_result* out);  // fetch_packed behind its checks; the second half of a trimmed run_packed
+    void plan_single(const mi355vits_pack_args* pack, int B, OutputPlan& op) const;  // a packed call's plan: plan_pack under the handle's settings
     // validates every stream, naming it (v1's streams arrive as v2 ones carrying the handle's window and mode, uncompressed)
-    void plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, StreamsPlan& sp) const;
+    void plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, OutputPlan& op) const;
     std::vector<mi355vits_stream_args2> streams_v1(const mi355vits_stream_args* streams, int n_streams) const;
-    void place_streams(StreamsPlan& sp) const;                          // place_pack per stream, then the block's layout and its limit
-    void fill_streams_table(const StreamsPlan& sp, int* tab) const;     // kernels.h: PACK_ENT_* / PACK_STREAM_*
-    void launch_streams(const StreamsPlan& sp);
-    // fetch_streams behind its checks; the second half of a measured run_streams (R: mi355vits_streams_result or mi355vits_streams_result2)
-    template <typename R> void streams_last_run(StreamsPlan& sp, R* out);
-    template <typename R> void copy_out_streams(StreamsPlan& sp, R* out);
-    template <typename R> void run_streams_plan(const mi355vits_run_args& args, const mi355vits_row_args* rows, StreamsPlan& sp, R* out);
-    void launch_flac_streams(const StreamsPlan& sp);  // the compressed streams' samples in d_pack_ -> frames, places, d_flac_out_
+    // The one pipeline over a plan; each step branches on `single` only where the device form differs.
+    void place_pack(PackPlan& plan) const;         // a stream's offsets / total from h_olen_ (and the edges, the loudness); the size limits
+    void place(OutputPlan& op) const;              // place_pack per stream, then (block form) the block's layout and its limit
+    void fill_table(const OutputPlan& op, int* tab) const;  // kernels.h: PACK_SEG_*, or PACK_ENT_* / PACK_STREAM_*
+    void launch(const OutputPlan& op);             // the pack kernel of the form, then launch_flac with a compressed stream
+    void launch_flac(const OutputPlan& op);        // the compressed streams' samples in d_pack_ -> frames, sizes / places, d_flac_out_
+    // Behind a fetch's checks, and the second half of a measured or compressed run: measure (ONE synchronisation, or none), place,
+    // the limiter's curves, the buffers behind the run's layout or in arena_p_, the table's upload, launch.
+    void finish_last_run(OutputPlan& op);
+    // R: mi355vits_packed_result (single plans), mi355vits_streams_result or mi355vits_streams_result2
+    template <typename R> void output_last_run(OutputPlan& op, R* out);  // finish_last_run, then the copy-out
+    template <typename R> void run_output(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan& op, R* out);
+    // FLAC: the sizes first (ONE synchronisation more than uncompressed), then exactly the frames behind the header the host writes
+    void copy_out_plan(OutputPlan& op, mi355vits_packed_result* out);
+    template <typename R> void copy_out_plan(OutputPlan& op, R* out);  // the block of a streams call
+    void flac_prof_bytes(double bytes);  // the frames' bytes onto the pack.flac record under way, once the host knows them
     void find_edges(float ratio);                                      // h_edges_ of the last run at `ratio` (k_edges, 8 B bytes, one synchronisation) unless held
-    void copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out);
-    void launch_flac(const PackPlan& plan);  // the stream at d_pack_ -> frames, sizes, d_flac_out_
-    void copy_out_flac(const PackPlan& plan, mi355vits_packed_result* out);  // sizes, ONE synchronisation more, then exactly the frames
     // k_edges and its copy on the stream for each of the distinct non-zero `ratios` the host does not hold; true: a synchronisation is
     // owed.  keep: what the host holds at other ratios stays (a streams call); else the ratio measured replaces it, as ever
     bool enqueue_edges(const std::vector<float>& ratios, bool keep);
@@ -514,17 +524,16 @@ class Engine {
     std::vector<int> h_ylen_;
     std::vector<unsigned char> h_in_;  // the call's host inputs, laid out like their device block (one upload)
     std::vector<int> h_slen_;         // per-stage valid lengths + audio lengths (one upload; packed calls: + the segment table)
-    std::vector<int> h_pack_seg_;     // fetch_packed's segment table (its own upload)
+    std::vector<int> h_pack_seg_;     // finish_last_run's table (its own upload)
     std::vector<LimitJob> h_limit_jobs_;  // k_limit's job table (its own upload)
     float* d_curve_ = nullptr;        // the curves of the pack being made (arena_lm_), nullptr when the limiter engages on no entry
-    // FLAC packs only (layout_flac)
+    // plans with a compressed stream only (layout)
     FlacJob* d_flac_jobs_ = nullptr;
     uint8_t *d_flac_slots_ = nullptr, *d_flac_out_ = nullptr;
     int* d_flac_sizes_ = nullptr;
     long long* d_flac_offsets_ = nullptr;
-    FlacJob h_flac_job_{};            // its own upload: a member outlives the copy
-    std::vector<FlacJob> h_flac_jobs_;  // a streams call's jobs, likewise
-    unsigned *d_flac_pre_ = nullptr, *d_flac_hdr_ = nullptr;  // streams calls only (layout_streams)
+    std::vector<FlacJob> h_flac_jobs_;  // the jobs' own upload: a member outlives the copy
+    unsigned *d_flac_pre_ = nullptr, *d_flac_hdr_ = nullptr;  // the block form only
     int2* d_flac_ftab_ = nullptr;
     int *d_flac_items_ = nullptr, *d_flac_jtab_ = nullptr;
     std::vector<int> h_flac_sizes_;   // the frame sizes and their total, as copied

@@ -318,54 +318,12 @@ void Engine::place_pack(PackPlan& plan) const {
     check_pack_size(-1, plan.total, plan.wav, set.enc);
 }
 
-void Engine::fill_pack_seg(const PackPlan& plan, int* seg) const {
-    const PackSettings& set = plan.set;
-    const size_t n = plan.n;
-    for (size_t i = 0; i < n; ++i) {
-        seg[PACK_SEG_OFFSET * n + i] = (int)plan.offsets[i];
-        seg[PACK_SEG_ROW * n + i] = plan.order[i];
-        seg[PACK_SEG_LENGTH * n + i] = (int)plan.lengths[i];
-        if (set.trimmed()) seg[PACK_SEG_SKIP * n + i] = plan.skip[i];
-        if (set.normalised()) {
-            // the entry's f32 scale: 32767 * gain in double, rounded once (F32LE: the gain itself)
-            const float scale = set.enc == PACK_ENC_F32 ? (float)plan.gain[i] : (float)(32767.0 * plan.gain[i]);
-            memcpy(&seg[pack_seg_scale_row(set.trimmed()) * n + i], &scale, 4);
-        }
-        if (plan.curved()) seg[pack_seg_curve_row(set.trimmed()) * n + i] = plan.curve[i];
-    }
-}
-
-void Engine::launch_pack(const PackPlan& plan) {
-    static const char* const labels[] = {"pcm16.pack", "pack.ulaw", "pack.alaw", "pack.f32"};  // by PackEncoding
-    ProfScope ps(prof_, labels[plan.set.enc], 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
-    m355::launch_pack(plan.set.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_,
-                      plan.set.trimmed(), plan.set.normalised(), plan.curved() ? d_curve_ : nullptr);
-}
-
-void Engine::copy_out_packed(const PackPlan& plan, mi355vits_packed_result* out) {
-    const int n = plan.n;
-    Owner* own = new_owner(out);
-    out->n = n;
-    out->total_samples = plan.total;
-    out->offsets = own->alloc<int64_t>(n);
-    out->lengths = own->alloc<int64_t>(n);
-    out->peaks = own->alloc<float>(n);
-    const size_t hdr = plan.header_bytes(), data = (size_t)plan.bps() * (size_t)plan.total;
-    const size_t pad = (plan.wav && (data & 1)) ? 1 : 0;  // the RIFF pad byte (write_wav_header)
-    const size_t lead = hdr == 58 ? 6 : 0;  // the 58-byte header starts 6 bytes into the block: the data behind it keeps the block's alignment
-    out->bytes = static_cast<uint8_t*>(own->take_pinned(lead + hdr + data + pad + 16)) + lead;
-    out->n_bytes = hdr + data + pad;
-    out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);  // the first data byte, whatever the encoding
-    std::vector<unsigned> pk(B_);
-    HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
-    if (plan.wav) write_wav_header(out->bytes, plan.set.enc, (uint32_t)run_hz_, plan.total, data);  // the rate the run ran at
-    for (int i = 0; i < n; ++i) {
-        out->offsets[i] = plan.offsets[i];
-        out->lengths[i] = plan.lengths[i];
-    }
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int i = 0; i < n; ++i) memcpy(&out->peaks[i], &pk[plan.order[i]], 4);
+// A packed call's plan: one stream under the handle's settings, read now.
+void Engine::plan_single(const mi355vits_pack_args* pack, int B, OutputPlan& op) const {
+    op.single = true;
+    op.streams.assign(1, PackPlan());
+    plan_pack(pack, B, pack_, op.streams[0]);
+    op.entries = op.streams[0].n;
 }
 
 void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
@@ -373,97 +331,51 @@ void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    PackPlan plan;
-    plan_pack(pack, args.batch, pack_, plan);
-    if (plan.set.flac()) check_flac_rate(output_rate());  // the rate this run will run at
-    if (!plan.set.trimmed() && !plan.set.normalised() && !plan.set.flac()) {
-        synthesize(args, rows, &plan);
-        copy_out_packed(plan, out);
-        return;
-    }
-    // (FLAC: the frames are made from the finished stream, behind it in the arena: the fetch's path, with nothing to measure)
-    // Trimming or a loudness target on: the offsets / the scales depend on the audio.  Synthesise without an early pack table (and
-    // without the padded int16 pass: a packed call looks at no MI355VITS_WANT_* flag), measure (k_edges and / or k_loud, their
-    // copies, ONE synchronisation), then what fetch_packed does.  A limit exceeded by the trimmed sizes leaves the handle as a failed run does: no result served.
-    mi355vits_run_args a = args;
-    a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
-    synthesize(a, rows, nullptr);
-    try {
-        pack_last_run(plan, out);
-        HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its edges and its pack
-    } catch (...) {
-        have_result_ = false;
-        throw;
-    }
+    OutputPlan op;
+    plan_single(pack, args.batch, op);
+    run_output(args, rows, op, out);
 }
 
 void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
     begin_fetch(out, "fetch_packed", false);
-    PackPlan plan;
-    plan_pack(pack, B_, pack_, plan);
-    if (plan.set.flac()) check_flac_rate(run_hz_);
-    pack_last_run(plan, out);
+    OutputPlan op;
+    plan_single(pack, B_, op);
+    output_last_run(op, out);
 }
 
-void Engine::pack_last_run(PackPlan& plan, mi355vits_packed_result* out) {
-    HIP_CHECK(hipSetDevice(device_));
-    measure_last_run({plan.set.trim_ratio}, plan.set.normalised(), false, plan.set.true_peak());
-    place_pack(plan);
-    if (plan.set.limiting()) {
-        // the limiter: one job per entry the ceiling would hold back; the curves are made before the pack, on the same stream
-        std::vector<LimitJob> jobs;
-        limit_pack(plan, jobs);
-        if (!jobs.empty()) {
-            run_limit_jobs(jobs, plan.set.limit_window, arena_lm_, true, plan.set.true_peak());
-            curve_offsets(plan, jobs);
-        }
+namespace {
+// the entry's f32 scale: 32767 * gain in double, rounded once (F32LE: the gain itself)
+float entry_scale(const PackSettings& set, double gain) { return set.enc == PACK_ENC_F32 ? (float)gain : (float)(32767.0 * gain); }
+
+// What the host checks of the sizes a FLAC launch reports.  The bytes of `count` frames from frame `first` on, each within what a
+// frame of FLAC_BLOCK samples can take ...
+size_t flac_frame_bytes(const int* sizes, size_t first, long count) {
+    size_t bytes = 0;
+    for (size_t f = first; f < first + (size_t)count; ++f) {
+        const int sz = sizes[f];
+        if (sz < 11 || sz > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sz) + " bytes");
+        bytes += (size_t)sz;
     }
-    // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
-    // else in an arena of its own
+    return bytes;
+}
+// ... and a total, a place or an end the device made from them against the host's own
+void flac_agree(bool same, const std::string& what) {
+    if (!same) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's " + what);
+}
+}  // namespace
+
+void Engine::flac_prof_bytes(double bytes) {
+    if (flac_prof_rec_ >= 0 && (size_t)flac_prof_rec_ < prof_.recs.size()) prof_.recs[(size_t)flac_prof_rec_].bytes += bytes;
+}
+
+// The result of a single plan: exactly the stream lands behind the header the host writes.  FLAC: the compressed size depends on the
+// audio, so the frame sizes and their total come first (4 * (frames + 1) bytes, ONE synchronisation more than an uncompressed
+// pack), then exactly the frames land behind the 42 header bytes.
+void Engine::copy_out_plan(OutputPlan& op, mi355vits_packed_result* out) {
+    const PackPlan& plan = op.streams[0];
     const bool flac = plan.set.flac();
-    ArenaCount need;
-    layout_pack(need, plan);
-    if (flac) layout_flac(need, plan);
-    if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
-        arena_b_.rewind(layout_b_end_);
-        layout_pack(arena_b_, plan);
-        if (flac) layout_flac(arena_b_, plan);
-    } else {
-        arena_p_.reserve(need.bytes + 4096, stream_);
-        arena_p_.reset();
-        layout_pack(arena_p_, plan);
-        if (flac) layout_flac(arena_p_, plan);
-    }
-    h_pack_seg_.assign((size_t)plan.seg_rows() * plan.n, 0);  // a member: it outlives the copy whatever HIP does with pageable sources
-    fill_pack_seg(plan, h_pack_seg_.data());
-    HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
-    launch_pack(plan);
-    if (flac) {
-        launch_flac(plan);
-        copy_out_flac(plan, out);
-        return;
-    }
-    copy_out_packed(plan, out);
-}
-
-// The S16LE stream k_pack just wrote as FLAC frames: one job, a workgroup per frame, the sizes scanned, the frames gathered.
-void Engine::launch_flac(const PackPlan& plan) {
-    const long frames = flac_frames((long)plan.total);
-    flac_prof_rec_ = -1;
-    if (frames == 0) return;
-    h_flac_job_ = FlacJob{reinterpret_cast<const int16_t*>(d_pack_), (long)plan.total, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(d_flac_jobs_, &h_flac_job_, sizeof(FlacJob), hipMemcpyHostToDevice, stream_));
-    ProfScope ps(prof_, "pack.flac", 0, 2.0 * (double)plan.total);  // + the frames' bytes once the host knows them (copy_out_flac)
-    flac_prof_rec_ = ps.rec;
-    launch_flac_frames(d_flac_jobs_, 1, frames, run_hz_, d_flac_slots_, d_flac_sizes_, stream_);
-    launch_flac_gather(d_flac_slots_, d_flac_sizes_, d_flac_offsets_, frames, d_flac_out_, stream_);
-}
-
-// The compressed size depends on the audio: the frame sizes and their total come first (4 * (frames + 1) bytes, ONE synchronisation
-// more than an uncompressed pack), then exactly the frames land behind the 42 header bytes the host writes.
-void Engine::copy_out_flac(const PackPlan& plan, mi355vits_packed_result* out) {
     const int n = plan.n;
-    const long frames = flac_frames((long)plan.total);
+    const long frames = op.n_frames;
     Owner* own = new_owner(out);
     out->n = n;
     out->total_samples = plan.total;
@@ -471,23 +383,30 @@ void Engine::copy_out_flac(const PackPlan& plan, mi355vits_packed_result* out) {
     out->lengths = own->alloc<int64_t>(n);
     out->peaks = own->alloc<float>(n);
     std::vector<unsigned> pk(B_);
-    h_flac_sizes_.assign((size_t)frames + 1, 0);
     HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
-    if (frames > 0) HIP_CHECK(hipMemcpyAsync(h_flac_sizes_.data(), d_flac_sizes_, 4 * ((size_t)frames + 1), hipMemcpyDeviceToHost, stream_));
+    if (flac) {
+        h_flac_sizes_.assign((size_t)frames + 1, 0);
+        if (frames > 0) HIP_CHECK(hipMemcpyAsync(h_flac_sizes_.data(), d_flac_sizes_, 4 * ((size_t)frames + 1), hipMemcpyDeviceToHost, stream_));
+    } else {
+        const size_t hdr = plan.header_bytes(), data = (size_t)plan.bps() * (size_t)plan.total;
+        const size_t pad = (plan.wav && (data & 1)) ? 1 : 0;  // the RIFF pad byte (write_wav_header)
+        const size_t lead = hdr == 58 ? 6 : 0;  // the 58-byte header starts 6 bytes into the block: the data behind it keeps the block's alignment
+        out->bytes = static_cast<uint8_t*>(own->take_pinned(lead + hdr + data + pad + 16)) + lead;
+        out->n_bytes = hdr + data + pad;
+        out->pcm = reinterpret_cast<int16_t*>(out->bytes + hdr);  // the first data byte, whatever the encoding
+        HIP_CHECK(hipMemcpyAsync(out->pcm, d_pack_, data, hipMemcpyDeviceToHost, stream_));  // exactly the stream: lands behind the header
+        if (plan.wav) write_wav_header(out->bytes, plan.set.enc, (uint32_t)run_hz_, plan.total, data);  // the rate the run ran at
+    }
     for (int i = 0; i < n; ++i) {
         out->offsets[i] = plan.offsets[i];
         out->lengths[i] = plan.lengths[i];
     }
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (int i = 0; i < n; ++i) memcpy(&out->peaks[i], &pk[plan.order[i]], 4);
-    size_t data = 0;
-    for (long f = 0; f < frames; ++f) {
-        const int sz = h_flac_sizes_[(size_t)f];
-        if (sz < 11 || sz > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sz) + " bytes");
-        data += (size_t)sz;
-    }
-    if ((unsigned)h_flac_sizes_[(size_t)frames] != (unsigned)data) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's total differs from the sum of the frame sizes");
-    if (flac_prof_rec_ >= 0 && (size_t)flac_prof_rec_ < prof_.recs.size()) prof_.recs[(size_t)flac_prof_rec_].bytes += (double)data;
+    if (!flac) return;
+    const size_t data = flac_frame_bytes(h_flac_sizes_.data(), 0, frames);
+    flac_agree((unsigned)h_flac_sizes_[(size_t)frames] == (unsigned)data, "total differs from the sum of the frame sizes");
+    flac_prof_bytes((double)data);
     const size_t lead = 6;  // the 42-byte header starts 6 bytes into the block: the frames behind it keep the block's alignment
     out->bytes = static_cast<uint8_t*>(own->take_pinned(lead + FLAC_HEADER_BYTES + data + 16)) + lead;
     out->n_bytes = FLAC_HEADER_BYTES + data;
@@ -522,11 +441,11 @@ std::vector<mi355vits_stream_args2> Engine::streams_v1(const mi355vits_stream_ar
     return v;
 }
 
-void Engine::plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, StreamsPlan& sp) const {
+void Engine::plan_streams(const mi355vits_stream_args2* streams, int n_streams, int B, OutputPlan& op) const {
     if (!streams || n_streams < 1)
         throw EngineError(MI355VITS_ERR_INVALID, "streams: a non-null array of n_streams >= 1 streams is required (n_streams = " + std::to_string(n_streams) + ")");
-    sp.streams.assign((size_t)n_streams, PackPlan());
-    sp.entries = 0;
+    op.streams.assign((size_t)n_streams, PackPlan());
+    op.entries = 0;
     for (int s = 0; s < n_streams; ++s) {
         const mi355vits_stream_args2& a2 = streams[s];
         const mi355vits_stream_args& a = a2.base;
@@ -563,84 +482,113 @@ void Engine::plan_streams(const mi355vits_stream_args2* streams, int n_streams, 
         set.ceil_mode = a2.ceiling_mode;
         set.compress = a2.compression;
         try {
-            plan_pack(&a.pack, B, set, sp.streams[s]);
+            plan_pack(&a.pack, B, set, op.streams[s]);
         } catch (const EngineError& e) {
             throw EngineError(e.code, name + e.what());
         }
-        sp.entries += sp.streams[s].n;
+        op.entries += op.streams[s].n;
     }
 }
 
-// Every stream placed as its own pack, then the streams in the block: each one's first data byte at the next multiple of 16 that
-// leaves room for its header, the header right in front of it, the RIFF pad byte behind an odd data size.
-void Engine::place_streams(StreamsPlan& sp) const {
-    const size_t S = sp.streams.size();
-    sp.begin.assign(S, 0);
-    sp.data.assign(S, 0);
-    sp.src.assign(S, -1);
-    sp.frames.assign(S, 0);
-    sp.dev.clear();
-    sp.audio = 0;
-    sp.n_flac = 0;
-    sp.n_frames = 0;
+// Every stream placed as its own pack, then (block form) the streams in the block: each one's first data byte at the next multiple
+// of 16 that leaves room for its header, the header right in front of it, the RIFF pad byte behind an odd data size.
+void Engine::place(OutputPlan& op) const {
+    const size_t S = op.streams.size();
+    op.begin.assign(S, 0);
+    op.data.assign(S, 0);
+    op.src.assign(S, -1);
+    op.frames.assign(S, 0);
+    op.dev.clear();
+    op.audio = 0;
+    op.n_flac = 0;
+    op.n_frames = 0;
     std::vector<int> flac;
     int64_t pos = 0;
     for (size_t s = 0; s < S; ++s) {
-        PackPlan& p = sp.streams[s];
+        PackPlan& p = op.streams[s];
         try {
             place_pack(p);
         } catch (const EngineError& e) {
+            if (op.single) throw;
             throw EngineError(e.code, "stream " + std::to_string(s) + ": " + e.what());
         }
-        sp.audio += p.audio;
+        op.audio += p.audio;
+        if (op.single) {
+            // no block around its one stream: k_pack writes it at d_pack_, where the one FLAC job reads it
+            op.dev.push_back(0);
+            if (p.set.flac()) {
+                op.src[0] = 0;
+                op.n_flac = 1;
+                op.n_frames = op.frames[0] = flac_frames((long)p.total);
+            }
+            return;
+        }
         if (p.set.flac()) {
             flac.push_back((int)s);  // behind the uncompressed streams, below
             continue;
         }
         const int64_t hdr = (int64_t)p.header_bytes(), bytes = (int64_t)p.bps() * p.total;
-        sp.data[s] = (pos + hdr + 15) & ~int64_t(15);
-        sp.begin[s] = sp.data[s] - hdr;
-        pos = sp.data[s] + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
-        sp.dev.push_back((int)s);
+        op.data[s] = (pos + hdr + 15) & ~int64_t(15);
+        op.begin[s] = op.data[s] - hdr;
+        pos = op.data[s] + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
+        op.dev.push_back((int)s);
         if (pos > STREAMS_MAX_BYTES) {
             // (what the remaining streams add only makes it larger: the size named is the block up to this stream)
             throw EngineError(MI355VITS_ERR_INVALID, "streams: block of " + std::to_string(pos) + " bytes exceeds 2^31 - 1");
         }
     }
-    sp.plain_bytes = sp.n_bytes = pos;
-    sp.flac_base = sp.flac_bound = 0;
+    op.plain_bytes = op.n_bytes = pos;
+    op.flac_base = op.flac_bound = 0;
     if (flac.empty()) return;
     // the compressed streams: their samples behind the uncompressed block, each at a multiple of 16; the block counted with every
     // file at its bound
-    sp.flac_base = (pos + 15) & ~int64_t(15);
-    int64_t at = sp.flac_base, bound = sp.flac_base;
+    op.flac_base = (pos + 15) & ~int64_t(15);
+    int64_t at = op.flac_base, bound = op.flac_base;
     for (int s : flac) {
-        const PackPlan& p = sp.streams[(size_t)s];
-        sp.src[(size_t)s] = at;
-        sp.frames[(size_t)s] = flac_frames((long)p.total);
-        sp.n_frames += sp.frames[(size_t)s];
-        sp.dev.push_back(s);
-        sp.n_bytes = at + 2 * p.total;
-        at = (sp.n_bytes + 15) & ~int64_t(15);
+        const PackPlan& p = op.streams[(size_t)s];
+        op.src[(size_t)s] = at;
+        op.frames[(size_t)s] = flac_frames((long)p.total);
+        op.n_frames += op.frames[(size_t)s];
+        op.dev.push_back(s);
+        op.n_bytes = at + 2 * p.total;
+        at = (op.n_bytes + 15) & ~int64_t(15);
         bound += flac_file_bound((long)p.total);
         if (bound > STREAMS_MAX_BYTES || at > STREAMS_MAX_BYTES)
             throw EngineError(MI355VITS_ERR_INVALID, "streams: block of " + std::to_string(std::max(bound, at)) + " bytes exceeds 2^31 - 1 (a FLAC stream counted at its bound)");
     }
-    sp.n_flac = (int)flac.size();
-    sp.flac_bound = bound - sp.flac_base;
+    op.n_flac = (int)flac.size();
+    op.flac_bound = bound - op.flac_base;
 }
 
-void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
-    const size_t n = (size_t)sp.entries;
-    int* st = tab + pack_ent_rows(sp.curved) * n;
+void Engine::fill_table(const OutputPlan& op, int* tab) const {
+    if (op.single) {
+        // k_pack's segment table [seg_rows][n]: only the rows its settings need
+        const PackPlan& plan = op.streams[0];
+        const PackSettings& set = plan.set;
+        const size_t n = plan.n;
+        for (size_t i = 0; i < n; ++i) {
+            tab[PACK_SEG_OFFSET * n + i] = (int)plan.offsets[i];
+            tab[PACK_SEG_ROW * n + i] = plan.order[i];
+            tab[PACK_SEG_LENGTH * n + i] = (int)plan.lengths[i];
+            if (set.trimmed()) tab[PACK_SEG_SKIP * n + i] = plan.skip[i];
+            if (set.normalised()) {
+                const float scale = entry_scale(set, plan.gain[i]);
+                memcpy(&tab[pack_seg_scale_row(set.trimmed()) * n + i], &scale, 4);
+            }
+            if (plan.curved()) tab[pack_seg_curve_row(set.trimmed()) * n + i] = plan.curve[i];
+        }
+        return;
+    }
+    const size_t n = (size_t)op.entries;
+    int* st = tab + pack_ent_rows(op.curved) * n;
     size_t e = 0;
-    for (size_t d = 0; d < sp.dev.size(); ++d) {
-        const size_t s = (size_t)sp.dev[d];  // in the order of their places (without a compressed stream: the order given)
-        const PackPlan& p = sp.streams[s];
+    for (size_t d = 0; d < op.dev.size(); ++d) {
+        const size_t s = (size_t)op.dev[d];  // in the order of their places (without a compressed stream: the order given)
+        const PackPlan& p = op.streams[s];
         const PackSettings& set = p.set;
         const int64_t bytes = (int64_t)p.bps() * p.total;
         // (a compressed stream: its samples as a headerless S16LE stream, k_flac_frames' source)
-        const int64_t data = set.flac() ? sp.src[s] : sp.data[s], begin = set.flac() ? sp.src[s] : sp.begin[s];
+        const int64_t data = set.flac() ? op.src[s] : op.data[s], begin = set.flac() ? op.src[s] : op.begin[s];
         for (int i = 0; i < p.n; ++i, ++e) {
             tab[PACK_ENT_OFFSET * n + e] = (int)(data + (int64_t)p.bps() * p.offsets[i]);
             tab[PACK_ENT_ROW * n + e] = p.order[i];
@@ -648,9 +596,8 @@ void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
             tab[PACK_ENT_SKIP * n + e] = set.trimmed() ? p.skip[i] : 0;
             const bool curved = p.curved() && p.curve[i] >= 0;
             tab[PACK_ENT_ENC * n + e] = set.enc | (set.normalised() ? (int)PACK_ENT_SCALED : 0) | (curved ? (int)PACK_ENT_CURVED : 0);
-            if (sp.curved) tab[PACK_ENT_CURVE * n + e] = curved ? p.curve[i] : 0;
-            float scale = 0.0f;  // fill_pack_seg's: 32767 * gain in double, rounded once (F32LE: the gain itself)
-            if (set.normalised()) scale = set.enc == PACK_ENC_F32 ? (float)p.gain[i] : (float)(32767.0 * p.gain[i]);
+            if (op.curved) tab[PACK_ENT_CURVE * n + e] = curved ? p.curve[i] : 0;
+            const float scale = set.normalised() ? entry_scale(set, p.gain[i]) : 0.0f;
             memcpy(&tab[PACK_ENT_SCALE * n + e], &scale, 4);
         }
         int* r = st + PACK_STREAM_WORDS * d;
@@ -665,38 +612,55 @@ void Engine::fill_streams_table(const StreamsPlan& sp, int* tab) const {
     }
 }
 
-void Engine::launch_streams(const StreamsPlan& sp) {
-    ProfScope ps(prof_, "pack.streams", 0, 4.0 * (double)sp.audio + (double)sp.n_bytes);
-    launch_pack_streams(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, sp.entries, (int)sp.streams.size(), d_pack_, (long)sp.n_bytes, stream_,
-                        sp.curved ? d_curve_ : nullptr);
+void Engine::launch(const OutputPlan& op) {
+    if (op.single) {
+        static const char* const labels[] = {"pcm16.pack", "pack.ulaw", "pack.alaw", "pack.f32"};  // by PackEncoding
+        const PackPlan& plan = op.streams[0];
+        ProfScope ps(prof_, labels[plan.set.enc], 0, 4.0 * (double)plan.audio + (double)plan.bps() * (double)plan.total);
+        launch_pack(plan.set.enc, o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, plan.n, d_pack_, (long)plan.total, stream_, plan.set.trimmed(),
+                    plan.set.normalised(), plan.curved() ? d_curve_ : nullptr);
+    } else {
+        ProfScope ps(prof_, "pack.streams", 0, 4.0 * (double)op.audio + (double)op.n_bytes);
+        launch_pack_streams(o_audio_, Lo_, o_peaks_, d_vol_, d_pack_seg_, op.entries, (int)op.streams.size(), d_pack_, (long)op.n_bytes, stream_,
+                            op.curved ? d_curve_ : nullptr);
+    }
+    flac_prof_rec_ = -1;
+    if (op.compressed()) launch_flac(op);
 }
 
-// The compressed streams of a block: a job per stream over its samples in k_pack_streams' buffer, k_flac_frames once over all of them,
-// the places and headers (k_flac_place), the compressed region (k_flac_gather_streams).  One profiler record.
-void Engine::launch_flac_streams(const StreamsPlan& sp) {
+// The compressed streams of a plan: a job per stream over its samples in the pack kernel's buffer, k_flac_frames once over all of
+// them (a workgroup per frame); then single: the sizes scanned and the frames gathered (k_flac_scan / k_flac_gather), block form: the
+// places and headers (k_flac_place) and the compressed region (k_flac_gather_streams).  One profiler record.
+void Engine::launch_flac(const OutputPlan& op) {
+    if (op.single && op.n_frames == 0) return;  // an empty stream: the header alone, written by the host
     h_flac_jobs_.clear();
     double samples = 0;
     long slot0 = 0;
-    for (int s : sp.dev) {
-        const PackPlan& p = sp.streams[(size_t)s];
+    for (int s : op.dev) {
+        const PackPlan& p = op.streams[(size_t)s];
         if (!p.set.flac()) continue;
-        h_flac_jobs_.push_back(FlacJob{reinterpret_cast<const int16_t*>(d_pack_ + sp.src[(size_t)s]), (long)p.total, 0, (int)slot0});
-        slot0 += sp.frames[(size_t)s];
+        h_flac_jobs_.push_back(FlacJob{reinterpret_cast<const int16_t*>(d_pack_ + op.src[(size_t)s]), (long)p.total, 0, (int)slot0});
+        slot0 += op.frames[(size_t)s];
         samples += (double)p.total;
     }
     HIP_CHECK(hipMemcpyAsync(d_flac_jobs_, h_flac_jobs_.data(), sizeof(FlacJob) * h_flac_jobs_.size(), hipMemcpyHostToDevice, stream_));
-    ProfScope ps(prof_, "pack.flac", 0, 2.0 * samples);  // + the frames' bytes once the host knows them (copy_out_streams)
+    ProfScope ps(prof_, "pack.flac", 0, 2.0 * samples);  // + the frames' bytes once the host knows them (copy_out_plan)
     flac_prof_rec_ = ps.rec;
-    launch_flac_frames(d_flac_jobs_, sp.n_flac, sp.n_frames, run_hz_, d_flac_slots_, d_flac_sizes_, stream_);
-    launch_flac_place(d_flac_jobs_, sp.n_flac, sp.n_frames, run_hz_, (long)sp.flac_base, d_flac_sizes_, d_flac_pre_, d_flac_ftab_, d_flac_hdr_,
+    launch_flac_frames(d_flac_jobs_, op.n_flac, op.n_frames, run_hz_, d_flac_slots_, d_flac_sizes_, stream_);
+    if (op.single) {
+        launch_flac_gather(d_flac_slots_, d_flac_sizes_, d_flac_offsets_, op.n_frames, d_flac_out_, stream_);
+        return;
+    }
+    launch_flac_place(d_flac_jobs_, op.n_flac, op.n_frames, run_hz_, (long)op.flac_base, d_flac_sizes_, d_flac_pre_, d_flac_ftab_, d_flac_hdr_,
                       d_flac_items_, d_flac_jtab_, stream_);
-    launch_flac_gather_streams(sp.n_flac, sp.n_frames, d_flac_slots_, d_flac_sizes_, d_flac_ftab_, d_flac_hdr_, d_flac_items_, (long)sp.flac_base,
-                               (long)sp.flac_bound, d_flac_out_, stream_);
+    launch_flac_gather_streams(op.n_flac, op.n_frames, d_flac_slots_, d_flac_sizes_, d_flac_ftab_, d_flac_hdr_, d_flac_items_, (long)op.flac_base,
+                               (long)op.flac_bound, d_flac_out_, stream_);
 }
 
-template <typename R> void Engine::copy_out_streams(StreamsPlan& sp, R* out) {
+// The result of a block-form plan: the block's bytes and the arrays of either streams result struct.
+template <typename R> void Engine::copy_out_plan(OutputPlan& op, R* out) {
     constexpr bool V2 = std::is_same<R, mi355vits_streams_result2>::value;
-    const size_t S = sp.streams.size(), E = (size_t)sp.entries;
+    const size_t S = op.streams.size(), E = (size_t)op.entries;
     Owner* own = new_owner(out);
     out->n_streams = (int32_t)S;
     out->n_entries = (int32_t)E;
@@ -717,65 +681,61 @@ template <typename R> void Engine::copy_out_streams(StreamsPlan& sp, R* out) {
     if constexpr (V2) {
         out->compression = own->alloc<int32_t>(S);
         out->frames = own->alloc<int32_t>(S);
-        out->uncompressed_bytes = sp.plain_bytes;
+        out->uncompressed_bytes = op.plain_bytes;
     }
     std::vector<unsigned> pk(B_);
-    size_t block_bytes = (size_t)sp.n_bytes;
+    size_t block_bytes = (size_t)op.n_bytes;
     std::vector<int64_t> fbytes(S, 0);  // compressed streams: header + frames
-    if (sp.compressed()) {
+    if (op.compressed()) {
         // The sizes depend on the audio: the frame sizes, four words per compressed stream and the block's end come first — ONE
         // synchronisation more than the same block uncompressed —, then exactly the block's bytes.
-        const size_t words = flac_info_words(sp.n_frames, sp.n_flac);
+        const size_t words = flac_info_words(op.n_frames, op.n_flac);
         h_flac_sizes_.assign(words, 0);
         HIP_CHECK(hipMemcpyAsync(h_flac_sizes_.data(), d_flac_sizes_, 4 * words, hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
-        const int* info = h_flac_sizes_.data() + sp.n_frames;
-        int64_t at = sp.flac_base;
+        const int* info = h_flac_sizes_.data() + op.n_frames;
+        int64_t at = op.flac_base;
         size_t f = 0, frame_bytes = 0;
         int j = 0;
-        for (int s : sp.dev) {
-            if (!sp.streams[(size_t)s].set.flac()) continue;
-            int64_t bytes = FLAC_HEADER_BYTES;
-            for (long k = 0; k < sp.frames[(size_t)s]; ++k, ++f) {
-                const int sz = h_flac_sizes_[f];
-                if (sz < 11 || sz > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sz) + " bytes");
-                bytes += sz;
-            }
-            if (info[FLAC_INFO_WORDS * j + FLAC_INFO_BASE] != (int)at || info[FLAC_INFO_WORDS * j + FLAC_INFO_BYTES] != (int)bytes)
-                throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's place of stream " + std::to_string(s) + " differs from the sum of its frame sizes");
-            sp.begin[(size_t)s] = at;
-            sp.data[(size_t)s] = at + FLAC_HEADER_BYTES;
+        for (int s : op.dev) {
+            if (!op.streams[(size_t)s].set.flac()) continue;
+            const int64_t bytes = FLAC_HEADER_BYTES + (int64_t)flac_frame_bytes(h_flac_sizes_.data(), f, op.frames[(size_t)s]);
+            f += (size_t)op.frames[(size_t)s];
+            flac_agree(info[FLAC_INFO_WORDS * j + FLAC_INFO_BASE] == (int)at && info[FLAC_INFO_WORDS * j + FLAC_INFO_BYTES] == (int)bytes,
+                       "place of stream " + std::to_string(s) + " differs from the sum of its frame sizes");
+            op.begin[(size_t)s] = at;
+            op.data[(size_t)s] = at + FLAC_HEADER_BYTES;
             fbytes[(size_t)s] = bytes;
             frame_bytes += (size_t)(bytes - FLAC_HEADER_BYTES);
             block_bytes = (size_t)(at + bytes);
             at = (at + bytes + 15) & ~int64_t(15);
             ++j;
         }
-        if ((int64_t)info[FLAC_INFO_WORDS * sp.n_flac] != (int64_t)block_bytes) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the device's block end differs from the host's");
-        if (flac_prof_rec_ >= 0 && (size_t)flac_prof_rec_ < prof_.recs.size()) prof_.recs[(size_t)flac_prof_rec_].bytes += (double)frame_bytes;
+        flac_agree((int64_t)info[FLAC_INFO_WORDS * op.n_flac] == (int64_t)block_bytes, "block end differs from the host's");
+        flac_prof_bytes((double)frame_bytes);
     }
     out->bytes = static_cast<uint8_t*>(own->take_pinned(block_bytes + 16));
     out->n_bytes = block_bytes;
     HIP_CHECK(hipMemcpyAsync(pk.data(), o_peaks_, sizeof(unsigned) * B_, hipMemcpyDeviceToHost, stream_));
-    if (!sp.compressed()) {
+    if (!op.compressed()) {
         HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, block_bytes, hipMemcpyDeviceToHost, stream_));  // exactly the block: finished files
     } else {
         // the uncompressed part up to where the compressed one starts (the gap's zeros are k_pack_streams'), then the compressed part
-        if (sp.flac_base > 0) HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, (size_t)sp.flac_base, hipMemcpyDeviceToHost, stream_));
-        HIP_CHECK(hipMemcpyAsync(out->bytes + sp.flac_base, d_flac_out_, block_bytes - (size_t)sp.flac_base, hipMemcpyDeviceToHost, stream_));
+        if (op.flac_base > 0) HIP_CHECK(hipMemcpyAsync(out->bytes, d_pack_, (size_t)op.flac_base, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(out->bytes + op.flac_base, d_flac_out_, block_bytes - (size_t)op.flac_base, hipMemcpyDeviceToHost, stream_));
     }
     size_t e = 0;
     for (size_t s = 0; s < S; ++s) {
-        const PackPlan& p = sp.streams[s];
+        const PackPlan& p = op.streams[s];
         const int64_t bytes = (int64_t)p.bps() * p.total;
-        out->stream_offset[s] = sp.begin[s];
-        out->data_offset[s] = sp.data[s];
-        out->stream_bytes[s] = p.set.flac() ? fbytes[s] : (sp.data[s] - sp.begin[s]) + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
+        out->stream_offset[s] = op.begin[s];
+        out->data_offset[s] = op.data[s];
+        out->stream_bytes[s] = p.set.flac() ? fbytes[s] : (op.data[s] - op.begin[s]) + bytes + ((p.wav && (bytes & 1)) ? 1 : 0);
         out->total_samples[s] = p.total;
         out->encoding[s] = p.set.enc;
         if constexpr (V2) {
             out->compression[s] = p.set.compress;
-            out->frames[s] = (int32_t)sp.frames[s];
+            out->frames[s] = (int32_t)op.frames[s];
         }
         out->entry_base[s] = (int32_t)e;
         for (int i = 0; i < p.n; ++i, ++e) {
@@ -799,19 +759,23 @@ template <typename R> void Engine::copy_out_streams(StreamsPlan& sp, R* out) {
     for (size_t i = 0; i < E; ++i) memcpy(&out->peaks[i], &pk[out->rows[i]], 4);
 }
 
-template <typename R> void Engine::run_streams_plan(const mi355vits_run_args& args, const mi355vits_row_args* rows, StreamsPlan& sp, R* out) {
-    if (!sp.measured() && !sp.compressed_planned()) {
-        synthesize(args, rows, nullptr, &sp);
-        copy_out_streams(sp, out);
+// A run with an output plan.  No stream trims, normalises or compresses: the places follow from the frame counts, so the table rides
+// in the run's own upload and the pack kernel is its last launch.  Else the offsets / the scales depend on the audio and the frames
+// are made from the finished stream: synthesise without an early table (and without the padded int16 pass: a packed-form call looks at
+// no MI355VITS_WANT_* flag), then what the fetch of the same plan does.  A failure there — a limit exceeded by the trimmed sizes —
+// leaves the handle as a failed run does: no result served.
+template <typename R> void Engine::run_output(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan& op, R* out) {
+    if (op.compressed()) check_flac_rate(output_rate());  // the rate this run will run at
+    if (!op.measured() && !op.compressed()) {
+        synthesize(args, rows, &op);
+        copy_out_plan(op, out);
         return;
     }
-    // Some stream trims, normalises or compresses: as a trimmed run_packed — synthesise without an early table and without the padded
-    // int16 pass, measure (ONE synchronisation, or none), then what fetch_streams does.  A limit exceeded by the trimmed sizes leaves no result served.
     mi355vits_run_args a = args;
     a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
     synthesize(a, rows, nullptr);
     try {
-        streams_last_run(sp, out);
+        output_last_run(op, out);
         HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its measurements and its pack
     } catch (...) {
         have_result_ = false;
@@ -824,18 +788,18 @@ void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_arg
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    StreamsPlan sp;
+    OutputPlan op;
     const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
-    plan_streams(v.empty() ? nullptr : v.data(), n_streams, args.batch, sp);
-    run_streams_plan(args, rows, sp, out);
+    plan_streams(v.empty() ? nullptr : v.data(), n_streams, args.batch, op);
+    run_output(args, rows, op, out);
 }
 
 void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out) {
     begin_fetch(out, "fetch_streams");
-    StreamsPlan sp;
+    OutputPlan op;
     const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
-    plan_streams(v.empty() ? nullptr : v.data(), n_streams, B_, sp);
-    streams_last_run(sp, out);
+    plan_streams(v.empty() ? nullptr : v.data(), n_streams, B_, op);
+    output_last_run(op, out);
 }
 
 void Engine::run_streams2(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args2* streams, int n_streams,
@@ -843,61 +807,65 @@ void Engine::run_streams2(const mi355vits_run_args& args, const mi355vits_row_ar
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
     if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    StreamsPlan sp;
-    plan_streams(streams, n_streams, args.batch, sp);
-    if (sp.compressed_planned()) check_flac_rate(output_rate());  // the rate this run will run at
-    run_streams_plan(args, rows, sp, out);
+    OutputPlan op;
+    plan_streams(streams, n_streams, args.batch, op);
+    run_output(args, rows, op, out);
 }
 
 void Engine::fetch_streams2(const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out) {
     begin_fetch(out, "fetch_streams2");
-    StreamsPlan sp;
-    plan_streams(streams, n_streams, B_, sp);
-    if (sp.compressed_planned()) check_flac_rate(run_hz_);
-    streams_last_run(sp, out);
+    OutputPlan op;
+    plan_streams(streams, n_streams, B_, op);
+    output_last_run(op, out);
 }
 
-template <typename R> void Engine::streams_last_run(StreamsPlan& sp, R* out) {
+template <typename R> void Engine::output_last_run(OutputPlan& op, R* out) {
+    finish_last_run(op);
+    copy_out_plan(op, out);
+}
+
+void Engine::finish_last_run(OutputPlan& op) {
+    if (op.compressed()) check_flac_rate(run_hz_);
     HIP_CHECK(hipSetDevice(device_));
     std::vector<float> ratios;
     bool loud = false, tp = false;
-    for (const PackPlan& p : sp.streams) {
+    for (const PackPlan& p : op.streams) {
         ratios.push_back(p.set.trim_ratio);
         loud = loud || p.set.normalised();
         tp = tp || p.set.true_peak();
     }
-    measure_last_run(ratios, loud, true, tp);
-    place_streams(sp);
+    // (a block keeps what the host holds at other ratios; a single call at a ratio not held replaces it, as ever)
+    measure_last_run(ratios, loud, !op.single, tp);
+    place(op);
     {
-        // the limiter: one job per distinct (row, target, ceiling, encoding class, window, mode) among the entries the ceiling would hold back
+        // the limiter: one job per distinct (row, target, ceiling, encoding class, window, mode) among the entries the ceiling would
+        // hold back; the curves are made before the pack, on the same stream (a single plan has one key: run_limit_jobs itself)
         std::vector<LimitJob> jobs;
         LimitKeys keys;
-        for (PackPlan& p : sp.streams)
+        for (PackPlan& p : op.streams)
             if (p.set.limiting()) limit_pack(p, jobs, &keys);
-        sp.curved = !jobs.empty();
-        if (sp.curved) {
+        op.curved = !jobs.empty();
+        if (op.curved) {
             run_limit_groups(jobs, keys);
-            for (PackPlan& p : sp.streams) curve_offsets(p, jobs);
+            for (PackPlan& p : op.streams) curve_offsets(p, jobs);
         }
     }
-    // where pack_last_run puts its buffers: behind the last run's frame-side layout where the arena has room, else in arena_p_
+    // behind the last run's frame-side layout where the arena has room (its data must stay: a reallocation would lose it),
+    // else in an arena of its own
     ArenaCount need;
-    layout_streams(need, sp);
+    layout(need, op);
     if (arena_b_.capacity() >= layout_b_end_ + need.bytes) {
         arena_b_.rewind(layout_b_end_);
-        layout_streams(arena_b_, sp);
+        layout(arena_b_, op);
     } else {
         arena_p_.reserve(need.bytes + 4096, stream_);
         arena_p_.reset();
-        layout_streams(arena_p_, sp);
+        layout(arena_p_, op);
     }
-    h_pack_seg_.assign(pack_streams_table_words(sp.entries, (int)sp.streams.size(), sp.curved), 0);
-    fill_streams_table(sp, h_pack_seg_.data());
+    h_pack_seg_.assign(op.table_words(), 0);  // a member: it outlives the copy whatever HIP does with pageable sources
+    fill_table(op, h_pack_seg_.data());
     HIP_CHECK(hipMemcpyAsync(d_pack_seg_, h_pack_seg_.data(), h_pack_seg_.size() * 4, hipMemcpyHostToDevice, stream_));
-    launch_streams(sp);
-    flac_prof_rec_ = -1;
-    if (sp.compressed()) launch_flac_streams(sp);
-    copy_out_streams(sp, out);
+    launch(op);
 }
 
 // ---------------------------------------------------------------- phoneme timing and levels (mi355vits_fetch_alignment)

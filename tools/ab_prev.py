@@ -2,11 +2,16 @@
 
     python tools/ab_prev.py bits  PREV.so NEW.so          # the same ragged batch through both: waveforms, lengths, PCM compared bitwise
     python tools/ab_prev.py bench PREV.so NEW.so [--batch 256 --steps 20 --rounds 2]
-    python tools/ab_prev.py digest [--root TREE]          # sha256 of a tree's own results: `bits` across an ABI change
+    python tools/ab_prev.py digest [--root TREE] [--emu]  # sha256 of a tree's own results: `bits` across an ABI change
 
 `bits` opens both files with THIS tree's binding, so PREV must export every entry point the binding knows.  When the ABI has grown
 since PREV, run `digest` once in each tree (or with --root on a checkout that holds its built library) and compare the lines: the
 ragged batch of `bits`, and the headline shape (256 rows x 128 ids x 6 forced frames) as padded int16 and as the default packed stream.
+Then the result paths on that ragged batch (`digest pack ...` / `digest streams ...` / `digest fail ...`): every packed-form call —
+run and fetch, each encoding, header, trim, target, limiter, true peak, FLAC, v1 and v2 streams — as the sha256 of its block and of
+every result array, with the profiler's (label, calls, bytes) of the call: the labels outside the synthesis graph spelled out, the
+graph's own as one hash.  `--emu` runs the result-path lines alone on the CPU model's library (tests/emu) with the tiny voice: the
+host code is the same, and the model is too slow for the full voices.
 
 `bench` swaps the file bench.py opens (mimic3_amd/csrc/libmi355vits.so) — the product reads no library switch — and always puts NEW
 back at the end.  Output: one line per run with ms/step and the kernel table rows named in --rows.
@@ -49,22 +54,158 @@ def run_bits(lib_path, math=None):
     return out
 
 
-def run_digest(root):
-    """One line per result of the tree at `root`, through that tree's own package and product library."""
+RAGGED = [97, 128, 33, 5, 64, 120, 1, 77]  # the eight rows of `bits`
+TRIM = (0.03, 3)
+TARGET = (-6.0, -6.0)
+HUGE = (1 << 31) - 100  # a silence that fits on its own and not with any audio behind it
+
+
+def digest_results(sha, emu_root=None):
+    """The result-path lines: one synthesis of the ragged batch per run line, every fetch line served from the run before it."""
+    import numpy as np
+
+    from mimic3_amd import weights as W
+    from mimic3_amd._native import Engine, NativeError, NativeLibrary
+    from mimic3_amd.config import VitsConfig
+
+    cfg = VitsConfig.tiny() if emu_root else VitsConfig.apope_low()
+    lib = NativeLibrary(os.path.join(emu_root, "tests", "emu", "libmi355vits_emu.so")) if emu_root else None
+    eng = Engine(W.pack(cfg, W.synthetic_weights(cfg, seed=11, frames_per_id=4.0)), device=0, library=lib)
+    Tx = 16 if emu_root else 128
+    lens = [max(1, n * Tx // 128) for n in RAGGED]
+    rng = np.random.default_rng(5)
+    ids = np.zeros((len(lens), Tx), np.int64)
+    for b, n in enumerate(lens):
+        ids[b, :n] = rng.integers(1, cfg.num_symbols, size=n)
+    run_args = (ids, lens, [0.667, 1.0, 0.8])
+    run_kw = dict(seed=1234, pcm_volume=np.linspace(0.5, 3.0, len(lens)))
+    eng.profile_enable(True)
+    eng.profile_reset()
+    eng.run(*run_args, seed=1234)
+    graph = set(eng.profile_report())  # the labels of the synthesis itself
+
+    def prof():
+        rep = sorted((k, v["calls"], v["bytes"]) for k, v in eng.profile_report().items())
+        own = " ".join(f"{k}:{c}:{b:.0f}" for k, c, b in rep if k not in graph)
+        return f"prof [{own}] graph {sha(np.frombuffer(repr([r for r in rep if r[0] in graph]).encode(), np.uint8))}"
+
+    def arrays(pa):
+        block = pa.flac if pa.compression else (pa.wav if pa.wav is not None else pa.data)
+        out = [np.frombuffer(bytes(block), np.uint8), np.int64(pa.total_samples)]
+        for k in ("offsets", "lengths", "peaks", "first", "end", "lufs", "gain", "limited"):
+            v = getattr(pa, k)
+            out.append(np.zeros(0) if v is None else np.asarray(v))
+        for k in ("stream_offset", "data_offset", "stream_bytes", "frames", "uncompressed_bytes"):
+            out.append(np.int64(-1 if getattr(pa, k, None) is None else getattr(pa, k)))
+        return out
+
+    def line(kind, name, call):
+        eng.profile_reset()
+        try:
+            got = call()
+        except NativeError as e:
+            print(f"digest {kind} {name}: error {e.code} {e}", flush=True)
+            return
+        got = got if isinstance(got, list) else [got]
+        whole = [np.asarray(got[0].block)] if getattr(got[0], "block", None) is not None else []
+        print(f"digest {kind} {name}: " + " ".join(sha(*arrays(pa)) for pa in got) + (f" block {sha(*whole)} " if whole else " ") + prof(), flush=True)
+
+    order = [5, 0, 7, 2, 6, 1]
+    pack = dict(order=order, lead_samples=[0, 9000, 1, 100, 7, 4097], tail_samples=33)
+    settings = {
+        "plain": {},
+        "trim": dict(trim=TRIM),
+        "target": dict(loudness=TARGET),
+        "target+limiter": dict(loudness=TARGET, limiter=32),
+        "target+truepeak": dict(loudness=TARGET, true_peak=True),
+        "flac": dict(compression="flac"),
+    }
+
+    def setup(encoding="s16le", trim=(0.0, 0), loudness=(None, -1.0), limiter=0, true_peak=False, compression=None):
+        eng.set_output_encoding(encoding)
+        eng.set_edge_trim(*trim)
+        eng.set_loudness_target(*loudness)
+        eng.set_loudness_limiter(limiter)
+        eng.set_loudness_ceiling_mode("true_peak" if true_peak else "sample")
+        eng.set_output_compression(compression)
+
+    for sname, st in settings.items():
+        for enc in ("s16le",) if sname == "flac" else ("s16le", "ulaw", "alaw", "f32le"):
+            for wav in (False,) if sname == "flac" else (False, True):
+                setup(encoding=enc, **st)
+                tag = f"{sname} {enc}{' wav' if wav else ''}"
+                line("pack", "run " + tag, lambda: eng.run_packed(*run_args, wav=wav, **pack, **run_kw))
+                line("pack", "fetch " + tag, lambda: eng.fetch_packed(wav=wav, **pack))
+    setup()
+    # v1: four streams that share rows, mixed encodings, a header, a trimmed and normalised one; then the same measured from a fetch
+    four = [
+        dict(order=[3], lead_samples=[1], wav=True, encoding="ulaw"),
+        dict(order=[0, 4, 3], lead_samples=[0, 777, 2], tail_samples=5, wav=True, encoding="f32le"),
+        dict(order=[1, 0], encoding="s16le", trim=TRIM, loudness=TARGET),
+        dict(order=[2, 3], lead_samples=[4096 + 453, 0], encoding="alaw"),
+        dict(order=[3, 6], wav=True, encoding="s16le"),
+    ]
+    plain4 = [dict(st) for st in four if "trim" not in st]
+    eng.set_loudness_limiter(16)  # the one pair of handle settings a v1 call reads
+    line("streams", "run v1 plain", lambda: eng.run_streams(*run_args, streams=plain4, **run_kw))
+    line("streams", "fetch v1 plain", lambda: eng.fetch_streams(plain4))
+    line("streams", "run v1 measured", lambda: eng.run_streams(*run_args, streams=four, **run_kw))
+    line("streams", "fetch v1 measured", lambda: eng.fetch_streams(four))
+    setup()
+    # v2: two FLAC streams, two windows, both modes (tests/streams2_cases.py: SEVEN)
+    seven = [
+        dict(order=[3], wav=True, encoding="s16le", compression=None),
+        dict(order=[2, 0, 1], lead_samples=[0, 9000, 100], tail_samples=33, compression="flac"),
+        dict(order=[3], lead_samples=[1], wav=True, encoding="ulaw"),
+        dict(order=[2, 0, 1], lead_samples=[0, 9000, 100], tail_samples=33, compression="flac", trim=TRIM, loudness=TARGET, limiter=32, true_peak=True),
+        dict(order=[1, 4], encoding="s16le", loudness=TARGET, limiter=8, true_peak=False),
+        dict(order=[1, 4], encoding="s16le", loudness=TARGET, limiter=0),
+        dict(order=[0, 4], lead_samples=[0, 777], tail_samples=5, encoding="f32le"),
+    ]
+    line("streams", "run v2 seven", lambda: eng.run_streams(*run_args, streams=seven, **run_kw))
+    line("streams", "fetch v2 seven", lambda: eng.fetch_streams(seven))
+    line("streams", "run v2 flac only", lambda: eng.run_streams(*run_args, streams=seven[1:2], **run_kw))
+    # failing calls: the code and the text; a failing late path serves nothing afterwards
+    line("fail", "run_packed duplicate row", lambda: eng.run_packed(*run_args, order=[1, 2, 1], **run_kw))
+    line("fail", "fetch_packed negative silence", lambda: eng.fetch_packed(order=[1, 2], lead_samples=[0, -4]))
+    line("fail", "run_packed early over the limit", lambda: eng.run_packed(*run_args, order=[1], lead_samples=[HUGE], **run_kw))
+    line("fail", "fetch_packed after it", lambda: eng.fetch_packed())
+    eng.run(*run_args, seed=1234)
+    setup(trim=TRIM)
+    line("fail", "run_packed trimmed over the limit", lambda: eng.run_packed(*run_args, order=[1], lead_samples=[HUGE], **run_kw))
+    line("fail", "fetch_packed after it", lambda: eng.fetch_packed())
+    setup()
+    eng.run(*run_args, seed=1234)
+    line("fail", "run_streams duplicate row", lambda: eng.run_streams(*run_args, streams=[dict(order=[0]), dict(order=[2, 2])], **run_kw))
+    line("fail", "fetch_streams negative tail", lambda: eng.fetch_streams([dict(order=[0]), dict(order=[2], tail_samples=-1)]))
+    line("fail", "fetch_streams flac with wav", lambda: eng.fetch_streams([dict(order=[0], compression="flac", wav=True)]))
+    line("fail", "run_streams trimmed over the limit",
+         lambda: eng.run_streams(*run_args, streams=[dict(order=[0]), dict(order=[1], lead_samples=[HUGE], trim=TRIM)], **run_kw))
+    line("fail", "fetch_packed after it", lambda: eng.fetch_packed())
+    line("fail", "run_streams block over the limit",
+         lambda: eng.run_streams(*run_args, streams=[dict(order=[0], lead_samples=[HUGE // 2]), dict(order=[1], lead_samples=[HUGE // 2])], **run_kw))
+    eng.close()
+
+
+def run_digest(root, emu=False):
+    """One line per result of the tree at `root`, through that tree's own package and product library (emu: the CPU model's)."""
     import hashlib
 
     sys.path.insert(0, root)
     import numpy as np
-
-    from mimic3_amd import weights as W
-    from mimic3_amd._native import Engine
-    from mimic3_amd.config import VitsConfig
 
     def sha(*arrays):
         h = hashlib.sha256()
         for a in arrays:
             h.update(np.ascontiguousarray(a).tobytes())
         return h.hexdigest()[:32]
+
+    if emu:
+        digest_results(sha, root)
+        return
+    from mimic3_amd import weights as W
+    from mimic3_amd._native import Engine
+    from mimic3_amd.config import VitsConfig
 
     for voice, (audio, lengths, pcm) in run_bits(os.path.join(root, "mimic3_amd", "csrc", "libmi355vits.so")).items():
         print(f"digest ragged {voice}: audio {sha(audio)} lengths {sha(lengths)} pcm {sha(pcm)}")
@@ -80,6 +221,7 @@ def run_digest(root):
                         pcm_volume=np.linspace(0.5, 3.0, B))
     print(f"digest headline packed wav: bytes {sha(np.frombuffer(bytes(pk.wav), np.uint8))} offsets {sha(pk.offsets)} peaks {sha(pk.peaks)}")
     eng.close()
+    digest_results(sha)
 
 
 def main():
@@ -88,13 +230,14 @@ def main():
     ap.add_argument("prev", nargs="?")
     ap.add_argument("new", nargs="?")
     ap.add_argument("--root", default=ROOT)
+    ap.add_argument("--emu", action="store_true", help="digest: the result-path lines on the CPU model's library of the tree")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--rows", default="flow.wn_layer_b3,dec.mrf_p.s2,dec.mrf_s.s1,dec.rb.s0,enc.ffn1,enc.ffn2,dec.conv_pre")
     a = ap.parse_args()
     if a.mode == "digest":
-        run_digest(os.path.abspath(a.root))
+        run_digest(os.path.abspath(a.root), a.emu)
         return
     if not a.prev or not a.new:
         ap.error("bits / bench need PREV.so and NEW.so")
