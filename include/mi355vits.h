@@ -314,8 +314,9 @@ int mi355vits_get_output_encoding(mi355vits_handle h);
 
 /* ---- Phoneme timing and levels: WHERE in a run's audio each phoneme sits, and how loud it is there.  What speech marks for
  * captions, visemes and lip-sync, a position for the reference's SSML <mark> (MarkResult carries a name and no time:
- * opentts_abc/__init__.py:131-139, mimic3_tts/tts.py:467-468), cutting a stream at word boundaries and duration editing
- * (forced_durations is the matching INPUT) need.  The reference cannot give it: onnx_model.run returns the waveform only.
+ * opentts_abc/__init__.py:131-139, mimic3_tts/tts.py:467-468), cutting a stream at word boundaries and duration editing need
+ * (forced_durations replays a complete table; a rate per phoneme, a held pause or a fitted row length need no second run:
+ * mi355vits_run_timed below).  The reference cannot give it: onnx_model.run returns the waveform only.
  * mi355vits_fetch_alignment serves the LAST COMPLETED RUN of the handle whatever its flags were (padded, MI355VITS_DEVICE_ONLY or
  * packed), at the rate it ran at, as mi355vits_fetch does.  One kernel (k_align) makes every array on the GPU.
  *   frames[b,t]   latent frames of phoneme t: the run's ceil(exp(logw) * length_scale), or its forced_durations value.
@@ -358,6 +359,54 @@ typedef struct mi355vits_alignment {
 
 int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_alignment* out);
 void mi355vits_free_alignment(mi355vits_alignment* r);
+
+/* ---- Timing control in ONE run: a rate per phoneme, held pauses, a fitted row length.  What SSML <prosody rate> around a few
+ * words, <break> inside a sentence and "fit this line into 2.40 s" (dubbing, captions, IVR prompts) need.  Without it a caller
+ * runs, fetches the alignment, edits the frames on the host and runs again with forced_durations: a text encoder, a duration
+ * predictor, a host round trip and a decoder pass spent to learn integers the device already held.  The reference can scale a
+ * whole sentence only (length_scale, one run per sentence).  mi355vits_run_timed is mi355vits_run_rows with the durations shaped
+ * where they become known: ONE kernel (k_durations_timed) takes the place of k_durations, before the run's only sizing
+ * synchronisation — no launch and no synchronisation more than the plain run.
+ * The rule, exact: integers and single IEEE f32 products rounded to nearest, no tolerance.  Per row b, L = input_lengths[b], t < L:
+ *   u[t]    = fl(w[t] * stretch[b,t])                    w[t] = exp(logw[t]) * length_scale[b], the float the plain run rounds up
+ *   c(x)    = x < CAP ? (int) ceilf(x) : CAP + 1          CAP = 4,194,304 frames
+ *   f[t](s) = max(c(fl(u[t] * s)), min_frames[b,t])      s a positive finite f32
+ *   F(s)    = f[0](s) + .. + f[L-1](s)                   in 64-bit integers
+ *  - target_frames[b] == 0 (or NULL): frames[t] = f[t](1.0f), factor 1.0f.  With stretch 1 and min_frames 0 that is bit for bit the
+ *    plain run's ceil(exp(logw) * length_scale).
+ *  - target_frames[b] = N, 1 .. CAP: F never falls as s grows and positive floats sort like their bit patterns.  s* = the largest
+ *    f32 in [2^-30, 2^30] with F(s*) <= N, found by bisection over the bit patterns; frames[t] = f[t](s*), and the N - F(s*)
+ *    frames still missing go to the phonemes that step at s' = nextafterf(s*, +inf), walking t upward: phoneme t receives
+ *    min(f[t](s') - f[t](s*), what is left).  The frames of the row then sum to N exactly: lengths[b] = N * hop_length in a native
+ *    run, ceil(N * hop_length * L / M) at another output rate.  factor_out[b] = s*.
+ *  - F(2^-30) > N: the target is below the floor (the minimum frames, and one frame for every other phoneme with u > 0):
+ *    MI355VITS_ERR_INVALID, "row 3: target of 40 frames is below the 57 the row needs at least".  F(2^30) < N (every stretch 0, say):
+ *    MI355VITS_ERR_INVALID naming the row.  Both are found at the run's sizing synchronisation, before anything behind the text
+ *    side is sized or launched: no partial audio, and the handle is left as by any run that fails there (a predicted duration out
+ *    of range): it serves no result until the next completed run.
+ *  - Positions t >= L: frames 0, whatever stretch and min_frames hold there (they are neither checked nor read).
+ *  - A row of a batch is bitwise the row alone (same tx_max class, see mi355vits_run_rows): the rule has no float sum in it.
+ *  - Scope: timing == NULL, or stretch, min_frames and target_frames all NULL: the call IS mi355vits_run_rows — the same launches,
+ *    bytes and synchronisations (factor_out, when given, reads 1.0f).  All flags work as there, MI355VITS_DEVICE_ONLY included; the
+ *    packed and streams forms need no call of their own: mi355vits_fetch_packed, _fetch_streams, _fetch_streams2 and
+ *    mi355vits_fetch_alignment serve the last completed run whatever made it, so a timed run with MI355VITS_DEVICE_ONLY followed by
+ *    one of them gives every output form at the cost of the ONE synchronisation more that the fetch takes.
+ *    mi355vits_fetch_alignment reports the fitted frames.  Feeding them back as forced_durations (same seed and keys) gives bitwise
+ *    the same audio.  Under MI355VITS_DEBUG_TAPS a timed run also serves the tap "dur_float" [B, 1, tx_max]: u[t], 0 behind the row.
+ *  - Errors, all MI355VITS_ERR_INVALID and, but for the two above, raised before anything is launched (the previous run stays
+ *    served): forced_durations together with any timing input ("timing and forced_durations exclude each other"); a stretch that
+ *    is not finite or outside 0 .. 2^20, a min_frames outside 0 .. CAP (checked at t < input_lengths[b] only; the message names row
+ *    and phoneme); a target_frames outside 0 .. CAP (names the row); a non-zero reserved field.
+ *  - With profiling enabled the kernel is reported as "durations.timed" in place of "durations". */
+typedef struct mi355vits_timing_args {
+    const float*   stretch;        /* [B, tx_max] or NULL (= 1): duration multiplier per phoneme; finite, 0 <= x <= 2^20 */
+    const int32_t* min_frames;     /* [B, tx_max] or NULL (= 0): 0 .. CAP; a pause symbol held at least this long */
+    const int32_t* target_frames;  /* [B] or NULL: 0 = none, else the row's latent frames, 1 .. CAP (duration = frames * hop / rate) */
+    float*         factor_out;     /* [B] or NULL, caller-owned: s* per row (1.0f without a target) */
+    int32_t        reserved[6];    /* must be 0 */
+} mi355vits_timing_args;
+int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                        const mi355vits_timing_args* timing /* may be NULL */, mi355vits_result* out);
 
 /* ---- Exact pauses: trim each entry's quiet edges in the packed streams.  A VITS voice puts a stretch of near-silence of its own at
  * the start and the end of every sentence; the reference adds its break (int(ms / 1000 * sample_rate) zero samples,

@@ -207,6 +207,15 @@ int mi355vits_test_spline_inverse(int device, int B, int T, int nb, int ch_x0, f
  * forced is not read there. */
 int mi355vits_test_durations(int device, int B, int T, int ch, float ea_m, float ea_logs, const float* z, const int32_t* len,
                              const int32_t* forced, const float* scales, float* logw, int32_t* w_ceil, int32_t* cum, int32_t* ylen);
+/* Kernel unit-test hook: the fit stage of launch_durations_timed (k_durations_timed; include/mi355vits.h, timing control) alone on
+ * a given u [B, T] (what the kernel otherwise makes from logw, length_scale and stretch).  len [B], min_frames [B, T] or NULL (= 0),
+ * target [B] or NULL (= none; 0 = none for that row, else 1 .. cap) -> frames [B, T], cum [B, T] (inclusive scan, saturating at
+ * 2 cap), ylen [B] = max(1, sum), factor [B] = s* (1.0f without a target), status [B]: 0 ok; 1 the target is below the floor
+ * F(2^-30): frames = f(2^-30), factor = 2^-30; 2 the target is above F(2^30): frames = f(2^30), factor = 2^30.
+ * Every output is written at every t < T (frames 0 and cum flat at and past len[b]); the caller's contents of the outputs are
+ * uploaded first, so a missing write shows.  u and min_frames are not read at and past len[b]. */
+int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const int32_t* len, const int32_t* min_frames,
+                                 const int32_t* target, int32_t* frames, int32_t* cum, int32_t* ylen, float* factor, int32_t* status);
 /* Kernel unit-test hook: launch_expand_prior (k_expand_prior; the length regulator + the prior's sample) with injected noise.
  * stats [B, 2 I, Tx] = m_p | logs_p, cum [B, Tx] (non-decreasing, >= 0), ylen [B] (0 <= ylen[b] <= Ty), scales [B, 3] (noise_scale is
  * the one read), injected [B, I, injected_frames] with injected_frames >= Ty, or NULL where every row's noise_scale is 0 (anything

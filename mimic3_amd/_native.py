@@ -32,7 +32,7 @@ HOOKS_LIBRARY = os.path.join(_HERE, "csrc", "libmi355vits_hooks.so")
 EXPORTED_SYMBOLS = (
     "mi355vits_version", "mi355vits_device_count", "mi355vits_create", "mi355vits_create_from_buffer", "mi355vits_clone", "mi355vits_destroy",
     "mi355vits_device_result", "mi355vits_set_math", "mi355vits_get_math",
-    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_fetch", "mi355vits_free_result",
+    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
@@ -56,6 +56,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
+    "mi355vits_test_fit_durations",
 )
 
 
@@ -118,6 +119,16 @@ class RowArgs(ctypes.Structure):
         ("scales", ctypes.POINTER(ctypes.c_float)),
         ("pcm_volume", ctypes.POINTER(ctypes.c_double)),
         ("utterance", ctypes.POINTER(ctypes.c_uint64)),
+    ]
+
+
+class TimingArgs(ctypes.Structure):  # mi355vits_timing_args
+    _fields_ = [
+        ("stretch", ctypes.POINTER(ctypes.c_float)),
+        ("min_frames", ctypes.POINTER(ctypes.c_int32)),
+        ("target_frames", ctypes.POINTER(ctypes.c_int32)),
+        ("factor_out", ctypes.POINTER(ctypes.c_float)),
+        ("reserved", ctypes.c_int32 * 6),
     ]
 
 
@@ -446,6 +457,7 @@ class NativeLibrary:
         L.mi355vits_get_config.argtypes = [H, ctypes.POINTER(CVitsConfig)]
         L.mi355vits_run.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(Result)]
         L.mi355vits_run_rows.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(Result)]
+        L.mi355vits_run_timed.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs), ctypes.POINTER(Result)]
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
@@ -551,6 +563,7 @@ class NativeLibrary:
             L.mi355vits_lab_mrf_plan.argtypes = [ctypes.c_int] * 3 + [i32p] * 7
             L.mi355vits_test_dds_stack.argtypes = [ctypes.c_int, ctypes.POINTER(DdsStackTest)]
             L.mi355vits_test_spline_inverse.argtypes = [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, f32p, i32p, f32p]
+            L.mi355vits_test_fit_durations.argtypes = [ctypes.c_int] * 3 + [f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p]
             L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
             L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
 
@@ -963,6 +976,28 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return logw, w_ceil, cum, ylen
 
+    def test_fit_durations(self, u, lengths, min_frames=None, target=None, device=0):
+        """The fit stage of launch_durations_timed alone on a given u [B, T]: lengths [B], min_frames [B, T] or None, target [B] or
+        None -> (frames [B, T], cum [B, T], ylen [B], factor [B], status [B]) (mi355vits_test_fit_durations).  The outputs start as
+        -77 / -7.5e29."""
+        self._need_hooks()
+        u = np.ascontiguousarray(u, np.float32)
+        B, T = u.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        mn = None if min_frames is None else np.ascontiguousarray(min_frames, np.int32)
+        tg = None if target is None else np.ascontiguousarray(target, np.int32)
+        assert ln.shape == (B,) and (mn is None or mn.shape == (B, T)) and (tg is None or tg.shape == (B,))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        frames, cum = np.full((B, T), -77, np.int32), np.full((B, T), -77, np.int32)
+        ylen, status, factor = np.full(B, -77, np.int32), np.full(B, -77, np.int32), np.full(B, -7.5e29, np.float32)
+        rc = self.lib.mi355vits_test_fit_durations(device, B, T, _fptr(u), ln.ctypes.data_as(i32p),
+                                                   None if mn is None else mn.ctypes.data_as(i32p),
+                                                   None if tg is None else tg.ctypes.data_as(i32p), frames.ctypes.data_as(i32p),
+                                                   cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p), _fptr(factor), status.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return frames, cum, ylen, factor, status
+
     def test_expand_prior(self, stats, cum, ylen, Ty, noise_scale=0.0, injected=None, z_prior=None, device=0) -> np.ndarray:
         """launch_expand_prior alone with injected noise: stats [B, 2 I, Tx], cum [B, Tx], ylen [B], noise_scale a number or [B],
         injected [B, I, frames >= Ty] or None -> z [B, I, Ty] (mi355vits_test_expand_prior)."""
@@ -1193,6 +1228,7 @@ class Engine:
         self.config = VitsConfig.from_c(c)
         self.device = device
         self._last_batch = 0  # rows of the last completed run (fetch_packed's default pack with a tail or a header)
+        self.last_timing_factor = None  # [B] of the last timed run_packed (run returns it as "timing_factor")
         self._last_rate = int(self.config.sample_rate)  # the rate it ran at (results of a run keep it)
 
     def _check(self, rc: int) -> None:
@@ -1213,23 +1249,72 @@ class Engine:
     # ---- one synthesis call ---------------------------------------------------------------------
     def run(self, ids, lengths, scales, sid=None, *, seed: int = 0, utterance_base: int = 0, noise_w=None,
             noise_z=None, forced_durations=None, want_float: bool = True, want_pcm16: bool = False,
-            device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None) -> Dict[str, np.ndarray]:
+            device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None,
+            stretch=None, min_frames=None, target_frames=None) -> Dict[str, np.ndarray]:
         """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
         ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
-        its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class)."""
+        its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class).
+        Timing (``mi355vits_run_timed``, when any of the three is given): ``stretch`` [B, Tx] duration multiplier per phoneme,
+        ``min_frames`` [B, Tx] frames a phoneme is held at least, ``target_frames`` [B] the row's latent frames (0 = none); the
+        result then carries ``"timing_factor"`` [B], the factor s* every row was fitted with (1.0 without a target)."""
+        timing, tkeep = self._timing_args(np.shape(ids), stretch, min_frames, target_frames)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
                   (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         r = Result()
-        if per_row:
+        if timing is not None:
+            self._check(self.native.lib.mi355vits_run_timed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                            ctypes.byref(timing), ctypes.byref(r)))
+        elif per_row:
             self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
         else:
             self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
         del keep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate  # read when the run started; only this thread sets it meanwhile
-        return self._take(r)
+        out = self._take(r)
+        if timing is not None:
+            out["timing_factor"] = tkeep[-1]
+        return out
+
+    @staticmethod
+    def _timing_args(shape, stretch, min_frames, target_frames):
+        """``mi355vits_timing_args`` (or None without any of the three) + the arrays it points into; the last of them is
+        ``factor_out`` [B].  Shapes are checked as ``forced_durations``' is."""
+        if stretch is None and min_frames is None and target_frames is None:
+            return None, []
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        B, Tx = shape
+        t, keep = TimingArgs(), []
+        if stretch is not None:
+            stretch = np.ascontiguousarray(stretch, dtype=np.float32)
+            if stretch.shape != (B, Tx):
+                raise ValueError("stretch must have shape [batch, phonemes]")
+            keep.append(stretch)
+            t.stretch = _fptr(stretch)
+        if min_frames is not None:
+            if not np.issubdtype(np.asarray(min_frames).dtype, np.integer):
+                raise ValueError("min_frames must hold integers")
+            min_frames = np.ascontiguousarray(min_frames, dtype=np.int32)
+            if min_frames.shape != (B, Tx):
+                raise ValueError("min_frames must have shape [batch, phonemes]")
+            keep.append(min_frames)
+            t.min_frames = min_frames.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if target_frames is not None:
+            if not np.issubdtype(np.asarray(target_frames).dtype, np.integer):
+                raise ValueError("target_frames must hold integers")
+            tf64 = np.asarray(target_frames, dtype=np.int64).reshape(-1)
+            if tf64.shape != (B,):
+                raise ValueError("target_frames must have shape [batch]")
+            target_frames = np.ascontiguousarray(np.clip(tf64, -1, 2**31 - 1), dtype=np.int32)  # (out of range either way: the library names the row)
+            keep.append(target_frames)
+            t.target_frames = target_frames.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        factor = np.full(B, np.nan, np.float32)
+        keep.append(factor)
+        t.factor_out = _fptr(factor)
+        return t, keep
 
     def _args(self, ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations, pcm_volume, utterance_keys):
         """The feed as ``mi355vits_run_args`` + ``mi355vits_row_args`` (flags not set): (args, rows, any per-row setting, the
@@ -1325,14 +1410,26 @@ class Engine:
 
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
-                   debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE) -> PackedAudio:
+                   debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE,
+                   stretch=None, min_frames=None, target_frames=None) -> PackedAudio:
         """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
         ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
         the last entry, with ``wav`` a 44-byte RIFF header in front.  Each entry is bitwise that row of
         ``run(..., want_pcm16=True)`` for the same arguments; one kernel, one device-to-host copy of exactly that many bytes.
         ``compression="flac"`` / ``None``: this call's stream compressed or not, whatever ``set_output_compression`` says (the
-        setting is put back afterwards); with FLAC the result's ``.flac`` is the file and ``wav=True`` raises ``ValueError``."""
+        setting is put back afterwards); with FLAC the result's ``.flac`` is the file and ``wav=True`` raises ``ValueError``.
+        With any of ``stretch`` / ``min_frames`` / ``target_frames`` (see ``run``): a timed run that keeps its audio on the device
+        (``mi355vits_run_timed`` with ``MI355VITS_DEVICE_ONLY``), then ``fetch_packed`` of it — one synchronisation more; the
+        factors are left in ``last_timing_factor``."""
+        if stretch is not None or min_frames is not None or target_frames is not None:
+            comp = self._call_compression(compression, wav)  # refuses wav + FLAC before anything runs
+            res = self.run(ids, lengths, scales, sid, seed=seed, utterance_base=utterance_base, noise_w=noise_w, noise_z=noise_z,
+                           forced_durations=forced_durations, want_float=False, want_pcm16=False, device_only=True,
+                           debug_taps=debug_taps, pcm_volume=pcm_volume, utterance_keys=utterance_keys, stretch=stretch,
+                           min_frames=min_frames, target_frames=target_frames)
+            self.last_timing_factor = res["timing_factor"]
+            return self.fetch_packed(order=order, lead_samples=lead_samples, tail_samples=tail_samples, wav=wav, compression=compression)
         comp = self._call_compression(compression, wav)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)

@@ -168,6 +168,14 @@ int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const
     });
 }
 
+int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                        const mi355vits_timing_args* timing, mi355vits_result* out) {
+    return result_call(h, out, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        h->eng->run(*args, rows, out, timing);
+    });
+}
+
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out) {
     return result_call(h, out, [&] { h->eng->fetch(want_flags, out); });
 }

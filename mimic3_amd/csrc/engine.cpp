@@ -1056,11 +1056,29 @@ void Engine::duration_predictor_det(int B, int Tx) {
         ProfScope ps(prof_, "dp.det", flops, 4.0 * B * (double)Tx * (H + 1));
         launch_dp_det(a, stream_);
     }
-    {
+    durations(B, Tx, 0, 0.0f, 0.0f);
+}
+
+// The durations of both predictors: k_durations, or in a timed run k_durations_timed IN ITS PLACE (the same EA^-1 and logw, then
+// the fit: kernels_timing.cpp), which also leaves status and factor of every row right behind d_ylen_.
+void Engine::durations(int B, int Tx, int ch, float ea_m, float ea_logs) {
+    if (!timed_run_) {
         ProfScope ps(prof_, "durations");
-        launch_durations(d_z2_, 0, 0.0f, 0.0f, d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_, d_cum_, d_ylen_, stream_);
+        launch_durations(d_z2_, ch, ea_m, ea_logs, d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_, d_cum_, d_ylen_, stream_);
+    } else {
+        DurTimedArgs a;
+        a.z = d_z2_; a.ch = ch; a.ea_m = ea_m; a.ea_logs = ea_logs;
+        a.len = d_len_; a.B = B; a.T = Tx;
+        a.scales = d_scales_;
+        a.stretch = d_stretch_; a.min_frames = d_minf_; a.target = d_target_;
+        a.logw = d_logw_; a.u = d_durf_;
+        a.w_ceil = d_wceil_; a.cum = d_cum_; a.ylen = d_ylen_;
+        a.factor = d_tfactor_; a.status = d_tstatus_;
+        ProfScope ps(prof_, "durations.timed");
+        launch_durations_timed(a, stream_);
     }
     tap("logw", d_logw_, {B, 1, Tx});
+    if (timed_run_) tap("dur_float", d_durf_, {B, 1, Tx});
 }
 
 void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
@@ -1184,13 +1202,7 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
         }
     }
     ch0 ^= 1;  // Flip before the ElementwiseAffine
-    {
-        ProfScope ps(prof_, "durations");
-        // logical channel 0 uses EA parameters [0]
-        launch_durations(d_z2_, ch0, model_->ea_m[0], model_->ea_logs[0], d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_,
-                         d_cum_, d_ylen_, stream_);
-    }
-    tap("logw", d_logw_, {B, 1, Tx});
+    durations(B, Tx, ch0, model_->ea_m[0], model_->ea_logs[0]);  // logical channel 0 uses EA parameters [0]
 }
 
 // =================================================================================================
@@ -1487,7 +1499,7 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
 // =================================================================================================
 // The sequence of alloc calls below IS the workspace layout: run() plays it against an ArenaCount for the size to reserve, then
 // against the arena for the pointers.
-template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w) {
+template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing) {
     const mi355vits_config& c = cfg_;
     const size_t H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels, fBT = B * Tx;
     const size_t nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
@@ -1501,7 +1513,15 @@ template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool for
     d_utt_ = ar.template alloc<unsigned long long>(B);
     d_forced_ = forced ? ar.template alloc<int>(fBT) : nullptr;
     d_noise_w_ = noise_w ? ar.template alloc<float>(fBT * 2) : nullptr;
-    d_ylen_ = ar.template alloc<int>(B);
+    d_stretch_ = (timing & 1) ? ar.template alloc<float>(fBT) : nullptr;
+    d_minf_ = (timing & 2) ? ar.template alloc<int>(fBT) : nullptr;
+    d_target_ = (timing & 4) ? ar.template alloc<int>(B) : nullptr;
+    // what the host reads at the run's one sizing synchronisation: ylen, and of a timed run status and factor, in ONE copy (4-byte
+    // words side by side: each of the three is B words)
+    d_ylen_ = ar.template alloc<int>(3 * B);
+    d_tstatus_ = d_ylen_ + B;
+    d_tfactor_ = reinterpret_cast<float*>(d_ylen_ + 2 * B);
+    d_durf_ = ar.template alloc<float>(fBT);
     d_peaks_ = ar.template alloc<unsigned>(B);
     d_wceil_ = ar.template alloc<int>(fBT);
     d_cum_ = ar.template alloc<int>(fBT);
@@ -1556,14 +1576,16 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_rtab_ = Lr ? d_alen_ + B : nullptr;
 }
 
-void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out) {
+void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
+                 const mi355vits_timing_args* timing) {
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
-    synthesize(args, rows, nullptr);
+    synthesize(args, rows, nullptr, timing);
     copy_out(args.flags, out);
 }
 
-void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan) {
+void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
+                        const mi355vits_timing_args* timing) {
     const mi355vits_config& c = cfg_;
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     const float* row_scales = rows ? rows->scales : nullptr;
@@ -1609,6 +1631,26 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         if (multi && (args.sid[b] < 0 || args.sid[b] >= c.n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "speaker id out of range");
     }
     if (args.noise_z && args.noise_z_frames < 1) throw EngineError(MI355VITS_ERR_INVALID, "noise_z_frames must be >= 1");
+    // timing (mi355vits_run_timed): without any of the three inputs the run is the plain one, launch for launch
+    int tmask = 0;
+    if (timing) {
+        for (int i = 0; i < 6; ++i)
+            if (timing->reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "timing: reserved fields must be 0");
+        tmask = (timing->stretch ? 1 : 0) | (timing->min_frames ? 2 : 0) | (timing->target_frames ? 4 : 0);
+        if (tmask && args.forced_durations) throw EngineError(MI355VITS_ERR_INVALID, "timing and forced_durations exclude each other");
+        for (int b = 0; b < B; ++b) {
+            const std::string rowname = "row " + std::to_string(b);
+            for (int t = 0; t < len32[b]; ++t) {
+                const size_t i = (size_t)b * Tx + t;
+                if (timing->stretch && !(std::isfinite(timing->stretch[i]) && timing->stretch[i] >= 0.0f && timing->stretch[i] <= 1048576.0f))
+                    throw EngineError(MI355VITS_ERR_INVALID, rowname + ", phoneme " + std::to_string(t) + ": stretch must be finite and within 0 .. 2^20");
+                if (timing->min_frames && (timing->min_frames[i] < 0 || timing->min_frames[i] > DURATION_FRAME_CAP))
+                    throw EngineError(MI355VITS_ERR_INVALID, rowname + ", phoneme " + std::to_string(t) + ": min_frames must be within 0 .. " + std::to_string(DURATION_FRAME_CAP));
+            }
+            if (timing->target_frames && (timing->target_frames[b] < 0 || timing->target_frames[b] > DURATION_FRAME_CAP))
+                throw EngineError(MI355VITS_ERR_INVALID, rowname + ": target_frames must be 0 (none) or within 1 .. " + std::to_string(DURATION_FRAME_CAP));
+        }
+    }
 
     HIP_CHECK(hipSetDevice(device_));
     have_result_ = false;
@@ -1626,11 +1668,12 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     // reallocate when the next call brings them
     const size_t fBT = (size_t)B * Tx;
     ArenaCount size_a;
-    layout_a(size_a, B, Tx, true, true);
+    layout_a(size_a, B, Tx, true, true, 7);
     arena_a_.reserve(size_a.bytes + 4096, stream_);
     arena_a_.reset();
-    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr);
+    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr, tmask);
     const size_t in_bytes = reinterpret_cast<unsigned char*>(d_ylen_) - reinterpret_cast<unsigned char*>(d_ids_);
+    timed_run_ = tmask != 0;
 
     HIP_CHECK(hipEventRecord(ev_start_, stream_));
     timed_ = false;
@@ -1648,6 +1691,9 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         put(d_utt_, utt.data(), (size_t)B * 8);
         if (args.forced_durations) put(d_forced_, args.forced_durations, fBT * 4);
         if (args.noise_w) put(d_noise_w_, args.noise_w, fBT * 2 * 4);
+        if (d_stretch_) put(d_stretch_, timing->stretch, fBT * 4);
+        if (d_minf_) put(d_minf_, timing->min_frames, fBT * 4);
+        if (d_target_) put(d_target_, timing->target_frames, (size_t)B * 4);
         // h_in_ is a member: it outlives the copy whatever HIP does with pageable sources
         HIP_CHECK(hipMemcpyAsync(d_ids_, h0, in_bytes, hipMemcpyHostToDevice, stream_));
     }
@@ -1669,9 +1715,23 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     duration_predictor(B, Tx, args);
 
     // ---------------- the one host round trip: frame counts size the rest of the graph
-    h_ylen_.resize(B);
-    HIP_CHECK(hipMemcpyAsync(h_ylen_.data(), d_ylen_, (size_t)B * 4, hipMemcpyDeviceToHost, stream_));
+    // (a timed run: status and factor of every row sit right behind ylen and come in the same copy)
+    const size_t nread = timed_run_ ? 3 : 1;
+    h_ylen_.resize(nread * B);
+    HIP_CHECK(hipMemcpyAsync(h_ylen_.data(), d_ylen_, nread * B * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+    if (timed_run_) {
+        for (int b = 0; b < B; ++b) {
+            const int st = h_ylen_[(size_t)B + b];
+            const std::string what = "row " + std::to_string(b) + ": target of " + std::to_string(timing->target_frames ? timing->target_frames[b] : 0) + " frames ";
+            if (st == TIMING_BELOW_FLOOR) throw EngineError(MI355VITS_ERR_INVALID, what + "is below the " + std::to_string(h_ylen_[b]) + " the row needs at least");
+            if (st == TIMING_UNREACHABLE) throw EngineError(MI355VITS_ERR_INVALID, what + "cannot be reached: at the largest factor, 2^30, the row has " + std::to_string(h_ylen_[b]) + " (is every stretched duration 0?)");
+            if (st != TIMING_OK) throw EngineError(MI355VITS_ERR_INTERNAL, "row " + std::to_string(b) + ": timing status " + std::to_string(st));
+        }
+        if (timing->factor_out) memcpy(timing->factor_out, h_ylen_.data() + 2 * (size_t)B, (size_t)B * 4);
+    } else if (timing && timing->factor_out) {
+        std::fill(timing->factor_out, timing->factor_out + B, 1.0f);
+    }
     int Ty = 1;
     for (int b = 0; b < B; ++b) {
         if (h_ylen_[b] < 1 || h_ylen_[b] > DURATION_FRAME_CAP) throw EngineError(MI355VITS_ERR_INVALID, "predicted duration out of range (bad weights or length_scale?)");

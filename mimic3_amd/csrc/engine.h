@@ -180,7 +180,9 @@ class Engine {
     // device pointers of the last run's results (valid until the next run on this handle); for device-side gathers
     void device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths);
     // rows: per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
-    void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out);
+    // timing: per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
+    void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
+             const mi355vits_timing_args* timing = nullptr);
     void fetch(uint32_t want, mi355vits_result* out);
     // the packed stream (mi355vits_run_packed / mi355vits_fetch_packed): pack == NULL = every row, in order, no silence, no header
     void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
@@ -273,7 +275,7 @@ class Engine {
     int mrf_stage(int i, int B, int ch, long T);       // the stage's leading resblocks in one launch; how many it took
     ConvArgs rb2_conv_args(int i, int j, int m, int B, int ch, long T) const;
     // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
-    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w);
+    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing);  // timing: 1 stretch | 2 min_frames | 4 target_frames
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
     // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
@@ -373,7 +375,10 @@ class Engine {
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with an output plan
     // the packed stream or block instead (its places made from the frame counts, its table uploaded with the per-stage lengths)
-    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan);
+    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
+                    const mi355vits_timing_args* timing = nullptr);
+    // k_durations, or in a timed run k_durations_timed in its place (the one call of both predictors)
+    void durations(int B, int Tx, int ch, float ea_m, float ea_logs);
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
     void plan_single(const mi355vits_pack_args* pack, int B, OutputPlan& op) const;  // a packed call's plan: plan_pack under the handle's settings
     // validates every stream, naming it (v1's streams arrive as v2 ones carrying the handle's window and mode, uncompressed)
@@ -466,6 +471,11 @@ class Engine {
     unsigned long long* d_utt_ = nullptr;
     int *d_len_ = nullptr, *d_wceil_ = nullptr, *d_cum_ = nullptr, *d_ylen_ = nullptr, *d_alen_ = nullptr,
         *d_forced_ = nullptr;
+    // a timed run's inputs (in the one upload, like d_forced_) and, right behind d_ylen_ (the same copy brings all three to the
+    // host), its status and factor per row; d_durf_ = the u[t] the fit ran on (the dur_float tap)
+    float *d_stretch_ = nullptr, *d_tfactor_ = nullptr, *d_durf_ = nullptr;
+    int *d_minf_ = nullptr, *d_target_ = nullptr, *d_tstatus_ = nullptr;
+    bool timed_run_ = false;
     float *d_x_ = nullptr, *d_x2_ = nullptr, *d_qkv_ = nullptr, *d_att_ = nullptr, *d_ffn_ = nullptr, *d_part_ = nullptr,
           *d_stats_ = nullptr;
     float *d_h_ = nullptr, *d_d0_ = nullptr, *d_d1_ = nullptr, *d_d2_ = nullptr, *d_theta_ = nullptr, *d_z2_ = nullptr,

@@ -560,6 +560,39 @@ constexpr int DURATION_FRAME_CAP = 1 << 22;
 // ylen = max(1, sum)
 void launch_durations(const float* z, int ch, float ea_m, float ea_logs, const int* len, const int* forced, int B,
                       int T, const float* scales, float* logw, int* w_ceil, int* cum, int* ylen, hipStream_t s);
+// the two expressions k_durations and k_durations_timed share, so that a timed run's durations start from the very bits an
+// untimed run rounds up: logw out of the flow's channel (EA^-1, es = expf(-ea_logs)), the float duration of a phoneme (m = 1 inside
+// the row, 0 behind it) and its guarded frame count
+__device__ __forceinline__ float duration_logw(float z, float ea_m, float es, float m) { return (z - ea_m) * es * m; }
+__device__ __forceinline__ float duration_float(float lw, float m, float length_scale) { return expf(lw) * m * length_scale; }
+// inf / NaN / absurd durations (bad weights, huge length_scale) must not reach the float -> int cast (UB): they become one
+// over-the-cap count, which the host turns into ERR_INVALID before sizing anything
+__device__ __forceinline__ int duration_count(float w) { return (w < (float)DURATION_FRAME_CAP) ? (int)ceilf(w) : DURATION_FRAME_CAP + 1; }
+
+// ---------------------------------------------------------------- timing control (kernels_timing.cpp; mi355vits_run_timed)
+// k_durations_timed in place of k_durations: EA^-1 and logw as there, then per row (L = len[b], t < L)
+//   u[t] = fl(w[t] * stretch[b,t]),  f[t](s) = max(c(fl(u[t] * s)), min_frames[b,t]),  F(s) = sum f[t](s)   (c = duration_count)
+// without a target frames = f(1.0f); with target N the largest f32 s* in [2^-30, 2^30] with F(s*) <= N by bisection over the bit
+// patterns, and the N - F(s*) frames still missing go, in index order, to the phonemes that step at nextafterf(s*): sum frames == N.
+// status: 0 ok; 1 F(2^-30) > N (frames = f(2^-30): the floor, factor = 2^-30); 2 F(2^30) < N (frames = f(2^30), factor = 2^30).
+// cum / ylen as k_durations.  Integers and single f32 products only: no result depends on the grid, the batch or an address.
+constexpr int TIMING_OK = 0, TIMING_BELOW_FLOOR = 1, TIMING_UNREACHABLE = 2;
+constexpr int TIMING_LDS_T = 16384;  // rows up to this many phonemes keep u and min_frames in LDS (128 KB); longer ones re-read them
+struct DurTimedArgs {
+    const float* z = nullptr; int ch = 0; float ea_m = 0, ea_logs = 0;  // as launch_durations ...
+    const float* u_in = nullptr;       // ... or (the lab hook: the fit stage alone) u [B, T] given; z, scales, stretch, logw unused
+    const int* len = nullptr; int B = 1, T = 0;
+    const float* scales = nullptr;
+    const float* stretch = nullptr;    // [B, T] or null (= 1)
+    const int* min_frames = nullptr;   // [B, T] or null (= 0)
+    const int* target = nullptr;       // [B] or null (= none)
+    float* logw = nullptr;             // [B, T]
+    float* u = nullptr;                // [B, T]: the u[t] the rule ran on, 0 behind the row (the dur_float tap)
+    int *w_ceil = nullptr, *cum = nullptr, *ylen = nullptr;
+    float* factor = nullptr;           // [B]: s*, 1.0f without a target
+    int* status = nullptr;             // [B]: TIMING_*
+};
+void launch_durations_timed(const DurTimedArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- length regulator + prior sampling (K6, K7)
 void launch_expand_prior(const float* stats /*[B,2I,Tx]: m_p | logs_p*/, const int* cum, const int* ylen,

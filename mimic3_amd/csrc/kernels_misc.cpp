@@ -1361,12 +1361,10 @@ __global__ __launch_bounds__(256) void k_durations(const float* z, int ch, float
     const float es = expf(-ea_logs);
     for (int t = threadIdx.x; t < T; t += 256) {
         const float m = t < L ? 1.0f : 0.0f;
-        const float lw = (z[((long)b * 2 + ch) * T + t] - ea_m) * es * m;
+        const float lw = duration_logw(z[((long)b * 2 + ch) * T + t], ea_m, es, m);
         logw[(long)b * T + t] = lw;
-        float w = expf(lw) * m * length_scale;
-        // inf / NaN / absurd durations (bad weights, huge length_scale) must not reach the float -> int cast (UB):
-        // they become one over-the-cap count, which the host turns into ERR_INVALID before sizing anything
-        int wc = (w < (float)DURATION_FRAME_CAP) ? (int)ceilf(w) : DURATION_FRAME_CAP + 1;
+        const float w = duration_float(lw, m, length_scale);
+        int wc = duration_count(w);  // guarded: inf / NaN / absurd durations become one over-the-cap count (kernels.h)
         if (forced) {
             wc = t < L ? forced[(long)b * T + t] : 0;
             if (wc < 0 || wc > DURATION_FRAME_CAP) wc = DURATION_FRAME_CAP + 1;

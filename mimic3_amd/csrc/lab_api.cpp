@@ -893,6 +893,46 @@ int mi355vits_test_durations(int device, int B, int T, int ch, float ea_m, float
     });
 }
 
+int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const int32_t* len, const int32_t* min_frames,
+                                 const int32_t* target, int32_t* frames, int32_t* cum, int32_t* ylen, float* factor, int32_t* status) {
+    return guarded(nullptr, [&] {
+        if (!u || !len || !frames || !cum || !ylen || !factor || !status) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        for (int b = 0; b < B; ++b) {
+            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+            if (target && (target[b] < 0 || target[b] > DURATION_FRAME_CAP)) throw EngineError(MI355VITS_ERR_INVALID, "target out of range");
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nt = (size_t)B * T, nb = (size_t)B * 4;
+        DevBuf du(nt * 4), dl(nb), dm(nt * 4), dt(nb), duo(nt * 4), dw(nt * 4), dc(nt * 4), dy(nb), dfa(nb), dst(nb);
+        HIP_CHECK(hipMemcpy(du.p, u, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, nb, hipMemcpyHostToDevice));
+        if (min_frames) HIP_CHECK(hipMemcpy(dm.p, min_frames, nt * 4, hipMemcpyHostToDevice));
+        if (target) HIP_CHECK(hipMemcpy(dt.p, target, nb, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dw.p, frames, nt * 4, hipMemcpyHostToDevice));  // the prior contents: a missing write shows
+        HIP_CHECK(hipMemcpy(dc.p, cum, nt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, ylen, nb, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dfa.p, factor, nb, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dst.p, status, nb, hipMemcpyHostToDevice));
+        DurTimedArgs a;
+        a.u_in = du.as<float>();
+        a.len = dl.as<int>(); a.B = B; a.T = T;
+        a.min_frames = min_frames ? dm.as<int>() : nullptr;
+        a.target = target ? dt.as<int>() : nullptr;
+        a.u = duo.as<float>();
+        a.w_ceil = dw.as<int>(); a.cum = dc.as<int>(); a.ylen = dy.as<int>();
+        a.factor = dfa.as<float>(); a.status = dst.as<int>();
+        launch_durations_timed(a, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(frames, dw.p, nt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cum, dc.p, nt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ylen, dy.p, nb, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(factor, dfa.p, nb, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(status, dst.p, nb, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z) {
     return guarded(nullptr, [&] {

@@ -717,6 +717,7 @@ class InferenceSession:
         self._utterances = 0
         self._lock = threading.Lock()
         self.last_lengths: Optional[np.ndarray] = None
+        self.last_timing_factor: Optional[np.ndarray] = None  # of the last timed run_pcm16 (the factor every row was fitted with)
         self._batcher: Optional[_MicroBatcher] = None
         if self._sess_options.micro_batch_window_ms and self._sess_options.micro_batch_window_ms > 0:
             self._batcher = _MicroBatcher(self, self._sess_options.micro_batch_window_ms * 1e-3,
@@ -751,7 +752,8 @@ class InferenceSession:
 
     # ---- engine extensions --------------------------------------------------------------------
     def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
-                  sample_rate: Optional[int] = None, alignment=False):
+                  sample_rate: Optional[int] = None, alignment=False, stretch=None, min_frames=None, target_frames=None,
+                  duration_ms=None):
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -766,25 +768,60 @@ class InferenceSession:
         conversion; not a per-row setting: micro-batched requests of different rates never share an engine call).
         ``alignment`` (``True``, or ``"levels"`` for peak and rms too): also where each phoneme sits in its row
         (``mi355vits_fetch_alignment``) — the call then goes straight to a lane, never through the micro-batcher, fetches the
-        alignment on that lane before releasing it, and returns (rows, lengths, ``_native.Alignment``)."""
+        alignment on that lane before releasing it, and returns (rows, lengths, ``_native.Alignment``).
+        Timing in the same run (``mi355vits_run_timed``): ``stretch`` [B, Tx] multiplies each phoneme's duration, ``min_frames``
+        [B, Tx] holds a phoneme (a pause symbol) at least that many latent frames, ``target_frames`` [B] fits the row to exactly
+        that many latent frames (0 = as predicted), or ``duration_ms`` [B] (0 / ``None`` = as predicted) the same in time:
+        ``max(1, round(ms / 1000 * sample_rate / hop))`` frames at the voice's native rate.  Such a call goes straight to a lane,
+        never through the micro-batcher; the factors it was fitted with are left in ``last_timing_factor``."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
-        if alignment:
+        timing = self._timing_kw(input_feed, stretch, min_frames, target_frames, duration_ms)
+        kw.update(timing)
+        if alignment or timing:
             ids, lengths, sid = self._feed(input_feed)
             keys = kw.pop("utterance_keys", None)
-            out, al = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys, _alignment=_alignment_levels(alignment),
-                                       want_float=False, want_pcm16=True, **kw)
+            out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys,
+                                   _alignment=_alignment_levels(alignment) if alignment else None, want_float=False, want_pcm16=True, **kw)
+            out, al = out if alignment else (out, None)
             self.last_lengths = out["lengths"]
-            return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"], al
+            if timing:
+                self.last_timing_factor = out["timing_factor"]
+            rows = [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])]
+            return (rows, out["lengths"], al) if alignment else (rows, out["lengths"])
         out = self._run(input_feed, _direct=direct, want_float=False, want_pcm16=True, **kw)
         return [out["pcm"][b, : int(out["lengths"][b])] for b in range(out["pcm"].shape[0])], out["lengths"]
+
+    def _timing_kw(self, input_feed, stretch, min_frames, target_frames, duration_ms) -> Dict[str, np.ndarray]:
+        """The timing keywords of ``Engine.run`` / ``run_packed`` (empty without any): ``duration_ms`` [B] becomes
+        ``target_frames`` at the voice's native rate, ``max(1, round(ms / 1000 * sample_rate / hop))``; 0 / None = no target."""
+        kw = {}
+        if stretch is not None:
+            kw["stretch"] = stretch
+        if min_frames is not None:
+            kw["min_frames"] = min_frames
+        if duration_ms is not None:
+            if target_frames is not None:
+                raise ValueError("give target_frames or duration_ms, not both")
+            B = np.asarray(input_feed["input"]).shape[0]
+            ms = np.array([0.0 if m is None else float(m) for m in np.asarray(duration_ms, object).reshape(-1)], np.float64)
+            if ms.shape != (B,):
+                raise ValueError("duration_ms must have shape [batch]")
+            if not np.all(np.isfinite(ms)) or np.any(ms < 0):
+                raise ValueError("duration_ms must be finite and >= 0")
+            per_ms = self.config.sample_rate / 1000.0 / self.config.hop_length
+            target_frames = [0 if m == 0 else max(1, int(round(m * per_ms))) for m in ms]
+        if target_frames is not None:
+            kw["target_frames"] = target_frames
+        return kw
 
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
-                   limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION) -> "_native.PackedAudio":
+                   limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION,
+                   stretch=None, min_frames=None, target_frames=None, duration_ms=None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -819,7 +856,9 @@ class InferenceSession:
         applied — as a complete FLAC file, its frames encoded on the GPU, lossless (``Engine.set_output_compression``):
         ``PackedAudio.flac`` is the file, ``.data`` / ``.rows`` / ``.wav`` are ``None``, ``.offsets`` / ``.lengths`` / ``.peaks`` /
         ``.total_samples`` are those of the uncompressed call.  ``wav=True`` with it raises ``ValueError``; any encoding but
-        "s16le" is refused by the library."""
+        "s16le" is refused by the library.
+        ``stretch`` / ``min_frames`` / ``target_frames`` / ``duration_ms``: timing in the same run, as for ``run_pcm16`` (a timed run
+        that keeps its audio on the device, then the pack: one synchronisation more)."""
         comp = self.output_compression if compression is _SESSION else _compression_name(compression)
         if comp and wav:
             raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
@@ -835,6 +874,7 @@ class InferenceSession:
             lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
         ids, lengths, sid = self._feed(input_feed)
         keys = kw.pop("utterance_keys", None)
+        kw.update(self._timing_kw(input_feed, stretch, min_frames, target_frames, duration_ms))
         if alignment:
             kw["_alignment"] = _alignment_levels(alignment)
         ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
