@@ -16,14 +16,40 @@
 extern "C" {
 #endif
 
-/* Kernel unit-test hook: one Conv1d through a chosen implementation on host buffers.
- * impl: 0 = generic VALU kernel, 1 = fp32-MFMA kernel, 2 = split-bf16 staged kernel (MI355VITS_MATH_BF16X3; needs
- * Cin % 32 == 0 and T > 512), 3 = the text encoder's slice kernel (MI355VITS_MATH_BF16X3; Cin % 192 == 0, K in {1, 3}, dilation
- * 1; Cin > 192: the raw sums of the 192-channel slices added up, no bias / residual), 4 = the 128-channel resblock conv with
- * every input channel resident in LDS (MI355VITS_MATH_BF16X3; Cin = Cout = 128, (K, dilation) in {(3,1), (3,2), (5,2), (5,6),
- * (7,3), (7,12)}, needs res and in_len).  mi355vits_test_conv_transpose1d: impl 0 = generic, 1 = f32-MFMA polyphase, 2 = the
- * staged split-bf16 polyphase kernels, 3 = the resident-input polyphase kernels (256 -> 128 and 128 -> 64 with stride 8 / K 16,
- * 64 -> 32 with stride 4 / K 8).  See tests/test_gpu_parity.py, tests/test_emu_engine.py. */
+/* Kernel unit-test hook: ONE Conv1d ("same" padding, odd or even K) through a chosen implementation on host buffers, with the standard
+ * epilogue of csrc/kernels_conv.cpp (epi_std), in this order:
+ *   v = conv(lrelu_{in_slope}(x * [t < in_len[b]])); v += bias; v += cond[b]; relu; (mask_before_res: v = 0 at t >= out_len[b]);
+ *   v = res + v (res_sub: res - v); v *= out_scale; (not mask_before_res: v = 0 at t >= out_len[b]); accumulate: v += y;  y = v.
+ * The hook packs the weights with the library's own pack functions, as the engine does for the chosen kernel.
+ * impl: 0 = launch_conv1d_generic (k_conv1d_generic: any shape), math MI355VITS_MATH_F32;
+ *       1 = launch_conv1d_mfma in MATH_F32 (k_conv1d_mfma staged, k_conv_direct_mfma, k_conv_direct_splitk — the launcher's rule; even Cin);
+ *       2 = launch_conv1d_mfma on the split-bf16 staged kernel (k_conv1d_b3), math MATH_BF16X3 or MATH_BF16W (the weights count with
+ *           their leading bf16 term only): Cin % 32 == 0 and T > 512, or any T with fixed_rule (the flow's and decoder's convs: the
+ *           kernel follows the layer, never T);
+ *       3 = launch_enc_conv_b3 (k_enc_b3, k_enc_b3w), math MATH_BF16X3 or MATH_BF16W: Cin = 96 or Cin % 192 == 0, K in {1, 3}, dilation 1;
+ *           Cin > 192: the raw sums of the 192-channel slices added up in slice order by the hook — no bias, cond, res, relu, scale,
+ *           out_len or accumulate;
+ *       4 = launch_rb_conv (k_rb_conv, k_rb_conv_pw: every input channel resident in LDS), math MATH_BF16X3: Cin = Cout = 128, (K,
+ *           dilation) in {(3,1), (3,2), (5,2), (5,6), (7,3), (7,12)}; needs res and in_len; no cond, relu, res_sub, mask_before_res, out_len.
+ * fixed_rule (impl 1 and 2 only) = ConvArgs.fixed_rule.  A shape, math mode or option the chosen kernel does not serve is
+ * MI355VITS_ERR_INVALID before any launch.  Which form of an impl runs is the launcher's business: mi355vits_lab_conv_plan reports it.
+ * The caller's y goes to the device first (it is the accumulate source, and a column no kernel writes keeps it).
+ * At and past in_len[b] / out_len[b] (0 <= len <= T; NULL = T), per row:
+ *   x       no kernel uses it at t >= in_len[b], and every one masks by SELECT: impl 0, 1 do not load it there (impl 1's staged form
+ *           does not even with 16-byte loads: a quad that straddles in_len[b] is loaded element by element); impl 2, 3, 4 clamp every
+ *           load to column max(in_len[b] - 1, 0) and discard by select.  Any finite or non-finite bits may lie there.
+ *   y       impl 0 - 3 write every column t < T of every row.  At out_len[b] <= t < T the epilogue above gives, and the kernels
+ *           write: exact zeros without accumulate and without mask_before_res (res is then discarded by select: any bits);
+ *           res * out_scale with mask_before_res (res or res - 0); plus the prior y with accumulate (the prior y and, with
+ *           mask_before_res, res are then READ there and enter by arithmetic).  Without out_len nothing is masked: a column
+ *           in_len[b] <= t < T holds the conv of the zero-extended row (its taps that reach below in_len[b], else bias + cond ...).
+ *           impl 4 never computes an item that starts at or past in_len[b]: it writes up to the end of the item that holds column
+ *           in_len[b] - 1 (item = the plan call's cols) and masks nothing (it has no out_len): at in_len[b] <= t inside that item
+ *           the same epilogue on the zero-extended row — res and, accumulating, the prior y are READ there and enter by arithmetic,
+ *           the consumer masks —, every later column keeps what y held; a row with in_len[b] = 0 is not touched.
+ *   res     impl 0 - 3: discarded by select at t >= out_len[b], except with mask_before_res (above); impl 4: above.
+ *   cond    [B, Cout], one value per row and channel: no padding.
+ * Columns below the lengths depend on nothing at or past them and on no other row. */
 typedef struct mi355vits_conv_test {
     int32_t impl, B, Cin, Cout, T, K, dilation;
     const float* x;       /* [B,Cin,T] */
@@ -36,14 +62,78 @@ typedef struct mi355vits_conv_test {
     int32_t relu;         /* relu on the output */
     float out_scale;
     int32_t res_sub;      /* y = res - conv instead of res + conv */
-    float* y;             /* [B,Cout,T], also the accumulate source when accumulate != 0 */
+    float* y;             /* [B,Cout,T]: its prior contents go to the device first; the accumulate source when accumulate != 0 */
     int32_t accumulate;
+    int32_t math;         /* MI355VITS_MATH_F32 for impl 0 / 1; _BF16X3 or _BF16W for impl 2 / 3; _BF16X3 for impl 4 */
+    const float* cond;    /* [B,Cout] or NULL */
+    int32_t mask_before_res;
+    int32_t fixed_rule;
 } mi355vits_conv_test;
 int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t);
-/* in_len [B] (0 <= in_len[b] <= Tin) or NULL = every row at full length; impl 3 only.  Output positions at or past in_len[b] x stride
- * are left undefined. */
+/* Kernel unit-test hook: ONE ConvTranspose1d (padding (K - stride) / 2) of lrelu_{in_slope}(x): x [B,Cin,Tin], w [Cin,Cout,K], y [B,Cout,
+ * Tin * stride].  impl: 0 = launch_conv_transpose1d (k_conv_transpose1d: any shape), 1 = the polyphase filters (convt_to_polyphase) on
+ * launch_conv1d_mfma in MATH_F32, 2 = on its split-bf16 staged kernels in MATH_BF16X3 (Cin % 32 == 0; 64-channel chunks run the
+ * persistent producer / consumer form), 3 = launch_ups_pl (k_ups_pl: 256 -> 128 and 128 -> 64 with stride 8 / K 16; k_ups64: 64 -> 32
+ * with stride 4 / K 8), MATH_BF16X3.  K >= stride with K - stride even (the output is then exactly Tin * stride samples); anything else,
+ * or a shape the chosen kernel does not serve, is MI355VITS_ERR_INVALID before any launch.
+ * in_len [B] (0 <= in_len[b] <= Tin) or NULL = every row at full length: impl 3 only (anything else: MI355VITS_ERR_INVALID).
+ * The caller's y goes to the device first.  impl 0 - 2 write every output position n < Tin * stride of every row.  impl 3 writes the
+ * positions of the items it computes: at least every n < in_len[b] * stride, computed from x * [t < in_len[b]] (x is not used at or
+ * past in_len[b]: clamped loads, select); positions at or past in_len[b] * stride are left undefined (written or not, by the item
+ * width the plan call reports), and a row with in_len[b] = 0 is not touched. */
 int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Cout, int Tin, int K, int stride,
                                     const float* x, const float* w, const float* bias, float in_slope, const int32_t* in_len, float* y);
+/* What the conv launchers would run for a hook call of this shape on the current device, every base pointer 16-byte aligned as the
+ * hooks' buffers are: stride = 0: mi355vits_test_conv1d(impl) on [B,Cin,T]; stride > 0: mi355vits_test_conv_transpose1d(impl) with
+ * Tin = T (dilation ignored).  has_res / has_cond: whether the call passes res / cond (they enter the choice of the epilogue path and
+ * of the encoder kernel's wide form); len = in_len [B] or NULL (the persistent kernels size their grid by the rows' items).
+ * The launchers' own functions (with the lab switches where they are read).  Host arithmetic only: no kernel runs.
+ * MI355VITS_ERR_INVALID where the hook would refuse the call. */
+enum {
+    MI355VITS_CONVK_GENERIC = 0, MI355VITS_CONVK_F32_STAGED = 1, MI355VITS_CONVK_F32_DIRECT = 2, MI355VITS_CONVK_F32_SPLITK = 3,
+    MI355VITS_CONVK_B3_STAGED32 = 4, MI355VITS_CONVK_B3_STAGED64 = 5, MI355VITS_CONVK_B3_PC = 6, MI355VITS_CONVK_ENC_B3 = 7,
+    MI355VITS_CONVK_ENC_B3W8 = 8, MI355VITS_CONVK_ENC_B3W6 = 9, MI355VITS_CONVK_RB_CONV = 10, MI355VITS_CONVK_RB_CONV_PW = 11,
+    MI355VITS_CONVK_UPS_PL = 12, MI355VITS_CONVK_UPS64 = 13, MI355VITS_CONVK_CONVT_GENERIC = 14
+};
+typedef struct mi355vits_conv_plan {
+    int32_t kernel;          /* MI355VITS_CONVK_* */
+    int32_t cols, rows;      /* a work item: conv positions (transposed: input positions; the generic transposed kernel: output samples) x output rows */
+    int32_t MT, NT, WM, WN;  /* tile shape of the staged / direct MFMA kernels; 0 where the kernel has one shape */
+    int32_t chunk;           /* input channels staged at a time (0: none) */
+    int32_t ring;            /* k_conv1d_mfma: 32 = 64-channel chunks (a tap's pairs unrolled), 0 = ring pipeline, -1 = plain loop */
+    int32_t rb_loop;         /* k_enc_b3 / k_enc_b3w: row blocks per workgroup */
+    int32_t vec, yvec, ovec; /* 16-byte staging loads / vector stores / the row-major epilogue through LDS */
+    int32_t grid[3];         /* persistent kernels: grid[0] workgroups */
+    int32_t lds_bytes;
+} mi355vits_conv_plan;
+int mi355vits_lab_conv_plan(int impl, int B, int Cin, int Cout, int T, int K, int dilation, int stride, int math, int fixed_rule,
+                            int has_res, int has_cond, const int32_t* len, mi355vits_conv_plan* out);
+/* Kernel unit-test hook: launch_enc_o_ln (k_enc_o_ln) alone, the attention block's tail of the text encoder:
+ *   y = LN_c(res + conv1x1(x * [t < in_len[b]]) + bias) * [t < ln_out_len[b]],  192 -> 192 channels, LayerNorm over the channels with
+ * gamma / beta [192] and eps, math MI355VITS_MATH_BF16X3 or _BF16W.  x, res [B,192,T]; in_len, ln_out_len [B] or NULL.  in_place = 0:
+ * y is a buffer of its own (the caller's y goes to the device first); in_place != 0: the kernel runs with y == res on the device (y's
+ * prior contents are not used) and the result is returned in y.  Anything else than 192 channels or these math modes:
+ * MI355VITS_ERR_INVALID.  At and past the lengths: x is not used at t >= in_len[b] (clamped loads, select); res IS read at every
+ * t < T (it enters the statistics of its own column only) and discarded by select at t >= ln_out_len[b]: any bits; y is written at
+ * every t < T, exact zeros at t >= ln_out_len[b]. */
+int mi355vits_test_enc_o_ln(int device, int math, int B, int T, const float* x, const float* w, const float* bias, const float* res,
+                            const float* gamma, const float* beta, float eps, const int32_t* in_len, const int32_t* ln_out_len,
+                            int in_place, float* y);
+/* Kernel unit-test hook: the decoder's tail, launch_conv_post_tanh then launch_pcm16, on host buffers:
+ *   audio[b, t] = tanh(sum_{c,k} w[c, k] * lrelu_0.01(x[b, c, t - (K - 1) / 2 + k] * [. < valid_len[b]])),  no bias, K odd;
+ *   peaks[b] = max_{t < valid_len[b]} |audio[b, t]| (0 for an empty row);
+ *   pcm[b, t] = audio_float_to_int16 of the row with its own peak (scale 32767 / max(0.01, peak), clip, truncate), then audioop.mul by
+ *   volumes[b] when volumes is given and != 1 (double product, clip, floor); 0 at t >= valid_len[b].
+ * x [B,Cin,L], w [1,Cin,K], valid_len [B] (0 <= valid_len[b] <= L), volumes [B] doubles or NULL.  audio [B,L], peaks [B], pcm [B,L]:
+ * their prior contents go to the device first (peaks is then zeroed, as the engine does before the launch).  *kernel (or NULL) = the
+ * kernel launch_conv_post_tanh picked: 0 = k_conv_post_tanh_dpp (K = 7, Cin % 4 == 0, L % 4 == 0), 1 = k_conv_post_tanh_vec (odd K <= 9,
+ * L % 4 == 0), 2 = k_conv_post_tanh (any); in the lab build and the CPU model MI355VITS_CONV_POST_V1 takes the first away,
+ * MI355VITS_CONV_POST_STAGED the first two.  All three give the same bits.
+ * At and past valid_len[b]: x is not used (select; the dpp kernel switches whole 16-byte loads off); audio is written at every
+ * t < L — the conv of the zero-extended row: non-zero within (K - 1) / 2 samples of valid_len[b], exact zeros behind; pcm is written
+ * at every t < L, zero there. */
+int mi355vits_test_conv_post(int device, int B, int Cin, int K, int L, const float* x, const float* w, const int32_t* valid_len,
+                             const double* volumes, float* audio, float* peaks, int16_t* pcm, int32_t* kernel);
 /* Test hook: fills the whole capacity of the handle's two workspace arenas with a 32-bit pattern (on the engine stream, then
  * synchronises).  A later run on the same handle that does not outgrow the workspace finds the pattern in every column it does
  * not write: the columns past a row's end must reach no valid sample (consumers mask by select, never by multiply). */

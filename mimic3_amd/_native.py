@@ -57,6 +57,7 @@ LAB_SYMBOLS = (
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
     "mi355vits_test_fit_durations",
+    "mi355vits_lab_conv_plan", "mi355vits_test_enc_o_ln", "mi355vits_test_conv_post",
 )
 
 
@@ -413,7 +414,24 @@ class ConvTest(ctypes.Structure):
         ("in_len", ctypes.POINTER(ctypes.c_int32)), ("out_len", ctypes.POINTER(ctypes.c_int32)),
         ("in_slope", ctypes.c_float), ("relu", ctypes.c_int32), ("out_scale", ctypes.c_float),
         ("res_sub", ctypes.c_int32), ("y", ctypes.POINTER(ctypes.c_float)), ("accumulate", ctypes.c_int32),
+        ("math", ctypes.c_int32), ("cond", ctypes.POINTER(ctypes.c_float)), ("mask_before_res", ctypes.c_int32),
+        ("fixed_rule", ctypes.c_int32),
     ]
+
+
+class ConvPlan(ctypes.Structure):
+    """include/mi355vits_lab.h: mi355vits_conv_plan."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kernel", "cols", "rows", "MT", "NT", "WM", "WN", "chunk", "ring", "rb_loop", "vec", "yvec",
+                                                "ovec")] + [("grid", ctypes.c_int32 * 3), ("lds_bytes", ctypes.c_int32)]
+
+    @property
+    def tile(self):
+        return (self.MT, self.NT, self.WM, self.WN)
+
+
+# mi355vits_conv_plan.kernel (MI355VITS_CONVK_*)
+(CONVK_GENERIC, CONVK_F32_STAGED, CONVK_F32_DIRECT, CONVK_F32_SPLITK, CONVK_B3_STAGED32, CONVK_B3_STAGED64, CONVK_B3_PC, CONVK_ENC_B3,
+ CONVK_ENC_B3W8, CONVK_ENC_B3W6, CONVK_RB_CONV, CONVK_RB_CONV_PW, CONVK_UPS_PL, CONVK_UPS64, CONVK_CONVT_GENERIC) = range(15)
 
 
 def _fptr(a: Optional[np.ndarray]):
@@ -561,6 +579,10 @@ class NativeLibrary:
             L.mi355vits_lab_wn_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p]
             L.mi355vits_test_mrf_stage.argtypes = [ctypes.c_int, ctypes.POINTER(MrfTest)]
             L.mi355vits_lab_mrf_plan.argtypes = [ctypes.c_int] * 3 + [i32p] * 7
+            L.mi355vits_lab_conv_plan.argtypes = [ctypes.c_int] * 12 + [i32p, ctypes.POINTER(ConvPlan)]
+            L.mi355vits_test_enc_o_ln.argtypes = [ctypes.c_int] * 4 + [f32p] * 6 + [ctypes.c_float, i32p, i32p, ctypes.c_int, f32p]
+            L.mi355vits_test_conv_post.argtypes = [ctypes.c_int] * 5 + [f32p, f32p, i32p, ctypes.POINTER(ctypes.c_double), f32p, f32p,
+                                                   ctypes.POINTER(ctypes.c_int16), i32p]
             L.mi355vits_test_dds_stack.argtypes = [ctypes.c_int, ctypes.POINTER(DdsStackTest)]
             L.mi355vits_test_spline_inverse.argtypes = [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, f32p, i32p, f32p]
             L.mi355vits_test_fit_durations.argtypes = [ctypes.c_int] * 3 + [f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p]
@@ -746,37 +768,48 @@ class NativeLibrary:
         return int(s.value), int(w.value), int(k.value)
 
     def test_conv1d(self, x, w, bias=None, res=None, dilation=1, impl=1, in_len=None, out_len=None, in_slope=1.0,
-                    relu=False, out_scale=1.0, res_sub=False, accumulate_into=None, device=0) -> np.ndarray:
+                    relu=False, out_scale=1.0, res_sub=False, accumulate_into=None, device=0, math=None, cond=None,
+                    mask_before_res=False, fixed_rule=False, y_prior=None) -> np.ndarray:
+        """One Conv1d through one kernel family (include/mi355vits_lab.h: mi355vits_test_conv1d).  math: MATH_F32 for impl 0 / 1,
+        MATH_BF16X3 (the default) or MATH_BF16W for impl 2 / 3, MATH_BF16X3 for impl 4.  cond [B, Cout].  y_prior = what the output
+        buffer holds before the launch (zeros) when not accumulating; accumulate_into = the same buffer AND y += ."""
         self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         B, Cin, T = x.shape
         Cout, _, K = w.shape
-        y = np.zeros((B, Cout, T), np.float32) if accumulate_into is None else np.ascontiguousarray(accumulate_into, np.float32).copy()
+        assert accumulate_into is None or y_prior is None
+        prior = accumulate_into if accumulate_into is not None else y_prior
+        y = np.zeros((B, Cout, T), np.float32) if prior is None else np.ascontiguousarray(prior, np.float32).copy()
+        assert y.shape == (B, Cout, T) and w.shape[1] == Cin
         keep = [x, w, y]
         t = ConvTest()
         t.impl, t.B, t.Cin, t.Cout, t.T, t.K, t.dilation = impl, B, Cin, Cout, T, K, dilation
         t.x, t.w, t.y = _fptr(x), _fptr(w), _fptr(y)
-        for name, arr in (("bias", bias), ("res", res)):
+        for name, arr, shape in (("bias", bias, (Cout,)), ("res", res, (B, Cout, T)), ("cond", cond, (B, Cout))):
             if arr is not None:
                 a = np.ascontiguousarray(arr, np.float32)
+                assert a.shape == shape, (name, a.shape, shape)
                 keep.append(a)
                 setattr(t, name, _fptr(a))
         for name, arr in (("in_len", in_len), ("out_len", out_len)):
             if arr is not None:
                 a = np.ascontiguousarray(arr, np.int32)
+                assert a.shape == (B,)
                 keep.append(a)
                 setattr(t, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
         t.in_slope, t.relu, t.out_scale, t.res_sub = in_slope, int(relu), out_scale, int(res_sub)
         t.accumulate = int(accumulate_into is not None)
+        t.math = (MATH_F32 if impl in (0, 1) else MATH_BF16X3) if math is None else int(math)
+        t.mask_before_res, t.fixed_rule = int(bool(mask_before_res)), int(bool(fixed_rule))
         rc = self.lib.mi355vits_test_conv1d(device, ctypes.byref(t))
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return y
 
-    def test_conv_transpose1d(self, x, w, bias, stride, in_slope=1.0, device=0, impl=0, in_len=None) -> np.ndarray:
+    def test_conv_transpose1d(self, x, w, bias, stride, in_slope=1.0, device=0, impl=0, in_len=None, y_prior=None) -> np.ndarray:
         """in_len [B]: per-row input lengths (impl 3 only; None = every row at full length); output positions at or past
-        in_len[b] x stride are left undefined."""
+        in_len[b] x stride are left undefined.  y_prior = what the output buffer holds before the launch (zeros)."""
         self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
@@ -784,13 +817,71 @@ class NativeLibrary:
         _, Cout, K = w.shape
         b = None if bias is None else np.ascontiguousarray(bias, np.float32)
         ln = None if in_len is None else np.ascontiguousarray(in_len, np.int32)
-        y = np.zeros((B, Cout, Tin * stride), np.float32)
+        y = np.zeros((B, Cout, Tin * stride), np.float32) if y_prior is None else np.ascontiguousarray(y_prior, np.float32).copy()
+        assert y.shape == (B, Cout, Tin * stride)
         rc = self.lib.mi355vits_test_conv_transpose1d(device, impl, B, Cin, Cout, Tin, K, stride, _fptr(x), _fptr(w),
                                                       _fptr(b), in_slope,
                                                       None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(y))
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return y
+
+    def lab_conv_plan(self, impl, B, Cin, Cout, T, K, dilation=1, stride=0, math=None, fixed_rule=False, has_res=False, has_cond=False,
+                      lengths=None) -> "ConvPlan":
+        """What the conv launchers would run for a hook call of this shape on the current device (include/mi355vits_lab.h:
+        mi355vits_lab_conv_plan): stride = 0: test_conv1d(impl); stride > 0: test_conv_transpose1d(impl) with Tin = T.  No kernel runs."""
+        self._need_hooks()
+        p = ConvPlan()
+        ln = None if lengths is None else np.ascontiguousarray(lengths, np.int32)
+        m = (MATH_F32 if impl in (0, 1) else MATH_BF16X3) if math is None else int(math)
+        rc = self.lib.mi355vits_lab_conv_plan(int(impl), int(B), int(Cin), int(Cout), int(T), int(K), int(dilation), int(stride), m,
+                                              int(bool(fixed_rule)), int(bool(has_res)), int(bool(has_cond)),
+                                              None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return p
+
+    def test_enc_o_ln(self, x, w, bias, res, gamma, beta, in_len=None, ln_out_len=None, eps=1e-5, math=MATH_BF16X3, in_place=False,
+                      y_prior=None, device=0) -> np.ndarray:
+        """launch_enc_o_ln alone (include/mi355vits_lab.h: mi355vits_test_enc_o_ln): y = LN_c(res + conv1x1(x * mask_in) + bias) *
+        mask_ln on [B, 192, T]; in_place: the kernel runs with y == res."""
+        self._need_hooks()
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        x, w, bias, res, gamma, beta = f(x), f(w), f(bias), f(res), f(gamma), f(beta)
+        B, C, T = x.shape
+        assert C == 192 and res.shape == x.shape and w.shape == (C, C, 1) and gamma.shape == beta.shape == (C,)
+        y = np.zeros_like(x) if y_prior is None else f(y_prior).copy()
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+        il, ol = i32(in_len), i32(ln_out_len)
+        ip = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        rc = self.lib.mi355vits_test_enc_o_ln(device, int(math), B, T, _fptr(x), _fptr(w), _fptr(bias), _fptr(res), _fptr(gamma), _fptr(beta),
+                                              float(eps), ip(il), ip(ol), int(bool(in_place)), _fptr(y))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return y
+
+    def test_conv_post(self, x, w, valid_len, volumes=None, audio_prior=None, pcm_prior=None, device=0):
+        """The decoder's tail, launch_conv_post_tanh then launch_pcm16 (include/mi355vits_lab.h: mi355vits_test_conv_post): x [B, Cin, L],
+        w [1, Cin, K] -> (audio [B, L] float32, peaks [B] float32, pcm [B, L] int16, the kernel that ran: 0 dpp, 1 vec, 2 staged)."""
+        self._need_hooks()
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float32)
+        B, Cin, L = x.shape
+        assert w.shape[:2] == (1, Cin)
+        K = w.shape[2]
+        vl = np.ascontiguousarray(valid_len, np.int32)
+        assert vl.shape == (B,)
+        vol = None if volumes is None else np.ascontiguousarray(volumes, np.float64)
+        audio = np.zeros((B, L), np.float32) if audio_prior is None else np.ascontiguousarray(audio_prior, np.float32).copy()
+        pcm = np.zeros((B, L), np.int16) if pcm_prior is None else np.ascontiguousarray(pcm_prior, np.int16).copy()
+        peaks = np.full(B, -1.0, np.float32)
+        kernel = ctypes.c_int32(-1)
+        rc = self.lib.mi355vits_test_conv_post(device, B, Cin, K, L, _fptr(x), _fptr(w), vl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               None if vol is None else vol.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _fptr(audio),
+                                               _fptr(peaks), pcm.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(kernel))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return audio, peaks, pcm, int(kernel.value)
 
     def emu_set_cu_count(self, n: int) -> None:
         """The compute units the CPU model reports to the grid sizing of every launch after this call (default 8; n < 1 restores it).

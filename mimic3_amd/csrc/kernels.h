@@ -56,6 +56,44 @@ struct ConvArgs {
     int item_order = 0;  // kernels_rbc.cpp (set by its launchers): 1 = the persistent workgroups walk their items XCD-major where the grid allows it (items.h)
 };
 
+// What a conv launcher runs for its arguments on the current device: the launchers' whole choice as a pure function (host arithmetic,
+// with the lab switches where they are read — at every call).  Each launcher below launches what its plan function returns and keeps
+// no rule of its own; mi355vits_lab_conv_plan (include/mi355vits_lab.h) reports the same values to the tests.
+enum ConvKernelForm {
+    CONVK_GENERIC = 0,        // k_conv1d_generic
+    CONVK_F32_STAGED = 1,     // k_conv1d_mfma (LDS-staged input chunks)
+    CONVK_F32_DIRECT = 2,     // k_conv_direct_mfma
+    CONVK_F32_SPLITK = 3,     // k_conv_direct_splitk
+    CONVK_B3_STAGED32 = 4,    // k_conv1d_b3, 32-channel chunks
+    CONVK_B3_STAGED64 = 5,    // k_conv1d_b3, 64-channel chunks (K <= 2)
+    CONVK_B3_PC = 6,          // k_conv1d_b3_pc (persistent producer / consumer form, 64-channel chunks)
+    CONVK_ENC_B3 = 7,         // k_enc_b3
+    CONVK_ENC_B3W8 = 8,       // k_enc_b3w, row blocks of eight 32-row tiles
+    CONVK_ENC_B3W6 = 9,       // k_enc_b3w, row blocks of six
+    CONVK_RB_CONV = 10,       // k_rb_conv (32-column items)
+    CONVK_RB_CONV_PW = 11,    // k_rb_conv_pw (128-column items)
+    CONVK_UPS_PL = 12,        // k_ups_pl
+    CONVK_UPS64 = 13,         // k_ups64
+    CONVK_CONVT_GENERIC = 14  // k_conv_transpose1d
+};
+struct ConvPlan {
+    int kernel = CONVK_GENERIC;
+    int MT = 0, NT = 0, WM = 0, WN = 0;  // tile shape of the staged / direct MFMA kernels (0: the kernel has one fixed shape)
+    int cols = 0, rows = 0;              // a work item: columns (output positions of the conv) x output rows
+    int chunk = 0;                       // input channels staged at a time (0: not staged by chunks)
+    int ring = 0;                        // k_conv1d_mfma's weight ring: 32 = a 64-channel chunk's pairs unrolled, 0 = ring, -1 = plain loop
+    int rb_loop = 0;                     // k_enc_b3 / k_enc_b3w: row blocks a workgroup walks over one staged slice
+    int vec = 0, yvec = 0, ovec = 0;     // ConvArgs.vec / yvec / ovec as the launcher sets them
+    unsigned gx = 0, gy = 0, gz = 0;     // the grid (persistent kernels: gx workgroups, 0 = nothing to do)
+    size_t shmem = 0;                    // dynamic LDS bytes
+    int nvalid = 0, item_order = 0;      // kernels_rbc.cpp: ConvArgs.nvalid / item_order as the launcher sets them (items.h)
+};
+ConvPlan conv1d_generic_plan(const ConvArgs& a);
+ConvPlan conv1d_mfma_plan(const ConvArgs& a);    // throws std::runtime_error where launch_conv1d_mfma would
+ConvPlan enc_conv_b3_plan(const ConvArgs& a);    // a.ksplit set; the launcher checks the shape
+ConvPlan rb_conv_plan(const ConvArgs& a);        // kernel, cols, rows; gx from a.in_len_host (null: the lengths are read back)
+ConvPlan ups_pl_plan(const ConvArgs& a);
+
 // Short-sequence dense conv of the text encoder (q/k/v, o, FFN: T = phonemes) in MATH_BF16X3 / BF16W: 64 x 64 output tiles, a
 // 192-channel slice of the input staged ONCE per workgroup as three bf16 planes (k_enc_b3, kernels_conv.cpp).  Cin % 192 == 0
 // (or Cin = 96: the pointwise conv in front of a coupling layer's WaveNet), K in {1, 3}, dil 1, EPI_STD, wb3 = layout-1 planes.
@@ -111,6 +149,7 @@ struct ConvTArgs {
     float in_slope = 1.0f;
 };
 void launch_conv_transpose1d(const ConvTArgs& a, hipStream_t s);
+ConvPlan conv_transpose1d_plan(const ConvTArgs& a);  // k_conv_transpose1d's tile (cols = output samples), grid and LDS
 // Polyphase repack: ConvTranspose1d weight [Cin,Cout,K] (+bias [Cout]) -> Conv1d weight
 // [stride*Cout, Cin, taps] (+bias [stride*Cout]) with taps = ceil(K/stride); see ConvArgs::shuf_*.
 int convt_taps(int K, int stride);
@@ -224,6 +263,9 @@ int wn_layer_geometry(const WnArgs& a);
 // mask = t < valid_len[b]: every row of a batch is synthesised as if it were alone (zero padding at its own end).
 void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, int Cin, int K, int B, int L,
                            const int* valid_len, float* audio, long audio_bs, unsigned* peak_bits, hipStream_t s);
+// which kernel the launcher above runs (with the lab switches, read at every call): 0 = k_conv_post_tanh_dpp, 1 = k_conv_post_tanh_vec,
+// 2 = k_conv_post_tanh.  All three give the same bits.
+int conv_post_kernel(const float* x, long x_bs, int x_ld, int Cin, int K, const float* audio, long audio_bs);
 // audio_float_to_int16 per utterance (utils.py:237-244) from the peaks found above.
 // volumes [B] (device; NULL = 1 for every row): a row's volume != 1 is followed by audioop.mul(pcm, 2, volume) (tts.py:542-543):
 // sample * volume in double, clipped to [-32768, 32767], rounded toward minus infinity.

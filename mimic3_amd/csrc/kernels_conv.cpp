@@ -436,13 +436,24 @@ __global__ __launch_bounds__(256) void k_conv1d_generic(ConvArgs a) {
     }
 }
 
+ConvPlan conv1d_generic_plan(const ConvArgs& a) {
+    ConvPlan p;
+    p.kernel = CONVK_GENERIC;
+    p.cols = G_T;
+    p.rows = G_CO;
+    p.chunk = G_CI;
+    const int LD = G_T + (a.K - 1) * a.dil;
+    p.shmem = sizeof(float) * ((size_t)G_CI * LD + (size_t)G_CO * G_CI * a.K);
+    p.gx = (a.T + G_T - 1) / G_T;
+    p.gy = (a.epi == EPI_GATE) ? (a.H + 15) / 16 : (a.Cout + G_CO - 1) / G_CO;
+    p.gz = a.B;
+    return p;
+}
+
 void launch_conv1d_generic(const ConvArgs& a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
-    const int LD = G_T + (a.K - 1) * a.dil;
-    const size_t shmem = sizeof(float) * ((size_t)G_CI * LD + (size_t)G_CO * G_CI * a.K);
-    const int ny = (a.epi == EPI_GATE) ? (a.H + 15) / 16 : (a.Cout + G_CO - 1) / G_CO;
-    dim3 grid((a.T + G_T - 1) / G_T, ny, a.B);
-    LAUNCH_KERNEL(k_conv1d_generic, grid, dim3(256), shmem, s, a);
+    const ConvPlan p = conv1d_generic_plan(a);
+    LAUNCH_KERNEL(k_conv1d_generic, dim3(p.gx, p.gy, p.gz), dim3(256), p.shmem, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1577,18 +1588,12 @@ bool enc_conv_b3_supported(int Cin, int Cout, int K, int dil) {
 }
 int enc_conv_b3_slices(int Cin) { return Cin >= ENC_CS ? Cin / ENC_CS : 1; }
 
-void launch_enc_conv_b3(const ConvArgs& a_in, hipStream_t s) {
-    if (a_in.T <= 0 || a_in.B <= 0) return;
-    ConvArgs a = a_in;
-    if (!enc_conv_b3_supported(a.Cin, a.Cout, a.K, a.dil) || a.epi != EPI_STD || !a.wb3 || a.shuf_s || a.Tin >= 0)
-        throw std::runtime_error("enc_conv_b3: unsupported conv");
-    if (a.ksplit != enc_conv_b3_slices(a.Cin)) throw std::runtime_error("enc_conv_b3: one workgroup per 192-channel slice");
+// large grids: the 128-column form (k_enc_b3w) when it still gives every CU a workgroup: one staged slice per 128 columns, every
+// row tile's fragments streamed by ONE wave and used for four column tiles; all of the conv's row blocks in one workgroup.
+// Otherwise, on grids that are still large: several 64-row blocks per workgroup over one staged slice (k_enc_b3, rb_loop > 1).
+ConvPlan enc_conv_b3_plan(const ConvArgs& a) {
+    ConvPlan p;
     const int ng = a.Cin >= ENC_CS ? ENC_NG : ENC_NG / 2;
-    if (a.ksplit > 1 && !a.part) throw std::runtime_error("enc_conv_b3: split conv without a partial-sum buffer");
-    static const int ablate = lab_getenv("MI355VITS_CONV_ABLATE") ? atoi(lab_getenv("MI355VITS_CONV_ABLATE")) : 0;
-    a.ablate = ablate;
-    // large grids: the 128-column form (k_enc_b3w) when it still gives every CU a workgroup: one staged slice per 128 columns, every
-    // row tile's fragments streamed by ONE wave and used for four column tiles; all of the conv's row blocks in one workgroup
     {
         constexpr int NCT = 4;
         const int nrt = (a.Cout + 31) / 32;
@@ -1600,50 +1605,82 @@ void launch_enc_conv_b3(const ConvArgs& a_in, hipStream_t s) {
         bool wide = wgs_w >= current_device_cu_count() && a.Cout % 32 == 0 && !a.cond && nrt >= 6;
         if (const char* f = lab_getenv("MI355VITS_ENC_WIDE")) wide = atoi(f) != 0 && a.Cout % 32 == 0 && !a.cond && (nrt >= 6 || atoi(f) > 1);  // lab / tests (2: also below six row tiles)
         if (wide) {
-            a.rb_loop = nblk;
+            p.kernel = nw == 8 ? CONVK_ENC_B3W8 : CONVK_ENC_B3W6;  // row blocks of six tiles (nw == 6): dealt to the eight waves (SIX)
+            p.cols = 32 * NCT;
+            p.rows = 32 * nw;
+            p.chunk = 16 * ng;
+            p.rb_loop = nblk;
             const int LDw = 32 * NCT + (a.K - 1) * a.dil;
-            const size_t shw = (size_t)3 * ng * 2 * LDw * 16;
-            dim3 gridw((a.T + 32 * NCT - 1) / (32 * NCT), 1, a.B * a.ksplit);
-            auto gow = [&](auto kfn) {
-#ifndef MI355_EMU
-                set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
-#endif
-                LAUNCH_KERNEL(kfn, gridw, dim3(512), shw, s, a);
-            };
-            const bool w1 = a.math == MATH_BF16W;
-            // row blocks of six tiles (nw == 6): dealt to the eight waves (SIX)
-            if (ng == ENC_NG) {
-                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT>); else gow(k_enc_b3w<false, ENC_NG, NCT>); }
-                else { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, true>); else gow(k_enc_b3w<false, ENC_NG, NCT, true>); }
-            } else {
-                if (nw == 8) { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT>); }
-                else { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, true>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, true>); }
-            }
-            return;
+            p.shmem = (size_t)3 * ng * 2 * LDw * 16;
+            p.gx = (a.T + 32 * NCT - 1) / (32 * NCT);
+            p.gy = 1;
+            p.gz = a.B * a.ksplit;
+            return p;
         }
     }
     const int LD = ENC_TB + (a.K - 1) * a.dil;
-    const size_t shmem = (size_t)3 * ng * 2 * LD * 16;
-    // otherwise, on grids that are still large: several 64-row blocks per workgroup over one staged slice — the most that divides the conv's row blocks and still
-    // leaves the launch four workgroups per CU (batch 256: FFN conv_1 six of twelve, q/k/v and conv_2 three; profiles/r06_enc_row_loop_ab.txt)
+    p.kernel = CONVK_ENC_B3;
+    p.cols = ENC_TB;
+    p.rows = 64;
+    p.chunk = 16 * ng;
+    p.shmem = (size_t)3 * ng * 2 * LD * 16;
+    // the most row blocks per workgroup that divides the conv's row blocks and still leaves the launch four workgroups per CU
+    // (batch 256: FFN conv_1 six of twelve, q/k/v and conv_2 three; profiles/r06_enc_row_loop_ab.txt)
     const int nrb = (a.Cout + 63) / 64;
     const long wgs = (long)((a.T + ENC_TB - 1) / ENC_TB) * nrb * a.B * a.ksplit;
-    a.rb_loop = 1;
+    p.rb_loop = 1;
     for (int r : {6, 4, 3, 2})
-        if (nrb % r == 0 && wgs / r >= 4L * current_device_cu_count()) { a.rb_loop = r; break; }
-    if (const char* f = lab_getenv("MI355VITS_ENC_ROWLOOP")) a.rb_loop = atoi(f) > 1 && nrb % atoi(f) == 0 ? atoi(f) : 1;  // lab / tests
-    dim3 grid((a.T + ENC_TB - 1) / ENC_TB, (nrb + a.rb_loop - 1) / a.rb_loop, a.B * a.ksplit);
+        if (nrb % r == 0 && wgs / r >= 4L * current_device_cu_count()) { p.rb_loop = r; break; }
+    if (const char* f = lab_getenv("MI355VITS_ENC_ROWLOOP")) p.rb_loop = atoi(f) > 1 && nrb % atoi(f) == 0 ? atoi(f) : 1;  // lab / tests
+    p.gx = (a.T + ENC_TB - 1) / ENC_TB;
+    p.gy = (nrb + p.rb_loop - 1) / p.rb_loop;
+    p.gz = a.B * a.ksplit;
+    return p;
+}
+
+void launch_enc_conv_b3(const ConvArgs& a_in, hipStream_t s) {
+    if (a_in.T <= 0 || a_in.B <= 0) return;
+    ConvArgs a = a_in;
+    if (!enc_conv_b3_supported(a.Cin, a.Cout, a.K, a.dil) || a.epi != EPI_STD || !a.wb3 || a.shuf_s || a.Tin >= 0)
+        throw std::runtime_error("enc_conv_b3: unsupported conv");
+    if (a.ksplit != enc_conv_b3_slices(a.Cin)) throw std::runtime_error("enc_conv_b3: one workgroup per 192-channel slice");
+    const int ng = a.Cin >= ENC_CS ? ENC_NG : ENC_NG / 2;
+    if (a.ksplit > 1 && !a.part) throw std::runtime_error("enc_conv_b3: split conv without a partial-sum buffer");
+    static const int ablate = lab_getenv("MI355VITS_CONV_ABLATE") ? atoi(lab_getenv("MI355VITS_CONV_ABLATE")) : 0;
+    a.ablate = ablate;
+    const ConvPlan p = enc_conv_b3_plan(a);
+    a.rb_loop = p.rb_loop;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    const bool w1 = a.math == MATH_BF16W;
+    if (p.kernel != CONVK_ENC_B3) {
+        constexpr int NCT = 4;
+        auto gow = [&](auto kfn) {
+#ifndef MI355_EMU
+            set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
+#endif
+            LAUNCH_KERNEL(kfn, grid, dim3(512), p.shmem, s, a);
+        };
+        const bool eight = p.kernel == CONVK_ENC_B3W8;
+        if (ng == ENC_NG) {
+            if (eight) { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT>); else gow(k_enc_b3w<false, ENC_NG, NCT>); }
+            else { if (w1) gow(k_enc_b3w<true, ENC_NG, NCT, true>); else gow(k_enc_b3w<false, ENC_NG, NCT, true>); }
+        } else {
+            if (eight) { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT>); }
+            else { if (w1) gow(k_enc_b3w<true, ENC_NG / 2, NCT, true>); else gow(k_enc_b3w<false, ENC_NG / 2, NCT, true>); }
+        }
+        return;
+    }
     auto go = [&](auto kfn) {
 #ifndef MI355_EMU
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
 #endif
-        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, a);
+        LAUNCH_KERNEL(kfn, grid, dim3(256), p.shmem, s, a);
     };
     if (ng == ENC_NG) {
-        if (a.math == MATH_BF16W) go(k_enc_b3<true, ENC_NG>);
+        if (w1) go(k_enc_b3<true, ENC_NG>);
         else go(k_enc_b3<false, ENC_NG>);
     } else {
-        if (a.math == MATH_BF16W) go(k_enc_b3<true, ENC_NG / 2>);
+        if (w1) go(k_enc_b3<true, ENC_NG / 2>);
         else go(k_enc_b3<false, ENC_NG / 2>);
     }
 }
@@ -1652,100 +1689,126 @@ namespace {
 
 struct TileCfg { int MT, NT, WM, WN; };
 
-template <int MT, int NT, int WM, int WN, int EPI>
-void launch_cfg(const ConvArgs& a, int n_tiles, hipStream_t s) {
-    constexpr int T_B = 32 * NT * WN;
+inline bool rows_16b(const float* ptr, long bs, int ld) { return (ld % 4 == 0) && (bs % 4 == 0) && (reinterpret_cast<uintptr_t>(ptr) % 16 == 0); }
+
+inline void plan_tile(const ConvArgs& a, int n_tiles, const TileCfg& c, ConvPlan& p) {
+    p.MT = c.MT; p.NT = c.NT; p.WM = c.WM; p.WN = c.WN;
+    p.cols = 32 * c.NT * c.WN;
+    p.rows = 32 * c.MT * c.WM;
+    p.gx = (a.T + p.cols - 1) / p.cols;
+    p.gy = (n_tiles + c.MT * c.WM - 1) / (c.MT * c.WM);
+    p.gz = a.B;
+}
+
+// the staged f32 kernel (k_conv1d_mfma) on the tile already in p
+void plan_cfg(const ConvArgs& a, ConvPlan& p) {
+    const int T_B = p.cols;
     const int LD = (T_B + (a.K - 1) * a.dil + 3 + 3) & ~3;
     // C_in chunk: fixed by C_in alone (largest even divisor <= 64) so that the summation order — and with it
     // every output bit — does not depend on the tile shape chosen for a batch size; only a receptive field too
     // large for LDS shrinks it further.
-    static const size_t lds_cap = [] { const char* e = lab_getenv("MI355VITS_CONV_LDS_KB"); return (size_t)(e ? atoi(e) : 60) * 1024; }();
+    const char* e_lds = lab_getenv("MI355VITS_CONV_LDS_KB");  // (the lab switches: read at every launch, tests flip them inside one process)
+    const size_t lds_cap = (size_t)(e_lds ? atoi(e_lds) : 60) * 1024;
     auto fits = [&](int c) { return (size_t)c * LD * sizeof(float) <= lds_cap; };
     int ci_c = 0;
-    static const int chunk_max = [] { const char* e = lab_getenv("MI355VITS_CONV_CHUNK"); return e ? atoi(e) : 64; }();
+    const char* e_chunk = lab_getenv("MI355VITS_CONV_CHUNK");
+    const int chunk_max = e_chunk ? atoi(e_chunk) : 64;
     for (int c = chunk_max; c >= 2; c -= 2)
         if (a.Cin % c == 0 && fits(c)) { ci_c = c; break; }
     if (ci_c == 0) throw std::runtime_error("conv1d_mfma: receptive field too large for LDS staging");
-    size_t shmem = (size_t)ci_c * LD * sizeof(float);
-    dim3 grid((a.T + T_B - 1) / T_B, (n_tiles + MT * WM - 1) / (MT * WM), a.B);
-    ConvArgs av = a;
-    av.vec = (a.x_ld % 4 == 0) && (a.x_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.x) % 16 == 0);
-    av.yvec = (a.y_ld % 4 == 0) && (a.y_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.y) % 16 == 0);
+    p.kernel = CONVK_F32_STAGED;
+    p.chunk = ci_c;
+    p.ring = ci_c == 64 ? 32 : ((((ci_c >> 1) & 7) == 0) ? 0 : -1);
+    p.shmem = (size_t)ci_c * LD * sizeof(float);
+    p.vec = rows_16b(a.x, a.x_bs, a.x_ld);
+    p.yvec = rows_16b(a.y, a.y_bs, a.y_ld);
     // row-major epilogue through LDS (EPI_STD): needs 16-byte aligned output / residual rows; for the polyphase
     // scatter also a phase count that divides the 32-row tile and keeps a lane's 4 rows inside one channel
-    static const bool no_ovec = lab_getenv("MI355VITS_CONV_NO_OVEC") != nullptr;
+    const bool no_ovec = lab_getenv("MI355VITS_CONV_NO_OVEC") != nullptr;
     // the polyphase scatter straight from registers already writes 1 KiB contiguous per store instruction (a lane owns
     // 4 consecutive samples); routing it through LDS measured slower (upsample 1.91 -> 2.34 ms/step), so it is opt-in
-    static const bool polyphase_via_lds = lab_getenv("MI355VITS_CONV_POLY_LDS") != nullptr;
-    av.ovec = EPI == EPI_STD && !no_ovec && av.yvec &&
-              (!a.res || ((a.res_ld % 4 == 0) && (a.res_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.res) % 16 == 0))) &&
-              (!a.shuf_s || (polyphase_via_lds && 32 % a.shuf_s == 0 && a.shuf_s % 4 == 0 && a.Cout % 4 == 0));
-    if (av.ovec) {
+    const bool polyphase_via_lds = lab_getenv("MI355VITS_CONV_POLY_LDS") != nullptr;
+    p.ovec = a.epi == EPI_STD && !no_ovec && p.yvec && (!a.res || rows_16b(a.res, a.res_bs, a.res_ld)) &&
+             (!a.shuf_s || (polyphase_via_lds && 32 % a.shuf_s == 0 && a.shuf_s % 4 == 0 && a.Cout % 4 == 0));
+    if (p.ovec) {
         const size_t s_ = a.shuf_s ? a.shuf_s : 1;
-        const size_t need = (32 * WM / s_) * (T_B * s_ + 4) * sizeof(float);
-        if (need > shmem) shmem = need;
-    }
-    if (ci_c == 64) {
-        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, 32>;
-        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, av, ci_c);
-    } else if (((ci_c >> 1) & 7) == 0) {
-        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, 0>;
-        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, av, ci_c);
-    } else {
-        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, -1>;
-        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, av, ci_c);
+        const size_t need = (32 * p.WM / s_) * (T_B * s_ + 4) * sizeof(float);
+        if (need > p.shmem) p.shmem = need;
     }
 }
 
-// split-bf16 staged kernel: 32-channel chunks (two 16-channel groups: 6 * 32 * LD bytes of LDS); convs with one or two taps
-// (the polyphase upsamplers) take 64-channel chunks when C_in allows — with so few taps a 32-channel chunk is only 72 - 144
-// MFMAs per wave between two stage / barrier cycles.  The chunk size is a function of the layer alone (never of the batch),
-// so the summation order of an output does not depend on what it is batched with.
-template <int MT, int NT, int WM, int WN, int EPI>
-void launch_b3(const ConvArgs& a, int n_tiles, hipStream_t s) {
-    constexpr int T_B = 32 * NT * WN;
+// split-bf16 staged kernel on the tile already in p: 32-channel chunks (two 16-channel groups: 6 * 32 * LD bytes of LDS); convs
+// with one or two taps (the polyphase upsamplers) take 64-channel chunks when C_in allows — with so few taps a 32-channel chunk is
+// only 72 - 144 MFMAs per wave between two stage / barrier cycles.  The chunk size is a function of the layer alone (never of the
+// batch), so the summation order of an output does not depend on what it is batched with.
+void plan_b3(const ConvArgs& a, ConvPlan& p) {
+    const int T_B = p.cols;
     const int LD = (T_B + (a.K - 1) * a.dil + 3 + 3) & ~3;
-    const bool wide = a.K <= 2 && a.Cin % 64 == 0 && EPI == EPI_STD;
-    size_t shmem = (size_t)6 * (wide ? 64 : 32) * LD;
-    dim3 grid((a.T + T_B - 1) / T_B, (n_tiles + MT * WM - 1) / (MT * WM), a.B);
-    ConvArgs av = a;
-    av.vec = (a.x_ld % 4 == 0) && (a.x_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.x) % 16 == 0);
-    av.yvec = (a.y_ld % 4 == 0) && (a.y_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.y) % 16 == 0);
-    static const bool no_ovec = lab_getenv("MI355VITS_CONV_NO_OVEC") != nullptr;
-    av.ovec = EPI == EPI_STD && !no_ovec && av.yvec && !a.shuf_s &&
-              (!a.res || ((a.res_ld % 4 == 0) && (a.res_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.res) % 16 == 0)));
-    if (av.ovec) {
-        const size_t need = (size_t)(32 * WM) * (T_B + 4) * sizeof(float);
-        if (need > shmem) shmem = need;
+    const bool wide = a.K <= 2 && a.Cin % 64 == 0 && a.epi == EPI_STD;
+    p.kernel = wide ? CONVK_B3_STAGED64 : CONVK_B3_STAGED32;
+    p.chunk = wide ? 64 : 32;
+    p.shmem = (size_t)6 * p.chunk * LD;
+    p.vec = rows_16b(a.x, a.x_bs, a.x_ld);
+    p.yvec = rows_16b(a.y, a.y_bs, a.y_ld);
+    const bool no_ovec = lab_getenv("MI355VITS_CONV_NO_OVEC") != nullptr;
+    p.ovec = a.epi == EPI_STD && !no_ovec && p.yvec && !a.shuf_s && (!a.res || rows_16b(a.res, a.res_bs, a.res_ld));
+    if (p.ovec) {
+        const size_t need = (size_t)(32 * p.WM) * (T_B + 4) * sizeof(float);
+        if (need > p.shmem) p.shmem = need;
     }
+    const bool no_pc = lab_getenv("MI355VITS_NO_B3_PC") != nullptr;
+    if (wide && a.shuf_s && (a.shuf_s & 3) == 0 && !no_pc && 2 * p.shmem <= 160 * 1024) {
+        // persistent producer / consumer form: two staging buffers, one workgroup per CU
+        const long total = (long)p.gx * p.gy * p.gz;
+        const int cus = current_device_cu_count();
+        p.kernel = CONVK_B3_PC;
+        p.shmem *= 2;
+        p.gx = (unsigned)(total < cus ? total : cus);
+        p.gy = p.gz = 1;
+    }
+}
+
+template <int MT, int NT, int WM, int WN, int EPI>
+void run_cfg(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.ring == 32) {
+        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, 32>;
+        LAUNCH_KERNEL(kfn, grid, dim3(256), p.shmem, s, a, p.chunk);
+    } else if (p.ring == 0) {
+        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, 0>;
+        LAUNCH_KERNEL(kfn, grid, dim3(256), p.shmem, s, a, p.chunk);
+    } else {
+        auto kfn = k_conv1d_mfma<MT, NT, WM, WN, EPI, -1>;
+        LAUNCH_KERNEL(kfn, grid, dim3(256), p.shmem, s, a, p.chunk);
+    }
+}
+
+template <int MT, int NT, int WM, int WN, int EPI>
+void run_b3(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const dim3 grid(p.gx, p.gy, p.gz);
+    const size_t shmem = p.shmem;
     auto go = [&](auto kfn) {
 #ifndef MI355_EMU
         if (shmem > 64 * 1024) {
             set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
         }
 #endif
-        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, av);
+        LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, a);
     };
     if constexpr (EPI == EPI_STD) {
-        static const bool no_pc = lab_getenv("MI355VITS_NO_B3_PC") != nullptr;
-        if (wide && a.shuf_s && (a.shuf_s & 3) == 0 && !no_pc && 2 * shmem <= 160 * 1024) {
-            // persistent producer / consumer form: two staging buffers, one workgroup per CU
-            const long total = (long)grid.x * grid.y * grid.z;
-            const int cus = current_device_cu_count();
-            shmem *= 2;
-            grid = dim3((unsigned)(total < cus ? total : cus), 1, 1);
+        if (p.kernel == CONVK_B3_PC) {
             auto gop = [&](auto kfn) {
 #ifndef MI355_EMU
                 set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), 160 * 1024);
 #endif
-                LAUNCH_KERNEL(kfn, grid, dim3(512), shmem, s, av);
+                LAUNCH_KERNEL(kfn, grid, dim3(512), shmem, s, a);
             };
             if (a.math == MATH_F16X2) gop(k_conv1d_b3_pc<MT, NT, WM, WN, 4, false, true>);
             else if (a.math == MATH_BF16W) gop(k_conv1d_b3_pc<MT, NT, WM, WN, 4, true>);
             else gop(k_conv1d_b3_pc<MT, NT, WM, WN, 4, false>);
             return;
         }
-        if (wide) {
+        if (p.kernel == CONVK_B3_STAGED64) {
             if (a.math == MATH_F16X2) go(k_conv1d_b3<MT, NT, WM, WN, EPI, 4, false, true>);
             else if (a.math == MATH_BF16W) go(k_conv1d_b3<MT, NT, WM, WN, EPI, 4, true>);
             else go(k_conv1d_b3<MT, NT, WM, WN, EPI, 4, false>);
@@ -1761,13 +1824,9 @@ void launch_b3(const ConvArgs& a, int n_tiles, hipStream_t s) {
 }
 
 template <int MT, int NT, int WM, int WN, int EPI>
-void launch_direct(const ConvArgs& a, int n_tiles, hipStream_t s) {
-    constexpr int T_B = 32 * NT * WN;
-    dim3 grid((a.T + T_B - 1) / T_B, (n_tiles + MT * WM - 1) / (MT * WM), a.B);
+void run_direct(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     auto kfn = k_conv_direct_mfma<MT, NT, WM, WN, EPI>;
-    ConvArgs av = a;
-    av.yvec = (a.y_ld % 4 == 0) && (a.y_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(a.y) % 16 == 0);
-    LAUNCH_KERNEL(kfn, grid, dim3(256), 0, s, av);
+    LAUNCH_KERNEL(kfn, dim3(p.gx, p.gy, p.gz), dim3(256), 0, s, a);
 }
 
 }  // namespace
@@ -1779,57 +1838,47 @@ bool conv1d_b3_supported(int Cin, int Cout, int K, int dil, int T_hint) {
     return Cin >= 32 && Cin % 32 == 0 && (size_t)6 * 32 * ((192 + (K - 1) * dil + 6) & ~3) <= 150 * 1024 && T_hint > 512;
 }
 
-void launch_conv1d_mfma(const ConvArgs& a_in, hipStream_t s) {
-    if (a_in.T <= 0 || a_in.B <= 0) return;
-    static const int ablate = lab_getenv("MI355VITS_CONV_ABLATE") ? atoi(lab_getenv("MI355VITS_CONV_ABLATE")) : 0;
-    ConvArgs a = a_in;
-    a.ablate = ablate;
+ConvPlan conv1d_mfma_plan(const ConvArgs& a) {
     if (!conv1d_mfma_supported(a.Cin, a.Cout, a.K, a.dil)) throw std::runtime_error("conv1d_mfma: unsupported shape");
+    ConvPlan p;
     const int n_tiles = n_tiles_for(a.epi, a.Cout, a.H);
+    auto blocks = [&](const TileCfg& c) {
+        const long tb = 32L * c.NT * c.WN;
+        return ((a.T + tb - 1) / tb) * ((n_tiles + c.MT * c.WM - 1) / (c.MT * c.WM)) * (long)a.B;
+    };
     if ((math_on_bf16(a.math) || (a.math == MATH_F16X2 && a.epi == EPI_STD)) && a.wb3 &&
         conv1d_b3_supported(a.Cin, a.Cout, a.K, a.dil, a.fixed_rule ? 1 << 30 : a.T)) {
         // split-bf16 path: one tile shape per epilogue kind (fixed by the layer, never by the batch)
-        if (a.epi == EPI_GATE) launch_b3<2, 3, 2, 2, EPI_GATE>(a, n_tiles, s);
-        else if (a.epi == EPI_RESSKIP) {
-            if (n_tiles >= 4) launch_b3<2, 3, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-            else launch_b3<1, 3, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
+        TileCfg c{2, 3, 2, 2};
+        if (a.epi == EPI_GATE) {
+        } else if (a.epi == EPI_RESSKIP) {
+            if (n_tiles < 4) c = TileCfg{1, 3, 2, 2};
         } else {
             // the largest tile whose grid still covers a good part of the chip, else the finest.  The three shapes walk
             // chunks, taps and groups in the same order: an output element gets the same bits from each, so the choice
             // may depend on the grid (batch 1 vs batch 32) without breaking "batched == unbatched"
-            auto nwg = [&](int MT, int NT, int WM, int WN) {
-                const long tb = 32L * NT * WN;
-                return ((a.T + tb - 1) / tb) * ((n_tiles + MT * WM - 1) / (MT * WM)) * (long)a.B;
-            };
-            if (n_tiles >= 4 && nwg(2, 3, 2, 2) >= 96) launch_b3<2, 3, 2, 2, EPI_STD>(a, n_tiles, s);
-            else if (n_tiles >= 2 && nwg(1, 3, 2, 2) >= 96) launch_b3<1, 3, 2, 2, EPI_STD>(a, n_tiles, s);
-            else launch_b3<1, 2, 1, 4, EPI_STD>(a, n_tiles, s);
+            if (n_tiles >= 4 && blocks(TileCfg{2, 3, 2, 2}) >= 96) c = TileCfg{2, 3, 2, 2};
+            else if (n_tiles >= 2 && blocks(TileCfg{1, 3, 2, 2}) >= 96) c = TileCfg{1, 3, 2, 2};
+            else c = TileCfg{1, 2, 1, 4};
         }
-        return;
+        plan_tile(a, n_tiles, c, p);
+        plan_b3(a, p);
+        return p;
     }
     // Tile choice.  Every CU works through ceil(blocks / 256) workgroups' worth of MFMA time, so a grid of 576
     // workgroups runs at 576 / 768 = 75 % of one of 1152: take the largest tile whose grid fills the 256 CUs to
     // >= 85 %, else the candidate that fills them best (small problems: the finest tile = most parallelism).
-    auto blocks = [&](int MT, int NT, int WM, int WN) {
-        const long tb = 32L * NT * WN;
-        return ((a.T + tb - 1) / tb) * ((n_tiles + MT * WM - 1) / (MT * WM)) * (long)a.B;
-    };
     auto fill = [&](long nb) { return (double)nb / (256.0 * (double)((nb + 255) / 256)); };
-    struct Cand { int MT, NT, WM, WN; };
-    static const Cand forced = [] {
-        Cand f{0, 0, 0, 0};
-        const char* e = lab_getenv("MI355VITS_CONV_CFG");
-        if (e) sscanf(e, "%d,%d,%d,%d", &f.MT, &f.NT, &f.WM, &f.WN);
-        return f;
-    }();
-    auto choose = [&](const Cand* c, int n) {
+    TileCfg forced{0, 0, 0, 0};
+    if (const char* e = lab_getenv("MI355VITS_CONV_CFG")) sscanf(e, "%d,%d,%d,%d", &forced.MT, &forced.NT, &forced.WM, &forced.WN);  // lab / tests
+    auto choose = [&](const TileCfg* c, int n) {
         if (forced.MT)
             for (int i = 0; i < n; ++i)
                 if (c[i].MT == forced.MT && c[i].NT == forced.NT && c[i].WM == forced.WM && c[i].WN == forced.WN) return i;
         int best = n - 1;
         double bf = -1.0;
         for (int i = 0; i < n; ++i) {  // candidates ordered from the largest tile to the smallest
-            const double f = fill(blocks(c[i].MT, c[i].NT, c[i].WM, c[i].WN));
+            const double f = fill(blocks(c[i]));
             if (f >= 0.85) return i;
             if (f > bf + 1e-9) { bf = f; best = i; }
         }
@@ -1837,63 +1886,94 @@ void launch_conv1d_mfma(const ConvArgs& a_in, hipStream_t s) {
     };
     // LDS-free streaming kernel: pointwise convs, and short sequences (encoder FFN) where the grid is too small to
     // hide the stage/barrier cycle of the staged kernel
-    static const int poly_direct_cin = lab_getenv("MI355VITS_POLY_DIRECT_CIN") ? atoi(lab_getenv("MI355VITS_POLY_DIRECT_CIN")) : 64;
+    const char* e_pd = lab_getenv("MI355VITS_POLY_DIRECT_CIN");
+    const int poly_direct_cin = e_pd ? atoi(e_pd) : 64;
     const bool direct = a.epi != EPI_GATE && ((a.K * (a.Cin >> 1)) % 8) == 0 &&
                         (a.shuf_s ? (a.K <= 2 && a.Cin <= poly_direct_cin && (a.shuf_s & 3) == 0)
                                   : (a.K == 1 || (a.K <= 3 && a.T <= 512 && !a.fixed_rule)));
     // deep + short (encoder FFN conv_2): split the k-steps over the four waves of a workgroup.  The rule looks at the
     // layer shape only, never at the batch size, so a row's bits do not depend on what it is batched with.
     if (direct && a.epi == EPI_STD && a.T <= 512 && a.K * (a.Cin >> 1) >= 512 && ((a.K * (a.Cin >> 1)) % 32) == 0) {
-        dim3 grid((a.T + 31) / 32, n_tiles, a.B);
-        auto kfn = k_conv_direct_splitk<EPI_STD>;
-        LAUNCH_KERNEL(kfn, grid, dim3(256), 4 * 16 * 64 * sizeof(float), s, a);
-        return;
+        p.kernel = CONVK_F32_SPLITK;
+        p.cols = 32;
+        p.rows = 32;
+        p.gx = (a.T + 31) / 32;
+        p.gy = n_tiles;
+        p.gz = a.B;
+        p.shmem = 4 * 16 * 64 * sizeof(float);
+        return p;
     }
+    TileCfg c;
     if (a.epi == EPI_GATE) {
-        const Cand c[] = {{2, 2, 2, 2}, {2, 1, 2, 2}};
-        if (choose(c, 2) == 0) launch_cfg<2, 2, 2, 2, EPI_GATE>(a, n_tiles, s);
-        else launch_cfg<2, 1, 2, 2, EPI_GATE>(a, n_tiles, s);
-        return;
+        const TileCfg cand[] = {{2, 2, 2, 2}, {2, 1, 2, 2}};
+        c = cand[choose(cand, 2)];
+    } else if (a.epi == EPI_STD && n_tiles == 1) {
+        const TileCfg cand[] = {{1, 2, 1, 4}, {1, 1, 1, 4}};
+        c = cand[choose(cand, 2)];
+    } else {  // EPI_RESSKIP, and EPI_STD with two row tiles or more
+        const TileCfg cand[] = {{2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
+        const int first = n_tiles >= 4 ? 0 : ((n_tiles >= 2 || a.epi == EPI_STD) ? 1 : 2);
+        c = cand[choose(cand + first, 3 - first) + first];
     }
-    if (a.epi == EPI_RESSKIP) {
-        const Cand c[] = {{2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
-        const int k = choose(c + (n_tiles >= 4 ? 0 : (n_tiles >= 2 ? 1 : 2)), n_tiles >= 4 ? 3 : (n_tiles >= 2 ? 2 : 1)) +
-                      (n_tiles >= 4 ? 0 : (n_tiles >= 2 ? 1 : 2));
-        if (direct) {
-            if (k == 0) launch_direct<2, 2, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-            else if (k == 1) launch_direct<1, 2, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-            else launch_direct<1, 1, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-        } else {
-            if (k == 0) launch_cfg<2, 2, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-            else if (k == 1) launch_cfg<1, 2, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-            else launch_cfg<1, 1, 2, 2, EPI_RESSKIP>(a, n_tiles, s);
-        }
-        return;
-    }
-    if (n_tiles == 1) {
-        const Cand c[] = {{1, 2, 1, 4}, {1, 1, 1, 4}};
-        const int k = choose(c, 2);
-        if (direct) {
-            if (k == 0) launch_direct<1, 2, 1, 4, EPI_STD>(a, n_tiles, s);
-            else launch_direct<1, 1, 1, 4, EPI_STD>(a, n_tiles, s);
-        } else {
-            if (k == 0) launch_cfg<1, 2, 1, 4, EPI_STD>(a, n_tiles, s);
-            else launch_cfg<1, 1, 1, 4, EPI_STD>(a, n_tiles, s);
-        }
-        return;
-    }
-    const Cand c[] = {{2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
-    const int first = n_tiles >= 4 ? 0 : 1;
-    const int k = choose(c + first, 3 - first) + first;
+    plan_tile(a, n_tiles, c, p);
     if (direct) {
-        if (k == 0) launch_direct<2, 2, 2, 2, EPI_STD>(a, n_tiles, s);
-        else if (k == 1) launch_direct<1, 2, 2, 2, EPI_STD>(a, n_tiles, s);
-        else launch_direct<1, 1, 2, 2, EPI_STD>(a, n_tiles, s);
+        p.kernel = CONVK_F32_DIRECT;
+        p.yvec = rows_16b(a.y, a.y_bs, a.y_ld);
     } else {
-        if (k == 0) launch_cfg<2, 2, 2, 2, EPI_STD>(a, n_tiles, s);
-        else if (k == 1) launch_cfg<1, 2, 2, 2, EPI_STD>(a, n_tiles, s);
-        else launch_cfg<1, 1, 2, 2, EPI_STD>(a, n_tiles, s);
+        plan_cfg(a, p);
     }
+    return p;
+}
+
+void launch_conv1d_mfma(const ConvArgs& a_in, hipStream_t s) {
+    if (a_in.T <= 0 || a_in.B <= 0) return;
+    static const int ablate = lab_getenv("MI355VITS_CONV_ABLATE") ? atoi(lab_getenv("MI355VITS_CONV_ABLATE")) : 0;
+    ConvArgs a = a_in;
+    a.ablate = ablate;
+    const ConvPlan p = conv1d_mfma_plan(a);
+    if (p.kernel == CONVK_F32_SPLITK) {
+        auto kfn = k_conv_direct_splitk<EPI_STD>;
+        LAUNCH_KERNEL(kfn, dim3(p.gx, p.gy, p.gz), dim3(256), p.shmem, s, a);
+        return;
+    }
+    a.yvec = p.yvec;
+    if (p.kernel != CONVK_F32_DIRECT) { a.vec = p.vec; a.ovec = p.ovec; }
+    // the instantiated (kernel, epilogue, tile) combinations: exactly what the plan can return
+#define CONV_RUN(RUN, EPI_, MT_, NT_, WM_, WN_)                                                          \
+    if (a.epi == EPI_ && p.MT == MT_ && p.NT == NT_ && p.WM == WM_ && p.WN == WN_) {                      \
+        RUN<MT_, NT_, WM_, WN_, EPI_>(a, p, s);                                                           \
+        return;                                                                                           \
+    }
+    if (p.kernel == CONVK_B3_STAGED32 || p.kernel == CONVK_B3_STAGED64 || p.kernel == CONVK_B3_PC) {
+        CONV_RUN(run_b3, EPI_GATE, 2, 3, 2, 2)
+        CONV_RUN(run_b3, EPI_RESSKIP, 2, 3, 2, 2)
+        CONV_RUN(run_b3, EPI_RESSKIP, 1, 3, 2, 2)
+        CONV_RUN(run_b3, EPI_STD, 2, 3, 2, 2)
+        CONV_RUN(run_b3, EPI_STD, 1, 3, 2, 2)
+        CONV_RUN(run_b3, EPI_STD, 1, 2, 1, 4)
+    } else if (p.kernel == CONVK_F32_DIRECT) {
+        CONV_RUN(run_direct, EPI_RESSKIP, 2, 2, 2, 2)
+        CONV_RUN(run_direct, EPI_RESSKIP, 1, 2, 2, 2)
+        CONV_RUN(run_direct, EPI_RESSKIP, 1, 1, 2, 2)
+        CONV_RUN(run_direct, EPI_STD, 1, 2, 1, 4)
+        CONV_RUN(run_direct, EPI_STD, 1, 1, 1, 4)
+        CONV_RUN(run_direct, EPI_STD, 2, 2, 2, 2)
+        CONV_RUN(run_direct, EPI_STD, 1, 2, 2, 2)
+        CONV_RUN(run_direct, EPI_STD, 1, 1, 2, 2)
+    } else {
+        CONV_RUN(run_cfg, EPI_GATE, 2, 2, 2, 2)
+        CONV_RUN(run_cfg, EPI_GATE, 2, 1, 2, 2)
+        CONV_RUN(run_cfg, EPI_RESSKIP, 2, 2, 2, 2)
+        CONV_RUN(run_cfg, EPI_RESSKIP, 1, 2, 2, 2)
+        CONV_RUN(run_cfg, EPI_RESSKIP, 1, 1, 2, 2)
+        CONV_RUN(run_cfg, EPI_STD, 1, 2, 1, 4)
+        CONV_RUN(run_cfg, EPI_STD, 1, 1, 1, 4)
+        CONV_RUN(run_cfg, EPI_STD, 2, 2, 2, 2)
+        CONV_RUN(run_cfg, EPI_STD, 1, 2, 2, 2)
+        CONV_RUN(run_cfg, EPI_STD, 1, 1, 2, 2)
+    }
+#undef CONV_RUN
+    throw std::runtime_error("conv1d_mfma: no kernel for the planned tile");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1962,14 +2042,26 @@ __global__ __launch_bounds__(256) void k_conv_transpose1d(ConvTArgs a) {
     }
 }
 
-void launch_conv_transpose1d(const ConvTArgs& a, hipStream_t s) {
-    if (a.Tin <= 0 || a.B <= 0) return;
+ConvPlan conv_transpose1d_plan(const ConvTArgs& a) {
+    ConvPlan p;
+    p.kernel = CONVK_CONVT_GENERIC;
+    p.cols = CT_N;
+    p.rows = CT_CO;
+    p.chunk = CT_CI;
     const int Tout = a.Tin * a.stride;
     const int taps = (a.K + a.stride - 1) / a.stride;
     const int NI = CT_N / a.stride + taps + 2;  // upper bound of i_hi - i_lo + 1
-    const size_t shmem = sizeof(float) * ((size_t)CT_CI * NI + (size_t)CT_CI * CT_CO * a.K);
-    dim3 grid((Tout + CT_N - 1) / CT_N, (a.Cout + CT_CO - 1) / CT_CO, a.B);
-    LAUNCH_KERNEL(k_conv_transpose1d, grid, dim3(256), shmem, s, a);
+    p.shmem = sizeof(float) * ((size_t)CT_CI * NI + (size_t)CT_CI * CT_CO * a.K);
+    p.gx = (Tout + CT_N - 1) / CT_N;
+    p.gy = (a.Cout + CT_CO - 1) / CT_CO;
+    p.gz = a.B;
+    return p;
+}
+
+void launch_conv_transpose1d(const ConvTArgs& a, hipStream_t s) {
+    if (a.Tin <= 0 || a.B <= 0) return;
+    const ConvPlan p = conv_transpose1d_plan(a);
+    LAUNCH_KERNEL(k_conv_transpose1d, dim3(p.gx, p.gy, p.gz), dim3(256), p.shmem, s, a);
 }
 
 // Polyphase view of ConvTranspose1d (A.2): output n = i*s + r - p, r in [0,s) takes taps k = r + m*s (m = 0..taps-1)
@@ -2263,19 +2355,26 @@ __global__ __launch_bounds__(256) void k_conv_post_tanh_dpp(const float* __restr
     }
 }
 
-void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, int Cin, int K, int B, int L,
-                           const int* valid_len, float* audio, long audio_bs, unsigned* peak_bits, hipStream_t s) {
-    if (L <= 0 || B <= 0) return;
-    static const bool no_vec = lab_getenv("MI355VITS_CONV_POST_STAGED") != nullptr;
+int conv_post_kernel(const float* x, long x_bs, int x_ld, int Cin, int K, const float* audio, long audio_bs) {
+    const bool no_vec = lab_getenv("MI355VITS_CONV_POST_STAGED") != nullptr;  // lab / tests (read at every launch, as the next one)
     const bool aligned = (x_ld % 4 == 0) && (x_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
                          (audio_bs % 4 == 0) && (reinterpret_cast<uintptr_t>(audio) % 16 == 0);
     const bool no_dpp = lab_getenv("MI355VITS_CONV_POST_V1") != nullptr;  // lab / tests: the round-1 kernels
-    if (aligned && K == 7 && Cin % CPD_CU == 0 && (long)Cin * x_ld * 4 < 0x7fffffffL && !no_vec && !no_dpp) {
+    if (aligned && K == 7 && Cin % CPD_CU == 0 && (long)Cin * x_ld * 4 < 0x7fffffffL && !no_vec && !no_dpp) return 0;
+    if (aligned && K <= 9 && (K & 1) && !no_vec) return 1;
+    return 2;
+}
+
+void launch_conv_post_tanh(const float* x, long x_bs, int x_ld, const float* w, int Cin, int K, int B, int L,
+                           const int* valid_len, float* audio, long audio_bs, unsigned* peak_bits, hipStream_t s) {
+    if (L <= 0 || B <= 0) return;
+    const int kernel = conv_post_kernel(x, x_bs, x_ld, Cin, K, audio, audio_bs);
+    if (kernel == 0) {
         dim3 grid((L + CPD_T - 1) / CPD_T, B);
         LAUNCH_KERNEL(k_conv_post_tanh_dpp, grid, dim3(256), 0, s, x, x_bs, x_ld, w, Cin, L, valid_len, audio, audio_bs, peak_bits);
         return;
     }
-    if (aligned && K <= 9 && (K & 1) && !no_vec) {
+    if (kernel == 1) {
         dim3 grid((L + CPV_T - 1) / CPV_T, B);
         LAUNCH_KERNEL(k_conv_post_tanh_vec, grid, dim3(256), 0, s, x, x_bs, x_ld, w, Cin, K, L, valid_len, audio, audio_bs,
                       peak_bits);

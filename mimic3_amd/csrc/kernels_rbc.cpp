@@ -1004,13 +1004,6 @@ inline int rbc_requested_order() {
     if (const char* f = lab_getenv("MI355VITS_RBC_ITEM_ORDER")) return atoi(f);  // lab / tests: 0 = items w, w + W, ... as in round 4
     return RBC_ITEM_ORDER;
 }
-// the items of a launch (N positions each, `extra` positions per row beyond its length) into the arguments; the persistent grid, 0 = no work
-inline int rbc_items(ConvArgs& a, int N, int extra, int cus) {
-    const ItemLaunch il = item_launch(a.in_len_host, a.in_len, a.B, a.T, N, extra, cus, rbc_requested_order());
-    a.nvalid = il.nvalid;
-    a.item_order = il.item_order;
-    return il.nvalid > 0 ? il.grid : 0;
-}
 inline bool rbc_shape(int K, int dil) {  // the "_low" voices' stage-0 convs (instantiated tap / dilation pairs)
     return (K == 3 && (dil == 1 || dil == 2)) || (K == 5 && (dil == 2 || dil == 6)) || (K == 7 && (dil == 3 || dil == 12));
 }
@@ -1026,28 +1019,45 @@ bool rb_conv_supported(const ConvArgs& a) {
            (long)RBC_C * ld * 4 < 0x7fffffffL;
 }
 
-// a.w = the conv's pack_conv_weights_p16 fragments.  wide = 128-column items (grids that fill the chip), else 32-column items:
-// the same bits either way
-void launch_rb_conv(ConvArgs a, hipStream_t s) {
-    if (a.T <= 0 || a.B <= 0) return;
-    if (!rb_conv_supported(a)) throw std::runtime_error("rb_conv: unsupported shape");
+// wide = 128-column items (grids that fill the chip: k_rb_conv_pw), else 32-column items (k_rb_conv): the same bits either way
+ConvPlan rb_conv_plan(const ConvArgs& a) {
+    ConvPlan p;
     const int cus = current_device_cu_count();
     // (the form follows the items that HAVE work: a ragged batch is as large as the sum of its rows)
     bool wide = valid_items(a.in_len_host, a.in_len, a.B, a.T, 128) >= cus;
     if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
+    p.kernel = wide ? CONVK_RB_CONV_PW : CONVK_RB_CONV;
+    p.cols = wide ? 128 : 32;
+    p.rows = RBC_C;
+    p.chunk = RBC_C;
+    const ItemLaunch il = item_launch(a.in_len_host, a.in_len, a.B, a.T, p.cols, 0, cus, rbc_requested_order());  // persistent: one workgroup per CU
+    p.nvalid = il.nvalid;
+    p.item_order = il.item_order;
+    p.gx = il.nvalid > 0 ? il.grid : 0;
+    p.gy = p.gz = 1;
+    return p;
+}
+
+// a.w = the conv's pack_conv_weights_p16 fragments
+void launch_rb_conv(ConvArgs a, hipStream_t s) {
+    if (a.T <= 0 || a.B <= 0) return;
+    if (!rb_conv_supported(a)) throw std::runtime_error("rb_conv: unsupported shape");
+    const ConvPlan p = rb_conv_plan(a);
+    const bool wide = p.kernel == CONVK_RB_CONV_PW;
+    a.nvalid = p.nvalid;
+    a.item_order = p.item_order;
     // wide items: the producer-wave form (twelve waves, k_rb_conv_pw); narrow items: k_rb_conv (eight waves)
-    auto go = [&](auto kfn, size_t lds, int ncols, int threads) {
-        const int grid = rbc_items(a, ncols, 0, cus);  // persistent: one workgroup per CU
-        if (grid <= 0) return;
+    auto go = [&](auto kfn, size_t lds, int threads) {
+        if (p.gx == 0) return;
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, dim3(grid), dim3(threads), lds, s, a);
+        LAUNCH_KERNEL(kfn, dim3(p.gx), dim3(threads), lds, s, a);
     };
 #if defined(MI355_LAB) && !defined(MI355_EMU)
     if (wide && lab_getenv("MI355VITS_RBC_CLOCKS") && ((a.K == 7 && a.dil == 3) || (a.K == 3 && a.dil == 1))) {
         static int shots = 0;
         if (shots < 4) {  // (two launches of each shape: the first warms the caches)
             ++shots;
-            const int grid = rbc_items(a, 128, 0, cus);
+            const int grid = (int)p.gx;
             float* dbg = nullptr;
             const size_t nb = (size_t)grid * 3 * 8 * 8 * 4;
             HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dbg), nb));
@@ -1083,8 +1093,8 @@ void launch_rb_conv(ConvArgs a, hipStream_t s) {
 #endif
 #define RBC_CASE(KK, DD)                                                              \
     if (a.K == KK && a.dil == DD) {                                                   \
-        if (wide) go(k_rb_conv_pw<KK, DD, 3>, RbcGeo<KK, DD, 8>::LDS, 128, 768);      \
-        else go(k_rb_conv<KK, DD>, RbcGeo<KK, DD, 2>::LDS, 32, 512);                  \
+        if (wide) go(k_rb_conv_pw<KK, DD, 3>, RbcGeo<KK, DD, 8>::LDS, 768);           \
+        else go(k_rb_conv<KK, DD>, RbcGeo<KK, DD, 2>::LDS, 512);                      \
         return;                                                                       \
     }
     RBC_CASE(3, 1)
@@ -1147,33 +1157,47 @@ bool ups_pl_supported(const ConvArgs& a) {
            a.x_ld >= a.Tin && a.y_ld >= a.shuf_T && (long)a.Cin * a.x_ld * 4 < 0x7fffffffL && (long)(a.Cin / 2) * a.y_ld * 4 < 0x7fffffffL;
 }
 
+// 256 -> 128: eight row blocks over 64-column items (32 records of planes: 123 KiB) or 32-column ones; 128 -> 64: 128- or 32-column
+// items; 64 -> 32 (k_ups64): 127- or 31-column items.  The wide items where the grid still gives every CU one.
+ConvPlan ups_pl_plan(const ConvArgs& a) {
+    ConvPlan p;
+    const int cus = current_device_cu_count();
+    const int wcols = a.Cin == 256 ? 64 : (a.Cin == 128 ? 128 : 127);
+    bool wide = (long)a.B * ((a.T + wcols - 1) / wcols) >= cus;
+    if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
+    p.kernel = a.Cin == 64 ? CONVK_UPS64 : CONVK_UPS_PL;
+    p.cols = wide ? wcols : (a.Cin == 64 ? 31 : 32);
+    p.rows = a.Cout;
+    p.chunk = a.Cin;
+    const ItemLaunch il = item_launch(a.in_len_host, a.in_len, a.B, a.T, p.cols, 1, cus, rbc_requested_order());  // a row of len input positions has len + 1 output positions
+    p.nvalid = il.nvalid;
+    p.item_order = il.item_order;
+    p.gx = il.nvalid > 0 ? il.grid : 0;
+    p.gy = p.gz = 1;
+    return p;
+}
+
 // a.w = the polyphase filter's pack_conv_weights_p16n fragments
 void launch_ups_pl(ConvArgs a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     if (!ups_pl_supported(a)) throw std::runtime_error("ups_pl: unsupported shape");
-    const int cus = current_device_cu_count();
-    auto go = [&](auto kfn, size_t lds, int ncols) {
-        const int grid = rbc_items(a, ncols, 1, cus);  // a row of len input positions has len + 1 output positions
-        if (grid <= 0) return;
+    const ConvPlan p = ups_pl_plan(a);
+    a.nvalid = p.nvalid;
+    a.item_order = p.item_order;
+    auto go = [&](auto kfn, size_t lds) {
+        if (p.gx == 0) return;
         set_max_dynamic_lds(reinterpret_cast<const void*>(kfn), (int)RBC_LDS_LIMIT);
-        LAUNCH_KERNEL(kfn, dim3(grid), dim3(512), lds, s, a);
+        LAUNCH_KERNEL(kfn, dim3(p.gx), dim3(512), lds, s, a);
     };
-    if (a.Cin == 256) {  // 256 -> 128: eight row blocks over 64-column items (32 records of planes: 123 KiB)
-        bool wide = (long)a.B * ((a.T + 63) / 64) >= cus;
-        if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
-        if (wide) go(k_ups_pl<256, 8, 4>, UpsGeo<256, 8, 4>::LDS, 64);
-        else go(k_ups_pl<256, 8, 2>, UpsGeo<256, 8, 2>::LDS, 32);
+    if (a.Cin == 256) {
+        if (p.cols == 64) go(k_ups_pl<256, 8, 4>, UpsGeo<256, 8, 4>::LDS);
+        else go(k_ups_pl<256, 8, 2>, UpsGeo<256, 8, 2>::LDS);
     } else if (a.Cin == 128) {
-        bool wide = (long)a.B * ((a.T + 127) / 128) >= cus;
-        if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;  // lab / tests
-        if (wide) go(k_ups_pl<128, 8, 8>, UpsGeo<128, 8, 8>::LDS, 128);
-        else go(k_ups_pl<128, 8, 2>, UpsGeo<128, 8, 2>::LDS, 32);
+        if (p.cols == 128) go(k_ups_pl<128, 8, 8>, UpsGeo<128, 8, 8>::LDS);
+        else go(k_ups_pl<128, 8, 2>, UpsGeo<128, 8, 2>::LDS);
     } else {
-        const long n127 = (long)a.B * ((a.T + 126) / 127);
-        bool wide = n127 >= cus;
-        if (const char* f = lab_getenv("MI355VITS_RBC_WIDE")) wide = atoi(f) != 0;
-        if (wide) go(k_ups64<8>, Ups64Geo<8>::LDS, 127);
-        else go(k_ups64<2>, Ups64Geo<2>::LDS, 31);
+        if (p.cols == 127) go(k_ups64<8>, Ups64Geo<8>::LDS);
+        else go(k_ups64<2>, Ups64Geo<2>::LDS);
     }
 }
 

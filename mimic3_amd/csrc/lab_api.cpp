@@ -13,45 +13,116 @@ int mi355vits_probe_weights(mi355vits_handle h, double out[8]) {
     return guarded(h, [&] { h->eng->probe_weights(out); });
 }
 
-// kernel unit-test hooks (host buffers in, host buffers out)
+// ---- the conv hooks (include/mi355vits_lab.h says what each impl reads and writes at and past a row's lengths)
+}  // extern "C"
+
+namespace {
+const float* const ALIGNED = reinterpret_cast<const float*>(uintptr_t(4096));  // a stand-in for a 16-byte aligned buffer (plan call: never read)
+
+struct ConvHookOpts { bool bias, res, cond, in_len, out_len, relu, res_sub, accumulate, mask_before_res; float out_scale; };
+
+// the launch arguments of mi355vits_test_conv1d without its buffers, after the checks the hook makes before any launch
+ConvArgs conv_hook_args(int impl, int B, int Cin, int Cout, int T, int K, int dil, int math, int fixed_rule, const ConvHookOpts& o) {
+    if (impl < 0 || impl > 4) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0 .. 4");
+    if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || K < 1 || dil < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+    if ((size_t)B * std::max(Cin, Cout) * T >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+    const bool ok_math = impl <= 1 ? math == MATH_F32 : impl == 4 ? math == MATH_BF16X3 : (math == MATH_BF16X3 || math == MATH_BF16W);
+    if (!ok_math) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 for impl 0 and 1, MATH_BF16X3 or MATH_BF16W for impl 2 and 3, MATH_BF16X3 for impl 4");
+    if (fixed_rule && impl != 1 && impl != 2) throw EngineError(MI355VITS_ERR_INVALID, "fixed_rule: impl 1 and 2 only");
+    ConvArgs a;
+    a.x_bs = (long)Cin * T; a.x_ld = T;
+    a.y_bs = (long)Cout * T; a.y_ld = T;
+    a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.K = K; a.dil = dil;
+    a.pad = (K * dil - dil) / 2;
+    a.relu = o.relu; a.out_scale = o.out_scale; a.res_sub = o.res_sub; a.accumulate = o.accumulate; a.mask_before_res = o.mask_before_res;
+    a.math = math;
+    a.fixed_rule = fixed_rule ? 1 : 0;
+    if (o.res) { a.res_bs = a.y_bs; a.res_ld = T; }
+    if (o.cond) a.cond_bs = Cout;
+    if (impl == 3) {  // the encoder's slice kernel (k_enc_b3); split convs: the raw slice sums added up by the hook, no epilogue
+        if (!enc_conv_b3_supported(Cin, Cout, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the encoder slice kernel");
+        a.ksplit = enc_conv_b3_slices(Cin);
+        if (a.ksplit > 1 && (o.bias || o.res || o.relu || o.accumulate || o.cond || o.res_sub || o.mask_before_res || o.out_len || o.out_scale != 1.0f))
+            throw EngineError(MI355VITS_ERR_INVALID, "split conv: raw sums only");
+    } else if (impl == 4) {  // the 128-channel resblock conv with every input channel resident (k_rb_conv / k_rb_conv_pw)
+        ConvArgs c = a;
+        c.res = o.res ? ALIGNED : nullptr; c.in_len = o.in_len ? reinterpret_cast<const int*>(ALIGNED) : nullptr;
+        c.cond = o.cond ? ALIGNED : nullptr; c.out_len = o.out_len ? reinterpret_cast<const int*>(ALIGNED) : nullptr;
+        if (!rb_conv_supported(c)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input kernel");
+    } else if (impl == 1 || impl == 2) {
+        if (!conv1d_mfma_supported(Cin, Cout, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
+        if (impl == 2 && !conv1d_b3_supported(Cin, Cout, K, dil, fixed_rule ? 1 << 30 : T))
+            throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the split-bf16 kernel");
+    }
+    return a;
+}
+
+// the polyphase view of mi355vits_test_conv_transpose1d impl 1 - 3 (ConvArgs::shuf_*), without its buffers
+ConvArgs convt_hook_args(int impl, int B, int Cin, int Cout, int Tin, int K, int stride) {
+    const int taps = convt_taps(K, stride);
+    ConvArgs u;
+    u.x_bs = (long)Cin * Tin; u.x_ld = Tin;
+    u.y_bs = (long)Cout * Tin * stride; u.y_ld = Tin * stride;
+    u.Cin = Cin; u.Cout = stride * Cout; u.K = taps; u.dil = 1;
+    u.pad = taps - 1; u.Tin = Tin;
+    u.shuf_s = stride; u.shuf_p = (K - stride) / 2; u.shuf_cout = Cout; u.shuf_T = Tin * stride;
+    u.B = B; u.T = Tin + taps - 1;
+    if (impl >= 2) u.math = MATH_BF16X3;
+    if (impl == 2) u.fixed_rule = 1;
+    return u;
+}
+
+void convt_hook_check(int impl, int B, int Cin, int Cout, int Tin, int K, int stride, bool has_len) {
+    if (impl < 0 || impl > 3) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0 .. 3");
+    if (B < 1 || Cin < 1 || Cout < 1 || Tin < 1 || K < 1 || stride < 1 || K < stride || ((K - stride) & 1))
+        throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+    if ((size_t)B * std::max(Cin, Cout * stride) * Tin >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+    if (has_len && impl != 3) throw EngineError(MI355VITS_ERR_INVALID, "per-row lengths: impl 3 only");
+    if ((impl == 1 || impl == 2) && !conv1d_mfma_supported(Cin, stride * Cout, convt_taps(K, stride), 1))
+        throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
+    if (impl == 2 && !conv1d_b3_supported(Cin, stride * Cout, convt_taps(K, stride), 1, 1 << 30))
+        throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the split-bf16 kernel");
+}
+
+void check_lens(const int32_t* len, int B, int T, const char* what) {
+    for (int b = 0; len && b < B; ++b)
+        if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, what);
+}
+}  // namespace
+
+extern "C" {
+
 int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
     return guarded(nullptr, [&] {
         if (!t || !t->x || !t->w || !t->y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const ConvHookOpts o{t->bias != nullptr, t->res != nullptr, t->cond != nullptr, t->in_len != nullptr, t->out_len != nullptr, t->relu != 0,
+                             t->res_sub != 0, t->accumulate != 0, t->mask_before_res != 0, t->out_scale};
+        ConvArgs a = conv_hook_args(t->impl, t->B, t->Cin, t->Cout, t->T, t->K, t->dilation, t->math, t->fixed_rule, o);
+        check_lens(t->in_len, t->B, t->T, "in_len out of range");
+        check_lens(t->out_len, t->B, t->T, "out_len out of range");
         HIP_CHECK(hipSetDevice(device));
         const size_t nx = (size_t)t->B * t->Cin * t->T, ny = (size_t)t->B * t->Cout * t->T;
         const size_t nw = (size_t)t->Cout * t->Cin * t->K;
-        DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(t->Cout * 4), dres(ny * 4), dil(t->B * 4), dol(t->B * 4);
+        DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(t->Cout * 4), dres(ny * 4), dil(t->B * 4), dol(t->B * 4), dcond((size_t)t->B * t->Cout * 4);
         std::vector<float> packed;
         HIP_CHECK(hipMemcpy(dx.p, t->x, nx * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dy.p, t->y, ny * 4, hipMemcpyHostToDevice));
-        ConvArgs a;
-        a.x = dx.as<float>(); a.x_bs = (long)t->Cin * t->T; a.x_ld = t->T;
-        a.y = dy.as<float>(); a.y_bs = (long)t->Cout * t->T; a.y_ld = t->T;
-        a.B = t->B; a.Cin = t->Cin; a.Cout = t->Cout; a.T = t->T; a.K = t->K; a.dil = t->dilation;
-        a.pad = (t->K * t->dilation - t->dilation) / 2;
-        a.in_slope = t->in_slope; a.relu = t->relu; a.out_scale = t->out_scale; a.res_sub = t->res_sub;
-        a.accumulate = t->accumulate;
+        a.x = dx.as<float>();
+        a.y = dy.as<float>();
+        a.in_slope = t->in_slope;
         if (t->bias) { HIP_CHECK(hipMemcpy(db.p, t->bias, t->Cout * 4, hipMemcpyHostToDevice)); a.bias = db.as<float>(); }
-        if (t->res) {
-            HIP_CHECK(hipMemcpy(dres.p, t->res, ny * 4, hipMemcpyHostToDevice));
-            a.res = dres.as<float>(); a.res_bs = a.y_bs; a.res_ld = t->T;
-        }
+        if (t->res) { HIP_CHECK(hipMemcpy(dres.p, t->res, ny * 4, hipMemcpyHostToDevice)); a.res = dres.as<float>(); }
+        if (t->cond) { HIP_CHECK(hipMemcpy(dcond.p, t->cond, (size_t)t->B * t->Cout * 4, hipMemcpyHostToDevice)); a.cond = dcond.as<float>(); }
         if (t->in_len) { HIP_CHECK(hipMemcpy(dil.p, t->in_len, t->B * 4, hipMemcpyHostToDevice)); a.in_len = dil.as<int>(); }
         if (t->out_len) { HIP_CHECK(hipMemcpy(dol.p, t->out_len, t->B * 4, hipMemcpyHostToDevice)); a.out_len = dol.as<int>(); }
-        if (t->impl == 3) {  // the encoder's slice kernel (k_enc_b3); split convs: the raw slice sums added up here, no epilogue
-            if (!enc_conv_b3_supported(t->Cin, t->Cout, t->K, t->dilation)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the encoder slice kernel");
+        if (t->impl == 3) {
             std::vector<uint32_t> b3(bf16x3_packed_words_mode(t->Cout, t->Cin, t->K, EPI_STD));
             pack_conv_weights_bf16x3_mode(t->w, t->Cout, t->Cin, t->K, EPI_STD, 1, b3.data());
             DevBuf db3(b3.size() * 4);
             HIP_CHECK(hipMemcpy(db3.p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
             a.wb3 = db3.as<float>();
-            a.math = MATH_BF16X3;
-            a.ksplit = enc_conv_b3_slices(t->Cin);
             DevBuf dpart(ny * 4 * (size_t)a.ksplit);
-            if (a.ksplit > 1) {
-                if (t->bias || t->res || t->relu || t->accumulate) throw EngineError(MI355VITS_ERR_INVALID, "split conv: raw sums only");
-                a.part = dpart.as<float>();
-            }
+            if (a.ksplit > 1) a.part = dpart.as<float>();
             launch_enc_conv_b3(a, nullptr);
             HIP_CHECK(hipDeviceSynchronize());
             HIP_CHECK(hipGetLastError());
@@ -65,19 +136,16 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
                 }
                 return;
             }
-        } else if (t->impl == 4) {  // the 128-channel resblock conv with every input channel resident (k_rb_conv / k_rb_conv_pw)
-            if (!rb_conv_supported(a)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input kernel");
+        } else if (t->impl == 4) {
             std::vector<uint32_t> pp(p16_packed_words(t->Cout, t->Cin, t->K));
             pack_conv_weights_p16(t->w, t->Cout, t->Cin, t->K, pp.data());
             DevBuf dpp(pp.size() * 4);
             HIP_CHECK(hipMemcpy(dpp.p, pp.data(), pp.size() * 4, hipMemcpyHostToDevice));
             a.w = dpp.as<float>();
-            a.math = MATH_BF16X3;
             a.in_len_host = t->in_len;
             launch_rb_conv(a, nullptr);
             HIP_CHECK(hipDeviceSynchronize());
         } else if (t->impl == 1 || t->impl == 2) {
-            if (!conv1d_mfma_supported(t->Cin, t->Cout, t->K, t->dilation)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
             packed.resize(mfma_packed_floats(t->Cout, t->Cin, t->K));
             pack_conv_weights_mfma(t->w, t->Cout, t->Cin, t->K, packed.data());
             DevBuf dp(packed.size() * 4);
@@ -85,14 +153,12 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
             a.w = dp.as<float>();
             std::vector<uint32_t> b3;
             std::unique_ptr<DevBuf> db3;
-            if (t->impl == 2) {  // split-bf16 staged kernel (MATH_BF16X3)
-                if (!conv1d_b3_supported(t->Cin, t->Cout, t->K, t->dilation, t->T)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the split-bf16 kernel");
+            if (t->impl == 2) {  // split-bf16 staged kernel (MATH_BF16X3 / MATH_BF16W)
                 b3.resize(bf16x3_packed_words_mode(t->Cout, t->Cin, t->K, EPI_STD));
                 pack_conv_weights_bf16x3_mode(t->w, t->Cout, t->Cin, t->K, EPI_STD, 1, b3.data());
                 db3.reset(new DevBuf(b3.size() * 4));
                 HIP_CHECK(hipMemcpy(db3->p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
                 a.wb3 = db3->as<float>();
-                a.math = MATH_BF16X3;
             }
             launch_conv1d_mfma(a, nullptr);
             HIP_CHECK(hipDeviceSynchronize());
@@ -104,6 +170,121 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
         }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(t->y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_conv_plan(int impl, int B, int Cin, int Cout, int T, int K, int dilation, int stride, int math, int fixed_rule,
+                            int has_res, int has_cond, const int32_t* len, mi355vits_conv_plan* out) {
+    return guarded(nullptr, [&] {
+        if (!out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        ConvPlan p;
+        if (stride > 0) {
+            convt_hook_check(impl, B, Cin, Cout, T, K, stride, len != nullptr);
+            check_lens(len, B, T, "in_len out of range");
+            if (impl == 0) {
+                ConvTArgs a;
+                a.B = B; a.Cin = Cin; a.Cout = Cout; a.Tin = T; a.K = K; a.stride = stride; a.pad = (K - stride) / 2;
+                p = conv_transpose1d_plan(a);
+            } else {
+                ConvArgs u = convt_hook_args(impl, B, Cin, Cout, T, K, stride);
+                u.x = u.w = u.bias = ALIGNED;
+                u.y = const_cast<float*>(ALIGNED);
+                if (impl == 2) u.wb3 = ALIGNED;
+                if (impl == 3) {
+                    std::vector<int> lens = len ? std::vector<int>(len, len + B) : std::vector<int>((size_t)B, T);
+                    u.in_len = reinterpret_cast<const int*>(ALIGNED);
+                    u.in_len_host = lens.data();
+                    if (!ups_pl_supported(u)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input polyphase kernels");
+                    p = ups_pl_plan(u);
+                } else {
+                    p = conv1d_mfma_plan(u);
+                }
+            }
+        } else {
+            const ConvHookOpts o{false, has_res != 0, has_cond != 0, len != nullptr, false, false, false, false, false, 1.0f};
+            ConvArgs a = conv_hook_args(impl, B, Cin, Cout, T, K, dilation, math, fixed_rule, o);
+            check_lens(len, B, T, "in_len out of range");
+            a.x = a.w = ALIGNED;
+            a.y = const_cast<float*>(ALIGNED);
+            if (has_res) a.res = ALIGNED;
+            if (has_cond) a.cond = ALIGNED;
+            if (impl >= 2) a.wb3 = ALIGNED;
+            if (len) { a.in_len = reinterpret_cast<const int*>(ALIGNED); a.in_len_host = len; }
+            p = impl == 0 ? conv1d_generic_plan(a) : impl <= 2 ? conv1d_mfma_plan(a) : impl == 3 ? enc_conv_b3_plan(a) : rb_conv_plan(a);
+        }
+        out->kernel = p.kernel; out->cols = p.cols; out->rows = p.rows;
+        out->MT = p.MT; out->NT = p.NT; out->WM = p.WM; out->WN = p.WN;
+        out->chunk = p.chunk; out->ring = p.ring; out->rb_loop = p.rb_loop;
+        out->vec = p.vec; out->yvec = p.yvec; out->ovec = p.ovec;
+        out->grid[0] = (int32_t)p.gx; out->grid[1] = (int32_t)p.gy; out->grid[2] = (int32_t)p.gz;
+        out->lds_bytes = (int32_t)p.shmem;
+    });
+}
+
+int mi355vits_test_enc_o_ln(int device, int math, int B, int T, const float* x, const float* w, const float* bias, const float* res,
+                            const float* gamma, const float* beta, float eps, const int32_t* in_len, const int32_t* ln_out_len,
+                            int in_place, float* y) {
+    return guarded(nullptr, [&] {
+        if (!x || !w || !res || !gamma || !beta || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || (size_t)B * 192 * T >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if (math != MATH_BF16X3 && math != MATH_BF16W) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_BF16X3 or MATH_BF16W");
+        check_lens(in_len, B, T, "in_len out of range");
+        check_lens(ln_out_len, B, T, "ln_out_len out of range");
+        const int C = 192;
+        if (!enc_o_ln_supported(C, C, 1)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t n = (size_t)B * C * T;
+        std::vector<uint32_t> b3(bf16x3_packed_words_mode(C, C, 1, EPI_STD));
+        pack_conv_weights_bf16x3_mode(w, C, C, 1, EPI_STD, 1, b3.data());
+        DevBuf dx(n * 4), dres(n * 4), dy(n * 4), db3(b3.size() * 4), db(C * 4), dg(C * 4), dbt(C * 4), dil((size_t)B * 4), dol((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dres.p, res, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(db3.p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dg.p, gamma, C * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dbt.p, beta, C * 4, hipMemcpyHostToDevice));
+        ConvArgs c;
+        c.x = dx.as<float>(); c.x_bs = (long)C * T; c.x_ld = T;
+        c.res = dres.as<float>(); c.res_bs = (long)C * T; c.res_ld = T;
+        c.y = in_place ? dres.as<float>() : dy.as<float>(); c.y_bs = (long)C * T; c.y_ld = T;
+        c.wb3 = db3.as<float>();
+        c.math = math;
+        c.B = B; c.Cin = C; c.Cout = C; c.T = T; c.K = 1; c.dil = 1; c.pad = 0;
+        if (bias) { HIP_CHECK(hipMemcpy(db.p, bias, C * 4, hipMemcpyHostToDevice)); c.bias = db.as<float>(); }
+        if (in_len) { HIP_CHECK(hipMemcpy(dil.p, in_len, (size_t)B * 4, hipMemcpyHostToDevice)); c.in_len = dil.as<int>(); }
+        const int* dout = nullptr;
+        if (ln_out_len) { HIP_CHECK(hipMemcpy(dol.p, ln_out_len, (size_t)B * 4, hipMemcpyHostToDevice)); dout = dol.as<int>(); }
+        launch_enc_o_ln(c, dg.as<float>(), dbt.as<float>(), dout, eps, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(y, in_place ? dres.p : dy.p, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_conv_post(int device, int B, int Cin, int K, int L, const float* x, const float* w, const int32_t* valid_len,
+                             const double* volumes, float* audio, float* peaks, int16_t* pcm, int32_t* kernel) {
+    return guarded(nullptr, [&] {
+        if (!x || !w || !valid_len || !audio || !peaks || !pcm) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || Cin < 1 || K < 1 || !(K & 1) || L < 1 || (size_t)B * Cin * L >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        check_lens(valid_len, B, L, "valid_len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nx = (size_t)B * Cin * L, na = (size_t)B * L;
+        DevBuf dx(nx * 4), dw((size_t)Cin * K * 4), dl((size_t)B * 4), dv((size_t)B * 8), da(na * 4), dp((size_t)B * 4), dq(na * 2);
+        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dw.p, w, (size_t)Cin * K * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, valid_len, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (volumes) HIP_CHECK(hipMemcpy(dv.p, volumes, (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, pcm, na * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));  // the peaks are an atomic maximum over bit patterns: zeroed before the launch, as the engine does
+        if (kernel) *kernel = conv_post_kernel(dx.as<float>(), (long)Cin * L, L, Cin, K, da.as<float>(), L);
+        launch_conv_post_tanh(dx.as<float>(), (long)Cin * L, L, dw.as<float>(), Cin, K, B, L, dl.as<int>(), da.as<float>(), L, dp.as<unsigned>(), nullptr);
+        launch_pcm16(da.as<float>(), L, dp.as<unsigned>(), dl.as<int>(), B, L, dq.as<int16_t>(), L, nullptr, volumes ? dv.as<double>() : nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(audio, da.p, na * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(pcm, dq.p, na * 2, hipMemcpyDeviceToHost));
     });
 }
 
@@ -470,13 +651,13 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
                                     const float* x, const float* w, const float* bias, float in_slope, const int32_t* in_len, float* y) {
     return guarded(nullptr, [&] {
         if (!x || !w || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
-        if (in_len && impl != 3) throw EngineError(MI355VITS_ERR_INVALID, "per-row lengths: impl 3 only");
-        for (int b = 0; in_len && b < B; ++b)
-            if (in_len[b] < 0 || in_len[b] > Tin) throw EngineError(MI355VITS_ERR_INVALID, "in_len out of range");
+        convt_hook_check(impl, B, Cin, Cout, Tin, K, stride, in_len != nullptr);
+        check_lens(in_len, B, Tin, "in_len out of range");
         HIP_CHECK(hipSetDevice(device));
         const size_t nx = (size_t)B * Cin * Tin, ny = (size_t)B * Cout * Tin * stride, nw = (size_t)Cin * Cout * K;
         DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(Cout * 4);
         HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));  // a position no kernel writes keeps the caller's value
         if (impl == 3) {
             // the resident-input polyphase kernels (k_ups_pl: 256 -> 128, 128 -> 64; k_ups64: 64 -> 32), MATH_BF16X3; a valid length per
             // row is part of their contract (the engine always has one): in_len, or every row at full length
@@ -490,15 +671,11 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
             HIP_CHECK(hipMemcpy(dpp.p, pp.data(), pp.size() * 4, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dbias.p, bv.data(), bv.size() * 4, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dlen.p, lens.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-            ConvArgs u;
-            u.x = dx.as<float>(); u.x_bs = (long)Cin * Tin; u.x_ld = Tin;
-            u.y = dy.as<float>(); u.y_bs = (long)Cout * Tin * stride; u.y_ld = Tin * stride;
+            ConvArgs u = convt_hook_args(impl, B, Cin, Cout, Tin, K, stride);
+            u.x = dx.as<float>();
+            u.y = dy.as<float>();
             u.w = dpp.as<float>(); u.bias = dbias.as<float>(); u.in_len = dlen.as<int>(); u.in_len_host = lens.data();
-            u.Cin = Cin; u.Cout = stride * Cout; u.K = taps; u.dil = 1;
-            u.in_slope = in_slope; u.pad = taps - 1; u.Tin = Tin;
-            u.shuf_s = stride; u.shuf_p = (K - stride) / 2; u.shuf_cout = Cout; u.shuf_T = Tin * stride;
-            u.B = B; u.T = Tin + taps - 1;
-            u.math = MATH_BF16X3;
+            u.in_slope = in_slope;
             if (!ups_pl_supported(u)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input polyphase kernels");
             launch_ups_pl(u, nullptr);
             HIP_CHECK(hipDeviceSynchronize());
@@ -508,31 +685,24 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
             const int taps = convt_taps(K, stride);
             std::vector<float> wv((size_t)stride * Cout * Cin * taps), bv((size_t)stride * Cout);
             convt_to_polyphase(w, bias, Cin, Cout, K, stride, wv.data(), bv.data());
-            if (!conv1d_mfma_supported(Cin, stride * Cout, taps, 1)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
             std::vector<float> pk(mfma_packed_floats(stride * Cout, Cin, taps));
             pack_conv_weights_mfma(wv.data(), stride * Cout, Cin, taps, pk.data());
             DevBuf dp(pk.size() * 4), dbias(bv.size() * 4);
             HIP_CHECK(hipMemcpy(dp.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(dbias.p, bv.data(), bv.size() * 4, hipMemcpyHostToDevice));
-            ConvArgs u;
-            u.x = dx.as<float>(); u.x_bs = (long)Cin * Tin; u.x_ld = Tin;
-            u.y = dy.as<float>(); u.y_bs = (long)Cout * Tin * stride; u.y_ld = Tin * stride;
+            ConvArgs u = convt_hook_args(impl, B, Cin, Cout, Tin, K, stride);
+            u.x = dx.as<float>();
+            u.y = dy.as<float>();
             u.w = dp.as<float>(); u.bias = dbias.as<float>();
-            u.Cin = Cin; u.Cout = stride * Cout; u.K = taps; u.dil = 1;
-            u.in_slope = in_slope; u.pad = taps - 1; u.Tin = Tin;
-            u.shuf_s = stride; u.shuf_p = (K - stride) / 2; u.shuf_cout = Cout; u.shuf_T = Tin * stride;
-            u.B = B; u.T = Tin + taps - 1;
+            u.in_slope = in_slope;
             std::vector<uint32_t> b3;
             std::unique_ptr<DevBuf> db3;
             if (impl == 2) {
-                if (!conv1d_b3_supported(Cin, stride * Cout, taps, 1, 1 << 30)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the split-bf16 kernel");
                 b3.resize(bf16x3_packed_words_mode(stride * Cout, Cin, taps, EPI_STD));
                 pack_conv_weights_bf16x3_mode(wv.data(), stride * Cout, Cin, taps, EPI_STD, 1, b3.data());
                 db3.reset(new DevBuf(b3.size() * 4));
                 HIP_CHECK(hipMemcpy(db3->p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
                 u.wb3 = db3->as<float>();
-                u.math = MATH_BF16X3;
-                u.fixed_rule = 1;
             }
             launch_conv1d_mfma(u, nullptr);
             HIP_CHECK(hipDeviceSynchronize());

@@ -235,6 +235,18 @@ class Twice:
     def test_wn_layer(self, *a, **k):
         return self._twice(self.lib.test_wn_layer, *a, **k)
 
+    def test_conv1d(self, *a, **k):
+        return self._twice(self.lib.test_conv1d, *a, **k)
+
+    def test_conv_transpose1d(self, *a, **k):
+        return self._twice(self.lib.test_conv_transpose1d, *a, **k)
+
+    def test_enc_o_ln(self, *a, **k):
+        return self._twice(self.lib.test_enc_o_ln, *a, **k)
+
+    def test_conv_post(self, *a, **k):
+        return self._twice(self.lib.test_conv_post, *a, **k)
+
 
 class Env:
     """Sets the lab switches the launchers read at every launch (lab build and CPU model) and puts the old values back."""
