@@ -408,6 +408,56 @@ typedef struct mi355vits_timing_args {
 int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
                         const mi355vits_timing_args* timing /* may be NULL */, mi355vits_result* out);
 
+/* ---- Blended and caller-supplied speakers per row.  On a multi-speaker voice the speaker is only a vector g of gin_channels
+ * floats: `sid` looks it up in the table emb_g, and every consumer of it (dp.cond, dec.cond, each flow's enc.cond_layer) is a 1x1
+ * projection of that vector.  mi355vits_run_speakers is mi355vits_run_timed with g of every row given as a blend of table rows
+ * ("70 % of speaker 12, 30 % of speaker 40", extrapolation such as 1.5 / -0.5 included) or as the caller's own vector (averaged,
+ * interpolated or fitted outside), per row of one batched call — no rewritten weight container with one more emb_g row and no
+ * second handle with a second weight replica per blend.  ONE kernel (k_speaker_cond_mix) makes g of all rows and every consumer's
+ * projection in ONE launch, in place of the 2 + flow_n_flows launches of the plain run; the tables ride in the run's one upload: no
+ * synchronisation and no host round trip more than the plain run.
+ * The rule, exact (no tolerance).  Per row b and channel i < gin_channels:
+ *  - Mix: the terms (mix_sid[b,k], mix_weight[b,k]), k = 0 .. n_terms - 1.  A term whose weight is exactly 0 (+0 or -0) is skipped: not
+ *    multiplied, its sid neither checked nor read — rows of one batch carry different term counts that way.  Over the remaining
+ *    terms, in order of k, with e_k = emb_g[mix_sid[b,k], :]:
+ *        g[i] = fl(w_0 * e_0[i]),   then   g[i] = fl(g[i] + fl(w_k * e_k[i]))
+ *    single IEEE f32 products and sums rounded to nearest, never a fused multiply-add.  A one-term mix of weight 1.0f gives g bitwise
+ *    the table row, -0.0 included.
+ *  - Vector: g[i] = vectors[b, i], bits in, bits out.
+ *  - Projections: every consumer's out[b, co] = W[co, :] . g + bias[co] is computed element for element as the plain run computes
+ *    it from a table row (per wave lane l: fmaf(W[co, i], g[i], acc) over i = l, l + 64, .. from 0.0f; a butterfly sum over the 64
+ *    lanes; + bias).  So:
+ *      * a speakers run is bitwise the plain run with sid = S on a voice whose emb_g carries that g as row S — audio, pcm, lengths, peaks;
+ *      * {s: 1.0} for every row, or vectors equal to mi355vits_get_speaker_embedding(s), is bitwise the plain run with sid = s;
+ *      * a row of a batch is bitwise the row alone (same noise key and tx_max class, see mi355vits_run_rows), and permuting the rows
+ *        of a batch permutes the results: nothing depends on the row block, the grid, the batch or an address.
+ *  - Scope: speakers == NULL: the call IS mi355vits_run_timed — the same launches, bytes and synchronisations.  With speakers,
+ *    args->sid may be NULL and is not read.  All flags work, MI355VITS_DEVICE_ONLY included; the packed, streams and alignment
+ *    forms need no call of their own: mi355vits_fetch_packed, _fetch_streams, _fetch_streams2 and mi355vits_fetch_alignment serve the
+ *    last completed run whatever made it.  rows and timing combine with speakers freely.  Under MI355VITS_DEBUG_TAPS a speakers run
+ *    also serves the tap "g" [B, gin_channels, 1].
+ *  - Errors, all MI355VITS_ERR_INVALID, raised before anything is launched (the previous run stays served): a single-speaker voice
+ *    ("voice has no speaker embedding"); mix_* together with vectors, or neither, or one of mix_sid / mix_weight alone; n_terms
+ *    outside 1 .. MI355VITS_MAX_SPEAKER_TERMS with mix_*, or not 0 with vectors; a sid outside the table at a non-zero weight (the
+ *    message names the row and the term); a weight that is not finite or beyond +-1024 (row and term); a vector value that is not
+ *    finite (row); a row whose every weight is 0 (row); a non-zero reserved field.
+ *  - With profiling enabled the kernel is reported as "speaker_cond.mix" in place of "speaker_cond". */
+#define MI355VITS_MAX_SPEAKER_TERMS 8
+typedef struct mi355vits_speaker_args {
+    int32_t        n_terms;     /* K, 1 .. MI355VITS_MAX_SPEAKER_TERMS with mix_*; 0 with vectors */
+    const int64_t* mix_sid;     /* [B, K] */
+    const float*   mix_weight;  /* [B, K] finite, |w| <= 1024; exactly 0 = term skipped */
+    const float*   vectors;     /* [B, gin_channels] finite; excludes mix_* */
+    int32_t        reserved[6]; /* must be 0 */
+} mi355vits_speaker_args;
+int mi355vits_run_speakers(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                           const mi355vits_timing_args* timing /* may be NULL */, const mi355vits_speaker_args* speakers /* may be NULL */,
+                           mi355vits_result* out);
+/* Row `sid` of the voice's speaker table emb_g -> out[0 .. gin_channels): copied from a host copy kept with the weights, no stream
+ * work, no synchronisation.  capacity = floats out can take.  A sid outside the table, capacity < gin_channels, a NULL out or a
+ * single-speaker voice: MI355VITS_ERR_INVALID. */
+int mi355vits_get_speaker_embedding(mi355vits_handle h, int64_t sid, float* out, size_t capacity);
+
 /* ---- Exact pauses: trim each entry's quiet edges in the packed streams.  A VITS voice puts a stretch of near-silence of its own at
  * the start and the end of every sentence; the reference adds its break (int(ms / 1000 * sample_rate) zero samples,
  * mimic3_tts/tts.py:452-465) on top of it, so a 250 ms break is heard as 250 ms plus two unknown tails.  With edge trimming on, an

@@ -315,6 +315,32 @@ int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const
  * not read there, nor in a row whose noise_scale is 0. */
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z);
+/* Kernel unit-test hook: launch_speaker_cond (k_speaker_cond, the plain run's conditioning) alone on host buffers: emb_g
+ * [n_speakers, gin], sid [B] (checked against the table), w [Cout, gin], bias [Cout] or NULL -> out [B, Cout].  out holds out_floats >=
+ * B * Cout floats: all of them go to the device first and come back, so a missing or a stray write shows. */
+int mi355vits_test_speaker_cond(int device, int B, int gin, int n_speakers, int Cout, const float* emb_g, const int64_t* sid,
+                                const float* w, const float* bias, float* out, size_t out_floats);
+/* Kernel unit-test hook: launch_speaker_cond_mix (k_speaker_cond_mix; include/mi355vits.h, blended and caller-supplied speakers)
+ * alone, ONE launch: the table emb_g [n_speakers, gin] with mix_sid / mix_weight [B, n_terms] (n_terms 1 .. 8; a sid at a non-zero
+ * weight is checked against the table, one at a zero weight may hold anything), or vectors [B, gin] with n_terms 0 and the other
+ * three NULL; n_jobs consumers (1 .. 10): w[q] [Cout[q], gin], bias[q] [Cout[q]] or NULL -> out[q] [B, Cout[q]], and g [B, gin].
+ * out[q] holds out_floats[q] >= B * Cout[q] floats and g holds g_floats >= B * gin: all of them go to the device first and come
+ * back, so a missing or a stray write shows.  A row whose every weight is 0 is served with g = 0 (the product refuses it earlier). */
+typedef struct mi355vits_speaker_mix_test {
+    int32_t B, gin, n_speakers, n_terms, n_jobs;
+    const float* emb_g;
+    const int64_t* mix_sid;
+    const float* mix_weight;
+    const float* vectors;
+    const float* w[10];
+    const float* bias[10];
+    int32_t Cout[10];
+    float* out[10];
+    size_t out_floats[10];
+    float* g;
+    size_t g_floats;
+} mi355vits_speaker_mix_test;
+int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test* t);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
  * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
  * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros

@@ -32,7 +32,8 @@ HOOKS_LIBRARY = os.path.join(_HERE, "csrc", "libmi355vits_hooks.so")
 EXPORTED_SYMBOLS = (
     "mi355vits_version", "mi355vits_device_count", "mi355vits_create", "mi355vits_create_from_buffer", "mi355vits_clone", "mi355vits_destroy",
     "mi355vits_device_result", "mi355vits_set_math", "mi355vits_get_math",
-    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_fetch", "mi355vits_free_result",
+    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_run_speakers",
+    "mi355vits_get_speaker_embedding", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
     "mi355vits_run_packed", "mi355vits_fetch_packed", "mi355vits_free_packed",
@@ -56,7 +57,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
-    "mi355vits_test_fit_durations",
+    "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix",
     "mi355vits_lab_conv_plan", "mi355vits_test_enc_o_ln", "mi355vits_test_conv_post",
 )
 
@@ -131,6 +132,66 @@ class TimingArgs(ctypes.Structure):  # mi355vits_timing_args
         ("factor_out", ctypes.POINTER(ctypes.c_float)),
         ("reserved", ctypes.c_int32 * 6),
     ]
+
+
+class SpeakerArgs(ctypes.Structure):  # mi355vits_speaker_args
+    _fields_ = [
+        ("n_terms", ctypes.c_int32),
+        ("mix_sid", ctypes.POINTER(ctypes.c_int64)),
+        ("mix_weight", ctypes.POINTER(ctypes.c_float)),
+        ("vectors", ctypes.POINTER(ctypes.c_float)),
+        ("reserved", ctypes.c_int32 * 6),
+    ]
+
+
+MAX_SPEAKER_TERMS = 8  # MI355VITS_MAX_SPEAKER_TERMS
+
+
+class SpeakerMixTest(ctypes.Structure):  # mi355vits_speaker_mix_test (include/mi355vits_lab.h)
+    _fields_ = [
+        ("B", ctypes.c_int32), ("gin", ctypes.c_int32), ("n_speakers", ctypes.c_int32), ("n_terms", ctypes.c_int32),
+        ("n_jobs", ctypes.c_int32),
+        ("emb_g", ctypes.POINTER(ctypes.c_float)),
+        ("mix_sid", ctypes.POINTER(ctypes.c_int64)),
+        ("mix_weight", ctypes.POINTER(ctypes.c_float)),
+        ("vectors", ctypes.POINTER(ctypes.c_float)),
+        ("w", ctypes.POINTER(ctypes.c_float) * 10),
+        ("bias", ctypes.POINTER(ctypes.c_float) * 10),
+        ("Cout", ctypes.c_int32 * 10),
+        ("out", ctypes.POINTER(ctypes.c_float) * 10),
+        ("out_floats", ctypes.c_size_t * 10),
+        ("g", ctypes.POINTER(ctypes.c_float)),
+        ("g_floats", ctypes.c_size_t),
+    ]
+
+
+def speaker_tables(speakers, n_rows: int, gin: int):
+    """``speakers`` (one entry per row: an ``int`` = that speaker as a one-term mix of weight 1, a dict ``{sid: weight}``, or a 1-D
+    float array of ``gin`` values) as the tables of ``mi355vits_speaker_args``: ``("mix", sid [B, K] int64, weight [B, K] float32)``
+    — dicts and ints padded with zero-weight terms to the longest row, a dict's terms in its own order — or ``("vectors", v [B,
+    gin] float32)``.  Entries of both kinds in one call raise ``ValueError``: the ABI takes one kind per call."""
+    speakers = list(speakers)
+    if len(speakers) != n_rows:
+        raise ValueError("speakers must have one entry per row")
+    is_mix = [isinstance(e, (dict, int, np.integer)) and not isinstance(e, bool) for e in speakers]
+    if all(is_mix):
+        rows = [list(e.items()) if isinstance(e, dict) else [(int(e), 1.0)] for e in speakers]
+        K = max(len(r) for r in rows)
+        if K < 1:
+            raise ValueError("a speaker mix needs at least one term")
+        if K > MAX_SPEAKER_TERMS:
+            raise ValueError(f"a speaker mix takes at most {MAX_SPEAKER_TERMS} terms")
+        sid, w = np.zeros((n_rows, K), np.int64), np.zeros((n_rows, K), np.float32)
+        for b, r in enumerate(rows):
+            for k, (s, x) in enumerate(r):
+                sid[b, k], w[b, k] = int(s), np.float32(x)
+        return "mix", sid, w
+    if any(is_mix):
+        raise ValueError("speakers: mixes (int / dict) and vectors go in calls of their own")
+    v = [np.asarray(e, np.float32) for e in speakers]
+    if any(e.shape != (gin,) for e in v):
+        raise ValueError("a speaker vector must be a 1-D array of gin_channels values")
+    return "vectors", np.ascontiguousarray(np.stack(v), dtype=np.float32)
 
 
 class Result(ctypes.Structure):
@@ -476,6 +537,9 @@ class NativeLibrary:
         L.mi355vits_run.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(Result)]
         L.mi355vits_run_rows.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(Result)]
         L.mi355vits_run_timed.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs), ctypes.POINTER(Result)]
+        L.mi355vits_run_speakers.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs),
+                                             ctypes.POINTER(SpeakerArgs), ctypes.POINTER(Result)]
+        L.mi355vits_get_speaker_embedding.argtypes = [H, ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
@@ -586,6 +650,8 @@ class NativeLibrary:
             L.mi355vits_test_dds_stack.argtypes = [ctypes.c_int, ctypes.POINTER(DdsStackTest)]
             L.mi355vits_test_spline_inverse.argtypes = [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, f32p, i32p, f32p]
             L.mi355vits_test_fit_durations.argtypes = [ctypes.c_int] * 3 + [f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p]
+            L.mi355vits_test_speaker_cond.argtypes = [ctypes.c_int] * 5 + [f32p, ctypes.POINTER(ctypes.c_int64), f32p, f32p, f32p, ctypes.c_size_t]
+            L.mi355vits_test_speaker_cond_mix.argtypes = [ctypes.c_int, ctypes.POINTER(SpeakerMixTest)]
             L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
             L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
 
@@ -1089,6 +1155,58 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return frames, cum, ylen, factor, status
 
+    def test_speaker_cond(self, emb_g, sid, w, bias=None, pad: int = 8, device=0) -> np.ndarray:
+        """launch_speaker_cond (k_speaker_cond) alone: emb_g [S, gin], sid [B], w [Cout, gin], bias [Cout] or None -> out, B * Cout
+        + ``pad`` floats that start as -7.5e29 (mi355vits_test_speaker_cond): ``out[:B * Cout].reshape(B, Cout)`` is the result."""
+        self._need_hooks()
+        emb_g, w = np.ascontiguousarray(emb_g, np.float32), np.ascontiguousarray(w, np.float32)
+        sid = np.ascontiguousarray(sid, np.int64).reshape(-1)
+        bias = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        (S, gin), Cout, B = emb_g.shape, w.shape[0], sid.shape[0]
+        assert w.shape == (Cout, gin) and (bias is None or bias.shape == (Cout,))
+        out = np.full(B * Cout + pad, -7.5e29, np.float32)
+        rc = self.lib.mi355vits_test_speaker_cond(device, B, gin, S, Cout, _fptr(emb_g), sid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                  _fptr(w), None if bias is None else _fptr(bias), _fptr(out), out.size)
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out
+
+    def test_speaker_cond_mix(self, consumers, emb_g=None, sid=None, weight=None, vectors=None, pad: int = 8, device=0):
+        """launch_speaker_cond_mix (k_speaker_cond_mix) alone, one launch: ``consumers`` = [(w [Cout, gin], bias [Cout] or None)],
+        with emb_g [S, gin], sid / weight [B, K], or vectors [B, gin] -> (g, [out per consumer]): flat arrays of B * gin and B * Cout
+        floats + ``pad`` floats each, which start as -7.5e29 (mi355vits_test_speaker_cond_mix)."""
+        self._need_hooks()
+        t, keep = SpeakerMixTest(), []
+        if vectors is not None:
+            vectors = np.ascontiguousarray(vectors, np.float32)
+            B, gin = vectors.shape
+            t.vectors = _fptr(vectors)
+        else:
+            emb_g, weight = np.ascontiguousarray(emb_g, np.float32), np.ascontiguousarray(weight, np.float32)
+            sid = np.ascontiguousarray(sid, np.int64)
+            (B, K), gin = weight.shape, emb_g.shape[1]
+            assert sid.shape == (B, K)
+            t.n_speakers, t.n_terms = emb_g.shape[0], K
+            t.emb_g, t.mix_weight, t.mix_sid = _fptr(emb_g), _fptr(weight), sid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        t.B, t.gin, t.n_jobs = B, gin, len(consumers)
+        outs = []
+        for q, (w, bias) in enumerate(consumers):
+            w = np.ascontiguousarray(w, np.float32)
+            assert w.ndim == 2 and w.shape[1] == gin
+            bias = None if bias is None else np.ascontiguousarray(bias, np.float32)
+            out = np.full(B * w.shape[0] + pad, -7.5e29, np.float32)
+            keep += [w, bias]
+            outs.append(out)
+            t.w[q], t.Cout[q], t.out[q], t.out_floats[q] = _fptr(w), w.shape[0], _fptr(out), out.size
+            if bias is not None:
+                t.bias[q] = _fptr(bias)
+        g = np.full(B * gin + pad, -7.5e29, np.float32)
+        t.g, t.g_floats = _fptr(g), g.size
+        rc = self.lib.mi355vits_test_speaker_cond_mix(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return g, outs
+
     def test_expand_prior(self, stats, cum, ylen, Ty, noise_scale=0.0, injected=None, z_prior=None, device=0) -> np.ndarray:
         """launch_expand_prior alone with injected noise: stats [B, 2 I, Tx], cum [B, Tx], ylen [B], noise_scale a number or [B],
         injected [B, I, frames >= Ty] or None -> z [B, I, Ty] (mi355vits_test_expand_prior)."""
@@ -1341,33 +1459,66 @@ class Engine:
     def run(self, ids, lengths, scales, sid=None, *, seed: int = 0, utterance_base: int = 0, noise_w=None,
             noise_z=None, forced_durations=None, want_float: bool = True, want_pcm16: bool = False,
             device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None,
-            stretch=None, min_frames=None, target_frames=None) -> Dict[str, np.ndarray]:
+            stretch=None, min_frames=None, target_frames=None, speakers=None) -> Dict[str, np.ndarray]:
         """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
         ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
         its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class).
         Timing (``mi355vits_run_timed``, when any of the three is given): ``stretch`` [B, Tx] duration multiplier per phoneme,
         ``min_frames`` [B, Tx] frames a phoneme is held at least, ``target_frames`` [B] the row's latent frames (0 = none); the
-        result then carries ``"timing_factor"`` [B], the factor s* every row was fitted with (1.0 without a target)."""
+        result then carries ``"timing_factor"`` [B], the factor s* every row was fitted with (1.0 without a target).
+        ``speakers`` (``mi355vits_run_speakers``; a multi-speaker voice): one entry per row in place of ``sid``, which is then not
+        read — an ``int`` (that speaker), a dict ``{sid: weight}`` (a blend, terms in the dict's order; weights need not sum to 1) or
+        a 1-D float array of ``gin_channels`` values (the caller's own vector); ints and dicts may be mixed in one call, vectors go
+        in a call of their own (``ValueError`` otherwise).  ``SpeakerArgs`` itself is taken as it is."""
         timing, tkeep = self._timing_args(np.shape(ids), stretch, min_frames, target_frames)
+        spk, skeep = self._speaker_args(np.shape(ids), speakers)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
                   (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         r = Result()
-        if timing is not None:
+        if spk is not None:
+            self._check(self.native.lib.mi355vits_run_speakers(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                               ctypes.byref(timing) if timing is not None else None,
+                                                               ctypes.byref(spk), ctypes.byref(r)))
+        elif timing is not None:
             self._check(self.native.lib.mi355vits_run_timed(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                             ctypes.byref(timing), ctypes.byref(r)))
         elif per_row:
             self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
         else:
             self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
-        del keep
+        del keep, skeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate  # read when the run started; only this thread sets it meanwhile
         out = self._take(r)
         if timing is not None:
             out["timing_factor"] = tkeep[-1]
         return out
+
+    def _speaker_args(self, shape, speakers):
+        """``mi355vits_speaker_args`` (or None without ``speakers``) + the arrays it points into (``speaker_tables``)."""
+        if speakers is None:
+            return None, []
+        if isinstance(speakers, SpeakerArgs):
+            return speakers, []
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        tab = speaker_tables(speakers, shape[0], int(self.config.gin_channels))
+        s = SpeakerArgs()
+        if tab[0] == "mix":
+            s.n_terms = tab[1].shape[1]
+            s.mix_sid, s.mix_weight = tab[1].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _fptr(tab[2])
+        else:
+            s.vectors = _fptr(tab[1])
+        return s, list(tab[1:])
+
+    def speaker_embedding(self, sid: int) -> np.ndarray:
+        """Row ``sid`` of the voice's speaker table ``emb_g`` [gin_channels] (``mi355vits_get_speaker_embedding``: a host copy, no
+        stream work) — the vector ``run(..., speakers=[sid])`` speaks with, to average, interpolate or fit from."""
+        out = np.empty(max(int(self.config.gin_channels), 1), np.float32)
+        self._check(self.native.lib.mi355vits_get_speaker_embedding(self._h, int(sid), _fptr(out), out.size))
+        return out[: int(self.config.gin_channels)]
 
     @staticmethod
     def _timing_args(shape, stretch, min_frames, target_frames):
@@ -1502,7 +1653,7 @@ class Engine:
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
                    debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE,
-                   stretch=None, min_frames=None, target_frames=None) -> PackedAudio:
+                   stretch=None, min_frames=None, target_frames=None, speakers=None) -> PackedAudio:
         """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
         ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
@@ -1512,14 +1663,15 @@ class Engine:
         setting is put back afterwards); with FLAC the result's ``.flac`` is the file and ``wav=True`` raises ``ValueError``.
         With any of ``stretch`` / ``min_frames`` / ``target_frames`` (see ``run``): a timed run that keeps its audio on the device
         (``mi355vits_run_timed`` with ``MI355VITS_DEVICE_ONLY``), then ``fetch_packed`` of it — one synchronisation more; the
-        factors are left in ``last_timing_factor``."""
-        if stretch is not None or min_frames is not None or target_frames is not None:
+        factors are left in ``last_timing_factor``.  ``speakers`` (see ``run``) goes the same way: a speakers run that keeps its
+        audio on the device, then ``fetch_packed``."""
+        if stretch is not None or min_frames is not None or target_frames is not None or speakers is not None:
             comp = self._call_compression(compression, wav)  # refuses wav + FLAC before anything runs
             res = self.run(ids, lengths, scales, sid, seed=seed, utterance_base=utterance_base, noise_w=noise_w, noise_z=noise_z,
                            forced_durations=forced_durations, want_float=False, want_pcm16=False, device_only=True,
                            debug_taps=debug_taps, pcm_volume=pcm_volume, utterance_keys=utterance_keys, stretch=stretch,
-                           min_frames=min_frames, target_frames=target_frames)
-            self.last_timing_factor = res["timing_factor"]
+                           min_frames=min_frames, target_frames=target_frames, speakers=speakers)
+            self.last_timing_factor = res.get("timing_factor", self.last_timing_factor)
             return self.fetch_packed(order=order, lead_samples=lead_samples, tail_samples=tail_samples, wav=wav, compression=compression)
         comp = self._call_compression(compression, wav)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,

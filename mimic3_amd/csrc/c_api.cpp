@@ -176,6 +176,20 @@ int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, cons
     });
 }
 
+int mi355vits_run_speakers(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                           const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers, mi355vits_result* out) {
+    return result_call(h, out, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        h->eng->run(*args, rows, out, timing, speakers);
+    });
+}
+
+int mi355vits_get_speaker_embedding(mi355vits_handle h, int64_t sid, float* out, size_t capacity) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return guarded(h, [&] { h->eng->speaker_embedding(sid, out, capacity); });
+}
+
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out) {
     return result_call(h, out, [&] { h->eng->fetch(want_flags, out); });
 }

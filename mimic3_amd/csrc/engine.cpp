@@ -659,6 +659,8 @@ void Engine::construct(const WeightsFile& wf, int device) {
         add_vec(wf, "dec.cond.weight", {C0, gin, 1});
         add_vec(wf, "dec.cond.bias", {C0});
         add_vec(wf, "emb_g.weight", {c.n_speakers, gin});
+        const HostTensor& e = wf.get("emb_g.weight", {c.n_speakers, gin});
+        model_->emb_g.assign(e.data, e.data + e.count);  // mi355vits_get_speaker_embedding serves table rows without stream work
     }
 
     // ---- one upload
@@ -1499,7 +1501,7 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
 // =================================================================================================
 // The sequence of alloc calls below IS the workspace layout: run() plays it against an ArenaCount for the size to reserve, then
 // against the arena for the pointers.
-template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing) {
+template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing, int speakers) {
     const mi355vits_config& c = cfg_;
     const size_t H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels, fBT = B * Tx;
     const size_t nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
@@ -1516,6 +1518,11 @@ template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool for
     d_stretch_ = (timing & 1) ? ar.template alloc<float>(fBT) : nullptr;
     d_minf_ = (timing & 2) ? ar.template alloc<int>(fBT) : nullptr;
     d_target_ = (timing & 4) ? ar.template alloc<int>(B) : nullptr;
+    const bool cond = c.n_speakers > 1 && c.gin_channels;
+    const size_t spk_terms = speakers > 0 ? speakers : (speakers == -2 ? MI355VITS_MAX_SPEAKER_TERMS : 0);
+    d_mix_sid_ = (cond && spk_terms) ? ar.template alloc<long long>(B * spk_terms) : nullptr;
+    d_mix_w_ = (cond && spk_terms) ? ar.template alloc<float>(B * spk_terms) : nullptr;
+    d_spk_vec_ = (cond && (speakers == -1 || speakers == -2)) ? ar.template alloc<float>(B * c.gin_channels) : nullptr;
     // what the host reads at the run's one sizing synchronisation: ylen, and of a timed run status and factor, in ONE copy (4-byte
     // words side by side: each of the three is B words)
     d_ylen_ = ar.template alloc<int>(3 * B);
@@ -1540,7 +1547,7 @@ template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool for
     d_theta_ = ar.template alloc<float>(fBT * nth);
     d_z2_ = ar.template alloc<float>(fBT * 2);
     d_logw_ = ar.template alloc<float>(fBT);
-    const bool cond = c.n_speakers > 1 && c.gin_channels;
+    d_g_ = (cond && speakers) ? ar.template alloc<float>(B * c.gin_channels) : nullptr;
     d_cond_dp_ = cond ? ar.template alloc<float>(B * H) : nullptr;
     d_cond_dec_ = cond ? ar.template alloc<float>(B * c.upsample_initial_channel) : nullptr;
     d_cond_flow_.clear();
@@ -1577,22 +1584,106 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
 }
 
 void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
-                 const mi355vits_timing_args* timing) {
+                 const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers) {
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
-    synthesize(args, rows, nullptr, timing);
+    synthesize(args, rows, nullptr, timing, speakers);
     copy_out(args.flags, out);
 }
 
+void Engine::speaker_embedding(int64_t sid, float* out, size_t capacity) const {
+    const mi355vits_config& c = cfg_;
+    if (c.n_speakers <= 1 || model_->emb_g.empty()) throw EngineError(MI355VITS_ERR_INVALID, "voice has no speaker embedding");
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "out must not be null");
+    if (sid < 0 || sid >= c.n_speakers)
+        throw EngineError(MI355VITS_ERR_INVALID, "speaker id " + std::to_string(sid) + " out of range (the voice has " + std::to_string(c.n_speakers) + " speakers)");
+    if (capacity < (size_t)c.gin_channels)
+        throw EngineError(MI355VITS_ERR_INVALID, "capacity of " + std::to_string(capacity) + " floats is below gin_channels = " + std::to_string(c.gin_channels));
+    memcpy(out, model_->emb_g.data() + (size_t)sid * c.gin_channels, (size_t)c.gin_channels * sizeof(float));
+}
+
+// A speakers run's validation (mi355vits_speaker_args; everything is refused before a launch): what layout_a takes as `speakers`
+static int check_speakers(const mi355vits_config& c, const mi355vits_speaker_args& sp, int B) {
+    for (int i = 0; i < 6; ++i)
+        if (sp.reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "speakers: reserved fields must be 0");
+    if (c.n_speakers <= 1 || c.gin_channels < 1) throw EngineError(MI355VITS_ERR_INVALID, "speakers: voice has no speaker embedding");
+    const bool mix = sp.mix_sid || sp.mix_weight;
+    if (mix && sp.vectors) throw EngineError(MI355VITS_ERR_INVALID, "speakers: mix_sid / mix_weight and vectors exclude each other");
+    if (!mix && !sp.vectors) throw EngineError(MI355VITS_ERR_INVALID, "speakers: give mix_sid and mix_weight, or vectors");
+    const int gin = c.gin_channels;
+    if (!mix) {
+        if (sp.n_terms != 0) throw EngineError(MI355VITS_ERR_INVALID, "speakers: n_terms must be 0 with vectors");
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < gin; ++i)
+                if (!std::isfinite(sp.vectors[(size_t)b * gin + i]))
+                    throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": speaker vector must be finite (channel " + std::to_string(i) + ")");
+        return -1;
+    }
+    if (!sp.mix_sid || !sp.mix_weight) throw EngineError(MI355VITS_ERR_INVALID, "speakers: mix_sid and mix_weight go together");
+    const int K = sp.n_terms;
+    if (K < 1 || K > MI355VITS_MAX_SPEAKER_TERMS)
+        throw EngineError(MI355VITS_ERR_INVALID, "speakers: n_terms must be within 1 .. " + std::to_string(MI355VITS_MAX_SPEAKER_TERMS));
+    for (int b = 0; b < B; ++b) {
+        bool any = false;
+        for (int k = 0; k < K; ++k) {
+            const float w = sp.mix_weight[(size_t)b * K + k];
+            const std::string where = "row " + std::to_string(b) + ", term " + std::to_string(k);
+            if (!std::isfinite(w) || std::fabs(w) > 1024.0f) throw EngineError(MI355VITS_ERR_INVALID, where + ": speaker weight must be finite and within -1024 .. 1024");
+            if (w == 0.0f) continue;  // a skipped term: its sid is not looked at
+            any = true;
+            const int64_t s = sp.mix_sid[(size_t)b * K + k];
+            if (s < 0 || s >= c.n_speakers)
+                throw EngineError(MI355VITS_ERR_INVALID, where + ": speaker id " + std::to_string(s) + " out of range (the voice has " + std::to_string(c.n_speakers) + " speakers)");
+        }
+        if (!any) throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": every speaker weight is 0");
+    }
+    return K;
+}
+
+void Engine::speaker_cond_mix(int B, int spk) {
+    const mi355vits_config& c = cfg_;
+    const int H = c.hidden_channels, gin = c.gin_channels;
+    SpeakerMixArgs m;
+    m.B = B; m.gin = gin; m.g = d_g_;
+    if (spk > 0) {
+        m.emb_g = vec("emb_g.weight"); m.sid = d_mix_sid_; m.weight = d_mix_w_; m.K = spk;
+    } else {
+        m.vectors = d_spk_vec_;
+    }
+    std::vector<SpeakerMixJob> jobs;
+    auto job = [&](const std::string& name, int Cout, float* out) {
+        SpeakerMixJob j;
+        j.w = vec(name + ".weight"); j.bias = vec(name + ".bias"); j.Cout = Cout; j.out = out;
+        jobs.push_back(j);
+    };
+    job("dp.cond", H, d_cond_dp_);
+    job("dec.cond", c.upsample_initial_channel, d_cond_dec_);
+    for (int j = 0; j < c.flow_n_flows; ++j) job(S("flow.flows.%d", 2 * j) + ".enc.cond_layer", 2 * H * c.flow_wn_layers, d_cond_flow_[j]);
+    // one launch (a voice with more than SPEAKER_MIX_MAX_JOBS - 2 flows: one per table-full)
+    for (size_t q0 = 0; q0 < jobs.size(); q0 += SPEAKER_MIX_MAX_JOBS) {
+        m.n_jobs = (int)std::min<size_t>(SPEAKER_MIX_MAX_JOBS, jobs.size() - q0);
+        double couts = 0;
+        for (int q = 0; q < m.n_jobs; ++q) {
+            m.jobs[q] = jobs[q0 + q];
+            couts += m.jobs[q].Cout;
+        }
+        // the weights once, the tables (K gin table values or gin vector values per row), the outputs
+        const double bytes = 4.0 * couts * (gin + 1) + 4.0 * B * (double)(spk > 0 ? spk : 1) * gin + 4.0 * B * couts;
+        ProfScope ps(prof_, "speaker_cond.mix", 2.0 * B * couts * gin, bytes);
+        launch_speaker_cond_mix(m, stream_);
+    }
+    tap("g", d_g_, {B, gin, 1});
+}
+
 void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
-                        const mi355vits_timing_args* timing) {
+                        const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers) {
     const mi355vits_config& c = cfg_;
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
     const float* row_scales = rows ? rows->scales : nullptr;
     if (!args.ids || !args.lengths || (!args.scales && !row_scales))
         throw EngineError(MI355VITS_ERR_INVALID, "input, input_lengths and scales are required");
     const bool multi = c.n_speakers > 1;
-    if (multi && !args.sid) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
+    if (multi && !args.sid && !speakers) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
     const int B = args.batch, Tx = args.tx_max;
     if ((long)B * Tx > (1L << 26)) throw EngineError(MI355VITS_ERR_INVALID, "batch * tx_max too large");
     if (Tx > rel_attention_valu_cap(c.hidden_channels, c.n_heads, c.window_size) &&
@@ -1628,7 +1719,7 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
             const int64_t id = args.ids[(long)b * Tx + t];
             if (id < 0 || id >= c.num_symbols) throw EngineError(MI355VITS_ERR_INVALID, "phoneme id out of range");
         }
-        if (multi && (args.sid[b] < 0 || args.sid[b] >= c.n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "speaker id out of range");
+        if (multi && !speakers && (args.sid[b] < 0 || args.sid[b] >= c.n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "speaker id out of range");
     }
     if (args.noise_z && args.noise_z_frames < 1) throw EngineError(MI355VITS_ERR_INVALID, "noise_z_frames must be >= 1");
     // timing (mi355vits_run_timed): without any of the three inputs the run is the plain one, launch for launch
@@ -1651,6 +1742,8 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
                 throw EngineError(MI355VITS_ERR_INVALID, rowname + ": target_frames must be 0 (none) or within 1 .. " + std::to_string(DURATION_FRAME_CAP));
         }
     }
+    // speakers (mi355vits_run_speakers): a blend or a vector per row in place of args.sid, which is then not read
+    const int spk = speakers ? check_speakers(c, *speakers, B) : 0;
 
     HIP_CHECK(hipSetDevice(device_));
     have_result_ = false;
@@ -1668,10 +1761,10 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     // reallocate when the next call brings them
     const size_t fBT = (size_t)B * Tx;
     ArenaCount size_a;
-    layout_a(size_a, B, Tx, true, true, 7);
+    layout_a(size_a, B, Tx, true, true, 7, -2);
     arena_a_.reserve(size_a.bytes + 4096, stream_);
     arena_a_.reset();
-    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr, tmask);
+    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr, tmask, spk);
     const size_t in_bytes = reinterpret_cast<unsigned char*>(d_ylen_) - reinterpret_cast<unsigned char*>(d_ids_);
     timed_run_ = tmask != 0;
 
@@ -1685,7 +1778,13 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         };
         put(d_ids_, args.ids, fBT * 8);
         put(d_len_, len32.data(), (size_t)B * 4);
-        if (multi) put(d_sid_, args.sid, (size_t)B * 8);
+        if (multi && !spk) put(d_sid_, args.sid, (size_t)B * 8);
+        if (spk > 0) {
+            put(d_mix_sid_, speakers->mix_sid, (size_t)B * spk * 8);
+            put(d_mix_w_, speakers->mix_weight, (size_t)B * spk * 4);
+        } else if (spk < 0) {
+            put(d_spk_vec_, speakers->vectors, (size_t)B * c.gin_channels * 4);
+        }
         put(d_scales_, sc3.data(), (size_t)B * 3 * 4);
         put(d_vol_, vol.data(), (size_t)B * 8);
         put(d_utt_, utt.data(), (size_t)B * 8);
@@ -1698,7 +1797,9 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         HIP_CHECK(hipMemcpyAsync(d_ids_, h0, in_bytes, hipMemcpyHostToDevice, stream_));
     }
 
-    if (gin) {
+    if (gin && spk) {
+        speaker_cond_mix(B, spk);
+    } else if (gin) {
         ProfScope ps(prof_, "speaker_cond");
         launch_speaker_cond(vec("emb_g.weight"), d_sid_, vec("dp.cond.weight"), vec("dp.cond.bias"), B, gin, H, d_cond_dp_, stream_);
         launch_speaker_cond(vec("emb_g.weight"), d_sid_, vec("dec.cond.weight"), vec("dec.cond.bias"), B, gin, C0, d_cond_dec_, stream_);

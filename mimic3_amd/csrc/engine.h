@@ -142,6 +142,7 @@ struct Model {
     std::unordered_map<std::string, ConvW> convs;
     std::unordered_map<std::string, size_t> vecs;
     float ea_m[2] = {0, 0}, ea_logs[2] = {0, 0};
+    std::vector<float> emb_g;  // host copy of emb_g.weight [n_speakers, gin] (empty for a single-speaker voice)
     int dp_filter = 0;  // deterministic duration predictor (dp_n_flows == 0): its filter width F; 0 for the stochastic one
     bool flow_reversed_out = false;
     size_t bytes = 0;
@@ -181,8 +182,11 @@ class Engine {
     void device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths);
     // rows: per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
     // timing: per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
+    // speakers: a blend of speakers or a vector per row in place of args.sid (mi355vits_run_speakers), or NULL: args.sid
     void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
-             const mi355vits_timing_args* timing = nullptr);
+             const mi355vits_timing_args* timing = nullptr, const mi355vits_speaker_args* speakers = nullptr);
+    // row `sid` of emb_g from the host copy kept with the weight replica (mi355vits_get_speaker_embedding): no stream work
+    void speaker_embedding(int64_t sid, float* out, size_t capacity) const;
     void fetch(uint32_t want, mi355vits_result* out);
     // the packed stream (mi355vits_run_packed / mi355vits_fetch_packed): pack == NULL = every row, in order, no silence, no header
     void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
@@ -275,7 +279,8 @@ class Engine {
     int mrf_stage(int i, int B, int ch, long T);       // the stage's leading resblocks in one launch; how many it took
     ConvArgs rb2_conv_args(int i, int j, int m, int B, int ch, long T) const;
     // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
-    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing);  // timing: 1 stretch | 2 min_frames | 4 target_frames
+    // timing: 1 stretch | 2 min_frames | 4 target_frames; speakers: 0 none, K = 1 .. 8 the mix tables, -1 the vectors, -2 both (sizing)
+    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing, int speakers);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
     // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
@@ -376,7 +381,9 @@ class Engine {
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with an output plan
     // the packed stream or block instead (its places made from the frame counts, its table uploaded with the per-stage lengths)
     void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
-                    const mi355vits_timing_args* timing = nullptr);
+                    const mi355vits_timing_args* timing = nullptr, const mi355vits_speaker_args* speakers = nullptr);
+    // the conditioning of a speakers run: k_speaker_cond_mix in place of the k_speaker_cond launches (spk as layout_a's speakers)
+    void speaker_cond_mix(int B, int spk);
     // k_durations, or in a timed run k_durations_timed in its place (the one call of both predictors)
     void durations(int B, int Tx, int ch, float ea_m, float ea_logs);
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
@@ -476,6 +483,9 @@ class Engine {
     float *d_stretch_ = nullptr, *d_tfactor_ = nullptr, *d_durf_ = nullptr;
     int *d_minf_ = nullptr, *d_target_ = nullptr, *d_tstatus_ = nullptr;
     bool timed_run_ = false;
+    // a speakers run's tables (in the one upload, like d_sid_) and the g [B, gin] its kernel leaves (the "g" tap)
+    long long* d_mix_sid_ = nullptr;
+    float *d_mix_w_ = nullptr, *d_spk_vec_ = nullptr, *d_g_ = nullptr;
     float *d_x_ = nullptr, *d_x2_ = nullptr, *d_qkv_ = nullptr, *d_att_ = nullptr, *d_ffn_ = nullptr, *d_part_ = nullptr,
           *d_stats_ = nullptr;
     float *d_h_ = nullptr, *d_d0_ = nullptr, *d_d1_ = nullptr, *d_d2_ = nullptr, *d_theta_ = nullptr, *d_z2_ = nullptr,

@@ -647,6 +647,39 @@ void launch_expand_prior(const float* stats /*[B,2I,Tx]: m_p | logs_p*/, const i
 void launch_speaker_cond(const float* emb_g, const long long* sid, const float* w, const float* bias, int B,
                          int gin, int Cout, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- blended / caller-supplied speakers (kernels_speaker.cpp;
+// mi355vits_run_speakers).  k_speaker_cond_mix: ONE launch makes g [B, gin] of every row and every consumer's projection of it.
+//   mix:     over the terms k < K of row b whose weight is not exactly 0, in order of k, per channel i:
+//            g[i] = fl(w_0 * e_0[i]), then g[i] = fl(g[i] + fl(w_k * e_k[i])), e_k = emb_g[sid[b,k], :]   (single f32 products and
+//            sums, never fused; a skipped term's sid is not read; a row without a term: g = 0, which the engine refuses beforehand)
+//   vectors: g[i] = vectors[b, i], bits in, bits out
+//   jobs:    out[b, co] = W[co, :] . g + bias[co] with k_speaker_cond's arithmetic per element: lane l of a wave accumulates
+//            fmaf(W[co, i], g[i], acc) over i = l, l + 64, .. from 0.0f, then wave_reduce_sum, then + bias
+// No result depends on the row block, the grid, the batch or an address.
+constexpr int SPEAKER_MIX_MAX_TERMS = 8;   // = MI355VITS_MAX_SPEAKER_TERMS
+constexpr int SPEAKER_MIX_MAX_JOBS = 10;   // dp.cond, dec.cond and a cond_layer per flow the kernel serves in one launch (2 + MI355VITS_MAX_STAGES)
+constexpr int SPEAKER_MIX_ROWS = 8;        // rows of a workgroup's block (<= 32: a wave stages eight at the most): their g vectors stay in LDS (8 x 512 floats = 16 KiB)
+constexpr int SPEAKER_MIX_LDS_FLOATS = 16384;  // the block's LDS budget: a gin above 2048 shrinks the block (gin <= 8192: two rows at least)
+constexpr int SPEAKER_MIX_TILE = 16;       // output channels of a workgroup: four per wave, their weight slices in registers
+struct SpeakerMixJob {
+    const float* w = nullptr;     // [Cout, gin]
+    const float* bias = nullptr;  // [Cout] or null (= 0)
+    float* out = nullptr;         // [B, Cout]
+    int Cout = 0;
+    int first_tile = 0;           // the job's first workgroup along grid x (filled in by the launcher)
+};
+struct SpeakerMixArgs {
+    const float* emb_g = nullptr;       // [n_speakers, gin]            (mix)
+    const long long* sid = nullptr;     // [B, K]                       (mix)
+    const float* weight = nullptr;      // [B, K]                       (mix)
+    const float* vectors = nullptr;     // [B, gin]: excludes the three above
+    int K = 0, B = 1, gin = 0;
+    float* g = nullptr;                 // [B, gin]: written by the workgroups of job 0, tile 0
+    int n_jobs = 0;
+    SpeakerMixJob jobs[SPEAKER_MIX_MAX_JOBS];
+};
+void launch_speaker_cond_mix(SpeakerMixArgs a, hipStream_t s);
+
 // misc
 void launch_fill(float* p, float v, size_t n, hipStream_t s);
 void launch_zero_row_tails(float* p, int B, int C, long T, const int* len, int factor, hipStream_t s);  // p[b, :, len[b] * factor:] = 0

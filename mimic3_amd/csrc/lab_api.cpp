@@ -1103,6 +1103,79 @@ int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const
     });
 }
 
+int mi355vits_test_speaker_cond(int device, int B, int gin, int n_speakers, int Cout, const float* emb_g, const int64_t* sid,
+                                const float* w, const float* bias, float* out, size_t out_floats) {
+    return guarded(nullptr, [&] {
+        if (!emb_g || !sid || !w || !out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || gin < 1 || gin > 8192 || n_speakers < 1 || Cout < 1 || out_floats < (size_t)B * Cout) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        for (int b = 0; b < B; ++b)
+            if (sid[b] < 0 || sid[b] >= n_speakers) throw EngineError(MI355VITS_ERR_INVALID, "sid out of range");
+        HIP_CHECK(hipSetDevice(device));
+        DevBuf de((size_t)n_speakers * gin * 4), ds((size_t)B * 8), dw((size_t)Cout * gin * 4), db((size_t)Cout * 4), dout(out_floats * 4);
+        HIP_CHECK(hipMemcpy(de.p, emb_g, (size_t)n_speakers * gin * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, sid, (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dw.p, w, (size_t)Cout * gin * 4, hipMemcpyHostToDevice));
+        if (bias) HIP_CHECK(hipMemcpy(db.p, bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dout.p, out, out_floats * 4, hipMemcpyHostToDevice));  // the prior contents: a missing or stray write shows
+        launch_speaker_cond(de.as<float>(), ds.as<long long>(), dw.as<float>(), bias ? db.as<float>() : nullptr, B, gin, Cout, dout.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.p, out_floats * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->g) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, gin = t->gin, K = t->n_terms, nj = t->n_jobs;
+        if (B < 1 || gin < 1 || gin > 8192 || nj < 1 || nj > SPEAKER_MIX_MAX_JOBS || t->g_floats < (size_t)B * gin) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        const bool mix = t->vectors == nullptr;
+        if (mix) {
+            if (!t->emb_g || !t->mix_sid || !t->mix_weight || t->n_speakers < 1 || K < 1 || K > SPEAKER_MIX_MAX_TERMS)
+                throw EngineError(MI355VITS_ERR_INVALID, "a mix needs emb_g, mix_sid, mix_weight and n_terms 1 .. 8");
+            for (size_t i = 0; i < (size_t)B * K; ++i)
+                if (t->mix_weight[i] != 0.0f && (t->mix_sid[i] < 0 || t->mix_sid[i] >= t->n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "sid out of range");
+        } else if (t->emb_g || t->mix_sid || t->mix_weight || K != 0) {
+            throw EngineError(MI355VITS_ERR_INVALID, "vectors exclude emb_g, mix_sid, mix_weight and n_terms");
+        }
+        for (int q = 0; q < nj; ++q)
+            if (!t->w[q] || !t->out[q] || t->Cout[q] < 1 || t->out_floats[q] < (size_t)B * t->Cout[q]) throw EngineError(MI355VITS_ERR_INVALID, "bad job");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t ne = mix ? (size_t)t->n_speakers * gin : 0, nk = mix ? (size_t)B * K : 0, nv = mix ? 0 : (size_t)B * gin;
+        DevBuf de(ne * 4), ds(nk * 8), dm(nk * 4), dv(nv * 4), dg(t->g_floats * 4);
+        if (mix) {
+            HIP_CHECK(hipMemcpy(de.p, t->emb_g, ne * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(ds.p, t->mix_sid, nk * 8, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dm.p, t->mix_weight, nk * 4, hipMemcpyHostToDevice));
+        } else {
+            HIP_CHECK(hipMemcpy(dv.p, t->vectors, nv * 4, hipMemcpyHostToDevice));
+        }
+        HIP_CHECK(hipMemcpy(dg.p, t->g, t->g_floats * 4, hipMemcpyHostToDevice));  // the prior contents: a missing or stray write shows
+        std::vector<std::unique_ptr<DevBuf>> dw, db, dout;
+        SpeakerMixArgs a;
+        a.B = B; a.gin = gin; a.K = K; a.g = dg.as<float>(); a.n_jobs = nj;
+        if (mix) { a.emb_g = de.as<float>(); a.sid = ds.as<long long>(); a.weight = dm.as<float>(); } else a.vectors = dv.as<float>();
+        for (int q = 0; q < nj; ++q) {
+            const size_t nw = (size_t)t->Cout[q] * gin;
+            dw.emplace_back(new DevBuf(nw * 4));
+            db.emplace_back(new DevBuf((size_t)t->Cout[q] * 4));
+            dout.emplace_back(new DevBuf(t->out_floats[q] * 4));
+            HIP_CHECK(hipMemcpy(dw[q]->p, t->w[q], nw * 4, hipMemcpyHostToDevice));
+            if (t->bias[q]) HIP_CHECK(hipMemcpy(db[q]->p, t->bias[q], (size_t)t->Cout[q] * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(dout[q]->p, t->out[q], t->out_floats[q] * 4, hipMemcpyHostToDevice));
+            a.jobs[q].w = dw[q]->as<float>();
+            a.jobs[q].bias = t->bias[q] ? db[q]->as<float>() : nullptr;
+            a.jobs[q].Cout = t->Cout[q];
+            a.jobs[q].out = dout[q]->as<float>();
+        }
+        launch_speaker_cond_mix(a, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(t->g, dg.p, t->g_floats * 4, hipMemcpyDeviceToHost));
+        for (int q = 0; q < nj; ++q) HIP_CHECK(hipMemcpy(t->out[q], dout[q]->p, t->out_floats[q] * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z) {
     return guarded(nullptr, [&] {

@@ -753,7 +753,7 @@ class InferenceSession:
     # ---- engine extensions --------------------------------------------------------------------
     def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
                   sample_rate: Optional[int] = None, alignment=False, stretch=None, min_frames=None, target_frames=None,
-                  duration_ms=None):
+                  duration_ms=None, speakers=None):
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -773,14 +773,21 @@ class InferenceSession:
         [B, Tx] holds a phoneme (a pause symbol) at least that many latent frames, ``target_frames`` [B] fits the row to exactly
         that many latent frames (0 = as predicted), or ``duration_ms`` [B] (0 / ``None`` = as predicted) the same in time:
         ``max(1, round(ms / 1000 * sample_rate / hop))`` frames at the voice's native rate.  Such a call goes straight to a lane,
-        never through the micro-batcher; the factors it was fitted with are left in ``last_timing_factor``."""
+        never through the micro-batcher; the factors it was fitted with are left in ``last_timing_factor``.
+        ``speakers`` (``mi355vits_run_speakers``; a multi-speaker voice): who speaks each row, in place of the feed's ``sid`` (which
+        may then be left out) — one entry per row: an ``int`` (that speaker), a dict ``{sid: weight}`` (a blend such as
+        ``{12: 0.7, 40: 0.3}``, extrapolation such as ``{12: 1.5, 40: -0.5}`` included) or a 1-D float array of ``gin_channels``
+        values (a vector of the caller's own: see ``speaker_embedding``).  Ints and dicts may be mixed in one call; vectors go in a
+        call of their own (``ValueError`` otherwise).  Such a call goes straight to a lane, never through the micro-batcher."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
         timing = self._timing_kw(input_feed, stretch, min_frames, target_frames, duration_ms)
         kw.update(timing)
-        if alignment or timing:
-            ids, lengths, sid = self._feed(input_feed)
+        if speakers is not None:
+            kw["speakers"] = speakers
+        if alignment or timing or speakers is not None:
+            ids, lengths, sid = self._feed(input_feed, speakers is not None)
             keys = kw.pop("utterance_keys", None)
             out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys,
                                    _alignment=_alignment_levels(alignment) if alignment else None, want_float=False, want_pcm16=True, **kw)
@@ -821,7 +828,7 @@ class InferenceSession:
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
                    limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION,
-                   stretch=None, min_frames=None, target_frames=None, duration_ms=None) -> "_native.PackedAudio":
+                   stretch=None, min_frames=None, target_frames=None, duration_ms=None, speakers=None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -858,7 +865,8 @@ class InferenceSession:
         ``.total_samples`` are those of the uncompressed call.  ``wav=True`` with it raises ``ValueError``; any encoding but
         "s16le" is refused by the library.
         ``stretch`` / ``min_frames`` / ``target_frames`` / ``duration_ms``: timing in the same run, as for ``run_pcm16`` (a timed run
-        that keeps its audio on the device, then the pack: one synchronisation more)."""
+        that keeps its audio on the device, then the pack: one synchronisation more).  ``speakers``: who speaks each row, as for
+        ``run_pcm16`` (likewise a run that keeps its audio on the device, then the pack)."""
         comp = self.output_compression if compression is _SESSION else _compression_name(compression)
         if comp and wav:
             raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
@@ -872,9 +880,11 @@ class InferenceSession:
             if lead_samples is not None:
                 raise InvalidArgument("give lead_ms or lead_samples, not both")
             lead_samples = [int((float(ms) / 1000.0) * rate) for ms in np.asarray(lead_ms, np.float64).reshape(-1)]
-        ids, lengths, sid = self._feed(input_feed)
+        ids, lengths, sid = self._feed(input_feed, speakers is not None)
         keys = kw.pop("utterance_keys", None)
         kw.update(self._timing_kw(input_feed, stretch, min_frames, target_frames, duration_ms))
+        if speakers is not None:
+            kw["speakers"] = speakers
         if alignment:
             kw["_alignment"] = _alignment_levels(alignment)
         ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
@@ -1045,11 +1055,12 @@ class InferenceSession:
         self.last_lengths = out["lengths"]
         return out
 
-    def _feed(self, input_feed):
-        """The feed dict checked as onnxruntime checks it: (ids [B, Tx], lengths [B], sid or None)."""
+    def _feed(self, input_feed, speakers: bool = False):
+        """The feed dict checked as onnxruntime checks it: (ids [B, Tx], lengths [B], sid or None).  ``speakers``: the call says
+        who speaks each row itself, so a multi-speaker voice's ``sid`` may be left out."""
         if not isinstance(input_feed, dict):
             raise InvalidArgument("input_feed must be a dict of numpy arrays")
-        required = ["input", "input_lengths", "scales"] + (["sid"] if self.config.is_multispeaker else [])
+        required = ["input", "input_lengths", "scales"] + (["sid"] if self.config.is_multispeaker and not speakers else [])
         for name in required:
             if name not in input_feed:
                 raise InvalidArgument(f"Required inputs ({name!r}) are missing from input feed ({list(input_feed)}).")
@@ -1066,6 +1077,16 @@ class InferenceSession:
         sid = input_feed.get("sid") if self.config.is_multispeaker else None
         lengths = np.asarray(input_feed["input_lengths"]).reshape(-1)
         return ids, lengths, sid
+
+    def speaker_embedding(self, sid: int) -> np.ndarray:
+        """Row ``sid`` of the voice's speaker table [gin_channels] (``mi355vits_get_speaker_embedding``; a host copy, no GPU work):
+        what ``speakers=[sid]`` speaks with — average, interpolate or fit such vectors and pass the result as ``speakers``."""
+        try:
+            return self._engine.speaker_embedding(sid)
+        except _native.NativeError as e:
+            if e.code == -1:
+                raise InvalidArgument(str(e)) from None
+            raise RuntimeError(str(e)) from None
 
     def reserve_utterances(self, n: int) -> int:
         """Reserve ``n`` consecutive Philox utterance indices of this session; returns the first.  Calls without
