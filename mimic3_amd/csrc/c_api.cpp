@@ -27,6 +27,27 @@ template <typename R, typename F> int result_call(mi355vits_handle h, R* out, F&
     if (rc != MI355VITS_OK && out) free_struct(out);
     return rc;
 }
+
+// A call on a handle that fills no result struct: the handle checked and locked; fn's int is what the call returns ...
+template <typename F> int locked(mi355vits_handle h, F&& fn) {
+    if (!h) return MI355VITS_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->eng->mu);
+    return fn();
+}
+// ... and with exceptions fenced: fn returns nothing, the call a status
+template <typename F> int locked_guarded(mi355vits_handle h, F&& fn) {
+    return locked(h, [&] { return guarded(h, fn); });
+}
+
+// The run* entry points: a result_call whose `args` must be there; fn receives them with rows, timing and speakers as the engine's RunCall.
+template <typename R, typename F>
+int run_call(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows, const mi355vits_timing_args* timing,
+             const mi355vits_speaker_args* speakers, R* out, F&& fn) {
+    return result_call(h, out, [&] {
+        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
+        fn(RunCall{*args, rows, timing, speakers});
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -84,9 +105,7 @@ int mi355vits_clone(mi355vits_handle src, mi355vits_handle* out) {
 
 int mi355vits_device_result(mi355vits_handle h, const int16_t** pcm, const float** audio, int64_t* row_stride,
                             int32_t* batch, const int32_t** device_lengths) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] {
+    return locked_guarded(h, [&] {
         long rs = 0;
         int b = 0;
         h->eng->device_buffers(pcm, audio, &rs, &b, device_lengths);
@@ -105,47 +124,31 @@ void mi355vits_destroy(mi355vits_handle h) {
 }
 
 int mi355vits_set_math(mi355vits_handle h, int mode) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_math(mode); });
+    return locked_guarded(h, [&] { h->eng->set_math(mode); });
 }
 int mi355vits_get_math(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->math();
+    return locked(h, [&] { return h->eng->math(); });
 }
 
 int mi355vits_set_output_rate(mi355vits_handle h, int32_t hz) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_output_rate(hz); });
+    return locked_guarded(h, [&] { h->eng->set_output_rate(hz); });
 }
 int32_t mi355vits_get_output_rate(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->output_rate();
+    return locked(h, [&] { return h->eng->output_rate(); });
 }
 
 int mi355vits_set_output_encoding(mi355vits_handle h, int enc) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_output_encoding(enc); });
+    return locked_guarded(h, [&] { h->eng->set_output_encoding(enc); });
 }
 int mi355vits_get_output_encoding(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->output_encoding();
+    return locked(h, [&] { return h->eng->output_encoding(); });
 }
 
 int mi355vits_set_output_compression(mi355vits_handle h, int mode) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_output_compression(mode); });
+    return locked_guarded(h, [&] { h->eng->set_output_compression(mode); });
 }
 int mi355vits_get_output_compression(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->output_compression();
+    return locked(h, [&] { return h->eng->output_compression(); });
 }
 
 int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
@@ -157,37 +160,26 @@ int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
 }
 
 int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_result* out) {
-    return mi355vits_run_rows(h, args, nullptr, out);
+    return mi355vits_run_speakers(h, args, nullptr, nullptr, nullptr, out);
 }
 
 int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                        mi355vits_result* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run(*args, rows, out);
-    });
+    return mi355vits_run_speakers(h, args, rows, nullptr, nullptr, out);
 }
 
 int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                         const mi355vits_timing_args* timing, mi355vits_result* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run(*args, rows, out, timing);
-    });
+    return mi355vits_run_speakers(h, args, rows, timing, nullptr, out);
 }
 
 int mi355vits_run_speakers(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                            const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers, mi355vits_result* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run(*args, rows, out, timing, speakers);
-    });
+    return run_call(h, args, rows, timing, speakers, out, [&](const RunCall& call) { h->eng->run(call, out); });
 }
 
 int mi355vits_get_speaker_embedding(mi355vits_handle h, int64_t sid, float* out, size_t capacity) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->speaker_embedding(sid, out, capacity); });
+    return locked_guarded(h, [&] { h->eng->speaker_embedding(sid, out, capacity); });
 }
 
 int mi355vits_fetch(mi355vits_handle h, uint32_t want_flags, mi355vits_result* out) {
@@ -198,10 +190,7 @@ void mi355vits_free_result(mi355vits_result* r) { free_struct(r); }
 
 int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                          const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run_packed(*args, rows, pack, out);
-    });
+    return run_call(h, args, rows, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_packed(call, pack, out); });
 }
 
 int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
@@ -212,10 +201,7 @@ void mi355vits_free_packed(mi355vits_packed_result* r) { free_struct(r); }
 
 int mi355vits_run_streams(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                           const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run_streams(*args, rows, streams, n_streams, out);
-    });
+    return run_call(h, args, rows, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams(call, streams, n_streams, out); });
 }
 
 int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
@@ -226,10 +212,7 @@ void mi355vits_free_streams(mi355vits_streams_result* r) { free_struct(r); }
 
 int mi355vits_run_streams2(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                            const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {
-    return result_call(h, out, [&] {
-        if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        h->eng->run_streams2(*args, rows, streams, n_streams, out);
-    });
+    return run_call(h, args, rows, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams2(call, streams, n_streams, out); });
 }
 
 int mi355vits_fetch_streams2(mi355vits_handle h, const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {
@@ -245,17 +228,15 @@ int mi355vits_fetch_alignment(mi355vits_handle h, uint32_t want, mi355vits_align
 void mi355vits_free_alignment(mi355vits_alignment* r) { free_struct(r); }
 
 int mi355vits_set_edge_trim(mi355vits_handle h, float ratio, int32_t keep_samples) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_edge_trim(ratio, keep_samples); });
+    return locked_guarded(h, [&] { h->eng->set_edge_trim(ratio, keep_samples); });
 }
 
 int mi355vits_get_edge_trim(mi355vits_handle h, float* ratio, int32_t* keep_samples) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    if (ratio) *ratio = h->eng->edge_trim_ratio();
-    if (keep_samples) *keep_samples = h->eng->edge_trim_keep();
-    return MI355VITS_OK;
+    return locked(h, [&] {
+        if (ratio) *ratio = h->eng->edge_trim_ratio();
+        if (keep_samples) *keep_samples = h->eng->edge_trim_keep();
+        return (int)MI355VITS_OK;
+    });
 }
 
 int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out) {
@@ -265,17 +246,15 @@ int mi355vits_fetch_edges(mi355vits_handle h, mi355vits_edges* out) {
 void mi355vits_free_edges(mi355vits_edges* r) { free_struct(r); }
 
 int mi355vits_set_loudness_target(mi355vits_handle h, float target_lufs, float ceiling_dbfs) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_loudness_target(target_lufs, ceiling_dbfs); });
+    return locked_guarded(h, [&] { h->eng->set_loudness_target(target_lufs, ceiling_dbfs); });
 }
 
 int mi355vits_get_loudness_target(mi355vits_handle h, float* target_lufs, float* ceiling_dbfs) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    if (target_lufs) *target_lufs = h->eng->loudness_target();
-    if (ceiling_dbfs) *ceiling_dbfs = h->eng->loudness_ceiling();
-    return MI355VITS_OK;
+    return locked(h, [&] {
+        if (target_lufs) *target_lufs = h->eng->loudness_target();
+        if (ceiling_dbfs) *ceiling_dbfs = h->eng->loudness_ceiling();
+        return (int)MI355VITS_OK;
+    });
 }
 
 int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out) {
@@ -285,15 +264,11 @@ int mi355vits_fetch_loudness(mi355vits_handle h, mi355vits_loudness* out) {
 void mi355vits_free_loudness(mi355vits_loudness* r) { free_struct(r); }
 
 int mi355vits_set_loudness_limiter(mi355vits_handle h, int32_t window_samples) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_loudness_limiter(window_samples); });
+    return locked_guarded(h, [&] { h->eng->set_loudness_limiter(window_samples); });
 }
 
 int32_t mi355vits_get_loudness_limiter(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->loudness_limiter();
+    return locked(h, [&] { return h->eng->loudness_limiter(); });
 }
 
 int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out) {
@@ -303,15 +278,11 @@ int mi355vits_fetch_limiter(mi355vits_handle h, mi355vits_limiter* out) {
 void mi355vits_free_limiter(mi355vits_limiter* r) { free_struct(r); }
 
 int mi355vits_set_loudness_ceiling_mode(mi355vits_handle h, int mode) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->set_loudness_ceiling_mode(mode); });
+    return locked_guarded(h, [&] { h->eng->set_loudness_ceiling_mode(mode); });
 }
 
 int mi355vits_get_loudness_ceiling_mode(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return h->eng->loudness_ceiling_mode();
+    return locked(h, [&] { return h->eng->loudness_ceiling_mode(); });
 }
 
 int mi355vits_fetch_true_peak(mi355vits_handle h, mi355vits_true_peak* out) {
@@ -323,15 +294,13 @@ void mi355vits_free_true_peak(mi355vits_true_peak* r) { free_struct(r); }
 const char* mi355vits_last_error(mi355vits_handle h) { return h ? h->err.c_str() : create_error().c_str(); }
 
 int mi355vits_profile_enable(mi355vits_handle h, int on) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    h->eng->profiler().enabled = on != 0;
-    return MI355VITS_OK;
+    return locked(h, [&] {
+        h->eng->profiler().enabled = on != 0;
+        return (int)MI355VITS_OK;
+    });
 }
 int mi355vits_profile_reset(mi355vits_handle h) {
-    if (!h) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    return guarded(h, [&] { h->eng->profiler().clear(); });
+    return locked_guarded(h, [&] { h->eng->profiler().clear(); });
 }
 long mi355vits_profile_report(mi355vits_handle h, char* buf, size_t cap) {
     if (!h || !buf || cap == 0) return MI355VITS_ERR_INVALID;
@@ -352,19 +321,18 @@ float mi355vits_last_run_ms(mi355vits_handle h) {
     return h->eng->last_run_ms();
 }
 
-long mi355vits_get_tap(mi355vits_handle h, const char* name, float* out, size_t capacity, int64_t dims[4]) {
+static long tap_call(mi355vits_handle h, const char* name, long row0, long nrows, float* out, size_t capacity, int64_t dims[4]) {
     if (!h || !name || !dims) return MI355VITS_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->eng->mu);
     long n = 0;
-    int rc = guarded(h, [&] { n = h->eng->get_tap(name, out, capacity, dims); });
+    int rc = guarded(h, [&] { n = h->eng->get_tap(name, out, capacity, dims, row0, nrows); });
     return rc == MI355VITS_OK ? n : rc;
 }
+long mi355vits_get_tap(mi355vits_handle h, const char* name, float* out, size_t capacity, int64_t dims[4]) {
+    return tap_call(h, name, 0, -1, out, capacity, dims);  // every row
+}
 long mi355vits_get_tap_rows(mi355vits_handle h, const char* name, long row0, long nrows, float* out, size_t capacity, int64_t dims[4]) {
-    if (!h || !name || !dims) return MI355VITS_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->eng->mu);
-    long n = 0;
-    int rc = guarded(h, [&] { n = h->eng->get_tap(name, out, capacity, dims, row0, nrows < 0 ? 0 : nrows); });
-    return rc == MI355VITS_OK ? n : rc;
+    return tap_call(h, name, row0, nrows < 0 ? 0 : nrows, out, capacity, dims);
 }
 long mi355vits_list_taps(mi355vits_handle h, char* buf, size_t cap) {
     if (!h || !buf || cap == 0) return MI355VITS_ERR_INVALID;

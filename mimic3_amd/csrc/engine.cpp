@@ -11,6 +11,7 @@
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <type_traits>
 
 namespace m355 {
 
@@ -824,22 +825,38 @@ void Engine::conv(const char* label, const ConvW& w, ConvArgs a) {
     else launch_conv1d_mfma(a, stream_);
 }
 
-void Engine::tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len, int factor) {
-    if (!taps_on_) return;
-    size_t cnt = 1;
-    for (auto d : dims) cnt *= (size_t)d;
+// a named buffer for the copy of an intermediate, or null: taps are off, or the name is taken (the first tap of a name stays)
+Tap* Engine::new_tap(const char* name, std::initializer_list<int64_t> dims) {
+    if (!taps_on_) return nullptr;
     for (auto& t : taps_)
-        if (t.name == name) return;
+        if (t.name == name) return nullptr;
     Tap t;
     t.name = name;
     t.dims.assign(dims.begin(), dims.end());
-    t.count = cnt;
+    t.count = 1;
+    for (auto d : dims) t.count *= (size_t)d;
     void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, cnt * sizeof(float) + 16));
+    HIP_CHECK(hipMalloc(&p, t.count * sizeof(float) + 16));
     t.dev = static_cast<float*>(p);
-    HIP_CHECK(hipMemcpyAsync(t.dev, dev, cnt * sizeof(float), hipMemcpyDeviceToDevice, stream_));
-    if (row_len && t.dims.size() == 3) launch_zero_row_tails(t.dev, (int)t.dims[0], (int)t.dims[1], (long)t.dims[2], row_len, factor, stream_);
     taps_.push_back(std::move(t));
+    return &taps_.back();
+}
+
+void Engine::tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len, int factor) {
+    Tap* t = new_tap(name, dims);
+    if (!t) return;
+    HIP_CHECK(hipMemcpyAsync(t->dev, dev, t->count * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+    if (row_len && t->dims.size() == 3) launch_zero_row_tails(t->dev, (int)t->dims[0], (int)t->dims[1], (long)t->dims[2], row_len, factor, stream_);
+}
+
+// an int32 array as floats for the tap interface (w_ceil): through the host, with copies that synchronise
+void Engine::tap_ints(const char* name, const int* dev, std::initializer_list<int64_t> dims) {
+    Tap* t = new_tap(name, dims);
+    if (!t) return;
+    std::vector<int> v(t->count);
+    HIP_CHECK(hipMemcpy(v.data(), dev, t->count * 4, hipMemcpyDeviceToHost));
+    const std::vector<float> f32(v.begin(), v.end());
+    HIP_CHECK(hipMemcpy(t->dev, f32.data(), t->count * 4, hipMemcpyHostToDevice));
 }
 
 // rows [row0, row0 + nrows) of the leading (batch) extent; nrows < 0: all rows (a batch-256 stage tap is 6.4 GB: the tests fetch the rows they check)
@@ -868,7 +885,7 @@ std::string Engine::list_taps() const {
 }
 
 float Engine::last_run_ms() {
-    if (!timed_) return -1.0f;
+    if (!end_recorded_) return -1.0f;
     float ms = -1.0f;
     if (hipEventElapsedTime(&ms, ev_start_, ev_end_) != hipSuccess) return -1.0f;
     return ms;
@@ -1031,9 +1048,9 @@ void Engine::dds(const std::string& key, float* X, float* Y1, float* Y2, int B, 
 
 // deterministic predictor (dp_n_flows == 0): k_dp_det writes logw into channel 0 of z2, and k_durations reads it back through an
 // identity ElementwiseAffine ((z - 0) * expf(-0) * m: exact).  noise_w is not used, as in upstream VITS.
-void Engine::duration_predictor_det(int B, int Tx) {
+void Engine::duration_predictor_det(const RunInputs& in) {
     const mi355vits_config& c = cfg_;
-    const int H = c.hidden_channels, DF = model_->dp_filter, K = c.dp_kernel_size;
+    const int B = in.B, Tx = in.Tx, H = c.hidden_channels, DF = model_->dp_filter, K = c.dp_kernel_size;
     DpDetArgs a;
     a.x = d_x_;
     a.cond = d_cond_dp_;
@@ -1058,13 +1075,14 @@ void Engine::duration_predictor_det(int B, int Tx) {
         ProfScope ps(prof_, "dp.det", flops, 4.0 * B * (double)Tx * (H + 1));
         launch_dp_det(a, stream_);
     }
-    durations(B, Tx, 0, 0.0f, 0.0f);
+    durations(in, 0, 0.0f, 0.0f);
 }
 
 // The durations of both predictors: k_durations, or in a timed run k_durations_timed IN ITS PLACE (the same EA^-1 and logw, then
 // the fit: kernels_timing.cpp), which also leaves status and factor of every row right behind d_ylen_.
-void Engine::durations(int B, int Tx, int ch, float ea_m, float ea_logs) {
-    if (!timed_run_) {
+void Engine::durations(const RunInputs& in, int ch, float ea_m, float ea_logs) {
+    const int B = in.B, Tx = in.Tx;
+    if (!in.timed()) {
         ProfScope ps(prof_, "durations");
         launch_durations(d_z2_, ch, ea_m, ea_logs, d_len_, d_forced_, B, Tx, d_scales_, d_logw_, d_wceil_, d_cum_, d_ylen_, stream_);
     } else {
@@ -1080,16 +1098,16 @@ void Engine::durations(int B, int Tx, int ch, float ea_m, float ea_logs) {
         launch_durations_timed(a, stream_);
     }
     tap("logw", d_logw_, {B, 1, Tx});
-    if (timed_run_) tap("dur_float", d_durf_, {B, 1, Tx});
+    if (in.timed()) tap("dur_float", d_durf_, {B, 1, Tx});
 }
 
-void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
+void Engine::duration_predictor(const RunInputs& in) {
     if (model_->dp_filter) {
-        duration_predictor_det(B, Tx);
+        duration_predictor_det(in);
         return;
     }
     const mi355vits_config& c = cfg_;
-    const int H = c.hidden_channels;
+    const int B = in.B, Tx = in.Tx, H = c.hidden_channels;
     const long bs = (long)H * Tx;
     const int nth = 3 * c.dp_num_bins - 1;
     // the whole stack in one launch each (k_dds_stack): pre + DDS layers + proj, and for a ConvFlow the spline too
@@ -1160,7 +1178,7 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
 
     {
         ProfScope ps(prof_, "sdp.noise");
-        launch_sdp_noise(d_z2_, d_noise_w_, B, Tx, d_scales_, args.seed, d_utt_, stream_);
+        launch_sdp_noise(d_z2_, d_noise_w_, B, Tx, d_scales_, in.seed, d_utt_, stream_);
     }
     int ch0 = 0;  // physical channel that is logical channel 0
     for (int j = c.dp_n_flows - 1; j >= 1; --j) {
@@ -1204,7 +1222,7 @@ void Engine::duration_predictor(int B, int Tx, const mi355vits_run_args& args) {
         }
     }
     ch0 ^= 1;  // Flip before the ElementwiseAffine
-    durations(B, Tx, ch0, model_->ea_m[0], model_->ea_logs[0]);  // logical channel 0 uses EA parameters [0]
+    durations(in, ch0, model_->ea_m[0], model_->ea_logs[0]);  // logical channel 0 uses EA parameters [0]
 }
 
 // =================================================================================================
@@ -1459,14 +1477,14 @@ void Engine::decoder_stage(int i, int B, int ch, long T) {
 }
 
 // expand, flows, conv_pre, stages, conv_post
-void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
+void Engine::flow_and_decoder(const RunInputs& in) {
     struct PhaseB { bool& f; explicit PhaseB(bool& r) : f(r) { f = true; } ~PhaseB() { f = false; } } phase_guard(phase_b_);
     const mi355vits_config& c = cfg_;
-    const int I = c.inter_channels, C0 = c.upsample_initial_channel;
+    const int B = in.B, Ty = Ty_, I = c.inter_channels, C0 = c.upsample_initial_channel;
     {
         ProfScope ps(prof_, "expand_prior", 0, 4.0 * B * I * Ty * 3);
-        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, args.noise_z_frames, B, I, Tx_, Ty, d_scales_,
-                            args.seed, d_utt_, d_z_, stream_);
+        launch_expand_prior(d_stats_, d_cum_, d_ylen_, d_noise_z_, in.noise_z_frames, B, I, Tx_, Ty, d_scales_,
+                            in.seed, d_utt_, d_z_, stream_);
     }
     tap("z_p", d_z_, {B, I, Ty}, d_ylen_, 1);
     for (int j = c.flow_n_flows - 1; j >= 0; --j) coupling_layer(j, B, Ty);
@@ -1499,30 +1517,45 @@ void Engine::flow_and_decoder(int B, int Ty, const mi355vits_run_args& args) {
 // =================================================================================================
 // one synthesis call
 // =================================================================================================
-// The sequence of alloc calls below IS the workspace layout: run() plays it against an ArenaCount for the size to reserve, then
+// The sequence of alloc calls below IS the workspace layout: a run plays it against an ArenaCount for the size to reserve, then
 // against the arena for the pointers.
-template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing, int speakers) {
+// Its head is the input block: the call's host inputs sit side by side so that ONE host-to-device copy brings them all (each copy
+// from pageable memory is a staging pass + a copy kernel: ~35 us apiece in the stream of a single utterance).  Each input is named
+// in ONE `field` line, which says whether it is allocated, where (the order of the lines) and what lands there: h_in_ grows by
+// every allocated field — its source where it has one, zeros else, padded as the arena pads — so h_in_ is the block byte for byte
+// and h_in_.size() its extent.  widest: the same list with every optional field there, the mix at MI355VITS_MAX_SPEAKER_TERMS
+// terms, whatever `in` brings, and nothing copied — what the sizing pass asks: a handle that served a call without them does not
+// reallocate when the next call brings them.
+template <typename A> void Engine::layout_a(A& ar, const RunInputs& in, bool widest) {
     const mi355vits_config& c = cfg_;
-    const size_t H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels, fBT = B * Tx;
+    const size_t B = in.B, Tx = in.Tx, H = c.hidden_channels, F = c.filter_channels, I = c.inter_channels, fBT = B * Tx, gin = c.gin_channels;
     const size_t nth = std::max(3 * c.dp_num_bins - 1, 0);  // 0: the deterministic predictor has no spline parameters
-    // the call's host inputs sit side by side so that ONE host-to-device copy brings them all (each copy from pageable memory
-    // is a staging pass + a copy kernel: ~35 us apiece in the stream of a single utterance): d_ids_ .. up to d_ylen_
-    d_ids_ = ar.template alloc<long long>(fBT);
-    d_sid_ = ar.template alloc<long long>(B);
-    d_len_ = ar.template alloc<int>(B);
-    d_scales_ = ar.template alloc<float>(B * 3);
-    d_vol_ = ar.template alloc<double>(B);
-    d_utt_ = ar.template alloc<unsigned long long>(B);
-    d_forced_ = forced ? ar.template alloc<int>(fBT) : nullptr;
-    d_noise_w_ = noise_w ? ar.template alloc<float>(fBT * 2) : nullptr;
-    d_stretch_ = (timing & 1) ? ar.template alloc<float>(fBT) : nullptr;
-    d_minf_ = (timing & 2) ? ar.template alloc<int>(fBT) : nullptr;
-    d_target_ = (timing & 4) ? ar.template alloc<int>(B) : nullptr;
-    const bool cond = c.n_speakers > 1 && c.gin_channels;
-    const size_t spk_terms = speakers > 0 ? speakers : (speakers == -2 ? MI355VITS_MAX_SPEAKER_TERMS : 0);
-    d_mix_sid_ = (cond && spk_terms) ? ar.template alloc<long long>(B * spk_terms) : nullptr;
-    d_mix_w_ = (cond && spk_terms) ? ar.template alloc<float>(B * spk_terms) : nullptr;
-    d_spk_vec_ = (cond && (speakers == -1 || speakers == -2)) ? ar.template alloc<float>(B * c.gin_channels) : nullptr;
+    const bool cond = c.n_speakers > 1 && gin;  // only such a voice takes a speakers run
+    // a field is there when the run brings `src`, or `anyway` (then left zero)
+    auto field = [&](auto*& dev, size_t n, const void* src, bool anyway) {
+        using T = std::remove_reference_t<decltype(*dev)>;
+        dev = (src || anyway) ? ar.template alloc<T>(n) : nullptr;
+        if (widest || !dev) return;
+        const size_t at = h_in_.size();
+        h_in_.resize(at + DeviceArena::padded(n * sizeof(T)), 0);
+        if (src) memcpy(h_in_.data() + at, src, n * sizeof(T));
+    };
+    const size_t K = widest ? MI355VITS_MAX_SPEAKER_TERMS : in.spk.n_terms;
+    h_in_.clear();
+    field(d_ids_, fBT, in.ids, true);
+    field(d_sid_, B, in.sid, true);
+    field(d_len_, B, in.len32.data(), true);
+    field(d_scales_, B * 3, in.sc3.data(), true);
+    field(d_vol_, B, in.vol.data(), true);
+    field(d_utt_, B, in.utt.data(), true);
+    field(d_forced_, fBT, in.forced_durations, widest);
+    field(d_noise_w_, fBT * 2, in.noise_w, widest);
+    field(d_stretch_, fBT, in.timing.stretch, widest);
+    field(d_minf_, fBT, in.timing.min_frames, widest);
+    field(d_target_, B, in.timing.target_frames, widest);
+    field(d_mix_sid_, B * K, in.spk.mix_sid, widest && cond);
+    field(d_mix_w_, B * K, in.spk.mix_weight, widest && cond);
+    field(d_spk_vec_, B * gin, in.spk.vectors, widest && cond);
     // what the host reads at the run's one sizing synchronisation: ylen, and of a timed run status and factor, in ONE copy (4-byte
     // words side by side: each of the three is B words)
     d_ylen_ = ar.template alloc<int>(3 * B);
@@ -1547,7 +1580,7 @@ template <typename A> void Engine::layout_a(A& ar, size_t B, size_t Tx, bool for
     d_theta_ = ar.template alloc<float>(fBT * nth);
     d_z2_ = ar.template alloc<float>(fBT * 2);
     d_logw_ = ar.template alloc<float>(fBT);
-    d_g_ = (cond && speakers) ? ar.template alloc<float>(B * c.gin_channels) : nullptr;
+    d_g_ = (cond && (widest || in.speakers != RunInputs::SPK_NONE)) ? ar.template alloc<float>(B * gin) : nullptr;
     d_cond_dp_ = cond ? ar.template alloc<float>(B * H) : nullptr;
     d_cond_dec_ = cond ? ar.template alloc<float>(B * c.upsample_initial_channel) : nullptr;
     d_cond_flow_.clear();
@@ -1583,12 +1616,11 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_rtab_ = Lr ? d_alen_ + B : nullptr;
 }
 
-void Engine::run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
-                 const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers) {
+void Engine::run(const RunCall& call, mi355vits_result* out) {
     if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
     memset(out, 0, sizeof(*out));
-    synthesize(args, rows, nullptr, timing, speakers);
-    copy_out(args.flags, out);
+    synthesize(call, nullptr);
+    copy_out(call.args.flags, out);
 }
 
 void Engine::speaker_embedding(int64_t sid, float* out, size_t capacity) const {
@@ -1602,8 +1634,10 @@ void Engine::speaker_embedding(int64_t sid, float* out, size_t capacity) const {
     memcpy(out, model_->emb_g.data() + (size_t)sid * c.gin_channels, (size_t)c.gin_channels * sizeof(float));
 }
 
-// A speakers run's validation (mi355vits_speaker_args; everything is refused before a launch): what layout_a takes as `speakers`
-static int check_speakers(const mi355vits_config& c, const mi355vits_speaker_args& sp, int B) {
+// A speakers run's part of check_inputs: in.spk = the caller's struct, in.speakers = which of the two forms it is
+static void check_speakers(const mi355vits_config& c, const mi355vits_speaker_args& sp, RunInputs& in) {
+    const int B = in.B;
+    in.spk = sp;
     for (int i = 0; i < 6; ++i)
         if (sp.reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "speakers: reserved fields must be 0");
     if (c.n_speakers <= 1 || c.gin_channels < 1) throw EngineError(MI355VITS_ERR_INVALID, "speakers: voice has no speaker embedding");
@@ -1617,7 +1651,8 @@ static int check_speakers(const mi355vits_config& c, const mi355vits_speaker_arg
             for (int i = 0; i < gin; ++i)
                 if (!std::isfinite(sp.vectors[(size_t)b * gin + i]))
                     throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": speaker vector must be finite (channel " + std::to_string(i) + ")");
-        return -1;
+        in.speakers = RunInputs::SPK_VECTORS;
+        return;
     }
     if (!sp.mix_sid || !sp.mix_weight) throw EngineError(MI355VITS_ERR_INVALID, "speakers: mix_sid and mix_weight go together");
     const int K = sp.n_terms;
@@ -1637,19 +1672,15 @@ static int check_speakers(const mi355vits_config& c, const mi355vits_speaker_arg
         }
         if (!any) throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": every speaker weight is 0");
     }
-    return K;
+    in.speakers = RunInputs::SPK_MIX;
 }
 
-void Engine::speaker_cond_mix(int B, int spk) {
+// Every consumer's projection of the speaker vector g of each row (a multi-speaker voice only): a k_speaker_cond launch per consumer
+// from emb_g[sid], or in a speakers run k_speaker_cond_mix for all of them, which makes g from the mix tables or takes the vectors.
+void Engine::conditioning(const RunInputs& in) {
     const mi355vits_config& c = cfg_;
-    const int H = c.hidden_channels, gin = c.gin_channels;
-    SpeakerMixArgs m;
-    m.B = B; m.gin = gin; m.g = d_g_;
-    if (spk > 0) {
-        m.emb_g = vec("emb_g.weight"); m.sid = d_mix_sid_; m.weight = d_mix_w_; m.K = spk;
-    } else {
-        m.vectors = d_spk_vec_;
-    }
+    const int B = in.B, H = c.hidden_channels, gin = c.n_speakers > 1 ? c.gin_channels : 0;
+    if (!gin) return;
     std::vector<SpeakerMixJob> jobs;
     auto job = [&](const std::string& name, int Cout, float* out) {
         SpeakerMixJob j;
@@ -1659,6 +1690,19 @@ void Engine::speaker_cond_mix(int B, int spk) {
     job("dp.cond", H, d_cond_dp_);
     job("dec.cond", c.upsample_initial_channel, d_cond_dec_);
     for (int j = 0; j < c.flow_n_flows; ++j) job(S("flow.flows.%d", 2 * j) + ".enc.cond_layer", 2 * H * c.flow_wn_layers, d_cond_flow_[j]);
+    if (in.speakers == RunInputs::SPK_NONE) {
+        ProfScope ps(prof_, "speaker_cond");
+        for (const SpeakerMixJob& j : jobs) launch_speaker_cond(vec("emb_g.weight"), d_sid_, j.w, j.bias, B, gin, j.Cout, j.out, stream_);
+        return;
+    }
+    const bool mix = in.speakers == RunInputs::SPK_MIX;
+    SpeakerMixArgs m;
+    m.B = B; m.gin = gin; m.g = d_g_;
+    if (mix) {
+        m.emb_g = vec("emb_g.weight"); m.sid = d_mix_sid_; m.weight = d_mix_w_; m.K = in.spk.n_terms;
+    } else {
+        m.vectors = d_spk_vec_;
+    }
     // one launch (a voice with more than SPEAKER_MIX_MAX_JOBS - 2 flows: one per table-full)
     for (size_t q0 = 0; q0 < jobs.size(); q0 += SPEAKER_MIX_MAX_JOBS) {
         m.n_jobs = (int)std::min<size_t>(SPEAKER_MIX_MAX_JOBS, jobs.size() - q0);
@@ -1668,22 +1712,21 @@ void Engine::speaker_cond_mix(int B, int spk) {
             couts += m.jobs[q].Cout;
         }
         // the weights once, the tables (K gin table values or gin vector values per row), the outputs
-        const double bytes = 4.0 * couts * (gin + 1) + 4.0 * B * (double)(spk > 0 ? spk : 1) * gin + 4.0 * B * couts;
+        const double bytes = 4.0 * couts * (gin + 1) + 4.0 * B * (double)(mix ? in.spk.n_terms : 1) * gin + 4.0 * B * couts;
         ProfScope ps(prof_, "speaker_cond.mix", 2.0 * B * couts * gin, bytes);
         launch_speaker_cond_mix(m, stream_);
     }
     tap("g", d_g_, {B, gin, 1});
 }
 
-void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
-                        const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers) {
-    const mi355vits_config& c = cfg_;
+RunInputs check_inputs(const mi355vits_config& c, const RunCall& call) {
+    const mi355vits_run_args& args = call.args;
     if (args.batch < 1 || args.tx_max < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    const float* row_scales = rows ? rows->scales : nullptr;
+    const float* row_scales = call.rows ? call.rows->scales : nullptr;
     if (!args.ids || !args.lengths || (!args.scales && !row_scales))
         throw EngineError(MI355VITS_ERR_INVALID, "input, input_lengths and scales are required");
     const bool multi = c.n_speakers > 1;
-    if (multi && !args.sid && !speakers) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
+    if (multi && !args.sid && !call.speakers) throw EngineError(MI355VITS_ERR_INVALID, "multi-speaker voice: feed 'sid' is required");
     const int B = args.batch, Tx = args.tx_max;
     if ((long)B * Tx > (1L << 26)) throw EngineError(MI355VITS_ERR_INVALID, "batch * tx_max too large");
     if (Tx > rel_attention_valu_cap(c.hidden_channels, c.n_heads, c.window_size) &&
@@ -1691,11 +1734,20 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
         throw EngineError(MI355VITS_ERR_INVALID, "tx_max above " + std::to_string(rel_attention_valu_cap(c.hidden_channels, c.n_heads, c.window_size)) +
                                                  " ids needs the streamed attention kernel, which supports an even head width <= 128 and a "
                                                  "relative window <= 15 only");
-    // per-row settings: rows->* where given, else args' value broadcast to every row (row b keyed utterance_base + b)
-    std::vector<float> sc3((size_t)B * 3);
-    std::vector<double> vol(B);
-    std::vector<unsigned long long> utt(B);
-    bool any_noise_z = false;  // some row samples the prior noise (the only case that reads injected noise_z)
+    RunInputs in;
+    in.B = B;
+    in.Tx = Tx;
+    in.seed = args.seed;
+    in.flags = args.flags;
+    in.ids = args.ids;
+    in.sid = (multi && !call.speakers) ? args.sid : nullptr;
+    in.forced_durations = args.forced_durations;
+    in.noise_w = args.noise_w;
+    in.noise_z = args.noise_z;
+    in.noise_z_frames = args.noise_z_frames;
+    in.sc3.resize((size_t)B * 3);
+    in.vol.resize(B);
+    in.utt.resize(B);
     for (int b = 0; b < B; ++b) {
         const float* sc = row_scales ? row_scales + (size_t)b * 3 : args.scales;
         auto bad = [&](const char* what) {  // a per-row message names the row
@@ -1705,163 +1757,105 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
             if (!std::isfinite(sc[i])) throw bad("scales must be finite");
         if (sc[0] < 0 || sc[2] < 0) throw bad("noise scales must be >= 0");
         if (!(sc[1] > 0)) throw bad("length_scale must be > 0");
-        for (int i = 0; i < 3; ++i) sc3[(size_t)b * 3 + i] = sc[i];
-        any_noise_z = any_noise_z || sc[0] != 0.0f;
-        const double v = (rows && rows->pcm_volume) ? rows->pcm_volume[b] : args.pcm_volume;
-        vol[b] = (v > 0.0) ? v : 1.0;
-        utt[b] = (rows && rows->utterance) ? rows->utterance[b] : args.utterance_base + (unsigned long long)b;
+        for (int i = 0; i < 3; ++i) in.sc3[(size_t)b * 3 + i] = sc[i];
+        in.any_noise_z = in.any_noise_z || sc[0] != 0.0f;
+        const double v = (call.rows && call.rows->pcm_volume) ? call.rows->pcm_volume[b] : args.pcm_volume;
+        in.vol[b] = (v > 0.0) ? v : 1.0;
+        in.utt[b] = (call.rows && call.rows->utterance) ? call.rows->utterance[b] : args.utterance_base + (unsigned long long)b;
     }
-    std::vector<int> len32(B);
+    in.len32.resize(B);
     for (int b = 0; b < B; ++b) {
         if (args.lengths[b] < 0 || args.lengths[b] > Tx) throw EngineError(MI355VITS_ERR_INVALID, "input_lengths out of range");
-        len32[b] = (int)args.lengths[b];
-        for (int t = 0; t < len32[b]; ++t) {
+        in.len32[b] = (int)args.lengths[b];
+        for (int t = 0; t < in.len32[b]; ++t) {
             const int64_t id = args.ids[(long)b * Tx + t];
             if (id < 0 || id >= c.num_symbols) throw EngineError(MI355VITS_ERR_INVALID, "phoneme id out of range");
         }
-        if (multi && !speakers && (args.sid[b] < 0 || args.sid[b] >= c.n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "speaker id out of range");
+        if (in.sid && (in.sid[b] < 0 || in.sid[b] >= c.n_speakers)) throw EngineError(MI355VITS_ERR_INVALID, "speaker id out of range");
     }
     if (args.noise_z && args.noise_z_frames < 1) throw EngineError(MI355VITS_ERR_INVALID, "noise_z_frames must be >= 1");
-    // timing (mi355vits_run_timed): without any of the three inputs the run is the plain one, launch for launch
-    int tmask = 0;
-    if (timing) {
+    // timing (mi355vits_run_timed)
+    if (call.timing) {
+        const mi355vits_timing_args& tm = in.timing = *call.timing;
         for (int i = 0; i < 6; ++i)
-            if (timing->reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "timing: reserved fields must be 0");
-        tmask = (timing->stretch ? 1 : 0) | (timing->min_frames ? 2 : 0) | (timing->target_frames ? 4 : 0);
-        if (tmask && args.forced_durations) throw EngineError(MI355VITS_ERR_INVALID, "timing and forced_durations exclude each other");
+            if (tm.reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "timing: reserved fields must be 0");
+        if (in.timed() && args.forced_durations) throw EngineError(MI355VITS_ERR_INVALID, "timing and forced_durations exclude each other");
         for (int b = 0; b < B; ++b) {
             const std::string rowname = "row " + std::to_string(b);
-            for (int t = 0; t < len32[b]; ++t) {
+            for (int t = 0; t < in.len32[b]; ++t) {
                 const size_t i = (size_t)b * Tx + t;
-                if (timing->stretch && !(std::isfinite(timing->stretch[i]) && timing->stretch[i] >= 0.0f && timing->stretch[i] <= 1048576.0f))
+                if (tm.stretch && !(std::isfinite(tm.stretch[i]) && tm.stretch[i] >= 0.0f && tm.stretch[i] <= 1048576.0f))
                     throw EngineError(MI355VITS_ERR_INVALID, rowname + ", phoneme " + std::to_string(t) + ": stretch must be finite and within 0 .. 2^20");
-                if (timing->min_frames && (timing->min_frames[i] < 0 || timing->min_frames[i] > DURATION_FRAME_CAP))
+                if (tm.min_frames && (tm.min_frames[i] < 0 || tm.min_frames[i] > DURATION_FRAME_CAP))
                     throw EngineError(MI355VITS_ERR_INVALID, rowname + ", phoneme " + std::to_string(t) + ": min_frames must be within 0 .. " + std::to_string(DURATION_FRAME_CAP));
             }
-            if (timing->target_frames && (timing->target_frames[b] < 0 || timing->target_frames[b] > DURATION_FRAME_CAP))
+            if (tm.target_frames && (tm.target_frames[b] < 0 || tm.target_frames[b] > DURATION_FRAME_CAP))
                 throw EngineError(MI355VITS_ERR_INVALID, rowname + ": target_frames must be 0 (none) or within 1 .. " + std::to_string(DURATION_FRAME_CAP));
         }
     }
     // speakers (mi355vits_run_speakers): a blend or a vector per row in place of args.sid, which is then not read
-    const int spk = speakers ? check_speakers(c, *speakers, B) : 0;
+    if (call.speakers) check_speakers(c, *call.speakers, in);
+    return in;
+}
 
+void Engine::begin_run(const RunInputs& in) {
     HIP_CHECK(hipSetDevice(device_));
     have_result_ = false;
     have_edges_ = false;
     have_loud_ = false;
     have_tp_ = false;
-    taps_on_ = (args.flags & MI355VITS_DEBUG_TAPS) != 0;
+    taps_on_ = (in.flags & MI355VITS_DEBUG_TAPS) != 0;
     for (auto& t : taps_) (void)hipFree(t.dev);
     taps_.clear();
+}
 
-    const int H = c.hidden_channels, C0 = c.upsample_initial_channel;
-    const int gin = multi ? c.gin_channels : 0;
-
-    // ---------------- phase A workspace.  Sized with the optional inputs present: a handle that served a call without them does not
-    // reallocate when the next call brings them
-    const size_t fBT = (size_t)B * Tx;
+void Engine::upload_inputs(const RunInputs& in) {
     ArenaCount size_a;
-    layout_a(size_a, B, Tx, true, true, 7, -2);
+    layout_a(size_a, in, true);
     arena_a_.reserve(size_a.bytes + 4096, stream_);
     arena_a_.reset();
-    layout_a(arena_a_, B, Tx, args.forced_durations != nullptr, args.noise_w != nullptr, tmask, spk);
-    const size_t in_bytes = reinterpret_cast<unsigned char*>(d_ylen_) - reinterpret_cast<unsigned char*>(d_ids_);
-    timed_run_ = tmask != 0;
-
     HIP_CHECK(hipEventRecord(ev_start_, stream_));
-    timed_ = false;
-    {
-        h_in_.assign(in_bytes, 0);
-        unsigned char* h0 = h_in_.data();
-        auto put = [&](const void* dev, const void* src, size_t bytes) {
-            memcpy(h0 + (reinterpret_cast<const unsigned char*>(dev) - reinterpret_cast<const unsigned char*>(d_ids_)), src, bytes);
-        };
-        put(d_ids_, args.ids, fBT * 8);
-        put(d_len_, len32.data(), (size_t)B * 4);
-        if (multi && !spk) put(d_sid_, args.sid, (size_t)B * 8);
-        if (spk > 0) {
-            put(d_mix_sid_, speakers->mix_sid, (size_t)B * spk * 8);
-            put(d_mix_w_, speakers->mix_weight, (size_t)B * spk * 4);
-        } else if (spk < 0) {
-            put(d_spk_vec_, speakers->vectors, (size_t)B * c.gin_channels * 4);
-        }
-        put(d_scales_, sc3.data(), (size_t)B * 3 * 4);
-        put(d_vol_, vol.data(), (size_t)B * 8);
-        put(d_utt_, utt.data(), (size_t)B * 8);
-        if (args.forced_durations) put(d_forced_, args.forced_durations, fBT * 4);
-        if (args.noise_w) put(d_noise_w_, args.noise_w, fBT * 2 * 4);
-        if (d_stretch_) put(d_stretch_, timing->stretch, fBT * 4);
-        if (d_minf_) put(d_minf_, timing->min_frames, fBT * 4);
-        if (d_target_) put(d_target_, timing->target_frames, (size_t)B * 4);
-        // h_in_ is a member: it outlives the copy whatever HIP does with pageable sources
-        HIP_CHECK(hipMemcpyAsync(d_ids_, h0, in_bytes, hipMemcpyHostToDevice, stream_));
-    }
+    end_recorded_ = false;
+    layout_a(arena_a_, in, false);
+    // h_in_ is a member: it outlives the copy whatever HIP does with pageable sources
+    HIP_CHECK(hipMemcpyAsync(d_ids_, h_in_.data(), h_in_.size(), hipMemcpyHostToDevice, stream_));
+}
 
-    if (gin && spk) {
-        speaker_cond_mix(B, spk);
-    } else if (gin) {
-        ProfScope ps(prof_, "speaker_cond");
-        launch_speaker_cond(vec("emb_g.weight"), d_sid_, vec("dp.cond.weight"), vec("dp.cond.bias"), B, gin, H, d_cond_dp_, stream_);
-        launch_speaker_cond(vec("emb_g.weight"), d_sid_, vec("dec.cond.weight"), vec("dec.cond.bias"), B, gin, C0, d_cond_dec_, stream_);
-        for (int j = 0; j < c.flow_n_flows; ++j) {
-            const std::string f = S("flow.flows.%d", 2 * j);
-            launch_speaker_cond(vec("emb_g.weight"), d_sid_, vec(f + ".enc.cond_layer.weight"), vec(f + ".enc.cond_layer.bias"), B, gin,
-                                2 * H * c.flow_wn_layers, d_cond_flow_[j], stream_);
-        }
-    }
-
-    B_ = B;
-    Tx_ = Tx;
-    text_encoder(B, Tx);
-    duration_predictor(B, Tx, args);
-
-    // ---------------- the one host round trip: frame counts size the rest of the graph
-    // (a timed run: status and factor of every row sit right behind ylen and come in the same copy)
-    const size_t nread = timed_run_ ? 3 : 1;
+// The one host round trip: frame counts size the rest of the graph (a timed run: status and factor of every row sit right behind
+// ylen and come in the same copy).  Here, too, the two checks that need them.
+void Engine::read_frame_counts(const RunInputs& in) {
+    const int B = in.B;
+    const size_t nread = in.timed() ? 3 : 1;
     h_ylen_.resize(nread * B);
     HIP_CHECK(hipMemcpyAsync(h_ylen_.data(), d_ylen_, nread * B * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
-    if (timed_run_) {
+    if (in.timed()) {
         for (int b = 0; b < B; ++b) {
             const int st = h_ylen_[(size_t)B + b];
-            const std::string what = "row " + std::to_string(b) + ": target of " + std::to_string(timing->target_frames ? timing->target_frames[b] : 0) + " frames ";
+            const std::string what = "row " + std::to_string(b) + ": target of " + std::to_string(in.timing.target_frames ? in.timing.target_frames[b] : 0) + " frames ";
             if (st == TIMING_BELOW_FLOOR) throw EngineError(MI355VITS_ERR_INVALID, what + "is below the " + std::to_string(h_ylen_[b]) + " the row needs at least");
             if (st == TIMING_UNREACHABLE) throw EngineError(MI355VITS_ERR_INVALID, what + "cannot be reached: at the largest factor, 2^30, the row has " + std::to_string(h_ylen_[b]) + " (is every stretched duration 0?)");
             if (st != TIMING_OK) throw EngineError(MI355VITS_ERR_INTERNAL, "row " + std::to_string(b) + ": timing status " + std::to_string(st));
         }
-        if (timing->factor_out) memcpy(timing->factor_out, h_ylen_.data() + 2 * (size_t)B, (size_t)B * 4);
-    } else if (timing && timing->factor_out) {
-        std::fill(timing->factor_out, timing->factor_out + B, 1.0f);
+        if (in.timing.factor_out) memcpy(in.timing.factor_out, h_ylen_.data() + 2 * (size_t)B, (size_t)B * 4);
+    } else if (in.timing.factor_out) {
+        std::fill(in.timing.factor_out, in.timing.factor_out + B, 1.0f);
     }
     int Ty = 1;
     for (int b = 0; b < B; ++b) {
         if (h_ylen_[b] < 1 || h_ylen_[b] > DURATION_FRAME_CAP) throw EngineError(MI355VITS_ERR_INVALID, "predicted duration out of range (bad weights or length_scale?)");
         Ty = std::max(Ty, h_ylen_[b]);
     }
-    if (args.noise_z && any_noise_z && args.noise_z_frames < Ty)
+    if (in.noise_z && in.any_noise_z && in.noise_z_frames < Ty)
         throw EngineError(MI355VITS_ERR_INVALID, "noise_z has fewer frames than the utterance needs");
-    if (taps_on_) {
-        // w_ceil as floats for the tap interface
-        std::vector<int> wc(fBT);
-        HIP_CHECK(hipMemcpy(wc.data(), d_wceil_, fBT * 4, hipMemcpyDeviceToHost));
-        std::vector<float> wf32(wc.begin(), wc.end());
-        Tap t;
-        t.name = "w_ceil";
-        t.dims = {B, 1, Tx};
-        t.count = fBT;
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, fBT * 4 + 16));
-        t.dev = static_cast<float*>(p);
-        HIP_CHECK(hipMemcpy(t.dev, wf32.data(), fBT * 4, hipMemcpyHostToDevice));
-        taps_.push_back(std::move(t));
-    }
+    tap_ints("w_ceil", d_wceil_, {B, 1, in.Tx});
     Ty_ = Ty;
-    const long hop = c.hop_length;
+    const long hop = cfg_.hop_length;
     L_ = (long)Ty * hop;
     // the rows the caller receives: the waveform itself, or with an output rate set what the resampler makes of it — lengths from
-    // the frame counts, so its table rides in the upload below
+    // the frame counts, so its table rides in the stage table's upload
     const bool rs = out_hz_ != 0;
-    run_hz_ = rs ? out_hz_ : c.sample_rate;
+    run_hz_ = rs ? out_hz_ : cfg_.sample_rate;
     run_L_ = rs ? rs_.L : 1;
     run_M_ = rs ? rs_.M : 1;
     h_olen_.resize(B);
@@ -1873,16 +1867,17 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
             throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": " + std::to_string(h_olen_[b]) + " samples at " + std::to_string(run_hz_) + " Hz do not fit 32 bits");
         if (rs) Lo_ = std::max<long>(Lo_, (long)h_olen_[b]);
     }
-    if (plan) place(*plan);  // places from the frame counts just read (no early plan trims, normalises or compresses); the size limits, before phase B is sized
+}
 
-    // ---------------- phase B workspace
-    const size_t nz_frames = (args.noise_z && any_noise_z) ? (size_t)args.noise_z_frames : 0;
+void Engine::size_frame_side(const RunInputs& in, const OutputPlan* plan) {
+    const bool rs = out_hz_ != 0;
+    const size_t B = in.B, Lr = rs ? Lo_ : 0;
     ArenaCount size_b;
-    layout_b(size_b, B, Ty, nz_frames, rs ? Lo_ : 0);
+    layout_b(size_b, B, Ty_, in.noise_z_held(), Lr);
     if (plan) layout(size_b, *plan);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
-    layout_b(arena_b_, B, Ty, nz_frames, rs ? Lo_ : 0);
+    layout_b(arena_b_, B, Ty_, in.noise_z_held(), Lr);
     layout_b_end_ = arena_b_.used();
     o_audio_ = rs ? d_raudio_ : d_audio_;
     o_peaks_ = rs ? d_rpeaks_ : d_peaks_;
@@ -1890,46 +1885,71 @@ void Engine::synthesize(const mi355vits_run_args& args, const mi355vits_row_args
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
     if (plan) layout(arena_b_, *plan);
-    if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, args.noise_z, (size_t)B * c.inter_channels * nz_frames * 4, hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::upload_stage_table(const RunInputs& in, const OutputPlan* plan) {
+    const mi355vits_config& c = cfg_;
+    const int B = in.B;
+    const long hop = c.hop_length;
+    const bool rs = out_hz_ != 0;
+    if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, in.noise_z, (size_t)B * c.inter_channels * in.noise_z_held() * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     // (a plan's table sits right behind d_slen_ in the arena: the same copy brings it; no early block has a curve row)
     h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + plan->table_words() : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
     if (plan) fill_table(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
-    {
-        long f = 1;
-        for (int i = 0; i <= c.n_upsamples; ++i) {
-            for (int b = 0; b < B; ++b) h_slen_[(size_t)i * B + b] = (int)(h_ylen_[b] * f);
-            if (i < c.n_upsamples) f *= c.upsample_rates[i];
-        }
-        for (int b = 0; b < B; ++b) h_slen_[(size_t)(c.n_upsamples + 1) * B + b] = (int)(h_ylen_[b] * hop);
+    long f = 1;
+    for (int i = 0; i <= c.n_upsamples; ++i) {
+        for (int b = 0; b < B; ++b) h_slen_[(size_t)i * B + b] = (int)(h_ylen_[b] * f);
+        if (i < c.n_upsamples) f *= c.upsample_rates[i];
     }
-    long rs_items = 0;
-    if (rs) rs_items = resample_fill_tab(rs_, h_slen_.data() + (d_alen_ - d_slen_), B, h_slen_.data() + (d_rtab_ - d_slen_));
+    for (int b = 0; b < B; ++b) h_slen_[(size_t)(c.n_upsamples + 1) * B + b] = (int)(h_ylen_[b] * hop);
+    rs_items_ = !rs ? 0 : resample_fill_tab(rs_, h_slen_.data() + (d_alen_ - d_slen_), B, h_slen_.data() + (d_rtab_ - d_slen_));
     HIP_CHECK(hipMemcpyAsync(d_slen_, h_slen_.data(), h_slen_.size() * 4, hipMemcpyHostToDevice, stream_));
+}
 
-    flow_and_decoder(B, Ty, args);
-    if (rs) {
-        double n_in = 0, n_out = 0;
-        for (int b = 0; b < B; ++b) {
-            n_in += (double)h_ylen_[b] * hop;
-            n_out += (double)h_olen_[b];
-        }
-        ProfScope ps(prof_, "resample", 2.0 * rs_.tpp * n_out, 4.0 * n_in + 4.0 * n_out);
-        HIP_CHECK(hipMemsetAsync(d_rpeaks_, 0, sizeof(unsigned) * B, stream_));
-        launch_resample(rs_, d_rs_coef_, d_audio_, L_, d_alen_, B, d_rtab_, rs_items, d_raudio_, Lo_, (int)Lo_, d_rpeaks_, stream_);
+// a run at another rate than the voice's: d_audio_ -> d_raudio_ over the rs_items_ of the table uploaded with the stage lengths
+void Engine::resample() {
+    if (!out_hz_) return;
+    double n_in = 0, n_out = 0;
+    for (int b = 0; b < B_; ++b) {
+        n_in += (double)h_ylen_[b] * cfg_.hop_length;
+        n_out += (double)h_olen_[b];
     }
+    ProfScope ps(prof_, "resample", 2.0 * rs_.tpp * n_out, 4.0 * n_in + 4.0 * n_out);
+    HIP_CHECK(hipMemsetAsync(d_rpeaks_, 0, sizeof(unsigned) * B_, stream_));
+    launch_resample(rs_, d_rs_coef_, d_audio_, L_, d_alen_, B_, d_rtab_, rs_items_, d_raudio_, Lo_, (int)Lo_, d_rpeaks_, stream_);
+}
 
+void Engine::output(const RunInputs& in, const OutputPlan* plan) {
     have_pcm_ = false;
     if (plan) {
         launch(*plan);  // the packed stream or block and nothing else (the pack kernel alone: no early plan is compressed): MI355VITS_WANT_* / DEVICE_ONLY are not looked at
-    } else if (args.flags & MI355VITS_WANT_PCM16) {
-        ProfScope ps(prof_, "pcm16", 0, 6.0 * B * (double)Lo_);
-        launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, B, (int)Lo_, d_pcm_, Lo_, stream_, d_vol_);
+    } else if (in.flags & MI355VITS_WANT_PCM16) {
+        ProfScope ps(prof_, "pcm16", 0, 6.0 * in.B * (double)Lo_);
+        launch_pcm16(o_audio_, Lo_, o_peaks_, o_alen_, in.B, (int)Lo_, d_pcm_, Lo_, stream_, d_vol_);
         have_pcm_ = true;
     }
     HIP_CHECK(hipEventRecord(ev_end_, stream_));
-    timed_ = true;
+    end_recorded_ = true;
     have_result_ = true;
+}
+
+void Engine::synthesize(const RunCall& call, OutputPlan* plan) {
+    const RunInputs in = check_inputs(cfg_, call);  // invalid input is refused here: nothing of the last run has been touched
+    begin_run(in);
+    upload_inputs(in);
+    conditioning(in);
+    B_ = in.B;
+    Tx_ = in.Tx;
+    text_encoder(in.B, in.Tx);
+    duration_predictor(in);
+    read_frame_counts(in);
+    if (plan) place(*plan);  // places from the frame counts just read (no early plan trims, normalises or compresses); the size limits, before the frame side is sized
+    size_frame_side(in, plan);
+    upload_stage_table(in, plan);
+    flow_and_decoder(in);
+    resample();
+    output(in, plan);
 }
 
 }  // namespace m355

@@ -166,6 +166,47 @@ struct PackSettings {
     bool flac() const { return compress == MI355VITS_COMPRESS_FLAC; }
 };
 
+// ---------------------------------------------------------------- one run's inputs
+// What a run* entry point was called with, unchecked: the one form every run call of the engine takes.
+struct RunCall {
+    const mi355vits_run_args& args;
+    const mi355vits_row_args* rows = nullptr;          // per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
+    const mi355vits_timing_args* timing = nullptr;     // per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
+    const mi355vits_speaker_args* speakers = nullptr;  // a blend of speakers or a vector per row in place of args.sid (mi355vits_run_speakers), or NULL: args.sid
+};
+// What validation leaves of a RunCall: everything the rest of the call reads.  The pointers are the caller's arrays; one that is null
+// is an input the run does not have.
+struct RunInputs {
+    int B = 0, Tx = 0;
+    uint64_t seed = 0;
+    uint32_t flags = 0;
+    const int64_t* ids = nullptr;
+    const int64_t* sid = nullptr;           // null when not read: a single-speaker voice, a speakers run
+    std::vector<int> len32;                 // [B] the lengths in 32 bits
+    // per-row settings: rows->* where given, else args' value for every row (row b keyed utterance_base + b)
+    std::vector<float> sc3;                 // [B,3] noise_scale, length_scale, noise_w
+    std::vector<double> vol;                // [B] PCM volume (0 or less: 1)
+    std::vector<unsigned long long> utt;    // [B] Philox keys
+    const int32_t* forced_durations = nullptr;
+    const float* noise_w = nullptr;
+    const float* noise_z = nullptr;
+    int noise_z_frames = 0;
+    bool any_noise_z = false;               // some row samples the prior noise (the only case that reads injected noise_z)
+    // timing: the caller's struct (all null without one); each of stretch, min_frames and target_frames is there or not, and without
+    // any of them the run is the plain one, launch for launch
+    mi355vits_timing_args timing{};
+    bool timed() const { return timing.stretch || timing.min_frames || timing.target_frames; }
+    // speakers: args.sid (NONE), spk.n_terms terms per row of spk.mix_sid / mix_weight (MIX), or spk.vectors, one per row (VECTORS)
+    enum Speakers { SPK_NONE, SPK_MIX, SPK_VECTORS };
+    Speakers speakers = SPK_NONE;
+    mi355vits_speaker_args spk{};  // the caller's struct (all null without one)
+    // the frames of injected noise_z the frame side holds: none unless some row reads it
+    size_t noise_z_held() const { return (noise_z && any_noise_z) ? (size_t)noise_z_frames : 0; }
+};
+// A call's checks, in the order a caller sees their errors; pure host code: no engine state, no HIP call.  Throws EngineError.
+// (What only the frame counts can tell — a timing status, too few noise_z frames — is checked where they are read.)
+RunInputs check_inputs(const mi355vits_config& c, const RunCall& call);
+
 // ---------------------------------------------------------------- the engine
 class Engine {
   public:
@@ -180,27 +221,20 @@ class Engine {
     const std::shared_ptr<Model>& model() const { return model_; }
     // device pointers of the last run's results (valid until the next run on this handle); for device-side gathers
     void device_buffers(const int16_t** pcm, const float** audio, long* row_stride, int* batch, const int** dev_lengths);
-    // rows: per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
-    // timing: per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
-    // speakers: a blend of speakers or a vector per row in place of args.sid (mi355vits_run_speakers), or NULL: args.sid
-    void run(const mi355vits_run_args& args, const mi355vits_row_args* rows, mi355vits_result* out,
-             const mi355vits_timing_args* timing = nullptr, const mi355vits_speaker_args* speakers = nullptr);
+    void run(const RunCall& call, mi355vits_result* out);
     // row `sid` of emb_g from the host copy kept with the weight replica (mi355vits_get_speaker_embedding): no stream work
     void speaker_embedding(int64_t sid, float* out, size_t capacity) const;
     void fetch(uint32_t want, mi355vits_result* out);
     // the packed stream (mi355vits_run_packed / mi355vits_fetch_packed): pack == NULL = every row, in order, no silence, no header
-    void run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
-                    mi355vits_packed_result* out);
+    void run_packed(const RunCall& call, const mi355vits_pack_args* pack, mi355vits_packed_result* out);
     void fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out);
     // several streams out of one run (mi355vits_run_streams / mi355vits_fetch_streams): each with its own pack, encoding, trim and
     // loudness target; the handle's own settings are neither read nor changed
-    void run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
-                     mi355vits_streams_result* out);
+    void run_streams(const RunCall& call, const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out);
     void fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out);
     // the same with compression, limiter window and ceiling mode per stream (mi355vits_run_streams2 / mi355vits_fetch_streams2): NONE
     // of the handle's pack settings is read
-    void run_streams2(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args2* streams, int n_streams,
-                      mi355vits_streams_result2* out);
+    void run_streams2(const RunCall& call, const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out);
     void fetch_streams2(const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out);
     // phoneme timing (and, with MI355VITS_ALIGN_LEVELS, levels) of the last completed run (mi355vits_fetch_alignment)
     void fetch_alignment(uint32_t want, mi355vits_alignment* out);
@@ -269,18 +303,21 @@ class Engine {
     ConvKernel pick_conv(const ConvW& w, const ConvArgs& a) const;  // the kernel conv() runs the filled-in `a` on (callers may ask ahead)
     // row_len / factor: frame-resolution taps of a ragged batch are zeroed past len[b] * factor (those columns are not computed)
     void tap(const char* name, const float* dev, std::initializer_list<int64_t> dims, const int* row_len = nullptr, int factor = 1);
+    void tap_ints(const char* name, const int* dev, std::initializer_list<int64_t> dims);  // an int32 array as floats (synchronises)
+    Tap* new_tap(const char* name, std::initializer_list<int64_t> dims);  // what both start with; null: taps off, or the name taken
     void text_encoder(int B, int Tx);
-    void duration_predictor(int B, int Tx, const mi355vits_run_args& args);
-    void duration_predictor_det(int B, int Tx);
+    void duration_predictor(const RunInputs& in);
+    void duration_predictor_det(const RunInputs& in);
     void dds(const std::string& key, float* X, float* Y1, float* Y2, int B, int T);
-    void flow_and_decoder(int B, int Ty, const mi355vits_run_args& args);
+    void flow_and_decoder(const RunInputs& in);
     void coupling_layer(int j, int B, int Ty);
     void decoder_stage(int i, int B, int ch, long T);  // upsampler i on bufC [B,ch,T] -> bufA, its resblocks -> bufC
     int mrf_stage(int i, int B, int ch, long T);       // the stage's leading resblocks in one launch; how many it took
     ConvArgs rb2_conv_args(int i, int j, int m, int B, int ch, long T) const;
     // the workspace layouts: run against ArenaCount for the size, then against the arena (engine.cpp)
-    // timing: 1 stretch | 2 min_frames | 4 target_frames; speakers: 0 none, K = 1 .. 8 the mix tables, -1 the vectors, -2 both (sizing)
-    template <typename A> void layout_a(A& ar, size_t B, size_t Tx, bool forced, bool noise_w, int timing, int speakers);
+    // in: the run whose inputs head the layout (the input block, copied into h_in_ as it is laid out); widest: every optional input
+    // there, at its largest, and nothing copied (sizing)
+    template <typename A> void layout_a(A& ar, const RunInputs& in, bool widest);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
     template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
     // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
@@ -380,12 +417,21 @@ class Engine {
     void copy_out(uint32_t want, mi355vits_result* out);
     // one synthesis call up to the finished float audio (+ the padded int16 pass when the flags ask for it); with an output plan
     // the packed stream or block instead (its places made from the frame counts, its table uploaded with the per-stage lengths)
-    void synthesize(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan* plan,
-                    const mi355vits_timing_args* timing = nullptr, const mi355vits_speaker_args* speakers = nullptr);
-    // the conditioning of a speakers run: k_speaker_cond_mix in place of the k_speaker_cond launches (spk as layout_a's speakers)
-    void speaker_cond_mix(int B, int spk);
+    void synthesize(const RunCall& call, OutputPlan* plan);
+    // its steps, in order (text_encoder, duration_predictor and flow_and_decoder above among them)
+    void begin_run(const RunInputs& in);       // the last run's caches dropped, its taps freed
+    void upload_inputs(const RunInputs& in);   // the text side sized and laid out, the inputs in ONE copy
+    // the k_speaker_cond launches, or in a speakers run k_speaker_cond_mix in their place
+    void conditioning(const RunInputs& in);
     // k_durations, or in a timed run k_durations_timed in its place (the one call of both predictors)
-    void durations(int B, int Tx, int ch, float ea_m, float ea_logs);
+    void durations(const RunInputs& in, int ch, float ea_m, float ea_logs);
+    // the run's one sizing synchronisation: the frame counts (a timed run: its statuses, factor_out), Ty_ / L_, h_olen_ at the run's rate
+    void read_frame_counts(const RunInputs& in);
+    void size_frame_side(const RunInputs& in, const OutputPlan* plan);  // layout_b, and behind it the plan's layout
+    // injected noise_z, then per-stage lengths, audio lengths, a resampled run's table (rs_items_) and an early plan's table in ONE copy
+    void upload_stage_table(const RunInputs& in, const OutputPlan* plan);
+    void resample();
+    void output(const RunInputs& in, const OutputPlan* plan);  // the plan's pack kernel, or the padded int16 pass when the flags ask
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
     void plan_single(const mi355vits_pack_args* pack, int B, OutputPlan& op) const;  // a packed call's plan: plan_pack under the handle's settings
     // validates every stream, naming it (v1's streams arrive as v2 ones carrying the handle's window and mode, uncompressed)
@@ -402,7 +448,8 @@ class Engine {
     void finish_last_run(OutputPlan& op);
     // R: mi355vits_packed_result (single plans), mi355vits_streams_result or mi355vits_streams_result2
     template <typename R> void output_last_run(OutputPlan& op, R* out);  // finish_last_run, then the copy-out
-    template <typename R> void run_output(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan& op, R* out);
+    // what the three packed-form run calls are: the result struct zeroed, make_plan(op) (the form's validation), then the run
+    template <typename R, typename F> void run_output(const RunCall& call, R* out, F&& make_plan);
     // FLAC: the sizes first (ONE synchronisation more than uncompressed), then exactly the frames behind the header the host writes
     void copy_out_plan(OutputPlan& op, mi355vits_packed_result* out);
     template <typename R> void copy_out_plan(OutputPlan& op, R* out);  // the block of a streams call
@@ -441,7 +488,7 @@ class Engine {
     int device_ = 0;
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_start_ = nullptr, ev_end_ = nullptr;
-    bool timed_ = false;
+    bool end_recorded_ = false;  // ev_end_ of a completed run is on the stream: last_run_ms has something to read
     bool phase_b_ = false;       // inside flow_and_decoder (see Engine::fill_conv, pick_conv)
     LabSwitches sw_;
     int math_ = MATH_BF16X3;     // which matrix-core path the dense convs take (include/mi355vits.h: MI355VITS_MATH_*)
@@ -482,7 +529,6 @@ class Engine {
     // host), its status and factor per row; d_durf_ = the u[t] the fit ran on (the dur_float tap)
     float *d_stretch_ = nullptr, *d_tfactor_ = nullptr, *d_durf_ = nullptr;
     int *d_minf_ = nullptr, *d_target_ = nullptr, *d_tstatus_ = nullptr;
-    bool timed_run_ = false;
     // a speakers run's tables (in the one upload, like d_sid_) and the g [B, gin] its kernel leaves (the "g" tap)
     long long* d_mix_sid_ = nullptr;
     float *d_mix_w_ = nullptr, *d_spk_vec_ = nullptr, *d_g_ = nullptr;
@@ -534,6 +580,7 @@ class Engine {
     const unsigned* o_peaks_ = nullptr;
     const int* o_alen_ = nullptr;
     long Lo_ = 0;                  // row stride and l_max of the results
+    long rs_items_ = 0;            // a resampled run: the work items of its table (resample_fill_tab), for k_resample
     std::vector<int64_t> h_olen_;  // [B] valid samples of a row at the run's rate
     int* d_slen_ = nullptr;  // [n_upsamples + 1][B] valid frames per decoder stage
     // packed calls only, at the END of layout_b (every other pointer keeps its offset): the segment table right behind

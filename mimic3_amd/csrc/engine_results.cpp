@@ -326,14 +326,8 @@ void Engine::plan_single(const mi355vits_pack_args* pack, int B, OutputPlan& op)
     op.entries = op.streams[0].n;
 }
 
-void Engine::run_packed(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_pack_args* pack,
-                        mi355vits_packed_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    OutputPlan op;
-    plan_single(pack, args.batch, op);
-    run_output(args, rows, op, out);
+void Engine::run_packed(const RunCall& call, const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
+    run_output(call, out, [&](OutputPlan& op) { plan_single(pack, call.args.batch, op); });
 }
 
 void Engine::fetch_packed(const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
@@ -759,21 +753,27 @@ template <typename R> void Engine::copy_out_plan(OutputPlan& op, R* out) {
     for (size_t i = 0; i < E; ++i) memcpy(&out->peaks[i], &pk[out->rows[i]], 4);
 }
 
-// A run with an output plan.  No stream trims, normalises or compresses: the places follow from the frame counts, so the table rides
+// A run with an output plan, which make_plan fills from the form's own arguments (validating them) once the result struct is
+// zeroed and the batch known to be one.  No stream trims, normalises or compresses: the places follow from the frame counts, so the table rides
 // in the run's own upload and the pack kernel is its last launch.  Else the offsets / the scales depend on the audio and the frames
 // are made from the finished stream: synthesise without an early table (and without the padded int16 pass: a packed-form call looks at
 // no MI355VITS_WANT_* flag), then what the fetch of the same plan does.  A failure there — a limit exceeded by the trimmed sizes —
 // leaves the handle as a failed run does: no result served.
-template <typename R> void Engine::run_output(const mi355vits_run_args& args, const mi355vits_row_args* rows, OutputPlan& op, R* out) {
+template <typename R, typename F> void Engine::run_output(const RunCall& call, R* out, F&& make_plan) {
+    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
+    memset(out, 0, sizeof(*out));
+    if (call.args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
+    OutputPlan op;
+    make_plan(op);
     if (op.compressed()) check_flac_rate(output_rate());  // the rate this run will run at
     if (!op.measured() && !op.compressed()) {
-        synthesize(args, rows, &op);
+        synthesize(call, &op);
         copy_out_plan(op, out);
         return;
     }
-    mi355vits_run_args a = args;
+    mi355vits_run_args a = call.args;
     a.flags &= ~(uint32_t)MI355VITS_WANT_PCM16;
-    synthesize(a, rows, nullptr);
+    synthesize(RunCall{a, call.rows, call.timing, call.speakers}, nullptr);
     try {
         output_last_run(op, out);
         HIP_CHECK(hipEventRecord(ev_end_, stream_));  // the run's time includes its measurements and its pack
@@ -783,15 +783,11 @@ template <typename R> void Engine::run_output(const mi355vits_run_args& args, co
     }
 }
 
-void Engine::run_streams(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args* streams, int n_streams,
-                         mi355vits_streams_result* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    OutputPlan op;
-    const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
-    plan_streams(v.empty() ? nullptr : v.data(), n_streams, args.batch, op);
-    run_output(args, rows, op, out);
+void Engine::run_streams(const RunCall& call, const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out) {
+    run_output(call, out, [&](OutputPlan& op) {
+        const std::vector<mi355vits_stream_args2> v = streams_v1(streams, n_streams);
+        plan_streams(v.empty() ? nullptr : v.data(), n_streams, call.args.batch, op);
+    });
 }
 
 void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, mi355vits_streams_result* out) {
@@ -802,14 +798,8 @@ void Engine::fetch_streams(const mi355vits_stream_args* streams, int n_streams, 
     output_last_run(op, out);
 }
 
-void Engine::run_streams2(const mi355vits_run_args& args, const mi355vits_row_args* rows, const mi355vits_stream_args2* streams, int n_streams,
-                          mi355vits_streams_result2* out) {
-    if (!out) throw EngineError(MI355VITS_ERR_INVALID, "result pointer is null");
-    memset(out, 0, sizeof(*out));
-    if (args.batch < 1) throw EngineError(MI355VITS_ERR_INVALID, "batch and tx_max must be >= 1");
-    OutputPlan op;
-    plan_streams(streams, n_streams, args.batch, op);
-    run_output(args, rows, op, out);
+void Engine::run_streams2(const RunCall& call, const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out) {
+    run_output(call, out, [&](OutputPlan& op) { plan_streams(streams, n_streams, call.args.batch, op); });
 }
 
 void Engine::fetch_streams2(const mi355vits_stream_args2* streams, int n_streams, mi355vits_streams_result2* out) {

@@ -11,10 +11,13 @@ Then the result paths on that ragged batch (`digest pack ...` / `digest streams 
 run and fetch, each encoding, header, trim, target, limiter, true peak, FLAC, v1 and v2 streams — as the sha256 of its block and of
 every result array, with the profiler's (label, calls, bytes) of the call: the labels outside the synthesis graph spelled out, the
 graph's own as one hash.  `--emu` runs the result-path lines alone on the CPU model's library (tests/emu) with the tiny voice: the
-host code is the same, and the model is too slow for the full voices.
+host code is the same, and the model is too slow for the full voices.  Last the input forms (`digest inputs ...`) on a multi-speaker
+voice: per-row settings, forced durations, injected noise, each timing input, a speaker mix, speaker vectors, their combinations and
+every class of refused input, as the sha256 of each result array with every profiler label of the call.
 
 `bench` swaps the file bench.py opens (mimic3_amd/csrc/libmi355vits.so) — the product reads no library switch — and always puts NEW
-back at the end.  Output: one line per run with ms/step and the kernel table rows named in --rows.
+back at the end.  Output: one line per run with ms/step, the host side of a call (wall time minus device time, one handle) and the
+kernel table rows named in --rows; a run without a result line ends the A/B.
 """
 import argparse
 import json
@@ -84,8 +87,10 @@ def digest_results(sha, emu_root=None):
     eng.run(*run_args, seed=1234)
     graph = set(eng.profile_report())  # the labels of the synthesis itself
 
-    def prof():
+    def prof(full=False):
         rep = sorted((k, v["calls"], v["bytes"]) for k, v in eng.profile_report().items())
+        if full:  # the graph itself differs between the forms: every label spelled out
+            return "prof [" + " ".join(f"{k}:{c}:{b:.0f}" for k, c, b in rep) + "]"
         own = " ".join(f"{k}:{c}:{b:.0f}" for k, c, b in rep if k not in graph)
         return f"prof [{own}] graph {sha(np.frombuffer(repr([r for r in rep if r[0] in graph]).encode(), np.uint8))}"
 
@@ -105,6 +110,10 @@ def digest_results(sha, emu_root=None):
             got = call()
         except NativeError as e:
             print(f"digest {kind} {name}: error {e.code} {e}", flush=True)
+            return
+        if isinstance(got, dict):  # a padded run (the `inputs` lines): its arrays by name
+            named = " ".join(f"{k} {sha(got[k])}" for k in ("audio", "lengths", "pcm", "peaks", "timing_factor") if k in got)
+            print(f"digest {kind} {name}: {named} {prof(full=True)}", flush=True)
             return
         got = got if isinstance(got, list) else [got]
         whole = [np.asarray(got[0].block)] if getattr(got[0], "block", None) is not None else []
@@ -184,6 +193,111 @@ def digest_results(sha, emu_root=None):
     line("fail", "fetch_packed after it", lambda: eng.fetch_packed())
     line("fail", "run_streams block over the limit",
          lambda: eng.run_streams(*run_args, streams=[dict(order=[0], lead_samples=[HUGE // 2]), dict(order=[1], lead_samples=[HUGE // 2])], **run_kw))
+
+    # ---- the input forms (`digest inputs ...`): every optional input of a run on the same ragged batch, on a multi-speaker voice;
+    # each line the sha256 of every result array and the profiler's (label, calls, bytes) of the whole call
+    from mimic3_amd._native import SpeakerArgs
+
+    def speaker_args(n_terms=0, sid=None, weight=None, vectors=None, reserved=0):  # the struct as given, unchecked by the binding
+        s = SpeakerArgs()
+        s.n_terms, s.reserved[3] = n_terms, reserved
+        s.keep = [None if a is None else np.ascontiguousarray(a, t) for a, t in ((sid, np.int64), (weight, np.float32), (vectors, np.float32))]
+        if sid is not None:
+            s.mix_sid = s.keep[0].ctypes.data_as(type(s.mix_sid))
+        if weight is not None:
+            s.mix_weight = s.keep[1].ctypes.data_as(type(s.mix_weight))
+        if vectors is not None:
+            s.vectors = s.keep[2].ctypes.data_as(type(s.vectors))
+        return s
+
+    line("inputs", "fail speakers on a single-speaker voice", lambda: eng.run(*run_args, speakers=[0] * len(lens)))
+    eng.close()
+    cfg = VitsConfig.tiny(n_speakers=4) if emu_root else VitsConfig.vctk_low()
+    blob = W.pack(cfg, W.synthetic_weights(cfg, seed=11, frames_per_id=4.0))
+    eng = Engine(blob, device=0, library=lib)
+    eng.profile_enable(True)
+    B, S, gin = len(lens), cfg.n_speakers, cfg.gin_channels
+    sid = np.arange(B) % S
+    kw = dict(seed=1234, want_pcm16=True)
+    rows = dict(pcm_volume=np.linspace(0.5, 3.0, B), utterance_keys=[7, 7, 1 << 40, 3, 2, 1, 0, 99])
+    row_scales = np.stack([np.linspace(0.0, 0.9, B), np.linspace(0.7, 1.6, B), np.linspace(0.9, 0.0, B)], axis=1)
+    base = eng.run(ids, lens, run_args[2], sid, **kw)
+    frames = base["lengths"] // cfg.hop_length
+    stretch = rng.uniform(0.5, 2.0, (B, Tx)).astype(np.float32)
+    stretch[1, 0] = 0.0
+    min_frames = rng.integers(0, 6, (B, Tx)).astype(np.int32)
+    target = (frames * 5 // 4 + min_frames.sum(axis=1)).astype(np.int32)
+    target[2] = 0
+    noise_w = rng.standard_normal((B, 2, Tx)).astype(np.float32)
+    ty = int(eng.run(ids, lens, run_args[2], sid, noise_w=noise_w, **kw)["ty_max"])
+    noise_z = rng.standard_normal((B, cfg.inter_channels, ty + 3)).astype(np.float32)
+    mix = [{b % S: 0.7, (b + 1) % S: 0.0, (b + 2) % S: 0.3 + 0.1 * b} for b in range(B)]  # K = 3, a zero-weight term in every row
+    vectors = [eng.speaker_embedding(b % S) * np.float32(0.5 + 0.1 * b) for b in range(B)]
+    wide_z = rng.standard_normal((B, cfg.inter_channels, 4 * ty + int(min_frames.sum(axis=1).max()))).astype(np.float32)  # frames for the timed rows
+    everything = dict(noise_w=noise_w, noise_z=wide_z, stretch=stretch, min_frames=min_frames, target_frames=target, speakers=mix, **rows)
+
+    def run(*a, **k):
+        return lambda: eng.run(ids, lens, *a, **{**kw, **k})
+
+    line("inputs", "plain sid", run(run_args[2], sid))
+    line("inputs", "rows", run(row_scales, sid, **rows))
+    line("inputs", "forced_durations", run(run_args[2], sid, forced_durations=rng.integers(1, 7, (B, Tx))))
+    line("inputs", "noise_w noise_z", run(run_args[2], sid, noise_w=noise_w, noise_z=noise_z))
+    line("inputs", "timing stretch", run(run_args[2], sid, stretch=stretch))
+    line("inputs", "timing min_frames", run(run_args[2], sid, min_frames=min_frames))
+    line("inputs", "timing target_frames", run(run_args[2], sid, target_frames=target))
+    line("inputs", "timing all three", run(run_args[2], sid, stretch=stretch, min_frames=min_frames, target_frames=target))
+    line("inputs", "speakers mix K=3", run(run_args[2], speakers=mix))
+    line("inputs", "speakers vectors", run(run_args[2], speakers=vectors))
+    line("inputs", "rows timing mix", run(row_scales, stretch=stretch, target_frames=target, speakers=mix, **rows))
+    eng.close()
+    eng = Engine(blob, device=0, library=lib)  # a fresh handle: its first call sizes the text side, the second brings every input
+    eng.profile_enable(True)
+    line("inputs", "fresh handle: no optional input", run(run_args[2], sid))
+    line("inputs", "fresh handle: every compatible input", run(row_scales, **everything))
+    # failing calls, one per class of check, with code and text
+    bad_scales = row_scales.copy()
+    bad_scales[3, 1] = 0.0
+    bad_ids = ids.copy()
+    bad_ids[2, 0] = cfg.num_symbols
+    bad_stretch = stretch.copy()
+    bad_stretch[2, 1] = np.nan
+    w3 = np.full((B, 3), 0.5, np.float32)
+    s3 = np.tile(np.arange(3), (B, 1))
+
+    def edit(a, at, v, dtype=None):
+        a = np.array(a, dtype)
+        a[at] = v
+        return a
+
+    line("inputs", "fail row scales", run(bad_scales, sid))
+    line("inputs", "fail length", lambda: eng.run(ids, edit(lens, 4, Tx + 1), run_args[2], sid, **kw))
+    line("inputs", "fail phoneme id", lambda: eng.run(bad_ids, lens, run_args[2], sid, **kw))
+    line("inputs", "fail sid", run(run_args[2], edit(sid, 5, S)))
+    line("inputs", "fail noise_z_frames", run(run_args[2], sid, noise_z=noise_z[:, :, :0]))
+    line("inputs", "fail timing with forced_durations", run(run_args[2], sid, stretch=stretch, forced_durations=np.ones((B, Tx), np.int32)))
+    line("inputs", "fail stretch", run(run_args[2], sid, stretch=bad_stretch))
+    line("inputs", "fail min_frames", run(run_args[2], sid, min_frames=edit(min_frames, (6, 0), -1)))
+    line("inputs", "fail target_frames", run(run_args[2], sid, target_frames=edit(target, 7, -1)))
+    line("inputs", "fail speakers reserved", run(run_args[2], speakers=speaker_args(3, s3, w3, reserved=1)))
+    line("inputs", "fail speakers mix and vectors", run(run_args[2], speakers=speaker_args(3, s3, w3, np.zeros((B, gin)))))
+    line("inputs", "fail speakers neither", run(run_args[2], speakers=speaker_args()))
+    line("inputs", "fail speakers n_terms with vectors", run(run_args[2], speakers=speaker_args(2, vectors=np.zeros((B, gin)))))
+    line("inputs", "fail speakers vector not finite", run(run_args[2], speakers=speaker_args(vectors=edit(np.zeros((B, gin)), (1, 2), np.inf))))
+    line("inputs", "fail speakers mix_sid alone", run(run_args[2], speakers=speaker_args(3, sid=s3)))
+    line("inputs", "fail speakers n_terms 0", run(run_args[2], speakers=speaker_args(0, s3, w3)))
+    line("inputs", "fail speakers n_terms 9", run(run_args[2], speakers=speaker_args(9, s3, w3)))
+    line("inputs", "fail speakers weight not finite", run(run_args[2], speakers=speaker_args(3, s3, edit(w3, (4, 1), np.nan))))
+    line("inputs", "fail speakers weight beyond 1024", run(run_args[2], speakers=speaker_args(3, s3, edit(w3, (4, 2), -1025.0))))
+    line("inputs", "fail speakers sid", run(run_args[2], speakers=speaker_args(3, edit(s3, (0, 2), S), w3)))
+    line("inputs", "fail speakers every weight 0", run(run_args[2], speakers=speaker_args(3, s3, edit(w3, 5, 0.0))))
+    line("inputs", "fetch_packed after the refused calls", lambda: eng.fetch_packed())  # the last completed run is still served
+    line("inputs", "fail target below the floor", run(run_args[2], sid, min_frames=np.full((B, Tx), 50, np.int32), target_frames=edit(target, 0, 1)))
+    line("inputs", "fetch_packed after it", lambda: eng.fetch_packed())
+    # wrong in two ways at once: the order of the checks decides which error the caller sees
+    line("inputs", "fail scales and id", lambda: eng.run(bad_ids, lens, bad_scales, sid, **kw))
+    line("inputs", "fail stretch and speaker weight", run(run_args[2], stretch=bad_stretch, speakers=speaker_args(3, s3, edit(w3, (0, 0), np.nan))))
+    line("inputs", "fail missing sid and length", lambda: eng.run(ids, edit(lens, 0, -1), run_args[2], **kw))
     eng.close()
 
 
@@ -268,9 +382,12 @@ def main():
                     d = json.loads(pr.stdout.strip().splitlines()[-1])
                     rf = d.get("roofline", {})
                     rows = "  ".join(f"{k}={rf.get('ms:' + k)}" for k in a.rows.split(","))
-                    print(f"{tag} b{a.batch} round {r}: ms/step {d['ms_per_step']:.3f} | {rows}", flush=True)
+                    host = d.get("host_ms_per_step", {})  # one handle driven sequentially: the call's wall time minus its device time
+                    print(f"{tag} b{a.batch} round {r}: ms/step {d['ms_per_step']:.3f} host_side {host.get('host_side_ms', float('nan')):.3f} "
+                          f"(call {host.get('one_handle_call_ms', float('nan')):.3f} device {host.get('device_ms', float('nan')):.3f}) | {rows}", flush=True)
                 except Exception as ex:  # noqa: BLE001
                     print(f"{tag}: no bench line ({ex}); stderr tail: {pr.stderr[-400:]}", flush=True)
+                    sys.exit(1)  # nothing more is started on a device a run may have left in trouble (NEW is put back below)
     finally:
         shutil.copy2(keep, PRODUCT)
         os.remove(keep)
