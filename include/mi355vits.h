@@ -458,6 +458,57 @@ int mi355vits_run_speakers(mi355vits_handle h, const mi355vits_run_args* args, c
  * single-speaker voice: MI355VITS_ERR_INVALID. */
 int mi355vits_get_speaker_embedding(mi355vits_handle h, int64_t sid, float* out, size_t capacity);
 
+/* ---- Level control in one run: a gain per phoneme with exact ramps.  pcm_volume is one factor per row behind the int16
+ * normalisation and the loudness target one gain per row; what shapes a PART of a row — an SSML <prosody volume="+6dB"> or <emphasis>
+ * around two words, a breath turned down, a word muted — is an envelope over the waveform that follows the phoneme boundaries.
+ * mi355vits_run_levels is mi355vits_run_speakers with such an envelope applied where the waveform becomes known: ONE kernel
+ * (k_levels) over the native waveform on the device, in place, right behind conv_post / tanh and in front of everything that reads
+ * it.  The boundaries are the run's own (the inclusive scan of its frames, already in device memory); gain and ramp ride in the run's
+ * one upload: no synchronisation and no host round trip more than the plain run.
+ * The rule, exact (integers and singly rounded IEEE operations, no tolerance).  Per row b, in native-rate samples, with
+ * L = input_lengths[b], c[t] the inclusive scan of the run's frames (natural, forced_durations or a timed fit), hop = hop_length,
+ * n = hop * max(1, c[L-1]) the row's valid native samples (n = hop when L = 0), R = ramp_samples[b] and ONE = 2^20:
+ *     q[t]     = (int32) rintf(gain[b,t] * 1048576.0f)      the product is exact (a power of two); ties to even; 0 <= q <= 2^30
+ *     qs(i)    for 0 <= i < n: q[t(i)], t(i) = the smallest t < L with hop * c[t] > i (phonemes of zero frames own no sample);
+ *              ONE when there is no such t (a row whose durations sum to 0 still has one frame of audio);
+ *              qs(i) = qs(0) for i < 0, qs(n - 1) for i >= n (edge values repeat)
+ *     S[k]     = sum of qs(i) over k - R <= i <= k + R      int64: exact in any order
+ *     scale[k] = (float) ((double) S[k] / (double) ((2 R + 1) * 2^20))       one double division, one conversion
+ *     y[k]     = x[k] * scale[k]                            one f32 product, rounded to nearest; 0 <= k < n
+ *     peak[b]  = fmaxf chain over |y[k]| from 0.0f          as the waveform's own kernel takes it (a NaN is never taken)
+ * What follows:
+ *  1. Where every phoneme within R samples has gain 1.0, S = (2 R + 1) * 2^20 and scale = 1.0f exactly: those samples keep their
+ *     bits.  A run with every gain 1.0 is bitwise the plain run: audio, pcm, lengths and peaks.
+ *  2. Inside a phoneme and further than R from its ends, scale = (float) (q / 2^20): the double quotient is exact there.
+ *  3. Across a boundary the gain moves linearly over 2 R + 1 samples centred on it; R = 0 is a step.  A phoneme shorter than 2 R + 1
+ *     samples never reaches its own gain: that is the moving average, and it is the contract.  The fixed-point step is 2^-20, so a
+ *     gain below 2^-21 is a mute (2^-21 itself is a tie and rounds to 0).  A NaN sample stays a NaN, and +-Inf under a scale of 0
+ *     becomes one (IEEE's invalid product: its sign and payload are the platform's).
+ *  4. Nothing depends on the grid, the CU count, the batch, the row block or an address: a row of a batch is bitwise the row alone
+ *     (same noise key and tx_max class, see mi355vits_run_rows).
+ *  5. The envelope is applied to the native waveform.  At another output rate (mi355vits_set_output_rate) the result is the
+ *     resampler's output of the shaped native row; mi355vits_fetch_alignment's spans still say where the change lands, because the
+ *     resampler has zero delay.  `peaks`, the int16 normalisation, every packed / streams / FLAC form, mi355vits_fetch_edges,
+ *     _fetch_loudness, _fetch_limiter, _fetch_true_peak and the levels of mi355vits_fetch_alignment see the shaped waveform;
+ *     MI355VITS_WANT_FLOAT returns it.
+ *  - Scope: levels == NULL or levels->gain == NULL: the call IS mi355vits_run_speakers — the same launches, bytes and
+ *    synchronisations.  rows, timing, speakers, forced_durations and all flags combine with levels freely.  The packed, streams and
+ *    alignment forms need no call of their own: a MI355VITS_DEVICE_ONLY levels run followed by mi355vits_fetch_packed,
+ *    _fetch_streams, _fetch_streams2 or mi355vits_fetch_alignment gives them, as after a timed run.
+ *  - Errors, all MI355VITS_ERR_INVALID, raised before anything is launched (the previous run stays served): a gain that is not
+ *    finite, negative or above 1024, looked at where t < input_lengths[b] only (the message names the row and the phoneme); a ramp
+ *    outside 0 .. 4096 (the row); a non-zero reserved field.
+ *  - With profiling enabled the kernel is reported as "levels", bytes = 8 * sum(native lengths) + 4 * B * (tx_max + 1); a run
+ *    without levels has no such line. */
+typedef struct mi355vits_level_args {
+    const float*   gain;          /* [B, tx_max] or NULL (= 1): linear gain per phoneme; finite, 0 <= x <= 1024 (-0.0 is 0) */
+    const int32_t* ramp_samples;  /* [B] or NULL (= 0): R per row, 0 .. 4096 native-rate samples */
+    int32_t        reserved[6];   /* must be 0 */
+} mi355vits_level_args;
+int mi355vits_run_levels(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                         const mi355vits_timing_args* timing /* may be NULL */, const mi355vits_speaker_args* speakers /* may be NULL */,
+                         const mi355vits_level_args* levels /* may be NULL */, mi355vits_result* out);
+
 /* ---- Exact pauses: trim each entry's quiet edges in the packed streams.  A VITS voice puts a stretch of near-silence of its own at
  * the start and the end of every sentence; the reference adds its break (int(ms / 1000 * sample_rate) zero samples,
  * mimic3_tts/tts.py:452-465) on top of it, so a 250 ms break is heard as 250 ms plus two unknown tails.  With edge trimming on, an

@@ -341,6 +341,14 @@ typedef struct mi355vits_speaker_mix_test {
     size_t g_floats;
 } mi355vits_speaker_mix_test;
 int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test* t);
+/* Kernel unit-test hook: launch_levels (k_levels; include/mi355vits.h, level control in one run) alone, ONE launch, on host buffers:
+ * cum [B, T] (the inclusive scan of the frames; read below len[b] only, where it must not decrease), len [B] (0 .. T), gain [B, T]
+ * (0 .. 1024 below len[b]; anything behind), ramp [B] (0 .. 4096) or NULL (= 0), hop >= 1, alen [B] = hop * max(1, c[len - 1])
+ * (checked), audio [B] rows of audio_bs >= alen[b] floats, shaped in place.  audio holds audio_floats >= B * audio_bs floats: all of
+ * them go to the device first and come back, so a stray write behind a row or behind the last row shows.  Row b starts audio_bs * b
+ * floats behind a 256-byte aligned address: an odd audio_bs gives every alignment.  peaks [B]: max |y| of every row. */
+int mi355vits_test_levels(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* gain,
+                          const int32_t* ramp, const int32_t* alen, int64_t audio_bs, float* audio, size_t audio_floats, float* peaks);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
  * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
  * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros

@@ -32,7 +32,7 @@ HOOKS_LIBRARY = os.path.join(_HERE, "csrc", "libmi355vits_hooks.so")
 EXPORTED_SYMBOLS = (
     "mi355vits_version", "mi355vits_device_count", "mi355vits_create", "mi355vits_create_from_buffer", "mi355vits_clone", "mi355vits_destroy",
     "mi355vits_device_result", "mi355vits_set_math", "mi355vits_get_math",
-    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_run_speakers",
+    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_run_speakers", "mi355vits_run_levels",
     "mi355vits_get_speaker_embedding", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
@@ -57,7 +57,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
-    "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix",
+    "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix", "mi355vits_test_levels",
     "mi355vits_lab_conv_plan", "mi355vits_test_enc_o_ln", "mi355vits_test_conv_post",
 )
 
@@ -145,6 +145,14 @@ class SpeakerArgs(ctypes.Structure):  # mi355vits_speaker_args
 
 
 MAX_SPEAKER_TERMS = 8  # MI355VITS_MAX_SPEAKER_TERMS
+
+
+class LevelArgs(ctypes.Structure):  # mi355vits_level_args
+    _fields_ = [
+        ("gain", ctypes.POINTER(ctypes.c_float)),
+        ("ramp_samples", ctypes.POINTER(ctypes.c_int32)),
+        ("reserved", ctypes.c_int32 * 6),
+    ]
 
 
 class SpeakerMixTest(ctypes.Structure):  # mi355vits_speaker_mix_test (include/mi355vits_lab.h)
@@ -540,6 +548,8 @@ class NativeLibrary:
         L.mi355vits_run_speakers.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs),
                                              ctypes.POINTER(SpeakerArgs), ctypes.POINTER(Result)]
         L.mi355vits_get_speaker_embedding.argtypes = [H, ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
+        L.mi355vits_run_levels.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs),
+                                           ctypes.POINTER(SpeakerArgs), ctypes.POINTER(LevelArgs), ctypes.POINTER(Result)]
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
@@ -652,6 +662,7 @@ class NativeLibrary:
             L.mi355vits_test_fit_durations.argtypes = [ctypes.c_int] * 3 + [f32p, i32p, i32p, i32p, i32p, i32p, i32p, f32p, i32p]
             L.mi355vits_test_speaker_cond.argtypes = [ctypes.c_int] * 5 + [f32p, ctypes.POINTER(ctypes.c_int64), f32p, f32p, f32p, ctypes.c_size_t]
             L.mi355vits_test_speaker_cond_mix.argtypes = [ctypes.c_int, ctypes.POINTER(SpeakerMixTest)]
+            L.mi355vits_test_levels.argtypes = [ctypes.c_int] * 4 + [i32p, i32p, f32p, i32p, i32p, ctypes.c_int64, f32p, ctypes.c_size_t, f32p]
             L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
             L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
 
@@ -1155,6 +1166,26 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return frames, cum, ylen, factor, status
 
+    def test_levels(self, cum, lengths, gain, ramp, hop: int, audio, audio_bs: int, alen, device=0):
+        """launch_levels (k_levels) alone, one launch: cum [B, T] int32, lengths [B], gain [B, T], ramp [B] or None, audio a flat array
+        of at least B * ``audio_bs`` floats whose row b starts at ``b * audio_bs`` (all of it goes to the device and comes back), alen
+        [B] = hop * max(1, c[len - 1]) -> (audio after the launch, peaks [B]) (mi355vits_test_levels)."""
+        self._need_hooks()
+        cum, gain = np.ascontiguousarray(cum, np.int32), np.ascontiguousarray(gain, np.float32)
+        B, T = cum.shape
+        ln, al = np.ascontiguousarray(lengths, np.int32), np.ascontiguousarray(alen, np.int32)
+        rp = None if ramp is None else np.ascontiguousarray(ramp, np.int32)
+        out = np.array(audio, np.float32, copy=True).reshape(-1)
+        assert gain.shape == (B, T) and ln.shape == (B,) and al.shape == (B,) and (rp is None or rp.shape == (B,)) and out.size >= B * audio_bs
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        peaks = np.full(B, -7.5e29, np.float32)
+        rc = self.lib.mi355vits_test_levels(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p), _fptr(gain),
+                                            None if rp is None else rp.ctypes.data_as(i32p), al.ctypes.data_as(i32p), int(audio_bs),
+                                            _fptr(out), out.size, _fptr(peaks))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out, peaks
+
     def test_speaker_cond(self, emb_g, sid, w, bias=None, pad: int = 8, device=0) -> np.ndarray:
         """launch_speaker_cond (k_speaker_cond) alone: emb_g [S, gin], sid [B], w [Cout, gin], bias [Cout] or None -> out, B * Cout
         + ``pad`` floats that start as -7.5e29 (mi355vits_test_speaker_cond): ``out[:B * Cout].reshape(B, Cout)`` is the result."""
@@ -1459,7 +1490,7 @@ class Engine:
     def run(self, ids, lengths, scales, sid=None, *, seed: int = 0, utterance_base: int = 0, noise_w=None,
             noise_z=None, forced_durations=None, want_float: bool = True, want_pcm16: bool = False,
             device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None,
-            stretch=None, min_frames=None, target_frames=None, speakers=None) -> Dict[str, np.ndarray]:
+            stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None) -> Dict[str, np.ndarray]:
         """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
         ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
         its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class).
@@ -1469,15 +1500,25 @@ class Engine:
         ``speakers`` (``mi355vits_run_speakers``; a multi-speaker voice): one entry per row in place of ``sid``, which is then not
         read — an ``int`` (that speaker), a dict ``{sid: weight}`` (a blend, terms in the dict's order; weights need not sum to 1) or
         a 1-D float array of ``gin_channels`` values (the caller's own vector); ints and dicts may be mixed in one call, vectors go
-        in a call of their own (``ValueError`` otherwise).  ``SpeakerArgs`` itself is taken as it is."""
+        in a call of their own (``ValueError`` otherwise).  ``SpeakerArgs`` itself is taken as it is.
+        Levels (``mi355vits_run_levels``, when ``gain`` is given): ``gain`` [B, Tx] linear gain per phoneme (0 .. 1024) and
+        ``ramp_samples`` (an int or [B], 0 .. 4096 native-rate samples; default 0) the half-width of the linear ramp across every
+        phoneme boundary: the envelope is applied to the native waveform on the device, in front of everything that reads it.
+        ``LevelArgs`` itself is taken as ``gain``."""
         timing, tkeep = self._timing_args(np.shape(ids), stretch, min_frames, target_frames)
         spk, skeep = self._speaker_args(np.shape(ids), speakers)
+        lvl, lkeep = self._level_args(np.shape(ids), gain, ramp_samples)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
                   (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         r = Result()
-        if spk is not None:
+        if lvl is not None:
+            self._check(self.native.lib.mi355vits_run_levels(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                             ctypes.byref(timing) if timing is not None else None,
+                                                             ctypes.byref(spk) if spk is not None else None,
+                                                             ctypes.byref(lvl), ctypes.byref(r)))
+        elif spk is not None:
             self._check(self.native.lib.mi355vits_run_speakers(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                                ctypes.byref(timing) if timing is not None else None,
                                                                ctypes.byref(spk), ctypes.byref(r)))
@@ -1488,13 +1529,43 @@ class Engine:
             self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
         else:
             self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
-        del keep, skeep
+        del keep, skeep, lkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate  # read when the run started; only this thread sets it meanwhile
         out = self._take(r)
         if timing is not None:
             out["timing_factor"] = tkeep[-1]
         return out
+
+    @staticmethod
+    def _level_args(shape, gain, ramp_samples):
+        """``mi355vits_level_args`` (or None without ``gain``) + the arrays it points into.  Shapes are checked as ``stretch``'s is."""
+        if gain is None:
+            if ramp_samples is not None:
+                raise ValueError("ramp_samples needs gain")
+            return None, []
+        if isinstance(gain, LevelArgs):
+            return gain, []
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        B, Tx = shape
+        v, keep = LevelArgs(), []
+        gain = np.ascontiguousarray(gain, dtype=np.float32)
+        if gain.shape != (B, Tx):
+            raise ValueError("gain must have shape [batch, phonemes]")
+        keep.append(gain)
+        v.gain = _fptr(gain)
+        if ramp_samples is not None:
+            if not np.issubdtype(np.asarray(ramp_samples).dtype, np.integer):
+                raise ValueError("ramp_samples must hold integers")
+            r64 = np.asarray(ramp_samples, dtype=np.int64)
+            r64 = np.full(B, int(r64), np.int64) if r64.ndim == 0 else r64
+            if r64.shape != (B,):
+                raise ValueError("ramp_samples must be an int or have shape [batch]")
+            ramp = np.ascontiguousarray(np.clip(r64, -1, 2**31 - 1), dtype=np.int32)  # (out of range either way: the library names the row)
+            keep.append(ramp)
+            v.ramp_samples = ramp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        return v, keep
 
     def _speaker_args(self, shape, speakers):
         """``mi355vits_speaker_args`` (or None without ``speakers``) + the arrays it points into (``speaker_tables``)."""
@@ -1653,7 +1724,7 @@ class Engine:
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
                    debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE,
-                   stretch=None, min_frames=None, target_frames=None, speakers=None) -> PackedAudio:
+                   stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None) -> PackedAudio:
         """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
         ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
@@ -1664,13 +1735,13 @@ class Engine:
         With any of ``stretch`` / ``min_frames`` / ``target_frames`` (see ``run``): a timed run that keeps its audio on the device
         (``mi355vits_run_timed`` with ``MI355VITS_DEVICE_ONLY``), then ``fetch_packed`` of it — one synchronisation more; the
         factors are left in ``last_timing_factor``.  ``speakers`` (see ``run``) goes the same way: a speakers run that keeps its
-        audio on the device, then ``fetch_packed``."""
-        if stretch is not None or min_frames is not None or target_frames is not None or speakers is not None:
+        audio on the device, then ``fetch_packed``; so do ``gain`` / ``ramp_samples`` (``mi355vits_run_levels``)."""
+        if stretch is not None or min_frames is not None or target_frames is not None or speakers is not None or gain is not None or ramp_samples is not None:
             comp = self._call_compression(compression, wav)  # refuses wav + FLAC before anything runs
             res = self.run(ids, lengths, scales, sid, seed=seed, utterance_base=utterance_base, noise_w=noise_w, noise_z=noise_z,
                            forced_durations=forced_durations, want_float=False, want_pcm16=False, device_only=True,
                            debug_taps=debug_taps, pcm_volume=pcm_volume, utterance_keys=utterance_keys, stretch=stretch,
-                           min_frames=min_frames, target_frames=target_frames, speakers=speakers)
+                           min_frames=min_frames, target_frames=target_frames, speakers=speakers, gain=gain, ramp_samples=ramp_samples)
             self.last_timing_factor = res.get("timing_factor", self.last_timing_factor)
             return self.fetch_packed(order=order, lead_samples=lead_samples, tail_samples=tail_samples, wav=wav, compression=compression)
         comp = self._call_compression(compression, wav)

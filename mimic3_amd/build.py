@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
-SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_timing.cpp", "kernels_speaker.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "kernels_limit.cpp", "kernels_truepeak.cpp", "kernels_flac.cpp", "launch_util.cpp", "engine.cpp", "engine_results.cpp", "c_api.cpp"]
+SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_timing.cpp", "kernels_speaker.cpp", "kernels_level.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "kernels_limit.cpp", "kernels_truepeak.cpp", "kernels_flac.cpp", "launch_util.cpp", "engine.cpp", "engine_results.cpp", "c_api.cpp"]
 # csrc/lab_api.cpp = the hooks of include/mi355vits_lab.h (kernel unit tests, conv micro-benchmark, box probes): NOT in the product
 # library; linked with the product's own objects into libmi355vits_hooks.so, and compiled into the lab build and the CPU model
 HOOK_SOURCES = ["lab_api.cpp"]

@@ -1556,6 +1556,8 @@ template <typename A> void Engine::layout_a(A& ar, const RunInputs& in, bool wid
     field(d_mix_sid_, B * K, in.spk.mix_sid, widest && cond);
     field(d_mix_w_, B * K, in.spk.mix_weight, widest && cond);
     field(d_spk_vec_, B * gin, in.spk.vectors, widest && cond);
+    field(d_gain_, fBT, in.lvl.gain, widest);
+    field(d_ramp_, B, in.lvl.ramp_samples, widest || in.levelled());  // a levels run without ramps: zeros
     // what the host reads at the run's one sizing synchronisation: ylen, and of a timed run status and factor, in ONE copy (4-byte
     // words side by side: each of the three is B words)
     d_ylen_ = ar.template alloc<int>(3 * B);
@@ -1795,6 +1797,25 @@ RunInputs check_inputs(const mi355vits_config& c, const RunCall& call) {
     }
     // speakers (mi355vits_run_speakers): a blend or a vector per row in place of args.sid, which is then not read
     if (call.speakers) check_speakers(c, *call.speakers, in);
+    // levels (mi355vits_run_levels): a gain per phoneme, a ramp per row; without a gain the struct's ramps are not looked at
+    if (call.levels) {
+        const mi355vits_level_args& lv = *call.levels;
+        for (int i = 0; i < 6; ++i)
+            if (lv.reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "levels: reserved fields must be 0");
+        if (lv.gain) {
+            in.lvl = lv;
+            for (int b = 0; b < B; ++b) {
+                const std::string rowname = "row " + std::to_string(b);
+                for (int t = 0; t < in.len32[b]; ++t) {
+                    const float g = lv.gain[(size_t)b * Tx + t];
+                    if (!(std::isfinite(g) && g >= 0.0f && g <= 1024.0f))
+                        throw EngineError(MI355VITS_ERR_INVALID, rowname + ", phoneme " + std::to_string(t) + ": gain must be finite and within 0 .. 1024");
+                }
+                if (lv.ramp_samples && (lv.ramp_samples[b] < 0 || lv.ramp_samples[b] > LEVELS_MAX_RAMP))
+                    throw EngineError(MI355VITS_ERR_INVALID, rowname + ": ramp_samples must be within 0 .. " + std::to_string(LEVELS_MAX_RAMP));
+            }
+        }
+    }
     return in;
 }
 
@@ -1907,6 +1928,17 @@ void Engine::upload_stage_table(const RunInputs& in, const OutputPlan* plan) {
     HIP_CHECK(hipMemcpyAsync(d_slen_, h_slen_.data(), h_slen_.size() * 4, hipMemcpyHostToDevice, stream_));
 }
 
+// a levels run: the envelope of the gains over the phoneme boundaries in d_cum_ onto the native waveform, in place, in front of
+// everything that reads it; the row peaks are taken again from the shaped samples
+void Engine::levels(const RunInputs& in) {
+    if (!in.levelled()) return;
+    double n = 0;
+    for (int b = 0; b < in.B; ++b) n += (double)h_ylen_[b] * cfg_.hop_length;
+    ProfScope ps(prof_, "levels", 0, 8.0 * n + 4.0 * in.B * (double)(in.Tx + 1));
+    HIP_CHECK(hipMemsetAsync(d_peaks_, 0, sizeof(unsigned) * in.B, stream_));
+    launch_levels(d_cum_, d_len_, d_gain_, d_ramp_, in.B, in.Tx, cfg_.hop_length, d_audio_, L_, d_alen_, L_, d_peaks_, stream_);
+}
+
 // a run at another rate than the voice's: d_audio_ -> d_raudio_ over the rs_items_ of the table uploaded with the stage lengths
 void Engine::resample() {
     if (!out_hz_) return;
@@ -1948,6 +1980,7 @@ void Engine::synthesize(const RunCall& call, OutputPlan* plan) {
     size_frame_side(in, plan);
     upload_stage_table(in, plan);
     flow_and_decoder(in);
+    levels(in);
     resample();
     output(in, plan);
 }

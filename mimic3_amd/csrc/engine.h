@@ -173,6 +173,7 @@ struct RunCall {
     const mi355vits_row_args* rows = nullptr;          // per-row scales / volume / noise keys (mi355vits_run_rows), or NULL: args' own for every row
     const mi355vits_timing_args* timing = nullptr;     // per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
     const mi355vits_speaker_args* speakers = nullptr;  // a blend of speakers or a vector per row in place of args.sid (mi355vits_run_speakers), or NULL: args.sid
+    const mi355vits_level_args* levels = nullptr;      // a gain per phoneme and a ramp per row (mi355vits_run_levels), or NULL: the waveform as it is
 };
 // What validation leaves of a RunCall: everything the rest of the call reads.  The pointers are the caller's arrays; one that is null
 // is an input the run does not have.
@@ -200,6 +201,9 @@ struct RunInputs {
     enum Speakers { SPK_NONE, SPK_MIX, SPK_VECTORS };
     Speakers speakers = SPK_NONE;
     mi355vits_speaker_args spk{};  // the caller's struct (all null without one)
+    // levels: the caller's struct (all null without one); without a gain the run is the plain one, launch for launch
+    mi355vits_level_args lvl{};
+    bool levelled() const { return lvl.gain != nullptr; }
     // the frames of injected noise_z the frame side holds: none unless some row reads it
     size_t noise_z_held() const { return (noise_z && any_noise_z) ? (size_t)noise_z_frames : 0; }
 };
@@ -430,6 +434,8 @@ class Engine {
     void size_frame_side(const RunInputs& in, const OutputPlan* plan);  // layout_b, and behind it the plan's layout
     // injected noise_z, then per-stage lengths, audio lengths, a resampled run's table (rs_items_) and an early plan's table in ONE copy
     void upload_stage_table(const RunInputs& in, const OutputPlan* plan);
+    // a levels run: k_levels shapes d_audio_ in place and takes the row peaks again (kernels_level.cpp); else nothing
+    void levels(const RunInputs& in);
     void resample();
     void output(const RunInputs& in, const OutputPlan* plan);  // the plan's pack kernel, or the padded int16 pass when the flags ask
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
@@ -532,6 +538,9 @@ class Engine {
     // a speakers run's tables (in the one upload, like d_sid_) and the g [B, gin] its kernel leaves (the "g" tap)
     long long* d_mix_sid_ = nullptr;
     float *d_mix_w_ = nullptr, *d_spk_vec_ = nullptr, *d_g_ = nullptr;
+    // a levels run's gain [B, Tx] and ramp [B] (in the one upload)
+    float* d_gain_ = nullptr;
+    int* d_ramp_ = nullptr;
     float *d_x_ = nullptr, *d_x2_ = nullptr, *d_qkv_ = nullptr, *d_att_ = nullptr, *d_ffn_ = nullptr, *d_part_ = nullptr,
           *d_stats_ = nullptr;
     float *d_h_ = nullptr, *d_d0_ = nullptr, *d_d1_ = nullptr, *d_d2_ = nullptr, *d_theta_ = nullptr, *d_z2_ = nullptr,

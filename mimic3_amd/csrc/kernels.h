@@ -680,6 +680,22 @@ struct SpeakerMixArgs {
 };
 void launch_speaker_cond_mix(SpeakerMixArgs a, hipStream_t s);
 
+// ---------------------------------------------------------------- a gain per phoneme with exact ramps (kernels_level.cpp;
+// mi355vits_run_levels).  k_levels: ONE launch over the valid samples of every row of the native waveform, in place.  Per row b,
+// with c = cum[b, :] (the inclusive scan of the run's frames), L = len[b], n = alen[b] = hop * max(1, c[L - 1]), R = ramp[b]:
+//   q[t]  = (int) rintf(gain[b, t] * 2^20)                    0 <= gain <= 1024
+//   qs(i) = q[t(i)], t(i) = the smallest t < L with hop * c[t] > i; 2^20 when there is none; edge values repeat outside [0, n)
+//   S[k]  = sum of qs(i) over k - R <= i <= k + R              (int64)
+//   y[k]  = x[k] * (float) ((double) S[k] / (double) ((2 R + 1) * 2^20)),  0 <= k < n;  peak_bits[b] = the bits of max |y[k]|
+// peak_bits [B] must be zero before the launch (same stream); nothing outside [0, n) of a row is read or written; l_max = the
+// longest row.  No result depends on the grid, the batch, the row block or an address.
+constexpr int LEVELS_TILE = LIMIT_TILE;  // samples of a work item
+constexpr int LEVELS_TABLE = 1024;       // non-empty phonemes of a tile's reach staged in LDS at once (16 KiB); more: walked in chunks
+constexpr int LEVELS_ONE = 1 << 20;     // the fixed-point unit of a gain
+constexpr int LEVELS_MAX_RAMP = 4096;    // R: samples at the native rate
+void launch_levels(const int* cum, const int* len, const float* gain, const int* ramp /* null: 0 */, int B, int T, int hop,
+                   float* audio, long audio_bs, const int* alen, long l_max, unsigned* peak_bits, hipStream_t s);
+
 // misc
 void launch_fill(float* p, float v, size_t n, hipStream_t s);
 void launch_zero_row_tails(float* p, int B, int C, long T, const int* len, int factor, hipStream_t s);  // p[b, :, len[b] * factor:] = 0

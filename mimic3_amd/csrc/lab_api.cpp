@@ -1176,6 +1176,45 @@ int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test
     });
 }
 
+int mi355vits_test_levels(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* gain,
+                          const int32_t* ramp, const int32_t* alen, int64_t audio_bs, float* audio, size_t audio_floats, float* peaks) {
+    return guarded(nullptr, [&] {
+        if (!cum || !len || !gain || !alen || !audio || !peaks) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || hop < 1 || audio_bs < 1 || audio_floats < (size_t)B * (size_t)audio_bs) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        long l_max = 0;
+        for (int b = 0; b < B; ++b) {
+            const int L = len[b];
+            if (L < 0 || L > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+            for (int t = 0; t < L; ++t) {
+                const float g = gain[(size_t)b * T + t];
+                if (cum[(size_t)b * T + t] < (t ? cum[(size_t)b * T + t - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
+                if (!(std::isfinite(g) && g >= 0.0f && g <= 1024.0f)) throw EngineError(MI355VITS_ERR_INVALID, "gain out of range");
+            }
+            const long long frames = L > 0 ? cum[(size_t)b * T + L - 1] : 0;
+            const long long n = (long long)hop * (frames < 1 ? 1 : frames);
+            if (n > audio_bs || n > 0x7fffffffLL || alen[b] != n) throw EngineError(MI355VITS_ERR_INVALID, "alen must be hop * max(1, c[len - 1]) and fit the row");
+            if (ramp && (ramp[b] < 0 || ramp[b] > LEVELS_MAX_RAMP)) throw EngineError(MI355VITS_ERR_INVALID, "ramp out of range");
+            l_max = std::max<long>(l_max, (long)n);
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nbt = (size_t)B * T;
+        DevBuf dc(nbt * 4), dl((size_t)B * 4), dg(nbt * 4), dr((size_t)B * 4), da((size_t)B * 4), dx(audio_floats * 4), dp((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dg.p, gain, nbt * 4, hipMemcpyHostToDevice));
+        if (ramp) HIP_CHECK(hipMemcpy(dr.p, ramp, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(da.p, alen, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dx.p, audio, audio_floats * 4, hipMemcpyHostToDevice));  // everything: a stray write shows
+        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
+        launch_levels(dc.as<int>(), dl.as<int>(), dg.as<float>(), ramp ? dr.as<int>() : nullptr, B, T, hop, dx.as<float>(), (long)audio_bs,
+                      da.as<int>(), l_max, dp.as<unsigned>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(audio, dx.p, audio_floats * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z) {
     return guarded(nullptr, [&] {

@@ -753,7 +753,7 @@ class InferenceSession:
     # ---- engine extensions --------------------------------------------------------------------
     def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
                   sample_rate: Optional[int] = None, alignment=False, stretch=None, min_frames=None, target_frames=None,
-                  duration_ms=None, speakers=None):
+                  duration_ms=None, speakers=None, gain_db=None, ramp_ms=None):
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -778,7 +778,12 @@ class InferenceSession:
         may then be left out) — one entry per row: an ``int`` (that speaker), a dict ``{sid: weight}`` (a blend such as
         ``{12: 0.7, 40: 0.3}``, extrapolation such as ``{12: 1.5, 40: -0.5}`` included) or a 1-D float array of ``gin_channels``
         values (a vector of the caller's own: see ``speaker_embedding``).  Ints and dicts may be mixed in one call; vectors go in a
-        call of their own (``ValueError`` otherwise).  Such a call goes straight to a lane, never through the micro-batcher."""
+        call of their own (``ValueError`` otherwise).  Such a call goes straight to a lane, never through the micro-batcher.
+        Levels in the same run (``mi355vits_run_levels``): ``gain_db`` — one list per row or a [B, Tx] array — is the gain of each
+        phoneme in dB (``-inf`` mutes; converted as ``np.float32(10 ** (dB / 20))``; a list shorter than Tx leaves the rest at 0 dB),
+        ``ramp_ms`` (a number or [B]) the half-width of the linear ramp across every phoneme boundary,
+        ``round(ms / 1000 * sample_rate)`` samples at the voice's native rate (default 0: steps).  The envelope is applied to the
+        waveform on the GPU in front of the int16 conversion.  Such a call goes straight to a lane, never through the micro-batcher."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -786,7 +791,9 @@ class InferenceSession:
         kw.update(timing)
         if speakers is not None:
             kw["speakers"] = speakers
-        if alignment or timing or speakers is not None:
+        levels = self._levels_kw(input_feed, gain_db, ramp_ms)
+        kw.update(levels)
+        if alignment or timing or speakers is not None or levels:
             ids, lengths, sid = self._feed(input_feed, speakers is not None)
             keys = kw.pop("utterance_keys", None)
             out = self._engine_run(ids, lengths, input_feed["scales"], sid, utterance_keys=keys,
@@ -823,12 +830,47 @@ class InferenceSession:
             kw["target_frames"] = target_frames
         return kw
 
+    def _levels_kw(self, input_feed, gain_db, ramp_ms) -> Dict[str, np.ndarray]:
+        """The level keywords of ``Engine.run`` / ``run_packed`` (empty without ``gain_db``): ``gain`` [B, Tx] =
+        ``np.float32(10 ** (dB / 20))`` (``-inf`` dB = 0), ``ramp_samples`` [B] = ``round(ms / 1000 * sample_rate)`` at the voice's
+        native rate."""
+        if gain_db is None:
+            if ramp_ms is not None:
+                raise ValueError("ramp_ms needs gain_db")
+            return {}
+        shape = np.asarray(input_feed["input"]).shape
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        B, Tx = shape
+        db = np.zeros((B, Tx), np.float64)
+        rows = list(gain_db)
+        if len(rows) != B:
+            raise ValueError("gain_db must have one entry per row")
+        for b, r in enumerate(rows):
+            r = np.asarray(r, np.float64).reshape(-1)
+            if r.size > Tx:
+                raise ValueError("gain_db: a row has more entries than the feed has phonemes")
+            db[b, : r.size] = r
+        if np.any(np.isnan(db)) or np.any(db == np.inf):
+            raise ValueError("gain_db must be a number or -inf")
+        kw = {"gain": np.float32(10.0 ** (db / 20.0))}
+        if ramp_ms is not None:
+            ms = np.asarray(ramp_ms, np.float64)
+            ms = np.full(B, float(ms)) if ms.ndim == 0 else ms
+            if ms.shape != (B,):
+                raise ValueError("ramp_ms must be a number or have shape [batch]")
+            if not np.all(np.isfinite(ms)) or np.any(ms < 0):
+                raise ValueError("ramp_ms must be finite and >= 0")
+            kw["ramp_samples"] = np.array([int(round(m / 1000.0 * self.config.sample_rate)) for m in ms], np.int64)
+        return kw
+
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
                    limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION,
-                   stretch=None, min_frames=None, target_frames=None, duration_ms=None, speakers=None) -> "_native.PackedAudio":
+                   stretch=None, min_frames=None, target_frames=None, duration_ms=None, speakers=None, gain_db=None,
+                   ramp_ms=None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -866,7 +908,8 @@ class InferenceSession:
         "s16le" is refused by the library.
         ``stretch`` / ``min_frames`` / ``target_frames`` / ``duration_ms``: timing in the same run, as for ``run_pcm16`` (a timed run
         that keeps its audio on the device, then the pack: one synchronisation more).  ``speakers``: who speaks each row, as for
-        ``run_pcm16`` (likewise a run that keeps its audio on the device, then the pack)."""
+        ``run_pcm16`` (likewise a run that keeps its audio on the device, then the pack).  ``gain_db`` / ``ramp_ms``: a gain per
+        phoneme with ramps, as for ``run_pcm16`` (likewise); the trim, the loudness target and the limiter see the shaped waveform."""
         comp = self.output_compression if compression is _SESSION else _compression_name(compression)
         if comp and wav:
             raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
@@ -885,6 +928,7 @@ class InferenceSession:
         kw.update(self._timing_kw(input_feed, stretch, min_frames, target_frames, duration_ms))
         if speakers is not None:
             kw["speakers"] = speakers
+        kw.update(self._levels_kw(input_feed, gain_db, ramp_ms))
         if alignment:
             kw["_alignment"] = _alignment_levels(alignment)
         ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
