@@ -509,6 +509,64 @@ int mi355vits_run_levels(mi355vits_handle h, const mi355vits_run_args* args, con
                          const mi355vits_timing_args* timing /* may be NULL */, const mi355vits_speaker_args* speakers /* may be NULL */,
                          const mi355vits_level_args* levels /* may be NULL */, mi355vits_result* out);
 
+/* ---- Pitch control in one run: a ratio per phoneme, duration kept.  VITS has no pitch input; what an SSML <prosody pitch="+10%"> or
+ * a few semitones of emphasis wants is a phoneme synthesized p times longer and played back p times faster: its pitch is multiplied
+ * by p, its duration unchanged.  mi355vits_run_pitch is mi355vits_run_levels with both halves in the run: the stretch of a timed run
+ * (k_durations_timed, unchanged) and a band-limited variable-rate warp of the native waveform along the run's own phoneme boundaries
+ * (k_pitch_plan, k_pitch) on the device, in front of everything that reads the waveform.  THIS IS RESAMPLING: formants move with the
+ * pitch.  It is not a formant-preserving voice change.
+ * The rule, exact (integers and singly rounded IEEE f32 operations, never fused, no tolerance).  Per row b, with L = input_lengths[b],
+ * p[t] = ratio[b,t], hop = hop_length, ONE = 2^20, P = 128, Z = 12:
+ *  1. Duration compensation.  The run is a timed run whose stretch is fl(stretch[b,t] * p[t]) (ONE f32 product, made on the host;
+ *     stretch is 1 when absent).  With forced_durations the table IS the synthesized frames: no compensation, the row gets shorter
+ *     or longer.
+ *  2. The time map.  fs[t] the run's frames (natural, timed or forced), c their inclusive scan, n = hop * max(1, c[L-1]);
+ *         inv[t] = (int) rintf(1048576.0f / p[t])            one f32 division, ties to even; 2^19 .. 2^21, p = 1 gives ONE
+ *         Tq[t]  = sum over u <= t of hop * fs[u] * inv[u]   int64: exact in any order; Tq[-1] = 0
+ *         wc[t]  = ceil(Tq[t] / ONE)                         the warped boundaries;  wlen = wc[L-1] the warped row length
+ *     (a row without frames has one pseudo-phoneme of hop samples with inv = ONE).  Output sample k (0 <= k < wlen) lies in the
+ *     smallest t with Tq[t] > k * ONE; (q, r) = divmod(k * ONE - Tq[t-1], inv[t]), i0 = hop * c[t-1] + q: its source position is
+ *     i0 + r / inv[t].  The map is continuous and monotone across boundaries: no phase restart at a boundary.
+ *  3. The sample.  D = max(inv[t], ONE).  If inv[t] == ONE and r == 0: y[k] = x[i0], bits in, bits out (a select).  Otherwise, over
+ *     the source samples j ASCENDING with N = (i0 - j) * inv[t] + r and |N| < Z * D, x[j] = 0 by select outside [0, n):
+ *         (idx, rem) = divmod(|N| * P, D);  phi = (float) rem / (float) D
+ *         coef = fl(h[idx] + fl(phi * fl(h[idx+1] - h[idx])));  acc = fl(acc + fl(coef * x[j])), from 0.0f
+ *     y[k] = acc when inv[t] >= ONE, else fl(fl((float) inv[t] * 2^-20) * acc): Smith's stretched prototype, whose cut-off follows
+ *     the span's step, so a raised pitch does not alias.  peaks[b] = the fmaxf chain over |y|, as k_levels takes it.
+ *  4. The table.  h[i], i = 0 .. Z*P + 1, = the f32 rounding of sinc(i / P) * I0(8 sqrt(1 - (i / (Z P))^2)) / I0(8), computed in
+ *     double on the host when the handle is created; entries at multiples of P are exactly 0, h[0] = 1, h[Z*P] = h[Z*P+1] = 0.
+ * What follows:
+ *  - Every ratio 1.0 is bitwise the plain run: lengths, peaks and the valid samples of audio and pcm (behind a row's length, up to
+ *    l_max, a pitch run leaves zeros).
+ *  - Samples further than Z source samples from a span with p != 1 keep their bits.
+ *  - A row of a batch is bitwise the row alone, and permuting rows permutes results.  Nothing depends on the grid, the CU count, the
+ *    batch or an address.  A unit impulse returns bitwise the interpolated coefficients.
+ *  - Everything behind the waveform works on the warped rows, with lengths wlen (then ceil(wlen L / M) at another output rate):
+ *    MI355VITS_WANT_FLOAT and the int16 pass, k_resample, every packed / streams / FLAC form (a MI355VITS_DEVICE_ONLY pitch run, then
+ *    the fetch), mi355vits_fetch_edges, _fetch_loudness, _fetch_limiter and _fetch_true_peak.
+ *  - mi355vits_fetch_alignment reports frames = the synthesized frames (fed back as forced_durations with the same ratios they give
+ *    bitwise the same audio), start[t] = ceil(wc[t-1] L / M), samples[t] = ceil(wc[t] L / M) - start[t]: the spans still tile the row
+ *    and sum to lengths[b].
+ *  - k_levels runs BEFORE the warp, on the synthesized waveform: its ramp of R samples lasts R / p samples in the result.
+ *  - No synchronisation and no host round trip more than the plain run: the warped lengths ride in the run's one sizing copy.
+ *  - Scope: pitch == NULL or pitch->ratio == NULL: the call IS mi355vits_run_levels — the same launches, bytes and synchronisations.
+ *  - Errors, all MI355VITS_ERR_INVALID, raised before anything is launched (the previous run stays served): a ratio that is not
+ *    finite or lies outside [0.5, 2], looked at where t < input_lengths[b] only (the message names row and phoneme); a product
+ *    stretch * ratio above 2^20 (row and phoneme); a row with target_frames[b] != 0 and a ratio other than 1.0 ("row 3: a fitted
+ *    length and a pitch ratio exclude each other": the fit counts synthesized frames, a warped row could not meet it exactly); a
+ *    non-zero reserved field.  At the sizing synchronisation: a warped row that does not fit 32 bits (the message names the row).
+ *  - With profiling enabled the kernels are reported as "pitch.plan" and "pitch", the latter with
+ *    bytes = 4 * (sum n + sum wlen) + 20 * B * tx_max; a run without pitch has no such lines.  Under MI355VITS_DEBUG_TAPS a pitch run
+ *    also serves "audio_synth" [B, 1, L]: the waveform in front of the warp. */
+typedef struct mi355vits_pitch_args {
+    const float* ratio;        /* [B, tx_max] or NULL (= 1): pitch multiplier per phoneme; finite, 0.5 <= x <= 2 */
+    int32_t      reserved[7];  /* must be 0 */
+} mi355vits_pitch_args;
+int mi355vits_run_pitch(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows /* may be NULL */,
+                        const mi355vits_timing_args* timing /* may be NULL */, const mi355vits_speaker_args* speakers /* may be NULL */,
+                        const mi355vits_level_args* levels /* may be NULL */, const mi355vits_pitch_args* pitch /* may be NULL */,
+                        mi355vits_result* out);
+
 /* ---- Exact pauses: trim each entry's quiet edges in the packed streams.  A VITS voice puts a stretch of near-silence of its own at
  * the start and the end of every sentence; the reference adds its break (int(ms / 1000 * sample_rate) zero samples,
  * mimic3_tts/tts.py:452-465) on top of it, so a 250 ms break is heard as 250 ms plus two unknown tails.  With edge trimming on, an

@@ -349,6 +349,23 @@ int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test
  * floats behind a 256-byte aligned address: an odd audio_bs gives every alignment.  peaks [B]: max |y| of every row. */
 int mi355vits_test_levels(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* gain,
                           const int32_t* ramp, const int32_t* alen, int64_t audio_bs, float* audio, size_t audio_floats, float* peaks);
+/* Kernel unit-test hooks of pitch control (include/mi355vits.h, mi355vits_run_pitch; kernels_pitch.cpp).
+ * mi355vits_test_pitch_table: the filter table h the handles use, Z P + 2 = 1,538 floats (capacity: floats `out` can take).
+ * mi355vits_test_pitch_plan: launch_pitch_plan (k_pitch_plan) alone, ONE launch: cum [B, T] (read below len[b] only, where it must
+ * not decrease), len [B] (0 .. T), ratio [B, T] (0.5 .. 2 below len[b]) or NULL (= 1), hop >= 1 -> tq [B, T] (int64), wc [B, T],
+ * wlen [B] (wc and wlen saturate at 2^31 - 1).
+ * mi355vits_test_pitch: the plan, then launch_pitch (k_pitch), one launch each, on host buffers: x [B] rows of x_bs floats, of which
+ * hop * max(1, c[len - 1]) are the row (must fit x_bs); y [B] rows of y_bs floats, y_ld <= y_bs of each written (the warped row, then
+ * zeros), y_ld >= every wlen[b] (checked; a saturated row is refused).  x holds x_floats >= B * x_bs and y y_floats >= B * y_bs
+ * floats: all of y goes to the device first and comes back, so a stray write behind a row's y_ld or behind the last row shows.  Row b
+ * of x and of y starts x_bs * b / y_bs * b floats behind a 256-byte aligned address: odd strides give every alignment.
+ * peaks [B]: max |y| of every row; wlen [B]: the warped lengths. */
+int mi355vits_test_pitch_table(float* out, size_t capacity);
+int mi355vits_test_pitch_plan(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* ratio,
+                              int64_t* tq, int32_t* wc, int32_t* wlen);
+int mi355vits_test_pitch(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* ratio,
+                         const float* x, int64_t x_bs, size_t x_floats, float* y, int64_t y_bs, int32_t y_ld, size_t y_floats,
+                         float* peaks, int32_t* wlen);
 /* Kernel unit-test hook: the product's resampler launch (k_resample, mi355vits_set_output_rate) on host buffers.  x [B] rows of
  * row_stride floats, lengths [B] (0 <= lengths[b] <= row_stride) valid samples of each; what lies past a row's length is never
  * looked at.  y [B] rows of y_stride floats, y_stride >= max_b ceil(lengths[b] * L / M): every sample of it is written (zeros

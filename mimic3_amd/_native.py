@@ -32,7 +32,7 @@ HOOKS_LIBRARY = os.path.join(_HERE, "csrc", "libmi355vits_hooks.so")
 EXPORTED_SYMBOLS = (
     "mi355vits_version", "mi355vits_device_count", "mi355vits_create", "mi355vits_create_from_buffer", "mi355vits_clone", "mi355vits_destroy",
     "mi355vits_device_result", "mi355vits_set_math", "mi355vits_get_math",
-    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_run_speakers", "mi355vits_run_levels",
+    "mi355vits_get_config", "mi355vits_run", "mi355vits_run_rows", "mi355vits_run_timed", "mi355vits_run_speakers", "mi355vits_run_levels", "mi355vits_run_pitch",
     "mi355vits_get_speaker_embedding", "mi355vits_fetch", "mi355vits_free_result",
     "mi355vits_last_error", "mi355vits_profile_enable", "mi355vits_profile_reset",
     "mi355vits_profile_report", "mi355vits_last_run_ms", "mi355vits_get_tap", "mi355vits_get_tap_rows", "mi355vits_list_taps",
@@ -58,6 +58,7 @@ LAB_SYMBOLS = (
     "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
     "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix", "mi355vits_test_levels",
+    "mi355vits_test_pitch_table", "mi355vits_test_pitch_plan", "mi355vits_test_pitch",
     "mi355vits_lab_conv_plan", "mi355vits_test_enc_o_ln", "mi355vits_test_conv_post",
 )
 
@@ -152,6 +153,13 @@ class LevelArgs(ctypes.Structure):  # mi355vits_level_args
         ("gain", ctypes.POINTER(ctypes.c_float)),
         ("ramp_samples", ctypes.POINTER(ctypes.c_int32)),
         ("reserved", ctypes.c_int32 * 6),
+    ]
+
+
+class PitchArgs(ctypes.Structure):  # mi355vits_pitch_args
+    _fields_ = [
+        ("ratio", ctypes.POINTER(ctypes.c_float)),
+        ("reserved", ctypes.c_int32 * 7),
     ]
 
 
@@ -550,6 +558,9 @@ class NativeLibrary:
         L.mi355vits_get_speaker_embedding.argtypes = [H, ctypes.c_int64, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
         L.mi355vits_run_levels.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs),
                                            ctypes.POINTER(SpeakerArgs), ctypes.POINTER(LevelArgs), ctypes.POINTER(Result)]
+        L.mi355vits_run_pitch.argtypes = [H, ctypes.POINTER(RunArgs), ctypes.POINTER(RowArgs), ctypes.POINTER(TimingArgs),
+                                          ctypes.POINTER(SpeakerArgs), ctypes.POINTER(LevelArgs), ctypes.POINTER(PitchArgs),
+                                          ctypes.POINTER(Result)]
         L.mi355vits_fetch.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(Result)]
         L.mi355vits_free_result.argtypes = [ctypes.POINTER(Result)]
         L.mi355vits_free_result.restype = None
@@ -663,6 +674,10 @@ class NativeLibrary:
             L.mi355vits_test_speaker_cond.argtypes = [ctypes.c_int] * 5 + [f32p, ctypes.POINTER(ctypes.c_int64), f32p, f32p, f32p, ctypes.c_size_t]
             L.mi355vits_test_speaker_cond_mix.argtypes = [ctypes.c_int, ctypes.POINTER(SpeakerMixTest)]
             L.mi355vits_test_levels.argtypes = [ctypes.c_int] * 4 + [i32p, i32p, f32p, i32p, i32p, ctypes.c_int64, f32p, ctypes.c_size_t, f32p]
+            L.mi355vits_test_pitch_table.argtypes = [f32p, ctypes.c_size_t]
+            L.mi355vits_test_pitch_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p, f32p, ctypes.POINTER(ctypes.c_int64), i32p, i32p]
+            L.mi355vits_test_pitch.argtypes = [ctypes.c_int] * 4 + [i32p, i32p, f32p, f32p, ctypes.c_int64, ctypes.c_size_t, f32p, ctypes.c_int64,
+                                               ctypes.c_int32, ctypes.c_size_t, f32p, i32p]
             L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
             L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
 
@@ -1186,6 +1201,54 @@ class NativeLibrary:
             raise NativeError(rc, self.create_error())
         return out, peaks
 
+    def test_pitch_table(self) -> np.ndarray:
+        """The filter table of pitch control, Z P + 2 = 1,538 floats (mi355vits_test_pitch_table)."""
+        self._need_hooks()
+        out = np.zeros(12 * 128 + 2, np.float32)
+        rc = self.lib.mi355vits_test_pitch_table(_fptr(out), out.size)
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out
+
+    def test_pitch_plan(self, cum, lengths, ratio, hop: int, device=0):
+        """launch_pitch_plan (k_pitch_plan) alone: cum [B, T] int32, lengths [B], ratio [B, T] or None -> (tq [B, T] int64,
+        wc [B, T] int32, wlen [B] int32) (mi355vits_test_pitch_plan)."""
+        self._need_hooks()
+        cum = np.ascontiguousarray(cum, np.int32)
+        B, T = cum.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        rt = None if ratio is None else np.ascontiguousarray(ratio, np.float32)
+        assert ln.shape == (B,) and (rt is None or rt.shape == (B, T))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        tq, wc, wlen = np.full((B, T), -1, np.int64), np.full((B, T), -1, np.int32), np.full(B, -1, np.int32)
+        rc = self.lib.mi355vits_test_pitch_plan(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p),
+                                                None if rt is None else _fptr(rt), tq.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                wc.ctypes.data_as(i32p), wlen.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return tq, wc, wlen
+
+    def test_pitch(self, cum, lengths, ratio, hop: int, x, x_bs: int, y, y_bs: int, y_ld: int, device=0):
+        """The plan, then launch_pitch (k_pitch), on host buffers: x a flat array of at least B * ``x_bs`` floats whose row b starts
+        at ``b * x_bs``, y likewise with ``y_bs`` (all of it goes to the device and comes back; ``y_ld`` floats of each row are
+        written) -> (y after the launch, peaks [B], wlen [B]) (mi355vits_test_pitch)."""
+        self._need_hooks()
+        cum = np.ascontiguousarray(cum, np.int32)
+        B, T = cum.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        rt = None if ratio is None else np.ascontiguousarray(ratio, np.float32)
+        xin = np.ascontiguousarray(x, np.float32).reshape(-1)
+        out = np.array(y, np.float32, copy=True).reshape(-1)
+        assert ln.shape == (B,) and (rt is None or rt.shape == (B, T)) and xin.size >= B * x_bs and out.size >= B * y_bs
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        peaks, wlen = np.full(B, -7.5e29, np.float32), np.full(B, -1, np.int32)
+        rc = self.lib.mi355vits_test_pitch(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p),
+                                           None if rt is None else _fptr(rt), _fptr(xin), int(x_bs), xin.size, _fptr(out), int(y_bs),
+                                           int(y_ld), out.size, _fptr(peaks), wlen.ctypes.data_as(i32p))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out, peaks, wlen
+
     def test_speaker_cond(self, emb_g, sid, w, bias=None, pad: int = 8, device=0) -> np.ndarray:
         """launch_speaker_cond (k_speaker_cond) alone: emb_g [S, gin], sid [B], w [Cout, gin], bias [Cout] or None -> out, B * Cout
         + ``pad`` floats that start as -7.5e29 (mi355vits_test_speaker_cond): ``out[:B * Cout].reshape(B, Cout)`` is the result."""
@@ -1490,7 +1553,8 @@ class Engine:
     def run(self, ids, lengths, scales, sid=None, *, seed: int = 0, utterance_base: int = 0, noise_w=None,
             noise_z=None, forced_durations=None, want_float: bool = True, want_pcm16: bool = False,
             device_only: bool = False, debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None,
-            stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None) -> Dict[str, np.ndarray]:
+            stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None,
+            pitch=None) -> Dict[str, np.ndarray]:
         """One synthesis call.  Per-row settings (``mi355vits_run_rows``): ``scales`` [B, 3], ``pcm_volume`` [B] and
         ``utterance_keys`` [B] (Philox utterance index of each row, instead of ``utterance_base + b``).  Row b is then bitwise
         its own call with scalar settings and ``utterance_base = utterance_keys[b]`` (same phoneme-length class).
@@ -1504,16 +1568,27 @@ class Engine:
         Levels (``mi355vits_run_levels``, when ``gain`` is given): ``gain`` [B, Tx] linear gain per phoneme (0 .. 1024) and
         ``ramp_samples`` (an int or [B], 0 .. 4096 native-rate samples; default 0) the half-width of the linear ramp across every
         phoneme boundary: the envelope is applied to the native waveform on the device, in front of everything that reads it.
-        ``LevelArgs`` itself is taken as ``gain``."""
+        ``LevelArgs`` itself is taken as ``gain``.
+        Pitch (``mi355vits_run_pitch``, when ``pitch`` is given): ``pitch`` [B, Tx] the pitch multiplier of each phoneme (0.5 .. 2);
+        the duration is kept (the run stretches each phoneme by its ratio and the device warps the waveform back), except with
+        ``forced_durations``, whose frames are the synthesized ones.  This is resampling: formants move with the pitch.
+        ``PitchArgs`` itself is taken as it is."""
         timing, tkeep = self._timing_args(np.shape(ids), stretch, min_frames, target_frames)
         spk, skeep = self._speaker_args(np.shape(ids), speakers)
         lvl, lkeep = self._level_args(np.shape(ids), gain, ramp_samples)
+        pit, pkeep = self._pitch_args(np.shape(ids), pitch)
         a, rows, per_row, keep = self._args(ids, lengths, scales, sid, seed, utterance_base, noise_w, noise_z, forced_durations,
                                             pcm_volume, utterance_keys)
         a.flags = (WANT_FLOAT if want_float else 0) | (WANT_PCM16 if want_pcm16 else 0) | \
                   (DEVICE_ONLY if device_only else 0) | (DEBUG_TAPS if debug_taps else 0)
         r = Result()
-        if lvl is not None:
+        if pit is not None:
+            self._check(self.native.lib.mi355vits_run_pitch(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
+                                                            ctypes.byref(timing) if timing is not None else None,
+                                                            ctypes.byref(spk) if spk is not None else None,
+                                                            ctypes.byref(lvl) if lvl is not None else None,
+                                                            ctypes.byref(pit), ctypes.byref(r)))
+        elif lvl is not None:
             self._check(self.native.lib.mi355vits_run_levels(self._h, ctypes.byref(a), ctypes.byref(rows) if per_row else None,
                                                              ctypes.byref(timing) if timing is not None else None,
                                                              ctypes.byref(spk) if spk is not None else None,
@@ -1529,7 +1604,7 @@ class Engine:
             self._check(self.native.lib.mi355vits_run_rows(self._h, ctypes.byref(a), ctypes.byref(rows), ctypes.byref(r)))
         else:
             self._check(self.native.lib.mi355vits_run(self._h, ctypes.byref(a), ctypes.byref(r)))
-        del keep, skeep, lkeep
+        del keep, skeep, lkeep, pkeep
         self._last_batch = int(a.batch)
         self._last_rate = self.output_rate  # read when the run started; only this thread sets it meanwhile
         out = self._take(r)
@@ -1566,6 +1641,22 @@ class Engine:
             keep.append(ramp)
             v.ramp_samples = ramp.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         return v, keep
+
+    @staticmethod
+    def _pitch_args(shape, pitch):
+        """``mi355vits_pitch_args`` (or None without ``pitch``) + the array it points into.  The shape is checked as ``stretch``'s is."""
+        if pitch is None:
+            return None, []
+        if isinstance(pitch, PitchArgs):
+            return pitch, []
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        ratio = np.ascontiguousarray(pitch, dtype=np.float32)
+        if ratio.shape != tuple(shape):
+            raise ValueError("pitch must have shape [batch, phonemes]")
+        v = PitchArgs()
+        v.ratio = _fptr(ratio)
+        return v, [ratio]
 
     def _speaker_args(self, shape, speakers):
         """``mi355vits_speaker_args`` (or None without ``speakers``) + the arrays it points into (``speaker_tables``)."""
@@ -1724,7 +1815,8 @@ class Engine:
     def run_packed(self, ids, lengths, scales, sid=None, *, order=None, lead_samples=None, tail_samples: int = 0, wav: bool = False,
                    seed: int = 0, utterance_base: int = 0, noise_w=None, noise_z=None, forced_durations=None,
                    debug_taps: bool = False, pcm_volume=1.0, utterance_keys=None, compression=_HANDLE,
-                   stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None) -> PackedAudio:
+                   stretch=None, min_frames=None, target_frames=None, speakers=None, gain=None, ramp_samples=None,
+                   pitch=None) -> PackedAudio:
         """One synthesis call whose result is ONE contiguous stream (``mi355vits_run_packed``; int16 unless
         ``set_output_encoding`` says otherwise — then the header is the 58-byte non-PCM one): entry i = the valid samples
         of row ``order[i]`` (default: every row in order) behind ``lead_samples[i]`` zero samples, ``tail_samples`` zeros after
@@ -1735,13 +1827,15 @@ class Engine:
         With any of ``stretch`` / ``min_frames`` / ``target_frames`` (see ``run``): a timed run that keeps its audio on the device
         (``mi355vits_run_timed`` with ``MI355VITS_DEVICE_ONLY``), then ``fetch_packed`` of it — one synchronisation more; the
         factors are left in ``last_timing_factor``.  ``speakers`` (see ``run``) goes the same way: a speakers run that keeps its
-        audio on the device, then ``fetch_packed``; so do ``gain`` / ``ramp_samples`` (``mi355vits_run_levels``)."""
-        if stretch is not None or min_frames is not None or target_frames is not None or speakers is not None or gain is not None or ramp_samples is not None:
+        audio on the device, then ``fetch_packed``; so do ``gain`` / ``ramp_samples`` (``mi355vits_run_levels``) and ``pitch``
+        (``mi355vits_run_pitch``)."""
+        if stretch is not None or min_frames is not None or target_frames is not None or speakers is not None or gain is not None or ramp_samples is not None or pitch is not None:
             comp = self._call_compression(compression, wav)  # refuses wav + FLAC before anything runs
             res = self.run(ids, lengths, scales, sid, seed=seed, utterance_base=utterance_base, noise_w=noise_w, noise_z=noise_z,
                            forced_durations=forced_durations, want_float=False, want_pcm16=False, device_only=True,
                            debug_taps=debug_taps, pcm_volume=pcm_volume, utterance_keys=utterance_keys, stretch=stretch,
-                           min_frames=min_frames, target_frames=target_frames, speakers=speakers, gain=gain, ramp_samples=ramp_samples)
+                           min_frames=min_frames, target_frames=target_frames, speakers=speakers, gain=gain, ramp_samples=ramp_samples,
+                           pitch=pitch)
             self.last_timing_factor = res.get("timing_factor", self.last_timing_factor)
             return self.fetch_packed(order=order, lead_samples=lead_samples, tail_samples=tail_samples, wav=wav, compression=compression)
         comp = self._call_compression(compression, wav)

@@ -18,13 +18,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
-SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_timing.cpp", "kernels_speaker.cpp", "kernels_level.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "kernels_limit.cpp", "kernels_truepeak.cpp", "kernels_flac.cpp", "launch_util.cpp", "engine.cpp", "engine_results.cpp", "c_api.cpp"]
+SOURCES = ["kernels_conv.cpp", "kernels_mrf.cpp", "kernels_mrfp.cpp", "kernels_mrfs.cpp", "kernels_rbc.cpp", "kernels_attn.cpp", "kernels_wn.cpp", "kernels_misc.cpp", "kernels_dp.cpp", "kernels_resample.cpp", "kernels_pack.cpp", "kernels_align.cpp", "kernels_timing.cpp", "kernels_speaker.cpp", "kernels_level.cpp", "kernels_pitch.cpp", "kernels_edges.cpp", "kernels_loudness.cpp", "kernels_limit.cpp", "kernels_truepeak.cpp", "kernels_flac.cpp", "launch_util.cpp", "engine.cpp", "engine_results.cpp", "c_api.cpp"]
 # csrc/lab_api.cpp = the hooks of include/mi355vits_lab.h (kernel unit tests, conv micro-benchmark, box probes): NOT in the product
 # library; linked with the product's own objects into libmi355vits_hooks.so, and compiled into the lab build and the CPU model
 HOOK_SOURCES = ["lab_api.cpp"]
 # k_true_peak's rule rounds every product and every sum once: no fused multiply-add (the CPU model's g++ gets the same flag);
-# k_speaker_cond_mix's blend of speakers likewise
-PER_FILE_FLAGS = {"kernels_truepeak.cpp": ["-ffp-contract=off"], "kernels_speaker.cpp": ["-ffp-contract=off"]}
+# k_speaker_cond_mix's blend of speakers and k_pitch's interpolated taps likewise
+PER_FILE_FLAGS = {"kernels_truepeak.cpp": ["-ffp-contract=off"], "kernels_speaker.cpp": ["-ffp-contract=off"], "kernels_pitch.cpp": ["-ffp-contract=off"]}
 MAX_COMPILE_JOBS = 16  # compilers at once, however many processors the machine reports
 LAB_FILE_FLAGS = {}  # per-file flags of the lab build's side of a running A/B (none at the moment)
 # throw-away instrumented twins of the lab build (MI355_LAB_VARIANT=<name> python -m mimic3_amd.build lab -> libmi355vits_lab_<name>.so)

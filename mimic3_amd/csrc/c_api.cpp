@@ -39,14 +39,15 @@ template <typename F> int locked_guarded(mi355vits_handle h, F&& fn) {
     return locked(h, [&] { return guarded(h, fn); });
 }
 
-// The run* entry points: a result_call whose `args` must be there; fn receives them with rows, timing, speakers and levels as the
-// engine's RunCall.
+// The run* entry points: a result_call whose `args` must be there; fn receives them with rows, timing, speakers, levels and pitch as
+// the engine's RunCall.
 template <typename R, typename F>
 int run_call(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows, const mi355vits_timing_args* timing,
-             const mi355vits_speaker_args* speakers, const mi355vits_level_args* levels, R* out, F&& fn) {
+             const mi355vits_speaker_args* speakers, const mi355vits_level_args* levels, const mi355vits_pitch_args* pitch, R* out,
+             F&& fn) {
     return result_call(h, out, [&] {
         if (!args) throw EngineError(MI355VITS_ERR_INVALID, "args must not be null");
-        fn(RunCall{*args, rows, timing, speakers, levels});
+        fn(RunCall{*args, rows, timing, speakers, levels, pitch});
     });
 }
 }  // namespace
@@ -161,28 +162,34 @@ int mi355vits_get_config(mi355vits_handle h, mi355vits_config* out) {
 }
 
 int mi355vits_run(mi355vits_handle h, const mi355vits_run_args* args, mi355vits_result* out) {
-    return mi355vits_run_levels(h, args, nullptr, nullptr, nullptr, nullptr, out);
+    return mi355vits_run_pitch(h, args, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mi355vits_run_rows(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                        mi355vits_result* out) {
-    return mi355vits_run_levels(h, args, rows, nullptr, nullptr, nullptr, out);
+    return mi355vits_run_pitch(h, args, rows, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 int mi355vits_run_timed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                         const mi355vits_timing_args* timing, mi355vits_result* out) {
-    return mi355vits_run_levels(h, args, rows, timing, nullptr, nullptr, out);
+    return mi355vits_run_pitch(h, args, rows, timing, nullptr, nullptr, nullptr, out);
 }
 
 int mi355vits_run_speakers(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                            const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers, mi355vits_result* out) {
-    return mi355vits_run_levels(h, args, rows, timing, speakers, nullptr, out);
+    return mi355vits_run_pitch(h, args, rows, timing, speakers, nullptr, nullptr, out);
 }
 
 int mi355vits_run_levels(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                          const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers,
                          const mi355vits_level_args* levels, mi355vits_result* out) {
-    return run_call(h, args, rows, timing, speakers, levels, out, [&](const RunCall& call) { h->eng->run(call, out); });
+    return mi355vits_run_pitch(h, args, rows, timing, speakers, levels, nullptr, out);
+}
+
+int mi355vits_run_pitch(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
+                        const mi355vits_timing_args* timing, const mi355vits_speaker_args* speakers,
+                        const mi355vits_level_args* levels, const mi355vits_pitch_args* pitch, mi355vits_result* out) {
+    return run_call(h, args, rows, timing, speakers, levels, pitch, out, [&](const RunCall& call) { h->eng->run(call, out); });
 }
 
 int mi355vits_get_speaker_embedding(mi355vits_handle h, int64_t sid, float* out, size_t capacity) {
@@ -197,7 +204,7 @@ void mi355vits_free_result(mi355vits_result* r) { free_struct(r); }
 
 int mi355vits_run_packed(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                          const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
-    return run_call(h, args, rows, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_packed(call, pack, out); });
+    return run_call(h, args, rows, nullptr, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_packed(call, pack, out); });
 }
 
 int mi355vits_fetch_packed(mi355vits_handle h, const mi355vits_pack_args* pack, mi355vits_packed_result* out) {
@@ -208,7 +215,7 @@ void mi355vits_free_packed(mi355vits_packed_result* r) { free_struct(r); }
 
 int mi355vits_run_streams(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                           const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
-    return run_call(h, args, rows, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams(call, streams, n_streams, out); });
+    return run_call(h, args, rows, nullptr, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams(call, streams, n_streams, out); });
 }
 
 int mi355vits_fetch_streams(mi355vits_handle h, const mi355vits_stream_args* streams, int32_t n_streams, mi355vits_streams_result* out) {
@@ -219,7 +226,7 @@ void mi355vits_free_streams(mi355vits_streams_result* r) { free_struct(r); }
 
 int mi355vits_run_streams2(mi355vits_handle h, const mi355vits_run_args* args, const mi355vits_row_args* rows,
                            const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {
-    return run_call(h, args, rows, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams2(call, streams, n_streams, out); });
+    return run_call(h, args, rows, nullptr, nullptr, nullptr, nullptr, out, [&](const RunCall& call) { h->eng->run_streams2(call, streams, n_streams, out); });
 }
 
 int mi355vits_fetch_streams2(mi355vits_handle h, const mi355vits_stream_args2* streams, int32_t n_streams, mi355vits_streams_result2* out) {

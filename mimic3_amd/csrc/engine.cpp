@@ -509,6 +509,9 @@ void Engine::construct(const WeightsFile& wf, int device) {
         }
     };
 
+    // ---- k_pitch's filter table (mi355vits_run_pitch): made on the host in double, staged with the weights
+    model_->vecs["pitch.table"] = stage(pitch_table().data(), pitch_table().size());
+
     // ---- text encoder
     add_vec(wf, "enc_p.emb.weight", {c.num_symbols, H});
     for (int i = 0; i < c.n_layers; ++i) {
@@ -1558,11 +1561,15 @@ template <typename A> void Engine::layout_a(A& ar, const RunInputs& in, bool wid
     field(d_spk_vec_, B * gin, in.spk.vectors, widest && cond);
     field(d_gain_, fBT, in.lvl.gain, widest);
     field(d_ramp_, B, in.lvl.ramp_samples, widest || in.levelled());  // a levels run without ramps: zeros
-    // what the host reads at the run's one sizing synchronisation: ylen, and of a timed run status and factor, in ONE copy (4-byte
-    // words side by side: each of the three is B words)
-    d_ylen_ = ar.template alloc<int>(3 * B);
+    field(d_ratio_, fBT, in.pit.ratio, widest);
+    // what the host reads at the run's one sizing synchronisation: ylen, of a timed run status and factor, and of a pitch run the
+    // warped lengths, in ONE copy (4-byte words side by side: each of the four is B words)
+    d_ylen_ = ar.template alloc<int>(4 * B);
     d_tstatus_ = d_ylen_ + B;
     d_tfactor_ = reinterpret_cast<float*>(d_ylen_ + 2 * B);
+    d_wlen_ = d_ylen_ + 3 * B;
+    d_tq_ = ar.template alloc<long long>(fBT);
+    d_wc_ = ar.template alloc<int>(fBT);
     d_durf_ = ar.template alloc<float>(fBT);
     d_peaks_ = ar.template alloc<unsigned>(B);
     d_wceil_ = ar.template alloc<int>(fBT);
@@ -1589,7 +1596,7 @@ template <typename A> void Engine::layout_a(A& ar, const RunInputs& in, bool wid
     for (int j = 0; cond && j < c.flow_n_flows; ++j) d_cond_flow_.push_back(ar.template alloc<float>(B * 2 * H * c.flow_wn_layers));
 }
 
-template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr) {
+template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr, size_t Lw) {
     const mi355vits_config& c = cfg_;
     const size_t H = c.hidden_channels, I = c.inter_channels, fBTy = B * Ty;
     size_t ch = c.upsample_initial_channel, T = Ty, max_stage = ch * T;  // the widest decoder tensor of a row
@@ -1609,13 +1616,17 @@ template <typename A> void Engine::layout_b(A& ar, size_t B, size_t Ty, size_t n
     d_bufT_ = ar.template alloc<float>(B * max_stage);
     d_bufC_ = ar.template alloc<float>(B * max_stage);
     d_audio_ = ar.template alloc<float>(B * L_);
-    d_pcm_ = ar.template alloc<int16_t>(B * (Lr ? Lr : (size_t)L_));  // of the rows the caller receives
+    d_pcm_ = ar.template alloc<int16_t>(B * (Lr ? Lr : (Lw ? Lw : (size_t)L_)));  // of the rows the caller receives
+    d_waudio_ = Lw ? ar.template alloc<float>(B * Lw) : nullptr;  // a pitch run: the warped rows (Lw: their stride)
+    d_wpeaks_ = Lw ? ar.template alloc<unsigned>(B) : nullptr;
     d_raudio_ = Lr ? ar.template alloc<float>(B * Lr) : nullptr;
     d_rpeaks_ = Lr ? ar.template alloc<unsigned>(B) : nullptr;
-    // per-stage valid lengths and (last row) the audio lengths; a resampled run's table behind them
-    d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B + (Lr ? resample_tab_ints((int)B) : 0));
+    // per-stage valid lengths and (last row) the audio lengths; a pitch run's table (the warped lengths, k_pitch's first items), then
+    // a resampled run's table behind them
+    d_slen_ = ar.template alloc<int>((size_t)(c.n_upsamples + 2) * B + (Lw ? pitch_tab_ints((int)B) : 0) + (Lr ? resample_tab_ints((int)B) : 0));
     d_alen_ = d_slen_ + (size_t)(c.n_upsamples + 1) * B;
-    d_rtab_ = Lr ? d_alen_ + B : nullptr;
+    d_walen_ = Lw ? d_alen_ + B : nullptr;
+    d_rtab_ = Lr ? d_alen_ + B + (Lw ? pitch_tab_ints((int)B) : 0) : nullptr;
 }
 
 void Engine::run(const RunCall& call, mi355vits_result* out) {
@@ -1816,6 +1827,35 @@ RunInputs check_inputs(const mi355vits_config& c, const RunCall& call) {
             }
         }
     }
+    // pitch (mi355vits_run_pitch): a ratio per phoneme; the duration half of the change is the stretch of a timed run
+    if (call.pitch) {
+        const mi355vits_pitch_args& pa = *call.pitch;
+        for (int i = 0; i < 7; ++i)
+            if (pa.reserved[i] != 0) throw EngineError(MI355VITS_ERR_INVALID, "pitch: reserved fields must be 0");
+        if (pa.ratio) {
+            in.pit = pa;
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < in.len32[b]; ++t) {
+                    const float p = pa.ratio[(size_t)b * Tx + t];
+                    if (!(std::isfinite(p) && p >= 0.5f && p <= 2.0f))
+                        throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ", phoneme " + std::to_string(t) + ": pitch ratio must be finite and within 0.5 .. 2");
+                    if (p != 1.0f && in.timing.target_frames && in.timing.target_frames[b] != 0)
+                        throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": a fitted length and a pitch ratio exclude each other");
+                }
+            if (!args.forced_durations) {  // (with forced_durations the table IS the synthesized frames: no compensation)
+                in.pitch_stretch.assign((size_t)B * Tx, 1.0f);
+                for (int b = 0; b < B; ++b)
+                    for (int t = 0; t < in.len32[b]; ++t) {
+                        const size_t i = (size_t)b * Tx + t;
+                        volatile float prod = (in.timing.stretch ? in.timing.stretch[i] : 1.0f) * pa.ratio[i];  // one f32 product
+                        if (!(prod <= 1048576.0f))
+                            throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ", phoneme " + std::to_string(t) + ": stretch times pitch ratio is above 2^20");
+                        in.pitch_stretch[i] = prod;
+                    }
+                in.timing.stretch = in.pitch_stretch.data();  // (the vector's storage moves with `in`)
+            }
+        }
+    }
     return in;
 }
 
@@ -1846,7 +1886,7 @@ void Engine::upload_inputs(const RunInputs& in) {
 // ylen and come in the same copy).  Here, too, the two checks that need them.
 void Engine::read_frame_counts(const RunInputs& in) {
     const int B = in.B;
-    const size_t nread = in.timed() ? 3 : 1;
+    const size_t nread = in.pitched() ? 4 : (in.timed() ? 3 : 1);
     h_ylen_.resize(nread * B);
     HIP_CHECK(hipMemcpyAsync(h_ylen_.data(), d_ylen_, nread * B * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1879,10 +1919,20 @@ void Engine::read_frame_counts(const RunInputs& in) {
     run_hz_ = rs ? out_hz_ : cfg_.sample_rate;
     run_L_ = rs ? rs_.L : 1;
     run_M_ = rs ? rs_.M : 1;
-    h_olen_.resize(B);
-    Lo_ = rs ? 0 : L_;
+    // the native-rate rows everything behind the waveform reads: the waveform itself, or in a pitch run its warp
+    pitched_ = in.pitched();
+    h_nlen_.resize(B);
+    Ln_ = pitched_ ? 1 : L_;
     for (int b = 0; b < B; ++b) {
-        const int64_t n = (int64_t)h_ylen_[b] * hop;
+        h_nlen_[b] = pitched_ ? (int64_t)h_ylen_[3 * (size_t)B + b] : (int64_t)h_ylen_[b] * hop;
+        if (pitched_ && (h_nlen_[b] < 1 || h_nlen_[b] >= 0x7fffffffLL))  // (k_pitch_plan saturates)
+            throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": the warped row does not fit 32 bits");
+        if (pitched_) Ln_ = std::max<long>(Ln_, (long)h_nlen_[b]);
+    }
+    h_olen_.resize(B);
+    Lo_ = rs ? 0 : Ln_;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = h_nlen_[b];
         h_olen_[b] = rs ? (int64_t)resample_out_len(n, rs_.L, rs_.M) : n;
         if (h_olen_[b] > 0x7fffffffLL)
             throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": " + std::to_string(h_olen_[b]) + " samples at " + std::to_string(run_hz_) + " Hz do not fit 32 bits");
@@ -1892,17 +1942,20 @@ void Engine::read_frame_counts(const RunInputs& in) {
 
 void Engine::size_frame_side(const RunInputs& in, const OutputPlan* plan) {
     const bool rs = out_hz_ != 0;
-    const size_t B = in.B, Lr = rs ? Lo_ : 0;
+    const size_t B = in.B, Lr = rs ? Lo_ : 0, Lw = pitched_ ? Ln_ : 0;
     ArenaCount size_b;
-    layout_b(size_b, B, Ty_, in.noise_z_held(), Lr);
+    layout_b(size_b, B, Ty_, in.noise_z_held(), Lr, Lw);
     if (plan) layout(size_b, *plan);
     arena_b_.reserve(size_b.bytes + 4096, stream_);
     arena_b_.reset();
-    layout_b(arena_b_, B, Ty_, in.noise_z_held(), Lr);
+    layout_b(arena_b_, B, Ty_, in.noise_z_held(), Lr, Lw);
     layout_b_end_ = arena_b_.used();
-    o_audio_ = rs ? d_raudio_ : d_audio_;
-    o_peaks_ = rs ? d_rpeaks_ : d_peaks_;
-    o_alen_ = rs ? d_rtab_ : d_alen_;
+    n_audio_ = pitched_ ? d_waudio_ : d_audio_;
+    n_peaks_ = pitched_ ? d_wpeaks_ : d_peaks_;
+    n_alen_ = pitched_ ? d_walen_ : d_alen_;
+    o_audio_ = rs ? d_raudio_ : n_audio_;
+    o_peaks_ = rs ? d_rpeaks_ : n_peaks_;
+    o_alen_ = rs ? d_rtab_ : n_alen_;
     d_pack_seg_ = nullptr;
     d_pack_ = nullptr;
     if (plan) layout(arena_b_, *plan);
@@ -1916,7 +1969,7 @@ void Engine::upload_stage_table(const RunInputs& in, const OutputPlan* plan) {
     if (d_noise_z_) HIP_CHECK(hipMemcpyAsync(d_noise_z_, in.noise_z, (size_t)B * c.inter_channels * in.noise_z_held() * 4, hipMemcpyHostToDevice, stream_));
     // per-stage valid lengths and (last row) the audio lengths: one copy
     // (a plan's table sits right behind d_slen_ in the arena: the same copy brings it; no early block has a curve row)
-    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + plan->table_words() : (size_t)(c.n_upsamples + 2) * B + (rs ? resample_tab_ints(B) : 0), 0);
+    h_slen_.assign(plan ? (size_t)(d_pack_seg_ - d_slen_) + plan->table_words() : (size_t)(c.n_upsamples + 2) * B + (pitched_ ? pitch_tab_ints(B) : 0) + (rs ? resample_tab_ints(B) : 0), 0);
     if (plan) fill_table(*plan, h_slen_.data() + (d_pack_seg_ - d_slen_));
     long f = 1;
     for (int i = 0; i <= c.n_upsamples; ++i) {
@@ -1924,7 +1977,8 @@ void Engine::upload_stage_table(const RunInputs& in, const OutputPlan* plan) {
         if (i < c.n_upsamples) f *= c.upsample_rates[i];
     }
     for (int b = 0; b < B; ++b) h_slen_[(size_t)(c.n_upsamples + 1) * B + b] = (int)(h_ylen_[b] * hop);
-    rs_items_ = !rs ? 0 : resample_fill_tab(rs_, h_slen_.data() + (d_alen_ - d_slen_), B, h_slen_.data() + (d_rtab_ - d_slen_));
+    pitch_items_ = !pitched_ ? 0 : pitch_fill_tab(h_nlen_.data(), B, h_slen_.data() + (d_walen_ - d_slen_));
+    rs_items_ = !rs ? 0 : resample_fill_tab(rs_, h_slen_.data() + (n_alen_ - d_slen_), B, h_slen_.data() + (d_rtab_ - d_slen_));
     HIP_CHECK(hipMemcpyAsync(d_slen_, h_slen_.data(), h_slen_.size() * 4, hipMemcpyHostToDevice, stream_));
 }
 
@@ -1939,17 +1993,41 @@ void Engine::levels(const RunInputs& in) {
     launch_levels(d_cum_, d_len_, d_gain_, d_ramp_, in.B, in.Tx, cfg_.hop_length, d_audio_, L_, d_alen_, L_, d_peaks_, stream_);
 }
 
-// a run at another rate than the voice's: d_audio_ -> d_raudio_ over the rs_items_ of the table uploaded with the stage lengths
+// a pitch run: the warped boundaries of every row from the frames the duration kernel just left, in front of the run's one sizing
+// copy, which brings wlen with the frame counts
+void Engine::pitch_plan(const RunInputs& in) {
+    if (!in.pitched()) return;
+    ProfScope ps(prof_, "pitch.plan", 0, 20.0 * in.B * (double)in.Tx);
+    launch_pitch_plan(d_cum_, d_len_, d_ratio_, in.B, in.Tx, cfg_.hop_length, d_tq_, d_wc_, d_wlen_, stream_);
+}
+
+// a pitch run: the band-limited warp of the (shaped) native waveform along d_tq_ into d_waudio_, which every consumer reads in
+// d_audio_'s place; the row peaks are taken from the warped samples
+void Engine::pitch(const RunInputs& in) {
+    if (!in.pitched()) return;
+    tap("audio_synth", d_audio_, {in.B, 1, L_}, d_alen_, 1);
+    double n = 0, w = 0;
+    for (int b = 0; b < in.B; ++b) {
+        n += (double)h_ylen_[b] * cfg_.hop_length;
+        w += (double)h_nlen_[b];
+    }
+    ProfScope ps(prof_, "pitch", 0, 4.0 * (n + w) + 20.0 * in.B * (double)in.Tx);
+    HIP_CHECK(hipMemsetAsync(d_wpeaks_, 0, sizeof(unsigned) * in.B, stream_));
+    launch_pitch(d_audio_, L_, d_alen_, d_cum_, d_len_, d_ratio_, d_tq_, d_wc_, d_walen_, pitch_items_, vec("pitch.table"), in.B, in.Tx, cfg_.hop_length,
+                 d_waudio_, Ln_, (int)Ln_, d_wpeaks_, stream_);
+}
+
+// a run at another rate than the voice's: the native rows -> d_raudio_ over the rs_items_ of the table uploaded with the stage lengths
 void Engine::resample() {
     if (!out_hz_) return;
     double n_in = 0, n_out = 0;
     for (int b = 0; b < B_; ++b) {
-        n_in += (double)h_ylen_[b] * cfg_.hop_length;
+        n_in += (double)h_nlen_[b];
         n_out += (double)h_olen_[b];
     }
     ProfScope ps(prof_, "resample", 2.0 * rs_.tpp * n_out, 4.0 * n_in + 4.0 * n_out);
     HIP_CHECK(hipMemsetAsync(d_rpeaks_, 0, sizeof(unsigned) * B_, stream_));
-    launch_resample(rs_, d_rs_coef_, d_audio_, L_, d_alen_, B_, d_rtab_, rs_items_, d_raudio_, Lo_, (int)Lo_, d_rpeaks_, stream_);
+    launch_resample(rs_, d_rs_coef_, n_audio_, Ln_, n_alen_, B_, d_rtab_, rs_items_, d_raudio_, Lo_, (int)Lo_, d_rpeaks_, stream_);
 }
 
 void Engine::output(const RunInputs& in, const OutputPlan* plan) {
@@ -1975,12 +2053,14 @@ void Engine::synthesize(const RunCall& call, OutputPlan* plan) {
     Tx_ = in.Tx;
     text_encoder(in.B, in.Tx);
     duration_predictor(in);
+    pitch_plan(in);
     read_frame_counts(in);
     if (plan) place(*plan);  // places from the frame counts just read (no early plan trims, normalises or compresses); the size limits, before the frame side is sized
     size_frame_side(in, plan);
     upload_stage_table(in, plan);
     flow_and_decoder(in);
     levels(in);
+    pitch(in);
     resample();
     output(in, plan);
 }

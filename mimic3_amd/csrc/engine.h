@@ -174,6 +174,7 @@ struct RunCall {
     const mi355vits_timing_args* timing = nullptr;     // per-phoneme stretch / minimum frames / a target per row (mi355vits_run_timed), or NULL: the plain run
     const mi355vits_speaker_args* speakers = nullptr;  // a blend of speakers or a vector per row in place of args.sid (mi355vits_run_speakers), or NULL: args.sid
     const mi355vits_level_args* levels = nullptr;      // a gain per phoneme and a ramp per row (mi355vits_run_levels), or NULL: the waveform as it is
+    const mi355vits_pitch_args* pitch = nullptr;       // a pitch ratio per phoneme (mi355vits_run_pitch), or NULL: the waveform as it is
 };
 // What validation leaves of a RunCall: everything the rest of the call reads.  The pointers are the caller's arrays; one that is null
 // is an input the run does not have.
@@ -204,6 +205,11 @@ struct RunInputs {
     // levels: the caller's struct (all null without one); without a gain the run is the plain one, launch for launch
     mi355vits_level_args lvl{};
     bool levelled() const { return lvl.gain != nullptr; }
+    // pitch: the caller's struct (null without one); without a ratio the run is the levels run, launch for launch.  Without
+    // forced_durations such a run is a timed run whose stretch is pitch_stretch = fl(stretch * ratio): timing.stretch points into it
+    mi355vits_pitch_args pit{};
+    std::vector<float> pitch_stretch;
+    bool pitched() const { return pit.ratio != nullptr; }
     // the frames of injected noise_z the frame side holds: none unless some row reads it
     size_t noise_z_held() const { return (noise_z && any_noise_z) ? (size_t)noise_z_frames : 0; }
 };
@@ -323,7 +329,7 @@ class Engine {
     // there, at its largest, and nothing copied (sizing)
     template <typename A> void layout_a(A& ar, const RunInputs& in, bool widest);
     // Lr: the row stride of the resampled audio, 0 in a native run (which lays out nothing for it)
-    template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr);
+    template <typename A> void layout_b(A& ar, size_t B, size_t Ty, size_t noise_z_frames, size_t Lr, size_t Lw);
     // what a packed call puts where (mi355vits_pack_args, validated; then the offsets made from the frame counts)
     struct PackPlan {
         int n = 0;
@@ -436,6 +442,10 @@ class Engine {
     void upload_stage_table(const RunInputs& in, const OutputPlan* plan);
     // a levels run: k_levels shapes d_audio_ in place and takes the row peaks again (kernels_level.cpp); else nothing
     void levels(const RunInputs& in);
+    // a pitch run: k_pitch_plan behind the duration kernel (its wlen rides in read_frame_counts' copy), k_pitch from d_audio_ into
+    // d_waudio_ behind levels() (kernels_pitch.cpp); else nothing
+    void pitch_plan(const RunInputs& in);
+    void pitch(const RunInputs& in);
     void resample();
     void output(const RunInputs& in, const OutputPlan* plan);  // the plan's pack kernel, or the padded int16 pass when the flags ask
     void plan_pack(const mi355vits_pack_args* pack, int B, const PackSettings& set, PackPlan& plan) const;  // validates; nothing sized or launched yet
@@ -541,6 +551,11 @@ class Engine {
     // a levels run's gain [B, Tx] and ramp [B] (in the one upload)
     float* d_gain_ = nullptr;
     int* d_ramp_ = nullptr;
+    // a pitch run's ratio [B, Tx] (in the one upload), k_pitch_plan's time map tq [B, Tx] and warped boundaries wc [B, Tx], and
+    // wlen [B] (the fourth group of d_ylen_'s block)
+    float* d_ratio_ = nullptr;
+    long long* d_tq_ = nullptr;
+    int *d_wc_ = nullptr, *d_wlen_ = nullptr;
     float *d_x_ = nullptr, *d_x2_ = nullptr, *d_qkv_ = nullptr, *d_att_ = nullptr, *d_ffn_ = nullptr, *d_part_ = nullptr,
           *d_stats_ = nullptr;
     float *d_h_ = nullptr, *d_d0_ = nullptr, *d_d1_ = nullptr, *d_d2_ = nullptr, *d_theta_ = nullptr, *d_z2_ = nullptr,
@@ -582,6 +597,18 @@ class Engine {
     std::vector<double> h_tp_;
     std::vector<float> h_tp_peaks_;
     bool have_tp_ = false;
+    // pitch (mi355vits_run_pitch): k_pitch warps d_audio_ into d_waudio_, which takes the native waveform's place for every consumer:
+    // the n_* view is the warped rows, or without pitch d_audio_ / d_peaks_ / d_alen_ / L_ themselves; the resampler reads it
+    bool pitched_ = false;         // the last run was a pitch run (fetch_alignment: boundaries from d_wc_)
+    float* d_waudio_ = nullptr;    // [B][Ln_] in the frame-side arena, pitch runs only
+    unsigned* d_wpeaks_ = nullptr;
+    int* d_walen_ = nullptr;       // pitch_fill_tab's table (the warped lengths, then k_pitch's first items), behind d_alen_ in the stage table (the same upload)
+    long pitch_items_ = 0;         // the work items of that table, for k_pitch
+    const float* n_audio_ = nullptr;
+    unsigned* n_peaks_ = nullptr;
+    const int* n_alen_ = nullptr;
+    long Ln_ = 0;                  // row stride of the n_* view
+    std::vector<int64_t> h_nlen_;  // [B] valid native-rate samples of a row of it
     float* d_raudio_ = nullptr;    // [B][Lo_] in the frame-side arena, resampled runs only
     unsigned* d_rpeaks_ = nullptr;
     int* d_rtab_ = nullptr;        // resample_fill_tab's table, behind the audio lengths in d_slen_'s block (the same upload)

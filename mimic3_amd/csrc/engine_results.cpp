@@ -877,7 +877,7 @@ void Engine::fetch_alignment(uint32_t want, mi355vits_alignment* out) {
         for (int b = 0; b < B_; ++b) audio += (double)h_olen_[b];
         ProfScope ps(prof_, "align", 0, levels ? 4.0 * audio + 20.0 * (double)n : 12.0 * (double)n);
         launch_align(d_wceil_, d_cum_, d_len_, B_, Tx_, o_audio_, Lo_, o_alen_, cfg_.hop_length, run_L_, run_M_, d, d + n, d + 2 * n,
-                     d_peak, d_rms, stream_);
+                     d_peak, d_rms, stream_, pitched_ ? d_wc_ : nullptr);
     }
     int32_t* h = static_cast<int32_t*>(new_owner(out)->take_pinned(arrays * n * 4 + 16));
     HIP_CHECK(hipMemcpyAsync(h, d, arrays * n * 4, hipMemcpyDeviceToHost, stream_));

@@ -425,7 +425,8 @@ void launch_resample(const ResampleFilter& f, const float* coef, const float* x,
 // given max |y| and (float) sqrt(sum((double) y y) / samples) over the span (0 for an empty one); peak == rms == nullptr: the
 // audio is not read.  At t >= len[b]: 0 frames, 0 samples, start = the end of the covered part, levels 0.
 void launch_align(const int* w_ceil, const int* cum, const int* len, int B, int T, const float* audio, long audio_bs, const int* alen,
-                  int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s);
+                  int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s,
+                  const int* wc = nullptr /* a pitch run: k_pitch_plan's warped boundaries take the place of hop * c */);
 
 // ---------------------------------------------------------------- the quiet edges of a run's rows (kernels_edges.cpp)
 // audio [B] rows of audio_bs floats with alen [B] valid samples (device), peak_bits [B] the rows' peaks, l_max >= every alen[b].
@@ -695,6 +696,33 @@ constexpr int LEVELS_ONE = 1 << 20;     // the fixed-point unit of a gain
 constexpr int LEVELS_MAX_RAMP = 4096;    // R: samples at the native rate
 void launch_levels(const int* cum, const int* len, const float* gain, const int* ramp /* null: 0 */, int B, int T, int hop,
                    float* audio, long audio_bs, const int* alen, long l_max, unsigned* peak_bits, hipStream_t s);
+
+// ---------------------------------------------------------------- a pitch ratio per phoneme, duration kept (kernels_pitch.cpp;
+// mi355vits_run_pitch: the rule is in include/mi355vits.h).  k_pitch_plan: per row b, with c = cum[b, :], L = len[b],
+// fs[t] = c[t] - c[t-1] and inv[t] = (int) rintf(2^20 / ratio[b, t]) (ratio null: 2^20):
+//   tq[b, t] = sum over u <= min(t, L - 1) of hop fs[u] inv[u]  (int64)     wc[b, t] = ceil(tq[b, t] / 2^20)
+//   wlen[b]  = wc[b, L - 1], or hop for a row without frames (L = 0 or c[L-1] = 0);  wc and wlen saturate at 2^31 - 1
+// k_pitch: y[b, k] for 0 <= k < wlen[b] by the rule (the band-limited warp of x[b, 0 .. x_len[b]) along tq), zeros for
+// wlen[b] <= k < y_ld; peak_bits[b] = the bits of max |y| (zero before the launch, same stream).  tq / wc / wlen must be
+// k_pitch_plan's of the same cum / len / ratio, x_len[b] = hop max(1, c[L-1]) and wlen[b] < 2^31 - 1, y_ld >= max wlen.
+// items_tab = pitch_fill_tab's table on the device (pitch_tab_ints(B) ints: [B] wlen, [B + 1] the first work item of a row; the
+// host makes it from the plan's wlen), items its return value: the grid is persistent over them.  Nothing
+// outside [0, x_len[b]) of a row of x is read.  No result depends on the grid, the batch, the row block or an address.
+constexpr int PITCH_ONE = 1 << 20;  // the fixed-point unit of the time map
+constexpr int PITCH_P = 128;        // filter table entries per source sample
+constexpr int PITCH_Z = 12;         // zero crossings either side
+constexpr int PITCH_TABLE_FLOATS = PITCH_Z * PITCH_P + 2;
+constexpr int PITCH_TILE = 1024;    // outputs of a work item
+// h[i] = (float) (sinc(i / P) I0(8 sqrt(1 - (i / (Z P))^2)) / I0(8)), in double; exactly 0 at the multiples of P, h[0] = 1,
+// h[Z P] = h[Z P + 1] = 0.  Computed once per process.
+const std::vector<float>& pitch_table();
+void launch_pitch_plan(const int* cum, const int* len, const float* ratio /* null: 1 */, int B, int T, int hop, long long* tq, int* wc,
+                       int* wlen, hipStream_t s);
+inline size_t pitch_tab_ints(int B) { return 2 * (size_t)B + 1; }
+long pitch_fill_tab(const int64_t* wlen, int B, int* tab);  // -> the work items
+void launch_pitch(const float* x, long x_bs, const int* x_len, const int* cum, const int* len, const float* ratio /* null: 1 */,
+                  const long long* tq, const int* wc, const int* items_tab, long items, const float* table, int B, int T, int hop,
+                  float* y, long y_bs, int y_ld, unsigned* peak_bits, hipStream_t s);
 
 // misc
 void launch_fill(float* p, float v, size_t n, hipStream_t s);

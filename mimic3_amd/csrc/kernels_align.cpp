@@ -6,6 +6,7 @@
 //   in exact 64-bit integers.  ceil(n L / M) is the resampler's length rule, so the spans tile the row: they sum to its length.
 //   Positions at or past the row's phoneme count: frames = samples = 0, start = the end of the covered part, levels 0 — selected by
 //   t < len[b], so neither frames nor cum is read there, whatever the workspace holds.
+//   A pitch run (mi355vits_run_pitch) gives wc, the warped boundaries of k_pitch_plan: wc[t] stands where hop c[t] stood.
 // Levels (optional): peak = max |y|, rms = (float) sqrt(sum((double) y y) / samples) over the span of the row's float waveform.
 //   * One wave per phoneme.  Lane l takes samples l, l + 64, .. of the span in ascending order: the 64 lanes of a pass load 256
 //     consecutive bytes.  Each lane keeps a double sum of squares (every square is exact in double) and a float max.
@@ -23,7 +24,7 @@
 namespace m355 {
 
 struct AlignArgs {
-    const int* w_ceil; const int* cum; const int* len; int B, T;
+    const int* w_ceil; const int* cum; const int* len; const int* wc; int B, T;
     const float* audio; long audio_bs; const int* alen;
     long long hop, L, M;
     int *frames, *start, *samples;
@@ -36,11 +37,20 @@ __device__ __forceinline__ long long align_ceil_div(long long a, long long m) { 
 __device__ __forceinline__ void align_span(const AlignArgs& a, int b, int t, int& fr, long long& s0, long long& s1) {
     const int n = a.len[b] < a.T ? a.len[b] : a.T;
     const int* cb = a.cum + (long)b * a.T;
-    const long long c_end = n > 0 ? cb[n - 1] : 0;
     const bool in = t < n;
+    fr = in ? a.w_ceil[(long)b * a.T + t] : 0;
+    if (a.wc) {
+        const int* wb = a.wc + (long)b * a.T;
+        const long long w_end = n > 0 ? wb[n - 1] : 0;
+        const long long w0 = in ? (t > 0 ? (long long)wb[t - 1] : 0LL) : w_end;
+        const long long w1 = in ? (long long)wb[t] : w_end;
+        s0 = align_ceil_div(w0 * a.L, a.M);
+        s1 = align_ceil_div(w1 * a.L, a.M);
+        return;
+    }
+    const long long c_end = n > 0 ? cb[n - 1] : 0;
     const long long c0 = in ? (t > 0 ? (long long)cb[t - 1] : 0LL) : c_end;
     const long long c1 = in ? (long long)cb[t] : c_end;
-    fr = in ? a.w_ceil[(long)b * a.T + t] : 0;
     s0 = align_ceil_div(a.hop * c0 * a.L, a.M);
     s1 = align_ceil_div(a.hop * c1 * a.L, a.M);
 }
@@ -102,10 +112,10 @@ template <bool LEVELS> __global__ __launch_bounds__(256) void k_align(AlignArgs 
 }
 
 void launch_align(const int* w_ceil, const int* cum, const int* len, int B, int T, const float* audio, long audio_bs, const int* alen,
-                  int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s) {
+                  int hop, int L, int M, int* frames, int* start, int* samples, float* peak, float* rms, hipStream_t s, const int* wc) {
     if (B <= 0 || T <= 0) return;
     AlignArgs a;
-    a.w_ceil = w_ceil; a.cum = cum; a.len = len; a.B = B; a.T = T;
+    a.w_ceil = w_ceil; a.cum = cum; a.len = len; a.wc = wc; a.B = B; a.T = T;
     a.audio = audio; a.audio_bs = audio_bs; a.alen = alen;
     a.hop = hop; a.L = L; a.M = M;
     a.frames = frames; a.start = start; a.samples = samples; a.peak = peak; a.rms = rms;

@@ -1215,6 +1215,105 @@ int mi355vits_test_levels(int device, int B, int T, int hop, const int32_t* cum,
     });
 }
 
+int mi355vits_test_pitch_table(float* out, size_t capacity) {
+    return guarded(nullptr, [&] {
+        const std::vector<float>& h = pitch_table();
+        if (!out || capacity < h.size()) throw EngineError(MI355VITS_ERR_INVALID, "pitch table: out must take " + std::to_string(h.size()) + " floats");
+        memcpy(out, h.data(), h.size() * sizeof(float));
+    });
+}
+
+namespace {
+// what both pitch hooks check of their inputs; returns the longest native row
+long check_pitch_inputs(int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* ratio, int64_t x_bs) {
+    if (!cum || !len) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+    if (B < 1 || T < 1 || hop < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+    long n_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = len[b];
+        if (L < 0 || L > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        for (int t = 0; t < L; ++t) {
+            if (cum[(size_t)b * T + t] < (t ? cum[(size_t)b * T + t - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
+            if (ratio) {
+                const float p = ratio[(size_t)b * T + t];
+                if (!(std::isfinite(p) && p >= 0.5f && p <= 2.0f)) throw EngineError(MI355VITS_ERR_INVALID, "ratio out of range");
+            }
+        }
+        const long long frames = L > 0 ? cum[(size_t)b * T + L - 1] : 0;
+        const long long n = (long long)hop * (frames < 1 ? 1 : frames);
+        if (n > 0x7fffffffLL || (x_bs > 0 && n > x_bs)) throw EngineError(MI355VITS_ERR_INVALID, "hop * max(1, c[len - 1]) must fit the row");
+        n_max = std::max<long>(n_max, (long)n);
+    }
+    return n_max;
+}
+}  // namespace
+
+int mi355vits_test_pitch_plan(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* ratio,
+                              int64_t* tq, int32_t* wc, int32_t* wlen) {
+    return guarded(nullptr, [&] {
+        if (!tq || !wc || !wlen) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        check_pitch_inputs(B, T, hop, cum, len, ratio, 0);
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nbt = (size_t)B * T;
+        DevBuf dc(nbt * 4), dl((size_t)B * 4), dr(nbt * 4), dq(nbt * 8), dw(nbt * 4), dn((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (ratio) HIP_CHECK(hipMemcpy(dr.p, ratio, nbt * 4, hipMemcpyHostToDevice));
+        launch_pitch_plan(dc.as<int>(), dl.as<int>(), ratio ? dr.as<float>() : nullptr, B, T, hop, dq.as<long long>(), dw.as<int>(), dn.as<int>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(tq, dq.p, nbt * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(wc, dw.p, nbt * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(wlen, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_pitch(int device, int B, int T, int hop, const int32_t* cum, const int32_t* len, const float* ratio,
+                         const float* x, int64_t x_bs, size_t x_floats, float* y, int64_t y_bs, int32_t y_ld, size_t y_floats,
+                         float* peaks, int32_t* wlen) {
+    return guarded(nullptr, [&] {
+        if (!x || !y || !peaks || !wlen) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (x_bs < 1 || y_bs < 1 || y_ld < 1 || y_ld > y_bs || B < 1 || x_floats < (size_t)B * (size_t)x_bs || y_floats < (size_t)B * (size_t)y_bs)
+            throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        check_pitch_inputs(B, T, hop, cum, len, ratio, x_bs);
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nbt = (size_t)B * T;
+        const std::vector<float>& h = pitch_table();
+        std::vector<int> alen(B);
+        for (int b = 0; b < B; ++b) {
+            const int frames = len[b] > 0 ? cum[(size_t)b * T + len[b] - 1] : 0;
+            alen[b] = hop * (frames < 1 ? 1 : frames);
+        }
+        DevBuf dc(nbt * 4), dl((size_t)B * 4), dr(nbt * 4), dq(nbt * 8), dw(nbt * 4), dn((size_t)B * 4), da((size_t)B * 4),
+            dx(x_floats * 4), dy(y_floats * 4), dp((size_t)B * 4), dh(h.size() * 4);
+        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (ratio) HIP_CHECK(hipMemcpy(dr.p, ratio, nbt * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(da.p, alen.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dx.p, x, x_floats * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, y, y_floats * 4, hipMemcpyHostToDevice));  // everything: a stray write shows
+        HIP_CHECK(hipMemcpy(dh.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
+        const float* dratio = ratio ? dr.as<float>() : nullptr;
+        launch_pitch_plan(dc.as<int>(), dl.as<int>(), dratio, B, T, hop, dq.as<long long>(), dw.as<int>(), dn.as<int>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(wlen, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            if (wlen[b] < 1 || wlen[b] == 0x7fffffff || wlen[b] > y_ld) throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": the warped row of " + std::to_string(wlen[b]) + " samples does not fit y_ld");
+        std::vector<int64_t> w64(wlen, wlen + B);
+        std::vector<int> tab(pitch_tab_ints(B));
+        const long items = pitch_fill_tab(w64.data(), B, tab.data());
+        DevBuf dt(tab.size() * 4);
+        HIP_CHECK(hipMemcpy(dt.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        launch_pitch(dx.as<float>(), (long)x_bs, da.as<int>(), dc.as<int>(), dl.as<int>(), dratio, dq.as<long long>(), dw.as<int>(), dt.as<int>(),
+                     items, dh.as<float>(), B, T, hop, dy.as<float>(), (long)y_bs, y_ld, dp.as<unsigned>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(y, dy.p, y_floats * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z) {
     return guarded(nullptr, [&] {

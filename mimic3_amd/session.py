@@ -753,7 +753,7 @@ class InferenceSession:
     # ---- engine extensions --------------------------------------------------------------------
     def run_pcm16(self, input_feed: Dict[str, np.ndarray], volume=None, direct: bool = False, utterance_keys=None,
                   sample_rate: Optional[int] = None, alignment=False, stretch=None, min_frames=None, target_frames=None,
-                  duration_ms=None, speakers=None, gain_db=None, ramp_ms=None):
+                  duration_ms=None, speakers=None, gain_db=None, ramp_ms=None, pitch=None, pitch_semitones=None):
         """``run`` + ``audio_float_to_int16`` (``utils.py:237-244``) fused on the GPU, per utterance over its
         valid samples.  Returns ([int16 [L_b]] per row, lengths).
 
@@ -783,7 +783,12 @@ class InferenceSession:
         phoneme in dB (``-inf`` mutes; converted as ``np.float32(10 ** (dB / 20))``; a list shorter than Tx leaves the rest at 0 dB),
         ``ramp_ms`` (a number or [B]) the half-width of the linear ramp across every phoneme boundary,
         ``round(ms / 1000 * sample_rate)`` samples at the voice's native rate (default 0: steps).  The envelope is applied to the
-        waveform on the GPU in front of the int16 conversion.  Such a call goes straight to a lane, never through the micro-batcher."""
+        waveform on the GPU in front of the int16 conversion.  Such a call goes straight to a lane, never through the micro-batcher.
+        Pitch in the same run (``mi355vits_run_pitch``): ``pitch`` — one list per row or a [B, Tx] array — is the pitch multiplier of
+        each phoneme (0.5 .. 2; a list shorter than Tx leaves the rest at 1), or ``pitch_semitones`` the same in semitones
+        (``np.float32(2 ** (st / 12))``); the two exclude each other.  Each phoneme keeps its duration; this is resampling,
+        so formants move with the pitch.  Such a call goes straight to a
+        lane, never through the micro-batcher."""
         kw = self._pcm_kw(volume, utterance_keys)
         if sample_rate is not None:
             kw["sample_rate"] = int(sample_rate)
@@ -792,6 +797,7 @@ class InferenceSession:
         if speakers is not None:
             kw["speakers"] = speakers
         levels = self._levels_kw(input_feed, gain_db, ramp_ms)
+        levels.update(self._pitch_kw(input_feed, pitch, pitch_semitones))
         kw.update(levels)
         if alignment or timing or speakers is not None or levels:
             ids, lengths, sid = self._feed(input_feed, speakers is not None)
@@ -864,13 +870,40 @@ class InferenceSession:
             kw["ramp_samples"] = np.array([int(round(m / 1000.0 * self.config.sample_rate)) for m in ms], np.int64)
         return kw
 
+    @staticmethod
+    def _pitch_kw(input_feed, pitch, pitch_semitones) -> Dict[str, np.ndarray]:
+        """The pitch keyword of ``Engine.run`` / ``run_packed`` (empty without either): ``pitch`` [B, Tx], the ratios themselves or
+        ``np.float32(2 ** (st / 12))``; rows shorter than Tx are filled with 1."""
+        if pitch is None and pitch_semitones is None:
+            return {}
+        if pitch is not None and pitch_semitones is not None:
+            raise ValueError("pitch and pitch_semitones exclude each other")
+        shape = np.asarray(input_feed["input"]).shape
+        if len(shape) != 2:
+            raise ValueError("'input' must have shape [batch, phonemes]")
+        B, Tx = shape
+        semis = pitch is None
+        name = "pitch_semitones" if semis else "pitch"
+        v = np.full((B, Tx), 0.0 if semis else 1.0, np.float64)
+        rows = list(pitch_semitones if semis else pitch)
+        if len(rows) != B:
+            raise ValueError(name + " must have one entry per row")
+        for b, r in enumerate(rows):
+            r = np.asarray(r, np.float64).reshape(-1)
+            if r.size > Tx:
+                raise ValueError(name + ": a row has more entries than the feed has phonemes")
+            v[b, : r.size] = r
+        if not np.all(np.isfinite(v)):
+            raise ValueError(name + " must be finite")
+        return {"pitch": np.float32(2.0 ** (v / 12.0)) if semis else v.astype(np.float32)}
+
     def run_packed(self, input_feed: Dict[str, np.ndarray], order=None, lead_ms=None, lead_samples=None, tail_ms=0, wav: bool = False,
                    volume=None, utterance_keys=None, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                    alignment=False, trim_db: Optional[float] = None, trim_keep_ms: Optional[float] = None,
                    loudness: Optional[float] = None, ceiling_db: Optional[float] = None,
                    limiter_ms: Optional[float] = None, true_peak: Optional[bool] = None, compression=_SESSION,
                    stretch=None, min_frames=None, target_frames=None, duration_ms=None, speakers=None, gain_db=None,
-                   ramp_ms=None) -> "_native.PackedAudio":
+                   ramp_ms=None, pitch=None, pitch_semitones=None) -> "_native.PackedAudio":
         """The batch's finished audio as ONE contiguous stream — int16, or with ``encoding`` (else the session's
         ``output_encoding``) "ulaw" / "alaw" G.711 bytes of that int16 stream or "f32le" the float samples themselves, written by
         the packing kernel; an unknown name raises ``ValueError`` — (``mi355vits_run_packed``): only the valid
@@ -909,7 +942,8 @@ class InferenceSession:
         ``stretch`` / ``min_frames`` / ``target_frames`` / ``duration_ms``: timing in the same run, as for ``run_pcm16`` (a timed run
         that keeps its audio on the device, then the pack: one synchronisation more).  ``speakers``: who speaks each row, as for
         ``run_pcm16`` (likewise a run that keeps its audio on the device, then the pack).  ``gain_db`` / ``ramp_ms``: a gain per
-        phoneme with ramps, as for ``run_pcm16`` (likewise); the trim, the loudness target and the limiter see the shaped waveform."""
+        phoneme with ramps, as for ``run_pcm16`` (likewise); the trim, the loudness target and the limiter see the shaped waveform.
+        ``pitch`` / ``pitch_semitones``: a pitch ratio per phoneme, as for ``run_pcm16`` (likewise: everything packs the warped rows)."""
         comp = self.output_compression if compression is _SESSION else _compression_name(compression)
         if comp and wav:
             raise ValueError("wav=True with compression='flac': a FLAC stream carries its own header")
@@ -929,6 +963,7 @@ class InferenceSession:
         if speakers is not None:
             kw["speakers"] = speakers
         kw.update(self._levels_kw(input_feed, gain_db, ramp_ms))
+        kw.update(self._pitch_kw(input_feed, pitch, pitch_semitones))
         if alignment:
             kw["_alignment"] = _alignment_levels(alignment)
         ratio = _trim_ratio(trim_db if trim_db is not None else self.edge_trim_db)
