@@ -160,7 +160,8 @@ int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int 
  *           the 128-column form only for (K - 1) * dilation <= 8), math MI355VITS_MATH_BF16X3.
  * A shape or math mode the chosen path does not serve is MI355VITS_ERR_INVALID before any launch.  Which form of an impl runs is
  * the launcher's business (its grid rule; in the lab build and the CPU model also MI355VITS_WN_B3_NT, MI355VITS_WN_EPI,
- * MI355VITS_WN_SIX_WAVES, read at every launch); all forms of one impl give the same bits.
+ * MI355VITS_WN_SIX_WAVES, read at every launch); all forms of one impl give the same bits.  (MI355VITS_WN_SHAPE=32, lab build and CPU
+ * model, is no form in that sense: it runs impl 2 on v_mfma_f32_32x32x16_bf16 with the packing of that form — other sums, other bits.)
  * At and past len[b] (0 <= len[b] <= T), per row:
  *   h_in    impl 1 and 2 never use it there: every staged column is masked at len[b] (impl 2 does load h_in there for the residual of
  *           the last tile it computes, and discards it by select: any finite or non-finite bits may lie there).  impl 0 READS it, as the
@@ -190,6 +191,11 @@ int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t);
  * k_wn_layer_b3 workgroup (32, 96 or 128), *f32_geometry = launch_wn_layer's wave geometry (0: 4 waves x 3 tiles, 1: 6 x 2, 2: 12 x 1).
  * The launchers' own functions (with the lab switches where they are read).  No kernel runs. */
 int mi355vits_lab_wn_plan(int B, int T, int K, int dilation, int32_t* b3_tile, int32_t* f32_geometry);
+/* The weight fragments k_wn_layer_b3 reads in the split-bf16 modes (csrc/kernels.h, pack_conv_weights_w16): w [Cout, Cin, K] ->
+ * out [Cout / 16][K][Cin / 32][3 planes][64 lanes][4] 32-bit words, two bf16 each (the even k-slot in the low half).  gate != 0: Cout = 2 H,
+ * tanh rows then sigmoid rows, paired per 16 channels.  Cin % 32 == 0, Cout % 32 == 0 (gate: Cout % 64 == 0).  Host only: no device is touched.
+ * MI355VITS_WN_SHAPE=32 (lab build and CPU model) makes the WaveNet hooks and the engine use the earlier 32x32x16 form and packing instead. */
+int mi355vits_lab_pack_w16(const float* w, int Cout, int Cin, int K, int gate, uint32_t* out);
 /* Kernel unit-test hook: ONE multi-receptive-field stage of the decoder (csrc/kernels_mrf.cpp, kernels_mrfp.cpp,
  * kernels_mrfs.cpp) on host buffers:  y = s * sum_j RB_j(x), s = out_scale when out_scale > 0, else 1 / nrb;
  *   RB_j: x1 = x + conv_{k_j, d1_j}(lrelu_0.1(x)) + b;  x2 = x1 + conv_{k_j, d2_j}(lrelu_0.1(x1)) + b   ("same" convs),

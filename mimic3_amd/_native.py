@@ -55,7 +55,7 @@ LAB_SYMBOLS = (
     "mi355vits_lab_g711_encode", "mi355vits_test_alignment", "mi355vits_lab_edges",
     "mi355vits_lab_loudness", "mi355vits_lab_loudness_plan", "mi355vits_lab_limit",
     "mi355vits_lab_limit_env", "mi355vits_lab_true_peak", "mi355vits_lab_true_peak_plan", "mi355vits_lab_flac", "mi355vits_lab_flac_jobs",
-    "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
+    "mi355vits_test_wn_layer", "mi355vits_lab_wn_plan", "mi355vits_lab_pack_w16", "mi355vits_test_mrf_stage", "mi355vits_lab_mrf_plan",
     "mi355vits_test_dds_stack", "mi355vits_test_spline_inverse", "mi355vits_test_durations", "mi355vits_test_expand_prior",
     "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix", "mi355vits_test_levels",
     "mi355vits_test_pitch_table", "mi355vits_test_pitch_plan", "mi355vits_test_pitch",
@@ -662,6 +662,7 @@ class NativeLibrary:
                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)]
             L.mi355vits_test_wn_layer.argtypes = [ctypes.c_int, ctypes.POINTER(WnTest)]
             L.mi355vits_lab_wn_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p]
+            L.mi355vits_lab_pack_w16.argtypes = [f32p] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32)]
             L.mi355vits_test_mrf_stage.argtypes = [ctypes.c_int, ctypes.POINTER(MrfTest)]
             L.mi355vits_lab_mrf_plan.argtypes = [ctypes.c_int] * 3 + [i32p] * 7
             L.mi355vits_lab_conv_plan.argtypes = [ctypes.c_int] * 12 + [i32p, ctypes.POINTER(ConvPlan)]
@@ -1036,6 +1037,18 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return int(tile.value), int(geom.value)
+
+    def lab_pack_w16(self, w, gate=False):
+        """k_wn_layer_b3's weight fragments of w [Cout, Cin, K] (include/mi355vits_lab.h: mi355vits_lab_pack_w16) as uint16 bf16 bit
+        patterns [Cout / 16, K, Cin / 32, 3 planes, 64 lanes, 8 k-slots]."""
+        self._need_hooks()
+        w = np.ascontiguousarray(w, np.float32)
+        Cout, Cin, K = w.shape
+        out = np.zeros((Cout // 16, K, Cin // 32, 3, 64, 4), np.uint32)
+        rc = self.lib.mi355vits_lab_pack_w16(_fptr(w), Cout, Cin, K, int(bool(gate)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return out.view(np.uint16).reshape(Cout // 16, K, Cin // 32, 3, 64, 8)
 
     def test_mrf_stage(self, x, ks, d1, d2, weights, biases, lengths, impl=0, math=None, out_scale=0.0, seg=0, y_prior=None, device=0):
         """One multi-receptive-field stage through one kernel (include/mi355vits_lab.h: mi355vits_test_mrf_stage): impl 0 = k_mrf_fused

@@ -1,6 +1,7 @@
 // b3.h — device building blocks of the split-bf16 (MATH_BF16X3) kernels: staging an activation chunk as three bf16
-// planes, and one wave's share of the implicit GEMM over such planes on v_mfma_f32_32x32x16_bf16.
-// (the split itself: hipx.h, split3_pk; the weight fragment order: kernels.h, pack_conv_weights_bf16x3_mode layout 1)
+// planes, and one wave's share of the implicit GEMM over such planes on v_mfma_f32_32x32x16_bf16 (b3_chunk*) or, for the WaveNet
+// layer, on v_mfma_f32_16x16x32_bf16 (b3_chunk16).
+// (the split itself: hipx.h, split3_pk; the weight fragment order: kernels.h, pack_conv_weights_bf16x3_mode layout 1 / pack_conv_weights_w16)
 #pragma once
 #include "kernels.h"
 
@@ -341,6 +342,78 @@ __device__ __forceinline__ void h2_chunk_lean(f32x16 (&acc)[MT][NT], const uint4
                 SCHED_FENCE();
                 MI355_UNROLL
                 for (int p = 0; p < 2; ++p) rb[j][p] = xq[p * PS + xoff + j * 32];
+                SCHED_FENCE();
+            }
+        }
+    }
+}
+
+// ---- the same implicit GEMM on v_mfma_f32_16x16x32_bf16 (k_wn_layer_b3 since the shape A/B, profiles/wn_shape_ab.txt): MT 16-row
+// tiles x NC 16-column tiles per wave, a STEP = one 32-channel group of one tap (taps outermost, then groups).  The plane image is
+// b3_chunk's — records of 8 channels, [plane][record][column] — and only the lane map of the reads differs: lane l reads record
+// 4 g + (l >> 4) of column (l & 15) + 16 c.  The weight fragments of a step (MT tiles x 3 planes, pack_conv_weights_w16: 192 uint4 per
+// tile and step) are fetched one step ahead into a ring of two; the column tile is the outer loop inside a step, and ONE B fragment
+// (3 planes, double-buffered) feeds all MT row tiles.  Per accumulator the six products keep b3_chunk's order (W2X0, W0X2, W1X1, W1X0,
+// W0X1, W0X0; W1: its three); the MT accumulators of a column tile are independent chains and take each product in turn.
+template <int MT, int NC, int NG /*32-channel groups per tap*/, bool W1>
+__device__ __forceinline__ void b3_chunk16(f32x4 (&acc)[MT][NC], const uint4* const (&wp)[MT], const uint4* __restrict__ xq, int PS, int LD, int K,
+                                           int dil) {
+    // wp[i]: (tap 0, group 0, plane 0) of row tile i, lane offset included.  xq: (plane 0, record lane >> 4, column lane & 15 of column tile 0).
+    static_assert(NG % 2 == 0 && NC % 2 == 0, "the ring positions are the same in every tap / step");
+    uint4 ra[2][MT][3];
+    uint4 rb[2][3];
+    const int drop = b3_drop();
+    constexpr int NPA = W1 ? 1 : 3;
+    MI355_UNROLL
+    for (int i = 0; i < MT; ++i)
+        MI355_UNROLL
+        for (int p = 0; p < NPA; ++p) ra[0][i][p] = wp[i][p * 64];
+    MI355_UNROLL
+    for (int p = 0; p < 3; ++p) rb[0][p] = xq[p * PS];
+    for (int k = 0; k < K; ++k) {
+        const bool last_tap = k == K - 1;
+        MI355_UNROLL
+        for (int g = 0; g < NG; ++g) {
+            const int cur = g & 1, nxt = cur ^ 1;
+            // next step's operands (the very last one re-reads itself: every load stays unconditional)
+            const bool wrap = g + 1 == NG;
+            const long woff = (wrap ? (last_tap ? (long)k * NG + g : (long)(k + 1) * NG) : (long)k * NG + g + 1) * 192;
+            const int xcur = k * dil + g * 4 * LD;
+            const int xnxt = wrap ? (last_tap ? xcur : (k + 1) * dil) : xcur + 4 * LD;
+            MI355_UNROLL
+            for (int i = 0; i < MT; ++i)
+                MI355_UNROLL
+                for (int p = 0; p < NPA; ++p) ra[nxt][i][p] = wp[i][woff + p * 64];
+            SCHED_FENCE();
+            MI355_UNROLL
+            for (int c = 0; c < NC; ++c) {
+                const int bc = c & 1;
+                const int xo = c + 1 < NC ? xcur + 16 * (c + 1) : xnxt;
+                MI355_UNROLL
+                for (int p = 0; p < 3; ++p) rb[bc ^ 1][p] = xq[p * PS + xo];
+                SCHED_FENCE();
+                if constexpr (!W1) {
+                    if (drop != 1) {
+                        MI355_UNROLL
+                        for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][2], rb[bc][0], acc[i][c]);  // small terms first
+                    }
+                }
+                if (drop != 2) {
+                    MI355_UNROLL
+                    for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][0], rb[bc][2], acc[i][c]);
+                }
+                if constexpr (!W1) {
+                    if (drop != 3) {
+                        MI355_UNROLL
+                        for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][1], rb[bc][1], acc[i][c]);
+                    }
+                    MI355_UNROLL
+                    for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][1], rb[bc][0], acc[i][c]);
+                }
+                MI355_UNROLL
+                for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][0], rb[bc][1], acc[i][c]);
+                MI355_UNROLL
+                for (int i = 0; i < MT; ++i) acc[i][c] = MFMA_16x16x32_BF16(ra[cur][i][0], rb[bc][0], acc[i][c]);
                 SCHED_FENCE();
             }
         }

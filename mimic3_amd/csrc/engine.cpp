@@ -276,9 +276,23 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
                         const int src = (r < 16 ? 0 : Hh) + 16 * q + (r & 15);
                         memcpy(wg.data() + ((size_t)32 * q + r) * row, w.data() + (size_t)src * row, row * sizeof(float));
                     }
+#if defined(MI355_LAB) || defined(MI355_EMU)
+                // (the split-bf16 form on these tiles is the lab build's and the CPU model's MI355VITS_WN_SHAPE=32 only; MATH_F16X2 below
+                // keeps the tile order in every build)
                 std::vector<uint32_t> bw(bf16x3_packed_words_mode(Cout, Cin, K, EPI_STD));
                 pack_conv_weights_bf16x3_mode(wg.data(), Cout, Cin, K, EPI_STD, 1, bw.data());
                 c.packed_b3w = stage(reinterpret_cast<const float*>(bw.data()), bw.size());
+#endif
+            }
+            // the two convs of a coupling's WaveNet layer ("flow.<j>.in.<l>", "flow.<j>.rs.<l>") as k_wn_layer_b3 reads them on 16x16x32
+            // tiles (kernels.h, pack_conv_weights_w16)
+            const bool wn_conv = key.compare(0, 5, "flow.") == 0 && (epi == EPI_GATE ? key.find(".in.") != std::string::npos && Cout == 2 * Cin
+                                                                                     : key.find(".rs.") != std::string::npos && K == 1 && epi == EPI_STD &&
+                                                                                           (Cout == Cin || Cout == 2 * Cin));
+            if (wn_conv && wn_layer_b3_supported(Cin, 1, 1)) {
+                std::vector<uint32_t> pw(w16_packed_words(Cout, Cin, K));
+                pack_conv_weights_w16(w.data(), Cout, Cin, K, epi == EPI_GATE, pw.data());
+                c.packed_w16 = stage(reinterpret_cast<const float*>(pw.data()), pw.size());
             }
             if (Cin % 16 == 0 && Cout % 32 == 0) {  // MATH_F16X2: WaveNet layers (gate convs: the tile order above), staged convs, polyphase upsamplers (plain rows)
                 std::vector<uint32_t> h2(f16x2_packed_words(Cout, Cin, K));
@@ -1264,15 +1278,18 @@ void Engine::coupling_layer(int j, int B, int Ty) {
         const bool fused = !sw_.force_generic && !sw_.no_fused_wn && !wn_b3;
         // fused layer on the bf16 matrix cores (k_wn_layer_b3), else on the f32 ones (k_wn_layer).  Chosen by the layer shape
         // alone (never by the grid size), so a row's bits do not depend on what it is batched with.
-        const bool b3 = fused && math_on_bf16(kmath()) && win.packed_b3w != NO_OFF && wrs.packed_b3s != NO_OFF &&
-                        wn_layer_b3_supported(H, win.K, dil);
+        const int wn_shape = wn_layer_b3_shape();  // 16; the lab build's A/B switch: 32
+        const bool b3 = fused && math_on_bf16(kmath()) && wn_layer_b3_supported(H, win.K, dil) &&
+                        (wn_shape == 32 ? win.packed_b3w != NO_OFF && wrs.packed_b3s != NO_OFF : win.packed_w16 != NO_OFF && wrs.packed_w16 != NO_OFF);
         if (b3 || (fused && wn_layer_fused_supported(H, win.K, dil))) {
             const bool h2 = b3 && math_ == MATH_F16X2 && win.packed_h2s != NO_OFF && wrs.packed_h2s != NO_OFF;  // two fp16 terms per operand
             WnArgs w;
             w.h_in = hcur; w.h_out = hnext; w.h_bs = hbs; w.h_ld = Ty;
             w.skip = d_fskip_; w.s_bs = hbs; w.s_ld = Ty;
-            w.w_in = P(h2 ? win.packed_h2s : (b3 ? win.packed_b3w : win.packed)); w.b_in = P(win.bias);
-            w.w_rs = P(h2 ? wrs.packed_h2s : (b3 ? wrs.packed_b3s : wrs.packed)); w.b_rs = P(wrs.bias);
+            const bool s16 = b3 && !h2 && wn_shape != 32;
+            w.w_in = P(h2 ? win.packed_h2s : (s16 ? win.packed_w16 : (b3 ? win.packed_b3w : win.packed))); w.b_in = P(win.bias);
+            w.w_rs = P(h2 ? wrs.packed_h2s : (s16 ? wrs.packed_w16 : (b3 ? wrs.packed_b3s : wrs.packed))); w.b_rs = P(wrs.bias);
+            w.shape = s16 ? 16 : 32;
             w.cond = cond_l; w.cond_bs = 2L * H * c.flow_wn_layers;
             w.len = d_ylen_;
             w.B = B; w.H = H; w.T = Ty; w.K = win.K; w.dil = dil; w.Crs = wrs.Cout; w.skip_init = (l == 0);

@@ -245,13 +245,25 @@ struct WnArgs {
     int ldx = 0, vec = 0;  // filled by the launcher
     int ablate = 0;        // timing experiments only (MI355VITS_WN_ABLATE): 1 no MFMA loops, 2 no staging, 4 no stores
     int math = 0;          // launch_wn_layer_b3: MATH_BF16X3 or MATH_BF16W
+    int shape = 16;        // launch_wn_layer_b3, split-bf16 modes: wn_layer_b3_shape() — which packing w_in / w_rs are in
 };
 bool wn_layer_fused_supported(int H, int K, int dil);
 void launch_wn_layer(WnArgs a, hipStream_t s);
-// MATH_BF16X3 form of the same layer (H = 192): w_in / w_rs are pack_conv_weights_bf16x3_mode(..., EPI_STD, layout 1)
-// fragments (plain row order: tanh rows, then sigmoid rows); 96 time columns x all rows per workgroup.
+// Split-operand form of the same layer (H = 192); 32, 96 or 128 time columns x all rows per workgroup.  The split-bf16 modes run on
+// v_mfma_f32_16x16x32_bf16 (since the shape A/B, profiles/wn_shape_ab.txt) and take pack_conv_weights_w16 fragments (w_in: gate = true);
+// MATH_F16X2 runs on 32x32x16 tiles and takes pack_conv_weights_f16x2 fragments (w_in: 32-row tiles of 16 tanh rows and their sigmoid rows).
 bool wn_layer_b3_supported(int H, int K, int dil);
 void launch_wn_layer_b3(WnArgs a, hipStream_t s);
+// 16, or 32 with MI355VITS_WN_SHAPE=32 (lab build and CPU model only: the 32x32x16 form and the layout-1 packing described above, for
+// the A/B).  Read at every call; the caller packs / picks the weights for it and passes it on as WnArgs::shape.
+int wn_layer_b3_shape();
+// Split-bf16 weight fragments of k_wn_layer_b3 on 16x16x32 tiles: [16-row tile][tap][32-channel group][plane][lane] x 16 B.  Row
+// 4 q + i of plain tile n is output channel 32 (n >> 1) + 8 q + 4 (n & 1) + i; gate = true (Cout = 2 H: tanh rows, then sigmoid rows):
+// tile 2 P is plain tile P of the tanh rows and tile 2 P + 1 the same rows of the sigmoid half.  Lane l holds row l & 15 and the k-slots
+// of record 4 g + (l >> 4) of the staged planes: slot e <-> input channel 32 g + 16 (l >> 5) + 8 (e >> 2) + 4 ((l >> 4) & 1) + (e & 3).
+// Cin % 32 == 0, Cout % 32 == 0 (gate: Cout % 64 == 0).
+size_t w16_packed_words(int Cout, int Cin, int K);
+void pack_conv_weights_w16(const float* w, int Cout, int Cin, int K, bool gate, uint32_t* out);
 // The 32-column tiles per workgroup (1, 3 or 4) launch_wn_layer_b3 takes for this layer on the current device, and the geometry
 // (0: 4 waves x 3 tiles, 1: 6 x 2, 2: 12 x 1) launch_wn_layer takes at H = 192: the launchers' own rules (lab build and CPU model:
 // with the switches they read), for the launchers and for the unit-test hooks' plan call.

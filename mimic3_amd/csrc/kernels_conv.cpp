@@ -555,6 +555,33 @@ void pack_conv_weights_bf16x3_mode(const float* w, int Cout, int Cin, int K, int
                 }
 }
 
+size_t w16_packed_words(int Cout, int Cin, int K) { return (size_t)(Cout / 16) * K * (Cin / 32) * 3 * 64 * 4; }
+
+void pack_conv_weights_w16(const float* w, int Cout, int Cin, int K, bool gate, uint32_t* out) {
+    const int ng = Cin / 32, H = Cout / 2;
+    for (int tile = 0; tile < Cout / 16; ++tile)
+        for (int k = 0; k < K; ++k)
+            for (int g = 0; g < ng; ++g)
+                for (int l = 0; l < 64; ++l) {
+                    const int n = gate ? tile >> 1 : tile, row = l & 15, kq = l >> 4;
+                    const int co = (gate && (tile & 1) ? H : 0) + 32 * (n >> 1) + 8 * (row >> 2) + 4 * (n & 1) + (row & 3);
+                    uint32_t plane[3][8];
+                    for (int e = 0; e < 8; ++e) {
+                        const int ci = 32 * g + 16 * (kq >> 1) + b3_slot_channel(1, kq & 1, e);
+                        const float v = w[((size_t)co * Cin + ci) * K + k];
+                        const uint32_t h = bf16_rne_bits(v);
+                        const float r1 = v - bf16_bits_to_float(h);
+                        const uint32_t m = bf16_rne_bits(r1);
+                        const float r2 = r1 - bf16_bits_to_float(m);
+                        plane[0][e] = h; plane[1][e] = m; plane[2][e] = bf16_rne_bits(r2);
+                    }
+                    for (int p = 0; p < 3; ++p) {
+                        uint32_t* o = out + (((((size_t)tile * K + k) * ng + g) * 3 + p) * 64 + l) * 4;
+                        for (int j = 0; j < 4; ++j) o[j] = plane[p][2 * j] | (plane[p][2 * j + 1] << 16);
+                    }
+                }
+}
+
 // IEEE half bits of a float, round to nearest even (host-side weight packing of MATH_F16X2)
 static inline uint32_t f16_rne_bits(float f) {
     uint32_t u;

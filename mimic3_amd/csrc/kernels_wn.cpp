@@ -424,17 +424,17 @@ __global__ __launch_bounds__(64 * NW) MIN_WAVES_PER_SIMD(3) void k_wn_layer_h192
 }
 
 // ------------------------------------------------------------------------------------------------
-// The same WaveNet layer in MATH_BF16X3 (f32 operands split 3 x bf16, six products on v_mfma_f32_32x32x16_bf16).
+// The same WaveNet layer in MATH_BF16X3 (f32 operands split 3 x bf16, six products on the bf16 matrix cores: v_mfma_f32_16x16x32_bf16
+// since the shape A/B of profiles/wn_shape_ab.txt, v_mfma_f32_32x32x16_bf16 before it and still in MATH_F16X2 — WnTiles below).
 // At 16x the f32 MFMA rate the 32-column geometry above would be bound by streaming the layer's weights (every
 // workgroup reads all of them; 32 columns of reuse), so the tile is turned around:
-//   * a workgroup owns 96 time columns of ALL 2H = 384 in-layer rows: B x T / 96 workgroups (256 for the batch-32
-//     bench shape: one per CU), four waves = one per SIMD with the whole 512-register file each;
-//   * a wave computes 3 row tiles x 3 column tiles (9 accumulators): every weight fragment feeds 3 MFMA groups, every
-//     activation fragment 3 — 18 operand fetches per 54 MFMAs;
-//   * h (+halo) is split into three bf16 planes once while it is staged (b3.h), the raw in-layer result goes through
-//     LDS (the dead h planes' space), is gated by all threads, split, and becomes the B operand of the res/skip conv;
-//     u never leaves the CU.
-// LDS: max(3 planes x 192 ch x 104 col x 2 B = 117 KiB, raw 384 x 96 x 4 B = 144 KiB).
+//   * a workgroup owns 96 time columns (32 / 128: wn_layer_b3_column_tiles) of ALL 2H = 384 in-layer rows: B x T / 96 workgroups (256 for
+//     the batch-32 bench shape: one per CU), four waves = one per SIMD with the whole 512-register file each;
+//   * a wave computes 96 rows x all columns (32x32x16: 3 row tiles x 3 column tiles, 16x16x32: 6 x 6): every weight fragment feeds all
+//     the column tiles, every activation fragment all the wave's row tiles;
+//   * h (+halo) is split into three bf16 planes once while it is staged (b3.h); the in-layer result is gated in the accumulators'
+//     registers, split, and stored into the dead h planes' space as the B operand of the res/skip conv; u never leaves the CU.
+// LDS: the h planes, 3 x 192 ch x (columns + halo) x 2 B = 117 KiB at 96 columns, 153 KiB at 128.
 // ------------------------------------------------------------------------------------------------
 constexpr int WNB_H = 192, WNB_NG = WNB_H / 16;
 constexpr int WNB_RING = 4;  // weight-fragment buffers of the four-wave form
@@ -466,83 +466,59 @@ constexpr int WNB_EPI = 1;   // epilogue form of the four-wave, 96-column kernel
 // H2 (MATH_F16X2): operands as two fp16 planes (activations x 2^4 while they are split, weights x 2^13 when packed), three
 // products per multiply-add; the accumulators run scaled by 2^17 (bias and conditioning enter scaled) and are unscaled,
 // exactly, where they leave the matrix cores — the gate and the residual / skip updates see the same values as before.
-// Four waves, one per SIMD with the whole register file each; MW = 3 row tiles (of the 12) per wave.
-// RA: weight-fragment ring (b3.h b3_chunk_ra): 2 = one group ahead (nt 1, bf16 weights, f16x2), 4 = three groups ahead
-// EP: the epilogue's old-value loads (h residual: L2 hits, skip accumulator: HBM) — 0 = one tile ahead of the stores (rounds 2 - 4), 1 = three
-// tiles ahead (48 loads in flight per lane: the nine tiles of a wave were nine dependent round trips)
-template <bool W1, int NT, bool H2, int RA, int EP>
-__device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
-    constexpr int MW = 3, NWV = 4, NTH = 256;
-    static_assert(!(W1 && H2), "one reduced-operand variant at a time");
-    constexpr int H = WNB_H, T_B = 32 * NT, NG = WNB_NG;
-    constexpr int NP = H2 ? 2 : 3, GW = H2 ? 128 : 192;  // planes per operand; uint4 per weight-fragment group
-    constexpr float ACC = H2 ? F16X2_ACC_SCALE : 1.0f, UNACC = H2 ? 1.0f / F16X2_ACC_SCALE : 1.0f;
-    DYN_SMEM(float, smem);
-    uint4* planes = reinterpret_cast<uint4*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, w = WAVE_UNIFORM(tid >> 6);
-    const int brow = lane >> 5, bcol = lane & 31;
-    const int b = blockIdx.y;
-    const int t0 = blockIdx.x * T_B;
-    int len = a.len ? a.len[b] : a.T;
-    if (len > a.T) len = a.T;
-    if (t0 >= len) return;  // ragged batches (round 6): a tile past its row's length is never computed (kernels_mrfp.cpp next_item)
-    const int pad = (a.K - 1) / 2 * a.dil;
-    const int tlo = t0 - pad;
-    const int ts = tlo >= 0 ? (tlo & ~3) : -(((-tlo) + 3) & ~3);
-    const int toff = tlo - ts;
-    const int LD = a.ldx;          // staged columns of the h tile
-    WN_TS_DECL();
-    WN_TS(0);
-    const int PS = NG * 2 * LD;    // uint4 per plane
-    const bool two = a.Crs == 2 * H;
+// Four waves, one per SIMD with the whole register file each; MW row tiles per wave (S = 32: 3 of the 12, S = 16: 6 of the 24).
+// RA (S = 32): weight-fragment ring (b3.h b3_chunk_ra): 2 = one group ahead (nt 1, bf16 weights, f16x2), 4 = three groups ahead.  S = 16:
+// b3_chunk16 keeps the fragments one 32-channel step ahead in every form.
+// EP: the epilogue's old-value loads (h residual: L2 hits, skip accumulator: HBM) — 0 = 16 values per lane ahead of the stores (one 32 x 32
+// tile: rounds 2 - 4), 1 = 48 values ahead (three 32 x 32 or twelve 16 x 16 tiles: a wave's tiles were as many dependent round trips)
+//
+// The MFMA shape (S) decides how a wave's 96 rows x T_B columns are cut into accumulator tiles, and nothing else: WnTiles<S> holds that
+// layout — which row of which conv an accumulator register is, where a lane's gated values go in u's planes, which chunk loop runs.
+//   S = 32 (v_mfma_f32_32x32x16_bf16; MATH_F16X2, and MI355VITS_WN_SHAPE=32 in the lab build and the CPU model): 3 x NT tiles of 32 x 32,
+//     gate-conv tile q = the tanh rows of channels 16 q .. 16 q + 15 and their sigmoid rows (packed_b3w), plain tiles in row order.
+//   S = 16 (v_mfma_f32_16x16x32_bf16, the product's split-bf16 form): 6 x 2 NT tiles of 16 x 16.  Row 4 q + i of 16-row tile n is channel
+//     32 (n >> 1) + 8 q + 4 (n & 1) + i (k_mrf_p's map); the gate conv is 12 pairs of a tanh tile and the sigmoid tile of the same 16
+//     channels, wave w owns pairs w, w + 4, w + 8, so a lane's tanh and sigmoid values of a channel sit in the same register of two tiles
+//     and its four gated values are one half record of u's planes (one 8-byte store per plane).  The res/skip conv has 24 plain tiles,
+//     six per wave (last layer: 12, three per wave).  Weights: pack_conv_weights_w16.
+template <int S> struct WnTiles;
 
-    if (!(LAB_ABLATE(a) & 2)) stage_planes<NG, NG, H2>(a.h_in + (long)b * a.h_bs, a.h_ld, LD, ts, len, 1.0f, planes, PS, tid, NTH);  // column sets x row batches: one round trip
-    __syncthreads();
-    WN_TS(1);
-
-    // ---- in-layer conv: wave w owns row tiles w, w + 4, w + 8 (rows 32 q .. 32 q + 31 of the 2H), all 3 column tiles
-    // (speaker conditioning without a branch per element — a test per load makes hipcc wait for each one in turn)
-    const float* condp = a.cond ? a.cond + (long)b * a.cond_bs : a.b_in;
-    const float cond_on = a.cond ? 1.0f : 0.0f;
-    {
-        f32x16 acc[MW][NT];
-        const uint4* wp[MW];
-        MI355_UNROLL
-        for (int i = 0; i < MW; ++i) {
-            const int q = w + NWV * i;
-            MI355_UNROLL
-            for (int r = 0; r < 16; ++r) {
-                // tile q = the tanh rows (tile rows 0 - 15) and the sigmoid rows (16 - 31) of channels 16 q .. 16 q + 15: see the gate below
-                const int c = (r < 8 ? 0 : H) + 16 * q + (r & 3) + 8 * ((r >> 2) & 1) + 4 * brow;
-                const float v = (a.b_in[c] + cond_on * condp[c]) * ACC;  // unconditional loads: all in flight together
-                MI355_UNROLL
-                for (int j = 0; j < NT; ++j) acc[i][j][r] = v;
-            }
-            wp[i] = reinterpret_cast<const uint4*>(a.w_in) + (long)q * a.K * NG * GW + lane;
-        }
-        if (!(LAB_ABLATE(a) & 1)) {
-            if constexpr (H2) h2_chunk<MW, NT, NG, NT>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
-            else if constexpr (RA > 2 && NT >= 4) b3_chunk_lean_ra<MW, NT, NG, W1, RA>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);  // (four column tiles: B single-buffered)
-            else if constexpr (RA > 2) b3_chunk_ra<MW, NT, NG, NT, W1, RA>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
-            else b3_chunk<MW, NT, NG, NT, W1>(acc, wp, planes + brow * LD + bcol + toff, PS, LD, a.K, NG, a.dil);
-        }
-        __syncthreads();  // every wave is done with the h planes: u's planes take their place (column pitch T_B)
-        WN_TS(2);
-        WN_TS(3);
-        // ---- gate in registers (round 6): the in-layer conv's rows are stored permuted (Engine::add_conv_data, packed_b3w / packed_h2s of a gate
-        // conv) so that 32-row tile q holds tanh rows of channels 16 q .. 16 q + 15 in its rows 0 - 15 and their sigmoid rows in 16 - 31: accumulator
-        // r < 8 and r + 8 of a lane are the two halves of ONE channel, and a lane's eight gated values of a (row tile, column tile) are exactly
-        // the eight k-slots of one B-operand record (16-channel group q, half brow, its column) of the res/skip conv — the raw result never
-        // goes through LDS (rounds 2 - 5: 144 ds_write_b32 + a barrier + 144 ds_read_b32 per lane).  Same values, same gate: same bits.
-        constexpr int PSU0 = NG * 2 * T_B;
+template <> struct WnTiles<32> {
+    typedef f32x16 Acc;
+    static constexpr int NR = 16, CW = 32, ROWS = 32, MW = 3, MW_LAST = 2;  // registers per tile, tile width / height, tiles per wave (last layer: with work)
+    static __device__ __forceinline__ int col(int lane) { return lane & 31; }
+    static __device__ __forceinline__ int krec(int lane) { return lane >> 5; }  // the lane's record within a k-group of the planes
+    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 5); }
+    static __device__ __forceinline__ int reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
+    static __device__ __forceinline__ int tile_row0(int q) { return 32 * q; }
+    static __device__ __forceinline__ int gate_tile(int w, int i) { return w + 4 * i; }
+    static __device__ __forceinline__ int gate_row(int H, int w, int i, int r, int lane) {
+        return (r < 8 ? 0 : H) + 16 * (w + 4 * i) + (r & 3) + 8 * ((r >> 2) & 1) + 4 * (lane >> 5);
+    }
+    template <int MT, int NC, bool W1, bool H2, int RA, bool LAST>
+    static __device__ __forceinline__ void conv(Acc (&acc)[MT][NC], const uint4* const (&wp)[MT], const uint4* xq, int PS, int LD, int K, int dil) {
+        constexpr int NG = WNB_NG;
+        if constexpr (H2) h2_chunk<MT, NC, NG, NC>(acc, wp, xq, PS, LD, K, NG, dil);
+        else if constexpr (LAST) b3_chunk<MT, NC, NG, NC, W1>(acc, wp, xq, PS, LD, K, NG, dil);
+        else if constexpr (RA > 2 && NC >= 4) b3_chunk_lean_ra<MT, NC, NG, W1, RA>(acc, wp, xq, PS, LD, K, NG, dil);  // (four column tiles: B single-buffered)
+        else if constexpr (RA > 2) b3_chunk_ra<MT, NC, NG, NC, W1, RA>(acc, wp, xq, PS, LD, K, NG, dil);
+        else b3_chunk<MT, NC, NG, NC, W1>(acc, wp, xq, PS, LD, K, NG, dil);
+    }
+    // gate in registers (round 6): accumulator r < 8 and r + 8 of a lane are the two halves of ONE channel, and a lane's eight gated values of a
+    // (row tile, column tile) are exactly the eight k-slots of one B-operand record (16-channel group q, half brow, its column) of the res/skip
+    // conv — the raw result never goes through LDS (rounds 2 - 5: 144 ds_write_b32 + a barrier + 144 ds_read_b32 per lane).
+    template <int NC, bool H2>
+    static __device__ __forceinline__ void gate_store(const Acc (&acc)[MW][NC], uint4* planes, int w, int lane, float UNACC) {
+        constexpr int T_B = 32 * NC, PSU0 = WNB_NG * 2 * T_B;
+        const int brow = lane >> 5, bcol = lane & 31;
         MI355_UNROLL
         for (int i = 0; i < MW; ++i)
             MI355_UNROLL
-            for (int j = 0; j < NT; ++j) {
+            for (int j = 0; j < NC; ++j) {
                 float u[8];
                 MI355_UNROLL
                 for (int e = 0; e < 8; ++e) u[e] = wn_gate_f(acc[i][j][e] * UNACC, acc[i][j][e + 8] * UNACC);
-                const int idx = (2 * (w + NWV * i) + brow) * T_B + 32 * j + bcol;
+                const int idx = (2 * (w + 4 * i) + brow) * T_B + 32 * j + bcol;
                 if constexpr (H2) {
                     uint4 h4, m4;
                     split2_pk(u[0] * F16X2_X_SCALE, u[1] * F16X2_X_SCALE, h4.x, m4.x);
@@ -563,7 +539,113 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
                 }
             }
     }
-    const int ntr = a.Crs / 32;
+};
+
+template <> struct WnTiles<16> {
+    typedef f32x4 Acc;
+    static constexpr int NR = 4, CW = 16, ROWS = 16, MW = 6, MW_LAST = 3;
+    static __device__ __forceinline__ int col(int lane) { return lane & 15; }
+    static __device__ __forceinline__ int krec(int lane) { return lane >> 4; }
+    static __device__ __forceinline__ int lane_row(int lane) { return 8 * (lane >> 4); }
+    static __device__ __forceinline__ int reg_row(int r) { return r; }
+    static __device__ __forceinline__ int tile_row0(int n) { return 32 * (n >> 1) + 4 * (n & 1); }
+    static __device__ __forceinline__ int gate_tile(int w, int i) { return 2 * (w + 4 * (i >> 1)) + (i & 1); }  // pair w + 4 (i / 2): tanh tile, sigmoid tile
+    static __device__ __forceinline__ int gate_row(int H, int w, int i, int r, int lane) {
+        return ((i & 1) ? H : 0) + tile_row0(w + 4 * (i >> 1)) + 8 * (lane >> 4) + r;
+    }
+    template <int MT, int NC, bool W1, bool H2, int RA, bool LAST>
+    static __device__ __forceinline__ void conv(Acc (&acc)[MT][NC], const uint4* const (&wp)[MT], const uint4* xq, int PS, int LD, int K, int dil) {
+        static_assert(!H2, "MATH_F16X2 runs on the 32x32x16 tiles");
+        b3_chunk16<MT, NC, WNB_H / 32, W1>(acc, wp, xq, PS, LD, K, dil);
+    }
+    // lane (q = lane >> 4, column c) holds channels 32 g + 8 q + 4 hh + 0..3 of pair (g, hh): slots 4 (q & 1) .. + 3 of record (16-channel
+    // group 2 g + (q >> 1), half hh) — the record's lower or upper 8 bytes in each plane
+    template <int NC, bool H2>
+    static __device__ __forceinline__ void gate_store(const Acc (&acc)[MW][NC], uint4* planes, int w, int lane, float) {
+        constexpr int T_B = 16 * NC, PSU0 = WNB_NG * 2 * T_B;
+        uint2* p2 = reinterpret_cast<uint2*>(planes);
+        const int q = lane >> 4, c = lane & 15;
+        MI355_UNROLL
+        for (int i = 0; i < MW / 2; ++i) {
+            const int pr = w + 4 * i;
+            const int rec = 2 * (2 * (pr >> 1) + (q >> 1)) + (pr & 1);
+            MI355_UNROLL
+            for (int j = 0; j < NC; ++j) {
+                float u[4];
+                MI355_UNROLL
+                for (int e = 0; e < 4; ++e) u[e] = wn_gate_f(acc[2 * i][j][e], acc[2 * i + 1][j][e]);
+                const int idx = rec * T_B + 16 * j + c;
+                uint2 h2, m2, l2;
+                split3_pk(u[0], u[1], h2.x, m2.x, l2.x);
+                split3_pk(u[2], u[3], h2.y, m2.y, l2.y);
+                p2[2 * idx + (q & 1)] = h2;
+                p2[2 * (PSU0 + idx) + (q & 1)] = m2;
+                p2[2 * (2 * PSU0 + idx) + (q & 1)] = l2;
+            }
+        }
+    }
+};
+
+template <int S, bool W1, int NT, bool H2, int RA, int EP>
+__device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
+    typedef WnTiles<S> TL;
+    typedef typename TL::Acc Acc;
+    constexpr int MW = TL::MW, NR = TL::NR, NWV = 4, NTH = 256;
+    static_assert(!(W1 && H2), "one reduced-operand variant at a time");
+    constexpr int H = WNB_H, T_B = 32 * NT, NG = WNB_NG, NC = T_B / TL::CW;  // NC column tiles per wave
+    constexpr int GW = H2 ? 128 : 192;  // uint4 per weight-fragment group (two fp16 or three bf16 planes)
+    constexpr int TAPW = S == 16 ? (H / 32) * 192 : NG * GW;  // uint4 per (row tile, tap) of the packed weights
+    constexpr float ACC = H2 ? F16X2_ACC_SCALE : 1.0f, UNACC = H2 ? 1.0f / F16X2_ACC_SCALE : 1.0f;
+    DYN_SMEM(float, smem);
+    uint4* planes = reinterpret_cast<uint4*>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, w = WAVE_UNIFORM(tid >> 6);
+    const int lrow = TL::lane_row(lane), bcol = TL::col(lane);
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.x * T_B;
+    int len = a.len ? a.len[b] : a.T;
+    if (len > a.T) len = a.T;
+    if (t0 >= len) return;  // ragged batches (round 6): a tile past its row's length is never computed (kernels_mrfp.cpp next_item)
+    const int pad = (a.K - 1) / 2 * a.dil;
+    const int tlo = t0 - pad;
+    const int ts = tlo >= 0 ? (tlo & ~3) : -(((-tlo) + 3) & ~3);
+    const int toff = tlo - ts;
+    const int LD = a.ldx;          // staged columns of the h tile
+    WN_TS_DECL();
+    WN_TS(0);
+    const int PS = NG * 2 * LD;    // uint4 per plane
+    const bool two = a.Crs == 2 * H;
+
+    if (!(LAB_ABLATE(a) & 2)) stage_planes<NG, NG, H2>(a.h_in + (long)b * a.h_bs, a.h_ld, LD, ts, len, 1.0f, planes, PS, tid, NTH);  // column sets x row batches: one round trip
+    __syncthreads();
+    WN_TS(1);
+
+    // ---- in-layer conv: the wave's MW row tiles of the 2H (WnTiles: which rows), all NC column tiles
+    // (speaker conditioning without a branch per element — a test per load makes hipcc wait for each one in turn)
+    const float* condp = a.cond ? a.cond + (long)b * a.cond_bs : a.b_in;
+    const float cond_on = a.cond ? 1.0f : 0.0f;
+    {
+        Acc acc[MW][NC];
+        const uint4* wp[MW];
+        MI355_UNROLL
+        for (int i = 0; i < MW; ++i) {
+            MI355_UNROLL
+            for (int r = 0; r < NR; ++r) {
+                const int c = TL::gate_row(H, w, i, r, lane);
+                const float v = (a.b_in[c] + cond_on * condp[c]) * ACC;  // unconditional loads: all in flight together
+                MI355_UNROLL
+                for (int j = 0; j < NC; ++j) acc[i][j][r] = v;
+            }
+            wp[i] = reinterpret_cast<const uint4*>(a.w_in) + (long)TL::gate_tile(w, i) * a.K * TAPW + lane;
+        }
+        if (!(LAB_ABLATE(a) & 1)) TL::template conv<MW, NC, W1, H2, RA, false>(acc, wp, planes + TL::krec(lane) * LD + bcol + toff, PS, LD, a.K, a.dil);
+        __syncthreads();  // every wave is done with the h planes: u's planes take their place (column pitch T_B)
+        WN_TS(2);
+        WN_TS(3);
+        // ---- gate in registers: the in-layer conv's rows are stored permuted (Engine::add_conv_data) so that a lane holds both halves of its
+        // channels, and its gated values are (part of) one B-operand record of the res/skip conv: WnTiles<S>::gate_store
+        TL::template gate_store<NC, H2>(acc, planes, w, lane, UNACC);
+    }
+    const int ntr = a.Crs / TL::ROWS;
     const float* src[MW];
     float* dst[MW];
     long ldr[MW];
@@ -573,50 +655,52 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
         const int q = w + NWV * i;
         valid[i] = q < ntr;
         const int qc = valid[i] ? q : ntr - 1;
-        to_h[i] = two && 32 * qc < H;  // wave-uniform
+        const int row0 = TL::tile_row0(qc);  // (a tile's rows lie within one 32-row block)
+        to_h[i] = two && row0 < H;  // wave-uniform
         if (to_h[i]) {
-            src[i] = a.h_in + (long)b * a.h_bs + (long)(32 * qc) * a.h_ld;
-            dst[i] = a.h_out + (long)b * a.h_bs + (long)(32 * qc) * a.h_ld;
+            src[i] = a.h_in + (long)b * a.h_bs + (long)row0 * a.h_ld;
+            dst[i] = a.h_out + (long)b * a.h_bs + (long)row0 * a.h_ld;
             ldr[i] = a.h_ld;
             use_old[i] = true;
         } else {
             const int sub = two ? H : 0;
-            src[i] = a.skip + (long)b * a.s_bs + (long)(32 * qc - sub) * a.s_ld;
-            dst[i] = a.skip + (long)b * a.s_bs + (long)(32 * qc - sub) * a.s_ld;
+            src[i] = a.skip + (long)b * a.s_bs + (long)(row0 - sub) * a.s_ld;
+            dst[i] = a.skip + (long)b * a.s_bs + (long)(row0 - sub) * a.s_ld;
             ldr[i] = a.s_ld;
             use_old[i] = !a.skip_init;
         }
     }
-    auto load_tile = [&](int i, int j, float (&old)[16]) {
-        const int t = t0 + j * 32 + bcol;
+    auto load_tile = [&](int i, int j, float (&old)[NR]) {
+        const int t = t0 + j * TL::CW + bcol;
         const int tc = t < a.T ? t : a.T - 1;
         if (valid[i] && use_old[i]) {
             MI355_UNROLL
-            for (int r = 0; r < 16; ++r) old[r] = src[i][(long)((r & 3) + 8 * (r >> 2) + 4 * brow) * ldr[i] + tc];
+            for (int r = 0; r < NR; ++r) old[r] = src[i][(long)(TL::reg_row(r) + lrow) * ldr[i] + tc];
         } else {
             MI355_UNROLL
-            for (int r = 0; r < 16; ++r) old[r] = 0.0f;
+            for (int r = 0; r < NR; ++r) old[r] = 0.0f;
         }
     };
-    constexpr int EPA = EP == 0 ? 1 : 3, EPR = EPA + 1;  // tiles ahead; ring of old-value tiles
-    float old[EPR][16];
+    // tiles ahead (EP 0: 16 old values of a lane in flight, EP 1: 48, whatever the tile size); ring of old-value tiles
+    constexpr int EPA = (EP == 0 ? 1 : 3) * (16 / NR), EPR = EPA + 1;
+    float old[EPR][NR];
     // EP >= 1: the same loads / stores as buffer instructions — a tile's base in the resource, ONE lane offset per tile, the row offsets in
     // SGPRs, and the wave-uniform / per-lane conditions folded into the offset (out of range: the load returns 0, the store is dropped), so
     // nothing between a load's issue and its use is conditional (hipcc's wait-count pass: DESIGN 4.6 item 1)
-    auto load_tile_b = [&](int i, int j, float (&o)[16]) MI355_INLINE_LAMBDA {
-        const int t = t0 + j * 32 + bcol;
+    auto load_tile_b = [&](int i, int j, float (&o)[NR]) MI355_INLINE_LAMBDA {
+        const int t = t0 + j * TL::CW + bcol;
         const int tc = t < a.T ? t : a.T - 1;
         const BufRsrc rs = buf_rsrc(src[i]);
         const unsigned row4 = 4u * (unsigned)ldr[i];
-        const unsigned vo = (valid[i] && use_old[i]) ? (unsigned)(4 * brow) * row4 + 4u * (unsigned)tc : BUF_OOB;
+        const unsigned vo = (valid[i] && use_old[i]) ? (unsigned)lrow * row4 + 4u * (unsigned)tc : BUF_OOB;
         MI355_UNROLL
-        for (int r = 0; r < 16; ++r) o[r] = buf_load_f32(rs, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * row4);
+        for (int r = 0; r < NR; ++r) o[r] = buf_load_f32(rs, vo, (unsigned)TL::reg_row(r) * row4);
     };
     constexpr int PSU = NG * 2 * T_B;
     __syncthreads();
     WN_TS(4);
-    // ---- res/skip 1x1 conv: Crs / 32 row tiles (12, last layer 6), tile q on wave q % 4
-    f32x16 acc[MW][NT];
+    // ---- res/skip 1x1 conv: Crs / ROWS row tiles, tile q on wave q % 4 (S = 32: 12, last layer 6; S = 16: 24, last layer 12)
+    Acc acc[MW][NC];
     {
         const uint4* wp[MW];
         MI355_UNROLL
@@ -624,91 +708,97 @@ __device__ __forceinline__ void wn_layer_b3_body(const WnArgs& a) {
             int q = w + NWV * i;
             if (q >= ntr) q = ntr - 1;  // beyond the last tile: recompute it, discarded below
             MI355_UNROLL
-            for (int r = 0; r < 16; ++r) {
-                const float v = a.b_rs[32 * q + (r & 3) + 8 * (r >> 2) + 4 * brow] * ACC;
+            for (int r = 0; r < NR; ++r) {
+                const float v = a.b_rs[TL::tile_row0(q) + TL::reg_row(r) + lrow] * ACC;
                 MI355_UNROLL
-                for (int j = 0; j < NT; ++j) acc[i][j][r] = v;
+                for (int j = 0; j < NC; ++j) acc[i][j][r] = v;
             }
-            wp[i] = reinterpret_cast<const uint4*>(a.w_rs) + (long)q * NG * GW + lane;
+            wp[i] = reinterpret_cast<const uint4*>(a.w_rs) + (long)q * TAPW + lane;
         }
         if (!(LAB_ABLATE(a) & 1)) {
+            const uint4* xq = planes + TL::krec(lane) * T_B + bcol;
             if (two) {
-                if constexpr (H2) h2_chunk<MW, NT, NG, NT>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-                else if constexpr (RA > 2 && NT >= 4) b3_chunk_lean_ra<MW, NT, NG, W1, RA>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-                else if constexpr (RA > 2) b3_chunk_ra<MW, NT, NG, NT, W1, RA>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-                else b3_chunk<MW, NT, NG, NT, W1>(acc, wp, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-            } else {  // 6 tiles: waves 0, 1 two tiles, waves 2, 3 one (second index clamped)
-                f32x16 a2[2][NT];
-                const uint4* w2[2] = {wp[0], wp[1]};
+                TL::template conv<MW, NC, W1, H2, RA, false>(acc, wp, xq, PSU, T_B, 1, 0);
+            } else {  // half the tiles.  S = 32, 6 tiles: waves 0, 1 two tiles, waves 2, 3 one (second index clamped); S = 16, 12 tiles: three each
+                constexpr int ML = TL::MW_LAST;
+                Acc a2[ML][NC];
+                const uint4* w2[ML];
                 MI355_UNROLL
-                for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < ML; ++i) {
+                    w2[i] = wp[i];
                     MI355_UNROLL
-                    for (int j = 0; j < NT; ++j) a2[i][j] = acc[i][j];
-                if constexpr (H2) h2_chunk<2, NT, NG, NT>(a2, w2, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
-                else b3_chunk<2, NT, NG, NT, W1>(a2, w2, planes + brow * T_B + bcol, PSU, T_B, 1, NG, 0);
+                    for (int j = 0; j < NC; ++j) a2[i][j] = acc[i][j];
+                }
+                TL::template conv<ML, NC, W1, H2, RA, true>(a2, w2, xq, PSU, T_B, 1, 0);
                 MI355_UNROLL
-                for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < ML; ++i)
                     MI355_UNROLL
-                    for (int j = 0; j < NT; ++j) acc[i][j] = a2[i][j];
+                    for (int j = 0; j < NC; ++j) acc[i][j] = a2[i][j];
             }
         }
         if constexpr (H2) {  // back to the unscaled domain (exact)
             MI355_UNROLL
             for (int i = 0; i < MW; ++i)
                 MI355_UNROLL
-                for (int j = 0; j < NT; ++j)
+                for (int j = 0; j < NC; ++j)
                     MI355_UNROLL
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] *= UNACC;
+                    for (int r = 0; r < NR; ++r) acc[i][j][r] *= UNACC;
         }
     }
     WN_TS(5);
     if ((LAB_ABLATE(a) & 4) && acc[0][0][0] != 1.2345f) return;
-    // ---- epilogue: rows < H (two-output layers): h' = (h + rs) * mask; the others: skip (+)= rs.  The 16 old values a
-    // lane needs per 32 x 32 tile are loaded unconditionally (clamped column) and one tile ahead of the stores: the
+    // ---- epilogue: rows < H (two-output layers): h' = (h + rs) * mask; the others: skip (+)= rs.  The old values a
+    // lane needs per tile are loaded unconditionally (clamped column) and ahead of the stores: the
     // memory counter retires in order, so a load issued after a store cannot be waited for without waiting for that
     // store's acknowledgement too — with tile k + 1's loads in front of tile k's stores no wait includes a fresh store.
-    auto store_tile = [&](int i, int j, const float (&old)[16]) {
-        const int t = t0 + j * 32 + bcol;
+    auto store_tile = [&](int i, int j, const float (&old)[NR]) {
+        const int t = t0 + j * TL::CW + bcol;
         if (!valid[i] || t >= a.T) return;
         const bool live = t < len || !to_h[i];  // h' is masked, skip is not (its consumer masks)
         MI355_UNROLL
-        for (int r = 0; r < 16; ++r) dst[i][(long)((r & 3) + 8 * (r >> 2) + 4 * brow) * ldr[i] + t] = live ? old[r] + acc[i][j][r] : 0.0f;
+        for (int r = 0; r < NR; ++r) dst[i][(long)(TL::reg_row(r) + lrow) * ldr[i] + t] = live ? old[r] + acc[i][j][r] : 0.0f;
     };
     if constexpr (EP == 0) {
-        load_tile(0, 0, old[0]);
         MI355_UNROLL
-        for (int k = 0; k < MW * NT; ++k) {
-            if (k + 1 < MW * NT) load_tile((k + 1) / NT, (k + 1) % NT, old[(k + 1) & 1]);
+        for (int k = 0; k < EPA && k < MW * NC; ++k) load_tile(k / NC, k % NC, old[k]);
+        MI355_UNROLL
+        for (int k = 0; k < MW * NC; ++k) {
+            if (k + EPA < MW * NC) load_tile((k + EPA) / NC, (k + EPA) % NC, old[(k + EPA) % EPR]);
             SCHED_FENCE();
-            store_tile(k / NT, k % NT, old[k & 1]);
+            store_tile(k / NC, k % NC, old[k % EPR]);
             SCHED_FENCE();
         }
     } else {
-        auto store_tile_b = [&](int i, int j, const float (&o)[16]) MI355_INLINE_LAMBDA {
-            const int t = t0 + j * 32 + bcol;
+        auto store_tile_b = [&](int i, int j, const float (&o)[NR]) MI355_INLINE_LAMBDA {
+            const int t = t0 + j * TL::CW + bcol;
             const bool live = t < len || !to_h[i];
             const BufRsrc rs = buf_rsrc(dst[i]);
             const unsigned row4 = 4u * (unsigned)ldr[i];
-            const unsigned vo = (valid[i] && t < a.T) ? (unsigned)(4 * brow) * row4 + 4u * (unsigned)t : BUF_OOB;
+            const unsigned vo = (valid[i] && t < a.T) ? (unsigned)lrow * row4 + 4u * (unsigned)t : BUF_OOB;
             MI355_UNROLL
-            for (int r = 0; r < 16; ++r) buf_store_f32(rs, vo, (unsigned)((r & 3) + 8 * (r >> 2)) * row4, live ? o[r] + acc[i][j][r] : 0.0f);
+            for (int r = 0; r < NR; ++r) buf_store_f32(rs, vo, (unsigned)TL::reg_row(r) * row4, live ? o[r] + acc[i][j][r] : 0.0f);
         };
         MI355_UNROLL
-        for (int k = 0; k < EPA && k < MW * NT; ++k) load_tile_b(k / NT, k % NT, old[k]);
+        for (int k = 0; k < EPA && k < MW * NC; ++k) load_tile_b(k / NC, k % NC, old[k]);
         MI355_UNROLL
-        for (int k = 0; k < MW * NT; ++k) {
-            if (k + EPA < MW * NT) load_tile_b((k + EPA) / NT, (k + EPA) % NT, old[(k + EPA) % EPR]);
+        for (int k = 0; k < MW * NC; ++k) {
+            if (k + EPA < MW * NC) load_tile_b((k + EPA) / NC, (k + EPA) % NC, old[(k + EPA) % EPR]);
             SCHED_FENCE();
-            store_tile_b(k / NT, k % NT, old[k % EPR]);
+            store_tile_b(k / NC, k % NC, old[k % EPR]);
             SCHED_FENCE();
         }
     }
     WN_TS_END();
 }
 
-template <bool W1, int NT, bool H2 = false, int RA = 2, int EP = 0>
+template <int S, bool W1, int NT, bool H2 = false, int RA = 2, int EP = 0>
 __global__ __launch_bounds__(256) void k_wn_layer_b3(WnArgs a) {
-    wn_layer_b3_body<W1, NT, H2, RA, EP>(a);
+    wn_layer_b3_body<S, W1, NT, H2, RA, EP>(a);
+}
+
+int wn_layer_b3_shape() {
+    const char* s = lab_getenv("MI355VITS_WN_SHAPE");  // read per launch: the A/B runs both forms in one process
+    return s && atoi(s) == 32 ? 32 : 16;
 }
 
 bool wn_layer_b3_supported(int H, int K, int dil) {
@@ -752,26 +842,45 @@ void launch_wn_layer_b3(WnArgs a, hipStream_t s) {
 #endif
         LAUNCH_KERNEL(kfn, grid, dim3(256), shmem, s, a);
     };
-    if (nt == 4 && a.math != MATH_F16X2) {
+    // the epilogue of the 96-column form (WNB_EPI: the loads three 32 x 32 tiles ahead; MI355VITS_WN_EPI=0: one tile ahead, the form past the buffer range)
+    int epi = WNB_EPI;
+    if (const char* f = lab_getenv("MI355VITS_WN_EPI")) epi = atoi(f);
+    if ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL) epi = 0;  // the rows of a tile (32 from its base) must fit the buffer range
+    if (a.math == MATH_F16X2) {  // two fp16 planes, on the 32x32x16 tiles
+        if (nt == 1) go(k_wn_layer_b3<32, false, 1, true>);
+        else go(k_wn_layer_b3<32, false, 3, true>);
+        return;
+    }
+    const bool w1 = a.math == MATH_BF16W;
+    if (a.shape != 32) {
+        // v_mfma_f32_16x16x32_bf16 (b3_chunk16: the weight fragments one 32-channel step ahead in every form — there is no ring to size,
+        // so the RA argument, left at 2 here, is not read by WnTiles<16>)
+        if (nt == 4) { if (w1) go(k_wn_layer_b3<16, true, 4, false, 2, 1>); else go(k_wn_layer_b3<16, false, 4, false, 2, 1>); }
+        else if (nt == 1) { if (w1) go(k_wn_layer_b3<16, true, 1>); else go(k_wn_layer_b3<16, false, 1>); }
+        else if (w1) go(k_wn_layer_b3<16, true, 3>);
+        else if (epi == 1) go(k_wn_layer_b3<16, false, 3, false, 2, 1>);
+        else go(k_wn_layer_b3<16, false, 3>);
+        return;
+    }
+#if defined(MI355_LAB) || defined(MI355_EMU)
+    // MI355VITS_WN_SHAPE=32: the 32x32x16 form this kernel had before the shape A/B (profiles/wn_shape_ab.txt), with its own packing
+    if (nt == 4) {
         // weight fragments three groups ahead as in the 96-column form, the B fragments single-buffered (b3_chunk_lean_ra: with both
         // double-buffered the loop spills 148 B at four column tiles)
-        if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 4, false, WNB_RING, 1>);
-        else go(k_wn_layer_b3<false, 4, false, WNB_RING, 1>);
+        if (w1) go(k_wn_layer_b3<32, true, 4, false, WNB_RING, 1>);
+        else go(k_wn_layer_b3<32, false, 4, false, WNB_RING, 1>);
     } else if (nt == 1) {
-        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 1, true>);
-        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 1>);
-        else go(k_wn_layer_b3<false, 1>);
+        if (w1) go(k_wn_layer_b3<32, true, 1>);
+        else go(k_wn_layer_b3<32, false, 1>);
     } else {
-        // default math, large grids: the weight fragments three groups ahead (WNB_RING), the epilogue's loads three tiles ahead (WNB_EPI;
-        // MI355VITS_WN_EPI=0: one tile ahead, the form past the buffer range)
-        int epi = WNB_EPI;
-        if (const char* f = lab_getenv("MI355VITS_WN_EPI")) epi = atoi(f);
-        if ((long)a.h_ld * 128 >= 0x7fffffffL || (long)a.s_ld * 128 >= 0x7fffffffL) epi = 0;  // a 32-row tile must fit the buffer range
-        if (a.math == MATH_F16X2) go(k_wn_layer_b3<false, 3, true>);
-        else if (a.math == MATH_BF16W) go(k_wn_layer_b3<true, 3>);
-        else if (epi == 1) go(k_wn_layer_b3<false, 3, false, WNB_RING, 1>);
-        else go(k_wn_layer_b3<false, 3, false, WNB_RING>);
+        // large grids: the weight fragments three groups ahead (WNB_RING)
+        if (w1) go(k_wn_layer_b3<32, true, 3>);
+        else if (epi == 1) go(k_wn_layer_b3<32, false, 3, false, WNB_RING, 1>);
+        else go(k_wn_layer_b3<32, false, 3, false, WNB_RING>);
     }
+#else
+    throw std::runtime_error("wn_layer_b3: the 32x32x16 form exists in the lab build only");
+#endif
 }
 
 bool wn_layer_fused_supported(int H, int K, int dil) {

@@ -835,8 +835,15 @@ int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t) {
                 pack_conv_weights_mfma_mode(w_rs.data(), Crs, H, 1, EPI_STD, pr.data());
                 dwi = upload(pi.data(), pi.size() * 4);
                 dwr = upload(pr.data(), pr.size() * 4);
+            } else if (wn_layer_b3_shape() != 32) {
+                // Engine::add_conv_data's packed_w16 of both convs (16x16x32 tiles)
+                std::vector<uint32_t> bi(w16_packed_words(2 * H, H, K)), br(w16_packed_words(Crs, H, 1));
+                pack_conv_weights_w16(w_in.data(), 2 * H, H, K, true, bi.data());
+                pack_conv_weights_w16(w_rs.data(), Crs, H, 1, false, br.data());
+                dwi = upload(bi.data(), bi.size() * 4);
+                dwr = upload(br.data(), br.size() * 4);
             } else {
-                // Engine::add_conv_data's packed_b3w: 32-row tile q of the gate conv = the tanh rows of channels 16 q .. 16 q + 15, then their
+                // MI355VITS_WN_SHAPE=32 (lab build, CPU model).  Engine::add_conv_data's packed_b3w: 32-row tile q of the gate conv = the tanh rows of channels 16 q .. 16 q + 15, then their
                 // sigmoid rows, as layout-1 planes; the res/skip conv in plain row order (packed_b3s)
                 const size_t row = (size_t)H * K;
                 std::vector<float> wg(w_in.size());
@@ -859,7 +866,7 @@ int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t) {
             if (t->cond) { w.cond = dc.as<float>(); w.cond_bs = 2L * H; }
             w.len = dl.as<int>();
             w.B = B; w.H = H; w.T = T; w.K = K; w.dil = dil; w.Crs = Crs; w.skip_init = t->skip_init != 0;
-            if (t->impl == 2) { w.math = MATH_BF16X3; launch_wn_layer_b3(w, nullptr); }
+            if (t->impl == 2) { w.math = MATH_BF16X3; w.shape = wn_layer_b3_shape(); launch_wn_layer_b3(w, nullptr); }
             else launch_wn_layer(w, nullptr);
         }
         HIP_CHECK(hipDeviceSynchronize());
@@ -1341,6 +1348,14 @@ int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const 
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_pack_w16(const float* w, int Cout, int Cin, int K, int gate, uint32_t* out) {
+    return guarded(nullptr, [&] {
+        if (!w || !out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (Cout < 1 || Cin < 1 || K < 1 || Cin % 32 != 0 || Cout % (gate ? 64 : 32) != 0) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        pack_conv_weights_w16(w, Cout, Cin, K, gate != 0, out);
     });
 }
 
