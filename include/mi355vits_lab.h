@@ -315,12 +315,86 @@ int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const
 /* Kernel unit-test hook: launch_expand_prior (k_expand_prior; the length regulator + the prior's sample) with injected noise.
  * stats [B, 2 I, Tx] = m_p | logs_p, cum [B, Tx] (non-decreasing, >= 0), ylen [B] (0 <= ylen[b] <= Ty), scales [B, 3] (noise_scale is
  * the one read), injected [B, I, injected_frames] with injected_frames >= Ty, or NULL where every row's noise_scale is 0 (anything
- * else would run the Philox generator, which has no reference here: MI355VITS_ERR_INVALID).
+ * else would run the Philox generator: that is mi355vits_test_expand_prior_keyed below, whose draws tests/small_ref.py restates from
+ * the published Philox4x32-10; here it is MI355VITS_ERR_INVALID).
  * z [B, I, Ty]: frame t of row b takes phoneme j = #{j : cum[b, j] <= t}: z = m_p[j] + injected * exp(logs_p[j]) * noise_scale (m_p[j]
  * alone, bit for bit, at noise_scale = 0).  Every element of z is written: exact zeros at t >= ylen[b] and where j = Tx; injected is
  * not read there, nor in a row whose noise_scale is 0. */
 int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
                                 const float* injected, int injected_frames, const float* scales, float* z);
+/* Kernel unit-test hook: launch_expand_prior (k_expand_prior) with the kernel's OWN noise (injected = NULL): as the hook above, with
+ * n = the Philox draw of csrc/kernels_misc.cpp (philox_normal) under key `seed`, utterance utt[b], tensor id 1, channel c, frame t:
+ *   Philox4x32-10 of counter (t, c, low32(utt), 1 ^ high32(utt) * 0x9E3779B9 mod 2^32) under key (low32(seed), high32(seed)) -> r;
+ *   u_i = ((float)(r_i >> 8) + 0.5f) * 2^-24 in float32 (from 2^23 on the sum rounds; the last value gives u = 1);
+ *   n = sqrtf(-2 logf(u_0)) * cosf(6.2831855f * u_1).
+ * scales [B, 3] (noise_scale is the one read), utt [B].  Every element of z [B, I, Ty] is written (its prior contents go to the device
+ * first): exact zeros at t >= ylen[b] and where no phoneme holds the frame; m_p[j] alone, bit for bit, in a row whose noise_scale is 0
+ * (no draw is made there). */
+int mi355vits_test_expand_prior_keyed(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
+                                      const float* scales, uint64_t seed, const uint64_t* utt, float* z);
+/* Kernel unit-test hook: launch_sdp_noise (k_sdp_noise) alone with the kernel's own noise (injected = NULL): z [B, 2, T],
+ * z[b, c, t] = n * noise_w[b] with n the draw above under tensor id 0, channel c, time t; scales [B, 3] (noise_w = scales[b, 2] is the one
+ * read), utt [B].  The kernel knows no length: every element of z is written (its prior contents go to the device first), a row whose
+ * noise_w is 0 as exact +0 (no draw is made there). */
+int mi355vits_test_sdp_noise(int device, int B, int T, uint64_t seed, const uint64_t* utt, const float* scales, float* z);
+/* Kernel unit-test hook: launch_embed (k_embed) alone, ONE launch: ids [B, T] int64, len [B] (0 <= len[b] <= T), emb [num_symbols, H]
+ * -> y [B, H, T] = emb[ids[b, t]][c] * scale (one float32 product) at t < len[b].  The caller's y goes to the device first; every element
+ * of it is written.  At len[b] <= t < T: exact zeros; ids ARE read there (an id outside 0 .. num_symbols - 1 reads row 0 — anywhere: the
+ * product's callers validate below the lengths, the kernel clamps as a second line) and the value is discarded by select. */
+int mi355vits_test_embed(int device, int B, int T, int H, int num_symbols, const int64_t* ids, const int32_t* len, const float* emb,
+                         float scale, float* y);
+/* Kernel unit-test hook: launch_layernorm (k_layernorm<cached> for C <= 256, k_layernorm<uncached> above) alone, ONE launch, the fields
+ * of LNArgs (csrc/kernels.h):
+ *   v = x  (nparts > 1: x[0] + x[1] + ... in slice order, slice p at x + p * part_stride floats, part_stride >= B C T);  v += bias[c];
+ *   v = 0 at t >= premask_len[b];  v += res;  y = (v - mean_c v) / sqrt(var_c v + eps) * gamma[c] + beta[c]  (two passes: the mean,
+ *   then the biased variance of the centred values);  gelu: y = erf-GELU(y);  y += add_to;  y = 0 at t >= out_len[b].
+ * alias: 0 = y is a buffer of its own (the caller's y goes to the device first); 1, 2, 3 = the kernel runs with y == x (slice 0),
+ * y == res, y == add_to on the device — the engine's three in-place uses — and the result is returned in y, whose prior contents are not
+ * used.  nparts > 1, bias or premask_len at C > 256 is the launcher's refusal: MI355VITS_ERR_INVALID before any launch.
+ * At and past the lengths (0 <= len <= T; NULL = T), per row: y is written at every t < T.  x (every slice), res and add_to are READ at
+ * every t < T; at t >= premask_len[b] x's slices and bias are discarded by select (any bits), at t >= out_len[b] the whole column is
+ * (x, res and add_to may hold any bits there: exact zeros come out).  A column's result depends on that column alone: on no other
+ * column, no other row, and not on T. */
+typedef struct mi355vits_layernorm_test {
+    int32_t B, C, T, nparts, gelu, alias;
+    float eps;
+    int64_t part_stride;         /* floats between the slices of x (nparts > 1) */
+    const float* x;              /* [B,C,T], or nparts slices of it */
+    const float* bias;           /* [C] or NULL */
+    const int32_t* premask_len;  /* [B] or NULL */
+    const float* res;            /* [B,C,T] or NULL */
+    const float* add_to;         /* [B,C,T] or NULL */
+    const float* gamma;          /* [C] */
+    const float* beta;           /* [C] */
+    const int32_t* out_len;      /* [B] or NULL */
+    float* y;                    /* [B,C,T] */
+} mi355vits_layernorm_test;
+int mi355vits_test_layernorm(int device, const mi355vits_layernorm_test* t);
+/* Kernel unit-test hook: launch_dp_det (k_dp_det<F32> in MI355VITS_MATH_F32, k_dp_det<split-bf16> in MATH_BF16X3) alone, ONE launch: the
+ * deterministic duration predictor (csrc/kernels_dp.cpp),
+ *   h1 = LN_1(relu(conv_1((x + cond[b]) * m)));  h2 = LN_2(relu(conv_2(h1 * m)));  logw = (proj_w . h2 + proj_b) * m,   m = [t < len[b]],
+ * "same" convs with K taps, LayerNorm over the F channels with eps 1e-5.  The hook packs w1 [F,H,K] and w2 [F,F,K] with the library's
+ * own pack functions, as Engine::duration_predictor_det does for the mode.  H, F multiples of 32 up to 256, K odd up to 7
+ * (dp_det_supported); anything else, or another math mode: MI355VITS_ERR_INVALID before any launch.
+ * At and past len[b] (0 <= len[b] <= T): x is not used there (MATH_F32 does not load it; the split-bf16 form clamps the load and
+ * discards by select): any bits.  logw (the caller's contents go to the device first) is written at every t < T: exact zeros at
+ * len[b] <= t < T.  Columns below len[b] depend on nothing at or past it, on no other row and not on where the tile seams fall. */
+typedef struct mi355vits_dp_det_test {
+    int32_t B, H, F, K, T, math;
+    const float* x;        /* [B,H,T] */
+    const float* cond;     /* [B,H] or NULL */
+    const int32_t* len;    /* [B] */
+    const float* w1; const float* b1; const float* g1; const float* be1;  /* conv_1 [F,H,K], its bias, norm_1's gamma / beta [F] */
+    const float* w2; const float* b2; const float* g2; const float* be2;  /* conv_2 [F,F,K], ... */
+    const float* proj_w;   /* [F] */
+    const float* proj_b;   /* [1] */
+    float* logw;           /* [B,T] */
+} mi355vits_dp_det_test;
+int mi355vits_test_dp_det(int device, const mi355vits_dp_det_test* t);
+/* How k_dp_det cuts a row: *cols = the output columns of a work item (the 64-column window less *halo), *halo = 2 (K / 2), the columns
+ * the two convs look to either side, *lds_bytes = dp_det_lds_bytes, the launch's dynamic LDS.  The library's own functions; host
+ * arithmetic only: no kernel runs.  MI355VITS_ERR_INVALID where the hook would refuse the shape or the math mode. */
+int mi355vits_lab_dp_det_plan(int H, int F, int K, int math, int32_t* cols, int32_t* halo, int32_t* lds_bytes);
 /* Kernel unit-test hook: launch_speaker_cond (k_speaker_cond, the plain run's conditioning) alone on host buffers: emb_g
  * [n_speakers, gin], sid [B] (checked against the table), w [Cout, gin], bias [Cout] or NULL -> out [B, Cout].  out holds out_floats >=
  * B * Cout floats: all of them go to the device first and come back, so a missing or a stray write shows. */

@@ -60,6 +60,8 @@ LAB_SYMBOLS = (
     "mi355vits_test_fit_durations", "mi355vits_test_speaker_cond", "mi355vits_test_speaker_cond_mix", "mi355vits_test_levels",
     "mi355vits_test_pitch_table", "mi355vits_test_pitch_plan", "mi355vits_test_pitch",
     "mi355vits_lab_conv_plan", "mi355vits_test_enc_o_ln", "mi355vits_test_conv_post",
+    "mi355vits_test_embed", "mi355vits_test_layernorm", "mi355vits_test_dp_det", "mi355vits_lab_dp_det_plan", "mi355vits_test_sdp_noise",
+    "mi355vits_test_expand_prior_keyed",
 )
 
 
@@ -95,6 +97,22 @@ class DdsStackTest(ctypes.Structure):
         ("z", ctypes.POINTER(ctypes.c_float)), ("out", ctypes.POINTER(ctypes.c_float)), ("x_out", ctypes.POINTER(ctypes.c_float))]
 
 
+class LayerNormTest(ctypes.Structure):
+    """struct mi355vits_layernorm_test of include/mi355vits_lab.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "C", "T", "nparts", "gelu", "alias")] + [("eps", ctypes.c_float), ("part_stride", ctypes.c_int64),
+        ("x", ctypes.POINTER(ctypes.c_float)), ("bias", ctypes.POINTER(ctypes.c_float)), ("premask_len", ctypes.POINTER(ctypes.c_int32)),
+        ("res", ctypes.POINTER(ctypes.c_float)), ("add_to", ctypes.POINTER(ctypes.c_float)), ("gamma", ctypes.POINTER(ctypes.c_float)),
+        ("beta", ctypes.POINTER(ctypes.c_float)), ("out_len", ctypes.POINTER(ctypes.c_int32)), ("y", ctypes.POINTER(ctypes.c_float))]
+
+
+class DpDetTest(ctypes.Structure):
+    """struct mi355vits_dp_det_test of include/mi355vits_lab.h"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "F", "K", "T", "math")] + [
+        ("x", ctypes.POINTER(ctypes.c_float)), ("cond", ctypes.POINTER(ctypes.c_float)), ("len", ctypes.POINTER(ctypes.c_int32))] + [
+        (n, ctypes.POINTER(ctypes.c_float)) for n in ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "proj_w", "proj_b", "logw")]
+
+
+LN_ALIAS = {None: 0, "x": 1, "res": 2, "add_to": 3}  # mi355vits_layernorm_test.alias
 MATH_F32, MATH_BF16X3, MATH_BF16W = 0, 1, 2  # csrc/kernels.h MathMode, MI355VITS_MATH_*
 
 
@@ -681,6 +699,13 @@ class NativeLibrary:
                                                ctypes.c_int32, ctypes.c_size_t, f32p, i32p]
             L.mi355vits_test_durations.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, f32p, i32p, i32p, f32p, f32p, i32p, i32p, i32p]
             L.mi355vits_test_expand_prior.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_int, f32p, f32p]
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            L.mi355vits_test_expand_prior_keyed.argtypes = [ctypes.c_int] * 5 + [f32p, i32p, i32p, f32p, ctypes.c_uint64, u64p, f32p]
+            L.mi355vits_test_sdp_noise.argtypes = [ctypes.c_int] * 3 + [ctypes.c_uint64, u64p, f32p, f32p]
+            L.mi355vits_test_embed.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int64), i32p, f32p, ctypes.c_float, f32p]
+            L.mi355vits_test_layernorm.argtypes = [ctypes.c_int, ctypes.POINTER(LayerNormTest)]
+            L.mi355vits_test_dp_det.argtypes = [ctypes.c_int, ctypes.POINTER(DpDetTest)]
+            L.mi355vits_lab_dp_det_plan.argtypes = [ctypes.c_int] * 4 + [i32p, i32p, i32p]
 
     def _need_hooks(self):
         if not self.has_hooks:
@@ -1334,6 +1359,129 @@ class NativeLibrary:
         if rc != 0:
             raise NativeError(rc, self.create_error())
         return z
+
+    def test_expand_prior_keyed(self, stats, cum, ylen, Ty, noise_scale, seed: int, utt, z_prior=None, device=0) -> np.ndarray:
+        """launch_expand_prior alone with the kernel's own Philox noise (tensor id 1) under ``seed`` and utt [B]: stats [B, 2 I, Tx],
+        cum [B, Tx], ylen [B], noise_scale a number or [B] -> z [B, I, Ty] (mi355vits_test_expand_prior_keyed)."""
+        self._need_hooks()
+        stats = np.ascontiguousarray(stats, np.float32)
+        B, I2, Tx = stats.shape
+        I = I2 // 2
+        cum, ylen = np.ascontiguousarray(cum, np.int32), np.ascontiguousarray(ylen, np.int32)
+        sc = np.zeros((B, 3), np.float32)
+        sc[:, 0] = np.asarray(noise_scale, np.float32)
+        u = np.ascontiguousarray(utt, np.uint64)
+        assert cum.shape == (B, Tx) and ylen.shape == (B,) and u.shape == (B,)
+        z = np.full((B, I, int(Ty)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
+        assert z.shape == (B, I, int(Ty))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        rc = self.lib.mi355vits_test_expand_prior_keyed(device, B, I, Tx, int(Ty), _fptr(stats), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p),
+                                                        _fptr(sc), int(seed), u.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _fptr(z))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return z
+
+    def test_sdp_noise(self, T: int, seed: int, utt, noise_w, z_prior=None, device=0) -> np.ndarray:
+        """launch_sdp_noise alone with the kernel's own Philox noise (tensor id 0): utt [B], noise_w a number or [B] -> z [B, 2, T]
+        (mi355vits_test_sdp_noise)."""
+        self._need_hooks()
+        u = np.ascontiguousarray(utt, np.uint64)
+        B = u.shape[0]
+        sc = np.zeros((B, 3), np.float32)
+        sc[:, 2] = np.asarray(noise_w, np.float32)
+        z = np.full((B, 2, int(T)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
+        assert u.shape == (B,) and z.shape == (B, 2, int(T))
+        rc = self.lib.mi355vits_test_sdp_noise(device, B, int(T), int(seed), u.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _fptr(sc), _fptr(z))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return z
+
+    def test_embed(self, ids, lengths, emb, scale: float, y_prior=None, device=0) -> np.ndarray:
+        """launch_embed alone: ids [B, T] int64, lengths [B], emb [num_symbols, H] -> y [B, H, T] (mi355vits_test_embed)."""
+        self._need_hooks()
+        ids = np.ascontiguousarray(ids, np.int64)
+        emb = np.ascontiguousarray(emb, np.float32)
+        ln = np.ascontiguousarray(lengths, np.int32)
+        B, T = ids.shape
+        S, H = emb.shape
+        y = np.full((B, H, T), -7.5e29, np.float32) if y_prior is None else np.ascontiguousarray(y_prior, np.float32).copy()
+        assert ln.shape == (B,) and y.shape == (B, H, T)
+        rc = self.lib.mi355vits_test_embed(device, B, T, H, S, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                           ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(emb), float(scale), _fptr(y))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return y
+
+    def test_layernorm(self, x, gamma, beta, eps=1e-5, bias=None, premask_len=None, res=None, add_to=None, gelu=False, out_len=None,
+                       alias=None, part_stride=None, y_prior=None, device=0) -> np.ndarray:
+        """launch_layernorm alone (mi355vits_test_layernorm): x [B, C, T], or [nparts, B, C, T] = the partial sums of a split conv (laid
+        out ``part_stride`` floats apart, default B C T); alias None / "x" / "res" / "add_to" = which input y is on the device."""
+        self._need_hooks()
+        f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+        x = f(x)
+        parts = x.shape[0] if x.ndim == 4 else 1
+        B, C, T = x.shape[-3:]
+        n = B * C * T
+        stride = n if part_stride is None else int(part_stride)
+        if parts > 1 and stride != n:
+            assert stride >= n
+            xs = np.full((parts - 1) * stride + n, -7.5e29, np.float32)
+            for p in range(parts):
+                xs[p * stride:p * stride + n] = x[p].ravel()
+            x = xs
+        gamma, beta, bias, res, add_to = f(gamma), f(beta), f(bias), f(res), f(add_to)
+        pl, ol = i32(premask_len), i32(out_len)
+        assert gamma.shape == (C,) and beta.shape == (C,) and (bias is None or bias.shape == (C,))
+        assert all(a is None or a.shape == (B, C, T) for a in (res, add_to)) and all(a is None or a.shape == (B,) for a in (pl, ol))
+        y = np.full((B, C, T), -7.5e29, np.float32) if y_prior is None else f(y_prior).copy()
+        assert y.shape == (B, C, T)
+        t = LayerNormTest()
+        t.B, t.C, t.T, t.nparts, t.gelu, t.alias, t.eps, t.part_stride = B, C, T, parts, int(bool(gelu)), LN_ALIAS[alias], float(eps), stride
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        t.x, t.bias, t.res, t.add_to, t.gamma, t.beta, t.y = _fptr(x), _fptr(bias), _fptr(res), _fptr(add_to), _fptr(gamma), _fptr(beta), _fptr(y)
+        t.premask_len = None if pl is None else pl.ctypes.data_as(i32p)
+        t.out_len = None if ol is None else ol.ctypes.data_as(i32p)
+        rc = self.lib.mi355vits_test_layernorm(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return y
+
+    def test_dp_det(self, x, lengths, w, cond=None, math=MATH_BF16X3, logw_prior=None, device=0) -> np.ndarray:
+        """launch_dp_det alone (mi355vits_test_dp_det): x [B, H, T], lengths [B], w = dict w1 [F, H, K], b1, g1, be1, w2 [F, F, K], b2, g2,
+        be2, proj_w [F], proj_b [1]; cond [B, H] or None -> logw [B, T]."""
+        self._need_hooks()
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        x = f(x)
+        B, H, T = x.shape
+        ln = np.ascontiguousarray(lengths, np.int32)
+        ww = {k: f(w[k]) for k in ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "proj_w", "proj_b")}
+        F, Hw, K = ww["w1"].shape
+        assert Hw == H and ww["w2"].shape == (F, F, K) and ww["proj_w"].size == F and ww["proj_b"].size == 1 and ln.shape == (B,)
+        assert all(ww[k].shape == (F,) for k in ("b1", "g1", "be1", "b2", "g2", "be2"))
+        c = None if cond is None else f(cond)
+        assert c is None or c.shape == (B, H)
+        logw = np.full((B, T), -7.5e29, np.float32) if logw_prior is None else f(logw_prior).copy()
+        assert logw.shape == (B, T)
+        t = DpDetTest()
+        t.B, t.H, t.F, t.K, t.T, t.math = B, H, F, K, T, int(math)
+        t.x, t.cond, t.len, t.logw = _fptr(x), _fptr(c), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(logw)
+        for k, v in ww.items():
+            setattr(t, k, _fptr(v))
+        rc = self.lib.mi355vits_test_dp_det(device, ctypes.byref(t))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return logw
+
+    def lab_dp_det_plan(self, H, F, K, math=MATH_BF16X3):
+        """(output columns of a k_dp_det work item, the two convs' reach 2 (K // 2), the launch's LDS bytes) from the library's own
+        functions (mi355vits_lab_dp_det_plan); NativeError where the hook would refuse the shape."""
+        self._need_hooks()
+        cols, halo, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self.lib.mi355vits_lab_dp_det_plan(int(H), int(F), int(K), int(math), ctypes.byref(cols), ctypes.byref(halo), ctypes.byref(lds))
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+        return cols.value, halo.value, lds.value
 
     def test_resample(self, x, lengths, in_hz: int, out_hz: int, device=0):
         """The product's resampler launch (k_resample) on caller-given f32 rows: x [B, row_stride], lengths [B] valid samples

@@ -596,6 +596,7 @@ struct DpDetArgs {
     int math = MATH_BF16X3;       // MATH_F32: v_mfma_f32_32x32x2_f32; any other mode: exact split-bf16 products
 };
 bool dp_det_supported(int H, int F, int K);  // H, F multiples of 32 up to 256; K odd up to 7
+int dp_det_tile_cols(int K);  // output columns of a work item: the 64-column window less the two convs' reach, 2 (K / 2)
 size_t dp_det_lds_bytes(int H, int F, int K, int math);
 void launch_dp_det(const DpDetArgs& a, hipStream_t s);
 

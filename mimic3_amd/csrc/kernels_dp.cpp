@@ -228,6 +228,8 @@ bool dp_det_supported(int H, int F, int K) {
     return H >= 32 && H % 32 == 0 && H <= DPD_MAX_C && F >= 32 && F % 32 == 0 && F <= DPD_MAX_C && K >= 1 && K % 2 == 1 && K <= 7;
 }
 
+int dp_det_tile_cols(int K) { return DPD_COLS - 2 * (K / 2); }
+
 size_t dp_det_lds_bytes(int H, int F, int K, int math) {
     const int LD = dpd_ld(K), C = H > F ? H : F;
     const size_t region = math == MATH_F32 ? (size_t)C * LD : (size_t)3 * 2 * (C / 16) * LD * 4;
@@ -237,7 +239,7 @@ size_t dp_det_lds_bytes(int H, int F, int K, int math) {
 void launch_dp_det(const DpDetArgs& a, hipStream_t s) {
     if (a.T <= 0 || a.B <= 0) return;
     if (!dp_det_supported(a.H, a.F, a.K)) throw std::runtime_error("dp_det: unsupported shape");
-    const int NO = DPD_COLS - 2 * (a.K / 2);
+    const int NO = dp_det_tile_cols(a.K);
     const dim3 grid((a.T + NO - 1) / NO, a.B), block(2 * a.F);  // F / 32 waves
     const size_t sh = dp_det_lds_bytes(a.H, a.F, a.K, a.math);
     auto go = [&](auto kfn) {

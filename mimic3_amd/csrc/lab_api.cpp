@@ -1351,6 +1351,172 @@ int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const 
     });
 }
 
+// ---- the text side's small kernels and the Philox noise (include/mi355vits_lab.h says what each reads and writes at and past the lengths)
+int mi355vits_test_expand_prior_keyed(int device, int B, int I, int Tx, int Ty, const float* stats, const int32_t* cum, const int32_t* ylen,
+                                      const float* scales, uint64_t seed, const uint64_t* utt, float* z) {
+    return guarded(nullptr, [&] {
+        if (!stats || !cum || !ylen || !scales || !utt || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || I < 1 || Tx < 1 || Ty < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        for (int b = 0; b < B; ++b) {
+            if (ylen[b] < 0 || ylen[b] > Ty) throw EngineError(MI355VITS_ERR_INVALID, "ylen out of range");
+            for (int j = 0; j < Tx; ++j)
+                if (cum[(size_t)b * Tx + j] < (j ? cum[(size_t)b * Tx + j - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
+        }
+        HIP_CHECK(hipSetDevice(device));
+        const size_t ns = (size_t)B * 2 * I * Tx, nc = (size_t)B * Tx, nz = (size_t)B * I * Ty;
+        DevBuf dst(ns * 4), dc(nc * 4), dy((size_t)B * 4), ds((size_t)B * 3 * 4), dz(nz * 4), du((size_t)B * 8);
+        HIP_CHECK(hipMemcpy(dst.p, stats, ns * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, cum, nc * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(du.p, utt, (size_t)B * 8, hipMemcpyHostToDevice));
+        launch_expand_prior(dst.as<float>(), dc.as<int>(), dy.as<int>(), nullptr, 0, B, I, Tx, Ty, ds.as<float>(), (unsigned long long)seed,
+                            du.as<unsigned long long>(), dz.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_sdp_noise(int device, int B, int T, uint64_t seed, const uint64_t* utt, const float* scales, float* z) {
+    return guarded(nullptr, [&] {
+        if (!utt || !scales || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nz = (size_t)B * 2 * T;
+        DevBuf dz(nz * 4), ds((size_t)B * 3 * 4), du((size_t)B * 8);
+        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(du.p, utt, (size_t)B * 8, hipMemcpyHostToDevice));
+        launch_sdp_noise(dz.as<float>(), nullptr, B, T, ds.as<float>(), (unsigned long long)seed, du.as<unsigned long long>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_embed(int device, int B, int T, int H, int num_symbols, const int64_t* ids, const int32_t* len, const float* emb,
+                         float scale, float* y) {
+    return guarded(nullptr, [&] {
+        if (!ids || !len || !emb || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        if (B < 1 || T < 1 || H < 1 || num_symbols < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        check_lens(len, B, T, "len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t ni = (size_t)B * T, ne = (size_t)num_symbols * H, ny = (size_t)B * H * T;
+        DevBuf di(ni * 8), dl((size_t)B * 4), de(ne * 4), dy(ny * 4);
+        HIP_CHECK(hipMemcpy(di.p, ids, ni * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(de.p, emb, ne * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));
+        launch_embed(di.as<long long>(), dl.as<int>(), de.as<float>(), B, T, H, num_symbols, scale, dy.as<float>(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_test_layernorm(int device, const mi355vits_layernorm_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->x || !t->gamma || !t->beta || !t->y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, C = t->C, T = t->T, NP = t->nparts;
+        if (B < 1 || C < 1 || T < 1 || NP < 1 || NP > 8) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        const size_t n = (size_t)B * C * T;
+        if (n >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+        const size_t stride = NP > 1 ? (size_t)t->part_stride : n;
+        if (NP > 1 && t->part_stride < (int64_t)n) throw EngineError(MI355VITS_ERR_INVALID, "part_stride must cover a slice");
+        if (t->alias < 0 || t->alias > 3 || (t->alias == 2 && !t->res) || (t->alias == 3 && !t->add_to))
+            throw EngineError(MI355VITS_ERR_INVALID, "alias: 0 none, 1 y == x, 2 y == res, 3 y == add_to (the aliased input must be given)");
+        check_lens(t->premask_len, B, T, "premask_len out of range");
+        check_lens(t->out_len, B, T, "out_len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        const size_t nx = (size_t)(NP - 1) * stride + n;
+        DevBuf dx(nx * 4), dy(n * 4), dres(n * 4), dadd(n * 4), db((size_t)C * 4), dg((size_t)C * 4), dbe((size_t)C * 4), dpl((size_t)B * 4), dol((size_t)B * 4);
+        HIP_CHECK(hipMemcpy(dx.p, t->x, nx * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, t->y, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dg.p, t->gamma, (size_t)C * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dbe.p, t->beta, (size_t)C * 4, hipMemcpyHostToDevice));
+        LNArgs a;
+        a.x = dx.as<float>(); a.gamma = dg.as<float>(); a.beta = dbe.as<float>();
+        a.B = B; a.C = C; a.T = T; a.gelu = t->gelu ? 1 : 0; a.eps = t->eps;
+        a.nparts = NP; a.part_stride = (long)stride;
+        if (t->res) { HIP_CHECK(hipMemcpy(dres.p, t->res, n * 4, hipMemcpyHostToDevice)); a.res = dres.as<float>(); }
+        if (t->add_to) { HIP_CHECK(hipMemcpy(dadd.p, t->add_to, n * 4, hipMemcpyHostToDevice)); a.add_to = dadd.as<float>(); }
+        if (t->bias) { HIP_CHECK(hipMemcpy(db.p, t->bias, (size_t)C * 4, hipMemcpyHostToDevice)); a.bias = db.as<float>(); }
+        if (t->premask_len) { HIP_CHECK(hipMemcpy(dpl.p, t->premask_len, (size_t)B * 4, hipMemcpyHostToDevice)); a.premask_len = dpl.as<int>(); }
+        if (t->out_len) { HIP_CHECK(hipMemcpy(dol.p, t->out_len, (size_t)B * 4, hipMemcpyHostToDevice)); a.out_len = dol.as<int>(); }
+        a.y = t->alias == 1 ? dx.as<float>() : t->alias == 2 ? dres.as<float>() : t->alias == 3 ? dadd.as<float>() : dy.as<float>();
+        try {
+            launch_layernorm(a, nullptr);
+        } catch (const EngineError&) {
+            throw;
+        } catch (const std::runtime_error& e) {  // the launcher's own refusal (thrown before any launch); a HIP error stays a device error
+            if (std::string(e.what()).rfind("layernorm:", 0) == 0) throw EngineError(MI355VITS_ERR_INVALID, e.what());
+            throw;
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(t->y, a.y, n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+int mi355vits_lab_dp_det_plan(int H, int F, int K, int math, int32_t* cols, int32_t* halo, int32_t* lds_bytes) {
+    return guarded(nullptr, [&] {
+        if (!dp_det_supported(H, F, K)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by k_dp_det");
+        if (math != MATH_F32 && math != MATH_BF16X3) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 or MATH_BF16X3");
+        if (cols) *cols = dp_det_tile_cols(K);
+        if (halo) *halo = 2 * (K / 2);
+        if (lds_bytes) *lds_bytes = (int32_t)dp_det_lds_bytes(H, F, K, math);
+    });
+}
+
+int mi355vits_test_dp_det(int device, const mi355vits_dp_det_test* t) {
+    return guarded(nullptr, [&] {
+        if (!t || !t->x || !t->len || !t->w1 || !t->b1 || !t->g1 || !t->be1 || !t->w2 || !t->b2 || !t->g2 || !t->be2 || !t->proj_w || !t->proj_b || !t->logw)
+            throw EngineError(MI355VITS_ERR_INVALID, "null argument");
+        const int B = t->B, H = t->H, F = t->F, K = t->K, T = t->T;
+        if (B < 1 || T < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
+        if (!dp_det_supported(H, F, K)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by k_dp_det");
+        if (t->math != MATH_F32 && t->math != MATH_BF16X3) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 or MATH_BF16X3");
+        if ((size_t)B * H * T >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
+        check_lens(t->len, B, T, "len out of range");
+        HIP_CHECK(hipSetDevice(device));
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        auto upload = [&](const void* p, size_t bytes) -> const float* {
+            keep.emplace_back(new DevBuf(bytes));
+            HIP_CHECK(hipMemcpy(keep.back()->p, p, bytes, hipMemcpyHostToDevice));
+            return keep.back()->as<float>();
+        };
+        // a conv's weights [Cout, Cin, K] as Engine::add_conv_data stages them for the mode (ConvW::packed / packed_b3s)
+        auto conv_w = [&](const float* w, int Cout, int Cin) -> const float* {
+            if (t->math == MATH_F32) {
+                std::vector<float> p(mfma_packed_floats(Cout, Cin, K), 0.0f);
+                pack_conv_weights_mfma_mode(w, Cout, Cin, K, EPI_STD, p.data());
+                return upload(p.data(), p.size() * 4);
+            }
+            std::vector<uint32_t> p(bf16x3_packed_words_mode(Cout, Cin, K, EPI_STD), 0u);
+            pack_conv_weights_bf16x3_mode(w, Cout, Cin, K, EPI_STD, 1, p.data());
+            return upload(p.data(), p.size() * 4);
+        };
+        DpDetArgs a;
+        a.x = upload(t->x, (size_t)B * H * T * 4);
+        if (t->cond) { a.cond = upload(t->cond, (size_t)B * H * 4); a.cond_bs = H; }
+        a.w1 = conv_w(t->w1, F, H); a.b1 = upload(t->b1, (size_t)F * 4); a.g1 = upload(t->g1, (size_t)F * 4); a.be1 = upload(t->be1, (size_t)F * 4);
+        a.w2 = conv_w(t->w2, F, F); a.b2 = upload(t->b2, (size_t)F * 4); a.g2 = upload(t->g2, (size_t)F * 4); a.be2 = upload(t->be2, (size_t)F * 4);
+        a.pw = upload(t->proj_w, (size_t)F * 4);
+        a.pb = upload(t->proj_b, 4);
+        a.len = reinterpret_cast<const int*>(upload(t->len, (size_t)B * 4));
+        DevBuf dout((size_t)B * T * 4);
+        HIP_CHECK(hipMemcpy(dout.p, t->logw, (size_t)B * T * 4, hipMemcpyHostToDevice));
+        a.out = dout.as<float>(); a.out_bs = T;
+        a.B = B; a.T = T; a.H = H; a.F = F; a.K = K; a.math = t->math;
+        launch_dp_det(a, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(t->logw, dout.p, (size_t)B * T * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 int mi355vits_lab_pack_w16(const float* w, int Cout, int Cin, int K, int gate, uint32_t* out) {
     return guarded(nullptr, [&] {
         if (!w || !out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
