@@ -533,6 +533,11 @@ def _fptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
 
+def _ptr(a: Optional[np.ndarray]):
+    """The ctypes pointer of an array's own element type (None stays None: an absent optional argument)."""
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
 class NativeLibrary:
     """One loaded copy of the C ABI."""
 
@@ -712,6 +717,13 @@ class NativeLibrary:
             raise RuntimeError(f"{self.path} is the product library: the hooks of include/mi355vits_lab.h live in "
                                "libmi355vits_hooks.so (mimic3_amd._native.hooks_library()), the lab build and the CPU model")
 
+    def _hook(self, name: str, *args) -> None:
+        """One call of a hook of include/mi355vits_lab.h: ``mi355vits_<name>(*args)``; a non-zero code raises with the library's message."""
+        self._need_hooks()
+        rc = getattr(self.lib, "mi355vits_" + name)(*args)
+        if rc != 0:
+            raise NativeError(rc, self.create_error())
+
     def version(self) -> str:
         return self.lib.mi355vits_version().decode()
 
@@ -724,19 +736,14 @@ class NativeLibrary:
     # ---- kernel unit-test hooks -------------------------------------------------------------
     def lab_g711_encode(self, law, samples) -> np.ndarray:
         """The device's G.711 encoders (the ones of the encoded packed streams) over int16 ``samples``; law "ulaw" / "alaw"."""
-        self._need_hooks()
         x = np.ascontiguousarray(samples, np.int16).reshape(-1)
         out = np.empty(x.shape[0], np.uint8)
-        rc = self.lib.mi355vits_lab_g711_encode(encoding_id(law), x.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), x.shape[0],
-                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_g711_encode", encoding_id(law), _ptr(x), x.shape[0], _ptr(out))
         return out
 
     def lab_flac(self, samples, rate: int, first_frame: int = 0):
         """The FLAC kernels alone over int16 ``samples`` (a contiguous 1-d int16 array is read where it is: its address modulo 16 is
         the samples' on the device) -> (the complete file as bytes, frame sizes int32 [ceil(n / 4096)])."""
-        self._need_hooks()
         x = np.asarray(samples)
         if x.dtype != np.int16 or x.ndim != 1 or not x.flags.c_contiguous:
             x = np.ascontiguousarray(samples, np.int16).reshape(-1)
@@ -745,18 +752,14 @@ class NativeLibrary:
         out = np.empty(42 + 16 * frames + 2 * n, np.uint8)
         sizes = np.zeros(max(frames, 1), np.int32)
         got = ctypes.c_size_t(0)
-        rc = self.lib.mi355vits_lab_flac(ctypes.c_void_p(x.ctypes.data), n, int(rate), int(first_frame),
-                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), out.shape[0], ctypes.byref(got),
-                                         sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_flac", ctypes.c_void_p(x.ctypes.data), n, int(rate), int(first_frame), _ptr(out), out.shape[0], ctypes.byref(got),
+                   _ptr(sizes))
         return out[: int(got.value)].tobytes(), sizes[:frames].copy()
 
     def lab_flac_jobs(self, arrays, rate: int):
         """SEVERAL int16 arrays as FLAC files in ONE block by the kernels of the streams calls alone (``mi355vits_lab_flac_jobs``):
         -> (the block uint8, offsets int64 [J] — multiples of 16 —, sizes int64 [J]); file j = block[offsets[j] : offsets[j] + sizes[j]].
         A contiguous 1-d int16 array is read where it is, as ``lab_flac`` reads it."""
-        self._need_hooks()
         xs = []
         for a in arrays:
             x = np.asarray(a)
@@ -770,77 +773,54 @@ class NativeLibrary:
         out = np.empty(cap, np.uint8)
         offsets, sizes = np.zeros(max(J, 1), np.int64), np.zeros(max(J, 1), np.int64)
         got = ctypes.c_size_t(0)
-        rc = self.lib.mi355vits_lab_flac_jobs(ptrs, ns, J, int(rate), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap, ctypes.byref(got),
-                                              offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                              sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_flac_jobs", ptrs, ns, J, int(rate), _ptr(out), cap, ctypes.byref(got), _ptr(offsets), _ptr(sizes))
         return out[: int(got.value)].copy(), offsets[:J].copy(), sizes[:J].copy()
 
     def lab_edges(self, audio, lengths, peaks, ratio):
         """The edge kernel (k_edges) alone: audio [B, stride] f32 with lengths [B] valid samples each (what lies behind them is never
         looked at), peaks [B] f32, 0 < ratio <= 1 -> (s_first, s_last) int32 [B]: the first / last sample with
         ``abs(y) >= peaks[b] * ratio`` in f32 (lengths[b] / -1 when there is none)."""
-        self._need_hooks()
         au = np.ascontiguousarray(audio, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         pk = np.ascontiguousarray(peaks, np.float32).reshape(-1)
         if au.ndim != 2 or ln.shape[0] != au.shape[0] or pk.shape[0] != au.shape[0]:
             raise ValueError("audio [B, stride], lengths [B], peaks [B]")
         B = au.shape[0]
-        i32p = ctypes.POINTER(ctypes.c_int32)
         first, last = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        rc = self.lib.mi355vits_lab_edges(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), _fptr(pk), B, float(ratio),
-                                          first.ctypes.data_as(i32p), last.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_edges", _ptr(au), au.shape[1], _ptr(ln), _ptr(pk), B, float(ratio), _ptr(first), _ptr(last))
         return first, last
 
     def lab_loudness(self, audio, lengths, rate):
         """The loudness kernels (k_loud, k_loud_gate) alone: audio [B, stride] f32 with lengths [B] valid samples each at ``rate`` Hz
         (what lies behind them is never looked at) -> (lufs float64 [B], blocks int32 [B], gated int32 [B]) as
         ``mi355vits_fetch_loudness`` defines them."""
-        self._need_hooks()
         au = np.ascontiguousarray(audio, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         if au.ndim != 2 or ln.shape[0] != au.shape[0]:
             raise ValueError("audio [B, stride], lengths [B]")
         B = au.shape[0]
-        i32p = ctypes.POINTER(ctypes.c_int32)
         lufs, blocks, gated = np.zeros(B, np.float64), np.zeros(B, np.int32), np.zeros(B, np.int32)
-        rc = self.lib.mi355vits_lab_loudness(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, int(rate),
-                                             lufs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), blocks.ctypes.data_as(i32p),
-                                             gated.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_loudness", _ptr(au), au.shape[1], _ptr(ln), B, int(rate), _ptr(lufs), _ptr(blocks), _ptr(gated))
         return lufs, blocks, gated
 
     def lab_true_peak(self, audio, lengths, offset=0, envelope=True):
         """The true-peak kernels (k_true_peak, k_true_peak_env) alone: audio [B, stride] f32 with lengths [B] valid samples each (what
         lies behind them is never looked at), on the device ``offset`` (0 .. 3) floats behind a 16-byte boundary -> (tp float64 [B],
         e float64 [B, stride] — the rule's ``e[t]`` at a row's valid samples, 0 behind them; ``None`` with ``envelope=False``)."""
-        self._need_hooks()
         au = np.ascontiguousarray(audio, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         if au.ndim != 2 or ln.shape[0] != au.shape[0]:
             raise ValueError("audio [B, stride], lengths [B]")
         B = au.shape[0]
-        f64p = ctypes.POINTER(ctypes.c_double)
         tp = np.zeros(B, np.float64)
         env = np.zeros(au.shape, np.float64) if envelope else None
-        rc = self.lib.mi355vits_lab_true_peak(_fptr(au), au.shape[1], ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), B, int(offset),
-                                              tp.ctypes.data_as(f64p), env.ctypes.data_as(f64p) if envelope else None)
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_true_peak", _ptr(au), au.shape[1], _ptr(ln), B, int(offset), _ptr(tp), _ptr(env))
         return tp, env
 
     def lab_true_peak_plan(self):
         """``(taps float64 [81], tile)``: the library's tap table ``h`` and the samples of a k_true_peak work item.  No kernel runs."""
-        self._need_hooks()
         taps, tile = np.zeros(81, np.float64), ctypes.c_int32()
-        rc = self.lib.mi355vits_lab_true_peak_plan(taps.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(tile))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_true_peak_plan", _ptr(taps), ctypes.byref(tile))
         return taps, int(tile.value)
 
     def lab_limit(self, audio, lengths, g, c, U, window, envelope=None):
@@ -849,40 +829,30 @@ class NativeLibrary:
         in samples -> (scale float32 [B, stride] — the rule's ``scale[k]`` at a row's valid samples, 0 behind them —, sq_min int64 [B],
         reduced int32 [B]) as ``include/mi355vits.h`` defines them.  Every row is a job, over the ceiling or not.  ``envelope``
         [B, stride] float64: the true-peak form — ``envelope[b, t]`` in place of ``abs(audio[b, t])``."""
-        self._need_hooks()
         au = np.ascontiguousarray(audio, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         gg = np.ascontiguousarray(g, np.float64).reshape(-1)
         if au.ndim != 2 or ln.shape[0] != au.shape[0] or gg.shape[0] != au.shape[0]:
             raise ValueError("audio [B, stride], lengths [B], g [B]")
         B = au.shape[0]
-        i32p = ctypes.POINTER(ctypes.c_int32)
         scale = np.zeros(au.shape, np.float32)
         sq_min, reduced = np.zeros(B, np.int64), np.zeros(B, np.int32)
-        f64p = ctypes.POINTER(ctypes.c_double)
         if envelope is not None:
             ev = np.ascontiguousarray(envelope, np.float64)
             if ev.shape != au.shape:
                 raise ValueError("envelope has the audio's shape")
-            rc = self.lib.mi355vits_lab_limit_env(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(f64p), float(c), float(U),
-                                                  int(window), ev.ctypes.data_as(f64p), _fptr(scale),
-                                                  sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), reduced.ctypes.data_as(i32p))
+            self._hook("lab_limit_env", _ptr(au), au.shape[1], _ptr(ln), B, _ptr(gg), float(c), float(U), int(window), _ptr(ev), _ptr(scale),
+                       _ptr(sq_min), _ptr(reduced))
         else:
-            rc = self.lib.mi355vits_lab_limit(_fptr(au), au.shape[1], ln.ctypes.data_as(i32p), B, gg.ctypes.data_as(f64p),
-                                              float(c), float(U), int(window), _fptr(scale), sq_min.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                              reduced.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+            self._hook("lab_limit", _ptr(au), au.shape[1], _ptr(ln), B, _ptr(gg), float(c), float(U), int(window), _ptr(scale), _ptr(sq_min),
+                       _ptr(reduced))
         return scale, sq_min, reduced
 
     def lab_loudness_plan(self, rate):
         """How k_loud cuts a row at ``rate`` Hz: ``(S, W, K)`` — the 100 ms step, the warm-up samples of a work item that starts
         inside a row, and the steps of a work item (an item is ``K * S`` samples of one row).  Host arithmetic only."""
-        self._need_hooks()
         s, w, k = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        rc = self.lib.mi355vits_lab_loudness_plan(int(rate), ctypes.byref(s), ctypes.byref(w), ctypes.byref(k))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_loudness_plan", int(rate), ctypes.byref(s), ctypes.byref(w), ctypes.byref(k))
         return int(s.value), int(w.value), int(k.value)
 
     def test_conv1d(self, x, w, bias=None, res=None, dilation=1, impl=1, in_len=None, out_len=None, in_slope=1.0,
@@ -891,7 +861,6 @@ class NativeLibrary:
         """One Conv1d through one kernel family (include/mi355vits_lab.h: mi355vits_test_conv1d).  math: MATH_F32 for impl 0 / 1,
         MATH_BF16X3 (the default) or MATH_BF16W for impl 2 / 3, MATH_BF16X3 for impl 4.  cond [B, Cout].  y_prior = what the output
         buffer holds before the launch (zeros) when not accumulating; accumulate_into = the same buffer AND y += ."""
-        self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         B, Cin, T = x.shape
@@ -903,32 +872,29 @@ class NativeLibrary:
         keep = [x, w, y]
         t = ConvTest()
         t.impl, t.B, t.Cin, t.Cout, t.T, t.K, t.dilation = impl, B, Cin, Cout, T, K, dilation
-        t.x, t.w, t.y = _fptr(x), _fptr(w), _fptr(y)
+        t.x, t.w, t.y = _ptr(x), _ptr(w), _ptr(y)
         for name, arr, shape in (("bias", bias, (Cout,)), ("res", res, (B, Cout, T)), ("cond", cond, (B, Cout))):
             if arr is not None:
                 a = np.ascontiguousarray(arr, np.float32)
                 assert a.shape == shape, (name, a.shape, shape)
                 keep.append(a)
-                setattr(t, name, _fptr(a))
+                setattr(t, name, _ptr(a))
         for name, arr in (("in_len", in_len), ("out_len", out_len)):
             if arr is not None:
                 a = np.ascontiguousarray(arr, np.int32)
                 assert a.shape == (B,)
                 keep.append(a)
-                setattr(t, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+                setattr(t, name, _ptr(a))
         t.in_slope, t.relu, t.out_scale, t.res_sub = in_slope, int(relu), out_scale, int(res_sub)
         t.accumulate = int(accumulate_into is not None)
         t.math = (MATH_F32 if impl in (0, 1) else MATH_BF16X3) if math is None else int(math)
         t.mask_before_res, t.fixed_rule = int(bool(mask_before_res)), int(bool(fixed_rule))
-        rc = self.lib.mi355vits_test_conv1d(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_conv1d", device, ctypes.byref(t))
         return y
 
     def test_conv_transpose1d(self, x, w, bias, stride, in_slope=1.0, device=0, impl=0, in_len=None, y_prior=None) -> np.ndarray:
         """in_len [B]: per-row input lengths (impl 3 only; None = every row at full length); output positions at or past
         in_len[b] x stride are left undefined.  y_prior = what the output buffer holds before the launch (zeros)."""
-        self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         B, Cin, Tin = x.shape
@@ -937,33 +903,24 @@ class NativeLibrary:
         ln = None if in_len is None else np.ascontiguousarray(in_len, np.int32)
         y = np.zeros((B, Cout, Tin * stride), np.float32) if y_prior is None else np.ascontiguousarray(y_prior, np.float32).copy()
         assert y.shape == (B, Cout, Tin * stride)
-        rc = self.lib.mi355vits_test_conv_transpose1d(device, impl, B, Cin, Cout, Tin, K, stride, _fptr(x), _fptr(w),
-                                                      _fptr(b), in_slope,
-                                                      None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(y))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_conv_transpose1d", device, impl, B, Cin, Cout, Tin, K, stride, _ptr(x), _ptr(w), _ptr(b), in_slope, _ptr(ln), _ptr(y))
         return y
 
     def lab_conv_plan(self, impl, B, Cin, Cout, T, K, dilation=1, stride=0, math=None, fixed_rule=False, has_res=False, has_cond=False,
                       lengths=None) -> "ConvPlan":
         """What the conv launchers would run for a hook call of this shape on the current device (include/mi355vits_lab.h:
         mi355vits_lab_conv_plan): stride = 0: test_conv1d(impl); stride > 0: test_conv_transpose1d(impl) with Tin = T.  No kernel runs."""
-        self._need_hooks()
         p = ConvPlan()
         ln = None if lengths is None else np.ascontiguousarray(lengths, np.int32)
         m = (MATH_F32 if impl in (0, 1) else MATH_BF16X3) if math is None else int(math)
-        rc = self.lib.mi355vits_lab_conv_plan(int(impl), int(B), int(Cin), int(Cout), int(T), int(K), int(dilation), int(stride), m,
-                                              int(bool(fixed_rule)), int(bool(has_res)), int(bool(has_cond)),
-                                              None if ln is None else ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_conv_plan", int(impl), int(B), int(Cin), int(Cout), int(T), int(K), int(dilation), int(stride), m, int(bool(fixed_rule)),
+                   int(bool(has_res)), int(bool(has_cond)), _ptr(ln), ctypes.byref(p))
         return p
 
     def test_enc_o_ln(self, x, w, bias, res, gamma, beta, in_len=None, ln_out_len=None, eps=1e-5, math=MATH_BF16X3, in_place=False,
                       y_prior=None, device=0) -> np.ndarray:
         """launch_enc_o_ln alone (include/mi355vits_lab.h: mi355vits_test_enc_o_ln): y = LN_c(res + conv1x1(x * mask_in) + bias) *
         mask_ln on [B, 192, T]; in_place: the kernel runs with y == res."""
-        self._need_hooks()
         f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
         x, w, bias, res, gamma, beta = f(x), f(w), f(bias), f(res), f(gamma), f(beta)
         B, C, T = x.shape
@@ -971,17 +928,13 @@ class NativeLibrary:
         y = np.zeros_like(x) if y_prior is None else f(y_prior).copy()
         i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
         il, ol = i32(in_len), i32(ln_out_len)
-        ip = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        rc = self.lib.mi355vits_test_enc_o_ln(device, int(math), B, T, _fptr(x), _fptr(w), _fptr(bias), _fptr(res), _fptr(gamma), _fptr(beta),
-                                              float(eps), ip(il), ip(ol), int(bool(in_place)), _fptr(y))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_enc_o_ln", device, int(math), B, T, _ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(gamma), _ptr(beta), float(eps), _ptr(il),
+                   _ptr(ol), int(bool(in_place)), _ptr(y))
         return y
 
     def test_conv_post(self, x, w, valid_len, volumes=None, audio_prior=None, pcm_prior=None, device=0):
         """The decoder's tail, launch_conv_post_tanh then launch_pcm16 (include/mi355vits_lab.h: mi355vits_test_conv_post): x [B, Cin, L],
         w [1, Cin, K] -> (audio [B, L] float32, peaks [B] float32, pcm [B, L] int16, the kernel that ran: 0 dpp, 1 vec, 2 staged)."""
-        self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         w = np.ascontiguousarray(w, np.float32)
         B, Cin, L = x.shape
@@ -994,11 +947,8 @@ class NativeLibrary:
         pcm = np.zeros((B, L), np.int16) if pcm_prior is None else np.ascontiguousarray(pcm_prior, np.int16).copy()
         peaks = np.full(B, -1.0, np.float32)
         kernel = ctypes.c_int32(-1)
-        rc = self.lib.mi355vits_test_conv_post(device, B, Cin, K, L, _fptr(x), _fptr(w), vl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                               None if vol is None else vol.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _fptr(audio),
-                                               _fptr(peaks), pcm.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(kernel))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_conv_post", device, B, Cin, K, L, _ptr(x), _ptr(w), _ptr(vl), _ptr(vol), _ptr(audio), _ptr(peaks), _ptr(pcm),
+                   ctypes.byref(kernel))
         return audio, peaks, pcm, int(kernel.value)
 
     def emu_set_cu_count(self, n: int) -> None:
@@ -1011,7 +961,6 @@ class NativeLibrary:
     def test_rel_attention(self, qkv, emb_rel_k, emb_rel_v, lengths, n_heads, impl=2, device=0) -> np.ndarray:
         """Relative-position attention through one kernel: impl 0 = VALU, 1 = f32-MFMA (T <= 512), 2 = streamed.
         qkv [B, 3H, T], emb_rel_* [2W+1, H/n_heads], lengths [B] -> [B, H, T]."""
-        self._need_hooks()
         qkv = np.ascontiguousarray(qkv, np.float32)
         ek = np.ascontiguousarray(emb_rel_k, np.float32)
         ev = np.ascontiguousarray(emb_rel_v, np.float32)
@@ -1020,10 +969,7 @@ class NativeLibrary:
         H = H3 // 3
         W = (ek.shape[0] - 1) // 2
         out = np.zeros((B, H, T), np.float32)
-        rc = self.lib.mi355vits_test_rel_attention(device, impl, B, T, H, n_heads, W, _fptr(qkv), _fptr(ek), _fptr(ev),
-                                                   ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(out))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_rel_attention", device, impl, B, T, H, n_heads, W, _ptr(qkv), _ptr(ek), _ptr(ev), _ptr(ln), _ptr(out))
         return out
 
     def test_wn_layer(self, h, skip, w_in, b_in, w_rs, b_rs, lengths, dilation=1, cond=None, skip_init=False, impl=1, math=None,
@@ -1032,7 +978,6 @@ class NativeLibrary:
         two-launch path, 1 = launch_wn_layer (MATH_F32), 2 = launch_wn_layer_b3 (MATH_BF16X3).  h, skip [B, H, T], w_in [2H, H, K],
         w_rs [Crs, H, 1], cond [B, 2H] or None, lengths [B]; h_out_prior = what the output buffer of h' holds before the launch
         (zeros).  Returns (h', skip'); with Crs = H, h' is h_out_prior unchanged."""
-        self._need_hooks()
         f = lambda a: np.ascontiguousarray(a, np.float32)
         h, w_in, b_in, w_rs, b_rs = f(h), f(w_in), f(b_in), f(w_rs), f(b_rs)
         skip = f(skip).copy()
@@ -1046,40 +991,31 @@ class NativeLibrary:
         t = WnTest()
         t.impl, t.B, t.H, t.T, t.K, t.dilation, t.Crs, t.skip_init = impl, B, H, T, w_in.shape[2], int(dilation), w_rs.shape[0], int(bool(skip_init))
         t.math = (MATH_BF16X3 if impl == 2 else MATH_F32) if math is None else int(math)
-        t.h_in, t.w_in, t.b_in, t.w_rs, t.b_rs, t.cond = _fptr(h), _fptr(w_in), _fptr(b_in), _fptr(w_rs), _fptr(b_rs), _fptr(c)
-        t.len, t.h_out, t.skip = ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(h_out), _fptr(skip)
-        rc = self.lib.mi355vits_test_wn_layer(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        t.h_in, t.w_in, t.b_in, t.w_rs, t.b_rs, t.cond = _ptr(h), _ptr(w_in), _ptr(b_in), _ptr(w_rs), _ptr(b_rs), _ptr(c)
+        t.len, t.h_out, t.skip = _ptr(ln), _ptr(h_out), _ptr(skip)
+        self._hook("test_wn_layer", device, ctypes.byref(t))
         return h_out, skip
 
     def lab_wn_plan(self, B, T, K=5, dilation=1):
         """What the WaveNet launchers pick for a [B, 192, T] layer on the current device: (the columns of a k_wn_layer_b3 tile — 32, 96
         or 128 —, launch_wn_layer's geometry 0 / 1 / 2).  No kernel runs."""
-        self._need_hooks()
         tile, geom = ctypes.c_int32(), ctypes.c_int32()
-        rc = self.lib.mi355vits_lab_wn_plan(int(B), int(T), int(K), int(dilation), ctypes.byref(tile), ctypes.byref(geom))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_wn_plan", int(B), int(T), int(K), int(dilation), ctypes.byref(tile), ctypes.byref(geom))
         return int(tile.value), int(geom.value)
 
     def lab_pack_w16(self, w, gate=False):
         """k_wn_layer_b3's weight fragments of w [Cout, Cin, K] (include/mi355vits_lab.h: mi355vits_lab_pack_w16) as uint16 bf16 bit
         patterns [Cout / 16, K, Cin / 32, 3 planes, 64 lanes, 8 k-slots]."""
-        self._need_hooks()
         w = np.ascontiguousarray(w, np.float32)
         Cout, Cin, K = w.shape
         out = np.zeros((Cout // 16, K, Cin // 32, 3, 64, 4), np.uint32)
-        rc = self.lib.mi355vits_lab_pack_w16(_fptr(w), Cout, Cin, K, int(bool(gate)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_pack_w16", _ptr(w), Cout, Cin, K, int(bool(gate)), _ptr(out))
         return out.view(np.uint16).reshape(Cout // 16, K, Cin // 32, 3, 64, 8)
 
     def test_mrf_stage(self, x, ks, d1, d2, weights, biases, lengths, impl=0, math=None, out_scale=0.0, seg=0, y_prior=None, device=0):
         """One multi-receptive-field stage through one kernel (include/mi355vits_lab.h: mi355vits_test_mrf_stage): impl 0 = k_mrf_fused
         (MATH_F32 unless math says MATH_BF16X3), 1 = k_mrf_p, 2 = k_mrf_s with segments of ``seg`` columns.  x [B, C, T];
         weights[j][q] [C, C, ks[j]], biases[j][q] [C]; lengths [B]; y_prior = what the output buffer holds before the launch (zeros)."""
-        self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         B, C, T = x.shape
         ln = np.ascontiguousarray(lengths, np.int32)
@@ -1097,22 +1033,17 @@ class NativeLibrary:
                 bq = np.ascontiguousarray(biases[j][q], np.float32)
                 assert w.shape == (C, C, ks[j]) and bq.shape == (C,)
                 keep += [w, bq]
-                t.w[j][q], t.bias[j][q] = _fptr(w), _fptr(bq)
-        t.x, t.len, t.out_scale, t.y = _fptr(x), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), float(out_scale), _fptr(y)
-        rc = self.lib.mi355vits_test_mrf_stage(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+                t.w[j][q], t.bias[j][q] = _ptr(w), _ptr(bq)
+        t.x, t.len, t.out_scale, t.y = _ptr(x), _ptr(ln), float(out_scale), _ptr(y)
+        self._hook("test_mrf_stage", device, ctypes.byref(t))
         return y
 
     def lab_mrf_plan(self, impl, C, ks, d1, d2):
         """How MRF kernel ``impl`` (0 fused, 1 k_mrf_p, 2 k_mrf_s) cuts a row: (work-item width, halo, x ring, x1 ring) in columns; the
         rings are the sweep's (0 otherwise).  NativeError where the kernel does not serve the stage.  Host arithmetic only."""
-        self._need_hooks()
         arr = lambda v: (ctypes.c_int32 * len(v))(*[int(e) for e in v])
         out = [ctypes.c_int32() for _ in range(4)]
-        rc = self.lib.mi355vits_lab_mrf_plan(int(impl), int(C), len(ks), arr(ks), arr(d1), arr(d2), *[ctypes.byref(o) for o in out])
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_mrf_plan", int(impl), int(C), len(ks), arr(ks), arr(d1), arr(d2), *[ctypes.byref(o) for o in out])
         return tuple(int(o.value) for o in out)
 
     def test_dds_stack(self, src, pre_w, pre_b, layers, lengths, impl=2, math=None, cond=None, z=None, zch=0, proj_w=None, proj_b=None,
@@ -1123,7 +1054,6 @@ class NativeLibrary:
         z[:, zch]); layers = a list of dicts dw_w [C, 1, K], dw_b, g1, b1, w1x1 [C, C, 1], bias1x1, g2, b2; proj_w [Cp, C, 1] or None;
         z [B, 2, T] or None.  out_prior / x_out_prior = what the output buffers hold before the launch (zeros).
         Returns (x_out, out or None, z or None)."""
-        self._need_hooks()
         f = lambda a: np.ascontiguousarray(a, np.float32)
         src, pre_w, pre_b = f(src), f(pre_w), f(pre_b)
         B, C, T = src.shape
@@ -1139,7 +1069,7 @@ class NativeLibrary:
                 a = f(lay[name])
                 assert a.shape == shape, (name, a.shape, shape)
                 keep.append(a)
-                getattr(t, name)[i] = _fptr(a)
+                getattr(t, name)[i] = _ptr(a)
         c = None if cond is None else f(cond)
         assert c is None or c.shape == (B, C)
         zz = None if z is None else f(z).copy()
@@ -1154,32 +1084,25 @@ class NativeLibrary:
         t.impl, t.B, t.C, t.T, t.K, t.n_layers, t.pre_mode, t.zch = int(impl), B, C, T, K, len(layers), int(affine), int(zch)
         t.math = (MATH_BF16X3 if impl == 3 else MATH_F32) if math is None else int(math)
         t.proj_cout, t.spline, t.nb, t.tail, t.inv_sqrt_fc = Cp, int(bool(spline)), int(nb), float(tail), float(inv_sqrt_fc)
-        t.src, t.pre_w, t.pre_b, t.cond, t.proj_w, t.proj_b = _fptr(src), _fptr(pre_w), _fptr(pre_b), _fptr(c), _fptr(pw), _fptr(pb)
-        t.len, t.z, t.out, t.x_out = ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(zz), _fptr(out), _fptr(x_out)
-        rc = self.lib.mi355vits_test_dds_stack(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        t.src, t.pre_w, t.pre_b, t.cond, t.proj_w, t.proj_b = _ptr(src), _ptr(pre_w), _ptr(pre_b), _ptr(c), _ptr(pw), _ptr(pb)
+        t.len, t.z, t.out, t.x_out = _ptr(ln), _ptr(zz), _ptr(out), _ptr(x_out)
+        self._hook("test_dds_stack", device, ctypes.byref(t))
         return x_out, out, zz
 
     def test_spline_inverse(self, theta, z, lengths, nb, ch_x0=0, tail=5.0, inv_sqrt_fc=1.0, device=0) -> np.ndarray:
         """launch_spline_inverse alone: theta [B, 3 nb - 1, T], z [B, 2, T], lengths [B] -> the new z (mi355vits_test_spline_inverse)."""
-        self._need_hooks()
         theta = np.ascontiguousarray(theta, np.float32)
         z = np.ascontiguousarray(z, np.float32).copy()
         ln = np.ascontiguousarray(lengths, np.int32)
         B, _, T = z.shape
         assert z.shape == (B, 2, T) and theta.shape[0] == B and theta.shape[2] == T and ln.shape == (B,)
         assert nb < 1 or theta.shape[1] >= 3 * min(nb, 16) - 1
-        rc = self.lib.mi355vits_test_spline_inverse(device, B, T, int(nb), int(ch_x0), float(tail), float(inv_sqrt_fc), _fptr(theta),
-                                                    ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(z))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_spline_inverse", device, B, T, int(nb), int(ch_x0), float(tail), float(inv_sqrt_fc), _ptr(theta), _ptr(ln), _ptr(z))
         return z
 
     def test_durations(self, z, lengths, ea_m=0.0, ea_logs=0.0, ch=0, length_scale=1.0, forced=None, device=0):
         """launch_durations alone: z [B, 2, T], lengths [B], length_scale a number or [B], forced [B, T] int32 or None ->
         (logw [B, T], w_ceil [B, T], cum [B, T], ylen [B]) (mi355vits_test_durations).  The outputs start as -77 / -7.5e29."""
-        self._need_hooks()
         z = np.ascontiguousarray(z, np.float32)
         B, _, T = z.shape
         ln = np.ascontiguousarray(lengths, np.int32)
@@ -1187,90 +1110,65 @@ class NativeLibrary:
         sc[:, 1] = np.asarray(length_scale, np.float32)
         fo = None if forced is None else np.ascontiguousarray(forced, np.int32)
         assert z.shape == (B, 2, T) and ln.shape == (B,) and (fo is None or fo.shape == (B, T))
-        i32p = ctypes.POINTER(ctypes.c_int32)
         logw = np.full((B, T), -7.5e29, np.float32)
         w_ceil, cum, ylen = np.full((B, T), -77, np.int32), np.full((B, T), -77, np.int32), np.full(B, -77, np.int32)
-        rc = self.lib.mi355vits_test_durations(device, B, T, int(ch), float(ea_m), float(ea_logs), _fptr(z), ln.ctypes.data_as(i32p),
-                                               None if fo is None else fo.ctypes.data_as(i32p), _fptr(sc), _fptr(logw),
-                                               w_ceil.ctypes.data_as(i32p), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_durations", device, B, T, int(ch), float(ea_m), float(ea_logs), _ptr(z), _ptr(ln), _ptr(fo), _ptr(sc), _ptr(logw),
+                   _ptr(w_ceil), _ptr(cum), _ptr(ylen))
         return logw, w_ceil, cum, ylen
 
     def test_fit_durations(self, u, lengths, min_frames=None, target=None, device=0):
         """The fit stage of launch_durations_timed alone on a given u [B, T]: lengths [B], min_frames [B, T] or None, target [B] or
         None -> (frames [B, T], cum [B, T], ylen [B], factor [B], status [B]) (mi355vits_test_fit_durations).  The outputs start as
         -77 / -7.5e29."""
-        self._need_hooks()
         u = np.ascontiguousarray(u, np.float32)
         B, T = u.shape
         ln = np.ascontiguousarray(lengths, np.int32)
         mn = None if min_frames is None else np.ascontiguousarray(min_frames, np.int32)
         tg = None if target is None else np.ascontiguousarray(target, np.int32)
         assert ln.shape == (B,) and (mn is None or mn.shape == (B, T)) and (tg is None or tg.shape == (B,))
-        i32p = ctypes.POINTER(ctypes.c_int32)
         frames, cum = np.full((B, T), -77, np.int32), np.full((B, T), -77, np.int32)
         ylen, status, factor = np.full(B, -77, np.int32), np.full(B, -77, np.int32), np.full(B, -7.5e29, np.float32)
-        rc = self.lib.mi355vits_test_fit_durations(device, B, T, _fptr(u), ln.ctypes.data_as(i32p),
-                                                   None if mn is None else mn.ctypes.data_as(i32p),
-                                                   None if tg is None else tg.ctypes.data_as(i32p), frames.ctypes.data_as(i32p),
-                                                   cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p), _fptr(factor), status.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_fit_durations", device, B, T, _ptr(u), _ptr(ln), _ptr(mn), _ptr(tg), _ptr(frames), _ptr(cum), _ptr(ylen), _ptr(factor),
+                   _ptr(status))
         return frames, cum, ylen, factor, status
 
     def test_levels(self, cum, lengths, gain, ramp, hop: int, audio, audio_bs: int, alen, device=0):
         """launch_levels (k_levels) alone, one launch: cum [B, T] int32, lengths [B], gain [B, T], ramp [B] or None, audio a flat array
         of at least B * ``audio_bs`` floats whose row b starts at ``b * audio_bs`` (all of it goes to the device and comes back), alen
         [B] = hop * max(1, c[len - 1]) -> (audio after the launch, peaks [B]) (mi355vits_test_levels)."""
-        self._need_hooks()
         cum, gain = np.ascontiguousarray(cum, np.int32), np.ascontiguousarray(gain, np.float32)
         B, T = cum.shape
         ln, al = np.ascontiguousarray(lengths, np.int32), np.ascontiguousarray(alen, np.int32)
         rp = None if ramp is None else np.ascontiguousarray(ramp, np.int32)
         out = np.array(audio, np.float32, copy=True).reshape(-1)
         assert gain.shape == (B, T) and ln.shape == (B,) and al.shape == (B,) and (rp is None or rp.shape == (B,)) and out.size >= B * audio_bs
-        i32p = ctypes.POINTER(ctypes.c_int32)
         peaks = np.full(B, -7.5e29, np.float32)
-        rc = self.lib.mi355vits_test_levels(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p), _fptr(gain),
-                                            None if rp is None else rp.ctypes.data_as(i32p), al.ctypes.data_as(i32p), int(audio_bs),
-                                            _fptr(out), out.size, _fptr(peaks))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_levels", device, B, T, int(hop), _ptr(cum), _ptr(ln), _ptr(gain), _ptr(rp), _ptr(al), int(audio_bs), _ptr(out), out.size,
+                   _ptr(peaks))
         return out, peaks
 
     def test_pitch_table(self) -> np.ndarray:
         """The filter table of pitch control, Z P + 2 = 1,538 floats (mi355vits_test_pitch_table)."""
-        self._need_hooks()
         out = np.zeros(12 * 128 + 2, np.float32)
-        rc = self.lib.mi355vits_test_pitch_table(_fptr(out), out.size)
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_pitch_table", _ptr(out), out.size)
         return out
 
     def test_pitch_plan(self, cum, lengths, ratio, hop: int, device=0):
         """launch_pitch_plan (k_pitch_plan) alone: cum [B, T] int32, lengths [B], ratio [B, T] or None -> (tq [B, T] int64,
         wc [B, T] int32, wlen [B] int32) (mi355vits_test_pitch_plan)."""
-        self._need_hooks()
         cum = np.ascontiguousarray(cum, np.int32)
         B, T = cum.shape
         ln = np.ascontiguousarray(lengths, np.int32)
         rt = None if ratio is None else np.ascontiguousarray(ratio, np.float32)
         assert ln.shape == (B,) and (rt is None or rt.shape == (B, T))
-        i32p = ctypes.POINTER(ctypes.c_int32)
         tq, wc, wlen = np.full((B, T), -1, np.int64), np.full((B, T), -1, np.int32), np.full(B, -1, np.int32)
-        rc = self.lib.mi355vits_test_pitch_plan(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p),
-                                                None if rt is None else _fptr(rt), tq.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                                wc.ctypes.data_as(i32p), wlen.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_pitch_plan", device, B, T, int(hop), _ptr(cum), _ptr(ln), _ptr(rt), _ptr(tq), _ptr(wc), _ptr(wlen))
         return tq, wc, wlen
 
     def test_pitch(self, cum, lengths, ratio, hop: int, x, x_bs: int, y, y_bs: int, y_ld: int, device=0):
         """The plan, then launch_pitch (k_pitch), on host buffers: x a flat array of at least B * ``x_bs`` floats whose row b starts
         at ``b * x_bs``, y likewise with ``y_bs`` (all of it goes to the device and comes back; ``y_ld`` floats of each row are
         written) -> (y after the launch, peaks [B], wlen [B]) (mi355vits_test_pitch)."""
-        self._need_hooks()
         cum = np.ascontiguousarray(cum, np.int32)
         B, T = cum.shape
         ln = np.ascontiguousarray(lengths, np.int32)
@@ -1278,48 +1176,40 @@ class NativeLibrary:
         xin = np.ascontiguousarray(x, np.float32).reshape(-1)
         out = np.array(y, np.float32, copy=True).reshape(-1)
         assert ln.shape == (B,) and (rt is None or rt.shape == (B, T)) and xin.size >= B * x_bs and out.size >= B * y_bs
-        i32p = ctypes.POINTER(ctypes.c_int32)
         peaks, wlen = np.full(B, -7.5e29, np.float32), np.full(B, -1, np.int32)
-        rc = self.lib.mi355vits_test_pitch(device, B, T, int(hop), cum.ctypes.data_as(i32p), ln.ctypes.data_as(i32p),
-                                           None if rt is None else _fptr(rt), _fptr(xin), int(x_bs), xin.size, _fptr(out), int(y_bs),
-                                           int(y_ld), out.size, _fptr(peaks), wlen.ctypes.data_as(i32p))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_pitch", device, B, T, int(hop), _ptr(cum), _ptr(ln), _ptr(rt), _ptr(xin), int(x_bs), xin.size,
+                   _ptr(out), int(y_bs), int(y_ld), out.size, _ptr(peaks), _ptr(wlen))
         return out, peaks, wlen
 
     def test_speaker_cond(self, emb_g, sid, w, bias=None, pad: int = 8, device=0) -> np.ndarray:
         """launch_speaker_cond (k_speaker_cond) alone: emb_g [S, gin], sid [B], w [Cout, gin], bias [Cout] or None -> out, B * Cout
         + ``pad`` floats that start as -7.5e29 (mi355vits_test_speaker_cond): ``out[:B * Cout].reshape(B, Cout)`` is the result."""
-        self._need_hooks()
         emb_g, w = np.ascontiguousarray(emb_g, np.float32), np.ascontiguousarray(w, np.float32)
         sid = np.ascontiguousarray(sid, np.int64).reshape(-1)
         bias = None if bias is None else np.ascontiguousarray(bias, np.float32)
         (S, gin), Cout, B = emb_g.shape, w.shape[0], sid.shape[0]
         assert w.shape == (Cout, gin) and (bias is None or bias.shape == (Cout,))
         out = np.full(B * Cout + pad, -7.5e29, np.float32)
-        rc = self.lib.mi355vits_test_speaker_cond(device, B, gin, S, Cout, _fptr(emb_g), sid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                                  _fptr(w), None if bias is None else _fptr(bias), _fptr(out), out.size)
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_speaker_cond", device, B, gin, S, Cout, _ptr(emb_g), _ptr(sid), _ptr(w), _ptr(bias), _ptr(out),
+                   out.size)
         return out
 
     def test_speaker_cond_mix(self, consumers, emb_g=None, sid=None, weight=None, vectors=None, pad: int = 8, device=0):
         """launch_speaker_cond_mix (k_speaker_cond_mix) alone, one launch: ``consumers`` = [(w [Cout, gin], bias [Cout] or None)],
         with emb_g [S, gin], sid / weight [B, K], or vectors [B, gin] -> (g, [out per consumer]): flat arrays of B * gin and B * Cout
         floats + ``pad`` floats each, which start as -7.5e29 (mi355vits_test_speaker_cond_mix)."""
-        self._need_hooks()
         t, keep = SpeakerMixTest(), []
         if vectors is not None:
             vectors = np.ascontiguousarray(vectors, np.float32)
             B, gin = vectors.shape
-            t.vectors = _fptr(vectors)
+            t.vectors = _ptr(vectors)
         else:
             emb_g, weight = np.ascontiguousarray(emb_g, np.float32), np.ascontiguousarray(weight, np.float32)
             sid = np.ascontiguousarray(sid, np.int64)
             (B, K), gin = weight.shape, emb_g.shape[1]
             assert sid.shape == (B, K)
             t.n_speakers, t.n_terms = emb_g.shape[0], K
-            t.emb_g, t.mix_weight, t.mix_sid = _fptr(emb_g), _fptr(weight), sid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+            t.emb_g, t.mix_weight, t.mix_sid = _ptr(emb_g), _ptr(weight), _ptr(sid)
         t.B, t.gin, t.n_jobs = B, gin, len(consumers)
         outs = []
         for q, (w, bias) in enumerate(consumers):
@@ -1329,20 +1219,17 @@ class NativeLibrary:
             out = np.full(B * w.shape[0] + pad, -7.5e29, np.float32)
             keep += [w, bias]
             outs.append(out)
-            t.w[q], t.Cout[q], t.out[q], t.out_floats[q] = _fptr(w), w.shape[0], _fptr(out), out.size
+            t.w[q], t.Cout[q], t.out[q], t.out_floats[q] = _ptr(w), w.shape[0], _ptr(out), out.size
             if bias is not None:
-                t.bias[q] = _fptr(bias)
+                t.bias[q] = _ptr(bias)
         g = np.full(B * gin + pad, -7.5e29, np.float32)
-        t.g, t.g_floats = _fptr(g), g.size
-        rc = self.lib.mi355vits_test_speaker_cond_mix(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        t.g, t.g_floats = _ptr(g), g.size
+        self._hook("test_speaker_cond_mix", device, ctypes.byref(t))
         return g, outs
 
     def test_expand_prior(self, stats, cum, ylen, Ty, noise_scale=0.0, injected=None, z_prior=None, device=0) -> np.ndarray:
         """launch_expand_prior alone with injected noise: stats [B, 2 I, Tx], cum [B, Tx], ylen [B], noise_scale a number or [B],
         injected [B, I, frames >= Ty] or None -> z [B, I, Ty] (mi355vits_test_expand_prior)."""
-        self._need_hooks()
         stats = np.ascontiguousarray(stats, np.float32)
         B, I2, Tx = stats.shape
         I = I2 // 2
@@ -1353,17 +1240,13 @@ class NativeLibrary:
         assert cum.shape == (B, Tx) and ylen.shape == (B,) and (inj is None or inj.shape[:2] == (B, I))
         z = np.full((B, I, int(Ty)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
         assert z.shape == (B, I, int(Ty))
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        rc = self.lib.mi355vits_test_expand_prior(device, B, I, Tx, int(Ty), _fptr(stats), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p),
-                                                  _fptr(inj), 0 if inj is None else inj.shape[2], _fptr(sc), _fptr(z))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_expand_prior", device, B, I, Tx, int(Ty), _ptr(stats), _ptr(cum), _ptr(ylen), _ptr(inj), 0 if inj is None else inj.shape[2],
+                   _ptr(sc), _ptr(z))
         return z
 
     def test_expand_prior_keyed(self, stats, cum, ylen, Ty, noise_scale, seed: int, utt, z_prior=None, device=0) -> np.ndarray:
         """launch_expand_prior alone with the kernel's own Philox noise (tensor id 1) under ``seed`` and utt [B]: stats [B, 2 I, Tx],
         cum [B, Tx], ylen [B], noise_scale a number or [B] -> z [B, I, Ty] (mi355vits_test_expand_prior_keyed)."""
-        self._need_hooks()
         stats = np.ascontiguousarray(stats, np.float32)
         B, I2, Tx = stats.shape
         I = I2 // 2
@@ -1374,31 +1257,23 @@ class NativeLibrary:
         assert cum.shape == (B, Tx) and ylen.shape == (B,) and u.shape == (B,)
         z = np.full((B, I, int(Ty)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
         assert z.shape == (B, I, int(Ty))
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        rc = self.lib.mi355vits_test_expand_prior_keyed(device, B, I, Tx, int(Ty), _fptr(stats), cum.ctypes.data_as(i32p), ylen.ctypes.data_as(i32p),
-                                                        _fptr(sc), int(seed), u.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _fptr(z))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_expand_prior_keyed", device, B, I, Tx, int(Ty), _ptr(stats), _ptr(cum), _ptr(ylen), _ptr(sc), int(seed), _ptr(u), _ptr(z))
         return z
 
     def test_sdp_noise(self, T: int, seed: int, utt, noise_w, z_prior=None, device=0) -> np.ndarray:
         """launch_sdp_noise alone with the kernel's own Philox noise (tensor id 0): utt [B], noise_w a number or [B] -> z [B, 2, T]
         (mi355vits_test_sdp_noise)."""
-        self._need_hooks()
         u = np.ascontiguousarray(utt, np.uint64)
         B = u.shape[0]
         sc = np.zeros((B, 3), np.float32)
         sc[:, 2] = np.asarray(noise_w, np.float32)
         z = np.full((B, 2, int(T)), -7.5e29, np.float32) if z_prior is None else np.ascontiguousarray(z_prior, np.float32).copy()
         assert u.shape == (B,) and z.shape == (B, 2, int(T))
-        rc = self.lib.mi355vits_test_sdp_noise(device, B, int(T), int(seed), u.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _fptr(sc), _fptr(z))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_sdp_noise", device, B, int(T), int(seed), _ptr(u), _ptr(sc), _ptr(z))
         return z
 
     def test_embed(self, ids, lengths, emb, scale: float, y_prior=None, device=0) -> np.ndarray:
         """launch_embed alone: ids [B, T] int64, lengths [B], emb [num_symbols, H] -> y [B, H, T] (mi355vits_test_embed)."""
-        self._need_hooks()
         ids = np.ascontiguousarray(ids, np.int64)
         emb = np.ascontiguousarray(emb, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32)
@@ -1406,17 +1281,13 @@ class NativeLibrary:
         S, H = emb.shape
         y = np.full((B, H, T), -7.5e29, np.float32) if y_prior is None else np.ascontiguousarray(y_prior, np.float32).copy()
         assert ln.shape == (B,) and y.shape == (B, H, T)
-        rc = self.lib.mi355vits_test_embed(device, B, T, H, S, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                           ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(emb), float(scale), _fptr(y))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_embed", device, B, T, H, S, _ptr(ids), _ptr(ln), _ptr(emb), float(scale), _ptr(y))
         return y
 
     def test_layernorm(self, x, gamma, beta, eps=1e-5, bias=None, premask_len=None, res=None, add_to=None, gelu=False, out_len=None,
                        alias=None, part_stride=None, y_prior=None, device=0) -> np.ndarray:
         """launch_layernorm alone (mi355vits_test_layernorm): x [B, C, T], or [nparts, B, C, T] = the partial sums of a split conv (laid
         out ``part_stride`` floats apart, default B C T); alias None / "x" / "res" / "add_to" = which input y is on the device."""
-        self._need_hooks()
         f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
         i32 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
         x = f(x)
@@ -1438,19 +1309,15 @@ class NativeLibrary:
         assert y.shape == (B, C, T)
         t = LayerNormTest()
         t.B, t.C, t.T, t.nparts, t.gelu, t.alias, t.eps, t.part_stride = B, C, T, parts, int(bool(gelu)), LN_ALIAS[alias], float(eps), stride
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        t.x, t.bias, t.res, t.add_to, t.gamma, t.beta, t.y = _fptr(x), _fptr(bias), _fptr(res), _fptr(add_to), _fptr(gamma), _fptr(beta), _fptr(y)
-        t.premask_len = None if pl is None else pl.ctypes.data_as(i32p)
-        t.out_len = None if ol is None else ol.ctypes.data_as(i32p)
-        rc = self.lib.mi355vits_test_layernorm(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        t.x, t.bias, t.res, t.add_to, t.gamma, t.beta, t.y = _ptr(x), _ptr(bias), _ptr(res), _ptr(add_to), _ptr(gamma), _ptr(beta), _ptr(y)
+        t.premask_len = _ptr(pl)
+        t.out_len = _ptr(ol)
+        self._hook("test_layernorm", device, ctypes.byref(t))
         return y
 
     def test_dp_det(self, x, lengths, w, cond=None, math=MATH_BF16X3, logw_prior=None, device=0) -> np.ndarray:
         """launch_dp_det alone (mi355vits_test_dp_det): x [B, H, T], lengths [B], w = dict w1 [F, H, K], b1, g1, be1, w2 [F, F, K], b2, g2,
         be2, proj_w [F], proj_b [1]; cond [B, H] or None -> logw [B, T]."""
-        self._need_hooks()
         f = lambda a: np.ascontiguousarray(a, np.float32)
         x = f(x)
         B, H, T = x.shape
@@ -1465,29 +1332,23 @@ class NativeLibrary:
         assert logw.shape == (B, T)
         t = DpDetTest()
         t.B, t.H, t.F, t.K, t.T, t.math = B, H, F, K, T, int(math)
-        t.x, t.cond, t.len, t.logw = _fptr(x), _fptr(c), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fptr(logw)
+        t.x, t.cond, t.len, t.logw = _ptr(x), _ptr(c), _ptr(ln), _ptr(logw)
         for k, v in ww.items():
-            setattr(t, k, _fptr(v))
-        rc = self.lib.mi355vits_test_dp_det(device, ctypes.byref(t))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+            setattr(t, k, _ptr(v))
+        self._hook("test_dp_det", device, ctypes.byref(t))
         return logw
 
     def lab_dp_det_plan(self, H, F, K, math=MATH_BF16X3):
         """(output columns of a k_dp_det work item, the two convs' reach 2 (K // 2), the launch's LDS bytes) from the library's own
         functions (mi355vits_lab_dp_det_plan); NativeError where the hook would refuse the shape."""
-        self._need_hooks()
         cols, halo, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        rc = self.lib.mi355vits_lab_dp_det_plan(int(H), int(F), int(K), int(math), ctypes.byref(cols), ctypes.byref(halo), ctypes.byref(lds))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("lab_dp_det_plan", int(H), int(F), int(K), int(math), ctypes.byref(cols), ctypes.byref(halo), ctypes.byref(lds))
         return cols.value, halo.value, lds.value
 
     def test_resample(self, x, lengths, in_hz: int, out_hz: int, device=0):
         """The product's resampler launch (k_resample) on caller-given f32 rows: x [B, row_stride], lengths [B] valid samples
         of each row (what lies past them is never looked at) -> (y [B, max n_out] with zeros past a row's output length,
         y_lengths [B], peaks [B])."""
-        self._need_hooks()
         x = np.ascontiguousarray(x, np.float32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         B, stride = x.shape
@@ -1497,18 +1358,13 @@ class NativeLibrary:
         y = np.empty((B, ys), np.float32)
         yl = np.zeros(B, np.int32)
         pk = np.zeros(B, np.float32)
-        rc = self.lib.mi355vits_test_resample(device, B, stride, _fptr(x), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                              int(in_hz), int(out_hz), ys, _fptr(y), yl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                              _fptr(pk))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_resample", device, B, stride, _ptr(x), _ptr(ln), int(in_hz), int(out_hz), ys, _ptr(y), _ptr(yl), _ptr(pk))
         return y, yl, pk
 
     def test_alignment(self, frames, lengths, audio, alen, hop: int, L: int = 1, M: int = 1, levels: bool = True, device=0) -> Alignment:
         """The product's alignment launch (k_align) alone on caller-given arrays: frames [B, T] int32 (read below lengths[b]
         only), lengths [B] phonemes of a row, audio [B, row_stride] f32 with alen [B] valid samples each (what lies past them is
         never looked at), hop samples per frame, L / M the rate ratio -> ``Alignment`` (``sample_rate`` None)."""
-        self._need_hooks()
         fr = np.ascontiguousarray(frames, np.int32)
         ln = np.ascontiguousarray(lengths, np.int32).reshape(-1)
         au = np.ascontiguousarray(audio, np.float32)
@@ -1516,22 +1372,15 @@ class NativeLibrary:
         B, T = fr.shape
         if au.ndim != 2 or au.shape[0] != B or ln.shape[0] != B or al.shape[0] != B:
             raise ValueError("frames [B, T], lengths [B], audio [B, row_stride], alen [B]")
-        i32p = ctypes.POINTER(ctypes.c_int32)
         o = [np.zeros((B, T), np.int32) for _ in range(3)]
         lv = [np.zeros((B, T), np.float32) for _ in range(2)] if levels else [None, None]
-        rc = self.lib.mi355vits_test_alignment(device, B, T, fr.ctypes.data_as(i32p), ln.ctypes.data_as(i32p), au.shape[1], _fptr(au),
-                                               al.ctypes.data_as(i32p), int(hop), int(L), int(M), o[0].ctypes.data_as(i32p),
-                                               o[1].ctypes.data_as(i32p), o[2].ctypes.data_as(i32p), _fptr(lv[0]), _fptr(lv[1]))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("test_alignment", device, B, T, _ptr(fr), _ptr(ln), au.shape[1], _ptr(au), _ptr(al), int(hop), int(L), int(M), _ptr(o[0]),
+                   _ptr(o[1]), _ptr(o[2]), _ptr(lv[0]), _ptr(lv[1]))
         return Alignment(o[0], o[1], o[2], lv[0], lv[1], None)
 
     def bench_conv1d(self, B, Cin, Cout, T, K, dilation=1, epi=0, reps=20, device=0) -> float:
-        self._need_hooks()
         ms = ctypes.c_float(-1.0)
-        rc = self.lib.mi355vits_bench_conv1d(device, B, Cin, Cout, T, K, dilation, epi, reps, ctypes.byref(ms))
-        if rc != 0:
-            raise NativeError(rc, self.create_error())
+        self._hook("bench_conv1d", device, B, Cin, Cout, T, K, dilation, epi, reps, ctypes.byref(ms))
         return float(ms.value)
 
     def probe_device(self, device=0) -> dict:

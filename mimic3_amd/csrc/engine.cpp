@@ -224,64 +224,40 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
     c.Cout = Cout; c.Cin = Cin; c.K = K; c.epi = epi;
     c.raw = stage(w.data(), w.size());
     if (bias) c.bias = stage(bias->data(), bias->size());
+    static_assert(sizeof(uint32_t) == sizeof(float), "bit patterns travel in the float arena");
+    auto stage_words = [&](const std::vector<uint32_t>& p) { return stage(reinterpret_cast<const float*>(p.data()), p.size()); };
     if (conv1d_mfma_supported(Cin, Cout, K, 1)) {
-        std::vector<float> pk(mfma_packed_floats(Cout, Cin, K), 0.0f);
-        pack_conv_weights_mfma_mode(w.data(), Cout, Cin, K, epi == EPI_GATE ? EPI_GATE : EPI_STD, pk.data());
+        const int pe = epi == EPI_GATE ? EPI_GATE : EPI_STD;
+        const std::vector<float> pk = conv_weights_mfma(w.data(), Cout, Cin, K, pe);
         c.packed = stage(pk.data(), pk.size());
         const bool rb = role == ROLE_RESBLOCK && epi == EPI_STD;
-        if (rb && Cin % 8 == 0 && Cout % 32 == 0) {
-            // fused MRF stage: a lane's A fragments of four consecutive channel pairs side by side
-            std::vector<float> p4(pk.size());
-            regroup_packed_x4(pk.data(), pk.size(), p4.data());
+        if (rb && Cin % 8 == 0 && Cout % 32 == 0) {  // fused MRF stage
+            const std::vector<float> p4 = conv_weights_mfma_x4(pk);
             c.packed4 = stage(p4.data(), p4.size());
         }
         if (rb && Cin % 16 == 0 && Cout % 32 == 0) {
             // the same weights as three bf16 planes for the split-operand path (MATH_BF16X3)
-            std::vector<uint32_t> b3(bf16x3_packed_words(Cout, Cin, K));
-            pack_conv_weights_bf16x3(w.data(), Cout, Cin, K, b3.data());
-            static_assert(sizeof(uint32_t) == sizeof(float), "bit patterns travel in the float arena");
-            c.packed_b3 = stage(reinterpret_cast<const float*>(b3.data()), b3.size());
+            c.packed_b3 = stage_words(conv_weights_bf16x3(w.data(), Cout, Cin, K));
             // ... and as two fp16 planes (MATH_F16X2, experimental), unless a weight is too large for the fixed scale
-            std::vector<uint32_t> h2(f16x2_packed_words(Cout, Cin, K));
-            if (pack_conv_weights_f16x2(w.data(), Cout, Cin, K, h2.data()))
-                c.packed_h2 = stage(reinterpret_cast<const float*>(h2.data()), h2.size());
+            const std::vector<uint32_t> h2 = conv_weights_f16x2(w.data(), Cout, Cin, K, 0);
+            if (!h2.empty()) c.packed_h2 = stage_words(h2);
         }
-        if (rb && Cin == Cout && Cin % 32 == 0 && (K == 3 || K == 5 || K == 7)) {
-            // ... and in the fragment order of k_mrf_p (16-row tiles, 32-channel k-groups)
-            std::vector<uint32_t> pp(p16_packed_words(Cout, Cin, K));
-            pack_conv_weights_p16(w.data(), Cout, Cin, K, pp.data());
-            c.packed_p = stage(reinterpret_cast<const float*>(pp.data()), pp.size());
-        }
-        if (role == ROLE_UPSAMPLER && epi == EPI_STD && (Cin == 64 || Cin == 128 || Cin == 256) && Cout % 128 == 0 && K == 2) {
-            // polyphase upsamplers 128 -> 64 / 64 -> 32: fragments of 16-row tiles in natural row order (k_ups_pl)
-            std::vector<uint32_t> pp(p16_packed_words(Cout, Cin, K));
-            pack_conv_weights_p16n(w.data(), Cout, Cin, K, pp.data());
-            c.packed_p = stage(reinterpret_cast<const float*>(pp.data()), pp.size());
-        }
+        // ... and in the fragment order of k_mrf_p (16-row tiles, 32-channel k-groups)
+        if (rb && Cin == Cout && Cin % 32 == 0 && (K == 3 || K == 5 || K == 7)) c.packed_p = stage_words(conv_weights_p16(w.data(), Cout, Cin, K));
+        // polyphase upsamplers 128 -> 64 / 64 -> 32: fragments of 16-row tiles in natural row order (k_ups_pl)
+        if (role == ROLE_UPSAMPLER && epi == EPI_STD && (Cin == 64 || Cin == 128 || Cin == 256) && Cout % 128 == 0 && K == 2)
+            c.packed_p = stage_words(conv_weights_p16n(w.data(), Cout, Cin, K));
         if (Cin % 32 == 0 && (epi == EPI_GATE ? (Cout / 2) % 32 == 0 : true)) {
             // ... and for the staged split-bf16 kernel (every dense conv with a multiple of 32 input channels)
-            const int pe = epi == EPI_GATE ? EPI_GATE : EPI_STD;
-            std::vector<uint32_t> b3(bf16x3_packed_words_mode(Cout, Cin, K, pe));
-            pack_conv_weights_bf16x3_mode(w.data(), Cout, Cin, K, pe, 1, b3.data());
-            c.packed_b3s = stage(reinterpret_cast<const float*>(b3.data()), b3.size());
-            // k_wn_layer_b3 gates in registers: 32-row tile q of a gate conv = the tanh rows of channels 16 q .. 16 q + 15, then their sigmoid
-            // rows (a lane of the 32 x 32 accumulator tile then holds both halves of its eight channels; kernels_wn.cpp)
+            c.packed_b3s = stage_words(conv_weights_bf16x3_staged(w.data(), Cout, Cin, K, pe));
+            // k_wn_layer_b3 gates in registers: a gate conv's rows in tile order (kernels.h, conv_weights_gate_tiles)
             std::vector<float> wg;
             if (epi == EPI_GATE && Cout % 32 == 0) {
-                const int Hh = Cout / 2;
-                const size_t row = (size_t)Cin * K;
-                wg.resize(w.size());
-                for (int q = 0; q < Cout / 32; ++q)
-                    for (int r = 0; r < 32; ++r) {
-                        const int src = (r < 16 ? 0 : Hh) + 16 * q + (r & 15);
-                        memcpy(wg.data() + ((size_t)32 * q + r) * row, w.data() + (size_t)src * row, row * sizeof(float));
-                    }
+                wg = conv_weights_gate_tiles(w.data(), Cout, Cin, K);
 #if defined(MI355_LAB) || defined(MI355_EMU)
                 // (the split-bf16 form on these tiles is the lab build's and the CPU model's MI355VITS_WN_SHAPE=32 only; MATH_F16X2 below
                 // keeps the tile order in every build)
-                std::vector<uint32_t> bw(bf16x3_packed_words_mode(Cout, Cin, K, EPI_STD));
-                pack_conv_weights_bf16x3_mode(wg.data(), Cout, Cin, K, EPI_STD, 1, bw.data());
-                c.packed_b3w = stage(reinterpret_cast<const float*>(bw.data()), bw.size());
+                c.packed_b3w = stage_words(conv_weights_bf16x3_staged(wg.data(), Cout, Cin, K));
 #endif
             }
             // the two convs of a coupling's WaveNet layer ("flow.<j>.in.<l>", "flow.<j>.rs.<l>") as k_wn_layer_b3 reads them on 16x16x32
@@ -289,15 +265,10 @@ const ConvW& Engine::add_conv_data(const std::string& key, const std::vector<flo
             const bool wn_conv = key.compare(0, 5, "flow.") == 0 && (epi == EPI_GATE ? key.find(".in.") != std::string::npos && Cout == 2 * Cin
                                                                                      : key.find(".rs.") != std::string::npos && K == 1 && epi == EPI_STD &&
                                                                                            (Cout == Cin || Cout == 2 * Cin));
-            if (wn_conv && wn_layer_b3_supported(Cin, 1, 1)) {
-                std::vector<uint32_t> pw(w16_packed_words(Cout, Cin, K));
-                pack_conv_weights_w16(w.data(), Cout, Cin, K, epi == EPI_GATE, pw.data());
-                c.packed_w16 = stage(reinterpret_cast<const float*>(pw.data()), pw.size());
-            }
+            if (wn_conv && wn_layer_b3_supported(Cin, 1, 1)) c.packed_w16 = stage_words(conv_weights_w16(w.data(), Cout, Cin, K, epi == EPI_GATE));
             if (Cin % 16 == 0 && Cout % 32 == 0) {  // MATH_F16X2: WaveNet layers (gate convs: the tile order above), staged convs, polyphase upsamplers (plain rows)
-                std::vector<uint32_t> h2(f16x2_packed_words(Cout, Cin, K));
-                if (pack_conv_weights_f16x2(wg.empty() ? w.data() : wg.data(), Cout, Cin, K, h2.data(), 1))
-                    c.packed_h2s = stage(reinterpret_cast<const float*>(h2.data()), h2.size());
+                const std::vector<uint32_t> h2 = conv_weights_f16x2(wg.empty() ? w.data() : wg.data(), Cout, Cin, K, 1);
+                if (!h2.empty()) c.packed_h2s = stage_words(h2);
             }
         }
     }
@@ -713,19 +684,8 @@ void Engine::probe_weights(double out[8]) {
     const int nwin = (int)std::min<size_t>(model_->bytes / win, 24);
     if (nwin < 1) throw EngineError(MI355VITS_ERR_INVALID, "weight arena smaller than one probe window");
     // (diagnostics of include/mi355vits_lab.h: hipMalloc / hipFree synchronise the device — not for a handle that is serving.)
-    // RAII: a HIP error in between must not leak the events or the sink
-    struct Ev {
-        hipEvent_t e = nullptr;
-        Ev() { HIP_CHECK(hipEventCreate(&e)); }
-        ~Ev() { if (e) (void)hipEventDestroy(e); }
-    } ev0, ev1;
-    struct Sink {
-        unsigned* p = nullptr;
-        explicit Sink(size_t n) { HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n)); }
-        ~Sink() { (void)hipFree(p); }
-    } sk((size_t)cus * 4 + 16);
-    hipEvent_t e0 = ev0.e, e1 = ev1.e;
-    unsigned* sink = sk.p;
+    DevBuf sk((size_t)cus * 4 + 16);
+    unsigned* sink = sk.as<unsigned>();
     std::vector<double> g8, g1;
     for (int wdx = 0; wdx < nwin; ++wdx) {
         const char* base = reinterpret_cast<const char*>(model_->dev_weights) + (size_t)wdx * win;
@@ -734,15 +694,8 @@ void Engine::probe_weights(double out[8]) {
                 if (mode == 0) launch_probe_l2_stream(base, n16, 4, sink, cus, stream_);
                 else launch_probe_l2_stream1(base, n16, 1, sink, cus, stream_);
             };
-            go();
-            HIP_CHECK(hipEventRecord(e0, stream_));
-            go();
-            go();
-            HIP_CHECK(hipEventRecord(e1, stream_));
-            HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            const double gbs = (double)cus * (mode == 0 ? 4 : 1) * win / (ms * 0.5e-3) / 1e9;
+            const double ms = timed(go, 1, 2, stream_);
+            const double gbs = (double)cus * (mode == 0 ? 4 : 1) * win / (ms * 1e-3) / 1e9;
             (mode == 0 ? g8 : g1).push_back(gbs);
         }
     }

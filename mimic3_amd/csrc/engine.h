@@ -84,6 +84,37 @@ struct ProfScope {
     }
 };
 
+// ---------------------------------------------------------------- RAII guards of the diagnostic and test calls
+// (hipMalloc / hipFree synchronise the device: not for the serving path, which lives in the arenas)
+struct DevBuf {
+    void* p = nullptr;
+    explicit DevBuf(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); }
+    ~DevBuf() { (void)hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    template <typename T> T* as() { return static_cast<T*>(p); }
+};
+struct Ev {  // a HIP error between create and destroy must not leak the event
+    hipEvent_t e = nullptr;
+    Ev() { HIP_CHECK(hipEventCreate(&e)); }
+    ~Ev() { if (e) (void)hipEventDestroy(e); }
+    Ev(const Ev&) = delete;
+    Ev& operator=(const Ev&) = delete;
+};
+// ms per launch between two events on `stream`: `warm` untimed launches, then `reps` timed ones
+template <typename F>
+double timed(F&& launch, int warm, int reps, hipStream_t stream = nullptr) {
+    Ev e0, e1;
+    for (int i = 0; i < warm; ++i) launch();
+    HIP_CHECK(hipEventRecord(e0.e, stream));
+    for (int i = 0; i < reps; ++i) launch();
+    HIP_CHECK(hipEventRecord(e1.e, stream));
+    HIP_CHECK(hipEventSynchronize(e1.e));
+    float ms = 0.0f;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0.e, e1.e));
+    return (double)ms / reps;
+}
+
 struct Tap {
     std::string name;
     float* dev;

@@ -264,6 +264,65 @@ int wn_layer_b3_shape();
 // Cin % 32 == 0, Cout % 32 == 0 (gate: Cout % 64 == 0).
 size_t w16_packed_words(int Cout, int Cin, int K);
 void pack_conv_weights_w16(const float* w, int Cout, int Cin, int K, bool gate, uint32_t* out);
+
+// ---------------------------------------------------------------- one function per packed weight format
+// The packed form of a conv's weights w [Cout, Cin, K], sized and filled: what Engine::add_conv_data stages into the weight arena and
+// what the hooks of lab_api.cpp hand a kernel.  Which conv gets which form is the caller's decision.
+inline std::vector<float> conv_weights_mfma(const float* w, int Cout, int Cin, int K, int epi = EPI_STD) {  // f32 MFMA fragments
+    std::vector<float> p(mfma_packed_floats(Cout, Cin, K), 0.0f);
+    pack_conv_weights_mfma_mode(w, Cout, Cin, K, epi, p.data());
+    return p;
+}
+inline std::vector<float> conv_weights_mfma_x4(const std::vector<float>& mfma) {  // a lane's fragments of four channel pairs side by side
+    std::vector<float> p(mfma.size());
+    regroup_packed_x4(mfma.data(), mfma.size(), p.data());
+    return p;
+}
+inline std::vector<uint32_t> conv_weights_bf16x3(const float* w, int Cout, int Cin, int K) {  // three bf16 planes, packed activation tiles
+    std::vector<uint32_t> p(bf16x3_packed_words(Cout, Cin, K));
+    pack_conv_weights_bf16x3(w, Cout, Cin, K, p.data());
+    return p;
+}
+inline std::vector<uint32_t> conv_weights_bf16x3_staged(const float* w, int Cout, int Cin, int K, int epi = EPI_STD) {  // ... staged planes
+    std::vector<uint32_t> p(bf16x3_packed_words_mode(Cout, Cin, K, epi));
+    pack_conv_weights_bf16x3_mode(w, Cout, Cin, K, epi, 1, p.data());
+    return p;
+}
+inline std::vector<uint32_t> conv_weights_p16(const float* w, int Cout, int Cin, int K) {  // k_mrf_p / k_rb_conv
+    std::vector<uint32_t> p(p16_packed_words(Cout, Cin, K));
+    pack_conv_weights_p16(w, Cout, Cin, K, p.data());
+    return p;
+}
+inline std::vector<uint32_t> conv_weights_p16n(const float* w, int Cout, int Cin, int K) {  // k_ups_pl: natural row order
+    std::vector<uint32_t> p(p16_packed_words(Cout, Cin, K));
+    pack_conv_weights_p16n(w, Cout, Cin, K, p.data());
+    return p;
+}
+inline std::vector<uint32_t> conv_weights_w16(const float* w, int Cout, int Cin, int K, bool gate) {  // k_wn_layer_b3, 16x16x32 tiles
+    std::vector<uint32_t> p(w16_packed_words(Cout, Cin, K));
+    pack_conv_weights_w16(w, Cout, Cin, K, gate, p.data());
+    return p;
+}
+// two fp16 planes (layout as for bf16x3); empty when a weight is too large for the fixed scale
+inline std::vector<uint32_t> conv_weights_f16x2(const float* w, int Cout, int Cin, int K, int layout) {
+    std::vector<uint32_t> p(f16x2_packed_words(Cout, Cin, K));
+    if (!pack_conv_weights_f16x2(w, Cout, Cin, K, p.data(), layout)) p.clear();
+    return p;
+}
+// The rows of a gate conv [2 H, Cin, K] in the tile order of the kernels that gate in registers: 32-row tile q = the tanh rows of
+// channels 16 q .. 16 q + 15, then their sigmoid rows (a lane of the 32 x 32 accumulator tile then holds both halves of its eight
+// channels; kernels_wn.cpp).  Cout % 32 == 0.
+inline std::vector<float> conv_weights_gate_tiles(const float* w, int Cout, int Cin, int K) {
+    const int H = Cout / 2;
+    const size_t row = (size_t)Cin * K;
+    std::vector<float> p((size_t)Cout * row);
+    for (int q = 0; q < Cout / 32; ++q)
+        for (int r = 0; r < 32; ++r) {
+            const int src = (r < 16 ? 0 : H) + 16 * q + (r & 15);
+            memcpy(p.data() + ((size_t)32 * q + r) * row, w + (size_t)src * row, row * sizeof(float));
+        }
+    return p;
+}
 // The 32-column tiles per workgroup (1, 3 or 4) launch_wn_layer_b3 takes for this layer on the current device, and the geometry
 // (0: 4 waves x 3 tiles, 1: 6 x 2, 2: 12 x 1) launch_wn_layer takes at H = 192: the launchers' own rules (lab build and CPU model:
 // with the switches they read), for the launchers and for the unit-test hooks' plan call.

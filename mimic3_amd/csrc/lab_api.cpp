@@ -5,6 +5,8 @@
 #include "c_api_internal.h"
 #include "mi355vits_lab.h"
 
+#include <algorithm>
+
 extern "C" {
 
 int mi355vits_probe_weights(mi355vits_handle h, double out[8]) {
@@ -84,10 +86,13 @@ void convt_hook_check(int impl, int B, int Cin, int Cout, int Tin, int K, int st
         throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the split-bf16 kernel");
 }
 
-void check_lens(const int32_t* len, int B, int T, const char* what) {
+void check_lens(const int32_t* len, int B, long T, const char* what) {
     for (int b = 0; len && b < B; ++b)
         if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, what);
 }
+
+// packed bit patterns travel as floats (ConvArgs::w / wb3 and the like)
+const float* in_words(HookScope& s, const std::vector<uint32_t>& p) { return reinterpret_cast<const float*>(s.in(p)); }
 }  // namespace
 
 extern "C" {
@@ -100,76 +105,45 @@ int mi355vits_test_conv1d(int device, const mi355vits_conv_test* t) {
         ConvArgs a = conv_hook_args(t->impl, t->B, t->Cin, t->Cout, t->T, t->K, t->dilation, t->math, t->fixed_rule, o);
         check_lens(t->in_len, t->B, t->T, "in_len out of range");
         check_lens(t->out_len, t->B, t->T, "out_len out of range");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t nx = (size_t)t->B * t->Cin * t->T, ny = (size_t)t->B * t->Cout * t->T;
-        const size_t nw = (size_t)t->Cout * t->Cin * t->K;
-        DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(t->Cout * 4), dres(ny * 4), dil(t->B * 4), dol(t->B * 4), dcond((size_t)t->B * t->Cout * 4);
-        std::vector<float> packed;
-        HIP_CHECK(hipMemcpy(dx.p, t->x, nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, t->y, ny * 4, hipMemcpyHostToDevice));
-        a.x = dx.as<float>();
-        a.y = dy.as<float>();
+        a.x = s.in(t->x, nx);
+        a.y = s.in<float>(t->y, ny);  // a position no kernel writes keeps the caller's value
         a.in_slope = t->in_slope;
-        if (t->bias) { HIP_CHECK(hipMemcpy(db.p, t->bias, t->Cout * 4, hipMemcpyHostToDevice)); a.bias = db.as<float>(); }
-        if (t->res) { HIP_CHECK(hipMemcpy(dres.p, t->res, ny * 4, hipMemcpyHostToDevice)); a.res = dres.as<float>(); }
-        if (t->cond) { HIP_CHECK(hipMemcpy(dcond.p, t->cond, (size_t)t->B * t->Cout * 4, hipMemcpyHostToDevice)); a.cond = dcond.as<float>(); }
-        if (t->in_len) { HIP_CHECK(hipMemcpy(dil.p, t->in_len, t->B * 4, hipMemcpyHostToDevice)); a.in_len = dil.as<int>(); }
-        if (t->out_len) { HIP_CHECK(hipMemcpy(dol.p, t->out_len, t->B * 4, hipMemcpyHostToDevice)); a.out_len = dol.as<int>(); }
+        a.bias = s.in(t->bias, (size_t)t->Cout);
+        a.res = s.in(t->res, ny);
+        a.cond = s.in(t->cond, (size_t)t->B * t->Cout);
+        a.in_len = s.in(t->in_len, (size_t)t->B);
+        a.out_len = s.in(t->out_len, (size_t)t->B);
         if (t->impl == 3) {
-            std::vector<uint32_t> b3(bf16x3_packed_words_mode(t->Cout, t->Cin, t->K, EPI_STD));
-            pack_conv_weights_bf16x3_mode(t->w, t->Cout, t->Cin, t->K, EPI_STD, 1, b3.data());
-            DevBuf db3(b3.size() * 4);
-            HIP_CHECK(hipMemcpy(db3.p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
-            a.wb3 = db3.as<float>();
-            DevBuf dpart(ny * 4 * (size_t)a.ksplit);
-            if (a.ksplit > 1) a.part = dpart.as<float>();
+            a.wb3 = in_words(s, conv_weights_bf16x3_staged(t->w, t->Cout, t->Cin, t->K));
+            if (a.ksplit > 1) a.part = s.scratch<float>(ny * (size_t)a.ksplit);
             launch_enc_conv_b3(a, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipGetLastError());
-            if (a.ksplit > 1) {
-                std::vector<float> parts(ny * (size_t)a.ksplit);
-                HIP_CHECK(hipMemcpy(parts.data(), dpart.p, parts.size() * 4, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < ny; ++i) {
-                    float v = parts[i];
-                    for (int sl = 1; sl < a.ksplit; ++sl) v += parts[(size_t)sl * ny + i];
-                    t->y[i] = v;
-                }
-                return;
-            }
         } else if (t->impl == 4) {
-            std::vector<uint32_t> pp(p16_packed_words(t->Cout, t->Cin, t->K));
-            pack_conv_weights_p16(t->w, t->Cout, t->Cin, t->K, pp.data());
-            DevBuf dpp(pp.size() * 4);
-            HIP_CHECK(hipMemcpy(dpp.p, pp.data(), pp.size() * 4, hipMemcpyHostToDevice));
-            a.w = dpp.as<float>();
+            a.w = in_words(s, conv_weights_p16(t->w, t->Cout, t->Cin, t->K));
             a.in_len_host = t->in_len;
             launch_rb_conv(a, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
         } else if (t->impl == 1 || t->impl == 2) {
-            packed.resize(mfma_packed_floats(t->Cout, t->Cin, t->K));
-            pack_conv_weights_mfma(t->w, t->Cout, t->Cin, t->K, packed.data());
-            DevBuf dp(packed.size() * 4);
-            HIP_CHECK(hipMemcpy(dp.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-            a.w = dp.as<float>();
-            std::vector<uint32_t> b3;
-            std::unique_ptr<DevBuf> db3;
-            if (t->impl == 2) {  // split-bf16 staged kernel (MATH_BF16X3 / MATH_BF16W)
-                b3.resize(bf16x3_packed_words_mode(t->Cout, t->Cin, t->K, EPI_STD));
-                pack_conv_weights_bf16x3_mode(t->w, t->Cout, t->Cin, t->K, EPI_STD, 1, b3.data());
-                db3.reset(new DevBuf(b3.size() * 4));
-                HIP_CHECK(hipMemcpy(db3->p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
-                a.wb3 = db3->as<float>();
-            }
+            a.w = s.in(conv_weights_mfma(t->w, t->Cout, t->Cin, t->K));
+            // impl 2: the split-bf16 staged kernel (MATH_BF16X3 / MATH_BF16W)
+            if (t->impl == 2) a.wb3 = in_words(s, conv_weights_bf16x3_staged(t->w, t->Cout, t->Cin, t->K));
             launch_conv1d_mfma(a, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
         } else {
-            HIP_CHECK(hipMemcpy(dw.p, t->w, nw * 4, hipMemcpyHostToDevice));
-            a.w = dw.as<float>();
+            a.w = s.in(t->w, (size_t)t->Cout * t->Cin * t->K);
             launch_conv1d_generic(a, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
         }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        s.finish();
+        if (t->impl == 3 && a.ksplit > 1) {
+            std::vector<float> parts(ny * (size_t)a.ksplit);
+            s.fetch(parts.data(), a.part, parts.size());
+            for (size_t i = 0; i < ny; ++i) {
+                float v = parts[i];
+                for (int sl = 1; sl < a.ksplit; ++sl) v += parts[(size_t)sl * ny + i];
+                t->y[i] = v;
+            }
+            return;
+        }
+        s.fetch(t->y, a.y, ny);
     });
 }
 
@@ -232,32 +206,22 @@ int mi355vits_test_enc_o_ln(int device, int math, int B, int T, const float* x, 
         check_lens(ln_out_len, B, T, "ln_out_len out of range");
         const int C = 192;
         if (!enc_o_ln_supported(C, C, 1)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t n = (size_t)B * C * T;
-        std::vector<uint32_t> b3(bf16x3_packed_words_mode(C, C, 1, EPI_STD));
-        pack_conv_weights_bf16x3_mode(w, C, C, 1, EPI_STD, 1, b3.data());
-        DevBuf dx(n * 4), dres(n * 4), dy(n * 4), db3(b3.size() * 4), db(C * 4), dg(C * 4), dbt(C * 4), dil((size_t)B * 4), dol((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dres.p, res, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(db3.p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dg.p, gamma, C * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dbt.p, beta, C * 4, hipMemcpyHostToDevice));
+        float* dres = s.in(res, n);
+        float* dy = in_place ? dres : s.in<float>(y, n);  // in place: the one device pointer serves as residual and as output
         ConvArgs c;
-        c.x = dx.as<float>(); c.x_bs = (long)C * T; c.x_ld = T;
-        c.res = dres.as<float>(); c.res_bs = (long)C * T; c.res_ld = T;
-        c.y = in_place ? dres.as<float>() : dy.as<float>(); c.y_bs = (long)C * T; c.y_ld = T;
-        c.wb3 = db3.as<float>();
+        c.x = s.in(x, n); c.x_bs = (long)C * T; c.x_ld = T;
+        c.res = dres; c.res_bs = (long)C * T; c.res_ld = T;
+        c.y = dy; c.y_bs = (long)C * T; c.y_ld = T;
+        c.wb3 = in_words(s, conv_weights_bf16x3_staged(w, C, C, 1));
         c.math = math;
         c.B = B; c.Cin = C; c.Cout = C; c.T = T; c.K = 1; c.dil = 1; c.pad = 0;
-        if (bias) { HIP_CHECK(hipMemcpy(db.p, bias, C * 4, hipMemcpyHostToDevice)); c.bias = db.as<float>(); }
-        if (in_len) { HIP_CHECK(hipMemcpy(dil.p, in_len, (size_t)B * 4, hipMemcpyHostToDevice)); c.in_len = dil.as<int>(); }
-        const int* dout = nullptr;
-        if (ln_out_len) { HIP_CHECK(hipMemcpy(dol.p, ln_out_len, (size_t)B * 4, hipMemcpyHostToDevice)); dout = dol.as<int>(); }
-        launch_enc_o_ln(c, dg.as<float>(), dbt.as<float>(), dout, eps, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(y, in_place ? dres.p : dy.p, n * 4, hipMemcpyDeviceToHost));
+        c.bias = s.in(bias, (size_t)C);
+        c.in_len = s.in(in_len, (size_t)B);
+        launch_enc_o_ln(c, s.in(gamma, (size_t)C), s.in(beta, (size_t)C), s.in(ln_out_len, (size_t)B), eps, nullptr);
+        s.finish();
+        s.fetch(y, dy, n);
     });
 }
 
@@ -267,24 +231,20 @@ int mi355vits_test_conv_post(int device, int B, int Cin, int K, int L, const flo
         if (!x || !w || !valid_len || !audio || !peaks || !pcm) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || Cin < 1 || K < 1 || !(K & 1) || L < 1 || (size_t)B * Cin * L >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
         check_lens(valid_len, B, L, "valid_len out of range");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t nx = (size_t)B * Cin * L, na = (size_t)B * L;
-        DevBuf dx(nx * 4), dw((size_t)Cin * K * 4), dl((size_t)B * 4), dv((size_t)B * 8), da(na * 4), dp((size_t)B * 4), dq(na * 2);
-        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, w, (size_t)Cin * K * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, valid_len, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (volumes) HIP_CHECK(hipMemcpy(dv.p, volumes, (size_t)B * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dq.p, pcm, na * 2, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));  // the peaks are an atomic maximum over bit patterns: zeroed before the launch, as the engine does
-        if (kernel) *kernel = conv_post_kernel(dx.as<float>(), (long)Cin * L, L, Cin, K, da.as<float>(), L);
-        launch_conv_post_tanh(dx.as<float>(), (long)Cin * L, L, dw.as<float>(), Cin, K, B, L, dl.as<int>(), da.as<float>(), L, dp.as<unsigned>(), nullptr);
-        launch_pcm16(da.as<float>(), L, dp.as<unsigned>(), dl.as<int>(), B, L, dq.as<int16_t>(), L, nullptr, volumes ? dv.as<double>() : nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(audio, da.p, na * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(pcm, dq.p, na * 2, hipMemcpyDeviceToHost));
+        const float* dx = s.in(x, nx);
+        const float* dw = s.in(w, (size_t)Cin * K);
+        const int* dl = s.in(valid_len, (size_t)B);
+        const double* dv = s.in(volumes, (size_t)B);
+        float* da = s.inout(audio, na);
+        unsigned* dp = s.filled<unsigned>((size_t)B, 0);  // the peaks are an atomic maximum over bit patterns: zeroed before the launch, as the engine does
+        int16_t* dq = s.inout(pcm, na);
+        if (kernel) *kernel = conv_post_kernel(dx, (long)Cin * L, L, Cin, K, da, L);
+        launch_conv_post_tanh(dx, (long)Cin * L, L, dw, Cin, K, B, L, dl, da, L, dp, nullptr);
+        launch_pcm16(da, L, dp, dl, B, L, dq, L, nullptr, dv);
+        s.finish();
+        s.fetch(peaks, dp, (size_t)B);
     });
 }
 
@@ -296,25 +256,19 @@ int mi355vits_test_resample(int device, int B, int64_t row_stride, const float* 
         ResampleFilter f;
         if (!resample_design(in_hz, out_hz, f)) throw EngineError(MI355VITS_ERR_INVALID, "rate pair not supported");
         std::vector<int> tab(resample_tab_ints(B));
+        check_lens(lengths, B, row_stride, "row length out of range");
         for (int b = 0; b < B; ++b)
-            if (lengths[b] < 0 || lengths[b] > row_stride || resample_out_len(lengths[b], f.L, f.M) > y_stride)
-                throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
+            if (resample_out_len(lengths[b], f.L, f.M) > y_stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
         const long items = resample_fill_tab(f, lengths, B, tab.data());
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nx = (size_t)B * row_stride, ny = (size_t)B * y_stride;
-        DevBuf dx(nx * 4), dy(ny * 4), dl(B * 4), dt(tab.size() * 4), dc(f.table.size() * 4), dp(B * 4);
-        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, lengths, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dt.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dc.p, f.table.data(), f.table.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dy.p, 0xff, ny * 4));  // NaNs: the kernel writes every sample of y
-        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
-        launch_resample(f, dc.as<float>(), dx.as<float>(), (long)row_stride, dl.as<int>(), B, dt.as<int>(), items, dy.as<float>(),
-                        (long)y_stride, (int)y_stride, dp.as<unsigned>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        const size_t ny = (size_t)B * y_stride;
+        float* dy = s.filled<float>(ny, 0xff);  // NaNs: the kernel writes every sample of y
+        unsigned* dp = s.filled<unsigned>((size_t)B, 0);
+        launch_resample(f, s.in(f.table), s.in(x, (size_t)B * row_stride), (long)row_stride, s.in(lengths, (size_t)B), B, s.in(tab), items, dy,
+                        (long)y_stride, (int)y_stride, dp, nullptr);
+        s.finish();
+        s.fetch(y, dy, ny);
+        s.fetch(peaks, dp, (size_t)B);
         for (int b = 0; b < B; ++b) y_lengths[b] = tab[b];
     });
 }
@@ -343,27 +297,18 @@ int mi355vits_test_alignment(int device, int B, int T, const int32_t* frames, co
             }
             if (resample_out_len(acc * hop, L, M) > 0x7fffffffLL) throw EngineError(MI355VITS_ERR_INVALID, "row does not fit 32 bits");
         }
-        HIP_CHECK(hipSetDevice(device));
-        const size_t na = (size_t)B * row_stride;
-        DevBuf df(n * 4), dc(n * 4), dl(B * 4), da(na * 4), dal(B * 4), dout(5 * n * 4);
-        HIP_CHECK(hipMemcpy(df.p, frames, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dc.p, cum.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dal.p, alen, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dout.p, 0xff, 5 * n * 4));  // the kernel writes every element it is asked for
-        int* d = dout.as<int>();
-        launch_align(df.as<int>(), dc.as<int>(), dl.as<int>(), B, T, da.as<float>(), (long)row_stride, dal.as<int>(), hop, L, M, d, d + n,
-                     d + 2 * n, out_peak ? reinterpret_cast<float*>(d + 3 * n) : nullptr, out_peak ? reinterpret_cast<float*>(d + 4 * n) : nullptr,
-                     nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out_frames, d, n * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_start, d + n, n * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_samples, d + 2 * n, n * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        int* d = s.filled<int>(5 * n, 0xff);  // five planes; the kernel writes every element it is asked for
+        launch_align(s.in(frames, n), s.in(cum), s.in(len, (size_t)B), B, T, s.in(audio, (size_t)B * row_stride), (long)row_stride,
+                     s.in(alen, (size_t)B), hop, L, M, d, d + n, d + 2 * n, out_peak ? reinterpret_cast<float*>(d + 3 * n) : nullptr,
+                     out_peak ? reinterpret_cast<float*>(d + 4 * n) : nullptr, nullptr);
+        s.finish();
+        s.fetch(out_frames, d, n);
+        s.fetch(out_start, d + n, n);
+        s.fetch(out_samples, d + 2 * n, n);
         if (out_peak) {
-            HIP_CHECK(hipMemcpy(out_peak, d + 3 * n, n * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(out_rms, d + 4 * n, n * 4, hipMemcpyDeviceToHost));
+            s.fetch(out_peak, d + 3 * n, n);
+            s.fetch(out_rms, d + 4 * n, n);
         }
     });
 }
@@ -372,12 +317,11 @@ int mi355vits_lab_g711_encode(int law, const int16_t* in, long n, uint8_t* out) 
     return guarded(nullptr, [&] {
         if (!in || !out || n < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
         if (law != MI355VITS_ENC_ULAW && law != MI355VITS_ENC_ALAW) throw EngineError(MI355VITS_ERR_INVALID, "law must be MI355VITS_ENC_ULAW or MI355VITS_ENC_ALAW");
-        DevBuf di((size_t)n * 2), dout((size_t)n);
-        HIP_CHECK(hipMemcpy(di.p, in, (size_t)n * 2, hipMemcpyHostToDevice));
-        launch_g711_encode(law, di.as<int16_t>(), n, dout.as<uint8_t>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n, hipMemcpyDeviceToHost));
+        HookScope s;
+        uint8_t* dout = s.scratch<uint8_t>((size_t)n);
+        launch_g711_encode(law, s.in(in, (size_t)n), n, dout, nullptr);
+        s.finish();
+        s.fetch(out, dout, (size_t)n);
     });
 }
 
@@ -390,18 +334,18 @@ int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_f
         const long frames = flac_frames(n);
         if (first_frame < 0 || (long)first_frame + frames > FLAC_MAX_FRAME_NUMBER + 1) throw EngineError(MI355VITS_ERR_INVALID, "frame numbers must stay below 2^21");
         const size_t lead = n > 0 ? (reinterpret_cast<uintptr_t>(pcm) & 15) : 0;  // the host pointer's place behind a 16-byte boundary, kept
-        DevBuf din(lead + (size_t)n * 2 + 16), djob(sizeof(FlacJob)), dslots((size_t)frames * FLAC_SLOT_BYTES), dsizes(((size_t)frames + 1) * 4),
-            doff((size_t)frames * 8), dout(flac_out_capacity(frames, n));
-        int16_t* src = reinterpret_cast<int16_t*>(din.as<uint8_t>() + lead);
-        if (n > 0) HIP_CHECK(hipMemcpy(src, pcm, (size_t)n * 2, hipMemcpyHostToDevice));
+        HookScope s;
+        int16_t* src = reinterpret_cast<int16_t*>(s.scratch<uint8_t>(lead + (size_t)n * 2 + 16) + lead);
+        if (n > 0) s.put(src, pcm, (size_t)n);
         const FlacJob job = {src, n, first_frame, 0};
-        HIP_CHECK(hipMemcpy(djob.p, &job, sizeof(job), hipMemcpyHostToDevice));
-        launch_flac_frames(djob.as<FlacJob>(), 1, frames, rate, dslots.as<uint8_t>(), dsizes.as<int>(), nullptr);
-        launch_flac_gather(dslots.as<uint8_t>(), dsizes.as<int>(), doff.as<long long>(), frames, dout.as<uint8_t>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
+        uint8_t* dslots = s.scratch<uint8_t>((size_t)frames * FLAC_SLOT_BYTES);
+        int* dsizes = s.scratch<int>((size_t)frames + 1);
+        uint8_t* dout = s.scratch<uint8_t>(flac_out_capacity(frames, n));
+        launch_flac_frames(s.in(&job, 1), 1, frames, rate, dslots, dsizes, nullptr);
+        launch_flac_gather(dslots, dsizes, s.scratch<long long>((size_t)frames), frames, dout, nullptr);
+        s.finish();
         std::vector<int> sizes((size_t)frames + 1, 0);
-        if (frames > 0) HIP_CHECK(hipMemcpy(sizes.data(), dsizes.p, sizes.size() * 4, hipMemcpyDeviceToHost));
+        if (frames > 0) s.fetch(sizes.data(), dsizes, sizes.size());
         size_t data = 0;
         for (long f = 0; f < frames; ++f) {
             if (sizes[f] < 11 || sizes[f] > 16 + 2 * FLAC_BLOCK) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: frame " + std::to_string(f) + " has " + std::to_string(sizes[f]) + " bytes");
@@ -411,7 +355,7 @@ int mi355vits_lab_flac(const int16_t* pcm, long n, int32_t rate, int32_t first_f
         *n_bytes = FLAC_HEADER_BYTES + data;
         if (cap < *n_bytes) throw EngineError(MI355VITS_ERR_INVALID, "flac: the file has " + std::to_string(*n_bytes) + " bytes, out holds " + std::to_string(cap));
         flac_stream_header(out, rate, n, sizes.data(), frames);
-        if (data) HIP_CHECK(hipMemcpy(out + FLAC_HEADER_BYTES, dout.p, data, hipMemcpyDeviceToHost));
+        s.fetch(out + FLAC_HEADER_BYTES, dout, data);
         if (frame_sizes)
             for (long f = 0; f < frames; ++f) frame_sizes[f] = sizes[f];
     });
@@ -435,29 +379,30 @@ int mi355vits_lab_flac_jobs(const int16_t* const* pcm, const long* n, int32_t n_
             bound += flac_file_bound(n[j]);
             if (bound > 0x7fffffffL) throw EngineError(MI355VITS_ERR_INVALID, "the block's bound exceeds 2^31 - 1 bytes");
         }
-        DevBuf din(src_bytes + 16), djobs(sizeof(FlacJob) * (size_t)n_jobs), dslots((size_t)frames * FLAC_SLOT_BYTES + 16),
-            dsizes(flac_info_words(frames, n_jobs) * 4), dpre(((size_t)frames + 1) * 4), dftab(((size_t)frames + 1) * 8),
-            dhdr((size_t)FLAC_HDR_WORDS * n_jobs * 4), ditems(flac_gather_items(bound) * 4), djtab((size_t)FLAC_JTAB_ROWS * n_jobs * 4),
-            dout((size_t)bound + 16);
+        HookScope s;
+        uint8_t* din = s.scratch<uint8_t>(src_bytes + 16);
+        uint8_t* dslots = s.scratch<uint8_t>((size_t)frames * FLAC_SLOT_BYTES + 16);
+        int* dsizes = s.scratch<int>(flac_info_words(frames, n_jobs));
+        int2* dftab = s.scratch<int2>((size_t)frames + 1);
+        unsigned* dhdr = s.scratch<unsigned>((size_t)FLAC_HDR_WORDS * n_jobs);
+        int* ditems = s.scratch<int>(flac_gather_items(bound));
+        uint8_t* dout = s.filled<uint8_t>((size_t)bound + 16, 0xa5);  // the gather writes every byte of the block
         std::vector<FlacJob> jobs((size_t)n_jobs);
         long slot0 = 0;
         for (int j = 0; j < n_jobs; ++j) {
-            int16_t* src = reinterpret_cast<int16_t*>(din.as<uint8_t>() + at[(size_t)j]);
-            if (n[j] > 0) HIP_CHECK(hipMemcpy(src, pcm[j], (size_t)n[j] * 2, hipMemcpyHostToDevice));
+            int16_t* src = reinterpret_cast<int16_t*>(din + at[(size_t)j]);
+            if (n[j] > 0) s.put(src, pcm[j], (size_t)n[j]);
             jobs[(size_t)j] = FlacJob{src, n[j], 0, (int)slot0};
             slot0 += flac_frames(n[j]);
         }
-        HIP_CHECK(hipMemcpy(djobs.p, jobs.data(), sizeof(FlacJob) * jobs.size(), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dout.p, 0xa5, (size_t)bound + 16));  // the gather writes every byte of the block
-        launch_flac_frames(djobs.as<FlacJob>(), n_jobs, frames, rate, dslots.as<uint8_t>(), dsizes.as<int>(), nullptr);
-        launch_flac_place(djobs.as<FlacJob>(), n_jobs, frames, rate, 0, dsizes.as<int>(), dpre.as<unsigned>(), dftab.as<int2>(), dhdr.as<unsigned>(),
-                          ditems.as<int>(), djtab.as<int>(), nullptr);
-        launch_flac_gather_streams(n_jobs, frames, dslots.as<uint8_t>(), dsizes.as<int>(), dftab.as<int2>(), dhdr.as<unsigned>(), ditems.as<int>(), 0,
-                                   bound, dout.as<uint8_t>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
+        const FlacJob* djobs = s.in(jobs);
+        launch_flac_frames(djobs, n_jobs, frames, rate, dslots, dsizes, nullptr);
+        launch_flac_place(djobs, n_jobs, frames, rate, 0, dsizes, s.scratch<unsigned>((size_t)frames + 1), dftab, dhdr, ditems,
+                          s.scratch<int>((size_t)FLAC_JTAB_ROWS * n_jobs), nullptr);
+        launch_flac_gather_streams(n_jobs, frames, dslots, dsizes, dftab, dhdr, ditems, 0, bound, dout, nullptr);
+        s.finish();
         std::vector<int> info(flac_info_words(frames, n_jobs));
-        HIP_CHECK(hipMemcpy(info.data(), dsizes.p, info.size() * 4, hipMemcpyDeviceToHost));
+        s.fetch(info.data(), dsizes, info.size());
         const int* in = info.data() + frames;
         for (int j = 0; j < n_jobs; ++j) {
             offsets[j] = in[FLAC_INFO_WORDS * j + FLAC_INFO_BASE];
@@ -469,7 +414,7 @@ int mi355vits_lab_flac_jobs(const int16_t* const* pcm, const long* n, int32_t n_
         if (end != offsets[n_jobs - 1] + sizes_out[n_jobs - 1]) throw EngineError(MI355VITS_ERR_INTERNAL, "flac: the block's end differs from the last file's");
         *n_bytes = (size_t)end;
         if (cap < *n_bytes) throw EngineError(MI355VITS_ERR_INVALID, "flac: the block has " + std::to_string(*n_bytes) + " bytes, out holds " + std::to_string(cap));
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)end, hipMemcpyDeviceToHost));
+        s.fetch(out, dout, (size_t)end);
     });
 }
 
@@ -478,23 +423,15 @@ int mi355vits_lab_edges(const float* audio, long stride, const int32_t* lens, co
     return guarded(nullptr, [&] {
         if (!audio || !lens || !peaks || !s_first || !s_last || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
         if (!(ratio > 0.0f && ratio <= 1.0f)) throw EngineError(MI355VITS_ERR_INVALID, "ratio must be in (0, 1]");
-        long l_max = 0;
-        for (int b = 0; b < B; ++b) {
-            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
-            l_max = std::max<long>(l_max, lens[b]);
-        }
-        const size_t na = (size_t)B * stride;
-        DevBuf da(na * 4), dl((size_t)B * 4), dp((size_t)B * 4), dout((size_t)B * 8);
-        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dp.p, peaks, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dout.p, 0x5a, (size_t)B * 8));  // the launch initialises its words itself
-        int* d = dout.as<int>();
-        launch_edges(da.as<float>(), stride, dl.as<int>(), dp.as<unsigned>(), B, l_max, ratio, d, d + B, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(s_first, d, (size_t)B * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(s_last, d + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+        check_lens(lens, B, stride, "row length out of range");
+        const long l_max = *std::max_element(lens, lens + B);
+        HookScope s;
+        int* d = s.filled<int>((size_t)B * 2, 0x5a);  // the launch initialises its words itself
+        launch_edges(s.in(audio, (size_t)B * stride), stride, s.in(lens, (size_t)B), reinterpret_cast<const unsigned*>(s.in(peaks, (size_t)B)), B, l_max,
+                     ratio, d, d + B, nullptr);
+        s.finish();
+        s.fetch(s_first, d, (size_t)B);
+        s.fetch(s_last, d + B, (size_t)B);
     });
 }
 
@@ -504,26 +441,18 @@ int mi355vits_lab_loudness(const float* audio, long stride, const int32_t* lens,
         if (!audio || !lens || !lufs || !blocks || !gated || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
         LoudnessPlan lp;
         if (!loudness_plan(rate, lp)) throw EngineError(MI355VITS_ERR_INVALID, "rate " + std::to_string(rate) + " Hz is below " + std::to_string(LOUD_MIN_HZ) + " Hz");
-        long l_max = 0;
-        for (int b = 0; b < B; ++b) {
-            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
-            l_max = std::max<long>(l_max, lens[b]);
-        }
-        const size_t na = (size_t)B * stride;
+        check_lens(lens, B, stride, "row length out of range");
+        const long l_max = *std::max_element(lens, lens + B);
         const long ldE = std::max<long>(1, loudness_steps(l_max, lp.S));
-        DevBuf da(na * 4), dl((size_t)B * 4), dE((size_t)B * ldE * 8), dout((size_t)B * 16);
-        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dE.p, 0xff, (size_t)B * ldE * 8));  // NaN: the launch writes every energy it reads
-        HIP_CHECK(hipMemset(dout.p, 0x5a, (size_t)B * 16));
-        double* d_lufs = dout.as<double>();
+        HookScope s;
+        double* dE = s.filled<double>((size_t)B * ldE, 0xff);  // NaN: the launch writes every energy it reads
+        double* d_lufs = s.filled<double>((size_t)B * 2, 0x5a);  // B doubles, then 2 B ints
         int* d_blocks = reinterpret_cast<int*>(d_lufs + B);
-        launch_loudness(rate, da.as<float>(), stride, dl.as<int>(), B, l_max, dE.as<double>(), ldE, d_lufs, d_blocks, d_blocks + B, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(lufs, d_lufs, (size_t)B * 8, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(blocks, d_blocks, (size_t)B * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(gated, d_blocks + B, (size_t)B * 4, hipMemcpyDeviceToHost));
+        launch_loudness(rate, s.in(audio, (size_t)B * stride), stride, s.in(lens, (size_t)B), B, l_max, dE, ldE, d_lufs, d_blocks, d_blocks + B, nullptr);
+        s.finish();
+        s.fetch(lufs, d_lufs, (size_t)B);
+        s.fetch(blocks, d_blocks, (size_t)B);
+        s.fetch(gated, d_blocks + B, (size_t)B);
     });
 }
 
@@ -556,23 +485,18 @@ int mi355vits_lab_limit_env(const float* audio, long stride, const int32_t* lens
         long floats = 0;
         const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
         if (tiles < 0) throw EngineError(MI355VITS_ERR_INVALID, "the curves together exceed 2^31 - 1 samples");
-        DevBuf da(na * 4), dj(jobs.size() * sizeof(LimitJob)), ds(jobs.size() * sizeof(LimitStat)), dc((size_t)floats * 4);
-        HIP_CHECK(hipMemcpy(da.p, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dj.p, jobs.data(), jobs.size() * sizeof(LimitJob), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(ds.p, 0x5a, jobs.size() * sizeof(LimitStat)));  // the launch initialises its words itself
-        HIP_CHECK(hipMemset(dc.p, 0xff, (size_t)floats * 4));              // NaN: the launch writes every curve element
-        DevBuf de(env ? (size_t)floats * 8 : 8);
+        HookScope s;
+        LimitStat* ds = s.filled<LimitStat>(jobs.size(), 0x5a);  // the launch initialises its words itself
+        float* dc = s.filled<float>((size_t)floats, 0xff);       // NaN: the launch writes every curve element
+        double* de = env ? s.scratch<double>((size_t)floats) : nullptr;
         if (env)  // the jobs' envelopes one behind the other, as k_true_peak_env leaves them
-            for (const LimitJob& j : jobs)
-                HIP_CHECK(hipMemcpy(de.as<double>() + j.off, env + (size_t)j.row * stride, (size_t)j.n * 8, hipMemcpyHostToDevice));
-        launch_limit(dj.as<LimitJob>(), (int)jobs.size(), tiles, L, da.as<float>(), stride, ds.as<LimitStat>(), dc.as<float>(), nullptr,
-                     env ? de.as<double>() : nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
+            for (const LimitJob& j : jobs) s.put(de + j.off, env + (size_t)j.row * stride, (size_t)j.n);
+        launch_limit(s.in(jobs), (int)jobs.size(), tiles, L, s.in(audio, na), stride, ds, dc, nullptr, de);
+        s.finish();
         std::vector<LimitStat> st(jobs.size());
         std::vector<float> cv((size_t)floats);
-        HIP_CHECK(hipMemcpy(st.data(), ds.p, st.size() * sizeof(LimitStat), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(cv.data(), dc.p, cv.size() * 4, hipMemcpyDeviceToHost));
+        s.fetch(st.data(), ds, st.size());
+        s.fetch(cv.data(), dc, cv.size());
         for (size_t j = 0; j < jobs.size(); ++j) {
             const int b = jobs[j].row;
             memcpy(scale_out + (size_t)b * stride, cv.data() + jobs[j].off, (size_t)jobs[j].n * 4);
@@ -586,41 +510,33 @@ int mi355vits_lab_true_peak(const float* audio, long stride, const int32_t* lens
     return guarded(nullptr, [&] {
         if (!audio || !lens || !tp || B < 1 || stride < 1) throw EngineError(MI355VITS_ERR_INVALID, "null or empty argument");
         if (offset_floats < 0 || offset_floats > 3) throw EngineError(MI355VITS_ERR_INVALID, "offset_floats must be 0 .. 3");
-        long l_max = 0;
+        check_lens(lens, B, stride, "row length out of range");
+        const long l_max = *std::max_element(lens, lens + B);
         std::vector<LimitJob> jobs;  // the envelope form: one job per non-empty row
         for (int b = 0; b < B; ++b) {
-            if (lens[b] < 0 || lens[b] > stride) throw EngineError(MI355VITS_ERR_INVALID, "row length out of range");
-            l_max = std::max<long>(l_max, lens[b]);
             if (lens[b] < 1) continue;
             LimitJob j;
             j.g = j.c = j.U = 1.0; j.row = b; j.n = lens[b]; j.off = j.tile0 = 0;
             jobs.push_back(j);
         }
         const size_t na = (size_t)B * stride;
-        DevBuf da((na + 4) * 4), dl((size_t)B * 4), dt((size_t)B * 8);
-        HIP_CHECK(hipMemset(da.p, 0xff, (na + 4) * 4));  // NaN in front of the first row and behind the last
-        float* d_audio = da.as<float>() + offset_floats;
-        HIP_CHECK(hipMemcpy(d_audio, audio, na * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dt.p, 0x5a, (size_t)B * 8));  // the launch initialises its words itself
-        launch_true_peak(d_audio, stride, dl.as<int>(), B, l_max, dt.as<double>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(tp, dt.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+        HookScope s;
+        float* d_audio = s.filled<float>(na + 4, 0xff) + offset_floats;  // NaN in front of the first row and behind the last
+        s.put(d_audio, audio, na);
+        double* dt = s.filled<double>((size_t)B, 0x5a);  // the launch initialises its words itself
+        launch_true_peak(d_audio, stride, s.in(lens, (size_t)B), B, l_max, dt, nullptr);
+        s.finish();
+        s.fetch(tp, dt, (size_t)B);
         if (!env_out) return;
         for (size_t i = 0; i < na; ++i) env_out[i] = 0.0;
         if (jobs.empty()) return;
         long floats = 0;
         const long tiles = limit_place_jobs(jobs.data(), (int)jobs.size(), &floats);
         if (tiles < 0) throw EngineError(MI355VITS_ERR_INVALID, "the envelopes together exceed 2^31 - 1 samples");
-        DevBuf dj(jobs.size() * sizeof(LimitJob)), de((size_t)floats * 8);
-        HIP_CHECK(hipMemcpy(dj.p, jobs.data(), jobs.size() * sizeof(LimitJob), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(de.p, 0xff, (size_t)floats * 8));  // NaN: the launch writes every element
-        launch_true_peak_env(dj.as<LimitJob>(), (int)jobs.size(), tiles, d_audio, stride, de.as<double>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        for (const LimitJob& j : jobs)
-            HIP_CHECK(hipMemcpy(env_out + (size_t)j.row * stride, de.as<double>() + j.off, (size_t)j.n * 8, hipMemcpyDeviceToHost));
+        double* de = s.filled<double>((size_t)floats, 0xff);  // NaN: the launch writes every element
+        launch_true_peak_env(s.in(jobs), (int)jobs.size(), tiles, d_audio, stride, de, nullptr);
+        s.finish();
+        for (const LimitJob& j : jobs) s.fetch(env_out + (size_t)j.row * stride, de + j.off, (size_t)j.n);
     });
 }
 
@@ -653,73 +569,46 @@ int mi355vits_test_conv_transpose1d(int device, int impl, int B, int Cin, int Co
         if (!x || !w || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         convt_hook_check(impl, B, Cin, Cout, Tin, K, stride, in_len != nullptr);
         check_lens(in_len, B, Tin, "in_len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nx = (size_t)B * Cin * Tin, ny = (size_t)B * Cout * Tin * stride, nw = (size_t)Cin * Cout * K;
-        DevBuf dx(nx * 4), dy(ny * 4), dw(nw * 4), db(Cout * 4);
-        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));  // a position no kernel writes keeps the caller's value
-        if (impl == 3) {
-            // the resident-input polyphase kernels (k_ups_pl: 256 -> 128, 128 -> 64; k_ups64: 64 -> 32), MATH_BF16X3; a valid length per
-            // row is part of their contract (the engine always has one): in_len, or every row at full length
-            const int taps = convt_taps(K, stride);
-            std::vector<float> wv((size_t)stride * Cout * Cin * taps), bv((size_t)stride * Cout);
-            convt_to_polyphase(w, bias, Cin, Cout, K, stride, wv.data(), bv.data());
-            std::vector<uint32_t> pp(p16_packed_words(stride * Cout, Cin, taps));
-            pack_conv_weights_p16n(wv.data(), stride * Cout, Cin, taps, pp.data());
-            std::vector<int> lens = in_len ? std::vector<int>(in_len, in_len + B) : std::vector<int>((size_t)B, Tin);
-            DevBuf dpp(pp.size() * 4), dbias(bv.size() * 4), dlen((size_t)B * 4);
-            HIP_CHECK(hipMemcpy(dpp.p, pp.data(), pp.size() * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dbias.p, bv.data(), bv.size() * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dlen.p, lens.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-            ConvArgs u = convt_hook_args(impl, B, Cin, Cout, Tin, K, stride);
-            u.x = dx.as<float>();
-            u.y = dy.as<float>();
-            u.w = dpp.as<float>(); u.bias = dbias.as<float>(); u.in_len = dlen.as<int>(); u.in_len_host = lens.data();
-            u.in_slope = in_slope;
-            if (!ups_pl_supported(u)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input polyphase kernels");
-            launch_ups_pl(u, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
-        } else if (impl == 1 || impl == 2) {
-            // polyphase filters on the MFMA conv kernel (the path Engine uses); impl 2: the split-bf16 staged kernels
-            // (MATH_BF16X3; 64-channel chunks run the persistent producer / consumer form)
-            const int taps = convt_taps(K, stride);
-            std::vector<float> wv((size_t)stride * Cout * Cin * taps), bv((size_t)stride * Cout);
-            convt_to_polyphase(w, bias, Cin, Cout, K, stride, wv.data(), bv.data());
-            std::vector<float> pk(mfma_packed_floats(stride * Cout, Cin, taps));
-            pack_conv_weights_mfma(wv.data(), stride * Cout, Cin, taps, pk.data());
-            DevBuf dp(pk.size() * 4), dbias(bv.size() * 4);
-            HIP_CHECK(hipMemcpy(dp.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dbias.p, bv.data(), bv.size() * 4, hipMemcpyHostToDevice));
-            ConvArgs u = convt_hook_args(impl, B, Cin, Cout, Tin, K, stride);
-            u.x = dx.as<float>();
-            u.y = dy.as<float>();
-            u.w = dp.as<float>(); u.bias = dbias.as<float>();
-            u.in_slope = in_slope;
-            std::vector<uint32_t> b3;
-            std::unique_ptr<DevBuf> db3;
-            if (impl == 2) {
-                b3.resize(bf16x3_packed_words_mode(stride * Cout, Cin, taps, EPI_STD));
-                pack_conv_weights_bf16x3_mode(wv.data(), stride * Cout, Cin, taps, EPI_STD, 1, b3.data());
-                db3.reset(new DevBuf(b3.size() * 4));
-                HIP_CHECK(hipMemcpy(db3->p, b3.data(), b3.size() * 4, hipMemcpyHostToDevice));
-                u.wb3 = db3->as<float>();
-            }
-            launch_conv1d_mfma(u, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
-        } else {
-            HIP_CHECK(hipMemcpy(dw.p, w, nw * 4, hipMemcpyHostToDevice));
+        HookScope s(device);
+        const size_t nx = (size_t)B * Cin * Tin, ny = (size_t)B * Cout * Tin * stride;
+        const float* dx = s.in(x, nx);
+        float* dy = s.inout(y, ny);  // a position no kernel writes keeps the caller's value
+        if (impl == 0) {
             ConvTArgs a;
-            a.x = dx.as<float>(); a.x_bs = (long)Cin * Tin; a.x_ld = Tin;
-            a.y = dy.as<float>(); a.y_bs = (long)Cout * Tin * stride; a.y_ld = Tin * stride;
-            a.w = dw.as<float>();
-            if (bias) { HIP_CHECK(hipMemcpy(db.p, bias, Cout * 4, hipMemcpyHostToDevice)); a.bias = db.as<float>(); }
+            a.x = dx; a.x_bs = (long)Cin * Tin; a.x_ld = Tin;
+            a.y = dy; a.y_bs = (long)Cout * Tin * stride; a.y_ld = Tin * stride;
+            a.w = s.in(w, (size_t)Cin * Cout * K);
+            a.bias = s.in(bias, (size_t)Cout);
             a.B = B; a.Cin = Cin; a.Cout = Cout; a.Tin = Tin; a.K = K; a.stride = stride; a.pad = (K - stride) / 2;
             a.in_slope = in_slope;
             launch_conv_transpose1d(a, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
+        } else {
+            // the polyphase filters [stride * Cout, Cin, taps] and their bias
+            const int taps = convt_taps(K, stride), PC = stride * Cout;
+            std::vector<float> wv((size_t)PC * Cin * taps), bv((size_t)PC);
+            convt_to_polyphase(w, bias, Cin, Cout, K, stride, wv.data(), bv.data());
+            ConvArgs u = convt_hook_args(impl, B, Cin, Cout, Tin, K, stride);
+            u.x = dx;
+            u.y = dy;
+            u.bias = s.in(bv);
+            u.in_slope = in_slope;
+            if (impl == 3) {
+                // the resident-input polyphase kernels (k_ups_pl: 256 -> 128, 128 -> 64; k_ups64: 64 -> 32), MATH_BF16X3; a valid length per
+                // row is part of their contract (the engine always has one): in_len, or every row at full length
+                const std::vector<int> lens = in_len ? std::vector<int>(in_len, in_len + B) : std::vector<int>((size_t)B, Tin);
+                u.w = in_words(s, conv_weights_p16n(wv.data(), PC, Cin, taps));
+                u.in_len = s.in(lens); u.in_len_host = lens.data();
+                if (!ups_pl_supported(u)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the resident-input polyphase kernels");
+                launch_ups_pl(u, nullptr);
+            } else {
+                // polyphase filters on the MFMA conv kernel (the path Engine uses); impl 2: the split-bf16 staged kernels
+                // (MATH_BF16X3; 64-channel chunks run the persistent producer / consumer form)
+                u.w = s.in(conv_weights_mfma(wv.data(), PC, Cin, taps));
+                if (impl == 2) u.wb3 = in_words(s, conv_weights_bf16x3_staged(wv.data(), PC, Cin, taps));
+                launch_conv1d_mfma(u, nullptr);
+            }
         }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -728,30 +617,21 @@ int mi355vits_test_rel_attention(int device, int impl, int B, int T, int H, int 
     return guarded(nullptr, [&] {
         if (!qkv || !emb_rel_k || !emb_rel_v || !len || !out) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || T < 1 || n_heads < 1 || H % n_heads || W < 0) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
-        for (int b = 0; b < B; ++b)
-            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        check_lens(len, B, T, "len out of range");
         const int d = H / n_heads, nrel = 2 * W + 1;
         if (impl == 0 && T > rel_attention_valu_cap(H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "T beyond the VALU kernel's LDS row buffer");
         if (impl == 1 && !rel_attention_mfma_supported(T, H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the MFMA kernel");
         if (impl == 2 && !rel_attention_stream_supported(H, n_heads, W)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the streamed kernel");
         if (impl < 0 || impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nq = (size_t)B * 3 * H * T, no = (size_t)B * H * T, ne = (size_t)nrel * d;
-        DevBuf dq(nq * 4), dk(ne * 4), dv(ne * 4), dl((size_t)B * 4), dout(no * 4);
-        HIP_CHECK(hipMemcpy(dq.p, qkv, nq * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dk.p, emb_rel_k, ne * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dv.p, emb_rel_v, ne * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dout.p, out, no * 4, hipMemcpyHostToDevice));
-        if (impl == 0)
-            launch_rel_attention(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
-        else if (impl == 1)
-            launch_rel_attention_mfma(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
-        else
-            launch_rel_attention_stream(dq.as<float>(), dk.as<float>(), dv.as<float>(), dl.as<int>(), B, T, H, n_heads, W, dout.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.p, no * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        const float* dq = s.in(qkv, (size_t)B * 3 * H * T);
+        const float *dk = s.in(emb_rel_k, (size_t)nrel * d), *dv = s.in(emb_rel_v, (size_t)nrel * d);
+        const int* dl = s.in(len, (size_t)B);
+        float* dout = s.inout(out, (size_t)B * H * T);
+        if (impl == 0) launch_rel_attention(dq, dk, dv, dl, B, T, H, n_heads, W, dout, nullptr);
+        else if (impl == 1) launch_rel_attention_mfma(dq, dk, dv, dl, B, T, H, n_heads, W, dout, nullptr);
+        else launch_rel_attention_stream(dq, dk, dv, dl, B, T, H, n_heads, W, dout, nullptr);
+        s.finish();
     });
 }
 
@@ -762,119 +642,79 @@ int mi355vits_test_wn_layer(int device, const mi355vits_wn_test* t) {
         const int B = t->B, H = t->H, T = t->T, K = t->K, dil = t->dilation, Crs = t->Crs;
         if (B < 1 || H < 1 || T < 1 || K < 1 || (K % 2) == 0 || dil < 1 || (Crs != H && Crs != 2 * H)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
         if ((long)B * H * T >= 0x7fffffffL / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
-        for (int b = 0; b < B; ++b)
-            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        check_lens(t->len, B, T, "len out of range");
         if (t->impl < 0 || t->impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
         if (t->impl == 2 ? t->math != MATH_BF16X3 : t->math != MATH_F32) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 for impl 0 and 1, MATH_BF16X3 for impl 2");
         if (t->impl == 1 && !wn_layer_fused_supported(H, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused f32 layer");
         if (t->impl == 2 && !wn_layer_b3_supported(H, K, dil)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused split-bf16 layer");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t n = (size_t)B * H * T;
-        const std::vector<float> w_in(t->w_in, t->w_in + (size_t)2 * H * H * K), w_rs(t->w_rs, t->w_rs + (size_t)Crs * H);
-        DevBuf dh(n * 4), dho(n * 4), dsk(n * 4), du(n * 4), dbi((size_t)2 * H * 4), dbr((size_t)Crs * 4), dc((size_t)B * 2 * H * 4), dl((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dh.p, t->h_in, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dho.p, t->h_out, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dsk.p, t->skip, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dbi.p, t->b_in, (size_t)2 * H * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dbr.p, t->b_rs, (size_t)Crs * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (t->cond) HIP_CHECK(hipMemcpy(dc.p, t->cond, (size_t)B * 2 * H * 4, hipMemcpyHostToDevice));
         const long hbs = (long)H * T;
-        auto upload = [](const void* p, size_t bytes) {
-            std::unique_ptr<DevBuf> d(new DevBuf(bytes));
-            HIP_CHECK(hipMemcpy(d->p, p, bytes, hipMemcpyHostToDevice));
-            return d;
-        };
-        std::unique_ptr<DevBuf> dwi, dwr;
-        const float* h_result = dho.as<float>();
+        float* dh = s.in(t->h_in, n);
+        float* dho = s.in<float>(t->h_out, n);
+        float* dsk = s.inout(t->skip, n);
+        const float *dbi = s.in(t->b_in, (size_t)2 * H), *dbr = s.in(t->b_rs, (size_t)Crs), *dc = s.in(t->cond, (size_t)B * 2 * H);
+        const int* dl = s.in(t->len, (size_t)B);
+        const float* h_result = dho;
         if (t->impl == 0) {
             // Engine::coupling_layer's two launches: the gate conv h -> u (no input mask: the engine's h is zero past a row), then the
-            // res/skip conv u -> (h in place, skip); weights as Engine::add_conv_data stages them for Engine::pick_conv's MFMA_F32 / GENERIC
-            // (each conv on its own, as add_conv_data decides per conv: packed fragments where the MFMA kernel takes it, raw weights else)
+            // res/skip conv u -> (h in place, skip); weights in the forms Engine::pick_conv's MFMA_F32 / GENERIC read (each conv on its
+            // own, as Engine::add_conv_data decides per conv: packed fragments where the MFMA kernel takes it, raw weights else)
             const bool mfma_in = conv1d_mfma_supported(H, 2 * H, K, 1), mfma_rs = conv1d_mfma_supported(H, Crs, 1, 1);
-            if (mfma_in) {
-                std::vector<float> pi(mfma_packed_floats(2 * H, H, K), 0.0f);
-                pack_conv_weights_mfma_mode(w_in.data(), 2 * H, H, K, EPI_GATE, pi.data());
-                dwi = upload(pi.data(), pi.size() * 4);
-            } else {
-                dwi = upload(w_in.data(), w_in.size() * 4);
-            }
-            if (mfma_rs) {
-                std::vector<float> pr(mfma_packed_floats(Crs, H, 1), 0.0f);
-                pack_conv_weights_mfma_mode(w_rs.data(), Crs, H, 1, EPI_STD, pr.data());
-                dwr = upload(pr.data(), pr.size() * 4);
-            } else {
-                dwr = upload(w_rs.data(), w_rs.size() * 4);
-            }
+            float* du = s.scratch<float>(n);
             ConvArgs in;
-            in.x = dh.as<float>(); in.x_bs = hbs; in.x_ld = T;
-            in.y = du.as<float>(); in.y_bs = hbs; in.y_ld = T;
+            in.x = dh; in.x_bs = hbs; in.x_ld = T;
+            in.y = du; in.y_bs = hbs; in.y_ld = T;
             in.epi = EPI_GATE; in.H = H; in.dil = dil;
-            if (t->cond) { in.cond = dc.as<float>(); in.cond_bs = 2L * H; }
+            if (dc) { in.cond = dc; in.cond_bs = 2L * H; }
             in.B = B; in.T = T;
-            in.fixed_rule = 1; in.Cin = H; in.Cout = 2 * H; in.K = K; in.bias = dbi.as<float>(); in.pad = (K * dil - dil) / 2;
-            in.w = dwi->as<float>(); in.math = MATH_F32;
+            in.fixed_rule = 1; in.Cin = H; in.Cout = 2 * H; in.K = K; in.bias = dbi; in.pad = (K * dil - dil) / 2;
+            in.w = mfma_in ? s.in(conv_weights_mfma(t->w_in, 2 * H, H, K, EPI_GATE)) : s.in(t->w_in, (size_t)2 * H * H * K);
+            in.math = MATH_F32;
             ConvArgs rs;
-            rs.x = du.as<float>(); rs.x_bs = hbs; rs.x_ld = T;
-            rs.y = dh.as<float>(); rs.y_bs = hbs; rs.y_ld = T;
-            rs.y2 = dsk.as<float>(); rs.y2_bs = hbs; rs.y2_ld = T;
+            rs.x = du; rs.x_bs = hbs; rs.x_ld = T;
+            rs.y = dh; rs.y_bs = hbs; rs.y_ld = T;
+            rs.y2 = dsk; rs.y2_bs = hbs; rs.y2_ld = T;
             rs.epi = EPI_RESSKIP; rs.H = H; rs.skip_init = t->skip_init != 0;
-            rs.out_len = dl.as<int>();
+            rs.out_len = dl;
             rs.B = B; rs.T = T;
-            rs.fixed_rule = 1; rs.Cin = H; rs.Cout = Crs; rs.K = 1; rs.bias = dbr.as<float>(); rs.pad = 0;
-            rs.w = dwr->as<float>(); rs.math = MATH_F32;
+            rs.fixed_rule = 1; rs.Cin = H; rs.Cout = Crs; rs.K = 1; rs.bias = dbr; rs.pad = 0;
+            rs.w = mfma_rs ? s.in(conv_weights_mfma(t->w_rs, Crs, H, 1)) : s.in(t->w_rs, (size_t)Crs * H);
+            rs.math = MATH_F32;
             if (mfma_in) launch_conv1d_mfma(in, nullptr);
             else launch_conv1d_generic(in, nullptr);
             if (mfma_rs) launch_conv1d_mfma(rs, nullptr);
             else launch_conv1d_generic(rs, nullptr);
-            h_result = dh.as<float>();  // in place
+            h_result = dh;  // in place
         } else {
-            if (t->impl == 1) {
-                std::vector<float> pi(mfma_packed_floats(2 * H, H, K), 0.0f), pr(mfma_packed_floats(Crs, H, 1), 0.0f);
-                pack_conv_weights_mfma_mode(w_in.data(), 2 * H, H, K, EPI_GATE, pi.data());
-                pack_conv_weights_mfma_mode(w_rs.data(), Crs, H, 1, EPI_STD, pr.data());
-                dwi = upload(pi.data(), pi.size() * 4);
-                dwr = upload(pr.data(), pr.size() * 4);
-            } else if (wn_layer_b3_shape() != 32) {
-                // Engine::add_conv_data's packed_w16 of both convs (16x16x32 tiles)
-                std::vector<uint32_t> bi(w16_packed_words(2 * H, H, K)), br(w16_packed_words(Crs, H, 1));
-                pack_conv_weights_w16(w_in.data(), 2 * H, H, K, true, bi.data());
-                pack_conv_weights_w16(w_rs.data(), Crs, H, 1, false, br.data());
-                dwi = upload(bi.data(), bi.size() * 4);
-                dwr = upload(br.data(), br.size() * 4);
-            } else {
-                // MI355VITS_WN_SHAPE=32 (lab build, CPU model).  Engine::add_conv_data's packed_b3w: 32-row tile q of the gate conv = the tanh rows of channels 16 q .. 16 q + 15, then their
-                // sigmoid rows, as layout-1 planes; the res/skip conv in plain row order (packed_b3s)
-                const size_t row = (size_t)H * K;
-                std::vector<float> wg(w_in.size());
-                for (int q = 0; q < 2 * H / 32; ++q)
-                    for (int r = 0; r < 32; ++r) {
-                        const int src = (r < 16 ? 0 : H) + 16 * q + (r & 15);
-                        memcpy(wg.data() + ((size_t)32 * q + r) * row, w_in.data() + (size_t)src * row, row * sizeof(float));
-                    }
-                std::vector<uint32_t> bi(bf16x3_packed_words_mode(2 * H, H, K, EPI_STD)), br(bf16x3_packed_words_mode(Crs, H, 1, EPI_STD));
-                pack_conv_weights_bf16x3_mode(wg.data(), 2 * H, H, K, EPI_STD, 1, bi.data());
-                pack_conv_weights_bf16x3_mode(w_rs.data(), Crs, H, 1, EPI_STD, 1, br.data());
-                dwi = upload(bi.data(), bi.size() * 4);
-                dwr = upload(br.data(), br.size() * 4);
-            }
             WnArgs w;
-            w.h_in = dh.as<float>(); w.h_out = dho.as<float>(); w.h_bs = hbs; w.h_ld = T;
-            w.skip = dsk.as<float>(); w.s_bs = hbs; w.s_ld = T;
-            w.w_in = dwi->as<float>(); w.b_in = dbi.as<float>();
-            w.w_rs = dwr->as<float>(); w.b_rs = dbr.as<float>();
-            if (t->cond) { w.cond = dc.as<float>(); w.cond_bs = 2L * H; }
-            w.len = dl.as<int>();
+            w.h_in = dh; w.h_out = dho; w.h_bs = hbs; w.h_ld = T;
+            w.skip = dsk; w.s_bs = hbs; w.s_ld = T;
+            w.b_in = dbi; w.b_rs = dbr;
+            if (dc) { w.cond = dc; w.cond_bs = 2L * H; }
+            w.len = dl;
             w.B = B; w.H = H; w.T = T; w.K = K; w.dil = dil; w.Crs = Crs; w.skip_init = t->skip_init != 0;
-            if (t->impl == 2) { w.math = MATH_BF16X3; w.shape = wn_layer_b3_shape(); launch_wn_layer_b3(w, nullptr); }
-            else launch_wn_layer(w, nullptr);
+            if (t->impl == 1) {
+                w.w_in = s.in(conv_weights_mfma(t->w_in, 2 * H, H, K, EPI_GATE));
+                w.w_rs = s.in(conv_weights_mfma(t->w_rs, Crs, H, 1));
+                launch_wn_layer(w, nullptr);
+            } else {
+                w.math = MATH_BF16X3;
+                w.shape = wn_layer_b3_shape();
+                if (w.shape != 32) {  // ConvW::packed_w16 of both convs (16x16x32 tiles)
+                    w.w_in = in_words(s, conv_weights_w16(t->w_in, 2 * H, H, K, true));
+                    w.w_rs = in_words(s, conv_weights_w16(t->w_rs, Crs, H, 1, false));
+                } else {  // MI355VITS_WN_SHAPE=32 (lab build, CPU model): ConvW::packed_b3w of the gate conv, packed_b3s of the res/skip conv
+                    w.w_in = in_words(s, conv_weights_bf16x3_staged(conv_weights_gate_tiles(t->w_in, 2 * H, H, K).data(), 2 * H, H, K));
+                    w.w_rs = in_words(s, conv_weights_bf16x3_staged(t->w_rs, Crs, H, 1));
+                }
+                launch_wn_layer_b3(w, nullptr);
+            }
         }
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
+        s.finish();
         // impl 1 and 2: whatever the device's h_out holds now (Crs = H: the launch must have left it as it was); impl 0 works in place
         // on its copy of h, which a last layer leaves untouched: nothing to report then
-        if (t->impl != 0 || Crs == 2 * H) HIP_CHECK(hipMemcpy(t->h_out, h_result, n * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(t->skip, dsk.p, n * 4, hipMemcpyDeviceToHost));
+        if (t->impl != 0 || Crs == 2 * H) s.fetch(t->h_out, h_result, n);
     });
 }
 
@@ -897,127 +737,101 @@ int mi355vits_test_dds_stack(int device, const mi355vits_dds_stack_test* t) {
         if (t->spline && (!t->proj_w || !t->z)) throw EngineError(MI355VITS_ERR_INVALID, "the spline needs proj and z");
         if (t->spline && (t->nb < 2 || t->nb > 16)) throw EngineError(MI355VITS_ERR_INVALID, "spline: 2 <= nb <= 16");
         if (t->spline && PC != 3 * t->nb - 1) throw EngineError(MI355VITS_ERR_INVALID, "spline: proj_cout must be 3 nb - 1");
-        for (int b = 0; b < B; ++b)
-            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        check_lens(t->len, B, T, "len out of range");
         if (t->impl < 0 || t->impl > 3) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1, 2 or 3");
         if (t->impl == 3 ? !math_on_bf16(t->math) : t->math != MATH_F32)
             throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 for impl 0, 1 and 2, MATH_BF16X3 or MATH_BF16W for impl 3");
         if (t->impl == 1 && !dds_layer_fused_supported(C)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the fused DDS layer");
         if (t->impl >= 2 && !dds_stack_supported(C, K, NL, PC)) throw EngineError(MI355VITS_ERR_INVALID, "shape not supported by the DDS stack kernels");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t n = (size_t)B * C * T, nz = (size_t)B * 2 * T, no = (size_t)B * PC * T;
-        auto upload = [](const void* p, size_t bytes) {
-            std::unique_ptr<DevBuf> d(new DevBuf(bytes));
-            if (bytes) HIP_CHECK(hipMemcpy(d->p, p, bytes, hipMemcpyHostToDevice));
-            return d;
-        };
-        std::vector<std::unique_ptr<DevBuf>> keep;
-        auto vecf = [&](const float* p, size_t count) -> const float* {
-            keep.push_back(upload(p, count * 4));
-            return keep.back()->as<float>();
-        };
-        // a dense 1x1 conv's weights [Cout, C, 1] in the format of the chosen path, as Engine::add_conv_data stages them
-        const bool b3 = t->impl == 3;
+        // a dense 1x1 conv's weights [Cout, C, 1] in the form the chosen path reads (ConvW::packed_b3s, packed, raw)
         auto conv_mfma = [&](int Cout) { return conv1d_mfma_supported(C, Cout, 1, 1); };
         auto dense = [&](const float* w, int Cout) -> const float* {
-            if (b3) {
-                std::vector<uint32_t> p(bf16x3_packed_words_mode(Cout, C, 1, EPI_STD), 0u);
-                pack_conv_weights_bf16x3_mode(w, Cout, C, 1, EPI_STD, 1, p.data());
-                keep.push_back(upload(p.data(), p.size() * 4));
-            } else if (t->impl != 0 || conv_mfma(Cout)) {
-                std::vector<float> p(mfma_packed_floats(Cout, C, 1), 0.0f);
-                pack_conv_weights_mfma_mode(w, Cout, C, 1, EPI_STD, p.data());
-                keep.push_back(upload(p.data(), p.size() * 4));
-            } else {
-                keep.push_back(upload(w, (size_t)Cout * C * 4));
-            }
-            return keep.back()->as<float>();
+            if (t->impl == 3) return in_words(s, conv_weights_bf16x3_staged(w, Cout, C, 1));
+            if (t->impl != 0 || conv_mfma(Cout)) return s.in(conv_weights_mfma(w, Cout, C, 1));
+            return s.in(w, (size_t)Cout * C);
         };
-        DevBuf dsrc(n * 4), dxo(n * 4), dz(nz * 4), dout(no * 4), dl((size_t)B * 4), dcond((size_t)B * C * 4);
-        HIP_CHECK(hipMemcpy(dsrc.p, t->src, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dxo.p, t->x_out, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (t->z) HIP_CHECK(hipMemcpy(dz.p, t->z, nz * 4, hipMemcpyHostToDevice));
-        if (PC) HIP_CHECK(hipMemcpy(dout.p, t->out, no * 4, hipMemcpyHostToDevice));
-        if (t->cond) HIP_CHECK(hipMemcpy(dcond.p, t->cond, (size_t)B * C * 4, hipMemcpyHostToDevice));
-        const float* pre_w = t->pre_mode == DDS_PRE_AFFINE ? vecf(t->pre_w, C) : dense(t->pre_w, C);
-        const float* pre_b = vecf(t->pre_b, C);
+        const float* dsrc = s.in(t->src, n);
+        float* dxo = s.inout(t->x_out, n);
+        float* dout = PC ? s.inout(t->out, no) : nullptr;
+        float* dz = s.inout(t->z, nz);
+        const int* dl = s.in(t->len, (size_t)B);
+        const float* dcond = s.in(t->cond, (size_t)B * C);
+        const float* pre_w = t->pre_mode == DDS_PRE_AFFINE ? s.in(t->pre_w, (size_t)C) : dense(t->pre_w, C);
+        const float* pre_b = s.in(t->pre_b, (size_t)C);
         const float *dw_w[DDS_STACK_MAX_LAYERS], *dw_b[DDS_STACK_MAX_LAYERS], *g1[DDS_STACK_MAX_LAYERS], *b1[DDS_STACK_MAX_LAYERS];
         const float *w1[DDS_STACK_MAX_LAYERS], *bb[DDS_STACK_MAX_LAYERS], *g2[DDS_STACK_MAX_LAYERS], *b2[DDS_STACK_MAX_LAYERS];
         for (int i = 0; i < NL; ++i) {
-            dw_w[i] = vecf(t->dw_w[i], (size_t)C * K); dw_b[i] = vecf(t->dw_b[i], C);
-            g1[i] = vecf(t->g1[i], C); b1[i] = vecf(t->b1[i], C);
-            w1[i] = dense(t->w1x1[i], C); bb[i] = vecf(t->bias1x1[i], C);
-            g2[i] = vecf(t->g2[i], C); b2[i] = vecf(t->b2[i], C);
+            dw_w[i] = s.in(t->dw_w[i], (size_t)C * K); dw_b[i] = s.in(t->dw_b[i], (size_t)C);
+            g1[i] = s.in(t->g1[i], (size_t)C); b1[i] = s.in(t->b1[i], (size_t)C);
+            w1[i] = dense(t->w1x1[i], C); bb[i] = s.in(t->bias1x1[i], (size_t)C);
+            g2[i] = s.in(t->g2[i], (size_t)C); b2[i] = s.in(t->b2[i], (size_t)C);
         }
         const float* proj_w = PC ? dense(t->proj_w, PC) : nullptr;
-        const float* proj_b = PC ? vecf(t->proj_b, PC) : nullptr;
+        const float* proj_b = PC ? s.in(t->proj_b, (size_t)PC) : nullptr;
         if (t->impl >= 2) {
             DdsStackArgs a;
-            a.src = dsrc.as<float>(); a.pre_mode = t->pre_mode; a.pre_w = pre_w; a.pre_b = pre_b;
-            if (t->cond) { a.cond = dcond.as<float>(); a.cond_bs = C; }
-            a.z = t->z ? dz.as<float>() : nullptr; a.zch = t->zch;
+            a.src = dsrc; a.pre_mode = t->pre_mode; a.pre_w = pre_w; a.pre_b = pre_b;
+            if (dcond) { a.cond = dcond; a.cond_bs = C; }
+            a.z = dz; a.zch = t->zch;
             a.n_layers = NL; a.K = K;
             for (int i = 0; i < NL; ++i) {
                 a.dw_w[i] = dw_w[i]; a.dw_b[i] = dw_b[i]; a.g1[i] = g1[i]; a.b1[i] = b1[i];
                 a.w1x1[i] = w1[i]; a.bias1x1[i] = bb[i]; a.g2[i] = g2[i]; a.b2[i] = b2[i];
             }
-            a.x_out = dxo.as<float>();
+            a.x_out = dxo;
             a.proj_w = proj_w; a.proj_b = proj_b; a.proj_cout = PC;
-            a.out = PC ? dout.as<float>() : nullptr;
+            a.out = dout;
             a.spline = t->spline ? 1 : 0; a.nb = t->nb; a.tail = t->tail; a.inv_sqrt_fc = t->inv_sqrt_fc;
-            a.len = dl.as<int>(); a.B = B; a.T = T; a.math = t->math;
+            a.len = dl; a.B = B; a.T = T; a.math = t->math;
             launch_dds_stack(a, C, nullptr);
         } else {
             // Engine::duration_predictor's launches without the stack kernels: x lives in d0 (d1 / d2: Engine::dds's scratch)
-            DevBuf d0(n * 4), d1(n * 4), d2(n * 4);
+            float *d0 = s.scratch<float>(n), *d1 = s.scratch<float>(n), *d2 = s.scratch<float>(n);
             const long bs = (long)C * T;
             auto conv1x1 = [&](const float* x, float* y, const float* w, const float* bias, int Cout, bool masked) {
                 ConvArgs a;
                 a.x = x; a.x_bs = bs; a.x_ld = T;
                 a.y = y; a.y_bs = (long)Cout * T; a.y_ld = T;
                 a.B = B; a.T = T; a.Cin = C; a.Cout = Cout; a.K = 1; a.bias = bias; a.pad = 0; a.w = w; a.math = MATH_F32;
-                if (masked) { a.in_len = dl.as<int>(); a.out_len = dl.as<int>(); }
+                if (masked) { a.in_len = dl; a.out_len = dl; }
                 return a;
             };
             auto run_conv = [&](const ConvArgs& a) {
                 if (conv_mfma(a.Cout)) launch_conv1d_mfma(a, nullptr);
                 else launch_conv1d_generic(a, nullptr);
             };
-            float* X = d0.as<float>();
+            float* X = d0;
             if (t->pre_mode == DDS_PRE_AFFINE) {
-                launch_convflow_pre(dz.as<float>(), t->zch, pre_w, pre_b, dsrc.as<float>(), B, C, T, X, nullptr);
+                launch_convflow_pre(dz, t->zch, pre_w, pre_b, dsrc, B, C, T, X, nullptr);
             } else {
-                ConvArgs a = conv1x1(dsrc.as<float>(), X, pre_w, pre_b, C, false);
-                if (t->cond) { a.cond = dcond.as<float>(); a.cond_bs = C; }
+                ConvArgs a = conv1x1(dsrc, X, pre_w, pre_b, C, false);
+                if (dcond) { a.cond = dcond; a.cond_bs = C; }
                 run_conv(a);
             }
             int dil = 1;
             for (int i = 0; i < NL; ++i) {
                 if (t->impl == 1) {  // x ping-pongs (k_dds_layer reads its neighbours' OLD columns)
-                    float* dst = X == d0.as<float>() ? d1.as<float>() : d0.as<float>();
-                    launch_dds_layer(X, dst, dw_w[i], dw_b[i], g1[i], b1[i], w1[i], bb[i], g2[i], b2[i], dl.as<int>(), B, C, T, K, dil, nullptr);
+                    float* dst = X == d0 ? d1 : d0;
+                    launch_dds_layer(X, dst, dw_w[i], dw_b[i], g1[i], b1[i], w1[i], bb[i], g2[i], b2[i], dl, B, C, T, K, dil, nullptr);
                     X = dst;
                 } else {
-                    launch_dds_dwconv_ln_gelu(X, dw_w[i], dw_b[i], g1[i], b1[i], dl.as<int>(), B, C, T, K, dil, d1.as<float>(), nullptr);
-                    run_conv(conv1x1(d1.as<float>(), d2.as<float>(), w1[i], bb[i], C, false));
+                    launch_dds_dwconv_ln_gelu(X, dw_w[i], dw_b[i], g1[i], b1[i], dl, B, C, T, K, dil, d1, nullptr);
+                    run_conv(conv1x1(d1, d2, w1[i], bb[i], C, false));
                     LNArgs ln;
-                    ln.x = d2.as<float>(); ln.y = X; ln.add_to = X; ln.gelu = 1;
+                    ln.x = d2; ln.y = X; ln.add_to = X; ln.gelu = 1;
                     ln.B = B; ln.C = C; ln.T = T; ln.gamma = g2[i]; ln.beta = b2[i];
                     launch_layernorm(ln, nullptr);
                 }
                 dil *= K;
             }
-            HIP_CHECK(hipMemcpyAsync(dxo.p, X, n * 4, hipMemcpyDeviceToDevice, nullptr));
-            if (PC) run_conv(conv1x1(X, dout.as<float>(), proj_w, proj_b, PC, true));
+            HIP_CHECK(hipMemcpyAsync(dxo, X, n * 4, hipMemcpyDeviceToDevice, nullptr));
+            if (PC) run_conv(conv1x1(X, dout, proj_w, proj_b, PC, true));
             if (t->spline)
-                launch_spline_inverse(dz.as<float>(), t->zch, dout.as<float>(), dl.as<int>(), B, T, t->nb, t->tail, t->inv_sqrt_fc, nullptr);
+                launch_spline_inverse(dz, t->zch, dout, dl, B, T, t->nb, t->tail, t->inv_sqrt_fc, nullptr);
         }
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->x_out, dxo.p, n * 4, hipMemcpyDeviceToHost));
-        if (PC) HIP_CHECK(hipMemcpy(t->out, dout.p, no * 4, hipMemcpyDeviceToHost));
-        if (t->z) HIP_CHECK(hipMemcpy(t->z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -1026,18 +840,11 @@ int mi355vits_test_spline_inverse(int device, int B, int T, int nb, int ch_x0, f
     return guarded(nullptr, [&] {
         if (!theta || !len || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || T < 1 || nb < 2 || nb > 16 || (ch_x0 != 0 && ch_x0 != 1)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape (2 <= nb <= 16)");
-        for (int b = 0; b < B; ++b)
-            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nt = (size_t)B * (3 * nb - 1) * T, nz = (size_t)B * 2 * T;
-        DevBuf dt(nt * 4), dz(nz * 4), dl((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dt.p, theta, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        launch_spline_inverse(dz.as<float>(), ch_x0, dt.as<float>(), dl.as<int>(), B, T, nb, tail, inv_sqrt_fc, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+        check_lens(len, B, T, "len out of range");
+        HookScope s(device);
+        launch_spline_inverse(s.inout(z, (size_t)B * 2 * T), ch_x0, s.in(theta, (size_t)B * (3 * nb - 1) * T), s.in(len, (size_t)B), B, T, nb, tail,
+                              inv_sqrt_fc, nullptr);
+        s.finish();
     });
 }
 
@@ -1046,27 +853,15 @@ int mi355vits_test_durations(int device, int B, int T, int ch, float ea_m, float
     return guarded(nullptr, [&] {
         if (!z || !len || !scales || !logw || !w_ceil || !cum || !ylen) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || T < 1 || (ch != 0 && ch != 1)) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
-        for (int b = 0; b < B; ++b)
-            if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nz = (size_t)B * 2 * T, nt = (size_t)B * T;
-        DevBuf dz(nz * 4), dl((size_t)B * 4), df(nt * 4), ds((size_t)B * 3 * 4), dlw(nt * 4), dw(nt * 4), dc(nt * 4), dy((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
-        if (forced) HIP_CHECK(hipMemcpy(df.p, forced, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dlw.p, logw, nt * 4, hipMemcpyHostToDevice));  // the prior contents: a missing write shows
-        HIP_CHECK(hipMemcpy(dw.p, w_ceil, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dc.p, cum, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
-        launch_durations(dz.as<float>(), ch, ea_m, ea_logs, dl.as<int>(), forced ? df.as<int>() : nullptr, B, T, ds.as<float>(),
-                         dlw.as<float>(), dw.as<int>(), dc.as<int>(), dy.as<int>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(logw, dlw.p, nt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(w_ceil, dw.p, nt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(cum, dc.p, nt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(ylen, dy.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        check_lens(len, B, T, "len out of range");
+        HookScope s(device);
+        const size_t nt = (size_t)B * T;
+        // the outputs' prior contents go up: a missing write shows
+        float* dlw = s.inout(logw, nt);
+        int *dw = s.inout(w_ceil, nt), *dc = s.inout(cum, nt), *dy = s.inout(ylen, (size_t)B);
+        launch_durations(s.in(z, (size_t)B * 2 * T), ch, ea_m, ea_logs, s.in(len, (size_t)B), s.in(forced, nt), B, T, s.in(scales, (size_t)B * 3), dlw, dw,
+                         dc, dy, nullptr);
+        s.finish();
     });
 }
 
@@ -1079,34 +874,19 @@ int mi355vits_test_fit_durations(int device, int B, int T, const float* u, const
             if (len[b] < 0 || len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
             if (target && (target[b] < 0 || target[b] > DURATION_FRAME_CAP)) throw EngineError(MI355VITS_ERR_INVALID, "target out of range");
         }
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nt = (size_t)B * T, nb = (size_t)B * 4;
-        DevBuf du(nt * 4), dl(nb), dm(nt * 4), dt(nb), duo(nt * 4), dw(nt * 4), dc(nt * 4), dy(nb), dfa(nb), dst(nb);
-        HIP_CHECK(hipMemcpy(du.p, u, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, nb, hipMemcpyHostToDevice));
-        if (min_frames) HIP_CHECK(hipMemcpy(dm.p, min_frames, nt * 4, hipMemcpyHostToDevice));
-        if (target) HIP_CHECK(hipMemcpy(dt.p, target, nb, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, frames, nt * 4, hipMemcpyHostToDevice));  // the prior contents: a missing write shows
-        HIP_CHECK(hipMemcpy(dc.p, cum, nt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, ylen, nb, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dfa.p, factor, nb, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dst.p, status, nb, hipMemcpyHostToDevice));
+        HookScope s(device);
+        const size_t nt = (size_t)B * T;
         DurTimedArgs a;
-        a.u_in = du.as<float>();
-        a.len = dl.as<int>(); a.B = B; a.T = T;
-        a.min_frames = min_frames ? dm.as<int>() : nullptr;
-        a.target = target ? dt.as<int>() : nullptr;
-        a.u = duo.as<float>();
-        a.w_ceil = dw.as<int>(); a.cum = dc.as<int>(); a.ylen = dy.as<int>();
-        a.factor = dfa.as<float>(); a.status = dst.as<int>();
+        a.u_in = s.in(u, nt);
+        a.len = s.in(len, (size_t)B); a.B = B; a.T = T;
+        a.min_frames = s.in(min_frames, nt);
+        a.target = s.in(target, (size_t)B);
+        a.u = s.scratch<float>(nt);
+        // the outputs' prior contents go up: a missing write shows
+        a.w_ceil = s.inout(frames, nt); a.cum = s.inout(cum, nt); a.ylen = s.inout(ylen, (size_t)B);
+        a.factor = s.inout(factor, (size_t)B); a.status = s.inout(status, (size_t)B);
         launch_durations_timed(a, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(frames, dw.p, nt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(cum, dc.p, nt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(ylen, dy.p, nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(factor, dfa.p, nb, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(status, dst.p, nb, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -1117,17 +897,11 @@ int mi355vits_test_speaker_cond(int device, int B, int gin, int n_speakers, int 
         if (B < 1 || gin < 1 || gin > 8192 || n_speakers < 1 || Cout < 1 || out_floats < (size_t)B * Cout) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
         for (int b = 0; b < B; ++b)
             if (sid[b] < 0 || sid[b] >= n_speakers) throw EngineError(MI355VITS_ERR_INVALID, "sid out of range");
-        HIP_CHECK(hipSetDevice(device));
-        DevBuf de((size_t)n_speakers * gin * 4), ds((size_t)B * 8), dw((size_t)Cout * gin * 4), db((size_t)Cout * 4), dout(out_floats * 4);
-        HIP_CHECK(hipMemcpy(de.p, emb_g, (size_t)n_speakers * gin * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ds.p, sid, (size_t)B * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, w, (size_t)Cout * gin * 4, hipMemcpyHostToDevice));
-        if (bias) HIP_CHECK(hipMemcpy(db.p, bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dout.p, out, out_floats * 4, hipMemcpyHostToDevice));  // the prior contents: a missing or stray write shows
-        launch_speaker_cond(de.as<float>(), ds.as<long long>(), dw.as<float>(), bias ? db.as<float>() : nullptr, B, gin, Cout, dout.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.p, out_floats * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        float* dout = s.inout(out, out_floats);  // the prior contents: a missing or stray write shows
+        launch_speaker_cond(s.in(emb_g, (size_t)n_speakers * gin), reinterpret_cast<const long long*>(s.in(sid, (size_t)B)), s.in(w, (size_t)Cout * gin),
+                            s.in(bias, (size_t)Cout), B, gin, Cout, dout, nullptr);
+        s.finish();
     });
 }
 
@@ -1147,39 +921,25 @@ int mi355vits_test_speaker_cond_mix(int device, const mi355vits_speaker_mix_test
         }
         for (int q = 0; q < nj; ++q)
             if (!t->w[q] || !t->out[q] || t->Cout[q] < 1 || t->out_floats[q] < (size_t)B * t->Cout[q]) throw EngineError(MI355VITS_ERR_INVALID, "bad job");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t ne = mix ? (size_t)t->n_speakers * gin : 0, nk = mix ? (size_t)B * K : 0, nv = mix ? 0 : (size_t)B * gin;
-        DevBuf de(ne * 4), ds(nk * 8), dm(nk * 4), dv(nv * 4), dg(t->g_floats * 4);
-        if (mix) {
-            HIP_CHECK(hipMemcpy(de.p, t->emb_g, ne * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(ds.p, t->mix_sid, nk * 8, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dm.p, t->mix_weight, nk * 4, hipMemcpyHostToDevice));
-        } else {
-            HIP_CHECK(hipMemcpy(dv.p, t->vectors, nv * 4, hipMemcpyHostToDevice));
-        }
-        HIP_CHECK(hipMemcpy(dg.p, t->g, t->g_floats * 4, hipMemcpyHostToDevice));  // the prior contents: a missing or stray write shows
-        std::vector<std::unique_ptr<DevBuf>> dw, db, dout;
+        HookScope s(device);
         SpeakerMixArgs a;
-        a.B = B; a.gin = gin; a.K = K; a.g = dg.as<float>(); a.n_jobs = nj;
-        if (mix) { a.emb_g = de.as<float>(); a.sid = ds.as<long long>(); a.weight = dm.as<float>(); } else a.vectors = dv.as<float>();
+        a.B = B; a.gin = gin; a.K = K; a.n_jobs = nj;
+        a.g = s.inout(t->g, t->g_floats);  // the prior contents: a missing or stray write shows
+        if (mix) {
+            a.emb_g = s.in(t->emb_g, (size_t)t->n_speakers * gin);
+            a.sid = reinterpret_cast<const long long*>(s.in(t->mix_sid, (size_t)B * K));
+            a.weight = s.in(t->mix_weight, (size_t)B * K);
+        } else {
+            a.vectors = s.in(t->vectors, (size_t)B * gin);
+        }
         for (int q = 0; q < nj; ++q) {
-            const size_t nw = (size_t)t->Cout[q] * gin;
-            dw.emplace_back(new DevBuf(nw * 4));
-            db.emplace_back(new DevBuf((size_t)t->Cout[q] * 4));
-            dout.emplace_back(new DevBuf(t->out_floats[q] * 4));
-            HIP_CHECK(hipMemcpy(dw[q]->p, t->w[q], nw * 4, hipMemcpyHostToDevice));
-            if (t->bias[q]) HIP_CHECK(hipMemcpy(db[q]->p, t->bias[q], (size_t)t->Cout[q] * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dout[q]->p, t->out[q], t->out_floats[q] * 4, hipMemcpyHostToDevice));
-            a.jobs[q].w = dw[q]->as<float>();
-            a.jobs[q].bias = t->bias[q] ? db[q]->as<float>() : nullptr;
+            a.jobs[q].w = s.in(t->w[q], (size_t)t->Cout[q] * gin);
+            a.jobs[q].bias = s.in(t->bias[q], (size_t)t->Cout[q]);
             a.jobs[q].Cout = t->Cout[q];
-            a.jobs[q].out = dout[q]->as<float>();
+            a.jobs[q].out = s.inout(t->out[q], t->out_floats[q]);
         }
         launch_speaker_cond_mix(a, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->g, dg.p, t->g_floats * 4, hipMemcpyDeviceToHost));
-        for (int q = 0; q < nj; ++q) HIP_CHECK(hipMemcpy(t->out[q], dout[q]->p, t->out_floats[q] * 4, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -1203,22 +963,14 @@ int mi355vits_test_levels(int device, int B, int T, int hop, const int32_t* cum,
             if (ramp && (ramp[b] < 0 || ramp[b] > LEVELS_MAX_RAMP)) throw EngineError(MI355VITS_ERR_INVALID, "ramp out of range");
             l_max = std::max<long>(l_max, (long)n);
         }
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t nbt = (size_t)B * T;
-        DevBuf dc(nbt * 4), dl((size_t)B * 4), dg(nbt * 4), dr((size_t)B * 4), da((size_t)B * 4), dx(audio_floats * 4), dp((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dg.p, gain, nbt * 4, hipMemcpyHostToDevice));
-        if (ramp) HIP_CHECK(hipMemcpy(dr.p, ramp, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(da.p, alen, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dx.p, audio, audio_floats * 4, hipMemcpyHostToDevice));  // everything: a stray write shows
-        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
-        launch_levels(dc.as<int>(), dl.as<int>(), dg.as<float>(), ramp ? dr.as<int>() : nullptr, B, T, hop, dx.as<float>(), (long)audio_bs,
-                      da.as<int>(), l_max, dp.as<unsigned>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(audio, dx.p, audio_floats * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        float* dx = s.inout(audio, audio_floats);  // everything: a stray write shows
+        unsigned* dp = s.filled<unsigned>((size_t)B, 0);
+        launch_levels(s.in(cum, nbt), s.in(len, (size_t)B), s.in(gain, nbt), s.in(ramp, (size_t)B), B, T, hop, dx, (long)audio_bs, s.in(alen, (size_t)B),
+                      l_max, dp, nullptr);
+        s.finish();
+        s.fetch(peaks, dp, (size_t)B);
     });
 }
 
@@ -1260,18 +1012,15 @@ int mi355vits_test_pitch_plan(int device, int B, int T, int hop, const int32_t* 
     return guarded(nullptr, [&] {
         if (!tq || !wc || !wlen) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         check_pitch_inputs(B, T, hop, cum, len, ratio, 0);
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t nbt = (size_t)B * T;
-        DevBuf dc(nbt * 4), dl((size_t)B * 4), dr(nbt * 4), dq(nbt * 8), dw(nbt * 4), dn((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (ratio) HIP_CHECK(hipMemcpy(dr.p, ratio, nbt * 4, hipMemcpyHostToDevice));
-        launch_pitch_plan(dc.as<int>(), dl.as<int>(), ratio ? dr.as<float>() : nullptr, B, T, hop, dq.as<long long>(), dw.as<int>(), dn.as<int>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(tq, dq.p, nbt * 8, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(wc, dw.p, nbt * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(wlen, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        long long* dq = s.scratch<long long>(nbt);
+        int *dw = s.scratch<int>(nbt), *dn = s.scratch<int>((size_t)B);
+        launch_pitch_plan(s.in(cum, nbt), s.in(len, (size_t)B), s.in(ratio, nbt), B, T, hop, dq, dw, dn, nullptr);
+        s.finish();
+        s.fetch(tq, dq, nbt);
+        s.fetch(wc, dw, nbt);
+        s.fetch(wlen, dn, (size_t)B);
     });
 }
 
@@ -1283,41 +1032,32 @@ int mi355vits_test_pitch(int device, int B, int T, int hop, const int32_t* cum, 
         if (x_bs < 1 || y_bs < 1 || y_ld < 1 || y_ld > y_bs || B < 1 || x_floats < (size_t)B * (size_t)x_bs || y_floats < (size_t)B * (size_t)y_bs)
             throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
         check_pitch_inputs(B, T, hop, cum, len, ratio, x_bs);
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t nbt = (size_t)B * T;
-        const std::vector<float>& h = pitch_table();
         std::vector<int> alen(B);
         for (int b = 0; b < B; ++b) {
             const int frames = len[b] > 0 ? cum[(size_t)b * T + len[b] - 1] : 0;
             alen[b] = hop * (frames < 1 ? 1 : frames);
         }
-        DevBuf dc(nbt * 4), dl((size_t)B * 4), dr(nbt * 4), dq(nbt * 8), dw(nbt * 4), dn((size_t)B * 4), da((size_t)B * 4),
-            dx(x_floats * 4), dy(y_floats * 4), dp((size_t)B * 4), dh(h.size() * 4);
-        HIP_CHECK(hipMemcpy(dc.p, cum, nbt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (ratio) HIP_CHECK(hipMemcpy(dr.p, ratio, nbt * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(da.p, alen.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dx.p, x, x_floats * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, y, y_floats * 4, hipMemcpyHostToDevice));  // everything: a stray write shows
-        HIP_CHECK(hipMemcpy(dh.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dp.p, 0, (size_t)B * 4));
-        const float* dratio = ratio ? dr.as<float>() : nullptr;
-        launch_pitch_plan(dc.as<int>(), dl.as<int>(), dratio, B, T, hop, dq.as<long long>(), dw.as<int>(), dn.as<int>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(wlen, dn.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        const int *dc = s.in(cum, nbt), *dl = s.in(len, (size_t)B);
+        const float* dratio = s.in(ratio, nbt);
+        long long* dq = s.scratch<long long>(nbt);
+        int *dw = s.scratch<int>(nbt), *dn = s.scratch<int>((size_t)B);
+        float* dy = s.in<float>(y, y_floats);  // everything: a stray write shows
+        unsigned* dp = s.filled<unsigned>((size_t)B, 0);
+        launch_pitch_plan(dc, dl, dratio, B, T, hop, dq, dw, dn, nullptr);
+        s.finish();
+        s.fetch(wlen, dn, (size_t)B);
         for (int b = 0; b < B; ++b)
             if (wlen[b] < 1 || wlen[b] == 0x7fffffff || wlen[b] > y_ld) throw EngineError(MI355VITS_ERR_INVALID, "row " + std::to_string(b) + ": the warped row of " + std::to_string(wlen[b]) + " samples does not fit y_ld");
         std::vector<int64_t> w64(wlen, wlen + B);
         std::vector<int> tab(pitch_tab_ints(B));
         const long items = pitch_fill_tab(w64.data(), B, tab.data());
-        DevBuf dt(tab.size() * 4);
-        HIP_CHECK(hipMemcpy(dt.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-        launch_pitch(dx.as<float>(), (long)x_bs, da.as<int>(), dc.as<int>(), dl.as<int>(), dratio, dq.as<long long>(), dw.as<int>(), dt.as<int>(),
-                     items, dh.as<float>(), B, T, hop, dy.as<float>(), (long)y_bs, y_ld, dp.as<unsigned>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(y, dy.p, y_floats * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(peaks, dp.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        launch_pitch(s.in(x, x_floats), (long)x_bs, s.in(alen), dc, dl, dratio, dq, dw, s.in(tab), items, s.in(pitch_table()), B, T, hop, dy, (long)y_bs,
+                     y_ld, dp, nullptr);
+        s.finish();
+        s.fetch(y, dy, y_floats);
+        s.fetch(peaks, dp, (size_t)B);
     });
 }
 
@@ -1333,21 +1073,11 @@ int mi355vits_test_expand_prior(int device, int B, int I, int Tx, int Ty, const 
             for (int j = 0; j < Tx; ++j)
                 if (cum[(size_t)b * Tx + j] < (j ? cum[(size_t)b * Tx + j - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
         }
-        HIP_CHECK(hipSetDevice(device));
-        const size_t ns = (size_t)B * 2 * I * Tx, nc = (size_t)B * Tx, ni = injected ? (size_t)B * I * injected_frames : 0, nz = (size_t)B * I * Ty;
-        DevBuf dst(ns * 4), dc(nc * 4), dy((size_t)B * 4), di(ni * 4), ds((size_t)B * 3 * 4), dz(nz * 4), du((size_t)B * 8);
-        HIP_CHECK(hipMemcpy(dst.p, stats, ns * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dc.p, cum, nc * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
-        if (ni) HIP_CHECK(hipMemcpy(di.p, injected, ni * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(du.p, 0, (size_t)B * 8));
-        launch_expand_prior(dst.as<float>(), dc.as<int>(), dy.as<int>(), injected ? di.as<float>() : nullptr, injected_frames, B, I, Tx, Ty,
-                            ds.as<float>(), 0ull, du.as<unsigned long long>(), dz.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        const size_t ni = injected ? (size_t)B * I * injected_frames : 0;
+        launch_expand_prior(s.in(stats, (size_t)B * 2 * I * Tx), s.in(cum, (size_t)B * Tx), s.in(ylen, (size_t)B), s.in(injected, ni), injected_frames, B, I,
+                            Tx, Ty, s.in(scales, (size_t)B * 3), 0ull, s.filled<unsigned long long>((size_t)B, 0), s.inout(z, (size_t)B * I * Ty), nullptr);
+        s.finish();
     });
 }
 
@@ -1362,20 +1092,11 @@ int mi355vits_test_expand_prior_keyed(int device, int B, int I, int Tx, int Ty, 
             for (int j = 0; j < Tx; ++j)
                 if (cum[(size_t)b * Tx + j] < (j ? cum[(size_t)b * Tx + j - 1] : 0)) throw EngineError(MI355VITS_ERR_INVALID, "cum must be non-negative and non-decreasing");
         }
-        HIP_CHECK(hipSetDevice(device));
-        const size_t ns = (size_t)B * 2 * I * Tx, nc = (size_t)B * Tx, nz = (size_t)B * I * Ty;
-        DevBuf dst(ns * 4), dc(nc * 4), dy((size_t)B * 4), ds((size_t)B * 3 * 4), dz(nz * 4), du((size_t)B * 8);
-        HIP_CHECK(hipMemcpy(dst.p, stats, ns * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dc.p, cum, nc * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, ylen, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(du.p, utt, (size_t)B * 8, hipMemcpyHostToDevice));
-        launch_expand_prior(dst.as<float>(), dc.as<int>(), dy.as<int>(), nullptr, 0, B, I, Tx, Ty, ds.as<float>(), (unsigned long long)seed,
-                            du.as<unsigned long long>(), dz.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        launch_expand_prior(s.in(stats, (size_t)B * 2 * I * Tx), s.in(cum, (size_t)B * Tx), s.in(ylen, (size_t)B), nullptr, 0, B, I, Tx, Ty,
+                            s.in(scales, (size_t)B * 3), (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(s.in(utt, (size_t)B)),
+                            s.inout(z, (size_t)B * I * Ty), nullptr);
+        s.finish();
     });
 }
 
@@ -1383,16 +1104,10 @@ int mi355vits_test_sdp_noise(int device, int B, int T, uint64_t seed, const uint
     return guarded(nullptr, [&] {
         if (!utt || !scales || !z) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || T < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nz = (size_t)B * 2 * T;
-        DevBuf dz(nz * 4), ds((size_t)B * 3 * 4), du((size_t)B * 8);
-        HIP_CHECK(hipMemcpy(dz.p, z, nz * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(ds.p, scales, (size_t)B * 3 * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(du.p, utt, (size_t)B * 8, hipMemcpyHostToDevice));
-        launch_sdp_noise(dz.as<float>(), nullptr, B, T, ds.as<float>(), (unsigned long long)seed, du.as<unsigned long long>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(z, dz.p, nz * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        launch_sdp_noise(s.inout(z, (size_t)B * 2 * T), nullptr, B, T, s.in(scales, (size_t)B * 3), (unsigned long long)seed,
+                         reinterpret_cast<const unsigned long long*>(s.in(utt, (size_t)B)), nullptr);
+        s.finish();
     });
 }
 
@@ -1402,17 +1117,10 @@ int mi355vits_test_embed(int device, int B, int T, int H, int num_symbols, const
         if (!ids || !len || !emb || !y) throw EngineError(MI355VITS_ERR_INVALID, "null argument");
         if (B < 1 || T < 1 || H < 1 || num_symbols < 1) throw EngineError(MI355VITS_ERR_INVALID, "bad shape");
         check_lens(len, B, T, "len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t ni = (size_t)B * T, ne = (size_t)num_symbols * H, ny = (size_t)B * H * T;
-        DevBuf di(ni * 8), dl((size_t)B * 4), de(ne * 4), dy(ny * 4);
-        HIP_CHECK(hipMemcpy(di.p, ids, ni * 8, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, len, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(de.p, emb, ne * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));
-        launch_embed(di.as<long long>(), dl.as<int>(), de.as<float>(), B, T, H, num_symbols, scale, dy.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        HookScope s(device);
+        launch_embed(reinterpret_cast<const long long*>(s.in(ids, (size_t)B * T)), s.in(len, (size_t)B), s.in(emb, (size_t)num_symbols * H), B, T, H,
+                     num_symbols, scale, s.inout(y, (size_t)B * H * T), nullptr);
+        s.finish();
     });
 }
 
@@ -1429,23 +1137,17 @@ int mi355vits_test_layernorm(int device, const mi355vits_layernorm_test* t) {
             throw EngineError(MI355VITS_ERR_INVALID, "alias: 0 none, 1 y == x, 2 y == res, 3 y == add_to (the aliased input must be given)");
         check_lens(t->premask_len, B, T, "premask_len out of range");
         check_lens(t->out_len, B, T, "out_len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        const size_t nx = (size_t)(NP - 1) * stride + n;
-        DevBuf dx(nx * 4), dy(n * 4), dres(n * 4), dadd(n * 4), db((size_t)C * 4), dg((size_t)C * 4), dbe((size_t)C * 4), dpl((size_t)B * 4), dol((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dx.p, t->x, nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, t->y, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dg.p, t->gamma, (size_t)C * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dbe.p, t->beta, (size_t)C * 4, hipMemcpyHostToDevice));
+        HookScope s(device);
         LNArgs a;
-        a.x = dx.as<float>(); a.gamma = dg.as<float>(); a.beta = dbe.as<float>();
+        float* dx = s.in(t->x, (size_t)(NP - 1) * stride + n);
+        float *dres = s.in(t->res, n), *dadd = s.in(t->add_to, n);
+        a.x = dx; a.res = dres; a.add_to = dadd;
+        a.gamma = s.in(t->gamma, (size_t)C); a.beta = s.in(t->beta, (size_t)C); a.bias = s.in(t->bias, (size_t)C);
+        a.premask_len = s.in(t->premask_len, (size_t)B); a.out_len = s.in(t->out_len, (size_t)B);
         a.B = B; a.C = C; a.T = T; a.gelu = t->gelu ? 1 : 0; a.eps = t->eps;
         a.nparts = NP; a.part_stride = (long)stride;
-        if (t->res) { HIP_CHECK(hipMemcpy(dres.p, t->res, n * 4, hipMemcpyHostToDevice)); a.res = dres.as<float>(); }
-        if (t->add_to) { HIP_CHECK(hipMemcpy(dadd.p, t->add_to, n * 4, hipMemcpyHostToDevice)); a.add_to = dadd.as<float>(); }
-        if (t->bias) { HIP_CHECK(hipMemcpy(db.p, t->bias, (size_t)C * 4, hipMemcpyHostToDevice)); a.bias = db.as<float>(); }
-        if (t->premask_len) { HIP_CHECK(hipMemcpy(dpl.p, t->premask_len, (size_t)B * 4, hipMemcpyHostToDevice)); a.premask_len = dpl.as<int>(); }
-        if (t->out_len) { HIP_CHECK(hipMemcpy(dol.p, t->out_len, (size_t)B * 4, hipMemcpyHostToDevice)); a.out_len = dol.as<int>(); }
-        a.y = t->alias == 1 ? dx.as<float>() : t->alias == 2 ? dres.as<float>() : t->alias == 3 ? dadd.as<float>() : dy.as<float>();
+        // an aliased output is the input's own device pointer, taken once; the caller's y goes up only where it is a buffer of its own
+        a.y = t->alias == 1 ? dx : t->alias == 2 ? dres : t->alias == 3 ? dadd : s.in<float>(t->y, n);
         try {
             launch_layernorm(a, nullptr);
         } catch (const EngineError&) {
@@ -1454,9 +1156,8 @@ int mi355vits_test_layernorm(int device, const mi355vits_layernorm_test* t) {
             if (std::string(e.what()).rfind("layernorm:", 0) == 0) throw EngineError(MI355VITS_ERR_INVALID, e.what());
             throw;
         }
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->y, a.y, n * 4, hipMemcpyDeviceToHost));
+        s.finish();
+        s.fetch(t->y, a.y, n);
     });
 }
 
@@ -1480,40 +1181,24 @@ int mi355vits_test_dp_det(int device, const mi355vits_dp_det_test* t) {
         if (t->math != MATH_F32 && t->math != MATH_BF16X3) throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 or MATH_BF16X3");
         if ((size_t)B * H * T >= 0x7fffffffull / 4) throw EngineError(MI355VITS_ERR_INVALID, "tensor too large for the hook");
         check_lens(t->len, B, T, "len out of range");
-        HIP_CHECK(hipSetDevice(device));
-        std::vector<std::unique_ptr<DevBuf>> keep;
-        auto upload = [&](const void* p, size_t bytes) -> const float* {
-            keep.emplace_back(new DevBuf(bytes));
-            HIP_CHECK(hipMemcpy(keep.back()->p, p, bytes, hipMemcpyHostToDevice));
-            return keep.back()->as<float>();
-        };
-        // a conv's weights [Cout, Cin, K] as Engine::add_conv_data stages them for the mode (ConvW::packed / packed_b3s)
+        HookScope s(device);
+        // a conv's weights [Cout, Cin, K] in the form the mode reads (ConvW::packed / packed_b3s)
         auto conv_w = [&](const float* w, int Cout, int Cin) -> const float* {
-            if (t->math == MATH_F32) {
-                std::vector<float> p(mfma_packed_floats(Cout, Cin, K), 0.0f);
-                pack_conv_weights_mfma_mode(w, Cout, Cin, K, EPI_STD, p.data());
-                return upload(p.data(), p.size() * 4);
-            }
-            std::vector<uint32_t> p(bf16x3_packed_words_mode(Cout, Cin, K, EPI_STD), 0u);
-            pack_conv_weights_bf16x3_mode(w, Cout, Cin, K, EPI_STD, 1, p.data());
-            return upload(p.data(), p.size() * 4);
+            if (t->math == MATH_F32) return s.in(conv_weights_mfma(w, Cout, Cin, K));
+            return in_words(s, conv_weights_bf16x3_staged(w, Cout, Cin, K));
         };
         DpDetArgs a;
-        a.x = upload(t->x, (size_t)B * H * T * 4);
-        if (t->cond) { a.cond = upload(t->cond, (size_t)B * H * 4); a.cond_bs = H; }
-        a.w1 = conv_w(t->w1, F, H); a.b1 = upload(t->b1, (size_t)F * 4); a.g1 = upload(t->g1, (size_t)F * 4); a.be1 = upload(t->be1, (size_t)F * 4);
-        a.w2 = conv_w(t->w2, F, F); a.b2 = upload(t->b2, (size_t)F * 4); a.g2 = upload(t->g2, (size_t)F * 4); a.be2 = upload(t->be2, (size_t)F * 4);
-        a.pw = upload(t->proj_w, (size_t)F * 4);
-        a.pb = upload(t->proj_b, 4);
-        a.len = reinterpret_cast<const int*>(upload(t->len, (size_t)B * 4));
-        DevBuf dout((size_t)B * T * 4);
-        HIP_CHECK(hipMemcpy(dout.p, t->logw, (size_t)B * T * 4, hipMemcpyHostToDevice));
-        a.out = dout.as<float>(); a.out_bs = T;
+        a.x = s.in(t->x, (size_t)B * H * T);
+        if (t->cond) { a.cond = s.in(t->cond, (size_t)B * H); a.cond_bs = H; }
+        a.w1 = conv_w(t->w1, F, H); a.b1 = s.in(t->b1, (size_t)F); a.g1 = s.in(t->g1, (size_t)F); a.be1 = s.in(t->be1, (size_t)F);
+        a.w2 = conv_w(t->w2, F, F); a.b2 = s.in(t->b2, (size_t)F); a.g2 = s.in(t->g2, (size_t)F); a.be2 = s.in(t->be2, (size_t)F);
+        a.pw = s.in(t->proj_w, (size_t)F);
+        a.pb = s.in(t->proj_b, 1);
+        a.len = s.in(t->len, (size_t)B);
+        a.out = s.inout(t->logw, (size_t)B * T); a.out_bs = T;
         a.B = B; a.T = T; a.H = H; a.F = F; a.K = K; a.math = t->math;
         launch_dp_det(a, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->logw, dout.p, (size_t)B * T * 4, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -1555,60 +1240,36 @@ int mi355vits_test_mrf_stage(int device, const mi355vits_mrf_test* t) {
         for (int j = 0; j < nrb; ++j)
             for (int q = 0; q < 2; ++q)
                 if (!t->w[j][q] || !t->bias[j][q]) throw EngineError(MI355VITS_ERR_INVALID, "null weight or bias");
-        for (int b = 0; b < B; ++b)
-            if (t->len[b] < 0 || t->len[b] > T) throw EngineError(MI355VITS_ERR_INVALID, "len out of range");
+        check_lens(t->len, B, T, "len out of range");
         if (t->impl < 0 || t->impl > 2) throw EngineError(MI355VITS_ERR_INVALID, "impl must be 0, 1 or 2");
         if (t->impl == 0 ? (t->math != MATH_F32 && t->math != MATH_BF16X3) : t->math != MATH_BF16X3)
             throw EngineError(MI355VITS_ERR_INVALID, "math mode: MATH_F32 or MATH_BF16X3 for impl 0, MATH_BF16X3 for impl 1 and 2");
         MrfPlan plan;
         if (!mrf_test_plan(t->impl, C, nrb, t->k, t->d1, t->d2, &plan)) throw EngineError(MI355VITS_ERR_INVALID, "stage not supported by the chosen kernel");
         if (t->impl == 2 && (t->seg < plan.width || t->seg % plan.width != 0)) throw EngineError(MI355VITS_ERR_INVALID, "seg must be a positive multiple of the sweep's step");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const size_t n = (size_t)B * C * T;
-        DevBuf dx(n * 4), dy(n * 4), dl((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dx.p, t->x, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dy.p, t->y, n * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, t->len, (size_t)B * 4, hipMemcpyHostToDevice));
-        std::vector<int> len_host(t->len, t->len + B);
-        std::vector<std::unique_ptr<DevBuf>> keep;
-        auto upload = [&](const void* p, size_t bytes) {
-            keep.emplace_back(new DevBuf(bytes));
-            HIP_CHECK(hipMemcpy(keep.back()->p, p, bytes, hipMemcpyHostToDevice));
-            return keep.back()->as<float>();
-        };
         MrfArgs m;
-        m.x = dx.as<float>(); m.x_bs = (long)C * T; m.x_ld = T;
-        m.y = dy.as<float>(); m.y_bs = (long)C * T; m.y_ld = T;
-        m.len = dl.as<int>(); m.len_host = len_host.data(); m.B = B; m.C = C; m.T = T;
+        m.x = s.in(t->x, n); m.x_bs = (long)C * T; m.x_ld = T;
+        m.y = s.inout(t->y, n); m.y_bs = (long)C * T; m.y_ld = T;
+        m.len = s.in(t->len, (size_t)B); m.len_host = t->len; m.B = B; m.C = C; m.T = T;
         m.nrb = nrb; m.math = t->math; m.out_scale = t->out_scale;
         for (int j = 0; j < nrb; ++j) {
             const int k = t->k[j];
             m.k[j] = k; m.d1[j] = t->d1[j]; m.d2[j] = t->d2[j];
             for (int q = 0; q < 2; ++q) {
                 const float* w = t->w[j][q];
-                if (t->impl != 0) {  // Engine::add_conv_data's packed_p
-                    std::vector<uint32_t> pp(p16_packed_words(C, C, k));
-                    pack_conv_weights_p16(w, C, C, k, pp.data());
-                    m.w[j][q] = upload(pp.data(), pp.size() * 4);
-                } else if (t->math == MATH_BF16X3) {  // packed_b3
-                    std::vector<uint32_t> b3(bf16x3_packed_words(C, C, k));
-                    pack_conv_weights_bf16x3(w, C, C, k, b3.data());
-                    m.w[j][q] = upload(b3.data(), b3.size() * 4);
-                } else {  // packed4
-                    std::vector<float> pk(mfma_packed_floats(C, C, k), 0.0f), p4(pk.size());
-                    pack_conv_weights_mfma_mode(w, C, C, k, EPI_STD, pk.data());
-                    regroup_packed_x4(pk.data(), pk.size(), p4.data());
-                    m.w[j][q] = upload(p4.data(), p4.size() * 4);
-                }
-                m.bias[j][q] = upload(t->bias[j][q], (size_t)C * 4);
+                // ConvW::packed_p for the register kernels, packed_b3 / packed4 for the fused stage
+                m.w[j][q] = t->impl != 0               ? in_words(s, conv_weights_p16(w, C, C, k))
+                            : t->math == MATH_BF16X3 ? in_words(s, conv_weights_bf16x3(w, C, C, k))
+                                                     : s.in(conv_weights_mfma_x4(conv_weights_mfma(w, C, C, k)));
+                m.bias[j][q] = s.in(t->bias[j][q], (size_t)C);
             }
         }
         if (t->impl == 0) launch_mrf_fused(m, nullptr);
         else if (t->impl == 1) launch_mrf_p(m, nullptr);
         else { m.seg = t->seg; launch_mrf_s(m, nullptr); }
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(t->y, dy.p, n * 4, hipMemcpyDeviceToHost));
+        s.finish();
     });
 }
 
@@ -1627,115 +1288,81 @@ int mi355vits_lab_mrf_plan(int impl, int C, int nrb, const int32_t* k, const int
 int mi355vits_bench_conv1d(int device, int B, int Cin, int Cout, int T, int K, int dilation, int epi, int reps,
                            float* ms_per_launch) {
     return guarded(nullptr, [&] {
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         if (!conv1d_mfma_supported(Cin, Cout, K, dilation) || reps < 1 || !ms_per_launch) throw EngineError(MI355VITS_ERR_INVALID, "bad arguments");
         const int H = Cout / 2;
         const size_t nx = (size_t)B * Cin * T, ny = (size_t)B * Cout * T, nw = (size_t)Cout * Cin * K;
-        std::vector<float> hx(nx), hw(nw), pk(mfma_packed_floats(Cout, Cin, K));
+        std::vector<float> hx(nx), hw(nw);
         unsigned st = 12345u;
         auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xFFFF) / 32768.0f - 1.0f; };
         for (auto& v : hx) v = rnd();
         for (auto& v : hw) v = rnd() * 0.05f;
-        pack_conv_weights_mfma_mode(hw.data(), Cout, Cin, K, epi == 1 ? EPI_GATE : EPI_STD, pk.data());
-        DevBuf dx(nx * 4), dy(ny * 4), dy2(ny * 4), dres(ny * 4), dp(pk.size() * 4), db(Cout * 4);
-        HIP_CHECK(hipMemcpy(dx.p, hx.data(), nx * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dp.p, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(dy.p, 0, ny * 4));
-        HIP_CHECK(hipMemset(dy2.p, 0, ny * 4));
-        HIP_CHECK(hipMemset(dres.p, 0, ny * 4));
-        HIP_CHECK(hipMemset(db.p, 0, Cout * 4));
         ConvArgs a;
-        a.x = dx.as<float>(); a.x_bs = (long)Cin * T; a.x_ld = T;
-        a.w = dp.as<float>(); a.bias = db.as<float>();
+        a.x = s.in(hx); a.x_bs = (long)Cin * T; a.x_ld = T;
+        a.w = s.in(conv_weights_mfma(hw.data(), Cout, Cin, K, epi == 1 ? EPI_GATE : EPI_STD));
+        a.bias = s.filled<float>((size_t)Cout, 0);
         a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.K = K; a.dil = dilation; a.pad = (K * dilation - dilation) / 2;
+        a.y = s.filled<float>(ny, 0); a.y_ld = T;
         if (epi == 1) {
             a.epi = EPI_GATE; a.H = H;
-            a.y = dy.as<float>(); a.y_bs = (long)H * T; a.y_ld = T;
+            a.y_bs = (long)H * T;
         } else if (epi == 2) {
-            a.epi = EPI_RESSKIP; a.H = Cout / 2;
-            a.y = dy.as<float>(); a.y_bs = (long)a.H * T; a.y_ld = T;
-            a.y2 = dy2.as<float>(); a.y2_bs = (long)a.H * T; a.y2_ld = T;
+            a.epi = EPI_RESSKIP; a.H = H;
+            a.y_bs = (long)H * T;
+            a.y2 = s.filled<float>(ny, 0); a.y2_bs = (long)H * T; a.y2_ld = T;
         } else {
-            a.y = dy.as<float>(); a.y_bs = (long)Cout * T; a.y_ld = T;
-            a.res = dres.as<float>(); a.res_bs = a.y_bs; a.res_ld = T;
+            a.y_bs = (long)Cout * T;
+            a.res = s.filled<float>(ny, 0); a.res_bs = a.y_bs; a.res_ld = T;
             a.in_slope = 0.1f;
         }
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
         for (int i = 0; i < 3; ++i) launch_conv1d_mfma(a, nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < reps; ++i) launch_conv1d_mfma(a, nullptr);
-        HIP_CHECK(hipEventRecord(e1, nullptr));
-        HIP_CHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        *ms_per_launch = ms / reps;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        HIP_CHECK(hipDeviceSynchronize());  // the timed launches start on an idle device
+        *ms_per_launch = (float)timed([&] { launch_conv1d_mfma(a, nullptr); }, 0, reps);
     });
 }
 
 int mi355vits_probe_device(int device, double out[8]) {
     return guarded(nullptr, [&] {
         if (!out) throw EngineError(MI355VITS_ERR_INVALID, "bad arguments");
-        HIP_CHECK(hipSetDevice(device));
+        HookScope s(device);
         const int cus = current_device_cu_count();
-        struct Ev {  // RAII: a HIP error below must not leak the events
-            hipEvent_t e = nullptr;
-            Ev() { HIP_CHECK(hipEventCreate(&e)); }
-            ~Ev() { if (e) (void)hipEventDestroy(e); }
-        } ev0, ev1;
-        hipEvent_t e0 = ev0.e, e1 = ev1.e;
-        auto timed = [&](auto&& launch, int warm, int reps) {
-            for (int i = 0; i < warm; ++i) launch();
-            HIP_CHECK(hipEventRecord(e0, nullptr));
-            for (int i = 0; i < reps; ++i) launch();
-            HIP_CHECK(hipEventRecord(e1, nullptr));
-            HIP_CHECK(hipEventSynchronize(e1));
-            float ms = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            return (double)ms / reps;
-        };
         // one zero-filled GiB serves everything: [0, 2.6 MB) the L2 table, [0, 24 MB) the big table, the halves as copy source / destination
         const size_t gib = (size_t)1 << 30;
-        DevBuf mem(gib), sink((size_t)cus * 4 + 16);
-        HIP_CHECK(hipMemset(mem.p, 0, gib));
+        char* base = s.filled<char>(gib, 0);
+        unsigned* sink = s.scratch<unsigned>((size_t)cus + 4);
         const int n16 = 256 * 8 * 80;  // 163,840 x 16 B = 2.62 MB
         const int reps_in = 8;
-        const double ms_stream = timed([&] { launch_probe_l2_stream(mem.p, n16, reps_in, sink.as<unsigned>(), cus, nullptr); }, 1, 3);
+        const double ms_stream = timed([&] { launch_probe_l2_stream(base, n16, reps_in, sink, cus, nullptr); }, 1, 3);
         out[0] = (double)cus * reps_in * n16 * 16.0 / (ms_stream * 1e-3) / 1e9;
         const int steps = 2000;
         auto chase = [&](unsigned nlines, int warm) {
-            const double ms = timed([&] { launch_probe_l2_latency(mem.as<unsigned>(), steps, nlines, sink.as<unsigned>(), cus, nullptr); }, warm, 2);
+            const double ms = timed([&] { launch_probe_l2_latency(reinterpret_cast<unsigned*>(base), steps, nlines, sink, cus, nullptr); }, warm, 2);
             return ms * 1e6 / steps;
         };
         out[1] = chase(1u << 15, 2);   // 2 MB: after two passes every XCD's L2 holds what its waves touch
         out[6] = chase(1u << 19, 2);   // 32 MB: past an L2, inside the memory-side cache
         out[7] = chase(1u << 24, 1);   // 1 GiB: HBM (and the TLB's reach)
         const long ncopy16 = (256L << 20) / 16;
-        char* base = static_cast<char*>(mem.p);
         const double ms_copy = timed([&] { launch_probe_copy(base, base + gib / 2, ncopy16, cus * 16, nullptr); }, 1, 3);
         out[2] = 2.0 * ncopy16 * 16.0 / (ms_copy * 1e-3) / 1e9;
         out[3] = (double)cus;
         const long slice16 = ncopy16 / cus;
-        const double ms_mixed = timed([&] { launch_probe_l2_mixed(mem.p, n16, reps_in, base + gib / 4, base + gib / 2, slice16, sink.as<unsigned>(), cus, nullptr); }, 1, 3);
+        const double ms_mixed = timed([&] { launch_probe_l2_mixed(base, n16, reps_in, base + gib / 4, base + gib / 2, slice16, sink, cus, nullptr); }, 1, 3);
         out[4] = (double)cus * reps_in * n16 * 16.0 / (ms_mixed * 1e-3) / 1e9;
         const int big16 = n16 * 9;
-        const double ms_big = timed([&] { launch_probe_l2_stream(mem.p, big16, 1, sink.as<unsigned>(), cus, nullptr); }, 1, 3);
+        const double ms_big = timed([&] { launch_probe_l2_stream(base, big16, 1, sink, cus, nullptr); }, 1, 3);
         out[5] = (double)cus * big16 * 16.0 / (ms_big * 1e-3) / 1e9;
     });
 }
 
 int mi355vits_test_mfma_layout(int device, float* err) {
     return guarded(nullptr, [&] {
-        HIP_CHECK(hipSetDevice(device));
-        DevBuf d((1024 + 256 + 256) * 4);
-        launch_mfma_selftest(d.as<float>(), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
+        HookScope s(device);
+        float* d = s.scratch<float>(1024 + 256 + 256);
+        launch_mfma_selftest(d, nullptr);
+        s.finish();
         std::vector<float> h(1536);
-        HIP_CHECK(hipMemcpy(h.data(), d.p, 1536 * 4, hipMemcpyDeviceToHost));
+        s.fetch(h.data(), d, h.size());
         float worst = 0.0f;
         for (int i = 0; i < 32; ++i)
             for (int j = 0; j < 32; ++j) {
